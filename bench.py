@@ -2,7 +2,7 @@
 """bench.py -- parties/s of one n-party PVW `encrypt` on MI355X, with the roofline of the
 dominant kernel (mac_rows) and the CPU restatement timed beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c1|c4shard]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c1|c4shard] [--dump-outputs DIR]
 
 A "step" is one full encrypt (sample r/e1/e2 from a seed, NTT, c1 = A r + e1,
 c2 = B r + e2 + m g; src/crypto/encryption.rs:105-214) over synthetic A-hat / B-hat that are
@@ -73,6 +73,49 @@ def measured_traffic(config, kernel_prefix):
     return best
 
 
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: every file of every rank together
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(directory, outputs, rank, world):
+    """--dump-outputs: what the timed path's last step handed its caller, as DIR/<name>.npy (DIR/<name>_rank<r>.npy at
+    N > 1).  `outputs` maps a name to (rows, words_per_row, fetch), fetch(indices) returning those rows (axis 0) as a
+    64-bit integer array.  The words are residues mod 61-bit primes or decoded u64 values, which float64 cannot hold
+    whole, so each one is written as the pair (high 32 bits, low 32 bits) on a trailing axis of 2: exact in float64,
+    comparable bit for bit.  DUMP_LIMIT_BYTES is shared out smallest array first; one larger than its share keeps a
+    fixed, seeded sample of its rows, and DIR/<name>_rows.npy (float64) lists which.  Returns the summary for the
+    JSON line."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    left = DUMP_LIMIT_BYTES // world - 2 * 256 * len(outputs)        # minus the .npy headers
+    order = sorted(outputs, key=lambda name: outputs[name][0] * outputs[name][1])
+    summary = {}
+    for i, name in enumerate(order):
+        rows, words, fetch = outputs[name]
+        share = left // (len(order) - i)
+        if rows * 16 * words <= share:
+            idx = np.arange(rows)
+            left -= rows * 16 * words
+        else:
+            keep = max(1, share // (16 * words + 8))                    # every row with its index
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, size=keep, replace=False))
+            np.save(os.path.join(directory, f"{name}{suffix}_rows.npy"), idx.astype(np.float64))
+            left -= keep * (16 * words + 8)
+        u = np.ascontiguousarray(fetch(idx)).view(np.uint64)
+        exact = np.stack([(u >> np.uint64(32)).astype(np.float64), (u & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1)
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), exact)
+        summary[name + suffix] = {"rows": rows, "rows_written": len(idx), "shape": list(exact.shape)}
+    return {"dir": directory, "arrays": summary,
+            "encoding": "float64 (high 32 bits, low 32 bits) of every 64-bit word on the last axis"}
+
+
+def device_rows(t):
+    """(rows, words_per_row, fetch) of a device tensor for dump_outputs: only the rows asked for leave the GPU"""
+    import torch
+    return t.shape[0], t[0].numel(), lambda idx: t[torch.as_tensor(idx, device=t.device)].cpu().numpy()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -96,7 +139,12 @@ def main():
                     help="run on libpvw_hip_tuning.so (the measurement build: honours the PVW_* schedule selectors of DESIGN 7a)")
     ap.add_argument("--sustain-seconds", type=float, default=2.0,
                     help="length of the back-to-back leg reported as `sustained` (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (float64, at most "
+                         "64 MB in all; a fixed, seeded sample of the rows when the outputs are larger)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     self_launch(args)
 
     import numpy as np
@@ -218,6 +266,12 @@ def main():
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
     value = n_total * max(Dm, 1) * args.steps / elapsed
+    # the ciphertext this rank's step returns (NTT form): c1 rows [clo, chi) and c2 rows of this rank's parties;
+    # with dealers, one row per (dealer, row)
+    dumped = None
+    if args.dump_outputs:
+        res = {"c1": c1m.view(-1, L, l), "c2": c2m.view(-1, L, l)} if Dm > 0 else {"c1": c1, "c2": c2}
+        dumped = dump_outputs(args.dump_outputs, {name: device_rows(t) for name, t in res.items()}, rank, world)
 
     # ---- roofline of the dominant kernel: HIP events around every mac_rows launch --------------
     params.set_profiling(True)
@@ -268,6 +322,8 @@ def main():
                      "launches_timed": mac_launches},
         "kernel_ms_per_step": {name: (v[0] / max(args.steps, 1)) for name, v in kt.items()},
     }
+    if dumped:
+        out["dumped_outputs"] = dumped
     # ---- sustained leg: >= --sustain-seconds of back-to-back steps (clocks and thermals settle; the driver's
     # gpu_busy sampler sees the GPU), then a profiled stretch of the same loop while the chip is still hot ----
     if args.sustain_seconds > 0:
@@ -430,7 +486,7 @@ def bench_keygen(args, world, rank, local_rank, dev):
     """Batched key generation b_i = s_i*A + e_i (public_key.rs:111-147, crs.rs:138-171) for the parties
     of this rank: batches of 16 parties, up to 128 per launch, against the transposed CRS on the matrix cores (gemm_digits)."""
     import numpy as np
-    import torch  # noqa: F401
+    import torch
 
     import pvw_rs_amd as P
     from pvw_rs_amd import _ffi
@@ -451,16 +507,28 @@ def bench_keygen(args, world, rank, local_rank, dev):
     def step():
         P.api._check(lib.pvw_keygen(h, lo, hi, sk.ctypes.data_as(C.c_void_p), None, seed.ctypes.data_as(C.c_void_p)))
 
-    steps = max(1, min(args.steps, 5))
-    step()
+    steps = args.steps
+    for _ in range(args.warmup):
+        step()
+    torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
         step()
+    torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs:
+        # this rank's rows of B-hat (NTT form), left on the device by the last step; only the rows dumped are read back
+        def b_rows(idx):
+            rows = np.zeros((len(idx), k, L, l), dtype=np.uint64)
+            for j, i in enumerate(idx):
+                P.api._check(lib.pvw_get_pk(h, lo + int(i), lo + int(i) + 1, rows[j].ctypes.data_as(C.c_void_p), P.REPR_NTT))
+            return rows
+        dumped = dump_outputs(args.dump_outputs, {"b_hat": (hi - lo, k * L * l, b_rows)}, rank, world)
     macs = L * l * n_per * k * k
     out = {
         "metric": "party public keys/s for batched PublicKey::generate (b_i = s_i*A + e_i), host sk in, B-hat resident out",
-        "value": n_per * world * steps / elapsed, "unit": "keys/s", "n_gpus": world, "steps": steps, "warmup": 1,
+        "value": n_per * world * steps / elapsed, "unit": "keys/s", "n_gpus": world, "steps": steps, "warmup": args.warmup,
         "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "u64", "data": "synthetic",
         "config": {"workload": "key generation at " + desc, "parties_per_gpu": n_per, "k": k, "l": l, "rns_limbs": L},
@@ -470,6 +538,8 @@ def bench_keygen(args, world, rank, local_rank, dev):
                      "modular_macs_per_s": macs / (elapsed / steps),
                      "note": "whole pvw_keygen call incl. H2D of the secret keys, prologues and re-tiling of B-hat"},
     }
+    if dumped:
+        out["dumped_outputs"] = dumped
     if rank == 0:
         print(json.dumps(out))
 
@@ -561,6 +631,12 @@ def bench_decrypt(args, world, rank, local_rank, dev):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # what pvw_decrypt_batch_device returns: the noisy polynomials (power basis) and the decoded values, taken before the
+    # worst-case leg below overwrites them
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, {"noisy": device_rows(noisy), "values": device_rows(vals_dev)}, rank, world)
+
     def kernel_times(which):
         params.set_profiling(True)
         params.reset_profiling()
@@ -622,6 +698,8 @@ def bench_decrypt(args, world, rank, local_rank, dev):
                                   "note": "the same decode with host big integers (pvw_decode_host), outside the timed region",
                                   "matches_device": bool([int(x) for x in vals] == [int(x) for x in vals_dev.cpu().numpy().view(np.uint64)])},
     }
+    if dumped:
+        out["dumped_outputs"] = dumped
     if rank == 0:
         print(json.dumps(out))
     if DIST_ON:
