@@ -257,6 +257,27 @@ PVW_API int32_t pvw_sk_free(pvw_sk* key);
 PVW_API int32_t pvw_decrypt_batch_device_sk(pvw_ctx* ctx, const pvw_sk* key, const uint64_t* d_c1s,
                                             const uint64_t* d_c2col, size_t num_dealers, uint32_t in_repr,
                                             uint64_t* d_noisy, uint64_t* d_out, void* stream);
+/* ---- decrypt for every party: the loop over decrypt_party_shares (decryption.rs:281-325) that examples/pvw.rs:138-149 runs
+ * for all parties and checks as results[recipient][dealer] (:157-170), as tests/crypto.rs:284-287 does; over a subset of
+ * dealers (the "valid" ciphertexts) it is examples/pvw_valid_dec.rs:201-209.  Every party of [party_lo, party_hi) decrypts
+ * its share of each of D dealer ciphertexts:
+ *   out[p][d] = decode_scalar_pvw_rns( sum_j NTT(sk[p][j]) * c1s[d][j] - c2s[d][party_lo + p] )   (decryption.rs:257-274, :10-58)
+ * sk [P][k][l] (P = party_hi - party_lo); c1s [D][k][L][l]; c2s [D][n][L][l] (whole ciphertexts, global party rows: the call
+ * reads rows [party_lo, party_hi) of each and no other); out_u64 [P][D].  out[p][d] is the word pvw_decrypt_batch returns for
+ * party p's key and column on the same input words, whatever they are.  Any D >= 1; in_repr POWER or NTT (POWER input is
+ * transformed in scratch: the caller's buffers are only read).  Argument errors (InvalidParameters for NULL, D = 0, an empty
+ * range or party_hi > n; InvalidFormat for in_repr) come before any device work.  The parties' s-hat rows and the dealers'
+ * c1 meet in one digit GEMM on the matrix cores; fewer than 22 parties run the per-party kernels party by party.
+ * Device scratch stays below about 4.5 GiB whatever P and D (dealers in groups of <= 128, parties in chunks); every
+ * region derived from the keys (coefficients, tiled s-hat, GEMM intermediate, noisy polynomials) is cleared before the
+ * call's work completes (pvw_selftest_secret_residue).  The host variant stages c1 and the c2 rows it needs in bounded
+ * pieces; the device variant is asynchronous on `stream` like pvw_decrypt_batch_device. */
+PVW_API int32_t pvw_decrypt_all(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* sk,
+                                const uint64_t* c1s, const uint64_t* c2s, size_t num_dealers, uint32_t in_repr,
+                                uint64_t* out_u64);
+PVW_API int32_t pvw_decrypt_all_device(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* d_sk,
+                                       const uint64_t* d_c1s, const uint64_t* d_c2s, size_t num_dealers,
+                                       uint32_t in_repr, uint64_t* d_out, void* stream);
 /* decode_scalar_pvw_rns alone, on the device: noisy [D][L][l] power basis (host) -> out_u64 [D] */
 PVW_API int32_t pvw_decode(pvw_ctx* ctx, const uint64_t* noisy, size_t count, uint64_t* out_u64);
 /* the same with host big integers on the host cores (no GPU needed): an independent

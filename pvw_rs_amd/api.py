@@ -677,6 +677,56 @@ def decrypt_party_shares(all_ciphertexts: Sequence[PvwCiphertext], secret_key: S
     return _decrypt_batch(p, all_ciphertexts, secret_key, party_index, return_noisy)
 
 
+def decrypt_many(ciphertexts: Sequence[PvwCiphertext], secret_keys: Sequence[SecretKey], party_lo: int) -> np.ndarray:
+    """Parties [party_lo, party_lo + len(secret_keys)) each decrypt their share of every ciphertext given -- any number of
+    them, e.g. the valid subset of examples/pvw_valid_dec.rs:201-209 -- in one call (pvw_decrypt_all): the counterpart of
+    encrypt_many.  Returns uint64 [parties][ciphertexts]; row i equals decrypt_party_shares for party party_lo + i."""
+    if len(ciphertexts) == 0:
+        raise PvwError(1, "No ciphertexts provided")
+    p = ciphertexts[0].params
+    for d, ct in enumerate(ciphertexts):
+        try:
+            ct.validate()
+        except PvwError as e:
+            raise PvwError(1, f"Ciphertext {d} invalid: {e}")
+    if len(secret_keys) == 0:
+        return np.zeros((0, len(ciphertexts)), dtype=np.uint64)
+    repr = ciphertexts[0].repr
+    if any(ct.repr != repr for ct in ciphertexts):
+        raise PvwError(18, "ciphertexts in different representations")
+    c1s = np.ascontiguousarray(np.stack([ct.c1 for ct in ciphertexts]), dtype=np.uint64)
+    c2s = np.ascontiguousarray(np.stack([ct.c2 for ct in ciphertexts]), dtype=np.uint64)
+    sk = np.ascontiguousarray(np.stack([_i64(k.secret_coeffs) for k in secret_keys]))
+    out = np.zeros((len(secret_keys), len(ciphertexts)), dtype=np.uint64)
+    try:
+        p._call("pvw_decrypt_all", party_lo, party_lo + len(secret_keys), _ptr(sk), _ptr(c1s), _ptr(c2s), len(ciphertexts),
+                repr, _ptr(out))
+    finally:
+        sk.fill(0)                                                         # the stacked copy of the keys (secret_key.rs:20-30)
+    return out
+
+
+def decrypt_all_party_shares(all_ciphertexts: Sequence[PvwCiphertext], parties: Sequence["Party"]) -> np.ndarray:
+    """Every party decrypts its share from every dealer (examples/pvw.rs:138-149, tests/crypto.rs:284-287) in one call:
+    results[recipient][dealer] (examples/pvw.rs:157-170) as uint64 [len(parties)][n].  An extension -- no single reference
+    function; the checks are decrypt_party_shares' (decryption.rs:286-305) for each party, which must have consecutive
+    indices."""
+    if len(all_ciphertexts) == 0:
+        raise PvwError(1, "No ciphertexts provided")
+    p = all_ciphertexts[0].params
+    if len(all_ciphertexts) != p.n:
+        raise PvwError(1, f"Expected {p.n} ciphertexts, got {len(all_ciphertexts)}")
+    if len(parties) == 0:
+        return np.zeros((0, p.n), dtype=np.uint64)
+    lo = parties[0].index
+    for i, party in enumerate(parties):
+        if party.index >= p.n:
+            raise PvwError(1, f"Party index {party.index} exceeds maximum {p.n - 1}")
+        if party.index != lo + i:
+            raise PvwError(1, f"Party indices must be consecutive: {party.index} follows {lo + i - 1}")
+    return decrypt_many(all_ciphertexts, [party.secret_key for party in parties], lo)
+
+
 class DeviceSecretKey:
     """pvw_sk: a SecretKey's NTT form on the device (pvw_sk_load); cleared by free() / on drop (pvw_sk_free), as the
     reference's SecretKey is ZeroizeOnDrop (secret_key.rs:20-30).  Use as a context manager or call free()."""

@@ -2379,6 +2379,227 @@ int32_t pvw_decrypt_batch(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, co
   return rc;
 }
 
+// ------------------------------------------------------------------------ decrypt for every party
+// Every party of [lo, hi) decrypts its share of each of D dealer ciphertexts in one call: the loop over
+// decrypt_party_shares (decryption.rs:281-325) that examples/pvw.rs:138-149 and tests/crypto.rs:284-287 run for all parties,
+// and examples/pvw_valid_dec.rs:201-209 over a subset of dealers.  For each (limb, slot)
+//   noisy[p][d] = sum_j s-hat_p[j] c1-hat_d[j] - c2-hat_d[p]      (decryption.rs:257-274)
+// is a (P x k) (k x D) product: the digit GEMM of key generation with the parties' s-hat as the MFMA-tiled rows (made
+// straight from the coefficients by shat_mftile) and the dealers' c1 as the digitised vectors (vec_digits reads the
+// [D][k][L][l] layout as it is, after a pass that reduces the caller's words below q).  gemm_finish_decrypt subtracts c2
+// and lays the noisy polynomials out as [party][dealer], the decode transforms back and decodes them in that order, and a
+// 2-D copy puts the chunk's results into out[p][d].
+// Fewer than PVW_DECRYPT_ALL_MIN_PARTIES parties: the GEMM pads its rows to whole workgroups and the digit tiles of every
+// dealer cost the same for one party as for a thousand, so the call runs the per-party path (decrypt_mac + decode, the
+// kernels of pvw_decrypt_batch) party by party instead.  Both give the words pvw_decrypt_batch gives.
+// Measured crossover (profiles/r04_decrypt_all.txt, config 3, 1024 dealers, each side forced): 16 parties 2.30 ms on the
+// matrix cores vs 1.82 party by party, 32 parties 2.82 vs 3.64 -- 0.114 ms per party against 1.77 + 0.033 per party: 22.
+#ifndef PVW_DECRYPT_ALL_MIN_PARTIES
+#define PVW_DECRYPT_ALL_MIN_PARTIES 22
+#endif
+static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+static int32_t decrypt_all_checks(pvw_ctx* c, u32 lo, u32 hi, const void* sk, const void* c1s, const void* c2s, size_t D,
+                                  uint32_t in_repr, const void* out) {
+  if (!c || !sk || !c1s || !c2s || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");          // decryption.rs:286-290
+  PVW_TRY(check_party_range(c, lo, hi));
+  if (lo == hi) return fail(PVW_ERR_INVALID_PARAMETERS, "empty party range");
+  PVW_TRY(check_repr(in_repr));
+  return PVW_OK;
+}
+// host: sk / c1s / c2s / out are host buffers (staged in bounded pieces); otherwise device pointers on `s`.
+// The caller's buffers are only read: POWER-basis input is transformed in scratch.
+static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, u32 hi, const int64_t* sk, const u64* c1s,
+                               const u64* c2s, size_t D, uint32_t in_repr, u64* out, bool host) {
+  const u32 k = c->k, l = c->l, L = c->L;
+  const size_t P = c->poly(), NP = (size_t)hi - lo;
+  const size_t ctw = (size_t)k * P;                      // words of one dealer's c1
+  const size_t c2d = (size_t)c->n * P;                   // words between dealers in c2s
+  const bool power = in_repr == PVW_REPR_POWER, stage = host || power;
+  const hipMemcpyKind kin = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  const hipMemcpyKind kout = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  const long min_parties = PVW_ENV_INT("PVW_DECRYPT_ALL_MIN_PARTIES", PVW_DECRYPT_ALL_MIN_PARTIES);   // tuning build only
+  const bool use_gemm = min_parties > 0 && NP >= (size_t)min_parties;
+  if (!use_gemm) {
+    // ---- party by party: dealers in chunks of <= 1 GiB of c1, each chunk's c1 shared by every party
+    size_t Dc = ((size_t)1 << 30) / (ctw * 8);
+    if (Dc == 0) Dc = 1;
+    if (Dc > D) Dc = D;
+    const size_t b_sk = host ? al256(NP * k * l * 8) : 0, b_c1 = stage ? al256(Dc * ctw * 8) : 0;
+    const size_t b_c2 = al256(Dc * P * 8), b_nz = al256(Dc * P * 8), b_out = host ? al256(Dc * 8) : 0;
+    PVW_TRY(ws_scratch(w, b_sk + b_c1 + b_c2 + b_nz + b_out));
+    char* base = (char*)w->scratch;
+    i64* d_sk = (i64*)base;
+    u64* d_c1 = (u64*)(base + b_sk);
+    u64* d_c2 = (u64*)(base + b_sk + b_c1);
+    u64* d_nz = (u64*)(base + b_sk + b_c1 + b_c2);
+    u64* d_out = (u64*)(base + b_sk + b_c1 + b_c2 + b_nz);
+    // key material: the uploaded coefficients, NTT(sk) (w->rhat), the noisy polynomials (m g-hat + noise) and the decoded values
+    ws_mark_secret(w, d_sk, b_sk);
+    ws_mark_secret(w, w->rhat, (size_t)k * P * 8);
+    ws_mark_secret(w, d_nz, b_nz + b_out);
+    if (host) PVW_HIP(hipMemcpyAsync(d_sk, sk, NP * k * l * 8, hipMemcpyHostToDevice, s));
+    const i64* skd = host ? d_sk : sk;
+    for (size_t d0 = 0; d0 < D; d0 += Dc) {
+      const size_t cnt = (D - d0) < Dc ? (D - d0) : Dc;
+      const u64* c1 = c1s + d0 * ctw;
+      if (stage) {
+        PVW_HIP(hipMemcpyAsync(d_c1, c1, cnt * ctw * 8, kin, s));
+        if (power) { ProfScope ps(c, "ntt", s); PVW_HIP(launch_ntt(d_c1, cnt * k, false, c->dt, L, l, s)); }
+        c1 = d_c1;
+      }
+      for (size_t p = 0; p < NP; ++p) {
+        // party lo + p's column of c2: one row of each dealer, n rows apart
+        PVW_HIP(hipMemcpy2DAsync(d_c2, P * 8, c2s + d0 * c2d + (lo + p) * P, c2d * 8, P * 8, cnt, kin, s));
+        if (power) { ProfScope ps(c, "ntt", s); PVW_HIP(launch_ntt(d_c2, cnt, false, c->dt, L, l, s)); }
+        {
+          ProfScope ps(c, "prep", s);
+          PVW_HIP(launch_prep(skd + p * k * l, nullptr, w->rhat, P, l, k, true, c->dt, L, l, s));   // secret_key.rs:98-112
+        }
+        bool ntt_domain = false;
+        const int32_t rm = decrypt_mac_only(c, w, c1, d_c2, cnt, d_nz, s, &ntt_domain);          // decryption.rs:257-274
+        if (w->dpart && (p == 0 || rm != PVW_OK)) ws_mark_secret(w, w->dpart, w->dpart_bytes);   // range sums of s-hat c1
+        PVW_TRY(rm);
+        if (ntt_domain && (cnt + 1) / 2 > (size_t)2 * c->num_cus) {                            // as in pvw_decrypt_batch_device
+          ProfScope pi(c, "intt", s);
+          PVW_HIP(launch_ntt(d_nz, cnt, true, c->dt, L, l, s));
+          ntt_domain = false;
+        }
+        u64* o = out + p * D + d0;
+        {
+          ProfScope ps(c, "decode", s);
+          PVW_HIP(launch_decode(d_nz, host ? d_out : o, cnt, c->dec_dev, s, ntt_domain ? &c->dt : nullptr));   // :116, :10-58
+        }
+        if (host) PVW_HIP(hipMemcpyAsync(o, d_out, cnt * 8, hipMemcpyDeviceToHost, s));
+      }
+    }
+    return PVW_OK;
+  }
+  // ---- matrix cores.  Dealers in groups of up to 128 (one gemm_digits launch each; c1 of the group reduced and digitised
+  // once per party chunk, <= 1 GiB with its digit tiles), parties in chunks that keep the rest below 3 GiB.
+  size_t Dg = D < 128 ? D : 128;
+  while (Dg > 1 && Dg * ctw * 72 > ((size_t)1 << 30)) Dg /= 2;     // c1 copy (8 bytes a word) + digit tiles (64)
+  const size_t nbg = (Dg + 15) / 16;
+  const bool direct = l <= 32;                                     // s-hat straight into the tiled operand (shat_mftile)
+  const size_t per_party = ctw * 8 * (direct ? 1 : 2) + nbg * 16 * P * 8 + Dg * P * 8 * (stage ? 2 : 1) + Dg * 8 + (host ? (size_t)k * l * 8 : 0);
+  size_t Pc = ((size_t)3 << 30) / per_party;
+  if (Pc >= NP) Pc = NP;
+  else if (Pc >= PVW_GEMM_ROWS_PER_WG) Pc -= Pc % PVW_GEMM_ROWS_PER_WG;   // whole workgroups of GEMM rows
+  if (Pc == 0) Pc = 1;
+  const size_t b_c1 = al256(Dg * ctw * 8), b_yd = al256(yd_bytes((u32)(16 * nbg), k, L, l)), b_sy = al256(sy_bytes((u32)(16 * nbg), L, l));
+  const size_t b_sk = host ? al256(Pc * k * l * 8) : 0, b_rows = direct ? 0 : al256(Pc * ctw * 8);
+  const size_t b_xm = al256(xm_words((u32)Pc, k, L, l) * 8), b_tmp = al256(nbg * gemm_tmp_words((u32)Pc, L, l) * 8);
+  const size_t b_c2 = stage ? al256(Dg * Pc * P * 8) : 0, b_nz = al256(Dg * Pc * P * 8), b_out = al256(Dg * Pc * 8);
+  PVW_TRY(ws_scratch(w, b_c1 + b_yd + b_sy + b_sk + b_rows + b_xm + b_tmp + b_c2 + b_nz + b_out));
+  char* base = (char*)w->scratch;
+  u64* d_c1 = (u64*)base;
+  signed char* d_yd = (signed char*)(base + b_c1);
+  int* d_sy = (int*)(base + b_c1 + b_yd);
+  char* sec = base + b_c1 + b_yd + b_sy;                           // from here on: everything derived from the keys
+  i64* d_sk = (i64*)sec;
+  u64* d_rows = (u64*)(sec + b_sk);
+  u64* d_xm = (u64*)(sec + b_sk + b_rows);
+  u64* d_tmp = (u64*)(sec + b_sk + b_rows + b_xm);
+  u64* d_c2 = (u64*)(sec + b_sk + b_rows + b_xm + b_tmp);
+  u64* d_nz = (u64*)(sec + b_sk + b_rows + b_xm + b_tmp + b_c2);
+  u64* d_out = (u64*)(sec + b_sk + b_rows + b_xm + b_tmp + b_c2 + b_nz);
+  // the uploaded coefficients, the tiled s-hat (and its rows, l = 64), the GEMM intermediate (s-hat c1), the noisy
+  // polynomials and the decoded values; the staged c2 rows share the region
+  ws_mark_secret(w, sec, b_sk + b_rows + b_xm + b_tmp + b_c2 + b_nz + b_out);
+  for (size_t p0 = 0; p0 < NP; p0 += Pc) {
+    const u32 pc = (u32)((NP - p0) < Pc ? (NP - p0) : Pc);
+    const i64* skp = sk + p0 * k * l;
+    if (host) {
+      PVW_HIP(hipMemcpyAsync(d_sk, skp, (size_t)pc * k * l * 8, hipMemcpyHostToDevice, s));
+      skp = d_sk;
+    }
+    {
+      ProfScope ps(c, "prep", s);
+      if (direct) {
+        PVW_HIP(launch_shat_mftile(skp, d_xm, pc, k, L, l, c->dt, s));                        // secret_key.rs:98-112
+      } else {
+        PVW_HIP(launch_prep(skp, nullptr, d_rows, P, l, pc * k, true, c->dt, L, l, s));
+        PVW_HIP(hipMemsetAsync(d_xm, 0, xm_words(pc, k, L, l) * 8, s));
+        PVW_HIP(launch_mftile(d_rows, false, d_xm, pc, k, L, l, s));
+      }
+    }
+    for (size_t d0 = 0; d0 < D; d0 += Dg) {
+      const u32 dg = (u32)((D - d0) < Dg ? (D - d0) : Dg);
+      {
+        ProfScope ps(c, "digits", s);
+        const u64* c1 = c1s + d0 * ctw;
+        if (stage) {
+          PVW_HIP(hipMemcpyAsync(d_c1, c1, (size_t)dg * ctw * 8, kin, s));
+          if (power) PVW_HIP(launch_ntt(d_c1, (size_t)dg * k, false, c->dt, L, l, s));
+          c1 = d_c1;
+        }
+        PVW_HIP(launch_reduce_words(c1, d_c1, (size_t)dg * ctw, c->dt, L, l, s));
+        // vector d = dealer: element j at d * k P + j * P + limb * l + slot
+        PVW_HIP(launch_vec_digits(d_c1, ctw, d_yd, d_sy, dg, k, L, l, c->dt, s, l, P));
+      }
+      const u64* c2p = c2s + d0 * c2d + (lo + p0) * P;
+      size_t c2v = c2d;
+      if (stage) {                                                 // rows [lo + p0, lo + p0 + pc) of each dealer only
+        PVW_HIP(hipMemcpy2DAsync(d_c2, (size_t)pc * P * 8, c2p, c2d * 8, (size_t)pc * P * 8, dg, kin, s));
+        if (power) { ProfScope ps(c, "ntt", s); PVW_HIP(launch_ntt(d_c2, (size_t)dg * pc, false, c->dt, L, l, s)); }
+        c2p = d_c2;
+        c2v = (size_t)pc * P;
+      }
+      GemmSection ga{d_xm, nullptr, nullptr, d_tmp, pc, 0, 0}, gb{nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
+      {
+        ProfScope ps(c, "gemm", s);
+        PVW_HIP(launch_gemm_digits_core(ga, gb, d_yd, d_sy, c->dt, k, L, l, dg, s));
+      }
+      {
+        ProfScope ps(c, "finish", s);
+        PVW_HIP(launch_finish_decrypt(ga, d_sy, c->dt, L, l, dg, c2p, c2v, P, d_nz, s));     // decryption.rs:257-274
+      }
+      const size_t cnt = (size_t)pc * dg;
+      bool xf = true;
+      if ((cnt + 1) / 2 > (size_t)2 * c->num_cus) {                // as in pvw_decrypt_batch_device
+        ProfScope pi(c, "intt", s);
+        PVW_HIP(launch_ntt(d_nz, cnt, true, c->dt, L, l, s));
+        xf = false;
+      }
+      {
+        ProfScope ps(c, "decode", s);
+        PVW_HIP(launch_decode(d_nz, d_out, cnt, c->dec_dev, s, xf ? &c->dt : nullptr));           // :116, :10-58
+      }
+      // results[recipient][dealer] (examples/pvw.rs:157-170): the chunk's [pc][dg] block into out[p0..][d0..]
+      PVW_HIP(hipMemcpy2DAsync(out + p0 * D + d0, D * 8, d_out, (size_t)dg * 8, (size_t)dg * 8, pc, kout, s));
+    }
+  }
+  return PVW_OK;
+}
+// single exit: nothing of a failed call stays queued, the key-derived regions are cleared behind the last launch that
+// reads them (host variant: before the workspace goes back to the pool)
+static int32_t decrypt_all_end(Workspace* w, hipStream_t s, int32_t rc, bool host) {
+  if (rc != PVW_OK) (void)hipStreamSynchronize(s);
+  if (ws_wipe_secrets(w, s) != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, "wipe failed");
+  if (host && hipStreamSynchronize(s) != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
+  return rc;
+}
+int32_t pvw_decrypt_all(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
+                        size_t D, uint32_t in_repr, uint64_t* out) {
+  PVW_TRY(decrypt_all_checks(c, lo, hi, sk, c1s, c2s, D, in_repr, out));
+  PVW_TRY(ensure_device(c));
+  Workspace* w;
+  PVW_TRY(ws_acquire(c, &w));
+  int32_t rc = decrypt_all_run(c, w, w->stream, lo, hi, sk, c1s, c2s, D, in_repr, out, true);
+  rc = decrypt_all_end(w, w->stream, rc, true);
+  ws_release(c, w);
+  return rc;
+}
+int32_t pvw_decrypt_all_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
+                               const uint64_t* d_c2s, size_t D, uint32_t in_repr, uint64_t* d_out, void* stream) {
+  PVW_TRY(decrypt_all_checks(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out));
+  PVW_TRY(ensure_device(c));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  Workspace* w;
+  PVW_TRY(ws_for_stream(c, s, &w));
+  return decrypt_all_end(w, s, decrypt_all_run(c, w, s, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out, false), false);
+}
+
 // ------------------------------------------------------------------------ key generation
 // b_i = s_i * A + e_i: for every party the k-term inner products over A's COLUMNS, i.e. one
 // mac_rows pass over the transposed CRS per party (public_key.rs:111-147, crs.rs:138-171).

@@ -1087,10 +1087,8 @@ hipError_t launch_vec_digits(const u64* vhat, size_t vstride, signed char* YD, i
   return hipGetLastError();
 }
 
-hipError_t launch_gemm_digits(const GemmSection& a, const GemmSection& b, const signed char* YD, const int* SY,
-                              const DevTables& t, u32 k, u32 L, u32 ell, u32 nv, size_t ostride_a, size_t ostride_b,
-                              hipStream_t s, const GemmErrSource* es_a, const GemmErrSource* es_b, u32 bytes) {
-  GemmSection sa = a, sb = b;
+hipError_t launch_gemm_digits_core(GemmSection& sa, GemmSection& sb, const signed char* YD, const int* SY,
+                                   const DevTables& t, u32 k, u32 L, u32 ell, u32 nv, hipStream_t s, u32 bytes) {
   const u32 kt = gemm_ktiles(k, bytes);
   sa.rt_groups = (sa.nrows + PVW_GEMM_ROWS_PER_WG - 1) / PVW_GEMM_ROWS_PER_WG;
   sb.rt_groups = (sb.nrows + PVW_GEMM_ROWS_PER_WG - 1) / PVW_GEMM_ROWS_PER_WG;
@@ -1138,6 +1136,21 @@ hipError_t launch_gemm_digits(const GemmSection& a, const GemmSection& b, const 
   }
 #undef PVW_GEMM_LAUNCH
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_gemm_digits(const GemmSection& a, const GemmSection& b, const signed char* YD, const int* SY,
+                              const DevTables& t, u32 k, u32 L, u32 ell, u32 nv, size_t ostride_a, size_t ostride_b,
+                              hipStream_t s, const GemmErrSource* es_a, const GemmErrSource* es_b, u32 bytes) {
+  GemmSection sa = a, sb = b;
+  if ((sa.nrows == 0 && sb.nrows == 0) || nv == 0) return hipSuccess;
+  {
+    const hipError_t ge = launch_gemm_digits_core(sa, sb, YD, SY, t, k, L, ell, nv, s, bytes);
+    if (ge != hipSuccess) return ge;
+  }
+  const u32 vbn = (nv + 15) / 16;
+  const u32 nv_pad = (vbn > 1 ? 4 : (nv + 3) / 4) * 4;
+  const size_t sy_b16 = sy_bytes(16, L, ell) / sizeof(int);
   // a section with an error source: gemm_finish_err_kernel (l <= 32; the tiled form only with tiled_swap)
   auto finish = [&](const GemmSection& sec, size_t ostride, const GemmErrSource* es) -> hipError_t {
     if (!sec.nrows) return hipSuccess;
@@ -1188,6 +1201,93 @@ hipError_t launch_gemm_digits(const GemmSection& a, const GemmSection& b, const 
   hipError_t fe = finish(sa, ostride_a, es_a);
   if (fe != hipSuccess) return fe;
   return finish(sb, ostride_b, es_b);
+}
+static inline u32 ilog2_u32(u32 x) { u32 b = 0; while ((1u << b) < x) ++b; return b; }
+
+// ---- decryption for many parties at once (pvw_decrypt_all): GEMM rows = parties, vectors = dealers ----
+// gemm_finish_decrypt: noisy[row][v] = (sum_j s-hat_row[j] c1-hat_v[j] + SY correction) - c2-hat_v[row]  (decryption.rs:257-274)
+// in the NTT domain, written as the [count][L][l] polynomials launch_decode(..., xf) reads, count = rows x nv in row-major
+// (party, dealer) order.  Every (limb, slot) pair of a polynomial is one index f = limb * l + slot of the P = L l words, and
+// the intermediate is [f][v][row] (tmp of gemm_digits: [limb][slot][v][row]), so one block = 128 rows x 32 consecutive f of
+// one vector:
+//   in:  wave w reads f = w, w + 4, ..: 128 consecutive rows of one f = ONE 1-KiB load per wave instruction (16 bytes a lane),
+//        adds the offset correction (wave-uniform) and leaves the pair in an LDS tile [row][f];
+//   out: 16 lanes per row take the row's 32 f = 256 contiguous bytes of c2 and of noisy per row (rows of c2 are P words
+//        apart; 4 rows per wave instruction, 1 KiB in, 1 KiB out).
+// c2 is read as the caller left it: submod on the raw word, as decrypt_mac does, so that unreduced words give what the
+// per-party path gives.  No c2 row outside [0, nrows) of the section is touched.
+__global__ __launch_bounds__(256) void gemm_finish_decrypt_kernel(const u64* __restrict__ tmp, size_t tmp_bstride, u32 nv_pad,
+                                                                  u32 rows_pad, const int* __restrict__ SY, size_t sy_b16,
+                                                                  const Mod* __restrict__ mods, u32 ell_log2, u32 P, u32 nrows,
+                                                                  u32 nv, const u64* __restrict__ c2, size_t c2_vstride,
+                                                                  size_t c2_rstride, u64* __restrict__ noisy) {
+  constexpr u32 TR = 128, TF = 32;
+  __shared__ __attribute__((aligned(16))) u64 tile[TR][TF + 2];   // +2: 16-byte aligned rows, banks spread
+  const u32 r0 = blockIdx.x * TR, f0 = blockIdx.y * TF, v = blockIdx.z;
+  const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const u64* tb = tmp + (size_t)(v >> 4) * tmp_bstride + (size_t)(v & 15) * rows_pad + r0 + 2 * lane;
+  const size_t fstride = (size_t)nv_pad * rows_pad;               // words between consecutive f of the intermediate
+  const u64* cb = reinterpret_cast<const u64*>(SY + (size_t)(v >> 4) * sy_b16 + (size_t)((v & 15) >> 2) * P * 32) + (v & 3);
+  v2u64 x[TF / 4];
+#pragma unroll
+  for (u32 i = 0; i < TF / 4; ++i) {                               // all loads in flight before the first use
+    const u32 f = f0 + wave + 4 * i;
+    // rows_pad is a multiple of TR: the pair lies inside the intermediate even past nrows
+    if (f < P) x[i] = __builtin_nontemporal_load(reinterpret_cast<const v2u64*>(tb + (size_t)f * fstride));
+  }
+#pragma unroll
+  for (u32 i = 0; i < TF / 4; ++i) {
+    const u32 fl = wave + 4 * i, f = f0 + fl;
+    if (f < P) {
+      const u64 q = mods[f >> ell_log2].q;
+      const u64 corr = cb[(size_t)f * 16];                         // SY records are 32 ints
+      tile[2 * lane][fl] = addmod(x[i].x, corr, q);
+      tile[2 * lane + 1][fl] = addmod(x[i].y, corr, q);
+    }
+  }
+  __syncthreads();
+  const u32 fp = (threadIdx.x & 15) * 2, f = f0 + fp;             // P is a multiple of 8: f and f + 1 share a limb
+  if (f >= P) return;
+  const u64 q = mods[f >> ell_log2].q;
+#pragma unroll
+  for (u32 i = 0; i < TR / 16; ++i) {
+    const u32 rl = (threadIdx.x >> 4) + 16 * i, row = r0 + rl;
+    if (row < nrows) {
+      const v2u64 cw = __builtin_nontemporal_load(reinterpret_cast<const v2u64*>(c2 + (size_t)v * c2_vstride + (size_t)row * c2_rstride + f));
+      const v2u64 t2 = *reinterpret_cast<const v2u64*>(&tile[rl][fp]);
+      const v2u64 o = (v2u64){submod(t2.x, cw.x, q), submod(t2.y, cw.y, q)};
+      *reinterpret_cast<v2u64*>(noisy + ((size_t)row * nv + v) * P + f) = o;
+    }
+  }
+}
+// words [count] of polynomials [.][L][l] -> their residues mod q_limb (dst may alias src).  The digit tiles need operands
+// below 2^62 (vec_digits_kernel); the per-party inner products reduce whatever 64-bit word they are given.
+__global__ __launch_bounds__(256) void reduce_words_kernel(const u64* __restrict__ src, u64* __restrict__ dst, size_t pairs,
+                                                           const Mod* __restrict__ mods, u32 ell_log2, u32 L) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= pairs) return;
+  const Mod m = mods[((2 * i) >> ell_log2) % L];
+  const v2u64 w = reinterpret_cast<const v2u64*>(src)[i];
+  reinterpret_cast<v2u64*>(dst)[i] = (v2u64){w.x < m.q ? w.x : reduce128(w.x, 0, m), w.y < m.q ? w.y : reduce128(w.y, 0, m)};
+}
+hipError_t launch_reduce_words(const u64* src, u64* dst, size_t words, const DevTables& t, u32 L, u32 ell, hipStream_t s) {
+  if (words == 0) return hipSuccess;
+  if (words % 2) return hipErrorInvalidValue;
+  const size_t pairs = words / 2;
+  reduce_words_kernel<<<dim3((u32)((pairs + 255) / 256)), dim3(256), 0, s>>>(src, dst, pairs, t.mods, ilog2_u32(ell), L);
+  return hipGetLastError();
+}
+hipError_t launch_finish_decrypt(const GemmSection& a, const int* SY, const DevTables& t, u32 L, u32 ell, u32 nv, const u64* c2,
+                                 size_t c2_vstride, size_t c2_rstride, u64* noisy, hipStream_t s) {
+  if (a.nrows == 0 || nv == 0) return hipSuccess;
+  const u32 vbn = (nv + 15) / 16;
+  const u32 nv_pad = (vbn > 1 ? 4 : (nv + 3) / 4) * 4;
+  const u32 rows_pad = a.rt_groups * PVW_GEMM_ROWS_PER_WG, P = L * ell;
+  static_assert(PVW_GEMM_ROWS_PER_WG % 128 == 0, "finish tiles of 128 rows");
+  const dim3 grid((a.nrows + 127) / 128, (P + 31) / 32, nv);
+  gemm_finish_decrypt_kernel<<<grid, dim3(256), 0, s>>>(a.tmp, a.tmp_bstride, nv_pad, rows_pad, SY, sy_bytes(16, L, ell) / sizeof(int),
+                                                        t.mods, ilog2_u32(ell), P, a.nrows, nv, c2, c2_vstride, c2_rstride, noisy);
+  return hipGetLastError();
 }
 hipError_t launch_mfma_probe(const signed char* A, const signed char* B, int* C, hipStream_t s) {
   mfma_i8_probe_kernel<<<dim3(1), dim3(64), 0, s>>>(A, B, C);

@@ -225,6 +225,17 @@ struct GemmErrSource {
 hipError_t launch_gemm_digits(const GemmSection& a, const GemmSection& b, const signed char* YD, const int* SY,
                               const DevTables& t, u32 k, u32 L, u32 ell, u32 nv, size_t ostride_a, size_t ostride_b,
                               hipStream_t s, const GemmErrSource* es_a = nullptr, const GemmErrSource* es_b = nullptr, u32 bytes = 8);
+// the GEMM of launch_gemm_digits alone (no finish pass): a.tmp / b.tmp receive the intermediate [limb][slot][v][row];
+// rt_groups and tmp_bstride of both sections are filled in
+hipError_t launch_gemm_digits_core(GemmSection& a, GemmSection& b, const signed char* YD, const int* SY, const DevTables& t, u32 k,
+                                   u32 L, u32 ell, u32 nv, hipStream_t s, u32 bytes = 8);
+// decrypt for many parties (pvw_decrypt_all): after launch_gemm_digits_core on section a (rows = parties, vectors = dealers'
+// c1), noisy[row][v] = intermediate + offset correction - c2[v * c2_vstride + row * c2_rstride] in the NTT domain, as
+// [a.nrows * nv][L][l] in (row, v) order -- the input of launch_decode(..., xf)
+hipError_t launch_finish_decrypt(const GemmSection& a, const int* SY, const DevTables& t, u32 L, u32 ell, u32 nv, const u64* c2,
+                                 size_t c2_vstride, size_t c2_rstride, u64* noisy, hipStream_t s);
+// dst[i] = src[i] mod q of its limb, for `words` words of [.][L][l] polynomials (words even; dst may alias src)
+hipError_t launch_reduce_words(const u64* src, u64* dst, size_t words, const DevTables& t, u32 L, u32 ell, hipStream_t s);
 // read-only probe: every wave streams `tiles` consecutive 1-KiB tiles (16 in flight), grid as mac_rows
 #if PVW_TUNING
 // time stamps (100 MHz ticks, [2b] start / [2b+1] end) and HW_ID words of the workgroups of the last stamped mac_rows launch

@@ -359,6 +359,48 @@ inline std::vector<uint64_t> decrypt_party_shares(const std::vector<PvwCiphertex
   check(pvw_decrypt_batch(p->ctx, sk.secret_coeffs.data(), c1s.data(), c2col.data(), cts.size(), cts[0].repr, out.data(), nullptr));
   return out;
 }
+// every party of [party_lo, party_lo + secret_keys.size()) decrypts its share of each ciphertext (any number of them, e.g.
+// the valid subset of examples/pvw_valid_dec.rs:201-209) in one call (pvw_decrypt_all): result[p][d]
+inline std::vector<std::vector<uint64_t>> decrypt_many(const std::vector<PvwCiphertext>& cts, const std::vector<const SecretKey*>& secret_keys,
+                                                       uint32_t party_lo) {
+  if (cts.empty()) throw PvwError(1, "No ciphertexts provided");
+  const auto& p = cts[0].params;
+  const size_t D = cts.size(), NP = secret_keys.size(), P = p->poly_words(), kl = (size_t)p->k * p->l;
+  if (NP == 0) return {};
+  std::vector<uint64_t> c1s, c2s, out(NP * D);
+  c1s.reserve(D * p->k * P);
+  c2s.reserve(D * p->n * P);
+  for (const auto& ct : cts) {
+    ct.validate();
+    if (ct.repr != cts[0].repr) throw PvwError(1, "ciphertexts in different representations");
+    c1s.insert(c1s.end(), ct.c1.begin(), ct.c1.end());
+    c2s.insert(c2s.end(), ct.c2.begin(), ct.c2.end());
+  }
+  std::vector<int64_t> sk(NP * kl);
+  for (size_t i = 0; i < NP; ++i) std::copy(secret_keys[i]->secret_coeffs.begin(), secret_keys[i]->secret_coeffs.end(), sk.begin() + i * kl);
+  const int32_t rc = pvw_decrypt_all(p->ctx, party_lo, party_lo + (uint32_t)NP, sk.data(), c1s.data(), c2s.data(), D, cts[0].repr, out.data());
+  std::fill(sk.begin(), sk.end(), 0);                                   // the copied keys do not outlive the call
+  check(rc);
+  std::vector<std::vector<uint64_t>> res(NP);
+  for (size_t i = 0; i < NP; ++i) res[i].assign(out.begin() + i * D, out.begin() + (i + 1) * D);
+  return res;
+}
+// the loop over decrypt_party_shares of examples/pvw.rs:138-149 as one call (an extension; no single reference function):
+// results[recipient][dealer] (:157-170) for parties with consecutive indices, checks as decryption.rs:286-305
+inline std::vector<std::vector<uint64_t>> decrypt_all_party_shares(const std::vector<PvwCiphertext>& cts, const std::vector<Party>& parties) {
+  if (cts.empty()) throw PvwError(1, "No ciphertexts provided");
+  const auto& p = cts[0].params;
+  if (cts.size() != p->n) throw PvwError(1, "Expected " + std::to_string(p->n) + " ciphertexts, got " + std::to_string(cts.size()));
+  if (parties.empty()) return {};
+  std::vector<const SecretKey*> keys;
+  for (size_t i = 0; i < parties.size(); ++i) {
+    if (parties[i].index >= p->n)
+      throw PvwError(1, "Party index " + std::to_string(parties[i].index) + " exceeds maximum " + std::to_string(p->n - 1));
+    if (parties[i].index != parties[0].index + i) throw PvwError(1, "Party indices must be consecutive");
+    keys.push_back(&parties[i].secret_key);
+  }
+  return decrypt_many(cts, keys, parties[0].index);
+}
 // decrypt_party_value (decryption.rs:249-278)
 inline uint64_t decrypt_party_value(const PvwCiphertext& ct, const SecretKey& sk, uint32_t party_index) {
   const auto& p = ct.params;

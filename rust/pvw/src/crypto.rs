@@ -188,3 +188,52 @@ pub fn decrypt_party_shares(all_ciphertexts: &[PvwCiphertext], secret_key: &Secr
     check(rc)?;
     Ok(out)
 }
+
+/// EXTENSION -- no single reference function behind it.  The loop examples/pvw.rs:138-149 and tests/crypto.rs:284-287
+/// run over `decrypt_party_shares` for every party, as one call: `results[recipient][dealer]` (examples/pvw.rs:157-170)
+/// from one digit GEMM of the parties' keys against all dealers' c1 (`pvw_decrypt_all`).  `parties` must carry
+/// consecutive indices; the checks and messages are those of decryption.rs:286-305, per party.
+pub fn decrypt_all_party_shares(all_ciphertexts: &[PvwCiphertext], parties: &[crate::keys::public_key::Party]) -> Result<Vec<Vec<u64>>> {
+    if all_ciphertexts.is_empty() {
+        return Err(PvwError::InvalidParameters("No ciphertexts provided".to_string()));
+    }
+    let params = &all_ciphertexts[0].params;
+    if all_ciphertexts.len() != params.n {
+        return Err(PvwError::InvalidParameters(format!("Expected {} ciphertexts, got {}", params.n, all_ciphertexts.len())));
+    }
+    if parties.is_empty() {
+        return Ok(Vec::new());
+    }
+    let lo = parties[0].index;
+    for (i, party) in parties.iter().enumerate() {
+        if party.index >= params.n {
+            return Err(PvwError::InvalidParameters(format!("Party index {} exceeds maximum {}", party.index, params.n - 1)));
+        }
+        if party.index != lo + i {
+            return Err(PvwError::InvalidParameters(format!("Party indices must be consecutive: {} follows {}", party.index, lo + i - 1)));
+        }
+    }
+    let words = poly_words(params);
+    let d = all_ciphertexts.len();
+    let (mut c1s, mut c2s) = (Vec::with_capacity(d * params.k * words), Vec::with_capacity(d * params.n * words));
+    for (dealer_idx, ciphertext) in all_ciphertexts.iter().enumerate() {
+        ciphertext
+            .validate()
+            .map_err(|e| PvwError::InvalidParameters(format!("Ciphertext {dealer_idx} invalid: {e}")))?;
+        for poly in ciphertext.c1.iter() {
+            poly_to_flat(poly, &mut c1s);
+        }
+        for poly in ciphertext.c2.iter() {
+            poly_to_flat(poly, &mut c2s);
+        }
+    }
+    let mut sk: Vec<i64> = parties.iter().flat_map(|p| flat_secret(&p.secret_key)).collect();
+    let np = parties.len();
+    let mut out = vec![0u64; np * d];
+    let rc = unsafe {
+        sys::pvw_decrypt_all(params.hip.raw(), lo as u32, (lo + np) as u32, sk.as_ptr(), c1s.as_ptr(), c2s.as_ptr(), d, sys::PVW_REPR_POWER, out.as_mut_ptr())
+    };
+    sk.zeroize();
+    check(rc)?;
+    Ok(out.chunks_exact(d).map(|r| r.to_vec()).collect())
+}
