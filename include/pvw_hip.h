@@ -37,7 +37,10 @@
  *     for pvw_encrypt_multi_device): that call allocates up to a second copy of
  *     the resident matrices and waits for the build.  A call made while its
  *     stream is being captured into a graph never builds anything: it uses the
- *     copies that are valid (pvw_prepare first) or the plain tiled matrices.
+ *     copies that are valid (pvw_prepare first) or the plain tiled matrices
+ *     (multi-dealer encrypt on the matrix cores fails without pvw_prepare(PVW_PREPARE_MFMA)).
+ *     A captured encrypt with PVW_RND_SEED repeats its randomness on every replay:
+ *     capture the *_rs_device calls, which draw from a pvw_rnd_state, instead.
  *     The context's own stream is created non-blocking: it is NOT ordered against
  *     the legacy default stream, so a caller that prepares or consumes the buffers
  *     on the default stream (stream 0 -- also what a framework's "current stream"
@@ -93,7 +96,7 @@ enum { PVW_RND_SEED = 0, PVW_RND_EXPLICIT = 1 };
 /* ChaCha8 stream-id domains of the counter-based sampler: stream = (domain<<32)|poly index */
 enum {
   PVW_DOM_R = 0, PVW_DOM_E1 = 1, PVW_DOM_E2 = 2, PVW_DOM_SK = 3, PVW_DOM_EKEY = 4,
-  PVW_DOM_CRS = 5, PVW_DOM_GAUSS = 6, PVW_DOM_PK = 7
+  PVW_DOM_CRS = 5, PVW_DOM_GAUSS = 6, PVW_DOM_PK = 7, PVW_DOM_CALL = 8 /* pvw_rnd_call_seed */
 };
 
 /* PvwParametersBuilder fields (src/params/parameters.rs:44-52).  The builder's
@@ -117,7 +120,8 @@ typedef struct {
 
 /* Randomness of one encrypt call.  The reference draws from thread_rng() inside
  * rayon closures (encryption.rs:138,164,180) and cannot be replayed; this ABI
- * makes the randomness an input.  SEED: r ~ CBD(secret_variance), e1/e2 uniform
+ * makes the randomness an input -- it travels with the call, so a call captured into a
+ * graph REPEATS it on every replay (use a pvw_rnd_state, below, for captured encrypts).  SEED: r ~ CBD(secret_variance), e1/e2 uniform
  * in [-bound, bound], each polynomial from its own ChaCha8 stream.  EXPLICIT:
  * small signed coefficients supplied by the caller. */
 typedef struct {
@@ -225,6 +229,53 @@ PVW_API int32_t pvw_encrypt_multi(pvw_ctx* ctx, const uint64_t* scalars, size_t 
 PVW_API int32_t pvw_encrypt_multi_device(pvw_ctx* ctx, const uint64_t* d_scalars, size_t num_dealers,
                                          size_t scalars_per_dealer, const uint8_t* seeds,
                                          uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream);
+
+/* ---- encrypt from a device randomness state -----------------------------------------------------------------------
+ * PVW_RND_SEED puts the seed into the kernel arguments: a call captured into a graph (hipGraph, torch.cuda.graph)
+ * REPEATS its r, e1, e2 on every replay, and two replays with different scalars reveal m - m' (c1 == c1',
+ * c2 - c2' = (m - m') g-hat).  The reference draws fresh randomness on every encrypt (encryption.rs:135-167).  A
+ * pvw_rnd_state holds a 32-byte seed S and a 64-bit counter c on the device; encrypt calls that take one read it when
+ * their kernels RUN and advance c themselves, so every replay and every queued asynchronous call draws new randomness.
+ *   call_seed(S, c) = words 0..7 (little-endian bytes) of the ChaCha8 block keyed by S with block counter c and stream
+ *   id (PVW_DOM_CALL << 32) | 0 (the layout of the samplers' streams); pvw_rnd_call_seed computes it on the host.
+ *   pvw_encrypt_rs[_device] running while the state holds c  ==  pvw_encrypt[_device] with PVW_RND_SEED and seed
+ *   call_seed(S, c); afterwards the state holds c + 1.
+ *   pvw_encrypt_multi_rs[_device] with D dealers  ==  pvw_encrypt_multi[_device] with seeds[d] = call_seed(S, c + d);
+ *   afterwards the state holds c + D.
+ * The state is ordered by the stream of the call that uses it: it must not be used by calls on two streams at once
+ * (host-buffer calls run on a pooled stream of their own and return when done: make sure earlier asynchronous work on
+ * the state has completed first).  Sharded contexts (one process per GPU) that create their states with the same (S, c)
+ * and make the same calls stay in step, so r stays shared across ranks.  The derived seeds never leave registers / LDS.
+ * No call allocates or synchronises with the host once pvw_prepare has run for its stream (multi-dealer: under stream
+ * capture without pvw_prepare(PVW_PREPARE_MFMA), the call returns PVW_ERR_INVALID_PARAMETERS and enqueues nothing).
+ * Argument errors (NULL handle, dealer count, scalars_per_dealer) come before any device work. */
+/* The state is an opaque handle (void*, like the buffers of pvw_host_alloc) made by pvw_rnd_state_create.
+ * create allocates the state on ctx's device (not under stream capture); the handle records that device and ctx's stream
+ * (used for NULL stream arguments below and by pvw_rnd_state_free) and does not read ctx again.  Free it before the context. */
+PVW_API int32_t pvw_rnd_state_create(pvw_ctx* ctx, const uint8_t seed[32], uint64_t counter, void** out);
+/* the counter once the work enqueued on `stream` so far is done (waits for that stream; not under capture) */
+PVW_API int32_t pvw_rnd_state_counter(void* st, void* stream, uint64_t* out);
+/* stream-ordered write of the counter (a one-lane kernel: may be captured) */
+PVW_API int32_t pvw_rnd_state_set_counter(void* st, uint64_t counter, void* stream);
+/* clears the device seed and counter (stream-ordered memset, then a wait on the recorded stream), then frees.  Work that
+ * uses the state on other streams must be complete.  NULL is a no-op. */
+PVW_API int32_t pvw_rnd_state_free(void* st);
+/* call_seed(seed, counter) on the host (no GPU needed) */
+PVW_API int32_t pvw_rnd_call_seed(const uint8_t seed[32], uint64_t counter, uint8_t out[32]);
+/* as pvw_encrypt / pvw_encrypt_device, with the randomness from `st` instead of a pvw_randomness_t */
+PVW_API int32_t pvw_encrypt_rs(pvw_ctx* ctx, const uint64_t* scalars, size_t num_scalars, void* st,
+                               uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr);
+PVW_API int32_t pvw_encrypt_rs_device(pvw_ctx* ctx, const uint64_t* d_scalars, size_t num_scalars, void* st,
+                                      uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream);
+/* as pvw_encrypt_multi / pvw_encrypt_multi_device, with the dealers' seeds derived from `st` */
+PVW_API int32_t pvw_encrypt_multi_rs(pvw_ctx* ctx, const uint64_t* scalars, size_t num_dealers, size_t scalars_per_dealer,
+                                     void* st, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr);
+PVW_API int32_t pvw_encrypt_multi_rs_device(pvw_ctx* ctx, const uint64_t* d_scalars, size_t num_dealers,
+                                            size_t scalars_per_dealer, void* st, uint64_t* d_c1, uint64_t* d_c2,
+                                            uint32_t out_repr, void* stream);
+/* SELF-TEST: 32-bit words of the device seed that were not zero when the calling thread's last pvw_rnd_state_free read
+ * it back after clearing it (0 = cleared).  No product path calls it. */
+PVW_API int32_t pvw_selftest_rnd_free_residue(uint64_t* nonzero_words);
 
 /* ---- decrypt (src/crypto/decryption.rs:249-325) ------------------------------------
  * One secret key against D dealer ciphertexts (decrypt_party_shares :281-325):

@@ -21,7 +21,7 @@ ERROR_NAMES = {
 }
 REPR_POWER, REPR_NTT = 0, 1
 RND_SEED, RND_EXPLICIT = 0, 1
-DOM_R, DOM_E1, DOM_E2, DOM_SK, DOM_EKEY, DOM_CRS, DOM_GAUSS, DOM_PK = range(8)
+DOM_R, DOM_E1, DOM_E2, DOM_SK, DOM_EKEY, DOM_CRS, DOM_GAUSS, DOM_PK, DOM_CALL = range(9)
 PREPARE_PACKED, PREPARE_MFMA = 1, 2
 
 
@@ -73,6 +73,16 @@ _SIGNATURES = {
     "pvw_encrypt_device": [_P, _P, C.c_size_t, C.POINTER(pvw_randomness_t), _P, _P, C.c_uint32, _P],
     "pvw_encrypt_multi": [_P, _P, C.c_size_t, C.c_size_t, _P, _P, _P, C.c_uint32],
     "pvw_encrypt_multi_device": [_P, _P, C.c_size_t, C.c_size_t, _P, _P, _P, C.c_uint32, _P],
+    "pvw_rnd_state_create": [_P, _P, C.c_uint64, C.POINTER(_P)],
+    "pvw_rnd_state_counter": [_P, _P, C.POINTER(C.c_uint64)],
+    "pvw_rnd_state_set_counter": [_P, C.c_uint64, _P],
+    "pvw_rnd_state_free": [_P],
+    "pvw_rnd_call_seed": [_P, C.c_uint64, _P],
+    "pvw_encrypt_rs": [_P, _P, C.c_size_t, _P, _P, _P, C.c_uint32],
+    "pvw_encrypt_rs_device": [_P, _P, C.c_size_t, _P, _P, _P, C.c_uint32, _P],
+    "pvw_encrypt_multi_rs": [_P, _P, C.c_size_t, C.c_size_t, _P, _P, _P, C.c_uint32],
+    "pvw_encrypt_multi_rs_device": [_P, _P, C.c_size_t, C.c_size_t, _P, _P, _P, C.c_uint32, _P],
+    "pvw_selftest_rnd_free_residue": [C.POINTER(C.c_uint64)],
     "pvw_decrypt_batch": [_P, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P],
     "pvw_decrypt_noisy_device": [_P, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P],
     "pvw_decrypt_batch_device": [_P, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P],

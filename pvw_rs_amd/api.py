@@ -587,16 +587,32 @@ def _randomness(params: PvwParameters, seed, r, e1, e2):
     return rnd, keep
 
 
+def _check_state(p: "PvwParameters", randomness: "DeviceRandomness", seed, explicit=False) -> None:
+    if not isinstance(randomness, DeviceRandomness):
+        raise PvwError(1, "randomness must be a DeviceRandomness")
+    if seed is not None or explicit:
+        raise PvwError(1, "give either a seed / explicit randomness or a DeviceRandomness, not both")
+    if randomness._h is None:
+        raise PvwError(1, "the DeviceRandomness has been freed")
+    if randomness._lib is not p._lib:
+        raise PvwError(1, "the DeviceRandomness was created through another build of the library")
+
+
 def encrypt(scalars: Sequence[int], global_pk: GlobalPublicKey, seed: Optional[bytes] = None, *,
-            r=None, e1=None, e2=None, repr: int = REPR_NTT) -> PvwCiphertext:
-    """encrypt (encryption.rs:105-214)."""
+            r=None, e1=None, e2=None, repr: int = REPR_NTT, randomness: Optional["DeviceRandomness"] = None) -> PvwCiphertext:
+    """encrypt (encryption.rs:105-214).  `randomness`: draw from that DeviceRandomness (seed call_seed(S, c), then c + 1)
+    instead of `seed` / explicit r, e1, e2."""
     p = global_pk.params
     sc = np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in scalars], dtype=np.uint64)
-    rnd, keep = _randomness(p, seed, r, e1, e2)
     c1 = np.zeros((p.k, p.L, p.l), dtype=np.uint64)
     c2 = np.zeros((p.n, p.L, p.l), dtype=np.uint64)
-    p._call("pvw_encrypt", _ptr(sc), len(sc), C.byref(rnd), _ptr(c1), _ptr(c2), repr)
-    del keep
+    if randomness is not None:
+        _check_state(p, randomness, seed, r is not None or e1 is not None or e2 is not None)
+        p._call("pvw_encrypt_rs", _ptr(sc), len(sc), randomness._h, _ptr(c1), _ptr(c2), repr)
+    else:
+        rnd, keep = _randomness(p, seed, r, e1, e2)
+        p._call("pvw_encrypt", _ptr(sc), len(sc), C.byref(rnd), _ptr(c1), _ptr(c2), repr)
+        del keep
     ct = PvwCiphertext(c1, c2, p, repr)
     ct.validate()                                                          # :204-211
     return ct
@@ -623,10 +639,12 @@ def _dealer_seed(seed: bytes, dealer: int) -> bytes:
 
 
 def encrypt_all_party_shares(all_shares: Sequence[Sequence[int]], global_pk: GlobalPublicKey,
-                             seed: bytes, repr: int = REPR_NTT) -> List[PvwCiphertext]:
+                             seed: Optional[bytes] = None, repr: int = REPR_NTT, *,
+                             randomness: Optional["DeviceRandomness"] = None) -> List[PvwCiphertext]:
     """encrypt_all_party_shares (encryption.rs:253-286): one batched device call; dealers share
     passes over the public key four at a time (pvw_encrypt_multi).  Dealer d uses
-    `_dealer_seed(seed, d)`, so the result equals d separate `encrypt_party_shares` calls."""
+    `_dealer_seed(seed, d)`, so the result equals d separate `encrypt_party_shares` calls.
+    `randomness` instead of `seed`: dealer d uses call_seed(S, c + d) of that DeviceRandomness, which then holds c + n."""
     p = global_pk.params
     n = p.n
     if len(all_shares) != n:
@@ -634,6 +652,16 @@ def encrypt_all_party_shares(all_shares: Sequence[Sequence[int]], global_pk: Glo
     for dealer_idx, dealer_shares in enumerate(all_shares):
         if len(dealer_shares) != n:
             raise PvwError(1, f"Dealer {dealer_idx} provided {len(dealer_shares)} shares but needs {n}")
+    if randomness is not None:
+        _check_state(p, randomness, seed)
+        sc = np.array([[int(s) & 0xFFFFFFFFFFFFFFFF for s in row] for row in all_shares], dtype=np.uint64)
+        D = sc.shape[0]
+        c1 = np.zeros((D, p.k, p.L, p.l), dtype=np.uint64)
+        c2 = np.zeros((D, p.n, p.L, p.l), dtype=np.uint64)
+        p._call("pvw_encrypt_multi_rs", _ptr(sc), D, sc.shape[1], randomness._h, _ptr(c1), _ptr(c2), repr)
+        return [PvwCiphertext(c1[d], c2[d], p, repr) for d in range(D)]
+    if seed is None:
+        raise PvwError(1, "encrypt_all_party_shares needs a 32-byte seed or a DeviceRandomness")
     return encrypt_many(all_shares, global_pk, [_dealer_seed(seed, d) for d in range(len(all_shares))], repr)
 
 
@@ -654,7 +682,7 @@ def encrypt_many(all_scalars: Sequence[Sequence[int]], global_pk: GlobalPublicKe
     return [PvwCiphertext(c1[d], c2[d], p, repr) for d in range(D)]
 
 
-def encrypt_broadcast(scalar: int, global_pk: GlobalPublicKey, seed: bytes, **kw) -> PvwCiphertext:
+def encrypt_broadcast(scalar: int, global_pk: GlobalPublicKey, seed: Optional[bytes] = None, **kw) -> PvwCiphertext:
     """encryption.rs:292-296."""
     return encrypt([scalar] * global_pk.params.n, global_pk, seed, **kw)
 
@@ -754,6 +782,79 @@ class DeviceSecretKey:
             self.free()
         except Exception:
             pass
+
+
+def _stream_ptr(stream):
+    """a torch stream (its .cuda_stream), a raw hipStream_t as an int, or None (the state's own stream)"""
+    if stream is None:
+        return None
+    return C.c_void_p(int(getattr(stream, "cuda_stream", stream)) or None)
+
+
+class DeviceRandomness:
+    """pvw_rnd_state: a 32-byte seed S and a 64-bit counter c on the device.  Encrypts given `randomness=` (or the
+    *_rs_device calls) read it when their kernels run and advance c themselves -- c + 1 per single encrypt, c + D per
+    D-dealer encrypt -- so calls captured into a graph draw fresh randomness on every replay, as the reference's
+    thread_rng() does on every encrypt (encryption.rs:135-167).  Calls on one stream at a time.  Freed (the device seed
+    cleared first) by free(), on leaving a `with` block, or when dropped; always through the library that created it."""
+
+    def __init__(self, params: "PvwParameters", seed: bytes, counter: int = 0):
+        self.params = params                     # keeps the context (whose stream the state records) alive
+        self._lib = params._lib
+        self._h = None
+        h = C.c_void_p()
+        sd = _seed(seed)
+        params._call("pvw_rnd_state_create", _ptr(sd), int(counter) & 0xFFFFFFFFFFFFFFFF, C.byref(h))
+        sd.fill(0)
+        self._h = h
+
+    @staticmethod
+    def call_seed(seed: bytes, counter: int) -> bytes:
+        """call_seed(S, c): the seed a call that runs at counter c draws from (host only, no GPU)."""
+        sd = _seed(seed)
+        out = np.zeros(32, dtype=np.uint8)
+        _check(_ffi.lib().pvw_rnd_call_seed(_ptr(sd), int(counter) & 0xFFFFFFFFFFFFFFFF, _ptr(out)))
+        return out.tobytes()
+
+    def _handle(self):
+        if self._h is None:
+            raise PvwError(1, "the DeviceRandomness has been freed")
+        return self._h
+
+    def counter(self, stream=None) -> int:
+        """the counter once the work enqueued on `stream` (default: the context's stream) is done; waits for it"""
+        v = C.c_uint64(0)
+        _check(self._lib.pvw_rnd_state_counter(self._handle(), _stream_ptr(stream), C.byref(v)), self._lib)
+        return int(v.value)
+
+    def set_counter(self, counter: int, stream=None) -> None:
+        """stream-ordered write of the counter"""
+        _check(self._lib.pvw_rnd_state_set_counter(self._handle(), int(counter) & 0xFFFFFFFFFFFFFFFF, _stream_ptr(stream)),
+               self._lib)
+
+    def free(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            _check(self._lib.pvw_rnd_state_free(h), self._lib)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _rnd_free_residue(lib=None) -> int:
+    """SELF-TEST: seed words the calling thread's last DeviceRandomness.free() found not cleared (0 = cleared)"""
+    v = C.c_uint64(0)
+    _check((lib or _ffi.lib()).pvw_selftest_rnd_free_residue(C.byref(v)), lib)
+    return int(v.value)
 
 
 def _decrypt_batch(p, cts, secret_key, party_index, return_noisy=False):

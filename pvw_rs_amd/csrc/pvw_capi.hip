@@ -1519,8 +1519,11 @@ static int32_t fill_encrypt_jobs(pvw_ctx* c, PrologueBatch& pb, u32 slot, u32 /*
 // all pointers are device pointers; explicit r/e1/e2 are GLOBAL arrays ([k][l], [k][l], [n][l])
 // out_c1 / out_c2 != NULL: the MAC stores its results there (device-visible HOST memory of a caller whose buffers are
 // pinned) while the addends stay in d_c1 / d_c2; NTT-domain output only
+// rs != NULL: the randomness comes from that device state (rnd is then a PVW_RND_SEED placeholder whose seed is not read):
+// the prologue derives the key from it when it runs, and the MAC advances its counter by one
 static int32_t encrypt_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, const pvw_randomness_t* rnd,
-                               u64* d_c1, u64* d_c2, uint32_t out_repr, hipStream_t s, u64* out_c1 = nullptr, u64* out_c2 = nullptr) {
+                               u64* d_c1, u64* d_c2, uint32_t out_repr, hipStream_t s, u64* out_c1 = nullptr, u64* out_c2 = nullptr,
+                               RndState* rs = nullptr) {
   const u32 k = c->k, l = c->l, L = c->L, rA = c->rowsA(), rB = c->rowsB();
   if (!out_c1) out_c1 = d_c1;
   if (!out_c2) out_c2 = d_c2;
@@ -1532,6 +1535,7 @@ static int32_t encrypt_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, c
   const u32 width = ensure_packed(c, s, !capturing);
   PrologueBatch pb{};
   PVW_TRY(fill_encrypt_jobs(c, pb, 0, 0, rnd, d_scalars, w->rhat, d_c1, d_c2));
+  pb.rnd = rs;
   // l <= 16: the addends travel in COMPACT form -- the prologue transforms r only and leaves the sampled e1 / e2 coefficients as
   // they are (8 l bytes per row instead of 8 L l written and read back); the MAC workgroups transform their own rows' e and add
   // m g-hat (MacSection::e_small, mac_small_addend).  Explicit randomness: the caller's e1 / e2 arrays ARE the compact form.
@@ -1565,6 +1569,10 @@ static int32_t encrypt_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, c
       a.e_small = es1;
       b.e_small = es2;
       b.scalars = d_scalars + c->party_lo;
+    }
+    if (rs) {
+      a.rnd_ctr = &rs->counter;                          // the prologue in front of this launch was the state's reader
+      a.rnd_adv = 1;
     }
     if (width) PVW_HIP(launch_mac_rows_packed(a, b, w->rhat, c->dt, k, L, l, width, s));   // the same sums over the packed copy
     else PVW_HIP(launch_mac_rows(a, b, w->rhat, c->dt, k, L, l, s));                       // crs.rs:188-201, encryption.rs:177-200
@@ -1643,15 +1651,48 @@ int32_t pvw_encrypt(pvw_ctx* c, const uint64_t* scalars, size_t num_scalars, con
 }
 
 // ------------------------------------------------------------------------ multi-dealer encrypt
+static bool multi_uses_gemm(size_t D) {
+  const int gemm_min = (int)PVW_ENV_INT("PVW_GEMM_MIN_DEALERS", 3);   // tuning build: read per call (tests switch it); measured at config 3: 2 dealers 0.23 ms on the VALU vs 0.25 here, 4 dealers 0.43 vs 0.26, 6 dealers 0.67 vs 0.31
+  return gemm_min > 0 && D >= (size_t)gemm_min;
+}
+static bool stream_capturing(hipStream_t s) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  const bool capturing = hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+  (void)hipGetLastError();
+  return capturing;
+}
+// A device-pointer multi-dealer call made under stream capture may not allocate or wait: on the matrix cores it needs the
+// MFMA copies and the stream's GEMM buffers that pvw_prepare(PVW_PREPARE_MFMA) builds.  Checked before the stream's workspace
+// is looked up (a first call on a stream would allocate it) and before anything is enqueued, so the capture stays intact.
+static int32_t multi_capture_check(pvw_ctx* c, hipStream_t s, size_t D) {
+  if (!multi_uses_gemm(D) || !stream_capturing(s)) return PVW_OK;
+  bool ready;
+  {
+    std::lock_guard<std::mutex> g(c->init_mu);
+    ready = c->xm_valid;
+  }
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    auto it = c->async_ws.find((void*)s);
+    const Workspace* w = it == c->async_ws.end() ? nullptr : it->second;
+    ready = ready && w && w->vhat16 && w->yd && w->sy && (w->gtmpA || !c->rowsA()) && (w->gtmpB || !c->rowsB());
+  }
+  if (!ready)
+    return fail(PVW_ERR_INVALID_PARAMETERS, "multi-dealer encrypt under stream capture: call pvw_prepare(PVW_PREPARE_MFMA) on "
+                                            "this stream first (and again after the matrices change)");
+  return PVW_OK;
+}
+
 // encrypt_all_party_shares (encryption.rs:253-286): dealer d encrypts scalars[d][0..n) with its own
 // randomness (seed d).  Groups of 4 dealers share one pass over A-hat / B-hat (mac_rows_multi).
 // Device layout: d_scalars [D][n]; d_c1 [D][rowsA][L][l]; d_c2 [D][rowsB][L][l].
+// rs != NULL: dealer d's seed is call_seed(S, c + d) of that device state instead of seeds + 32 d (seeds is not read), with
+// c the counter when the call's kernels run; the call's last kernel advances the counter by D.
 static int32_t encrypt_multi_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, const uint8_t* seeds,
-                                     size_t D, u64* d_c1, u64* d_c2, uint32_t out_repr, hipStream_t s) {
+                                     size_t D, u64* d_c1, u64* d_c2, uint32_t out_repr, hipStream_t s, RndState* rs = nullptr) {
   const u32 k = c->k, l = c->l, L = c->L, rA = c->rowsA(), rB = c->rowsB();
   const size_t P = c->poly();
-  const int gemm_min = (int)PVW_ENV_INT("PVW_GEMM_MIN_DEALERS", 3);   // tuning build: read per call (tests switch it); measured at config 3: 2 dealers 0.23 ms on the VALU vs 0.25 here, 4 dealers 0.43 vs 0.26, 6 dealers 0.67 vs 0.31
-  const bool use_gemm = gemm_min > 0 && D >= (size_t)gemm_min;
+  const bool use_gemm = multi_uses_gemm(D);
   if (use_gemm) {
     PVW_TRY(ws_gemm_buffers(c, w));
     PVW_TRY(ensure_xm(c, s));
@@ -1670,10 +1711,15 @@ static int32_t encrypt_multi_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scal
       PrologueBatch pb{};
       pvw_randomness_t rnd{};
       rnd.mode = PVW_RND_SEED;
-      memcpy(rnd.seed, seeds + d * 32, 32);
+      if (!rs) memcpy(rnd.seed, seeds + d * 32, 32);
       PVW_TRY(fill_encrypt_jobs(c, pb, 0, 0, &rnd, d_scalars + d * c->n, vh + (size_t)v0 * k * P,
                                 d_c1 + d * rA * P, d_c2 + d * rB * P));
-      for (u32 x = 0; x < cnt; ++x) pb.key[x] = make_key(seeds + (d + x) * 32);
+      if (rs) {
+        pb.rnd = rs;                                            // replica x: call_seed(S, counter + d + x)
+        pb.rnd_off = d;
+      } else {
+        for (u32 x = 0; x < cnt; ++x) pb.key[x] = make_key(seeds + (d + x) * 32);
+      }
       pb.job[0].rep_key = pb.job[1].rep_key = pb.job[2].rep_key = 1;
       pb.job[0].rep_out = (size_t)k * P;                       // r-hat vectors
       pb.job[1].rep_out = (size_t)rA * P;                      // c1 planes
@@ -1686,6 +1732,7 @@ static int32_t encrypt_multi_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scal
     }
     u64* c1g = d_c1 + d0 * rA * P;
     u64* c2g = d_c2 + d0 * rB * P;
+    const bool last = d0 + nv == D;                             // its last kernel advances the randomness state
     if (use_gemm) {
       {
         ProfScope ps(c, "vec_digits", s);
@@ -1699,7 +1746,12 @@ static int32_t encrypt_multi_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scal
         for (u32 v0 = 0; v0 < nv; v0 += PVW_MAX_PROLOGUE_KEYS) {
           GemmErrSource e{};
           e.span = (nv - v0) < PVW_MAX_PROLOGUE_KEYS ? (nv - v0) : PVW_MAX_PROLOGUE_KEYS;
-          for (u32 x = 0; x < e.span; ++x) e.key[x] = make_key(seeds + (d0 + v0 + x) * 32);
+          if (rs) {
+            e.rnd = rs;                                         // vector x: call_seed(S, base + d0 + v0 + x)
+            e.rnd_off = d0 + v0;
+          } else {
+            for (u32 x = 0; x < e.span; ++x) e.key[x] = make_key(seeds + (d0 + v0 + x) * 32);
+          }
           e.key_v = 1;
           e.domain = DOM_E2; e.index0 = c->party_lo; e.index_row = 1; e.index_v = 0; e.bound = c->b2;
           e.scalars = d_scalars + d0 * c->n + c->party_lo; e.scalar_v = c->n;
@@ -1707,11 +1759,20 @@ static int32_t encrypt_multi_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scal
         }
         b.addend = nullptr;
       }
+      if (rs && last) {
+        GemmSection& fin = rB ? b : a;                          // the finish pass launched last
+        fin.rnd_ctr = &rs->counter;
+        fin.rnd_adv = D;
+      }
       PVW_HIP(launch_gemm_digits(a, b, w->yd, w->sy, c->dt, k, L, l, nv, (size_t)rA * P, (size_t)rB * P, s, nullptr, fused_e2 ? es.data() : nullptr, c->xm_bytes));
     } else {
       ProfScope ps(c, "mac_rows_multi", s);
       MacSection a{c->dA, c1g, c1g, rA, 0}, b{c->dB, c2g, c2g, rB, 0};
       MultiVec mv{vh, (size_t)k * P, (size_t)rA * P, (size_t)rB * P, nv};
+      if (rs && last) {
+        a.rnd_ctr = &rs->counter;
+        a.rnd_adv = D;
+      }
       PVW_HIP(launch_mac_rows_multi(a, b, mv, c->dt, k, L, l, s));
     }
   }
@@ -1746,16 +1807,24 @@ int32_t pvw_encrypt_multi_device(pvw_ctx* c, const uint64_t* d_scalars, size_t n
   PVW_TRY(encrypt_multi_checks(c, num_dealers, scalars_per_dealer, out_repr));
   PVW_TRY(ensure_device(c));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  PVW_TRY(multi_capture_check(c, s, num_dealers));
   Workspace* w;
   PVW_TRY(ws_for_stream(c, s, &w));
   return encrypt_multi_enqueue(c, w, d_scalars, seeds, num_dealers, d_c1, d_c2, out_repr, s);
 }
 
+static int32_t encrypt_multi_host(pvw_ctx* c, const uint64_t* scalars, size_t num_dealers, const uint8_t* seeds, RndState* rs,
+                                  uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr);
 int32_t pvw_encrypt_multi(pvw_ctx* c, const uint64_t* scalars, size_t num_dealers, size_t scalars_per_dealer,
                           const uint8_t* seeds, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
   if (!c || !scalars || !seeds || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   PVW_TRY(encrypt_multi_checks(c, num_dealers, scalars_per_dealer, out_repr));
   PVW_TRY(ensure_device(c));
+  return encrypt_multi_host(c, scalars, num_dealers, seeds, nullptr, c1_out, c2_out, out_repr);
+}
+// host buffers, staged in passes of `per` dealers (seeds, or the device randomness state rs, which each pass advances)
+static int32_t encrypt_multi_host(pvw_ctx* c, const uint64_t* scalars, size_t num_dealers, const uint8_t* seeds, RndState* rs,
+                                  uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
   const size_t P = c->poly(), rA = c->rowsA(), rB = c->rowsB(), n = c->n;
   Workspace* w;
   PVW_TRY(ws_acquire(c, &w));
@@ -1775,7 +1844,7 @@ int32_t pvw_encrypt_multi(pvw_ctx* c, const uint64_t* scalars, size_t num_dealer
     u64* d_c1 = (u64*)(base + b_sc);
     u64* d_c2 = (u64*)(base + b_sc + b_c1);
     if (hipMemcpyAsync(d_sc, scalars + d0 * n, cnt * n * 8, hipMemcpyHostToDevice, w->stream) != hipSuccess) { rc = fail(PVW_ERR_INTERNAL, "H2D failed"); break; }
-    rc = encrypt_multi_enqueue(c, w, d_sc, seeds + d0 * 32, cnt, d_c1, d_c2, out_repr, w->stream);
+    rc = encrypt_multi_enqueue(c, w, d_sc, seeds ? seeds + d0 * 32 : nullptr, cnt, d_c1, d_c2, out_repr, w->stream, rs);
     for (size_t d = 0; rc == PVW_OK && d < cnt; ++d) {
       // a sharded context writes its rows at their global positions inside each dealer's block
       if (hipMemcpyAsync(c1_out + ((d0 + d) * c->k + c->c1_lo) * P, d_c1 + d * rA * P, rA * P * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
@@ -1786,6 +1855,172 @@ int32_t pvw_encrypt_multi(pvw_ctx* c, const uint64_t* scalars, size_t num_dealer
   }
   ws_release(c, w);
   return rc;
+}
+
+// ------------------------------------------------------------------------ device randomness state
+// The reference draws fresh randomness on every encrypt (encryption.rs:135-167, thread_rng()).  A state on the device
+// (seed S, counter c) gives calls that are captured into a graph, or queued asynchronously, the same property: the kernels
+// derive call_seed(S, c + i) when they run and advance c themselves.  The handle records the device and the stream of the
+// context it was created for and never reads the context again.
+struct pvw_rnd_state {
+  int device;
+  hipStream_t stream;   // the creating context's stream: NULL stream arguments and the clearing in pvw_rnd_state_free
+  RndState* dev;
+};
+static thread_local uint64_t g_rnd_free_residue = 0;   // pvw_selftest_rnd_free_residue
+
+int32_t pvw_rnd_call_seed(const uint8_t seed[32], uint64_t counter, uint8_t out[32]) {
+  if (!seed || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const ChaChaKey s = make_key(seed);
+  const ChaChaKey k = call_seed(s.w, counter);
+  for (int i = 0; i < 8; ++i)
+    for (int b = 0; b < 4; ++b) out[4 * i + b] = (uint8_t)(k.w[i] >> (8 * b));
+  return PVW_OK;
+}
+
+int32_t pvw_rnd_state_create(pvw_ctx* c, const uint8_t seed[32], uint64_t counter, void** out) {
+  if (!c || !seed || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  *out = nullptr;
+  PVW_TRY(ensure_device(c));
+  if (stream_capturing(c->stream)) return fail(PVW_ERR_INVALID_PARAMETERS, "pvw_rnd_state_create allocates: not under stream capture");
+  RndState h{};
+  const ChaChaKey k = make_key(seed);
+  for (int i = 0; i < 8; ++i) h.seed[i] = k.w[i];
+  h.counter = h.base = counter;
+  pvw_rnd_state* st = new pvw_rnd_state{c->device, c->stream, nullptr};
+  hipError_t e = hipMalloc((void**)&st->dev, sizeof(RndState));
+  if (e == hipSuccess) e = hipMemcpyAsync(st->dev, &h, sizeof h, hipMemcpyHostToDevice, st->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(st->stream);
+  memset(&h, 0, sizeof h);
+  if (e != hipSuccess) {
+    if (st->dev) { (void)hipMemset(st->dev, 0, sizeof(RndState)); hipFree(st->dev); }
+    delete st;
+    (void)hipGetLastError();
+    return fail(PVW_ERR_INTERNAL, std::string("creating the randomness state failed: ") + hipGetErrorString(e));
+  }
+  *out = st;
+  return PVW_OK;
+}
+
+int32_t pvw_rnd_state_counter(void* handle, void* stream, uint64_t* out) {
+  pvw_rnd_state* st = (pvw_rnd_state*)handle;
+  if (!st || !st->dev || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  hipStream_t s = stream ? (hipStream_t)stream : st->stream;
+  PVW_HIP(hipSetDevice(st->device));
+  if (stream_capturing(s)) return fail(PVW_ERR_INVALID_PARAMETERS, "pvw_rnd_state_counter waits for its stream: not under stream capture");
+  uint64_t v = 0;
+  PVW_HIP(hipMemcpyAsync(&v, &st->dev->counter, sizeof v, hipMemcpyDeviceToHost, s));
+  PVW_HIP(hipStreamSynchronize(s));
+  *out = v;
+  return PVW_OK;
+}
+
+int32_t pvw_rnd_state_set_counter(void* handle, uint64_t counter, void* stream) {
+  pvw_rnd_state* st = (pvw_rnd_state*)handle;
+  if (!st || !st->dev) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  hipStream_t s = stream ? (hipStream_t)stream : st->stream;
+  PVW_HIP(hipSetDevice(st->device));
+  PVW_HIP(launch_rnd_set_counter(st->dev, counter, s));   // the value travels as a kernel argument: capturable, no host buffer
+  return PVW_OK;
+}
+
+int32_t pvw_rnd_state_free(void* handle) {
+  pvw_rnd_state* st = (pvw_rnd_state*)handle;
+  if (!st) return PVW_OK;
+  int32_t rc = PVW_OK;
+  if (st->dev) {
+    u32 back[8];
+    memset(back, 0xff, sizeof back);
+    if (hipSetDevice(st->device) != hipSuccess || hipMemsetAsync(st->dev, 0, sizeof(RndState), st->stream) != hipSuccess ||
+        hipMemcpyAsync(back, st->dev->seed, sizeof back, hipMemcpyDeviceToHost, st->stream) != hipSuccess ||
+        hipStreamSynchronize(st->stream) != hipSuccess) {
+      (void)hipGetLastError();
+      rc = fail(PVW_ERR_INTERNAL, "clearing the randomness state failed");
+    }
+    g_rnd_free_residue = 0;
+    for (u32 x : back) g_rnd_free_residue += x != 0;
+    hipFree(st->dev);
+  }
+  delete st;
+  return rc;
+}
+
+int32_t pvw_selftest_rnd_free_residue(uint64_t* nonzero_words) {
+  if (!nonzero_words) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  *nonzero_words = g_rnd_free_residue;
+  return PVW_OK;
+}
+
+// after the argument checks of the call (the handle itself is not read before them)
+static int32_t rnd_state_checks(const pvw_ctx* c, const pvw_rnd_state* st) {
+  if (!st->dev) return fail(PVW_ERR_INVALID_PARAMETERS, "randomness state has been freed");
+  if (c->rowsA() == 0 && c->rowsB() == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "the context holds no rows to encrypt");
+  if (c->device >= 0 && st->device != c->device) return fail(PVW_ERR_INVALID_PARAMETERS, "the randomness state lives on another device");
+  return PVW_OK;
+}
+
+int32_t pvw_encrypt_rs_device(pvw_ctx* c, const uint64_t* d_scalars, size_t num_scalars, void* handle, uint64_t* d_c1,
+                              uint64_t* d_c2, uint32_t out_repr, void* stream) {
+  pvw_rnd_state* st = (pvw_rnd_state*)handle;
+  if (!c || !d_scalars || !st || (!d_c1 && c->rowsA()) || (!d_c2 && c->rowsB())) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  pvw_randomness_t rnd{};
+  rnd.mode = PVW_RND_SEED;
+  PVW_TRY(encrypt_checks(c, num_scalars, &rnd, out_repr));
+  PVW_TRY(ensure_device(c));
+  PVW_TRY(rnd_state_checks(c, st));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  Workspace* w;
+  PVW_TRY(ws_for_stream(c, s, &w));
+  return encrypt_enqueue(c, w, d_scalars, &rnd, d_c1, d_c2, out_repr, s, nullptr, nullptr, st->dev);
+}
+
+int32_t pvw_encrypt_rs(pvw_ctx* c, const uint64_t* scalars, size_t num_scalars, void* handle, uint64_t* c1_out,
+                       uint64_t* c2_out, uint32_t out_repr) {
+  pvw_rnd_state* st = (pvw_rnd_state*)handle;
+  if (!c || !scalars || !st || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  pvw_randomness_t rnd{};
+  rnd.mode = PVW_RND_SEED;
+  PVW_TRY(encrypt_checks(c, num_scalars, &rnd, out_repr));
+  PVW_TRY(ensure_device(c));
+  PVW_TRY(rnd_state_checks(c, st));
+  const size_t P = c->poly();
+  Workspace* w;
+  PVW_TRY(ws_acquire(c, &w));
+  int32_t rc = ws_host_buffers(c, w);
+  if (rc == PVW_OK && hipMemcpyAsync(w->scalars, scalars, (size_t)c->n * 8, hipMemcpyHostToDevice, w->stream) != hipSuccess)
+    rc = fail(PVW_ERR_INTERNAL, "H2D failed");
+  if (rc == PVW_OK) rc = encrypt_enqueue(c, w, w->scalars, &rnd, w->c1, w->c2, out_repr, w->stream, nullptr, nullptr, st->dev);
+  if (rc == PVW_OK &&
+      (hipMemcpyAsync(c1_out + (size_t)c->c1_lo * P, w->c1, (size_t)c->rowsA() * P * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
+       hipMemcpyAsync(c2_out + (size_t)c->party_lo * P, w->c2, (size_t)c->rowsB() * P * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess))
+    rc = fail(PVW_ERR_INTERNAL, "D2H failed");
+  if (hipStreamSynchronize(w->stream) != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
+  ws_release(c, w);
+  return rc;
+}
+
+int32_t pvw_encrypt_multi_rs_device(pvw_ctx* c, const uint64_t* d_scalars, size_t num_dealers, size_t scalars_per_dealer,
+                                    void* handle, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
+  pvw_rnd_state* st = (pvw_rnd_state*)handle;
+  if (!c || !d_scalars || !st || (!d_c1 && c->rowsA()) || (!d_c2 && c->rowsB())) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(encrypt_multi_checks(c, num_dealers, scalars_per_dealer, out_repr));
+  PVW_TRY(ensure_device(c));
+  PVW_TRY(rnd_state_checks(c, st));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  PVW_TRY(multi_capture_check(c, s, num_dealers));
+  Workspace* w;
+  PVW_TRY(ws_for_stream(c, s, &w));
+  return encrypt_multi_enqueue(c, w, d_scalars, nullptr, num_dealers, d_c1, d_c2, out_repr, s, st->dev);
+}
+
+int32_t pvw_encrypt_multi_rs(pvw_ctx* c, const uint64_t* scalars, size_t num_dealers, size_t scalars_per_dealer,
+                             void* handle, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+  pvw_rnd_state* st = (pvw_rnd_state*)handle;
+  if (!c || !scalars || !st || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(encrypt_multi_checks(c, num_dealers, scalars_per_dealer, out_repr));
+  PVW_TRY(ensure_device(c));
+  PVW_TRY(rnd_state_checks(c, st));
+  return encrypt_multi_host(c, scalars, num_dealers, nullptr, st->dev, c1_out, c2_out, out_repr);
 }
 
 // ------------------------------------------------------------------------ decode (host, integers)

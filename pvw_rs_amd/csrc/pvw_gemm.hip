@@ -857,6 +857,7 @@ __global__ __launch_bounds__(256) void gemm_finish_kernel(GemmSection sec, const
   constexpr int VPB = PVW_FINISH_VPB, PT = 32 * ELL / 256 ? 32 * ELL / 256 : 1;   // elements per thread per tile
   static_assert(sizeof(u64) * VPB * ELL * 33 <= 48 * 1024 || ELL > 32, "finish tiles");
   __shared__ u64 tile[VPB][ELL][33];
+  rnd_advance(sec.rnd_ctr, sec.rnd_adv);
   const u32 rb = blockIdx.x, v0 = blockIdx.y * VPB, limb = blockIdx.z;
   const u32 row0 = rb * 32;
   u64 in[VPB][PT];
@@ -946,7 +947,17 @@ __global__ __launch_bounds__(32 * VPB) void gemm_finish_err_kernel(GemmSection s
   // every lane stays: a lane past the end still carries 16-byte pieces of its neighbours' rows to memory
   const bool v_ok = v_raw < v_hi;
   const u32 row = row_raw < sec.nrows ? row_raw : sec.nrows - 1, v = v_ok ? v_raw : v_hi - 1;
+  rnd_advance(sec.rnd_ctr, sec.rnd_adv);                         // reads `base` below, never the counter
   i64 c[ELL];
+  // device randomness state: the key of each of the block's VPB vectors is derived ONCE, by the first lane of the
+  // half-wave that works on it, into LDS (one ChaCha8 block per (workgroup, vector) instead of one per thread)
+  __shared__ ChaChaKey vkey[VPB];
+  if (es.rnd && !es.explicit_coeffs) {
+    if ((tid & 31) == 0) vkey[tid >> 5] = call_seed(es.rnd->seed, es.rnd->base + es.rnd_off + (u64)(v - v_lo) * es.key_v);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();                             // the two half-waves of a wave read their own keys only
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
   {
     i64* o = coef + tid * CST;
     if (es.explicit_coeffs) {
@@ -955,7 +966,7 @@ __global__ __launch_bounds__(32 * VPB) void gemm_finish_err_kernel(GemmSection s
       for (int sl = 0; sl < ELL; sl += 2) *reinterpret_cast<v2u64*>(o + sl) = *reinterpret_cast<const v2u64*>(ec + sl);
     } else {
       ChaChaRng g;
-      g.init(es.key[(v - v_lo) * es.key_v], es.domain, es.index0 + row * es.index_row + v * es.index_v);
+      g.init(es.rnd ? vkey[tid >> 5] : es.key[(v - v_lo) * es.key_v], es.domain, es.index0 + row * es.index_row + v * es.index_v);
       auto emit = [o](u32 sl, i64 val) { o[sl] = val; };       // (dynamic index: through LDS, then into registers)
       sample_uniform_poly(g, ELL, es.bound, emit);
     }
@@ -1160,6 +1171,8 @@ hipError_t launch_gemm_digits(const GemmSection& a, const GemmSection& b, const 
       // one launch per GemmErrSource of the array: es[i] covers the next es[i].span vectors (0: all that are left)
       for (u32 v_lo = 0; v_lo < nv; ++es) {
         const u32 span = es->span && es->span < nv - v_lo ? es->span : nv - v_lo, v_hi = v_lo + span;
+        GemmSection sec_l = sec;                               // only the last launch advances a randomness state
+        if (v_hi < nv) sec_l.rnd_ctr = nullptr;
         // 8 vectors per block and the limbs cut into ranges (each range repeats the sampling).  Tuning build, PVW_FINISH_VPB=2:
         // one wave per block (32 rows x 2 vectors) sweeping ALL limbs, so that every error polynomial is drawn ONCE -- measured
         // no better (64 dealers 0.946 vs 0.928 ms per step, key generation 4.17 vs 4.10 ms: profiles/r03_finish_ab.txt): the pass
@@ -1171,9 +1184,9 @@ hipError_t launch_gemm_digits(const GemmSection& a, const GemmSection& b, const 
         if (one_wave) {
           const dim3 grid(gx, (span + 1) / 2, 1);
           switch (ell) {
-            case 8: gemm_finish_err_kernel<8, 2><<<grid, dim3(64), 0, s>>>(sec, t, L, nv, nv_pad, rows_pad, ostride, SY, sy_b16, *es, v_lo, v_hi); break;
-            case 16: gemm_finish_err_kernel<16, 2><<<grid, dim3(64), 0, s>>>(sec, t, L, nv, nv_pad, rows_pad, ostride, SY, sy_b16, *es, v_lo, v_hi); break;
-            default: gemm_finish_err_kernel<32, 2><<<grid, dim3(64), 0, s>>>(sec, t, L, nv, nv_pad, rows_pad, ostride, SY, sy_b16, *es, v_lo, v_hi); break;
+            case 8: gemm_finish_err_kernel<8, 2><<<grid, dim3(64), 0, s>>>(sec_l, t, L, nv, nv_pad, rows_pad, ostride, SY, sy_b16, *es, v_lo, v_hi); break;
+            case 16: gemm_finish_err_kernel<16, 2><<<grid, dim3(64), 0, s>>>(sec_l, t, L, nv, nv_pad, rows_pad, ostride, SY, sy_b16, *es, v_lo, v_hi); break;
+            default: gemm_finish_err_kernel<32, 2><<<grid, dim3(64), 0, s>>>(sec_l, t, L, nv, nv_pad, rows_pad, ostride, SY, sy_b16, *es, v_lo, v_hi); break;
           }
         }
 #endif
@@ -1185,9 +1198,9 @@ hipError_t launch_gemm_digits(const GemmSection& a, const GemmSection& b, const 
           if (lz > L) lz = L;
           const dim3 grid(gx, gy, lz);
           switch (ell) {
-            case 8: gemm_finish_err_kernel<8, 8><<<grid, dim3(256), 0, s>>>(sec, t, L, nv, nv_pad, rows_pad, ostride, SY, sy_b16, *es, v_lo, v_hi); break;
-            case 16: gemm_finish_err_kernel<16, 8><<<grid, dim3(256), 0, s>>>(sec, t, L, nv, nv_pad, rows_pad, ostride, SY, sy_b16, *es, v_lo, v_hi); break;
-            default: gemm_finish_err_kernel<32, 8><<<grid, dim3(256), 0, s>>>(sec, t, L, nv, nv_pad, rows_pad, ostride, SY, sy_b16, *es, v_lo, v_hi); break;
+            case 8: gemm_finish_err_kernel<8, 8><<<grid, dim3(256), 0, s>>>(sec_l, t, L, nv, nv_pad, rows_pad, ostride, SY, sy_b16, *es, v_lo, v_hi); break;
+            case 16: gemm_finish_err_kernel<16, 8><<<grid, dim3(256), 0, s>>>(sec_l, t, L, nv, nv_pad, rows_pad, ostride, SY, sy_b16, *es, v_lo, v_hi); break;
+            default: gemm_finish_err_kernel<32, 8><<<grid, dim3(256), 0, s>>>(sec_l, t, L, nv, nv_pad, rows_pad, ostride, SY, sy_b16, *es, v_lo, v_hi); break;
           }
         }
         v_lo = v_hi;

@@ -23,7 +23,35 @@
 
 namespace pvw {
 
-enum { DOM_R = 0, DOM_E1 = 1, DOM_E2 = 2, DOM_SK = 3, DOM_EKEY = 4, DOM_CRS = 5, DOM_GAUSS = 6, DOM_PK = 7 };
+enum { DOM_R = 0, DOM_E1 = 1, DOM_E2 = 2, DOM_SK = 3, DOM_EKEY = 4, DOM_CRS = 5, DOM_GAUSS = 6, DOM_PK = 7, DOM_CALL = 8 };
+
+// Device randomness state of pvw_rnd_state: the 32-byte seed S and the counter c of the next call.  An encrypt that reads
+// it seeds dealer / call i with call_seed(S, c + i) when its kernels RUN (not when they are enqueued), so graph replays and
+// queued eager calls each draw fresh randomness.  `base` is the counter the running call started from: every prologue that
+// reads the state copies `counter` there (one lane), later readers of the same call (the fused e2 finish pass) read `base`,
+// and one lane of the call's last kernel, which reads neither word, adds the call's advance to `counter`.
+struct RndState {
+  u32 seed[8];
+  u64 counter;
+  u64 base;
+};
+// call_seed(S, c): words 0..7 of the ChaCha8 block keyed by S with block counter c and stream id (DOM_CALL << 32) | 0
+PVW_HD ChaChaKey call_seed(const u32 seed[8], u64 c) {
+  ChaChaKey k;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) k.w[i] = seed[i];
+  ChaChaRng g;
+  g.init(k, DOM_CALL, 0);
+  g.counter = c;
+  g.refill();
+#pragma unroll
+  for (int i = 0; i < 8; ++i) k.w[i] = g.buf[i];
+  return k;
+}
+// one lane of the whole grid adds `adv` to the state's counter (the kernel must not read the counter itself)
+__device__ __forceinline__ void rnd_advance(u64* ctr, u64 adv) {
+  if (ctr && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *ctr += adv;
+}
 
 // per-context device tables (all device pointers)
 struct DevTables {
@@ -69,6 +97,9 @@ struct MacSection {
   // bytes per row cross memory instead of 8 L l written by the prologue and read back here.
   const i64* e_small = nullptr;
   const u64* scalars = nullptr;
+  // not NULL (section a): one lane adds rnd_adv to this RndState counter (the call's last kernel; see RndState)
+  u64* rnd_ctr = nullptr;
+  u64 rnd_adv = 0;
 };
 // group != 0: polynomial p goes to out + (p / group) * stride_group + (p % group) * stride_poly
 hipError_t launch_prep(const i64* coeffs, const u64* scalars, u64* out, size_t stride_poly,
@@ -115,8 +146,14 @@ struct PrologueBatch {   // sizeof must stay below the 4 KiB kernel-argument lim
   u32 reps;    // 0 is read as 1
   u32 total;   // filled in by the launcher (polynomials per replica)
   u32 key_window, key_rep;   // filled in by the launcher: replica r reads keys [r * key_rep, r * key_rep + key_window)
+  // not NULL: key i of replica r is call_seed(S, counter + rnd_off + r * key_rep + i), derived by each workgroup from the
+  // device state when it runs (key[] is not read); block (0, 0) also copies counter to RndState::base
+  RndState* rnd;
+  u64 rnd_off;
 };
 hipError_t launch_prologue(const PrologueBatch& batch, const DevTables& t, u32 L, u32 ell, hipStream_t s);
+// st->counter = counter, ordered on s
+hipError_t launch_rnd_set_counter(RndState* st, u64 counter, hipStream_t s);
 
 // c1 (section a: A-hat rows) and c2 (section b: B-hat rows) in a single launch
 hipError_t launch_mac_rows(const MacSection& a, const MacSection& b, const u64* rhat, const DevTables& t, u32 k, u32 L, u32 ell,
@@ -183,6 +220,9 @@ struct GemmSection {
   u32 tiled_swap = 0;
   // element stride between consecutive GEMM rows in out / addend (0 = one polynomial, L * l)
   size_t row_stride = 0;
+  // not NULL: the finish pass of this section adds rnd_adv to this RndState counter (one lane; see RndState)
+  u64* rnd_ctr = nullptr;
+  u64 rnd_adv = 0;
 };
 inline size_t gemm_tmp_words(u32 rows, u32 L, u32 ell) {
   return (size_t)L * ell * 16 * (((rows + PVW_GEMM_ROWS_PER_WG - 1) / PVW_GEMM_ROWS_PER_WG) * PVW_GEMM_ROWS_PER_WG);
@@ -221,6 +261,10 @@ struct GemmErrSource {
   u64 bound;                        // uniform in [-bound, bound]
   const u64* scalars;               // NULL, or m of (row, v) at scalars[v * scalar_v + row]: + m g-hat (encode_scalar)
   size_t scalar_v;
+  // not NULL: the key of vector v is call_seed(S, base + rnd_off + (v - first vector of this element) * key_v), derived
+  // once per (workgroup, vector) from the device state (key[] is not read)
+  const RndState* rnd;
+  u64 rnd_off;
 };
 hipError_t launch_gemm_digits(const GemmSection& a, const GemmSection& b, const signed char* YD, const int* SY,
                               const DevTables& t, u32 k, u32 L, u32 ell, u32 nv, size_t ostride_a, size_t ostride_b,

@@ -175,6 +175,7 @@ __global__ __launch_bounds__(256) void mac_rows_kernel(MacSection sa, MacSection
   static_assert(JC * HALF >= 64, "the wave partials reuse the r-hat slabs");
   const u32 item = blockIdx.x;
   stamp_begin<STAMP>(item);
+  rnd_advance(sa.rnd_ctr, sa.rnd_adv);                        // randomness state of the encrypt (this kernel does not read it)
   const MacItem it = mac_item(sa, sb, item, L);
   const u32 limb = it.limb;
   const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -318,6 +319,7 @@ __global__ __launch_bounds__(256, PVW_PACKED_WPC) void mac_rows_packed61_kernel(
   __shared__ u64 adl[128];                                    // compact addends of the workgroup's rows (mac_small_addend)
   const u32 item = blockIdx.x;
   stamp_begin<STAMP>(item);
+  rnd_advance(sa.rnd_ctr, sa.rnd_adv);                        // randomness state of the encrypt (this kernel does not read it)
   const MacItem it = mac_item(sa, sb, item, L);
   const u32 limb = it.limb;
   const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -399,6 +401,7 @@ __global__ __launch_bounds__(256, PVW_PACKED_WPC) void mac_rows_packedw_kernel(M
   __shared__ u64 adl[128];                                    // compact addends of the workgroup's rows (mac_small_addend)
   const u32 item = blockIdx.x;
   stamp_begin<STAMP>(item);
+  rnd_advance(sa.rnd_ctr, sa.rnd_adv);                        // randomness state of the encrypt (this kernel does not read it)
   const MacItem it = mac_item(sa, sb, item, L);
   const u32 limb = it.limb;
   const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -529,6 +532,7 @@ __global__ __launch_bounds__(256) void mac_rows_multi_kernel(MacSection sa, MacS
   constexpr int JC = ELL <= 8 ? 16 : (ELL == 16 ? 8 : (ELL == 32 ? 8 : 4));   // LDS = 4*NV*JC*HALF*16 B <= 32 KiB
   constexpr int U = JC < 8 ? JC : 8;
   __shared__ v2u64 lds[4 * NV * JC * HALF];
+  rnd_advance(sa.rnd_ctr, sa.rnd_adv);                        // randomness state of the encrypt (this kernel does not read it)
 
   const u32 limb = blockIdx.x % L;
   const u32 rbg = blockIdx.x / L;

@@ -327,9 +327,20 @@ __global__ __launch_bounds__(256) void prologue_kernel(PrologueBatch b, u32 L, u
     const u32* src = reinterpret_cast<const u32*>(&b.job[0]);
     const u32 nw = b.njobs * JOB_WORDS;
     for (u32 w = tid; w < nw; w += 256) jobw[w] = src[w];
-    const u32* ksrc = reinterpret_cast<const u32*>(&b.key[rep * b.key_rep]);
-    const u32 kw = b.key_window * KEY_WORDS;
-    for (u32 w = tid; w < kw; w += 256) keyw[w] = ksrc[w];
+    if (b.rnd) {
+      // device randomness state: this replica's keys are derived here, one ChaCha8 block per key, straight into LDS
+      if (tid < b.key_window) {
+        const u64 c0 = b.rnd->counter;
+        if (tid == 0 && blockIdx.x == 0 && rep == 0) b.rnd->base = c0;   // what later readers of this call start from
+        const ChaChaKey kd = call_seed(b.rnd->seed, c0 + b.rnd_off + (u64)rep * b.key_rep + tid);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) keyw[tid * KEY_WORDS + i] = kd.w[i];
+      }
+    } else {
+      const u32* ksrc = reinterpret_cast<const u32*>(&b.key[rep * b.key_rep]);
+      const u32 kw = b.key_window * KEY_WORDS;
+      for (u32 w = tid; w < kw; w += 256) keyw[w] = ksrc[w];
+    }
   }
   if (stage_tables && tid >= 64) {
     // the three waves that do not sample bring the twiddle / gadget tables into LDS
@@ -555,6 +566,13 @@ hipError_t launch_prologue(const PrologueBatch& batch, const DevTables& t, u32 L
   const u32 stage = (sc_bytes + tab_bytes + desc_bytes <= 64 * 1024) ? 1u : 0u;
   const size_t lds = sc_bytes + (stage ? tab_bytes : 0) + desc_bytes;
   PVW_DISPATCH_ELL(ell, prologue_kernel<E><<<dim3(blocks, b.reps), dim3(256), lds, s>>>(b, L, PB, stage, t));
+  return hipGetLastError();
+}
+
+// pvw_rnd_state_set_counter: a stream-ordered store whose value is a kernel argument (capturable, no host staging)
+__global__ void rnd_set_counter_kernel(RndState* st, u64 counter) { st->counter = counter; }
+hipError_t launch_rnd_set_counter(RndState* st, u64 counter, hipStream_t s) {
+  rnd_set_counter_kernel<<<dim3(1), dim3(1), 0, s>>>(st, counter);
   return hipGetLastError();
 }
 

@@ -230,6 +230,42 @@ class DeviceSecretKey {
   pvw_sk* key_ = nullptr;
 };
 
+// A randomness state on the device (pvw_rnd_state): seed S and counter c.  Encrypts that take it draw call_seed(S, c + i)
+// when their kernels run and advance c themselves, so captured / queued calls get fresh randomness each time -- what the
+// reference's thread_rng() gives every encrypt (encryption.rs:135-167).  Seeded once from the OS by default.  Ordered by
+// the stream of the calls that use it; cleared and freed when the handle goes.  Keeps its parameters alive.
+class DeviceRandomness {
+ public:
+  DeviceRandomness(const std::shared_ptr<PvwParameters>& p, const Seed& seed, uint64_t counter = 0) : params_(p) {
+    check(pvw_rnd_state_create(params_->ctx, seed.data(), counter, &st_));
+  }
+  explicit DeviceRandomness(const std::shared_ptr<PvwParameters>& p) : DeviceRandomness(p, os_seed()) {}
+  DeviceRandomness(const DeviceRandomness&) = delete;
+  DeviceRandomness& operator=(const DeviceRandomness&) = delete;
+  DeviceRandomness(DeviceRandomness&& o) noexcept : params_(std::move(o.params_)), st_(o.st_) { o.st_ = nullptr; }
+  ~DeviceRandomness() { if (st_) pvw_rnd_state_free(st_); }
+  // the counter once the work enqueued on `stream` (NULL: the context's stream) is done
+  uint64_t counter(void* stream = nullptr) const { uint64_t v = 0; check(pvw_rnd_state_counter(st_, stream, &v)); return v; }
+  void set_counter(uint64_t c, void* stream = nullptr) { check(pvw_rnd_state_set_counter(st_, c, stream)); }
+  // the seed a call that runs at counter c draws from (host only)
+  static Seed call_seed(const Seed& seed, uint64_t c) { Seed out{}; check(pvw_rnd_call_seed(seed.data(), c, out.data())); return out; }
+  void* raw() const { return st_; }
+  const std::shared_ptr<PvwParameters>& params() const { return params_; }
+
+ private:
+  static Seed os_seed() {
+    std::random_device rd;
+    Seed s{};
+    for (size_t i = 0; i < s.size(); i += 4) {
+      const uint32_t w = rd();
+      for (size_t b = 0; b < 4; ++b) s[i + b] = (uint8_t)(w >> (8 * b));
+    }
+    return s;
+  }
+  std::shared_ptr<PvwParameters> params_;
+  void* st_ = nullptr;  // pvw_rnd_state handle
+};
+
 // Party (src/keys/public_key.rs:17-22)
 class Party {
  public:
@@ -301,6 +337,15 @@ inline PvwCiphertext encrypt(const std::vector<uint64_t>& scalars, const GlobalP
   ct.validate();                                                                                     // :204-211
   return ct;
 }
+// the same with the randomness drawn from a DeviceRandomness (call_seed(S, c); the state then holds c + 1)
+inline PvwCiphertext encrypt(const std::vector<uint64_t>& scalars, const GlobalPublicKey& gpk, DeviceRandomness& rnd,
+                             uint32_t repr = PVW_REPR_NTT) {
+  const auto& p = gpk.params;
+  PvwCiphertext ct{std::vector<uint64_t>((size_t)p->k * p->poly_words()), std::vector<uint64_t>((size_t)p->n * p->poly_words()), p, repr};
+  check(pvw_encrypt_rs(p->ctx, scalars.data(), scalars.size(), rnd.raw(), ct.c1.data(), ct.c2.data(), repr));
+  ct.validate();
+  return ct;
+}
 inline Seed dealer_seed(Seed s, uint32_t dealer) {
   for (int i = 0; i < 4; ++i) s[28 + i] ^= (uint8_t)(dealer >> (8 * i));
   return s;
@@ -330,6 +375,28 @@ inline std::vector<PvwCiphertext> encrypt_all_party_shares(const std::vector<std
     std::copy(sd.begin(), sd.end(), seeds.begin() + d * 32);
   }
   check(pvw_encrypt_multi(p->ctx, scalars.data(), D, n, seeds.data(), c1.data(), c2.data(), repr));
+  std::vector<PvwCiphertext> out;
+  for (size_t d = 0; d < D; ++d) {
+    PvwCiphertext ct{std::vector<uint64_t>(c1.begin() + d * p->k * P, c1.begin() + (d + 1) * p->k * P),
+                     std::vector<uint64_t>(c2.begin() + d * n * P, c2.begin() + (d + 1) * n * P), p, repr};
+    ct.validate();
+    out.push_back(std::move(ct));
+  }
+  return out;
+}
+// ... with dealer d's randomness call_seed(S, c + d) of a DeviceRandomness (the state then holds c + n)
+inline std::vector<PvwCiphertext> encrypt_all_party_shares(const std::vector<std::vector<uint64_t>>& all_shares,
+                                                           const GlobalPublicKey& gpk, DeviceRandomness& rnd,
+                                                           uint32_t repr = PVW_REPR_NTT) {
+  const auto& p = gpk.params;
+  if (all_shares.size() != p->n) throw PvwError(1, "Must provide shares for all parties");
+  const size_t D = all_shares.size(), n = p->n, P = p->poly_words();
+  std::vector<uint64_t> scalars(D * n), c1(D * p->k * P), c2(D * n * P);
+  for (size_t d = 0; d < D; ++d) {
+    if (all_shares[d].size() != n) throw PvwError(1, "Party must provide n shares");
+    std::copy(all_shares[d].begin(), all_shares[d].end(), scalars.begin() + d * n);
+  }
+  check(pvw_encrypt_multi_rs(p->ctx, scalars.data(), D, n, rnd.raw(), c1.data(), c2.data(), repr));
   std::vector<PvwCiphertext> out;
   for (size_t d = 0; d < D; ++d) {
     PvwCiphertext ct{std::vector<uint64_t>(c1.begin() + d * p->k * P, c1.begin() + (d + 1) * p->k * P),

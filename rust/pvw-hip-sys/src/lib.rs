@@ -92,6 +92,7 @@ pub const PVW_DOM_EKEY: u32 = 4;
 pub const PVW_DOM_CRS: u32 = 5;
 pub const PVW_DOM_GAUSS: u32 = 6;
 pub const PVW_DOM_PK: u32 = 7;
+pub const PVW_DOM_CALL: u32 = 8;
 
 extern "C" {
     // ---- errors / device ------------------------------------------------------------------
@@ -130,6 +131,16 @@ extern "C" {
     pub fn pvw_encrypt_device(ctx: *mut PvwCtx, d_scalars: *const u64, num_scalars: usize, rnd: *const PvwRandomnessT, d_c1: *mut u64, d_c2: *mut u64, out_repr: u32, stream: *mut c_void) -> i32;
     pub fn pvw_encrypt_multi(ctx: *mut PvwCtx, scalars: *const u64, num_dealers: usize, scalars_per_dealer: usize, seeds: *const u8, c1_out: *mut u64, c2_out: *mut u64, out_repr: u32) -> i32;
     pub fn pvw_encrypt_multi_device(ctx: *mut PvwCtx, d_scalars: *const u64, num_dealers: usize, scalars_per_dealer: usize, seeds: *const u8, d_c1: *mut u64, d_c2: *mut u64, out_repr: u32, stream: *mut c_void) -> i32;
+    // ---- encrypt from a device randomness state (an opaque handle: seed + counter on the device) ----
+    pub fn pvw_rnd_state_create(ctx: *mut PvwCtx, seed: *const u8, counter: u64, out: *mut *mut c_void) -> i32;
+    pub fn pvw_rnd_state_counter(st: *mut c_void, stream: *mut c_void, out: *mut u64) -> i32;
+    pub fn pvw_rnd_state_set_counter(st: *mut c_void, counter: u64, stream: *mut c_void) -> i32;
+    pub fn pvw_rnd_state_free(st: *mut c_void) -> i32;
+    pub fn pvw_rnd_call_seed(seed: *const u8, counter: u64, out: *mut u8) -> i32;
+    pub fn pvw_encrypt_rs(ctx: *mut PvwCtx, scalars: *const u64, num_scalars: usize, st: *mut c_void, c1_out: *mut u64, c2_out: *mut u64, out_repr: u32) -> i32;
+    pub fn pvw_encrypt_rs_device(ctx: *mut PvwCtx, d_scalars: *const u64, num_scalars: usize, st: *mut c_void, d_c1: *mut u64, d_c2: *mut u64, out_repr: u32, stream: *mut c_void) -> i32;
+    pub fn pvw_encrypt_multi_rs(ctx: *mut PvwCtx, scalars: *const u64, num_dealers: usize, scalars_per_dealer: usize, st: *mut c_void, c1_out: *mut u64, c2_out: *mut u64, out_repr: u32) -> i32;
+    pub fn pvw_encrypt_multi_rs_device(ctx: *mut PvwCtx, d_scalars: *const u64, num_dealers: usize, scalars_per_dealer: usize, st: *mut c_void, d_c1: *mut u64, d_c2: *mut u64, out_repr: u32, stream: *mut c_void) -> i32;
     // ---- decrypt (src/crypto/decryption.rs:249-325) and gadget decode (:10-247) ---------------
     pub fn pvw_decrypt_batch(ctx: *mut PvwCtx, sk: *const i64, c1s: *const u64, c2col: *const u64, num_dealers: usize, in_repr: u32, out_u64: *mut u64, noisy_out: *mut u64) -> i32;
     pub fn pvw_decrypt_noisy_device(ctx: *mut PvwCtx, d_sk: *const i64, d_c1s: *const u64, d_c2col: *const u64, num_dealers: usize, in_repr: u32, d_noisy: *mut u64, stream: *mut c_void) -> i32;
@@ -149,6 +160,7 @@ extern "C" {
     pub fn pvw_selftest_siphash(msg: *const u8, len: usize, k0: u64, k1: u64, c_rounds: i32, d_rounds: i32, out: *mut u64) -> i32;
     pub fn pvw_selftest_decode_tables(ctx: *const PvwCtx, info_out: *mut u32) -> i32;
     pub fn pvw_selftest_decode_shortcuts(ctx: *const PvwCtx, noisy: *const u64, count: usize, out_u64: *mut u64, short_path: *mut u8) -> i32;
+    pub fn pvw_selftest_rnd_free_residue(nonzero_words: *mut u64) -> i32;
     pub fn pvw_build_is_tuning() -> i32;
     // ---- ring primitives (fhe-math call sites: change_representation, from_coefficients) ---------
     pub fn pvw_ntt_forward(ctx: *mut PvwCtx, polys: *mut u64, count: usize) -> i32;

@@ -49,6 +49,62 @@ pub fn encrypt(scalars: &[u64], global_pk: &GlobalPublicKey) -> Result<PvwCipher
     ciphertext_from_flat(&c1, &c2, params)
 }
 
+/// A randomness state on the device (`pvw_rnd_state`): a seed drawn ONCE from `thread_rng` and a counter.  `encrypt_with` /
+/// `encrypt_all_party_shares_with` draw call `i`'s randomness from it on the device (`call_seed(S, c + i)`) and advance the
+/// counter there, so no host work per call is needed for fresh randomness, and device-pointer calls captured into a graph
+/// draw anew on every replay -- the reference's contract (`thread_rng()` on every encrypt, encryption.rs:135-167).
+/// Holds its parameters, so the context it was created for outlives it; dropping it clears the device seed.
+pub struct DeviceRandomness {
+    params: Arc<PvwParameters>,
+    raw: *mut std::ffi::c_void,
+}
+
+impl DeviceRandomness {
+    pub fn new(params: &Arc<PvwParameters>) -> Result<Self> {
+        let mut seed = fresh_seed();
+        let mut raw: *mut std::ffi::c_void = std::ptr::null_mut();
+        let rc = unsafe { sys::pvw_rnd_state_create(params.hip.raw(), seed.as_ptr(), 0, &mut raw) };
+        seed.zeroize();
+        check(rc)?;
+        Ok(Self { params: params.clone(), raw })
+    }
+
+    /// the counter once the work on the context's stream is done
+    pub fn counter(&self) -> Result<u64> {
+        let mut v = 0u64;
+        check(unsafe { sys::pvw_rnd_state_counter(self.raw, std::ptr::null_mut(), &mut v) })?;
+        Ok(v)
+    }
+
+    pub fn params(&self) -> &Arc<PvwParameters> {
+        &self.params
+    }
+
+    pub fn raw(&self) -> *mut std::ffi::c_void {
+        self.raw
+    }
+}
+
+impl Drop for DeviceRandomness {
+    fn drop(&mut self) {
+        if !self.raw.is_null() {
+            unsafe { sys::pvw_rnd_state_free(self.raw) };
+            self.raw = std::ptr::null_mut();
+        }
+    }
+}
+
+/// `encrypt` with the randomness drawn from a `DeviceRandomness` on the device.
+pub fn encrypt_with(scalars: &[u64], global_pk: &GlobalPublicKey, rnd: &DeviceRandomness) -> Result<PvwCiphertext> {
+    let params = &global_pk.params;
+    let words = poly_words(params);
+    let (mut c1, mut c2) = (vec![0u64; params.k * words], vec![0u64; params.n * words]);
+    check(unsafe {
+        sys::pvw_encrypt_rs(params.hip.raw(), scalars.as_ptr(), scalars.len(), rnd.raw(), c1.as_mut_ptr(), c2.as_mut_ptr(), sys::PVW_REPR_POWER)
+    })?;
+    ciphertext_from_flat(&c1, &c2, params)
+}
+
 /// `encrypt_party_shares` (encryption.rs:221-245).
 pub fn encrypt_party_shares(party_shares: &[u64], party_index: usize, global_pk: &GlobalPublicKey) -> Result<PvwCiphertext> {
     if party_index >= global_pk.params.n {
@@ -86,6 +142,34 @@ pub fn encrypt_all_party_shares(all_shares: &[Vec<u64>], global_pk: &GlobalPubli
     let (mut c1, mut c2) = (vec![0u64; n * params.k * words], vec![0u64; n * n * words]);
     check(unsafe {
         sys::pvw_encrypt_multi(params.hip.raw(), scalars.as_ptr(), n, n, seeds.as_ptr(), c1.as_mut_ptr(), c2.as_mut_ptr(), sys::PVW_REPR_POWER)
+    })?;
+    (0..n)
+        .map(|d| ciphertext_from_flat(&c1[d * params.k * words..(d + 1) * params.k * words], &c2[d * n * words..(d + 1) * n * words], params))
+        .collect()
+}
+
+/// `encrypt_all_party_shares` with dealer d's randomness drawn from a `DeviceRandomness` (`call_seed(S, c + d)`).
+pub fn encrypt_all_party_shares_with(all_shares: &[Vec<u64>], global_pk: &GlobalPublicKey, rnd: &DeviceRandomness) -> Result<Vec<PvwCiphertext>> {
+    let params = &global_pk.params;
+    let n = params.n;
+    if all_shares.len() != n {
+        return Err(PvwError::InvalidParameters(format!("Must provide shares for all {n} parties")));
+    }
+    for (dealer_idx, dealer_shares) in all_shares.iter().enumerate() {
+        if dealer_shares.len() != n {
+            return Err(PvwError::InvalidParameters(format!(
+                "Dealer {} provided {} shares but needs {}",
+                dealer_idx,
+                dealer_shares.len(),
+                n
+            )));
+        }
+    }
+    let words = poly_words(params);
+    let scalars: Vec<u64> = all_shares.iter().flat_map(|row| row.iter().copied()).collect();
+    let (mut c1, mut c2) = (vec![0u64; n * params.k * words], vec![0u64; n * n * words]);
+    check(unsafe {
+        sys::pvw_encrypt_multi_rs(params.hip.raw(), scalars.as_ptr(), n, n, rnd.raw(), c1.as_mut_ptr(), c2.as_mut_ptr(), sys::PVW_REPR_POWER)
     })?;
     (0..n)
         .map(|d| ciphertext_from_flat(&c1[d * params.k * words..(d + 1) * params.k * words], &c2[d * n * words..(d + 1) * n * words], params))
