@@ -69,6 +69,20 @@ PVW_HD u64 mulmod_shoup(u64 a, u64 w, u64 wp, u64 q) {
   return r >= q ? r - q : r;
 }
 inline u64 shoup_precompute(u64 w, u64 q) { return (u64)(((u128)w << 64) / q); }
+// The constant pair of "multiply by 256 mod q" (the digit step of the GEMM operands): w = 256 mod q and
+// wp = floor(w * 2^64 / q), from the Barrett ratio alone.  For q > 256, wp = floor(2^72 / q) = floor(2^128 / q) >> 56.
+// For q < 256 that shift overflows (and 256 is not below q): w = 256 mod q, and with 2^64 = h q + r64 (h = ratio_hi),
+// w 2^64 / q = w h + w r64 / q, where w r64 < 2^16.
+PVW_HD void mul256_consts(const Mod& m, u64& w, u64& wp) {
+  if (m.q > 256) {
+    w = 256;
+    wp = (m.ratio_hi << 8) | (m.ratio_lo >> 56);
+  } else {
+    w = 256 % m.q;
+    const u64 r64 = (u64)0 - m.ratio_hi * m.q;                  // 2^64 mod q
+    wp = w * m.ratio_hi + (u64)((u32)(w * r64) / (u32)m.q);
+  }
+}
 PVW_HD u64 addmod(u64 a, u64 b, u64 q) {
   u64 s = a + b;
   return s >= q ? s - q : s;

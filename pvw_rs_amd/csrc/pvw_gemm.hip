@@ -190,7 +190,8 @@ __global__ __launch_bounds__(64) void vec_digits_kernel(const u64* __restrict__ 
   const Mod m = t.mods[limb];
   const u32 JB = (k + 3) / 4;
   const u32 vg = v >> 2, v4 = v & 3;
-  const u64 w256p = (m.ratio_hi << 8) | (m.ratio_lo >> 56);   // floor(256 * 2^64 / q) = floor(2^128 / q) >> 56
+  u64 w256, w256p;                                              // 256 mod q and its Shoup companion
+  mul256_consts(m, w256, w256p);
   const u64* y = vhat + (size_t)v * vstride + (size_t)limb * lstride + slot;
   signed char* tiles = YD + (((size_t)vg * L + limb) * ELL + slot) * (size_t)JB * 1024;
   u64 csum_lo = 0;                                                // sum of the shifted copies (each < 2^62), 96 bits
@@ -215,7 +216,7 @@ __global__ __launch_bounds__(64) void vec_digits_kernel(const u64* __restrict__ 
         rh[a] = (u32)(dgt >> 32);
         csum_lo += cur;
         csum_hi += csum_lo < cur;
-        cur = mulmod_shoup(cur, 256, w256p, m.q);
+        cur = mulmod_shoup(cur, w256, w256p, m.q);
       }
       // 8x8 byte transpose: column b gets the bytes a = 0..7
       u32 cl[8], ch[8];
@@ -345,7 +346,8 @@ __global__ __launch_bounds__(64) void vec_digits7_kernel(const u64* __restrict__
   const Mod m = t.mods[limb];
   const u32 KT = 7 * (k / 32);
   const u32 vg = v >> 2, v4 = v & 3;
-  const u64 w256p = (m.ratio_hi << 8) | (m.ratio_lo >> 56);   // floor(256 * 2^64 / q)
+  u64 w256, w256p;                                              // 256 mod q and its Shoup companion
+  mul256_consts(m, w256, w256p);
   const u64* y = vhat + (size_t)v * vstride + (size_t)limb * lstride + slot;
   signed char* tiles = YD + (((size_t)vg * L + limb) * ELL + slot) * (size_t)KT * 1024;
   u64 csum_lo = 0;
@@ -369,7 +371,7 @@ __global__ __launch_bounds__(64) void vec_digits7_kernel(const u64* __restrict__
         hi[p] = (u32)(dgt >> 32);
         csum_lo += cur[p];
         csum_hi += csum_lo < cur[p];
-        cur[p] = mulmod_shoup(cur[p], 256, w256p, m.q);
+        cur[p] = mulmod_shoup(cur[p], w256, w256p, m.q);
       }
       // digit b of the 16 elements = one 16-byte run: byte transposes of four elements at a time
       u32 run[8][4];

@@ -122,3 +122,56 @@ def decode_cases(l, moduli):
             noise[0], noise[l - 1] = n0, top_noise
             cases.append([(-(msg * D ** j) + noise[j]) % Q for j in range(l)])
     return cases
+
+
+# ---------------------------------------------------------------- modulus classes
+# Concrete primes at the widths where the kernels switch code paths (stream width of the packed mac_rows: widest modulus
+# <= 40 / 48 / 56 / 61 bits; the 7-byte digit contraction: widest <= 56 bits; FASTQ recombination: smallest >= 55 bits;
+# the Shoup constant of the digit step: q > 256; reduce128: q < 2^62).  All are 1 (mod 128), so they serve every l <= 64,
+# except where noted.
+MOD_TINY = [17, 97, 241]                                          # 1 (mod 16) only: l = 8
+MOD_ABOVE_256 = [257, 337]                                        # 337: 1 (mod 16) only
+MOD_AROUND_32 = [0xFFFFFD81, 0x100000181]
+MOD_TOP_40 = [0xFFFFFFEE81, 0xFFFFFFEB81]
+MOD_BOTTOM_48 = [0x10000000181, 0x10000000981]                    # 41 bits: the 48-bit stream from its bottom
+MOD_BOTTOM_56 = [0x1000000000781]                                 # 49 bits: the 56-bit stream from its bottom
+MOD_TOP_54 = [0x3FFFFFFFFFFF01, 0x3FFFFFFFFFFE81]
+MOD_BOTTOM_55 = [0x40000000000E01, 0x40000000001D01]
+MOD_TOP_56 = [0xFFFFFFFFFFFA81, 0xFFFFFFFFFFF481, 0xFFFFFFFFFFD981]
+MOD_BOTTOM_57 = [0x100000000000D81, 0x100000000001081]
+MOD_BOTTOM_62 = [0x2000000000000581, 0x2000000000000881]
+MOD_TOP_62 = [0x3FFFFFFFFFFFEC81, 0x3FFFFFFFFFFFDE01]
+MOD_CLASSES = {
+    "tiny": MOD_TINY, "above256": MOD_ABOVE_256, "around32": MOD_AROUND_32, "top40": MOD_TOP_40, "bottom48": MOD_BOTTOM_48,
+    "bottom56": MOD_BOTTOM_56, "top54": MOD_TOP_54, "bottom55": MOD_BOTTOM_55, "top56": MOD_TOP_56, "bottom57": MOD_BOTTOM_57,
+    "bottom62": MOD_BOTTOM_62, "top62": MOD_TOP_62,
+}
+EDGE_MODULI = sorted({q for c in MOD_CLASSES.values() for q in c})
+_B61 = M.bench_moduli(2)                                          # 61 bits, 1 (mod 64): l <= 32
+
+# pure chains: one class each (the max-bits rules see that class alone)
+PURE_CHAINS = {name: list(c) for name, c in MOD_CLASSES.items()}
+# mixed chains: a tiny q_0 (which the decode tables treat specially) and a tiny last limb; one 54-bit modulus among 61-bit
+# ones (FASTQ off for every limb); one 57-bit modulus among top-of-56 ones (off the 7-byte form, onto the 61-bit stream);
+# one 62-bit modulus among 40-bit ones (no packed stream); 257 among 61-bit ones; a tiny modulus and 257 among top-of-56
+# ones (every modulus <= 56 bits: multi-dealer encrypt takes the 7-byte contraction, vec_digits7_kernel, with q < 256 / 257)
+MIXED_CHAINS = {
+    "tiny_first": [MOD_TINY[2]] + _B61,
+    "tiny_last": _B61 + [MOD_TINY[2]],
+    "tiny_all": [MOD_TINY[0]] + _B61 + [MOD_TINY[1], MOD_TINY[2]],
+    "above256_first": [MOD_ABOVE_256[0]] + _B61,
+    "top54_among_61": [_B61[0], MOD_TOP_54[0], _B61[1]],
+    "bottom57_among_top56": MOD_TOP_56[:2] + [MOD_BOTTOM_57[0]],
+    "top62_among_40": [MOD_TOP_40[0], MOD_TOP_62[0], MOD_TOP_40[1]],
+    "tiny_among_56": [MOD_TINY[2]] + MOD_TOP_56[:2],
+    "above256_among_56": [MOD_ABOVE_256[0]] + MOD_TOP_56[1:],
+}
+EDGE_CHAINS = {**{"pure_" + k: v for k, v in PURE_CHAINS.items()}, **{"mixed_" + k: v for k, v in MIXED_CHAINS.items()}}
+
+
+def chain_max_l(moduli):
+    """largest ring degree l <= 64 every modulus of the chain serves (q = 1 mod 2l)"""
+    l = 64
+    while any((q - 1) % (2 * l) for q in moduli):
+        l //= 2
+    return l

@@ -69,16 +69,18 @@ def _random_inputs(p, lo, hi, D, seed):
 
 def _all(p, lo, hi, sk, c1, c2, repr=P.REPR_NTT):
     out = np.zeros((hi - lo, c1.shape[0]), dtype=np.uint64)
-    p._call("pvw_decrypt_all", lo, hi, sk.ctypes.data, np.ascontiguousarray(c1).ctypes.data, np.ascontiguousarray(c2).ctypes.data,
-            c1.shape[0], repr, out.ctypes.data)
+    # the contiguous copies are held in locals: a temporary's buffer would be freed before the call reads it
+    sk, c1, c2 = np.ascontiguousarray(sk), np.ascontiguousarray(c1), np.ascontiguousarray(c2)
+    p._call("pvw_decrypt_all", lo, hi, sk.ctypes.data, c1.ctypes.data, c2.ctypes.data, c1.shape[0], repr, out.ctypes.data)
     return out
 
 
 def _per_party(p, sk_p, c1, c2col, repr=P.REPR_NTT, noisy=False):
     out = np.zeros(c1.shape[0], dtype=np.uint64)
     nz = np.zeros((c1.shape[0], p.L, p.l), dtype=np.uint64) if noisy else None
-    p._call("pvw_decrypt_batch", np.ascontiguousarray(sk_p).ctypes.data, np.ascontiguousarray(c1).ctypes.data,
-            np.ascontiguousarray(c2col).ctypes.data, c1.shape[0], repr, out.ctypes.data, None if nz is None else nz.ctypes.data)
+    sk_p, c1, c2col = np.ascontiguousarray(sk_p), np.ascontiguousarray(c1), np.ascontiguousarray(c2col)   # held: see _all
+    p._call("pvw_decrypt_batch", sk_p.ctypes.data, c1.ctypes.data, c2col.ctypes.data, c1.shape[0], repr, out.ctypes.data,
+            None if nz is None else nz.ctypes.data)
     return (out, nz) if noisy else out
 
 

@@ -523,9 +523,10 @@ DECRYPT_SHAPE_CASES = [
 ]
 
 
-def decrypt_mac_case(k, l, L, D):
+def decrypt_mac_case(k, l, L, D, moduli=None):
     """(closure returning the noisy polynomials, oracle's) for decrypt_party_value's <sk, c1> - c2 (decryption.rs:257-274)"""
-    moduli = M.bench_moduli(L)
+    moduli = moduli or M.bench_moduli(L)
+    L = len(moduli)
     p = build_params(3, k, l, moduli)
     orc = O.Oracle(moduli, l)
     c1s = orc.fill_uniform(SEED, M.DOM_CRS, 0, D * k).reshape(D, k, L, l)
@@ -928,8 +929,8 @@ def test_batched_keygen_super_groups_against_c_oracle(n, k, l, L):
     batched_keygen_case(n, k, l, L)
 
 
-def batched_keygen_case(n, k, l, L):
-    moduli = M.bench_moduli(L)
+def batched_keygen_case(n, k, l, L, moduli=None):
+    moduli = moduli or M.bench_moduli(L)
     p = build_params(n, k, l, moduli)
     seed = bytes([0x5A]) * 32
     crs = P.PvwCrs.new_deterministic(p, seed)
