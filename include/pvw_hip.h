@@ -15,7 +15,8 @@
  *     PVW_ERR_* codes, which map 1:1 onto the PvwError variants of
  *     src/errors.rs:13-70.  pvw_last_error() returns the thread-local message.
  *   - polynomial = [L][l] uint64_t, limb-major (the Array2<u64> (num_moduli,
- *     degree) of src/params/parameters.rs:433-458), residues in [0, q_i).
+ *     degree) of src/params/parameters.rs:433-458), residues in [0, q_i)
+ *     (words >= q_i: "Residue words" below).
  *     Matrices are row-major arrays of polynomials: A is [k][k], B is [n][k].
  *   - `repr`: PVW_REPR_POWER = coefficients (fhe-math Representation::PowerBasis),
  *     PVW_REPR_NTT = this library's NTT domain (slot s of limb i holds the
@@ -91,6 +92,13 @@ enum {
 };
 
 enum { PVW_REPR_POWER = 0, PVW_REPR_NTT = 1 };
+/* Residue words.  Every uint64_t residue word w a caller passes in limb i (CRS, public keys, ciphertexts c1 / c2,
+ * polynomials for the transforms, noisy residues for the decode) means w mod q_i: any 64-bit word is accepted and
+ * no call checks or rejects it.  Every residue word a call returns is below q_i, with one exception: an NTT-domain
+ * load (pvw_load_crs[_device] / pvw_load_pk[_device] with PVW_REPR_NTT) stores the caller's words as given, and
+ * pvw_get_crs / pvw_get_pk in PVW_REPR_NTT hand those stored words back unchanged.  Signed inputs (secret-key
+ * coefficients, key errors ek, explicit r / e1 / e2, scalars read as int64) mean their signed residue
+ * ((c % q) + q) % q, as parameters.rs:440-443. */
 enum { PVW_RND_SEED = 0, PVW_RND_EXPLICIT = 1 };
 
 /* ChaCha8 stream-id domains of the counter-based sampler: stream = (domain<<32)|poly index */

@@ -88,6 +88,10 @@ PVW_HD u64 addmod(u64 a, u64 b, u64 q) {
   return s >= q ? s - q : s;
 }
 PVW_HD u64 submod(u64 a, u64 b, u64 q) { return a >= b ? a - b : a + q - b; }
+// w mod q for ANY 64-bit word.  Every residue word a caller passes means w mod q_i (include/pvw_hip.h), while addmod,
+// submod, the NTTs below and the balanced digits of the GEMM operands need words below q: the kernels put caller words
+// through this at their load.  A word the kernels made themselves is below q and costs the compare only.
+PVW_HD u64 reduce_word(u64 w, const Mod& m) { return w < m.q ? w : reduce128(w, 0, m); }
 
 // non-negative residue of a signed value: ((c % q) + q) % q  (parameters.rs:440-443,
 // the rule Poly::from_coefficients(&[i64]) follows as well, tests/params.rs:733-767)
@@ -194,7 +198,8 @@ PVW_HD u32 bitrev32(u32 i, u32 bits) {
 // ---------------------------------------------------------------- l-point negacyclic NTT
 // In-register transform of one limb, L_ a compile-time 8/16/32/64: natural order in,
 // bit-reversed order out (slot s holds a(psi^(2*bitrev(s)+1))).  tw[i] = psi^bitrev(i),
-// twp[i] = floor(tw[i]*2^64/q) (Shoup).
+// twp[i] = floor(tw[i]*2^64/q) (Shoup).  Inputs must be below q (addmod / submod): reduce caller words with reduce_word
+// first -- on a word >= q the first butterfly can wrap at 2^64 and leave a slot that is not congruent to the transform.
 template <int L_>
 PVW_HD void ntt_forward(u64 (&a)[L_], const u64* tw, const u64* twp, const Mod& m) {
   int step = L_;
@@ -213,7 +218,7 @@ PVW_HD void ntt_forward(u64 (&a)[L_], const u64* tw, const u64* twp, const Mod& 
     }
   }
 }
-// inverse: bit-reversed in, natural out; itw[i] = psi^-bitrev(i); linv = l^-1
+// inverse: bit-reversed in, natural out; itw[i] = psi^-bitrev(i); linv = l^-1.  Inputs below q, as for ntt_forward.
 template <int L_>
 PVW_HD void ntt_inverse(u64 (&a)[L_], const u64* itw, const u64* itwp, u64 linv, u64 linvp, const Mod& m) {
   int step = 1;

@@ -917,8 +917,8 @@ static int32_t ensure_xm(pvw_ctx* c, hipStream_t s) {
   // encrypt contracts over 7/8 of the terms.  Tuning build: PVW_GEMM_BYTES=8 keeps all 8.
   c->xm_bytes = gemm7_ok(c->dt.max_q_bits, c->k) && PVW_ENV_INT("PVW_GEMM_BYTES", 7) != 8 ? 7 : 8;
   ProfScope ps(c, "mftile", s);
-  PVW_HIP(launch_mftile(c->dA, true, c->xmA, rA, c->k, c->L, c->l, s, c->xm_bytes));
-  PVW_HIP(launch_mftile(c->dB, true, c->xmB, rB, c->k, c->L, c->l, s, c->xm_bytes));
+  PVW_HIP(launch_mftile(c->dA, true, c->xmA, rA, c->k, c->L, c->l, s, c->xm_bytes, c->dt.mods));
+  PVW_HIP(launch_mftile(c->dB, true, c->xmB, rB, c->k, c->L, c->l, s, c->xm_bytes, c->dt.mods));
   PVW_HIP(hipStreamSynchronize(s));
   c->xm_valid = true;
   return PVW_OK;

@@ -408,7 +408,7 @@ PVW_HD u64 decode_one_fixed(const DecodeTables& t, const u64* noisy, BN x, BN y,
   auto tmp = [&](u32 limb, u32 i) -> u64 {
     const Mod m = t.mods[limb];
     const u64* z = noisy + (size_t)limb * l;
-    return submod(mulmod_shoup(z[i], t.dmod[limb], t.dmodp[limb], m.q), z[i + 1], m.q);
+    return submod(mulmod_shoup(z[i], t.dmod[limb], t.dmodp[limb], m.q), reduce_word(z[i + 1], m), m.q);   // caller words: w mod q
   };
   // Horner over tmp_0 .. tmp_{l-2} (:30-33), lifted and centred
   bool neg = lift_centered(t, x, [&](u32 limb) -> u64 {
@@ -452,7 +452,7 @@ PVW_HD u64 decode_one_fixed(const DecodeTables& t, const u64* noisy, BN x, BN y,
   // plaintext = -z_0 - noise_0 (:51-53), then extract_constant_term_as_u64 (:226-247)
   bool vneg = lift_centered(t, x, [&](u32 limb) -> u64 {
     const Mod m = t.mods[limb];
-    u64 z0 = noisy[(size_t)limb * l];
+    u64 z0 = reduce_word(noisy[(size_t)limb * l], m);
     u64 a = z0 ? m.q - z0 : 0;
     return submod(a, nres[(int)limb], m.q);
   });

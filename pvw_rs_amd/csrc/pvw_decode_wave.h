@@ -403,7 +403,8 @@ __device__ __forceinline__ void decode_chain_body(u64* __restrict__ noisy, u64* 
   if (live) {
     if (xf.itw) stage_inverse(t.mods, xf, zs, noisy + (size_t)d * L * l, L, l, wsub * 64 + lane, WPC * 64);
     else
-      for (u32 x = wsub * 64 + lane; x < L * l; x += WPC * 64) zs[x] = noisy[(size_t)d * L * l + x];
+      for (u32 x = wsub * 64 + lane; x < L * l; x += WPC * 64)   // caller words: w means w mod q (tmp / z0 need them below q)
+        zs[x] = reduce_word(noisy[(size_t)d * L * l + x], t.mods[x / l]);
   }
   __syncthreads();
   const u64 tk0b = dbg ? clock64() : 0;

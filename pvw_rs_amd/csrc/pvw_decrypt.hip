@@ -104,8 +104,8 @@ __global__ __launch_bounds__(1024) void decrypt_mac_kernel(const u64* __restrict
     }
     const size_t o = (size_t)d * pairs + e;
     v2u64 c2 = reinterpret_cast<const v2u64*>(c2col)[o];
-    s.x = submod(s.x, c2.x, m.q);
-    s.y = submod(s.y, c2.y, m.q);
+    s.x = submod(s.x, reduce_word(c2.x, m), m.q);     // c2 as the caller passed it: w means w mod q
+    s.y = submod(s.y, reduce_word(c2.y, m), m.q);
     reinterpret_cast<v2u64*>(noisy)[o] = s;
   }
 }
@@ -189,8 +189,8 @@ __global__ __launch_bounds__(MAXT) void decrypt_mac_grouped_kernel(const u64* __
         reinterpret_cast<v2u64*>(partial)[(size_t)blockIdx.y * dealers * pairs + o] = sres;
       } else {
         v2u64 c2 = reinterpret_cast<const v2u64*>(c2col)[o];
-        sres.x = submod(sres.x, c2.x, m.q);
-        sres.y = submod(sres.y, c2.y, m.q);
+        sres.x = submod(sres.x, reduce_word(c2.x, m), m.q);     // c2 as the caller passed it: w means w mod q
+        sres.y = submod(sres.y, reduce_word(c2.y, m), m.q);
         reinterpret_cast<v2u64*>(noisy)[o] = sres;
       }
     }
@@ -318,8 +318,8 @@ __global__ __launch_bounds__(1024) void decrypt_mac_fw_kernel(const u64* __restr
         reinterpret_cast<v2u64*>(partial)[(size_t)blockIdx.y * dealers * pairs + o] = sres;
       } else {
         v2u64 c2 = reinterpret_cast<const v2u64*>(c2col)[o];
-        sres.x = submod(sres.x, c2.x, m.q);
-        sres.y = submod(sres.y, c2.y, m.q);
+        sres.x = submod(sres.x, reduce_word(c2.x, m), m.q);     // c2 as the caller passed it: w means w mod q
+        sres.y = submod(sres.y, reduce_word(c2.y, m), m.q);
         reinterpret_cast<v2u64*>(noisy)[o] = sres;
       }
     }
@@ -354,8 +354,8 @@ __global__ __launch_bounds__(256) void decrypt_finish_kernel(const u64* __restri
       acc.x = addmod(acc.x, p.x, m.q);
       acc.y = addmod(acc.y, p.y, m.q);
     }
-    a[2 * b] = submod(acc.x, c2.x, m.q);
-    a[2 * b + 1] = submod(acc.y, c2.y, m.q);
+    a[2 * b] = submod(acc.x, reduce_word(c2.x, m), m.q);           // c2 as the caller passed it: w means w mod q
+    a[2 * b + 1] = submod(acc.y, reduce_word(c2.y, m), m.q);
   }
   __builtin_amdgcn_wave_barrier();
   const u64* tw = t.itw + (size_t)limb * ELL;

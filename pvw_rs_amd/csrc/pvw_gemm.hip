@@ -204,7 +204,7 @@ __global__ __launch_bounds__(64) void vec_digits_kernel(const u64* __restrict__ 
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
       const u32 j = 4 * jb + jj;
-      u64 cur = j < k ? y[(size_t)j * jstride] : 0;
+      u64 cur = j < k ? reduce_word(y[(size_t)j * jstride], m) : 0;   // the digits below rebuild w only for w < 2^63 - 2^55
       // the 8 balanced base-256 digits of w < 2^62 are the bytes of (w + 0x80..80) with their top bits
       // flipped: adding 128 to every byte position propagates exactly the carries of "digit > 127"
       const u64 C = 0x8080808080808080ULL;
@@ -294,9 +294,10 @@ __global__ __launch_bounds__(64) void vec_digits_kernel(const u64* __restrict__ 
 // p = 0..15; digit fragment of lane (h, col = 8 v4 + b): digit b of the shifted copy a of y_v[32 g + 16 h + p].
 // tiled matrix (or API-layout rows) -> XM7[limb][slot][row tile][g*7 + a][lane][16 bytes]; one thread per (row, limb,
 // slot, g, h) reads its 16 elements and writes 7 fragments.  A one-off per matrix (pvw_prepare / first multi-dealer call).
+// Byte 7 is dropped, so each word is reduced mod its limb's q first (a caller's word w means w mod q and may be >= 2^56).
 template <int ELL>
 __global__ __launch_bounds__(256) void mftile7_kernel(const u64* __restrict__ src, u32 src_is_tiled, u64* __restrict__ XM,
-                                                       u32 rows, u32 k, u32 L) {
+                                                       u32 rows, u32 k, u32 L, const Mod* __restrict__ mods) {
   constexpr int R = 128 / ELL;
   const u32 G = k / 32, KT = 7 * G;
   const u32 RT = ((rows + PVW_GEMM_ROWS_PER_WG - 1) / PVW_GEMM_ROWS_PER_WG) * (PVW_GEMM_ROWS_PER_WG / 32);
@@ -310,6 +311,7 @@ __global__ __launch_bounds__(256) void mftile7_kernel(const u64* __restrict__ sr
   const u32 limb = r % L;
   r /= L;
   const u32 h = r & 1, g = (u32)(r >> 1);
+  const Mod md = mods[limb];
   u64 x[16];
 #pragma unroll
   for (int p = 0; p < 16; ++p) {
@@ -318,7 +320,7 @@ __global__ __launch_bounds__(256) void mftile7_kernel(const u64* __restrict__ sr
     if (row < rows)
       v = src_is_tiled ? src[(((size_t)(row / R) * L + limb) * k + j) * 128 + (row % R) * ELL + slot]
                        : src[(((size_t)row * k + j) * L + limb) * ELL + slot];
-    x[p] = v;
+    x[p] = reduce_word(v, md);
   }
   const u32 rt = row >> 5, m = row & 31;
   u64* base = XM + ((((size_t)limb * ELL + slot) * RT + rt) * KT + (size_t)g * 7) * 128 + (h * 32 + m) * 2;
@@ -359,7 +361,7 @@ __global__ __launch_bounds__(64) void vec_digits7_kernel(const u64* __restrict__
     const bool on = jb < nblk;
     u64 cur[16];
 #pragma unroll
-    for (int p = 0; p < 16; ++p) cur[p] = on ? y[(size_t)(16 * jb + p) * jstride] : 0;
+    for (int p = 0; p < 16; ++p) cur[p] = on ? reduce_word(y[(size_t)(16 * jb + p) * jstride], m) : 0;   // as vec_digits_kernel
 #pragma unroll 1
     for (u32 a = 0; a < 7; ++a) {
       const u64 C = 0x8080808080808080ULL;
@@ -1031,12 +1033,14 @@ __global__ __launch_bounds__(32 * VPB) void gemm_finish_err_kernel(GemmSection s
     __builtin_amdgcn_wave_barrier();                             // the staging rows are rewritten for the next limb
   }
 }
-hipError_t launch_mftile(const u64* src, bool src_is_tiled, u64* XM, u32 rows, u32 k, u32 L, u32 ell, hipStream_t s, u32 bytes) {
+hipError_t launch_mftile(const u64* src, bool src_is_tiled, u64* XM, u32 rows, u32 k, u32 L, u32 ell, hipStream_t s, u32 bytes,
+                         const Mod* mods) {
   if (rows == 0) return hipSuccess;
   if (bytes == 7) {
+    if (!mods) return hipErrorInvalidValue;
     const u32 RT = ((rows + PVW_GEMM_ROWS_PER_WG - 1) / PVW_GEMM_ROWS_PER_WG) * (PVW_GEMM_ROWS_PER_WG / 32);
     const size_t threads = (size_t)RT * 32 * L * ell * (k / 32) * 2;
-    PVW_DISPATCH_ELL(ell, mftile7_kernel<E><<<dim3((u32)((threads + 255) / 256)), dim3(256), 0, s>>>(src, src_is_tiled ? 1u : 0u, XM, rows, k, L));
+    PVW_DISPATCH_ELL(ell, mftile7_kernel<E><<<dim3((u32)((threads + 255) / 256)), dim3(256), 0, s>>>(src, src_is_tiled ? 1u : 0u, XM, rows, k, L, mods));
     return hipGetLastError();
   }
   if (!src_is_tiled && ell <= 32) {      // API-layout rows: the LDS-transposing form (writes every tile, padding included)
@@ -1229,8 +1233,8 @@ static inline u32 ilog2_u32(u32 x) { u32 b = 0; while ((1u << b) < x) ++b; retur
 //        adds the offset correction (wave-uniform) and leaves the pair in an LDS tile [row][f];
 //   out: 16 lanes per row take the row's 32 f = 256 contiguous bytes of c2 and of noisy per row (rows of c2 are P words
 //        apart; 4 rows per wave instruction, 1 KiB in, 1 KiB out).
-// c2 is read as the caller left it: submod on the raw word, as decrypt_mac does, so that unreduced words give what the
-// per-party path gives.  No c2 row outside [0, nrows) of the section is touched.
+// c2 is read as the caller left it and reduced before the subtraction (a word w means w mod q, include/pvw_hip.h), as
+// decrypt_mac does.  No c2 row outside [0, nrows) of the section is touched.
 __global__ __launch_bounds__(256) void gemm_finish_decrypt_kernel(const u64* __restrict__ tmp, size_t tmp_bstride, u32 nv_pad,
                                                                   u32 rows_pad, const int* __restrict__ SY, size_t sy_b16,
                                                                   const Mod* __restrict__ mods, u32 ell_log2, u32 P, u32 nrows,
@@ -1263,14 +1267,15 @@ __global__ __launch_bounds__(256) void gemm_finish_decrypt_kernel(const u64* __r
   __syncthreads();
   const u32 fp = (threadIdx.x & 15) * 2, f = f0 + fp;             // P is a multiple of 8: f and f + 1 share a limb
   if (f >= P) return;
-  const u64 q = mods[f >> ell_log2].q;
+  const Mod m = mods[f >> ell_log2];
+  const u64 q = m.q;
 #pragma unroll
   for (u32 i = 0; i < TR / 16; ++i) {
     const u32 rl = (threadIdx.x >> 4) + 16 * i, row = r0 + rl;
     if (row < nrows) {
       const v2u64 cw = __builtin_nontemporal_load(reinterpret_cast<const v2u64*>(c2 + (size_t)v * c2_vstride + (size_t)row * c2_rstride + f));
       const v2u64 t2 = *reinterpret_cast<const v2u64*>(&tile[rl][fp]);
-      const v2u64 o = (v2u64){submod(t2.x, cw.x, q), submod(t2.y, cw.y, q)};
+      const v2u64 o = (v2u64){submod(t2.x, reduce_word(cw.x, m), q), submod(t2.y, reduce_word(cw.y, m), q)};
       *reinterpret_cast<v2u64*>(noisy + ((size_t)row * nv + v) * P + f) = o;
     }
   }

@@ -235,10 +235,13 @@ inline size_t yd_bytes(u32 nv, u32 k, u32 L, u32 ell) { return (size_t)((nv + 3)
 // K tiles (32 contraction rows each) of the digit GEMM.  bytes = 8: a tile is 4 consecutive j x the 8 bytes of the matrix
 // element.  bytes = 7 (every modulus below 2^56, k a multiple of 64): byte 7 of every element is zero and is left out of
 // the contraction -- a tile is one byte position a < 7 of 32 consecutive j, 7 tiles per 32 j instead of 8 (gemm7_ok).
+// launch_mftile with bytes = 7 reduces every element mod `mods` of its limb first (required then): a caller's word may be
+// >= 2^56 while its residue is not.
 inline u32 gemm_ktiles(u32 k, u32 bytes) { return bytes == 7 ? 7 * (k / 32) : (k + 3) / 4; }
 inline bool gemm7_ok(u32 max_q_bits, u32 k) { return max_q_bits <= 56 && k % 64 == 0 && k >= 64; }
 inline size_t sy_bytes(u32 nv, u32 L, u32 ell) { return (size_t)((nv + 3) / 4) * L * ell * 32 * sizeof(int); }
-hipError_t launch_mftile(const u64* src, bool src_is_tiled, u64* XM, u32 rows, u32 k, u32 L, u32 ell, hipStream_t s, u32 bytes = 8);
+hipError_t launch_mftile(const u64* src, bool src_is_tiled, u64* XM, u32 rows, u32 k, u32 L, u32 ell, hipStream_t s, u32 bytes = 8,
+                         const Mod* mods = nullptr);
 // small coefficients [row][j][l] -> NTT -> MFMA-tiled raw operand in one pass (l <= 32); padding included
 hipError_t launch_shat_mftile(const i64* coeffs, u64* XM, u32 rows, u32 k, u32 L, u32 ell, const DevTables& t, hipStream_t s);
 // element j of vector v at (limb, slot): vhat[v * vstride + limb * lstride + j * jstride + slot];

@@ -113,8 +113,8 @@ __global__ __launch_bounds__(64) void ntt_poly_kernel(u64* __restrict__ polys, u
 #pragma unroll
   for (int s = 0; s < ELL; s += 2) {
     v2u64 v = *reinterpret_cast<const v2u64*>(p + s);
-    a[s] = v.x;
-    a[s + 1] = v.y;
+    a[s] = reduce_word(v.x, m);                    // caller words (pvw_ntt_*, power-basis ciphertexts): w means w mod q
+    a[s + 1] = reduce_word(v.y, m);
   }
   if (inverse) ntt_inverse<ELL>(a, t.itw + (size_t)limb * ELL, t.itwp + (size_t)limb * ELL, t.linv[limb], t.linvp[limb], m);
   else ntt_forward<ELL>(a, t.tw + (size_t)limb * ELL, t.twp + (size_t)limb * ELL, m);
@@ -144,8 +144,8 @@ __global__ __launch_bounds__(256) void ntt_kernel(u64* __restrict__ polys, u32 c
   u64* a = buf + (threadIdx.x / H) * ELL;
   if (on) {
     const v2u64 v = *reinterpret_cast<const v2u64*>(p);
-    a[2 * b] = v.x;
-    a[2 * b + 1] = v.y;
+    a[2 * b] = reduce_word(v.x, m);                // as ntt_poly_kernel
+    a[2 * b + 1] = reduce_word(v.y, m);
   }
   __builtin_amdgcn_wave_barrier();
   if (inverse) {
@@ -208,7 +208,12 @@ __global__ __launch_bounds__(256) void tile_kernel(const u64* __restrict__ src, 
     a[s] = v.x;
     a[s + 1] = v.y;
   }
-  if (ntt_first) ntt_forward<ELL>(a, t.tw + (size_t)limb * ELL, t.twp + (size_t)limb * ELL, t.mods[limb]);
+  if (ntt_first) {                                 // the transform needs words below q; without it the words are stored as given
+    const Mod m = t.mods[limb];
+#pragma unroll
+    for (int s = 0; s < ELL; ++s) a[s] = reduce_word(a[s], m);
+    ntt_forward<ELL>(a, t.tw + (size_t)limb * ELL, t.twp + (size_t)limb * ELL, m);
+  }
   const u32 trow = row0_tiled + row;
   u64* o = M + (((size_t)(trow / R) * L + limb) * k + j) * 128 + (trow % R) * ELL;
 #pragma unroll
@@ -235,7 +240,12 @@ __global__ __launch_bounds__(256) void untile_kernel(const u64* __restrict__ M, 
     a[s] = v.x;
     a[s + 1] = v.y;
   }
-  if (intt_after) ntt_inverse<ELL>(a, t.itw + (size_t)limb * ELL, t.itwp + (size_t)limb * ELL, t.linv[limb], t.linvp[limb], t.mods[limb]);
+  if (intt_after) {                                // an NTT-domain load keeps the caller's words: reduce them before the transform
+    const Mod m = t.mods[limb];
+#pragma unroll
+    for (int s = 0; s < ELL; ++s) a[s] = reduce_word(a[s], m);
+    ntt_inverse<ELL>(a, t.itw + (size_t)limb * ELL, t.itwp + (size_t)limb * ELL, t.linv[limb], t.linvp[limb], m);
+  }
   u64* o = dst + tid * ELL;
 #pragma unroll
   for (int s = 0; s < ELL; s += 2)

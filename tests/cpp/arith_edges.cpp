@@ -1,11 +1,14 @@
 // Host check of pvw_rs_amd/csrc/pvw_arith.h (the arithmetic every kernel is built from) against unsigned __int128 `%`,
 // for the moduli given on stdin (decimal, whitespace-separated): reduce128, mulmod, mulmod_shoup, signed_residue, the lazy
 // accumulator up to its 2^32-term bound, the l-point NTT against direct evaluation, and the digit step of the GEMM operands
-// (mul256_consts + mulmod_shoup).  Prints one "FAIL <what> q=<q> ..." line per failing (check, modulus) and ends with
+// (mul256_consts + mulmod_shoup), and reduce_word on unreduced caller words: alone, ahead of the l-point NTTs and ahead
+// of the balanced digits of the GEMM operands.  Prints one "FAIL <what> q=<q> ..." line per failing (check, modulus) and ends with
 // "ARITH_EDGES_OK <moduli>" when nothing failed.
 //
 // -DPVW_PARENT_DIGIT_STEP: the digit step through the constant pair the kernels used before mul256_consts (w = 256,
 // wp = floor(2^128 / q) >> 56), which the test suite expects to fail exactly for q < 256.
+// -DPVW_RAW_WORDS: the unreduced words go into the NTTs and the digits without reduce_word, as the kernels took them
+// before it; the test suite expects the raw_words checks to fail then.
 #include <cinttypes>
 #include <cstdio>
 #include <set>
@@ -219,6 +222,84 @@ static void check_ntt(u64 q, const Mod& m) {
   }
 }
 
+// the unreduced word classes of the residue-word contract (include/pvw_hip.h): w means w mod q for any 64-bit w
+static std::vector<u64> raw_words(u64 q) {
+  const u64 w = next_u64() % q;
+  std::vector<u64> v = {q - 1, q, 2 * q - 1, w + q, w + (~0ULL - w) / q * q, (1ULL << 56) - 1, 1ULL << 56, 1ULL << 61,
+                        1ULL << 62, (1ULL << 63) - (1ULL << 55) - 1, (1ULL << 63) - (1ULL << 55), 1ULL << 63, 0 - q, ~0ULL};
+  for (int i = 0; i < 16; ++i) v.push_back(next_u64());
+  return v;
+}
+
+static u64 load_word(u64 w, const Mod& m) {   // what a kernel does with a caller's word at its load
+#ifdef PVW_RAW_WORDS
+  (void)m;
+  return w;
+#else
+  return reduce_word(w, m);
+#endif
+}
+
+static void check_reduce_word(u64 q, const Mod& m, const std::vector<u64>& ops) {
+  std::vector<u64> ws = raw_words(q);
+  ws.insert(ws.end(), ops.begin(), ops.end());
+  for (u64 w : ws) check(reduce_word(w, m) == w % q, "reduce_word", q, w);
+  // the balanced base-256 digits of the GEMM operands ((w + C) ^ C, vec_digits_kernel) rebuild the loaded word exactly
+  const u64 C = 0x8080808080808080ULL;
+  for (u64 w : ws) {
+    const u64 x = load_word(w, m), d = (x + C) ^ C;
+    __int128 v = 0;
+    for (int b = 7; b >= 0; --b) v = v * 256 + (signed char)(d >> (8 * b));
+    check(v >= 0 && (u64)v % q == w % q, "raw_words.digits", q, w);
+  }
+}
+
+// an l-point NTT of rows of unreduced words (one class per row, and rows mixing them) against the transform of the words
+// reduced: every slot below q and equal
+template <int L_>
+static void check_ntt_raw(u64 q, const Mod& m) {
+  if ((q - 1) % (2 * L_) != 0) return;
+  u64 psi = 0;
+  for (u64 g = 2; g < q && !psi; ++g) {
+    const u64 c = ref_pow(g, (q - 1) / (2 * L_), q);
+    if (ref_pow(c, L_, q) == q - 1) psi = c;
+  }
+  if (!psi) return;
+  const u64 ipsi = ref_pow(psi, q - 2, q);
+  u32 bits = 0;
+  while ((1 << bits) < L_) ++bits;
+  u64 tw[L_], twp[L_], itw[L_], itwp[L_];
+  for (int i = 0; i < L_; ++i) {
+    tw[i] = ref_pow(psi, bitrev32(i, bits), q);
+    twp[i] = shoup_precompute(tw[i], q);
+    itw[i] = ref_pow(ipsi, bitrev32(i, bits), q);
+    itwp[i] = shoup_precompute(itw[i], q);
+  }
+  const u64 linv = ref_pow(L_, q - 2, q), linvp = shoup_precompute(linv, q);
+  const std::vector<u64> ws = raw_words(q);
+  const char* fw = L_ == 8 ? "raw_words.ntt_forward.8" : L_ == 16 ? "raw_words.ntt_forward.16" : L_ == 32 ? "raw_words.ntt_forward.32" : "raw_words.ntt_forward.64";
+  const char* iv = L_ == 8 ? "raw_words.ntt_inverse.8" : L_ == 16 ? "raw_words.ntt_inverse.16" : L_ == 32 ? "raw_words.ntt_inverse.32" : "raw_words.ntt_inverse.64";
+  for (size_t row = 0; row < ws.size() + 4; ++row) {
+    u64 raw[L_], a[L_], b[L_], ra[L_], rb[L_];
+    for (int j = 0; j < L_; ++j) raw[j] = row < ws.size() ? ws[row] - (u64)j * (row & 1) : ws[(row + 3 * j) % ws.size()];
+    for (int j = 0; j < L_; ++j) {
+      a[j] = b[j] = load_word(raw[j], m);
+      ra[j] = rb[j] = raw[j] % q;
+    }
+    ntt_forward<L_>(a, tw, twp, m);
+    ntt_forward<L_>(ra, tw, twp, m);
+    ntt_inverse<L_>(b, itw, itwp, linv, linvp, m);
+    ntt_inverse<L_>(rb, itw, itwp, linv, linvp, m);
+    bool okf = true, oki = true;
+    for (int s = 0; s < L_; ++s) {
+      okf = okf && a[s] == ra[s] && a[s] < q;
+      oki = oki && b[s] == rb[s] && b[s] < q;
+    }
+    check(okf, fw, q, raw[0]);
+    check(oki, iv, q, raw[0]);
+  }
+}
+
 int main() {
   std::vector<u64> moduli;
   unsigned long long q;
@@ -233,6 +314,11 @@ int main() {
     check_ntt<16>(qq, m);
     check_ntt<32>(qq, m);
     check_ntt<64>(qq, m);
+    check_reduce_word(qq, m, ops);
+    check_ntt_raw<8>(qq, m);
+    check_ntt_raw<16>(qq, m);
+    check_ntt_raw<32>(qq, m);
+    check_ntt_raw<64>(qq, m);
   }
   if (g_fail) return 1;
   printf("ARITH_EDGES_OK %zu\n", moduli.size());

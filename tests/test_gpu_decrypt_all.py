@@ -199,6 +199,15 @@ def test_unreduced_and_extreme_words(hi):
     got2 = _all(p, lo, hi, sk, c1, c2u)
     _check_against_per_party(p, lo, hi, sk, c1, c2u, got2, parties=range(min(hi - lo, 6)))
     assert np.array_equal(got2[:, :6], base[:, :6])
+    # a word w means w mod q: the modified dealers equal the oracle on the reduced words (and so does the per-party path)
+    m = M.Params(48, 32, 8, EXAMPLE_MODULI)
+    orc = O.Oracle(EXAMPLE_MODULI, 8)
+    for got, c1x, c2x in ((got1, c1u, c2), (got2, c1, c2u)):
+        for i in sorted({0, 1, hi - lo - 1}):
+            noisy = orc.decrypt_noisy(sk[i], c1x % q, c2x[:, lo + i] % q)
+            want = [M.decode_scalar_pvw(rns_to_ring(noisy[d], EXAMPLE_MODULI), m) for d in range(D)]
+            assert [int(v) for v in got[i]] == want, f"party {lo + i}"
+            assert [int(v) for v in _per_party(p, sk[i], c1x, c2x[:, lo + i])] == want
 
 
 def _device_variant_body():

@@ -645,7 +645,14 @@ def test_digit_gemm_seven_byte_extreme_matrix_bytes(n, k, l, L, D):
     digit_gemm_extreme_case(n, k, l, EXAMPLE_MODULI[:L], D)
 
 
-def digit_gemm_extreme_case(n, k, l, moduli, D):
+@pytest.mark.parametrize("moduli", [M.bench_moduli(2), EXAMPLE_MODULI[:2]], ids=["61-bit: 8-byte", "56-bit: 7-byte"])
+def test_digit_gemm_extreme_matrix_bytes_kept_raw(moduli):
+    # the same byte patterns kept as the raw words they are (0xFF.., 0x80.., ... >= q): a word w means w mod q, so the
+    # ciphertexts must be the oracle's on the reduced matrices (the 7-byte operand holds 7 bytes of the REDUCED word)
+    digit_gemm_extreme_case(64, 256, 8, moduli, 20, raw=True)
+
+
+def digit_gemm_extreme_case(n, k, l, moduli, D, raw=False):
     L = len(moduli)
     p = build_params(n, k, l, moduli)
     rng = np.random.default_rng(k + l)
@@ -662,12 +669,17 @@ def digit_gemm_extreme_case(n, k, l, moduli, D):
                 m[i] = np.uint64(pats[(i // 3 + i) % len(pats)])
         m[0] = 0
         m[1 % rows] = np.uint64(0xFFFFFFFFFFFFFFFF)
+        if raw:
+            return m
         bits = np.uint64(max(moduli).bit_length())
         return np.minimum(m % (np.uint64(1) << bits), q - np.uint64(1))   # residues below q with the byte patterns intact
 
     a_hat, b_hat = patterned(k), patterned(n)
     gpk = P.GlobalPublicKey.new(P.PvwCrs.from_polynomials(p, a_hat, P.REPR_NTT))
     gpk.load_rows(0, b_hat, P.REPR_NTT)
+    if raw:
+        assert (a_hat >= q).any() and (b_hat >= q).any()
+        a_hat, b_hat = a_hat % q, b_hat % q                              # what the oracle takes
     rows = [[int(x) for x in rng.integers(0, 1 << 64, size=n, dtype=np.uint64)] for _ in range(D)]
     seeds = [P.api._dealer_seed(SEED, d) for d in range(D)]
     many = P.encrypt_many(rows, gpk, seeds)
