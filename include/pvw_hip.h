@@ -163,6 +163,9 @@ PVW_API int32_t pvw_ctx_q_total(const pvw_ctx* ctx, uint64_t* words, size_t cap,
 PVW_API int32_t pvw_ctx_gadget(const pvw_ctx* ctx, uint64_t* poly_out /*[L][l]*/, uint32_t repr);
 /* verify_correctness_condition (parameters.rs:510-551) */
 PVW_API int32_t pvw_ctx_verify_correctness_condition(const pvw_ctx* ctx, int32_t* ok_out);
+/* the total_bound of verify_correctness_condition (parameters.rs:516-543): the three terms summed in f64 in the reference's
+ * order, floored and saturated to u64.  The noise a checked decrypt reports is compared with it. */
+PVW_API int32_t pvw_ctx_noise_bound(const pvw_ctx* ctx, uint64_t* out);
 /* suggest_error_bounds (parameters.rs:554-603) */
 PVW_API int32_t pvw_suggest_error_bounds(uint32_t n, uint32_t k, uint32_t l, const uint64_t* moduli,
                                  uint32_t num_moduli, float variance, uint32_t* bound1_out,
@@ -337,6 +340,52 @@ PVW_API int32_t pvw_decrypt_all(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_
 PVW_API int32_t pvw_decrypt_all_device(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* d_sk,
                                        const uint64_t* d_c1s, const uint64_t* d_c2s, size_t num_dealers,
                                        uint32_t in_repr, uint64_t* d_out, void* stream);
+/* ---- checked decryption: each share's noise and whether its decode was lossy --------------------------
+ * For a noisy polynomial z (power basis) let P be the decode's plaintext before the u64 conversion, centre(-z_0 - noise_0)
+ * (decryption.rs:51-53).  Then residual_i = centre(-z_i - P Delta^i mod Q), i = 0 .. l-1, centre into (-Q/2, Q/2], and
+ *   noise[d]  = min(max_i |residual_i|, 2^64 - 1)         (exact below 2^64 - 1, saturating above)
+ *   status[d] = PVW_DEC_LOSSY when the returned word is not P (P < 0 or P >= 2^64: the conversion of :226-247 decided it,
+ *               "small negative -> 0" included); every other bit 0
+ *   out[d]    = the word the unchecked entry point returns on the same input words, bit for bit.
+ * For an honest ciphertext residual is the decryption noise s e1 - e r - e2 (up to sign); for garbage noise saturates.
+ * noise and status may each be NULL.  Every entry below extends the one it names and keeps its argument rules. */
+enum { PVW_DEC_LOSSY = 1 };
+/* extends pvw_decrypt_batch (host buffers): noise [D], status [D] */
+PVW_API int32_t pvw_decrypt_batch_checked(pvw_ctx* ctx, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col,
+                                          size_t num_dealers, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise,
+                                          uint32_t* status);
+/* extends pvw_decrypt_batch_device: d_noise [D], d_status [D] on the device */
+PVW_API int32_t pvw_decrypt_batch_checked_device(pvw_ctx* ctx, const int64_t* d_sk, const uint64_t* d_c1s,
+                                                 const uint64_t* d_c2col, size_t num_dealers, uint32_t in_repr,
+                                                 uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status,
+                                                 void* stream);
+/* extends pvw_decrypt_batch_device_sk */
+PVW_API int32_t pvw_decrypt_batch_device_sk_checked(pvw_ctx* ctx, const pvw_sk* key, const uint64_t* d_c1s,
+                                                    const uint64_t* d_c2col, size_t num_dealers, uint32_t in_repr,
+                                                    uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise,
+                                                    uint32_t* d_status, void* stream);
+/* extend pvw_decrypt_all / pvw_decrypt_all_device: noise / status [P][D] like out (both sides of the 22-party dispatch) */
+PVW_API int32_t pvw_decrypt_all_checked(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* sk,
+                                        const uint64_t* c1s, const uint64_t* c2s, size_t num_dealers, uint32_t in_repr,
+                                        uint64_t* out_u64, uint64_t* noise, uint32_t* status);
+PVW_API int32_t pvw_decrypt_all_checked_device(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* d_sk,
+                                               const uint64_t* d_c1s, const uint64_t* d_c2s, size_t num_dealers,
+                                               uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status,
+                                               void* stream);
+/* extends pvw_decode (host buffers, decode on the device) */
+PVW_API int32_t pvw_decode_checked(pvw_ctx* ctx, const uint64_t* noisy, size_t count, uint64_t* out_u64, uint64_t* noise,
+                                   uint32_t* status);
+/* extends pvw_decode_device */
+PVW_API int32_t pvw_decode_checked_device(pvw_ctx* ctx, const uint64_t* d_noisy, size_t count, uint64_t* d_out,
+                                          uint64_t* d_noise, uint32_t* d_status, void* stream);
+/* extends pvw_decode_host: host big integers, residuals by the definition above (no GPU needed) */
+PVW_API int32_t pvw_decode_checked_host(const pvw_ctx* ctx, const uint64_t* noisy, size_t count, uint64_t* out_u64,
+                                        uint64_t* noise, uint32_t* status);
+/* extends pvw_selftest_decode_fixed: the fixed-width device decode with its report, run on the host (the recurrence
+ * residual_{i+1} = Delta residual_i + tmp_i on the residues, one lift a step).  No product path calls it. */
+PVW_API int32_t pvw_selftest_decode_checked(const pvw_ctx* ctx, const uint64_t* noisy, size_t count, uint64_t* out_u64,
+                                            uint64_t* noise, uint32_t* status);
+
 /* decode_scalar_pvw_rns alone, on the device: noisy [D][L][l] power basis (host) -> out_u64 [D] */
 PVW_API int32_t pvw_decode(pvw_ctx* ctx, const uint64_t* noisy, size_t count, uint64_t* out_u64);
 /* the same with host big integers on the host cores (no GPU needed): an independent

@@ -91,6 +91,16 @@ _SIGNATURES = {
     "pvw_decrypt_batch_device_sk": [_P, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P],
     "pvw_decrypt_all": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, C.c_uint32, _P],
     "pvw_decrypt_all_device": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P],
+    "pvw_decrypt_batch_checked": [_P, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P],
+    "pvw_decrypt_batch_checked_device": [_P, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, _P, _P],
+    "pvw_decrypt_batch_device_sk_checked": [_P, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, _P, _P],
+    "pvw_decrypt_all_checked": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P],
+    "pvw_decrypt_all_checked_device": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, _P],
+    "pvw_decode_checked": [_P, _P, C.c_size_t, _P, _P, _P],
+    "pvw_decode_checked_device": [_P, _P, C.c_size_t, _P, _P, _P, _P],
+    "pvw_decode_checked_host": [_P, _P, C.c_size_t, _P, _P, _P],
+    "pvw_selftest_decode_checked": [_P, _P, C.c_size_t, _P, _P, _P],
+    "pvw_ctx_noise_bound": [_P, C.POINTER(C.c_uint64)],
     "pvw_decode": [_P, _P, C.c_size_t, _P],
     "pvw_decode_host": [_P, _P, C.c_size_t, _P],
     "pvw_decode_device": [_P, _P, C.c_size_t, _P, _P],

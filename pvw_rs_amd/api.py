@@ -215,6 +215,13 @@ class PvwParameters:
         self._call("pvw_ctx_verify_correctness_condition", C.byref(ok))
         return bool(ok.value)
 
+    def noise_bound(self) -> int:
+        """total_bound of verify_correctness_condition (parameters.rs:516-543), floored and saturated to u64: the default
+        bound a checked decrypt's noise is held to."""
+        v = C.c_uint64()
+        self._call("pvw_ctx_noise_bound", C.byref(v))
+        return int(v.value)
+
     @staticmethod
     def suggest_error_bounds(n, k, l, moduli, variance) -> Tuple[int, int]:   # :554-603
         m = _u64(list(moduli))
@@ -755,6 +762,129 @@ def decrypt_all_party_shares(all_ciphertexts: Sequence[PvwCiphertext], parties: 
     return decrypt_many(all_ciphertexts, [party.secret_key for party in parties], lo)
 
 
+# ---- checked decryption ----
+DEC_LOSSY = 1    # status bit: the returned word is not the plaintext P (P < 0 or P >= 2^64)
+
+
+class CheckedDecryption:
+    """What a checked decrypt reports per share: values (the words the unchecked call returns), noise (min(max_i
+    |residual_i|, 2^64 - 1), uint64), lossy (the value is not the plaintext) and valid = ~lossy & (noise <= bound).  Arrays
+    of one shape: [D] for one party, [parties][D] for many."""
+
+    def __init__(self, values: np.ndarray, noise: np.ndarray, status: np.ndarray, bound: int):
+        self.values = values
+        self.noise = noise
+        self.status = status
+        self.lossy = (status & DEC_LOSSY) != 0
+        self.bound = int(bound)
+        self.valid = ~self.lossy & (noise <= np.uint64(min(self.bound, (1 << 64) - 1)))
+
+    def __iter__(self):                                                     # values, noise, lossy, valid = ...
+        return iter((self.values, self.noise, self.lossy, self.valid))
+
+
+def _bound(p: "PvwParameters", bound) -> int:
+    b = p.noise_bound() if bound is None else int(bound)
+    if b < 0:
+        raise PvwError(1, "the noise bound must be non-negative")
+    return b
+
+
+def decrypt_party_shares_checked(all_ciphertexts: Sequence[PvwCiphertext], secret_key: SecretKey, party_index: int,
+                                 bound: Optional[int] = None) -> CheckedDecryption:
+    """decrypt_party_shares (decryption.rs:281-325) with each share's report (pvw_decrypt_batch_checked): the same
+    checks and values, plus noise / lossy / valid against `bound` (default: noise_bound())."""
+    if len(all_ciphertexts) == 0:
+        raise PvwError(1, "No ciphertexts provided")
+    p = all_ciphertexts[0].params
+    if len(all_ciphertexts) != p.n:
+        raise PvwError(1, f"Expected {p.n} ciphertexts, got {len(all_ciphertexts)}")
+    if party_index >= p.n:
+        raise PvwError(1, f"Party index {party_index} exceeds maximum {p.n - 1}")
+    for d, ct in enumerate(all_ciphertexts):
+        try:
+            ct.validate()
+        except PvwError as e:
+            raise PvwError(1, f"Ciphertext {d} invalid: {e}")
+    return _decrypt_batch_checked(p, all_ciphertexts, secret_key, party_index, _bound(p, bound))
+
+
+def decrypt_party_value_checked(ciphertext: PvwCiphertext, secret_key: SecretKey, party_index: int,
+                                bound: Optional[int] = None) -> Tuple[int, int, bool, bool]:
+    """decrypt_party_value (decryption.rs:249-278) with its report: (value, noise, lossy, valid)."""
+    r = _decrypt_batch_checked(ciphertext.params, [ciphertext], secret_key, party_index, _bound(ciphertext.params, bound))
+    return int(r.values[0]), int(r.noise[0]), bool(r.lossy[0]), bool(r.valid[0])
+
+
+def _decrypt_batch_checked(p, cts, secret_key, party_index, bound) -> CheckedDecryption:
+    repr = cts[0].repr
+    c1s = np.ascontiguousarray(np.stack([ct.c1 for ct in cts]), dtype=np.uint64)
+    c2col = np.ascontiguousarray(np.stack([ct.c2[party_index] for ct in cts]), dtype=np.uint64)
+    sk = _i64(secret_key.secret_coeffs)
+    out = np.zeros(len(cts), dtype=np.uint64)
+    noise = np.zeros(len(cts), dtype=np.uint64)
+    status = np.zeros(len(cts), dtype=np.uint32)
+    p._call("pvw_decrypt_batch_checked", _ptr(sk), _ptr(c1s), _ptr(c2col), len(cts), repr, _ptr(out), _ptr(noise),
+            _ptr(status))
+    return CheckedDecryption(out, noise, status, bound)
+
+
+def decrypt_many_checked(ciphertexts: Sequence[PvwCiphertext], secret_keys: Sequence[SecretKey], party_lo: int,
+                         bound: Optional[int] = None) -> CheckedDecryption:
+    """decrypt_many with each share's report (pvw_decrypt_all_checked): values, noise, lossy, valid as [parties][D]."""
+    if len(ciphertexts) == 0:
+        raise PvwError(1, "No ciphertexts provided")
+    p = ciphertexts[0].params
+    for d, ct in enumerate(ciphertexts):
+        try:
+            ct.validate()
+        except PvwError as e:
+            raise PvwError(1, f"Ciphertext {d} invalid: {e}")
+    b = _bound(p, bound)
+    shape = (len(secret_keys), len(ciphertexts))
+    if len(secret_keys) == 0:
+        return CheckedDecryption(np.zeros(shape, np.uint64), np.zeros(shape, np.uint64), np.zeros(shape, np.uint32), b)
+    repr = ciphertexts[0].repr
+    if any(ct.repr != repr for ct in ciphertexts):
+        raise PvwError(18, "ciphertexts in different representations")
+    c1s = np.ascontiguousarray(np.stack([ct.c1 for ct in ciphertexts]), dtype=np.uint64)
+    c2s = np.ascontiguousarray(np.stack([ct.c2 for ct in ciphertexts]), dtype=np.uint64)
+    sk = np.ascontiguousarray(np.stack([_i64(k.secret_coeffs) for k in secret_keys]))
+    out = np.zeros(shape, dtype=np.uint64)
+    noise = np.zeros(shape, dtype=np.uint64)
+    status = np.zeros(shape, dtype=np.uint32)
+    try:
+        p._call("pvw_decrypt_all_checked", party_lo, party_lo + len(secret_keys), _ptr(sk), _ptr(c1s), _ptr(c2s),
+                len(ciphertexts), repr, _ptr(out), _ptr(noise), _ptr(status))
+    finally:
+        sk.fill(0)                                                         # the stacked copy of the keys (secret_key.rs:20-30)
+    return CheckedDecryption(out, noise, status, b)
+
+
+def decrypt_all_party_shares_checked(all_ciphertexts: Sequence[PvwCiphertext], parties: Sequence["Party"],
+                                     bound: Optional[int] = None) -> CheckedDecryption:
+    """decrypt_all_party_shares with each share's report: its checks, then decrypt_many_checked."""
+    if len(all_ciphertexts) == 0:
+        raise PvwError(1, "No ciphertexts provided")
+    p = all_ciphertexts[0].params
+    if len(all_ciphertexts) != p.n:
+        raise PvwError(1, f"Expected {p.n} ciphertexts, got {len(all_ciphertexts)}")
+    lo = parties[0].index if len(parties) else 0
+    for i, party in enumerate(parties):
+        if party.index >= p.n:
+            raise PvwError(1, f"Party index {party.index} exceeds maximum {p.n - 1}")
+        if party.index != lo + i:
+            raise PvwError(1, f"Party indices must be consecutive: {party.index} follows {lo + i - 1}")
+    return decrypt_many_checked(all_ciphertexts, [party.secret_key for party in parties], lo, bound)
+
+
+def _dptr(x):
+    """a device buffer: a torch tensor (its data_ptr()), a raw address as an int, or None"""
+    if x is None:
+        return None
+    return C.c_void_p(int(x.data_ptr() if hasattr(x, "data_ptr") else x) or None)
+
+
 class DeviceSecretKey:
     """pvw_sk: a SecretKey's NTT form on the device (pvw_sk_load); cleared by free() / on drop (pvw_sk_free), as the
     reference's SecretKey is ZeroizeOnDrop (secret_key.rs:20-30).  Use as a context manager or call free()."""
@@ -770,6 +900,15 @@ class DeviceSecretKey:
         h, self._h = getattr(self, "_h", None), None
         if h:
             _check(_ffi.lib().pvw_sk_free(h))
+
+    def decrypt_device_checked(self, d_c1s, d_c2col, num_dealers: int, d_noisy, d_out, d_noise=None, d_status=None,
+                               stream=None, in_repr: int = REPR_NTT) -> None:
+        """pvw_decrypt_batch_device_sk_checked: device buffers (torch tensors or raw addresses) -- d_out [D] the values,
+        d_noise [D] uint64 and d_status [D] uint32 the report (either may be None); asynchronous on `stream`."""
+        if not self._h:
+            raise PvwError(1, "the DeviceSecretKey has been freed")
+        self.params._call("pvw_decrypt_batch_device_sk_checked", self._h, _dptr(d_c1s), _dptr(d_c2col), int(num_dealers),
+                          in_repr, _dptr(d_noisy), _dptr(d_out), _dptr(d_noise), _dptr(d_status), _stream_ptr(stream))
 
     def __enter__(self):
         return self
@@ -904,3 +1043,27 @@ def decode_scalar_pvw_host(params: PvwParameters, noisy: np.ndarray) -> List[int
     out = np.zeros(len(a), dtype=np.uint64)
     params._call("pvw_decode_host", _ptr(a), len(a), _ptr(out))
     return [int(v) for v in out]
+
+
+def _decode_checked(params: PvwParameters, noisy, fn: str, bound) -> CheckedDecryption:
+    a = _u64(noisy).reshape(-1, params.L, params.l)
+    out = np.zeros(len(a), dtype=np.uint64)
+    noise = np.zeros(len(a), dtype=np.uint64)
+    status = np.zeros(len(a), dtype=np.uint32)
+    params._call(fn, _ptr(a), len(a), _ptr(out), _ptr(noise), _ptr(status))
+    return CheckedDecryption(out, noise, status, _bound(params, bound))
+
+
+def decode_scalar_pvw_checked(params: PvwParameters, noisy: np.ndarray, bound: Optional[int] = None) -> CheckedDecryption:
+    """decode_scalar_pvw with each polynomial's report (pvw_decode_checked, on the device)."""
+    return _decode_checked(params, noisy, "pvw_decode_checked", bound)
+
+
+def decode_scalar_pvw_checked_host(params: PvwParameters, noisy: np.ndarray, bound: Optional[int] = None) -> CheckedDecryption:
+    """The same with host big integers, residuals by their definition (pvw_decode_checked_host; no GPU)."""
+    return _decode_checked(params, noisy, "pvw_decode_checked_host", bound)
+
+
+def _selftest_decode_checked(params: PvwParameters, noisy: np.ndarray) -> CheckedDecryption:
+    """Host run of the fixed-width device decode with its report (self-test hook, see pvw_hip.h)."""
+    return _decode_checked(params, noisy, "pvw_selftest_decode_checked", 0)

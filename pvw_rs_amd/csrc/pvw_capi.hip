@@ -387,6 +387,7 @@ static void build_decode_tables(pvw_ctx* c) {
     const bool room = BigInt::cmp(c->halfQ, c->delta_pow.shl(61) + c->delta) > 0;
     t.hs_on = (t.sc_on && all_inv && room && c->l >= 3 && c->moduli[0] < (1ULL << 62)) ? 1 : 0;
   }
+  t.ck_mul = BigInt::cmp(c->Q, c->delta.shl(64)) > 0 ? 1 : 0;   // Delta (2^64 - 1) < Q
   auto bind = [&](DecodeTables& d, const u64* base, const Mod* mods) {
     d = t;
     d.mods = mods;
@@ -748,6 +749,14 @@ int32_t pvw_ctx_verify_correctness_condition(const pvw_ctx* c, int32_t* ok) {
   if (!c || !ok) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   double bound = correctness_bound((double)c->n, (double)c->k, (double)c->l, (double)c->b1, (double)c->b2);
   *ok = c->delta_pow.to_double() > bound ? 1 : 0;   // parameters.rs:547-550 (to_f64 saturates to +inf)
+  return PVW_OK;
+}
+
+// total_bound of verify_correctness_condition (parameters.rs:516-543), the f64 sum floored and saturated to u64
+int32_t pvw_ctx_noise_bound(const pvw_ctx* c, uint64_t* out) {
+  if (!c || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const double b = std::floor(correctness_bound((double)c->n, (double)c->k, (double)c->l, (double)c->b1, (double)c->b2));
+  *out = !(b >= 0.0) ? 0 : (b >= 18446744073709551616.0 ? ~(uint64_t)0 : (uint64_t)b);
   return PVW_OK;
 }
 
@@ -2035,10 +2044,12 @@ static BigInt crt_lift(const pvw_ctx* c, const uint64_t* poly, u32 coeff) {
   }
   return acc % c->Q;
 }
-static uint64_t decode_one(const pvw_ctx* c, const uint64_t* noisy) {   // decryption.rs:10-58
+// the plaintext before the u64 conversion, P = centre(-z_0 - noise_0) (decryption.rs:10-53); z: the centred coefficients
+static BigInt decode_plain(const pvw_ctx* c, const uint64_t* noisy, std::vector<BigInt>& z) {
   const u32 l = c->l;
   const BigInt &Q = c->Q, &D = c->delta;
-  std::vector<BigInt> z(l), tmp(l), noise(l);
+  std::vector<BigInt> tmp(l), noise(l);
+  z.assign(l, BigInt());
   for (u32 j = 0; j < l; ++j) z[j] = center(crt_lift(c, noisy, j), c);                  // :109-137
   for (u32 i = 0; i + 1 < l; ++i) tmp[i] = (z[i] * D - z[i + 1]).mod_floor(Q);          // :19-27
   BigInt last = tmp[0];
@@ -2064,7 +2075,10 @@ static uint64_t decode_one(const pvw_ctx* c, const uint64_t* noisy) {   // decry
     }
     noise[i] = quo.mod_floor(Q);
   }
-  BigInt plain = center((-z[0] - noise[0]).mod_floor(Q), c);                            // :51-53
+  return center((-z[0] - noise[0]).mod_floor(Q), c);                                    // :51-53
+}
+static uint64_t decode_convert(const pvw_ctx* c, const BigInt& plain) {
+  const BigInt& Q = c->Q;
   if (plain.is_negative()) {                                                            // :226-247
     BigInt abs = -plain;
     if (abs <= BigInt(1000)) return 0;
@@ -2072,6 +2086,10 @@ static uint64_t decode_one(const pvw_ctx* c, const uint64_t* noisy) {   // decry
     return pos.fits_u64() ? pos.low_u64() : 0;
   }
   return plain.fits_u64() ? plain.low_u64() : 0;
+}
+static uint64_t decode_one(const pvw_ctx* c, const uint64_t* noisy) {   // decryption.rs:10-58
+  std::vector<BigInt> z;
+  return decode_convert(c, decode_plain(c, noisy, z));
 }
 
 int32_t pvw_decode_host(const pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out) {
@@ -2090,6 +2108,46 @@ int32_t pvw_decode_host(const pvw_ctx* c, const uint64_t* noisy, size_t count, u
     th.emplace_back([=]() {
       for (size_t d = t; d < count; d += nt) out[d] = decode_one(c, noisy + d * P);
     });
+  for (auto& x : th) x.join();
+  return PVW_OK;
+}
+
+// checked decode on the host: residual_i = centre(-z_i - P Delta^i) by the definition, in big integers (not the
+// recurrence the device runs); noise = min(max_i |residual_i|, 2^64 - 1), status = DEC_LOSSY when out is not P
+static void decode_checked_one(const pvw_ctx* c, const uint64_t* noisy, u64* out, u64* noise, u32* status) {
+  std::vector<BigInt> z;
+  const BigInt plain = decode_plain(c, noisy, z);
+  *out = decode_convert(c, plain);
+  if (status) *status = (plain.is_negative() || !plain.fits_u64()) ? (u32)DEC_LOSSY : 0u;
+  if (!noise) return;
+  const BigInt sat(~(u64)0);
+  BigInt dpow(1), mx;
+  for (u32 i = 0; i < c->l; ++i) {
+    BigInt r = center((-z[i] - plain * dpow).mod_floor(c->Q), c);
+    if (r.is_negative()) r = -r;
+    if (BigInt::cmp(r, mx) > 0) mx = r;
+    dpow = dpow * c->delta;
+  }
+  *noise = BigInt::cmp(mx, sat) >= 0 ? PVW_NOISE_SAT : mx.low_u64();
+}
+int32_t pvw_decode_checked_host(const pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out, uint64_t* noise,
+                                uint32_t* status) {
+  if (!c || ((!noisy || !out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const size_t P = c->poly();
+  unsigned nt = std::thread::hardware_concurrency();
+  if (nt == 0) nt = 1;
+  if (nt > 32) nt = 32;
+  if (count < 64) nt = 1;
+  auto run = [=](size_t d0, size_t step) {
+    for (size_t d = d0; d < count; d += step)
+      decode_checked_one(c, noisy + d * P, out + d, noise ? noise + d : nullptr, status ? status + d : nullptr);
+  };
+  if (nt == 1) {
+    run(0, 1);
+    return PVW_OK;
+  }
+  std::vector<std::thread> th;
+  for (unsigned t = 0; t < nt; ++t) th.emplace_back(run, (size_t)t, (size_t)nt);
   for (auto& x : th) x.join();
   return PVW_OK;
 }
@@ -2193,6 +2251,18 @@ int32_t pvw_selftest_decode_fixed(const pvw_ctx* c, const uint64_t* noisy, size_
   std::vector<u64> x(t.W + 1), y(t.W), nres(t.L);
   for (size_t d = 0; d < count; ++d)
     out[d] = decode_one_fixed(t, noisy + d * c->poly(), BN{x.data(), 1}, BN{y.data(), 1}, BN{nres.data(), 1});
+  return PVW_OK;
+}
+
+// the checked form of the same: decode_one_fixed<true>, the residual recurrence on the residues, one lift a step
+int32_t pvw_selftest_decode_checked(const pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out, uint64_t* noise,
+                                    uint32_t* status) {
+  if (!c || ((!noisy || !out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const DecodeTables& t = c->dec_host;
+  std::vector<u64> x(t.W + 1), y(t.W), nres(t.L);
+  for (size_t d = 0; d < count; ++d)
+    out[d] = decode_one_fixed<true>(t, noisy + d * c->poly(), BN{x.data(), 1}, BN{y.data(), 1}, BN{nres.data(), 1},
+                                      noise ? noise + d : nullptr, status ? status + d : nullptr);
   return PVW_OK;
 }
 
@@ -2321,6 +2391,46 @@ int32_t pvw_decode_device(pvw_ctx* c, const uint64_t* d_noisy, size_t count, uin
   return PVW_OK;
 }
 
+// checked decode: out as pvw_decode_device, plus noise[d] / status[d] (either may be NULL)
+int32_t pvw_decode_checked_device(pvw_ctx* c, const uint64_t* d_noisy, size_t count, uint64_t* d_out, uint64_t* d_noise,
+                                  uint32_t* d_status, void* stream) {
+  if (!c || ((!d_noisy || !d_out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (count == 0) return PVW_OK;
+  PVW_TRY(ensure_device(c));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  ProfScope ps(c, "decode", s);
+  PVW_HIP(launch_decode(const_cast<u64*>(d_noisy), d_out, count, c->dec_dev, s, nullptr, nullptr, 0, nullptr, d_noise, d_status));
+  return PVW_OK;
+}
+// host buffers in and out
+int32_t pvw_decode_checked(pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out, uint64_t* noise, uint32_t* status) {
+  if (!c || ((!noisy || !out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (count == 0) return PVW_OK;
+  PVW_TRY(ensure_device(c));
+  Workspace* w;
+  PVW_TRY(ws_acquire(c, &w));
+  const size_t inb = (count * c->poly() * 8 + 255) & ~(size_t)255, ob = (count * 8 + 255) & ~(size_t)255;
+  int32_t rc = ws_scratch(w, inb + 2 * ob + count * 4);
+  if (rc == PVW_OK) {
+    char* base = (char*)w->scratch;
+    u64* d_out = (u64*)(base + inb);
+    u64* d_ns = noise ? (u64*)(base + inb + ob) : nullptr;
+    u32* d_st = status ? (u32*)(base + inb + 2 * ob) : nullptr;
+    if (hipMemcpyAsync(base, noisy, count * c->poly() * 8, hipMemcpyHostToDevice, w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "H2D failed");
+    if (rc == PVW_OK) {
+      ProfScope ps(c, "decode", w->stream);
+      if (launch_decode((u64*)base, d_out, count, c->dec_dev, w->stream, nullptr, nullptr, 0, nullptr, d_ns, d_st) != hipSuccess)
+        rc = fail(PVW_ERR_INTERNAL, "decode launch failed");
+    }
+    if (rc == PVW_OK && (hipMemcpyAsync(out, d_out, count * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
+                         (noise && hipMemcpyAsync(noise, d_ns, count * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess) ||
+                         (status && hipMemcpyAsync(status, d_st, count * 4, hipMemcpyDeviceToHost, w->stream) != hipSuccess) ||
+                         hipStreamSynchronize(w->stream) != hipSuccess)) rc = fail(PVW_ERR_INTERNAL, "D2H failed");
+  }
+  ws_release(c, w);
+  return rc;
+}
+
 // ------------------------------------------------------------------------ decrypt
 // noisy[d] = sum_j s-hat[j] (.) c1s[d][j] - c2col[d]  for D ciphertexts (decryption.rs:257-274): the inner products as one
 // launch, cut into ranges of j when that gives the launch enough short workgroups (decrypt_split).  Returns in
@@ -2416,7 +2526,8 @@ struct pvw_sk {
   size_t bytes;
 };
 static int32_t decrypt_batch_core(pvw_ctx* c, const int64_t* d_sk, const u64* key_shat, const uint64_t* d_c1s, const uint64_t* d_c2col,
-                                  size_t D, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, void* stream);
+                                  size_t D, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, void* stream,
+                                  uint64_t* d_noise = nullptr, uint32_t* d_status = nullptr);
 int32_t pvw_decrypt_batch_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col,
                                  size_t D, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, void* stream) {
   if (!c || !d_sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
@@ -2427,6 +2538,20 @@ int32_t pvw_decrypt_batch_device_sk(pvw_ctx* c, const pvw_sk* key, const uint64_
   if (!c || !key || !key->shat) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   if (key->ctx != c) return fail(PVW_ERR_INVALID_PARAMETERS, "the key was loaded for another context");
   return decrypt_batch_core(c, nullptr, key->shat, d_c1s, d_c2col, D, in_repr, d_noisy, d_out, stream);
+}
+// checked forms: the same words in d_out, plus d_noise / d_status [D] (either may be NULL)
+int32_t pvw_decrypt_batch_checked_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
+                                         uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status,
+                                         void* stream) {
+  if (!c || !d_sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  return decrypt_batch_core(c, d_sk, nullptr, d_c1s, d_c2col, D, in_repr, d_noisy, d_out, stream, d_noise, d_status);
+}
+int32_t pvw_decrypt_batch_device_sk_checked(pvw_ctx* c, const pvw_sk* key, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
+                                            uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise,
+                                            uint32_t* d_status, void* stream) {
+  if (!c || !key || !key->shat) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (key->ctx != c) return fail(PVW_ERR_INVALID_PARAMETERS, "the key was loaded for another context");
+  return decrypt_batch_core(c, nullptr, key->shat, d_c1s, d_c2col, D, in_repr, d_noisy, d_out, stream, d_noise, d_status);
 }
 int32_t pvw_sk_load(pvw_ctx* c, const int64_t* sk, pvw_sk** out) {
   if (!c || !sk || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
@@ -2468,7 +2593,8 @@ int32_t pvw_sk_free(pvw_sk* key) {
   return rc;
 }
 static int32_t decrypt_batch_core(pvw_ctx* c, const int64_t* d_sk, const u64* key_shat, const uint64_t* d_c1s, const uint64_t* d_c2col,
-                                  size_t D, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, void* stream) {
+                                  size_t D, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, void* stream,
+                                  uint64_t* d_noise, uint32_t* d_status) {
   if (!c || ((!d_c1s || !d_c2col || !d_noisy || !d_out) && D)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   PVW_TRY(check_repr(in_repr));
   if (in_repr != PVW_REPR_NTT) return fail(PVW_ERR_INVALID_FORMAT, "device decrypt takes NTT-domain ciphertexts");
@@ -2527,7 +2653,8 @@ static int32_t decrypt_batch_core(pvw_ctx* c, const int64_t* d_sk, const u64* ke
     // one pass on one stream: the decode is the last launch to follow the inner products, and clears NTT(sk) on its way
     bool by_decode = false;
     PVW_HIP(launch_decode(nz, d_out + d0, cnt, c->dec_dev, ds, ntt_domain ? &c->dt : nullptr,                    // :116, :10-58
-                          overlap || key_shat ? nullptr : w->rhat, overlap || key_shat ? 0 : (size_t)k * P * 8, &by_decode));
+                          overlap || key_shat ? nullptr : w->rhat, overlap || key_shat ? 0 : (size_t)k * P * 8, &by_decode,
+                          d_noise ? d_noise + d0 : nullptr, d_status ? d_status + d0 : nullptr));
     if (by_decode) shat_wiped = true;
   }
   if (overlap) {
@@ -2553,8 +2680,18 @@ static int32_t decrypt_batch_core(pvw_ctx* c, const int64_t* d_sk, const u64* ke
   return rc != PVW_OK ? rc : rw;
 }
 
+static int32_t decrypt_batch_host(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
+                                  uint32_t in_repr, uint64_t* out_u64, uint64_t* noisy_out, uint64_t* noise, uint32_t* status);
 int32_t pvw_decrypt_batch(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
                           uint32_t in_repr, uint64_t* out_u64, uint64_t* noisy_out) {
+  return decrypt_batch_host(c, sk, c1s, c2col, D, in_repr, out_u64, noisy_out, nullptr, nullptr);
+}
+int32_t pvw_decrypt_batch_checked(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
+                                  uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status) {
+  return decrypt_batch_host(c, sk, c1s, c2col, D, in_repr, out_u64, nullptr, noise, status);
+}
+static int32_t decrypt_batch_host(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
+                                  uint32_t in_repr, uint64_t* out_u64, uint64_t* noisy_out, uint64_t* noise, uint32_t* status) {
   if (!c || !sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");          // decryption.rs:286-290
   if (!c1s || !c2col || !out_u64) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
@@ -2571,7 +2708,8 @@ int32_t pvw_decrypt_batch(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, co
   const size_t b_c1 = (per * k * P * 8 + 255) & ~(size_t)255;
   const size_t b_c2 = (per * P * 8 + 255) & ~(size_t)255;
   const size_t b_out = (per * 8 + 255) & ~(size_t)255;
-  int32_t rc = ws_scratch(w, b_sk + b_c1 + 2 * b_c2 + b_out);
+  const size_t b_ns = noise ? b_out : 0, b_st = status ? ((per * 4 + 255) & ~(size_t)255) : 0;
+  int32_t rc = ws_scratch(w, b_sk + b_c1 + 2 * b_c2 + b_out + b_ns + b_st);
   if (rc == PVW_OK) {
     char* base = (char*)w->scratch;
     i64* d_sk = (i64*)base;
@@ -2579,6 +2717,8 @@ int32_t pvw_decrypt_batch(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, co
     u64* d_c2 = (u64*)(base + b_sk + b_c1);
     u64* d_nz = (u64*)(base + b_sk + b_c1 + b_c2);
     u64* d_out = (u64*)(base + b_sk + b_c1 + 2 * b_c2);
+    u64* d_ns = noise ? (u64*)(base + b_sk + b_c1 + 2 * b_c2 + b_out) : nullptr;
+    u32* d_st = status ? (u32*)(base + b_sk + b_c1 + 2 * b_c2 + b_out + b_ns) : nullptr;
     if (hipMemcpyAsync(d_sk, sk, k * l * 8, hipMemcpyHostToDevice, w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "H2D failed");
     for (size_t d0 = 0; rc == PVW_OK && d0 < D; d0 += per) {
       const size_t cnt = (D - d0) < per ? (D - d0) : per;
@@ -2596,10 +2736,13 @@ int32_t pvw_decrypt_batch(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, co
       }
       if (rc == PVW_OK) {
         ProfScope ps(c, "decode", w->stream);
-        if (launch_decode(d_nz, d_out, cnt, c->dec_dev, w->stream, ntt_domain ? &c->dt : nullptr) != hipSuccess)
+        if (launch_decode(d_nz, d_out, cnt, c->dec_dev, w->stream, ntt_domain ? &c->dt : nullptr, nullptr, 0, nullptr, d_ns, d_st) !=
+            hipSuccess)
           rc = fail(PVW_ERR_INTERNAL, "decode launch failed");   // decryption.rs:116, :277
       }
       if (rc == PVW_OK && (hipMemcpyAsync(out_u64 + d0, d_out, cnt * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
+                           (noise && hipMemcpyAsync(noise + d0, d_ns, cnt * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess) ||
+                           (status && hipMemcpyAsync(status + d0, d_st, cnt * 4, hipMemcpyDeviceToHost, w->stream) != hipSuccess) ||
                            (noisy_out && hipMemcpyAsync(noisy_out + d0 * P, d_nz, cnt * P * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess) ||
                            hipStreamSynchronize(w->stream) != hipSuccess))
         rc = fail(PVW_ERR_INTERNAL, "D2H failed");
@@ -2644,8 +2787,10 @@ static int32_t decrypt_all_checks(pvw_ctx* c, u32 lo, u32 hi, const void* sk, co
 }
 // host: sk / c1s / c2s / out are host buffers (staged in bounded pieces); otherwise device pointers on `s`.
 // The caller's buffers are only read: POWER-basis input is transformed in scratch.
+// noise / status (either may be NULL, same side as out): the checked decode's report, [P][D] like out
 static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, u32 hi, const int64_t* sk, const u64* c1s,
-                               const u64* c2s, size_t D, uint32_t in_repr, u64* out, bool host) {
+                               const u64* c2s, size_t D, uint32_t in_repr, u64* out, bool host, u64* noise = nullptr,
+                               u32* status = nullptr) {
   const u32 k = c->k, l = c->l, L = c->L;
   const size_t P = c->poly(), NP = (size_t)hi - lo;
   const size_t ctw = (size_t)k * P;                      // words of one dealer's c1
@@ -2662,17 +2807,21 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
     if (Dc > D) Dc = D;
     const size_t b_sk = host ? al256(NP * k * l * 8) : 0, b_c1 = stage ? al256(Dc * ctw * 8) : 0;
     const size_t b_c2 = al256(Dc * P * 8), b_nz = al256(Dc * P * 8), b_out = host ? al256(Dc * 8) : 0;
-    PVW_TRY(ws_scratch(w, b_sk + b_c1 + b_c2 + b_nz + b_out));
+    const size_t b_ns = host && noise ? al256(Dc * 8) : 0, b_st = host && status ? al256(Dc * 4) : 0;
+    PVW_TRY(ws_scratch(w, b_sk + b_c1 + b_c2 + b_nz + b_out + b_ns + b_st));
     char* base = (char*)w->scratch;
     i64* d_sk = (i64*)base;
     u64* d_c1 = (u64*)(base + b_sk);
     u64* d_c2 = (u64*)(base + b_sk + b_c1);
     u64* d_nz = (u64*)(base + b_sk + b_c1 + b_c2);
     u64* d_out = (u64*)(base + b_sk + b_c1 + b_c2 + b_nz);
-    // key material: the uploaded coefficients, NTT(sk) (w->rhat), the noisy polynomials (m g-hat + noise) and the decoded values
+    u64* d_ns = (u64*)(base + b_sk + b_c1 + b_c2 + b_nz + b_out);
+    u32* d_st = (u32*)(base + b_sk + b_c1 + b_c2 + b_nz + b_out + b_ns);
+    // key material: the uploaded coefficients, NTT(sk) (w->rhat), the noisy polynomials (m g-hat + noise), the decoded values
+    // and their reports
     ws_mark_secret(w, d_sk, b_sk);
     ws_mark_secret(w, w->rhat, (size_t)k * P * 8);
-    ws_mark_secret(w, d_nz, b_nz + b_out);
+    ws_mark_secret(w, d_nz, b_nz + b_out + b_ns + b_st);
     if (host) PVW_HIP(hipMemcpyAsync(d_sk, sk, NP * k * l * 8, hipMemcpyHostToDevice, s));
     const i64* skd = host ? d_sk : sk;
     for (size_t d0 = 0; d0 < D; d0 += Dc) {
@@ -2701,11 +2850,16 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
           ntt_domain = false;
         }
         u64* o = out + p * D + d0;
+        u64* on = noise ? noise + p * D + d0 : nullptr;
+        u32* os = status ? status + p * D + d0 : nullptr;
         {
           ProfScope ps(c, "decode", s);
-          PVW_HIP(launch_decode(d_nz, host ? d_out : o, cnt, c->dec_dev, s, ntt_domain ? &c->dt : nullptr));   // :116, :10-58
+          PVW_HIP(launch_decode(d_nz, host ? d_out : o, cnt, c->dec_dev, s, ntt_domain ? &c->dt : nullptr, nullptr, 0, nullptr,
+                                on && host ? d_ns : on, os && host ? d_st : os));                                    // :116, :10-58
         }
         if (host) PVW_HIP(hipMemcpyAsync(o, d_out, cnt * 8, hipMemcpyDeviceToHost, s));
+        if (host && on) PVW_HIP(hipMemcpyAsync(on, d_ns, cnt * 8, hipMemcpyDeviceToHost, s));
+        if (host && os) PVW_HIP(hipMemcpyAsync(os, d_st, cnt * 4, hipMemcpyDeviceToHost, s));
       }
     }
     return PVW_OK;
@@ -2725,7 +2879,8 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
   const size_t b_sk = host ? al256(Pc * k * l * 8) : 0, b_rows = direct ? 0 : al256(Pc * ctw * 8);
   const size_t b_xm = al256(xm_words((u32)Pc, k, L, l) * 8), b_tmp = al256(nbg * gemm_tmp_words((u32)Pc, L, l) * 8);
   const size_t b_c2 = stage ? al256(Dg * Pc * P * 8) : 0, b_nz = al256(Dg * Pc * P * 8), b_out = al256(Dg * Pc * 8);
-  PVW_TRY(ws_scratch(w, b_c1 + b_yd + b_sy + b_sk + b_rows + b_xm + b_tmp + b_c2 + b_nz + b_out));
+  const size_t b_ns = noise ? al256(Dg * Pc * 8) : 0, b_st = status ? al256(Dg * Pc * 4) : 0;
+  PVW_TRY(ws_scratch(w, b_c1 + b_yd + b_sy + b_sk + b_rows + b_xm + b_tmp + b_c2 + b_nz + b_out + b_ns + b_st));
   char* base = (char*)w->scratch;
   u64* d_c1 = (u64*)base;
   signed char* d_yd = (signed char*)(base + b_c1);
@@ -2738,9 +2893,11 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
   u64* d_c2 = (u64*)(sec + b_sk + b_rows + b_xm + b_tmp);
   u64* d_nz = (u64*)(sec + b_sk + b_rows + b_xm + b_tmp + b_c2);
   u64* d_out = (u64*)(sec + b_sk + b_rows + b_xm + b_tmp + b_c2 + b_nz);
+  u64* d_ns = (u64*)(sec + b_sk + b_rows + b_xm + b_tmp + b_c2 + b_nz + b_out);
+  u32* d_st = (u32*)(sec + b_sk + b_rows + b_xm + b_tmp + b_c2 + b_nz + b_out + b_ns);
   // the uploaded coefficients, the tiled s-hat (and its rows, l = 64), the GEMM intermediate (s-hat c1), the noisy
-  // polynomials and the decoded values; the staged c2 rows share the region
-  ws_mark_secret(w, sec, b_sk + b_rows + b_xm + b_tmp + b_c2 + b_nz + b_out);
+  // polynomials, the decoded values and their reports; the staged c2 rows share the region
+  ws_mark_secret(w, sec, b_sk + b_rows + b_xm + b_tmp + b_c2 + b_nz + b_out + b_ns + b_st);
   for (size_t p0 = 0; p0 < NP; p0 += Pc) {
     const u32 pc = (u32)((NP - p0) < Pc ? (NP - p0) : Pc);
     const i64* skp = sk + p0 * k * l;
@@ -2798,10 +2955,13 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
       }
       {
         ProfScope ps(c, "decode", s);
-        PVW_HIP(launch_decode(d_nz, d_out, cnt, c->dec_dev, s, xf ? &c->dt : nullptr));           // :116, :10-58
+        PVW_HIP(launch_decode(d_nz, d_out, cnt, c->dec_dev, s, xf ? &c->dt : nullptr, nullptr, 0, nullptr, noise ? d_ns : nullptr,
+                              status ? d_st : nullptr));                                                 // :116, :10-58
       }
       // results[recipient][dealer] (examples/pvw.rs:157-170): the chunk's [pc][dg] block into out[p0..][d0..]
       PVW_HIP(hipMemcpy2DAsync(out + p0 * D + d0, D * 8, d_out, (size_t)dg * 8, (size_t)dg * 8, pc, kout, s));
+      if (noise) PVW_HIP(hipMemcpy2DAsync(noise + p0 * D + d0, D * 8, d_ns, (size_t)dg * 8, (size_t)dg * 8, pc, kout, s));
+      if (status) PVW_HIP(hipMemcpy2DAsync(status + p0 * D + d0, D * 4, d_st, (size_t)dg * 4, (size_t)dg * 4, pc, kout, s));
     }
   }
   return PVW_OK;
@@ -2833,6 +2993,29 @@ int32_t pvw_decrypt_all_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64
   Workspace* w;
   PVW_TRY(ws_for_stream(c, s, &w));
   return decrypt_all_end(w, s, decrypt_all_run(c, w, s, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out, false), false);
+}
+// checked forms: the same words in out, plus noise / status [P][D] (either may be NULL)
+int32_t pvw_decrypt_all_checked(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
+                                size_t D, uint32_t in_repr, uint64_t* out, uint64_t* noise, uint32_t* status) {
+  PVW_TRY(decrypt_all_checks(c, lo, hi, sk, c1s, c2s, D, in_repr, out));
+  PVW_TRY(ensure_device(c));
+  Workspace* w;
+  PVW_TRY(ws_acquire(c, &w));
+  int32_t rc = decrypt_all_run(c, w, w->stream, lo, hi, sk, c1s, c2s, D, in_repr, out, true, noise, status);
+  rc = decrypt_all_end(w, w->stream, rc, true);
+  ws_release(c, w);
+  return rc;
+}
+int32_t pvw_decrypt_all_checked_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
+                                       const uint64_t* d_c2s, size_t D, uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise,
+                                       uint32_t* d_status, void* stream) {
+  PVW_TRY(decrypt_all_checks(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out));
+  PVW_TRY(ensure_device(c));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  Workspace* w;
+  PVW_TRY(ws_for_stream(c, s, &w));
+  return decrypt_all_end(w, s, decrypt_all_run(c, w, s, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out, false, d_noise, d_status),
+                         false);
 }
 
 // ------------------------------------------------------------------------ key generation

@@ -64,7 +64,15 @@ struct DecodeTables {
   // for noise_{l-1} (hs_on: every limb's inverse exists, Delta has at least 64 bits, sc_on)
   u32 hs_on;
   const u64* dpm;     // [4][L]
+  // checked decode: Delta * (2^64 - 1) < Q, so a step of the residual recurrence from a residual below 2^64
+  // needs no reduction of Delta * r mod Q (wave form: one multiply-add and a centred subtraction); 0: every step is lifted
+  u32 ck_mul;
 };
+
+// status word of the checked decode: the returned word is not the plaintext P (P < 0 or P >= 2^64)
+enum : u32 { DEC_LOSSY = 1 };
+// noise word of the checked decode once a residual leaves 64 bits
+#define PVW_NOISE_SAT (~(u64)0)
 
 PVW_HD void bn_zero(BN a, int W) { for (int i = 0; i < W; ++i) a[i] = 0; }
 PVW_HD void bn_load(BN a, const u64* src, int W) { for (int i = 0; i < W; ++i) a[i] = src[i]; }
@@ -401,7 +409,13 @@ PVW_HD u64 small_top_expected(u64 e0, u64 q0, const Mod& m) {
 
 // decode_scalar_pvw_rns for one ciphertext.  noisy: [L][l] power-basis residues of this dealer.
 // x: (W+1)-word and y: W-word big-integer scratch; nres: L-word scratch (residues of the current noise).
-PVW_HD u64 decode_one_fixed(const DecodeTables& t, const u64* noisy, BN x, BN y, BN nres) {
+// CK (checked decode): also *noise = min(max_i |residual_i|, 2^64 - 1), residual_i = centre(-z_i - P Delta^i),
+// and *status (DEC_LOSSY when the returned word is not P).  residual_0 = noise_0 and residual_{i+1} = Delta residual_i + tmp_i
+// (mod Q): the recurrence runs on the residues of noise_0 left in nres, one centred lift per step, and stops at the first
+// residual that leaves 64 bits.
+template <bool CK = false>
+PVW_HD u64 decode_one_fixed(const DecodeTables& t, const u64* noisy, BN x, BN y, BN nres, u64* noise = nullptr,
+                            u32* status = nullptr) {
   const int W = (int)t.W;
   const u32 L = t.L, l = t.ell;
   // tmp_i = z_i * Delta - z_{i+1}  (mod q_limb), straight from the noisy residues (:19-27)
@@ -456,15 +470,40 @@ PVW_HD u64 decode_one_fixed(const DecodeTables& t, const u64* noisy, BN x, BN y,
     u64 a = z0 ? m.q - z0 : 0;
     return submod(a, nres[(int)limb], m.q);
   });
-  if (vneg && !bn_is_zero(x, W)) {
+  u64 result;
+  bool lossy;
+  {
     bool hi = false;
     for (int w = 1; w < W; ++w) hi |= x[w] != 0;
-    if (!hi && x[0] <= 1000) return 0;       // small negative -> 0 (:233-235)
-    bn_rsub_c(x, t.Q, W);                    // (v + Q) % Q = Q - |v|
+    const bool pneg = vneg && !bn_is_zero(x, W);
+    lossy = pneg || hi;
+    if (pneg && !hi && x[0] <= 1000) {
+      result = 0;                            // small negative -> 0 (:233-235)
+    } else {
+      if (pneg) bn_rsub_c(x, t.Q, W);        // (v + Q) % Q = Q - |v|
+      bool fits = true;
+      for (int w = 1; w < W; ++w) fits &= x[w] == 0;
+      result = fits ? x[0] : 0;              // does not fit u64 (:240,:243)
+    }
   }
-  for (int w = 1; w < W; ++w)
-    if (x[w] != 0) return 0;                 // does not fit u64 (:240,:243)
-  return x[0];
+  if constexpr (CK) {
+    u64 mx = 0;
+    bool sat = false;
+    for (u32 i = 0; !sat && i < l; ++i) {
+      if (i) {                               // nres: residues of residual_{i-1} -> residual_i = Delta residual_{i-1} + tmp_{i-1}
+        for (u32 limb = 0; limb < L; ++limb) {
+          const Mod m = t.mods[limb];
+          nres[(int)limb] = addmod(mulmod_shoup(nres[(int)limb], t.dmod[limb], t.dmodp[limb], m.q), tmp(limb, i - 1), m.q);
+        }
+      }
+      lift_centered(t, x, [&](u32 limb) -> u64 { return nres[(int)limb]; });
+      for (int w = 1; w < W; ++w) sat |= x[w] != 0;
+      if (!sat && x[0] > mx) mx = x[0];
+    }
+    if (noise) *noise = sat ? PVW_NOISE_SAT : mx;
+    if (status) *status = lossy ? (u32)DEC_LOSSY : 0u;
+  }
+  return result;
 }
 
 }  // namespace pvw

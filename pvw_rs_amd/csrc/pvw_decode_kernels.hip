@@ -29,6 +29,21 @@ __global__ __launch_bounds__(64) void decode_kernel(const u64* __restrict__ nois
   out[d] = decode_one_fixed(t, noisy + (size_t)d * t.L * t.ell, x, y, nres);
 }
 
+// the same with the checked report: noise[d] / status[d], either may be NULL
+__global__ __launch_bounds__(64) void decode_checked_kernel(const u64* __restrict__ noisy, u64* __restrict__ out,
+                                                             u64* __restrict__ noise, u32* __restrict__ status, u32 count,
+                                                             DecodeTables t) {
+  extern __shared__ u64 dsm[];
+  const u32 d = blockIdx.x * 64 + threadIdx.x;
+  u64* base = dsm + threadIdx.x;
+  BN x{base, 64};
+  BN y{base + (size_t)(t.W + 1) * 64, 64};
+  BN nres{base + (size_t)(2 * t.W + 1) * 64, 64};
+  if (d >= count) return;
+  out[d] = decode_one_fixed<true>(t, noisy + (size_t)d * t.L * t.ell, x, y, nres, noise ? noise + d : nullptr,
+                                    status ? status + d : nullptr);
+}
+
 // decode, lifted-chain form (pvw_decode_wave.h): 4 waves per ciphertext, cpw ciphertexts per workgroup
 // XF: the residues arrive in the NTT domain and are transformed back while they are staged (stage_inverse).  A separate
 // instance because the compiler gives it 94 registers where the plain one has 79: at most 80 keep the decode co-resident
@@ -50,6 +65,17 @@ __global__ __launch_bounds__(512) void decode_chain_kernel(u64* __restrict__ noi
   decode_chain_body<4>(noisy, out, count, cpw_dbg, t, xf, blockIdx.x, dws);
 }
 
+// the lifted-chain decode with the checked report -- instances of their own, so that the unchecked ones keep
+// their register budget; the wipe is not offered (the checked entry points wipe on their stream)
+template <bool XF>
+__global__ __launch_bounds__(512) void decode_chain_checked_kernel(u64* __restrict__ noisy, u64* __restrict__ out,
+                                                                    u64* __restrict__ noise, u32* __restrict__ status,
+                                                                    u32 count, u32 cpw_dbg, DecodeTables t, InverseTables xf) {
+  extern __shared__ u64 dws[];
+  if (!XF) xf.itw = nullptr;
+  decode_chain_body<4, true>(noisy, out, count, cpw_dbg, t, xf, blockIdx.x, dws, noise, status);
+}
+
 // Kernels that may ask for more than the default 64 KiB of dynamic LDS.  The attribute is per device and per
 // code object, so it is set once per CONTEXT while the context initialises its device (ensure_device, under the
 // context's init mutex, after hipSetDevice) -- not lazily behind process-wide flags.
@@ -58,6 +84,9 @@ hipError_t init_kernel_attributes() {
   hipError_t e = hipFuncSetAttribute((const void*)decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, big);
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)decode_chain_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)decode_chain_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)decode_checked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)decode_chain_checked_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)decode_chain_checked_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
 #if PVW_TUNING
   if (e == hipSuccess) e = init_probe_attributes();
 #endif
@@ -70,9 +99,11 @@ static size_t decode_chain_lds(const DecodeTables& t, u32 cpw, u32 wpc) {
 }
 
 hipError_t launch_decode(u64* noisy, u64* out, size_t count, const DecodeTables& t, hipStream_t s, const DevTables* xf,
-                         u64* wipe, size_t wipe_bytes, bool* wiped) {
+                         u64* wipe, size_t wipe_bytes, bool* wiped, u64* noise, u32* status) {
   if (wiped) *wiped = false;
   if (count == 0) return hipSuccess;
+  const bool checked = noise || status;
+  if (checked) wipe = nullptr;
   InverseTables inv{nullptr, nullptr, nullptr, nullptr};
   if (xf) inv = InverseTables{xf->itw, xf->itwp, xf->linv, xf->linvp};
   // by shape: the lifted chain (4 waves per ciphertext, 2 ciphertexts per workgroup) while L <= 64 and W + 2 <= 63
@@ -91,6 +122,11 @@ hipError_t launch_decode(u64* noisy, u64* out, size_t count, const DecodeTables&
       // tuning build only: PVW_DECODE_TIMING=1..6: out[] = cycles of a phase (results are NOT values; tools/decode_timing.py)
       const u32 dbg = (u32)PVW_ENV_INT("PVW_DECODE_TIMING", 0);
       const u32 no_small = PVW_ENV_INT("PVW_DECODE_SMALL", 1) == 0 ? 1u << 31 : 0;     // tuning build: every lift in full
+      if (checked) {
+        if (xf) decode_chain_checked_kernel<true><<<grid, block, bytes, s>>>(noisy, out, noise, status, (u32)count, cpw | ((dbg & 0xff) << 16) | no_small, t, inv);
+        else decode_chain_checked_kernel<false><<<grid, block, bytes, s>>>(noisy, out, noise, status, (u32)count, cpw | ((dbg & 0xff) << 16) | no_small, t, inv);
+        return hipGetLastError();
+      }
       if (xf) decode_chain_kernel<true><<<grid, block, bytes, s>>>(noisy, out, (u32)count, cpw | ((dbg & 0xff) << 16) | no_small, t, inv, wipe, wipe16, ndec);
       else decode_chain_kernel<false><<<grid, block, bytes, s>>>(noisy, out, (u32)count, cpw | ((dbg & 0xff) << 16) | no_small, t, inv, wipe, wipe16, ndec);
       return hipGetLastError();
@@ -102,7 +138,8 @@ hipError_t launch_decode(u64* noisy, u64* out, size_t count, const DecodeTables&
   }
   const size_t lds = (size_t)(2 * t.W + 1 + t.L) * 64 * sizeof(u64);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
-  decode_kernel<<<dim3((u32)((count + 63) / 64)), dim3(64), lds, s>>>(noisy, out, (u32)count, t);
+  if (checked) decode_checked_kernel<<<dim3((u32)((count + 63) / 64)), dim3(64), lds, s>>>(noisy, out, noise, status, (u32)count, t);
+  else decode_kernel<<<dim3((u32)((count + 63) / 64)), dim3(64), lds, s>>>(noisy, out, (u32)count, t);
   return hipGetLastError();
 }
 

@@ -373,9 +373,12 @@ __device__ __forceinline__ void stage_inverse(const Mod* mods, const InverseTabl
     }
   }
 }
-template <int WPC>
+// CK (checked decode): also noise_out[d] / status_out[d] (each may be NULL) -- the report of the residual
+// recurrence below, on the wave that ran the chain; the unchecked instances do not contain it.
+template <int WPC, bool CK = false>
 __device__ __forceinline__ void decode_chain_body(u64* __restrict__ noisy, u64* __restrict__ out, u32 count, u32 cpw_dbg,
-                                                  const DecodeTables& t, const InverseTables& xf, u32 blk, u64* dws) {
+                                                  const DecodeTables& t, const InverseTables& xf, u32 blk, u64* dws,
+                                                  u64* __restrict__ noise_out = nullptr, u32* __restrict__ status_out = nullptr) {
   const u32 cpw = cpw_dbg & 0xffff;
   const u32 dbg = PVW_TUNING ? ((cpw_dbg >> 16) & 0xff) : 0;
   const bool no_small = PVW_TUNING && (cpw_dbg >> 31);     // tuning build: PVW_DECODE_SMALL=0, every lift in full        // tuning build, dbg != 0: timing experiment, out[] = cycle counts
@@ -595,6 +598,40 @@ __device__ __forceinline__ void decode_chain_body(u64* __restrict__ noisy, u64* 
     const u64 tk3 = clock64();
     if (lane == 0 && dbg < 8) out[d] = dbg == 1 ? (tk1 - tk0) : (dbg == 2 ? (tk2 - tk1) : (dbg == 7 ? (tk1 - tk0b) : (tk3 - tk2)));
     return;
+  }
+  if constexpr (CK) {
+    // residual_i = centre(-z_i - P Delta^i), i < l: residual_0 = noise_0 (-z_0 - P = noise_0 mod Q, |noise_0| < Q/2) and
+    // residual_{i+1} = Delta residual_i + tmp_i mod Q, with tmp_i in [0, Q) in its lift slot.  The recurrence stops at the first
+    // residual of more than one word: the maximum saturates there.  ck_mul: Delta |r| < Q, so -Delta r mod Q is Q - Delta r
+    // or Delta r and the step is a product, one normalisation and a centred subtraction; otherwise (small Q) the step's
+    // residues are lifted in full.
+    const bool pz = __ballot(v != 0) == 0;
+    const bool lossy = vneg ? !pz : __ballot(lane > 0 && v != 0) != 0;
+    bool sat = __ballot(lane > 0 && nm != 0) != 0;
+    u64 rm = readlane_u64(nm, 0), mx = rm;
+    bool rneg = nneg;
+    for (u32 i = 0; !sat && i + 1 < l; ++i) {
+      u64 x;
+      bool xneg;
+      if (t.ck_mul) {
+        const u128 pr = (u128)dlw * rm;
+        const u64 s = wave_normalize((u64)pr, (u64)(pr >> 64), 0, lane);
+        const u64 b = (rneg || rm == 0) ? s : wave_sub(Qw, s, lane);        // (-Delta r_i) mod Q
+        x = sub_centre(Tl[(size_t)i * 64 + lane], false, b, xneg);           // tmp_i - (-Delta r_i), centred
+      } else {
+        u64 rr = c.limb_on ? reduce128(rm, 0, c.m) : 0;
+        if (rneg && rr) rr = q - rr;
+        x = wave_lift_centered<true>(c, addmod(mulmod_shoup(rr, dm, dmp, q), tmp(i), q), xneg);
+      }
+      sat = __ballot(lane > 0 && x != 0) != 0;
+      rm = readlane_u64(x, 0);
+      rneg = xneg;
+      if (!sat && rm > mx) mx = rm;
+    }
+    if (lane == 0) {
+      if (noise_out) noise_out[d] = sat ? PVW_NOISE_SAT : mx;
+      if (status_out) status_out[d] = lossy ? (u32)DEC_LOSSY : 0u;
+    }
   }
   const bool vzero = __ballot(v != 0) == 0;
   u64 result;

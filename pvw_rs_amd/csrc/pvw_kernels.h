@@ -301,7 +301,11 @@ hipError_t launch_mfma_probe(const signed char* A, const signed char* B, int* C,
 // wipe / wipe_bytes (a multiple of 16): a region the decode launch clears as well (NTT(sk) of the decrypt it closes; every
 // launch in front of it on `s` must be done with it); *wiped says whether this launch took that on (the fixed-width
 // fallback does not).
+// noise / status (either may be NULL; both NULL: the unchecked kernels): the checked decode's report per ciphertext
+// (pvw_decode.h: decode_one_fixed, pvw_decode_wave.h: decode_chain_body), out[] unchanged.  A checked launch
+// takes no wipe (*wiped comes back false).
 hipError_t launch_decode(u64* noisy, u64* out, size_t count, const DecodeTables& t, hipStream_t s, const DevTables* xf = nullptr,
-                         u64* wipe = nullptr, size_t wipe_bytes = 0, bool* wiped = nullptr);
+                         u64* wipe = nullptr, size_t wipe_bytes = 0, bool* wiped = nullptr, u64* noise = nullptr,
+                         u32* status = nullptr);
 
 }  // namespace pvw

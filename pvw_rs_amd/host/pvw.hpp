@@ -426,6 +426,41 @@ inline std::vector<uint64_t> decrypt_party_shares(const std::vector<PvwCiphertex
   check(pvw_decrypt_batch(p->ctx, sk.secret_coeffs.data(), c1s.data(), c2col.data(), cts.size(), cts[0].repr, out.data(), nullptr));
   return out;
 }
+// decrypt_party_shares with each share's report (pvw_decrypt_batch_checked): values as decrypt_party_shares,
+// noise (max |residual|, saturating), lossy (the value is not the plaintext), valid = !lossy && noise <= bound
+struct CheckedShares {
+  std::vector<uint64_t> values, noise;
+  std::vector<bool> lossy, valid;
+};
+inline CheckedShares decrypt_party_shares_checked(const std::vector<PvwCiphertext>& cts, const SecretKey& sk, uint32_t party_index,
+                                                  uint64_t bound) {
+  if (cts.empty()) throw PvwError(1, "No ciphertexts provided");
+  const auto& p = cts[0].params;
+  if (cts.size() != p->n) throw PvwError(1, "Expected n ciphertexts");
+  if (party_index >= p->n) throw PvwError(1, "Party index exceeds maximum");
+  const size_t P = p->poly_words(), D = cts.size();
+  std::vector<uint64_t> c1s, c2col;
+  std::vector<uint32_t> status(D);
+  CheckedShares r{std::vector<uint64_t>(D), std::vector<uint64_t>(D), std::vector<bool>(D), std::vector<bool>(D)};
+  for (const auto& ct : cts) {
+    ct.validate();
+    c1s.insert(c1s.end(), ct.c1.begin(), ct.c1.end());
+    c2col.insert(c2col.end(), ct.c2.begin() + (size_t)party_index * P, ct.c2.begin() + (size_t)(party_index + 1) * P);
+  }
+  check(pvw_decrypt_batch_checked(p->ctx, sk.secret_coeffs.data(), c1s.data(), c2col.data(), D, cts[0].repr, r.values.data(),
+                                  r.noise.data(), status.data()));
+  for (size_t d = 0; d < D; ++d) {
+    r.lossy[d] = (status[d] & PVW_DEC_LOSSY) != 0;
+    r.valid[d] = !r.lossy[d] && r.noise[d] <= bound;
+  }
+  return r;
+}
+// the default bound of a checked decrypt: total_bound of verify_correctness_condition (parameters.rs:516-543)
+inline uint64_t noise_bound(const pvw_ctx* ctx) {
+  uint64_t b = 0;
+  check(pvw_ctx_noise_bound(ctx, &b));
+  return b;
+}
 // every party of [party_lo, party_lo + secret_keys.size()) decrypts its share of each ciphertext (any number of them, e.g.
 // the valid subset of examples/pvw_valid_dec.rs:201-209) in one call (pvw_decrypt_all): result[p][d]
 inline std::vector<std::vector<uint64_t>> decrypt_many(const std::vector<PvwCiphertext>& cts, const std::vector<const SecretKey*>& secret_keys,

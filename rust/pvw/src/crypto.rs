@@ -273,6 +273,43 @@ pub fn decrypt_party_shares(all_ciphertexts: &[PvwCiphertext], secret_key: &Secr
     Ok(out)
 }
 
+/// EXTENSION: `decrypt_party_shares` with each share's report (`pvw_decrypt_batch_checked`) -- the same checks
+/// and values, plus `noise[d]` (max |residual|, saturating at u64::MAX) and `lossy[d]` (the value is not the plaintext).
+/// A share is valid when it is not lossy and its noise is at most the caller's bound (e.g. `pvw_ctx_noise_bound`).
+pub fn decrypt_party_shares_checked(all_ciphertexts: &[PvwCiphertext], secret_key: &SecretKey, party_index: usize) -> Result<(Vec<u64>, Vec<u64>, Vec<bool>)> {
+    if all_ciphertexts.is_empty() {
+        return Err(PvwError::InvalidParameters("No ciphertexts provided".to_string()));
+    }
+    let params = &all_ciphertexts[0].params;
+    if all_ciphertexts.len() != params.n {
+        return Err(PvwError::InvalidParameters(format!("Expected {} ciphertexts, got {}", params.n, all_ciphertexts.len())));
+    }
+    if party_index >= params.n {
+        return Err(PvwError::InvalidParameters(format!("Party index {} exceeds maximum {}", party_index, params.n - 1)));
+    }
+    let words = poly_words(params);
+    let d = all_ciphertexts.len();
+    let (mut c1s, mut c2col) = (Vec::with_capacity(d * params.k * words), Vec::with_capacity(d * words));
+    for (dealer_idx, ciphertext) in all_ciphertexts.iter().enumerate() {
+        ciphertext
+            .validate()
+            .map_err(|e| PvwError::InvalidParameters(format!("Ciphertext {dealer_idx} invalid: {e}")))?;
+        for poly in ciphertext.c1.iter() {
+            poly_to_flat(poly, &mut c1s);
+        }
+        poly_to_flat(&ciphertext.c2[party_index], &mut c2col);
+    }
+    let mut sk = flat_secret(secret_key);
+    let (mut out, mut noise, mut status) = (vec![0u64; d], vec![0u64; d], vec![0u32; d]);
+    let rc = unsafe {
+        sys::pvw_decrypt_batch_checked(params.hip.raw(), sk.as_ptr(), c1s.as_ptr(), c2col.as_ptr(), d, sys::PVW_REPR_POWER, out.as_mut_ptr(),
+                                       noise.as_mut_ptr(), status.as_mut_ptr())
+    };
+    sk.zeroize();
+    check(rc)?;
+    Ok((out, noise, status.iter().map(|s| s & sys::PVW_DEC_LOSSY != 0).collect()))
+}
+
 /// EXTENSION -- no single reference function behind it.  The loop examples/pvw.rs:138-149 and tests/crypto.rs:284-287
 /// run over `decrypt_party_shares` for every party, as one call: `results[recipient][dealer]` (examples/pvw.rs:157-170)
 /// from one digit GEMM of the parties' keys against all dealers' c1 (`pvw_decrypt_all`).  `parties` must carry
