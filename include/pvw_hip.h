@@ -485,6 +485,51 @@ PVW_API int32_t pvw_prepare(pvw_ctx* ctx, uint32_t flags, void* stream, uint64_t
 PVW_API int32_t pvw_ctx_packed_active(const pvw_ctx* ctx, uint32_t* width_out);
 PVW_API int32_t pvw_ctx_synchronize(pvw_ctx* ctx);
 
+/* ---- wire format, version 1: this library's own byte form of parameters, CRS rows, public-key rows, ciphertexts
+ * and secret keys (the reference serialises them through serde, encryption.rs:298-354, public_key.rs:471-622, crs.rs:228-295,
+ * parameters.rs:606-664; its fhe-math Poly bytes are not reproducible here).  A blob is a header that carries the parameters
+ * and a body.  A packed polynomial holds limb row i at w_i = bitlen(q_i) bits per residue, least significant bit first, rows
+ * back to back: pvw_wire_poly_bytes = (l/8) * sum_i w_i, and polynomial p of a body starts at byte p * poly_bytes.
+ *   Writers emit w mod q_i for every word w (unreduced and reduced words give the same bytes).  Readers reject any field >= q_i
+ *   with PVW_ERR_DESERIALIZATION; the message names the first bad polynomial, limb and slot.
+ *   Kinds: 1 parameters (no body), 2 CRS rows, 3 public-key rows (row = k polynomials), 4 ciphertext (c1 rows then c2 rows),
+ *   5 secret key (k*l int64, not packed).  The device codec takes L <= 64 moduli and 16-byte aligned device pointers. */
+PVW_API int32_t pvw_wire_poly_bytes(const pvw_ctx* ctx, size_t* out);
+/* the header of a blob of `kind` for this context: rows [lo, hi) (kinds 2 / 3), c1 rows [lo, hi) and c2 rows [lo2, hi2) (kind 4);
+ * unused range arguments are ignored.  *len = header length (a multiple of 16); out = NULL only reports it.  cap < *len:
+ * PVW_ERR_SERIALIZATION.  Ranges beyond the parameters: PVW_ERR_INVALID_FORMAT. */
+PVW_API int32_t pvw_wire_header(const pvw_ctx* ctx, uint32_t kind, uint32_t repr, uint32_t lo, uint32_t hi, uint32_t lo2,
+                                uint32_t hi2, uint8_t* out, size_t cap, size_t* len);
+/* checks a whole blob (header + body, len bytes) against this context.  Wrong magic, version, kind or representation,
+ * other moduli / variance / bounds, other roots for an NTT-domain body, bad ranges, a body_len that does not match, a
+ * truncated blob or trailing bytes: PVW_ERR_INVALID_FORMAT; other n / k / l / L: PVW_ERR_DIMENSION_MISMATCH.  Outputs (each
+ * may be NULL): kind, repr, ranges[4] = {lo, hi, lo2, hi2} (0 where unused), header_len (the body starts there). */
+PVW_API int32_t pvw_wire_header_check(const pvw_ctx* ctx, const uint8_t* data, size_t len, uint32_t* kind, uint32_t* repr,
+                                      uint32_t* ranges, size_t* header_len);
+/* `count` polynomials [L][l] <-> count * poly_bytes packed bytes, host buffers, on the device (synchronous).  pack: `out` may
+ * be pvw_host_alloc memory, which the kernel then writes directly.  unpack: on rejection polys is written all the same. */
+PVW_API int32_t pvw_wire_pack(pvw_ctx* ctx, const uint64_t* polys, size_t count, uint8_t* out);
+PVW_API int32_t pvw_wire_pack_device(pvw_ctx* ctx, const uint64_t* d_polys, size_t count, uint8_t* d_out, void* stream);
+PVW_API int32_t pvw_wire_unpack(pvw_ctx* ctx, const uint8_t* data, size_t count, uint64_t* polys);
+/* asynchronous on `stream`, no host synchronisation (may be captured): *d_bad (device word) = the number of rejected residues;
+ * rejected slots hold the raw field value.  d_out of pack may be pvw_host_alloc memory. */
+PVW_API int32_t pvw_wire_unpack_device(pvw_ctx* ctx, const uint8_t* d_in, size_t count, uint64_t* d_polys, uint64_t* d_bad,
+                                       void* stream);
+/* the same codec in plain C++ on the host (no GPU needed): the reference the device codec is tested against.
+ * unpack_host: *bad_out (may be NULL) = rejected residues; PVW_ERR_DESERIALIZATION if any. */
+PVW_API int32_t pvw_wire_pack_host(const pvw_ctx* ctx, const uint64_t* polys, size_t count, uint8_t* out);
+PVW_API int32_t pvw_wire_unpack_host(const pvw_ctx* ctx, const uint8_t* data, size_t count, uint64_t* polys, uint64_t* bad_out);
+/* pvw_load_pk / pvw_load_crs from a packed body (rows [party_lo, party_hi) / [0, k); rows outside the context's shard are not
+ * read).  Every row the context holds is checked before any is stored: a rejected body (PVW_ERR_DESERIALIZATION) leaves the
+ * resident matrix, num_public_keys and the derived copies as they were.  Bodies up to 1 GiB are staged on the device whole,
+ * larger ones are read twice.  On success the derived copies are invalidated as by pvw_load_pk / pvw_load_crs. */
+PVW_API int32_t pvw_load_pk_wire(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const uint8_t* body, uint32_t repr);
+/* pvw_get_pk / pvw_get_crs packed: untiled (and transformed for POWER) and packed on the device, only the packed bytes are
+ * copied to the host.  Rows the context does not hold are not written. */
+PVW_API int32_t pvw_get_pk_wire(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, uint8_t* body_out, uint32_t repr);
+PVW_API int32_t pvw_load_crs_wire(pvw_ctx* ctx, const uint8_t* body, uint32_t repr);
+PVW_API int32_t pvw_get_crs_wire(pvw_ctx* ctx, uint8_t* body_out, uint32_t repr);
+
 #ifdef __cplusplus
 }
 #endif

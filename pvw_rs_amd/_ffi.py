@@ -23,6 +23,7 @@ REPR_POWER, REPR_NTT = 0, 1
 RND_SEED, RND_EXPLICIT = 0, 1
 DOM_R, DOM_E1, DOM_E2, DOM_SK, DOM_EKEY, DOM_CRS, DOM_GAUSS, DOM_PK, DOM_CALL = range(9)
 PREPARE_PACKED, PREPARE_MFMA = 1, 2
+WIRE_PARAMS, WIRE_CRS, WIRE_PK, WIRE_CT, WIRE_SK = 1, 2, 3, 4, 5     # wire format v1 kinds
 
 
 class pvw_params_t(C.Structure):
@@ -128,6 +129,20 @@ _SIGNATURES = {
     "pvw_prepare": [_P, C.c_uint32, _P, C.POINTER(C.c_uint64)],
     "pvw_ctx_packed_active": [_P, C.POINTER(C.c_uint32)],
     "pvw_ctx_synchronize": [_P],
+    "pvw_wire_poly_bytes": [_P, C.POINTER(C.c_size_t)],
+    "pvw_wire_header": [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_size_t,
+                        C.POINTER(C.c_size_t)],
+    "pvw_wire_header_check": [_P, _P, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _P, C.POINTER(C.c_size_t)],
+    "pvw_wire_pack": [_P, _P, C.c_size_t, _P],
+    "pvw_wire_pack_device": [_P, _P, C.c_size_t, _P, _P],
+    "pvw_wire_unpack": [_P, _P, C.c_size_t, _P],
+    "pvw_wire_unpack_device": [_P, _P, C.c_size_t, _P, _P, _P],
+    "pvw_wire_pack_host": [_P, _P, C.c_size_t, _P],
+    "pvw_wire_unpack_host": [_P, _P, C.c_size_t, _P, C.POINTER(C.c_uint64)],
+    "pvw_load_pk_wire": [_P, C.c_uint32, C.c_uint32, _P, C.c_uint32],
+    "pvw_get_pk_wire": [_P, C.c_uint32, C.c_uint32, _P, C.c_uint32],
+    "pvw_load_crs_wire": [_P, _P, C.c_uint32],
+    "pvw_get_crs_wire": [_P, _P, C.c_uint32],
 }
 
 # include/pvw_hip_tuning.h: exported by the measurement build only

@@ -14,6 +14,7 @@ marshals numpy arrays.  Differences forced by the boundary:
 from __future__ import annotations
 
 import ctypes as C
+import struct
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -320,6 +321,34 @@ class PvwParameters:
     def synchronize(self) -> None:
         self._call("pvw_ctx_synchronize")
 
+    # -- wire format v1 ----------------------------------------------------------
+    def wire_poly_bytes(self) -> int:
+        """bytes of one packed polynomial: (l/8) * sum_i bitlen(q_i)"""
+        out = C.c_size_t()
+        self._call("pvw_wire_poly_bytes", C.byref(out))
+        return int(out.value)
+
+    def to_bytes(self) -> bytes:
+        """the parameters as a wire blob of kind 1 (a header, no body)"""
+        return bytes(_wire_header(self, _ffi.WIRE_PARAMS))
+
+    @staticmethod
+    def from_bytes(data, device: int = -1) -> "PvwParameters":
+        """parameters from a kind-1 blob (host only: no device work)"""
+        raw = bytes(data[:_WIRE_FIXED]) if len(data) >= _WIRE_FIXED else b""
+        if len(raw) < _WIRE_FIXED or raw[:4] != _WIRE_MAGIC:
+            raise PvwError(18, "wire: truncated header or bad magic")
+        version, kind = struct.unpack_from("<HH", raw, 4)
+        if version != 1 or kind != _ffi.WIRE_PARAMS:
+            raise PvwError(18, f"wire: version {version} kind {kind}, expected version 1 kind {_ffi.WIRE_PARAMS}")
+        n, k, l, L, var, b1, b2 = struct.unpack_from("<IIIIfQQ", raw, 12)
+        if len(data) < _WIRE_FIXED + 8 * L:
+            raise PvwError(18, "wire: truncated header")
+        moduli = list(struct.unpack_from(f"<{L}Q", bytes(data[_WIRE_FIXED:_WIRE_FIXED + 8 * L])))
+        p = PvwParameters(n, k, l, moduli, var, b1, b2, device)
+        _wire_check(p, data, _ffi.WIRE_PARAMS)
+        return p
+
 
 # ------------------------------------------------------------------------------------
 # CRS (src/params/crs.rs)
@@ -384,6 +413,26 @@ class PvwCrs:
     def validate(self) -> None:
         return None
 
+    def to_bytes(self, repr: int = REPR_POWER) -> bytes:
+        """the rows this context holds as a wire blob of kind 2 (packed on the device)"""
+        p = self.params
+        pb = p.wire_poly_bytes() * p.k
+        full = np.zeros(p.k * pb, dtype=np.uint8)
+        p._call("pvw_get_crs_wire", _ptr(full), repr)
+        return bytes(_wire_header(p, _ffi.WIRE_CRS, repr, p.c1_lo, p.c1_hi)) + full[p.c1_lo * pb:p.c1_hi * pb].tobytes()
+
+    @staticmethod
+    def from_bytes(params: PvwParameters, data) -> "PvwCrs":
+        """load a kind-2 blob (checked on the device: a residue >= q_i raises DeserializationError, nothing is loaded)"""
+        repr, rg, hl, a = _wire_check(params, data, _ffi.WIRE_CRS)
+        if not (rg[0] <= params.c1_lo and params.c1_hi <= rg[1]):
+            raise PvwError(18, f"wire: the blob holds CRS rows [{rg[0]}, {rg[1]}), this context needs [{params.c1_lo}, {params.c1_hi})")
+        pb = params.wire_poly_bytes() * params.k
+        full = np.zeros(params.k * pb + 1, dtype=np.uint8)
+        full[rg[0] * pb:rg[1] * pb] = a[hl:]
+        params._call("pvw_load_crs_wire", _ptr(full), repr)
+        return PvwCrs(params)
+
 
 # ------------------------------------------------------------------------------------
 # keys (src/keys)
@@ -440,6 +489,22 @@ class SecretKey:
 
     def __len__(self):
         return len(self.secret_coeffs)
+
+    def to_bytes(self) -> bytearray:
+        """a wire blob of kind 5: the k*l coefficients as little-endian i64 after the header.  A bytearray the caller owns
+        and should wipe (blob[:] = bytes(len(blob))) when done with it; no other copy of the coefficients is made."""
+        p = self.params
+        head = _wire_header(p, _ffi.WIRE_SK)
+        out = bytearray(len(head) + self.secret_coeffs.size * 8)
+        out[:len(head)] = head.tobytes()
+        np.frombuffer(out, dtype="<i8", offset=len(head))[:] = self.secret_coeffs.ravel()
+        return out
+
+    @staticmethod
+    def from_bytes(params: PvwParameters, data) -> "SecretKey":
+        _, _, hl, _ = _wire_check(params, data, _ffi.WIRE_SK)
+        view = np.frombuffer(data, dtype="<i8", offset=hl).reshape(params.k, params.l)
+        return SecretKey(params, view)
 
 
 class Party:
@@ -540,6 +605,33 @@ class GlobalPublicKey:
         self.params._call("pvw_is_full", C.byref(out))
         return bool(out.value)
 
+    def to_bytes(self, party_lo: Optional[int] = None, party_hi: Optional[int] = None, repr: int = REPR_POWER) -> bytes:
+        """rows [party_lo, party_hi) (default: the rows this context holds) as a wire blob of kind 3, packed on the device"""
+        p = self.params
+        lo = p.party_lo if party_lo is None else party_lo
+        hi = p.party_hi if party_hi is None else party_hi
+        if not (p.party_lo <= lo <= hi <= p.party_hi):
+            raise PvwError(1, f"rows [{lo}, {hi}) are not all held by this context ([{p.party_lo}, {p.party_hi}))")
+        head = _wire_header(p, _ffi.WIRE_PK, repr, lo, hi)
+        blob = np.empty(len(head) + (hi - lo) * p.k * p.wire_poly_bytes() + 1, dtype=np.uint8)
+        blob[:len(head)] = head
+        p._call("pvw_get_pk_wire", lo, hi, _ptr(blob[len(head):]), repr)
+        return blob[:-1].tobytes()
+
+    def load_bytes(self, data) -> None:
+        """add_public_key for the rows of a kind-3 blob.  Checked on the device before anything is stored: a residue >= q_i
+        raises DeserializationError and leaves the key, num_public_keys and the derived copies as they were."""
+        p = self.params
+        repr, rg, hl, a = _wire_check(p, data, _ffi.WIRE_PK)
+        body = np.ascontiguousarray(a[hl:]) if len(a) > hl else np.zeros(1, dtype=np.uint8)
+        p._call("pvw_load_pk_wire", rg[0], rg[1], _ptr(body), repr)
+
+    @staticmethod
+    def from_bytes(crs: PvwCrs, data) -> "GlobalPublicKey":
+        g = GlobalPublicKey(crs)
+        g.load_bytes(data)
+        return g
+
 
 # ------------------------------------------------------------------------------------
 # crypto (src/crypto)
@@ -571,6 +663,35 @@ class PvwCiphertext:
 
     def c2_components(self):
         return self.c2
+
+    def to_bytes(self, party_lo: Optional[int] = None, party_hi: Optional[int] = None) -> bytes:
+        """a wire blob of kind 4: the c1 rows this context holds, then c2 rows [party_lo, party_hi) (default: the parties this
+        context holds), packed on the device"""
+        p = self.params
+        lo = p.party_lo if party_lo is None else party_lo
+        hi = p.party_hi if party_hi is None else party_hi
+        if not (0 <= lo <= hi <= p.n):
+            raise PvwError(1, f"party range [{lo}, {hi}) outside [0, {p.n})")
+        polys = _u64(np.concatenate([np.asarray(self.c1)[p.c1_lo:p.c1_hi], np.asarray(self.c2)[lo:hi]]).reshape(-1, p.L, p.l))
+        head = _wire_header(p, _ffi.WIRE_CT, self.repr, p.c1_lo, p.c1_hi, lo, hi)
+        blob = np.empty(len(head) + len(polys) * p.wire_poly_bytes() + 1, dtype=np.uint8)
+        blob[:len(head)] = head
+        p._call("pvw_wire_pack", _ptr(polys), len(polys), _ptr(blob[len(head):]))
+        return blob[:-1].tobytes()
+
+    @staticmethod
+    def from_bytes(params: PvwParameters, data) -> "PvwCiphertext":
+        """a kind-4 blob, unpacked and checked on the device; rows the blob does not carry are zero"""
+        repr, rg, hl, a = _wire_check(params, data, _ffi.WIRE_CT)
+        n1, n2 = rg[1] - rg[0], rg[3] - rg[2]
+        words = np.zeros((n1 + n2, params.L, params.l), dtype=np.uint64)
+        body = np.ascontiguousarray(a[hl:]) if len(a) > hl else np.zeros(1, dtype=np.uint8)
+        params._call("pvw_wire_unpack", _ptr(body), n1 + n2, _ptr(words))
+        c1 = np.zeros((params.k, params.L, params.l), dtype=np.uint64)
+        c2 = np.zeros((params.n, params.L, params.l), dtype=np.uint64)
+        c1[rg[0]:rg[1]] = words[:n1]
+        c2[rg[2]:rg[3]] = words[n1:]
+        return PvwCiphertext(c1, c2, params, repr)
 
 
 def _randomness(params: PvwParameters, seed, r, e1, e2):
@@ -1067,3 +1188,63 @@ def decode_scalar_pvw_checked_host(params: PvwParameters, noisy: np.ndarray, bou
 def _selftest_decode_checked(params: PvwParameters, noisy: np.ndarray) -> CheckedDecryption:
     """Host run of the fixed-width device decode with its report (self-test hook, see pvw_hip.h)."""
     return _decode_checked(params, noisy, "pvw_selftest_decode_checked", 0)
+
+
+# ---- wire format, version 1 (DESIGN 9) ----
+_WIRE_MAGIC = b"PVWw"
+_WIRE_FIXED = 48                     # header bytes before the moduli
+
+
+def _wire_header(p: PvwParameters, kind: int, repr: int = REPR_POWER, lo: int = 0, hi: int = 0, lo2: int = 0, hi2: int = 0) -> np.ndarray:
+    n = C.c_size_t()
+    p._call("pvw_wire_header", kind, repr, lo, hi, lo2, hi2, None, 0, C.byref(n))
+    buf = np.zeros(n.value, dtype=np.uint8)
+    p._call("pvw_wire_header", kind, repr, lo, hi, lo2, hi2, _ptr(buf), n.value, C.byref(n))
+    return buf
+
+
+def _wire_check(p: PvwParameters, data, kind: int):
+    """pvw_wire_header_check on a whole blob, which must be of `kind`: (repr, ranges, header length, the blob as uint8)"""
+    a = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, dtype=np.uint8)[:0]
+    kd, rp, hl = C.c_uint32(), C.c_uint32(), C.c_size_t()
+    rg = (C.c_uint32 * 4)()
+    buf = a if len(a) else np.zeros(1, dtype=np.uint8)
+    p._call("pvw_wire_header_check", _ptr(buf), len(a), C.byref(kd), C.byref(rp), rg, C.byref(hl))
+    if kd.value != kind:
+        raise PvwError(18, f"wire: the blob is of kind {kd.value}, expected kind {kind}")
+    return rp.value, tuple(int(x) for x in rg), int(hl.value), a
+
+
+def wire_pack_host(params: PvwParameters, polys) -> bytes:
+    """the format's packing of polynomials [..][L][l] in plain C++ on the host (pvw_wire_pack_host)"""
+    a = _u64(polys)
+    count = a.size // (params.L * params.l)
+    out = np.zeros(count * params.wire_poly_bytes() + 1, dtype=np.uint8)
+    params._call("pvw_wire_pack_host", _ptr(a), count, _ptr(out))
+    return out[:-1].tobytes()
+
+
+def wire_unpack_host(params: PvwParameters, data, count: int) -> np.ndarray:
+    """pvw_wire_unpack_host: DeserializationError naming the first residue >= q_i"""
+    a = np.frombuffer(bytes(data) + b"\0", dtype=np.uint8)
+    out = np.zeros((count, params.L, params.l), dtype=np.uint64)
+    bad = C.c_uint64()
+    params._call("pvw_wire_unpack_host", _ptr(a), count, _ptr(out), C.byref(bad))
+    return out
+
+
+def wire_pack(params: PvwParameters, polys) -> bytes:
+    """pvw_wire_pack: packed on the device"""
+    a = _u64(polys)
+    count = a.size // (params.L * params.l)
+    out = np.zeros(count * params.wire_poly_bytes() + 1, dtype=np.uint8)
+    params._call("pvw_wire_pack", _ptr(a), count, _ptr(out))
+    return out[:-1].tobytes()
+
+
+def wire_unpack(params: PvwParameters, data, count: int) -> np.ndarray:
+    """pvw_wire_unpack: unpacked and checked on the device"""
+    a = np.frombuffer(bytes(data) + b"\0", dtype=np.uint8)
+    out = np.zeros((count, params.L, params.l), dtype=np.uint64)
+    params._call("pvw_wire_unpack", _ptr(a), count, _ptr(out))
+    return out

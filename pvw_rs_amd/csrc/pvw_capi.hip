@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -485,6 +486,7 @@ static int32_t ensure_device(pvw_ctx* c) {
   c->num_cus = (u32)prop.multiProcessorCount;
   PVW_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   PVW_HIP(init_kernel_attributes());          // per device: dynamic-LDS limits of the decode kernels
+  PVW_HIP(init_wire_attributes());            // ... and of the wire codec
   PVW_TRY(upload_tables(c));
   c->dev_ready = true;
   c->roots_locked = true;
@@ -3295,6 +3297,461 @@ int32_t pvw_keygen(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, cons
   ws_release(c, w);
   if (rc == PVW_OK && hi > c->num_keys) c->num_keys = hi;
   return rc;
+}
+
+// ------------------------------------------------------------------------ wire format, version 1
+// Header: magic "PVWw", u16 version, u16 kind, u32 repr, u32 n k l L, f32 secret_variance, u64 error_bound_1 / _2, L x u64 moduli,
+// [NTT bodies: L x u64 psi], row ranges as u32 pairs (CRS / public key: 1 pair, ciphertext: 2), u64 body_len, zero bytes up to a
+// multiple of 16.  Body: packed polynomials (kinds 2-4), k*l i64 (kind 5), nothing (kind 1).
+enum { WIRE_PARAMS = 1, WIRE_CRS = 2, WIRE_PK = 3, WIRE_CT = 4, WIRE_SK = 5 };
+static const size_t WIRE_FIXED = 48;            // bytes before the moduli
+static u32 wire_width(u64 q) {
+  u32 b = 0;
+  for (; q; q >>= 1) ++b;
+  return b;
+}
+static size_t wire_poly_bytes(const pvw_ctx* c) {
+  size_t s = 0;
+  for (u64 q : c->moduli) s += wire_width(q);
+  return s * c->l / 8;
+}
+static u32 wire_nranges(u32 kind) { return kind == WIRE_CT ? 2 : (kind == WIRE_CRS || kind == WIRE_PK ? 1 : 0); }
+static size_t wire_header_len(const pvw_ctx* c, u32 kind, u32 repr) {
+  size_t n = WIRE_FIXED + 8 * (size_t)c->L + (repr == PVW_REPR_NTT ? 8 * (size_t)c->L : 0) + 8 * wire_nranges(kind) + 8;
+  return (n + 15) & ~(size_t)15;
+}
+// the body length of a (kind, repr, ranges) the context can hold, or an error
+static int32_t wire_body_len(const pvw_ctx* c, u32 kind, u32 repr, const u32 r[4], size_t* out) {
+  if (kind < WIRE_PARAMS || kind > WIRE_SK) return fail(PVW_ERR_INVALID_FORMAT, "wire: unknown kind " + std::to_string(kind));
+  PVW_TRY(check_repr(repr));
+  if ((kind == WIRE_PARAMS || kind == WIRE_SK) && repr != PVW_REPR_POWER)
+    return fail(PVW_ERR_INVALID_FORMAT, "wire: parameters and secret keys carry repr POWER");
+  const size_t pb = wire_poly_bytes(c);
+  auto range = [&](u32 lo, u32 hi, u32 bound, const char* what) -> int32_t {
+    if (lo > hi || hi > bound)
+      return fail(PVW_ERR_INVALID_FORMAT, std::string("wire: ") + what + " range [" + std::to_string(lo) + ", " + std::to_string(hi) +
+                                              ") outside [0, " + std::to_string(bound) + ")");
+    return PVW_OK;
+  };
+  switch (kind) {
+    case WIRE_PARAMS: *out = 0; break;
+    case WIRE_SK: *out = (size_t)c->k * c->l * 8; break;
+    case WIRE_CRS: PVW_TRY(range(r[0], r[1], c->k, "CRS row")); *out = (size_t)(r[1] - r[0]) * c->k * pb; break;
+    case WIRE_PK: PVW_TRY(range(r[0], r[1], c->n, "public-key row")); *out = (size_t)(r[1] - r[0]) * c->k * pb; break;
+    default:
+      PVW_TRY(range(r[0], r[1], c->k, "c1 row"));
+      PVW_TRY(range(r[2], r[3], c->n, "c2 row"));
+      *out = ((size_t)(r[1] - r[0]) + (r[3] - r[2])) * pb;
+  }
+  return PVW_OK;
+}
+static void le_put(uint8_t* p, u64 v, int bytes) {
+  for (int i = 0; i < bytes; ++i) p[i] = (uint8_t)(v >> (8 * i));
+}
+static u64 le_get(const uint8_t* p, int bytes) {
+  u64 v = 0;
+  for (int i = 0; i < bytes; ++i) v |= (u64)p[i] << (8 * i);
+  return v;
+}
+static u32 f32_bits(float f) {
+  u32 b;
+  memcpy(&b, &f, 4);
+  return b;
+}
+
+// host codec (plain C++, the reference implementation of the format)
+static void wire_pack_one(const pvw_ctx* c, const u64* poly, uint8_t* out) {
+  u128 acc = 0;
+  u32 nb = 0;
+  size_t o = 0;
+  for (u32 i = 0; i < c->L; ++i) {
+    const u64 q = c->moduli[i];
+    const u32 w = wire_width(q);
+    for (u32 j = 0; j < c->l; ++j) {
+      acc |= (u128)(poly[(size_t)i * c->l + j] % q) << nb;
+      nb += w;
+      while (nb >= 8) {
+        out[o++] = (uint8_t)acc;
+        acc >>= 8;
+        nb -= 8;
+      }
+    }
+  }
+}
+// returns the number of fields >= q_i; *first = limb * l + slot of the first one
+static size_t wire_unpack_one(const pvw_ctx* c, const uint8_t* in, u64* poly, size_t* first) {
+  u128 acc = 0;
+  u32 nb = 0;
+  size_t o = 0, bad = 0;
+  for (u32 i = 0; i < c->L; ++i) {
+    const u64 q = c->moduli[i];
+    const u32 w = wire_width(q);
+    for (u32 j = 0; j < c->l; ++j) {
+      while (nb < w) {
+        acc |= (u128)in[o++] << nb;
+        nb += 8;
+      }
+      const u64 v = (u64)acc & ((1ull << w) - 1);
+      acc >>= w;
+      nb -= w;
+      if (poly) poly[(size_t)i * c->l + j] = v;
+      if (v >= q && bad++ == 0 && first) *first = (size_t)i * c->l + j;
+    }
+  }
+  return bad;
+}
+static int32_t wire_reject(const pvw_ctx* c, size_t poly, size_t at, const uint8_t* in) {
+  std::vector<u64> words(c->poly());
+  wire_unpack_one(c, in, words.data(), nullptr);
+  const u32 limb = (u32)(at / c->l), slot = (u32)(at % c->l);
+  char buf[200];
+  snprintf(buf, sizeof buf, "wire: residue out of range at polynomial %zu, limb %u, slot %u (field %llu >= q_%u = %llu)", poly, limb,
+           slot, (unsigned long long)words[at], limb, (unsigned long long)c->moduli[limb]);
+  return fail(PVW_ERR_DESERIALIZATION, buf);
+}
+// first rejected residue among `count` packed polynomials on the host (the error path of the device readers)
+static int32_t wire_find_reject(const pvw_ctx* c, const uint8_t* in, size_t count, size_t poly0) {
+  const size_t pb = wire_poly_bytes(c);
+  for (size_t p = 0; p < count; ++p) {
+    size_t at = 0;
+    if (wire_unpack_one(c, in + p * pb, nullptr, &at)) return wire_reject(c, poly0 + p, at, in + p * pb);
+  }
+  return fail(PVW_ERR_DESERIALIZATION, "wire: residues out of range (the host rescan found none: was the input changed meanwhile?)");
+}
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static int32_t wire_device_checks(const pvw_ctx* c) {
+  if (c->L > 64) return fail(PVW_ERR_INVALID_PARAMETERS, "the device wire codec takes at most 64 moduli");
+  return PVW_OK;
+}
+// polynomials per staging chunk: a multiple of 16 (every chunk starts 16-byte aligned in both forms), about `bytes` of words
+static size_t wire_chunk_polys(const pvw_ctx* c, size_t bytes) {
+  size_t n = bytes / (c->poly() * 8) / 16 * 16;
+  return n ? n : 16;
+}
+static size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+static int32_t wire_pack_enqueue(pvw_ctx* c, const u64* d_polys, size_t count, uint8_t* d_out, hipStream_t s) {
+  ProfScope ps(c, "wire_pack", s);
+  PVW_HIP(launch_wire_pack(d_polys, count, d_out, c->dt.mods, c->L, c->l, s));
+  return PVW_OK;
+}
+static int32_t wire_unpack_enqueue(pvw_ctx* c, const uint8_t* d_in, size_t count, u64* d_polys, u64* d_bad, hipStream_t s) {
+  ProfScope ps(c, "wire_unpack", s);
+  PVW_HIP(launch_wire_unpack(d_in, count, d_polys, (unsigned long long*)d_bad, c->dt.mods, c->L, c->l, s));
+  return PVW_OK;
+}
+
+// rows [lo, hi) of a matrix (k polynomials a row) from a packed host body: every row the shard holds is staged and checked
+// before any of them is unpacked, so a rejected body leaves the resident matrix as it was.  `commit` runs between the two
+// (invalidates the derived copies, allocates the matrix).  Bodies up to 1 GiB are staged whole; larger ones are read twice.
+static int32_t wire_load_rows(pvw_ctx* c, u64** Mp, u32 shard_lo, u32 shard_hi, u32 lo, u32 hi, const uint8_t* body, uint32_t repr,
+                              const std::function<int32_t()>& commit) {
+  const u32 a = lo > shard_lo ? lo : shard_lo, b = hi < shard_hi ? hi : shard_hi;
+  if (a >= b) return commit();
+  const size_t k = c->k, pb = wire_poly_bytes(c), rowbytes = k * pb, rowwords = k * c->poly();
+  const u32 m = 16 / (u32)(k & 15 ? (k & 1 ? 1 : (k & 3 ? 2 : (k & 7 ? 4 : 8))) : 16);   // rows of a 16-polynomial multiple
+  const uint8_t* src = body + (size_t)(a - lo) * rowbytes;
+  const size_t total = (size_t)(b - a) * rowbytes;
+  const bool whole = total <= ((size_t)1 << 30);
+  size_t stage_rows = whole ? (size_t)(b - a) : ((size_t)256 << 20) / rowbytes / m * m;
+  if (stage_rows == 0) stage_rows = m;
+  size_t word_rows = ((size_t)256 << 20) / (rowwords * 8) / m * m;
+  if (word_rows == 0) word_rows = m;
+  Workspace* w;
+  PVW_TRY(ws_acquire(c, &w));
+  uint8_t* d_pk = nullptr;
+  int32_t rc = PVW_OK;
+  if (hipMalloc((void**)&d_pk, up16(stage_rows * rowbytes) + 16) != hipSuccess) {
+    (void)hipGetLastError();
+    rc = fail(PVW_ERR_INTERNAL, "wire: no device memory for the staged body");
+  }
+  u64* d_bad = d_pk ? (u64*)(d_pk + up16(stage_rows * rowbytes)) : nullptr;
+  auto stage = [&](u32 r0, u32 cnt) -> int32_t {
+    PVW_HIP(hipMemcpyAsync(d_pk, src + (size_t)(r0 - a) * rowbytes, (size_t)cnt * rowbytes, hipMemcpyHostToDevice, w->stream));
+    return PVW_OK;
+  };
+  // pass 1: check
+  if (rc == PVW_OK && hipMemsetAsync(d_bad, 0, 8, w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "memset failed");
+  for (u32 r0 = a; rc == PVW_OK && r0 < b; r0 += (u32)stage_rows) {
+    const u32 cnt = (size_t)(b - r0) < stage_rows ? (b - r0) : (u32)stage_rows;
+    rc = stage(r0, cnt);
+    if (rc == PVW_OK) rc = wire_unpack_enqueue(c, d_pk, (size_t)cnt * k, nullptr, d_bad, w->stream);
+    if (rc == PVW_OK && !whole && hipStreamSynchronize(w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
+  }
+  u64 bad = 0;
+  if (rc == PVW_OK && (hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
+                       hipStreamSynchronize(w->stream) != hipSuccess))
+    rc = fail(PVW_ERR_INTERNAL, "wire: reading the check count failed");
+  if (rc == PVW_OK && bad) rc = wire_find_reject(c, src, (size_t)(b - a) * k, (size_t)(a - lo) * k);
+  // pass 2: unpack and tile
+  if (rc == PVW_OK) rc = commit();
+  if (rc == PVW_OK) rc = ws_scratch(w, word_rows * rowwords * 8);
+  for (u32 r0 = a; rc == PVW_OK && r0 < b; r0 += (u32)stage_rows) {
+    const u32 cnt = (size_t)(b - r0) < stage_rows ? (b - r0) : (u32)stage_rows;
+    if (!whole) rc = stage(r0, cnt);
+    for (u32 s0 = 0; rc == PVW_OK && s0 < cnt; s0 += (u32)word_rows) {
+      const u32 sc = (size_t)(cnt - s0) < word_rows ? (cnt - s0) : (u32)word_rows;
+      rc = wire_unpack_enqueue(c, d_pk + (size_t)s0 * rowbytes, (size_t)sc * k, (u64*)w->scratch, d_bad, w->stream);
+      if (rc == PVW_OK) rc = load_rows_device(c, *Mp, shard_lo, shard_hi, r0 + s0, r0 + s0 + sc, (const u64*)w->scratch, repr, w->stream);
+      if (rc == PVW_OK && hipStreamSynchronize(w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
+    }
+  }
+  if (hipStreamSynchronize(w->stream) != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
+  hipFree(d_pk);
+  ws_release(c, w);
+  return rc;
+}
+// rows [lo, hi) of a resident matrix, packed, to a host body (rows the shard does not hold are not written)
+static int32_t wire_get_rows(pvw_ctx* c, const u64* M, u32 shard_lo, u32 shard_hi, u32 lo, u32 hi, uint8_t* body, uint32_t repr) {
+  const u32 a = lo > shard_lo ? lo : shard_lo, b = hi < shard_hi ? hi : shard_hi;
+  if (a >= b) return PVW_OK;
+  if (!M) return fail(PVW_ERR_INVALID_PARAMETERS, "matrix not loaded");
+  const size_t k = c->k, pb = wire_poly_bytes(c), rowbytes = k * pb, rowwords = k * c->poly();
+  const u32 m = 16 / (u32)(k & 15 ? (k & 1 ? 1 : (k & 3 ? 2 : (k & 7 ? 4 : 8))) : 16);
+  size_t chunk = ((size_t)256 << 20) / (rowwords * 8) / m * m;
+  if (chunk == 0) chunk = m;
+  Workspace* w;
+  PVW_TRY(ws_acquire(c, &w));
+  const size_t cw = up16(chunk * rowwords * 8);
+  int32_t rc = ws_scratch(w, cw + up16(chunk * rowbytes));
+  for (u32 r0 = a; rc == PVW_OK && r0 < b; r0 += (u32)chunk) {
+    const u32 cnt = (size_t)(b - r0) < chunk ? (b - r0) : (u32)chunk;
+    uint8_t* d_pk = (uint8_t*)w->scratch + cw;
+    if (launch_untile(M, (u64*)w->scratch, cnt, r0 - shard_lo, c->k, c->L, c->l, repr == PVW_REPR_POWER, c->dt, w->stream) != hipSuccess)
+      rc = fail(PVW_ERR_INTERNAL, "untile failed");
+    if (rc == PVW_OK) rc = wire_pack_enqueue(c, (const u64*)w->scratch, (size_t)cnt * k, d_pk, w->stream);
+    if (rc == PVW_OK && (hipMemcpyAsync(body + (size_t)(r0 - lo) * rowbytes, d_pk, (size_t)cnt * rowbytes, hipMemcpyDeviceToHost,
+                                        w->stream) != hipSuccess ||
+                         hipStreamSynchronize(w->stream) != hipSuccess))
+      rc = fail(PVW_ERR_INTERNAL, "D2H failed");
+  }
+  ws_release(c, w);
+  return rc;
+}
+
+int32_t pvw_wire_poly_bytes(const pvw_ctx* c, size_t* out) {
+  if (!c || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  *out = wire_poly_bytes(c);
+  return PVW_OK;
+}
+
+int32_t pvw_wire_header(const pvw_ctx* c, uint32_t kind, uint32_t repr, uint32_t lo, uint32_t hi, uint32_t lo2, uint32_t hi2,
+                        uint8_t* out, size_t cap, size_t* len) {
+  if (!c || !len) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const u32 r[4] = {lo, hi, lo2, hi2};
+  size_t body = 0;
+  PVW_TRY(wire_body_len(c, kind, repr, r, &body));
+  const size_t hl = wire_header_len(c, kind, repr);
+  *len = hl;
+  if (!out) return PVW_OK;
+  if (cap < hl) return fail(PVW_ERR_SERIALIZATION, "wire: header buffer holds " + std::to_string(cap) + " bytes, needs " + std::to_string(hl));
+  memset(out, 0, hl);
+  memcpy(out, "PVWw", 4);
+  le_put(out + 4, 1, 2);
+  le_put(out + 6, kind, 2);
+  le_put(out + 8, repr, 4);
+  le_put(out + 12, c->n, 4);
+  le_put(out + 16, c->k, 4);
+  le_put(out + 20, c->l, 4);
+  le_put(out + 24, c->L, 4);
+  le_put(out + 28, f32_bits(c->variance), 4);
+  le_put(out + 32, c->b1, 8);
+  le_put(out + 40, c->b2, 8);
+  uint8_t* p = out + WIRE_FIXED;
+  for (u64 q : c->moduli) { le_put(p, q, 8); p += 8; }
+  if (repr == PVW_REPR_NTT)
+    for (u64 psi : c->psi) { le_put(p, psi, 8); p += 8; }
+  for (u32 i = 0; i < 2 * wire_nranges(kind); ++i) { le_put(p, r[i], 4); p += 4; }
+  le_put(p, body, 8);
+  return PVW_OK;
+}
+
+int32_t pvw_wire_header_check(const pvw_ctx* c, const uint8_t* in, size_t len, uint32_t* kind_out, uint32_t* repr_out,
+                              uint32_t* ranges, size_t* header_len) {
+  if (!c || !in) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (len < WIRE_FIXED) return fail(PVW_ERR_INVALID_FORMAT, "wire: truncated header (" + std::to_string(len) + " bytes)");
+  if (memcmp(in, "PVWw", 4) != 0) return fail(PVW_ERR_INVALID_FORMAT, "wire: bad magic");
+  const u32 version = (u32)le_get(in + 4, 2), kind = (u32)le_get(in + 6, 2), repr = (u32)le_get(in + 8, 4);
+  if (version != 1) return fail(PVW_ERR_INVALID_FORMAT, "wire: unsupported version " + std::to_string(version));
+  if (kind < WIRE_PARAMS || kind > WIRE_SK) return fail(PVW_ERR_INVALID_FORMAT, "wire: unknown kind " + std::to_string(kind));
+  const char* names[4] = {"n", "k", "l", "L"};
+  const u32 mine[4] = {c->n, c->k, c->l, c->L};
+  for (int f = 0; f < 4; ++f) {
+    const u32 v = (u32)le_get(in + 12 + 4 * f, 4);
+    if (v != mine[f]) {
+      char buf[120];
+      snprintf(buf, sizeof buf, "wire: parameter %s differs: expected %u, actual %u", names[f], mine[f], v);
+      return fail(PVW_ERR_DIMENSION_MISMATCH, buf);
+    }
+  }
+  if ((u32)le_get(in + 28, 4) != f32_bits(c->variance) || le_get(in + 32, 8) != c->b1 || le_get(in + 40, 8) != c->b2)
+    return fail(PVW_ERR_INVALID_FORMAT, "wire: the blob was written for other parameters (variance or error bounds differ)");
+  if (repr != PVW_REPR_POWER && repr != PVW_REPR_NTT) return fail(PVW_ERR_INVALID_FORMAT, "wire: unknown representation");
+  const size_t hl = wire_header_len(c, kind, repr);
+  if (len < hl) return fail(PVW_ERR_INVALID_FORMAT, "wire: truncated header (" + std::to_string(len) + " of " + std::to_string(hl) + " bytes)");
+  const uint8_t* p = in + WIRE_FIXED;
+  for (u32 i = 0; i < c->L; ++i, p += 8)
+    if (le_get(p, 8) != c->moduli[i]) return fail(PVW_ERR_INVALID_FORMAT, "wire: the blob was written for other moduli (q_" + std::to_string(i) + ")");
+  if (repr == PVW_REPR_NTT)
+    for (u32 i = 0; i < c->L; ++i, p += 8)
+      if (le_get(p, 8) != c->psi[i])
+        return fail(PVW_ERR_INVALID_FORMAT, "wire: NTT-domain body under other roots (psi_" + std::to_string(i) + " differs from this context's)");
+  u32 r[4] = {0, 0, 0, 0};
+  for (u32 i = 0; i < 2 * wire_nranges(kind); ++i, p += 4) r[i] = (u32)le_get(p, 4);
+  size_t body = 0;
+  PVW_TRY(wire_body_len(c, kind, repr, r, &body));
+  if (le_get(p, 8) != body) return fail(PVW_ERR_INVALID_FORMAT, "wire: body_len does not match the kind and row ranges");
+  for (const uint8_t* z = p + 8; z < in + hl; ++z)
+    if (*z) return fail(PVW_ERR_INVALID_FORMAT, "wire: header padding is not zero");
+  if (len < hl + body) return fail(PVW_ERR_INVALID_FORMAT, "wire: truncated body (" + std::to_string(len - hl) + " of " + std::to_string(body) + " bytes)");
+  if (len > hl + body) return fail(PVW_ERR_INVALID_FORMAT, "wire: " + std::to_string(len - hl - body) + " trailing bytes");
+  if (kind_out) *kind_out = kind;
+  if (repr_out) *repr_out = repr;
+  if (ranges) memcpy(ranges, r, sizeof r);
+  if (header_len) *header_len = hl;
+  return PVW_OK;
+}
+
+int32_t pvw_wire_pack_host(const pvw_ctx* c, const uint64_t* polys, size_t count, uint8_t* out) {
+  if (!c || ((!polys || !out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const size_t pb = wire_poly_bytes(c), P = c->poly();
+  if (count) memset(out, 0, count * pb);
+  for (size_t p = 0; p < count; ++p) wire_pack_one(c, polys + p * P, out + p * pb);
+  return PVW_OK;
+}
+
+int32_t pvw_wire_unpack_host(const pvw_ctx* c, const uint8_t* in, size_t count, uint64_t* polys, uint64_t* bad_out) {
+  if (!c || ((!polys || !in) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const size_t pb = wire_poly_bytes(c), P = c->poly();
+  size_t bad = 0, first_poly = 0, first_at = 0;
+  for (size_t p = 0; p < count; ++p) {
+    size_t at = 0;
+    const size_t nb = wire_unpack_one(c, in + p * pb, polys + p * P, &at);
+    if (nb && !bad) { first_poly = p; first_at = at; }
+    bad += nb;
+  }
+  if (bad_out) *bad_out = bad;
+  return bad ? wire_reject(c, first_poly, first_at, in + first_poly * pb) : PVW_OK;
+}
+
+int32_t pvw_wire_pack_device(pvw_ctx* c, const uint64_t* d_polys, size_t count, uint8_t* d_out, void* stream) {
+  if (!c || ((!d_polys || !d_out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (!aligned16(d_polys) || !aligned16(d_out)) return fail(PVW_ERR_INVALID_PARAMETERS, "wire: device buffers must be 16-byte aligned");
+  PVW_TRY(wire_device_checks(c));
+  PVW_TRY(ensure_device(c));
+  return wire_pack_enqueue(c, d_polys, count, d_out, stream ? (hipStream_t)stream : c->stream);
+}
+
+int32_t pvw_wire_unpack_device(pvw_ctx* c, const uint8_t* d_in, size_t count, uint64_t* d_polys, uint64_t* d_bad, void* stream) {
+  if (!c || !d_bad || ((!d_in || !d_polys) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (!aligned16(d_in) || !aligned16(d_polys)) return fail(PVW_ERR_INVALID_PARAMETERS, "wire: device buffers must be 16-byte aligned");
+  PVW_TRY(wire_device_checks(c));
+  PVW_TRY(ensure_device(c));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  PVW_HIP(hipMemsetAsync(d_bad, 0, 8, s));
+  return wire_unpack_enqueue(c, d_in, count, d_polys, d_bad, s);
+}
+
+int32_t pvw_wire_pack(pvw_ctx* c, const uint64_t* polys, size_t count, uint8_t* out) {
+  if (!c || ((!polys || !out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(wire_device_checks(c));
+  if (!count) return PVW_OK;
+  PVW_TRY(ensure_device(c));
+  const size_t pb = wire_poly_bytes(c), P = c->poly(), chunk = wire_chunk_polys(c, (size_t)256 << 20);
+  // output the device can write (pvw_host_alloc, or pinned / registered by the caller): the kernel stores into it directly
+  uint8_t* direct = (uint8_t*)device_alias(out, count * pb);
+  if (direct && !aligned16(direct)) direct = nullptr;
+  Workspace* w;
+  PVW_TRY(ws_acquire(c, &w));
+  const size_t n0 = count < chunk ? count : chunk, cw = up16(n0 * P * 8);
+  int32_t rc = ws_scratch(w, cw + up16(n0 * pb));
+  for (size_t p0 = 0; rc == PVW_OK && p0 < count; p0 += chunk) {
+    const size_t cnt = count - p0 < chunk ? count - p0 : chunk;
+    uint8_t* d_pk = direct ? direct + p0 * pb : (uint8_t*)w->scratch + cw;
+    if (hipMemcpyAsync(w->scratch, polys + p0 * P, cnt * P * 8, hipMemcpyHostToDevice, w->stream) != hipSuccess)
+      rc = fail(PVW_ERR_INTERNAL, "H2D failed");
+    if (rc == PVW_OK) rc = wire_pack_enqueue(c, (const u64*)w->scratch, cnt, d_pk, w->stream);
+    if (rc == PVW_OK && !direct && hipMemcpyAsync(out + p0 * pb, d_pk, cnt * pb, hipMemcpyDeviceToHost, w->stream) != hipSuccess)
+      rc = fail(PVW_ERR_INTERNAL, "D2H failed");
+    if (hipStreamSynchronize(w->stream) != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
+  }
+  ws_release(c, w);
+  return rc;
+}
+
+int32_t pvw_wire_unpack(pvw_ctx* c, const uint8_t* in, size_t count, uint64_t* polys) {
+  if (!c || ((!polys || !in) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(wire_device_checks(c));
+  if (!count) return PVW_OK;
+  PVW_TRY(ensure_device(c));
+  const size_t pb = wire_poly_bytes(c), P = c->poly(), chunk = wire_chunk_polys(c, (size_t)256 << 20);
+  Workspace* w;
+  PVW_TRY(ws_acquire(c, &w));
+  const size_t n0 = count < chunk ? count : chunk, cw = up16(n0 * P * 8), cp = up16(n0 * pb);
+  int32_t rc = ws_scratch(w, cw + cp + 16);
+  u64* d_bad = (u64*)((uint8_t*)w->scratch + cw + cp);
+  u64 bad = 0;
+  for (size_t p0 = 0; rc == PVW_OK && p0 < count; p0 += chunk) {
+    const size_t cnt = count - p0 < chunk ? count - p0 : chunk;
+    uint8_t* d_pk = (uint8_t*)w->scratch + cw;
+    u64 nb = 0;
+    if (hipMemcpyAsync(d_pk, in + p0 * pb, cnt * pb, hipMemcpyHostToDevice, w->stream) != hipSuccess ||
+        hipMemsetAsync(d_bad, 0, 8, w->stream) != hipSuccess)
+      rc = fail(PVW_ERR_INTERNAL, "H2D failed");
+    if (rc == PVW_OK) rc = wire_unpack_enqueue(c, d_pk, cnt, (u64*)w->scratch, d_bad, w->stream);
+    if (rc == PVW_OK && (hipMemcpyAsync(polys + p0 * P, w->scratch, cnt * P * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
+                         hipMemcpyAsync(&nb, d_bad, 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess))
+      rc = fail(PVW_ERR_INTERNAL, "D2H failed");
+    if (hipStreamSynchronize(w->stream) != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
+    bad += nb;
+  }
+  ws_release(c, w);
+  if (rc == PVW_OK && bad) rc = wire_find_reject(c, in, count, 0);
+  return rc;
+}
+
+int32_t pvw_load_pk_wire(pvw_ctx* c, uint32_t lo, uint32_t hi, const uint8_t* body, uint32_t repr) {
+  if (!c || (!body && lo != hi)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(check_repr(repr));
+  PVW_TRY(check_party_range(c, lo, hi));
+  PVW_TRY(wire_device_checks(c));
+  PVW_TRY(ensure_device(c));
+  PVW_TRY(wire_load_rows(c, &c->dB, c->party_lo, c->party_hi, lo, hi, body, repr, [&]() -> int32_t {
+    c->xm_valid = false; c->pkB_valid = false; c->pk_wide = false;
+    return ensure_matrix(c, &c->dB, c->rowsB());
+  }));
+  if (hi > c->num_keys) c->num_keys = hi;                                          // public_key.rs:245-247
+  return PVW_OK;
+}
+
+int32_t pvw_get_pk_wire(pvw_ctx* c, uint32_t lo, uint32_t hi, uint8_t* body_out, uint32_t repr) {
+  if (!c || (!body_out && lo != hi)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(check_repr(repr));
+  PVW_TRY(check_party_range(c, lo, hi));
+  PVW_TRY(wire_device_checks(c));
+  PVW_TRY(ensure_device(c));
+  return wire_get_rows(c, c->dB, c->party_lo, c->party_hi, lo, hi, body_out, repr);
+}
+
+int32_t pvw_load_crs_wire(pvw_ctx* c, const uint8_t* body, uint32_t repr) {
+  if (!c || !body) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(check_repr(repr));
+  PVW_TRY(wire_device_checks(c));
+  PVW_TRY(ensure_device(c));
+  PVW_TRY(wire_load_rows(c, &c->dA, c->c1_lo, c->c1_hi, 0, c->k, body, repr, [&]() -> int32_t {
+    c->xm_valid = false; c->pkA_valid = false; c->pk_wide = false;
+    return ensure_matrix(c, &c->dA, c->rowsA());
+  }));
+  c->crs_loaded = true;
+  return PVW_OK;
+}
+
+int32_t pvw_get_crs_wire(pvw_ctx* c, uint8_t* body_out, uint32_t repr) {
+  if (!c || !body_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(check_repr(repr));
+  PVW_TRY(wire_device_checks(c));
+  PVW_TRY(ensure_device(c));
+  return wire_get_rows(c, c->dA, c->c1_lo, c->c1_hi, 0, c->k, body_out, repr);
 }
 
 }  // extern "C"

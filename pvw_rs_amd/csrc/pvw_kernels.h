@@ -308,4 +308,12 @@ hipError_t launch_decode(u64* noisy, u64* out, size_t count, const DecodeTables&
                          u64* wipe = nullptr, size_t wipe_bytes = 0, bool* wiped = nullptr, u64* noise = nullptr,
                          u32* status = nullptr);
 
+// wire format v1 (pvw_wire.hip): `count` polynomials [L][ell] u64 <-> packed bytes (w_i = bit length of q_i bits per
+// residue).  words / packed pointers 16-byte aligned; L <= 64.  Unpack: *bad += residues >= q_i (the caller zeroes it);
+// words == NULL only counts.  init_wire_attributes: dynamic-LDS limit of both kernels (once per device).
+hipError_t launch_wire_pack(const u64* words, size_t count, unsigned char* out, const Mod* mods, u32 L, u32 ell, hipStream_t s);
+hipError_t launch_wire_unpack(const unsigned char* in, size_t count, u64* words, unsigned long long* bad, const Mod* mods, u32 L,
+                              u32 ell, hipStream_t s);
+hipError_t init_wire_attributes();
+
 }  // namespace pvw

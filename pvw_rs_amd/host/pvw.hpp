@@ -8,6 +8,7 @@
 //   polynomial  = std::vector<uint64_t> of L*l residues, limb-major (parameters.rs:433-458)
 //   randomness  = a 32-byte seed (the reference uses thread_rng(), encryption.rs:138,164,180)
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <memory>
@@ -310,6 +311,29 @@ class GlobalPublicKey {
   uint32_t num_public_keys() const { uint32_t v = 0; check(pvw_num_public_keys(params->ctx, &v)); return v; }   // :344
   bool is_full() const { int32_t v = 0; check(pvw_is_full(params->ctx, &v)); return v != 0; }                   // :349
   std::pair<uint32_t, uint32_t> dimensions() const { return {params->n, params->k}; }
+  // wire format v1: rows [lo, hi) as a kind-3 blob, packed on the device
+  std::vector<uint8_t> to_bytes(uint32_t lo, uint32_t hi, uint32_t repr = PVW_REPR_POWER) const {
+    size_t hl = 0, pb = 0;
+    check(pvw_wire_header(params->ctx, 3, repr, lo, hi, 0, 0, nullptr, 0, &hl));
+    check(pvw_wire_poly_bytes(params->ctx, &pb));
+    std::vector<uint8_t> out(hl + (size_t)(hi - lo) * params->k * pb);
+    check(pvw_wire_header(params->ctx, 3, repr, lo, hi, 0, 0, out.data(), hl, &hl));
+    check(pvw_get_pk_wire(params->ctx, lo, hi, out.data() + hl, repr));
+    return out;
+  }
+  // the rows of a kind-3 blob, checked before anything is stored (DeserializationError leaves the key as it was)
+  void load_bytes(const std::vector<uint8_t>& blob) {
+    uint32_t kind = 0, repr = 0, r[4] = {0, 0, 0, 0};
+    size_t hl = 0;
+    check(pvw_wire_header_check(params->ctx, blob.data(), blob.size(), &kind, &repr, r, &hl));
+    if (kind != 3) throw PvwError(PVW_ERR_INVALID_FORMAT, "wire: not a public-key blob");
+    check(pvw_load_pk_wire(params->ctx, r[0], r[1], blob.data() + hl, repr));
+  }
+  static GlobalPublicKey from_bytes(const PvwCrs& crs, const std::vector<uint8_t>& blob) {
+    GlobalPublicKey g(crs);
+    g.load_bytes(blob);
+    return g;
+  }
 };
 
 // PvwCiphertext (src/crypto/encryption.rs:15-24)
@@ -322,6 +346,36 @@ class PvwCiphertext {
   void validate() const {                                                                            // :41-76
     if (c1.size() != (size_t)params->k * params->poly_words()) throw PvwError(1, "c1 has the wrong number of components");
     if (c2.size() != (size_t)params->n * params->poly_words()) throw PvwError(1, "c2 has the wrong number of components");
+  }
+  // wire format v1: c1 rows [0, k) and c2 rows [lo, hi) as a kind-4 blob, packed on the device
+  std::vector<uint8_t> to_bytes(uint32_t lo, uint32_t hi) const {
+    validate();
+    const size_t P = params->poly_words();
+    size_t hl = 0, pb = 0;
+    check(pvw_wire_header(params->ctx, 4, repr, 0, params->k, lo, hi, nullptr, 0, &hl));
+    check(pvw_wire_poly_bytes(params->ctx, &pb));
+    std::vector<uint64_t> polys(c1);
+    polys.insert(polys.end(), c2.begin() + (size_t)lo * P, c2.begin() + (size_t)hi * P);
+    const size_t count = polys.size() / P;
+    std::vector<uint8_t> out(hl + count * pb);
+    check(pvw_wire_header(params->ctx, 4, repr, 0, params->k, lo, hi, out.data(), hl, &hl));
+    check(pvw_wire_pack(params->ctx, polys.data(), count, out.data() + hl));
+    return out;
+  }
+  std::vector<uint8_t> to_bytes() const { return to_bytes(0, params->n); }
+  // a kind-4 blob, unpacked and checked on the device; rows the blob does not carry are zero
+  static PvwCiphertext from_bytes(const std::shared_ptr<PvwParameters>& p, const std::vector<uint8_t>& blob) {
+    uint32_t kind = 0, rp = 0, r[4] = {0, 0, 0, 0};
+    size_t hl = 0;
+    check(pvw_wire_header_check(p->ctx, blob.data(), blob.size(), &kind, &rp, r, &hl));
+    if (kind != 4) throw PvwError(PVW_ERR_INVALID_FORMAT, "wire: not a ciphertext blob");
+    const size_t P = p->poly_words(), n1 = r[1] - r[0], n2 = r[3] - r[2];
+    std::vector<uint64_t> words((n1 + n2) * P);
+    check(pvw_wire_unpack(p->ctx, blob.data() + hl, n1 + n2, words.data()));
+    PvwCiphertext ct{std::vector<uint64_t>((size_t)p->k * P), std::vector<uint64_t>((size_t)p->n * P), p, rp};
+    std::copy(words.begin(), words.begin() + n1 * P, ct.c1.begin() + (size_t)r[0] * P);
+    std::copy(words.begin() + n1 * P, words.end(), ct.c2.begin() + (size_t)r[2] * P);
+    return ct;
   }
 };
 

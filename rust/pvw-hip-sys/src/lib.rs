@@ -194,4 +194,18 @@ extern "C" {
     pub fn pvw_prepare(ctx: *mut PvwCtx, flags: u32, stream: *mut c_void, bytes_out: *mut u64) -> i32;
     pub fn pvw_ctx_packed_active(ctx: *const PvwCtx, width_out: *mut u32) -> i32;
     pub fn pvw_ctx_synchronize(ctx: *mut PvwCtx) -> i32;
+    // ---- wire format, version 1; the `pvw` shim keeps fhe-math serde ------------------
+    pub fn pvw_wire_poly_bytes(ctx: *const PvwCtx, out: *mut usize) -> i32;
+    pub fn pvw_wire_header(ctx: *const PvwCtx, kind: u32, repr: u32, lo: u32, hi: u32, lo2: u32, hi2: u32, out: *mut u8, cap: usize, len: *mut usize) -> i32;
+    pub fn pvw_wire_header_check(ctx: *const PvwCtx, data: *const u8, len: usize, kind: *mut u32, repr: *mut u32, ranges: *mut u32, header_len: *mut usize) -> i32;
+    pub fn pvw_wire_pack(ctx: *mut PvwCtx, polys: *const u64, count: usize, out: *mut u8) -> i32;
+    pub fn pvw_wire_pack_device(ctx: *mut PvwCtx, d_polys: *const u64, count: usize, d_out: *mut u8, stream: *mut c_void) -> i32;
+    pub fn pvw_wire_unpack(ctx: *mut PvwCtx, data: *const u8, count: usize, polys: *mut u64) -> i32;
+    pub fn pvw_wire_unpack_device(ctx: *mut PvwCtx, d_in: *const u8, count: usize, d_polys: *mut u64, d_bad: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_wire_pack_host(ctx: *const PvwCtx, polys: *const u64, count: usize, out: *mut u8) -> i32;
+    pub fn pvw_wire_unpack_host(ctx: *const PvwCtx, data: *const u8, count: usize, polys: *mut u64, bad_out: *mut u64) -> i32;
+    pub fn pvw_load_pk_wire(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, body: *const u8, repr: u32) -> i32;
+    pub fn pvw_get_pk_wire(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, body_out: *mut u8, repr: u32) -> i32;
+    pub fn pvw_load_crs_wire(ctx: *mut PvwCtx, body: *const u8, repr: u32) -> i32;
+    pub fn pvw_get_crs_wire(ctx: *mut PvwCtx, body_out: *mut u8, repr: u32) -> i32;
 }
