@@ -38,13 +38,13 @@ static int32_t fail(int32_t code, const std::string& msg) {
   g_last_error = msg;
   return code;
 }
-#define PVW_HIP(expr)                                                                      \
+#define PVW_HIP_AS(code, expr)                                                             \
   do {                                                                                     \
     hipError_t e_ = (expr);                                                                \
     if (e_ != hipSuccess)                                                                  \
-      return fail(PVW_ERR_INTERNAL, std::string("HIP error: ") + hipGetErrorString(e_) +  \
-                                        " at " #expr);                                     \
+      return fail(code, std::string("HIP error: ") + hipGetErrorString(e_) + " at " #expr); \
   } while (0)
+#define PVW_HIP(expr) PVW_HIP_AS(PVW_ERR_INTERNAL, expr)
 #define PVW_TRY(expr)              \
   do {                             \
     int32_t rc_ = (expr);          \
@@ -133,24 +133,32 @@ struct Workspace {
   u64* gtmpA = nullptr;      // GEMM intermediates [limb][slot][v][row]
   u64* gtmpB = nullptr;
   u64* gtmpK = nullptr;      // ... for key generation (k rows)
-  // helper stream + events for pvw_decrypt_batch_device (decode of chunk i under the MAC of chunk i+1)
+  // helper stream + events (ws_aux): decode of chunk i under the MAC of chunk i+1, key uploads under key generation
   hipStream_t aux = nullptr;
+  bool aux_used = false;     // by the current host call: drained by host_call
   std::vector<hipEvent_t> events;
   // device regions that hold secret-key material during the current call (sk coefficients, NTT(sk), key errors,
   // their MFMA-tiled / digitised copies): cleared on the call's stream before the workspace goes back to the pool
   // (the reference's SecretKey is Zeroize + ZeroizeOnDrop, src/keys/secret_key.rs:20-30).  `wiped` remembers what
-  // the last call cleared, for pvw_selftest_secret_residue.
-  struct Span { void* p; size_t bytes; };
+  // the last call that had any cleared, for pvw_selftest_secret_residue.
+  struct Span { void* p; size_t bytes; bool cleared; };
   std::vector<Span> secrets, wiped;
 };
-static void ws_mark_secret(Workspace* w, void* p, size_t bytes) {
-  if (p && bytes) w->secrets.push_back(Workspace::Span{p, bytes});
+// cleared: a kernel has cleared the region already (the wipe records it without a memset).  Marking a region again
+// replaces its earlier mark.
+static void ws_mark_secret(Workspace* w, void* p, size_t bytes, bool cleared = false) {
+  if (!p || !bytes) return;
+  for (Workspace::Span& sp : w->secrets)
+    if (sp.p == p) { sp.bytes = bytes > sp.bytes ? bytes : sp.bytes; sp.cleared = cleared; return; }
+  w->secrets.push_back(Workspace::Span{p, bytes, cleared});
 }
-// enqueue the wipes on `s` (call after the last kernel that reads the regions has been enqueued on `s`)
+// enqueue the wipes on `s` (call after the last kernel that reads the regions has been enqueued on `s`); nothing
+// marked: nothing enqueued, and the record of the last wipe stays
 static hipError_t ws_wipe_secrets(Workspace* w, hipStream_t s) {
+  if (w->secrets.empty()) return hipSuccess;
   hipError_t rc = hipSuccess;
   for (const Workspace::Span& sp : w->secrets) {
-    hipError_t e = hipMemsetAsync(sp.p, 0, sp.bytes, s);
+    hipError_t e = sp.cleared ? hipSuccess : hipMemsetAsync(sp.p, 0, sp.bytes, s);
     if (e != hipSuccess) rc = e;
   }
   w->wiped = w->secrets;
@@ -582,6 +590,80 @@ static int32_t ws_for_stream(pvw_ctx* c, hipStream_t s, Workspace** out) {
   return PVW_OK;
 }
 
+// The scratch of one call: regions added in order, each rounded up to `align` bytes (256; the wire codec's 16).  `total`
+// is what ws_scratch is asked for; at<T>(i) points into the block that take() bound.
+struct Scratch {
+  size_t align, total = 0;
+  std::vector<size_t> off;
+  char* base = nullptr;
+  explicit Scratch(size_t a = 256) : align(a) {}
+  size_t add(size_t bytes) {
+    off.push_back(total);
+    total += (bytes + align - 1) & ~(align - 1);
+    return off.size() - 1;
+  }
+  int32_t take(Workspace* w) {
+    PVW_TRY(ws_scratch(w, total));
+    base = (char*)w->scratch;
+    return PVW_OK;
+  }
+  template <class T = u64> T* at(size_t i) const { return (T*)(base + off[i]); }
+  size_t bytes(size_t i) const { return (i + 1 < off.size() ? off[i + 1] : total) - off[i]; }   // rounded
+  // regions i..j (one contiguous span) hold key material for the rest of the call
+  void secret(Workspace* w, size_t i, size_t j) const { ws_mark_secret(w, base + off[i], off[j] + bytes(j) - off[i]); }
+};
+
+// the helper stream and at least `events` events, for a call that runs on two streams
+static int32_t ws_aux(Workspace* w, size_t events) {
+  if (!w->aux) PVW_HIP(hipStreamCreateWithFlags(&w->aux, hipStreamNonBlocking));
+  while (w->events.size() < events) {
+    hipEvent_t e;
+    PVW_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    w->events.push_back(e);
+  }
+  w->aux_used = true;
+  return PVW_OK;
+}
+
+// Every host-buffer entry point runs its body here, on a pooled workspace and its stream.  However the body returns (early
+// through PVW_HIP / PVW_TRY included), the helper stream is drained, the regions the body marked secret are cleared behind
+// its last launch, the stream is drained, and only then does the workspace go back to the pool.  The first error wins.
+template <class Body>
+static int32_t host_call(pvw_ctx* c, Body&& body) {
+  Workspace* w;
+  PVW_TRY(ws_acquire(c, &w));
+  int32_t rc = body(w);
+  auto keep = [&](hipError_t e, const char* what) {
+    if (e != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, std::string(what) + " failed: " + hipGetErrorString(e));
+  };
+  if (w->aux_used) keep(hipStreamSynchronize(w->aux), "helper stream sync");
+  w->aux_used = false;
+  keep(ws_wipe_secrets(w, w->stream), "wipe");
+  keep(hipStreamSynchronize(w->stream), "stream sync");
+  ws_release(c, w);
+  return rc;
+}
+
+// device-pointer calls: the caller's stream (NULL: the context's) and its workspace; dealers != 0: a multi-dealer encrypt,
+// checked against stream capture before the workspace is looked up
+static hipStream_t call_stream(const pvw_ctx* c, void* stream) { return stream ? (hipStream_t)stream : c->stream; }
+static int32_t multi_capture_check(pvw_ctx* c, hipStream_t s, size_t D);
+static int32_t device_ws(pvw_ctx* c, void* stream, hipStream_t* s, Workspace** w, size_t dealers = 0) {
+  *s = call_stream(c, stream);
+  if (dealers) PVW_TRY(multi_capture_check(c, *s, dealers));
+  return ws_for_stream(c, *s, w);
+}
+// the end of a device-pointer call that marked key material: nothing of a failed call stays queued; the regions are
+// cleared on the caller's stream behind the call's last launch (no wait on success)
+static int32_t device_end(Workspace* w, hipStream_t s, int32_t rc) {
+  if (rc != PVW_OK) {
+    if (w->aux) (void)hipStreamSynchronize(w->aux);
+    (void)hipStreamSynchronize(s);
+  }
+  if (ws_wipe_secrets(w, s) != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, "wipe failed");
+  return rc;
+}
+
 // ------------------------------------------------------------------------ parameters
 static int32_t validate_params(const pvw_params_t* p) {
   if (!p) return fail(PVW_ERR_INVALID_PARAMETERS, "params is NULL");
@@ -879,23 +961,17 @@ static int32_t load_rows_host(pvw_ctx* c, u64* M, u32 shard_lo, u32 shard_hi, u3
   const u32 a = lo > shard_lo ? lo : shard_lo, b = hi < shard_hi ? hi : shard_hi;
   if (a >= b) return PVW_OK;
   const size_t rowwords = (size_t)c->k * c->poly();
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
   size_t chunk = ((size_t)256 << 20) / (rowwords * 8);
   if (chunk == 0) chunk = 1;
-  int32_t rc = ws_scratch(w, (chunk < (size_t)(b - a) ? chunk : (size_t)(b - a)) * rowwords * 8);
-  for (u32 r0 = a; rc == PVW_OK && r0 < b; r0 += (u32)chunk) {
-    const u32 cnt = (b - r0) < chunk ? (b - r0) : (u32)chunk;
-    if (hipMemcpyAsync(w->scratch, src + (size_t)(r0 - lo) * rowwords, cnt * rowwords * 8,
-                       hipMemcpyHostToDevice, w->stream) != hipSuccess) {
-      rc = fail(PVW_ERR_INTERNAL, "H2D copy failed");
-      break;
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(ws_scratch(w, (chunk < (size_t)(b - a) ? chunk : (size_t)(b - a)) * rowwords * 8));
+    for (u32 r0 = a; r0 < b; r0 += (u32)chunk) {
+      const u32 cnt = (b - r0) < chunk ? (b - r0) : (u32)chunk;
+      PVW_HIP(hipMemcpyAsync(w->scratch, src + (size_t)(r0 - lo) * rowwords, cnt * rowwords * 8, hipMemcpyHostToDevice, w->stream));
+      PVW_TRY(load_rows_device(c, M, shard_lo, shard_hi, r0, r0 + cnt, (const u64*)w->scratch, repr, w->stream));
     }
-    rc = load_rows_device(c, M, shard_lo, shard_hi, r0, r0 + cnt, (const u64*)w->scratch, repr, w->stream);
-    if (rc == PVW_OK && hipStreamSynchronize(w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
-  }
-  ws_release(c, w);
-  return rc;
+    return PVW_OK;
+  });
 }
 // dealers per gemm_digits launch: PVW_GEMM_VB batches of 16 (they share one pass over the matrix through L2)
 static u32 gemm_vb() {   // tuning build: PVW_GEMM_VB
@@ -994,9 +1070,9 @@ int32_t pvw_prepare(pvw_ctx* c, uint32_t flags, void* stream, uint64_t* bytes_ou
   if (flags & ~(uint32_t)(PVW_PREPARE_PACKED | PVW_PREPARE_MFMA)) return fail(PVW_ERR_INVALID_PARAMETERS, "unknown prepare flag");
   PVW_TRY(ensure_device(c));
   if (!c->crs_loaded) return fail(PVW_ERR_CRS, "CRS not loaded");
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t s;
   Workspace* w;
-  PVW_TRY(ws_for_stream(c, s, &w));
+  PVW_TRY(device_ws(c, stream, &s, &w));
   size_t taken = 0;
   if (flags & PVW_PREPARE_PACKED) (void)ensure_packed(c, s, true, &taken);       // 0 = does not qualify / no room: pvw_ctx_packed_active tells
   if (flags & PVW_PREPARE_MFMA) {
@@ -1016,11 +1092,19 @@ static int32_t check_repr(uint32_t repr) {
   return PVW_OK;
 }
 
+// matrix A (the CRS) or B (the public key) is about to change: its MFMA-tiled and packed copies are stale, and whether
+// the matrices hold unreduced words is not known until they are packed again
+static void matrix_changed(pvw_ctx* c, bool crs) {
+  c->xm_valid = false;
+  (crs ? c->pkA_valid : c->pkB_valid) = false;
+  c->pk_wide = false;
+}
+
 int32_t pvw_load_crs(pvw_ctx* c, const uint64_t* a, uint32_t repr) {
   if (!c || !a) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   PVW_TRY(check_repr(repr));
   PVW_TRY(ensure_device(c));
-  c->xm_valid = false; c->pkA_valid = false; c->pk_wide = false;
+  matrix_changed(c, true);
   PVW_TRY(ensure_matrix(c, &c->dA, c->rowsA()));
   PVW_TRY(load_rows_host(c, c->dA, c->c1_lo, c->c1_hi, 0, c->k, a, repr));
   c->crs_loaded = true;
@@ -1030,17 +1114,16 @@ int32_t pvw_load_crs_device(pvw_ctx* c, const uint64_t* d_a, uint32_t repr, void
   if (!c || !d_a) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   PVW_TRY(check_repr(repr));
   PVW_TRY(ensure_device(c));
-  c->xm_valid = false; c->pkA_valid = false; c->pk_wide = false;
+  matrix_changed(c, true);
   PVW_TRY(ensure_matrix(c, &c->dA, c->rowsA()));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  PVW_TRY(load_rows_device(c, c->dA, c->c1_lo, c->c1_hi, 0, c->k, d_a, repr, s));
+  PVW_TRY(load_rows_device(c, c->dA, c->c1_lo, c->c1_hi, 0, c->k, d_a, repr, call_stream(c, stream)));
   c->crs_loaded = true;
   return PVW_OK;
 }
 int32_t pvw_crs_generate(pvw_ctx* c, const uint8_t seed[32]) {
   if (!c || !seed) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   PVW_TRY(ensure_device(c));
-  c->xm_valid = false; c->pkA_valid = false; c->pk_wide = false;
+  matrix_changed(c, true);
   PVW_TRY(ensure_matrix(c, &c->dA, c->rowsA()));
   {
     ProfScope ps(c, "fill_uniform", c->stream);
@@ -1188,22 +1271,17 @@ static int32_t get_rows(pvw_ctx* c, const u64* M, u32 shard_lo, u32 shard_hi, u3
   if (a >= b) return PVW_OK;
   if (!M) return fail(PVW_ERR_INVALID_PARAMETERS, "matrix not loaded");
   const size_t rowwords = (size_t)c->k * c->poly();
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
   size_t chunk = ((size_t)256 << 20) / (rowwords * 8);
   if (chunk == 0) chunk = 1;
-  int32_t rc = ws_scratch(w, (chunk < (size_t)(b - a) ? chunk : (size_t)(b - a)) * rowwords * 8);
-  for (u32 r0 = a; rc == PVW_OK && r0 < b; r0 += (u32)chunk) {
-    const u32 cnt = (b - r0) < chunk ? (b - r0) : (u32)chunk;
-    if (launch_untile(M, (u64*)w->scratch, cnt, r0 - shard_lo, c->k, c->L, c->l, repr == PVW_REPR_POWER,
-                      c->dt, w->stream) != hipSuccess ||
-        hipMemcpyAsync(dst + (size_t)(r0 - lo) * rowwords, w->scratch, cnt * rowwords * 8,
-                       hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
-        hipStreamSynchronize(w->stream) != hipSuccess)
-      rc = fail(PVW_ERR_INTERNAL, "untile / D2H failed");
-  }
-  ws_release(c, w);
-  return rc;
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(ws_scratch(w, (chunk < (size_t)(b - a) ? chunk : (size_t)(b - a)) * rowwords * 8));
+    for (u32 r0 = a; r0 < b; r0 += (u32)chunk) {
+      const u32 cnt = (b - r0) < chunk ? (b - r0) : (u32)chunk;
+      PVW_HIP(launch_untile(M, (u64*)w->scratch, cnt, r0 - shard_lo, c->k, c->L, c->l, repr == PVW_REPR_POWER, c->dt, w->stream));
+      PVW_HIP(hipMemcpyAsync(dst + (size_t)(r0 - lo) * rowwords, w->scratch, cnt * rowwords * 8, hipMemcpyDeviceToHost, w->stream));
+    }
+    return PVW_OK;
+  });
 }
 int32_t pvw_get_crs(pvw_ctx* c, uint64_t* a_out, uint32_t repr) {
   if (!c || !a_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
@@ -1226,7 +1304,7 @@ int32_t pvw_load_pk(pvw_ctx* c, uint32_t lo, uint32_t hi, const uint64_t* b, uin
   PVW_TRY(check_repr(repr));
   PVW_TRY(check_party_range(c, lo, hi));
   PVW_TRY(ensure_device(c));
-  c->xm_valid = false; c->pkB_valid = false; c->pk_wide = false;
+  matrix_changed(c, false);
   PVW_TRY(ensure_matrix(c, &c->dB, c->rowsB()));
   PVW_TRY(load_rows_host(c, c->dB, c->party_lo, c->party_hi, lo, hi, b, repr));
   if (hi > c->num_keys) c->num_keys = hi;                                          // public_key.rs:245-247
@@ -1237,17 +1315,16 @@ int32_t pvw_load_pk_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const uint64_t*
   PVW_TRY(check_repr(repr));
   PVW_TRY(check_party_range(c, lo, hi));
   PVW_TRY(ensure_device(c));
-  c->xm_valid = false; c->pkB_valid = false; c->pk_wide = false;
+  matrix_changed(c, false);
   PVW_TRY(ensure_matrix(c, &c->dB, c->rowsB()));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  PVW_TRY(load_rows_device(c, c->dB, c->party_lo, c->party_hi, lo, hi, d_b, repr, s));
+  PVW_TRY(load_rows_device(c, c->dB, c->party_lo, c->party_hi, lo, hi, d_b, repr, call_stream(c, stream)));
   if (hi > c->num_keys) c->num_keys = hi;
   return PVW_OK;
 }
 int32_t pvw_pk_fill_uniform(pvw_ctx* c, const uint8_t seed[32]) {
   if (!c || !seed) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   PVW_TRY(ensure_device(c));
-  c->xm_valid = false; c->pkB_valid = false; c->pk_wide = false;
+  matrix_changed(c, false);
   PVW_TRY(ensure_matrix(c, &c->dB, c->rowsB()));
   {
     ProfScope ps(c, "fill_uniform", c->stream);
@@ -1289,6 +1366,21 @@ static int32_t cbd_job(float variance, SampleJob& j) {
   return PVW_OK;
 }
 
+// one sampling launch into scratch, copied to `out` (secret: the staged values are key material)
+static int32_t sample_host(pvw_ctx* c, const char* name, size_t bytes, void* out, bool secret,
+                           const std::function<hipError_t(i64*, hipStream_t)>& launch) {
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(ws_scratch(w, bytes));
+    if (secret) ws_mark_secret(w, w->scratch, bytes);
+    {
+      ProfScope ps(c, name, w->stream);
+      PVW_HIP(launch((i64*)w->scratch, w->stream));
+    }
+    PVW_HIP(hipMemcpyAsync(out, w->scratch, bytes, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
+}
+
 int32_t pvw_sample_cbd(pvw_ctx* c, const uint8_t seed[32], uint32_t domain, uint32_t index0, size_t count,
                        float variance, int64_t* out) {
   if (!c || !seed || (!out && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
@@ -1297,23 +1389,9 @@ int32_t pvw_sample_cbd(pvw_ctx* c, const uint8_t seed[32], uint32_t domain, uint
   if (count == 0) return PVW_OK;
   PVW_TRY(ensure_device(c));
   j.domain = domain; j.index0 = index0; j.count = (u32)count; j.out_poly0 = 0;
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  int32_t rc = ws_scratch(w, count * c->l * 8);
-  if (rc == PVW_OK) {
-    ProfScope ps(c, "sample", w->stream);
-    if (launch_sample((i64*)w->scratch, make_key(seed), c->l, j, z, z, w->stream) != hipSuccess)
-      rc = fail(PVW_ERR_INTERNAL, "sample launch failed");
-  }
-  if (rc == PVW_OK && hipMemcpyAsync(out, w->scratch, count * c->l * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess)
-    rc = fail(PVW_ERR_INTERNAL, "D2H failed");
-  if (rc == PVW_OK && domain == PVW_DOM_SK) {            // SecretKey::random: the staged coefficients are key material
-    ws_mark_secret(w, w->scratch, count * c->l * 8);
-    if (ws_wipe_secrets(w, w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "wipe failed");
-  }
-  if (hipStreamSynchronize(w->stream) != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, "D2H failed");
-  ws_release(c, w);
-  return rc;
+  // SecretKey::random: the staged coefficients are key material
+  return sample_host(c, "sample", count * c->l * 8, out, domain == PVW_DOM_SK,
+                     [&](i64* d, hipStream_t s) { return launch_sample(d, make_key(seed), c->l, j, z, z, s); });
 }
 
 int32_t pvw_sample_uniform(pvw_ctx* c, const uint8_t seed[32], uint32_t domain, uint32_t index0, size_t count,
@@ -1324,19 +1402,8 @@ int32_t pvw_sample_uniform(pvw_ctx* c, const uint8_t seed[32], uint32_t domain, 
   PVW_TRY(ensure_device(c));
   SampleJob j{}, z{};
   j.kind = SAMPLE_UNIFORM; j.domain = domain; j.index0 = index0; j.count = (u32)count; j.bound = bound;
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  int32_t rc = ws_scratch(w, count * c->l * 8);
-  if (rc == PVW_OK) {
-    ProfScope ps(c, "sample", w->stream);
-    if (launch_sample((i64*)w->scratch, make_key(seed), c->l, j, z, z, w->stream) != hipSuccess)
-      rc = fail(PVW_ERR_INTERNAL, "sample launch failed");
-  }
-  if (rc == PVW_OK && (hipMemcpyAsync(out, w->scratch, count * c->l * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
-                       hipStreamSynchronize(w->stream) != hipSuccess))
-    rc = fail(PVW_ERR_INTERNAL, "D2H failed");
-  ws_release(c, w);
-  return rc;
+  return sample_host(c, "sample", count * c->l * 8, out, false,
+                     [&](i64* d, hipStream_t s) { return launch_sample(d, make_key(seed), c->l, j, z, z, s); });
 }
 
 int32_t pvw_sample_gaussian(pvw_ctx* c, const uint8_t seed[32], uint32_t index0, size_t count, uint64_t bound,
@@ -1345,19 +1412,8 @@ int32_t pvw_sample_gaussian(pvw_ctx* c, const uint8_t seed[32], uint32_t index0,
   if (bound >= (1ull << 62)) return fail(PVW_ERR_SAMPLING, "bound must be below 2^62");
   if (count == 0) return PVW_OK;
   PVW_TRY(ensure_device(c));
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  int32_t rc = ws_scratch(w, count * 8);
-  if (rc == PVW_OK) {
-    ProfScope ps(c, "gaussian", w->stream);
-    if (launch_gaussian((i64*)w->scratch, make_key(seed), index0, (u32)count, bound, w->stream) != hipSuccess)
-      rc = fail(PVW_ERR_INTERNAL, "gaussian launch failed");
-  }
-  if (rc == PVW_OK && (hipMemcpyAsync(out, w->scratch, count * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
-                       hipStreamSynchronize(w->stream) != hipSuccess))
-    rc = fail(PVW_ERR_INTERNAL, "D2H failed");
-  ws_release(c, w);
-  return rc;
+  return sample_host(c, "gaussian", count * 8, out, false,
+                     [&](i64* d, hipStream_t s) { return launch_gaussian(d, make_key(seed), index0, (u32)count, bound, s); });
 }
 
 int32_t pvw_sample_secret_keys(const pvw_ctx* cc, const uint8_t seed[32], uint32_t party_lo, uint32_t count,
@@ -1369,72 +1425,44 @@ int32_t pvw_sample_secret_keys(const pvw_ctx* cc, const uint8_t seed[32], uint32
 }
 
 // ------------------------------------------------------------------------ ring primitives on host buffers
-int32_t pvw_ntt_forward(pvw_ctx* c, uint64_t* polys, size_t count) {
+static int32_t ntt_host(pvw_ctx* c, uint64_t* polys, size_t count, bool inverse) {
   if (!c || (!polys && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   if (count == 0) return PVW_OK;
   PVW_TRY(ensure_device(c));
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
   const size_t bytes = count * c->poly() * 8;
-  int32_t rc = ws_scratch(w, bytes);
-  if (rc == PVW_OK) {
-    if (hipMemcpyAsync(w->scratch, polys, bytes, hipMemcpyHostToDevice, w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "H2D failed");
-    if (rc == PVW_OK) {
-      ProfScope ps(c, "ntt", w->stream);
-      if (launch_ntt((u64*)w->scratch, count, false, c->dt, c->L, c->l, w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "ntt launch failed");
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(ws_scratch(w, bytes));
+    PVW_HIP(hipMemcpyAsync(w->scratch, polys, bytes, hipMemcpyHostToDevice, w->stream));
+    {
+      ProfScope ps(c, inverse ? "intt" : "ntt", w->stream);
+      PVW_HIP(launch_ntt((u64*)w->scratch, count, inverse, c->dt, c->L, c->l, w->stream));
     }
-    if (rc == PVW_OK && (hipMemcpyAsync(polys, w->scratch, bytes, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
-                         hipStreamSynchronize(w->stream) != hipSuccess)) rc = fail(PVW_ERR_INTERNAL, "D2H failed");
-  }
-  ws_release(c, w);
-  return rc;
+    PVW_HIP(hipMemcpyAsync(polys, w->scratch, bytes, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
 }
-int32_t pvw_ntt_inverse(pvw_ctx* c, uint64_t* polys, size_t count) {
-  if (!c || (!polys && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  if (count == 0) return PVW_OK;
-  PVW_TRY(ensure_device(c));
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  const size_t bytes = count * c->poly() * 8;
-  int32_t rc = ws_scratch(w, bytes);
-  if (rc == PVW_OK) {
-    if (hipMemcpyAsync(w->scratch, polys, bytes, hipMemcpyHostToDevice, w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "H2D failed");
-    if (rc == PVW_OK) {
-      ProfScope ps(c, "intt", w->stream);
-      if (launch_ntt((u64*)w->scratch, count, true, c->dt, c->L, c->l, w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "intt launch failed");
-    }
-    if (rc == PVW_OK && (hipMemcpyAsync(polys, w->scratch, bytes, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
-                         hipStreamSynchronize(w->stream) != hipSuccess)) rc = fail(PVW_ERR_INTERNAL, "D2H failed");
-  }
-  ws_release(c, w);
-  return rc;
-}
+int32_t pvw_ntt_forward(pvw_ctx* c, uint64_t* polys, size_t count) { return ntt_host(c, polys, count, false); }
+int32_t pvw_ntt_inverse(pvw_ctx* c, uint64_t* polys, size_t count) { return ntt_host(c, polys, count, true); }
 
 static int32_t small_to_poly_impl(pvw_ctx* c, const int64_t* coeffs, const uint64_t* scalar, size_t count,
                                   uint64_t* polys, uint32_t repr) {
   PVW_TRY(check_repr(repr));
   if (count == 0) return PVW_OK;
   PVW_TRY(ensure_device(c));
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  const size_t inb = count * c->l * 8, outb = count * c->poly() * 8, scb = scalar ? count * 8 : 0;
-  const size_t off_out = (inb + 255) & ~(size_t)255, off_sc = off_out + ((outb + 255) & ~(size_t)255);
-  int32_t rc = ws_scratch(w, off_sc + scb + 256);
-  if (rc == PVW_OK) {
-    char* base = (char*)w->scratch;
-    if (hipMemcpyAsync(base, coeffs, inb, hipMemcpyHostToDevice, w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "H2D failed");
-    if (rc == PVW_OK && scalar && hipMemcpyAsync(base + off_sc, scalar, scb, hipMemcpyHostToDevice, w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "H2D failed");
-    if (rc == PVW_OK) {
+  Scratch sc;
+  const size_t r_in = sc.add(count * c->l * 8), r_out = sc.add(count * c->poly() * 8), r_sc = sc.add(scalar ? count * 8 : 0);
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    PVW_HIP(hipMemcpyAsync(sc.at<i64>(r_in), coeffs, count * c->l * 8, hipMemcpyHostToDevice, w->stream));
+    if (scalar) PVW_HIP(hipMemcpyAsync(sc.at(r_sc), scalar, count * 8, hipMemcpyHostToDevice, w->stream));
+    {
       ProfScope ps(c, "prep", w->stream);
-      if (launch_prep((const i64*)base, scalar ? (const u64*)(base + off_sc) : nullptr, (u64*)(base + off_out),
-                      c->poly(), c->l, (u32)count, repr == PVW_REPR_NTT, c->dt, c->L, c->l, w->stream) != hipSuccess)
-        rc = fail(PVW_ERR_INTERNAL, "prep launch failed");
+      PVW_HIP(launch_prep(sc.at<i64>(r_in), scalar ? sc.at(r_sc) : nullptr, sc.at(r_out), c->poly(), c->l, (u32)count,
+                          repr == PVW_REPR_NTT, c->dt, c->L, c->l, w->stream));
     }
-    if (rc == PVW_OK && (hipMemcpyAsync(polys, base + off_out, outb, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
-                         hipStreamSynchronize(w->stream) != hipSuccess)) rc = fail(PVW_ERR_INTERNAL, "D2H failed");
-  }
-  ws_release(c, w);
-  return rc;
+    PVW_HIP(hipMemcpyAsync(polys, sc.at(r_out), count * c->poly() * 8, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
 }
 int32_t pvw_small_to_poly(pvw_ctx* c, const int64_t* coeffs, size_t count, uint64_t* polys, uint32_t repr) {
   if (!c || ((!coeffs || !polys) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
@@ -1608,10 +1636,47 @@ int32_t pvw_encrypt_device(pvw_ctx* c, const uint64_t* d_scalars, size_t num_sca
   if (!c || !d_scalars || (!d_c1 && c->rowsA()) || (!d_c2 && c->rowsB())) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   PVW_TRY(encrypt_checks(c, num_scalars, rnd, out_repr));
   PVW_TRY(ensure_device(c));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t s;
   Workspace* w;
-  PVW_TRY(ws_for_stream(c, s, &w));
+  PVW_TRY(device_ws(c, stream, &s, &w));
   return encrypt_enqueue(c, w, d_scalars, rnd, d_c1, d_c2, out_repr, s);
+}
+
+// host buffers (pvw_encrypt, pvw_encrypt_rs): the scalars, and explicit randomness as global arrays, staged on the device
+static int32_t encrypt_host(pvw_ctx* c, const uint64_t* scalars, const pvw_randomness_t* rnd, RndState* rs, uint64_t* c1_out,
+                            uint64_t* c2_out, uint32_t out_repr) {
+  const size_t l = c->l, k = c->k, P = c->poly();
+  // Output buffers the device can write (pvw_host_alloc, or memory the caller pinned / registered): the MAC stores c1 / c2
+  // straight into them, 64 bytes per (row, limb) as its workgroups finish -- the 4.7 MB of config 3 cross PCIe under the
+  // kernel instead of after it.  Pageable buffers take the copy.
+  u64 *dir1 = nullptr, *dir2 = nullptr;
+  if (out_repr == PVW_REPR_NTT) {
+    dir1 = (u64*)device_alias(c1_out, k * P * 8);
+    dir2 = (u64*)device_alias(c2_out, (size_t)c->n * P * 8);
+    if (!dir1 || !dir2) dir1 = dir2 = nullptr;
+  }
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(ws_host_buffers(c, w));
+    pvw_randomness_t dr = *rnd;
+    if (rnd->mode == PVW_RND_EXPLICIT) {
+      PVW_TRY(ws_scratch(w, (2 * k + c->n) * l * 8));
+      i64* base = (i64*)w->scratch;
+      PVW_HIP(hipMemcpyAsync(base, rnd->r, k * l * 8, hipMemcpyHostToDevice, w->stream));
+      PVW_HIP(hipMemcpyAsync(base + k * l, rnd->e1, k * l * 8, hipMemcpyHostToDevice, w->stream));
+      PVW_HIP(hipMemcpyAsync(base + 2 * k * l, rnd->e2, (size_t)c->n * l * 8, hipMemcpyHostToDevice, w->stream));
+      dr.r = base;
+      dr.e1 = base + k * l;
+      dr.e2 = base + 2 * k * l;
+    }
+    PVW_HIP(hipMemcpyAsync(w->scalars, scalars, (size_t)c->n * 8, hipMemcpyHostToDevice, w->stream));
+    PVW_TRY(encrypt_enqueue(c, w, w->scalars, &dr, w->c1, w->c2, out_repr, w->stream, dir1 ? dir1 + (size_t)c->c1_lo * P : nullptr,
+                            dir2 ? dir2 + (size_t)c->party_lo * P : nullptr, rs));
+    if (!dir1) {
+      PVW_HIP(hipMemcpyAsync(c1_out + (size_t)c->c1_lo * P, w->c1, (size_t)c->rowsA() * P * 8, hipMemcpyDeviceToHost, w->stream));
+      PVW_HIP(hipMemcpyAsync(c2_out + (size_t)c->party_lo * P, w->c2, (size_t)c->rowsB() * P * 8, hipMemcpyDeviceToHost, w->stream));
+    }
+    return PVW_OK;
+  });
 }
 
 int32_t pvw_encrypt(pvw_ctx* c, const uint64_t* scalars, size_t num_scalars, const pvw_randomness_t* rnd,
@@ -1619,46 +1684,7 @@ int32_t pvw_encrypt(pvw_ctx* c, const uint64_t* scalars, size_t num_scalars, con
   if (!c || !scalars || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   PVW_TRY(encrypt_checks(c, num_scalars, rnd, out_repr));
   PVW_TRY(ensure_device(c));
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  int32_t rc = ws_host_buffers(c, w);
-  const size_t l = c->l, k = c->k, P = c->poly();
-  pvw_randomness_t dr = *rnd;
-  if (rc == PVW_OK && rnd->mode == PVW_RND_EXPLICIT) {
-    // upload the explicit small polynomials as global arrays
-    const size_t words = (2 * k + c->n) * l;
-    rc = ws_scratch(w, words * 8);
-    if (rc == PVW_OK) {
-      i64* base = (i64*)w->scratch;
-      if (hipMemcpyAsync(base, rnd->r, k * l * 8, hipMemcpyHostToDevice, w->stream) != hipSuccess ||
-          hipMemcpyAsync(base + k * l, rnd->e1, k * l * 8, hipMemcpyHostToDevice, w->stream) != hipSuccess ||
-          hipMemcpyAsync(base + 2 * k * l, rnd->e2, (size_t)c->n * l * 8, hipMemcpyHostToDevice, w->stream) != hipSuccess)
-        rc = fail(PVW_ERR_INTERNAL, "H2D failed");
-      dr.r = base;
-      dr.e1 = base + k * l;
-      dr.e2 = base + 2 * k * l;
-    }
-  }
-  if (rc == PVW_OK && hipMemcpyAsync(w->scalars, scalars, (size_t)c->n * 8, hipMemcpyHostToDevice, w->stream) != hipSuccess)
-    rc = fail(PVW_ERR_INTERNAL, "H2D failed");
-  // Output buffers the device can write (pvw_host_alloc, or memory the caller pinned / registered): the MAC stores c1 / c2
-  // straight into them, 64 bytes per (row, limb) as its workgroups finish -- the 4.7 MB of config 3 cross PCIe under the
-  // kernel instead of after it.  Pageable buffers take the copy.
-  u64 *dir1 = nullptr, *dir2 = nullptr;
-  if (rc == PVW_OK && out_repr == PVW_REPR_NTT) {
-    dir1 = (u64*)device_alias(c1_out, (size_t)c->k * P * 8);
-    dir2 = (u64*)device_alias(c2_out, (size_t)c->n * P * 8);
-    if (!dir1 || !dir2) dir1 = dir2 = nullptr;
-  }
-  if (rc == PVW_OK) rc = encrypt_enqueue(c, w, w->scalars, &dr, w->c1, w->c2, out_repr, w->stream,
-                                         dir1 ? dir1 + (size_t)c->c1_lo * P : nullptr, dir2 ? dir2 + (size_t)c->party_lo * P : nullptr);
-  if (rc == PVW_OK && !dir1 &&
-      (hipMemcpyAsync(c1_out + (size_t)c->c1_lo * P, w->c1, (size_t)c->rowsA() * P * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
-       hipMemcpyAsync(c2_out + (size_t)c->party_lo * P, w->c2, (size_t)c->rowsB() * P * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess))
-    rc = fail(PVW_ERR_INTERNAL, "D2H failed");
-  if (hipStreamSynchronize(w->stream) != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
-  ws_release(c, w);
-  return rc;
+  return encrypt_host(c, scalars, rnd, nullptr, c1_out, c2_out, out_repr);
 }
 
 // ------------------------------------------------------------------------ multi-dealer encrypt
@@ -1817,10 +1843,9 @@ int32_t pvw_encrypt_multi_device(pvw_ctx* c, const uint64_t* d_scalars, size_t n
   if (!c || !d_scalars || !seeds || (!d_c1 && c->rowsA()) || (!d_c2 && c->rowsB())) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   PVW_TRY(encrypt_multi_checks(c, num_dealers, scalars_per_dealer, out_repr));
   PVW_TRY(ensure_device(c));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  PVW_TRY(multi_capture_check(c, s, num_dealers));
+  hipStream_t s;
   Workspace* w;
-  PVW_TRY(ws_for_stream(c, s, &w));
+  PVW_TRY(device_ws(c, stream, &s, &w, num_dealers));
   return encrypt_multi_enqueue(c, w, d_scalars, seeds, num_dealers, d_c1, d_c2, out_repr, s);
 }
 
@@ -1837,35 +1862,28 @@ int32_t pvw_encrypt_multi(pvw_ctx* c, const uint64_t* scalars, size_t num_dealer
 static int32_t encrypt_multi_host(pvw_ctx* c, const uint64_t* scalars, size_t num_dealers, const uint8_t* seeds, RndState* rs,
                                   uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
   const size_t P = c->poly(), rA = c->rowsA(), rB = c->rowsB(), n = c->n;
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
   // dealers per pass: bounded staging (<= ~512 MiB of ciphertext)
   size_t per = ((size_t)512 << 20) / ((rA + rB) * P * 8 + n * 8);
   if (per < 4) per = 4;
   per &= ~(size_t)3;
   if (per > num_dealers) per = num_dealers;
-  const size_t b_sc = (per * n * 8 + 255) & ~(size_t)255;
-  const size_t b_c1 = (per * rA * P * 8 + 255) & ~(size_t)255;
-  const size_t b_c2 = (per * rB * P * 8 + 255) & ~(size_t)255;
-  int32_t rc = ws_scratch(w, b_sc + b_c1 + b_c2);
-  for (size_t d0 = 0; rc == PVW_OK && d0 < num_dealers; d0 += per) {
-    const size_t cnt = (num_dealers - d0) < per ? (num_dealers - d0) : per;
-    char* base = (char*)w->scratch;
-    u64* d_sc = (u64*)base;
-    u64* d_c1 = (u64*)(base + b_sc);
-    u64* d_c2 = (u64*)(base + b_sc + b_c1);
-    if (hipMemcpyAsync(d_sc, scalars + d0 * n, cnt * n * 8, hipMemcpyHostToDevice, w->stream) != hipSuccess) { rc = fail(PVW_ERR_INTERNAL, "H2D failed"); break; }
-    rc = encrypt_multi_enqueue(c, w, d_sc, seeds ? seeds + d0 * 32 : nullptr, cnt, d_c1, d_c2, out_repr, w->stream, rs);
-    for (size_t d = 0; rc == PVW_OK && d < cnt; ++d) {
-      // a sharded context writes its rows at their global positions inside each dealer's block
-      if (hipMemcpyAsync(c1_out + ((d0 + d) * c->k + c->c1_lo) * P, d_c1 + d * rA * P, rA * P * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
-          hipMemcpyAsync(c2_out + ((d0 + d) * n + c->party_lo) * P, d_c2 + d * rB * P, rB * P * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess)
-        rc = fail(PVW_ERR_INTERNAL, "D2H failed");
+  Scratch sc;
+  const size_t r_sc = sc.add(per * n * 8), r_c1 = sc.add(per * rA * P * 8), r_c2 = sc.add(per * rB * P * 8);
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    u64 *d_sc = sc.at(r_sc), *d_c1 = sc.at(r_c1), *d_c2 = sc.at(r_c2);
+    for (size_t d0 = 0; d0 < num_dealers; d0 += per) {
+      const size_t cnt = (num_dealers - d0) < per ? (num_dealers - d0) : per;
+      PVW_HIP(hipMemcpyAsync(d_sc, scalars + d0 * n, cnt * n * 8, hipMemcpyHostToDevice, w->stream));
+      PVW_TRY(encrypt_multi_enqueue(c, w, d_sc, seeds ? seeds + d0 * 32 : nullptr, cnt, d_c1, d_c2, out_repr, w->stream, rs));
+      for (size_t d = 0; d < cnt; ++d) {
+        // a sharded context writes its rows at their global positions inside each dealer's block
+        PVW_HIP(hipMemcpyAsync(c1_out + ((d0 + d) * c->k + c->c1_lo) * P, d_c1 + d * rA * P, rA * P * 8, hipMemcpyDeviceToHost, w->stream));
+        PVW_HIP(hipMemcpyAsync(c2_out + ((d0 + d) * n + c->party_lo) * P, d_c2 + d * rB * P, rB * P * 8, hipMemcpyDeviceToHost, w->stream));
+      }
     }
-    if (rc == PVW_OK && hipStreamSynchronize(w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
-  }
-  ws_release(c, w);
-  return rc;
+    return PVW_OK;
+  });
 }
 
 // ------------------------------------------------------------------------ device randomness state
@@ -1979,9 +1997,9 @@ int32_t pvw_encrypt_rs_device(pvw_ctx* c, const uint64_t* d_scalars, size_t num_
   PVW_TRY(encrypt_checks(c, num_scalars, &rnd, out_repr));
   PVW_TRY(ensure_device(c));
   PVW_TRY(rnd_state_checks(c, st));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t s;
   Workspace* w;
-  PVW_TRY(ws_for_stream(c, s, &w));
+  PVW_TRY(device_ws(c, stream, &s, &w));
   return encrypt_enqueue(c, w, d_scalars, &rnd, d_c1, d_c2, out_repr, s, nullptr, nullptr, st->dev);
 }
 
@@ -1994,20 +2012,7 @@ int32_t pvw_encrypt_rs(pvw_ctx* c, const uint64_t* scalars, size_t num_scalars, 
   PVW_TRY(encrypt_checks(c, num_scalars, &rnd, out_repr));
   PVW_TRY(ensure_device(c));
   PVW_TRY(rnd_state_checks(c, st));
-  const size_t P = c->poly();
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  int32_t rc = ws_host_buffers(c, w);
-  if (rc == PVW_OK && hipMemcpyAsync(w->scalars, scalars, (size_t)c->n * 8, hipMemcpyHostToDevice, w->stream) != hipSuccess)
-    rc = fail(PVW_ERR_INTERNAL, "H2D failed");
-  if (rc == PVW_OK) rc = encrypt_enqueue(c, w, w->scalars, &rnd, w->c1, w->c2, out_repr, w->stream, nullptr, nullptr, st->dev);
-  if (rc == PVW_OK &&
-      (hipMemcpyAsync(c1_out + (size_t)c->c1_lo * P, w->c1, (size_t)c->rowsA() * P * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
-       hipMemcpyAsync(c2_out + (size_t)c->party_lo * P, w->c2, (size_t)c->rowsB() * P * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess))
-    rc = fail(PVW_ERR_INTERNAL, "D2H failed");
-  if (hipStreamSynchronize(w->stream) != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
-  ws_release(c, w);
-  return rc;
+  return encrypt_host(c, scalars, &rnd, st->dev, c1_out, c2_out, out_repr);
 }
 
 int32_t pvw_encrypt_multi_rs_device(pvw_ctx* c, const uint64_t* d_scalars, size_t num_dealers, size_t scalars_per_dealer,
@@ -2017,10 +2022,9 @@ int32_t pvw_encrypt_multi_rs_device(pvw_ctx* c, const uint64_t* d_scalars, size_
   PVW_TRY(encrypt_multi_checks(c, num_dealers, scalars_per_dealer, out_repr));
   PVW_TRY(ensure_device(c));
   PVW_TRY(rnd_state_checks(c, st));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  PVW_TRY(multi_capture_check(c, s, num_dealers));
+  hipStream_t s;
   Workspace* w;
-  PVW_TRY(ws_for_stream(c, s, &w));
+  PVW_TRY(device_ws(c, stream, &s, &w, num_dealers));
   return encrypt_multi_enqueue(c, w, d_scalars, nullptr, num_dealers, d_c1, d_c2, out_repr, s, st->dev);
 }
 
@@ -2155,65 +2159,49 @@ int32_t pvw_decode_checked_host(const pvw_ctx* c, const uint64_t* noisy, size_t 
 }
 
 #if PVW_TUNING
+// seconds per pass of `probe` (one warm-up pass first) over the resident public key section
+static int32_t time_read_probe(pvw_ctx* c, uint32_t reps, double* seconds_per_pass, uint64_t* bytes_per_pass,
+                               const std::function<hipError_t(size_t tiles, u64* sink, hipStream_t s)>& probe) {
+  PVW_TRY(ensure_device(c));
+  if (!c->dB || c->rowsB() == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no public key section resident");
+  const size_t tiles = c->tiled_words(c->rowsB()) / 128;
+  hipEvent_t a = nullptr, b = nullptr;
+  const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(ws_scratch(w, ((tiles + 63) / 64 + 1) * 8));
+    PVW_HIP(hipEventCreate(&a));
+    PVW_HIP(hipEventCreate(&b));
+    PVW_HIP(probe(tiles, (u64*)w->scratch, w->stream));   // warm-up
+    PVW_HIP(hipEventRecord(a, w->stream));
+    for (uint32_t i = 0; i < reps; ++i) PVW_HIP(probe(tiles, (u64*)w->scratch, w->stream));
+    PVW_HIP(hipEventRecord(b, w->stream));
+    PVW_HIP(hipEventSynchronize(b));
+    float ms = 0;
+    PVW_HIP(hipEventElapsedTime(&ms, a, b));
+    *seconds_per_pass = (double)ms * 1e-3 / reps;
+    *bytes_per_pass = (uint64_t)tiles * 1024;
+    return PVW_OK;
+  });
+  if (a) hipEventDestroy(a);
+  if (b) hipEventDestroy(b);
+  return rc;
+}
 // MEASUREMENT AID (tuning build only, include/pvw_hip_tuning.h): seconds per pass of a read-only kernel with mac_rows' access pattern over the resident public
 // key section (B-hat, tiled): what the memory system delivers to this pattern, next to what mac_rows achieves
 int32_t pvw_selftest_read_bandwidth(pvw_ctx* c, uint32_t reps, double* seconds_per_pass, uint64_t* bytes_per_pass) {
   if (!c || !seconds_per_pass || !bytes_per_pass || reps == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(ensure_device(c));
-  if (!c->dB || c->rowsB() == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no public key section resident");
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  const size_t tiles = c->tiled_words(c->rowsB()) / 128;
   const u32 tpw = c->k >= 64 ? (c->k / 4 / 16) * 16 : 16;           // a workgroup covers k tiles, as in mac_rows
-  int32_t rc = ws_scratch(w, ((tiles + 63) / 64 + 1) * 8);
-  hipEvent_t a = nullptr, b = nullptr;
-  if (rc == PVW_OK && (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess)) rc = fail(PVW_ERR_INTERNAL, "event");
-  if (rc == PVW_OK) {
-    bool ok = launch_read_probe(c->dB, tiles, tpw, (u64*)w->scratch, w->stream) == hipSuccess;   // warm-up
-    ok = ok && hipEventRecord(a, w->stream) == hipSuccess;
-    for (uint32_t i = 0; ok && i < reps; ++i) ok = launch_read_probe(c->dB, tiles, tpw, (u64*)w->scratch, w->stream) == hipSuccess;
-    ok = ok && hipEventRecord(b, w->stream) == hipSuccess && hipEventSynchronize(b) == hipSuccess;
-    float ms = 0;
-    ok = ok && hipEventElapsedTime(&ms, a, b) == hipSuccess;
-    if (!ok) rc = fail(PVW_ERR_INTERNAL, "read probe failed");
-    *seconds_per_pass = (double)ms * 1e-3 / reps;
-    *bytes_per_pass = (uint64_t)tiles * 1024;
-  }
-  if (a) hipEventDestroy(a);
-  if (b) hipEventDestroy(b);
-  ws_release(c, w);
-  return rc;
+  return time_read_probe(c, reps, seconds_per_pass, bytes_per_pass,
+                         [&](size_t tiles, u64* sink, hipStream_t s) { return launch_read_probe(c->dB, tiles, tpw, sink, s); });
 }
 // MEASUREMENT AID: the read probe with U tiles (2U when dbuf) in flight per wave and lds_bytes of dead LDS per
 // workgroup (caps the workgroups resident per CU): bandwidth against bytes in flight
 int32_t pvw_tuning_read_probe(pvw_ctx* c, uint32_t reps, uint32_t u, uint32_t dbuf, uint32_t lds_bytes, double* seconds_per_pass,
                               uint64_t* bytes_per_pass) {
   if (!c || !seconds_per_pass || !bytes_per_pass || reps == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(ensure_device(c));
-  if (!c->dB || c->rowsB() == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no public key section resident");
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  const size_t tiles = c->tiled_words(c->rowsB()) / 128;
   const u32 tpw = c->k >= 128 ? (c->k / 4 / 32) * 32 : 32;
-  int32_t rc = ws_scratch(w, ((tiles + 63) / 64 + 1) * 8);
-  hipEvent_t a = nullptr, b = nullptr;
-  if (rc == PVW_OK && (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess)) rc = fail(PVW_ERR_INTERNAL, "event");
-  if (rc == PVW_OK) {
-    bool ok = launch_read_probe2(c->dB, tiles, tpw, (u64*)w->scratch, u, (dbuf & 1) != 0, lds_bytes, w->stream, (dbuf >> 1) & 1) == hipSuccess;
-    ok = ok && hipEventRecord(a, w->stream) == hipSuccess;
-    for (uint32_t i = 0; ok && i < reps; ++i)
-      ok = launch_read_probe2(c->dB, tiles, tpw, (u64*)w->scratch, u, (dbuf & 1) != 0, lds_bytes, w->stream, (dbuf >> 1) & 1) == hipSuccess;
-    ok = ok && hipEventRecord(b, w->stream) == hipSuccess && hipEventSynchronize(b) == hipSuccess;
-    float ms = 0;
-    ok = ok && hipEventElapsedTime(&ms, a, b) == hipSuccess;
-    if (!ok) rc = fail(PVW_ERR_INTERNAL, "read probe failed");
-    *seconds_per_pass = (double)ms * 1e-3 / reps;
-    *bytes_per_pass = (uint64_t)tiles * 1024;
-  }
-  if (a) hipEventDestroy(a);
-  if (b) hipEventDestroy(b);
-  ws_release(c, w);
-  return rc;
+  return time_read_probe(c, reps, seconds_per_pass, bytes_per_pass, [&](size_t tiles, u64* sink, hipStream_t s) {
+    return launch_read_probe2(c->dB, tiles, tpw, sink, u, (dbuf & 1) != 0, lds_bytes, s, (dbuf >> 1) & 1);
+  });
 }
 // MEASUREMENT AID: start / end stamps of the workgroups of the last mac_rows launch made with PVW_MAC_VARIANT=40 / 41
 int32_t pvw_tuning_read_stamps(pvw_ctx* c, uint64_t* stamps, uint32_t* hw_id, uint32_t count) {
@@ -2229,20 +2217,15 @@ int32_t pvw_tuning_read_stamps(pvw_ctx* c, uint64_t* stamps, uint32_t* hw_id, ui
 int32_t pvw_selftest_mfma_i8(pvw_ctx* c, const int8_t* a, const int8_t* b, int32_t* out) {
   if (!c || !a || !b || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   PVW_TRY(ensure_device(c));
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  int32_t rc = ws_scratch(w, 8192);
-  if (rc == PVW_OK) {
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(ws_scratch(w, 8192));
     char* base = (char*)w->scratch;
-    if (hipMemcpyAsync(base, a, 1024, hipMemcpyHostToDevice, w->stream) != hipSuccess ||
-        hipMemcpyAsync(base + 1024, b, 1024, hipMemcpyHostToDevice, w->stream) != hipSuccess ||
-        launch_mfma_probe((const signed char*)base, (const signed char*)base + 1024, (int*)(base + 2048), w->stream) != hipSuccess ||
-        hipMemcpyAsync(out, base + 2048, 4096, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
-        hipStreamSynchronize(w->stream) != hipSuccess)
-      rc = fail(PVW_ERR_INTERNAL, "mfma probe failed");
-  }
-  ws_release(c, w);
-  return rc;
+    PVW_HIP(hipMemcpyAsync(base, a, 1024, hipMemcpyHostToDevice, w->stream));
+    PVW_HIP(hipMemcpyAsync(base + 1024, b, 1024, hipMemcpyHostToDevice, w->stream));
+    PVW_HIP(launch_mfma_probe((const signed char*)base, (const signed char*)base + 1024, (int*)(base + 2048), w->stream));
+    PVW_HIP(hipMemcpyAsync(out, base + 2048, 4096, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
 }
 
 // host execution of the fixed-width decode that the GPU runs (pvw_decode.h) -- a SELF-TEST hook so
@@ -2360,77 +2343,57 @@ int32_t pvw_selftest_decode_shortcuts(const pvw_ctx* c, const uint64_t* noisy, s
   return PVW_OK;
 }
 
-// decode_scalar_pvw_rns on the device, host buffers in and out
-int32_t pvw_decode(pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out) {
-  if (!c || ((!noisy || !out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  if (count == 0) return PVW_OK;
-  PVW_TRY(ensure_device(c));
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  const size_t inb = (count * c->poly() * 8 + 255) & ~(size_t)255;
-  int32_t rc = ws_scratch(w, inb + count * 8);
-  if (rc == PVW_OK) {
-    char* base = (char*)w->scratch;
-    if (hipMemcpyAsync(base, noisy, count * c->poly() * 8, hipMemcpyHostToDevice, w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "H2D failed");
-    if (rc == PVW_OK) {
-      ProfScope ps(c, "decode", w->stream);
-      if (launch_decode((u64*)base, (u64*)(base + inb), count, c->dec_dev, w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "decode launch failed");
-    }
-    if (rc == PVW_OK && (hipMemcpyAsync(out, base + inb, count * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
-                         hipStreamSynchronize(w->stream) != hipSuccess)) rc = fail(PVW_ERR_INTERNAL, "D2H failed");
+// The decode of `cnt` noisy polynomials at nz (decryption.rs:116, :10-58), still in the NTT domain when `ntt_domain`.  The
+// decode can transform back while it stages its input (no launch for :116), at the price of 94 instead of 79 registers.
+// Taken while its workgroups (two ciphertexts each) are resident all at once anyway; beyond, and when the decode shares the
+// chip with other work (`shared`), the 79-register decode runs behind a transform launch of its own.  noise / status: the
+// checked decode's report (NULL: not asked for); wipe / wipe_bytes / wiped: as launch_decode.
+static int32_t decode_tail(pvw_ctx* c, u64* nz, size_t cnt, bool ntt_domain, bool shared, hipStream_t s, u64* out,
+                           u64* noise = nullptr, u32* status = nullptr, u64* wipe = nullptr, size_t wipe_bytes = 0,
+                           bool* wiped = nullptr) {
+  if (ntt_domain && (shared || (cnt + 1) / 2 > (size_t)2 * c->num_cus)) {
+    ProfScope pi(c, "intt", s);
+    PVW_HIP(launch_ntt(nz, cnt, true, c->dt, c->L, c->l, s));
+    ntt_domain = false;
   }
-  ws_release(c, w);
-  return rc;
-}
-
-int32_t pvw_decode_device(pvw_ctx* c, const uint64_t* d_noisy, size_t count, uint64_t* d_out, void* stream) {
-  if (!c || ((!d_noisy || !d_out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  if (count == 0) return PVW_OK;
-  PVW_TRY(ensure_device(c));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   ProfScope ps(c, "decode", s);
-  PVW_HIP(launch_decode(const_cast<u64*>(d_noisy), d_out, count, c->dec_dev, s));    // power basis in: read only
+  PVW_HIP(launch_decode(nz, out, cnt, c->dec_dev, s, ntt_domain ? &c->dt : nullptr, wipe, wipe_bytes, wiped, noise, status));
   return PVW_OK;
 }
 
-// checked decode: out as pvw_decode_device, plus noise[d] / status[d] (either may be NULL)
+// decode_scalar_pvw_rns on the device; checked: plus noise[d] / status[d] (either may be NULL)
 int32_t pvw_decode_checked_device(pvw_ctx* c, const uint64_t* d_noisy, size_t count, uint64_t* d_out, uint64_t* d_noise,
                                   uint32_t* d_status, void* stream) {
   if (!c || ((!d_noisy || !d_out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   if (count == 0) return PVW_OK;
   PVW_TRY(ensure_device(c));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  ProfScope ps(c, "decode", s);
-  PVW_HIP(launch_decode(const_cast<u64*>(d_noisy), d_out, count, c->dec_dev, s, nullptr, nullptr, 0, nullptr, d_noise, d_status));
-  return PVW_OK;
+  // power basis in: read only
+  return decode_tail(c, const_cast<u64*>(d_noisy), count, false, false, call_stream(c, stream), d_out, d_noise, d_status);
+}
+int32_t pvw_decode_device(pvw_ctx* c, const uint64_t* d_noisy, size_t count, uint64_t* d_out, void* stream) {
+  return pvw_decode_checked_device(c, d_noisy, count, d_out, nullptr, nullptr, stream);
 }
 // host buffers in and out
 int32_t pvw_decode_checked(pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out, uint64_t* noise, uint32_t* status) {
   if (!c || ((!noisy || !out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   if (count == 0) return PVW_OK;
   PVW_TRY(ensure_device(c));
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  const size_t inb = (count * c->poly() * 8 + 255) & ~(size_t)255, ob = (count * 8 + 255) & ~(size_t)255;
-  int32_t rc = ws_scratch(w, inb + 2 * ob + count * 4);
-  if (rc == PVW_OK) {
-    char* base = (char*)w->scratch;
-    u64* d_out = (u64*)(base + inb);
-    u64* d_ns = noise ? (u64*)(base + inb + ob) : nullptr;
-    u32* d_st = status ? (u32*)(base + inb + 2 * ob) : nullptr;
-    if (hipMemcpyAsync(base, noisy, count * c->poly() * 8, hipMemcpyHostToDevice, w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "H2D failed");
-    if (rc == PVW_OK) {
-      ProfScope ps(c, "decode", w->stream);
-      if (launch_decode((u64*)base, d_out, count, c->dec_dev, w->stream, nullptr, nullptr, 0, nullptr, d_ns, d_st) != hipSuccess)
-        rc = fail(PVW_ERR_INTERNAL, "decode launch failed");
-    }
-    if (rc == PVW_OK && (hipMemcpyAsync(out, d_out, count * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
-                         (noise && hipMemcpyAsync(noise, d_ns, count * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess) ||
-                         (status && hipMemcpyAsync(status, d_st, count * 4, hipMemcpyDeviceToHost, w->stream) != hipSuccess) ||
-                         hipStreamSynchronize(w->stream) != hipSuccess)) rc = fail(PVW_ERR_INTERNAL, "D2H failed");
-  }
-  ws_release(c, w);
-  return rc;
+  Scratch sc;
+  const size_t r_nz = sc.add(count * c->poly() * 8), r_out = sc.add(count * 8), r_ns = sc.add(noise ? count * 8 : 0),
+               r_st = sc.add(status ? count * 4 : 0);
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    PVW_HIP(hipMemcpyAsync(sc.at(r_nz), noisy, count * c->poly() * 8, hipMemcpyHostToDevice, w->stream));
+    PVW_TRY(decode_tail(c, sc.at(r_nz), count, false, false, w->stream, sc.at(r_out), noise ? sc.at(r_ns) : nullptr,
+                        status ? sc.at<u32>(r_st) : nullptr));
+    PVW_HIP(hipMemcpyAsync(out, sc.at(r_out), count * 8, hipMemcpyDeviceToHost, w->stream));
+    if (noise) PVW_HIP(hipMemcpyAsync(noise, sc.at(r_ns), count * 8, hipMemcpyDeviceToHost, w->stream));
+    if (status) PVW_HIP(hipMemcpyAsync(status, sc.at(r_st), count * 4, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
+}
+int32_t pvw_decode(pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out) {
+  return pvw_decode_checked(c, noisy, count, out, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------ decrypt
@@ -2463,42 +2426,70 @@ static int32_t decrypt_mac_only(pvw_ctx* c, Workspace* w, const u64* d_c1s, cons
   }
   return PVW_OK;
 }
-static int32_t decrypt_mac_intt(pvw_ctx* c, Workspace* w, const u64* d_c1s, const u64* d_c2col, size_t D, u64* d_noisy,
-                                hipStream_t s) {
-  bool ntt_domain = false;
-  PVW_TRY(decrypt_mac_only(c, w, d_c1s, d_c2col, D, d_noisy, s, &ntt_domain));
-  if (ntt_domain) {
-    ProfScope ps(c, "intt", s);
-    PVW_HIP(launch_ntt(d_noisy, D, true, c->dt, c->L, c->l, s));
-  }
-  return PVW_OK;
-}
-
-// ntt_domain == NULL: d_noisy comes back in power basis; otherwise *ntt_domain says whether the caller (the decode) still has to
-// transform it back
-static int32_t decrypt_enqueue(pvw_ctx* c, Workspace* w, const i64* d_sk, u64* d_c1s, u64* d_c2col, size_t D,
-                               uint32_t in_repr, u64* d_noisy, hipStream_t s, bool inputs_mutable, bool* ntt_domain = nullptr) {
+// decrypt_party_shares with device pointers end to end: <sk, c1> - c2, the transform back and the gadget decode of D dealer
+// ciphertexts (NTT domain, on `s`); only D x u64 are produced.  The key is d_sk, its
+// coefficients (NTT(sk) is made in w->rhat and marked secret), or key_shat, a resident key's.  Large batches are cut into
+// chunks of about 2 GiB and the decode of chunk i (integer-ALU work, a few waves per CU) runs on a helper stream under the
+// HBM-bound MAC of chunk i+1; `s` waits for the last decode before the call's work counts as complete.
+static int32_t decrypt_batch_enqueue(pvw_ctx* c, Workspace* w, hipStream_t s, const int64_t* d_sk, const u64* key_shat,
+                                     const u64* d_c1s, const u64* d_c2col, size_t D, u64* d_noisy, u64* d_out, u64* d_noise,
+                                     u32* d_status) {
   const u32 k = c->k, l = c->l, L = c->L;
-  const size_t P = c->poly();
-  {
+  const size_t P = c->poly(), shat_bytes = (size_t)k * P * 8;
+  // chunks of about 2 GiB of ciphertext (measured: at config 5 in full, 18 GB, overlapping the decode is -7 %;
+  // with 0.3 GB chunks the cross-stream events cost more than the decode they hide, +29 %): below 3 GiB in all,
+  // one pass on the caller's stream.  PVW_DECRYPT_CHUNK=<dealers> overrides.
+  const long chunk_env = PVW_ENV_INT("PVW_DECRYPT_CHUNK", 0);   // tuning build only (read per call)
+  const double total_gib = (double)D * k * P * 8 / (double)((size_t)1 << 30);
+  size_t chunk = D;
+  if (chunk_env >= 64) chunk = (size_t)chunk_env;
+  else if (total_gib >= 3.0) chunk = (D + (size_t)(total_gib / 2.0) - 1) / (size_t)(total_gib / 2.0);
+  const size_t nch = (D + chunk - 1) / chunk;
+  if (!key_shat) {
+    ws_mark_secret(w, w->rhat, shat_bytes);
     ProfScope ps(c, "prep", s);
-    // NTT(sk[j]) in the ciphertext layout [k][L][l]   (secret_key.rs:98-112, once per call)
-    PVW_HIP(launch_prep(d_sk, nullptr, w->rhat, P, l, k, true, c->dt, L, l, s));
+    PVW_HIP(launch_prep(d_sk, nullptr, w->rhat, P, l, k, true, c->dt, L, l, s));   // NTT(sk[j]) once per call (secret_key.rs:98-112)
   }
-  if (in_repr == PVW_REPR_POWER) {
-    if (!inputs_mutable) return fail(PVW_ERR_INVALID_FORMAT, "power-basis ciphertexts need a mutable device buffer");
-    ProfScope ps(c, "ntt", s);
-    PVW_HIP(launch_ntt(d_c1s, D * k, false, c->dt, L, l, s));
-    PVW_HIP(launch_ntt(d_c2col, D, false, c->dt, L, l, s));
+  const bool overlap = nch >= 2;
+  if (overlap) PVW_TRY(ws_aux(w, nch + 1));
+  // one pass on one stream: the decode is the last launch to follow the inner products, and clears NTT(sk) on its way
+  const bool decode_wipes = !overlap && !key_shat;
+  for (size_t i = 0; i < nch; ++i) {
+    const size_t d0 = i * chunk, cnt = (D - d0) < chunk ? (D - d0) : chunk;
+    u64* nz = d_noisy + d0 * P;
+    bool ntt_domain = false;
+    PVW_TRY(decrypt_mac_only(c, w, d_c1s + d0 * k * P, d_c2col + d0 * P, cnt, nz, s, &ntt_domain, !overlap, key_shat));   // decryption.rs:257-274
+    hipStream_t ds = s;
+    if (overlap) {
+      PVW_HIP(hipEventRecord(w->events[i], s));
+      PVW_HIP(hipStreamWaitEvent(w->aux, w->events[i], 0));
+      ds = w->aux;
+    }
+    bool by_decode = false;
+    PVW_TRY(decode_tail(c, nz, cnt, ntt_domain, overlap, ds, d_out + d0, d_noise ? d_noise + d0 : nullptr,
+                        d_status ? d_status + d0 : nullptr, decode_wipes ? w->rhat : nullptr, decode_wipes ? shat_bytes : 0,
+                        &by_decode));
+    if (by_decode) ws_mark_secret(w, w->rhat, shat_bytes, true);   // recorded as this call's wiped region, no memset
   }
-  if (ntt_domain) return decrypt_mac_only(c, w, d_c1s, d_c2col, D, d_noisy, s, ntt_domain);
-  return decrypt_mac_intt(c, w, d_c1s, d_c2col, D, d_noisy, s);
-}
-// NTT(sk) sits in w->rhat while a decrypt runs: cleared on the call's stream behind the last kernel that read it
-static int32_t wipe_shat(pvw_ctx* c, Workspace* w, hipStream_t s) {
-  ws_mark_secret(w, w->rhat, (size_t)c->k * c->poly() * 8);
-  PVW_HIP(ws_wipe_secrets(w, s));
+  if (overlap) {
+    PVW_HIP(hipEventRecord(w->events[nch], w->aux));
+    PVW_HIP(hipStreamWaitEvent(s, w->events[nch], 0));
+  }
   return PVW_OK;
+}
+// the device-pointer entry points: their argument checks, then the enqueue on the caller's stream
+static int32_t decrypt_batch_core(pvw_ctx* c, const int64_t* d_sk, const u64* key_shat, const uint64_t* d_c1s, const uint64_t* d_c2col,
+                                  size_t D, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, void* stream,
+                                  uint64_t* d_noise = nullptr, uint32_t* d_status = nullptr) {
+  if (!c || ((!d_c1s || !d_c2col || !d_noisy || !d_out) && D)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(check_repr(in_repr));
+  if (in_repr != PVW_REPR_NTT) return fail(PVW_ERR_INVALID_FORMAT, "device decrypt takes NTT-domain ciphertexts");
+  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");          // decryption.rs:286-290
+  PVW_TRY(ensure_device(c));
+  hipStream_t s;
+  Workspace* w;
+  PVW_TRY(device_ws(c, stream, &s, &w));
+  return device_end(w, s, decrypt_batch_enqueue(c, w, s, d_sk, key_shat, d_c1s, d_c2col, D, d_noisy, d_out, d_noise, d_status));
 }
 
 int32_t pvw_decrypt_noisy_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col,
@@ -2507,18 +2498,77 @@ int32_t pvw_decrypt_noisy_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t
   PVW_TRY(check_repr(in_repr));
   if (in_repr != PVW_REPR_NTT) return fail(PVW_ERR_INVALID_FORMAT, "device decrypt takes NTT-domain ciphertexts");
   PVW_TRY(ensure_device(c));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t s;
   Workspace* w;
-  PVW_TRY(ws_for_stream(c, s, &w));
-  int32_t rc = decrypt_enqueue(c, w, d_sk, const_cast<u64*>(d_c1s), const_cast<u64*>(d_c2col), D, in_repr, d_noisy, s, false);
-  int32_t rw = wipe_shat(c, w, s);
-  return rc != PVW_OK ? rc : rw;
+  PVW_TRY(device_ws(c, stream, &s, &w));
+  const size_t P = c->poly();
+  ws_mark_secret(w, w->rhat, (size_t)c->k * P * 8);           // NTT(sk), cleared behind the last launch that reads it
+  auto run = [&]() -> int32_t {
+    {
+      ProfScope ps(c, "prep", s);
+      PVW_HIP(launch_prep(d_sk, nullptr, w->rhat, P, c->l, c->k, true, c->dt, c->L, c->l, s));   // secret_key.rs:98-112
+    }
+    bool ntt_domain = false;
+    PVW_TRY(decrypt_mac_only(c, w, d_c1s, d_c2col, D, d_noisy, s, &ntt_domain));
+    if (ntt_domain) {
+      ProfScope ps(c, "intt", s);
+      PVW_HIP(launch_ntt(d_noisy, D, true, c->dt, c->L, c->l, s));
+    }
+    return PVW_OK;
+  };
+  return device_end(w, s, run());
 }
 
-// decrypt_party_shares with device pointers end to end: <sk, c1> - c2, INTT and gadget decode for D dealer
-// ciphertexts; only D x u64 are produced.  Large batches are cut into chunks of about 2 GiB and the
-// decode of chunk i (integer-ALU work, a few waves per CU) runs on a helper stream under the HBM-bound MAC of
-// chunk i+1; the caller's stream waits for the last decode before the call's work counts as complete.
+// host buffers: dealers in chunks of <= 1 GiB of ciphertext, staged on the device (a POWER-basis chunk transformed there) and
+// decrypted by the device path; the uploaded coefficients and NTT(sk) do not outlive the call (secret_key.rs:20-30)
+static int32_t decrypt_batch_staged(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
+                                    uint32_t in_repr, uint64_t* out_u64, uint64_t* noisy_out, uint64_t* noise, uint32_t* status) {
+  if (!c || !sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");          // decryption.rs:286-290
+  if (!c1s || !c2col || !out_u64) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(check_repr(in_repr));
+  PVW_TRY(ensure_device(c));
+  const size_t k = c->k, l = c->l, P = c->poly();
+  size_t per = ((size_t)1 << 30) / (k * P * 8);
+  if (per == 0) per = 1;
+  if (per > D) per = D;
+  Scratch sc;
+  const size_t r_sk = sc.add(k * l * 8), r_c1 = sc.add(per * k * P * 8), r_c2 = sc.add(per * P * 8), r_nz = sc.add(per * P * 8),
+               r_out = sc.add(per * 8), r_ns = sc.add(noise ? per * 8 : 0), r_st = sc.add(status ? per * 4 : 0);
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    i64* d_sk = sc.at<i64>(r_sk);
+    u64 *d_c1 = sc.at(r_c1), *d_c2 = sc.at(r_c2), *d_nz = sc.at(r_nz), *d_out = sc.at(r_out);
+    ws_mark_secret(w, d_sk, k * l * 8);
+    PVW_HIP(hipMemcpyAsync(d_sk, sk, k * l * 8, hipMemcpyHostToDevice, w->stream));
+    for (size_t d0 = 0; d0 < D; d0 += per) {
+      const size_t cnt = (D - d0) < per ? (D - d0) : per;
+      PVW_HIP(hipMemcpyAsync(d_c1, c1s + d0 * k * P, cnt * k * P * 8, hipMemcpyHostToDevice, w->stream));
+      PVW_HIP(hipMemcpyAsync(d_c2, c2col + d0 * P, cnt * P * 8, hipMemcpyHostToDevice, w->stream));
+      if (in_repr == PVW_REPR_POWER) {
+        ProfScope ps(c, "ntt", w->stream);
+        PVW_HIP(launch_ntt(d_c1, cnt * k, false, c->dt, c->L, c->l, w->stream));
+        PVW_HIP(launch_ntt(d_c2, cnt, false, c->dt, c->L, c->l, w->stream));
+      }
+      PVW_TRY(decrypt_batch_enqueue(c, w, w->stream, d_sk, nullptr, d_c1, d_c2, cnt, d_nz, d_out, noise ? sc.at(r_ns) : nullptr,
+                                    status ? sc.at<u32>(r_st) : nullptr));
+      PVW_HIP(hipMemcpyAsync(out_u64 + d0, d_out, cnt * 8, hipMemcpyDeviceToHost, w->stream));
+      if (noise) PVW_HIP(hipMemcpyAsync(noise + d0, sc.at(r_ns), cnt * 8, hipMemcpyDeviceToHost, w->stream));
+      if (status) PVW_HIP(hipMemcpyAsync(status + d0, sc.at(r_st), cnt * 4, hipMemcpyDeviceToHost, w->stream));
+      if (noisy_out) PVW_HIP(hipMemcpyAsync(noisy_out + d0 * P, d_nz, cnt * P * 8, hipMemcpyDeviceToHost, w->stream));
+    }
+    return PVW_OK;
+  });
+}
+int32_t pvw_decrypt_batch(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
+                          uint32_t in_repr, uint64_t* out_u64, uint64_t* noisy_out) {
+  return decrypt_batch_staged(c, sk, c1s, c2col, D, in_repr, out_u64, noisy_out, nullptr, nullptr);
+}
+int32_t pvw_decrypt_batch_checked(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
+                                  uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status) {
+  return decrypt_batch_staged(c, sk, c1s, c2col, D, in_repr, out_u64, nullptr, noise, status);
+}
+
 // A secret key kept on the device in the form the inner products read (NTT(sk[j]) in the ciphertext layout,
 // secret_key.rs:98-112): decrypt calls that take one skip the transform of the key and the wipe behind it.  The reference's
 // SecretKey lives as long as its owner does and is ZeroizeOnDrop (secret_key.rs:20-30); so does this: pvw_sk_free clears it.
@@ -2527,9 +2577,6 @@ struct pvw_sk {
   u64* shat;       // [k][L][l]
   size_t bytes;
 };
-static int32_t decrypt_batch_core(pvw_ctx* c, const int64_t* d_sk, const u64* key_shat, const uint64_t* d_c1s, const uint64_t* d_c2col,
-                                  size_t D, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, void* stream,
-                                  uint64_t* d_noise = nullptr, uint32_t* d_status = nullptr);
 int32_t pvw_decrypt_batch_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col,
                                  size_t D, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, void* stream) {
   if (!c || !d_sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
@@ -2594,171 +2641,6 @@ int32_t pvw_sk_free(pvw_sk* key) {
   delete key;
   return rc;
 }
-static int32_t decrypt_batch_core(pvw_ctx* c, const int64_t* d_sk, const u64* key_shat, const uint64_t* d_c1s, const uint64_t* d_c2col,
-                                  size_t D, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, void* stream,
-                                  uint64_t* d_noise, uint32_t* d_status) {
-  if (!c || ((!d_c1s || !d_c2col || !d_noisy || !d_out) && D)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(check_repr(in_repr));
-  if (in_repr != PVW_REPR_NTT) return fail(PVW_ERR_INVALID_FORMAT, "device decrypt takes NTT-domain ciphertexts");
-  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");          // decryption.rs:286-290
-  PVW_TRY(ensure_device(c));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  Workspace* w;
-  PVW_TRY(ws_for_stream(c, s, &w));
-  const u32 k = c->k, l = c->l, L = c->L;
-  const size_t P = c->poly();
-  // chunks of about 2 GiB of ciphertext (measured: at config 5 in full, 18 GB, overlapping the decode is -7 %;
-  // with 0.3 GB chunks the cross-stream events cost more than the decode they hide, +29 %): below 3 GiB in all,
-  // one pass on the caller's stream.  PVW_DECRYPT_CHUNK=<dealers> overrides.
-  const long chunk_env = PVW_ENV_INT("PVW_DECRYPT_CHUNK", 0);   // tuning build only (read per call)
-  const double total_gib = (double)D * k * P * 8 / (double)((size_t)1 << 30);
-  size_t chunk = D;
-  if (chunk_env >= 64) chunk = (size_t)chunk_env;
-  else if (total_gib >= 3.0) chunk = (D + (size_t)(total_gib / 2.0) - 1) / (size_t)(total_gib / 2.0);
-  const size_t nch = (D + chunk - 1) / chunk;
-  if (!key_shat) {
-    ProfScope ps(c, "prep", s);
-    PVW_HIP(launch_prep(d_sk, nullptr, w->rhat, P, l, k, true, c->dt, L, l, s));   // NTT(sk[j]) once per call (secret_key.rs:98-112)
-  }
-  const bool overlap = nch >= 2;
-  if (overlap) {
-    if (!w->aux) PVW_HIP(hipStreamCreateWithFlags(&w->aux, hipStreamNonBlocking));
-    while (w->events.size() < nch + 1) {
-      hipEvent_t e;
-      PVW_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      w->events.push_back(e);
-    }
-  }
-  bool shat_wiped = false;
-  auto chunks = [&]() -> int32_t {
-  for (size_t i = 0; i < nch; ++i) {
-    const size_t d0 = i * chunk, cnt = (D - d0) < chunk ? (D - d0) : chunk;
-    u64* nz = d_noisy + d0 * P;
-    bool ntt_domain = false;
-    PVW_TRY(decrypt_mac_only(c, w, d_c1s + d0 * k * P, d_c2col + d0 * P, cnt, nz, s, &ntt_domain, !overlap, key_shat));   // decryption.rs:257-274
-    hipStream_t ds = s;
-    if (overlap) {
-      PVW_HIP(hipEventRecord(w->events[i], s));
-      PVW_HIP(hipStreamWaitEvent(w->aux, w->events[i], 0));
-      ds = w->aux;
-    }
-    // The decode can transform back while it stages its input (no launch for decryption.rs:116), at the price of 94
-    // instead of 79 registers.  Taken while its workgroups (two ciphertexts each) are resident all at once anyway; beyond,
-    // and when the decode shares the chip with the next chunk's inner products, the 79-register decode runs behind a
-    // transform launch of its own (on the helper stream when there is one).
-    if (ntt_domain && (overlap || (cnt + 1) / 2 > (size_t)2 * c->num_cus)) {
-      ProfScope pi(c, "intt", ds);
-      PVW_HIP(launch_ntt(nz, cnt, true, c->dt, L, l, ds));
-      ntt_domain = false;
-    }
-    ProfScope ps(c, "decode", ds);
-    // one pass on one stream: the decode is the last launch to follow the inner products, and clears NTT(sk) on its way
-    bool by_decode = false;
-    PVW_HIP(launch_decode(nz, d_out + d0, cnt, c->dec_dev, ds, ntt_domain ? &c->dt : nullptr,                    // :116, :10-58
-                          overlap || key_shat ? nullptr : w->rhat, overlap || key_shat ? 0 : (size_t)k * P * 8, &by_decode,
-                          d_noise ? d_noise + d0 : nullptr, d_status ? d_status + d0 : nullptr));
-    if (by_decode) shat_wiped = true;
-  }
-  if (overlap) {
-    PVW_HIP(hipEventRecord(w->events[nch], w->aux));
-    PVW_HIP(hipStreamWaitEvent(s, w->events[nch], 0));
-  }
-  return PVW_OK;
-  };
-  int32_t rc = chunks();
-  if (rc != PVW_OK) {                       // nothing of a failed call stays queued behind the caller's back
-    if (w->aux) hipStreamSynchronize(w->aux);
-    hipStreamSynchronize(s);
-  }
-  int32_t rw = PVW_OK;
-  if (key_shat) return rc;                  // a resident key: nothing of it was copied anywhere
-  if (rc == PVW_OK && shat_wiped) {         // cleared by the decode launch: recorded as this call's wiped region
-    ws_mark_secret(w, w->rhat, (size_t)k * P * 8);
-    w->wiped = w->secrets;
-    w->secrets.clear();
-  } else {
-    rw = wipe_shat(c, w, s);                // every decrypt_mac launch above is on `s`
-  }
-  return rc != PVW_OK ? rc : rw;
-}
-
-static int32_t decrypt_batch_host(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
-                                  uint32_t in_repr, uint64_t* out_u64, uint64_t* noisy_out, uint64_t* noise, uint32_t* status);
-int32_t pvw_decrypt_batch(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
-                          uint32_t in_repr, uint64_t* out_u64, uint64_t* noisy_out) {
-  return decrypt_batch_host(c, sk, c1s, c2col, D, in_repr, out_u64, noisy_out, nullptr, nullptr);
-}
-int32_t pvw_decrypt_batch_checked(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
-                                  uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status) {
-  return decrypt_batch_host(c, sk, c1s, c2col, D, in_repr, out_u64, nullptr, noise, status);
-}
-static int32_t decrypt_batch_host(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
-                                  uint32_t in_repr, uint64_t* out_u64, uint64_t* noisy_out, uint64_t* noise, uint32_t* status) {
-  if (!c || !sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");          // decryption.rs:286-290
-  if (!c1s || !c2col || !out_u64) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(check_repr(in_repr));
-  PVW_TRY(ensure_device(c));
-  const size_t k = c->k, l = c->l, P = c->poly();
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  // dealers per pass: bounded staging (<= ~1 GiB of ciphertext)
-  size_t per = ((size_t)1 << 30) / (k * P * 8);
-  if (per == 0) per = 1;
-  if (per > D) per = D;
-  const size_t b_sk = (k * l * 8 + 255) & ~(size_t)255;
-  const size_t b_c1 = (per * k * P * 8 + 255) & ~(size_t)255;
-  const size_t b_c2 = (per * P * 8 + 255) & ~(size_t)255;
-  const size_t b_out = (per * 8 + 255) & ~(size_t)255;
-  const size_t b_ns = noise ? b_out : 0, b_st = status ? ((per * 4 + 255) & ~(size_t)255) : 0;
-  int32_t rc = ws_scratch(w, b_sk + b_c1 + 2 * b_c2 + b_out + b_ns + b_st);
-  if (rc == PVW_OK) {
-    char* base = (char*)w->scratch;
-    i64* d_sk = (i64*)base;
-    u64* d_c1 = (u64*)(base + b_sk);
-    u64* d_c2 = (u64*)(base + b_sk + b_c1);
-    u64* d_nz = (u64*)(base + b_sk + b_c1 + b_c2);
-    u64* d_out = (u64*)(base + b_sk + b_c1 + 2 * b_c2);
-    u64* d_ns = noise ? (u64*)(base + b_sk + b_c1 + 2 * b_c2 + b_out) : nullptr;
-    u32* d_st = status ? (u32*)(base + b_sk + b_c1 + 2 * b_c2 + b_out + b_ns) : nullptr;
-    if (hipMemcpyAsync(d_sk, sk, k * l * 8, hipMemcpyHostToDevice, w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "H2D failed");
-    for (size_t d0 = 0; rc == PVW_OK && d0 < D; d0 += per) {
-      const size_t cnt = (D - d0) < per ? (D - d0) : per;
-      if (hipMemcpyAsync(d_c1, c1s + d0 * k * P, cnt * k * P * 8, hipMemcpyHostToDevice, w->stream) != hipSuccess ||
-          hipMemcpyAsync(d_c2, c2col + d0 * P, cnt * P * 8, hipMemcpyHostToDevice, w->stream) != hipSuccess) {
-        rc = fail(PVW_ERR_INTERNAL, "H2D failed");
-        break;
-      }
-      bool ntt_domain = false;
-      rc = decrypt_enqueue(c, w, d_sk, d_c1, d_c2, cnt, in_repr, d_nz, w->stream, true, &ntt_domain);
-      if (rc == PVW_OK && ntt_domain && (cnt + 1) / 2 > (size_t)2 * c->num_cus) {      // as in pvw_decrypt_batch_device
-        ProfScope pi(c, "intt", w->stream);
-        if (launch_ntt(d_nz, cnt, true, c->dt, c->L, c->l, w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "intt launch failed");
-        ntt_domain = false;
-      }
-      if (rc == PVW_OK) {
-        ProfScope ps(c, "decode", w->stream);
-        if (launch_decode(d_nz, d_out, cnt, c->dec_dev, w->stream, ntt_domain ? &c->dt : nullptr, nullptr, 0, nullptr, d_ns, d_st) !=
-            hipSuccess)
-          rc = fail(PVW_ERR_INTERNAL, "decode launch failed");   // decryption.rs:116, :277
-      }
-      if (rc == PVW_OK && (hipMemcpyAsync(out_u64 + d0, d_out, cnt * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
-                           (noise && hipMemcpyAsync(noise + d0, d_ns, cnt * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess) ||
-                           (status && hipMemcpyAsync(status + d0, d_st, cnt * 4, hipMemcpyDeviceToHost, w->stream) != hipSuccess) ||
-                           (noisy_out && hipMemcpyAsync(noisy_out + d0 * P, d_nz, cnt * P * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess) ||
-                           hipStreamSynchronize(w->stream) != hipSuccess))
-        rc = fail(PVW_ERR_INTERNAL, "D2H failed");
-    }
-    // the uploaded coefficients and NTT(sk) do not outlive the call (secret_key.rs:20-30)
-    ws_mark_secret(w, d_sk, k * l * 8);
-    ws_mark_secret(w, w->rhat, k * P * 8);
-    if ((ws_wipe_secrets(w, w->stream) != hipSuccess || hipStreamSynchronize(w->stream) != hipSuccess) && rc == PVW_OK)
-      rc = fail(PVW_ERR_INTERNAL, "wipe failed");
-  }
-  ws_release(c, w);
-  return rc;
-}
-
 // ------------------------------------------------------------------------ decrypt for every party
 // Every party of [lo, hi) decrypts its share of each of D dealer ciphertexts in one call: the loop over
 // decrypt_party_shares (decryption.rs:281-325) that examples/pvw.rs:138-149 and tests/crypto.rs:284-287 run for all parties,
@@ -2777,7 +2659,6 @@ static int32_t decrypt_batch_host(pvw_ctx* c, const int64_t* sk, const uint64_t*
 #ifndef PVW_DECRYPT_ALL_MIN_PARTIES
 #define PVW_DECRYPT_ALL_MIN_PARTIES 22
 #endif
-static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 static int32_t decrypt_all_checks(pvw_ctx* c, u32 lo, u32 hi, const void* sk, const void* c1s, const void* c2s, size_t D,
                                   uint32_t in_repr, const void* out) {
   if (!c || !sk || !c1s || !c2s || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
@@ -2807,23 +2688,19 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
     size_t Dc = ((size_t)1 << 30) / (ctw * 8);
     if (Dc == 0) Dc = 1;
     if (Dc > D) Dc = D;
-    const size_t b_sk = host ? al256(NP * k * l * 8) : 0, b_c1 = stage ? al256(Dc * ctw * 8) : 0;
-    const size_t b_c2 = al256(Dc * P * 8), b_nz = al256(Dc * P * 8), b_out = host ? al256(Dc * 8) : 0;
-    const size_t b_ns = host && noise ? al256(Dc * 8) : 0, b_st = host && status ? al256(Dc * 4) : 0;
-    PVW_TRY(ws_scratch(w, b_sk + b_c1 + b_c2 + b_nz + b_out + b_ns + b_st));
-    char* base = (char*)w->scratch;
-    i64* d_sk = (i64*)base;
-    u64* d_c1 = (u64*)(base + b_sk);
-    u64* d_c2 = (u64*)(base + b_sk + b_c1);
-    u64* d_nz = (u64*)(base + b_sk + b_c1 + b_c2);
-    u64* d_out = (u64*)(base + b_sk + b_c1 + b_c2 + b_nz);
-    u64* d_ns = (u64*)(base + b_sk + b_c1 + b_c2 + b_nz + b_out);
-    u32* d_st = (u32*)(base + b_sk + b_c1 + b_c2 + b_nz + b_out + b_ns);
+    Scratch sc;
+    const size_t r_sk = sc.add(host ? NP * k * l * 8 : 0), r_c1 = sc.add(stage ? Dc * ctw * 8 : 0), r_c2 = sc.add(Dc * P * 8),
+                 r_nz = sc.add(Dc * P * 8), r_out = sc.add(host ? Dc * 8 : 0), r_ns = sc.add(host && noise ? Dc * 8 : 0),
+                 r_st = sc.add(host && status ? Dc * 4 : 0);
+    PVW_TRY(sc.take(w));
+    i64* d_sk = sc.at<i64>(r_sk);
+    u64 *d_c1 = sc.at(r_c1), *d_c2 = sc.at(r_c2), *d_nz = sc.at(r_nz), *d_out = sc.at(r_out), *d_ns = sc.at(r_ns);
+    u32* d_st = sc.at<u32>(r_st);
     // key material: the uploaded coefficients, NTT(sk) (w->rhat), the noisy polynomials (m g-hat + noise), the decoded values
     // and their reports
-    ws_mark_secret(w, d_sk, b_sk);
+    sc.secret(w, r_sk, r_sk);
     ws_mark_secret(w, w->rhat, (size_t)k * P * 8);
-    ws_mark_secret(w, d_nz, b_nz + b_out + b_ns + b_st);
+    sc.secret(w, r_nz, r_st);
     if (host) PVW_HIP(hipMemcpyAsync(d_sk, sk, NP * k * l * 8, hipMemcpyHostToDevice, s));
     const i64* skd = host ? d_sk : sk;
     for (size_t d0 = 0; d0 < D; d0 += Dc) {
@@ -2846,19 +2723,10 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
         const int32_t rm = decrypt_mac_only(c, w, c1, d_c2, cnt, d_nz, s, &ntt_domain);          // decryption.rs:257-274
         if (w->dpart && (p == 0 || rm != PVW_OK)) ws_mark_secret(w, w->dpart, w->dpart_bytes);   // range sums of s-hat c1
         PVW_TRY(rm);
-        if (ntt_domain && (cnt + 1) / 2 > (size_t)2 * c->num_cus) {                            // as in pvw_decrypt_batch_device
-          ProfScope pi(c, "intt", s);
-          PVW_HIP(launch_ntt(d_nz, cnt, true, c->dt, L, l, s));
-          ntt_domain = false;
-        }
         u64* o = out + p * D + d0;
         u64* on = noise ? noise + p * D + d0 : nullptr;
         u32* os = status ? status + p * D + d0 : nullptr;
-        {
-          ProfScope ps(c, "decode", s);
-          PVW_HIP(launch_decode(d_nz, host ? d_out : o, cnt, c->dec_dev, s, ntt_domain ? &c->dt : nullptr, nullptr, 0, nullptr,
-                                on && host ? d_ns : on, os && host ? d_st : os));                                    // :116, :10-58
-        }
+        PVW_TRY(decode_tail(c, d_nz, cnt, ntt_domain, false, s, host ? d_out : o, on && host ? d_ns : on, os && host ? d_st : os));
         if (host) PVW_HIP(hipMemcpyAsync(o, d_out, cnt * 8, hipMemcpyDeviceToHost, s));
         if (host && on) PVW_HIP(hipMemcpyAsync(on, d_ns, cnt * 8, hipMemcpyDeviceToHost, s));
         if (host && os) PVW_HIP(hipMemcpyAsync(os, d_st, cnt * 4, hipMemcpyDeviceToHost, s));
@@ -2877,29 +2745,23 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
   if (Pc >= NP) Pc = NP;
   else if (Pc >= PVW_GEMM_ROWS_PER_WG) Pc -= Pc % PVW_GEMM_ROWS_PER_WG;   // whole workgroups of GEMM rows
   if (Pc == 0) Pc = 1;
-  const size_t b_c1 = al256(Dg * ctw * 8), b_yd = al256(yd_bytes((u32)(16 * nbg), k, L, l)), b_sy = al256(sy_bytes((u32)(16 * nbg), L, l));
-  const size_t b_sk = host ? al256(Pc * k * l * 8) : 0, b_rows = direct ? 0 : al256(Pc * ctw * 8);
-  const size_t b_xm = al256(xm_words((u32)Pc, k, L, l) * 8), b_tmp = al256(nbg * gemm_tmp_words((u32)Pc, L, l) * 8);
-  const size_t b_c2 = stage ? al256(Dg * Pc * P * 8) : 0, b_nz = al256(Dg * Pc * P * 8), b_out = al256(Dg * Pc * 8);
-  const size_t b_ns = noise ? al256(Dg * Pc * 8) : 0, b_st = status ? al256(Dg * Pc * 4) : 0;
-  PVW_TRY(ws_scratch(w, b_c1 + b_yd + b_sy + b_sk + b_rows + b_xm + b_tmp + b_c2 + b_nz + b_out + b_ns + b_st));
-  char* base = (char*)w->scratch;
-  u64* d_c1 = (u64*)base;
-  signed char* d_yd = (signed char*)(base + b_c1);
-  int* d_sy = (int*)(base + b_c1 + b_yd);
-  char* sec = base + b_c1 + b_yd + b_sy;                           // from here on: everything derived from the keys
-  i64* d_sk = (i64*)sec;
-  u64* d_rows = (u64*)(sec + b_sk);
-  u64* d_xm = (u64*)(sec + b_sk + b_rows);
-  u64* d_tmp = (u64*)(sec + b_sk + b_rows + b_xm);
-  u64* d_c2 = (u64*)(sec + b_sk + b_rows + b_xm + b_tmp);
-  u64* d_nz = (u64*)(sec + b_sk + b_rows + b_xm + b_tmp + b_c2);
-  u64* d_out = (u64*)(sec + b_sk + b_rows + b_xm + b_tmp + b_c2 + b_nz);
-  u64* d_ns = (u64*)(sec + b_sk + b_rows + b_xm + b_tmp + b_c2 + b_nz + b_out);
-  u32* d_st = (u32*)(sec + b_sk + b_rows + b_xm + b_tmp + b_c2 + b_nz + b_out + b_ns);
+  Scratch sc;
+  const size_t r_c1 = sc.add(Dg * ctw * 8), r_yd = sc.add(yd_bytes((u32)(16 * nbg), k, L, l)), r_sy = sc.add(sy_bytes((u32)(16 * nbg), L, l));
+  // from here on: everything derived from the keys
+  const size_t r_sk = sc.add(host ? Pc * k * l * 8 : 0), r_rows = sc.add(direct ? 0 : Pc * ctw * 8);
+  const size_t r_xm = sc.add(xm_words((u32)Pc, k, L, l) * 8), r_tmp = sc.add(nbg * gemm_tmp_words((u32)Pc, L, l) * 8);
+  const size_t r_c2 = sc.add(stage ? Dg * Pc * P * 8 : 0), r_nz = sc.add(Dg * Pc * P * 8), r_out = sc.add(Dg * Pc * 8);
+  const size_t r_ns = sc.add(noise ? Dg * Pc * 8 : 0), r_st = sc.add(status ? Dg * Pc * 4 : 0);
+  PVW_TRY(sc.take(w));
+  u64 *d_c1 = sc.at(r_c1), *d_rows = sc.at(r_rows), *d_xm = sc.at(r_xm), *d_tmp = sc.at(r_tmp), *d_c2 = sc.at(r_c2), *d_nz = sc.at(r_nz),
+      *d_out = sc.at(r_out), *d_ns = sc.at(r_ns);
+  signed char* d_yd = sc.at<signed char>(r_yd);
+  int* d_sy = sc.at<int>(r_sy);
+  i64* d_sk = sc.at<i64>(r_sk);
+  u32* d_st = sc.at<u32>(r_st);
   // the uploaded coefficients, the tiled s-hat (and its rows, l = 64), the GEMM intermediate (s-hat c1), the noisy
   // polynomials, the decoded values and their reports; the staged c2 rows share the region
-  ws_mark_secret(w, sec, b_sk + b_rows + b_xm + b_tmp + b_c2 + b_nz + b_out + b_ns + b_st);
+  sc.secret(w, r_sk, r_st);
   for (size_t p0 = 0; p0 < NP; p0 += Pc) {
     const u32 pc = (u32)((NP - p0) < Pc ? (NP - p0) : Pc);
     const i64* skp = sk + p0 * k * l;
@@ -2948,18 +2810,7 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
         ProfScope ps(c, "finish", s);
         PVW_HIP(launch_finish_decrypt(ga, d_sy, c->dt, L, l, dg, c2p, c2v, P, d_nz, s));     // decryption.rs:257-274
       }
-      const size_t cnt = (size_t)pc * dg;
-      bool xf = true;
-      if ((cnt + 1) / 2 > (size_t)2 * c->num_cus) {                // as in pvw_decrypt_batch_device
-        ProfScope pi(c, "intt", s);
-        PVW_HIP(launch_ntt(d_nz, cnt, true, c->dt, L, l, s));
-        xf = false;
-      }
-      {
-        ProfScope ps(c, "decode", s);
-        PVW_HIP(launch_decode(d_nz, d_out, cnt, c->dec_dev, s, xf ? &c->dt : nullptr, nullptr, 0, nullptr, noise ? d_ns : nullptr,
-                              status ? d_st : nullptr));                                                 // :116, :10-58
-      }
+      PVW_TRY(decode_tail(c, d_nz, (size_t)pc * dg, true, false, s, d_out, noise ? d_ns : nullptr, status ? d_st : nullptr));
       // results[recipient][dealer] (examples/pvw.rs:157-170): the chunk's [pc][dg] block into out[p0..][d0..]
       PVW_HIP(hipMemcpy2DAsync(out + p0 * D + d0, D * 8, d_out, (size_t)dg * 8, (size_t)dg * 8, pc, kout, s));
       if (noise) PVW_HIP(hipMemcpy2DAsync(noise + p0 * D + d0, D * 8, d_ns, (size_t)dg * 8, (size_t)dg * 8, pc, kout, s));
@@ -2968,56 +2819,33 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
   }
   return PVW_OK;
 }
-// single exit: nothing of a failed call stays queued, the key-derived regions are cleared behind the last launch that
-// reads them (host variant: before the workspace goes back to the pool)
-static int32_t decrypt_all_end(Workspace* w, hipStream_t s, int32_t rc, bool host) {
-  if (rc != PVW_OK) (void)hipStreamSynchronize(s);
-  if (ws_wipe_secrets(w, s) != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, "wipe failed");
-  if (host && hipStreamSynchronize(s) != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
-  return rc;
-}
-int32_t pvw_decrypt_all(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
-                        size_t D, uint32_t in_repr, uint64_t* out) {
-  PVW_TRY(decrypt_all_checks(c, lo, hi, sk, c1s, c2s, D, in_repr, out));
-  PVW_TRY(ensure_device(c));
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  int32_t rc = decrypt_all_run(c, w, w->stream, lo, hi, sk, c1s, c2s, D, in_repr, out, true);
-  rc = decrypt_all_end(w, w->stream, rc, true);
-  ws_release(c, w);
-  return rc;
-}
-int32_t pvw_decrypt_all_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
-                               const uint64_t* d_c2s, size_t D, uint32_t in_repr, uint64_t* d_out, void* stream) {
-  PVW_TRY(decrypt_all_checks(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out));
-  PVW_TRY(ensure_device(c));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  Workspace* w;
-  PVW_TRY(ws_for_stream(c, s, &w));
-  return decrypt_all_end(w, s, decrypt_all_run(c, w, s, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out, false), false);
-}
-// checked forms: the same words in out, plus noise / status [P][D] (either may be NULL)
+// host buffers in and out
 int32_t pvw_decrypt_all_checked(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
                                 size_t D, uint32_t in_repr, uint64_t* out, uint64_t* noise, uint32_t* status) {
   PVW_TRY(decrypt_all_checks(c, lo, hi, sk, c1s, c2s, D, in_repr, out));
   PVW_TRY(ensure_device(c));
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  int32_t rc = decrypt_all_run(c, w, w->stream, lo, hi, sk, c1s, c2s, D, in_repr, out, true, noise, status);
-  rc = decrypt_all_end(w, w->stream, rc, true);
-  ws_release(c, w);
-  return rc;
+  return host_call(c, [&](Workspace* w) {
+    return decrypt_all_run(c, w, w->stream, lo, hi, sk, c1s, c2s, D, in_repr, out, true, noise, status);
+  });
 }
+int32_t pvw_decrypt_all(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
+                        size_t D, uint32_t in_repr, uint64_t* out) {
+  return pvw_decrypt_all_checked(c, lo, hi, sk, c1s, c2s, D, in_repr, out, nullptr, nullptr);
+}
+// device pointers on the caller's stream
 int32_t pvw_decrypt_all_checked_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
                                        const uint64_t* d_c2s, size_t D, uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise,
                                        uint32_t* d_status, void* stream) {
   PVW_TRY(decrypt_all_checks(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out));
   PVW_TRY(ensure_device(c));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t s;
   Workspace* w;
-  PVW_TRY(ws_for_stream(c, s, &w));
-  return decrypt_all_end(w, s, decrypt_all_run(c, w, s, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out, false, d_noise, d_status),
-                         false);
+  PVW_TRY(device_ws(c, stream, &s, &w));
+  return device_end(w, s, decrypt_all_run(c, w, s, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out, false, d_noise, d_status));
+}
+int32_t pvw_decrypt_all_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
+                               const uint64_t* d_c2s, size_t D, uint32_t in_repr, uint64_t* d_out, void* stream) {
+  return pvw_decrypt_all_checked_device(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out, nullptr, nullptr, stream);
 }
 
 // ------------------------------------------------------------------------ key generation
@@ -3037,36 +2865,27 @@ static int32_t keygen_gemm_swapped(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 l
   hipStream_t s = w->stream;
   const u32 chunk = (b - a) < 1024 ? (b - a) : 1024;
   const u32 nb = (k + 15) / 16;                                      // batches of 16 column-vectors
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t b_api = al((size_t)k * k * P * 8);
-  const size_t b_yd = al(yd_bytes(16 * nb, k, L, l)), b_sy = al(sy_bytes(16 * nb, L, l));   // whole batches: the last one is read in full
-  const size_t b_small = al((size_t)2 * chunk * k * l * 8);                     // sk | ek of one chunk; two of these (double buffer)
   const bool direct = l <= 32;                                        // see the chunk loop
-  const size_t b_rows = direct ? 0 : al((size_t)chunk * k * P * 8);   // l = 64 only: s-hat rows | e rows, API layout [p][j or col][P]
-  const size_t b_xm = al(xm_words(chunk, k, L, l) * 8);
-  const size_t b_tmp = al((size_t)nb * gemm_tmp_words(chunk, L, l) * 8);
-  PVW_TRY(ws_scratch(w, b_api + b_yd + b_sy + 2 * b_small + 2 * b_rows + b_xm + b_tmp));
-  char* base = (char*)w->scratch;
-  u64* d_api = (u64*)base;
-  signed char* d_yd = (signed char*)(base + b_api);
-  int* d_sy = (int*)(base + b_api + b_yd);
-  i64* d_small2[2] = {(i64*)(base + b_api + b_yd + b_sy), (i64*)(base + b_api + b_yd + b_sy + b_small)};
-  u64* d_srow = (u64*)(base + b_api + b_yd + b_sy + 2 * b_small);
-  u64* d_erow = (u64*)(base + b_api + b_yd + b_sy + 2 * b_small + b_rows);
-  u64* d_xm = (u64*)(base + b_api + b_yd + b_sy + 2 * b_small + 2 * b_rows);
-  u64* d_tmp = (u64*)(base + b_api + b_yd + b_sy + 2 * b_small + 2 * b_rows + b_xm);
+  Scratch sc;
+  const size_t r_api = sc.add((size_t)k * k * P * 8);
+  const size_t r_yd = sc.add(yd_bytes(16 * nb, k, L, l)), r_sy = sc.add(sy_bytes(16 * nb, L, l));   // whole batches: the last one is read in full
+  const size_t r_small0 = sc.add((size_t)2 * chunk * k * l * 8), r_small1 = sc.add((size_t)2 * chunk * k * l * 8);   // sk | ek of one chunk, double buffered
+  const size_t r_srow = sc.add(direct ? 0 : (size_t)chunk * k * P * 8);   // l = 64 only: s-hat rows | e rows, API layout [p][j or col][P]
+  const size_t r_erow = sc.add(direct ? 0 : (size_t)chunk * k * P * 8);
+  const size_t r_xm = sc.add(xm_words(chunk, k, L, l) * 8);
+  const size_t r_tmp = sc.add((size_t)nb * gemm_tmp_words(chunk, L, l) * 8);
+  PVW_TRY(sc.take(w));
+  u64 *d_api = sc.at(r_api), *d_srow = sc.at(r_srow), *d_erow = sc.at(r_erow), *d_xm = sc.at(r_xm), *d_tmp = sc.at(r_tmp);
+  signed char* d_yd = sc.at<signed char>(r_yd);
+  int* d_sy = sc.at<int>(r_sy);
+  i64* d_small2[2] = {sc.at<i64>(r_small0), sc.at<i64>(r_small1)};
   // everything derived from the secret keys: their coefficients (and explicit key errors), the MFMA-tiled copy of
   // NTT(s), the GEMM intermediate (s A without the error) and, for l = 64, the rows of NTT(s) and of the transformed
-  // errors -- cleared by pvw_keygen when the call ends
-  ws_mark_secret(w, d_small2[0], 2 * b_small + 2 * b_rows + b_xm + b_tmp);
+  // errors -- cleared when the call ends
+  sc.secret(w, r_small0, r_tmp);
   // the secret keys of chunk i+1 are uploaded on a helper stream while chunk i computes
   const u32 nchunks = (b - a + chunk - 1) / chunk;
-  if (!w->aux) PVW_HIP(hipStreamCreateWithFlags(&w->aux, hipStreamNonBlocking));
-  while (w->events.size() < 2 * (size_t)nchunks + 2) {
-    hipEvent_t e;
-    PVW_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    w->events.push_back(e);
-  }
+  PVW_TRY(ws_aux(w, 2 * (size_t)nchunks + 2));
   auto upload = [&](u32 ci, hipStream_t st) -> int32_t {
     const u32 q0 = a + ci * chunk, cn = (b - q0) < chunk ? (b - q0) : chunk;
     const size_t wd = (size_t)cn * k * l;
@@ -3134,45 +2953,14 @@ static int32_t keygen_gemm_swapped(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 l
   return PVW_OK;
 }
 
-// single exit of a key generation: both streams are drained whatever happened (an early return must not leave
-// copies from the caller's sk / ek buffers or launches on pooled scratch in flight), the secret-bearing
-// regions are cleared, and only then does the workspace go back to the pool
-static int32_t keygen_finish(Workspace* w, int32_t rc) {
-  if (w->aux && hipStreamSynchronize(w->aux) != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
-  if (hipStreamSynchronize(w->stream) != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
-  if ((ws_wipe_secrets(w, w->stream) != hipSuccess || hipStreamSynchronize(w->stream) != hipSuccess) && rc == PVW_OK)
-    rc = fail(PVW_ERR_INTERNAL, "wipe failed");
-  return rc;
-}
-
-int32_t pvw_keygen(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const int64_t* ek, const uint8_t seed[32]) {
-  if (!c || !sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  if (!ek && !seed) return fail(PVW_ERR_INVALID_PARAMETERS, "either explicit key errors or a seed is required");
-  PVW_TRY(check_party_range(c, lo, hi));
-  PVW_TRY(ensure_device(c));
-  c->xm_valid = false; c->pkB_valid = false; c->pk_wide = false;
-  if (!c->crs_loaded) return fail(PVW_ERR_CRS, "CRS not loaded");
-  if (c->rowsA() != c->k) return fail(PVW_ERR_KEY_GENERATION, "key generation needs the full CRS on this context");
-  PVW_TRY(ensure_matrix(c, &c->dB, c->rowsB()));
-  const u32 a = lo > c->party_lo ? lo : c->party_lo, b = hi < c->party_hi ? hi : c->party_hi;
+// fewer than 64 parties, or PVW_KEYGEN_SWAP=0: the CRS transposed once per call and streamed, the parties' s-hat as the
+// vectors -- 16 per pass on the matrix cores (everything around the GEMM batched over super-groups of up to 128 parties),
+// 4 per pass on the VALU
+static int32_t keygen_transposed(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 lo, const int64_t* sk, const int64_t* ek,
+                                 const uint8_t* seed, bool use_gemm) {
   const u32 k = c->k, l = c->l, L = c->L;
   const size_t P = c->poly();
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
   hipStream_t s = w->stream;
-  // >= 8 parties: the matrix cores (gemm_digits, 16 parties per pass over A^T, everything around it batched
-  // over super-groups of up to 128 parties); fewer: 4 per pass on the VALU
-  const int gemm_min = (int)PVW_ENV_INT("PVW_GEMM_MIN_DEALERS", 8);   // tuning build only
-  const bool use_gemm = gemm_min > 0 && (b - a) >= (u32)gemm_min;
-  // default matrix-core form: parties as GEMM rows, the CRS columns digitised once (PVW_KEYGEN_SWAP=0: the earlier
-  // form with the transposed CRS as the streamed operand and the secret keys digitised per super-group)
-  const int swap_roles = (int)PVW_ENV_INT("PVW_KEYGEN_SWAP", 1);   // tuning build, per call: the tests walk both
-  if (use_gemm && swap_roles && (b - a) >= 64) {
-    int32_t rc2 = keygen_finish(w, keygen_gemm_swapped(c, w, a, b, lo, sk, ek, seed));
-    ws_release(c, w);
-    if (rc2 == PVW_OK && hi > c->num_keys) c->num_keys = hi;
-    return rc2;
-  }
   const u32 group = use_gemm ? 16 : 4;
   // super-group: parties whose sampling, NTTs, digit tiles and final tiling are single launches; bounded so
   // that the digit tiles stay below ~2 GiB
@@ -3184,117 +2972,104 @@ int32_t pvw_keygen(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, cons
     if (m > 8) m = 8;
     sg = 16 * (u32)m;
   }
-  // scratch: A in API layout [k][k][P] | A^T in API layout | A^T tiled or MFMA-tiled | sk,ek of one chunk |
-  //          rows of B for one super-group | gemm intermediate | (gemm) s-hat vectors, digit tiles, column sums
-  const size_t b_api = ((size_t)k * k * P * 8 + 255) & ~(size_t)255;
-  const size_t b_tt = ((use_gemm ? xm_words(k, k, L, l) : c->tiled_words(k)) * 8 + 255) & ~(size_t)255;
   u32 chunk = (b - a) < 1024 ? (b - a) : 1024;         // parties whose sk / ek are uploaded together
   if (chunk > sg) chunk -= chunk % sg;                  // whole super-groups per chunk
-  const size_t b_small = ((size_t)2 * chunk * k * l * 8 + 255) & ~(size_t)255;
-  const size_t b_row = ((size_t)sg * k * P * 8 + 255) & ~(size_t)255;
-  const size_t b_tmp = use_gemm ? (((size_t)(sg / 16) * gemm_tmp_words(k, L, l) * 8 + 255) & ~(size_t)255) : 0;
-  const size_t b_vh = use_gemm ? b_row : 0;
-  const size_t b_yd = use_gemm ? ((yd_bytes(sg, k, L, l) + 255) & ~(size_t)255) : 0;
-  const size_t b_sy = use_gemm ? ((sy_bytes(sg, L, l) + 255) & ~(size_t)255) : 0;
-  int32_t rc = ws_scratch(w, 2 * b_api + b_tt + b_small + b_row + b_tmp + b_vh + b_yd + b_sy);
-  if (rc == PVW_OK) {
-    char* base = (char*)w->scratch;
-    u64* d_api = (u64*)base;
-    u64* d_apiT = (u64*)(base + b_api);
-    u64* d_tt = (u64*)(base + 2 * b_api);
-    i64* d_small = (i64*)(base + 2 * b_api + b_tt);
-    u64* d_row = (u64*)(base + 2 * b_api + b_tt + b_small);
-    u64* d_tmp = (u64*)(base + 2 * b_api + b_tt + b_small + b_row);
-    char* gb0 = base + 2 * b_api + b_tt + b_small + b_row + b_tmp;
-    u64* d_vh = (u64*)gb0;
-    signed char* d_yd = (signed char*)(gb0 + b_vh);
-    int* d_sy = (int*)(gb0 + b_vh + b_yd);
-    // secret-bearing regions (cleared by keygen_finish): uploaded sk / ek coefficients; NTT(s) vectors, their digit
-    // tiles and column sums (matrix-core form) or the s-hat vectors in w->rhat (VALU form).  d_row holds e only
-    // until the product is added onto it, then rows of the public key.
-    ws_mark_secret(w, d_small, b_small);
-    if (use_gemm) {
-      ws_mark_secret(w, d_tmp, b_tmp);                       // s A^T without the error
-      ws_mark_secret(w, d_vh, b_vh + b_yd + b_sy);
+  // scratch: A in API layout [k][k][P] | A^T in API layout | A^T tiled or MFMA-tiled | sk,ek of one chunk |
+  //          rows of B for one super-group | gemm intermediate | (gemm) s-hat vectors, digit tiles, column sums
+  Scratch sc;
+  const size_t r_api = sc.add((size_t)k * k * P * 8), r_apiT = sc.add((size_t)k * k * P * 8);
+  const size_t r_tt = sc.add((use_gemm ? xm_words(k, k, L, l) : c->tiled_words(k)) * 8);
+  const size_t r_small = sc.add((size_t)2 * chunk * k * l * 8), r_row = sc.add((size_t)sg * k * P * 8);
+  const size_t r_tmp = sc.add(use_gemm ? (size_t)(sg / 16) * gemm_tmp_words(k, L, l) * 8 : 0);
+  const size_t r_vh = sc.add(use_gemm ? (size_t)sg * k * P * 8 : 0);
+  const size_t r_yd = sc.add(use_gemm ? yd_bytes(sg, k, L, l) : 0), r_sy = sc.add(use_gemm ? sy_bytes(sg, L, l) : 0);
+  PVW_TRY(sc.take(w));
+  u64 *d_api = sc.at(r_api), *d_apiT = sc.at(r_apiT), *d_tt = sc.at(r_tt), *d_row = sc.at(r_row), *d_tmp = sc.at(r_tmp), *d_vh = sc.at(r_vh);
+  i64* d_small = sc.at<i64>(r_small);
+  signed char* d_yd = sc.at<signed char>(r_yd);
+  int* d_sy = sc.at<int>(r_sy);
+  // secret-bearing regions (cleared when the call ends): uploaded sk / ek coefficients; NTT(s) vectors, their digit
+  // tiles and column sums (matrix-core form) or the s-hat vectors in w->rhat (VALU form).  d_row holds e only
+  // until the product is added onto it, then rows of the public key.
+  sc.secret(w, r_small, r_small);
+  if (use_gemm) {
+    sc.secret(w, r_tmp, r_tmp);                            // s A^T without the error
+    sc.secret(w, r_vh, r_sy);
+  }
+  else ws_mark_secret(w, w->rhat, w->rhat_bytes);
+  // A -> API layout -> transpose polynomials (A^T[c][j] = A[j][c]) -> tiled / MFMA-tiled
+  PVW_HIP(launch_untile(c->dA, d_api, k, 0, k, L, l, false, c->dt, s));
+  PVW_HIP(launch_transpose_polys(d_api, d_apiT, k, (u32)P, s));
+  PVW_HIP(hipMemsetAsync(d_tt, 0, sc.bytes(r_tt), s));
+  if (use_gemm) PVW_HIP(launch_mftile(d_apiT, false, d_tt, k, k, L, l, s));
+  else PVW_HIP(launch_tile(d_apiT, d_tt, k, 0, k, L, l, false, c->dt, s));
+  for (u32 p0 = a; p0 < b; p0 += sg) {
+    const u32 nv = (b - p0) < sg ? (b - p0) : sg;
+    const u32 in_chunk = (p0 - a) % chunk;                       // position inside the uploaded chunk
+    if (in_chunk == 0) {
+      const u32 cn = (b - p0) < chunk ? (b - p0) : chunk;
+      const size_t words = (size_t)cn * k * l;
+      PVW_HIP(hipMemcpyAsync(d_small, sk + (size_t)(p0 - lo) * k * l, words * 8, hipMemcpyHostToDevice, s));
+      if (ek) PVW_HIP(hipMemcpyAsync(d_small + (size_t)chunk * k * l, ek + (size_t)(p0 - lo) * k * l, words * 8, hipMemcpyHostToDevice, s));
     }
-    else ws_mark_secret(w, w->rhat, w->rhat_bytes);
-    // A -> API layout -> transpose polynomials (A^T[c][j] = A[j][c]) -> tiled / MFMA-tiled
-    bool okk = launch_untile(c->dA, d_api, k, 0, k, L, l, false, c->dt, s) == hipSuccess;
-    okk = okk && launch_transpose_polys(d_api, d_apiT, k, (u32)P, s) == hipSuccess;
-    okk = okk && hipMemsetAsync(d_tt, 0, b_tt, s) == hipSuccess;
-    if (use_gemm) okk = okk && launch_mftile(d_apiT, false, d_tt, k, k, L, l, s) == hipSuccess;
-    else okk = okk && launch_tile(d_apiT, d_tt, k, 0, k, L, l, false, c->dt, s) == hipSuccess;
-    if (!okk) rc = fail(PVW_ERR_INTERNAL, "CRS transpose failed");
-    for (u32 p0 = a; rc == PVW_OK && p0 < b; p0 += sg) {
-      const u32 nv = (b - p0) < sg ? (b - p0) : sg;
-      const u32 in_chunk = (p0 - a) % chunk;                       // position inside the uploaded chunk
-      if (in_chunk == 0) {
-        const u32 cn = (b - p0) < chunk ? (b - p0) : chunk;
-        const size_t words = (size_t)cn * k * l;
-        if (hipMemcpyAsync(d_small, sk + (size_t)(p0 - lo) * k * l, words * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-            (ek && hipMemcpyAsync(d_small + (size_t)chunk * k * l, ek + (size_t)(p0 - lo) * k * l, words * 8, hipMemcpyHostToDevice, s) != hipSuccess)) {
-          rc = fail(PVW_ERR_INTERNAL, "H2D failed");
-          break;
-        }
-      }
-      ProfScope ps(c, "keygen", s);
-      bool ok2 = true;
-      if (use_gemm) {
-        // ONE prologue launch for the super-group: the (s, e) families of party p0 replicated over its nv parties.
-        // s-hat_p (secret_key.rs:98-112) goes to the vector layout [party][limb][j][slot]; e_p (public_key.rs:128-132),
-        // sampled or explicit, to NTT form in the row buffer [nv][k][P]
-        {
-          PrologueBatch pb{};
-          if (seed) pb.key[0] = make_key(seed);
-          PrologueJob& js = pb.job[0];
-          PrologueJob& je = pb.job[1];
-          js.sj.count = k; js.explicit_coeffs = d_small + (size_t)in_chunk * k * l;
-          js.out = d_vh; js.stride_poly = l; js.stride_limb = (size_t)k * l;
-          js.rep_coeffs = (size_t)k * l; js.rep_out = (size_t)k * P;
-          je.sj.kind = SAMPLE_UNIFORM; je.sj.domain = DOM_EKEY; je.sj.index0 = p0 * k; je.sj.count = k; je.sj.bound = c->b1;
-          je.rep_index0 = k;
-          if (ek) { je.explicit_coeffs = d_small + (size_t)(chunk + in_chunk) * k * l; je.rep_coeffs = (size_t)k * l; }
-          je.out = d_row; je.stride_poly = P; je.stride_limb = l; je.rep_out = (size_t)k * P;
-          pb.njobs = 2;
-          pb.reps = nv;
-          ok2 = launch_prologue(pb, c->dt, L, l, s) == hipSuccess;
-        }
-        ok2 = ok2 && launch_vec_digits(d_vh, (size_t)k * P, d_yd, d_sy, nv, k, L, l, c->dt, s) == hipSuccess;
-        // all batches of 16 parties in one launch (crs.rs:152-168): they share A^T through L2
-        // ... and the finish pass writes b_p = s_p*A + e_p straight into the tiled B-hat (no re-tiling launch)
-        GemmSection ga{d_tt, d_row, d_row, d_tmp, k, 0, 0}, gb{nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
-        ga.tiled_out = c->dB;
-        ga.tiled_row0 = p0 - c->party_lo;
-        ok2 = ok2 && launch_gemm_digits(ga, gb, d_yd, d_sy, c->dt, k, L, l, nv, (size_t)k * P, 0, s) == hipSuccess;
-      } else {
-        u64* vh = w->rhat;
-        PrologueBatch pb{};
-        if (seed) pb.key[0] = make_key(seed);
-        {
-          PrologueJob& js = pb.job[0];
-          PrologueJob& je = pb.job[1];
-          js.sj.count = k; js.explicit_coeffs = d_small + (size_t)in_chunk * k * l;              // secret_key.rs:98-112
-          js.out = vh; js.stride_poly = l; js.stride_limb = (size_t)k * l;
-          js.rep_coeffs = (size_t)k * l; js.rep_out = (size_t)k * P;
-          je.sj.kind = SAMPLE_UNIFORM; je.sj.domain = DOM_EKEY; je.sj.index0 = p0 * k; je.sj.count = k; je.sj.bound = c->b1;  // public_key.rs:128-132
-          je.rep_index0 = k;
-          if (ek) { je.explicit_coeffs = d_small + (size_t)(chunk + in_chunk) * k * l; je.rep_coeffs = (size_t)k * l; }
-          je.out = d_row; je.stride_poly = P; je.stride_limb = l; je.rep_out = (size_t)k * P;
-        }
-        pb.njobs = 2;
-        pb.reps = nv;
-        ok2 = launch_prologue(pb, c->dt, L, l, s) == hipSuccess;
-        MacSection sa{d_tt, d_row, d_row, k, 0}, sb{nullptr, nullptr, nullptr, 0, 0};
-        MultiVec mv{vh, (size_t)k * P, (size_t)k * P, 0, nv};
-        ok2 = ok2 && launch_mac_rows_multi(sa, sb, mv, c->dt, k, L, l, s) == hipSuccess;
-      }
-      // VALU path: d_row is [nv][k polys][P] = nv rows of B in API layout -> tile into B
-      if (!use_gemm) ok2 = ok2 && launch_tile(d_row, c->dB, nv, p0 - c->party_lo, k, L, l, false, c->dt, s) == hipSuccess;
-      if (!ok2) rc = fail(PVW_ERR_KEY_GENERATION, "keygen launch failed");
+    ProfScope ps(c, "keygen", s);
+    // ONE prologue launch for the super-group: the (s, e) families of party p0 replicated over its nv parties.  s-hat_p
+    // (secret_key.rs:98-112) goes to the vector layout [party][limb][j][slot] (d_vh, or w->rhat on the VALU); e_p
+    // (public_key.rs:128-132), sampled or explicit, to NTT form in the row buffer [nv][k][P]
+    PrologueBatch pb{};
+    if (seed) pb.key[0] = make_key(seed);
+    PrologueJob& js = pb.job[0];
+    PrologueJob& je = pb.job[1];
+    u64* vh = use_gemm ? d_vh : w->rhat;
+    js.sj.count = k; js.explicit_coeffs = d_small + (size_t)in_chunk * k * l;
+    js.out = vh; js.stride_poly = l; js.stride_limb = (size_t)k * l;
+    js.rep_coeffs = (size_t)k * l; js.rep_out = (size_t)k * P;
+    je.sj.kind = SAMPLE_UNIFORM; je.sj.domain = DOM_EKEY; je.sj.index0 = p0 * k; je.sj.count = k; je.sj.bound = c->b1;
+    je.rep_index0 = k;
+    if (ek) { je.explicit_coeffs = d_small + (size_t)(chunk + in_chunk) * k * l; je.rep_coeffs = (size_t)k * l; }
+    je.out = d_row; je.stride_poly = P; je.stride_limb = l; je.rep_out = (size_t)k * P;
+    pb.njobs = 2;
+    pb.reps = nv;
+    PVW_HIP_AS(PVW_ERR_KEY_GENERATION, launch_prologue(pb, c->dt, L, l, s));
+    if (use_gemm) {
+      PVW_HIP_AS(PVW_ERR_KEY_GENERATION, launch_vec_digits(d_vh, (size_t)k * P, d_yd, d_sy, nv, k, L, l, c->dt, s));
+      // all batches of 16 parties in one launch (crs.rs:152-168): they share A^T through L2
+      // ... and the finish pass writes b_p = s_p*A + e_p straight into the tiled B-hat (no re-tiling launch)
+      GemmSection ga{d_tt, d_row, d_row, d_tmp, k, 0, 0}, gb{nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
+      ga.tiled_out = c->dB;
+      ga.tiled_row0 = p0 - c->party_lo;
+      PVW_HIP_AS(PVW_ERR_KEY_GENERATION, launch_gemm_digits(ga, gb, d_yd, d_sy, c->dt, k, L, l, nv, (size_t)k * P, 0, s));
+    } else {
+      MacSection sa{d_tt, d_row, d_row, k, 0}, sb{nullptr, nullptr, nullptr, 0, 0};
+      MultiVec mv{vh, (size_t)k * P, (size_t)k * P, 0, nv};
+      PVW_HIP_AS(PVW_ERR_KEY_GENERATION, launch_mac_rows_multi(sa, sb, mv, c->dt, k, L, l, s));
+      // d_row is [nv][k polys][P] = nv rows of B in API layout -> tile into B
+      PVW_HIP_AS(PVW_ERR_KEY_GENERATION, launch_tile(d_row, c->dB, nv, p0 - c->party_lo, k, L, l, false, c->dt, s));
     }
   }
-  rc = keygen_finish(w, rc);
-  ws_release(c, w);
+  return PVW_OK;
+}
+
+int32_t pvw_keygen(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const int64_t* ek, const uint8_t seed[32]) {
+  if (!c || !sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (!ek && !seed) return fail(PVW_ERR_INVALID_PARAMETERS, "either explicit key errors or a seed is required");
+  PVW_TRY(check_party_range(c, lo, hi));
+  PVW_TRY(ensure_device(c));
+  matrix_changed(c, false);
+  if (!c->crs_loaded) return fail(PVW_ERR_CRS, "CRS not loaded");
+  if (c->rowsA() != c->k) return fail(PVW_ERR_KEY_GENERATION, "key generation needs the full CRS on this context");
+  PVW_TRY(ensure_matrix(c, &c->dB, c->rowsB()));
+  const u32 a = lo > c->party_lo ? lo : c->party_lo, b = hi < c->party_hi ? hi : c->party_hi;
+  // >= 8 parties: the matrix cores (gemm_digits, 16 parties per pass); fewer: 4 per pass on the VALU
+  const int gemm_min = (int)PVW_ENV_INT("PVW_GEMM_MIN_DEALERS", 8);   // tuning build only
+  const bool use_gemm = gemm_min > 0 && (b - a) >= (u32)gemm_min;
+  // default matrix-core form: parties as GEMM rows, the CRS columns digitised once (PVW_KEYGEN_SWAP=0: the earlier
+  // form with the transposed CRS as the streamed operand and the secret keys digitised per super-group)
+  const int swap_roles = (int)PVW_ENV_INT("PVW_KEYGEN_SWAP", 1);   // tuning build, per call: the tests walk both
+  const int32_t rc = host_call(c, [&](Workspace* w) {
+    return use_gemm && swap_roles && (b - a) >= 64 ? keygen_gemm_swapped(c, w, a, b, lo, sk, ek, seed)
+                                                   : keygen_transposed(c, w, a, b, lo, sk, ek, seed, use_gemm);
+  });
   if (rc == PVW_OK && hi > c->num_keys) c->num_keys = hi;
   return rc;
 }
@@ -3429,7 +3204,6 @@ static size_t wire_chunk_polys(const pvw_ctx* c, size_t bytes) {
   size_t n = bytes / (c->poly() * 8) / 16 * 16;
   return n ? n : 16;
 }
-static size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 static int32_t wire_pack_enqueue(pvw_ctx* c, const u64* d_polys, size_t count, uint8_t* d_out, hipStream_t s) {
   ProfScope ps(c, "wire_pack", s);
   PVW_HIP(launch_wire_pack(d_polys, count, d_out, c->dt.mods, c->L, c->l, s));
@@ -3457,48 +3231,45 @@ static int32_t wire_load_rows(pvw_ctx* c, u64** Mp, u32 shard_lo, u32 shard_hi, 
   if (stage_rows == 0) stage_rows = m;
   size_t word_rows = ((size_t)256 << 20) / (rowwords * 8) / m * m;
   if (word_rows == 0) word_rows = m;
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  uint8_t* d_pk = nullptr;
-  int32_t rc = PVW_OK;
-  if (hipMalloc((void**)&d_pk, up16(stage_rows * rowbytes) + 16) != hipSuccess) {
+  // the staged body and the check count behind it, outside the pooled scratch (which takes the unpacked words)
+  Scratch st(16);
+  const size_t r_pk = st.add(stage_rows * rowbytes), r_bad = st.add(8);
+  if (hipMalloc((void**)&st.base, st.total) != hipSuccess) {
     (void)hipGetLastError();
-    rc = fail(PVW_ERR_INTERNAL, "wire: no device memory for the staged body");
+    return fail(PVW_ERR_INTERNAL, "wire: no device memory for the staged body");
   }
-  u64* d_bad = d_pk ? (u64*)(d_pk + up16(stage_rows * rowbytes)) : nullptr;
-  auto stage = [&](u32 r0, u32 cnt) -> int32_t {
-    PVW_HIP(hipMemcpyAsync(d_pk, src + (size_t)(r0 - a) * rowbytes, (size_t)cnt * rowbytes, hipMemcpyHostToDevice, w->stream));
-    return PVW_OK;
-  };
-  // pass 1: check
-  if (rc == PVW_OK && hipMemsetAsync(d_bad, 0, 8, w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "memset failed");
-  for (u32 r0 = a; rc == PVW_OK && r0 < b; r0 += (u32)stage_rows) {
-    const u32 cnt = (size_t)(b - r0) < stage_rows ? (b - r0) : (u32)stage_rows;
-    rc = stage(r0, cnt);
-    if (rc == PVW_OK) rc = wire_unpack_enqueue(c, d_pk, (size_t)cnt * k, nullptr, d_bad, w->stream);
-    if (rc == PVW_OK && !whole && hipStreamSynchronize(w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
-  }
-  u64 bad = 0;
-  if (rc == PVW_OK && (hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
-                       hipStreamSynchronize(w->stream) != hipSuccess))
-    rc = fail(PVW_ERR_INTERNAL, "wire: reading the check count failed");
-  if (rc == PVW_OK && bad) rc = wire_find_reject(c, src, (size_t)(b - a) * k, (size_t)(a - lo) * k);
-  // pass 2: unpack and tile
-  if (rc == PVW_OK) rc = commit();
-  if (rc == PVW_OK) rc = ws_scratch(w, word_rows * rowwords * 8);
-  for (u32 r0 = a; rc == PVW_OK && r0 < b; r0 += (u32)stage_rows) {
-    const u32 cnt = (size_t)(b - r0) < stage_rows ? (b - r0) : (u32)stage_rows;
-    if (!whole) rc = stage(r0, cnt);
-    for (u32 s0 = 0; rc == PVW_OK && s0 < cnt; s0 += (u32)word_rows) {
-      const u32 sc = (size_t)(cnt - s0) < word_rows ? (cnt - s0) : (u32)word_rows;
-      rc = wire_unpack_enqueue(c, d_pk + (size_t)s0 * rowbytes, (size_t)sc * k, (u64*)w->scratch, d_bad, w->stream);
-      if (rc == PVW_OK) rc = load_rows_device(c, *Mp, shard_lo, shard_hi, r0 + s0, r0 + s0 + sc, (const u64*)w->scratch, repr, w->stream);
-      if (rc == PVW_OK && hipStreamSynchronize(w->stream) != hipSuccess) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
+  uint8_t* d_pk = st.at<uint8_t>(r_pk);
+  u64* d_bad = st.at(r_bad);
+  const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
+    auto stage = [&](u32 r0, u32 cnt) {
+      return hipMemcpyAsync(d_pk, src + (size_t)(r0 - a) * rowbytes, (size_t)cnt * rowbytes, hipMemcpyHostToDevice, w->stream);
+    };
+    // pass 1: check
+    PVW_HIP(hipMemsetAsync(d_bad, 0, 8, w->stream));
+    for (u32 r0 = a; r0 < b; r0 += (u32)stage_rows) {
+      const u32 cnt = (size_t)(b - r0) < stage_rows ? (b - r0) : (u32)stage_rows;
+      PVW_HIP(stage(r0, cnt));
+      PVW_TRY(wire_unpack_enqueue(c, d_pk, (size_t)cnt * k, nullptr, d_bad, w->stream));
     }
-  }
-  if (hipStreamSynchronize(w->stream) != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
-  hipFree(d_pk);
-  ws_release(c, w);
+    u64 bad = 0;
+    PVW_HIP(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, w->stream));
+    PVW_HIP(hipStreamSynchronize(w->stream));
+    if (bad) return wire_find_reject(c, src, (size_t)(b - a) * k, (size_t)(a - lo) * k);
+    // pass 2: unpack and tile
+    PVW_TRY(commit());
+    PVW_TRY(ws_scratch(w, word_rows * rowwords * 8));
+    for (u32 r0 = a; r0 < b; r0 += (u32)stage_rows) {
+      const u32 cnt = (size_t)(b - r0) < stage_rows ? (b - r0) : (u32)stage_rows;
+      if (!whole) PVW_HIP(stage(r0, cnt));
+      for (u32 s0 = 0; s0 < cnt; s0 += (u32)word_rows) {
+        const u32 sc = (size_t)(cnt - s0) < word_rows ? (cnt - s0) : (u32)word_rows;
+        PVW_TRY(wire_unpack_enqueue(c, d_pk + (size_t)s0 * rowbytes, (size_t)sc * k, (u64*)w->scratch, d_bad, w->stream));
+        PVW_TRY(load_rows_device(c, *Mp, shard_lo, shard_hi, r0 + s0, r0 + s0 + sc, (const u64*)w->scratch, repr, w->stream));
+      }
+    }
+    return PVW_OK;
+  });
+  hipFree(st.base);
   return rc;
 }
 // rows [lo, hi) of a resident matrix, packed, to a host body (rows the shard does not hold are not written)
@@ -3510,23 +3281,18 @@ static int32_t wire_get_rows(pvw_ctx* c, const u64* M, u32 shard_lo, u32 shard_h
   const u32 m = 16 / (u32)(k & 15 ? (k & 1 ? 1 : (k & 3 ? 2 : (k & 7 ? 4 : 8))) : 16);
   size_t chunk = ((size_t)256 << 20) / (rowwords * 8) / m * m;
   if (chunk == 0) chunk = m;
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  const size_t cw = up16(chunk * rowwords * 8);
-  int32_t rc = ws_scratch(w, cw + up16(chunk * rowbytes));
-  for (u32 r0 = a; rc == PVW_OK && r0 < b; r0 += (u32)chunk) {
-    const u32 cnt = (size_t)(b - r0) < chunk ? (b - r0) : (u32)chunk;
-    uint8_t* d_pk = (uint8_t*)w->scratch + cw;
-    if (launch_untile(M, (u64*)w->scratch, cnt, r0 - shard_lo, c->k, c->L, c->l, repr == PVW_REPR_POWER, c->dt, w->stream) != hipSuccess)
-      rc = fail(PVW_ERR_INTERNAL, "untile failed");
-    if (rc == PVW_OK) rc = wire_pack_enqueue(c, (const u64*)w->scratch, (size_t)cnt * k, d_pk, w->stream);
-    if (rc == PVW_OK && (hipMemcpyAsync(body + (size_t)(r0 - lo) * rowbytes, d_pk, (size_t)cnt * rowbytes, hipMemcpyDeviceToHost,
-                                        w->stream) != hipSuccess ||
-                         hipStreamSynchronize(w->stream) != hipSuccess))
-      rc = fail(PVW_ERR_INTERNAL, "D2H failed");
-  }
-  ws_release(c, w);
-  return rc;
+  Scratch sc(16);
+  const size_t r_w = sc.add(chunk * rowwords * 8), r_pk = sc.add(chunk * rowbytes);
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    for (u32 r0 = a; r0 < b; r0 += (u32)chunk) {
+      const u32 cnt = (size_t)(b - r0) < chunk ? (b - r0) : (u32)chunk;
+      PVW_HIP(launch_untile(M, sc.at(r_w), cnt, r0 - shard_lo, c->k, c->L, c->l, repr == PVW_REPR_POWER, c->dt, w->stream));
+      PVW_TRY(wire_pack_enqueue(c, sc.at(r_w), (size_t)cnt * k, sc.at<uint8_t>(r_pk), w->stream));
+      PVW_HIP(hipMemcpyAsync(body + (size_t)(r0 - lo) * rowbytes, sc.at<uint8_t>(r_pk), (size_t)cnt * rowbytes, hipMemcpyDeviceToHost, w->stream));
+    }
+    return PVW_OK;
+  });
 }
 
 int32_t pvw_wire_poly_bytes(const pvw_ctx* c, size_t* out) {
@@ -3639,7 +3405,7 @@ int32_t pvw_wire_pack_device(pvw_ctx* c, const uint64_t* d_polys, size_t count, 
   if (!aligned16(d_polys) || !aligned16(d_out)) return fail(PVW_ERR_INVALID_PARAMETERS, "wire: device buffers must be 16-byte aligned");
   PVW_TRY(wire_device_checks(c));
   PVW_TRY(ensure_device(c));
-  return wire_pack_enqueue(c, d_polys, count, d_out, stream ? (hipStream_t)stream : c->stream);
+  return wire_pack_enqueue(c, d_polys, count, d_out, call_stream(c, stream));
 }
 
 int32_t pvw_wire_unpack_device(pvw_ctx* c, const uint8_t* d_in, size_t count, uint64_t* d_polys, uint64_t* d_bad, void* stream) {
@@ -3647,7 +3413,7 @@ int32_t pvw_wire_unpack_device(pvw_ctx* c, const uint8_t* d_in, size_t count, ui
   if (!aligned16(d_in) || !aligned16(d_polys)) return fail(PVW_ERR_INVALID_PARAMETERS, "wire: device buffers must be 16-byte aligned");
   PVW_TRY(wire_device_checks(c));
   PVW_TRY(ensure_device(c));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t s = call_stream(c, stream);
   PVW_HIP(hipMemsetAsync(d_bad, 0, 8, s));
   return wire_unpack_enqueue(c, d_in, count, d_polys, d_bad, s);
 }
@@ -3661,22 +3427,20 @@ int32_t pvw_wire_pack(pvw_ctx* c, const uint64_t* polys, size_t count, uint8_t* 
   // output the device can write (pvw_host_alloc, or pinned / registered by the caller): the kernel stores into it directly
   uint8_t* direct = (uint8_t*)device_alias(out, count * pb);
   if (direct && !aligned16(direct)) direct = nullptr;
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  const size_t n0 = count < chunk ? count : chunk, cw = up16(n0 * P * 8);
-  int32_t rc = ws_scratch(w, cw + up16(n0 * pb));
-  for (size_t p0 = 0; rc == PVW_OK && p0 < count; p0 += chunk) {
-    const size_t cnt = count - p0 < chunk ? count - p0 : chunk;
-    uint8_t* d_pk = direct ? direct + p0 * pb : (uint8_t*)w->scratch + cw;
-    if (hipMemcpyAsync(w->scratch, polys + p0 * P, cnt * P * 8, hipMemcpyHostToDevice, w->stream) != hipSuccess)
-      rc = fail(PVW_ERR_INTERNAL, "H2D failed");
-    if (rc == PVW_OK) rc = wire_pack_enqueue(c, (const u64*)w->scratch, cnt, d_pk, w->stream);
-    if (rc == PVW_OK && !direct && hipMemcpyAsync(out + p0 * pb, d_pk, cnt * pb, hipMemcpyDeviceToHost, w->stream) != hipSuccess)
-      rc = fail(PVW_ERR_INTERNAL, "D2H failed");
-    if (hipStreamSynchronize(w->stream) != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
-  }
-  ws_release(c, w);
-  return rc;
+  const size_t n0 = count < chunk ? count : chunk;
+  Scratch sc(16);
+  const size_t r_w = sc.add(n0 * P * 8), r_pk = sc.add(n0 * pb);
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    for (size_t p0 = 0; p0 < count; p0 += chunk) {
+      const size_t cnt = count - p0 < chunk ? count - p0 : chunk;
+      uint8_t* d_pk = direct ? direct + p0 * pb : sc.at<uint8_t>(r_pk);
+      PVW_HIP(hipMemcpyAsync(sc.at(r_w), polys + p0 * P, cnt * P * 8, hipMemcpyHostToDevice, w->stream));
+      PVW_TRY(wire_pack_enqueue(c, sc.at(r_w), cnt, d_pk, w->stream));
+      if (!direct) PVW_HIP(hipMemcpyAsync(out + p0 * pb, d_pk, cnt * pb, hipMemcpyDeviceToHost, w->stream));
+    }
+    return PVW_OK;
+  });
 }
 
 int32_t pvw_wire_unpack(pvw_ctx* c, const uint8_t* in, size_t count, uint64_t* polys) {
@@ -3685,28 +3449,23 @@ int32_t pvw_wire_unpack(pvw_ctx* c, const uint8_t* in, size_t count, uint64_t* p
   if (!count) return PVW_OK;
   PVW_TRY(ensure_device(c));
   const size_t pb = wire_poly_bytes(c), P = c->poly(), chunk = wire_chunk_polys(c, (size_t)256 << 20);
-  Workspace* w;
-  PVW_TRY(ws_acquire(c, &w));
-  const size_t n0 = count < chunk ? count : chunk, cw = up16(n0 * P * 8), cp = up16(n0 * pb);
-  int32_t rc = ws_scratch(w, cw + cp + 16);
-  u64* d_bad = (u64*)((uint8_t*)w->scratch + cw + cp);
-  u64 bad = 0;
-  for (size_t p0 = 0; rc == PVW_OK && p0 < count; p0 += chunk) {
-    const size_t cnt = count - p0 < chunk ? count - p0 : chunk;
-    uint8_t* d_pk = (uint8_t*)w->scratch + cw;
-    u64 nb = 0;
-    if (hipMemcpyAsync(d_pk, in + p0 * pb, cnt * pb, hipMemcpyHostToDevice, w->stream) != hipSuccess ||
-        hipMemsetAsync(d_bad, 0, 8, w->stream) != hipSuccess)
-      rc = fail(PVW_ERR_INTERNAL, "H2D failed");
-    if (rc == PVW_OK) rc = wire_unpack_enqueue(c, d_pk, cnt, (u64*)w->scratch, d_bad, w->stream);
-    if (rc == PVW_OK && (hipMemcpyAsync(polys + p0 * P, w->scratch, cnt * P * 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess ||
-                         hipMemcpyAsync(&nb, d_bad, 8, hipMemcpyDeviceToHost, w->stream) != hipSuccess))
-      rc = fail(PVW_ERR_INTERNAL, "D2H failed");
-    if (hipStreamSynchronize(w->stream) != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, "stream sync failed");
-    bad += nb;
-  }
-  ws_release(c, w);
-  if (rc == PVW_OK && bad) rc = wire_find_reject(c, in, count, 0);
+  const size_t n0 = count < chunk ? count : chunk;
+  Scratch sc(16);
+  const size_t r_w = sc.add(n0 * P * 8), r_pk = sc.add(n0 * pb), r_bad = sc.add(8);
+  u64 bad = 0;                                    // residues >= q_i over all chunks
+  const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    PVW_HIP(hipMemsetAsync(sc.at(r_bad), 0, 8, w->stream));
+    for (size_t p0 = 0; p0 < count; p0 += chunk) {
+      const size_t cnt = count - p0 < chunk ? count - p0 : chunk;
+      PVW_HIP(hipMemcpyAsync(sc.at<uint8_t>(r_pk), in + p0 * pb, cnt * pb, hipMemcpyHostToDevice, w->stream));
+      PVW_TRY(wire_unpack_enqueue(c, sc.at<uint8_t>(r_pk), cnt, sc.at(r_w), sc.at(r_bad), w->stream));
+      PVW_HIP(hipMemcpyAsync(polys + p0 * P, sc.at(r_w), cnt * P * 8, hipMemcpyDeviceToHost, w->stream));
+    }
+    PVW_HIP(hipMemcpyAsync(&bad, sc.at(r_bad), 8, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
+  if (rc == PVW_OK && bad) return wire_find_reject(c, in, count, 0);
   return rc;
 }
 
@@ -3717,7 +3476,7 @@ int32_t pvw_load_pk_wire(pvw_ctx* c, uint32_t lo, uint32_t hi, const uint8_t* bo
   PVW_TRY(wire_device_checks(c));
   PVW_TRY(ensure_device(c));
   PVW_TRY(wire_load_rows(c, &c->dB, c->party_lo, c->party_hi, lo, hi, body, repr, [&]() -> int32_t {
-    c->xm_valid = false; c->pkB_valid = false; c->pk_wide = false;
+    matrix_changed(c, false);
     return ensure_matrix(c, &c->dB, c->rowsB());
   }));
   if (hi > c->num_keys) c->num_keys = hi;                                          // public_key.rs:245-247
@@ -3739,7 +3498,7 @@ int32_t pvw_load_crs_wire(pvw_ctx* c, const uint8_t* body, uint32_t repr) {
   PVW_TRY(wire_device_checks(c));
   PVW_TRY(ensure_device(c));
   PVW_TRY(wire_load_rows(c, &c->dA, c->c1_lo, c->c1_hi, 0, c->k, body, repr, [&]() -> int32_t {
-    c->xm_valid = false; c->pkA_valid = false; c->pk_wide = false;
+    matrix_changed(c, true);
     return ensure_matrix(c, &c->dA, c->rowsA());
   }));
   c->crs_loaded = true;
