@@ -1530,7 +1530,7 @@ static int32_t encrypt_checks(pvw_ctx* c, size_t num_scalars, const pvw_randomne
 // the three polynomial families of one encrypt (encryption.rs:135-154 r, :161-167 e1, :195-196
 // encode + e2) as prologue jobs [3*slot, 3*slot+3) seeded by key `slot` of the batch:
 // r -> r-hat [L][k][l]; NTT(e1) -> c1 rows; NTT(e2) + scalar*g-hat -> c2 rows (the MAC adds onto them)
-static int32_t fill_encrypt_jobs(pvw_ctx* c, PrologueBatch& pb, u32 slot, u32 /*unused*/, const pvw_randomness_t* rnd,
+static int32_t fill_encrypt_jobs(pvw_ctx* c, PrologueBatch& pb, u32 slot, const pvw_randomness_t* rnd,
                                  const u64* d_scalars, u64* rhat, u64* d_c1, u64* d_c2) {
   const u32 k = c->k, l = c->l;
   const size_t P = c->poly();
@@ -1555,6 +1555,13 @@ static int32_t fill_encrypt_jobs(pvw_ctx* c, PrologueBatch& pb, u32 slot, u32 /*
   return PVW_OK;
 }
 
+static bool stream_capturing(hipStream_t s) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  const bool capturing = hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+  (void)hipGetLastError();
+  return capturing;
+}
+
 // all pointers are device pointers; explicit r/e1/e2 are GLOBAL arrays ([k][l], [k][l], [n][l])
 // out_c1 / out_c2 != NULL: the MAC stores its results there (device-visible HOST memory of a caller whose buffers are
 // pinned) while the addends stay in d_c1 / d_c2; NTT-domain output only
@@ -1567,17 +1574,14 @@ static int32_t encrypt_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, c
   if (!out_c1) out_c1 = d_c1;
   if (!out_c2) out_c2 = d_c2;
   if (out_repr == PVW_REPR_POWER && (out_c1 != d_c1 || out_c2 != d_c2)) return fail(PVW_ERR_INTERNAL, "direct output is NTT-domain only");
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  const bool capturing = hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-  (void)hipGetLastError();
   // first call after a matrix change (and no pvw_prepare since): builds the packed copies -- allocates and synchronises
-  const u32 width = ensure_packed(c, s, !capturing);
+  const u32 width = ensure_packed(c, s, !stream_capturing(s));
   PrologueBatch pb{};
-  PVW_TRY(fill_encrypt_jobs(c, pb, 0, 0, rnd, d_scalars, w->rhat, d_c1, d_c2));
+  PVW_TRY(fill_encrypt_jobs(c, pb, 0, rnd, d_scalars, w->rhat, d_c1, d_c2));
   pb.rnd = rs;
   // l <= 16: the addends travel in COMPACT form -- the prologue transforms r only and leaves the sampled e1 / e2 coefficients as
   // they are (8 l bytes per row instead of 8 L l written and read back); the MAC workgroups transform their own rows' e and add
-  // m g-hat (MacSection::e_small, mac_small_addend).  Explicit randomness: the caller's e1 / e2 arrays ARE the compact form.
+  // m g-hat (MacSection::e_small, mac_small_make).  Explicit randomness: the caller's e1 / e2 arrays ARE the compact form.
   // (Round 3 also measured five forms of making r-hat and / or the addends inside the MAC launch instead of in a launch in front
   // of it: none was faster -- profiles/r03_front_ab.txt.)  Tuning build: PVW_MAC_COMPACT=0 the round-2 form (full addends).
   const bool compact = l <= 16 && w->esmall && PVW_ENV_INT("PVW_MAC_COMPACT", 1) != 0;
@@ -1603,7 +1607,7 @@ static int32_t encrypt_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, c
   }
   {
     ProfScope ps(c, "mac_rows", s);
-    MacSection a{width ? c->pkA : c->dA, compact ? nullptr : d_c1, out_c1, rA, 0}, b{width ? c->pkB : c->dB, compact ? nullptr : d_c2, out_c2, rB, 0};
+    MacSection a(width ? c->pkA : c->dA, compact ? nullptr : d_c1, out_c1, rA), b(width ? c->pkB : c->dB, compact ? nullptr : d_c2, out_c2, rB);
     if (compact) {
       a.e_small = es1;
       b.e_small = es2;
@@ -1692,12 +1696,6 @@ static bool multi_uses_gemm(size_t D) {
   const int gemm_min = (int)PVW_ENV_INT("PVW_GEMM_MIN_DEALERS", 3);   // tuning build: read per call (tests switch it); measured at config 3: 2 dealers 0.23 ms on the VALU vs 0.25 here, 4 dealers 0.43 vs 0.26, 6 dealers 0.67 vs 0.31
   return gemm_min > 0 && D >= (size_t)gemm_min;
 }
-static bool stream_capturing(hipStream_t s) {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  const bool capturing = hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-  (void)hipGetLastError();
-  return capturing;
-}
 // A device-pointer multi-dealer call made under stream capture may not allocate or wait: on the matrix cores it needs the
 // MFMA copies and the stream's GEMM buffers that pvw_prepare(PVW_PREPARE_MFMA) builds.  Checked before the stream's workspace
 // is looked up (a first call on a stream would allocate it) and before anything is enqueued, so the capture stays intact.
@@ -1749,7 +1747,7 @@ static int32_t encrypt_multi_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scal
       pvw_randomness_t rnd{};
       rnd.mode = PVW_RND_SEED;
       if (!rs) memcpy(rnd.seed, seeds + d * 32, 32);
-      PVW_TRY(fill_encrypt_jobs(c, pb, 0, 0, &rnd, d_scalars + d * c->n, vh + (size_t)v0 * k * P,
+      PVW_TRY(fill_encrypt_jobs(c, pb, 0, &rnd, d_scalars + d * c->n, vh + (size_t)v0 * k * P,
                                 d_c1 + d * rA * P, d_c2 + d * rB * P));
       if (rs) {
         pb.rnd = rs;                                            // replica x: call_seed(S, counter + d + x)
@@ -1804,7 +1802,7 @@ static int32_t encrypt_multi_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scal
       PVW_HIP(launch_gemm_digits(a, b, w->yd, w->sy, c->dt, k, L, l, nv, (size_t)rA * P, (size_t)rB * P, s, nullptr, fused_e2 ? es.data() : nullptr, c->xm_bytes));
     } else {
       ProfScope ps(c, "mac_rows_multi", s);
-      MacSection a{c->dA, c1g, c1g, rA, 0}, b{c->dB, c2g, c2g, rB, 0};
+      MacSection a(c->dA, c1g, c1g, rA), b(c->dB, c2g, c2g, rB);
       MultiVec mv{vh, (size_t)k * P, (size_t)rA * P, (size_t)rB * P, nv};
       if (rs && last) {
         a.rnd_ctr = &rs->counter;
@@ -3040,7 +3038,7 @@ static int32_t keygen_transposed(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 lo,
       ga.tiled_row0 = p0 - c->party_lo;
       PVW_HIP_AS(PVW_ERR_KEY_GENERATION, launch_gemm_digits(ga, gb, d_yd, d_sy, c->dt, k, L, l, nv, (size_t)k * P, 0, s));
     } else {
-      MacSection sa{d_tt, d_row, d_row, k, 0}, sb{nullptr, nullptr, nullptr, 0, 0};
+      MacSection sa(d_tt, d_row, d_row, k), sb;
       MultiVec mv{vh, (size_t)k * P, (size_t)k * P, 0, nv};
       PVW_HIP_AS(PVW_ERR_KEY_GENERATION, launch_mac_rows_multi(sa, sb, mv, c->dt, k, L, l, s));
       // d_row is [nv][k polys][P] = nv rows of B in API layout -> tile into B

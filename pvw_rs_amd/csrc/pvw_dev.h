@@ -22,3 +22,12 @@ typedef int v16i32 __attribute__((ext_vector_type(16)));
     case 64: { constexpr int E = 64; __VA_ARGS__; } break;   \
     default: return hipErrorInvalidValue;                \
   }
+// ... and the stream width of the packed matrix copy (pvw_mac.hip) of those that unpack with constant shifts
+#define PVW_DISPATCH_PACKED_WIDTH(width, ...)            \
+  switch (width) {                                       \
+    case 40: { constexpr int W = 40; __VA_ARGS__; } break;   \
+    case 48: { constexpr int W = 48; __VA_ARGS__; } break;   \
+    case 56: { constexpr int W = 56; __VA_ARGS__; } break;   \
+    case 61: { constexpr int W = 61; __VA_ARGS__; } break;   \
+    default: return hipErrorInvalidValue;                \
+  }

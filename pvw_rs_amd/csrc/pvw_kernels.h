@@ -84,13 +84,15 @@ struct SampleJob {
 };
 
 // one section of the streamed tiled matrix: out[row] = sum_j M[row][j]*rhat[j] + addend[row]
-// (addend may alias out; NULL = none).  row_blocks is filled in by the launcher.
+// (addend may alias out; NULL = none).  A default-constructed section has no rows.
 struct MacSection {
-  const u64* M;
-  const u64* addend;
-  u64* out;
-  u32 nrows;
-  u32 row_blocks;
+  const u64* M = nullptr;
+  const u64* addend = nullptr;
+  u64* out = nullptr;
+  u32 nrows = 0;
+  u32 row_blocks = 0;   // the launcher's: row blocks of 128 / l rows
+  MacSection() = default;
+  MacSection(const u64* M_, const u64* addend_, u64* out_, u32 nrows_) : M(M_), addend(addend_), out(out_), nrows(nrows_) {}
   // l <= 16: the addend of row i in COMPACT form instead of `addend` -- the l small coefficients of its error polynomial
   // (e_small[i][l], as sampled or as the caller supplied them) and, for c2 rows, the scalar m_i (scalars[i]; NULL: none).
   // The kernel transforms them itself (NTT(e_i) + m_i g-hat for its limb: encryption.rs:161-167, :195-196) -- 8 l + 8

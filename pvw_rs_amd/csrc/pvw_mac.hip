@@ -55,7 +55,7 @@ __device__ __forceinline__ void stamp_end(u32 item) {
 #endif
 }
 
-// what a MAC workgroup needs to know about its output rows; shared by the three streaming kernels
+// what a MAC workgroup needs to know about its output rows; shared by the four kernels
 struct MacItem {
   const u64* M;
   const u64* addend;
@@ -63,6 +63,7 @@ struct MacItem {
   const i64* e_small;      // compact addends (MacSection): small coefficients per row ...
   const u64* scalars;      // ... and the row's scalar
   u32 nrows, rb, limb;
+  bool in_a;
   __device__ __forceinline__ bool has_addend() const { return addend != nullptr || e_small != nullptr; }
 };
 __device__ __forceinline__ MacItem mac_item(const MacSection& sa, const MacSection& sb, u32 item, u32 L) {
@@ -71,6 +72,7 @@ __device__ __forceinline__ MacItem mac_item(const MacSection& sa, const MacSecti
   it.limb = item % L;
   const u32 rbg = item / L;
   const bool in_a = rbg < sa.row_blocks;
+  it.in_a = in_a;
   it.rb = in_a ? rbg : rbg - sa.row_blocks;
   it.M = in_a ? sa.M : sb.M;
   it.addend = in_a ? sa.addend : sb.addend;
@@ -80,19 +82,59 @@ __device__ __forceinline__ MacItem mac_item(const MacSection& sa, const MacSecti
   it.nrows = in_a ? sa.nrows : sb.nrows;
   return it;
 }
-// Wave 0 of a MAC workgroup makes its rows' addends from the compact form (MacSection::e_small / scalars): lane i < R
-// fetches row i's l small coefficients and scalar at the top of the kernel (mac_small_fetch: the loads ride with the first
-// tile loads) and, AFTER its share of the inner products, reduces them mod this workgroup's modulus, transforms them
-// (l-point NTT in registers) and adds m_i g-hat (encryption.rs:161-167, :195-196; encode_scalar parameters.rs:346-367) --
-// ~250 instructions on R lanes -- then the wave redistributes through `adl` (R * ELL words of LDS) and every lane gets its
-// (row rho, slot pair sp) pair.  Bit-identical to what the prologue launch would have written as the addend.  (Doing it at
-// the top instead, before wave 0's first MAC, cost 2.5 us per round of workgroups: the coefficients arrive no earlier than
-// the tiles, and the transform then stands between the tiles and their MACs.)
-template <int ELL>
+// Compact addends (MacSection::e_small / scalars, l <= 16): what lane i < R of wave 0 holds of row i between mac_small_fetch
+// and mac_small_make, and the LDS the wave redistributes the finished addends through.  l > 16 has no compact form: both empty.
+template <int ELL, bool = (ELL <= 16)>
 struct SmallAddend {
   v2u64 e[ELL / 2];
   u64 m;
+  struct Lds { u64 w[128]; };   // R rows x ELL words
 };
+template <int ELL>
+struct SmallAddend<ELL, false> {
+  struct Lds {};
+};
+// The frame of a single-dealer MAC workgroup (256 threads = 4 waves, one (row block, limb) item): which rows and limb it owns,
+// where lane (rho, sp) of wave 0 stores its slot pair, the wave's r-hat slab in LDS, the lane's two lazy accumulators and the
+// addend of its output (requested by mac_addend_request, added by mac_finish).  `limb`, and with it the modulus, is uniform.
+template <int ELL>
+struct MacFrame {
+  static constexpr int HALF = ELL / 2;   // 16-byte slot pairs per polynomial limb
+  static constexpr int R = 128 / ELL;    // rows per tile
+  MacItem it;
+  u32 item, limb, wave, lane, sp, rho, out_row;
+  size_t out_o;
+  const v2u64* rp;                       // r-hat of the limb: [j][slot pair]
+  v2u64* lw;                             // the wave's slab of `slab` 16-byte elements
+  Acc a0, a1;
+  v2u64 add_pf;
+  SmallAddend<ELL> small;
+};
+template <int ELL, bool STAMP>
+__device__ __forceinline__ void mac_frame(MacFrame<ELL>& f, const MacSection& sa, const MacSection& sb, const u64* rhat, u32 k, u32 L,
+                                          v2u64* lds, u32 slab) {
+  f.item = blockIdx.x;
+  stamp_begin<STAMP>(f.item);
+  rnd_advance(sa.rnd_ctr, sa.rnd_adv);                        // randomness state of the encrypt (no MAC kernel reads it)
+  f.it = mac_item(sa, sb, f.item, L);
+  f.limb = f.it.limb;
+  f.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  f.lane = threadIdx.x & 63;
+  f.sp = f.lane % f.HALF;
+  f.rho = f.lane / f.HALF;
+  f.rp = reinterpret_cast<const v2u64*>(rhat + (size_t)f.limb * k * ELL);
+  f.lw = lds + f.wave * slab;
+  f.out_row = f.it.rb * f.R + f.rho;
+  f.out_o = (((size_t)f.out_row * L + f.limb) * ELL) / 2 + f.sp;
+  f.add_pf = (v2u64){0, 0};
+  acc_zero(f.a0);
+  acc_zero(f.a1);
+}
+// Wave 0 of a MAC workgroup makes its rows' addends from the compact form: lane i < R fetches row i's l small coefficients
+// and scalar (mac_small_fetch) and, AFTER its share of the inner products, reduces them mod this workgroup's modulus,
+// transforms them (l-point NTT in registers) and adds m_i g-hat (encryption.rs:161-167, :195-196; encode_scalar
+// parameters.rs:346-367) -- ~250 instructions on R lanes -- then the wave redistributes through `adl` and every lane gets its
+// (row rho, slot pair sp) pair (mac_small_make).  Bit-identical to what the prologue launch would have written as the addend.
 template <int ELL>
 __device__ __forceinline__ void mac_small_fetch(const MacItem& it, u32 lane, SmallAddend<ELL>& sa) {
   constexpr int R = 128 / ELL;
@@ -133,21 +175,46 @@ __device__ __forceinline__ v2u64 mac_small_make(const MacItem& it, const DevTabl
   __builtin_amdgcn_wave_barrier();
   return *reinterpret_cast<const v2u64*>(adl + rho * ELL + 2 * sp);      // (rows past the section's end are never stored)
 }
-// cross-wave sum of the four wave partials, addend, store (wave 0); `lds` holds at least 256 v2u64
-__device__ __forceinline__ void mac_epilogue(v2u64* lds, const v2u64& part, const Mod& m, const MacItem& it, u32 wave, u32 lane,
-                                             u32 out_row, size_t out_o, v2u64 add_pf) {
+// The addend of this lane's output is requested by the wave that will write the result -- the compact form's coefficients, or
+// the 16 bytes of e1 / e2 + m*g that the prologue wrote -- right behind the kernel's first matrix loads, so that it rides with
+// them: at the end it would cost the workgroup one more exposed memory latency.  Only the loads go out here; the compact
+// form's transform waits for mac_finish (at the top, before wave 0's first MAC, it cost 2.5 us per round of workgroups: the
+// coefficients arrive no earlier than the tiles, and the transform then stands between the tiles and their MACs).
+template <int ELL>
+__device__ __forceinline__ void mac_addend_request(MacFrame<ELL>& f) {
+  if (f.wave != 0) return;
+  if constexpr (ELL <= 16) {
+    if (f.it.e_small) {
+      mac_small_fetch<ELL>(f.it, f.lane, f.small);
+      return;
+    }
+  }
+  if (f.it.addend && f.out_row < f.it.nrows) f.add_pf = reinterpret_cast<const v2u64*>(f.it.addend)[f.out_o];
+}
+// the four wave partials cross LDS (`lds` holds at least 256 v2u64) ...
+__device__ __forceinline__ void mac_partials_put(v2u64* lds, const v2u64& part, u32 wave, u32 lane) {
   __syncthreads();  // all waves are done with their r-hat slices
   lds[wave * 64 + lane] = part;
   __syncthreads();
+}
+// ... and a lane of wave 0 adds up its four
+__device__ __forceinline__ v2u64 mac_partials_sum(const v2u64* lds, u32 lane, const Mod& m) {
+  v2u64 s = lds[lane];
+#pragma unroll
+  for (int w = 1; w < 4; ++w) {
+    const v2u64 tq = lds[w * 64 + lane];
+    s.x = addmod(s.x, tq.x, m.q);
+    s.y = addmod(s.y, tq.y, m.q);
+  }
+  return s;
+}
+// cross-wave sum, addend, store (wave 0)
+__device__ __forceinline__ void mac_epilogue(v2u64* lds, const v2u64& part, const Mod& m, const MacItem& it, u32 wave, u32 lane,
+                                             u32 out_row, size_t out_o, v2u64 add_pf) {
+  mac_partials_put(lds, part, wave, lane);
   if (wave == 0) {
     if (out_row < it.nrows) {
-      v2u64 s = lds[lane];
-#pragma unroll
-      for (int w = 1; w < 4; ++w) {
-        const v2u64 tq = lds[w * 64 + lane];
-        s.x = addmod(s.x, tq.x, m.q);
-        s.y = addmod(s.y, tq.y, m.q);
-      }
+      v2u64 s = mac_partials_sum(lds, lane, m);
       if (it.has_addend()) {
         s.x = addmod(s.x, add_pf.x, m.q);
         s.y = addmod(s.y, add_pf.y, m.q);
@@ -155,6 +222,20 @@ __device__ __forceinline__ void mac_epilogue(v2u64* lds, const v2u64& part, cons
       reinterpret_cast<v2u64*>(it.out)[out_o] = s;
     }
   }
+}
+// the tail of a single-dealer MAC workgroup: one Barrett reduction per wave partial ("wavefront-wide": q, ratio are SGPRs),
+// wave 0's compact addend, mac_epilogue
+template <int ELL, bool STAMP>
+__device__ __forceinline__ void mac_finish(MacFrame<ELL>& f, const DevTables& t, v2u64* lds, typename SmallAddend<ELL>::Lds& adl) {
+  const Mod m = t.mods[f.limb];
+  if constexpr (ELL <= 16) {
+    if (f.wave == 0 && f.it.e_small) f.add_pf = mac_small_make<ELL>(f.it, t, m, f.small, f.lane, f.rho, f.sp, adl.w);
+  }
+  v2u64 part;
+  part.x = acc_reduce(f.a0, m);
+  part.y = acc_reduce(f.a1, m);
+  mac_epilogue(lds, part, m, f.it, f.wave, f.lane, f.out_row, f.out_o, f.add_pf);
+  stamp_end<STAMP>(f.item);
 }
 
 // ------------------------------------------------------------------------------------
@@ -167,37 +248,25 @@ __device__ __forceinline__ void mac_epilogue(v2u64* lds, const v2u64& part, cons
 template <int ELL, int U, bool ILV = false, bool STAMP = false>
 __global__ __launch_bounds__(256) void mac_rows_kernel(MacSection sa, MacSection sb, const u64* __restrict__ rhat, DevTables t, u32 k, u32 L) {
   constexpr int NW = 4;
-  constexpr int HALF = ELL / 2;   // 16-byte slot pairs per polynomial limb
-  constexpr int R = 128 / ELL;    // rows per tile
+  constexpr int HALF = ELL / 2;
   constexpr int JC = ELL <= 16 ? 64 : (ELL == 32 ? 32 : 16);  // j per staged r-hat chunk (LDS <= 32 KiB)
   __shared__ v2u64 lds[NW * JC * HALF];
-  __shared__ u64 adl[ELL <= 16 ? 128 : 1];                    // compact addends of the workgroup's rows (mac_small_addend)
+  __shared__ typename SmallAddend<ELL>::Lds adl;
   static_assert(JC * HALF >= 64, "the wave partials reuse the r-hat slabs");
-  const u32 item = blockIdx.x;
-  stamp_begin<STAMP>(item);
-  rnd_advance(sa.rnd_ctr, sa.rnd_adv);                        // randomness state of the encrypt (this kernel does not read it)
-  const MacItem it = mac_item(sa, sb, item, L);
-  const u32 limb = it.limb;
-  const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const u32 sp = lane % HALF, rho = lane / HALF;
+  MacFrame<ELL> f;
+  mac_frame<ELL, STAMP>(f, sa, sb, rhat, k, L, lds, JC * HALF);
+  const u32 wave = f.wave, lane = f.lane, sp = f.sp;
   // ILV: local tile t of a wave is global tile (t / U) * NW*U + wave * U + t % U
   const u32 kq = ILV ? k / NW : (k + NW - 1) / NW;
   const u32 j0 = ILV ? 0 : (wave * kq < k ? wave * kq : k);
   const u32 j1 = ILV ? kq : ((j0 + kq) < k ? (j0 + kq) : k);
   auto gmap = [&](u32 tt) -> u32 { return ILV ? (tt / U) * NW * U + wave * U + tt % U : tt; };
 
-  const v2u64* Mp = reinterpret_cast<const v2u64*>(it.M + ((size_t)it.rb * L + limb) * (size_t)k * 128) + lane;
-  const v2u64* rp = reinterpret_cast<const v2u64*>(rhat + (size_t)limb * k * ELL);
-  v2u64* lw = lds + wave * (JC * HALF);
+  const v2u64* Mp = reinterpret_cast<const v2u64*>(f.it.M + ((size_t)f.it.rb * L + f.limb) * (size_t)k * 128) + lane;
+  const v2u64* rp = f.rp;
+  v2u64* lw = f.lw;
+  Acc &a0 = f.a0, &a1 = f.a1;
 
-  const u32 out_row = it.rb * R + rho;
-  const size_t out_o = (((size_t)out_row * L + limb) * ELL) / 2 + sp;
-  v2u64 add_pf = (v2u64){0, 0};
-  SmallAddend<(ELL <= 16 ? ELL : 2)> small;
-
-  Acc a0, a1;
-  acc_zero(a0);
-  acc_zero(a1);
   for (u32 jc = j0; jc < j1; jc += JC) {
     const u32 cnt = (j1 - jc) < (u32)JC ? (j1 - jc) : (u32)JC;
     auto ld = [&](u32 tile) -> v2u64 { return __builtin_nontemporal_load(Mp + (size_t)gmap(jc + tile) * 64); };
@@ -210,15 +279,7 @@ __global__ __launch_bounds__(256) void mac_rows_kernel(MacSection sa, MacSection
 #pragma unroll
       for (int u = 0; u < U; ++u) x[u] = ld(u);
     }
-    // the addend of this lane's output is made (compact form, l <= 16) or requested (e1 / e2 + m*g written by the prologue) now,
-    // by the wave that will write the result: at the end it would cost the workgroup one more exposed memory latency
-    if (jc == j0 && wave == 0) {
-      bool fetched = false;
-      if constexpr (ELL <= 16) {
-        if (it.e_small) { mac_small_fetch<ELL>(it, lane, small); fetched = true; }
-      }
-      if (!fetched && it.addend && out_row < it.nrows) add_pf = reinterpret_cast<const v2u64*>(it.addend)[out_o];
-    }
+    if (jc == j0) mac_addend_request(f);                       // first trip: behind the first U tile loads
     constexpr int RN = JC * HALF / 64;
     v2u64 rv[RN];
 #pragma unroll
@@ -266,16 +327,7 @@ __global__ __launch_bounds__(256) void mac_rows_kernel(MacSection sa, MacSection
       acc_mac_dev(a1, xv.y, y.y);
     }
   }
-  // one Barrett reduction per wave partial ("wavefront-wide": q, ratio are SGPRs)
-  const Mod m = t.mods[limb];
-  if constexpr (ELL <= 16) {
-    if (wave == 0 && it.e_small) add_pf = mac_small_make<ELL>(it, t, m, small, lane, rho, sp, adl);
-  }
-  v2u64 part;
-  part.x = acc_reduce(a0, m);
-  part.y = acc_reduce(a1, m);
-  mac_epilogue(lds, part, m, it, wave, lane, out_row, out_o, add_pf);
-  stamp_end<STAMP>(item);
+  mac_finish<ELL, STAMP>(f, t, lds, adl);
 }
 
 // ------------------------------------------------------------------------------------
@@ -313,39 +365,24 @@ __device__ __forceinline__ u64 pk_get(const v2u64 (&a)[N], int bit) {
 template <int ELL, bool STAMP = false>
 __global__ __launch_bounds__(256, PVW_PACKED_WPC) void mac_rows_packed61_kernel(MacSection sa, MacSection sb, const u64* __restrict__ rhat,
                                                                                DevTables t, u32 k, u32 L) {
-  constexpr int HALF = ELL / 2, R = 128 / ELL, JC = 64, NW = 4, W = 61;
+  constexpr int HALF = ELL / 2, JC = 64, NW = 4, W = 61;
   static_assert(ELL <= 16, "one period of 64 j per r-hat slab");
   __shared__ v2u64 lds[NW * JC * HALF];
-  __shared__ u64 adl[128];                                    // compact addends of the workgroup's rows (mac_small_addend)
-  const u32 item = blockIdx.x;
-  stamp_begin<STAMP>(item);
-  rnd_advance(sa.rnd_ctr, sa.rnd_adv);                        // randomness state of the encrypt (this kernel does not read it)
-  const MacItem it = mac_item(sa, sb, item, L);
-  const u32 limb = it.limb;
-  const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const u32 sp = lane % HALF, rho = lane / HALF;
+  __shared__ typename SmallAddend<ELL>::Lds adl;
+  MacFrame<ELL> f;
+  mac_frame<ELL, STAMP>(f, sa, sb, rhat, k, L, lds, JC * HALF);
+  const u32 wave = f.wave, lane = f.lane, sp = f.sp;
   const u32 kq = k / NW, periods = kq / 64;                   // the launcher guarantees k % 256 == 0
   const u32 chunks = k / 64 * W;                              // per (row block, limb)
-  const v2u64* Pp = reinterpret_cast<const v2u64*>(it.M) + (((size_t)it.rb * L + limb) * chunks + (size_t)wave * periods * W) * 64 + lane;
-  const v2u64* rp = reinterpret_cast<const v2u64*>(rhat + (size_t)limb * k * ELL) + (size_t)wave * kq * HALF;
-  v2u64* lw = lds + wave * (JC * HALF);
-  const u32 out_row = it.rb * R + rho;
-  const size_t out_o = (((size_t)out_row * L + limb) * ELL) / 2 + sp;
-  v2u64 add_pf = (v2u64){0, 0};
-  Acc a0, a1;
-  acc_zero(a0);
-  acc_zero(a1);
+  const v2u64* Pp = reinterpret_cast<const v2u64*>(f.it.M) + (((size_t)f.it.rb * L + f.limb) * chunks + (size_t)wave * periods * W) * 64 + lane;
+  const v2u64* rp = f.rp + (size_t)wave * kq * HALF;
+  v2u64* lw = f.lw;
+  Acc &a0 = f.a0, &a1 = f.a1;
   auto ldc = [&](u32 c) -> v2u64 { return __builtin_nontemporal_load(Pp + (size_t)c * 64); };
   v2u64 xa[16], xb[16];
 #pragma unroll
   for (int u = 0; u < 16; ++u) xa[u] = ldc(u);                // group 0 of the first period
-  // the addend of this lane's output is made (compact form) or requested (e1 / e2 + m*g written by the prologue) now, by the
-  // wave that will write the result: at the end it would cost the workgroup one more exposed memory latency
-  SmallAddend<ELL> small;
-  if (wave == 0) {
-    if (it.e_small) mac_small_fetch<ELL>(it, lane, small);
-    else if (it.addend && out_row < it.nrows) add_pf = reinterpret_cast<const v2u64*>(it.addend)[out_o];
-  }
+  mac_addend_request(f);
   for (u32 pd = 0; pd < periods; ++pd) {
     const u32 cb = pd * W;
     // this period's r-hat slab: 64 j x HALF sixteen-byte elements, HALF per lane
@@ -383,51 +420,30 @@ __global__ __launch_bounds__(256, PVW_PACKED_WPC) void mac_rows_packed61_kernel(
     group(2, xa, xb);
     group(3, xb, xa);                                          // leaves the next period's group 0 in xa
   }
-  const Mod m = t.mods[limb];
-  if (wave == 0 && it.e_small) add_pf = mac_small_make<ELL>(it, t, m, small, lane, rho, sp, adl);
-  v2u64 part;
-  part.x = acc_reduce(a0, m);
-  part.y = acc_reduce(a1, m);
-  mac_epilogue(lds, part, m, it, wave, lane, out_row, out_o, add_pf);
-  stamp_end<STAMP>(item);
+  mac_finish<ELL, STAMP>(f, t, lds, adl);
 }
 
 template <int ELL, int W, bool STAMP = false>
 __global__ __launch_bounds__(256, PVW_PACKED_WPC) void mac_rows_packedw_kernel(MacSection sa, MacSection sb, const u64* __restrict__ rhat,
                                                                               DevTables t, u32 k, u32 L) {
-  constexpr int HALF = ELL / 2, R = 128 / ELL, JC = 64, NW = 4, CG = W / 4;   // CG chunks per group of 16 j
+  constexpr int HALF = ELL / 2, JC = 64, NW = 4, CG = W / 4;   // CG chunks per group of 16 j
   static_assert(ELL <= 16 && W % 4 == 0 && W < 64, "whole chunks per group");
   __shared__ v2u64 lds[NW * JC * HALF];
-  __shared__ u64 adl[128];                                    // compact addends of the workgroup's rows (mac_small_addend)
-  const u32 item = blockIdx.x;
-  stamp_begin<STAMP>(item);
-  rnd_advance(sa.rnd_ctr, sa.rnd_adv);                        // randomness state of the encrypt (this kernel does not read it)
-  const MacItem it = mac_item(sa, sb, item, L);
-  const u32 limb = it.limb;
-  const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const u32 sp = lane % HALF, rho = lane / HALF;
+  __shared__ typename SmallAddend<ELL>::Lds adl;
+  MacFrame<ELL> f;
+  mac_frame<ELL, STAMP>(f, sa, sb, rhat, k, L, lds, JC * HALF);
+  const u32 wave = f.wave, lane = f.lane, sp = f.sp;
   const u32 kq = k / NW, gw = kq / 16;                        // the launcher guarantees k % 64 == 0: gw groups per wave
   const u32 chunks = k / 16 * CG;                             // per (row block, limb)
-  const v2u64* Pp = reinterpret_cast<const v2u64*>(it.M) + (((size_t)it.rb * L + limb) * chunks + (size_t)wave * gw * CG) * 64 + lane;
-  const v2u64* rp = reinterpret_cast<const v2u64*>(rhat + (size_t)limb * k * ELL) + (size_t)wave * kq * HALF;
-  v2u64* lw = lds + wave * (JC * HALF);
-  const u32 out_row = it.rb * R + rho;
-  const size_t out_o = (((size_t)out_row * L + limb) * ELL) / 2 + sp;
-  v2u64 add_pf = (v2u64){0, 0};
-  Acc a0, a1;
-  acc_zero(a0);
-  acc_zero(a1);
+  const v2u64* Pp = reinterpret_cast<const v2u64*>(f.it.M) + (((size_t)f.it.rb * L + f.limb) * chunks + (size_t)wave * gw * CG) * 64 + lane;
+  const v2u64* rp = f.rp + (size_t)wave * kq * HALF;
+  v2u64* lw = f.lw;
+  Acc &a0 = f.a0, &a1 = f.a1;
   auto ldc = [&](u32 c) -> v2u64 { return __builtin_nontemporal_load(Pp + (size_t)c * 64); };
   v2u64 xa[CG], xb[CG];
 #pragma unroll
   for (int u = 0; u < CG; ++u) xa[u] = ldc(u);                // group 0
-  // the addend of this lane's output is made (compact form) or requested (e1 / e2 + m*g written by the prologue) now, by the
-  // wave that will write the result: at the end it would cost the workgroup one more exposed memory latency
-  SmallAddend<ELL> small;
-  if (wave == 0) {
-    if (it.e_small) mac_small_fetch<ELL>(it, lane, small);
-    else if (it.addend && out_row < it.nrows) add_pf = reinterpret_cast<const v2u64*>(it.addend)[out_o];
-  }
+  mac_addend_request(f);
   // group g of this wave: j = 16 g .. 16 g + 15 of its range = chunks CG g .. CG g + CG - 1, residue i of the group at
   // bit W i.  Every fourth group starts a slab of (up to) 64 j of r-hat: its loads go out first, the next group's
   // chunks behind them, and only then are the slab's elements awaited and written to LDS.
@@ -467,13 +483,7 @@ __global__ __launch_bounds__(256, PVW_PACKED_WPC) void mac_rows_packedw_kernel(M
     group(g, xa, xb);
     if (g + 1 < gw) group(g + 1, xb, xa);
   }
-  const Mod m = t.mods[limb];
-  if (wave == 0 && it.e_small) add_pf = mac_small_make<ELL>(it, t, m, small, lane, rho, sp, adl);
-  v2u64 part;
-  part.x = acc_reduce(a0, m);
-  part.y = acc_reduce(a1, m);
-  mac_epilogue(lds, part, m, it, wave, lane, out_row, out_o, add_pf);
-  stamp_end<STAMP>(item);
+  mac_finish<ELL, STAMP>(f, t, lds, adl);
 }
 
 // tiled matrix -> W-bit packed copy: one thread per (row block, limb, lane) walks its k residue pairs and emits the
@@ -534,15 +544,9 @@ __global__ __launch_bounds__(256) void mac_rows_multi_kernel(MacSection sa, MacS
   __shared__ v2u64 lds[4 * NV * JC * HALF];
   rnd_advance(sa.rnd_ctr, sa.rnd_adv);                        // randomness state of the encrypt (this kernel does not read it)
 
-  const u32 limb = blockIdx.x % L;
-  const u32 rbg = blockIdx.x / L;
-  const bool in_a = rbg < sa.row_blocks;
-  const u32 rb = in_a ? rbg : rbg - sa.row_blocks;
-  const u64* __restrict__ M = in_a ? sa.M : sb.M;
-  const u64* addend = in_a ? sa.addend : sb.addend;
-  u64* out = in_a ? sa.out : sb.out;
-  const u32 nrows = in_a ? sa.nrows : sb.nrows;
-  const size_t ostride = in_a ? mv.out_stride_a : mv.out_stride_b;
+  const MacItem it = mac_item(sa, sb, blockIdx.x, L);
+  const u32 limb = it.limb;
+  const size_t ostride = it.in_a ? mv.out_stride_a : mv.out_stride_b;
 
   const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const u32 sp = lane % HALF, rho = lane / HALF;
@@ -550,7 +554,7 @@ __global__ __launch_bounds__(256) void mac_rows_multi_kernel(MacSection sa, MacS
   const u32 j0 = wave * kq < k ? wave * kq : k;
   const u32 j1 = (j0 + kq) < k ? (j0 + kq) : k;
 
-  const v2u64* Mp = reinterpret_cast<const v2u64*>(M + ((size_t)rb * L + limb) * (size_t)k * 128) + lane;
+  const v2u64* Mp = reinterpret_cast<const v2u64*>(it.M + ((size_t)it.rb * L + limb) * (size_t)k * 128) + lane;
   v2u64* lw = lds + wave * (NV * JC * HALF);
 
   Acc a0[NV], a1[NV];
@@ -597,30 +601,22 @@ __global__ __launch_bounds__(256) void mac_rows_multi_kernel(MacSection sa, MacS
   }
 
   const Mod m = mods[limb];
-  const u32 row = rb * R + rho;
+  const u32 row = it.rb * R + rho;
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
     v2u64 part;
     part.x = acc_reduce(a0[v], m);
     part.y = acc_reduce(a1[v], m);
-    __syncthreads();
-    lds[wave * 64 + lane] = part;
-    __syncthreads();
-    if (wave == 0 && row < nrows && (u32)v < mv.nv) {
-      v2u64 s = lds[lane];
-#pragma unroll
-      for (int w = 1; w < 4; ++w) {
-        v2u64 tq = lds[w * 64 + lane];
-        s.x = addmod(s.x, tq.x, m.q);
-        s.y = addmod(s.y, tq.y, m.q);
-      }
+    mac_partials_put(lds, part, wave, lane);
+    if (wave == 0 && row < it.nrows && (u32)v < mv.nv) {
+      v2u64 s = mac_partials_sum(lds, lane, m);
       const size_t o = ((size_t)v * ostride + ((size_t)row * L + limb) * ELL) / 2 + sp;
-      if (addend) {
-        v2u64 e = reinterpret_cast<const v2u64*>(addend)[o];
+      if (it.addend) {
+        v2u64 e = reinterpret_cast<const v2u64*>(it.addend)[o];
         s.x = addmod(s.x, e.x, m.q);
         s.y = addmod(s.y, e.y, m.q);
       }
-      reinterpret_cast<v2u64*>(out)[o] = s;
+      reinterpret_cast<v2u64*>(it.out)[o] = s;
     }
   }
 }
@@ -708,89 +704,69 @@ static bool mac_grid(MacSection& sa, MacSection& sb, u32 L, u32 ell, u32& blocks
   blocks = (sa.row_blocks + sb.row_blocks) * L;
   return blocks != 0;
 }
+// the one launch of every single-dealer form (kern == nullptr: the geometry has no instance)
+using MacKernel = void (*)(MacSection, MacSection, const u64*, DevTables, u32, u32);
+static hipError_t mac_launch(MacKernel kern, const MacSection& a, const MacSection& b, const u64* rhat, const DevTables& t, u32 k, u32 L,
+                             u32 ell, hipStream_t s) {
+  if (!kern) return hipErrorInvalidValue;
+  MacSection sa = a, sb = b;
+  u32 blocks;
+  if (!mac_grid(sa, sb, L, ell, blocks)) return hipSuccess;
+  kern<<<dim3(blocks), dim3(256), 0, s>>>(sa, sb, rhat, t, k, L);
+  return hipGetLastError();
+}
 
 // PVW_MAC_VARIANT (tuning build only): 0 (default) by shape | 17 the non-interleaved schedule | 40 default + per-workgroup
 // time stamps | 44 (launch_mac_rows_packed) the packed kernel + stamps.  The sweeps that chose the defaults
 // (double-buffered non-temporal loads; the four waves interleave groups of 16 tiles when k allows it: +5 % at l = 16,
 // k = 512, +2 % at n = 16384) are profiles/r01_variant_sweep.txt and r01d_mac_ilv_sweep.txt; the persistent / work-queue,
 // XCD-contiguous, 8- and 16-wave and single-buffer forms they and profiles/r02_mac_rows_timeline.txt closed are gone.
+template <bool STAMP>
+static hipError_t mac_rows_instance(u32 ell, bool ilv, MacKernel& kern) {
+  PVW_DISPATCH_ELL(ell, {
+    constexpr int U = E == 16 ? 16 : 8;                       // tiles in flight per wave of the non-interleaved schedule
+    kern = mac_rows_kernel<E, U>;
+    if constexpr (E <= 16) {
+      if (ilv) kern = mac_rows_kernel<E, 16, true, STAMP>;
+    }
+  });
+  return hipSuccess;
+}
 hipError_t launch_mac_rows(const MacSection& a, const MacSection& b, const u64* rhat, const DevTables& t, u32 k, u32 L, u32 ell,
                            hipStream_t s) {
-  MacSection sa = a, sb = b;
-  u32 blocks;
-  if (!mac_grid(sa, sb, L, ell, blocks)) return hipSuccess;
-  [[maybe_unused]] const int variant = (int)PVW_ENV_INT("PVW_MAC_VARIANT", 0);
-  const dim3 grid(blocks);
-  switch (ell) {
-    case 8:
-    case 16:
-#if PVW_TUNING
-      if (variant == 40 && k % 64 == 0) {
-        if (ell == 8) mac_rows_kernel<8, 16, true, true><<<grid, dim3(256), 0, s>>>(sa, sb, rhat, t, k, L);
-        else mac_rows_kernel<16, 16, true, true><<<grid, dim3(256), 0, s>>>(sa, sb, rhat, t, k, L);
-        break;
-      }
-      if (variant == 17) {
-        if (ell == 8) mac_rows_kernel<8, 8><<<grid, dim3(256), 0, s>>>(sa, sb, rhat, t, k, L);
-        else mac_rows_kernel<16, 16><<<grid, dim3(256), 0, s>>>(sa, sb, rhat, t, k, L);
-        break;
-      }
-#endif
-      if (k % 64 == 0) {
-        if (ell == 8) mac_rows_kernel<8, 16, true><<<grid, dim3(256), 0, s>>>(sa, sb, rhat, t, k, L);
-        else mac_rows_kernel<16, 16, true><<<grid, dim3(256), 0, s>>>(sa, sb, rhat, t, k, L);
-      } else if (ell == 8) {
-        mac_rows_kernel<8, 8><<<grid, dim3(256), 0, s>>>(sa, sb, rhat, t, k, L);
-      } else {
-        mac_rows_kernel<16, 16><<<grid, dim3(256), 0, s>>>(sa, sb, rhat, t, k, L);
-      }
-      break;
-    case 32: mac_rows_kernel<32, 8><<<grid, dim3(256), 0, s>>>(sa, sb, rhat, t, k, L); break;
-    case 64: mac_rows_kernel<64, 8><<<grid, dim3(256), 0, s>>>(sa, sb, rhat, t, k, L); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  const int variant = (int)PVW_ENV_INT("PVW_MAC_VARIANT", 0);
+  const bool ilv = k % 64 == 0 && variant != 17;
+  MacKernel kern = nullptr;
+  const hipError_t e = variant == 40 ? mac_rows_instance<PVW_TUNING != 0>(ell, ilv, kern) : mac_rows_instance<false>(ell, ilv, kern);
+  return e != hipSuccess ? e : mac_launch(kern, a, b, rhat, t, k, L, ell, s);
 }
 
+// the geometries a `width`-bit packed stream exists for (the kernels' static_asserts and "the launcher guarantees" notes)
+static bool packed_ok(u32 width, u32 k, u32 ell) {
+  if (ell > 16) return false;
+  return width == 61 ? k % 256 == 0 : ((width == 40 || width == 48 || width == 56) && k % 64 == 0);
+}
 u32 packed_width(u32 max_q_bits, u32 k, u32 ell) {
-  if (ell > 16 || max_q_bits == 0) return 0;
+  if (max_q_bits == 0) return 0;
   const u32 w = max_q_bits <= 40 ? 40 : (max_q_bits <= 48 ? 48 : (max_q_bits <= 56 ? 56 : (max_q_bits <= 61 ? 61 : 0)));
-  if (w == 0) return 0;
-  if (w == 61) return k % 256 == 0 ? 61 : 0;
-  return k % 64 == 0 ? w : 0;
+  return packed_ok(w, k, ell) ? w : 0;
 }
 
+template <bool STAMP>
+static hipError_t mac_rows_packed_instance(u32 ell, u32 width, MacKernel& kern) {
+  PVW_DISPATCH_ELL(ell, if constexpr (E <= 16) {
+    PVW_DISPATCH_PACKED_WIDTH(width, if constexpr (W == 61) kern = mac_rows_packed61_kernel<E, STAMP>;
+                                     else kern = mac_rows_packedw_kernel<E, W, STAMP>);
+  });
+  return hipSuccess;
+}
 hipError_t launch_mac_rows_packed(const MacSection& a, const MacSection& b, const u64* rhat, const DevTables& t, u32 k, u32 L,
                                   u32 ell, u32 width, hipStream_t s) {
-  if (ell > 16 || width == 0 || (width == 61 ? k % 256 != 0 : (k % 64 != 0 || width % 4 != 0))) return hipErrorInvalidValue;
-  MacSection sa = a, sb = b;
-  u32 blocks;
-  if (!mac_grid(sa, sb, L, ell, blocks)) return hipSuccess;
-  const dim3 grid(blocks);
-#define PVW_PACKEDW(Wv)                                                                                   \
-  do {                                                                                                    \
-    if (stamp) {                                                                                          \
-      if (ell == 8) mac_rows_packedw_kernel<8, Wv, PVW_TUNING != 0><<<grid, dim3(256), 0, s>>>(sa, sb, rhat, t, k, L);   \
-      else mac_rows_packedw_kernel<16, Wv, PVW_TUNING != 0><<<grid, dim3(256), 0, s>>>(sa, sb, rhat, t, k, L);           \
-    } else if (ell == 8) mac_rows_packedw_kernel<8, Wv><<<grid, dim3(256), 0, s>>>(sa, sb, rhat, t, k, L);   \
-    else mac_rows_packedw_kernel<16, Wv><<<grid, dim3(256), 0, s>>>(sa, sb, rhat, t, k, L);                  \
-  } while (0)
-  const bool stamp = PVW_TUNING && PVW_ENV_INT("PVW_MAC_VARIANT", 0) == 44;   // per-workgroup time stamps (tools/mac_timeline.py c3 44)
-  switch (width) {
-    case 61:
-      if (stamp) {
-        if (ell == 8) mac_rows_packed61_kernel<8, PVW_TUNING != 0><<<grid, dim3(256), 0, s>>>(sa, sb, rhat, t, k, L);
-        else mac_rows_packed61_kernel<16, PVW_TUNING != 0><<<grid, dim3(256), 0, s>>>(sa, sb, rhat, t, k, L);
-      } else if (ell == 8) mac_rows_packed61_kernel<8><<<grid, dim3(256), 0, s>>>(sa, sb, rhat, t, k, L);
-      else mac_rows_packed61_kernel<16><<<grid, dim3(256), 0, s>>>(sa, sb, rhat, t, k, L);
-      break;
-    case 56: PVW_PACKEDW(56); break;
-    case 48: PVW_PACKEDW(48); break;
-    case 40: PVW_PACKEDW(40); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef PVW_PACKEDW
-  return hipGetLastError();
+  if (!packed_ok(width, k, ell)) return hipErrorInvalidValue;
+  const bool stamp = PVW_ENV_INT("PVW_MAC_VARIANT", 0) == 44;   // per-workgroup time stamps (tools/mac_timeline.py c3 44)
+  MacKernel kern = nullptr;
+  const hipError_t e = stamp ? mac_rows_packed_instance<PVW_TUNING != 0>(ell, width, kern) : mac_rows_packed_instance<false>(ell, width, kern);
+  return e != hipSuccess ? e : mac_launch(kern, a, b, rhat, t, k, L, ell, s);
 }
 
 hipError_t launch_pack(const u64* M, u64* P, u32 rows, u32 k, u32 L, u32 ell, u32 width, u32* wide_flag, hipStream_t s) {
@@ -799,24 +775,15 @@ hipError_t launch_pack(const u64* M, u64* P, u32 rows, u32 k, u32 L, u32 ell, u3
   const u32 R = 128 / ell;
   const size_t items = (size_t)((rows + R - 1) / R) * L;
   const dim3 grid((u32)((items * 64 + 255) / 256)), blk(256);
-  switch (width) {
-    case 61: pack_kernel<61><<<grid, blk, 0, s>>>(M, P, k, items, wide_flag); break;
-    case 56: pack_kernel<56><<<grid, blk, 0, s>>>(M, P, k, items, wide_flag); break;
-    case 48: pack_kernel<48><<<grid, blk, 0, s>>>(M, P, k, items, wide_flag); break;
-    case 40: pack_kernel<40><<<grid, blk, 0, s>>>(M, P, k, items, wide_flag); break;
-    default: return hipErrorInvalidValue;
-  }
+  PVW_DISPATCH_PACKED_WIDTH(width, pack_kernel<W><<<grid, blk, 0, s>>>(M, P, k, items, wide_flag));
   return hipGetLastError();
 }
 
 hipError_t launch_mac_rows_multi(const MacSection& a, const MacSection& b, const MultiVec& mv,
                                  const DevTables& t, u32 k, u32 L, u32 ell, hipStream_t s) {
-  const u32 R = 128 / ell;
   MacSection sa = a, sb = b;
-  sa.row_blocks = (sa.nrows + R - 1) / R;
-  sb.row_blocks = (sb.nrows + R - 1) / R;
-  const u32 blocks = (sa.row_blocks + sb.row_blocks) * L;
-  if (blocks == 0 || mv.nv == 0) return hipSuccess;
+  u32 blocks;
+  if (!mac_grid(sa, sb, L, ell, blocks) || mv.nv == 0) return hipSuccess;
   if (mv.nv > 4) return hipErrorInvalidValue;
   if (mv.nv <= 2) {
     PVW_DISPATCH_ELL(ell, mac_rows_multi_kernel<E, 2><<<dim3(blocks), dim3(256), 0, s>>>(sa, sb, mv, t.mods, k, L));
