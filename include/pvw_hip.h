@@ -386,6 +386,67 @@ PVW_API int32_t pvw_decode_checked_host(const pvw_ctx* ctx, const uint64_t* nois
 PVW_API int32_t pvw_selftest_decode_checked(const pvw_ctx* ctx, const uint64_t* noisy, size_t count, uint64_t* out_u64,
                                             uint64_t* noise, uint32_t* status);
 
+/* ---- sums of dealers' ciphertexts: the scheme is additively homomorphic, so the component-wise sum of the valid
+ * dealers' ciphertexts is a ciphertext of the sum of their shares under the same keys -- the step examples/pvw.rs:138-170 and
+ * examples/pvw_valid_dec.rs:150-209 take on decrypted shares (party i's result is the sum over the valid dealers), taken
+ * before the decrypt.  Nobody needs a key to fold; a party then needs one inner product and one decode instead of D.
+ *   c1_out[j] = sum_{d valid} c1s[d][j],  c2_out[r - row_lo] = sum_{d valid} c2s[d][r]  (r in [row_lo, row_hi)), word by word mod q_i.
+ * c1s [D][k][L][l]; c2s [D][n][L][l] (whole ciphertexts, global party rows: rows [row_lo, row_hi) are read and no other);
+ * valid: uint8_t[D], dealer d is summed when valid[d] != 0, NULL = every dealer; *count (may be NULL) = dealers summed.
+ * Element-wise, so PVW_REPR_POWER and PVW_REPR_NTT alike: all inputs in one representation, the output in the same (the call
+ * does not transform).  Residue words as everywhere: any 64-bit input word, every output word below q_i.
+ * Argument errors (InvalidParameters for NULL, D = 0, D >= 2^32, an empty row range, row_hi > n) come before any device work.
+ * The noise of the result is the sum of the dealers' noises: pvw_ctx_sum_capacity says for how many dealers the decode is
+ * PROVEN exact; no sum entry point refuses on noise grounds -- the checked decode of the aggregate reports its exact noise. */
+/* device pointers, asynchronous on `stream`; d_valid is read when the kernel runs (a captured call replays with the mask of the
+ * moment).  An all-zero mask writes zeros and *d_count = 0.  After pvw_prepare(PVW_PREPARE_SUM) on the stream the call neither
+ * allocates nor synchronises; under stream capture without it: PVW_ERR_INVALID_PARAMETERS naming pvw_prepare, nothing enqueued. */
+PVW_API int32_t pvw_ct_sum_device(pvw_ctx* ctx, const uint64_t* d_c1s, const uint64_t* d_c2s, size_t num_dealers,
+                                  const uint8_t* d_valid, uint32_t row_lo, uint32_t row_hi, uint64_t* d_c1_out, uint64_t* d_c2_out,
+                                  uint32_t* d_count, void* stream);
+/* host buffers (synchronous): only the valid dealers are staged, in bounded pieces.  No valid dealer: PVW_ERR_INSUFFICIENT_DATA
+ * before any device work. */
+PVW_API int32_t pvw_ct_sum(pvw_ctx* ctx, const uint64_t* c1s, const uint64_t* c2s, size_t num_dealers, const uint8_t* valid,
+                           uint32_t row_lo, uint32_t row_hi, uint64_t* c1_out, uint64_t* c2_out, uint32_t* count);
+/* the same function in plain loops on the host cores (no GPU needed): what the device kernels are tested against */
+PVW_API int32_t pvw_ct_sum_host(const pvw_ctx* ctx, const uint64_t* c1s, const uint64_t* c2s, size_t num_dealers,
+                                const uint8_t* valid, uint32_t row_lo, uint32_t row_hi, uint64_t* c1_out, uint64_t* c2_out,
+                                uint32_t* count);
+/* One party's aggregate share: the sum over (c1, the party's column c2col [D][L][l]) of the valid dealers, then the decrypt of
+ * that ONE ciphertext (decryption.rs:257-274) and its checked decode (contract unchanged): out[1], noise[1] = the
+ * exact max residual of the aggregate, status[1] = PVW_DEC_LOSSY when the sum of the plaintexts is not representable
+ * (>= 2^64 or negative).  noise / status / count may be NULL.  d_noisy [L][l] (power basis) is an optional output (NULL: kept
+ * in scratch and cleared).  in_repr POWER or NTT (the sum is transformed in scratch; the caller's buffers are only read).
+ * Key hygiene as pvw_decrypt_batch*.  The device forms follow pvw_ct_sum_device's rules on pvw_prepare and stream capture. */
+PVW_API int32_t pvw_decrypt_sum_checked_device(pvw_ctx* ctx, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col,
+                                               size_t num_dealers, const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy,
+                                               uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count,
+                                               void* stream);
+/* with a resident key (pvw_sk_load) */
+PVW_API int32_t pvw_decrypt_sum_device_sk_checked(pvw_ctx* ctx, const pvw_sk* key, const uint64_t* d_c1s, const uint64_t* d_c2col,
+                                                  size_t num_dealers, const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy,
+                                                  uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count,
+                                                  void* stream);
+/* host buffers; no valid dealer: PVW_ERR_INSUFFICIENT_DATA before any device work */
+PVW_API int32_t pvw_decrypt_sum_checked(pvw_ctx* ctx, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col,
+                                        size_t num_dealers, const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64,
+                                        uint64_t* noise, uint32_t* status, uint32_t* count);
+/* Every party of [party_lo, party_hi) decrypts its aggregate share: the sum over c1 and rows [party_lo, party_hi) of c2, then
+ * pvw_decrypt_all_checked's machinery on that ONE ciphertext.  sk [P][k][l]; c1s [D][k][L][l]; c2s [D][n][L][l]; out / noise /
+ * status [P].  Argument rules of pvw_decrypt_all plus those of pvw_ct_sum. */
+PVW_API int32_t pvw_decrypt_all_sum_checked(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* sk,
+                                            const uint64_t* c1s, const uint64_t* c2s, size_t num_dealers, const uint8_t* valid,
+                                            uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status, uint32_t* count);
+PVW_API int32_t pvw_decrypt_all_sum_checked_device(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* d_sk,
+                                                   const uint64_t* d_c1s, const uint64_t* d_c2s, size_t num_dealers,
+                                                   const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise,
+                                                   uint32_t* d_status, uint32_t* d_count, void* stream);
+/* Advisory, host only: *max_dealers = floor(R / noise_bound) (saturated to u64), R the largest integer with
+ * R (Delta^(l-1) + 1) < Q / 2.  max_i |noise_i| <= R is SUFFICIENT for the gadget decode to be exact (every intermediate of
+ * decryption.rs:10-58 stays below Q/2 in magnitude); it is not necessary, and honest noise is far below pvw_ctx_noise_bound.
+ * The reference's gate (parameters.rs:510-551) is not a decoding radius and promises nothing about an aggregate. */
+PVW_API int32_t pvw_ctx_sum_capacity(const pvw_ctx* ctx, uint64_t* max_dealers);
+
 /* decode_scalar_pvw_rns alone, on the device: noisy [D][L][l] power basis (host) -> out_u64 [D] */
 PVW_API int32_t pvw_decode(pvw_ctx* ctx, const uint64_t* noisy, size_t count, uint64_t* out_u64);
 /* the same with host big integers on the host cores (no GPU needed): an independent
@@ -474,11 +535,14 @@ PVW_API int32_t pvw_ctx_derived_bytes(const pvw_ctx* ctx, uint64_t* packed_bytes
  *                       61 bits); skipped -- not an error -- when the geometry does not qualify or memory is short
  *                       (pvw_ctx_packed_active tells; the tiled matrices are streamed then, and the allocation is
  *                       retried by later encrypts every so often);
- *   PVW_PREPARE_MFMA    the MFMA-tiled copies and digit buffers of multi-dealer encrypt (encryption.rs:253-286).
+ *   PVW_PREPARE_MFMA    the MFMA-tiled copies and digit buffers of multi-dealer encrypt (encryption.rs:253-286);
+ *   PVW_PREPARE_SUM     the scratch of the pvw_ct_sum_device / pvw_decrypt_sum_* / pvw_decrypt_all_sum_checked_device calls (the
+ *                       slice sums, the summed ciphertext, and the decrypt scratch for the context's own party range); needs
+ *                       no CRS and builds no copy.
  * It allocates, waits for the builds, and returns the bytes it allocated for the copies in *bytes_out (may be NULL).
  * Any later pvw_load_crs* / pvw_load_pk* / pvw_keygen / pvw_*_generate / fill invalidates the copies of the matrix it
  * touched; call pvw_prepare again (only that matrix's copies are rebuilt; nothing is reallocated). */
-enum { PVW_PREPARE_PACKED = 1, PVW_PREPARE_MFMA = 2 };
+enum { PVW_PREPARE_PACKED = 1, PVW_PREPARE_MFMA = 2, PVW_PREPARE_SUM = 4 };
 PVW_API int32_t pvw_prepare(pvw_ctx* ctx, uint32_t flags, void* stream, uint64_t* bytes_out);
 /* the stream single-dealer encrypt would use right now: *width_out = bits per residue of the valid packed copies,
  * 0 = the tiled matrices (copies not built, invalidated, geometry not eligible, or no room) */

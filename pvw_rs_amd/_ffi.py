@@ -22,7 +22,7 @@ ERROR_NAMES = {
 REPR_POWER, REPR_NTT = 0, 1
 RND_SEED, RND_EXPLICIT = 0, 1
 DOM_R, DOM_E1, DOM_E2, DOM_SK, DOM_EKEY, DOM_CRS, DOM_GAUSS, DOM_PK, DOM_CALL = range(9)
-PREPARE_PACKED, PREPARE_MFMA = 1, 2
+PREPARE_PACKED, PREPARE_MFMA, PREPARE_SUM = 1, 2, 4
 WIRE_PARAMS, WIRE_CRS, WIRE_PK, WIRE_CT, WIRE_SK = 1, 2, 3, 4, 5     # wire format v1 kinds
 
 
@@ -102,6 +102,15 @@ _SIGNATURES = {
     "pvw_decode_checked_host": [_P, _P, C.c_size_t, _P, _P, _P],
     "pvw_selftest_decode_checked": [_P, _P, C.c_size_t, _P, _P, _P],
     "pvw_ctx_noise_bound": [_P, C.POINTER(C.c_uint64)],
+    "pvw_ct_sum_device": [_P, _P, _P, C.c_size_t, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P],
+    "pvw_ct_sum": [_P, _P, _P, C.c_size_t, _P, C.c_uint32, C.c_uint32, _P, _P, _P],
+    "pvw_ct_sum_host": [_P, _P, _P, C.c_size_t, _P, C.c_uint32, C.c_uint32, _P, _P, _P],
+    "pvw_decrypt_sum_checked_device": [_P, _P, _P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, _P, _P, _P, _P],
+    "pvw_decrypt_sum_device_sk_checked": [_P, _P, _P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, _P, _P, _P, _P],
+    "pvw_decrypt_sum_checked": [_P, _P, _P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, _P, _P],
+    "pvw_decrypt_all_sum_checked": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, _P, _P],
+    "pvw_decrypt_all_sum_checked_device": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, _P, _P, _P],
+    "pvw_ctx_sum_capacity": [_P, C.POINTER(C.c_uint64)],
     "pvw_decode": [_P, _P, C.c_size_t, _P],
     "pvw_decode_host": [_P, _P, C.c_size_t, _P],
     "pvw_decode_device": [_P, _P, C.c_size_t, _P, _P],

@@ -223,6 +223,14 @@ class PvwParameters:
         self._call("pvw_ctx_noise_bound", C.byref(v))
         return int(v.value)
 
+    def sum_capacity(self) -> int:
+        """pvw_ctx_sum_capacity: the number of dealers' ciphertexts, each at noise_bound(), whose sum is PROVEN to decode exactly
+        (floor(R / noise_bound()), R (Delta^(l-1) + 1) < Q / 2).  Advisory and sufficient only: honest noise is far below
+        noise_bound(), and the checked decode of an aggregate reports its exact noise."""
+        v = C.c_uint64()
+        self._call("pvw_ctx_sum_capacity", C.byref(v))
+        return int(v.value)
+
     @staticmethod
     def suggest_error_bounds(n, k, l, moduli, variance) -> Tuple[int, int]:   # :554-603
         m = _u64(list(moduli))
@@ -999,6 +1007,91 @@ def decrypt_all_party_shares_checked(all_ciphertexts: Sequence[PvwCiphertext], p
     return decrypt_many_checked(all_ciphertexts, [party.secret_key for party in parties], lo, bound)
 
 
+# ---- sums of dealers' ciphertexts ----
+def _sum_inputs(cts: Sequence[PvwCiphertext], valid):
+    """the checks every sum shares: (params, repr, valid as uint8 [D] or None)"""
+    if len(cts) == 0:
+        raise PvwError(1, "No ciphertexts provided")
+    p, repr = cts[0].params, cts[0].repr
+    shape1, shape2 = (p.k, p.L, p.l), (p.n, p.L, p.l)
+    for d, ct in enumerate(cts):
+        if ct.params is not p and (ct.params.n, ct.params.k, ct.params.l, list(ct.params.moduli())) != (p.n, p.k, p.l, list(p.moduli())):
+            raise PvwError(15, f"Ciphertext {d} belongs to other parameters")
+        if np.shape(ct.c1) != shape1 or np.shape(ct.c2) != shape2:
+            raise PvwError(15, f"Ciphertext {d}: expected c1 {shape1} and c2 {shape2}, got {np.shape(ct.c1)} and {np.shape(ct.c2)}")
+        if ct.repr != repr:
+            raise PvwError(15, f"Ciphertext {d} is in representation {ct.repr}, ciphertext 0 in {repr}")
+    v = None
+    if valid is not None:
+        v = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+        if v.shape != (len(cts),):
+            raise PvwError(15, f"valid: expected {len(cts)} flags, got {v.size}")
+    if v is not None and not v.any():
+        raise PvwError(17, f"No valid dealer among the {len(cts)} ciphertexts: expected at least 1, got 0")
+    return p, repr, v
+
+
+def aggregate_ciphertexts(cts: Sequence[PvwCiphertext], valid=None, *, host: bool = False) -> PvwCiphertext:
+    """The sum of the valid dealers' ciphertexts (pvw_ct_sum): a ciphertext of the sum of their shares under the same keys,
+    in the same representation; no key is needed.  valid: one flag per ciphertext (None = all).  host=True computes it on
+    the host cores (pvw_ct_sum_host, no GPU).  Its noise is the sum of the dealers' noises (PvwParameters.sum_capacity)."""
+    p, repr, v = _sum_inputs(cts, valid)
+    c1s = np.ascontiguousarray(np.stack([ct.c1 for ct in cts]), dtype=np.uint64)
+    c2s = np.ascontiguousarray(np.stack([ct.c2 for ct in cts]), dtype=np.uint64)
+    c1 = np.zeros((p.k, p.L, p.l), dtype=np.uint64)
+    c2 = np.zeros((p.n, p.L, p.l), dtype=np.uint64)
+    p._call("pvw_ct_sum_host" if host else "pvw_ct_sum", _ptr(c1s), _ptr(c2s), len(cts), _ptr(v), 0, p.n, _ptr(c1), _ptr(c2), None)
+    return PvwCiphertext(c1, c2, p, repr)
+
+
+def _sum_bound(p, bound, count: int) -> int:
+    return _bound(p, count * p.noise_bound() if bound is None else bound)
+
+
+def decrypt_party_sum(cts: Sequence[PvwCiphertext], secret_key: SecretKey, party_index: int, valid=None,
+                      bound: Optional[int] = None) -> CheckedDecryption:
+    """Party party_index's aggregate share -- the sum of its shares from the valid dealers (examples/pvw_valid_dec.rs:201-209)
+    -- from ONE decrypt of the summed ciphertext (pvw_decrypt_sum_checked).  Arrays of shape [1]; bound defaults to
+    count * noise_bound()."""
+    p, repr, v = _sum_inputs(cts, valid)
+    if not 0 <= party_index < p.n:
+        raise PvwError(1, f"Party index {party_index} exceeds maximum {p.n - 1}")
+    c1s = np.ascontiguousarray(np.stack([ct.c1 for ct in cts]), dtype=np.uint64)
+    c2col = np.ascontiguousarray(np.stack([ct.c2[party_index] for ct in cts]), dtype=np.uint64)
+    sk = _i64(secret_key.secret_coeffs)
+    out, noise, status, count = np.zeros(1, np.uint64), np.zeros(1, np.uint64), np.zeros(1, np.uint32), C.c_uint32()
+    p._call("pvw_decrypt_sum_checked", _ptr(sk), _ptr(c1s), _ptr(c2col), len(cts), _ptr(v), repr, _ptr(out), _ptr(noise),
+            _ptr(status), C.byref(count))
+    return CheckedDecryption(out, noise, status, _sum_bound(p, bound, count.value))
+
+
+def decrypt_all_party_sums(cts: Sequence[PvwCiphertext], parties: Sequence["Party"], valid=None,
+                           bound: Optional[int] = None) -> CheckedDecryption:
+    """Every party's aggregate share in one call (pvw_decrypt_all_sum_checked): arrays of shape [len(parties)].  The parties
+    must have consecutive indices; bound defaults to count * noise_bound()."""
+    p, repr, v = _sum_inputs(cts, valid)
+    count = int(v.sum()) if v is not None else len(cts)
+    b = _sum_bound(p, bound, count)
+    if len(parties) == 0:
+        return CheckedDecryption(np.zeros(0, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.uint32), b)
+    lo = parties[0].index
+    for i, party in enumerate(parties):
+        if party.index >= p.n:
+            raise PvwError(1, f"Party index {party.index} exceeds maximum {p.n - 1}")
+        if party.index != lo + i:
+            raise PvwError(1, f"Party indices must be consecutive: {party.index} follows {lo + i - 1}")
+    c1s = np.ascontiguousarray(np.stack([ct.c1 for ct in cts]), dtype=np.uint64)
+    c2s = np.ascontiguousarray(np.stack([ct.c2 for ct in cts]), dtype=np.uint64)
+    sk = np.ascontiguousarray(np.stack([_i64(party.secret_key.secret_coeffs) for party in parties]))
+    out, noise, status = np.zeros(len(parties), np.uint64), np.zeros(len(parties), np.uint64), np.zeros(len(parties), np.uint32)
+    try:
+        p._call("pvw_decrypt_all_sum_checked", lo, lo + len(parties), _ptr(sk), _ptr(c1s), _ptr(c2s), len(cts), _ptr(v), repr,
+                _ptr(out), _ptr(noise), _ptr(status), None)
+    finally:
+        sk.fill(0)                                                         # the stacked copy of the keys (secret_key.rs:20-30)
+    return CheckedDecryption(out, noise, status, b)
+
+
 def _dptr(x):
     """a device buffer: a torch tensor (its data_ptr()), a raw address as an int, or None"""
     if x is None:
@@ -1030,6 +1123,17 @@ class DeviceSecretKey:
             raise PvwError(1, "the DeviceSecretKey has been freed")
         self.params._call("pvw_decrypt_batch_device_sk_checked", self._h, _dptr(d_c1s), _dptr(d_c2col), int(num_dealers),
                           in_repr, _dptr(d_noisy), _dptr(d_out), _dptr(d_noise), _dptr(d_status), _stream_ptr(stream))
+
+    def decrypt_sum_device_checked(self, d_c1s, d_c2col, num_dealers: int, d_out, d_valid=None, d_noisy=None, d_noise=None,
+                                   d_status=None, d_count=None, stream=None, in_repr: int = REPR_NTT) -> None:
+        """pvw_decrypt_sum_device_sk_checked: this party's aggregate share from ONE decrypt of the sum of the valid dealers'
+        ciphertexts.  Device buffers: d_valid uint8 [D] (None = all), d_out / d_noise / d_status [1], d_count uint32 [1];
+        asynchronous on `stream`."""
+        if not self._h:
+            raise PvwError(1, "the DeviceSecretKey has been freed")
+        self.params._call("pvw_decrypt_sum_device_sk_checked", self._h, _dptr(d_c1s), _dptr(d_c2col), int(num_dealers),
+                          _dptr(d_valid), in_repr, _dptr(d_noisy), _dptr(d_out), _dptr(d_noise), _dptr(d_status), _dptr(d_count),
+                          _stream_ptr(stream))
 
     def __enter__(self):
         return self

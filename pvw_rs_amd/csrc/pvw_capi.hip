@@ -121,6 +121,8 @@ struct Workspace {
   i64* esmall = nullptr;     // [rowsA + rowsB][l] sampled e1 | e2 coefficients of one encrypt (compact addends, l <= 16)
   u64* dpart = nullptr;      // range sums of a split decrypt_mac [nsplit][dealers][L][l]
   size_t dpart_bytes = 0;
+  u64* sumbuf = nullptr;     // ciphertext sums (sum_layout): slice sums | summed c1 | summed c2 rows | noisy | results
+  size_t sumbuf_bytes = 0;
   u64* scalars = nullptr;    // [n]
   u64* c1 = nullptr;         // [rowsA][L][l]
   u64* c2 = nullptr;         // [rowsB][L][l]
@@ -536,6 +538,8 @@ static void ws_free(Workspace* w) {
   hipFree(w->rhat);
   hipFree(w->esmall);
   hipFree(w->dpart);
+  if (w->sumbuf) hipMemset(w->sumbuf, 0, w->sumbuf_bytes);   // may hold the noisy polynomial of the last aggregate decrypt
+  hipFree(w->sumbuf);
   hipFree(w->scalars);
   hipFree(w->c1);
   hipFree(w->c2);
@@ -648,6 +652,7 @@ static int32_t host_call(pvw_ctx* c, Body&& body) {
 // checked against stream capture before the workspace is looked up
 static hipStream_t call_stream(const pvw_ctx* c, void* stream) { return stream ? (hipStream_t)stream : c->stream; }
 static int32_t multi_capture_check(pvw_ctx* c, hipStream_t s, size_t D);
+static int32_t sum_prepare(pvw_ctx* c, Workspace* w, hipStream_t s);
 static int32_t device_ws(pvw_ctx* c, void* stream, hipStream_t* s, Workspace** w, size_t dealers = 0) {
   *s = call_stream(c, stream);
   if (dealers) PVW_TRY(multi_capture_check(c, *s, dealers));
@@ -1067,13 +1072,14 @@ static u32 ensure_packed(pvw_ctx* c, hipStream_t s, bool may_build = true, size_
 // mutators take &mut self, public_key.rs:214-263: a change and a use never overlap).
 int32_t pvw_prepare(pvw_ctx* c, uint32_t flags, void* stream, uint64_t* bytes_out) {
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL context");
-  if (flags & ~(uint32_t)(PVW_PREPARE_PACKED | PVW_PREPARE_MFMA)) return fail(PVW_ERR_INVALID_PARAMETERS, "unknown prepare flag");
+  if (flags & ~(uint32_t)(PVW_PREPARE_PACKED | PVW_PREPARE_MFMA | PVW_PREPARE_SUM)) return fail(PVW_ERR_INVALID_PARAMETERS, "unknown prepare flag");
   PVW_TRY(ensure_device(c));
-  if (!c->crs_loaded) return fail(PVW_ERR_CRS, "CRS not loaded");
+  if (!c->crs_loaded && flags != PVW_PREPARE_SUM) return fail(PVW_ERR_CRS, "CRS not loaded");   // the sums read no matrix
   hipStream_t s;
   Workspace* w;
   PVW_TRY(device_ws(c, stream, &s, &w));
   size_t taken = 0;
+  if (flags & PVW_PREPARE_SUM) PVW_TRY(sum_prepare(c, w, s));
   if (flags & PVW_PREPARE_PACKED) (void)ensure_packed(c, s, true, &taken);       // 0 = does not qualify / no room: pvw_ctx_packed_active tells
   if (flags & PVW_PREPARE_MFMA) {
     const bool had_a = c->xmA != nullptr, had_b = c->xmB != nullptr;
@@ -2671,7 +2677,7 @@ static int32_t decrypt_all_checks(pvw_ctx* c, u32 lo, u32 hi, const void* sk, co
 // noise / status (either may be NULL, same side as out): the checked decode's report, [P][D] like out
 static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, u32 hi, const int64_t* sk, const u64* c1s,
                                const u64* c2s, size_t D, uint32_t in_repr, u64* out, bool host, u64* noise = nullptr,
-                               u32* status = nullptr) {
+                               u32* status = nullptr, size_t* need_only = nullptr) {
   const u32 k = c->k, l = c->l, L = c->L;
   const size_t P = c->poly(), NP = (size_t)hi - lo;
   const size_t ctw = (size_t)k * P;                      // words of one dealer's c1
@@ -2690,6 +2696,7 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
     const size_t r_sk = sc.add(host ? NP * k * l * 8 : 0), r_c1 = sc.add(stage ? Dc * ctw * 8 : 0), r_c2 = sc.add(Dc * P * 8),
                  r_nz = sc.add(Dc * P * 8), r_out = sc.add(host ? Dc * 8 : 0), r_ns = sc.add(host && noise ? Dc * 8 : 0),
                  r_st = sc.add(host && status ? Dc * 4 : 0);
+    if (need_only) { *need_only = sc.total; return PVW_OK; }   // the scratch this call would take, nothing else
     PVW_TRY(sc.take(w));
     i64* d_sk = sc.at<i64>(r_sk);
     u64 *d_c1 = sc.at(r_c1), *d_c2 = sc.at(r_c2), *d_nz = sc.at(r_nz), *d_out = sc.at(r_out), *d_ns = sc.at(r_ns);
@@ -2750,6 +2757,7 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
   const size_t r_xm = sc.add(xm_words((u32)Pc, k, L, l) * 8), r_tmp = sc.add(nbg * gemm_tmp_words((u32)Pc, L, l) * 8);
   const size_t r_c2 = sc.add(stage ? Dg * Pc * P * 8 : 0), r_nz = sc.add(Dg * Pc * P * 8), r_out = sc.add(Dg * Pc * 8);
   const size_t r_ns = sc.add(noise ? Dg * Pc * 8 : 0), r_st = sc.add(status ? Dg * Pc * 4 : 0);
+  if (need_only) { *need_only = sc.total; return PVW_OK; }
   PVW_TRY(sc.take(w));
   u64 *d_c1 = sc.at(r_c1), *d_rows = sc.at(r_rows), *d_xm = sc.at(r_xm), *d_tmp = sc.at(r_tmp), *d_c2 = sc.at(r_c2), *d_nz = sc.at(r_nz),
       *d_out = sc.at(r_out), *d_ns = sc.at(r_ns);
@@ -2844,6 +2852,389 @@ int32_t pvw_decrypt_all_checked_device(pvw_ctx* c, uint32_t lo, uint32_t hi, con
 int32_t pvw_decrypt_all_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
                                const uint64_t* d_c2s, size_t D, uint32_t in_repr, uint64_t* d_out, void* stream) {
   return pvw_decrypt_all_checked_device(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out, nullptr, nullptr, stream);
+}
+
+// ------------------------------------------------------------------------ sums of dealers' ciphertexts
+// The scheme is additively homomorphic: (sum_d c1_d, sum_d c2_d) over the valid dealers is a ciphertext of sum_d m_d under the
+// same keys, so the per-party sum of shares that examples/pvw.rs:138-170 and examples/pvw_valid_dec.rs:150-209 take after D
+// decrypts is one streaming pass over the ciphertexts (launch_ct_sum) and ONE decrypt.
+// Workspace::sumbuf, fixed by the context's geometry (byte offsets): the slice sums of the split kernel form | the summed c1
+// [k] | the summed c2 rows [n] (row r at its global position; directly behind c1, so c1 and row 0 are one run of k + 1
+// polynomials) | the noisy polynomial of a single aggregate decrypt | out [n], noise [n], status [n] of the host-buffer calls.
+struct SumLayout { size_t c1, c2, noisy, io, total; };
+static SumLayout sum_layout(const pvw_ctx* c) {
+  const size_t P8 = c->poly() * 8;
+  SumLayout o;
+  o.c1 = ct_sum_partial_items_max() * 16;
+  o.c2 = o.c1 + (size_t)c->k * P8;
+  o.noisy = o.c2 + (size_t)c->n * P8;
+  o.io = o.noisy + ((P8 + 255) & ~(size_t)255);
+  o.total = o.io + (((size_t)c->n * 20 + 255) & ~(size_t)255);
+  return o;
+}
+static bool sum_buffer_ready(const pvw_ctx* c, const Workspace* w) { return w && w->sumbuf_bytes >= sum_layout(c).total; }
+static int32_t sum_buffer(pvw_ctx* c, Workspace* w, hipStream_t s) {
+  if (sum_buffer_ready(c, w)) return PVW_OK;
+  const size_t need = sum_layout(c).total;
+  if (w->sumbuf) {
+    PVW_HIP(hipStreamSynchronize(s));
+    hipMemset(w->sumbuf, 0, w->sumbuf_bytes);
+    hipFree(w->sumbuf);
+    w->sumbuf = nullptr;
+    w->sumbuf_bytes = 0;
+  }
+  PVW_HIP(hipMalloc((void**)&w->sumbuf, need));
+  w->sumbuf_bytes = need;
+  return PVW_OK;
+}
+// range sums of the single-ciphertext decrypt behind a sum (decrypt_mac_only grows Workspace::dpart to this)
+static size_t sum_dpart_need(const pvw_ctx* c) {
+  const u32 ns = decrypt_split(c->k, c->L, c->l, 1);
+  return ns > 1 ? (size_t)ns * c->poly() * 8 : 0;
+}
+// A device-pointer sum made under stream capture may not allocate or wait: the stream's workspace, its sum buffer and what
+// the decrypt behind the sum takes (dpart_need bytes of range sums, scratch_need bytes of scratch) must be there --
+// pvw_prepare(PVW_PREPARE_SUM) makes them.  Checked before the workspace is looked up and before anything is enqueued.
+static int32_t sum_capture_check(pvw_ctx* c, hipStream_t s, size_t dpart_need, size_t scratch_need) {
+  if (!stream_capturing(s)) return PVW_OK;
+  bool ready;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    auto it = c->async_ws.find((void*)s);
+    const Workspace* w = it == c->async_ws.end() ? nullptr : it->second;
+    ready = sum_buffer_ready(c, w) && w->dpart_bytes >= dpart_need && w->scratch_bytes >= scratch_need;
+  }
+  if (!ready)
+    return fail(PVW_ERR_INVALID_PARAMETERS, "ciphertext sum under stream capture: call pvw_prepare(PVW_PREPARE_SUM) on this stream "
+                                            "first (it sizes the scratch for the context's own party range)");
+  return PVW_OK;
+}
+static int32_t decrypt_all_sum_need(pvw_ctx* c, u32 lo, u32 hi, size_t* need) {
+  return decrypt_all_run(c, nullptr, nullptr, lo, hi, nullptr, nullptr, nullptr, 1, PVW_REPR_NTT, nullptr, false, (u64*)8, (u32*)8, need);
+}
+// pvw_prepare(PVW_PREPARE_SUM)
+static int32_t sum_prepare(pvw_ctx* c, Workspace* w, hipStream_t s) {
+  PVW_TRY(sum_buffer(c, w, s));
+  const size_t dneed = sum_dpart_need(c);
+  if (w->dpart_bytes < dneed) {
+    if (w->dpart) { PVW_HIP(hipStreamSynchronize(s)); hipFree(w->dpart); w->dpart = nullptr; w->dpart_bytes = 0; }
+    PVW_HIP(hipMalloc((void**)&w->dpart, dneed));
+    w->dpart_bytes = dneed;
+  }
+  size_t need = 0;
+  if (c->party_hi > c->party_lo) PVW_TRY(decrypt_all_sum_need(c, c->party_lo, c->party_hi, &need));
+  if (w->scratch_bytes < need) PVW_HIP(hipStreamSynchronize(s));
+  return ws_scratch(w, need);
+}
+
+// c2: the first polynomial summed of dealer 0 -- c2s + row_lo L l with c2_stride = n L l (whole ciphertexts), or a party's
+// column with c2_stride = L l -- `rows` polynomials per dealer; c1_stride = k L l.  valid / count: device pointers (or NULL).
+static int32_t ct_sum_enqueue(pvw_ctx* c, Workspace* w, hipStream_t s, const u64* c1s, const u64* c2, size_t c2_stride, size_t rows,
+                              size_t D, const uint8_t* valid, u64* c1_out, u64* c2_out, u32* count, bool accumulate = false) {
+  const size_t P = c->poly();
+  SumRegion a, b;
+  a.in = c1s; a.out = c1_out; a.stride = (size_t)c->k * P; a.items = (size_t)c->k * P / 2;
+  b.in = c2; b.out = c2_out; b.stride = c2_stride; b.items = rows * P / 2;
+  const size_t items = a.items + b.items;
+  u32 ns = ct_sum_slices(items, D);
+  if ((size_t)ns * items > ct_sum_partial_items_max()) ns = (u32)(ct_sum_partial_items_max() / items);   // a forced count (tuning build)
+  ProfScope ps(c, "ct_sum", s);
+  PVW_HIP(launch_ct_sum(a, b, valid, D, c->dt, c->L, c->l, ns > 1 ? w->sumbuf : nullptr, ns, accumulate, count, s));
+  return PVW_OK;
+}
+static size_t count_valid(const uint8_t* valid, size_t D) {
+  if (!valid) return D;
+  size_t nv = 0;
+  for (size_t d = 0; d < D; ++d) nv += valid[d] != 0;
+  return nv;
+}
+static int32_t no_valid_dealer(size_t D) {
+  char buf[112];
+  snprintf(buf, sizeof buf, "No valid dealer among the %zu ciphertexts: expected at least 1, got 0", D);
+  return fail(PVW_ERR_INSUFFICIENT_DATA, buf);
+}
+// dealers per staged piece: <= 1 GiB of ciphertext words, at most the valid dealers
+static size_t sum_stage_dealers(const pvw_ctx* c, size_t rows, size_t nv) {
+  size_t per = ((size_t)1 << 30) / (((size_t)c->k + rows) * c->poly() * 8);
+  if (per == 0) per = 1;
+  return per < nv ? per : nv;
+}
+// host buffers: runs of valid dealers are copied next to each other into st_c1 [per][k] / st_c2 [per][rows] and every full
+// piece is summed into d_c1_out / d_c2_out (the first piece stores, the later ones add); masked-out dealers are not copied
+static int32_t ct_sum_staged(pvw_ctx* c, Workspace* w, u64* st_c1, u64* st_c2, size_t per, const u64* c1s, const u64* c2,
+                             size_t c2_stride, size_t rows, size_t D, const uint8_t* valid, u64* d_c1_out, u64* d_c2_out) {
+  const size_t P = c->poly(), ctw = (size_t)c->k * P;
+  hipStream_t s = w->stream;
+  size_t fill = 0;
+  bool first = true;
+  auto flush = [&]() -> int32_t {
+    if (!fill) return PVW_OK;
+    PVW_TRY(ct_sum_enqueue(c, w, s, st_c1, st_c2, rows * P, rows, fill, nullptr, d_c1_out, d_c2_out, nullptr, !first));
+    first = false;
+    fill = 0;
+    return PVW_OK;
+  };
+  for (size_t d = 0; d < D;) {
+    if (valid && !valid[d]) { ++d; continue; }
+    size_t run = 1;
+    while (d + run < D && fill + run < per && (!valid || valid[d + run])) ++run;
+    PVW_HIP(hipMemcpyAsync(st_c1 + fill * ctw, c1s + d * ctw, run * ctw * 8, hipMemcpyHostToDevice, s));
+    PVW_HIP(hipMemcpy2DAsync(st_c2 + fill * rows * P, rows * P * 8, c2 + d * c2_stride, c2_stride * 8, rows * P * 8, run,
+                             hipMemcpyHostToDevice, s));
+    fill += run;
+    d += run;
+    if (fill == per) PVW_TRY(flush());
+  }
+  return flush();
+}
+
+static int32_t ct_sum_checks(const pvw_ctx* c, const void* c1s, const void* c2s, size_t D, u32 lo, u32 hi, const void* c1_out,
+                             const void* c2_out) {
+  if (!c || !c1s || !c2s || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");
+  if (D >> 32) return fail(PVW_ERR_INVALID_PARAMETERS, "a sum takes fewer than 2^32 dealers");
+  if (lo > hi) return fail(PVW_ERR_INVALID_PARAMETERS, "row_lo > row_hi");
+  if (hi > c->n) {
+    char buf[96];
+    snprintf(buf, sizeof buf, "Row index %u exceeds maximum %u", hi - 1, c->n - 1);
+    return fail(PVW_ERR_INVALID_PARAMETERS, buf);
+  }
+  if (lo == hi) return fail(PVW_ERR_INVALID_PARAMETERS, "empty row range");
+  return PVW_OK;
+}
+int32_t pvw_ct_sum_device(pvw_ctx* c, const uint64_t* d_c1s, const uint64_t* d_c2s, size_t D, const uint8_t* d_valid, uint32_t lo,
+                          uint32_t hi, uint64_t* d_c1_out, uint64_t* d_c2_out, uint32_t* d_count, void* stream) {
+  PVW_TRY(ct_sum_checks(c, d_c1s, d_c2s, D, lo, hi, d_c1_out, d_c2_out));
+  PVW_TRY(ensure_device(c));
+  hipStream_t s = call_stream(c, stream);
+  PVW_TRY(sum_capture_check(c, s, 0, 0));
+  Workspace* w;
+  PVW_TRY(ws_for_stream(c, s, &w));
+  PVW_TRY(sum_buffer(c, w, s));
+  const size_t P = c->poly();
+  return ct_sum_enqueue(c, w, s, d_c1s, d_c2s + (size_t)lo * P, (size_t)c->n * P, hi - lo, D, d_valid, d_c1_out, d_c2_out, d_count);
+}
+int32_t pvw_ct_sum(pvw_ctx* c, const uint64_t* c1s, const uint64_t* c2s, size_t D, const uint8_t* valid, uint32_t lo, uint32_t hi,
+                   uint64_t* c1_out, uint64_t* c2_out, uint32_t* count) {
+  PVW_TRY(ct_sum_checks(c, c1s, c2s, D, lo, hi, c1_out, c2_out));
+  const size_t nv = count_valid(valid, D);
+  if (nv == 0) return no_valid_dealer(D);
+  PVW_TRY(ensure_device(c));
+  const size_t P = c->poly(), k = c->k, rows = hi - lo, per = sum_stage_dealers(c, rows, nv);
+  Scratch sc;
+  const size_t r_c1 = sc.add(per * k * P * 8), r_c2 = sc.add(per * rows * P * 8);
+  const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    PVW_TRY(sum_buffer(c, w, w->stream));
+    const SumLayout sl = sum_layout(c);
+    u64 *d_c1 = (u64*)((char*)w->sumbuf + sl.c1), *d_c2 = (u64*)((char*)w->sumbuf + sl.c2);
+    PVW_TRY(ct_sum_staged(c, w, sc.at(r_c1), sc.at(r_c2), per, c1s, c2s + (size_t)lo * P, (size_t)c->n * P, rows, D, valid, d_c1, d_c2));
+    PVW_HIP(hipMemcpyAsync(c1_out, d_c1, k * P * 8, hipMemcpyDeviceToHost, w->stream));
+    PVW_HIP(hipMemcpyAsync(c2_out, d_c2, rows * P * 8, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
+  if (rc == PVW_OK && count) *count = (uint32_t)nv;
+  return rc;
+}
+// the same function in plain loops (no GPU): a 128-bit sum per word, one Barrett step at the end
+int32_t pvw_ct_sum_host(const pvw_ctx* c, const uint64_t* c1s, const uint64_t* c2s, size_t D, const uint8_t* valid, uint32_t lo,
+                        uint32_t hi, uint64_t* c1_out, uint64_t* c2_out, uint32_t* count) {
+  PVW_TRY(ct_sum_checks(c, c1s, c2s, D, lo, hi, c1_out, c2_out));
+  const size_t nv = count_valid(valid, D);
+  if (nv == 0) return no_valid_dealer(D);
+  const size_t P = c->poly(), l = c->l;
+  auto region = [&](const u64* in, size_t stride, size_t words, u64* out) {
+    for (size_t i = 0; i < words; ++i) {
+      u128 acc = 0;
+      for (size_t d = 0; d < D; ++d)
+        if (!valid || valid[d]) acc += in[d * stride + i];
+      out[i] = reduce128((u64)acc, (u64)(acc >> 64), c->mods[(i % P) / l]);
+    }
+  };
+  region(c1s, (size_t)c->k * P, (size_t)c->k * P, c1_out);
+  region(c2s + (size_t)lo * P, (size_t)c->n * P, (size_t)(hi - lo) * P, c2_out);
+  if (count) *count = (uint32_t)nv;
+  return PVW_OK;
+}
+
+// One party's aggregate share.  The summed ciphertext sits in the sum buffer (c1 | the column's sum: k + 1 polynomials in one
+// run, public); this is the rest: a POWER-basis sum is transformed there, then the single-ciphertext decrypt and its checked
+// decode (decrypt_batch_enqueue with D = 1: the split decrypt_mac + decrypt_finish + the checked decode chain).
+static int32_t decrypt_sum_tail(pvw_ctx* c, Workspace* w, hipStream_t s, const int64_t* d_sk, const u64* key_shat, uint32_t in_repr,
+                                u64* d_noisy, u64* d_out, u64* d_noise, u32* d_status) {
+  const SumLayout sl = sum_layout(c);
+  u64 *c1 = (u64*)((char*)w->sumbuf + sl.c1), *c2 = (u64*)((char*)w->sumbuf + sl.c2);
+  if (in_repr == PVW_REPR_POWER) {
+    ProfScope ps(c, "ntt", s);
+    PVW_HIP(launch_ntt(c1, (size_t)c->k + 1, false, c->dt, c->L, c->l, s));
+  }
+  if (d_noisy) return decrypt_batch_enqueue(c, w, s, d_sk, key_shat, c1, c2, 1, d_noisy, d_out, d_noise, d_status);
+  // m g + noise of the aggregate is the key holder's: kept in the sum buffer and cleared by a launch right behind the decode
+  // (a kernel, so that a captured call clears it on every replay in order); a call that fails on the way leaves it marked
+  d_noisy = (u64*)((char*)w->sumbuf + sl.noisy);
+  ws_mark_secret(w, d_noisy, c->poly() * 8);
+  PVW_TRY(decrypt_batch_enqueue(c, w, s, d_sk, key_shat, c1, c2, 1, d_noisy, d_out, d_noise, d_status));
+  PVW_HIP(launch_wipe_words(d_noisy, c->poly(), s));
+  ws_mark_secret(w, d_noisy, c->poly() * 8, true);
+  return PVW_OK;
+}
+static int32_t decrypt_sum_core(pvw_ctx* c, const int64_t* d_sk, const u64* key_shat, const uint64_t* d_c1s, const uint64_t* d_c2col,
+                                size_t D, const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out,
+                                uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, void* stream) {
+  if (!c || !d_c1s || !d_c2col || !d_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");          // decryption.rs:286-290
+  if (D >> 32) return fail(PVW_ERR_INVALID_PARAMETERS, "a sum takes fewer than 2^32 dealers");
+  PVW_TRY(check_repr(in_repr));
+  PVW_TRY(ensure_device(c));
+  hipStream_t s = call_stream(c, stream);
+  PVW_TRY(sum_capture_check(c, s, sum_dpart_need(c), 0));
+  Workspace* w;
+  PVW_TRY(ws_for_stream(c, s, &w));
+  PVW_TRY(sum_buffer(c, w, s));
+  const SumLayout sl = sum_layout(c);
+  auto run = [&]() -> int32_t {
+    PVW_TRY(ct_sum_enqueue(c, w, s, d_c1s, d_c2col, c->poly(), 1, D, d_valid, (u64*)((char*)w->sumbuf + sl.c1),
+                           (u64*)((char*)w->sumbuf + sl.c2), d_count));
+    return decrypt_sum_tail(c, w, s, d_sk, key_shat, in_repr, d_noisy, d_out, d_noise, d_status);
+  };
+  return device_end(w, s, run());
+}
+int32_t pvw_decrypt_sum_checked_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
+                                       const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise,
+                                       uint32_t* d_status, uint32_t* d_count, void* stream) {
+  if (!c || !d_sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  return decrypt_sum_core(c, d_sk, nullptr, d_c1s, d_c2col, D, d_valid, in_repr, d_noisy, d_out, d_noise, d_status, d_count, stream);
+}
+int32_t pvw_decrypt_sum_device_sk_checked(pvw_ctx* c, const pvw_sk* key, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
+                                          const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out,
+                                          uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, void* stream) {
+  if (!c || !key || !key->shat) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (key->ctx != c) return fail(PVW_ERR_INVALID_PARAMETERS, "the key was loaded for another context");
+  return decrypt_sum_core(c, nullptr, key->shat, d_c1s, d_c2col, D, d_valid, in_repr, d_noisy, d_out, d_noise, d_status, d_count, stream);
+}
+int32_t pvw_decrypt_sum_checked(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
+                                const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status,
+                                uint32_t* count) {
+  if (!c || !sk || !c1s || !c2col || !out_u64) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");          // decryption.rs:286-290
+  if (D >> 32) return fail(PVW_ERR_INVALID_PARAMETERS, "a sum takes fewer than 2^32 dealers");
+  PVW_TRY(check_repr(in_repr));
+  const size_t nv = count_valid(valid, D);
+  if (nv == 0) return no_valid_dealer(D);
+  PVW_TRY(ensure_device(c));
+  const size_t P = c->poly(), k = c->k, l = c->l, per = sum_stage_dealers(c, 1, nv);
+  Scratch sc;
+  const size_t r_sk = sc.add(k * l * 8), r_c1 = sc.add(per * k * P * 8), r_c2 = sc.add(per * P * 8);
+  const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    PVW_TRY(sum_buffer(c, w, w->stream));
+    const SumLayout sl = sum_layout(c);
+    i64* d_sk = sc.at<i64>(r_sk);
+    u64* io = (u64*)((char*)w->sumbuf + sl.io);                  // out | noise | status: the key holder's
+    sc.secret(w, r_sk, r_sk);
+    ws_mark_secret(w, io, 24);
+    PVW_HIP(hipMemcpyAsync(d_sk, sk, k * l * 8, hipMemcpyHostToDevice, w->stream));
+    PVW_TRY(ct_sum_staged(c, w, sc.at(r_c1), sc.at(r_c2), per, c1s, c2col, P, 1, D, valid, (u64*)((char*)w->sumbuf + sl.c1),
+                          (u64*)((char*)w->sumbuf + sl.c2)));
+    PVW_TRY(decrypt_sum_tail(c, w, w->stream, d_sk, nullptr, in_repr, nullptr, io, noise ? io + 1 : nullptr,
+                             status ? (u32*)(io + 2) : nullptr));
+    PVW_HIP(hipMemcpyAsync(out_u64, io, 8, hipMemcpyDeviceToHost, w->stream));
+    if (noise) PVW_HIP(hipMemcpyAsync(noise, io + 1, 8, hipMemcpyDeviceToHost, w->stream));
+    if (status) PVW_HIP(hipMemcpyAsync(status, io + 2, 4, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
+  if (rc == PVW_OK && count) *count = (uint32_t)nv;
+  return rc;
+}
+
+// Every party's aggregate share: the sum over c1 and rows [lo, hi) of c2 (row r at its global position of the sum buffer, so the
+// buffer reads as ONE whole ciphertext), then decrypt_all_run on that one ciphertext: the 22-party dispatch is its own.
+static int32_t decrypt_all_sum_tail(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, u32 hi, const int64_t* d_sk, uint32_t in_repr,
+                                    u64* d_out, u64* d_noise, u32* d_status) {
+  const SumLayout sl = sum_layout(c);
+  u64 *c1 = (u64*)((char*)w->sumbuf + sl.c1), *c2 = (u64*)((char*)w->sumbuf + sl.c2);
+  if (in_repr == PVW_REPR_POWER) {
+    ProfScope ps(c, "ntt", s);
+    PVW_HIP(launch_ntt(c1, c->k, false, c->dt, c->L, c->l, s));
+    PVW_HIP(launch_ntt(c2 + (size_t)lo * c->poly(), hi - lo, false, c->dt, c->L, c->l, s));
+  }
+  return decrypt_all_run(c, w, s, lo, hi, d_sk, c1, c2, 1, PVW_REPR_NTT, d_out, false, d_noise, d_status);
+}
+int32_t pvw_decrypt_all_sum_checked_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
+                                           const uint64_t* d_c2s, size_t D, const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_out,
+                                           uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, void* stream) {
+  PVW_TRY(decrypt_all_checks(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out));
+  if (D >> 32) return fail(PVW_ERR_INVALID_PARAMETERS, "a sum takes fewer than 2^32 dealers");
+  PVW_TRY(ensure_device(c));
+  hipStream_t s = call_stream(c, stream);
+  size_t need = 0;
+  PVW_TRY(decrypt_all_sum_need(c, lo, hi, &need));
+  PVW_TRY(sum_capture_check(c, s, sum_dpart_need(c), need));
+  Workspace* w;
+  PVW_TRY(ws_for_stream(c, s, &w));
+  PVW_TRY(sum_buffer(c, w, s));
+  PVW_TRY(ws_scratch(w, need));                                    // before anything of this call is enqueued
+  const SumLayout sl = sum_layout(c);
+  const size_t P = c->poly();
+  auto run = [&]() -> int32_t {
+    PVW_TRY(ct_sum_enqueue(c, w, s, d_c1s, d_c2s + (size_t)lo * P, (size_t)c->n * P, hi - lo, D, d_valid,
+                           (u64*)((char*)w->sumbuf + sl.c1), (u64*)((char*)w->sumbuf + sl.c2) + (size_t)lo * P, d_count));
+    return decrypt_all_sum_tail(c, w, s, lo, hi, d_sk, in_repr, d_out, d_noise, d_status);
+  };
+  return device_end(w, s, run());
+}
+int32_t pvw_decrypt_all_sum_checked(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
+                                    size_t D, const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise,
+                                    uint32_t* status, uint32_t* count) {
+  PVW_TRY(decrypt_all_checks(c, lo, hi, sk, c1s, c2s, D, in_repr, out_u64));
+  if (D >> 32) return fail(PVW_ERR_INVALID_PARAMETERS, "a sum takes fewer than 2^32 dealers");
+  const size_t nv = count_valid(valid, D);
+  if (nv == 0) return no_valid_dealer(D);
+  PVW_TRY(ensure_device(c));
+  const size_t P = c->poly(), k = c->k, l = c->l, NP = (size_t)hi - lo, per = sum_stage_dealers(c, NP, nv);
+  size_t need = 0;
+  PVW_TRY(decrypt_all_sum_need(c, lo, hi, &need));
+  // the staged pieces and the decrypt's own scratch share the front of the block (stream order: the sum has read the pieces
+  // before the decrypt writes there); the uploaded keys sit behind both
+  Scratch st;
+  const size_t r_c1 = st.add(per * k * P * 8), r_c2 = st.add(per * NP * P * 8);
+  Scratch sc;
+  const size_t r_main = sc.add(need > st.total ? need : st.total), r_sk = sc.add(NP * k * l * 8);
+  const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    PVW_TRY(sum_buffer(c, w, w->stream));
+    st.base = sc.at<char>(r_main);
+    const SumLayout sl = sum_layout(c);
+    i64* d_sk = sc.at<i64>(r_sk);
+    u64 *d_out = (u64*)((char*)w->sumbuf + sl.io), *d_ns = d_out + c->n;
+    u32* d_st = (u32*)(d_ns + c->n);
+    sc.secret(w, r_sk, r_sk);
+    ws_mark_secret(w, d_out, (size_t)c->n * 20);
+    PVW_HIP(hipMemcpyAsync(d_sk, sk, NP * k * l * 8, hipMemcpyHostToDevice, w->stream));
+    PVW_TRY(ct_sum_staged(c, w, st.at(r_c1), st.at(r_c2), per, c1s, c2s + (size_t)lo * P, (size_t)c->n * P, NP, D, valid,
+                          (u64*)((char*)w->sumbuf + sl.c1), (u64*)((char*)w->sumbuf + sl.c2) + (size_t)lo * P));
+    PVW_TRY(decrypt_all_sum_tail(c, w, w->stream, lo, hi, d_sk, in_repr, d_out, noise ? d_ns : nullptr, status ? d_st : nullptr));
+    PVW_HIP(hipMemcpyAsync(out_u64, d_out, NP * 8, hipMemcpyDeviceToHost, w->stream));
+    if (noise) PVW_HIP(hipMemcpyAsync(noise, d_ns, NP * 8, hipMemcpyDeviceToHost, w->stream));
+    if (status) PVW_HIP(hipMemcpyAsync(status, d_st, NP * 4, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
+  if (rc == PVW_OK && count) *count = (uint32_t)nv;
+  return rc;
+}
+
+// Advisory: for how many dealers at the builder's noise bound the gadget decode of the aggregate is PROVEN exact.  With
+// z_j = -P Delta^j + n_j and max |n_j| <= R, R (Delta^(l-1) + 1) < Q / 2, every tmp_i and the Horner value
+// n_0 Delta^(l-1) - n_(l-1) of decryption.rs:10-58 stay below Q / 2 in magnitude, so the chain is exact: sufficient, not
+// necessary.  Q is odd: R = floor((Q - 1) / (2 (Delta^(l-1) + 1))).
+int32_t pvw_ctx_sum_capacity(const pvw_ctx* c, uint64_t* max_dealers) {
+  if (!c || !max_dealers) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  uint64_t nb = 0;
+  PVW_TRY(pvw_ctx_noise_bound(c, &nb));
+  const BigInt R = (c->Q - BigInt(1)) / ((c->delta_pow + BigInt(1)) * BigInt(2));
+  const BigInt cap = nb ? R / BigInt(nb) : R;
+  *max_dealers = cap.fits_u64() ? (cap.mag.empty() ? 0 : cap.mag[0]) : ~(uint64_t)0;
+  return PVW_OK;
 }
 
 // ------------------------------------------------------------------------ key generation

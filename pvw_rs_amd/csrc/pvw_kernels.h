@@ -199,6 +199,30 @@ hipError_t launch_decrypt_mac(const u64* c1s, const u64* shat, const u64* c2col,
 hipError_t launch_decrypt_finish(const u64* partial, u32 nsplit, const u64* c2col, u64* noisy, const DevTables& t, u32 L, u32 ell,
                                  size_t dealers, hipStream_t s);
 
+// ---- sum of dealers' ciphertexts (pvw_sum.hip): out = sum over the valid dealers d of in + d * stride, word by word mod q ----
+// One region of the sum: `items` 16-byte items (two words of one limb) per dealer, dealer d's at in + d * stride words; a
+// whole number of polynomials starting on a polynomial boundary (item i is in limb (2 i mod L l) / l).  c1 is one region
+// (stride k L l), the c2 rows [row_lo, row_hi) of whole ciphertexts (in = c2s + row_lo L l, stride n L l) or one party's
+// column (stride L l) the other; both travel in ONE launch.
+struct SumRegion {
+  const u64* in = nullptr;
+  u64* out = nullptr;
+  size_t stride = 0;    // words between consecutive dealers (even)
+  size_t items = 0;
+};
+#define PVW_SUM_MAX_SLICES 64
+// slices of dealers (gridDim.y) for `items` items in all: 1 = unsplit.  With nslices > 1 `partial` holds nslices x items
+// 16-byte slice sums and ct_sum_finish adds them up.  Bounded: nslices * items <= ct_sum_partial_items_max().
+u32 ct_sum_slices(size_t items, size_t dealers);
+inline size_t ct_sum_partial_items_max() { return (size_t)(1024 + 512) * 256; }   // (1024 / wgs + 1) * wgs workgroups, wgs < 512
+// valid: NULL = every dealer, else valid[d] != 0 (device bytes, read when the kernel runs).  accumulate: out += the sum
+// (out holds an earlier piece's result).  count: NULL, or receives the number of dealers summed.  dealers < 2^32.
+hipError_t launch_ct_sum(const SumRegion& a, const SumRegion& b, const unsigned char* valid, size_t dealers, const DevTables& t, u32 L,
+                         u32 ell, u64* partial, u32 nslices, bool accumulate, u32* count, hipStream_t s);
+
+// p[0 .. words) = 0, as a kernel launch on s
+hipError_t launch_wipe_words(u64* p, size_t words, hipStream_t s);
+
 // ---- digit GEMM on the matrix cores (see pvw_gemm.hip) ----
 #ifndef PVW_GEMM_RPW
 #define PVW_GEMM_RPW 1                                   // row tiles (of 32 rows) per wave

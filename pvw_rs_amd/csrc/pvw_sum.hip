@@ -1,0 +1,164 @@
+// pvw_sum.hip -- the homomorphic sum of dealers' ciphertexts on gfx950: out = sum over the valid dealers d of in_d, word by
+// word mod q of the word's limb (the step examples/pvw.rs:138-170 and examples/pvw_valid_dec.rs:150-209 take on decrypted
+// shares, taken on the ciphertexts instead).  An HBM-bound stream: every valid dealer's words are read once.
+#include <hip/hip_runtime.h>
+
+#include "pvw_arith.h"
+#include "pvw_kernels.h"
+#include "pvw_dev.h"
+
+namespace pvw {
+
+// One 16-byte item (two words of one limb: l is even) per thread; a wave reads 1 KiB contiguous of one dealer per load.
+// The dealers of the workgroup's slice are walked 64 at a time: lane i reads valid[d0 + i] and the ballot is the slice's
+// mask, wave-uniform in a scalar register pair.  The set bits are taken U at a time, so U loads of U VALID dealers are in
+// flight per wave whatever the mask looks like, and a dealer that is masked out is never addressed.
+// Accumulation is lazy: a 64-bit sum and a 32-bit carry count per word, one 128 -> 64 Barrett step at the end
+// (any 64-bit input word is accepted; fewer than 2^32 dealers).
+template <int U>
+__global__ __launch_bounds__(256) void ct_sum_kernel(SumRegion ra, SumRegion rb, const unsigned char* __restrict__ valid, u32 dealers,
+                                                     u32 per_slice, const Mod* __restrict__ mods, u32 ell, u32 L,
+                                                     u64* __restrict__ partial, u32 accumulate, u32* __restrict__ count) {
+  const size_t items_a = ra.items, total = ra.items + rb.items;
+  const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const u32 lane = threadIdx.x & 63;
+  const u32 dlo = blockIdx.y * per_slice;
+  const u32 dhi = (dealers - dlo) < per_slice ? dealers : dlo + per_slice;
+  // the number of dealers summed: one lane of one workgroup (the mask of ALL dealers, whatever the slices are)
+  if (count && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) {
+    u32 n = 0;
+    for (u64 d0 = 0; d0 < dealers; d0 += 64) {
+      const bool on = d0 + lane < dealers && (!valid || valid[d0 + lane] != 0);
+      n += (u32)__builtin_popcountll(__builtin_amdgcn_ballot_w64(on));
+    }
+    if (lane == 0) *count = n;
+  }
+  const bool live = g < total;
+  const bool in_a = g < items_a;
+  const size_t it = live ? (in_a ? g : g - items_a) : 0;
+  const v2u64* src = reinterpret_cast<const v2u64*>(live ? (in_a ? ra.in : rb.in) : ra.in) + it;
+  const size_t stride = (in_a ? ra.stride : rb.stride) / 2;      // 16-byte items between dealers
+  u64 s0 = 0, s1 = 0;
+  u32 c0 = 0, c1 = 0;
+  bool on = dlo + lane < dhi && (!valid || valid[dlo + lane] != 0);
+  for (u64 d0 = dlo; d0 < dhi; d0 += 64) {
+    u64 m = __builtin_amdgcn_ballot_w64(on);
+    on = d0 + 64 + lane < dhi && (!valid || valid[d0 + 64 + lane] != 0);   // the next 64 dealers' bytes, under this chunk's loads
+    while (m) {
+      v2u64 x[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        x[u] = (v2u64){0, 0};
+        if (m) {                                                 // wave-uniform
+          const u32 b = (u32)__builtin_ctzll(m);
+          m &= m - 1;
+          if (live) x[u] = __builtin_nontemporal_load(src + (size_t)(d0 + b) * stride);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);                         // every load of the group issued before its first add
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        u64 t = s0 + x[u].x;
+        c0 += t < s0;
+        s0 = t;
+        t = s1 + x[u].y;
+        c1 += t < s1;
+        s1 = t;
+      }
+    }
+  }
+  if (!live) return;
+  const u32 poly = L * ell;
+  const Mod mq = mods[(u32)((2 * it) % poly) / ell];
+  v2u64 res = (v2u64){reduce128(s0, c0, mq), reduce128(s1, c1, mq)};
+  if (partial) {                                                 // split form: the slice's sum, reduced, for ct_sum_finish
+    reinterpret_cast<v2u64*>(partial)[(size_t)blockIdx.y * total + g] = res;
+    return;
+  }
+  v2u64* o = reinterpret_cast<v2u64*>(in_a ? ra.out : rb.out) + it;
+  if (accumulate) {                                              // out += sum (a later piece of a staged call)
+    const v2u64 p = *o;
+    res.x = addmod(res.x, reduce_word(p.x, mq), mq.q);
+    res.y = addmod(res.y, reduce_word(p.y, mq), mq.q);
+  }
+  *o = res;
+}
+
+// out = sum of the S slice sums (each below q) of the split form
+__global__ __launch_bounds__(256) void ct_sum_finish_kernel(const u64* __restrict__ partial, u32 nslices, SumRegion ra, SumRegion rb,
+                                                            const Mod* __restrict__ mods, u32 ell, u32 L, u32 accumulate) {
+  const size_t items_a = ra.items, total = ra.items + rb.items;
+  const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= total) return;
+  const bool in_a = g < items_a;
+  const size_t it = in_a ? g : g - items_a;
+  const u64 q = mods[(u32)((2 * it) % (L * ell)) / ell].q;
+  const v2u64* p = reinterpret_cast<const v2u64*>(partial) + g;
+  v2u64 acc = p[0];
+  for (u32 s = 1; s < nslices; ++s) {
+    const v2u64 t = p[(size_t)s * total];
+    acc.x = addmod(acc.x, t.x, q);
+    acc.y = addmod(acc.y, t.y, q);
+  }
+  v2u64* o = reinterpret_cast<v2u64*>(in_a ? ra.out : rb.out) + it;
+  if (accumulate) {
+    const Mod mq = mods[(u32)((2 * it) % (L * ell)) / ell];
+    const v2u64 t = *o;
+    acc.x = addmod(acc.x, reduce_word(t.x, mq), q);
+    acc.y = addmod(acc.y, reduce_word(t.y, mq), q);
+  }
+  *o = acc;
+}
+
+// How many slices the dealers are cut into (1 = the unsplit form), from the shape alone.  With fewer than two workgroups
+// per CU (256 CUs) the items alone do not fill the chip -- one party's view at n = 4096, k = 256, l = 8, L = 17 is 69
+// workgroups -- so the dealers are cut until about four workgroups per CU exist, never into slices of fewer than 8
+// dealers (one group of loads), at most PVW_SUM_MAX_SLICES.
+u32 ct_sum_slices(size_t items, size_t dealers) {
+  if (items == 0 || dealers == 0) return 1;
+  const size_t wgs = (items + 255) / 256;
+  long ns = PVW_ENV_INT("PVW_SUM_SPLIT", 0);                     // tuning build: forced slice count (1 = unsplit)
+  if (ns <= 0) ns = wgs >= 512 ? 1 : (long)((1024 + wgs - 1) / wgs);
+  if (ns > PVW_SUM_MAX_SLICES) ns = PVW_SUM_MAX_SLICES;
+  while (ns > 1 && dealers / (size_t)ns < 8) --ns;
+  return (u32)(ns < 1 ? 1 : ns);
+}
+
+hipError_t launch_ct_sum(const SumRegion& a, const SumRegion& b, const unsigned char* valid, size_t dealers, const DevTables& t, u32 L,
+                         u32 ell, u64* partial, u32 nslices, bool accumulate, u32* count, hipStream_t s) {
+  const size_t total = a.items + b.items;
+  if (total == 0 || dealers == 0 || dealers >> 32) return hipErrorInvalidValue;
+  const size_t wgs = (total + 255) / 256;
+  if (wgs >> 31) return hipErrorInvalidValue;
+  const bool deep = PVW_ENV_INT("PVW_SUM_U", 8) == 16;            // tuning build: 16 loads in flight per wave instead of 8
+  if (nslices <= 1 || !partial) {
+    if (deep)
+      ct_sum_kernel<16><<<dim3((u32)wgs, 1), dim3(256), 0, s>>>(a, b, valid, (u32)dealers, (u32)dealers, t.mods, ell, L, nullptr,
+                                                                accumulate ? 1u : 0u, count);
+    else
+      ct_sum_kernel<8><<<dim3((u32)wgs, 1), dim3(256), 0, s>>>(a, b, valid, (u32)dealers, (u32)dealers, t.mods, ell, L, nullptr,
+                                                               accumulate ? 1u : 0u, count);
+    return hipGetLastError();
+  }
+  const u32 per = (u32)((dealers + nslices - 1) / nslices);
+  const u32 ny = (u32)((dealers + per - 1) / per);               // no empty slice: every partial plane is written
+  ct_sum_kernel<8><<<dim3((u32)wgs, ny), dim3(256), 0, s>>>(a, b, valid, (u32)dealers, per, t.mods, ell, L, partial, 0u, count);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  ct_sum_finish_kernel<<<dim3((u32)wgs), dim3(256), 0, s>>>(partial, ny, a, b, t.mods, ell, L, accumulate ? 1u : 0u);
+  return hipGetLastError();
+}
+
+// p[0 .. words) = 0 as a kernel on `s`: the clearing of a small key-derived scratch region that has to stay ordered behind its
+// last reader when the call is captured into a graph and replayed
+__global__ __launch_bounds__(256) void wipe_words_kernel(u64* __restrict__ p, size_t words) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < words) p[i] = 0;
+}
+hipError_t launch_wipe_words(u64* p, size_t words, hipStream_t s) {
+  if (!words) return hipSuccess;
+  wipe_words_kernel<<<dim3((u32)((words + 255) / 256)), dim3(256), 0, s>>>(p, words);
+  return hipGetLastError();
+}
+
+}  // namespace pvw

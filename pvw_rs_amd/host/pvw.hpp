@@ -566,4 +566,79 @@ inline uint64_t decrypt_party_value(const PvwCiphertext& ct, const SecretKey& sk
   return out;
 }
 
+// ---- sums of dealers' ciphertexts: the scheme is additively homomorphic, so party i's result of
+// examples/pvw_valid_dec.rs:201-209 (the sum of its shares from the valid dealers) comes from ONE decrypt of the summed ciphertext
+struct SumInputs {
+  std::vector<uint64_t> c1s, c2s;
+  std::vector<uint8_t> valid;      // empty = every dealer
+  const uint8_t* valid_ptr() const { return valid.empty() ? nullptr : valid.data(); }
+};
+inline SumInputs sum_inputs(const std::vector<PvwCiphertext>& cts, const std::vector<bool>& valid) {
+  if (cts.empty()) throw PvwError(1, "No ciphertexts provided");
+  if (!valid.empty() && valid.size() != cts.size()) throw PvwError(PVW_ERR_DIMENSION_MISMATCH, "valid: one flag per ciphertext expected");
+  SumInputs in;
+  for (const auto& ct : cts) {
+    if (ct.repr != cts[0].repr || ct.c1.size() != cts[0].c1.size() || ct.c2.size() != cts[0].c2.size())
+      throw PvwError(PVW_ERR_DIMENSION_MISMATCH, "ciphertexts of different shapes or representations");
+    ct.validate();
+    in.c1s.insert(in.c1s.end(), ct.c1.begin(), ct.c1.end());
+    in.c2s.insert(in.c2s.end(), ct.c2.begin(), ct.c2.end());
+  }
+  for (bool v : valid) in.valid.push_back(v ? 1 : 0);
+  return in;
+}
+// the sum of the valid dealers' ciphertexts (pvw_ct_sum): same parameters and representation, no key needed
+inline PvwCiphertext aggregate_ciphertexts(const std::vector<PvwCiphertext>& cts, const std::vector<bool>& valid = {}) {
+  const SumInputs in = sum_inputs(cts, valid);
+  const auto& p = cts[0].params;
+  PvwCiphertext out{std::vector<uint64_t>(cts[0].c1.size()), std::vector<uint64_t>(cts[0].c2.size()), p, cts[0].repr};
+  check(pvw_ct_sum(p->ctx, in.c1s.data(), in.c2s.data(), cts.size(), in.valid_ptr(), 0, p->n, out.c1.data(), out.c2.data(), nullptr));
+  return out;
+}
+// party_index's aggregate share with its report (pvw_decrypt_sum_checked); bound 0 = count * noise_bound
+inline CheckedShares decrypt_party_sum(const std::vector<PvwCiphertext>& cts, const SecretKey& sk, uint32_t party_index,
+                                       const std::vector<bool>& valid = {}, uint64_t bound = 0) {
+  const SumInputs in = sum_inputs(cts, valid);
+  const auto& p = cts[0].params;
+  if (party_index >= p->n) throw PvwError(1, "Party index exceeds maximum");
+  const size_t P = p->poly_words();
+  std::vector<uint64_t> c2col;
+  for (const auto& ct : cts) c2col.insert(c2col.end(), ct.c2.begin() + (size_t)party_index * P, ct.c2.begin() + (size_t)(party_index + 1) * P);
+  uint32_t status = 0, count = 0;
+  CheckedShares r{std::vector<uint64_t>(1), std::vector<uint64_t>(1), std::vector<bool>(1), std::vector<bool>(1)};
+  check(pvw_decrypt_sum_checked(p->ctx, sk.secret_coeffs.data(), in.c1s.data(), c2col.data(), cts.size(), in.valid_ptr(), cts[0].repr,
+                                r.values.data(), r.noise.data(), &status, &count));
+  if (!bound) bound = (uint64_t)count * noise_bound(p->ctx);
+  r.lossy[0] = (status & PVW_DEC_LOSSY) != 0;
+  r.valid[0] = !r.lossy[0] && r.noise[0] <= bound;
+  return r;
+}
+// every party's aggregate share in one call (pvw_decrypt_all_sum_checked); parties with consecutive indices
+inline CheckedShares decrypt_all_party_sums(const std::vector<PvwCiphertext>& cts, const std::vector<Party>& parties,
+                                            const std::vector<bool>& valid = {}, uint64_t bound = 0) {
+  const SumInputs in = sum_inputs(cts, valid);
+  const auto& p = cts[0].params;
+  const size_t NP = parties.size(), kl = (size_t)p->k * p->l;
+  CheckedShares r{std::vector<uint64_t>(NP), std::vector<uint64_t>(NP), std::vector<bool>(NP), std::vector<bool>(NP)};
+  if (NP == 0) return r;
+  std::vector<int64_t> sk(NP * kl);
+  for (size_t i = 0; i < NP; ++i) {
+    if (parties[i].index >= p->n || parties[i].index != parties[0].index + i) throw PvwError(1, "Party indices must be consecutive and below n");
+    std::copy(parties[i].secret_key.secret_coeffs.begin(), parties[i].secret_key.secret_coeffs.end(), sk.begin() + i * kl);
+  }
+  std::vector<uint32_t> status(NP);
+  uint32_t count = 0;
+  const int32_t rc = pvw_decrypt_all_sum_checked(p->ctx, parties[0].index, parties[0].index + (uint32_t)NP, sk.data(), in.c1s.data(),
+                                                 in.c2s.data(), cts.size(), in.valid_ptr(), cts[0].repr, r.values.data(), r.noise.data(),
+                                                 status.data(), &count);
+  std::fill(sk.begin(), sk.end(), 0);                                   // the copied keys do not outlive the call
+  check(rc);
+  if (!bound) bound = (uint64_t)count * noise_bound(p->ctx);
+  for (size_t i = 0; i < NP; ++i) {
+    r.lossy[i] = (status[i] & PVW_DEC_LOSSY) != 0;
+    r.valid[i] = !r.lossy[i] && r.noise[i] <= bound;
+  }
+  return r;
+}
+
 }  // namespace pvw_host

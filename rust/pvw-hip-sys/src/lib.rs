@@ -58,6 +58,7 @@ pub struct PvwRandomnessT {
 
 pub const PVW_PREPARE_PACKED: u32 = 1;
 pub const PVW_PREPARE_MFMA: u32 = 2;
+pub const PVW_PREPARE_SUM: u32 = 4;
 /// status bit of the checked decrypt: the returned word is not the plaintext (pvw_hip.h)
 pub const PVW_DEC_LOSSY: u32 = 1;
 pub const PVW_OK: i32 = 0;
@@ -163,6 +164,15 @@ extern "C" {
     pub fn pvw_decode_checked_host(ctx: *const PvwCtx, noisy: *const u64, count: usize, out_u64: *mut u64, noise: *mut u64, status: *mut u32) -> i32;
     pub fn pvw_selftest_decode_checked(ctx: *const PvwCtx, noisy: *const u64, count: usize, out_u64: *mut u64, noise: *mut u64, status: *mut u32) -> i32;
     pub fn pvw_ctx_noise_bound(ctx: *const PvwCtx, out: *mut u64) -> i32;
+    pub fn pvw_ct_sum_device(ctx: *mut PvwCtx, d_c1s: *const u64, d_c2s: *const u64, num_dealers: usize, d_valid: *const u8, row_lo: u32, row_hi: u32, d_c1_out: *mut u64, d_c2_out: *mut u64, d_count: *mut u32, stream: *mut c_void) -> i32;
+    pub fn pvw_ct_sum(ctx: *mut PvwCtx, c1s: *const u64, c2s: *const u64, num_dealers: usize, valid: *const u8, row_lo: u32, row_hi: u32, c1_out: *mut u64, c2_out: *mut u64, count: *mut u32) -> i32;
+    pub fn pvw_ct_sum_host(ctx: *const PvwCtx, c1s: *const u64, c2s: *const u64, num_dealers: usize, valid: *const u8, row_lo: u32, row_hi: u32, c1_out: *mut u64, c2_out: *mut u64, count: *mut u32) -> i32;
+    pub fn pvw_decrypt_sum_checked_device(ctx: *mut PvwCtx, d_sk: *const i64, d_c1s: *const u64, d_c2col: *const u64, num_dealers: usize, d_valid: *const u8, in_repr: u32, d_noisy: *mut u64, d_out: *mut u64, d_noise: *mut u64, d_status: *mut u32, d_count: *mut u32, stream: *mut c_void) -> i32;
+    pub fn pvw_decrypt_sum_device_sk_checked(ctx: *mut PvwCtx, key: *const PvwSk, d_c1s: *const u64, d_c2col: *const u64, num_dealers: usize, d_valid: *const u8, in_repr: u32, d_noisy: *mut u64, d_out: *mut u64, d_noise: *mut u64, d_status: *mut u32, d_count: *mut u32, stream: *mut c_void) -> i32;
+    pub fn pvw_decrypt_sum_checked(ctx: *mut PvwCtx, sk: *const i64, c1s: *const u64, c2col: *const u64, num_dealers: usize, valid: *const u8, in_repr: u32, out_u64: *mut u64, noise: *mut u64, status: *mut u32, count: *mut u32) -> i32;
+    pub fn pvw_decrypt_all_sum_checked(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, sk: *const i64, c1s: *const u64, c2s: *const u64, num_dealers: usize, valid: *const u8, in_repr: u32, out_u64: *mut u64, noise: *mut u64, status: *mut u32, count: *mut u32) -> i32;
+    pub fn pvw_decrypt_all_sum_checked_device(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, d_sk: *const i64, d_c1s: *const u64, d_c2s: *const u64, num_dealers: usize, d_valid: *const u8, in_repr: u32, d_out: *mut u64, d_noise: *mut u64, d_status: *mut u32, d_count: *mut u32, stream: *mut c_void) -> i32;
+    pub fn pvw_ctx_sum_capacity(ctx: *const PvwCtx, max_dealers: *mut u64) -> i32;
     pub fn pvw_decode(ctx: *mut PvwCtx, noisy: *const u64, count: usize, out_u64: *mut u64) -> i32;
     pub fn pvw_decode_host(ctx: *const PvwCtx, noisy: *const u64, count: usize, out_u64: *mut u64) -> i32;
     pub fn pvw_decode_device(ctx: *mut PvwCtx, d_noisy: *const u64, count: usize, d_out: *mut u64, stream: *mut c_void) -> i32;

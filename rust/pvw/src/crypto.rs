@@ -358,3 +358,104 @@ pub fn decrypt_all_party_shares(all_ciphertexts: &[PvwCiphertext], parties: &[cr
     check(rc)?;
     Ok(out.chunks_exact(d).map(|r| r.to_vec()).collect())
 }
+
+/// The checks and flat buffers every sum shares: (c1s, c2s, valid bytes or empty = every dealer).
+fn sum_inputs(ciphertexts: &[PvwCiphertext], valid: Option<&[bool]>) -> Result<(Vec<u64>, Vec<u64>, Vec<u8>)> {
+    if ciphertexts.is_empty() {
+        return Err(PvwError::InvalidParameters("No ciphertexts provided".to_string()));
+    }
+    let params = &ciphertexts[0].params;
+    if let Some(v) = valid {
+        if v.len() != ciphertexts.len() {
+            return Err(PvwError::DimensionMismatch { expected: ciphertexts.len(), actual: v.len() });
+        }
+        if !v.iter().any(|&b| b) {
+            return Err(PvwError::InsufficientData { expected: 1, actual: 0 });
+        }
+    }
+    let words = poly_words(params);
+    let d = ciphertexts.len();
+    let (mut c1s, mut c2s) = (Vec::with_capacity(d * params.k * words), Vec::with_capacity(d * params.n * words));
+    for (dealer_idx, ciphertext) in ciphertexts.iter().enumerate() {
+        ciphertext
+            .validate()
+            .map_err(|e| PvwError::InvalidParameters(format!("Ciphertext {dealer_idx} invalid: {e}")))?;
+        for poly in ciphertext.c1.iter() {
+            poly_to_flat(poly, &mut c1s);
+        }
+        for poly in ciphertext.c2.iter() {
+            poly_to_flat(poly, &mut c2s);
+        }
+    }
+    Ok((c1s, c2s, valid.map(|v| v.iter().map(|&b| b as u8).collect()).unwrap_or_default()))
+}
+
+fn valid_ptr(valid: &[u8]) -> *const u8 {
+    if valid.is_empty() { std::ptr::null() } else { valid.as_ptr() }
+}
+
+/// EXTENSION: the sum of the valid dealers' ciphertexts (`pvw_ct_sum`) -- a ciphertext of the sum of their
+/// shares under the same keys, folded without any key.  What examples/pvw_valid_dec.rs:150-209 reaches by decrypting every
+/// dealer's share and adding the results; the noise of the sum is the sum of the dealers' noises (`pvw_ctx_sum_capacity`).
+pub fn aggregate_ciphertexts(ciphertexts: &[PvwCiphertext], valid: Option<&[bool]>) -> Result<PvwCiphertext> {
+    let (c1s, c2s, v) = sum_inputs(ciphertexts, valid)?;
+    let params = &ciphertexts[0].params;
+    let words = poly_words(params);
+    let (mut c1, mut c2) = (vec![0u64; params.k * words], vec![0u64; params.n * words]);
+    check(unsafe {
+        sys::pvw_ct_sum(params.hip.raw(), c1s.as_ptr(), c2s.as_ptr(), ciphertexts.len(), valid_ptr(&v), 0, params.n as u32, c1.as_mut_ptr(),
+                        c2.as_mut_ptr(), std::ptr::null_mut())
+    })?;
+    ciphertext_from_flat(&c1, &c2, params)
+}
+
+/// EXTENSION: party `party_index`'s aggregate share from ONE decrypt of the summed ciphertext (`pvw_decrypt_sum_checked`):
+/// (value, noise, lossy, dealers summed).  `noise` is the exact max residual of the aggregate.
+pub fn decrypt_party_sum(ciphertexts: &[PvwCiphertext], secret_key: &SecretKey, party_index: usize, valid: Option<&[bool]>) -> Result<(u64, u64, bool, u32)> {
+    let (c1s, c2s, v) = sum_inputs(ciphertexts, valid)?;
+    let params = &ciphertexts[0].params;
+    if party_index >= params.n {
+        return Err(PvwError::InvalidParameters(format!("Party index {} exceeds maximum {}", party_index, params.n - 1)));
+    }
+    let words = poly_words(params);
+    let c2col: Vec<u64> = c2s.chunks_exact(params.n * words).flat_map(|ct| ct[party_index * words..(party_index + 1) * words].to_vec()).collect();
+    let mut sk = flat_secret(secret_key);
+    let (mut out, mut noise, mut status, mut count) = (0u64, 0u64, 0u32, 0u32);
+    let rc = unsafe {
+        sys::pvw_decrypt_sum_checked(params.hip.raw(), sk.as_ptr(), c1s.as_ptr(), c2col.as_ptr(), ciphertexts.len(), valid_ptr(&v),
+                                     sys::PVW_REPR_POWER, &mut out, &mut noise, &mut status, &mut count)
+    };
+    sk.zeroize();
+    check(rc)?;
+    Ok((out, noise, status & sys::PVW_DEC_LOSSY != 0, count))
+}
+
+/// EXTENSION: every party's aggregate share in one call (`pvw_decrypt_all_sum_checked`): (values, noise, lossy) per party.
+/// `parties` must carry consecutive indices.
+pub fn decrypt_all_party_sums(ciphertexts: &[PvwCiphertext], parties: &[crate::keys::public_key::Party], valid: Option<&[bool]>) -> Result<(Vec<u64>, Vec<u64>, Vec<bool>)> {
+    let (c1s, c2s, v) = sum_inputs(ciphertexts, valid)?;
+    let params = &ciphertexts[0].params;
+    if parties.is_empty() {
+        return Ok((Vec::new(), Vec::new(), Vec::new()));
+    }
+    let lo = parties[0].index;
+    for (i, party) in parties.iter().enumerate() {
+        if party.index >= params.n {
+            return Err(PvwError::InvalidParameters(format!("Party index {} exceeds maximum {}", party.index, params.n - 1)));
+        }
+        if party.index != lo + i {
+            return Err(PvwError::InvalidParameters(format!("Party indices must be consecutive: {} follows {}", party.index, lo + i - 1)));
+        }
+    }
+    let mut sk: Vec<i64> = parties.iter().flat_map(|p| flat_secret(&p.secret_key)).collect();
+    let np = parties.len();
+    let (mut out, mut noise, mut status) = (vec![0u64; np], vec![0u64; np], vec![0u32; np]);
+    let rc = unsafe {
+        sys::pvw_decrypt_all_sum_checked(params.hip.raw(), lo as u32, (lo + np) as u32, sk.as_ptr(), c1s.as_ptr(), c2s.as_ptr(), ciphertexts.len(),
+                                         valid_ptr(&v), sys::PVW_REPR_POWER, out.as_mut_ptr(), noise.as_mut_ptr(), status.as_mut_ptr(),
+                                         std::ptr::null_mut())
+    };
+    sk.zeroize();
+    check(rc)?;
+    Ok((out, noise, status.iter().map(|s| s & sys::PVW_DEC_LOSSY != 0).collect()))
+}
