@@ -415,7 +415,7 @@ PVW_API int32_t pvw_ct_sum_host(const pvw_ctx* ctx, const uint64_t* c1s, const u
 /* One party's aggregate share: the sum over (c1, the party's column c2col [D][L][l]) of the valid dealers, then the decrypt of
  * that ONE ciphertext (decryption.rs:257-274) and its checked decode (contract unchanged): out[1], noise[1] = the
  * exact max residual of the aggregate, status[1] = PVW_DEC_LOSSY when the sum of the plaintexts is not representable
- * (>= 2^64 or negative).  noise / status / count may be NULL.  d_noisy [L][l] (power basis) is an optional output (NULL: kept
+ * (>= 2^64 or negative; pvw_decrypt_sum_plain* below return such a sum exactly, reduced or wide).  noise / status / count may be NULL.  d_noisy [L][l] (power basis) is an optional output (NULL: kept
  * in scratch and cleared).  in_repr POWER or NTT (the sum is transformed in scratch; the caller's buffers are only read).
  * Key hygiene as pvw_decrypt_batch*.  The device forms follow pvw_ct_sum_device's rules on pvw_prepare and stream capture. */
 PVW_API int32_t pvw_decrypt_sum_checked_device(pvw_ctx* ctx, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col,
@@ -446,6 +446,94 @@ PVW_API int32_t pvw_decrypt_all_sum_checked_device(pvw_ctx* ctx, uint32_t party_
  * decryption.rs:10-58 stays below Q/2 in magnitude); it is not necessary, and honest noise is far below pvw_ctx_noise_bound.
  * The reference's gate (parameters.rs:510-551) is not a decoding radius and promises nothing about an aggregate. */
 PVW_API int32_t pvw_ctx_sum_capacity(const pvw_ctx* ctx, uint64_t* max_dealers);
+
+/* ---- plain-modulus decode: exact shares and aggregates beyond 64 bits -----------------------------------
+ * PVSS shares live in Z_p, and a party wants sum_d share_d mod p; the u64 conversion at the end of the reference's decode
+ * (extract_constant_term_as_u64, decryption.rs:226-247) returns 0 once the recovered plaintext P leaves [0, 2^64), which the
+ * sum of sixteen 61-bit shares does.  These entry points finish the decode in the caller's modulus, or hand back the wide
+ * integer, on the device, in the launch that ran the chain.  P is 8.6's P: the centred plaintext before the conversion.
+ * Each entry is the checked one it names plus the plain options, three trailing arguments (a pvw_plain_t, flattened so that
+ * every argument keeps a fixed-width C type):
+ *   plain_modulus  0 = none; else 2 <= plain_modulus < 2^62, ANY integer (even, a power of two, composite):
+ *                  out[d] = P mod plain_modulus, the mathematical residue in [0, plain_modulus) -- P = -5 gives modulus - 5.
+ *                  0: out[d] is the word the checked entry point returns, bit for bit.
+ *   wide_words     0 = none; else 1 .. W, W = the 64-bit words of Q: wide[d] receives the low wide_words words of |P|.
+ *   wide           [count][wide_words], little-endian magnitude of P, laid out like out (so [P][D][wide_words] for
+ *                  pvw_decrypt_all_plain*); a device pointer in the *_device forms.
+ * noise[d] keeps its 8.6 definition.  status[d]: PVW_DEC_LOSSY keeps its meaning exactly ("the plain u64 entry point's word
+ * would not be P" -- informational here, out is exact regardless); PVW_DEC_NEGATIVE: P < 0; PVW_DEC_WIDE_TRUNCATED: |P| does
+ * not fit wide_words words (never set when wide_words == 0).  Only these entry points set the two new bits.
+ * Argument errors, PVW_ERR_INVALID_PARAMETERS before any device work: plain_modulus 1 or >= 2^62; wide_words > W;
+ * wide_words != 0 with wide NULL.  plain_modulus = 0 and wide_words = 0 make a call identical to the checked call it extends.
+ * Input side: encrypt still takes u64 scalars read as i64 (encryption.rs:195), so a share must be below 2^63 to mean itself;
+ * reduced shares with p < 2^62 always are, and a share encoded as a negative i64 comes back as its residue.
+ * Radius: the result is exact whenever the noise is inside the decoding radius pvw_ctx_sum_capacity describes; |P| itself
+ * only has to stay below Q/2 (tmp_i = z_i Delta - z_{i+1} cancels P exactly mod Q, so the noise chain does not depend on P).
+ * Key hygiene, pvw_prepare(PVW_PREPARE_SUM) and stream-capture rules are those of the call each one extends; the scratch
+ * pvw_prepare fixes covers wide at wide_words = W.  The options travel by value into the launch: a captured call replays
+ * with them. */
+typedef struct {
+  uint64_t modulus;     /* 0 = none; else 2 <= modulus < 2^62 */
+  uint32_t wide_words;  /* 0 = none; else 1 .. W */
+  uint64_t* wide;       /* [count][wide_words] */
+} pvw_plain_t;          /* the three trailing arguments below, as one value (host/pvw.hpp carries them so) */
+enum { PVW_DEC_NEGATIVE = 2, PVW_DEC_WIDE_TRUNCATED = 4 };
+PVW_API int32_t pvw_decode_plain(pvw_ctx* ctx, const uint64_t* noisy, size_t count, uint64_t* out_u64, uint64_t* noise,
+                                 uint32_t* status, uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide);
+PVW_API int32_t pvw_decode_plain_device(pvw_ctx* ctx, const uint64_t* d_noisy, size_t count, uint64_t* d_out,
+                                        uint64_t* d_noise, uint32_t* d_status, uint64_t plain_modulus, uint32_t wide_words,
+                                        uint64_t* d_wide, void* stream);
+/* host big integers, by the definition (no GPU needed) */
+PVW_API int32_t pvw_decode_plain_host(const pvw_ctx* ctx, const uint64_t* noisy, size_t count, uint64_t* out_u64,
+                                      uint64_t* noise, uint32_t* status, uint64_t plain_modulus, uint32_t wide_words,
+                                      uint64_t* wide);
+/* SELF-TEST: the fixed-width device algorithm with the plain tail, run on the host.  No product path calls it. */
+PVW_API int32_t pvw_selftest_decode_plain(const pvw_ctx* ctx, const uint64_t* noisy, size_t count, uint64_t* out_u64,
+                                          uint64_t* noise, uint32_t* status, uint64_t plain_modulus, uint32_t wide_words,
+                                          uint64_t* wide);
+PVW_API int32_t pvw_decrypt_batch_plain(pvw_ctx* ctx, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col,
+                                        size_t num_dealers, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise,
+                                        uint32_t* status, uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide);
+PVW_API int32_t pvw_decrypt_batch_plain_device(pvw_ctx* ctx, const int64_t* d_sk, const uint64_t* d_c1s,
+                                               const uint64_t* d_c2col, size_t num_dealers, uint32_t in_repr,
+                                               uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status,
+                                               uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream);
+PVW_API int32_t pvw_decrypt_batch_device_sk_plain(pvw_ctx* ctx, const pvw_sk* key, const uint64_t* d_c1s,
+                                                  const uint64_t* d_c2col, size_t num_dealers, uint32_t in_repr,
+                                                  uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status,
+                                                  uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream);
+/* wide [P][D][wide_words], inside the regions the call marks secret and clears */
+PVW_API int32_t pvw_decrypt_all_plain(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* sk,
+                                      const uint64_t* c1s, const uint64_t* c2s, size_t num_dealers, uint32_t in_repr,
+                                      uint64_t* out_u64, uint64_t* noise, uint32_t* status, uint64_t plain_modulus,
+                                      uint32_t wide_words, uint64_t* wide);
+PVW_API int32_t pvw_decrypt_all_plain_device(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* d_sk,
+                                             const uint64_t* d_c1s, const uint64_t* d_c2s, size_t num_dealers,
+                                             uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status,
+                                             uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream);
+/* the aggregate share in Z_p: out[0] = (sum over the valid dealers of the party's shares) mod plain_modulus, wide [1][wide_words] */
+PVW_API int32_t pvw_decrypt_sum_plain(pvw_ctx* ctx, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col,
+                                      size_t num_dealers, const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64,
+                                      uint64_t* noise, uint32_t* status, uint32_t* count, uint64_t plain_modulus,
+                                      uint32_t wide_words, uint64_t* wide);
+PVW_API int32_t pvw_decrypt_sum_plain_device(pvw_ctx* ctx, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col,
+                                             size_t num_dealers, const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy,
+                                             uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count,
+                                             uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream);
+PVW_API int32_t pvw_decrypt_sum_device_sk_plain(pvw_ctx* ctx, const pvw_sk* key, const uint64_t* d_c1s, const uint64_t* d_c2col,
+                                                size_t num_dealers, const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy,
+                                                uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count,
+                                                uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream);
+/* out / noise / status [P], wide [P][wide_words] */
+PVW_API int32_t pvw_decrypt_all_sum_plain(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* sk,
+                                          const uint64_t* c1s, const uint64_t* c2s, size_t num_dealers, const uint8_t* valid,
+                                          uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status, uint32_t* count,
+                                          uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide);
+PVW_API int32_t pvw_decrypt_all_sum_plain_device(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* d_sk,
+                                                 const uint64_t* d_c1s, const uint64_t* d_c2s, size_t num_dealers,
+                                                 const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise,
+                                                 uint32_t* d_status, uint32_t* d_count, uint64_t plain_modulus,
+                                                 uint32_t wide_words, uint64_t* d_wide, void* stream);
 
 /* decode_scalar_pvw_rns alone, on the device: noisy [D][L][l] power basis (host) -> out_u64 [D] */
 PVW_API int32_t pvw_decode(pvw_ctx* ctx, const uint64_t* noisy, size_t count, uint64_t* out_u64);
@@ -536,7 +624,7 @@ PVW_API int32_t pvw_ctx_derived_bytes(const pvw_ctx* ctx, uint64_t* packed_bytes
  *                       (pvw_ctx_packed_active tells; the tiled matrices are streamed then, and the allocation is
  *                       retried by later encrypts every so often);
  *   PVW_PREPARE_MFMA    the MFMA-tiled copies and digit buffers of multi-dealer encrypt (encryption.rs:253-286);
- *   PVW_PREPARE_SUM     the scratch of the pvw_ct_sum_device / pvw_decrypt_sum_* / pvw_decrypt_all_sum_checked_device calls (the
+ *   PVW_PREPARE_SUM     the scratch of the pvw_ct_sum_device / pvw_decrypt_sum_* / pvw_decrypt_all_sum_{checked,plain}_device calls (the
  *                       slice sums, the summed ciphertext, and the decrypt scratch for the context's own party range); needs
  *                       no CRS and builds no copy.
  * It allocates, waits for the builds, and returns the bytes it allocated for the copies in *bytes_out (may be NULL).

@@ -111,6 +111,21 @@ _SIGNATURES = {
     "pvw_decrypt_all_sum_checked": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, _P, _P],
     "pvw_decrypt_all_sum_checked_device": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, _P, _P, _P],
     "pvw_ctx_sum_capacity": [_P, C.POINTER(C.c_uint64)],
+    # plain-modulus decode: the checked call plus (plain_modulus, wide_words, wide)
+    "pvw_decode_plain": [_P, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.c_uint32, _P],
+    "pvw_decode_plain_device": [_P, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P],
+    "pvw_decode_plain_host": [_P, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.c_uint32, _P],
+    "pvw_selftest_decode_plain": [_P, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.c_uint32, _P],
+    "pvw_decrypt_batch_plain": [_P, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, C.c_uint64, C.c_uint32, _P],
+    "pvw_decrypt_batch_plain_device": [_P, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P],
+    "pvw_decrypt_batch_device_sk_plain": [_P, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P],
+    "pvw_decrypt_all_plain": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, C.c_uint64, C.c_uint32, _P],
+    "pvw_decrypt_all_plain_device": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P],
+    "pvw_decrypt_sum_plain": [_P, _P, _P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P],
+    "pvw_decrypt_sum_plain_device": [_P, _P, _P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P],
+    "pvw_decrypt_sum_device_sk_plain": [_P, _P, _P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P],
+    "pvw_decrypt_all_sum_plain": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P],
+    "pvw_decrypt_all_sum_plain_device": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P],
     "pvw_decode": [_P, _P, C.c_size_t, _P],
     "pvw_decode_host": [_P, _P, C.c_size_t, _P],
     "pvw_decode_device": [_P, _P, C.c_size_t, _P, _P],

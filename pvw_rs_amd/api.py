@@ -893,23 +893,50 @@ def decrypt_all_party_shares(all_ciphertexts: Sequence[PvwCiphertext], parties: 
 
 # ---- checked decryption ----
 DEC_LOSSY = 1    # status bit: the returned word is not the plaintext P (P < 0 or P >= 2^64)
+DEC_NEGATIVE = 2          # plain decode: P < 0
+DEC_WIDE_TRUNCATED = 4    # plain decode: |P| does not fit the wide words asked for
 
 
 class CheckedDecryption:
     """What a checked decrypt reports per share: values (the words the unchecked call returns), noise (min(max_i
     |residual_i|, 2^64 - 1), uint64), lossy (the value is not the plaintext) and valid = ~lossy & (noise <= bound).  Arrays
-    of one shape: [D] for one party, [parties][D] for many."""
+    of one shape: [D] for one party, [parties][D] for many.
+    Plain decode (plain_modulus= / wide= of the calls below): values are exact whatever lossy says, so valid keeps
+    the noise test only; negative / truncated are the two further status bits.  residues are the u64 words the call returned
+    (P mod plain_modulus with a modulus); values are the same unless wide=True, which makes values an object array of Python
+    integers, sign applied."""
 
-    def __init__(self, values: np.ndarray, noise: np.ndarray, status: np.ndarray, bound: int):
-        self.values = values
+    def __init__(self, values: np.ndarray, noise: np.ndarray, status: np.ndarray, bound: int, plain: bool = False,
+                 wide: Optional[np.ndarray] = None):
         self.noise = noise
         self.status = status
         self.lossy = (status & DEC_LOSSY) != 0
+        self.negative = (status & DEC_NEGATIVE) != 0
+        self.truncated = (status & DEC_WIDE_TRUNCATED) != 0
         self.bound = int(bound)
-        self.valid = ~self.lossy & (noise <= np.uint64(min(self.bound, (1 << 64) - 1)))
+        within = noise <= np.uint64(min(self.bound, (1 << 64) - 1))
+        self.valid = within if plain else ~self.lossy & within
+        self.residues = values                                              # the u64 words the call returned
+        if wide is not None:
+            flat = wide.reshape(-1, wide.shape[-1])
+            ints = np.empty(flat.shape[0], dtype=object)
+            for i, (row, ng) in enumerate(zip(flat, self.negative.reshape(-1))):
+                v = sum(int(w) << (64 * j) for j, w in enumerate(row))
+                ints[i] = -v if ng else v
+            values = ints.reshape(status.shape)
+        self.values = values
 
     def __iter__(self):                                                     # values, noise, lossy, valid = ...
         return iter((self.values, self.noise, self.lossy, self.valid))
+
+
+def _plain(p: "PvwParameters", plain_modulus, wide, shape):
+    """the plain options of a host-buffer call: (on, modulus, wide_words, wide array or None)"""
+    m = 0 if plain_modulus is None else int(plain_modulus)
+    if m and not 2 <= m < 1 << 62:
+        raise PvwError(1, "plain_modulus must be in [2, 2^62)")
+    ww = (p.q_total().bit_length() + 63) // 64 if wide else 0
+    return bool(m or ww), m, ww, (np.zeros(tuple(shape) + (ww,), dtype=np.uint64) if ww else None)
 
 
 def _bound(p: "PvwParameters", bound) -> int:
@@ -920,9 +947,11 @@ def _bound(p: "PvwParameters", bound) -> int:
 
 
 def decrypt_party_shares_checked(all_ciphertexts: Sequence[PvwCiphertext], secret_key: SecretKey, party_index: int,
-                                 bound: Optional[int] = None) -> CheckedDecryption:
+                                 bound: Optional[int] = None, *, plain_modulus: Optional[int] = None,
+                                 wide: bool = False) -> CheckedDecryption:
     """decrypt_party_shares (decryption.rs:281-325) with each share's report (pvw_decrypt_batch_checked): the same
-    checks and values, plus noise / lossy / valid against `bound` (default: noise_bound())."""
+    checks and values, plus noise / lossy / valid against `bound` (default: noise_bound()).  plain_modulus / wide: the
+    plain decode (pvw_decrypt_batch_plain) -- values mod plain_modulus, or as exact Python integers."""
     if len(all_ciphertexts) == 0:
         raise PvwError(1, "No ciphertexts provided")
     p = all_ciphertexts[0].params
@@ -935,7 +964,7 @@ def decrypt_party_shares_checked(all_ciphertexts: Sequence[PvwCiphertext], secre
             ct.validate()
         except PvwError as e:
             raise PvwError(1, f"Ciphertext {d} invalid: {e}")
-    return _decrypt_batch_checked(p, all_ciphertexts, secret_key, party_index, _bound(p, bound))
+    return _decrypt_batch_checked(p, all_ciphertexts, secret_key, party_index, _bound(p, bound), plain_modulus, wide)
 
 
 def decrypt_party_value_checked(ciphertext: PvwCiphertext, secret_key: SecretKey, party_index: int,
@@ -945,7 +974,7 @@ def decrypt_party_value_checked(ciphertext: PvwCiphertext, secret_key: SecretKey
     return int(r.values[0]), int(r.noise[0]), bool(r.lossy[0]), bool(r.valid[0])
 
 
-def _decrypt_batch_checked(p, cts, secret_key, party_index, bound) -> CheckedDecryption:
+def _decrypt_batch_checked(p, cts, secret_key, party_index, bound, plain_modulus=None, wide=False) -> CheckedDecryption:
     repr = cts[0].repr
     c1s = np.ascontiguousarray(np.stack([ct.c1 for ct in cts]), dtype=np.uint64)
     c2col = np.ascontiguousarray(np.stack([ct.c2[party_index] for ct in cts]), dtype=np.uint64)
@@ -953,14 +982,21 @@ def _decrypt_batch_checked(p, cts, secret_key, party_index, bound) -> CheckedDec
     out = np.zeros(len(cts), dtype=np.uint64)
     noise = np.zeros(len(cts), dtype=np.uint64)
     status = np.zeros(len(cts), dtype=np.uint32)
+    on, m, ww, wd = _plain(p, plain_modulus, wide, out.shape)
+    if on:
+        p._call("pvw_decrypt_batch_plain", _ptr(sk), _ptr(c1s), _ptr(c2col), len(cts), repr, _ptr(out), _ptr(noise),
+                _ptr(status), m, ww, _ptr(wd))
+        return CheckedDecryption(out, noise, status, bound, True, wd)
     p._call("pvw_decrypt_batch_checked", _ptr(sk), _ptr(c1s), _ptr(c2col), len(cts), repr, _ptr(out), _ptr(noise),
             _ptr(status))
     return CheckedDecryption(out, noise, status, bound)
 
 
 def decrypt_many_checked(ciphertexts: Sequence[PvwCiphertext], secret_keys: Sequence[SecretKey], party_lo: int,
-                         bound: Optional[int] = None) -> CheckedDecryption:
-    """decrypt_many with each share's report (pvw_decrypt_all_checked): values, noise, lossy, valid as [parties][D]."""
+                         bound: Optional[int] = None, *, plain_modulus: Optional[int] = None,
+                         wide: bool = False) -> CheckedDecryption:
+    """decrypt_many with each share's report (pvw_decrypt_all_checked): values, noise, lossy, valid as [parties][D].
+    plain_modulus / wide: the plain decode (pvw_decrypt_all_plain)."""
     if len(ciphertexts) == 0:
         raise PvwError(1, "No ciphertexts provided")
     p = ciphertexts[0].params
@@ -982,12 +1018,17 @@ def decrypt_many_checked(ciphertexts: Sequence[PvwCiphertext], secret_keys: Sequ
     out = np.zeros(shape, dtype=np.uint64)
     noise = np.zeros(shape, dtype=np.uint64)
     status = np.zeros(shape, dtype=np.uint32)
+    on, m, ww, wd = _plain(p, plain_modulus, wide, shape)
     try:
-        p._call("pvw_decrypt_all_checked", party_lo, party_lo + len(secret_keys), _ptr(sk), _ptr(c1s), _ptr(c2s),
-                len(ciphertexts), repr, _ptr(out), _ptr(noise), _ptr(status))
+        if on:
+            p._call("pvw_decrypt_all_plain", party_lo, party_lo + len(secret_keys), _ptr(sk), _ptr(c1s), _ptr(c2s),
+                    len(ciphertexts), repr, _ptr(out), _ptr(noise), _ptr(status), m, ww, _ptr(wd))
+        else:
+            p._call("pvw_decrypt_all_checked", party_lo, party_lo + len(secret_keys), _ptr(sk), _ptr(c1s), _ptr(c2s),
+                    len(ciphertexts), repr, _ptr(out), _ptr(noise), _ptr(status))
     finally:
         sk.fill(0)                                                         # the stacked copy of the keys (secret_key.rs:20-30)
-    return CheckedDecryption(out, noise, status, b)
+    return CheckedDecryption(out, noise, status, b, on, wd)
 
 
 def decrypt_all_party_shares_checked(all_ciphertexts: Sequence[PvwCiphertext], parties: Sequence["Party"],
@@ -1049,10 +1090,11 @@ def _sum_bound(p, bound, count: int) -> int:
 
 
 def decrypt_party_sum(cts: Sequence[PvwCiphertext], secret_key: SecretKey, party_index: int, valid=None,
-                      bound: Optional[int] = None) -> CheckedDecryption:
+                      bound: Optional[int] = None, *, plain_modulus: Optional[int] = None, wide: bool = False) -> CheckedDecryption:
     """Party party_index's aggregate share -- the sum of its shares from the valid dealers (examples/pvw_valid_dec.rs:201-209)
     -- from ONE decrypt of the summed ciphertext (pvw_decrypt_sum_checked).  Arrays of shape [1]; bound defaults to
-    count * noise_bound()."""
+    count * noise_bound().  plain_modulus / wide: the plain decode (pvw_decrypt_sum_plain) -- the sum of the
+    shares mod plain_modulus, or as an exact Python integer, where the u64 word of a field-sized sum is 0."""
     p, repr, v = _sum_inputs(cts, valid)
     if not 0 <= party_index < p.n:
         raise PvwError(1, f"Party index {party_index} exceeds maximum {p.n - 1}")
@@ -1060,15 +1102,22 @@ def decrypt_party_sum(cts: Sequence[PvwCiphertext], secret_key: SecretKey, party
     c2col = np.ascontiguousarray(np.stack([ct.c2[party_index] for ct in cts]), dtype=np.uint64)
     sk = _i64(secret_key.secret_coeffs)
     out, noise, status, count = np.zeros(1, np.uint64), np.zeros(1, np.uint64), np.zeros(1, np.uint32), C.c_uint32()
-    p._call("pvw_decrypt_sum_checked", _ptr(sk), _ptr(c1s), _ptr(c2col), len(cts), _ptr(v), repr, _ptr(out), _ptr(noise),
-            _ptr(status), C.byref(count))
-    return CheckedDecryption(out, noise, status, _sum_bound(p, bound, count.value))
+    on, m, ww, wd = _plain(p, plain_modulus, wide, out.shape)
+    if on:
+        p._call("pvw_decrypt_sum_plain", _ptr(sk), _ptr(c1s), _ptr(c2col), len(cts), _ptr(v), repr, _ptr(out), _ptr(noise),
+                _ptr(status), C.byref(count), m, ww, _ptr(wd))
+    else:
+        p._call("pvw_decrypt_sum_checked", _ptr(sk), _ptr(c1s), _ptr(c2col), len(cts), _ptr(v), repr, _ptr(out), _ptr(noise),
+                _ptr(status), C.byref(count))
+    return CheckedDecryption(out, noise, status, _sum_bound(p, bound, count.value), on, wd)
 
 
 def decrypt_all_party_sums(cts: Sequence[PvwCiphertext], parties: Sequence["Party"], valid=None,
-                           bound: Optional[int] = None) -> CheckedDecryption:
+                           bound: Optional[int] = None, *, plain_modulus: Optional[int] = None,
+                           wide: bool = False) -> CheckedDecryption:
     """Every party's aggregate share in one call (pvw_decrypt_all_sum_checked): arrays of shape [len(parties)].  The parties
-    must have consecutive indices; bound defaults to count * noise_bound()."""
+    must have consecutive indices; bound defaults to count * noise_bound().  plain_modulus / wide: the plain decode
+    (pvw_decrypt_all_sum_plain)."""
     p, repr, v = _sum_inputs(cts, valid)
     count = int(v.sum()) if v is not None else len(cts)
     b = _sum_bound(p, bound, count)
@@ -1084,12 +1133,17 @@ def decrypt_all_party_sums(cts: Sequence[PvwCiphertext], parties: Sequence["Part
     c2s = np.ascontiguousarray(np.stack([ct.c2 for ct in cts]), dtype=np.uint64)
     sk = np.ascontiguousarray(np.stack([_i64(party.secret_key.secret_coeffs) for party in parties]))
     out, noise, status = np.zeros(len(parties), np.uint64), np.zeros(len(parties), np.uint64), np.zeros(len(parties), np.uint32)
+    on, m, ww, wd = _plain(p, plain_modulus, wide, out.shape)
     try:
-        p._call("pvw_decrypt_all_sum_checked", lo, lo + len(parties), _ptr(sk), _ptr(c1s), _ptr(c2s), len(cts), _ptr(v), repr,
-                _ptr(out), _ptr(noise), _ptr(status), None)
+        if on:
+            p._call("pvw_decrypt_all_sum_plain", lo, lo + len(parties), _ptr(sk), _ptr(c1s), _ptr(c2s), len(cts), _ptr(v), repr,
+                    _ptr(out), _ptr(noise), _ptr(status), None, m, ww, _ptr(wd))
+        else:
+            p._call("pvw_decrypt_all_sum_checked", lo, lo + len(parties), _ptr(sk), _ptr(c1s), _ptr(c2s), len(cts), _ptr(v), repr,
+                    _ptr(out), _ptr(noise), _ptr(status), None)
     finally:
         sk.fill(0)                                                         # the stacked copy of the keys (secret_key.rs:20-30)
-    return CheckedDecryption(out, noise, status, b)
+    return CheckedDecryption(out, noise, status, b, on, wd)
 
 
 def _dptr(x):
@@ -1116,21 +1170,35 @@ class DeviceSecretKey:
             _check(_ffi.lib().pvw_sk_free(h))
 
     def decrypt_device_checked(self, d_c1s, d_c2col, num_dealers: int, d_noisy, d_out, d_noise=None, d_status=None,
-                               stream=None, in_repr: int = REPR_NTT) -> None:
+                               stream=None, in_repr: int = REPR_NTT, *, plain_modulus: Optional[int] = None, wide=None,
+                               wide_words: int = 0) -> None:
         """pvw_decrypt_batch_device_sk_checked: device buffers (torch tensors or raw addresses) -- d_out [D] the values,
-        d_noise [D] uint64 and d_status [D] uint32 the report (either may be None); asynchronous on `stream`."""
+        d_noise [D] uint64 and d_status [D] uint32 the report (either may be None); asynchronous on `stream`.
+        plain_modulus / wide (a device buffer [D][wide_words]): pvw_decrypt_batch_device_sk_plain."""
         if not self._h:
             raise PvwError(1, "the DeviceSecretKey has been freed")
+        if plain_modulus or wide is not None:
+            self.params._call("pvw_decrypt_batch_device_sk_plain", self._h, _dptr(d_c1s), _dptr(d_c2col), int(num_dealers),
+                              in_repr, _dptr(d_noisy), _dptr(d_out), _dptr(d_noise), _dptr(d_status), int(plain_modulus or 0),
+                              int(wide_words), _dptr(wide), _stream_ptr(stream))
+            return
         self.params._call("pvw_decrypt_batch_device_sk_checked", self._h, _dptr(d_c1s), _dptr(d_c2col), int(num_dealers),
                           in_repr, _dptr(d_noisy), _dptr(d_out), _dptr(d_noise), _dptr(d_status), _stream_ptr(stream))
 
     def decrypt_sum_device_checked(self, d_c1s, d_c2col, num_dealers: int, d_out, d_valid=None, d_noisy=None, d_noise=None,
-                                   d_status=None, d_count=None, stream=None, in_repr: int = REPR_NTT) -> None:
+                                   d_status=None, d_count=None, stream=None, in_repr: int = REPR_NTT, *,
+                                   plain_modulus: Optional[int] = None, wide=None, wide_words: int = 0) -> None:
         """pvw_decrypt_sum_device_sk_checked: this party's aggregate share from ONE decrypt of the sum of the valid dealers'
         ciphertexts.  Device buffers: d_valid uint8 [D] (None = all), d_out / d_noise / d_status [1], d_count uint32 [1];
-        asynchronous on `stream`."""
+        asynchronous on `stream`.  plain_modulus / wide (a device buffer [wide_words]): pvw_decrypt_sum_device_sk_plain
+        (DESIGN 8.8)."""
         if not self._h:
             raise PvwError(1, "the DeviceSecretKey has been freed")
+        if plain_modulus or wide is not None:
+            self.params._call("pvw_decrypt_sum_device_sk_plain", self._h, _dptr(d_c1s), _dptr(d_c2col), int(num_dealers),
+                              _dptr(d_valid), in_repr, _dptr(d_noisy), _dptr(d_out), _dptr(d_noise), _dptr(d_status),
+                              _dptr(d_count), int(plain_modulus or 0), int(wide_words), _dptr(wide), _stream_ptr(stream))
+            return
         self.params._call("pvw_decrypt_sum_device_sk_checked", self._h, _dptr(d_c1s), _dptr(d_c2col), int(num_dealers),
                           _dptr(d_valid), in_repr, _dptr(d_noisy), _dptr(d_out), _dptr(d_noise), _dptr(d_status), _dptr(d_count),
                           _stream_ptr(stream))
@@ -1292,6 +1360,36 @@ def decode_scalar_pvw_checked_host(params: PvwParameters, noisy: np.ndarray, bou
 def _selftest_decode_checked(params: PvwParameters, noisy: np.ndarray) -> CheckedDecryption:
     """Host run of the fixed-width device decode with its report (self-test hook, see pvw_hip.h)."""
     return _decode_checked(params, noisy, "pvw_selftest_decode_checked", 0)
+
+
+def _decode_plain(params: PvwParameters, noisy, fn: str, bound, plain_modulus, wide_words) -> CheckedDecryption:
+    """the plain decode of [count][L][l] polynomials: wide_words None = every word of Q, 0 = none"""
+    a = _u64(noisy).reshape(-1, params.L, params.l)
+    out = np.zeros(len(a), dtype=np.uint64)
+    noise = np.zeros(len(a), dtype=np.uint64)
+    status = np.zeros(len(a), dtype=np.uint32)
+    m = int(plain_modulus or 0)
+    ww = (params.q_total().bit_length() + 63) // 64 if wide_words is None else int(wide_words)
+    wd = np.zeros((len(a), ww), dtype=np.uint64) if ww else None
+    params._call(fn, _ptr(a), len(a), _ptr(out), _ptr(noise), _ptr(status), m, ww, _ptr(wd))
+    return CheckedDecryption(out, noise, status, _bound(params, bound), bool(m or ww), wd)
+
+
+def decode_scalar_pvw_plain(params: PvwParameters, noisy: np.ndarray, plain_modulus: Optional[int] = None, wide_words: Optional[int] = 0,
+                            bound: Optional[int] = None) -> CheckedDecryption:
+    """decode_scalar_pvw_checked finished in the caller's modulus and / or as wide integers (pvw_decode_plain, on the device)."""
+    return _decode_plain(params, noisy, "pvw_decode_plain", bound, plain_modulus, wide_words)
+
+
+def decode_scalar_pvw_plain_host(params: PvwParameters, noisy: np.ndarray, plain_modulus: Optional[int] = None,
+                                 wide_words: Optional[int] = 0, bound: Optional[int] = None) -> CheckedDecryption:
+    """The same with host big integers, by the definition (pvw_decode_plain_host; no GPU)."""
+    return _decode_plain(params, noisy, "pvw_decode_plain_host", bound, plain_modulus, wide_words)
+
+
+def _selftest_decode_plain(params: PvwParameters, noisy: np.ndarray, plain_modulus=None, wide_words=0) -> CheckedDecryption:
+    """Host run of the fixed-width device decode with the plain tail (self-test hook, see pvw_hip.h)."""
+    return _decode_plain(params, noisy, "pvw_selftest_decode_plain", 0, plain_modulus, wide_words)
 
 
 # ---- wire format, version 1 (DESIGN 9) ----

@@ -156,11 +156,16 @@ static void ws_mark_secret(Workspace* w, void* p, size_t bytes, bool cleared = f
 }
 // enqueue the wipes on `s` (call after the last kernel that reads the regions has been enqueued on `s`); nothing
 // marked: nothing enqueued, and the record of the last wipe stays
+// Under stream capture the wipes are kernels, not memset nodes: a captured call has to clear its regions on every replay, in
+// order (pvw_selftest_secret_residue after a replay found regions cleared by memset nodes not cleared).
+static bool stream_capturing(hipStream_t s);
 static hipError_t ws_wipe_secrets(Workspace* w, hipStream_t s) {
   if (w->secrets.empty()) return hipSuccess;
   hipError_t rc = hipSuccess;
+  const bool by_kernel = stream_capturing(s);
   for (const Workspace::Span& sp : w->secrets) {
-    hipError_t e = sp.cleared ? hipSuccess : hipMemsetAsync(sp.p, 0, sp.bytes, s);
+    hipError_t e = hipSuccess;
+    if (!sp.cleared) e = by_kernel && sp.bytes % 8 == 0 ? launch_wipe_words((u64*)sp.p, sp.bytes / 8, s) : hipMemsetAsync(sp.p, 0, sp.bytes, s);
     if (e != hipSuccess) rc = e;
   }
   w->wiped = w->secrets;
@@ -2124,11 +2129,20 @@ int32_t pvw_decode_host(const pvw_ctx* c, const uint64_t* noisy, size_t count, u
 
 // checked decode on the host: residual_i = centre(-z_i - P Delta^i) by the definition, in big integers (not the
 // recurrence the device runs); noise = min(max_i |residual_i|, 2^64 - 1), status = DEC_LOSSY when out is not P
-static void decode_checked_one(const pvw_ctx* c, const uint64_t* noisy, u64* out, u64* noise, u32* status) {
+// plain decode on the host, by the definition: modulus != 0: out = P mod modulus in [0, modulus); wide_words != 0:
+// the low words of |P| to wide; status also says P < 0 and |P| not fitting the wide words
+static void decode_checked_one(const pvw_ctx* c, const uint64_t* noisy, u64* out, u64* noise, u32* status, u64 modulus = 0,
+                               u32 wide_words = 0, u64* wide = nullptr) {
   std::vector<BigInt> z;
   const BigInt plain = decode_plain(c, noisy, z);
-  *out = decode_convert(c, plain);
-  if (status) *status = (plain.is_negative() || !plain.fits_u64()) ? (u32)DEC_LOSSY : 0u;
+  *out = modulus ? plain.mod_small(modulus) : decode_convert(c, plain);
+  u32 st = (plain.is_negative() || !plain.fits_u64()) ? (u32)DEC_LOSSY : 0u;
+  if (modulus || wide_words) {
+    if (plain.is_negative()) st |= DEC_NEGATIVE;
+    if (wide_words && plain.mag.size() > wide_words) st |= DEC_WIDE_TRUNCATED;
+    for (u32 w = 0; w < wide_words; ++w) wide[w] = w < plain.mag.size() ? plain.mag[w] : 0;
+  }
+  if (status) *status = st;
   if (!noise) return;
   const BigInt sat(~(u64)0);
   BigInt dpow(1), mx;
@@ -2140,9 +2154,27 @@ static void decode_checked_one(const pvw_ctx* c, const uint64_t* noisy, u64* out
   }
   *noise = BigInt::cmp(mx, sat) >= 0 ? PVW_NOISE_SAT : mx.low_u64();
 }
-int32_t pvw_decode_checked_host(const pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out, uint64_t* noise,
-                                uint32_t* status) {
-  if (!c || ((!noisy || !out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+// The plain options of one call, checked before any device work: modulus 0 (none) or 2 <= modulus < 2^62, any
+// integer; wide_words 0 (none) or 1 .. W, W = the 64-bit words of Q; wide [count][wide_words] where wide_words != 0.
+static int32_t plain_args(const pvw_ctx* c, u64 modulus, u32 wide_words, u64* wide, PlainArgs* pa) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (modulus == 1 || (modulus >> 62)) return fail(PVW_ERR_INVALID_PARAMETERS, "plain modulus must be 0 (none) or in [2, 2^62)");
+  if (wide_words > c->Q.mag.size()) {
+    char buf[96];
+    snprintf(buf, sizeof buf, "wide_words %u exceeds the %zu words of Q", wide_words, c->Q.mag.size());
+    return fail(PVW_ERR_INVALID_PARAMETERS, buf);
+  }
+  if (wide_words && !wide) return fail(PVW_ERR_INVALID_PARAMETERS, "wide_words without a wide buffer");
+  pa->m = modulus ? make_mod(modulus) : Mod{0, 0, 0};
+  pa->wide_words = wide_words;
+  pa->wide = wide_words ? wide : nullptr;
+  return PVW_OK;
+}
+int32_t pvw_decode_plain_host(const pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out, uint64_t* noise,
+                              uint32_t* status, uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
+  PlainArgs pa;
+  PVW_TRY(plain_args(c, plain_modulus, wide_words, wide, &pa));
+  if ((!noisy || !out) && count) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   const size_t P = c->poly();
   unsigned nt = std::thread::hardware_concurrency();
   if (nt == 0) nt = 1;
@@ -2150,7 +2182,8 @@ int32_t pvw_decode_checked_host(const pvw_ctx* c, const uint64_t* noisy, size_t 
   if (count < 64) nt = 1;
   auto run = [=](size_t d0, size_t step) {
     for (size_t d = d0; d < count; d += step)
-      decode_checked_one(c, noisy + d * P, out + d, noise ? noise + d : nullptr, status ? status + d : nullptr);
+      decode_checked_one(c, noisy + d * P, out + d, noise ? noise + d : nullptr, status ? status + d : nullptr, plain_modulus,
+                         wide_words, wide_words ? wide + d * wide_words : nullptr);
   };
   if (nt == 1) {
     run(0, 1);
@@ -2160,6 +2193,11 @@ int32_t pvw_decode_checked_host(const pvw_ctx* c, const uint64_t* noisy, size_t 
   for (unsigned t = 0; t < nt; ++t) th.emplace_back(run, (size_t)t, (size_t)nt);
   for (auto& x : th) x.join();
   return PVW_OK;
+}
+int32_t pvw_decode_checked_host(const pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out, uint64_t* noise,
+                                uint32_t* status) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  return pvw_decode_plain_host(c, noisy, count, out, noise, status, 0, 0, nullptr);
 }
 
 #if PVW_TUNING
@@ -2252,6 +2290,22 @@ int32_t pvw_selftest_decode_checked(const pvw_ctx* c, const uint64_t* noisy, siz
   for (size_t d = 0; d < count; ++d)
     out[d] = decode_one_fixed<true>(t, noisy + d * c->poly(), BN{x.data(), 1}, BN{y.data(), 1}, BN{nres.data(), 1},
                                       noise ? noise + d : nullptr, status ? status + d : nullptr);
+  return PVW_OK;
+}
+
+// the plain form of the same: decode_one_fixed<true, true>, the tail the fixed-width kernel runs
+int32_t pvw_selftest_decode_plain(const pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out, uint64_t* noise,
+                                  uint32_t* status, uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
+  PlainArgs pa;
+  PVW_TRY(plain_args(c, plain_modulus, wide_words, wide, &pa));
+  if ((!noisy || !out) && count) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (!pa.m.q && !pa.wide_words) return pvw_selftest_decode_checked(c, noisy, count, out, noise, status);
+  const DecodeTables& t = c->dec_host;
+  std::vector<u64> x(t.W + 1), y(t.W), nres(t.L);
+  for (size_t d = 0; d < count; ++d)
+    out[d] = decode_one_fixed<true, true>(t, noisy + d * c->poly(), BN{x.data(), 1}, BN{y.data(), 1}, BN{nres.data(), 1},
+                                            noise ? noise + d : nullptr, status ? status + d : nullptr, &pa,
+                                            pa.wide_words ? wide + d * pa.wide_words : nullptr);
   return PVW_OK;
 }
 
@@ -2354,47 +2408,86 @@ int32_t pvw_selftest_decode_shortcuts(const pvw_ctx* c, const uint64_t* noisy, s
 // checked decode's report (NULL: not asked for); wipe / wipe_bytes / wiped: as launch_decode.
 static int32_t decode_tail(pvw_ctx* c, u64* nz, size_t cnt, bool ntt_domain, bool shared, hipStream_t s, u64* out,
                            u64* noise = nullptr, u32* status = nullptr, u64* wipe = nullptr, size_t wipe_bytes = 0,
-                           bool* wiped = nullptr) {
+                           bool* wiped = nullptr, const PlainArgs* pl = nullptr) {
   if (ntt_domain && (shared || (cnt + 1) / 2 > (size_t)2 * c->num_cus)) {
     ProfScope pi(c, "intt", s);
     PVW_HIP(launch_ntt(nz, cnt, true, c->dt, c->L, c->l, s));
     ntt_domain = false;
   }
   ProfScope ps(c, "decode", s);
-  PVW_HIP(launch_decode(nz, out, cnt, c->dec_dev, s, ntt_domain ? &c->dt : nullptr, wipe, wipe_bytes, wiped, noise, status));
+  PVW_HIP(launch_decode(nz, out, cnt, c->dec_dev, s, ntt_domain ? &c->dt : nullptr, wipe, wipe_bytes, wiped, noise, status, pl));
   return PVW_OK;
 }
+// the options with the wide words of ciphertext `first` of the call's at the front; NULL when no option is set (the callee then
+// runs the checked decode as it is)
+struct PlainAt {
+  PlainArgs a;
+  bool on;
+  PlainAt(const PlainArgs* pl, u64* wide_base, size_t first) : a{}, on(false) {
+    if (!pl || (!pl->m.q && !pl->wide_words)) return;
+    a = *pl;
+    a.wide = a.wide_words ? wide_base + first * a.wide_words : nullptr;
+    on = true;
+  }
+  PlainAt(const PlainArgs* pl, size_t first) : PlainAt(pl, pl ? pl->wide : nullptr, first) {}
+  const PlainArgs* ptr() const { return on ? &a : nullptr; }
+};
+static size_t plain_ww(const PlainArgs* pl) { return pl ? pl->wide_words : 0; }
 
 // decode_scalar_pvw_rns on the device; checked: plus noise[d] / status[d] (either may be NULL)
-int32_t pvw_decode_checked_device(pvw_ctx* c, const uint64_t* d_noisy, size_t count, uint64_t* d_out, uint64_t* d_noise,
-                                  uint32_t* d_status, void* stream) {
+static int32_t decode_device_core(pvw_ctx* c, const uint64_t* d_noisy, size_t count, uint64_t* d_out, uint64_t* d_noise,
+                                  uint32_t* d_status, void* stream, const PlainArgs* pl) {
   if (!c || ((!d_noisy || !d_out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   if (count == 0) return PVW_OK;
   PVW_TRY(ensure_device(c));
   // power basis in: read only
-  return decode_tail(c, const_cast<u64*>(d_noisy), count, false, false, call_stream(c, stream), d_out, d_noise, d_status);
+  return decode_tail(c, const_cast<u64*>(d_noisy), count, false, false, call_stream(c, stream), d_out, d_noise, d_status, nullptr, 0,
+                     nullptr, PlainAt(pl, 0).ptr());
+}
+int32_t pvw_decode_checked_device(pvw_ctx* c, const uint64_t* d_noisy, size_t count, uint64_t* d_out, uint64_t* d_noise,
+                                  uint32_t* d_status, void* stream) {
+  return decode_device_core(c, d_noisy, count, d_out, d_noise, d_status, stream, nullptr);
+}
+// plain forms: the checked call plus the plain options
+int32_t pvw_decode_plain_device(pvw_ctx* c, const uint64_t* d_noisy, size_t count, uint64_t* d_out, uint64_t* d_noise,
+                                uint32_t* d_status, uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream) {
+  PlainArgs pa;
+  PVW_TRY(plain_args(c, plain_modulus, wide_words, d_wide, &pa));
+  return decode_device_core(c, d_noisy, count, d_out, d_noise, d_status, stream, &pa);
 }
 int32_t pvw_decode_device(pvw_ctx* c, const uint64_t* d_noisy, size_t count, uint64_t* d_out, void* stream) {
   return pvw_decode_checked_device(c, d_noisy, count, d_out, nullptr, nullptr, stream);
 }
 // host buffers in and out
-int32_t pvw_decode_checked(pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out, uint64_t* noise, uint32_t* status) {
+static int32_t decode_staged(pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out, uint64_t* noise, uint32_t* status,
+                             const PlainArgs* pl) {
   if (!c || ((!noisy || !out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   if (count == 0) return PVW_OK;
   PVW_TRY(ensure_device(c));
+  const size_t ww = plain_ww(pl);
   Scratch sc;
   const size_t r_nz = sc.add(count * c->poly() * 8), r_out = sc.add(count * 8), r_ns = sc.add(noise ? count * 8 : 0),
-               r_st = sc.add(status ? count * 4 : 0);
+               r_st = sc.add(status ? count * 4 : 0), r_wd = sc.add(count * ww * 8);
   return host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
     PVW_HIP(hipMemcpyAsync(sc.at(r_nz), noisy, count * c->poly() * 8, hipMemcpyHostToDevice, w->stream));
     PVW_TRY(decode_tail(c, sc.at(r_nz), count, false, false, w->stream, sc.at(r_out), noise ? sc.at(r_ns) : nullptr,
-                        status ? sc.at<u32>(r_st) : nullptr));
+                        status ? sc.at<u32>(r_st) : nullptr, nullptr, 0, nullptr, PlainAt(pl, sc.at(r_wd), 0).ptr()));
     PVW_HIP(hipMemcpyAsync(out, sc.at(r_out), count * 8, hipMemcpyDeviceToHost, w->stream));
     if (noise) PVW_HIP(hipMemcpyAsync(noise, sc.at(r_ns), count * 8, hipMemcpyDeviceToHost, w->stream));
     if (status) PVW_HIP(hipMemcpyAsync(status, sc.at(r_st), count * 4, hipMemcpyDeviceToHost, w->stream));
+    if (ww) PVW_HIP(hipMemcpyAsync(pl->wide, sc.at(r_wd), count * ww * 8, hipMemcpyDeviceToHost, w->stream));
     return PVW_OK;
   });
+}
+int32_t pvw_decode_checked(pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out, uint64_t* noise, uint32_t* status) {
+  return decode_staged(c, noisy, count, out, noise, status, nullptr);
+}
+int32_t pvw_decode_plain(pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out, uint64_t* noise, uint32_t* status,
+                         uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
+  PlainArgs pa;
+  PVW_TRY(plain_args(c, plain_modulus, wide_words, wide, &pa));
+  return decode_staged(c, noisy, count, out, noise, status, &pa);
 }
 int32_t pvw_decode(pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out) {
   return pvw_decode_checked(c, noisy, count, out, nullptr, nullptr);
@@ -2437,7 +2530,7 @@ static int32_t decrypt_mac_only(pvw_ctx* c, Workspace* w, const u64* d_c1s, cons
 // HBM-bound MAC of chunk i+1; `s` waits for the last decode before the call's work counts as complete.
 static int32_t decrypt_batch_enqueue(pvw_ctx* c, Workspace* w, hipStream_t s, const int64_t* d_sk, const u64* key_shat,
                                      const u64* d_c1s, const u64* d_c2col, size_t D, u64* d_noisy, u64* d_out, u64* d_noise,
-                                     u32* d_status) {
+                                     u32* d_status, const PlainArgs* pl = nullptr) {
   const u32 k = c->k, l = c->l, L = c->L;
   const size_t P = c->poly(), shat_bytes = (size_t)k * P * 8;
   // chunks of about 2 GiB of ciphertext (measured: at config 5 in full, 18 GB, overlapping the decode is -7 %;
@@ -2472,7 +2565,7 @@ static int32_t decrypt_batch_enqueue(pvw_ctx* c, Workspace* w, hipStream_t s, co
     bool by_decode = false;
     PVW_TRY(decode_tail(c, nz, cnt, ntt_domain, overlap, ds, d_out + d0, d_noise ? d_noise + d0 : nullptr,
                         d_status ? d_status + d0 : nullptr, decode_wipes ? w->rhat : nullptr, decode_wipes ? shat_bytes : 0,
-                        &by_decode));
+                        &by_decode, PlainAt(pl, d0).ptr()));
     if (by_decode) ws_mark_secret(w, w->rhat, shat_bytes, true);   // recorded as this call's wiped region, no memset
   }
   if (overlap) {
@@ -2484,7 +2577,7 @@ static int32_t decrypt_batch_enqueue(pvw_ctx* c, Workspace* w, hipStream_t s, co
 // the device-pointer entry points: their argument checks, then the enqueue on the caller's stream
 static int32_t decrypt_batch_core(pvw_ctx* c, const int64_t* d_sk, const u64* key_shat, const uint64_t* d_c1s, const uint64_t* d_c2col,
                                   size_t D, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, void* stream,
-                                  uint64_t* d_noise = nullptr, uint32_t* d_status = nullptr) {
+                                  uint64_t* d_noise = nullptr, uint32_t* d_status = nullptr, const PlainArgs* pl = nullptr) {
   if (!c || ((!d_c1s || !d_c2col || !d_noisy || !d_out) && D)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   PVW_TRY(check_repr(in_repr));
   if (in_repr != PVW_REPR_NTT) return fail(PVW_ERR_INVALID_FORMAT, "device decrypt takes NTT-domain ciphertexts");
@@ -2493,7 +2586,7 @@ static int32_t decrypt_batch_core(pvw_ctx* c, const int64_t* d_sk, const u64* ke
   hipStream_t s;
   Workspace* w;
   PVW_TRY(device_ws(c, stream, &s, &w));
-  return device_end(w, s, decrypt_batch_enqueue(c, w, s, d_sk, key_shat, d_c1s, d_c2col, D, d_noisy, d_out, d_noise, d_status));
+  return device_end(w, s, decrypt_batch_enqueue(c, w, s, d_sk, key_shat, d_c1s, d_c2col, D, d_noisy, d_out, d_noise, d_status, pl));
 }
 
 int32_t pvw_decrypt_noisy_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col,
@@ -2526,7 +2619,8 @@ int32_t pvw_decrypt_noisy_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t
 // host buffers: dealers in chunks of <= 1 GiB of ciphertext, staged on the device (a POWER-basis chunk transformed there) and
 // decrypted by the device path; the uploaded coefficients and NTT(sk) do not outlive the call (secret_key.rs:20-30)
 static int32_t decrypt_batch_staged(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
-                                    uint32_t in_repr, uint64_t* out_u64, uint64_t* noisy_out, uint64_t* noise, uint32_t* status) {
+                                    uint32_t in_repr, uint64_t* out_u64, uint64_t* noisy_out, uint64_t* noise, uint32_t* status,
+                                    const PlainArgs* pl = nullptr) {
   if (!c || !sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");          // decryption.rs:286-290
   if (!c1s || !c2col || !out_u64) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
@@ -2539,6 +2633,7 @@ static int32_t decrypt_batch_staged(pvw_ctx* c, const int64_t* sk, const uint64_
   Scratch sc;
   const size_t r_sk = sc.add(k * l * 8), r_c1 = sc.add(per * k * P * 8), r_c2 = sc.add(per * P * 8), r_nz = sc.add(per * P * 8),
                r_out = sc.add(per * 8), r_ns = sc.add(noise ? per * 8 : 0), r_st = sc.add(status ? per * 4 : 0);
+  const size_t ww = plain_ww(pl), r_wd = sc.add(per * ww * 8);
   return host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
     i64* d_sk = sc.at<i64>(r_sk);
@@ -2555,10 +2650,11 @@ static int32_t decrypt_batch_staged(pvw_ctx* c, const int64_t* sk, const uint64_
         PVW_HIP(launch_ntt(d_c2, cnt, false, c->dt, c->L, c->l, w->stream));
       }
       PVW_TRY(decrypt_batch_enqueue(c, w, w->stream, d_sk, nullptr, d_c1, d_c2, cnt, d_nz, d_out, noise ? sc.at(r_ns) : nullptr,
-                                    status ? sc.at<u32>(r_st) : nullptr));
+                                    status ? sc.at<u32>(r_st) : nullptr, PlainAt(pl, sc.at(r_wd), 0).ptr()));
       PVW_HIP(hipMemcpyAsync(out_u64 + d0, d_out, cnt * 8, hipMemcpyDeviceToHost, w->stream));
       if (noise) PVW_HIP(hipMemcpyAsync(noise + d0, sc.at(r_ns), cnt * 8, hipMemcpyDeviceToHost, w->stream));
       if (status) PVW_HIP(hipMemcpyAsync(status + d0, sc.at(r_st), cnt * 4, hipMemcpyDeviceToHost, w->stream));
+      if (ww) PVW_HIP(hipMemcpyAsync(pl->wide + d0 * ww, sc.at(r_wd), cnt * ww * 8, hipMemcpyDeviceToHost, w->stream));
       if (noisy_out) PVW_HIP(hipMemcpyAsync(noisy_out + d0 * P, d_nz, cnt * P * 8, hipMemcpyDeviceToHost, w->stream));
     }
     return PVW_OK;
@@ -2571,6 +2667,13 @@ int32_t pvw_decrypt_batch(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, co
 int32_t pvw_decrypt_batch_checked(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
                                   uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status) {
   return decrypt_batch_staged(c, sk, c1s, c2col, D, in_repr, out_u64, nullptr, noise, status);
+}
+int32_t pvw_decrypt_batch_plain(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D, uint32_t in_repr,
+                                uint64_t* out_u64, uint64_t* noise, uint32_t* status, uint64_t plain_modulus, uint32_t wide_words,
+                                uint64_t* wide) {
+  PlainArgs pa;
+  PVW_TRY(plain_args(c, plain_modulus, wide_words, wide, &pa));
+  return decrypt_batch_staged(c, sk, c1s, c2col, D, in_repr, out_u64, nullptr, noise, status, &pa);
 }
 
 // A secret key kept on the device in the form the inner products read (NTT(sk[j]) in the ciphertext layout,
@@ -2605,6 +2708,25 @@ int32_t pvw_decrypt_batch_device_sk_checked(pvw_ctx* c, const pvw_sk* key, const
   if (!c || !key || !key->shat) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   if (key->ctx != c) return fail(PVW_ERR_INVALID_PARAMETERS, "the key was loaded for another context");
   return decrypt_batch_core(c, nullptr, key->shat, d_c1s, d_c2col, D, in_repr, d_noisy, d_out, stream, d_noise, d_status);
+}
+// plain forms
+int32_t pvw_decrypt_batch_plain_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
+                                       uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status,
+                                       uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream) {
+  if (!c || !d_sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PlainArgs pa;
+  PVW_TRY(plain_args(c, plain_modulus, wide_words, d_wide, &pa));
+  return decrypt_batch_core(c, d_sk, nullptr, d_c1s, d_c2col, D, in_repr, d_noisy, d_out, stream, d_noise, d_status, &pa);
+}
+int32_t pvw_decrypt_batch_device_sk_plain(pvw_ctx* c, const pvw_sk* key, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
+                                          uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise,
+                                          uint32_t* d_status, uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide,
+                                          void* stream) {
+  if (!c || !key || !key->shat) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (key->ctx != c) return fail(PVW_ERR_INVALID_PARAMETERS, "the key was loaded for another context");
+  PlainArgs pa;
+  PVW_TRY(plain_args(c, plain_modulus, wide_words, d_wide, &pa));
+  return decrypt_batch_core(c, nullptr, key->shat, d_c1s, d_c2col, D, in_repr, d_noisy, d_out, stream, d_noise, d_status, &pa);
 }
 int32_t pvw_sk_load(pvw_ctx* c, const int64_t* sk, pvw_sk** out) {
   if (!c || !sk || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
@@ -2677,7 +2799,8 @@ static int32_t decrypt_all_checks(pvw_ctx* c, u32 lo, u32 hi, const void* sk, co
 // noise / status (either may be NULL, same side as out): the checked decode's report, [P][D] like out
 static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, u32 hi, const int64_t* sk, const u64* c1s,
                                const u64* c2s, size_t D, uint32_t in_repr, u64* out, bool host, u64* noise = nullptr,
-                               u32* status = nullptr, size_t* need_only = nullptr) {
+                               u32* status = nullptr, size_t* need_only = nullptr, const PlainArgs* pl = nullptr) {
+  const size_t ww = plain_ww(pl);                        // plain decode: wide [P][D][ww] like out, same side
   const u32 k = c->k, l = c->l, L = c->L;
   const size_t P = c->poly(), NP = (size_t)hi - lo;
   const size_t ctw = (size_t)k * P;                      // words of one dealer's c1
@@ -2695,17 +2818,18 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
     Scratch sc;
     const size_t r_sk = sc.add(host ? NP * k * l * 8 : 0), r_c1 = sc.add(stage ? Dc * ctw * 8 : 0), r_c2 = sc.add(Dc * P * 8),
                  r_nz = sc.add(Dc * P * 8), r_out = sc.add(host ? Dc * 8 : 0), r_ns = sc.add(host && noise ? Dc * 8 : 0),
-                 r_st = sc.add(host && status ? Dc * 4 : 0);
+                 r_st = sc.add(host && status ? Dc * 4 : 0), r_wd = sc.add(host ? Dc * ww * 8 : 0);
     if (need_only) { *need_only = sc.total; return PVW_OK; }   // the scratch this call would take, nothing else
     PVW_TRY(sc.take(w));
     i64* d_sk = sc.at<i64>(r_sk);
     u64 *d_c1 = sc.at(r_c1), *d_c2 = sc.at(r_c2), *d_nz = sc.at(r_nz), *d_out = sc.at(r_out), *d_ns = sc.at(r_ns);
     u32* d_st = sc.at<u32>(r_st);
+    u64* d_wd = sc.at(r_wd);
     // key material: the uploaded coefficients, NTT(sk) (w->rhat), the noisy polynomials (m g-hat + noise), the decoded values
-    // and their reports
+    // and their reports, wide words included
     sc.secret(w, r_sk, r_sk);
     ws_mark_secret(w, w->rhat, (size_t)k * P * 8);
-    sc.secret(w, r_nz, r_st);
+    sc.secret(w, r_nz, r_wd);
     if (host) PVW_HIP(hipMemcpyAsync(d_sk, sk, NP * k * l * 8, hipMemcpyHostToDevice, s));
     const i64* skd = host ? d_sk : sk;
     for (size_t d0 = 0; d0 < D; d0 += Dc) {
@@ -2731,7 +2855,9 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
         u64* o = out + p * D + d0;
         u64* on = noise ? noise + p * D + d0 : nullptr;
         u32* os = status ? status + p * D + d0 : nullptr;
-        PVW_TRY(decode_tail(c, d_nz, cnt, ntt_domain, false, s, host ? d_out : o, on && host ? d_ns : on, os && host ? d_st : os));
+        PVW_TRY(decode_tail(c, d_nz, cnt, ntt_domain, false, s, host ? d_out : o, on && host ? d_ns : on, os && host ? d_st : os,
+                            nullptr, 0, nullptr, (host ? PlainAt(pl, d_wd, 0) : PlainAt(pl, p * D + d0)).ptr()));
+        if (host && ww) PVW_HIP(hipMemcpyAsync(pl->wide + (p * D + d0) * ww, d_wd, cnt * ww * 8, hipMemcpyDeviceToHost, s));
         if (host) PVW_HIP(hipMemcpyAsync(o, d_out, cnt * 8, hipMemcpyDeviceToHost, s));
         if (host && on) PVW_HIP(hipMemcpyAsync(on, d_ns, cnt * 8, hipMemcpyDeviceToHost, s));
         if (host && os) PVW_HIP(hipMemcpyAsync(os, d_st, cnt * 4, hipMemcpyDeviceToHost, s));
@@ -2756,7 +2882,7 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
   const size_t r_sk = sc.add(host ? Pc * k * l * 8 : 0), r_rows = sc.add(direct ? 0 : Pc * ctw * 8);
   const size_t r_xm = sc.add(xm_words((u32)Pc, k, L, l) * 8), r_tmp = sc.add(nbg * gemm_tmp_words((u32)Pc, L, l) * 8);
   const size_t r_c2 = sc.add(stage ? Dg * Pc * P * 8 : 0), r_nz = sc.add(Dg * Pc * P * 8), r_out = sc.add(Dg * Pc * 8);
-  const size_t r_ns = sc.add(noise ? Dg * Pc * 8 : 0), r_st = sc.add(status ? Dg * Pc * 4 : 0);
+  const size_t r_ns = sc.add(noise ? Dg * Pc * 8 : 0), r_st = sc.add(status ? Dg * Pc * 4 : 0), r_wd = sc.add(Dg * Pc * ww * 8);
   if (need_only) { *need_only = sc.total; return PVW_OK; }
   PVW_TRY(sc.take(w));
   u64 *d_c1 = sc.at(r_c1), *d_rows = sc.at(r_rows), *d_xm = sc.at(r_xm), *d_tmp = sc.at(r_tmp), *d_c2 = sc.at(r_c2), *d_nz = sc.at(r_nz),
@@ -2765,9 +2891,10 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
   int* d_sy = sc.at<int>(r_sy);
   i64* d_sk = sc.at<i64>(r_sk);
   u32* d_st = sc.at<u32>(r_st);
+  u64* d_wd = sc.at(r_wd);
   // the uploaded coefficients, the tiled s-hat (and its rows, l = 64), the GEMM intermediate (s-hat c1), the noisy
-  // polynomials, the decoded values and their reports; the staged c2 rows share the region
-  sc.secret(w, r_sk, r_st);
+  // polynomials, the decoded values and their reports (wide words included); the staged c2 rows share the region
+  sc.secret(w, r_sk, r_wd);
   for (size_t p0 = 0; p0 < NP; p0 += Pc) {
     const u32 pc = (u32)((NP - p0) < Pc ? (NP - p0) : Pc);
     const i64* skp = sk + p0 * k * l;
@@ -2816,38 +2943,64 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
         ProfScope ps(c, "finish", s);
         PVW_HIP(launch_finish_decrypt(ga, d_sy, c->dt, L, l, dg, c2p, c2v, P, d_nz, s));     // decryption.rs:257-274
       }
-      PVW_TRY(decode_tail(c, d_nz, (size_t)pc * dg, true, false, s, d_out, noise ? d_ns : nullptr, status ? d_st : nullptr));
+      PVW_TRY(decode_tail(c, d_nz, (size_t)pc * dg, true, false, s, d_out, noise ? d_ns : nullptr, status ? d_st : nullptr, nullptr, 0,
+                          nullptr, PlainAt(pl, d_wd, 0).ptr()));
       // results[recipient][dealer] (examples/pvw.rs:157-170): the chunk's [pc][dg] block into out[p0..][d0..]
       PVW_HIP(hipMemcpy2DAsync(out + p0 * D + d0, D * 8, d_out, (size_t)dg * 8, (size_t)dg * 8, pc, kout, s));
       if (noise) PVW_HIP(hipMemcpy2DAsync(noise + p0 * D + d0, D * 8, d_ns, (size_t)dg * 8, (size_t)dg * 8, pc, kout, s));
       if (status) PVW_HIP(hipMemcpy2DAsync(status + p0 * D + d0, D * 4, d_st, (size_t)dg * 4, (size_t)dg * 4, pc, kout, s));
+      if (ww) PVW_HIP(hipMemcpy2DAsync(pl->wide + (p0 * D + d0) * ww, D * ww * 8, d_wd, (size_t)dg * ww * 8, (size_t)dg * ww * 8, pc, kout, s));
     }
   }
   return PVW_OK;
 }
 // host buffers in and out
-int32_t pvw_decrypt_all_checked(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
-                                size_t D, uint32_t in_repr, uint64_t* out, uint64_t* noise, uint32_t* status) {
+static int32_t decrypt_all_staged(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
+                                  size_t D, uint32_t in_repr, uint64_t* out, uint64_t* noise, uint32_t* status, const PlainArgs* pl) {
   PVW_TRY(decrypt_all_checks(c, lo, hi, sk, c1s, c2s, D, in_repr, out));
   PVW_TRY(ensure_device(c));
   return host_call(c, [&](Workspace* w) {
-    return decrypt_all_run(c, w, w->stream, lo, hi, sk, c1s, c2s, D, in_repr, out, true, noise, status);
+    return decrypt_all_run(c, w, w->stream, lo, hi, sk, c1s, c2s, D, in_repr, out, true, noise, status, nullptr, PlainAt(pl, 0).ptr());
   });
+}
+int32_t pvw_decrypt_all_checked(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
+                                size_t D, uint32_t in_repr, uint64_t* out, uint64_t* noise, uint32_t* status) {
+  return decrypt_all_staged(c, lo, hi, sk, c1s, c2s, D, in_repr, out, noise, status, nullptr);
+}
+int32_t pvw_decrypt_all_plain(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
+                              size_t D, uint32_t in_repr, uint64_t* out, uint64_t* noise, uint32_t* status, uint64_t plain_modulus,
+                              uint32_t wide_words, uint64_t* wide) {
+  PlainArgs pa;
+  PVW_TRY(plain_args(c, plain_modulus, wide_words, wide, &pa));
+  return decrypt_all_staged(c, lo, hi, sk, c1s, c2s, D, in_repr, out, noise, status, &pa);
 }
 int32_t pvw_decrypt_all(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
                         size_t D, uint32_t in_repr, uint64_t* out) {
   return pvw_decrypt_all_checked(c, lo, hi, sk, c1s, c2s, D, in_repr, out, nullptr, nullptr);
 }
 // device pointers on the caller's stream
-int32_t pvw_decrypt_all_checked_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
+static int32_t decrypt_all_device_core(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
                                        const uint64_t* d_c2s, size_t D, uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise,
-                                       uint32_t* d_status, void* stream) {
+                                       uint32_t* d_status, void* stream, const PlainArgs* pl) {
   PVW_TRY(decrypt_all_checks(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out));
   PVW_TRY(ensure_device(c));
   hipStream_t s;
   Workspace* w;
   PVW_TRY(device_ws(c, stream, &s, &w));
-  return device_end(w, s, decrypt_all_run(c, w, s, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out, false, d_noise, d_status));
+  return device_end(w, s, decrypt_all_run(c, w, s, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out, false, d_noise, d_status, nullptr,
+                                          PlainAt(pl, 0).ptr()));
+}
+int32_t pvw_decrypt_all_checked_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
+                                       const uint64_t* d_c2s, size_t D, uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise,
+                                       uint32_t* d_status, void* stream) {
+  return decrypt_all_device_core(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out, d_noise, d_status, stream, nullptr);
+}
+int32_t pvw_decrypt_all_plain_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
+                                     const uint64_t* d_c2s, size_t D, uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise,
+                                     uint32_t* d_status, uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream) {
+  PlainArgs pa;
+  PVW_TRY(plain_args(c, plain_modulus, wide_words, d_wide, &pa));
+  return decrypt_all_device_core(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out, d_noise, d_status, stream, &pa);
 }
 int32_t pvw_decrypt_all_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
                                const uint64_t* d_c2s, size_t D, uint32_t in_repr, uint64_t* d_out, void* stream) {
@@ -2860,7 +3013,8 @@ int32_t pvw_decrypt_all_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64
 // decrypts is one streaming pass over the ciphertexts (launch_ct_sum) and ONE decrypt.
 // Workspace::sumbuf, fixed by the context's geometry (byte offsets): the slice sums of the split kernel form | the summed c1
 // [k] | the summed c2 rows [n] (row r at its global position; directly behind c1, so c1 and row 0 are one run of k + 1
-// polynomials) | the noisy polynomial of a single aggregate decrypt | out [n], noise [n], status [n] of the host-buffer calls.
+// polynomials) | the noisy polynomial of a single aggregate decrypt | out [n], noise [n], status [n], wide [n][W] of the host-buffer
+// calls.
 struct SumLayout { size_t c1, c2, noisy, io, total; };
 static SumLayout sum_layout(const pvw_ctx* c) {
   const size_t P8 = c->poly() * 8;
@@ -2869,7 +3023,8 @@ static SumLayout sum_layout(const pvw_ctx* c) {
   o.c2 = o.c1 + (size_t)c->k * P8;
   o.noisy = o.c2 + (size_t)c->n * P8;
   o.io = o.noisy + ((P8 + 255) & ~(size_t)255);
-  o.total = o.io + (((size_t)c->n * 20 + 255) & ~(size_t)255);
+  // per party: out, noise (8 bytes each), status (4, padded to 8), and the wide words of a plain decode at wide_words = W
+  o.total = o.io + (((size_t)c->n * (24 + 8 * c->Q.mag.size()) + 255) & ~(size_t)255);
   return o;
 }
 static bool sum_buffer_ready(const pvw_ctx* c, const Workspace* w) { return w && w->sumbuf_bytes >= sum_layout(c).total; }
@@ -2909,8 +3064,12 @@ static int32_t sum_capture_check(pvw_ctx* c, hipStream_t s, size_t dpart_need, s
                                             "first (it sizes the scratch for the context's own party range)");
   return PVW_OK;
 }
-static int32_t decrypt_all_sum_need(pvw_ctx* c, u32 lo, u32 hi, size_t* need) {
-  return decrypt_all_run(c, nullptr, nullptr, lo, hi, nullptr, nullptr, nullptr, 1, PVW_REPR_NTT, nullptr, false, (u64*)8, (u32*)8, need);
+// wide_words: of the call (a plain decode); pvw_prepare sizes for W, the most any call may ask for
+static int32_t decrypt_all_sum_need(pvw_ctx* c, u32 lo, u32 hi, size_t* need, u32 wide_words) {
+  PlainArgs pa{};
+  pa.wide_words = wide_words;
+  return decrypt_all_run(c, nullptr, nullptr, lo, hi, nullptr, nullptr, nullptr, 1, PVW_REPR_NTT, nullptr, false, (u64*)8, (u32*)8, need,
+                         &pa);
 }
 // pvw_prepare(PVW_PREPARE_SUM)
 static int32_t sum_prepare(pvw_ctx* c, Workspace* w, hipStream_t s) {
@@ -2922,7 +3081,7 @@ static int32_t sum_prepare(pvw_ctx* c, Workspace* w, hipStream_t s) {
     w->dpart_bytes = dneed;
   }
   size_t need = 0;
-  if (c->party_hi > c->party_lo) PVW_TRY(decrypt_all_sum_need(c, c->party_lo, c->party_hi, &need));
+  if (c->party_hi > c->party_lo) PVW_TRY(decrypt_all_sum_need(c, c->party_lo, c->party_hi, &need, (u32)c->Q.mag.size()));
   if (w->scratch_bytes < need) PVW_HIP(hipStreamSynchronize(s));
   return ws_scratch(w, need);
 }
@@ -3061,26 +3220,27 @@ int32_t pvw_ct_sum_host(const pvw_ctx* c, const uint64_t* c1s, const uint64_t* c
 // run, public); this is the rest: a POWER-basis sum is transformed there, then the single-ciphertext decrypt and its checked
 // decode (decrypt_batch_enqueue with D = 1: the split decrypt_mac + decrypt_finish + the checked decode chain).
 static int32_t decrypt_sum_tail(pvw_ctx* c, Workspace* w, hipStream_t s, const int64_t* d_sk, const u64* key_shat, uint32_t in_repr,
-                                u64* d_noisy, u64* d_out, u64* d_noise, u32* d_status) {
+                                u64* d_noisy, u64* d_out, u64* d_noise, u32* d_status, const PlainArgs* pl = nullptr) {
   const SumLayout sl = sum_layout(c);
   u64 *c1 = (u64*)((char*)w->sumbuf + sl.c1), *c2 = (u64*)((char*)w->sumbuf + sl.c2);
   if (in_repr == PVW_REPR_POWER) {
     ProfScope ps(c, "ntt", s);
     PVW_HIP(launch_ntt(c1, (size_t)c->k + 1, false, c->dt, c->L, c->l, s));
   }
-  if (d_noisy) return decrypt_batch_enqueue(c, w, s, d_sk, key_shat, c1, c2, 1, d_noisy, d_out, d_noise, d_status);
+  if (d_noisy) return decrypt_batch_enqueue(c, w, s, d_sk, key_shat, c1, c2, 1, d_noisy, d_out, d_noise, d_status, pl);
   // m g + noise of the aggregate is the key holder's: kept in the sum buffer and cleared by a launch right behind the decode
   // (a kernel, so that a captured call clears it on every replay in order); a call that fails on the way leaves it marked
   d_noisy = (u64*)((char*)w->sumbuf + sl.noisy);
   ws_mark_secret(w, d_noisy, c->poly() * 8);
-  PVW_TRY(decrypt_batch_enqueue(c, w, s, d_sk, key_shat, c1, c2, 1, d_noisy, d_out, d_noise, d_status));
+  PVW_TRY(decrypt_batch_enqueue(c, w, s, d_sk, key_shat, c1, c2, 1, d_noisy, d_out, d_noise, d_status, pl));
   PVW_HIP(launch_wipe_words(d_noisy, c->poly(), s));
   ws_mark_secret(w, d_noisy, c->poly() * 8, true);
   return PVW_OK;
 }
 static int32_t decrypt_sum_core(pvw_ctx* c, const int64_t* d_sk, const u64* key_shat, const uint64_t* d_c1s, const uint64_t* d_c2col,
                                 size_t D, const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out,
-                                uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, void* stream) {
+                                uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, void* stream,
+                                const PlainArgs* pl = nullptr) {
   if (!c || !d_c1s || !d_c2col || !d_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");          // decryption.rs:286-290
   if (D >> 32) return fail(PVW_ERR_INVALID_PARAMETERS, "a sum takes fewer than 2^32 dealers");
@@ -3095,7 +3255,7 @@ static int32_t decrypt_sum_core(pvw_ctx* c, const int64_t* d_sk, const u64* key_
   auto run = [&]() -> int32_t {
     PVW_TRY(ct_sum_enqueue(c, w, s, d_c1s, d_c2col, c->poly(), 1, D, d_valid, (u64*)((char*)w->sumbuf + sl.c1),
                            (u64*)((char*)w->sumbuf + sl.c2), d_count));
-    return decrypt_sum_tail(c, w, s, d_sk, key_shat, in_repr, d_noisy, d_out, d_noise, d_status);
+    return decrypt_sum_tail(c, w, s, d_sk, key_shat, in_repr, d_noisy, d_out, d_noise, d_status, PlainAt(pl, 0).ptr());
   };
   return device_end(w, s, run());
 }
@@ -3112,9 +3272,30 @@ int32_t pvw_decrypt_sum_device_sk_checked(pvw_ctx* c, const pvw_sk* key, const u
   if (key->ctx != c) return fail(PVW_ERR_INVALID_PARAMETERS, "the key was loaded for another context");
   return decrypt_sum_core(c, nullptr, key->shat, d_c1s, d_c2col, D, d_valid, in_repr, d_noisy, d_out, d_noise, d_status, d_count, stream);
 }
-int32_t pvw_decrypt_sum_checked(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
-                                const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status,
-                                uint32_t* count) {
+// plain forms
+int32_t pvw_decrypt_sum_plain_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
+                                     const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise,
+                                     uint32_t* d_status, uint32_t* d_count, uint64_t plain_modulus, uint32_t wide_words,
+                                     uint64_t* d_wide, void* stream) {
+  if (!c || !d_sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PlainArgs pa;
+  PVW_TRY(plain_args(c, plain_modulus, wide_words, d_wide, &pa));
+  return decrypt_sum_core(c, d_sk, nullptr, d_c1s, d_c2col, D, d_valid, in_repr, d_noisy, d_out, d_noise, d_status, d_count, stream, &pa);
+}
+int32_t pvw_decrypt_sum_device_sk_plain(pvw_ctx* c, const pvw_sk* key, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
+                                        const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out,
+                                        uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, uint64_t plain_modulus,
+                                        uint32_t wide_words, uint64_t* d_wide, void* stream) {
+  if (!c || !key || !key->shat) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (key->ctx != c) return fail(PVW_ERR_INVALID_PARAMETERS, "the key was loaded for another context");
+  PlainArgs pa;
+  PVW_TRY(plain_args(c, plain_modulus, wide_words, d_wide, &pa));
+  return decrypt_sum_core(c, nullptr, key->shat, d_c1s, d_c2col, D, d_valid, in_repr, d_noisy, d_out, d_noise, d_status, d_count, stream,
+                          &pa);
+}
+static int32_t decrypt_sum_staged(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
+                                  const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status,
+                                  uint32_t* count, const PlainArgs* pl) {
   if (!c || !sk || !c1s || !c2col || !out_u64) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");          // decryption.rs:286-290
   if (D >> 32) return fail(PVW_ERR_INVALID_PARAMETERS, "a sum takes fewer than 2^32 dealers");
@@ -3132,25 +3313,39 @@ int32_t pvw_decrypt_sum_checked(pvw_ctx* c, const int64_t* sk, const uint64_t* c
     i64* d_sk = sc.at<i64>(r_sk);
     u64* io = (u64*)((char*)w->sumbuf + sl.io);                  // out | noise | status: the key holder's
     sc.secret(w, r_sk, r_sk);
-    ws_mark_secret(w, io, 24);
+    const size_t ww = plain_ww(pl);
+    ws_mark_secret(w, io, 24 + ww * 8);
     PVW_HIP(hipMemcpyAsync(d_sk, sk, k * l * 8, hipMemcpyHostToDevice, w->stream));
     PVW_TRY(ct_sum_staged(c, w, sc.at(r_c1), sc.at(r_c2), per, c1s, c2col, P, 1, D, valid, (u64*)((char*)w->sumbuf + sl.c1),
                           (u64*)((char*)w->sumbuf + sl.c2)));
     PVW_TRY(decrypt_sum_tail(c, w, w->stream, d_sk, nullptr, in_repr, nullptr, io, noise ? io + 1 : nullptr,
-                             status ? (u32*)(io + 2) : nullptr));
+                             status ? (u32*)(io + 2) : nullptr, PlainAt(pl, io + 3, 0).ptr()));
     PVW_HIP(hipMemcpyAsync(out_u64, io, 8, hipMemcpyDeviceToHost, w->stream));
     if (noise) PVW_HIP(hipMemcpyAsync(noise, io + 1, 8, hipMemcpyDeviceToHost, w->stream));
     if (status) PVW_HIP(hipMemcpyAsync(status, io + 2, 4, hipMemcpyDeviceToHost, w->stream));
+    if (ww) PVW_HIP(hipMemcpyAsync(pl->wide, io + 3, ww * 8, hipMemcpyDeviceToHost, w->stream));
     return PVW_OK;
   });
   if (rc == PVW_OK && count) *count = (uint32_t)nv;
   return rc;
 }
+int32_t pvw_decrypt_sum_checked(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
+                                const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status,
+                                uint32_t* count) {
+  return decrypt_sum_staged(c, sk, c1s, c2col, D, valid, in_repr, out_u64, noise, status, count, nullptr);
+}
+int32_t pvw_decrypt_sum_plain(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D, const uint8_t* valid,
+                              uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status, uint32_t* count,
+                              uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
+  PlainArgs pa;
+  PVW_TRY(plain_args(c, plain_modulus, wide_words, wide, &pa));
+  return decrypt_sum_staged(c, sk, c1s, c2col, D, valid, in_repr, out_u64, noise, status, count, &pa);
+}
 
 // Every party's aggregate share: the sum over c1 and rows [lo, hi) of c2 (row r at its global position of the sum buffer, so the
 // buffer reads as ONE whole ciphertext), then decrypt_all_run on that one ciphertext: the 22-party dispatch is its own.
 static int32_t decrypt_all_sum_tail(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, u32 hi, const int64_t* d_sk, uint32_t in_repr,
-                                    u64* d_out, u64* d_noise, u32* d_status) {
+                                    u64* d_out, u64* d_noise, u32* d_status, const PlainArgs* pl = nullptr) {
   const SumLayout sl = sum_layout(c);
   u64 *c1 = (u64*)((char*)w->sumbuf + sl.c1), *c2 = (u64*)((char*)w->sumbuf + sl.c2);
   if (in_repr == PVW_REPR_POWER) {
@@ -3158,17 +3353,18 @@ static int32_t decrypt_all_sum_tail(pvw_ctx* c, Workspace* w, hipStream_t s, u32
     PVW_HIP(launch_ntt(c1, c->k, false, c->dt, c->L, c->l, s));
     PVW_HIP(launch_ntt(c2 + (size_t)lo * c->poly(), hi - lo, false, c->dt, c->L, c->l, s));
   }
-  return decrypt_all_run(c, w, s, lo, hi, d_sk, c1, c2, 1, PVW_REPR_NTT, d_out, false, d_noise, d_status);
+  return decrypt_all_run(c, w, s, lo, hi, d_sk, c1, c2, 1, PVW_REPR_NTT, d_out, false, d_noise, d_status, nullptr, pl);
 }
-int32_t pvw_decrypt_all_sum_checked_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
+static int32_t decrypt_all_sum_device_core(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
                                            const uint64_t* d_c2s, size_t D, const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_out,
-                                           uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, void* stream) {
+                                           uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, void* stream,
+                                           const PlainArgs* pl) {
   PVW_TRY(decrypt_all_checks(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out));
   if (D >> 32) return fail(PVW_ERR_INVALID_PARAMETERS, "a sum takes fewer than 2^32 dealers");
   PVW_TRY(ensure_device(c));
   hipStream_t s = call_stream(c, stream);
   size_t need = 0;
-  PVW_TRY(decrypt_all_sum_need(c, lo, hi, &need));
+  PVW_TRY(decrypt_all_sum_need(c, lo, hi, &need, (u32)plain_ww(pl)));
   PVW_TRY(sum_capture_check(c, s, sum_dpart_need(c), need));
   Workspace* w;
   PVW_TRY(ws_for_stream(c, s, &w));
@@ -3179,21 +3375,35 @@ int32_t pvw_decrypt_all_sum_checked_device(pvw_ctx* c, uint32_t lo, uint32_t hi,
   auto run = [&]() -> int32_t {
     PVW_TRY(ct_sum_enqueue(c, w, s, d_c1s, d_c2s + (size_t)lo * P, (size_t)c->n * P, hi - lo, D, d_valid,
                            (u64*)((char*)w->sumbuf + sl.c1), (u64*)((char*)w->sumbuf + sl.c2) + (size_t)lo * P, d_count));
-    return decrypt_all_sum_tail(c, w, s, lo, hi, d_sk, in_repr, d_out, d_noise, d_status);
+    return decrypt_all_sum_tail(c, w, s, lo, hi, d_sk, in_repr, d_out, d_noise, d_status, PlainAt(pl, 0).ptr());
   };
   return device_end(w, s, run());
 }
-int32_t pvw_decrypt_all_sum_checked(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
-                                    size_t D, const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise,
-                                    uint32_t* status, uint32_t* count) {
+int32_t pvw_decrypt_all_sum_checked_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
+                                           const uint64_t* d_c2s, size_t D, const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_out,
+                                           uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, void* stream) {
+  return decrypt_all_sum_device_core(c, lo, hi, d_sk, d_c1s, d_c2s, D, d_valid, in_repr, d_out, d_noise, d_status, d_count, stream, nullptr);
+}
+int32_t pvw_decrypt_all_sum_plain_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
+                                         const uint64_t* d_c2s, size_t D, const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_out,
+                                         uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, uint64_t plain_modulus,
+                                         uint32_t wide_words, uint64_t* d_wide, void* stream) {
+  PlainArgs pa;
+  PVW_TRY(plain_args(c, plain_modulus, wide_words, d_wide, &pa));
+  return decrypt_all_sum_device_core(c, lo, hi, d_sk, d_c1s, d_c2s, D, d_valid, in_repr, d_out, d_noise, d_status, d_count, stream, &pa);
+}
+static int32_t decrypt_all_sum_staged(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
+                                      size_t D, const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise,
+                                      uint32_t* status, uint32_t* count, const PlainArgs* pl) {
   PVW_TRY(decrypt_all_checks(c, lo, hi, sk, c1s, c2s, D, in_repr, out_u64));
   if (D >> 32) return fail(PVW_ERR_INVALID_PARAMETERS, "a sum takes fewer than 2^32 dealers");
   const size_t nv = count_valid(valid, D);
   if (nv == 0) return no_valid_dealer(D);
   PVW_TRY(ensure_device(c));
   const size_t P = c->poly(), k = c->k, l = c->l, NP = (size_t)hi - lo, per = sum_stage_dealers(c, NP, nv);
+  const size_t ww = plain_ww(pl);
   size_t need = 0;
-  PVW_TRY(decrypt_all_sum_need(c, lo, hi, &need));
+  PVW_TRY(decrypt_all_sum_need(c, lo, hi, &need, (u32)ww));
   // the staged pieces and the decrypt's own scratch share the front of the block (stream order: the sum has read the pieces
   // before the decrypt writes there); the uploaded keys sit behind both
   Scratch st;
@@ -3208,19 +3418,34 @@ int32_t pvw_decrypt_all_sum_checked(pvw_ctx* c, uint32_t lo, uint32_t hi, const 
     i64* d_sk = sc.at<i64>(r_sk);
     u64 *d_out = (u64*)((char*)w->sumbuf + sl.io), *d_ns = d_out + c->n;
     u32* d_st = (u32*)(d_ns + c->n);
+    u64* d_wd = d_ns + 2 * (size_t)c->n;                          // behind the status words, 8-byte aligned
     sc.secret(w, r_sk, r_sk);
-    ws_mark_secret(w, d_out, (size_t)c->n * 20);
+    ws_mark_secret(w, d_out, (size_t)c->n * (24 + 8 * ww));
     PVW_HIP(hipMemcpyAsync(d_sk, sk, NP * k * l * 8, hipMemcpyHostToDevice, w->stream));
     PVW_TRY(ct_sum_staged(c, w, st.at(r_c1), st.at(r_c2), per, c1s, c2s + (size_t)lo * P, (size_t)c->n * P, NP, D, valid,
                           (u64*)((char*)w->sumbuf + sl.c1), (u64*)((char*)w->sumbuf + sl.c2) + (size_t)lo * P));
-    PVW_TRY(decrypt_all_sum_tail(c, w, w->stream, lo, hi, d_sk, in_repr, d_out, noise ? d_ns : nullptr, status ? d_st : nullptr));
+    PVW_TRY(decrypt_all_sum_tail(c, w, w->stream, lo, hi, d_sk, in_repr, d_out, noise ? d_ns : nullptr, status ? d_st : nullptr,
+                                 PlainAt(pl, d_wd, 0).ptr()));
     PVW_HIP(hipMemcpyAsync(out_u64, d_out, NP * 8, hipMemcpyDeviceToHost, w->stream));
     if (noise) PVW_HIP(hipMemcpyAsync(noise, d_ns, NP * 8, hipMemcpyDeviceToHost, w->stream));
     if (status) PVW_HIP(hipMemcpyAsync(status, d_st, NP * 4, hipMemcpyDeviceToHost, w->stream));
+    if (ww) PVW_HIP(hipMemcpyAsync(pl->wide, d_wd, NP * ww * 8, hipMemcpyDeviceToHost, w->stream));
     return PVW_OK;
   });
   if (rc == PVW_OK && count) *count = (uint32_t)nv;
   return rc;
+}
+int32_t pvw_decrypt_all_sum_checked(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
+                                    size_t D, const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise,
+                                    uint32_t* status, uint32_t* count) {
+  return decrypt_all_sum_staged(c, lo, hi, sk, c1s, c2s, D, valid, in_repr, out_u64, noise, status, count, nullptr);
+}
+int32_t pvw_decrypt_all_sum_plain(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
+                                  size_t D, const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status,
+                                  uint32_t* count, uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
+  PlainArgs pa;
+  PVW_TRY(plain_args(c, plain_modulus, wide_words, wide, &pa));
+  return decrypt_all_sum_staged(c, lo, hi, sk, c1s, c2s, D, valid, in_repr, out_u64, noise, status, count, &pa);
 }
 
 // Advisory: for how many dealers at the builder's noise bound the gadget decode of the aggregate is PROVEN exact.  With

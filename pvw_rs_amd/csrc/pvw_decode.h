@@ -69,8 +69,19 @@ struct DecodeTables {
   u32 ck_mul;
 };
 
-// status word of the checked decode: the returned word is not the plaintext P (P < 0 or P >= 2^64)
-enum : u32 { DEC_LOSSY = 1 };
+// status word of the checked decode: the returned word is not the plaintext P (P < 0 or P >= 2^64).  The plain decode
+//  adds: P < 0; |P| does not fit the wide words asked for.
+enum : u32 { DEC_LOSSY = 1, DEC_NEGATIVE = 2, DEC_WIDE_TRUNCATED = 4 };
+// plain decode: out = P mod m.q (m.q == 0: the checked decode's word) and the low wide_words words of |P| at
+// wide[d * wide_words ..] (wide_words == 0: none).  Passed by value into the launch.  m is the library's Barrett pair for ANY
+// 2 <= q < 2^62: make_mod's ratio is floor((2^128 - 1) / q), which is floor(2^128 / q) - 1 when q is a power of two and
+// floor(2^128 / q) otherwise; either way x ratio / 2^128 > x / q - 1 for x < 2^128, so reduce128's quotient is at most one
+// short (its two conditional subtractions cover two) and nothing in it needs q odd or prime.
+struct PlainArgs {
+  Mod m;
+  u32 wide_words;
+  u64* wide;
+};
 // noise word of the checked decode once a residual leaves 64 bits
 #define PVW_NOISE_SAT (~(u64)0)
 
@@ -413,9 +424,12 @@ PVW_HD u64 small_top_expected(u64 e0, u64 q0, const Mod& m) {
 // and *status (DEC_LOSSY when the returned word is not P).  residual_0 = noise_0 and residual_{i+1} = Delta residual_i + tmp_i
 // (mod Q): the recurrence runs on the residues of noise_0 left in nres, one centred lift per step, and stops at the first
 // residual that leaves 64 bits.
-template <bool CK = false>
+// PL (plain decode; implies the report): the tail on |P| = x, vneg before the u64 conversion -- a Horner over the
+// words from the top, one reduce128 of (r : word) a word (r < q < 2^62), the sign folded in; the low pa->wide_words words to
+// `wide` (this ciphertext's).
+template <bool CK = false, bool PL = false>
 PVW_HD u64 decode_one_fixed(const DecodeTables& t, const u64* noisy, BN x, BN y, BN nres, u64* noise = nullptr,
-                            u32* status = nullptr) {
+                            u32* status = nullptr, const PlainArgs* pa = nullptr, u64* wide = nullptr) {
   const int W = (int)t.W;
   const u32 L = t.L, l = t.ell;
   // tmp_i = z_i * Delta - z_{i+1}  (mod q_limb), straight from the noisy residues (:19-27)
@@ -470,6 +484,23 @@ PVW_HD u64 decode_one_fixed(const DecodeTables& t, const u64* noisy, BN x, BN y,
     u64 a = z0 ? m.q - z0 : 0;
     return submod(a, nres[(int)limb], m.q);
   });
+  u64 presidue = 0;
+  u32 pbits = 0;
+  if constexpr (PL) {
+    const bool pneg = vneg && !bn_is_zero(x, W);
+    if (pneg) pbits |= DEC_NEGATIVE;
+    if (pa->m.q) {
+      u64 r = 0;
+      for (int w = W - 1; w >= 0; --w) r = reduce128(x[w], r, pa->m);
+      presidue = (pneg && r) ? pa->m.q - r : r;
+    }
+    if (pa->wide_words) {
+      for (int w = 0; w < W; ++w) {
+        if (w < (int)pa->wide_words) wide[w] = x[w];
+        else if (x[w]) pbits |= DEC_WIDE_TRUNCATED;
+      }
+    }
+  }
   u64 result;
   bool lossy;
   {
@@ -501,7 +532,10 @@ PVW_HD u64 decode_one_fixed(const DecodeTables& t, const u64* noisy, BN x, BN y,
       if (!sat && x[0] > mx) mx = x[0];
     }
     if (noise) *noise = sat ? PVW_NOISE_SAT : mx;
-    if (status) *status = lossy ? (u32)DEC_LOSSY : 0u;
+    if (status) *status = (lossy ? (u32)DEC_LOSSY : 0u) | pbits;
+  }
+  if constexpr (PL) {
+    if (pa->m.q) result = presidue;
   }
   return result;
 }

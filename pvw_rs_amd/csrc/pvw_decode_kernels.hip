@@ -44,6 +44,21 @@ __global__ __launch_bounds__(64) void decode_checked_kernel(const u64* __restric
                                     status ? status + d : nullptr);
 }
 
+// the same with the plain tail: P mod pa.m.q and / or the words of |P|, in this launch
+__global__ __launch_bounds__(64) void decode_plain_kernel(const u64* __restrict__ noisy, u64* __restrict__ out,
+                                                           u64* __restrict__ noise, u32* __restrict__ status, u32 count,
+                                                           DecodeTables t, PlainArgs pa) {
+  extern __shared__ u64 dsm[];
+  const u32 d = blockIdx.x * 64 + threadIdx.x;
+  u64* base = dsm + threadIdx.x;
+  BN x{base, 64};
+  BN y{base + (size_t)(t.W + 1) * 64, 64};
+  BN nres{base + (size_t)(2 * t.W + 1) * 64, 64};
+  if (d >= count) return;
+  out[d] = decode_one_fixed<true, true>(t, noisy + (size_t)d * t.L * t.ell, x, y, nres, noise ? noise + d : nullptr,
+                                          status ? status + d : nullptr, &pa, pa.wide + (size_t)d * pa.wide_words);
+}
+
 // decode, lifted-chain form (pvw_decode_wave.h): 4 waves per ciphertext, cpw ciphertexts per workgroup
 // XF: the residues arrive in the NTT domain and are transformed back while they are staged (stage_inverse).  A separate
 // instance because the compiler gives it 94 registers where the plain one has 79: at most 80 keep the decode co-resident
@@ -76,6 +91,17 @@ __global__ __launch_bounds__(512) void decode_chain_checked_kernel(u64* __restri
   decode_chain_body<4, true>(noisy, out, count, cpw_dbg, t, xf, blockIdx.x, dws, noise, status);
 }
 
+// the checked lifted-chain decode with the plain tail: a third family, so that the other two stay as they are
+template <bool XF>
+__global__ __launch_bounds__(512) void decode_chain_plain_kernel(u64* __restrict__ noisy, u64* __restrict__ out,
+                                                                  u64* __restrict__ noise, u32* __restrict__ status,
+                                                                  u32 count, u32 cpw_dbg, DecodeTables t, InverseTables xf,
+                                                                  PlainArgs pa) {
+  extern __shared__ u64 dws[];
+  if (!XF) xf.itw = nullptr;
+  decode_chain_body<4, true, true>(noisy, out, count, cpw_dbg, t, xf, blockIdx.x, dws, noise, status, &pa);
+}
+
 // Kernels that may ask for more than the default 64 KiB of dynamic LDS.  The attribute is per device and per
 // code object, so it is set once per CONTEXT while the context initialises its device (ensure_device, under the
 // context's init mutex, after hipSetDevice) -- not lazily behind process-wide flags.
@@ -87,6 +113,9 @@ hipError_t init_kernel_attributes() {
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)decode_checked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, big);
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)decode_chain_checked_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)decode_chain_checked_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)decode_plain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)decode_chain_plain_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)decode_chain_plain_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
 #if PVW_TUNING
   if (e == hipSuccess) e = init_probe_attributes();
 #endif
@@ -99,10 +128,11 @@ static size_t decode_chain_lds(const DecodeTables& t, u32 cpw, u32 wpc) {
 }
 
 hipError_t launch_decode(u64* noisy, u64* out, size_t count, const DecodeTables& t, hipStream_t s, const DevTables* xf,
-                         u64* wipe, size_t wipe_bytes, bool* wiped, u64* noise, u32* status) {
+                         u64* wipe, size_t wipe_bytes, bool* wiped, u64* noise, u32* status, const PlainArgs* plain) {
   if (wiped) *wiped = false;
   if (count == 0) return hipSuccess;
-  const bool checked = noise || status;
+  if (plain && !plain->m.q && !plain->wide_words) plain = nullptr;        // no option set: the checked decode as it is
+  const bool checked = noise || status || plain;
   if (checked) wipe = nullptr;
   InverseTables inv{nullptr, nullptr, nullptr, nullptr};
   if (xf) inv = InverseTables{xf->itw, xf->itwp, xf->linv, xf->linvp};
@@ -122,6 +152,11 @@ hipError_t launch_decode(u64* noisy, u64* out, size_t count, const DecodeTables&
       // tuning build only: PVW_DECODE_TIMING=1..6: out[] = cycles of a phase (results are NOT values; tools/decode_timing.py)
       const u32 dbg = (u32)PVW_ENV_INT("PVW_DECODE_TIMING", 0);
       const u32 no_small = PVW_ENV_INT("PVW_DECODE_SMALL", 1) == 0 ? 1u << 31 : 0;     // tuning build: every lift in full
+      if (plain) {
+        if (xf) decode_chain_plain_kernel<true><<<grid, block, bytes, s>>>(noisy, out, noise, status, (u32)count, cpw | ((dbg & 0xff) << 16) | no_small, t, inv, *plain);
+        else decode_chain_plain_kernel<false><<<grid, block, bytes, s>>>(noisy, out, noise, status, (u32)count, cpw | ((dbg & 0xff) << 16) | no_small, t, inv, *plain);
+        return hipGetLastError();
+      }
       if (checked) {
         if (xf) decode_chain_checked_kernel<true><<<grid, block, bytes, s>>>(noisy, out, noise, status, (u32)count, cpw | ((dbg & 0xff) << 16) | no_small, t, inv);
         else decode_chain_checked_kernel<false><<<grid, block, bytes, s>>>(noisy, out, noise, status, (u32)count, cpw | ((dbg & 0xff) << 16) | no_small, t, inv);
@@ -138,7 +173,8 @@ hipError_t launch_decode(u64* noisy, u64* out, size_t count, const DecodeTables&
   }
   const size_t lds = (size_t)(2 * t.W + 1 + t.L) * 64 * sizeof(u64);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
-  if (checked) decode_checked_kernel<<<dim3((u32)((count + 63) / 64)), dim3(64), lds, s>>>(noisy, out, noise, status, (u32)count, t);
+  if (plain) decode_plain_kernel<<<dim3((u32)((count + 63) / 64)), dim3(64), lds, s>>>(noisy, out, noise, status, (u32)count, t, *plain);
+  else if (checked) decode_checked_kernel<<<dim3((u32)((count + 63) / 64)), dim3(64), lds, s>>>(noisy, out, noise, status, (u32)count, t);
   else decode_kernel<<<dim3((u32)((count + 63) / 64)), dim3(64), lds, s>>>(noisy, out, (u32)count, t);
   return hipGetLastError();
 }

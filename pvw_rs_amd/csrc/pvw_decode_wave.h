@@ -375,10 +375,14 @@ __device__ __forceinline__ void stage_inverse(const Mod* mods, const InverseTabl
 }
 // CK (checked decode): also noise_out[d] / status_out[d] (each may be NULL) -- the report of the residual
 // recurrence below, on the wave that ran the chain; the unchecked instances do not contain it.
-template <int WPC, bool CK = false>
+// PL (plain decode; with CK): the tail on (v, vneg), word w of |P| in lane w, before the u64 conversion throws
+// the high words away: |P| mod pa.m.q as a Horner over the significant words from the top (v_readlane, one reduce128 of
+// (r : word) a word, r < q < 2^62), the sign folded in; lanes < pa.wide_words store their word to consecutive addresses.
+template <int WPC, bool CK = false, bool PL = false>
 __device__ __forceinline__ void decode_chain_body(u64* __restrict__ noisy, u64* __restrict__ out, u32 count, u32 cpw_dbg,
                                                   const DecodeTables& t, const InverseTables& xf, u32 blk, u64* dws,
-                                                  u64* __restrict__ noise_out = nullptr, u32* __restrict__ status_out = nullptr) {
+                                                  u64* __restrict__ noise_out = nullptr, u32* __restrict__ status_out = nullptr,
+                                                  const PlainArgs* pa = nullptr) {
   const u32 cpw = cpw_dbg & 0xffff;
   const u32 dbg = PVW_TUNING ? ((cpw_dbg >> 16) & 0xff) : 0;
   const bool no_small = PVW_TUNING && (cpw_dbg >> 31);     // tuning build: PVW_DECODE_SMALL=0, every lift in full        // tuning build, dbg != 0: timing experiment, out[] = cycle counts
@@ -628,9 +632,28 @@ __device__ __forceinline__ void decode_chain_body(u64* __restrict__ noisy, u64* 
       rneg = xneg;
       if (!sat && rm > mx) mx = rm;
     }
+    u32 st = lossy ? (u32)DEC_LOSSY : 0u;
+    if constexpr (PL) {
+      if (vneg && !pz) st |= DEC_NEGATIVE;
+      const u32 ww = pa->wide_words;
+      if (ww) {
+        if (__ballot(lane >= ww && lane < W && v != 0)) st |= DEC_WIDE_TRUNCATED;
+        if (lane < ww) pa->wide[(size_t)d * ww + lane] = lane < W ? v : 0;
+      }
+    }
     if (lane == 0) {
       if (noise_out) noise_out[d] = sat ? PVW_NOISE_SAT : mx;
-      if (status_out) status_out[d] = lossy ? (u32)DEC_LOSSY : 0u;
+      if (status_out) status_out[d] = st;
+    }
+    if constexpr (PL) {
+      if (pa->m.q) {
+        const unsigned long long nzw = __ballot(lane < W && v != 0);
+        u64 r = 0;
+        for (u32 w = nzw ? 64 - (u32)__builtin_clzll(nzw) : 0; w-- > 0;) r = reduce128(readlane_u64(v, w), r, pa->m);
+        if (vneg && r) r = pa->m.q - r;
+        if (lane == 0) out[d] = r;
+        return;
+      }
     }
   }
   const bool vzero = __ballot(v != 0) == 0;

@@ -330,9 +330,11 @@ hipError_t launch_mfma_probe(const signed char* A, const signed char* B, int* C,
 // noise / status (either may be NULL; both NULL: the unchecked kernels): the checked decode's report per ciphertext
 // (pvw_decode.h: decode_one_fixed, pvw_decode_wave.h: decode_chain_body), out[] unchanged.  A checked launch
 // takes no wipe (*wiped comes back false).
+// plain (NULL or no option set: none): the checked launch with the plain tail -- out[] = P mod plain->m.q and / or
+// the words of |P| at plain->wide, in the same launch; the shape dispatch is the same.
 hipError_t launch_decode(u64* noisy, u64* out, size_t count, const DecodeTables& t, hipStream_t s, const DevTables* xf = nullptr,
                          u64* wipe = nullptr, size_t wipe_bytes = 0, bool* wiped = nullptr, u64* noise = nullptr,
-                         u32* status = nullptr);
+                         u32* status = nullptr, const PlainArgs* plain = nullptr);
 
 // wire format v1 (pvw_wire.hip): `count` polynomials [L][ell] u64 <-> packed bytes (w_i = bit length of q_i bits per
 // residue).  words / packed pointers 16-byte aligned; L <= 64.  Unpack: *bad += residues >= q_i (the caller zeroes it);

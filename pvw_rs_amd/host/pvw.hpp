@@ -482,12 +482,29 @@ inline std::vector<uint64_t> decrypt_party_shares(const std::vector<PvwCiphertex
 }
 // decrypt_party_shares with each share's report (pvw_decrypt_batch_checked): values as decrypt_party_shares,
 // noise (max |residual|, saturating), lossy (the value is not the plaintext), valid = !lossy && noise <= bound
+// plain (NULL or both fields 0: none): values = P mod plain->modulus and / or wide = plain->wide_words little-endian
+// words of |P| per share (stored here; plain->wide is not used); valid then drops !lossy -- the values are exact -- and keeps the
+// noise test; negative / truncated are the two further status bits
 struct CheckedShares {
   std::vector<uint64_t> values, noise;
   std::vector<bool> lossy, valid;
+  std::vector<bool> negative, truncated;
+  std::vector<uint64_t> wide;
 };
+inline bool plain_on(const pvw_plain_t* plain) { return plain && (plain->modulus || plain->wide_words); }
+inline void checked_report(CheckedShares& r, const std::vector<uint32_t>& status, uint64_t bound, bool plain) {
+  const size_t n = status.size();
+  r.negative.assign(n, false);
+  r.truncated.assign(n, false);
+  for (size_t d = 0; d < n; ++d) {
+    r.lossy[d] = (status[d] & PVW_DEC_LOSSY) != 0;
+    r.negative[d] = (status[d] & PVW_DEC_NEGATIVE) != 0;
+    r.truncated[d] = (status[d] & PVW_DEC_WIDE_TRUNCATED) != 0;
+    r.valid[d] = (plain || !r.lossy[d]) && r.noise[d] <= bound;
+  }
+}
 inline CheckedShares decrypt_party_shares_checked(const std::vector<PvwCiphertext>& cts, const SecretKey& sk, uint32_t party_index,
-                                                  uint64_t bound) {
+                                                  uint64_t bound, const pvw_plain_t* plain = nullptr) {
   if (cts.empty()) throw PvwError(1, "No ciphertexts provided");
   const auto& p = cts[0].params;
   if (cts.size() != p->n) throw PvwError(1, "Expected n ciphertexts");
@@ -501,12 +518,15 @@ inline CheckedShares decrypt_party_shares_checked(const std::vector<PvwCiphertex
     c1s.insert(c1s.end(), ct.c1.begin(), ct.c1.end());
     c2col.insert(c2col.end(), ct.c2.begin() + (size_t)party_index * P, ct.c2.begin() + (size_t)(party_index + 1) * P);
   }
-  check(pvw_decrypt_batch_checked(p->ctx, sk.secret_coeffs.data(), c1s.data(), c2col.data(), D, cts[0].repr, r.values.data(),
-                                  r.noise.data(), status.data()));
-  for (size_t d = 0; d < D; ++d) {
-    r.lossy[d] = (status[d] & PVW_DEC_LOSSY) != 0;
-    r.valid[d] = !r.lossy[d] && r.noise[d] <= bound;
+  if (plain_on(plain)) {
+    r.wide.assign(D * plain->wide_words, 0);
+    check(pvw_decrypt_batch_plain(p->ctx, sk.secret_coeffs.data(), c1s.data(), c2col.data(), D, cts[0].repr, r.values.data(),
+                                  r.noise.data(), status.data(), plain->modulus, plain->wide_words, r.wide.data()));
+  } else {
+    check(pvw_decrypt_batch_checked(p->ctx, sk.secret_coeffs.data(), c1s.data(), c2col.data(), D, cts[0].repr, r.values.data(),
+                                    r.noise.data(), status.data()));
   }
+  checked_report(r, status, bound, plain_on(plain));
   return r;
 }
 // the default bound of a checked decrypt: total_bound of verify_correctness_condition (parameters.rs:516-543)
@@ -595,27 +615,34 @@ inline PvwCiphertext aggregate_ciphertexts(const std::vector<PvwCiphertext>& cts
   check(pvw_ct_sum(p->ctx, in.c1s.data(), in.c2s.data(), cts.size(), in.valid_ptr(), 0, p->n, out.c1.data(), out.c2.data(), nullptr));
   return out;
 }
-// party_index's aggregate share with its report (pvw_decrypt_sum_checked); bound 0 = count * noise_bound
+// party_index's aggregate share with its report (pvw_decrypt_sum_checked); bound 0 = count * noise_bound.  plain: the sum of
+// the shares mod plain->modulus, or wide, where the u64 word of a field-sized sum is 0 (pvw_decrypt_sum_plain)
 inline CheckedShares decrypt_party_sum(const std::vector<PvwCiphertext>& cts, const SecretKey& sk, uint32_t party_index,
-                                       const std::vector<bool>& valid = {}, uint64_t bound = 0) {
+                                       const std::vector<bool>& valid = {}, uint64_t bound = 0, const pvw_plain_t* plain = nullptr) {
   const SumInputs in = sum_inputs(cts, valid);
   const auto& p = cts[0].params;
   if (party_index >= p->n) throw PvwError(1, "Party index exceeds maximum");
   const size_t P = p->poly_words();
   std::vector<uint64_t> c2col;
   for (const auto& ct : cts) c2col.insert(c2col.end(), ct.c2.begin() + (size_t)party_index * P, ct.c2.begin() + (size_t)(party_index + 1) * P);
-  uint32_t status = 0, count = 0;
+  std::vector<uint32_t> status(1);
+  uint32_t count = 0;
   CheckedShares r{std::vector<uint64_t>(1), std::vector<uint64_t>(1), std::vector<bool>(1), std::vector<bool>(1)};
-  check(pvw_decrypt_sum_checked(p->ctx, sk.secret_coeffs.data(), in.c1s.data(), c2col.data(), cts.size(), in.valid_ptr(), cts[0].repr,
-                                r.values.data(), r.noise.data(), &status, &count));
+  if (plain_on(plain)) {
+    r.wide.assign(plain->wide_words, 0);
+    check(pvw_decrypt_sum_plain(p->ctx, sk.secret_coeffs.data(), in.c1s.data(), c2col.data(), cts.size(), in.valid_ptr(), cts[0].repr,
+                                r.values.data(), r.noise.data(), status.data(), &count, plain->modulus, plain->wide_words, r.wide.data()));
+  } else {
+    check(pvw_decrypt_sum_checked(p->ctx, sk.secret_coeffs.data(), in.c1s.data(), c2col.data(), cts.size(), in.valid_ptr(), cts[0].repr,
+                                  r.values.data(), r.noise.data(), status.data(), &count));
+  }
   if (!bound) bound = (uint64_t)count * noise_bound(p->ctx);
-  r.lossy[0] = (status & PVW_DEC_LOSSY) != 0;
-  r.valid[0] = !r.lossy[0] && r.noise[0] <= bound;
+  checked_report(r, status, bound, plain_on(plain));
   return r;
 }
 // every party's aggregate share in one call (pvw_decrypt_all_sum_checked); parties with consecutive indices
 inline CheckedShares decrypt_all_party_sums(const std::vector<PvwCiphertext>& cts, const std::vector<Party>& parties,
-                                            const std::vector<bool>& valid = {}, uint64_t bound = 0) {
+                                            const std::vector<bool>& valid = {}, uint64_t bound = 0, const pvw_plain_t* plain = nullptr) {
   const SumInputs in = sum_inputs(cts, valid);
   const auto& p = cts[0].params;
   const size_t NP = parties.size(), kl = (size_t)p->k * p->l;
@@ -628,16 +655,18 @@ inline CheckedShares decrypt_all_party_sums(const std::vector<PvwCiphertext>& ct
   }
   std::vector<uint32_t> status(NP);
   uint32_t count = 0;
-  const int32_t rc = pvw_decrypt_all_sum_checked(p->ctx, parties[0].index, parties[0].index + (uint32_t)NP, sk.data(), in.c1s.data(),
-                                                 in.c2s.data(), cts.size(), in.valid_ptr(), cts[0].repr, r.values.data(), r.noise.data(),
-                                                 status.data(), &count);
+  if (plain_on(plain)) r.wide.assign(NP * plain->wide_words, 0);
+  const int32_t rc =
+      plain_on(plain)
+          ? pvw_decrypt_all_sum_plain(p->ctx, parties[0].index, parties[0].index + (uint32_t)NP, sk.data(), in.c1s.data(), in.c2s.data(),
+                                      cts.size(), in.valid_ptr(), cts[0].repr, r.values.data(), r.noise.data(), status.data(), &count,
+                                      plain->modulus, plain->wide_words, r.wide.data())
+          : pvw_decrypt_all_sum_checked(p->ctx, parties[0].index, parties[0].index + (uint32_t)NP, sk.data(), in.c1s.data(), in.c2s.data(),
+                                        cts.size(), in.valid_ptr(), cts[0].repr, r.values.data(), r.noise.data(), status.data(), &count);
   std::fill(sk.begin(), sk.end(), 0);                                   // the copied keys do not outlive the call
   check(rc);
   if (!bound) bound = (uint64_t)count * noise_bound(p->ctx);
-  for (size_t i = 0; i < NP; ++i) {
-    r.lossy[i] = (status[i] & PVW_DEC_LOSSY) != 0;
-    r.valid[i] = !r.lossy[i] && r.noise[i] <= bound;
-  }
+  checked_report(r, status, bound, plain_on(plain));
   return r;
 }
 

@@ -61,6 +61,8 @@ pub const PVW_PREPARE_MFMA: u32 = 2;
 pub const PVW_PREPARE_SUM: u32 = 4;
 /// status bit of the checked decrypt: the returned word is not the plaintext (pvw_hip.h)
 pub const PVW_DEC_LOSSY: u32 = 1;
+pub const PVW_DEC_NEGATIVE: u32 = 2;
+pub const PVW_DEC_WIDE_TRUNCATED: u32 = 4;
 pub const PVW_OK: i32 = 0;
 pub const PVW_ERR_INVALID_PARAMETERS: i32 = 1;
 pub const PVW_ERR_SAMPLING: i32 = 2;
@@ -173,6 +175,21 @@ extern "C" {
     pub fn pvw_decrypt_all_sum_checked(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, sk: *const i64, c1s: *const u64, c2s: *const u64, num_dealers: usize, valid: *const u8, in_repr: u32, out_u64: *mut u64, noise: *mut u64, status: *mut u32, count: *mut u32) -> i32;
     pub fn pvw_decrypt_all_sum_checked_device(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, d_sk: *const i64, d_c1s: *const u64, d_c2s: *const u64, num_dealers: usize, d_valid: *const u8, in_repr: u32, d_out: *mut u64, d_noise: *mut u64, d_status: *mut u32, d_count: *mut u32, stream: *mut c_void) -> i32;
     pub fn pvw_ctx_sum_capacity(ctx: *const PvwCtx, max_dealers: *mut u64) -> i32;
+    // ---- plain-modulus decode: the checked call plus (plain_modulus, wide_words, wide) ----
+    pub fn pvw_decode_plain(ctx: *mut PvwCtx, noisy: *const u64, count: usize, out_u64: *mut u64, noise: *mut u64, status: *mut u32, plain_modulus: u64, wide_words: u32, wide: *mut u64) -> i32;
+    pub fn pvw_decode_plain_device(ctx: *mut PvwCtx, d_noisy: *const u64, count: usize, d_out: *mut u64, d_noise: *mut u64, d_status: *mut u32, plain_modulus: u64, wide_words: u32, d_wide: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_decode_plain_host(ctx: *const PvwCtx, noisy: *const u64, count: usize, out_u64: *mut u64, noise: *mut u64, status: *mut u32, plain_modulus: u64, wide_words: u32, wide: *mut u64) -> i32;
+    pub fn pvw_selftest_decode_plain(ctx: *const PvwCtx, noisy: *const u64, count: usize, out_u64: *mut u64, noise: *mut u64, status: *mut u32, plain_modulus: u64, wide_words: u32, wide: *mut u64) -> i32;
+    pub fn pvw_decrypt_batch_plain(ctx: *mut PvwCtx, sk: *const i64, c1s: *const u64, c2col: *const u64, num_dealers: usize, in_repr: u32, out_u64: *mut u64, noise: *mut u64, status: *mut u32, plain_modulus: u64, wide_words: u32, wide: *mut u64) -> i32;
+    pub fn pvw_decrypt_batch_plain_device(ctx: *mut PvwCtx, d_sk: *const i64, d_c1s: *const u64, d_c2col: *const u64, num_dealers: usize, in_repr: u32, d_noisy: *mut u64, d_out: *mut u64, d_noise: *mut u64, d_status: *mut u32, plain_modulus: u64, wide_words: u32, d_wide: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_decrypt_batch_device_sk_plain(ctx: *mut PvwCtx, key: *const PvwSk, d_c1s: *const u64, d_c2col: *const u64, num_dealers: usize, in_repr: u32, d_noisy: *mut u64, d_out: *mut u64, d_noise: *mut u64, d_status: *mut u32, plain_modulus: u64, wide_words: u32, d_wide: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_decrypt_all_plain(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, sk: *const i64, c1s: *const u64, c2s: *const u64, num_dealers: usize, in_repr: u32, out_u64: *mut u64, noise: *mut u64, status: *mut u32, plain_modulus: u64, wide_words: u32, wide: *mut u64) -> i32;
+    pub fn pvw_decrypt_all_plain_device(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, d_sk: *const i64, d_c1s: *const u64, d_c2s: *const u64, num_dealers: usize, in_repr: u32, d_out: *mut u64, d_noise: *mut u64, d_status: *mut u32, plain_modulus: u64, wide_words: u32, d_wide: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_decrypt_sum_plain(ctx: *mut PvwCtx, sk: *const i64, c1s: *const u64, c2col: *const u64, num_dealers: usize, valid: *const u8, in_repr: u32, out_u64: *mut u64, noise: *mut u64, status: *mut u32, count: *mut u32, plain_modulus: u64, wide_words: u32, wide: *mut u64) -> i32;
+    pub fn pvw_decrypt_sum_plain_device(ctx: *mut PvwCtx, d_sk: *const i64, d_c1s: *const u64, d_c2col: *const u64, num_dealers: usize, d_valid: *const u8, in_repr: u32, d_noisy: *mut u64, d_out: *mut u64, d_noise: *mut u64, d_status: *mut u32, d_count: *mut u32, plain_modulus: u64, wide_words: u32, d_wide: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_decrypt_sum_device_sk_plain(ctx: *mut PvwCtx, key: *const PvwSk, d_c1s: *const u64, d_c2col: *const u64, num_dealers: usize, d_valid: *const u8, in_repr: u32, d_noisy: *mut u64, d_out: *mut u64, d_noise: *mut u64, d_status: *mut u32, d_count: *mut u32, plain_modulus: u64, wide_words: u32, d_wide: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_decrypt_all_sum_plain(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, sk: *const i64, c1s: *const u64, c2s: *const u64, num_dealers: usize, valid: *const u8, in_repr: u32, out_u64: *mut u64, noise: *mut u64, status: *mut u32, count: *mut u32, plain_modulus: u64, wide_words: u32, wide: *mut u64) -> i32;
+    pub fn pvw_decrypt_all_sum_plain_device(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, d_sk: *const i64, d_c1s: *const u64, d_c2s: *const u64, num_dealers: usize, d_valid: *const u8, in_repr: u32, d_out: *mut u64, d_noise: *mut u64, d_status: *mut u32, d_count: *mut u32, plain_modulus: u64, wide_words: u32, d_wide: *mut u64, stream: *mut c_void) -> i32;
     pub fn pvw_decode(ctx: *mut PvwCtx, noisy: *const u64, count: usize, out_u64: *mut u64) -> i32;
     pub fn pvw_decode_host(ctx: *const PvwCtx, noisy: *const u64, count: usize, out_u64: *mut u64) -> i32;
     pub fn pvw_decode_device(ctx: *mut PvwCtx, d_noisy: *const u64, count: usize, d_out: *mut u64, stream: *mut c_void) -> i32;

@@ -277,6 +277,36 @@ pub fn decrypt_party_shares(all_ciphertexts: &[PvwCiphertext], secret_key: &Secr
 /// and values, plus `noise[d]` (max |residual|, saturating at u64::MAX) and `lossy[d]` (the value is not the plaintext).
 /// A share is valid when it is not lossy and its noise is at most the caller's bound (e.g. `pvw_ctx_noise_bound`).
 pub fn decrypt_party_shares_checked(all_ciphertexts: &[PvwCiphertext], secret_key: &SecretKey, party_index: usize) -> Result<(Vec<u64>, Vec<u64>, Vec<bool>)> {
+    let r = decrypt_party_shares_plain(all_ciphertexts, secret_key, party_index, &PlainOptions::default())?;
+    Ok((r.values, r.noise, r.status.iter().map(|s| s & sys::PVW_DEC_LOSSY != 0).collect()))
+}
+
+/// EXTENSION: the plain options of a decrypt.  `modulus` 0 = none, else 2 <= modulus < 2^62 (any integer): the
+/// values come back as P mod modulus, the mathematical residue, where the u64 conversion of decryption.rs:226-247 returns 0
+/// for P < 0 or P >= 2^64.  `wide_words` 0 = none, else 1 ..= words of Q: the low words of |P| per share.  Both 0: the
+/// checked call as it is.
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct PlainOptions {
+    pub modulus: u64,
+    pub wide_words: u32,
+}
+
+/// What a plain decrypt reports: per share the value, the noise, the status bits (`PVW_DEC_LOSSY`,
+/// `PVW_DEC_NEGATIVE`, `PVW_DEC_WIDE_TRUNCATED`) and `wide_words` little-endian words of |P| (empty when none were asked for).
+#[derive(Clone, Debug, Default)]
+pub struct PlainDecryption {
+    pub values: Vec<u64>,
+    pub noise: Vec<u64>,
+    pub status: Vec<u32>,
+    pub wide: Vec<u64>,
+}
+
+fn wide_ptr(wide: &mut Vec<u64>) -> *mut u64 {
+    if wide.is_empty() { std::ptr::null_mut() } else { wide.as_mut_ptr() }
+}
+
+/// EXTENSION: `decrypt_party_shares_checked` with the plain options (`pvw_decrypt_batch_plain`).
+pub fn decrypt_party_shares_plain(all_ciphertexts: &[PvwCiphertext], secret_key: &SecretKey, party_index: usize, plain: &PlainOptions) -> Result<PlainDecryption> {
     if all_ciphertexts.is_empty() {
         return Err(PvwError::InvalidParameters("No ciphertexts provided".to_string()));
     }
@@ -301,13 +331,14 @@ pub fn decrypt_party_shares_checked(all_ciphertexts: &[PvwCiphertext], secret_ke
     }
     let mut sk = flat_secret(secret_key);
     let (mut out, mut noise, mut status) = (vec![0u64; d], vec![0u64; d], vec![0u32; d]);
+    let mut wide = vec![0u64; d * plain.wide_words as usize];
     let rc = unsafe {
-        sys::pvw_decrypt_batch_checked(params.hip.raw(), sk.as_ptr(), c1s.as_ptr(), c2col.as_ptr(), d, sys::PVW_REPR_POWER, out.as_mut_ptr(),
-                                       noise.as_mut_ptr(), status.as_mut_ptr())
+        sys::pvw_decrypt_batch_plain(params.hip.raw(), sk.as_ptr(), c1s.as_ptr(), c2col.as_ptr(), d, sys::PVW_REPR_POWER, out.as_mut_ptr(),
+                                     noise.as_mut_ptr(), status.as_mut_ptr(), plain.modulus, plain.wide_words, wide_ptr(&mut wide))
     };
     sk.zeroize();
     check(rc)?;
-    Ok((out, noise, status.iter().map(|s| s & sys::PVW_DEC_LOSSY != 0).collect()))
+    Ok(PlainDecryption { values: out, noise, status, wide })
 }
 
 /// EXTENSION -- no single reference function behind it.  The loop examples/pvw.rs:138-149 and tests/crypto.rs:284-287
@@ -412,6 +443,14 @@ pub fn aggregate_ciphertexts(ciphertexts: &[PvwCiphertext], valid: Option<&[bool
 /// EXTENSION: party `party_index`'s aggregate share from ONE decrypt of the summed ciphertext (`pvw_decrypt_sum_checked`):
 /// (value, noise, lossy, dealers summed).  `noise` is the exact max residual of the aggregate.
 pub fn decrypt_party_sum(ciphertexts: &[PvwCiphertext], secret_key: &SecretKey, party_index: usize, valid: Option<&[bool]>) -> Result<(u64, u64, bool, u32)> {
+    let (r, count) = decrypt_party_sum_plain(ciphertexts, secret_key, party_index, valid, &PlainOptions::default())?;
+    Ok((r.values[0], r.noise[0], r.status[0] & sys::PVW_DEC_LOSSY != 0, count))
+}
+
+/// EXTENSION: `decrypt_party_sum` with the plain options (`pvw_decrypt_sum_plain`): the sum of the party's shares
+/// mod `plain.modulus` and / or as wide words -- exact where the u64 word of a field-sized sum is 0.  (report of one share,
+/// dealers summed)
+pub fn decrypt_party_sum_plain(ciphertexts: &[PvwCiphertext], secret_key: &SecretKey, party_index: usize, valid: Option<&[bool]>, plain: &PlainOptions) -> Result<(PlainDecryption, u32)> {
     let (c1s, c2s, v) = sum_inputs(ciphertexts, valid)?;
     let params = &ciphertexts[0].params;
     if party_index >= params.n {
@@ -421,22 +460,31 @@ pub fn decrypt_party_sum(ciphertexts: &[PvwCiphertext], secret_key: &SecretKey, 
     let c2col: Vec<u64> = c2s.chunks_exact(params.n * words).flat_map(|ct| ct[party_index * words..(party_index + 1) * words].to_vec()).collect();
     let mut sk = flat_secret(secret_key);
     let (mut out, mut noise, mut status, mut count) = (0u64, 0u64, 0u32, 0u32);
+    let mut wide = vec![0u64; plain.wide_words as usize];
     let rc = unsafe {
-        sys::pvw_decrypt_sum_checked(params.hip.raw(), sk.as_ptr(), c1s.as_ptr(), c2col.as_ptr(), ciphertexts.len(), valid_ptr(&v),
-                                     sys::PVW_REPR_POWER, &mut out, &mut noise, &mut status, &mut count)
+        sys::pvw_decrypt_sum_plain(params.hip.raw(), sk.as_ptr(), c1s.as_ptr(), c2col.as_ptr(), ciphertexts.len(), valid_ptr(&v),
+                                   sys::PVW_REPR_POWER, &mut out, &mut noise, &mut status, &mut count, plain.modulus, plain.wide_words,
+                                   wide_ptr(&mut wide))
     };
     sk.zeroize();
     check(rc)?;
-    Ok((out, noise, status & sys::PVW_DEC_LOSSY != 0, count))
+    Ok((PlainDecryption { values: vec![out], noise: vec![noise], status: vec![status], wide }, count))
 }
 
 /// EXTENSION: every party's aggregate share in one call (`pvw_decrypt_all_sum_checked`): (values, noise, lossy) per party.
 /// `parties` must carry consecutive indices.
 pub fn decrypt_all_party_sums(ciphertexts: &[PvwCiphertext], parties: &[crate::keys::public_key::Party], valid: Option<&[bool]>) -> Result<(Vec<u64>, Vec<u64>, Vec<bool>)> {
+    let r = decrypt_all_party_sums_plain(ciphertexts, parties, valid, &PlainOptions::default())?;
+    Ok((r.values, r.noise, r.status.iter().map(|s| s & sys::PVW_DEC_LOSSY != 0).collect()))
+}
+
+/// EXTENSION: `decrypt_all_party_sums` with the plain options (`pvw_decrypt_all_sum_plain`); wide is
+/// [parties][wide_words].
+pub fn decrypt_all_party_sums_plain(ciphertexts: &[PvwCiphertext], parties: &[crate::keys::public_key::Party], valid: Option<&[bool]>, plain: &PlainOptions) -> Result<PlainDecryption> {
     let (c1s, c2s, v) = sum_inputs(ciphertexts, valid)?;
     let params = &ciphertexts[0].params;
     if parties.is_empty() {
-        return Ok((Vec::new(), Vec::new(), Vec::new()));
+        return Ok(PlainDecryption::default());
     }
     let lo = parties[0].index;
     for (i, party) in parties.iter().enumerate() {
@@ -450,12 +498,13 @@ pub fn decrypt_all_party_sums(ciphertexts: &[PvwCiphertext], parties: &[crate::k
     let mut sk: Vec<i64> = parties.iter().flat_map(|p| flat_secret(&p.secret_key)).collect();
     let np = parties.len();
     let (mut out, mut noise, mut status) = (vec![0u64; np], vec![0u64; np], vec![0u32; np]);
+    let mut wide = vec![0u64; np * plain.wide_words as usize];
     let rc = unsafe {
-        sys::pvw_decrypt_all_sum_checked(params.hip.raw(), lo as u32, (lo + np) as u32, sk.as_ptr(), c1s.as_ptr(), c2s.as_ptr(), ciphertexts.len(),
-                                         valid_ptr(&v), sys::PVW_REPR_POWER, out.as_mut_ptr(), noise.as_mut_ptr(), status.as_mut_ptr(),
-                                         std::ptr::null_mut())
+        sys::pvw_decrypt_all_sum_plain(params.hip.raw(), lo as u32, (lo + np) as u32, sk.as_ptr(), c1s.as_ptr(), c2s.as_ptr(), ciphertexts.len(),
+                                       valid_ptr(&v), sys::PVW_REPR_POWER, out.as_mut_ptr(), noise.as_mut_ptr(), status.as_mut_ptr(),
+                                       std::ptr::null_mut(), plain.modulus, plain.wide_words, wide_ptr(&mut wide))
     };
     sk.zeroize();
     check(rc)?;
-    Ok((out, noise, status.iter().map(|s| s & sys::PVW_DEC_LOSSY != 0).collect()))
+    Ok(PlainDecryption { values: out, noise, status, wide })
 }
