@@ -535,6 +535,26 @@ static int32_t ws_scratch(Workspace* w, size_t bytes) {
   w->scratch_bytes = bytes;
   return PVW_OK;
 }
+// Grows one of the workspace's own buffers (dpart, sumbuf) to `need` bytes: `s`, whose queued work may still read the old
+// block, is drained first; clear: the old block may hold key material.  (ws_scratch waits for nothing and resets `wiped`.)
+static int32_t ws_grow(u64** buf, size_t* have, size_t need, hipStream_t s, bool clear) {
+  if (*have >= need) return PVW_OK;
+  if (*buf) {
+    PVW_HIP(hipStreamSynchronize(s));
+    if (clear) hipMemset(*buf, 0, *have);
+    hipFree(*buf);
+    *buf = nullptr;
+    *have = 0;
+  }
+  PVW_HIP(hipMalloc((void**)buf, need));
+  *have = need;
+  return PVW_OK;
+}
+// items (dealers' ciphertext words, rows) per staged piece of at most 1 GiB: at least one, at most `most`
+static size_t chunk_1gib(size_t item_bytes, size_t most) {
+  const size_t per = ((size_t)1 << 30) / item_bytes;
+  return per == 0 ? 1 : (per < most ? per : most);
+}
 static void ws_free(Workspace* w) {
   if (!w) return;
   // r-hat / s-hat vectors and the staging block may hold key material of the last call
@@ -601,6 +621,7 @@ static int32_t ws_for_stream(pvw_ctx* c, hipStream_t s, Workspace** out) {
 
 // The scratch of one call: regions added in order, each rounded up to `align` bytes (256; the wire codec's 16).  `total`
 // is what ws_scratch is asked for; at<T>(i) points into the block that take() bound.
+// A call's results take their regions through Report::reserve and are addressed through Report::in.
 struct Scratch {
   size_t align, total = 0;
   std::vector<size_t> off;
@@ -620,6 +641,67 @@ struct Scratch {
   size_t bytes(size_t i) const { return (i + 1 < off.size() ? off[i + 1] : total) - off[i]; }   // rounded
   // regions i..j (one contiguous span) hold key material for the rest of the call
   void secret(Workspace* w, size_t i, size_t j) const { ws_mark_secret(w, base + off[i], off[j] + bytes(j) - off[i]); }
+};
+
+// What a decode reports for each result: out, and where asked for noise and status (the checked decode), the value
+// mod `m` in out and the wide words [.][ww] (the plain decode).  One value stands for the caller's buffers (host or
+// device) and, through in() / packed_at(), for the staging copy with the same fields.
+struct Report {
+  u64* out = nullptr;
+  u64* noise = nullptr;
+  u32* status = nullptr;
+  u64* wide = nullptr;
+  size_t ww = 0;
+  Mod m{0, 0, 0};                                        // q = 0: no plain modulus
+  template <class T> static T* from(T* p, size_t i) { return p ? p + i : nullptr; }
+  // the same report starting at result i
+  Report at(size_t i) const {
+    Report r = *this;
+    r.out = from(out, i), r.noise = from(noise, i), r.status = from(status, i), r.wide = from(wide, i * ww);
+    return r;
+  }
+  // launch_decode's options: NULL when none is set (the checked decode then runs as it is)
+  bool plain_on() const { return m.q || ww; }
+  PlainArgs plain() const { return PlainArgs{m, (u32)ww, ww ? wide : nullptr}; }
+  // Scratch regions for n results, always four and in this order: out | noise | status | wide; returns the first one's index
+  static size_t reserve(Scratch& sc, size_t n, bool noise, bool status, size_t ww) {
+    const size_t r = sc.add(n * 8);
+    sc.add(noise ? n * 8 : 0), sc.add(status ? n * 4 : 0), sc.add(n * ww * 8);
+    return r;
+  }
+  size_t reserve(Scratch& sc, size_t n) const { return reserve(sc, n, noise, status, ww); }
+  // this report's fields in the regions reserved at r
+  Report in(const Scratch& sc, size_t r) const {
+    Report d = *this;
+    d.out = sc.at(r), d.noise = noise ? sc.at(r + 1) : nullptr, d.status = status ? sc.at<u32>(r + 2) : nullptr;
+    d.wide = ww ? sc.at(r + 3) : nullptr;
+    return d;
+  }
+  // ... and back to back at `base`: out [n] | noise [n] | status [n] (4 bytes each, 8 reserved) | wide [n][ww]
+  static size_t packed_bytes(size_t n, size_t ww) { return n * (24 + 8 * ww); }
+  Report packed_at(u64* base, size_t n) const {
+    Report d = *this;
+    d.out = base, d.noise = noise ? base + n : nullptr, d.status = status ? (u32*)(base + 2 * n) : nullptr;
+    d.wide = ww ? base + 3 * n : nullptr;
+    return d;
+  }
+  // n results into dst, a report of the same fields (wide_first: the wide words ahead of out instead of behind status)
+  int32_t copy_to(const Report& dst, size_t n, hipMemcpyKind kind, hipStream_t s, bool wide_first = false) const {
+    if (ww && wide_first) PVW_HIP(hipMemcpyAsync(dst.wide, wide, n * ww * 8, kind, s));
+    PVW_HIP(hipMemcpyAsync(dst.out, out, n * 8, kind, s));
+    if (noise) PVW_HIP(hipMemcpyAsync(dst.noise, noise, n * 8, kind, s));
+    if (status) PVW_HIP(hipMemcpyAsync(dst.status, status, n * 4, kind, s));
+    if (ww && !wide_first) PVW_HIP(hipMemcpyAsync(dst.wide, wide, n * ww * 8, kind, s));
+    return PVW_OK;
+  }
+  // a [rows][cols] block into dst, whose rows are D results apart
+  int32_t copy_block_to(const Report& dst, size_t rows, size_t cols, size_t D, hipMemcpyKind kind, hipStream_t s) const {
+    PVW_HIP(hipMemcpy2DAsync(dst.out, D * 8, out, cols * 8, cols * 8, rows, kind, s));
+    if (noise) PVW_HIP(hipMemcpy2DAsync(dst.noise, D * 8, noise, cols * 8, cols * 8, rows, kind, s));
+    if (status) PVW_HIP(hipMemcpy2DAsync(dst.status, D * 4, status, cols * 4, cols * 4, rows, kind, s));
+    if (ww) PVW_HIP(hipMemcpy2DAsync(dst.wide, D * ww * 8, wide, cols * ww * 8, cols * ww * 8, rows, kind, s));
+    return PVW_OK;
+  }
 };
 
 // the helper stream and at least `events` events, for a call that runs on two streams
@@ -672,6 +754,23 @@ static int32_t device_end(Workspace* w, hipStream_t s, int32_t rc) {
   }
   if (ws_wipe_secrets(w, s) != hipSuccess && rc == PVW_OK) rc = fail(PVW_ERR_INTERNAL, "wipe failed");
   return rc;
+}
+
+// Every device-pointer entry point that marks key material runs its body here, host_call's counterpart: on the caller's
+// stream and that stream's workspace, ended by device_end.  pre(s) runs BEFORE the workspace is looked up: the checks a call
+// made under stream capture has to pass before anything is allocated (sum_capture_check).
+template <class Pre, class Body>
+static int32_t device_call(pvw_ctx* c, void* stream, Pre&& pre, Body&& body) {
+  PVW_TRY(ensure_device(c));
+  const hipStream_t s = call_stream(c, stream);
+  PVW_TRY(pre(s));
+  Workspace* w;
+  PVW_TRY(ws_for_stream(c, s, &w));
+  return device_end(w, s, body(w, s));
+}
+template <class Body>
+static int32_t device_call(pvw_ctx* c, void* stream, Body&& body) {
+  return device_call(c, stream, [](hipStream_t) { return (int32_t)PVW_OK; }, body);
 }
 
 // ------------------------------------------------------------------------ parameters
@@ -2154,9 +2253,10 @@ static void decode_checked_one(const pvw_ctx* c, const uint64_t* noisy, u64* out
   }
   *noise = BigInt::cmp(mx, sat) >= 0 ? PVW_NOISE_SAT : mx.low_u64();
 }
-// The plain options of one call, checked before any device work: modulus 0 (none) or 2 <= modulus < 2^62, any
-// integer; wide_words 0 (none) or 1 .. W, W = the 64-bit words of Q; wide [count][wide_words] where wide_words != 0.
-static int32_t plain_args(const pvw_ctx* c, u64 modulus, u32 wide_words, u64* wide, PlainArgs* pa) {
+// The report of one call from the entry point's arguments.  Its plain options are checked before any device work:
+// modulus 0 (none) or 2 <= modulus < 2^62, any integer; wide_words 0 (none) or 1 .. W, W = the 64-bit words of Q; wide
+// [count][wide_words] where wide_words != 0.  The checked and unchecked forms are the call with no option set.
+static int32_t report_args(const pvw_ctx* c, u64* out, u64* noise, u32* status, u64 modulus, u32 wide_words, u64* wide, Report* r) {
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   if (modulus == 1 || (modulus >> 62)) return fail(PVW_ERR_INVALID_PARAMETERS, "plain modulus must be 0 (none) or in [2, 2^62)");
   if (wide_words > c->Q.mag.size()) {
@@ -2165,15 +2265,16 @@ static int32_t plain_args(const pvw_ctx* c, u64 modulus, u32 wide_words, u64* wi
     return fail(PVW_ERR_INVALID_PARAMETERS, buf);
   }
   if (wide_words && !wide) return fail(PVW_ERR_INVALID_PARAMETERS, "wide_words without a wide buffer");
-  pa->m = modulus ? make_mod(modulus) : Mod{0, 0, 0};
-  pa->wide_words = wide_words;
-  pa->wide = wide_words ? wide : nullptr;
+  r->out = out, r->noise = noise, r->status = status;
+  r->m = modulus ? make_mod(modulus) : Mod{0, 0, 0};
+  r->ww = wide_words;
+  r->wide = wide_words ? wide : nullptr;
   return PVW_OK;
 }
 int32_t pvw_decode_plain_host(const pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out, uint64_t* noise,
                               uint32_t* status, uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
-  PlainArgs pa;
-  PVW_TRY(plain_args(c, plain_modulus, wide_words, wide, &pa));
+  Report rep;
+  PVW_TRY(report_args(c, out, noise, status, plain_modulus, wide_words, wide, &rep));
   if ((!noisy || !out) && count) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   const size_t P = c->poly();
   unsigned nt = std::thread::hardware_concurrency();
@@ -2296,10 +2397,11 @@ int32_t pvw_selftest_decode_checked(const pvw_ctx* c, const uint64_t* noisy, siz
 // the plain form of the same: decode_one_fixed<true, true>, the tail the fixed-width kernel runs
 int32_t pvw_selftest_decode_plain(const pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out, uint64_t* noise,
                                   uint32_t* status, uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
-  PlainArgs pa;
-  PVW_TRY(plain_args(c, plain_modulus, wide_words, wide, &pa));
+  Report rep;
+  PVW_TRY(report_args(c, out, noise, status, plain_modulus, wide_words, wide, &rep));
   if ((!noisy || !out) && count) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  if (!pa.m.q && !pa.wide_words) return pvw_selftest_decode_checked(c, noisy, count, out, noise, status);
+  const PlainArgs pa = rep.plain();
+  if (!rep.plain_on()) return pvw_selftest_decode_checked(c, noisy, count, out, noise, status);
   const DecodeTables& t = c->dec_host;
   std::vector<u64> x(t.W + 1), y(t.W), nres(t.L);
   for (size_t d = 0; d < count; ++d)
@@ -2404,96 +2506,104 @@ int32_t pvw_selftest_decode_shortcuts(const pvw_ctx* c, const uint64_t* noisy, s
 // The decode of `cnt` noisy polynomials at nz (decryption.rs:116, :10-58), still in the NTT domain when `ntt_domain`.  The
 // decode can transform back while it stages its input (no launch for :116), at the price of 94 instead of 79 registers.
 // Taken while its workgroups (two ciphertexts each) are resident all at once anyway; beyond, and when the decode shares the
-// chip with other work (`shared`), the 79-register decode runs behind a transform launch of its own.  noise / status: the
-// checked decode's report (NULL: not asked for); wipe / wipe_bytes / wiped: as launch_decode.
-static int32_t decode_tail(pvw_ctx* c, u64* nz, size_t cnt, bool ntt_domain, bool shared, hipStream_t s, u64* out,
-                           u64* noise = nullptr, u32* status = nullptr, u64* wipe = nullptr, size_t wipe_bytes = 0,
-                           bool* wiped = nullptr, const PlainArgs* pl = nullptr) {
+// chip with other work (`shared`), the 79-register decode runs behind a transform launch of its own.  rep: where the results
+// go (device pointers; a field not asked for reaches launch_decode as NULL); wipe / wipe_bytes / wiped: as launch_decode.
+static int32_t decode_tail(pvw_ctx* c, u64* nz, size_t cnt, bool ntt_domain, bool shared, hipStream_t s, const Report& rep,
+                           u64* wipe = nullptr, size_t wipe_bytes = 0, bool* wiped = nullptr) {
   if (ntt_domain && (shared || (cnt + 1) / 2 > (size_t)2 * c->num_cus)) {
     ProfScope pi(c, "intt", s);
     PVW_HIP(launch_ntt(nz, cnt, true, c->dt, c->L, c->l, s));
     ntt_domain = false;
   }
+  const PlainArgs pa = rep.plain();
   ProfScope ps(c, "decode", s);
-  PVW_HIP(launch_decode(nz, out, cnt, c->dec_dev, s, ntt_domain ? &c->dt : nullptr, wipe, wipe_bytes, wiped, noise, status, pl));
+  PVW_HIP(launch_decode(nz, rep.out, cnt, c->dec_dev, s, ntt_domain ? &c->dt : nullptr, wipe, wipe_bytes, wiped, rep.noise, rep.status,
+                        rep.plain_on() ? &pa : nullptr));
   return PVW_OK;
 }
-// the options with the wide words of ciphertext `first` of the call's at the front; NULL when no option is set (the callee then
-// runs the checked decode as it is)
-struct PlainAt {
-  PlainArgs a;
-  bool on;
-  PlainAt(const PlainArgs* pl, u64* wide_base, size_t first) : a{}, on(false) {
-    if (!pl || (!pl->m.q && !pl->wide_words)) return;
-    a = *pl;
-    a.wide = a.wide_words ? wide_base + first * a.wide_words : nullptr;
-    on = true;
-  }
-  PlainAt(const PlainArgs* pl, size_t first) : PlainAt(pl, pl ? pl->wide : nullptr, first) {}
-  const PlainArgs* ptr() const { return on ? &a : nullptr; }
-};
-static size_t plain_ww(const PlainArgs* pl) { return pl ? pl->wide_words : 0; }
 
-// decode_scalar_pvw_rns on the device; checked: plus noise[d] / status[d] (either may be NULL)
-static int32_t decode_device_core(pvw_ctx* c, const uint64_t* d_noisy, size_t count, uint64_t* d_out, uint64_t* d_noise,
-                                  uint32_t* d_status, void* stream, const PlainArgs* pl) {
-  if (!c || ((!d_noisy || !d_out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+// decode_scalar_pvw_rns on the device; checked: plus noise[d] / status[d] (either may be NULL); plain (DESIGN
+// 8.8): the checked call plus the plain options
+int32_t pvw_decode_plain_device(pvw_ctx* c, const uint64_t* d_noisy, size_t count, uint64_t* d_out, uint64_t* d_noise,
+                                uint32_t* d_status, uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream) {
+  Report rep;
+  PVW_TRY(report_args(c, d_out, d_noise, d_status, plain_modulus, wide_words, d_wide, &rep));
+  if ((!d_noisy || !d_out) && count) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   if (count == 0) return PVW_OK;
   PVW_TRY(ensure_device(c));
   // power basis in: read only
-  return decode_tail(c, const_cast<u64*>(d_noisy), count, false, false, call_stream(c, stream), d_out, d_noise, d_status, nullptr, 0,
-                     nullptr, PlainAt(pl, 0).ptr());
+  return decode_tail(c, const_cast<u64*>(d_noisy), count, false, false, call_stream(c, stream), rep);
 }
 int32_t pvw_decode_checked_device(pvw_ctx* c, const uint64_t* d_noisy, size_t count, uint64_t* d_out, uint64_t* d_noise,
                                   uint32_t* d_status, void* stream) {
-  return decode_device_core(c, d_noisy, count, d_out, d_noise, d_status, stream, nullptr);
-}
-// plain forms: the checked call plus the plain options
-int32_t pvw_decode_plain_device(pvw_ctx* c, const uint64_t* d_noisy, size_t count, uint64_t* d_out, uint64_t* d_noise,
-                                uint32_t* d_status, uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream) {
-  PlainArgs pa;
-  PVW_TRY(plain_args(c, plain_modulus, wide_words, d_wide, &pa));
-  return decode_device_core(c, d_noisy, count, d_out, d_noise, d_status, stream, &pa);
+  return pvw_decode_plain_device(c, d_noisy, count, d_out, d_noise, d_status, 0, 0, nullptr, stream);
 }
 int32_t pvw_decode_device(pvw_ctx* c, const uint64_t* d_noisy, size_t count, uint64_t* d_out, void* stream) {
   return pvw_decode_checked_device(c, d_noisy, count, d_out, nullptr, nullptr, stream);
 }
 // host buffers in and out
-static int32_t decode_staged(pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out, uint64_t* noise, uint32_t* status,
-                             const PlainArgs* pl) {
-  if (!c || ((!noisy || !out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+int32_t pvw_decode_plain(pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out, uint64_t* noise, uint32_t* status,
+                         uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
+  Report rep;
+  PVW_TRY(report_args(c, out, noise, status, plain_modulus, wide_words, wide, &rep));
+  if ((!noisy || !out) && count) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   if (count == 0) return PVW_OK;
   PVW_TRY(ensure_device(c));
-  const size_t ww = plain_ww(pl);
   Scratch sc;
-  const size_t r_nz = sc.add(count * c->poly() * 8), r_out = sc.add(count * 8), r_ns = sc.add(noise ? count * 8 : 0),
-               r_st = sc.add(status ? count * 4 : 0), r_wd = sc.add(count * ww * 8);
+  const size_t r_nz = sc.add(count * c->poly() * 8), r_rep = rep.reserve(sc, count);
   return host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
+    const Report dev = rep.in(sc, r_rep);
     PVW_HIP(hipMemcpyAsync(sc.at(r_nz), noisy, count * c->poly() * 8, hipMemcpyHostToDevice, w->stream));
-    PVW_TRY(decode_tail(c, sc.at(r_nz), count, false, false, w->stream, sc.at(r_out), noise ? sc.at(r_ns) : nullptr,
-                        status ? sc.at<u32>(r_st) : nullptr, nullptr, 0, nullptr, PlainAt(pl, sc.at(r_wd), 0).ptr()));
-    PVW_HIP(hipMemcpyAsync(out, sc.at(r_out), count * 8, hipMemcpyDeviceToHost, w->stream));
-    if (noise) PVW_HIP(hipMemcpyAsync(noise, sc.at(r_ns), count * 8, hipMemcpyDeviceToHost, w->stream));
-    if (status) PVW_HIP(hipMemcpyAsync(status, sc.at(r_st), count * 4, hipMemcpyDeviceToHost, w->stream));
-    if (ww) PVW_HIP(hipMemcpyAsync(pl->wide, sc.at(r_wd), count * ww * 8, hipMemcpyDeviceToHost, w->stream));
-    return PVW_OK;
+    PVW_TRY(decode_tail(c, sc.at(r_nz), count, false, false, w->stream, dev));
+    return dev.copy_to(rep, count, hipMemcpyDeviceToHost, w->stream);
   });
 }
 int32_t pvw_decode_checked(pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out, uint64_t* noise, uint32_t* status) {
-  return decode_staged(c, noisy, count, out, noise, status, nullptr);
-}
-int32_t pvw_decode_plain(pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out, uint64_t* noise, uint32_t* status,
-                         uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
-  PlainArgs pa;
-  PVW_TRY(plain_args(c, plain_modulus, wide_words, wide, &pa));
-  return decode_staged(c, noisy, count, out, noise, status, &pa);
+  return pvw_decode_plain(c, noisy, count, out, noise, status, 0, 0, nullptr);
 }
 int32_t pvw_decode(pvw_ctx* c, const uint64_t* noisy, size_t count, uint64_t* out) {
   return pvw_decode_checked(c, noisy, count, out, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------ decrypt
+// A secret key kept on the device in the form the inner products read (NTT(sk[j]) in the ciphertext layout,
+// secret_key.rs:98-112): decrypt calls that take one skip the transform of the key and the wipe behind it.  The reference's
+// SecretKey lives as long as its owner does and is ZeroizeOnDrop (secret_key.rs:20-30); so does this: pvw_sk_free clears it.
+struct pvw_sk {
+  pvw_ctx* ctx;
+  u64* shat;       // [k][L][l]
+  size_t bytes;
+};
+// The key of one decrypt on the device: its coefficients (NTT(sk) is then made in w->rhat, marked secret and cleared behind
+// the call), or a resident key's NTT(sk).  Exactly one is set.  key_coeffs / key_resident: from an entry point's argument,
+// with its checks; rc is what the call returns before it does anything else.
+struct KeyRef {
+  const int64_t* coeffs;
+  const u64* shat;
+  int32_t rc;
+};
+static KeyRef key_coeffs(const pvw_ctx* c, const int64_t* d_sk) {
+  if (!c || !d_sk) return KeyRef{nullptr, nullptr, fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument")};
+  return KeyRef{d_sk, nullptr, PVW_OK};
+}
+static KeyRef key_resident(const pvw_ctx* c, const pvw_sk* sk) {
+  if (!c || !sk || !sk->shat) return KeyRef{nullptr, nullptr, fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument")};
+  if (sk->ctx != c) return KeyRef{nullptr, nullptr, fail(PVW_ERR_INVALID_PARAMETERS, "the key was loaded for another context")};
+  return KeyRef{nullptr, sk->shat, PVW_OK};
+}
+// The checks the decrypt families share; each family calls them in the order it has always made them.
+static int32_t check_dealers(size_t D, bool sum = false) {
+  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");          // decryption.rs:286-290
+  if (sum && (D >> 32)) return fail(PVW_ERR_INVALID_PARAMETERS, "a sum takes fewer than 2^32 dealers");
+  return PVW_OK;
+}
+static int32_t check_ntt_input(uint32_t in_repr) {
+  PVW_TRY(check_repr(in_repr));
+  if (in_repr != PVW_REPR_NTT) return fail(PVW_ERR_INVALID_FORMAT, "device decrypt takes NTT-domain ciphertexts");
+  return PVW_OK;
+}
+
 // noisy[d] = sum_j s-hat[j] (.) c1s[d][j] - c2col[d]  for D ciphertexts (decryption.rs:257-274): the inner products as one
 // launch, cut into ranges of j when that gives the launch enough short workgroups (decrypt_split).  Returns in
 // *ntt_domain whether d_noisy still has to be transformed back (change_representation(PowerBasis), :116): with ranges
@@ -2504,14 +2614,7 @@ static int32_t decrypt_mac_only(pvw_ctx* c, Workspace* w, const u64* d_c1s, cons
   if (!shat) shat = w->rhat;                           // NTT(sk) made by this call (launch_prep); else a resident key's
   const u32 k = c->k, l = c->l, L = c->L;
   const u32 ns = decrypt_split(k, L, l, D);
-  if (ns > 1) {
-    const size_t need = (size_t)ns * D * c->poly() * 8;
-    if (w->dpart_bytes < need) {
-      if (w->dpart) { PVW_HIP(hipStreamSynchronize(s)); hipFree(w->dpart); w->dpart = nullptr; w->dpart_bytes = 0; }
-      PVW_HIP(hipMalloc((void**)&w->dpart, need));
-      w->dpart_bytes = need;
-    }
-  }
+  if (ns > 1) PVW_TRY(ws_grow(&w->dpart, &w->dpart_bytes, (size_t)ns * D * c->poly() * 8, s, false));
   {
     ProfScope ps(c, "decrypt_mac", s);
     PVW_HIP(launch_decrypt_mac(d_c1s, shat, d_c2col, d_noisy, c->dt, k, L, l, D, s, w->dpart, ns, alone));
@@ -2524,13 +2627,11 @@ static int32_t decrypt_mac_only(pvw_ctx* c, Workspace* w, const u64* d_c1s, cons
   return PVW_OK;
 }
 // decrypt_party_shares with device pointers end to end: <sk, c1> - c2, the transform back and the gadget decode of D dealer
-// ciphertexts (NTT domain, on `s`); only D x u64 are produced.  The key is d_sk, its
-// coefficients (NTT(sk) is made in w->rhat and marked secret), or key_shat, a resident key's.  Large batches are cut into
+// ciphertexts (NTT domain, on `s`); only D x u64 (and the report asked for) are produced.  Large batches are cut into
 // chunks of about 2 GiB and the decode of chunk i (integer-ALU work, a few waves per CU) runs on a helper stream under the
 // HBM-bound MAC of chunk i+1; `s` waits for the last decode before the call's work counts as complete.
-static int32_t decrypt_batch_enqueue(pvw_ctx* c, Workspace* w, hipStream_t s, const int64_t* d_sk, const u64* key_shat,
-                                     const u64* d_c1s, const u64* d_c2col, size_t D, u64* d_noisy, u64* d_out, u64* d_noise,
-                                     u32* d_status, const PlainArgs* pl = nullptr) {
+static int32_t decrypt_batch_enqueue(pvw_ctx* c, Workspace* w, hipStream_t s, KeyRef key, const u64* d_c1s, const u64* d_c2col,
+                                     size_t D, u64* d_noisy, const Report& rep) {
   const u32 k = c->k, l = c->l, L = c->L;
   const size_t P = c->poly(), shat_bytes = (size_t)k * P * 8;
   // chunks of about 2 GiB of ciphertext (measured: at config 5 in full, 18 GB, overlapping the decode is -7 %;
@@ -2542,20 +2643,20 @@ static int32_t decrypt_batch_enqueue(pvw_ctx* c, Workspace* w, hipStream_t s, co
   if (chunk_env >= 64) chunk = (size_t)chunk_env;
   else if (total_gib >= 3.0) chunk = (D + (size_t)(total_gib / 2.0) - 1) / (size_t)(total_gib / 2.0);
   const size_t nch = (D + chunk - 1) / chunk;
-  if (!key_shat) {
+  if (!key.shat) {
     ws_mark_secret(w, w->rhat, shat_bytes);
     ProfScope ps(c, "prep", s);
-    PVW_HIP(launch_prep(d_sk, nullptr, w->rhat, P, l, k, true, c->dt, L, l, s));   // NTT(sk[j]) once per call (secret_key.rs:98-112)
+    PVW_HIP(launch_prep(key.coeffs, nullptr, w->rhat, P, l, k, true, c->dt, L, l, s));   // NTT(sk[j]) once per call (secret_key.rs:98-112)
   }
   const bool overlap = nch >= 2;
   if (overlap) PVW_TRY(ws_aux(w, nch + 1));
   // one pass on one stream: the decode is the last launch to follow the inner products, and clears NTT(sk) on its way
-  const bool decode_wipes = !overlap && !key_shat;
+  const bool decode_wipes = !overlap && !key.shat;
   for (size_t i = 0; i < nch; ++i) {
     const size_t d0 = i * chunk, cnt = (D - d0) < chunk ? (D - d0) : chunk;
     u64* nz = d_noisy + d0 * P;
     bool ntt_domain = false;
-    PVW_TRY(decrypt_mac_only(c, w, d_c1s + d0 * k * P, d_c2col + d0 * P, cnt, nz, s, &ntt_domain, !overlap, key_shat));   // decryption.rs:257-274
+    PVW_TRY(decrypt_mac_only(c, w, d_c1s + d0 * k * P, d_c2col + d0 * P, cnt, nz, s, &ntt_domain, !overlap, key.shat));   // decryption.rs:257-274
     hipStream_t ds = s;
     if (overlap) {
       PVW_HIP(hipEventRecord(w->events[i], s));
@@ -2563,9 +2664,8 @@ static int32_t decrypt_batch_enqueue(pvw_ctx* c, Workspace* w, hipStream_t s, co
       ds = w->aux;
     }
     bool by_decode = false;
-    PVW_TRY(decode_tail(c, nz, cnt, ntt_domain, overlap, ds, d_out + d0, d_noise ? d_noise + d0 : nullptr,
-                        d_status ? d_status + d0 : nullptr, decode_wipes ? w->rhat : nullptr, decode_wipes ? shat_bytes : 0,
-                        &by_decode, PlainAt(pl, d0).ptr()));
+    PVW_TRY(decode_tail(c, nz, cnt, ntt_domain, overlap, ds, rep.at(d0), decode_wipes ? w->rhat : nullptr,
+                        decode_wipes ? shat_bytes : 0, &by_decode));
     if (by_decode) ws_mark_secret(w, w->rhat, shat_bytes, true);   // recorded as this call's wiped region, no memset
   }
   if (overlap) {
@@ -2574,33 +2674,29 @@ static int32_t decrypt_batch_enqueue(pvw_ctx* c, Workspace* w, hipStream_t s, co
   }
   return PVW_OK;
 }
-// the device-pointer entry points: their argument checks, then the enqueue on the caller's stream
-static int32_t decrypt_batch_core(pvw_ctx* c, const int64_t* d_sk, const u64* key_shat, const uint64_t* d_c1s, const uint64_t* d_c2col,
-                                  size_t D, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, void* stream,
-                                  uint64_t* d_noise = nullptr, uint32_t* d_status = nullptr, const PlainArgs* pl = nullptr) {
-  if (!c || ((!d_c1s || !d_c2col || !d_noisy || !d_out) && D)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(check_repr(in_repr));
-  if (in_repr != PVW_REPR_NTT) return fail(PVW_ERR_INVALID_FORMAT, "device decrypt takes NTT-domain ciphertexts");
-  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");          // decryption.rs:286-290
-  PVW_TRY(ensure_device(c));
-  hipStream_t s;
-  Workspace* w;
-  PVW_TRY(device_ws(c, stream, &s, &w));
-  return device_end(w, s, decrypt_batch_enqueue(c, w, s, d_sk, key_shat, d_c1s, d_c2col, D, d_noisy, d_out, d_noise, d_status, pl));
+// the device-pointer entry points: their argument checks, then the enqueue on the caller's stream.  checked: the
+// same words in d_out, plus d_noise / d_status [D] (either may be NULL); plain: DESIGN 8.8
+static int32_t decrypt_batch_device(pvw_ctx* c, KeyRef key, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D, uint32_t in_repr,
+                                    uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status, uint64_t plain_modulus,
+                                    uint32_t wide_words, uint64_t* d_wide, void* stream) {
+  Report rep;
+  PVW_TRY(key.rc);
+  PVW_TRY(report_args(c, d_out, d_noise, d_status, plain_modulus, wide_words, d_wide, &rep));
+  if ((!d_c1s || !d_c2col || !d_noisy || !d_out) && D) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(check_ntt_input(in_repr));
+  PVW_TRY(check_dealers(D));
+  return device_call(c, stream, [&](Workspace* w, hipStream_t s) {
+    return decrypt_batch_enqueue(c, w, s, key, d_c1s, d_c2col, D, d_noisy, rep);
+  });
 }
 
 int32_t pvw_decrypt_noisy_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col,
                                  size_t D, uint32_t in_repr, uint64_t* d_noisy, void* stream) {
   if (!c || !d_sk || ((!d_c1s || !d_c2col || !d_noisy) && D)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(check_repr(in_repr));
-  if (in_repr != PVW_REPR_NTT) return fail(PVW_ERR_INVALID_FORMAT, "device decrypt takes NTT-domain ciphertexts");
-  PVW_TRY(ensure_device(c));
-  hipStream_t s;
-  Workspace* w;
-  PVW_TRY(device_ws(c, stream, &s, &w));
-  const size_t P = c->poly();
-  ws_mark_secret(w, w->rhat, (size_t)c->k * P * 8);           // NTT(sk), cleared behind the last launch that reads it
-  auto run = [&]() -> int32_t {
+  PVW_TRY(check_ntt_input(in_repr));
+  return device_call(c, stream, [&](Workspace* w, hipStream_t s) -> int32_t {
+    const size_t P = c->poly();
+    ws_mark_secret(w, w->rhat, (size_t)c->k * P * 8);           // NTT(sk), cleared behind the last launch that reads it
     {
       ProfScope ps(c, "prep", s);
       PVW_HIP(launch_prep(d_sk, nullptr, w->rhat, P, c->l, c->k, true, c->dt, c->L, c->l, s));   // secret_key.rs:98-112
@@ -2612,32 +2708,30 @@ int32_t pvw_decrypt_noisy_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t
       PVW_HIP(launch_ntt(d_noisy, D, true, c->dt, c->L, c->l, s));
     }
     return PVW_OK;
-  };
-  return device_end(w, s, run());
+  });
 }
 
 // host buffers: dealers in chunks of <= 1 GiB of ciphertext, staged on the device (a POWER-basis chunk transformed there) and
 // decrypted by the device path; the uploaded coefficients and NTT(sk) do not outlive the call (secret_key.rs:20-30)
 static int32_t decrypt_batch_staged(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
                                     uint32_t in_repr, uint64_t* out_u64, uint64_t* noisy_out, uint64_t* noise, uint32_t* status,
-                                    const PlainArgs* pl = nullptr) {
-  if (!c || !sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");          // decryption.rs:286-290
+                                    uint64_t plain_modulus = 0, uint32_t wide_words = 0, uint64_t* wide = nullptr) {
+  Report rep;
+  PVW_TRY(report_args(c, out_u64, noise, status, plain_modulus, wide_words, wide, &rep));
+  if (!sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(check_dealers(D));
   if (!c1s || !c2col || !out_u64) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   PVW_TRY(check_repr(in_repr));
   PVW_TRY(ensure_device(c));
-  const size_t k = c->k, l = c->l, P = c->poly();
-  size_t per = ((size_t)1 << 30) / (k * P * 8);
-  if (per == 0) per = 1;
-  if (per > D) per = D;
+  const size_t k = c->k, l = c->l, P = c->poly(), per = chunk_1gib(k * P * 8, D);
   Scratch sc;
   const size_t r_sk = sc.add(k * l * 8), r_c1 = sc.add(per * k * P * 8), r_c2 = sc.add(per * P * 8), r_nz = sc.add(per * P * 8),
-               r_out = sc.add(per * 8), r_ns = sc.add(noise ? per * 8 : 0), r_st = sc.add(status ? per * 4 : 0);
-  const size_t ww = plain_ww(pl), r_wd = sc.add(per * ww * 8);
+               r_rep = rep.reserve(sc, per);
   return host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
     i64* d_sk = sc.at<i64>(r_sk);
-    u64 *d_c1 = sc.at(r_c1), *d_c2 = sc.at(r_c2), *d_nz = sc.at(r_nz), *d_out = sc.at(r_out);
+    u64 *d_c1 = sc.at(r_c1), *d_c2 = sc.at(r_c2), *d_nz = sc.at(r_nz);
+    const Report dev = rep.in(sc, r_rep);
     ws_mark_secret(w, d_sk, k * l * 8);
     PVW_HIP(hipMemcpyAsync(d_sk, sk, k * l * 8, hipMemcpyHostToDevice, w->stream));
     for (size_t d0 = 0; d0 < D; d0 += per) {
@@ -2649,12 +2743,8 @@ static int32_t decrypt_batch_staged(pvw_ctx* c, const int64_t* sk, const uint64_
         PVW_HIP(launch_ntt(d_c1, cnt * k, false, c->dt, c->L, c->l, w->stream));
         PVW_HIP(launch_ntt(d_c2, cnt, false, c->dt, c->L, c->l, w->stream));
       }
-      PVW_TRY(decrypt_batch_enqueue(c, w, w->stream, d_sk, nullptr, d_c1, d_c2, cnt, d_nz, d_out, noise ? sc.at(r_ns) : nullptr,
-                                    status ? sc.at<u32>(r_st) : nullptr, PlainAt(pl, sc.at(r_wd), 0).ptr()));
-      PVW_HIP(hipMemcpyAsync(out_u64 + d0, d_out, cnt * 8, hipMemcpyDeviceToHost, w->stream));
-      if (noise) PVW_HIP(hipMemcpyAsync(noise + d0, sc.at(r_ns), cnt * 8, hipMemcpyDeviceToHost, w->stream));
-      if (status) PVW_HIP(hipMemcpyAsync(status + d0, sc.at(r_st), cnt * 4, hipMemcpyDeviceToHost, w->stream));
-      if (ww) PVW_HIP(hipMemcpyAsync(pl->wide + d0 * ww, sc.at(r_wd), cnt * ww * 8, hipMemcpyDeviceToHost, w->stream));
+      PVW_TRY(decrypt_batch_enqueue(c, w, w->stream, key_coeffs(c, d_sk), d_c1, d_c2, cnt, d_nz, dev));
+      PVW_TRY(dev.copy_to(rep.at(d0), cnt, hipMemcpyDeviceToHost, w->stream));
       if (noisy_out) PVW_HIP(hipMemcpyAsync(noisy_out + d0 * P, d_nz, cnt * P * 8, hipMemcpyDeviceToHost, w->stream));
     }
     return PVW_OK;
@@ -2671,62 +2761,39 @@ int32_t pvw_decrypt_batch_checked(pvw_ctx* c, const int64_t* sk, const uint64_t*
 int32_t pvw_decrypt_batch_plain(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D, uint32_t in_repr,
                                 uint64_t* out_u64, uint64_t* noise, uint32_t* status, uint64_t plain_modulus, uint32_t wide_words,
                                 uint64_t* wide) {
-  PlainArgs pa;
-  PVW_TRY(plain_args(c, plain_modulus, wide_words, wide, &pa));
-  return decrypt_batch_staged(c, sk, c1s, c2col, D, in_repr, out_u64, nullptr, noise, status, &pa);
+  return decrypt_batch_staged(c, sk, c1s, c2col, D, in_repr, out_u64, nullptr, noise, status, plain_modulus, wide_words, wide);
 }
 
-// A secret key kept on the device in the form the inner products read (NTT(sk[j]) in the ciphertext layout,
-// secret_key.rs:98-112): decrypt calls that take one skip the transform of the key and the wipe behind it.  The reference's
-// SecretKey lives as long as its owner does and is ZeroizeOnDrop (secret_key.rs:20-30); so does this: pvw_sk_free clears it.
-struct pvw_sk {
-  pvw_ctx* ctx;
-  u64* shat;       // [k][L][l]
-  size_t bytes;
-};
-int32_t pvw_decrypt_batch_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col,
-                                 size_t D, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, void* stream) {
-  if (!c || !d_sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  return decrypt_batch_core(c, d_sk, nullptr, d_c1s, d_c2col, D, in_repr, d_noisy, d_out, stream);
-}
-int32_t pvw_decrypt_batch_device_sk(pvw_ctx* c, const pvw_sk* key, const uint64_t* d_c1s, const uint64_t* d_c2col,
-                                    size_t D, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, void* stream) {
-  if (!c || !key || !key->shat) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  if (key->ctx != c) return fail(PVW_ERR_INVALID_PARAMETERS, "the key was loaded for another context");
-  return decrypt_batch_core(c, nullptr, key->shat, d_c1s, d_c2col, D, in_repr, d_noisy, d_out, stream);
-}
-// checked forms: the same words in d_out, plus d_noise / d_status [D] (either may be NULL)
-int32_t pvw_decrypt_batch_checked_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
-                                         uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status,
-                                         void* stream) {
-  if (!c || !d_sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  return decrypt_batch_core(c, d_sk, nullptr, d_c1s, d_c2col, D, in_repr, d_noisy, d_out, stream, d_noise, d_status);
-}
-int32_t pvw_decrypt_batch_device_sk_checked(pvw_ctx* c, const pvw_sk* key, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
-                                            uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise,
-                                            uint32_t* d_status, void* stream) {
-  if (!c || !key || !key->shat) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  if (key->ctx != c) return fail(PVW_ERR_INVALID_PARAMETERS, "the key was loaded for another context");
-  return decrypt_batch_core(c, nullptr, key->shat, d_c1s, d_c2col, D, in_repr, d_noisy, d_out, stream, d_noise, d_status);
-}
-// plain forms
 int32_t pvw_decrypt_batch_plain_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
                                        uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status,
                                        uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream) {
-  if (!c || !d_sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PlainArgs pa;
-  PVW_TRY(plain_args(c, plain_modulus, wide_words, d_wide, &pa));
-  return decrypt_batch_core(c, d_sk, nullptr, d_c1s, d_c2col, D, in_repr, d_noisy, d_out, stream, d_noise, d_status, &pa);
+  return decrypt_batch_device(c, key_coeffs(c, d_sk), d_c1s, d_c2col, D, in_repr, d_noisy, d_out, d_noise, d_status, plain_modulus, wide_words, d_wide,
+                              stream);
 }
 int32_t pvw_decrypt_batch_device_sk_plain(pvw_ctx* c, const pvw_sk* key, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
                                           uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise,
                                           uint32_t* d_status, uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide,
                                           void* stream) {
-  if (!c || !key || !key->shat) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  if (key->ctx != c) return fail(PVW_ERR_INVALID_PARAMETERS, "the key was loaded for another context");
-  PlainArgs pa;
-  PVW_TRY(plain_args(c, plain_modulus, wide_words, d_wide, &pa));
-  return decrypt_batch_core(c, nullptr, key->shat, d_c1s, d_c2col, D, in_repr, d_noisy, d_out, stream, d_noise, d_status, &pa);
+  return decrypt_batch_device(c, key_resident(c, key), d_c1s, d_c2col, D, in_repr, d_noisy, d_out, d_noise, d_status, plain_modulus, wide_words, d_wide,
+                              stream);
+}
+int32_t pvw_decrypt_batch_checked_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
+                                         uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status,
+                                         void* stream) {
+  return decrypt_batch_device(c, key_coeffs(c, d_sk), d_c1s, d_c2col, D, in_repr, d_noisy, d_out, d_noise, d_status, 0, 0, nullptr, stream);
+}
+int32_t pvw_decrypt_batch_device_sk_checked(pvw_ctx* c, const pvw_sk* key, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
+                                            uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise,
+                                            uint32_t* d_status, void* stream) {
+  return decrypt_batch_device(c, key_resident(c, key), d_c1s, d_c2col, D, in_repr, d_noisy, d_out, d_noise, d_status, 0, 0, nullptr, stream);
+}
+int32_t pvw_decrypt_batch_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col,
+                                 size_t D, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, void* stream) {
+  return decrypt_batch_device(c, key_coeffs(c, d_sk), d_c1s, d_c2col, D, in_repr, d_noisy, d_out, nullptr, nullptr, 0, 0, nullptr, stream);
+}
+int32_t pvw_decrypt_batch_device_sk(pvw_ctx* c, const pvw_sk* key, const uint64_t* d_c1s, const uint64_t* d_c2col,
+                                    size_t D, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, void* stream) {
+  return decrypt_batch_device(c, key_resident(c, key), d_c1s, d_c2col, D, in_repr, d_noisy, d_out, nullptr, nullptr, 0, 0, nullptr, stream);
 }
 int32_t pvw_sk_load(pvw_ctx* c, const int64_t* sk, pvw_sk** out) {
   if (!c || !sk || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
@@ -2788,123 +2855,137 @@ int32_t pvw_sk_free(pvw_sk* key) {
 static int32_t decrypt_all_checks(pvw_ctx* c, u32 lo, u32 hi, const void* sk, const void* c1s, const void* c2s, size_t D,
                                   uint32_t in_repr, const void* out) {
   if (!c || !sk || !c1s || !c2s || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");          // decryption.rs:286-290
+  PVW_TRY(check_dealers(D));
   PVW_TRY(check_party_range(c, lo, hi));
   if (lo == hi) return fail(PVW_ERR_INVALID_PARAMETERS, "empty party range");
   PVW_TRY(check_repr(in_repr));
   return PVW_OK;
 }
-// host: sk / c1s / c2s / out are host buffers (staged in bounded pieces); otherwise device pointers on `s`.
-// The caller's buffers are only read: POWER-basis input is transformed in scratch.
-// noise / status (either may be NULL, same side as out): the checked decode's report, [P][D] like out
-static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, u32 hi, const int64_t* sk, const u64* c1s,
-                               const u64* c2s, size_t D, uint32_t in_repr, u64* out, bool host, u64* noise = nullptr,
-                               u32* status = nullptr, size_t* need_only = nullptr, const PlainArgs* pl = nullptr) {
-  const size_t ww = plain_ww(pl);                        // plain decode: wide [P][D][ww] like out, same side
+// Which side a call for NP parties and D dealers takes, its chunk sizes and its scratch, from the shape of the call alone
+// (no workspace, stream or pointer): what the call takes is known before it runs (pvw_prepare, sum_capture_check).
+// host: host buffers, staged in bounded pieces; stage: c1 / c2 are copied (host, or POWER-basis input: the caller's buffers
+// are only read); noise / status / ww: the report asked for.  The staged report follows r_nz directly.
+struct AllLayout {
+  bool use_gemm = false, direct = false;
+  size_t Dc = 0;                      // party by party: dealers per chunk
+  size_t Dg = 0, nbg = 0, Pc = 0;     // matrix cores: dealers per group, their batches of 16, parties per chunk
+  Scratch sc;
+  size_t r_sk = 0, r_c1 = 0, r_c2 = 0, r_nz = 0, r_rep = 0, r_yd = 0, r_sy = 0, r_rows = 0, r_xm = 0, r_tmp = 0;
+};
+static AllLayout decrypt_all_layout(const pvw_ctx* c, size_t NP, size_t D, bool host, bool stage, bool noise, bool status, size_t ww) {
   const u32 k = c->k, l = c->l, L = c->L;
-  const size_t P = c->poly(), NP = (size_t)hi - lo;
-  const size_t ctw = (size_t)k * P;                      // words of one dealer's c1
-  const size_t c2d = (size_t)c->n * P;                   // words between dealers in c2s
-  const bool power = in_repr == PVW_REPR_POWER, stage = host || power;
-  const hipMemcpyKind kin = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  const hipMemcpyKind kout = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  const size_t P = c->poly(), ctw = (size_t)k * P;       // ctw: words of one dealer's c1
   const long min_parties = PVW_ENV_INT("PVW_DECRYPT_ALL_MIN_PARTIES", PVW_DECRYPT_ALL_MIN_PARTIES);   // tuning build only
-  const bool use_gemm = min_parties > 0 && NP >= (size_t)min_parties;
-  if (!use_gemm) {
-    // ---- party by party: dealers in chunks of <= 1 GiB of c1, each chunk's c1 shared by every party
-    size_t Dc = ((size_t)1 << 30) / (ctw * 8);
-    if (Dc == 0) Dc = 1;
-    if (Dc > D) Dc = D;
-    Scratch sc;
-    const size_t r_sk = sc.add(host ? NP * k * l * 8 : 0), r_c1 = sc.add(stage ? Dc * ctw * 8 : 0), r_c2 = sc.add(Dc * P * 8),
-                 r_nz = sc.add(Dc * P * 8), r_out = sc.add(host ? Dc * 8 : 0), r_ns = sc.add(host && noise ? Dc * 8 : 0),
-                 r_st = sc.add(host && status ? Dc * 4 : 0), r_wd = sc.add(host ? Dc * ww * 8 : 0);
-    if (need_only) { *need_only = sc.total; return PVW_OK; }   // the scratch this call would take, nothing else
-    PVW_TRY(sc.take(w));
-    i64* d_sk = sc.at<i64>(r_sk);
-    u64 *d_c1 = sc.at(r_c1), *d_c2 = sc.at(r_c2), *d_nz = sc.at(r_nz), *d_out = sc.at(r_out), *d_ns = sc.at(r_ns);
-    u32* d_st = sc.at<u32>(r_st);
-    u64* d_wd = sc.at(r_wd);
-    // key material: the uploaded coefficients, NTT(sk) (w->rhat), the noisy polynomials (m g-hat + noise), the decoded values
-    // and their reports, wide words included
-    sc.secret(w, r_sk, r_sk);
-    ws_mark_secret(w, w->rhat, (size_t)k * P * 8);
-    sc.secret(w, r_nz, r_wd);
-    if (host) PVW_HIP(hipMemcpyAsync(d_sk, sk, NP * k * l * 8, hipMemcpyHostToDevice, s));
-    const i64* skd = host ? d_sk : sk;
-    for (size_t d0 = 0; d0 < D; d0 += Dc) {
-      const size_t cnt = (D - d0) < Dc ? (D - d0) : Dc;
-      const u64* c1 = c1s + d0 * ctw;
-      if (stage) {
-        PVW_HIP(hipMemcpyAsync(d_c1, c1, cnt * ctw * 8, kin, s));
-        if (power) { ProfScope ps(c, "ntt", s); PVW_HIP(launch_ntt(d_c1, cnt * k, false, c->dt, L, l, s)); }
-        c1 = d_c1;
-      }
-      for (size_t p = 0; p < NP; ++p) {
-        // party lo + p's column of c2: one row of each dealer, n rows apart
-        PVW_HIP(hipMemcpy2DAsync(d_c2, P * 8, c2s + d0 * c2d + (lo + p) * P, c2d * 8, P * 8, cnt, kin, s));
-        if (power) { ProfScope ps(c, "ntt", s); PVW_HIP(launch_ntt(d_c2, cnt, false, c->dt, L, l, s)); }
-        {
-          ProfScope ps(c, "prep", s);
-          PVW_HIP(launch_prep(skd + p * k * l, nullptr, w->rhat, P, l, k, true, c->dt, L, l, s));   // secret_key.rs:98-112
-        }
-        bool ntt_domain = false;
-        const int32_t rm = decrypt_mac_only(c, w, c1, d_c2, cnt, d_nz, s, &ntt_domain);          // decryption.rs:257-274
-        if (w->dpart && (p == 0 || rm != PVW_OK)) ws_mark_secret(w, w->dpart, w->dpart_bytes);   // range sums of s-hat c1
-        PVW_TRY(rm);
-        u64* o = out + p * D + d0;
-        u64* on = noise ? noise + p * D + d0 : nullptr;
-        u32* os = status ? status + p * D + d0 : nullptr;
-        PVW_TRY(decode_tail(c, d_nz, cnt, ntt_domain, false, s, host ? d_out : o, on && host ? d_ns : on, os && host ? d_st : os,
-                            nullptr, 0, nullptr, (host ? PlainAt(pl, d_wd, 0) : PlainAt(pl, p * D + d0)).ptr()));
-        if (host && ww) PVW_HIP(hipMemcpyAsync(pl->wide + (p * D + d0) * ww, d_wd, cnt * ww * 8, hipMemcpyDeviceToHost, s));
-        if (host) PVW_HIP(hipMemcpyAsync(o, d_out, cnt * 8, hipMemcpyDeviceToHost, s));
-        if (host && on) PVW_HIP(hipMemcpyAsync(on, d_ns, cnt * 8, hipMemcpyDeviceToHost, s));
-        if (host && os) PVW_HIP(hipMemcpyAsync(os, d_st, cnt * 4, hipMemcpyDeviceToHost, s));
-      }
-    }
-    return PVW_OK;
+  AllLayout a;
+  Scratch& sc = a.sc;
+  a.use_gemm = min_parties > 0 && NP >= (size_t)min_parties;
+  if (!a.use_gemm) {
+    // dealers in chunks of <= 1 GiB of c1, each chunk's c1 shared by every party
+    const size_t Dc = a.Dc = chunk_1gib(ctw * 8, D);
+    a.r_sk = sc.add(host ? NP * k * l * 8 : 0), a.r_c1 = sc.add(stage ? Dc * ctw * 8 : 0), a.r_c2 = sc.add(Dc * P * 8);
+    a.r_nz = sc.add(Dc * P * 8), a.r_rep = Report::reserve(sc, host ? Dc : 0, noise, status, ww);
+    return a;
   }
-  // ---- matrix cores.  Dealers in groups of up to 128 (one gemm_digits launch each; c1 of the group reduced and digitised
-  // once per party chunk, <= 1 GiB with its digit tiles), parties in chunks that keep the rest below 3 GiB.
+  // Dealers in groups of up to 128 (one gemm_digits launch each; c1 of the group reduced and digitised once per party chunk,
+  // <= 1 GiB with its digit tiles), parties in chunks that keep the rest below 3 GiB.
   size_t Dg = D < 128 ? D : 128;
   while (Dg > 1 && Dg * ctw * 72 > ((size_t)1 << 30)) Dg /= 2;     // c1 copy (8 bytes a word) + digit tiles (64)
   const size_t nbg = (Dg + 15) / 16;
-  const bool direct = l <= 32;                                     // s-hat straight into the tiled operand (shat_mftile)
-  const size_t per_party = ctw * 8 * (direct ? 1 : 2) + nbg * 16 * P * 8 + Dg * P * 8 * (stage ? 2 : 1) + Dg * 8 + (host ? (size_t)k * l * 8 : 0);
+  a.direct = l <= 32;                                              // s-hat straight into the tiled operand (shat_mftile)
+  const size_t per_party = ctw * 8 * (a.direct ? 1 : 2) + nbg * 16 * P * 8 + Dg * P * 8 * (stage ? 2 : 1) + Dg * 8 + (host ? (size_t)k * l * 8 : 0);
   size_t Pc = ((size_t)3 << 30) / per_party;
   if (Pc >= NP) Pc = NP;
   else if (Pc >= PVW_GEMM_ROWS_PER_WG) Pc -= Pc % PVW_GEMM_ROWS_PER_WG;   // whole workgroups of GEMM rows
   if (Pc == 0) Pc = 1;
-  Scratch sc;
-  const size_t r_c1 = sc.add(Dg * ctw * 8), r_yd = sc.add(yd_bytes((u32)(16 * nbg), k, L, l)), r_sy = sc.add(sy_bytes((u32)(16 * nbg), L, l));
+  a.Dg = Dg, a.nbg = nbg, a.Pc = Pc;
+  a.r_c1 = sc.add(Dg * ctw * 8), a.r_yd = sc.add(yd_bytes((u32)(16 * nbg), k, L, l)), a.r_sy = sc.add(sy_bytes((u32)(16 * nbg), L, l));
   // from here on: everything derived from the keys
-  const size_t r_sk = sc.add(host ? Pc * k * l * 8 : 0), r_rows = sc.add(direct ? 0 : Pc * ctw * 8);
-  const size_t r_xm = sc.add(xm_words((u32)Pc, k, L, l) * 8), r_tmp = sc.add(nbg * gemm_tmp_words((u32)Pc, L, l) * 8);
-  const size_t r_c2 = sc.add(stage ? Dg * Pc * P * 8 : 0), r_nz = sc.add(Dg * Pc * P * 8), r_out = sc.add(Dg * Pc * 8);
-  const size_t r_ns = sc.add(noise ? Dg * Pc * 8 : 0), r_st = sc.add(status ? Dg * Pc * 4 : 0), r_wd = sc.add(Dg * Pc * ww * 8);
-  if (need_only) { *need_only = sc.total; return PVW_OK; }
-  PVW_TRY(sc.take(w));
-  u64 *d_c1 = sc.at(r_c1), *d_rows = sc.at(r_rows), *d_xm = sc.at(r_xm), *d_tmp = sc.at(r_tmp), *d_c2 = sc.at(r_c2), *d_nz = sc.at(r_nz),
-      *d_out = sc.at(r_out), *d_ns = sc.at(r_ns);
-  signed char* d_yd = sc.at<signed char>(r_yd);
-  int* d_sy = sc.at<int>(r_sy);
-  i64* d_sk = sc.at<i64>(r_sk);
-  u32* d_st = sc.at<u32>(r_st);
-  u64* d_wd = sc.at(r_wd);
+  a.r_sk = sc.add(host ? Pc * k * l * 8 : 0), a.r_rows = sc.add(a.direct ? 0 : Pc * ctw * 8);
+  a.r_xm = sc.add(xm_words((u32)Pc, k, L, l) * 8), a.r_tmp = sc.add(nbg * gemm_tmp_words((u32)Pc, L, l) * 8);
+  a.r_c2 = sc.add(stage ? Dg * Pc * P * 8 : 0), a.r_nz = sc.add(Dg * Pc * P * 8);
+  a.r_rep = Report::reserve(sc, Dg * Pc, noise, status, ww);
+  return a;
+}
+// The shape of one call, as both sides take it.  host: sk / c1s / c2s / rep are host buffers; otherwise device pointers on `s`.
+// rep: [P][D], on the same side.
+struct AllCall {
+  u32 lo;
+  size_t NP, D;
+  const int64_t* sk;
+  const u64 *c1s, *c2s;
+  bool host, power;
+  Report rep;
+};
+// ---- party by party
+static int32_t decrypt_all_by_party(pvw_ctx* c, Workspace* w, hipStream_t s, const AllLayout& a, const AllCall& q) {
+  const u32 k = c->k, l = c->l, L = c->L;
+  const size_t P = c->poly(), ctw = (size_t)k * P, c2d = (size_t)c->n * P, D = q.D;   // c2d: words between dealers in c2s
+  const hipMemcpyKind kin = q.host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  const Scratch& sc = a.sc;
+  i64* d_sk = sc.at<i64>(a.r_sk);
+  u64 *d_c1 = sc.at(a.r_c1), *d_c2 = sc.at(a.r_c2), *d_nz = sc.at(a.r_nz);
+  const Report dev = q.rep.in(sc, a.r_rep);
+  // key material: the uploaded coefficients, NTT(sk) (w->rhat), the noisy polynomials (m g-hat + noise), the decoded values
+  // and their reports, wide words included
+  sc.secret(w, a.r_sk, a.r_sk);
+  ws_mark_secret(w, w->rhat, (size_t)k * P * 8);
+  sc.secret(w, a.r_nz, a.r_rep + 3);
+  if (q.host) PVW_HIP(hipMemcpyAsync(d_sk, q.sk, q.NP * k * l * 8, hipMemcpyHostToDevice, s));
+  const i64* skd = q.host ? d_sk : q.sk;
+  for (size_t d0 = 0; d0 < D; d0 += a.Dc) {
+    const size_t cnt = (D - d0) < a.Dc ? (D - d0) : a.Dc;
+    const u64* c1 = q.c1s + d0 * ctw;
+    if (q.host || q.power) {
+      PVW_HIP(hipMemcpyAsync(d_c1, c1, cnt * ctw * 8, kin, s));
+      if (q.power) { ProfScope ps(c, "ntt", s); PVW_HIP(launch_ntt(d_c1, cnt * k, false, c->dt, L, l, s)); }
+      c1 = d_c1;
+    }
+    for (size_t p = 0; p < q.NP; ++p) {
+      // party lo + p's column of c2: one row of each dealer, n rows apart
+      PVW_HIP(hipMemcpy2DAsync(d_c2, P * 8, q.c2s + d0 * c2d + (q.lo + p) * P, c2d * 8, P * 8, cnt, kin, s));
+      if (q.power) { ProfScope ps(c, "ntt", s); PVW_HIP(launch_ntt(d_c2, cnt, false, c->dt, L, l, s)); }
+      {
+        ProfScope ps(c, "prep", s);
+        PVW_HIP(launch_prep(skd + p * k * l, nullptr, w->rhat, P, l, k, true, c->dt, L, l, s));   // secret_key.rs:98-112
+      }
+      bool ntt_domain = false;
+      const int32_t rm = decrypt_mac_only(c, w, c1, d_c2, cnt, d_nz, s, &ntt_domain);          // decryption.rs:257-274
+      if (w->dpart && (p == 0 || rm != PVW_OK)) ws_mark_secret(w, w->dpart, w->dpart_bytes);   // range sums of s-hat c1
+      PVW_TRY(rm);
+      const Report to = q.rep.at(p * D + d0);
+      PVW_TRY(decode_tail(c, d_nz, cnt, ntt_domain, false, s, q.host ? dev : to));
+      if (q.host) PVW_TRY(dev.copy_to(to, cnt, hipMemcpyDeviceToHost, s, true));
+    }
+  }
+  return PVW_OK;
+}
+// ---- matrix cores
+static int32_t decrypt_all_gemm(pvw_ctx* c, Workspace* w, hipStream_t s, const AllLayout& a, const AllCall& q) {
+  const u32 k = c->k, l = c->l, L = c->L;
+  const size_t P = c->poly(), ctw = (size_t)k * P, c2d = (size_t)c->n * P, D = q.D;
+  const bool stage = q.host || q.power;
+  const hipMemcpyKind kin = q.host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  const hipMemcpyKind kout = q.host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  const Scratch& sc = a.sc;
+  u64 *d_c1 = sc.at(a.r_c1), *d_rows = sc.at(a.r_rows), *d_xm = sc.at(a.r_xm), *d_tmp = sc.at(a.r_tmp), *d_c2 = sc.at(a.r_c2),
+      *d_nz = sc.at(a.r_nz);
+  signed char* d_yd = sc.at<signed char>(a.r_yd);
+  int* d_sy = sc.at<int>(a.r_sy);
+  i64* d_sk = sc.at<i64>(a.r_sk);
+  const Report dev = q.rep.in(sc, a.r_rep);
   // the uploaded coefficients, the tiled s-hat (and its rows, l = 64), the GEMM intermediate (s-hat c1), the noisy
   // polynomials, the decoded values and their reports (wide words included); the staged c2 rows share the region
-  sc.secret(w, r_sk, r_wd);
-  for (size_t p0 = 0; p0 < NP; p0 += Pc) {
-    const u32 pc = (u32)((NP - p0) < Pc ? (NP - p0) : Pc);
-    const i64* skp = sk + p0 * k * l;
-    if (host) {
+  sc.secret(w, a.r_sk, a.r_rep + 3);
+  for (size_t p0 = 0; p0 < q.NP; p0 += a.Pc) {
+    const u32 pc = (u32)((q.NP - p0) < a.Pc ? (q.NP - p0) : a.Pc);
+    const i64* skp = q.sk + p0 * k * l;
+    if (q.host) {
       PVW_HIP(hipMemcpyAsync(d_sk, skp, (size_t)pc * k * l * 8, hipMemcpyHostToDevice, s));
       skp = d_sk;
     }
     {
       ProfScope ps(c, "prep", s);
-      if (direct) {
+      if (a.direct) {
         PVW_HIP(launch_shat_mftile(skp, d_xm, pc, k, L, l, c->dt, s));                        // secret_key.rs:98-112
       } else {
         PVW_HIP(launch_prep(skp, nullptr, d_rows, P, l, pc * k, true, c->dt, L, l, s));
@@ -2912,25 +2993,25 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
         PVW_HIP(launch_mftile(d_rows, false, d_xm, pc, k, L, l, s));
       }
     }
-    for (size_t d0 = 0; d0 < D; d0 += Dg) {
-      const u32 dg = (u32)((D - d0) < Dg ? (D - d0) : Dg);
+    for (size_t d0 = 0; d0 < D; d0 += a.Dg) {
+      const u32 dg = (u32)((D - d0) < a.Dg ? (D - d0) : a.Dg);
       {
         ProfScope ps(c, "digits", s);
-        const u64* c1 = c1s + d0 * ctw;
+        const u64* c1 = q.c1s + d0 * ctw;
         if (stage) {
           PVW_HIP(hipMemcpyAsync(d_c1, c1, (size_t)dg * ctw * 8, kin, s));
-          if (power) PVW_HIP(launch_ntt(d_c1, (size_t)dg * k, false, c->dt, L, l, s));
+          if (q.power) PVW_HIP(launch_ntt(d_c1, (size_t)dg * k, false, c->dt, L, l, s));
           c1 = d_c1;
         }
         PVW_HIP(launch_reduce_words(c1, d_c1, (size_t)dg * ctw, c->dt, L, l, s));
         // vector d = dealer: element j at d * k P + j * P + limb * l + slot
         PVW_HIP(launch_vec_digits(d_c1, ctw, d_yd, d_sy, dg, k, L, l, c->dt, s, l, P));
       }
-      const u64* c2p = c2s + d0 * c2d + (lo + p0) * P;
+      const u64* c2p = q.c2s + d0 * c2d + (q.lo + p0) * P;
       size_t c2v = c2d;
       if (stage) {                                                 // rows [lo + p0, lo + p0 + pc) of each dealer only
         PVW_HIP(hipMemcpy2DAsync(d_c2, (size_t)pc * P * 8, c2p, c2d * 8, (size_t)pc * P * 8, dg, kin, s));
-        if (power) { ProfScope ps(c, "ntt", s); PVW_HIP(launch_ntt(d_c2, (size_t)dg * pc, false, c->dt, L, l, s)); }
+        if (q.power) { ProfScope ps(c, "ntt", s); PVW_HIP(launch_ntt(d_c2, (size_t)dg * pc, false, c->dt, L, l, s)); }
         c2p = d_c2;
         c2v = (size_t)pc * P;
       }
@@ -2943,64 +3024,51 @@ static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, 
         ProfScope ps(c, "finish", s);
         PVW_HIP(launch_finish_decrypt(ga, d_sy, c->dt, L, l, dg, c2p, c2v, P, d_nz, s));     // decryption.rs:257-274
       }
-      PVW_TRY(decode_tail(c, d_nz, (size_t)pc * dg, true, false, s, d_out, noise ? d_ns : nullptr, status ? d_st : nullptr, nullptr, 0,
-                          nullptr, PlainAt(pl, d_wd, 0).ptr()));
+      PVW_TRY(decode_tail(c, d_nz, (size_t)pc * dg, true, false, s, dev));
       // results[recipient][dealer] (examples/pvw.rs:157-170): the chunk's [pc][dg] block into out[p0..][d0..]
-      PVW_HIP(hipMemcpy2DAsync(out + p0 * D + d0, D * 8, d_out, (size_t)dg * 8, (size_t)dg * 8, pc, kout, s));
-      if (noise) PVW_HIP(hipMemcpy2DAsync(noise + p0 * D + d0, D * 8, d_ns, (size_t)dg * 8, (size_t)dg * 8, pc, kout, s));
-      if (status) PVW_HIP(hipMemcpy2DAsync(status + p0 * D + d0, D * 4, d_st, (size_t)dg * 4, (size_t)dg * 4, pc, kout, s));
-      if (ww) PVW_HIP(hipMemcpy2DAsync(pl->wide + (p0 * D + d0) * ww, D * ww * 8, d_wd, (size_t)dg * ww * 8, (size_t)dg * ww * 8, pc, kout, s));
+      PVW_TRY(dev.copy_block_to(q.rep.at(p0 * D + d0), pc, dg, D, kout, s));
     }
   }
   return PVW_OK;
 }
+static int32_t decrypt_all_run(pvw_ctx* c, Workspace* w, hipStream_t s, const AllCall& q) {
+  AllLayout a = decrypt_all_layout(c, q.NP, q.D, q.host, q.host || q.power, q.rep.noise, q.rep.status, q.rep.ww);
+  PVW_TRY(a.sc.take(w));
+  return a.use_gemm ? decrypt_all_gemm(c, w, s, a, q) : decrypt_all_by_party(c, w, s, a, q);
+}
 // host buffers in and out
-static int32_t decrypt_all_staged(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
-                                  size_t D, uint32_t in_repr, uint64_t* out, uint64_t* noise, uint32_t* status, const PlainArgs* pl) {
-  PVW_TRY(decrypt_all_checks(c, lo, hi, sk, c1s, c2s, D, in_repr, out));
-  PVW_TRY(ensure_device(c));
-  return host_call(c, [&](Workspace* w) {
-    return decrypt_all_run(c, w, w->stream, lo, hi, sk, c1s, c2s, D, in_repr, out, true, noise, status, nullptr, PlainAt(pl, 0).ptr());
-  });
-}
-int32_t pvw_decrypt_all_checked(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
-                                size_t D, uint32_t in_repr, uint64_t* out, uint64_t* noise, uint32_t* status) {
-  return decrypt_all_staged(c, lo, hi, sk, c1s, c2s, D, in_repr, out, noise, status, nullptr);
-}
 int32_t pvw_decrypt_all_plain(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
                               size_t D, uint32_t in_repr, uint64_t* out, uint64_t* noise, uint32_t* status, uint64_t plain_modulus,
                               uint32_t wide_words, uint64_t* wide) {
-  PlainArgs pa;
-  PVW_TRY(plain_args(c, plain_modulus, wide_words, wide, &pa));
-  return decrypt_all_staged(c, lo, hi, sk, c1s, c2s, D, in_repr, out, noise, status, &pa);
+  Report rep;
+  PVW_TRY(report_args(c, out, noise, status, plain_modulus, wide_words, wide, &rep));
+  PVW_TRY(decrypt_all_checks(c, lo, hi, sk, c1s, c2s, D, in_repr, out));
+  PVW_TRY(ensure_device(c));
+  const AllCall q{lo, (size_t)hi - lo, D, sk, c1s, c2s, true, in_repr == PVW_REPR_POWER, rep};
+  return host_call(c, [&](Workspace* w) { return decrypt_all_run(c, w, w->stream, q); });
+}
+int32_t pvw_decrypt_all_checked(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
+                                size_t D, uint32_t in_repr, uint64_t* out, uint64_t* noise, uint32_t* status) {
+  return pvw_decrypt_all_plain(c, lo, hi, sk, c1s, c2s, D, in_repr, out, noise, status, 0, 0, nullptr);
 }
 int32_t pvw_decrypt_all(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
                         size_t D, uint32_t in_repr, uint64_t* out) {
   return pvw_decrypt_all_checked(c, lo, hi, sk, c1s, c2s, D, in_repr, out, nullptr, nullptr);
 }
 // device pointers on the caller's stream
-static int32_t decrypt_all_device_core(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
-                                       const uint64_t* d_c2s, size_t D, uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise,
-                                       uint32_t* d_status, void* stream, const PlainArgs* pl) {
+int32_t pvw_decrypt_all_plain_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
+                                     const uint64_t* d_c2s, size_t D, uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise,
+                                     uint32_t* d_status, uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream) {
+  Report rep;
+  PVW_TRY(report_args(c, d_out, d_noise, d_status, plain_modulus, wide_words, d_wide, &rep));
   PVW_TRY(decrypt_all_checks(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out));
-  PVW_TRY(ensure_device(c));
-  hipStream_t s;
-  Workspace* w;
-  PVW_TRY(device_ws(c, stream, &s, &w));
-  return device_end(w, s, decrypt_all_run(c, w, s, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out, false, d_noise, d_status, nullptr,
-                                          PlainAt(pl, 0).ptr()));
+  const AllCall q{lo, (size_t)hi - lo, D, d_sk, d_c1s, d_c2s, false, in_repr == PVW_REPR_POWER, rep};
+  return device_call(c, stream, [&](Workspace* w, hipStream_t s) { return decrypt_all_run(c, w, s, q); });
 }
 int32_t pvw_decrypt_all_checked_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
                                        const uint64_t* d_c2s, size_t D, uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise,
                                        uint32_t* d_status, void* stream) {
-  return decrypt_all_device_core(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out, d_noise, d_status, stream, nullptr);
-}
-int32_t pvw_decrypt_all_plain_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
-                                     const uint64_t* d_c2s, size_t D, uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise,
-                                     uint32_t* d_status, uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream) {
-  PlainArgs pa;
-  PVW_TRY(plain_args(c, plain_modulus, wide_words, d_wide, &pa));
-  return decrypt_all_device_core(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out, d_noise, d_status, stream, &pa);
+  return pvw_decrypt_all_plain_device(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out, d_noise, d_status, 0, 0, nullptr, stream);
 }
 int32_t pvw_decrypt_all_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
                                const uint64_t* d_c2s, size_t D, uint32_t in_repr, uint64_t* d_out, void* stream) {
@@ -3013,8 +3081,8 @@ int32_t pvw_decrypt_all_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64
 // decrypts is one streaming pass over the ciphertexts (launch_ct_sum) and ONE decrypt.
 // Workspace::sumbuf, fixed by the context's geometry (byte offsets): the slice sums of the split kernel form | the summed c1
 // [k] | the summed c2 rows [n] (row r at its global position; directly behind c1, so c1 and row 0 are one run of k + 1
-// polynomials) | the noisy polynomial of a single aggregate decrypt | out [n], noise [n], status [n], wide [n][W] of the host-buffer
-// calls.
+// polynomials) | the noisy polynomial of a single aggregate decrypt | io: the staged report of the host-buffer calls
+// (Report::packed_at, sized for n parties and the wide words of a plain decode at wide_words = W).
 struct SumLayout { size_t c1, c2, noisy, io, total; };
 static SumLayout sum_layout(const pvw_ctx* c) {
   const size_t P8 = c->poly() * 8;
@@ -3023,24 +3091,20 @@ static SumLayout sum_layout(const pvw_ctx* c) {
   o.c2 = o.c1 + (size_t)c->k * P8;
   o.noisy = o.c2 + (size_t)c->n * P8;
   o.io = o.noisy + ((P8 + 255) & ~(size_t)255);
-  // per party: out, noise (8 bytes each), status (4, padded to 8), and the wide words of a plain decode at wide_words = W
-  o.total = o.io + (((size_t)c->n * (24 + 8 * c->Q.mag.size()) + 255) & ~(size_t)255);
+  o.total = o.io + ((Report::packed_bytes(c->n, c->Q.mag.size()) + 255) & ~(size_t)255);
   return o;
 }
+// the parts of a workspace's sum buffer; a call's staged report: Report::packed_at(io, parties)
+struct SumView { u64 *c1, *c2, *noisy, *io; };
+static SumView sum_view(const pvw_ctx* c, const Workspace* w) {
+  const SumLayout sl = sum_layout(c);
+  char* b = (char*)w->sumbuf;
+  return SumView{(u64*)(b + sl.c1), (u64*)(b + sl.c2), (u64*)(b + sl.noisy), (u64*)(b + sl.io)};
+}
 static bool sum_buffer_ready(const pvw_ctx* c, const Workspace* w) { return w && w->sumbuf_bytes >= sum_layout(c).total; }
+// may hold the noisy polynomial and the results of the last aggregate decrypt: cleared before it is replaced
 static int32_t sum_buffer(pvw_ctx* c, Workspace* w, hipStream_t s) {
-  if (sum_buffer_ready(c, w)) return PVW_OK;
-  const size_t need = sum_layout(c).total;
-  if (w->sumbuf) {
-    PVW_HIP(hipStreamSynchronize(s));
-    hipMemset(w->sumbuf, 0, w->sumbuf_bytes);
-    hipFree(w->sumbuf);
-    w->sumbuf = nullptr;
-    w->sumbuf_bytes = 0;
-  }
-  PVW_HIP(hipMalloc((void**)&w->sumbuf, need));
-  w->sumbuf_bytes = need;
-  return PVW_OK;
+  return ws_grow(&w->sumbuf, &w->sumbuf_bytes, sum_layout(c).total, s, true);
 }
 // range sums of the single-ciphertext decrypt behind a sum (decrypt_mac_only grows Workspace::dpart to this)
 static size_t sum_dpart_need(const pvw_ctx* c) {
@@ -3064,24 +3128,16 @@ static int32_t sum_capture_check(pvw_ctx* c, hipStream_t s, size_t dpart_need, s
                                             "first (it sizes the scratch for the context's own party range)");
   return PVW_OK;
 }
-// wide_words: of the call (a plain decode); pvw_prepare sizes for W, the most any call may ask for
-static int32_t decrypt_all_sum_need(pvw_ctx* c, u32 lo, u32 hi, size_t* need, u32 wide_words) {
-  PlainArgs pa{};
-  pa.wide_words = wide_words;
-  return decrypt_all_run(c, nullptr, nullptr, lo, hi, nullptr, nullptr, nullptr, 1, PVW_REPR_NTT, nullptr, false, (u64*)8, (u32*)8, need,
-                         &pa);
+// the scratch of the device-pointer decrypt behind a sum for NP parties: one NTT-domain ciphertext, the full checked report
+// and wide_words of the call (a plain decode); pvw_prepare sizes for W, the most any call may ask for
+static size_t decrypt_all_sum_need(const pvw_ctx* c, size_t NP, size_t wide_words) {
+  return decrypt_all_layout(c, NP, 1, false, false, true, true, wide_words).sc.total;
 }
 // pvw_prepare(PVW_PREPARE_SUM)
 static int32_t sum_prepare(pvw_ctx* c, Workspace* w, hipStream_t s) {
   PVW_TRY(sum_buffer(c, w, s));
-  const size_t dneed = sum_dpart_need(c);
-  if (w->dpart_bytes < dneed) {
-    if (w->dpart) { PVW_HIP(hipStreamSynchronize(s)); hipFree(w->dpart); w->dpart = nullptr; w->dpart_bytes = 0; }
-    PVW_HIP(hipMalloc((void**)&w->dpart, dneed));
-    w->dpart_bytes = dneed;
-  }
-  size_t need = 0;
-  if (c->party_hi > c->party_lo) PVW_TRY(decrypt_all_sum_need(c, c->party_lo, c->party_hi, &need, (u32)c->Q.mag.size()));
+  PVW_TRY(ws_grow(&w->dpart, &w->dpart_bytes, sum_dpart_need(c), s, false));
+  const size_t need = c->party_hi > c->party_lo ? decrypt_all_sum_need(c, c->party_hi - c->party_lo, c->Q.mag.size()) : 0;
   if (w->scratch_bytes < need) PVW_HIP(hipStreamSynchronize(s));
   return ws_scratch(w, need);
 }
@@ -3111,12 +3167,6 @@ static int32_t no_valid_dealer(size_t D) {
   char buf[112];
   snprintf(buf, sizeof buf, "No valid dealer among the %zu ciphertexts: expected at least 1, got 0", D);
   return fail(PVW_ERR_INSUFFICIENT_DATA, buf);
-}
-// dealers per staged piece: <= 1 GiB of ciphertext words, at most the valid dealers
-static size_t sum_stage_dealers(const pvw_ctx* c, size_t rows, size_t nv) {
-  size_t per = ((size_t)1 << 30) / (((size_t)c->k + rows) * c->poly() * 8);
-  if (per == 0) per = 1;
-  return per < nv ? per : nv;
 }
 // host buffers: runs of valid dealers are copied next to each other into st_c1 [per][k] / st_c2 [per][rows] and every full
 // piece is summed into d_c1_out / d_c2_out (the first piece stores, the later ones add); masked-out dealers are not copied
@@ -3150,8 +3200,7 @@ static int32_t ct_sum_staged(pvw_ctx* c, Workspace* w, u64* st_c1, u64* st_c2, s
 static int32_t ct_sum_checks(const pvw_ctx* c, const void* c1s, const void* c2s, size_t D, u32 lo, u32 hi, const void* c1_out,
                              const void* c2_out) {
   if (!c || !c1s || !c2s || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");
-  if (D >> 32) return fail(PVW_ERR_INVALID_PARAMETERS, "a sum takes fewer than 2^32 dealers");
+  PVW_TRY(check_dealers(D, true));
   if (lo > hi) return fail(PVW_ERR_INVALID_PARAMETERS, "row_lo > row_hi");
   if (hi > c->n) {
     char buf[96];
@@ -3161,6 +3210,7 @@ static int32_t ct_sum_checks(const pvw_ctx* c, const void* c1s, const void* c2s,
   if (lo == hi) return fail(PVW_ERR_INVALID_PARAMETERS, "empty row range");
   return PVW_OK;
 }
+// Not a device_call: the sum marks no key material, and device_end would drain the stream of a call that failed.
 int32_t pvw_ct_sum_device(pvw_ctx* c, const uint64_t* d_c1s, const uint64_t* d_c2s, size_t D, const uint8_t* d_valid, uint32_t lo,
                           uint32_t hi, uint64_t* d_c1_out, uint64_t* d_c2_out, uint32_t* d_count, void* stream) {
   PVW_TRY(ct_sum_checks(c, d_c1s, d_c2s, D, lo, hi, d_c1_out, d_c2_out));
@@ -3179,17 +3229,16 @@ int32_t pvw_ct_sum(pvw_ctx* c, const uint64_t* c1s, const uint64_t* c2s, size_t 
   const size_t nv = count_valid(valid, D);
   if (nv == 0) return no_valid_dealer(D);
   PVW_TRY(ensure_device(c));
-  const size_t P = c->poly(), k = c->k, rows = hi - lo, per = sum_stage_dealers(c, rows, nv);
+  const size_t P = c->poly(), k = c->k, rows = hi - lo, per = chunk_1gib((k + rows) * P * 8, nv);
   Scratch sc;
   const size_t r_c1 = sc.add(per * k * P * 8), r_c2 = sc.add(per * rows * P * 8);
   const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
     PVW_TRY(sum_buffer(c, w, w->stream));
-    const SumLayout sl = sum_layout(c);
-    u64 *d_c1 = (u64*)((char*)w->sumbuf + sl.c1), *d_c2 = (u64*)((char*)w->sumbuf + sl.c2);
-    PVW_TRY(ct_sum_staged(c, w, sc.at(r_c1), sc.at(r_c2), per, c1s, c2s + (size_t)lo * P, (size_t)c->n * P, rows, D, valid, d_c1, d_c2));
-    PVW_HIP(hipMemcpyAsync(c1_out, d_c1, k * P * 8, hipMemcpyDeviceToHost, w->stream));
-    PVW_HIP(hipMemcpyAsync(c2_out, d_c2, rows * P * 8, hipMemcpyDeviceToHost, w->stream));
+    const SumView v = sum_view(c, w);
+    PVW_TRY(ct_sum_staged(c, w, sc.at(r_c1), sc.at(r_c2), per, c1s, c2s + (size_t)lo * P, (size_t)c->n * P, rows, D, valid, v.c1, v.c2));
+    PVW_HIP(hipMemcpyAsync(c1_out, v.c1, k * P * 8, hipMemcpyDeviceToHost, w->stream));
+    PVW_HIP(hipMemcpyAsync(c2_out, v.c2, rows * P * 8, hipMemcpyDeviceToHost, w->stream));
     return PVW_OK;
   });
   if (rc == PVW_OK && count) *count = (uint32_t)nv;
@@ -3219,112 +3268,92 @@ int32_t pvw_ct_sum_host(const pvw_ctx* c, const uint64_t* c1s, const uint64_t* c
 // One party's aggregate share.  The summed ciphertext sits in the sum buffer (c1 | the column's sum: k + 1 polynomials in one
 // run, public); this is the rest: a POWER-basis sum is transformed there, then the single-ciphertext decrypt and its checked
 // decode (decrypt_batch_enqueue with D = 1: the split decrypt_mac + decrypt_finish + the checked decode chain).
-static int32_t decrypt_sum_tail(pvw_ctx* c, Workspace* w, hipStream_t s, const int64_t* d_sk, const u64* key_shat, uint32_t in_repr,
-                                u64* d_noisy, u64* d_out, u64* d_noise, u32* d_status, const PlainArgs* pl = nullptr) {
-  const SumLayout sl = sum_layout(c);
-  u64 *c1 = (u64*)((char*)w->sumbuf + sl.c1), *c2 = (u64*)((char*)w->sumbuf + sl.c2);
+static int32_t decrypt_sum_tail(pvw_ctx* c, Workspace* w, hipStream_t s, KeyRef key, uint32_t in_repr, u64* d_noisy, const Report& rep) {
+  const SumView v = sum_view(c, w);
   if (in_repr == PVW_REPR_POWER) {
     ProfScope ps(c, "ntt", s);
-    PVW_HIP(launch_ntt(c1, (size_t)c->k + 1, false, c->dt, c->L, c->l, s));
+    PVW_HIP(launch_ntt(v.c1, (size_t)c->k + 1, false, c->dt, c->L, c->l, s));
   }
-  if (d_noisy) return decrypt_batch_enqueue(c, w, s, d_sk, key_shat, c1, c2, 1, d_noisy, d_out, d_noise, d_status, pl);
+  if (d_noisy) return decrypt_batch_enqueue(c, w, s, key, v.c1, v.c2, 1, d_noisy, rep);
   // m g + noise of the aggregate is the key holder's: kept in the sum buffer and cleared by a launch right behind the decode
   // (a kernel, so that a captured call clears it on every replay in order); a call that fails on the way leaves it marked
-  d_noisy = (u64*)((char*)w->sumbuf + sl.noisy);
-  ws_mark_secret(w, d_noisy, c->poly() * 8);
-  PVW_TRY(decrypt_batch_enqueue(c, w, s, d_sk, key_shat, c1, c2, 1, d_noisy, d_out, d_noise, d_status, pl));
-  PVW_HIP(launch_wipe_words(d_noisy, c->poly(), s));
-  ws_mark_secret(w, d_noisy, c->poly() * 8, true);
+  ws_mark_secret(w, v.noisy, c->poly() * 8);
+  PVW_TRY(decrypt_batch_enqueue(c, w, s, key, v.c1, v.c2, 1, v.noisy, rep));
+  PVW_HIP(launch_wipe_words(v.noisy, c->poly(), s));
+  ws_mark_secret(w, v.noisy, c->poly() * 8, true);
   return PVW_OK;
 }
-static int32_t decrypt_sum_core(pvw_ctx* c, const int64_t* d_sk, const u64* key_shat, const uint64_t* d_c1s, const uint64_t* d_c2col,
-                                size_t D, const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out,
-                                uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, void* stream,
-                                const PlainArgs* pl = nullptr) {
-  if (!c || !d_c1s || !d_c2col || !d_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");          // decryption.rs:286-290
-  if (D >> 32) return fail(PVW_ERR_INVALID_PARAMETERS, "a sum takes fewer than 2^32 dealers");
-  PVW_TRY(check_repr(in_repr));
-  PVW_TRY(ensure_device(c));
-  hipStream_t s = call_stream(c, stream);
-  PVW_TRY(sum_capture_check(c, s, sum_dpart_need(c), 0));
-  Workspace* w;
-  PVW_TRY(ws_for_stream(c, s, &w));
-  PVW_TRY(sum_buffer(c, w, s));
-  const SumLayout sl = sum_layout(c);
-  auto run = [&]() -> int32_t {
-    PVW_TRY(ct_sum_enqueue(c, w, s, d_c1s, d_c2col, c->poly(), 1, D, d_valid, (u64*)((char*)w->sumbuf + sl.c1),
-                           (u64*)((char*)w->sumbuf + sl.c2), d_count));
-    return decrypt_sum_tail(c, w, s, d_sk, key_shat, in_repr, d_noisy, d_out, d_noise, d_status, PlainAt(pl, 0).ptr());
-  };
-  return device_end(w, s, run());
+// shared by the host-buffer and device-pointer forms; any_null: of the family's own pointer arguments
+static int32_t decrypt_sum_checks(bool any_null, size_t D, uint32_t in_repr) {
+  if (any_null) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(check_dealers(D, true));
+  return check_repr(in_repr);
 }
-int32_t pvw_decrypt_sum_checked_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
-                                       const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise,
-                                       uint32_t* d_status, uint32_t* d_count, void* stream) {
-  if (!c || !d_sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  return decrypt_sum_core(c, d_sk, nullptr, d_c1s, d_c2col, D, d_valid, in_repr, d_noisy, d_out, d_noise, d_status, d_count, stream);
+// device pointers; checked and plain forms
+static int32_t decrypt_sum_device(pvw_ctx* c, KeyRef key, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D, const uint8_t* d_valid,
+                                  uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status,
+                                  uint32_t* d_count, uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream) {
+  Report rep;
+  PVW_TRY(key.rc);
+  PVW_TRY(report_args(c, d_out, d_noise, d_status, plain_modulus, wide_words, d_wide, &rep));
+  PVW_TRY(decrypt_sum_checks(!d_c1s || !d_c2col || !d_out, D, in_repr));
+  return device_call(c, stream, [&](hipStream_t s) { return sum_capture_check(c, s, sum_dpart_need(c), 0); },
+                     [&](Workspace* w, hipStream_t s) -> int32_t {
+    PVW_TRY(sum_buffer(c, w, s));
+    const SumView v = sum_view(c, w);
+    PVW_TRY(ct_sum_enqueue(c, w, s, d_c1s, d_c2col, c->poly(), 1, D, d_valid, v.c1, v.c2, d_count));
+    return decrypt_sum_tail(c, w, s, key, in_repr, d_noisy, rep);
+  });
 }
-int32_t pvw_decrypt_sum_device_sk_checked(pvw_ctx* c, const pvw_sk* key, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
-                                          const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out,
-                                          uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, void* stream) {
-  if (!c || !key || !key->shat) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  if (key->ctx != c) return fail(PVW_ERR_INVALID_PARAMETERS, "the key was loaded for another context");
-  return decrypt_sum_core(c, nullptr, key->shat, d_c1s, d_c2col, D, d_valid, in_repr, d_noisy, d_out, d_noise, d_status, d_count, stream);
-}
-// plain forms
 int32_t pvw_decrypt_sum_plain_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
                                      const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise,
                                      uint32_t* d_status, uint32_t* d_count, uint64_t plain_modulus, uint32_t wide_words,
                                      uint64_t* d_wide, void* stream) {
-  if (!c || !d_sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PlainArgs pa;
-  PVW_TRY(plain_args(c, plain_modulus, wide_words, d_wide, &pa));
-  return decrypt_sum_core(c, d_sk, nullptr, d_c1s, d_c2col, D, d_valid, in_repr, d_noisy, d_out, d_noise, d_status, d_count, stream, &pa);
+  return decrypt_sum_device(c, key_coeffs(c, d_sk), d_c1s, d_c2col, D, d_valid, in_repr, d_noisy, d_out, d_noise, d_status, d_count, plain_modulus,
+                            wide_words, d_wide, stream);
 }
 int32_t pvw_decrypt_sum_device_sk_plain(pvw_ctx* c, const pvw_sk* key, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
                                         const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out,
                                         uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, uint64_t plain_modulus,
                                         uint32_t wide_words, uint64_t* d_wide, void* stream) {
-  if (!c || !key || !key->shat) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  if (key->ctx != c) return fail(PVW_ERR_INVALID_PARAMETERS, "the key was loaded for another context");
-  PlainArgs pa;
-  PVW_TRY(plain_args(c, plain_modulus, wide_words, d_wide, &pa));
-  return decrypt_sum_core(c, nullptr, key->shat, d_c1s, d_c2col, D, d_valid, in_repr, d_noisy, d_out, d_noise, d_status, d_count, stream,
-                          &pa);
+  return decrypt_sum_device(c, key_resident(c, key), d_c1s, d_c2col, D, d_valid, in_repr, d_noisy, d_out, d_noise, d_status, d_count, plain_modulus,
+                            wide_words, d_wide, stream);
 }
-static int32_t decrypt_sum_staged(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
-                                  const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status,
-                                  uint32_t* count, const PlainArgs* pl) {
-  if (!c || !sk || !c1s || !c2col || !out_u64) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "No ciphertexts provided");          // decryption.rs:286-290
-  if (D >> 32) return fail(PVW_ERR_INVALID_PARAMETERS, "a sum takes fewer than 2^32 dealers");
-  PVW_TRY(check_repr(in_repr));
+int32_t pvw_decrypt_sum_checked_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
+                                       const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise,
+                                       uint32_t* d_status, uint32_t* d_count, void* stream) {
+  return decrypt_sum_device(c, key_coeffs(c, d_sk), d_c1s, d_c2col, D, d_valid, in_repr, d_noisy, d_out, d_noise, d_status, d_count, 0, 0, nullptr, stream);
+}
+int32_t pvw_decrypt_sum_device_sk_checked(pvw_ctx* c, const pvw_sk* key, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
+                                          const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out,
+                                          uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, void* stream) {
+  return decrypt_sum_device(c, key_resident(c, key), d_c1s, d_c2col, D, d_valid, in_repr, d_noisy, d_out, d_noise, d_status, d_count, 0, 0, nullptr, stream);
+}
+// host buffers
+int32_t pvw_decrypt_sum_plain(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D, const uint8_t* valid,
+                              uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status, uint32_t* count,
+                              uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
+  Report rep;
+  PVW_TRY(report_args(c, out_u64, noise, status, plain_modulus, wide_words, wide, &rep));
+  PVW_TRY(decrypt_sum_checks(!sk || !c1s || !c2col || !out_u64, D, in_repr));
   const size_t nv = count_valid(valid, D);
   if (nv == 0) return no_valid_dealer(D);
   PVW_TRY(ensure_device(c));
-  const size_t P = c->poly(), k = c->k, l = c->l, per = sum_stage_dealers(c, 1, nv);
+  const size_t P = c->poly(), k = c->k, l = c->l, per = chunk_1gib((k + 1) * P * 8, nv);
   Scratch sc;
   const size_t r_sk = sc.add(k * l * 8), r_c1 = sc.add(per * k * P * 8), r_c2 = sc.add(per * P * 8);
   const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
     PVW_TRY(sum_buffer(c, w, w->stream));
-    const SumLayout sl = sum_layout(c);
+    const SumView v = sum_view(c, w);
+    const Report dev = rep.packed_at(v.io, 1);                        // out | noise | status | wide: the key holder's
     i64* d_sk = sc.at<i64>(r_sk);
-    u64* io = (u64*)((char*)w->sumbuf + sl.io);                  // out | noise | status: the key holder's
     sc.secret(w, r_sk, r_sk);
-    const size_t ww = plain_ww(pl);
-    ws_mark_secret(w, io, 24 + ww * 8);
+    ws_mark_secret(w, v.io, Report::packed_bytes(1, rep.ww));
     PVW_HIP(hipMemcpyAsync(d_sk, sk, k * l * 8, hipMemcpyHostToDevice, w->stream));
-    PVW_TRY(ct_sum_staged(c, w, sc.at(r_c1), sc.at(r_c2), per, c1s, c2col, P, 1, D, valid, (u64*)((char*)w->sumbuf + sl.c1),
-                          (u64*)((char*)w->sumbuf + sl.c2)));
-    PVW_TRY(decrypt_sum_tail(c, w, w->stream, d_sk, nullptr, in_repr, nullptr, io, noise ? io + 1 : nullptr,
-                             status ? (u32*)(io + 2) : nullptr, PlainAt(pl, io + 3, 0).ptr()));
-    PVW_HIP(hipMemcpyAsync(out_u64, io, 8, hipMemcpyDeviceToHost, w->stream));
-    if (noise) PVW_HIP(hipMemcpyAsync(noise, io + 1, 8, hipMemcpyDeviceToHost, w->stream));
-    if (status) PVW_HIP(hipMemcpyAsync(status, io + 2, 4, hipMemcpyDeviceToHost, w->stream));
-    if (ww) PVW_HIP(hipMemcpyAsync(pl->wide, io + 3, ww * 8, hipMemcpyDeviceToHost, w->stream));
-    return PVW_OK;
+    PVW_TRY(ct_sum_staged(c, w, sc.at(r_c1), sc.at(r_c2), per, c1s, c2col, P, 1, D, valid, v.c1, v.c2));
+    PVW_TRY(decrypt_sum_tail(c, w, w->stream, key_coeffs(c, d_sk), in_repr, nullptr, dev));
+    return dev.copy_to(rep, 1, hipMemcpyDeviceToHost, w->stream);
   });
   if (rc == PVW_OK && count) *count = (uint32_t)nv;
   return rc;
@@ -3332,78 +3361,58 @@ static int32_t decrypt_sum_staged(pvw_ctx* c, const int64_t* sk, const uint64_t*
 int32_t pvw_decrypt_sum_checked(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
                                 const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status,
                                 uint32_t* count) {
-  return decrypt_sum_staged(c, sk, c1s, c2col, D, valid, in_repr, out_u64, noise, status, count, nullptr);
-}
-int32_t pvw_decrypt_sum_plain(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D, const uint8_t* valid,
-                              uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status, uint32_t* count,
-                              uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
-  PlainArgs pa;
-  PVW_TRY(plain_args(c, plain_modulus, wide_words, wide, &pa));
-  return decrypt_sum_staged(c, sk, c1s, c2col, D, valid, in_repr, out_u64, noise, status, count, &pa);
+  return pvw_decrypt_sum_plain(c, sk, c1s, c2col, D, valid, in_repr, out_u64, noise, status, count, 0, 0, nullptr);
 }
 
 // Every party's aggregate share: the sum over c1 and rows [lo, hi) of c2 (row r at its global position of the sum buffer, so the
 // buffer reads as ONE whole ciphertext), then decrypt_all_run on that one ciphertext: the 22-party dispatch is its own.
 static int32_t decrypt_all_sum_tail(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, u32 hi, const int64_t* d_sk, uint32_t in_repr,
-                                    u64* d_out, u64* d_noise, u32* d_status, const PlainArgs* pl = nullptr) {
-  const SumLayout sl = sum_layout(c);
-  u64 *c1 = (u64*)((char*)w->sumbuf + sl.c1), *c2 = (u64*)((char*)w->sumbuf + sl.c2);
+                                    const Report& rep) {
+  const SumView v = sum_view(c, w);
   if (in_repr == PVW_REPR_POWER) {
     ProfScope ps(c, "ntt", s);
-    PVW_HIP(launch_ntt(c1, c->k, false, c->dt, c->L, c->l, s));
-    PVW_HIP(launch_ntt(c2 + (size_t)lo * c->poly(), hi - lo, false, c->dt, c->L, c->l, s));
+    PVW_HIP(launch_ntt(v.c1, c->k, false, c->dt, c->L, c->l, s));
+    PVW_HIP(launch_ntt(v.c2 + (size_t)lo * c->poly(), hi - lo, false, c->dt, c->L, c->l, s));
   }
-  return decrypt_all_run(c, w, s, lo, hi, d_sk, c1, c2, 1, PVW_REPR_NTT, d_out, false, d_noise, d_status, nullptr, pl);
-}
-static int32_t decrypt_all_sum_device_core(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
-                                           const uint64_t* d_c2s, size_t D, const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_out,
-                                           uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, void* stream,
-                                           const PlainArgs* pl) {
-  PVW_TRY(decrypt_all_checks(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out));
-  if (D >> 32) return fail(PVW_ERR_INVALID_PARAMETERS, "a sum takes fewer than 2^32 dealers");
-  PVW_TRY(ensure_device(c));
-  hipStream_t s = call_stream(c, stream);
-  size_t need = 0;
-  PVW_TRY(decrypt_all_sum_need(c, lo, hi, &need, (u32)plain_ww(pl)));
-  PVW_TRY(sum_capture_check(c, s, sum_dpart_need(c), need));
-  Workspace* w;
-  PVW_TRY(ws_for_stream(c, s, &w));
-  PVW_TRY(sum_buffer(c, w, s));
-  PVW_TRY(ws_scratch(w, need));                                    // before anything of this call is enqueued
-  const SumLayout sl = sum_layout(c);
-  const size_t P = c->poly();
-  auto run = [&]() -> int32_t {
-    PVW_TRY(ct_sum_enqueue(c, w, s, d_c1s, d_c2s + (size_t)lo * P, (size_t)c->n * P, hi - lo, D, d_valid,
-                           (u64*)((char*)w->sumbuf + sl.c1), (u64*)((char*)w->sumbuf + sl.c2) + (size_t)lo * P, d_count));
-    return decrypt_all_sum_tail(c, w, s, lo, hi, d_sk, in_repr, d_out, d_noise, d_status, PlainAt(pl, 0).ptr());
-  };
-  return device_end(w, s, run());
-}
-int32_t pvw_decrypt_all_sum_checked_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
-                                           const uint64_t* d_c2s, size_t D, const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_out,
-                                           uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, void* stream) {
-  return decrypt_all_sum_device_core(c, lo, hi, d_sk, d_c1s, d_c2s, D, d_valid, in_repr, d_out, d_noise, d_status, d_count, stream, nullptr);
+  return decrypt_all_run(c, w, s, AllCall{lo, (size_t)hi - lo, 1, d_sk, v.c1, v.c2, false, false, rep});
 }
 int32_t pvw_decrypt_all_sum_plain_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
                                          const uint64_t* d_c2s, size_t D, const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_out,
                                          uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, uint64_t plain_modulus,
                                          uint32_t wide_words, uint64_t* d_wide, void* stream) {
-  PlainArgs pa;
-  PVW_TRY(plain_args(c, plain_modulus, wide_words, d_wide, &pa));
-  return decrypt_all_sum_device_core(c, lo, hi, d_sk, d_c1s, d_c2s, D, d_valid, in_repr, d_out, d_noise, d_status, d_count, stream, &pa);
+  Report rep;
+  PVW_TRY(report_args(c, d_out, d_noise, d_status, plain_modulus, wide_words, d_wide, &rep));
+  PVW_TRY(decrypt_all_checks(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out));
+  PVW_TRY(check_dealers(D, true));
+  const size_t P = c->poly(), need = decrypt_all_sum_need(c, (size_t)hi - lo, rep.ww);
+  return device_call(c, stream, [&](hipStream_t s) { return sum_capture_check(c, s, sum_dpart_need(c), need); },
+                     [&](Workspace* w, hipStream_t s) -> int32_t {
+    PVW_TRY(sum_buffer(c, w, s));
+    PVW_TRY(ws_scratch(w, need));                                    // before anything of this call is enqueued
+    const SumView v = sum_view(c, w);
+    PVW_TRY(ct_sum_enqueue(c, w, s, d_c1s, d_c2s + (size_t)lo * P, (size_t)c->n * P, hi - lo, D, d_valid, v.c1, v.c2 + (size_t)lo * P,
+                           d_count));
+    return decrypt_all_sum_tail(c, w, s, lo, hi, d_sk, in_repr, rep);
+  });
 }
-static int32_t decrypt_all_sum_staged(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
-                                      size_t D, const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise,
-                                      uint32_t* status, uint32_t* count, const PlainArgs* pl) {
+int32_t pvw_decrypt_all_sum_checked_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
+                                           const uint64_t* d_c2s, size_t D, const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_out,
+                                           uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, void* stream) {
+  return pvw_decrypt_all_sum_plain_device(c, lo, hi, d_sk, d_c1s, d_c2s, D, d_valid, in_repr, d_out, d_noise, d_status, d_count, 0, 0,
+                                          nullptr, stream);
+}
+int32_t pvw_decrypt_all_sum_plain(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
+                                  size_t D, const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status,
+                                  uint32_t* count, uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
+  Report rep;
+  PVW_TRY(report_args(c, out_u64, noise, status, plain_modulus, wide_words, wide, &rep));
   PVW_TRY(decrypt_all_checks(c, lo, hi, sk, c1s, c2s, D, in_repr, out_u64));
-  if (D >> 32) return fail(PVW_ERR_INVALID_PARAMETERS, "a sum takes fewer than 2^32 dealers");
+  PVW_TRY(check_dealers(D, true));
   const size_t nv = count_valid(valid, D);
   if (nv == 0) return no_valid_dealer(D);
   PVW_TRY(ensure_device(c));
-  const size_t P = c->poly(), k = c->k, l = c->l, NP = (size_t)hi - lo, per = sum_stage_dealers(c, NP, nv);
-  const size_t ww = plain_ww(pl);
-  size_t need = 0;
-  PVW_TRY(decrypt_all_sum_need(c, lo, hi, &need, (u32)ww));
+  const size_t P = c->poly(), k = c->k, l = c->l, NP = (size_t)hi - lo, per = chunk_1gib((k + NP) * P * 8, nv);
+  const size_t need = decrypt_all_sum_need(c, NP, rep.ww);
   // the staged pieces and the decrypt's own scratch share the front of the block (stream order: the sum has read the pieces
   // before the decrypt writes there); the uploaded keys sit behind both
   Scratch st;
@@ -3414,23 +3423,16 @@ static int32_t decrypt_all_sum_staged(pvw_ctx* c, uint32_t lo, uint32_t hi, cons
     PVW_TRY(sc.take(w));
     PVW_TRY(sum_buffer(c, w, w->stream));
     st.base = sc.at<char>(r_main);
-    const SumLayout sl = sum_layout(c);
+    const SumView v = sum_view(c, w);
+    const Report dev = rep.packed_at(v.io, c->n);
     i64* d_sk = sc.at<i64>(r_sk);
-    u64 *d_out = (u64*)((char*)w->sumbuf + sl.io), *d_ns = d_out + c->n;
-    u32* d_st = (u32*)(d_ns + c->n);
-    u64* d_wd = d_ns + 2 * (size_t)c->n;                          // behind the status words, 8-byte aligned
     sc.secret(w, r_sk, r_sk);
-    ws_mark_secret(w, d_out, (size_t)c->n * (24 + 8 * ww));
+    ws_mark_secret(w, v.io, Report::packed_bytes(c->n, rep.ww));
     PVW_HIP(hipMemcpyAsync(d_sk, sk, NP * k * l * 8, hipMemcpyHostToDevice, w->stream));
-    PVW_TRY(ct_sum_staged(c, w, st.at(r_c1), st.at(r_c2), per, c1s, c2s + (size_t)lo * P, (size_t)c->n * P, NP, D, valid,
-                          (u64*)((char*)w->sumbuf + sl.c1), (u64*)((char*)w->sumbuf + sl.c2) + (size_t)lo * P));
-    PVW_TRY(decrypt_all_sum_tail(c, w, w->stream, lo, hi, d_sk, in_repr, d_out, noise ? d_ns : nullptr, status ? d_st : nullptr,
-                                 PlainAt(pl, d_wd, 0).ptr()));
-    PVW_HIP(hipMemcpyAsync(out_u64, d_out, NP * 8, hipMemcpyDeviceToHost, w->stream));
-    if (noise) PVW_HIP(hipMemcpyAsync(noise, d_ns, NP * 8, hipMemcpyDeviceToHost, w->stream));
-    if (status) PVW_HIP(hipMemcpyAsync(status, d_st, NP * 4, hipMemcpyDeviceToHost, w->stream));
-    if (ww) PVW_HIP(hipMemcpyAsync(pl->wide, d_wd, NP * ww * 8, hipMemcpyDeviceToHost, w->stream));
-    return PVW_OK;
+    PVW_TRY(ct_sum_staged(c, w, st.at(r_c1), st.at(r_c2), per, c1s, c2s + (size_t)lo * P, (size_t)c->n * P, NP, D, valid, v.c1,
+                          v.c2 + (size_t)lo * P));
+    PVW_TRY(decrypt_all_sum_tail(c, w, w->stream, lo, hi, d_sk, in_repr, dev));
+    return dev.copy_to(rep, NP, hipMemcpyDeviceToHost, w->stream);
   });
   if (rc == PVW_OK && count) *count = (uint32_t)nv;
   return rc;
@@ -3438,14 +3440,7 @@ static int32_t decrypt_all_sum_staged(pvw_ctx* c, uint32_t lo, uint32_t hi, cons
 int32_t pvw_decrypt_all_sum_checked(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
                                     size_t D, const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise,
                                     uint32_t* status, uint32_t* count) {
-  return decrypt_all_sum_staged(c, lo, hi, sk, c1s, c2s, D, valid, in_repr, out_u64, noise, status, count, nullptr);
-}
-int32_t pvw_decrypt_all_sum_plain(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
-                                  size_t D, const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status,
-                                  uint32_t* count, uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
-  PlainArgs pa;
-  PVW_TRY(plain_args(c, plain_modulus, wide_words, wide, &pa));
-  return decrypt_all_sum_staged(c, lo, hi, sk, c1s, c2s, D, valid, in_repr, out_u64, noise, status, count, &pa);
+  return pvw_decrypt_all_sum_plain(c, lo, hi, sk, c1s, c2s, D, valid, in_repr, out_u64, noise, status, count, 0, 0, nullptr);
 }
 
 // Advisory: for how many dealers at the builder's noise bound the gadget decode of the aggregate is PROVEN exact.  With
