@@ -104,7 +104,8 @@ enum { PVW_RND_SEED = 0, PVW_RND_EXPLICIT = 1 };
 /* ChaCha8 stream-id domains of the counter-based sampler: stream = (domain<<32)|poly index */
 enum {
   PVW_DOM_R = 0, PVW_DOM_E1 = 1, PVW_DOM_E2 = 2, PVW_DOM_SK = 3, PVW_DOM_EKEY = 4,
-  PVW_DOM_CRS = 5, PVW_DOM_GAUSS = 6, PVW_DOM_PK = 7, PVW_DOM_CALL = 8 /* pvw_rnd_call_seed */
+  PVW_DOM_CRS = 5, PVW_DOM_GAUSS = 6, PVW_DOM_PK = 7, PVW_DOM_CALL = 8 /* pvw_rnd_call_seed */,
+  PVW_DOM_SHAMIR = 9 /* polynomial coefficients of pvw_shamir_shares* / pvw_deal_shares*: stream index = j */
 };
 
 /* PvwParametersBuilder fields (src/params/parameters.rs:44-52).  The builder's
@@ -534,6 +535,59 @@ PVW_API int32_t pvw_decrypt_all_sum_plain_device(pvw_ctx* ctx, uint32_t party_lo
                                                  const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise,
                                                  uint32_t* d_status, uint32_t* d_count, uint64_t plain_modulus,
                                                  uint32_t wide_words, uint64_t* d_wide, void* stream);
+
+/* ---- Shamir shares: from secrets to ciphertexts in one call, and back --------------------------------------
+ * The dealing end of the protocol the reference's examples sketch (examples/pvw.rs:95-131 fill the share matrix with arbitrary
+ * numbers; the reference has no sharing code, so this contract is the library's own).  All arithmetic in Z_p, p = plain_modulus:
+ *   p prime, n < p < 2^62 (the points 1..n and their differences must be invertible); primality is checked on the host with a
+ *   deterministic Miller-Rabin.  A composite p, p <= n, p >= 2^62: PVW_ERR_INVALID_PARAMETERS before any device work; so are
+ *   degree >= n, num_dealers = 0 and NULL arguments.
+ *   f_d(x) = s_d + a_{d,1} x + ... + a_{d,t} x^t mod p (t = degree, 0 <= t <= n - 1); shares[d][i] = f_d(i + 1) in [0, p) for the
+ *   global party index i: any t + 1 shares determine s_d.  secrets [D] and explicit coefficients are words that mean w mod p (any
+ *   word is accepted).  t = 0 copies the secret to every party and draws nothing.
+ *   a_{d,j} (j = 1..t) = the first accepted draw of its own ChaCha8 stream: key = dealer d's 32-byte seed (seeds + 32 d, the
+ *   seed pvw_encrypt_multi takes for that dealer), stream id (PVW_DOM_SHAMIR << 32) | j, draws next_u64() >> clz(p) accepted when
+ *   < p.  coeffs != NULL ([D][t] words) replaces the draw (seeds may then be NULL).
+ * shares [D][n]: the host routine writes every column; the device routines write columns [party_lo, party_hi) of a sharded
+ * context and leave the others untouched. */
+/* the contract in plain C++ on the host cores (no GPU needed): what the kernel is tested against */
+PVW_API int32_t pvw_shamir_shares_host(const pvw_ctx* ctx, const uint64_t* secrets, size_t num_dealers, uint32_t degree,
+                                       uint64_t plain_modulus, const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out);
+/* device pointers (seeds stays a HOST pointer), asynchronous on `stream`; allocates nothing and may be captured */
+PVW_API int32_t pvw_shamir_shares_device(pvw_ctx* ctx, const uint64_t* d_secrets, size_t num_dealers, uint32_t degree,
+                                         uint64_t plain_modulus, const uint8_t* seeds, const uint64_t* d_coeffs, uint64_t* d_shares,
+                                         void* stream);
+/* host buffers (synchronous); the staged secrets, coefficients and shares are cleared before the call returns */
+PVW_API int32_t pvw_shamir_shares(pvw_ctx* ctx, const uint64_t* secrets, size_t num_dealers, uint32_t degree,
+                                  uint64_t plain_modulus, const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out);
+/* Deal: the shares are made on the device and encrypted in the same call -- neither they nor the coefficients exist on the host.
+ *   pvw_deal_shares*(secrets, D, degree, p, seeds, ...)  ==  pvw_encrypt_multi*(shares, D, n, seeds, ...) bit for bit, with
+ *   shares = pvw_shamir_shares_host(secrets, D, degree, p, seeds, NULL): both representations, both sides of the dealer-count
+ *   dispatch, sharded contexts.  The arguments, checks and buffer layouts of the pvw_encrypt_multi* call each one extends (those
+ *   checks come first, then the ones above).  _rs forms: dealer d's key is call_seed(S, c + d), derived when the kernels run;
+ *   afterwards the state holds c + D, exactly as pvw_encrypt_multi_rs*.
+ * The shares live in workspace scratch of a fixed size (one pass of dealers, [128][n] words) built together with the digit buffers:
+ * pvw_prepare(PVW_PREPARE_MFMA) covers it, after which the *_device forms neither allocate nor synchronise and may be captured
+ * (every replay of the _rs form deals a fresh sharing); under stream capture without it: the error of pvw_encrypt_multi_device,
+ * nothing enqueued.  The scratch (and the uploaded secrets of the host-buffer forms) is cleared behind the call's last launch
+ * (pvw_selftest_secret_residue). */
+PVW_API int32_t pvw_deal_shares(pvw_ctx* ctx, const uint64_t* secrets, size_t num_dealers, uint32_t degree, uint64_t plain_modulus,
+                                const uint8_t* seeds /*[D][32]*/, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr);
+PVW_API int32_t pvw_deal_shares_device(pvw_ctx* ctx, const uint64_t* d_secrets, size_t num_dealers, uint32_t degree,
+                                       uint64_t plain_modulus, const uint8_t* seeds, uint64_t* d_c1, uint64_t* d_c2,
+                                       uint32_t out_repr, void* stream);
+PVW_API int32_t pvw_deal_shares_rs(pvw_ctx* ctx, const uint64_t* secrets, size_t num_dealers, uint32_t degree,
+                                   uint64_t plain_modulus, void* st, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr);
+PVW_API int32_t pvw_deal_shares_rs_device(pvw_ctx* ctx, const uint64_t* d_secrets, size_t num_dealers, uint32_t degree,
+                                          uint64_t plain_modulus, void* st, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr,
+                                          void* stream);
+/* Reconstruction, host only (no GPU, no context: t + 1 values per secret, and the combining party is not the dealer):
+ *   out[s] = sum_i shares[s][i] * w_i mod p, w_i the Lagrange weights at 0 of the points indices[i] + 1, computed once.
+ * indices [count]: global party indices; shares [num_secrets][count] (any words, read mod p).  count = 0, duplicate indices, an
+ * index >= p - 1, a composite p or p >= 2^62: PVW_ERR_INVALID_PARAMETERS.  count must be at least degree + 1 for the result to
+ * be the secret; the routine cannot know the degree and does not check. */
+PVW_API int32_t pvw_shamir_reconstruct(uint64_t plain_modulus, const uint64_t* indices, const uint64_t* shares, size_t count,
+                                       size_t num_secrets, uint64_t* out);
 
 /* decode_scalar_pvw_rns alone, on the device: noisy [D][L][l] power basis (host) -> out_u64 [D] */
 PVW_API int32_t pvw_decode(pvw_ctx* ctx, const uint64_t* noisy, size_t count, uint64_t* out_u64);

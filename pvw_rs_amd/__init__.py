@@ -5,7 +5,7 @@
 interface over that ABI; `host/pvw.hpp` is the same mirror in C++.
 There is no CPU fallback: device entry points fail loudly without the library / a GPU.
 """
-from ._ffi import (DOM_CALL, DOM_CRS, DOM_E1, DOM_E2, DOM_EKEY, DOM_GAUSS, DOM_PK, DOM_R, DOM_SK, PREPARE_MFMA, PREPARE_PACKED, PREPARE_SUM,
+from ._ffi import (DOM_SHAMIR, DOM_CALL, DOM_CRS, DOM_E1, DOM_E2, DOM_EKEY, DOM_GAUSS, DOM_PK, DOM_R, DOM_SK, PREPARE_MFMA, PREPARE_PACKED, PREPARE_SUM,
                    REPR_NTT, REPR_POWER)
 from .api import (DEC_LOSSY, DEC_NEGATIVE, DEC_WIDE_TRUNCATED, CheckedDecryption, DeviceRandomness, DeviceSecretKey, GlobalPublicKey, Party, PvwCiphertext, PvwCrs, PvwError, PvwParameters,
                   PvwParametersBuilder, SecretKey, decode_scalar_pvw, decode_scalar_pvw_host, decrypt_all_party_shares, decrypt_many,
@@ -13,7 +13,8 @@ from .api import (DEC_LOSSY, DEC_NEGATIVE, DEC_WIDE_TRUNCATED, CheckedDecryption
                   decrypt_many_checked, decrypt_party_shares_checked, decrypt_party_value_checked,
                   decrypt_party_value, device_available, encrypt, encrypt_all_party_shares,
                   encrypt_broadcast, encrypt_many, encrypt_party_shares, aggregate_ciphertexts, decrypt_party_sum,
-                  decrypt_all_party_sums, decode_scalar_pvw_plain, decode_scalar_pvw_plain_host)
+                  decrypt_all_party_sums, decode_scalar_pvw_plain, decode_scalar_pvw_plain_host,
+                  shamir_shares, deal_party_shares, shamir_reconstruct)
 
 __all__ = [
     "PvwParametersBuilder", "PvwParameters", "PvwCrs", "SecretKey", "DeviceSecretKey", "DeviceRandomness", "Party", "GlobalPublicKey",
@@ -24,5 +25,6 @@ __all__ = [
     "decrypt_all_party_shares_checked", "decode_scalar_pvw_checked", "decode_scalar_pvw_checked_host",
     "decode_scalar_pvw_plain", "decode_scalar_pvw_plain_host",
     "aggregate_ciphertexts", "decrypt_party_sum", "decrypt_all_party_sums",
+    "shamir_shares", "deal_party_shares", "shamir_reconstruct",
     "device_available", "REPR_POWER", "REPR_NTT",
 ]

@@ -21,7 +21,7 @@ ERROR_NAMES = {
 }
 REPR_POWER, REPR_NTT = 0, 1
 RND_SEED, RND_EXPLICIT = 0, 1
-DOM_R, DOM_E1, DOM_E2, DOM_SK, DOM_EKEY, DOM_CRS, DOM_GAUSS, DOM_PK, DOM_CALL = range(9)
+DOM_R, DOM_E1, DOM_E2, DOM_SK, DOM_EKEY, DOM_CRS, DOM_GAUSS, DOM_PK, DOM_CALL, DOM_SHAMIR = range(10)
 PREPARE_PACKED, PREPARE_MFMA, PREPARE_SUM = 1, 2, 4
 WIRE_PARAMS, WIRE_CRS, WIRE_PK, WIRE_CT, WIRE_SK = 1, 2, 3, 4, 5     # wire format v1 kinds
 
@@ -126,6 +126,15 @@ _SIGNATURES = {
     "pvw_decrypt_sum_device_sk_plain": [_P, _P, _P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P],
     "pvw_decrypt_all_sum_plain": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P],
     "pvw_decrypt_all_sum_plain_device": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P],
+    # Shamir shares
+    "pvw_shamir_shares_host": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint64, _P, _P, _P],
+    "pvw_shamir_shares_device": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint64, _P, _P, _P, _P],
+    "pvw_shamir_shares": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint64, _P, _P, _P],
+    "pvw_deal_shares": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint64, _P, _P, _P, C.c_uint32],
+    "pvw_deal_shares_device": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint64, _P, _P, _P, C.c_uint32, _P],
+    "pvw_deal_shares_rs": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint64, _P, _P, _P, C.c_uint32],
+    "pvw_deal_shares_rs_device": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint64, _P, _P, _P, C.c_uint32, _P],
+    "pvw_shamir_reconstruct": [C.c_uint64, _P, _P, C.c_size_t, C.c_size_t, _P],
     "pvw_decode": [_P, _P, C.c_size_t, _P],
     "pvw_decode_host": [_P, _P, C.c_size_t, _P],
     "pvw_decode_device": [_P, _P, C.c_size_t, _P, _P],

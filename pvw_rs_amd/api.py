@@ -818,6 +818,75 @@ def encrypt_many(all_scalars: Sequence[Sequence[int]], global_pk: GlobalPublicKe
     return [PvwCiphertext(c1[d], c2[d], p, repr) for d in range(D)]
 
 
+def _words(values) -> np.ndarray:
+    return np.array([int(v) & 0xFFFFFFFFFFFFFFFF for v in values], dtype=np.uint64)
+
+
+def _seeds(seeds, D: int) -> np.ndarray:
+    if len(seeds) != D:
+        raise PvwError(15, f"expected {D} seeds, got {len(seeds)}")
+    return np.concatenate([_seed(s) for s in seeds])
+
+
+def shamir_shares(params: PvwParameters, secrets: Sequence[int], degree: int, plain_modulus: int,
+                  seeds: Optional[Sequence[bytes]] = None, coeffs=None, host: bool = False) -> np.ndarray:
+    """EXTENSION (DESIGN 8.9): shares[d][i] = f_d(i + 1) mod plain_modulus, f_d = secrets[d] + a_{d,1} x + ... of `degree`;
+    the a_{d,j} are drawn from dealer d's 32-byte seed (stream (DOM_SHAMIR << 32) | j) or given as coeffs [D][degree].
+    On the device (pvw_shamir_shares); host=True: the plain C++ restatement (pvw_shamir_shares_host, no GPU).  A sharded
+    context's device call writes its own columns of the (D, n) result and leaves the others zero."""
+    se = _words(secrets)
+    D = len(se)
+    sd = _seeds(seeds, D) if seeds is not None else None
+    co = None
+    if coeffs is not None:
+        co = np.array([[int(v) & 0xFFFFFFFFFFFFFFFF for v in row] for row in coeffs], dtype=np.uint64).reshape(D, -1)
+        if co.shape[1] != int(degree):
+            raise PvwError(15, f"expected {int(degree)} coefficients per dealer, got {co.shape[1]}")
+    out = np.zeros((D, params.n), dtype=np.uint64)
+    params._call("pvw_shamir_shares_host" if host else "pvw_shamir_shares", _ptr(se), D, int(degree), int(plain_modulus),
+                 _ptr(sd), _ptr(co), _ptr(out))
+    return out
+
+
+def deal_party_shares(secrets: Sequence[int], degree: int, plain_modulus: int, global_pk: GlobalPublicKey,
+                      seeds: Optional[Sequence[bytes]] = None, randomness: Optional["DeviceRandomness"] = None,
+                      out_repr: int = REPR_NTT) -> List[PvwCiphertext]:
+    """EXTENSION: dealer d shares secrets[d] among the n parties and encrypts the shares, in one device call
+    (pvw_deal_shares): what encrypt_many(shamir_shares(..., seeds), global_pk, seeds) returns, without the shares or the
+    polynomial coefficients ever existing on the host.  `randomness` instead of `seeds`: dealer d uses call_seed(S, c + d)
+    of that DeviceRandomness, which then holds c + D."""
+    p = global_pk.params
+    se = _words(secrets)
+    D = len(se)
+    c1 = np.zeros((D, p.k, p.L, p.l), dtype=np.uint64)
+    c2 = np.zeros((D, p.n, p.L, p.l), dtype=np.uint64)
+    if randomness is not None:
+        _check_state(p, randomness, seeds)
+        p._call("pvw_deal_shares_rs", _ptr(se), D, int(degree), int(plain_modulus), randomness._h, _ptr(c1), _ptr(c2), out_repr)
+    else:
+        if seeds is None:
+            raise PvwError(1, "deal_party_shares needs one 32-byte seed per dealer or a DeviceRandomness")
+        sd = _seeds(seeds, D)
+        p._call("pvw_deal_shares", _ptr(se), D, int(degree), int(plain_modulus), _ptr(sd), _ptr(c1), _ptr(c2), out_repr)
+    return [PvwCiphertext(c1[d], c2[d], p, out_repr) for d in range(D)]
+
+
+def shamir_reconstruct(indices: Sequence[int], shares, plain_modulus: int):
+    """EXTENSION: the secret(s) from the shares of the parties `indices` (global indices, at least degree + 1
+    of them), by Lagrange interpolation at 0 on the host (pvw_shamir_reconstruct; no GPU, no context).  shares: one value
+    per index -> an int; or rows [num_secrets][len(indices)] -> a list of ints."""
+    idx = _words(indices)
+    single = len(shares) == 0 or np.ndim(shares[0]) == 0
+    rows = [shares] if single else shares
+    sh = np.array([[int(v) & 0xFFFFFFFFFFFFFFFF for v in row] for row in rows], dtype=np.uint64).reshape(len(rows), -1)
+    if sh.shape[1] != len(idx):
+        raise PvwError(15, f"expected {len(idx)} shares per secret, got {sh.shape[1]}")
+    out = np.zeros(len(rows), dtype=np.uint64)
+    L = _ffi.lib()
+    _check(L.pvw_shamir_reconstruct(int(plain_modulus), _ptr(idx), _ptr(sh), len(idx), len(rows), _ptr(out)), L)
+    return int(out[0]) if single else [int(v) for v in out]
+
+
 def encrypt_broadcast(scalar: int, global_pk: GlobalPublicKey, seed: Optional[bytes] = None, **kw) -> PvwCiphertext:
     """encryption.rs:292-296."""
     return encrypt([scalar] * global_pk.params.n, global_pk, seed, **kw)

@@ -8,6 +8,7 @@
 // gate (:510-551) and the integer gadget decode (src/crypto/decryption.rs:10-247).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -135,6 +136,8 @@ struct Workspace {
   u64* gtmpA = nullptr;      // GEMM intermediates [limb][slot][v][row]
   u64* gtmpB = nullptr;
   u64* gtmpK = nullptr;      // ... for key generation (k rows)
+  u64* shares = nullptr;     // Shamir shares of one pass of dealers [SHARE_PASS][n] (pvw_deal_shares*; built with the digit buffers)
+  size_t shares_bytes = 0;
   // helper stream + events (ws_aux): decode of chunk i under the MAC of chunk i+1, key uploads under key generation
   hipStream_t aux = nullptr;
   bool aux_used = false;     // by the current host call: drained by host_call
@@ -575,6 +578,8 @@ static void ws_free(Workspace* w) {
   hipFree(w->gtmpA);
   hipFree(w->gtmpB);
   hipFree(w->gtmpK);
+  if (w->shares) hipMemset(w->shares, 0, w->shares_bytes);   // the last deal's shares, if its wipe did not run
+  hipFree(w->shares);
   for (hipEvent_t e : w->events) hipEventDestroy(e);
   if (w->aux) hipStreamDestroy(w->aux);
   if (w->own_stream && w->stream) hipStreamDestroy(w->stream);
@@ -1090,8 +1095,19 @@ static u32 gemm_vb() {   // tuning build: PVW_GEMM_VB
   }();
   return v;
 }
+// the shares of one pass of dealers of pvw_deal_shares* (DESIGN 8.9): the largest group encrypt_multi_enqueue forms, 128 dealers
+enum { SHARE_PASS = 128 };
+static int32_t ws_share_buffer(pvw_ctx* c, Workspace* w) {
+  if (w->shares) return PVW_OK;
+  const size_t bytes = (size_t)SHARE_PASS * c->n * 8;
+  PVW_HIP(hipMalloc((void**)&w->shares, bytes));
+  w->shares_bytes = bytes;
+  PVW_HIP(hipMemset(w->shares, 0, bytes));                 // recycled device memory may hold an earlier owner's data
+  return PVW_OK;
+}
 static int32_t ws_gemm_buffers(pvw_ctx* c, Workspace* w) {
   const u32 vb = gemm_vb();
+  PVW_TRY(ws_share_buffer(c, w));
   if (!w->vhat16) PVW_HIP(hipMalloc((void**)&w->vhat16, (size_t)16 * vb * c->k * c->poly() * 8));
   if (!w->yd) PVW_HIP(hipMalloc((void**)&w->yd, yd_bytes(16 * vb, c->k, c->L, c->l)));
   if (!w->sy) PVW_HIP(hipMalloc((void**)&w->sy, sy_bytes(16 * vb, c->L, c->l)));
@@ -1833,8 +1849,19 @@ static int32_t multi_capture_check(pvw_ctx* c, hipStream_t s, size_t D) {
 // Device layout: d_scalars [D][n]; d_c1 [D][rowsA][L][l]; d_c2 [D][rowsB][L][l].
 // rs != NULL: dealer d's seed is call_seed(S, c + d) of that device state instead of seeds + 32 d (seeds is not read), with
 // c the counter when the call's kernels run; the call's last kernel advances the counter by D.
+// deal != NULL (pvw_deal_shares*): d_scalars is not read; the scalars of each pass of dealers are their Shamir
+// shares, made into w->shares by shamir_enqueue in front of the pass (under the same seeds / state, domain DOM_SHAMIR).
+struct ShamirDeal {
+  const u64* d_secrets;   // [D]
+  const u64* d_coeffs;    // [D][degree], or NULL: drawn from the dealers' seeds
+  u32 degree;
+  Mod m;
+};
+static int32_t shamir_enqueue(pvw_ctx* c, const ShamirDeal& deal, const uint8_t* seeds, RndState* rs, u64 rnd_off, size_t D,
+                              u64* d_shares, hipStream_t s);
 static int32_t encrypt_multi_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, const uint8_t* seeds,
-                                     size_t D, u64* d_c1, u64* d_c2, uint32_t out_repr, hipStream_t s, RndState* rs = nullptr) {
+                                     size_t D, u64* d_c1, u64* d_c2, uint32_t out_repr, hipStream_t s, RndState* rs = nullptr,
+                                     const ShamirDeal* deal = nullptr) {
   const u32 k = c->k, l = c->l, L = c->L, rA = c->rowsA(), rB = c->rowsB();
   const size_t P = c->poly();
   const bool use_gemm = multi_uses_gemm(D);
@@ -1848,6 +1875,11 @@ static int32_t encrypt_multi_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scal
   u64* vh = use_gemm ? w->vhat16 : w->rhat;
   for (size_t d0 = 0; d0 < D; d0 += group) {
     const u32 nv = (u32)((D - d0) < group ? (D - d0) : group);
+    const u64* gsc = deal ? w->shares : d_scalars + d0 * c->n;   // the pass's scalars [nv][n]
+    if (deal) {
+      const ShamirDeal dd{deal->d_secrets + d0, deal->d_coeffs ? deal->d_coeffs + d0 * deal->degree : nullptr, deal->degree, deal->m};
+      PVW_TRY(shamir_enqueue(c, dd, seeds ? seeds + d0 * 32 : nullptr, rs, d0, nv, w->shares, s));
+    }
     // prologue: the (r, e1, e2) families of dealer d0 replicated over the nv dealers of this pass (up to 64 keys
     // per launch): r-hat_d -> vh[v], NTT(e1), NTT(e2) + m*g-hat -> output planes
     for (u32 v0 = 0; v0 < nv; v0 += PVW_MAX_PROLOGUE_KEYS) {
@@ -1857,7 +1889,7 @@ static int32_t encrypt_multi_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scal
       pvw_randomness_t rnd{};
       rnd.mode = PVW_RND_SEED;
       if (!rs) memcpy(rnd.seed, seeds + d * 32, 32);
-      PVW_TRY(fill_encrypt_jobs(c, pb, 0, &rnd, d_scalars + d * c->n, vh + (size_t)v0 * k * P,
+      PVW_TRY(fill_encrypt_jobs(c, pb, 0, &rnd, gsc + (size_t)v0 * c->n, vh + (size_t)v0 * k * P,
                                 d_c1 + d * rA * P, d_c2 + d * rB * P));
       if (rs) {
         pb.rnd = rs;                                            // replica x: call_seed(S, counter + d + x)
@@ -1899,7 +1931,7 @@ static int32_t encrypt_multi_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scal
           }
           e.key_v = 1;
           e.domain = DOM_E2; e.index0 = c->party_lo; e.index_row = 1; e.index_v = 0; e.bound = c->b2;
-          e.scalars = d_scalars + d0 * c->n + c->party_lo; e.scalar_v = c->n;
+          e.scalars = gsc + c->party_lo; e.scalar_v = c->n;
           es.push_back(e);
         }
         b.addend = nullptr;
@@ -2144,6 +2176,269 @@ int32_t pvw_encrypt_multi_rs(pvw_ctx* c, const uint64_t* scalars, size_t num_dea
   PVW_TRY(ensure_device(c));
   PVW_TRY(rnd_state_checks(c, st));
   return encrypt_multi_host(c, scalars, num_dealers, nullptr, st->dev, c1_out, c2_out, out_repr);
+}
+
+// ------------------------------------------------------------------------ Shamir shares
+// f_d(x) = s_d + a_{d,1} x + ... + a_{d,t} x^t over Z_p, party i gets f_d(i + 1).  The reference has no sharing code (its
+// examples fill the share matrix with arbitrary numbers, examples/pvw.rs:95-131): the contract is this library's own.
+static Mod shamir_mod(u64 p) {
+  Mod m = make_mod(p);
+  if (p == 2) { m.ratio_lo = 0; m.ratio_hi = (u64)1 << 63; }   // make_mod's quotient is one short for a power of two
+  return m;
+}
+static int32_t shamir_modulus_check(u64 p) {
+  if (p >= ((u64)1 << 62)) return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must be below 2^62");
+  if (!is_prime_u64(p)) return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must be prime (Shamir shares live in a field)");
+  return PVW_OK;
+}
+static int32_t shamir_checks(const pvw_ctx* c, size_t D, uint32_t degree, u64 p) {
+  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no dealers");
+  if (p <= c->n) return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must exceed the party count (evaluation points 1..n)");
+  PVW_TRY(shamir_modulus_check(p));
+  if (degree >= c->n) {
+    char buf[96];
+    snprintf(buf, sizeof buf, "degree %u needs more than %u parties", degree, c->n);
+    return fail(PVW_ERR_INVALID_PARAMETERS, buf);
+  }
+  return PVW_OK;
+}
+
+// the contract in plain C++ (no GPU): sequential draws, Horner.  Writes all n columns, whatever the context's shard.
+int32_t pvw_shamir_shares_host(const pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t degree,
+                               uint64_t plain_modulus, const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out) {
+  if (!c || !secrets || !shares_out || (degree && !seeds && !coeffs)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(shamir_checks(c, num_dealers, degree, plain_modulus));
+  const Mod m = shamir_mod(plain_modulus);
+  const u32 n = c->n, t = degree;
+  std::vector<u64> a((size_t)t + 1);
+  for (size_t d = 0; d < num_dealers; ++d) {
+    a[0] = reduce_word(secrets[d], m);
+    for (u32 j = 1; j <= t; ++j) {
+      if (coeffs) {
+        a[j] = reduce_word(coeffs[d * t + (j - 1)], m);
+      } else {
+        ChaChaRng g;
+        g.init(make_key(seeds + d * 32), PVW_DOM_SHAMIR, j);
+        u64* o = &a[j];
+        sample_residues_poly(g, 1, m.q, [o](u32, u64 v) { *o = v; });
+      }
+    }
+    for (u32 i = 0; i < n; ++i) {
+      const u64 x = (u64)i + 1;
+      u64 acc = a[t];
+      for (u32 j = t; j-- > 0;) acc = addmod(mulmod(acc, x, m), a[j], m.q);
+      shares_out[d * n + i] = acc;
+    }
+  }
+  volatile u64* va = a.data();                               // the coefficients are as secret as the secret
+  for (size_t j = 0; j <= t; ++j) va[j] = 0;
+  return PVW_OK;
+}
+
+// Lagrange weights at 0 for the points x_i = indices[i] + 1, once; then one dot product per secret.  Host only.
+int32_t pvw_shamir_reconstruct(uint64_t plain_modulus, const uint64_t* indices, const uint64_t* shares, size_t count,
+                               size_t num_secrets, uint64_t* out) {
+  if (!indices || !shares || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (count == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no shares to reconstruct from");
+  if (plain_modulus < 2) return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must be prime (Shamir shares live in a field)");
+  PVW_TRY(shamir_modulus_check(plain_modulus));
+  const Mod m = shamir_mod(plain_modulus);
+  for (size_t i = 0; i < count; ++i)
+    if (indices[i] >= m.q - 1) return fail(PVW_ERR_INVALID_PARAMETERS, "party index out of range for plain_modulus");
+  {
+    std::vector<u64> sorted(indices, indices + count);
+    std::sort(sorted.begin(), sorted.end());
+    for (size_t i = 1; i < count; ++i)
+      if (sorted[i] == sorted[i - 1]) return fail(PVW_ERR_INVALID_PARAMETERS, "duplicate party index");
+  }
+  // w_i = prod_{j != i} x_j / (x_j - x_i)
+  std::vector<u64> w(count);
+  for (size_t i = 0; i < count; ++i) {
+    const u64 xi = indices[i] + 1;
+    u64 num = 1, den = 1;
+    for (size_t j = 0; j < count; ++j) {
+      if (j == i) continue;
+      const u64 xj = indices[j] + 1;
+      num = mulmod(num, xj, m);
+      den = mulmod(den, submod(xj, xi, m.q), m);
+    }
+    w[i] = mulmod(num, powmod(den, m.q - 2, m), m);
+  }
+  for (size_t sidx = 0; sidx < num_secrets; ++sidx) {
+    u64 acc = 0;
+    for (size_t i = 0; i < count; ++i) acc = addmod(acc, mulmod(reduce_word(shares[sidx * count + i], m), w[i], m), m.q);
+    out[sidx] = acc;
+  }
+  return PVW_OK;
+}
+
+// the shares of dealers [0, D) into d_shares [D][n] (columns [party_lo, party_hi)), PVW_MAX_PROLOGUE_KEYS dealers per launch.
+// seeds: the dealers' host seeds; rs: the device state instead (dealer d: call_seed(S, counter + rnd_off + d)).
+static int32_t shamir_enqueue(pvw_ctx* c, const ShamirDeal& deal, const uint8_t* seeds, RndState* rs, u64 rnd_off, size_t D,
+                              u64* d_shares, hipStream_t s) {
+  ProfScope ps(c, "shamir_eval", s);
+  for (size_t d0 = 0; d0 < D; d0 += PVW_MAX_PROLOGUE_KEYS) {
+    ShamirBatch b{};
+    b.nd = (u32)((D - d0) < PVW_MAX_PROLOGUE_KEYS ? (D - d0) : PVW_MAX_PROLOGUE_KEYS);
+    b.secrets = deal.d_secrets + d0;
+    b.coeffs = deal.d_coeffs ? deal.d_coeffs + d0 * deal.degree : nullptr;
+    b.shares = d_shares + d0 * c->n;
+    b.row_stride = c->n;
+    b.degree = deal.degree;
+    b.party_lo = c->party_lo;
+    b.party_hi = c->party_hi;
+    b.m = deal.m;
+    if (!b.coeffs && deal.degree) {
+      if (rs) {
+        b.rnd = rs;
+        b.rnd_off = rnd_off + d0;
+      } else {
+        for (u32 x = 0; x < b.nd; ++x) b.key[x] = make_key(seeds + (d0 + x) * 32);
+      }
+    }
+    PVW_HIP(launch_shamir_eval(b, s));
+    memset(&b, 0, sizeof b);
+  }
+  return PVW_OK;
+}
+
+int32_t pvw_shamir_shares_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t degree,
+                                 uint64_t plain_modulus, const uint8_t* seeds, const uint64_t* d_coeffs, uint64_t* d_shares,
+                                 void* stream) {
+  if (!c || !d_secrets || !d_shares || (degree && !seeds && !d_coeffs)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(shamir_checks(c, num_dealers, degree, plain_modulus));
+  PVW_TRY(ensure_device(c));
+  const ShamirDeal deal{d_secrets, d_coeffs, degree, shamir_mod(plain_modulus)};
+  return shamir_enqueue(c, deal, seeds, nullptr, 0, num_dealers, d_shares, call_stream(c, stream));
+}
+
+int32_t pvw_shamir_shares(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t degree, uint64_t plain_modulus,
+                          const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out) {
+  if (!c || !secrets || !shares_out || (degree && !seeds && !coeffs)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(shamir_checks(c, num_dealers, degree, plain_modulus));
+  PVW_TRY(ensure_device(c));
+  const size_t n = c->n, t = degree, rB = c->rowsB();
+  const size_t per = chunk_1gib((n + (coeffs ? t : 0) + 1) * 8, num_dealers);
+  Scratch sc;
+  const size_t r_se = sc.add(per * 8), r_co = sc.add(coeffs ? per * t * 8 : 0), r_sh = sc.add(per * n * 8);
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    sc.secret(w, r_se, r_sh);                                  // secrets, coefficients and shares alike
+    u64 *d_se = sc.at(r_se), *d_co = coeffs && t ? sc.at(r_co) : nullptr, *d_sh = sc.at(r_sh);
+    for (size_t d0 = 0; d0 < num_dealers; d0 += per) {
+      const size_t cnt = (num_dealers - d0) < per ? (num_dealers - d0) : per;
+      PVW_HIP(hipMemcpyAsync(d_se, secrets + d0, cnt * 8, hipMemcpyHostToDevice, w->stream));
+      if (d_co) PVW_HIP(hipMemcpyAsync(d_co, coeffs + d0 * t, cnt * t * 8, hipMemcpyHostToDevice, w->stream));
+      const ShamirDeal deal{d_se, d_co, degree, shamir_mod(plain_modulus)};
+      PVW_TRY(shamir_enqueue(c, deal, seeds ? seeds + d0 * 32 : nullptr, nullptr, 0, cnt, d_sh, w->stream));
+      // a sharded context writes its own columns only
+      if (rB) PVW_HIP(hipMemcpy2DAsync(shares_out + d0 * n + c->party_lo, n * 8, d_sh + c->party_lo, n * 8, rB * 8, cnt,
+                                       hipMemcpyDeviceToHost, w->stream));
+      PVW_HIP(hipStreamSynchronize(w->stream));                // the next pass reuses the staging
+    }
+    return PVW_OK;
+  });
+}
+
+// Under stream capture a deal may not allocate: the share scratch is built with the digit buffers by pvw_prepare(PVW_PREPARE_MFMA),
+// whatever the dealer count (checked before the stream's workspace is looked up, like multi_capture_check)
+static int32_t deal_capture_check(pvw_ctx* c, hipStream_t s, size_t D) {
+  if (!stream_capturing(s)) return PVW_OK;
+  bool ready;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    auto it = c->async_ws.find((void*)s);
+    ready = it != c->async_ws.end() && it->second->shares;
+  }
+  if (!ready)
+    return fail(PVW_ERR_INVALID_PARAMETERS, "multi-dealer encrypt under stream capture: call pvw_prepare(PVW_PREPARE_MFMA) on "
+                                            "this stream first (and again after the matrices change)");
+  return multi_capture_check(c, s, D);
+}
+
+// what a deal leaves in the workspace: the shares, and below the matrix-core threshold the dealers' r-hat in the vectors the
+// workspace shares with key material (with r-hat a share is c2 - <b-hat, r-hat>; pvw_selftest_secret_residue always scans them)
+static void deal_mark(Workspace* w, size_t D) {
+  ws_mark_secret(w, w->shares, w->shares_bytes);
+  if (!multi_uses_gemm(D)) ws_mark_secret(w, w->rhat, w->rhat_bytes);
+}
+// device pointers: encrypt_multi_enqueue with the shares made pass by pass in the workspace's share scratch, which the call marks
+// secret (cleared on the stream behind the call's last launch)
+static int32_t deal_device(pvw_ctx* c, const uint64_t* d_secrets, size_t D, uint32_t degree, uint64_t p, const uint8_t* seeds,
+                           RndState* rs, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
+  const ShamirDeal deal{d_secrets, nullptr, degree, shamir_mod(p)};
+  return device_call(c, stream, [&](hipStream_t s) { return deal_capture_check(c, s, D); },
+                     [&](Workspace* w, hipStream_t s) -> int32_t {
+                       PVW_TRY(ws_share_buffer(c, w));
+                       deal_mark(w, D);
+                       return encrypt_multi_enqueue(c, w, nullptr, seeds, D, d_c1, d_c2, out_repr, s, rs, &deal);
+                     });
+}
+// host buffers: encrypt_multi_host's staging with the secrets in place of the scalars
+static int32_t deal_host(pvw_ctx* c, const uint64_t* secrets, size_t D, uint32_t degree, uint64_t p, const uint8_t* seeds,
+                         RndState* rs, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+  const size_t P = c->poly(), rA = c->rowsA(), rB = c->rowsB(), n = c->n;
+  size_t per = ((size_t)512 << 20) / ((rA + rB) * P * 8 + 8);
+  if (per < 4) per = 4;
+  per &= ~(size_t)3;
+  if (per > D) per = D;
+  Scratch sc;
+  const size_t r_se = sc.add(per * 8), r_c1 = sc.add(per * rA * P * 8), r_c2 = sc.add(per * rB * P * 8);
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    PVW_TRY(ws_share_buffer(c, w));
+    sc.secret(w, r_se, r_se);
+    deal_mark(w, D);
+    u64 *d_se = sc.at(r_se), *d_c1 = sc.at(r_c1), *d_c2 = sc.at(r_c2);
+    for (size_t d0 = 0; d0 < D; d0 += per) {
+      const size_t cnt = (D - d0) < per ? (D - d0) : per;
+      PVW_HIP(hipMemcpyAsync(d_se, secrets + d0, cnt * 8, hipMemcpyHostToDevice, w->stream));
+      const ShamirDeal deal{d_se, nullptr, degree, shamir_mod(p)};
+      PVW_TRY(encrypt_multi_enqueue(c, w, nullptr, seeds ? seeds + d0 * 32 : nullptr, cnt, d_c1, d_c2, out_repr, w->stream, rs, &deal));
+      for (size_t d = 0; d < cnt; ++d) {
+        PVW_HIP(hipMemcpyAsync(c1_out + ((d0 + d) * c->k + c->c1_lo) * P, d_c1 + d * rA * P, rA * P * 8, hipMemcpyDeviceToHost, w->stream));
+        PVW_HIP(hipMemcpyAsync(c2_out + ((d0 + d) * n + c->party_lo) * P, d_c2 + d * rB * P, rB * P * 8, hipMemcpyDeviceToHost, w->stream));
+      }
+      if (d0 + cnt < D) PVW_HIP(hipStreamSynchronize(w->stream));   // the next pass reuses the pageable staging
+    }
+    return PVW_OK;
+  });
+}
+
+int32_t pvw_deal_shares_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t degree, uint64_t plain_modulus,
+                               const uint8_t* seeds, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
+  if (!c || !d_secrets || !seeds || (!d_c1 && c->rowsA()) || (!d_c2 && c->rowsB())) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(encrypt_multi_checks(c, num_dealers, c->n, out_repr));
+  PVW_TRY(shamir_checks(c, num_dealers, degree, plain_modulus));
+  return deal_device(c, d_secrets, num_dealers, degree, plain_modulus, seeds, nullptr, d_c1, d_c2, out_repr, stream);
+}
+int32_t pvw_deal_shares(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t degree, uint64_t plain_modulus,
+                        const uint8_t* seeds, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+  if (!c || !secrets || !seeds || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(encrypt_multi_checks(c, num_dealers, c->n, out_repr));
+  PVW_TRY(shamir_checks(c, num_dealers, degree, plain_modulus));
+  PVW_TRY(ensure_device(c));
+  return deal_host(c, secrets, num_dealers, degree, plain_modulus, seeds, nullptr, c1_out, c2_out, out_repr);
+}
+int32_t pvw_deal_shares_rs_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t degree, uint64_t plain_modulus,
+                                  void* handle, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
+  pvw_rnd_state* st = (pvw_rnd_state*)handle;
+  if (!c || !d_secrets || !st || (!d_c1 && c->rowsA()) || (!d_c2 && c->rowsB())) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(encrypt_multi_checks(c, num_dealers, c->n, out_repr));
+  PVW_TRY(shamir_checks(c, num_dealers, degree, plain_modulus));
+  PVW_TRY(ensure_device(c));
+  PVW_TRY(rnd_state_checks(c, st));
+  return deal_device(c, d_secrets, num_dealers, degree, plain_modulus, nullptr, st->dev, d_c1, d_c2, out_repr, stream);
+}
+int32_t pvw_deal_shares_rs(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t degree, uint64_t plain_modulus,
+                           void* handle, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+  pvw_rnd_state* st = (pvw_rnd_state*)handle;
+  if (!c || !secrets || !st || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(encrypt_multi_checks(c, num_dealers, c->n, out_repr));
+  PVW_TRY(shamir_checks(c, num_dealers, degree, plain_modulus));
+  PVW_TRY(ensure_device(c));
+  PVW_TRY(rnd_state_checks(c, st));
+  return deal_host(c, secrets, num_dealers, degree, plain_modulus, nullptr, st->dev, c1_out, c2_out, out_repr);
 }
 
 // ------------------------------------------------------------------------ decode (host, integers)

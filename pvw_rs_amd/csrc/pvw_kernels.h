@@ -220,6 +220,25 @@ inline size_t ct_sum_partial_items_max() { return (size_t)(1024 + 512) * 256; } 
 hipError_t launch_ct_sum(const SumRegion& a, const SumRegion& b, const unsigned char* valid, size_t dealers, const DevTables& t, u32 L,
                          u32 ell, u64* partial, u32 nslices, bool accumulate, u32* count, hipStream_t s);
 
+// ---- Shamir shares (pvw_shamir.hip): shares[d * row_stride + i] = f_d(i + 1) mod m.q for the dealers of the batch
+// and the parties i of [party_lo, party_hi); f_d = secrets[d] + sum_{j=1..degree} a_{d,j} x^j.  a_{d,j} = coeffs[d * degree + j - 1]
+// (any word, read mod m.q), or with coeffs == NULL the first accepted draw of the ChaCha8 stream (key of dealer d,
+// (DOM_SHAMIR << 32) | j).  Dealer d's key is key[d], or with rnd != NULL call_seed(S, counter + rnd_off + d), derived when the
+// kernel runs (the kernel does not write the state).  nd <= PVW_MAX_PROLOGUE_KEYS; m.q prime, party_hi < m.q < 2^62.
+enum { DOM_SHAMIR = 9 };
+struct ShamirBatch {
+  const u64* secrets;   // [nd] device words, read mod m.q
+  const u64* coeffs;    // [nd][degree] device words, or NULL: drawn
+  u64* shares;
+  size_t row_stride;    // words between consecutive dealers' rows (columns are GLOBAL party indices)
+  u32 nd, degree, party_lo, party_hi;
+  Mod m;
+  ChaChaKey key[PVW_MAX_PROLOGUE_KEYS];
+  const RndState* rnd;
+  u64 rnd_off;
+};
+hipError_t launch_shamir_eval(const ShamirBatch& b, hipStream_t s);
+
 // p[0 .. words) = 0, as a kernel launch on s
 hipError_t launch_wipe_words(u64* p, size_t words, hipStream_t s);
 

@@ -607,6 +607,66 @@ inline SumInputs sum_inputs(const std::vector<PvwCiphertext>& cts, const std::ve
   for (bool v : valid) in.valid.push_back(v ? 1 : 0);
   return in;
 }
+// ---- Shamir shares ----
+// shares[d][i] = f_d(i + 1) mod plain_modulus for dealer d's polynomial of `degree` with constant term secrets[d]; its other
+// coefficients are drawn from seeds[d] (stream (PVW_DOM_SHAMIR << 32) | j) or given as coeffs [D][degree].  Row-major (D, n).
+// On the device (pvw_shamir_shares); host = true: the plain C++ restatement (pvw_shamir_shares_host, no GPU).
+inline std::vector<uint64_t> shamir_shares(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& secrets, uint32_t degree,
+                                           uint64_t plain_modulus, const std::vector<Seed>& seeds,
+                                           const std::vector<uint64_t>& coeffs = {}, bool host = false) {
+  const size_t D = secrets.size();
+  if (!seeds.empty() && seeds.size() != D) throw PvwError(15, "one seed per dealer");
+  if (!coeffs.empty() && coeffs.size() != D * degree) throw PvwError(15, "degree coefficients per dealer");
+  std::vector<uint8_t> sd(seeds.size() * 32);
+  for (size_t d = 0; d < seeds.size(); ++d) std::copy(seeds[d].begin(), seeds[d].end(), sd.begin() + d * 32);
+  std::vector<uint64_t> out(D * p->n);
+  const uint8_t* sdp = sd.empty() ? nullptr : sd.data();
+  const uint64_t* cop = coeffs.empty() ? nullptr : coeffs.data();
+  check(host ? pvw_shamir_shares_host(p->ctx, secrets.data(), D, degree, plain_modulus, sdp, cop, out.data())
+             : pvw_shamir_shares(p->ctx, secrets.data(), D, degree, plain_modulus, sdp, cop, out.data()));
+  return out;
+}
+inline std::vector<PvwCiphertext> deal_ciphertexts(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& c1,
+                                                   const std::vector<uint64_t>& c2, size_t D, uint32_t repr) {
+  const size_t n = p->n, P = p->poly_words();
+  std::vector<PvwCiphertext> out;
+  for (size_t d = 0; d < D; ++d)
+    out.push_back(PvwCiphertext{std::vector<uint64_t>(c1.begin() + d * p->k * P, c1.begin() + (d + 1) * p->k * P),
+                                std::vector<uint64_t>(c2.begin() + d * n * P, c2.begin() + (d + 1) * n * P), p, repr});
+  return out;
+}
+// dealer d shares secrets[d] among the n parties and encrypts the shares in ONE device call (pvw_deal_shares): what
+// encrypt of shamir_shares(...) under the same seeds returns, without the shares or coefficients existing on the host
+inline std::vector<PvwCiphertext> deal_party_shares(const std::vector<uint64_t>& secrets, uint32_t degree, uint64_t plain_modulus,
+                                                    const GlobalPublicKey& gpk, const std::vector<Seed>& seeds,
+                                                    uint32_t out_repr = PVW_REPR_NTT) {
+  const auto& p = gpk.params;
+  const size_t D = secrets.size(), P = p->poly_words();
+  if (seeds.size() != D) throw PvwError(15, "one seed per dealer");
+  std::vector<uint8_t> sd(D * 32);
+  for (size_t d = 0; d < D; ++d) std::copy(seeds[d].begin(), seeds[d].end(), sd.begin() + d * 32);
+  std::vector<uint64_t> c1(D * p->k * P), c2(D * p->n * P);
+  check(pvw_deal_shares(p->ctx, secrets.data(), D, degree, plain_modulus, sd.data(), c1.data(), c2.data(), out_repr));
+  return deal_ciphertexts(p, c1, c2, D, out_repr);
+}
+// ... with dealer d's randomness (polynomial and encryption) from call_seed(S, c + d) of a DeviceRandomness
+inline std::vector<PvwCiphertext> deal_party_shares(const std::vector<uint64_t>& secrets, uint32_t degree, uint64_t plain_modulus,
+                                                    const GlobalPublicKey& gpk, DeviceRandomness& rnd, uint32_t out_repr = PVW_REPR_NTT) {
+  const auto& p = gpk.params;
+  const size_t D = secrets.size(), P = p->poly_words();
+  std::vector<uint64_t> c1(D * p->k * P), c2(D * p->n * P);
+  check(pvw_deal_shares_rs(p->ctx, secrets.data(), D, degree, plain_modulus, rnd.raw(), c1.data(), c2.data(), out_repr));
+  return deal_ciphertexts(p, c1, c2, D, out_repr);
+}
+// the secrets from the shares of the parties `indices` (at least degree + 1): shares [num_secrets][indices.size()], row-major
+inline std::vector<uint64_t> shamir_reconstruct(const std::vector<uint64_t>& indices, const std::vector<uint64_t>& shares,
+                                                uint64_t plain_modulus) {
+  if (indices.empty() || shares.size() % indices.size()) throw PvwError(15, "shares must hold one value per index and secret");
+  std::vector<uint64_t> out(shares.size() / indices.size());
+  check(pvw_shamir_reconstruct(plain_modulus, indices.data(), shares.data(), indices.size(), out.size(), out.data()));
+  return out;
+}
+
 // the sum of the valid dealers' ciphertexts (pvw_ct_sum): same parameters and representation, no key needed
 inline PvwCiphertext aggregate_ciphertexts(const std::vector<PvwCiphertext>& cts, const std::vector<bool>& valid = {}) {
   const SumInputs in = sum_inputs(cts, valid);

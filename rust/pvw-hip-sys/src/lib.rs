@@ -98,6 +98,7 @@ pub const PVW_DOM_CRS: u32 = 5;
 pub const PVW_DOM_GAUSS: u32 = 6;
 pub const PVW_DOM_PK: u32 = 7;
 pub const PVW_DOM_CALL: u32 = 8;
+pub const PVW_DOM_SHAMIR: u32 = 9;
 
 extern "C" {
     // ---- errors / device ------------------------------------------------------------------
@@ -146,6 +147,15 @@ extern "C" {
     pub fn pvw_encrypt_rs_device(ctx: *mut PvwCtx, d_scalars: *const u64, num_scalars: usize, st: *mut c_void, d_c1: *mut u64, d_c2: *mut u64, out_repr: u32, stream: *mut c_void) -> i32;
     pub fn pvw_encrypt_multi_rs(ctx: *mut PvwCtx, scalars: *const u64, num_dealers: usize, scalars_per_dealer: usize, st: *mut c_void, c1_out: *mut u64, c2_out: *mut u64, out_repr: u32) -> i32;
     pub fn pvw_encrypt_multi_rs_device(ctx: *mut PvwCtx, d_scalars: *const u64, num_dealers: usize, scalars_per_dealer: usize, st: *mut c_void, d_c1: *mut u64, d_c2: *mut u64, out_repr: u32, stream: *mut c_void) -> i32;
+    // ---- Shamir shares ------------------------------------------------------------
+    pub fn pvw_shamir_shares_host(ctx: *const PvwCtx, secrets: *const u64, num_dealers: usize, degree: u32, plain_modulus: u64, seeds: *const u8, coeffs: *const u64, shares_out: *mut u64) -> i32;
+    pub fn pvw_shamir_shares_device(ctx: *mut PvwCtx, d_secrets: *const u64, num_dealers: usize, degree: u32, plain_modulus: u64, seeds: *const u8, d_coeffs: *const u64, d_shares: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_shares(ctx: *mut PvwCtx, secrets: *const u64, num_dealers: usize, degree: u32, plain_modulus: u64, seeds: *const u8, coeffs: *const u64, shares_out: *mut u64) -> i32;
+    pub fn pvw_deal_shares(ctx: *mut PvwCtx, secrets: *const u64, num_dealers: usize, degree: u32, plain_modulus: u64, seeds: *const u8, c1_out: *mut u64, c2_out: *mut u64, out_repr: u32) -> i32;
+    pub fn pvw_deal_shares_device(ctx: *mut PvwCtx, d_secrets: *const u64, num_dealers: usize, degree: u32, plain_modulus: u64, seeds: *const u8, d_c1: *mut u64, d_c2: *mut u64, out_repr: u32, stream: *mut c_void) -> i32;
+    pub fn pvw_deal_shares_rs(ctx: *mut PvwCtx, secrets: *const u64, num_dealers: usize, degree: u32, plain_modulus: u64, st: *mut c_void, c1_out: *mut u64, c2_out: *mut u64, out_repr: u32) -> i32;
+    pub fn pvw_deal_shares_rs_device(ctx: *mut PvwCtx, d_secrets: *const u64, num_dealers: usize, degree: u32, plain_modulus: u64, st: *mut c_void, d_c1: *mut u64, d_c2: *mut u64, out_repr: u32, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_reconstruct(plain_modulus: u64, indices: *const u64, shares: *const u64, count: usize, num_secrets: usize, out: *mut u64) -> i32;
     // ---- decrypt (src/crypto/decryption.rs:249-325) and gadget decode (:10-247) ---------------
     pub fn pvw_decrypt_batch(ctx: *mut PvwCtx, sk: *const i64, c1s: *const u64, c2col: *const u64, num_dealers: usize, in_repr: u32, out_u64: *mut u64, noisy_out: *mut u64) -> i32;
     pub fn pvw_decrypt_noisy_device(ctx: *mut PvwCtx, d_sk: *const i64, d_c1s: *const u64, d_c2col: *const u64, num_dealers: usize, in_repr: u32, d_noisy: *mut u64, stream: *mut c_void) -> i32;

@@ -425,6 +425,64 @@ fn valid_ptr(valid: &[u8]) -> *const u8 {
     if valid.is_empty() { std::ptr::null() } else { valid.as_ptr() }
 }
 
+/// EXTENSION: dealer d shares `secrets[d]` among the n parties with a random polynomial of `degree` over
+/// Z_`plain_modulus` (prime, n < p < 2^62) and encrypts the shares, in ONE device call (`pvw_deal_shares`): neither the
+/// shares nor the coefficients exist on the host.  Each dealer's seed comes from `thread_rng` and is cleared afterwards.
+pub fn deal_party_shares(secrets: &[u64], degree: u32, plain_modulus: u64, global_pk: &GlobalPublicKey) -> Result<Vec<PvwCiphertext>> {
+    let params = &global_pk.params;
+    let (n, dealers) = (params.n, secrets.len());
+    let words = poly_words(params);
+    let mut seeds = vec![0u8; 32 * dealers];
+    rand::thread_rng().fill_bytes(&mut seeds);
+    let (mut c1, mut c2) = (vec![0u64; dealers * params.k * words], vec![0u64; dealers * n * words]);
+    let rc = unsafe {
+        sys::pvw_deal_shares(params.hip.raw(), secrets.as_ptr(), dealers, degree, plain_modulus, seeds.as_ptr(), c1.as_mut_ptr(), c2.as_mut_ptr(),
+                             sys::PVW_REPR_POWER)
+    };
+    seeds.zeroize();
+    check(rc)?;
+    (0..dealers)
+        .map(|d| ciphertext_from_flat(&c1[d * params.k * words..(d + 1) * params.k * words], &c2[d * n * words..(d + 1) * n * words], params))
+        .collect()
+}
+
+/// `deal_party_shares` with dealer d's randomness drawn from a `DeviceRandomness` (`call_seed(S, c + d)`).
+pub fn deal_party_shares_with(secrets: &[u64], degree: u32, plain_modulus: u64, global_pk: &GlobalPublicKey, rnd: &DeviceRandomness) -> Result<Vec<PvwCiphertext>> {
+    let params = &global_pk.params;
+    let (n, dealers) = (params.n, secrets.len());
+    let words = poly_words(params);
+    let (mut c1, mut c2) = (vec![0u64; dealers * params.k * words], vec![0u64; dealers * n * words]);
+    check(unsafe {
+        sys::pvw_deal_shares_rs(params.hip.raw(), secrets.as_ptr(), dealers, degree, plain_modulus, rnd.raw(), c1.as_mut_ptr(), c2.as_mut_ptr(),
+                                sys::PVW_REPR_POWER)
+    })?;
+    (0..dealers)
+        .map(|d| ciphertext_from_flat(&c1[d * params.k * words..(d + 1) * params.k * words], &c2[d * n * words..(d + 1) * n * words], params))
+        .collect()
+}
+
+/// EXTENSION: the shares themselves, `[dealers][n]` row-major, made on the device (`pvw_shamir_shares`) from
+/// one 32-byte seed per dealer, or from explicit coefficients `[dealers][degree]`.
+pub fn shamir_shares(params: &Arc<PvwParameters>, secrets: &[u64], degree: u32, plain_modulus: u64, seeds: Option<&[u8]>, coeffs: Option<&[u64]>) -> Result<Vec<u64>> {
+    let mut out = vec![0u64; secrets.len() * params.n];
+    check(unsafe {
+        sys::pvw_shamir_shares(params.hip.raw(), secrets.as_ptr(), secrets.len(), degree, plain_modulus,
+                               seeds.map_or(std::ptr::null(), |s| s.as_ptr()), coeffs.map_or(std::ptr::null(), |c| c.as_ptr()), out.as_mut_ptr())
+    })?;
+    Ok(out)
+}
+
+/// EXTENSION: the secrets from the shares of the parties `indices` (at least degree + 1 of them):
+/// `shares` is `[num_secrets][indices.len()]` row-major.  Host only (`pvw_shamir_reconstruct`).
+pub fn shamir_reconstruct(indices: &[u64], shares: &[u64], plain_modulus: u64) -> Result<Vec<u64>> {
+    if indices.is_empty() || shares.len() % indices.len() != 0 {
+        return Err(PvwError::InvalidParameters("shares must hold one value per index and secret".into()));
+    }
+    let mut out = vec![0u64; shares.len() / indices.len()];
+    check(unsafe { sys::pvw_shamir_reconstruct(plain_modulus, indices.as_ptr(), shares.as_ptr(), indices.len(), out.len(), out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
 /// EXTENSION: the sum of the valid dealers' ciphertexts (`pvw_ct_sum`) -- a ciphertext of the sum of their
 /// shares under the same keys, folded without any key.  What examples/pvw_valid_dec.rs:150-209 reaches by decrypting every
 /// dealer's share and adding the results; the noise of the sum is the sum of the dealers' noises (`pvw_ctx_sum_capacity`).
