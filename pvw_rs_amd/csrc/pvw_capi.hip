@@ -553,9 +553,15 @@ static int32_t ws_grow(u64** buf, size_t* have, size_t need, hipStream_t s, bool
   *have = need;
   return PVW_OK;
 }
+// The staging budget of the host-buffer calls: the bytes one staged piece may take on the device, 1 GiB.  Every bound below
+// is a multiple of it (tuning build: PVW_STAGE_BYTES, read per call, so that the tests take several pieces at small shapes).
+static size_t stage_budget() {
+  const long b = PVW_ENV_INT("PVW_STAGE_BYTES", 0);
+  return b > 0 ? (size_t)b : (size_t)1 << 30;
+}
 // items (dealers' ciphertext words, rows) per staged piece of at most 1 GiB: at least one, at most `most`
 static size_t chunk_1gib(size_t item_bytes, size_t most) {
-  const size_t per = ((size_t)1 << 30) / item_bytes;
+  const size_t per = stage_budget() / item_bytes;
   return per == 0 ? 1 : (per < most ? per : most);
 }
 static void ws_free(Workspace* w) {
@@ -2003,7 +2009,7 @@ static int32_t encrypt_multi_host(pvw_ctx* c, const uint64_t* scalars, size_t nu
                                   uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
   const size_t P = c->poly(), rA = c->rowsA(), rB = c->rowsB(), n = c->n;
   // dealers per pass: bounded staging (<= ~512 MiB of ciphertext)
-  size_t per = ((size_t)512 << 20) / ((rA + rB) * P * 8 + n * 8);
+  size_t per = stage_budget() / 2 / ((rA + rB) * P * 8 + n * 8);
   if (per < 4) per = 4;
   per &= ~(size_t)3;
   if (per > num_dealers) per = num_dealers;
@@ -2378,7 +2384,7 @@ static int32_t deal_device(pvw_ctx* c, const uint64_t* d_secrets, size_t D, uint
 static int32_t deal_host(pvw_ctx* c, const uint64_t* secrets, size_t D, uint32_t degree, uint64_t p, const uint8_t* seeds,
                          RndState* rs, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
   const size_t P = c->poly(), rA = c->rowsA(), rB = c->rowsB(), n = c->n;
-  size_t per = ((size_t)512 << 20) / ((rA + rB) * P * 8 + 8);
+  size_t per = stage_budget() / 2 / ((rA + rB) * P * 8 + 8);
   if (per < 4) per = 4;
   per &= ~(size_t)3;
   if (per > D) per = D;
@@ -2388,7 +2394,8 @@ static int32_t deal_host(pvw_ctx* c, const uint64_t* secrets, size_t D, uint32_t
     PVW_TRY(sc.take(w));
     PVW_TRY(ws_share_buffer(c, w));
     sc.secret(w, r_se, r_se);
-    deal_mark(w, D);
+    deal_mark(w, per);                                           // each pass takes the matrix cores or the VALU by its OWN dealer
+    if (D % per) deal_mark(w, D % per);                          // count: a last pass of 1 or 2 leaves r-hat in the workspace
     u64 *d_se = sc.at(r_se), *d_c1 = sc.at(r_c1), *d_c2 = sc.at(r_c2);
     for (size_t d0 = 0; d0 < D; d0 += per) {
       const size_t cnt = (D - d0) < per ? (D - d0) : per;
@@ -3184,11 +3191,11 @@ static AllLayout decrypt_all_layout(const pvw_ctx* c, size_t NP, size_t D, bool 
   // Dealers in groups of up to 128 (one gemm_digits launch each; c1 of the group reduced and digitised once per party chunk,
   // <= 1 GiB with its digit tiles), parties in chunks that keep the rest below 3 GiB.
   size_t Dg = D < 128 ? D : 128;
-  while (Dg > 1 && Dg * ctw * 72 > ((size_t)1 << 30)) Dg /= 2;     // c1 copy (8 bytes a word) + digit tiles (64)
+  while (Dg > 1 && Dg * ctw * 72 > stage_budget()) Dg /= 2;     // c1 copy (8 bytes a word) + digit tiles (64)
   const size_t nbg = (Dg + 15) / 16;
   a.direct = l <= 32;                                              // s-hat straight into the tiled operand (shat_mftile)
   const size_t per_party = ctw * 8 * (a.direct ? 1 : 2) + nbg * 16 * P * 8 + Dg * P * 8 * (stage ? 2 : 1) + Dg * 8 + (host ? (size_t)k * l * 8 : 0);
-  size_t Pc = ((size_t)3 << 30) / per_party;
+  size_t Pc = 3 * stage_budget() / per_party;
   if (Pc >= NP) Pc = NP;
   else if (Pc >= PVW_GEMM_ROWS_PER_WG) Pc -= Pc % PVW_GEMM_ROWS_PER_WG;   // whole workgroups of GEMM rows
   if (Pc == 0) Pc = 1;

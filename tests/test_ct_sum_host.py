@@ -38,10 +38,11 @@ def test_both_libraries_export_the_entry_points():
 
 
 def test_the_shipped_library_has_no_split_switch():
+    # ... nor the staging budget of the host-buffer calls (tests/test_gpu_staged_pieces.py shrinks it in the tuning build)
     s = subprocess.run(["strings", "-a", _ffi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert "PVW_SUM_SPLIT" not in s
+    assert "PVW_SUM_SPLIT" not in s and "PVW_STAGE_BYTES" not in s
     s = subprocess.run(["strings", "-a", _ffi.LIB_TUNING_PATH], capture_output=True, text=True, check=True).stdout
-    assert "PVW_SUM_SPLIT" in s
+    assert "PVW_SUM_SPLIT" in s and "PVW_STAGE_BYTES" in s
 
 
 # ---- pvw_ct_sum_host against Python integers ------------------------------------------------------------------------
