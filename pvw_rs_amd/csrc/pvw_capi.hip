@@ -52,6 +52,14 @@ static int32_t fail(int32_t code, const std::string& msg) {
     if (rc_ != PVW_OK) return rc_; \
   } while (0)
 
+// a stream under capture takes no allocation and no wait
+static bool stream_capturing(hipStream_t s) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  const bool capturing = hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+  (void)hipGetLastError();
+  return capturing;
+}
+
 // ------------------------------------------------------------------------ number theory (host)
 static bool is_prime_u64(u64 n) {
   if (n < 2) return false;
@@ -161,7 +169,6 @@ static void ws_mark_secret(Workspace* w, void* p, size_t bytes, bool cleared = f
 // marked: nothing enqueued, and the record of the last wipe stays
 // Under stream capture the wipes are kernels, not memset nodes: a captured call has to clear its regions on every replay, in
 // order (pvw_selftest_secret_residue after a replay found regions cleared by memset nodes not cleared).
-static bool stream_capturing(hipStream_t s);
 static hipError_t ws_wipe_secrets(Workspace* w, hipStream_t s) {
   if (w->secrets.empty()) return hipSuccess;
   hipError_t rc = hipSuccess;
@@ -715,6 +722,57 @@ struct Report {
   }
 };
 
+// A device randomness state's handle (pvw_rnd_state_create, further down): it records the device and the stream of the context
+// it was created for and never reads the context again.
+struct pvw_rnd_state {
+  int device;
+  hipStream_t stream;   // the creating context's stream: NULL stream arguments and the clearing in pvw_rnd_state_free
+  RndState* dev;
+};
+// after the argument checks of the call (the handle itself is not read before them)
+static int32_t rnd_state_checks(const pvw_ctx* c, const pvw_rnd_state* st) {
+  if (!st->dev) return fail(PVW_ERR_INVALID_PARAMETERS, "randomness state has been freed");
+  if (c->rowsA() == 0 && c->rowsB() == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "the context holds no rows to encrypt");
+  if (c->device >= 0 && st->device != c->device) return fail(PVW_ERR_INVALID_PARAMETERS, "the randomness state lives on another device");
+  return PVW_OK;
+}
+
+// Where the dealers of an encrypt get their keys: dealer i of this value has host seed seeds[first + i] (32 bytes each), or
+// call_seed(S, counter + first + i) of a device state, drawn when the kernels run.  An entry point builds it from its argument
+// without reading the handle; checks() is the handle's first read.
+struct DealerKeys {
+  const uint8_t* seeds = nullptr;
+  const pvw_rnd_state* st = nullptr;
+  bool by_state = false;
+  u64 first = 0;
+  static DealerKeys host(const uint8_t* seeds) { return DealerKeys{seeds, nullptr, false, 0}; }
+  static DealerKeys state(const void* handle) { return DealerKeys{nullptr, (const pvw_rnd_state*)handle, true, 0}; }
+  bool missing() const { return by_state ? !st : !seeds; }
+  int32_t checks(const pvw_ctx* c) const { return by_state ? rnd_state_checks(c, st) : (int32_t)PVW_OK; }
+  // the state, for the counter advance that the last kernel of a call performs; NULL with host seeds
+  RndState* state() const { return by_state ? st->dev : nullptr; }
+  // the same source starting i dealers further on
+  DealerKeys from(size_t i) const {
+    DealerKeys k = *this;
+    k.first += i;
+    return k;
+  }
+  // ... for the staged piece of a host-buffer call that starts at dealer i: the pieces in front of it have advanced the
+  // state's counter past their dealers, so only host seeds move on
+  DealerKeys piece(size_t i) const { return by_state ? *this : from(i); }
+  // the keys of dealers [0, count) into a kernel-side batch (PrologueBatch, GemmErrSource, ShamirBatch): count keys, or
+  // the state and the offset of its first dealer
+  template <class Batch>
+  void fill(Batch& b, u32 count) const {
+    if (by_state) {
+      b.rnd = st->dev;
+      b.rnd_off = first;
+    } else {
+      for (u32 x = 0; x < count; ++x) b.key[x] = make_key(seeds + (first + x) * 32);
+    }
+  }
+};
+
 // the helper stream and at least `events` events, for a call that runs on two streams
 static int32_t ws_aux(Workspace* w, size_t events) {
   if (!w->aux) PVW_HIP(hipStreamCreateWithFlags(&w->aux, hipStreamNonBlocking));
@@ -746,14 +804,54 @@ static int32_t host_call(pvw_ctx* c, Body&& body) {
   return rc;
 }
 
-// device-pointer calls: the caller's stream (NULL: the context's) and its workspace; dealers != 0: a multi-dealer encrypt,
-// checked against stream capture before the workspace is looked up
+// multi-dealer encrypt: the VALU below this many dealers, the matrix cores from it on
+static bool multi_uses_gemm(size_t D) {
+  const int gemm_min = (int)PVW_ENV_INT("PVW_GEMM_MIN_DEALERS", 3);   // tuning build: read per call (tests switch it); measured at config 3: 2 dealers 0.23 ms on the VALU vs 0.25 here, 4 dealers 0.43 vs 0.26, 6 dealers 0.67 vs 0.31
+  return gemm_min > 0 && D >= (size_t)gemm_min;
+}
+// A device-pointer multi-dealer call made under stream capture may not allocate or wait: on the matrix cores it needs the
+// MFMA copies and the stream's GEMM buffers that pvw_prepare(PVW_PREPARE_MFMA) builds.  Checked before the stream's workspace
+// is looked up (a first call on a stream would allocate it) and before anything is enqueued, so the capture stays intact.
+static int32_t multi_capture_check(pvw_ctx* c, hipStream_t s, size_t D) {
+  if (!multi_uses_gemm(D) || !stream_capturing(s)) return PVW_OK;
+  bool ready;
+  {
+    std::lock_guard<std::mutex> g(c->init_mu);
+    ready = c->xm_valid;
+  }
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    auto it = c->async_ws.find((void*)s);
+    const Workspace* w = it == c->async_ws.end() ? nullptr : it->second;
+    ready = ready && w && w->vhat16 && w->yd && w->sy && (w->gtmpA || !c->rowsA()) && (w->gtmpB || !c->rowsB());
+  }
+  if (!ready)
+    return fail(PVW_ERR_INVALID_PARAMETERS, "multi-dealer encrypt under stream capture: call pvw_prepare(PVW_PREPARE_MFMA) on "
+                                            "this stream first (and again after the matrices change)");
+  return PVW_OK;
+}
+
+// Under stream capture a deal may not allocate: the share scratch is built with the digit buffers by pvw_prepare(PVW_PREPARE_MFMA),
+// whatever the dealer count (checked before the stream's workspace is looked up, like multi_capture_check)
+static int32_t deal_capture_check(pvw_ctx* c, hipStream_t s, size_t D) {
+  if (!stream_capturing(s)) return PVW_OK;
+  bool ready;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    auto it = c->async_ws.find((void*)s);
+    ready = it != c->async_ws.end() && it->second->shares;
+  }
+  if (!ready)
+    return fail(PVW_ERR_INVALID_PARAMETERS, "multi-dealer encrypt under stream capture: call pvw_prepare(PVW_PREPARE_MFMA) on "
+                                            "this stream first (and again after the matrices change)");
+  return multi_capture_check(c, s, D);
+}
+
+// device-pointer calls: the caller's stream (NULL: the context's) and its workspace
 static hipStream_t call_stream(const pvw_ctx* c, void* stream) { return stream ? (hipStream_t)stream : c->stream; }
-static int32_t multi_capture_check(pvw_ctx* c, hipStream_t s, size_t D);
 static int32_t sum_prepare(pvw_ctx* c, Workspace* w, hipStream_t s);
-static int32_t device_ws(pvw_ctx* c, void* stream, hipStream_t* s, Workspace** w, size_t dealers = 0) {
+static int32_t device_ws(pvw_ctx* c, void* stream, hipStream_t* s, Workspace** w) {
   *s = call_stream(c, stream);
-  if (dealers) PVW_TRY(multi_capture_check(c, *s, dealers));
   return ws_for_stream(c, *s, w);
 }
 // the end of a device-pointer call that marked key material: nothing of a failed call stays queued; the regions are
@@ -767,9 +865,10 @@ static int32_t device_end(Workspace* w, hipStream_t s, int32_t rc) {
   return rc;
 }
 
-// Every device-pointer entry point that marks key material runs its body here, host_call's counterpart: on the caller's
-// stream and that stream's workspace, ended by device_end.  pre(s) runs BEFORE the workspace is looked up: the checks a call
-// made under stream capture has to pass before anything is allocated (sum_capture_check).
+// Every device-pointer entry point that marks key material, and every encrypt, runs its body here, host_call's counterpart:
+// on the caller's stream and that stream's workspace, ended by device_end (which enqueues nothing for a call that marked
+// nothing).  pre(s) runs BEFORE the workspace is looked up: the checks a call made under stream capture has to pass before
+// anything is allocated (sum_capture_check, multi_capture_check), and an encrypt's first read of its randomness handle.
 template <class Pre, class Body>
 static int32_t device_call(pvw_ctx* c, void* stream, Pre&& pre, Body&& body) {
   PVW_TRY(ensure_device(c));
@@ -1635,9 +1734,20 @@ int32_t pvw_host_free(void* p) {
 }
 
 // ------------------------------------------------------------------------ encrypt
-static int32_t encrypt_checks(pvw_ctx* c, size_t num_scalars, const pvw_randomness_t* rnd, uint32_t out_repr) {
+// explicit randomness of one encrypt: r [k][l], e1 [k][l], e2 [n][l] as GLOBAL arrays; all NULL: drawn from the dealer's key
+struct ExplicitRnd {
+  const i64 *r = nullptr, *e1 = nullptr, *e2 = nullptr;
+  static ExplicitRnd of(const pvw_randomness_t* rnd) {
+    return rnd && rnd->mode == PVW_RND_EXPLICIT ? ExplicitRnd{rnd->r, rnd->e1, rnd->e2} : ExplicitRnd{};
+  }
+};
+// a seed form's key source: the seed field of its pvw_randomness_t (NULL: encrypt_checks refuses the call)
+static DealerKeys seed_of(const pvw_randomness_t* rnd) { return DealerKeys::host(rnd ? rnd->seed : nullptr); }
+
+// rnd: the seed forms' argument; the _rs forms (keys.by_state) have none
+static int32_t encrypt_checks(pvw_ctx* c, size_t num_scalars, const pvw_randomness_t* rnd, const DealerKeys& keys, uint32_t out_repr) {
   PVW_TRY(check_repr(out_repr));
-  if (!rnd) return fail(PVW_ERR_INVALID_PARAMETERS, "randomness is NULL");
+  if (!keys.by_state && !rnd) return fail(PVW_ERR_INVALID_PARAMETERS, "randomness is NULL");
   if (num_scalars != c->n) {                                                        // encryption.rs:109-115
     char buf[96];
     snprintf(buf, sizeof buf, "Must provide exactly n=%u scalars, got %zu", c->n, num_scalars);
@@ -1650,6 +1760,7 @@ static int32_t encrypt_checks(pvw_ctx* c, size_t num_scalars, const pvw_randomne
   pvw_ctx_verify_correctness_condition(c, &ok);
   if (!ok)                                                                          // :124-128
     return fail(PVW_ERR_INVALID_PARAMETERS, "Parameters do not satisfy correctness condition - decryption may fail");
+  if (keys.by_state) return PVW_OK;
   if (rnd->mode == PVW_RND_EXPLICIT) {
     if (!rnd->r || (!rnd->e1 && c->rowsA()) || (!rnd->e2 && c->rowsB()))
       return fail(PVW_ERR_INVALID_PARAMETERS, "explicit randomness pointers are NULL");
@@ -1660,9 +1771,9 @@ static int32_t encrypt_checks(pvw_ctx* c, size_t num_scalars, const pvw_randomne
 }
 
 // the three polynomial families of one encrypt (encryption.rs:135-154 r, :161-167 e1, :195-196
-// encode + e2) as prologue jobs [3*slot, 3*slot+3) seeded by key `slot` of the batch:
+// encode + e2) as prologue jobs [3*slot, 3*slot+3) seeded by key `slot` of the batch, which the caller fills (DealerKeys::fill):
 // r -> r-hat [L][k][l]; NTT(e1) -> c1 rows; NTT(e2) + scalar*g-hat -> c2 rows (the MAC adds onto them)
-static int32_t fill_encrypt_jobs(pvw_ctx* c, PrologueBatch& pb, u32 slot, const pvw_randomness_t* rnd,
+static int32_t fill_encrypt_jobs(pvw_ctx* c, PrologueBatch& pb, u32 slot, const ExplicitRnd& ex,
                                  const u64* d_scalars, u64* rhat, u64* d_c1, u64* d_c2) {
   const u32 k = c->k, l = c->l;
   const size_t P = c->poly();
@@ -1674,34 +1785,25 @@ static int32_t fill_encrypt_jobs(pvw_ctx* c, PrologueBatch& pb, u32 slot, const 
   jr.sj.domain = DOM_R; jr.sj.index0 = 0; jr.sj.count = k;
   j1.sj.kind = SAMPLE_UNIFORM; j1.sj.domain = DOM_E1; j1.sj.index0 = c->c1_lo; j1.sj.count = c->rowsA(); j1.sj.bound = c->b1;
   j2.sj.kind = SAMPLE_UNIFORM; j2.sj.domain = DOM_E2; j2.sj.index0 = c->party_lo; j2.sj.count = c->rowsB(); j2.sj.bound = c->b2;
-  if (rnd->mode == PVW_RND_EXPLICIT) {
-    jr.explicit_coeffs = rnd->r;
-    j1.explicit_coeffs = rnd->e1 + (size_t)c->c1_lo * l;
-    j2.explicit_coeffs = rnd->e2 + (size_t)c->party_lo * l;
+  if (ex.r) {
+    jr.explicit_coeffs = ex.r;
+    j1.explicit_coeffs = ex.e1 + (size_t)c->c1_lo * l;
+    j2.explicit_coeffs = ex.e2 + (size_t)c->party_lo * l;
   }
   jr.out = rhat; jr.stride_poly = l; jr.stride_limb = (size_t)k * l;
   j1.out = d_c1; j1.stride_poly = P; j1.stride_limb = l;
   j2.out = d_c2; j2.stride_poly = P; j2.stride_limb = l; j2.scalars = d_scalars + c->party_lo;
   jr.key_idx = j1.key_idx = j2.key_idx = slot;
-  pb.key[slot] = make_key(rnd->seed);
   return PVW_OK;
-}
-
-static bool stream_capturing(hipStream_t s) {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  const bool capturing = hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-  (void)hipGetLastError();
-  return capturing;
 }
 
 // all pointers are device pointers; explicit r/e1/e2 are GLOBAL arrays ([k][l], [k][l], [n][l])
 // out_c1 / out_c2 != NULL: the MAC stores its results there (device-visible HOST memory of a caller whose buffers are
 // pinned) while the addends stay in d_c1 / d_c2; NTT-domain output only
-// rs != NULL: the randomness comes from that device state (rnd is then a PVW_RND_SEED placeholder whose seed is not read):
-// the prologue derives the key from it when it runs, and the MAC advances its counter by one
-static int32_t encrypt_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, const pvw_randomness_t* rnd,
-                               u64* d_c1, u64* d_c2, uint32_t out_repr, hipStream_t s, u64* out_c1 = nullptr, u64* out_c2 = nullptr,
-                               RndState* rs = nullptr) {
+// keys: dealer 0's seed, or a device state: the prologue derives the key from it when it runs, and the MAC advances its
+// counter by one
+static int32_t encrypt_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, const DealerKeys& keys, const ExplicitRnd& ex,
+                               u64* d_c1, u64* d_c2, uint32_t out_repr, hipStream_t s, u64* out_c1 = nullptr, u64* out_c2 = nullptr) {
   const u32 k = c->k, l = c->l, L = c->L, rA = c->rowsA(), rB = c->rowsB();
   if (!out_c1) out_c1 = d_c1;
   if (!out_c2) out_c2 = d_c2;
@@ -1709,8 +1811,8 @@ static int32_t encrypt_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, c
   // first call after a matrix change (and no pvw_prepare since): builds the packed copies -- allocates and synchronises
   const u32 width = ensure_packed(c, s, !stream_capturing(s));
   PrologueBatch pb{};
-  PVW_TRY(fill_encrypt_jobs(c, pb, 0, rnd, d_scalars, w->rhat, d_c1, d_c2));
-  pb.rnd = rs;
+  PVW_TRY(fill_encrypt_jobs(c, pb, 0, ex, d_scalars, w->rhat, d_c1, d_c2));
+  keys.fill(pb, 1);
   // l <= 16: the addends travel in COMPACT form -- the prologue transforms r only and leaves the sampled e1 / e2 coefficients as
   // they are (8 l bytes per row instead of 8 L l written and read back); the MAC workgroups transform their own rows' e and add
   // m g-hat (MacSection::e_small, mac_small_make).  Explicit randomness: the caller's e1 / e2 arrays ARE the compact form.
@@ -1719,7 +1821,7 @@ static int32_t encrypt_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, c
   const bool compact = l <= 16 && w->esmall && PVW_ENV_INT("PVW_MAC_COMPACT", 1) != 0;
   const i64 *es1 = nullptr, *es2 = nullptr;
   if (compact) {
-    if (rnd->mode == PVW_RND_EXPLICIT) {
+    if (ex.r) {
       es1 = pb.job[1].explicit_coeffs;
       es2 = pb.job[2].explicit_coeffs;
       pb.njobs = 1;                                   // r only
@@ -1745,7 +1847,7 @@ static int32_t encrypt_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, c
       b.e_small = es2;
       b.scalars = d_scalars + c->party_lo;
     }
-    if (rs) {
+    if (RndState* rs = keys.state()) {
       a.rnd_ctr = &rs->counter;                          // the prologue in front of this launch was the state's reader
       a.rnd_adv = 1;
     }
@@ -1767,20 +1869,26 @@ static int32_t encrypt_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, c
 // sets of (r-hat, addends) and one wait per stream and call: the prologue does run under the previous MAC (26 us there
 // instead of 11), but the MAC behind the cross-stream wait starts as late as it did behind the prologue: step = MAC +
 // 7.6-7.9 us against MAC + 7.8-8.3 us in order (same box, 183-184 us MACs).  Not kept.
-int32_t pvw_encrypt_device(pvw_ctx* c, const uint64_t* d_scalars, size_t num_scalars, const pvw_randomness_t* rnd,
-                           uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
-  if (!c || !d_scalars || (!d_c1 && c->rowsA()) || (!d_c2 && c->rowsB())) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(encrypt_checks(c, num_scalars, rnd, out_repr));
-  PVW_TRY(ensure_device(c));
-  hipStream_t s;
-  Workspace* w;
-  PVW_TRY(device_ws(c, stream, &s, &w));
-  return encrypt_enqueue(c, w, d_scalars, rnd, d_c1, d_c2, out_repr, s);
+
+// The two single-dealer frames.  rnd: the seed forms' argument, NULL in the _rs forms (a seed form's NULL rnd is not a "NULL
+// argument": encrypt_checks names it, behind the representation check).
+static int32_t encrypt_device(pvw_ctx* c, const uint64_t* d_scalars, size_t num_scalars, const pvw_randomness_t* rnd,
+                              const DealerKeys& keys, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
+  if (!c || !d_scalars || (keys.by_state && keys.missing()) || (!d_c1 && c->rowsA()) || (!d_c2 && c->rowsB()))
+    return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(encrypt_checks(c, num_scalars, rnd, keys, out_repr));
+  return device_call(c, stream, [&](hipStream_t) { return keys.checks(c); }, [&](Workspace* w, hipStream_t s) {
+    return encrypt_enqueue(c, w, d_scalars, keys, ExplicitRnd::of(rnd), d_c1, d_c2, out_repr, s);
+  });
 }
 
-// host buffers (pvw_encrypt, pvw_encrypt_rs): the scalars, and explicit randomness as global arrays, staged on the device
-static int32_t encrypt_host(pvw_ctx* c, const uint64_t* scalars, const pvw_randomness_t* rnd, RndState* rs, uint64_t* c1_out,
-                            uint64_t* c2_out, uint32_t out_repr) {
+// host buffers: the scalars, and explicit randomness as global arrays, staged on the device
+static int32_t encrypt_host(pvw_ctx* c, const uint64_t* scalars, size_t num_scalars, const pvw_randomness_t* rnd,
+                            const DealerKeys& keys, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+  if (!c || !scalars || (keys.by_state && keys.missing()) || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(encrypt_checks(c, num_scalars, rnd, keys, out_repr));
+  PVW_TRY(ensure_device(c));
+  PVW_TRY(keys.checks(c));
   const size_t l = c->l, k = c->k, P = c->poly();
   // Output buffers the device can write (pvw_host_alloc, or memory the caller pinned / registered): the MAC stores c1 / c2
   // straight into them, 64 bytes per (row, limb) as its workgroups finish -- the 4.7 MB of config 3 cross PCIe under the
@@ -1793,20 +1901,18 @@ static int32_t encrypt_host(pvw_ctx* c, const uint64_t* scalars, const pvw_rando
   }
   return host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(ws_host_buffers(c, w));
-    pvw_randomness_t dr = *rnd;
-    if (rnd->mode == PVW_RND_EXPLICIT) {
+    ExplicitRnd ex = ExplicitRnd::of(rnd);
+    if (ex.r) {
       PVW_TRY(ws_scratch(w, (2 * k + c->n) * l * 8));
       i64* base = (i64*)w->scratch;
-      PVW_HIP(hipMemcpyAsync(base, rnd->r, k * l * 8, hipMemcpyHostToDevice, w->stream));
-      PVW_HIP(hipMemcpyAsync(base + k * l, rnd->e1, k * l * 8, hipMemcpyHostToDevice, w->stream));
-      PVW_HIP(hipMemcpyAsync(base + 2 * k * l, rnd->e2, (size_t)c->n * l * 8, hipMemcpyHostToDevice, w->stream));
-      dr.r = base;
-      dr.e1 = base + k * l;
-      dr.e2 = base + 2 * k * l;
+      PVW_HIP(hipMemcpyAsync(base, ex.r, k * l * 8, hipMemcpyHostToDevice, w->stream));
+      PVW_HIP(hipMemcpyAsync(base + k * l, ex.e1, k * l * 8, hipMemcpyHostToDevice, w->stream));
+      PVW_HIP(hipMemcpyAsync(base + 2 * k * l, ex.e2, (size_t)c->n * l * 8, hipMemcpyHostToDevice, w->stream));
+      ex = ExplicitRnd{base, base + k * l, base + 2 * k * l};
     }
     PVW_HIP(hipMemcpyAsync(w->scalars, scalars, (size_t)c->n * 8, hipMemcpyHostToDevice, w->stream));
-    PVW_TRY(encrypt_enqueue(c, w, w->scalars, &dr, w->c1, w->c2, out_repr, w->stream, dir1 ? dir1 + (size_t)c->c1_lo * P : nullptr,
-                            dir2 ? dir2 + (size_t)c->party_lo * P : nullptr, rs));
+    PVW_TRY(encrypt_enqueue(c, w, w->scalars, keys, ex, w->c1, w->c2, out_repr, w->stream, dir1 ? dir1 + (size_t)c->c1_lo * P : nullptr,
+                            dir2 ? dir2 + (size_t)c->party_lo * P : nullptr));
     if (!dir1) {
       PVW_HIP(hipMemcpyAsync(c1_out + (size_t)c->c1_lo * P, w->c1, (size_t)c->rowsA() * P * 8, hipMemcpyDeviceToHost, w->stream));
       PVW_HIP(hipMemcpyAsync(c2_out + (size_t)c->party_lo * P, w->c2, (size_t)c->rowsB() * P * 8, hipMemcpyDeviceToHost, w->stream));
@@ -1815,373 +1921,24 @@ static int32_t encrypt_host(pvw_ctx* c, const uint64_t* scalars, const pvw_rando
   });
 }
 
-int32_t pvw_encrypt(pvw_ctx* c, const uint64_t* scalars, size_t num_scalars, const pvw_randomness_t* rnd,
-                    uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
-  if (!c || !scalars || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(encrypt_checks(c, num_scalars, rnd, out_repr));
-  PVW_TRY(ensure_device(c));
-  return encrypt_host(c, scalars, rnd, nullptr, c1_out, c2_out, out_repr);
+// The exports of one operation differ in their key source alone.  Every frame runs in this order, which the tests hold it to:
+// NULL arguments (the handle for NULL only), the argument checks, ensure_device, DealerKeys::checks (the first read of a
+// handle), then the workspace and the stream.
+int32_t pvw_encrypt_device(pvw_ctx* c, const uint64_t* d_scalars, size_t num_scalars, const pvw_randomness_t* rnd,
+                           uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
+  return encrypt_device(c, d_scalars, num_scalars, rnd, seed_of(rnd), d_c1, d_c2, out_repr, stream);
 }
-
-// ------------------------------------------------------------------------ multi-dealer encrypt
-static bool multi_uses_gemm(size_t D) {
-  const int gemm_min = (int)PVW_ENV_INT("PVW_GEMM_MIN_DEALERS", 3);   // tuning build: read per call (tests switch it); measured at config 3: 2 dealers 0.23 ms on the VALU vs 0.25 here, 4 dealers 0.43 vs 0.26, 6 dealers 0.67 vs 0.31
-  return gemm_min > 0 && D >= (size_t)gemm_min;
-}
-// A device-pointer multi-dealer call made under stream capture may not allocate or wait: on the matrix cores it needs the
-// MFMA copies and the stream's GEMM buffers that pvw_prepare(PVW_PREPARE_MFMA) builds.  Checked before the stream's workspace
-// is looked up (a first call on a stream would allocate it) and before anything is enqueued, so the capture stays intact.
-static int32_t multi_capture_check(pvw_ctx* c, hipStream_t s, size_t D) {
-  if (!multi_uses_gemm(D) || !stream_capturing(s)) return PVW_OK;
-  bool ready;
-  {
-    std::lock_guard<std::mutex> g(c->init_mu);
-    ready = c->xm_valid;
-  }
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    auto it = c->async_ws.find((void*)s);
-    const Workspace* w = it == c->async_ws.end() ? nullptr : it->second;
-    ready = ready && w && w->vhat16 && w->yd && w->sy && (w->gtmpA || !c->rowsA()) && (w->gtmpB || !c->rowsB());
-  }
-  if (!ready)
-    return fail(PVW_ERR_INVALID_PARAMETERS, "multi-dealer encrypt under stream capture: call pvw_prepare(PVW_PREPARE_MFMA) on "
-                                            "this stream first (and again after the matrices change)");
-  return PVW_OK;
-}
-
-// encrypt_all_party_shares (encryption.rs:253-286): dealer d encrypts scalars[d][0..n) with its own
-// randomness (seed d).  Groups of 4 dealers share one pass over A-hat / B-hat (mac_rows_multi).
-// Device layout: d_scalars [D][n]; d_c1 [D][rowsA][L][l]; d_c2 [D][rowsB][L][l].
-// rs != NULL: dealer d's seed is call_seed(S, c + d) of that device state instead of seeds + 32 d (seeds is not read), with
-// c the counter when the call's kernels run; the call's last kernel advances the counter by D.
-// deal != NULL (pvw_deal_shares*, DESIGN 8.9): d_scalars is not read; the scalars of each pass of dealers are their Shamir
-// shares, made into w->shares by shamir_enqueue in front of the pass (under the same seeds / state, domain DOM_SHAMIR).
-struct ShamirDeal {
-  const u64* d_secrets;   // [D]
-  const u64* d_coeffs;    // [D][degree], or NULL: drawn from the dealers' seeds
-  u32 degree;
-  Mod m;
-};
-static int32_t shamir_enqueue(pvw_ctx* c, const ShamirDeal& deal, const uint8_t* seeds, RndState* rs, u64 rnd_off, size_t D,
-                              u64* d_shares, hipStream_t s);
-static int32_t encrypt_multi_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, const uint8_t* seeds,
-                                     size_t D, u64* d_c1, u64* d_c2, uint32_t out_repr, hipStream_t s, RndState* rs = nullptr,
-                                     const ShamirDeal* deal = nullptr) {
-  const u32 k = c->k, l = c->l, L = c->L, rA = c->rowsA(), rB = c->rowsB();
-  const size_t P = c->poly();
-  const bool use_gemm = multi_uses_gemm(D);
-  if (use_gemm) {
-    PVW_TRY(ws_gemm_buffers(c, w));
-    PVW_TRY(ensure_xm(c, s));
-  }
-  const size_t group = use_gemm ? (size_t)16 * gemm_vb() : 4;
-  // matrix-core passes: the c2 finish pass draws e2 and encodes the scalars itself (tuning build: PVW_FUSED_E2=0 the prologue does)
-  const bool fused_e2 = use_gemm && l <= 32 && PVW_ENV_INT("PVW_FUSED_E2", 1) != 0;
-  u64* vh = use_gemm ? w->vhat16 : w->rhat;
-  for (size_t d0 = 0; d0 < D; d0 += group) {
-    const u32 nv = (u32)((D - d0) < group ? (D - d0) : group);
-    const u64* gsc = deal ? w->shares : d_scalars + d0 * c->n;   // the pass's scalars [nv][n]
-    if (deal) {
-      const ShamirDeal dd{deal->d_secrets + d0, deal->d_coeffs ? deal->d_coeffs + d0 * deal->degree : nullptr, deal->degree, deal->m};
-      PVW_TRY(shamir_enqueue(c, dd, seeds ? seeds + d0 * 32 : nullptr, rs, d0, nv, w->shares, s));
-    }
-    // prologue: the (r, e1, e2) families of dealer d0 replicated over the nv dealers of this pass (up to 64 keys
-    // per launch): r-hat_d -> vh[v], NTT(e1), NTT(e2) + m*g-hat -> output planes
-    for (u32 v0 = 0; v0 < nv; v0 += PVW_MAX_PROLOGUE_KEYS) {
-      const u32 cnt = (nv - v0) < PVW_MAX_PROLOGUE_KEYS ? (nv - v0) : PVW_MAX_PROLOGUE_KEYS;
-      const size_t d = d0 + v0;
-      PrologueBatch pb{};
-      pvw_randomness_t rnd{};
-      rnd.mode = PVW_RND_SEED;
-      if (!rs) memcpy(rnd.seed, seeds + d * 32, 32);
-      PVW_TRY(fill_encrypt_jobs(c, pb, 0, &rnd, gsc + (size_t)v0 * c->n, vh + (size_t)v0 * k * P,
-                                d_c1 + d * rA * P, d_c2 + d * rB * P));
-      if (rs) {
-        pb.rnd = rs;                                            // replica x: call_seed(S, counter + d + x)
-        pb.rnd_off = d;
-      } else {
-        for (u32 x = 0; x < cnt; ++x) pb.key[x] = make_key(seeds + (d + x) * 32);
-      }
-      pb.job[0].rep_key = pb.job[1].rep_key = pb.job[2].rep_key = 1;
-      pb.job[0].rep_out = (size_t)k * P;                       // r-hat vectors
-      pb.job[1].rep_out = (size_t)rA * P;                      // c1 planes
-      pb.job[2].rep_out = (size_t)rB * P;                      // c2 planes
-      pb.job[2].rep_scalars = c->n;
-      pb.njobs = fused_e2 ? 2 : 3;                              // fused: e2 + m g-hat are made by the c2 finish pass
-      pb.reps = cnt;
-      ProfScope ps(c, "prologue", s);
-      PVW_HIP(launch_prologue(pb, c->dt, L, l, s));
-    }
-    u64* c1g = d_c1 + d0 * rA * P;
-    u64* c2g = d_c2 + d0 * rB * P;
-    const bool last = d0 + nv == D;                             // its last kernel advances the randomness state
-    if (use_gemm) {
-      {
-        ProfScope ps(c, "vec_digits", s);
-        PVW_HIP(launch_vec_digits(vh, (size_t)k * P, w->yd, w->sy, nv, k, L, l, c->dt, s, 0, 0, c->xm_bytes));
-      }
-      ProfScope ps(c, "gemm_digits", s);
-      GemmSection a{c->xmA, c1g, c1g, w->gtmpA, rA, 0, 0}, b{c->xmB, c2g, c2g, w->gtmpB, rB, 0, 0};
-      std::vector<GemmErrSource> es;
-      if (fused_e2) {
-        // e2_d[i] (encryption.rs:195-196): dealer d's key, stream DOM_E2 / party index, uniform in [-b2, b2]; + m_{d,i} g-hat
-        for (u32 v0 = 0; v0 < nv; v0 += PVW_MAX_PROLOGUE_KEYS) {
-          GemmErrSource e{};
-          e.span = (nv - v0) < PVW_MAX_PROLOGUE_KEYS ? (nv - v0) : PVW_MAX_PROLOGUE_KEYS;
-          if (rs) {
-            e.rnd = rs;                                         // vector x: call_seed(S, base + d0 + v0 + x)
-            e.rnd_off = d0 + v0;
-          } else {
-            for (u32 x = 0; x < e.span; ++x) e.key[x] = make_key(seeds + (d0 + v0 + x) * 32);
-          }
-          e.key_v = 1;
-          e.domain = DOM_E2; e.index0 = c->party_lo; e.index_row = 1; e.index_v = 0; e.bound = c->b2;
-          e.scalars = gsc + c->party_lo; e.scalar_v = c->n;
-          es.push_back(e);
-        }
-        b.addend = nullptr;
-      }
-      if (rs && last) {
-        GemmSection& fin = rB ? b : a;                          // the finish pass launched last
-        fin.rnd_ctr = &rs->counter;
-        fin.rnd_adv = D;
-      }
-      PVW_HIP(launch_gemm_digits(a, b, w->yd, w->sy, c->dt, k, L, l, nv, (size_t)rA * P, (size_t)rB * P, s, nullptr, fused_e2 ? es.data() : nullptr, c->xm_bytes));
-    } else {
-      ProfScope ps(c, "mac_rows_multi", s);
-      MacSection a(c->dA, c1g, c1g, rA), b(c->dB, c2g, c2g, rB);
-      MultiVec mv{vh, (size_t)k * P, (size_t)rA * P, (size_t)rB * P, nv};
-      if (rs && last) {
-        a.rnd_ctr = &rs->counter;
-        a.rnd_adv = D;
-      }
-      PVW_HIP(launch_mac_rows_multi(a, b, mv, c->dt, k, L, l, s));
-    }
-  }
-  if (out_repr == PVW_REPR_POWER) {
-    ProfScope ps(c, "intt", s);
-    PVW_HIP(launch_ntt(d_c1, D * rA, true, c->dt, L, l, s));
-    PVW_HIP(launch_ntt(d_c2, D * rB, true, c->dt, L, l, s));
-  }
-  return PVW_OK;
-}
-
-static int32_t encrypt_multi_checks(pvw_ctx* c, size_t D, size_t per_dealer, uint32_t out_repr) {
-  PVW_TRY(check_repr(out_repr));
-  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no dealers");
-  if (per_dealer != c->n) {                                                          // encryption.rs:264-274
-    char buf[96];
-    snprintf(buf, sizeof buf, "Dealer provided %zu shares but needs %u", per_dealer, c->n);
-    return fail(PVW_ERR_INVALID_PARAMETERS, buf);
-  }
-  if (c->num_keys < c->party_hi)
-    return fail(PVW_ERR_INVALID_PARAMETERS, "Global public key is not complete (missing party keys)");
-  if (!c->crs_loaded) return fail(PVW_ERR_CRS, "CRS not loaded");
-  int32_t ok = 0;
-  pvw_ctx_verify_correctness_condition(c, &ok);
-  if (!ok) return fail(PVW_ERR_INVALID_PARAMETERS, "Parameters do not satisfy correctness condition - decryption may fail");
-  return PVW_OK;
-}
-
-int32_t pvw_encrypt_multi_device(pvw_ctx* c, const uint64_t* d_scalars, size_t num_dealers, size_t scalars_per_dealer,
-                                 const uint8_t* seeds, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
-  if (!c || !d_scalars || !seeds || (!d_c1 && c->rowsA()) || (!d_c2 && c->rowsB())) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(encrypt_multi_checks(c, num_dealers, scalars_per_dealer, out_repr));
-  PVW_TRY(ensure_device(c));
-  hipStream_t s;
-  Workspace* w;
-  PVW_TRY(device_ws(c, stream, &s, &w, num_dealers));
-  return encrypt_multi_enqueue(c, w, d_scalars, seeds, num_dealers, d_c1, d_c2, out_repr, s);
-}
-
-static int32_t encrypt_multi_host(pvw_ctx* c, const uint64_t* scalars, size_t num_dealers, const uint8_t* seeds, RndState* rs,
-                                  uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr);
-int32_t pvw_encrypt_multi(pvw_ctx* c, const uint64_t* scalars, size_t num_dealers, size_t scalars_per_dealer,
-                          const uint8_t* seeds, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
-  if (!c || !scalars || !seeds || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(encrypt_multi_checks(c, num_dealers, scalars_per_dealer, out_repr));
-  PVW_TRY(ensure_device(c));
-  return encrypt_multi_host(c, scalars, num_dealers, seeds, nullptr, c1_out, c2_out, out_repr);
-}
-// host buffers, staged in passes of `per` dealers (seeds, or the device randomness state rs, which each pass advances)
-static int32_t encrypt_multi_host(pvw_ctx* c, const uint64_t* scalars, size_t num_dealers, const uint8_t* seeds, RndState* rs,
-                                  uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
-  const size_t P = c->poly(), rA = c->rowsA(), rB = c->rowsB(), n = c->n;
-  // dealers per pass: bounded staging (<= ~512 MiB of ciphertext)
-  size_t per = stage_budget() / 2 / ((rA + rB) * P * 8 + n * 8);
-  if (per < 4) per = 4;
-  per &= ~(size_t)3;
-  if (per > num_dealers) per = num_dealers;
-  Scratch sc;
-  const size_t r_sc = sc.add(per * n * 8), r_c1 = sc.add(per * rA * P * 8), r_c2 = sc.add(per * rB * P * 8);
-  return host_call(c, [&](Workspace* w) -> int32_t {
-    PVW_TRY(sc.take(w));
-    u64 *d_sc = sc.at(r_sc), *d_c1 = sc.at(r_c1), *d_c2 = sc.at(r_c2);
-    for (size_t d0 = 0; d0 < num_dealers; d0 += per) {
-      const size_t cnt = (num_dealers - d0) < per ? (num_dealers - d0) : per;
-      PVW_HIP(hipMemcpyAsync(d_sc, scalars + d0 * n, cnt * n * 8, hipMemcpyHostToDevice, w->stream));
-      PVW_TRY(encrypt_multi_enqueue(c, w, d_sc, seeds ? seeds + d0 * 32 : nullptr, cnt, d_c1, d_c2, out_repr, w->stream, rs));
-      for (size_t d = 0; d < cnt; ++d) {
-        // a sharded context writes its rows at their global positions inside each dealer's block
-        PVW_HIP(hipMemcpyAsync(c1_out + ((d0 + d) * c->k + c->c1_lo) * P, d_c1 + d * rA * P, rA * P * 8, hipMemcpyDeviceToHost, w->stream));
-        PVW_HIP(hipMemcpyAsync(c2_out + ((d0 + d) * n + c->party_lo) * P, d_c2 + d * rB * P, rB * P * 8, hipMemcpyDeviceToHost, w->stream));
-      }
-    }
-    return PVW_OK;
-  });
-}
-
-// ------------------------------------------------------------------------ device randomness state
-// The reference draws fresh randomness on every encrypt (encryption.rs:135-167, thread_rng()).  A state on the device
-// (seed S, counter c) gives calls that are captured into a graph, or queued asynchronously, the same property: the kernels
-// derive call_seed(S, c + i) when they run and advance c themselves.  The handle records the device and the stream of the
-// context it was created for and never reads the context again.
-struct pvw_rnd_state {
-  int device;
-  hipStream_t stream;   // the creating context's stream: NULL stream arguments and the clearing in pvw_rnd_state_free
-  RndState* dev;
-};
-static thread_local uint64_t g_rnd_free_residue = 0;   // pvw_selftest_rnd_free_residue
-
-int32_t pvw_rnd_call_seed(const uint8_t seed[32], uint64_t counter, uint8_t out[32]) {
-  if (!seed || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  const ChaChaKey s = make_key(seed);
-  const ChaChaKey k = call_seed(s.w, counter);
-  for (int i = 0; i < 8; ++i)
-    for (int b = 0; b < 4; ++b) out[4 * i + b] = (uint8_t)(k.w[i] >> (8 * b));
-  return PVW_OK;
-}
-
-int32_t pvw_rnd_state_create(pvw_ctx* c, const uint8_t seed[32], uint64_t counter, void** out) {
-  if (!c || !seed || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  *out = nullptr;
-  PVW_TRY(ensure_device(c));
-  if (stream_capturing(c->stream)) return fail(PVW_ERR_INVALID_PARAMETERS, "pvw_rnd_state_create allocates: not under stream capture");
-  RndState h{};
-  const ChaChaKey k = make_key(seed);
-  for (int i = 0; i < 8; ++i) h.seed[i] = k.w[i];
-  h.counter = h.base = counter;
-  pvw_rnd_state* st = new pvw_rnd_state{c->device, c->stream, nullptr};
-  hipError_t e = hipMalloc((void**)&st->dev, sizeof(RndState));
-  if (e == hipSuccess) e = hipMemcpyAsync(st->dev, &h, sizeof h, hipMemcpyHostToDevice, st->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(st->stream);
-  memset(&h, 0, sizeof h);
-  if (e != hipSuccess) {
-    if (st->dev) { (void)hipMemset(st->dev, 0, sizeof(RndState)); hipFree(st->dev); }
-    delete st;
-    (void)hipGetLastError();
-    return fail(PVW_ERR_INTERNAL, std::string("creating the randomness state failed: ") + hipGetErrorString(e));
-  }
-  *out = st;
-  return PVW_OK;
-}
-
-int32_t pvw_rnd_state_counter(void* handle, void* stream, uint64_t* out) {
-  pvw_rnd_state* st = (pvw_rnd_state*)handle;
-  if (!st || !st->dev || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  hipStream_t s = stream ? (hipStream_t)stream : st->stream;
-  PVW_HIP(hipSetDevice(st->device));
-  if (stream_capturing(s)) return fail(PVW_ERR_INVALID_PARAMETERS, "pvw_rnd_state_counter waits for its stream: not under stream capture");
-  uint64_t v = 0;
-  PVW_HIP(hipMemcpyAsync(&v, &st->dev->counter, sizeof v, hipMemcpyDeviceToHost, s));
-  PVW_HIP(hipStreamSynchronize(s));
-  *out = v;
-  return PVW_OK;
-}
-
-int32_t pvw_rnd_state_set_counter(void* handle, uint64_t counter, void* stream) {
-  pvw_rnd_state* st = (pvw_rnd_state*)handle;
-  if (!st || !st->dev) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  hipStream_t s = stream ? (hipStream_t)stream : st->stream;
-  PVW_HIP(hipSetDevice(st->device));
-  PVW_HIP(launch_rnd_set_counter(st->dev, counter, s));   // the value travels as a kernel argument: capturable, no host buffer
-  return PVW_OK;
-}
-
-int32_t pvw_rnd_state_free(void* handle) {
-  pvw_rnd_state* st = (pvw_rnd_state*)handle;
-  if (!st) return PVW_OK;
-  int32_t rc = PVW_OK;
-  if (st->dev) {
-    u32 back[8];
-    memset(back, 0xff, sizeof back);
-    if (hipSetDevice(st->device) != hipSuccess || hipMemsetAsync(st->dev, 0, sizeof(RndState), st->stream) != hipSuccess ||
-        hipMemcpyAsync(back, st->dev->seed, sizeof back, hipMemcpyDeviceToHost, st->stream) != hipSuccess ||
-        hipStreamSynchronize(st->stream) != hipSuccess) {
-      (void)hipGetLastError();
-      rc = fail(PVW_ERR_INTERNAL, "clearing the randomness state failed");
-    }
-    g_rnd_free_residue = 0;
-    for (u32 x : back) g_rnd_free_residue += x != 0;
-    hipFree(st->dev);
-  }
-  delete st;
-  return rc;
-}
-
-int32_t pvw_selftest_rnd_free_residue(uint64_t* nonzero_words) {
-  if (!nonzero_words) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  *nonzero_words = g_rnd_free_residue;
-  return PVW_OK;
-}
-
-// after the argument checks of the call (the handle itself is not read before them)
-static int32_t rnd_state_checks(const pvw_ctx* c, const pvw_rnd_state* st) {
-  if (!st->dev) return fail(PVW_ERR_INVALID_PARAMETERS, "randomness state has been freed");
-  if (c->rowsA() == 0 && c->rowsB() == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "the context holds no rows to encrypt");
-  if (c->device >= 0 && st->device != c->device) return fail(PVW_ERR_INVALID_PARAMETERS, "the randomness state lives on another device");
-  return PVW_OK;
-}
-
 int32_t pvw_encrypt_rs_device(pvw_ctx* c, const uint64_t* d_scalars, size_t num_scalars, void* handle, uint64_t* d_c1,
                               uint64_t* d_c2, uint32_t out_repr, void* stream) {
-  pvw_rnd_state* st = (pvw_rnd_state*)handle;
-  if (!c || !d_scalars || !st || (!d_c1 && c->rowsA()) || (!d_c2 && c->rowsB())) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  pvw_randomness_t rnd{};
-  rnd.mode = PVW_RND_SEED;
-  PVW_TRY(encrypt_checks(c, num_scalars, &rnd, out_repr));
-  PVW_TRY(ensure_device(c));
-  PVW_TRY(rnd_state_checks(c, st));
-  hipStream_t s;
-  Workspace* w;
-  PVW_TRY(device_ws(c, stream, &s, &w));
-  return encrypt_enqueue(c, w, d_scalars, &rnd, d_c1, d_c2, out_repr, s, nullptr, nullptr, st->dev);
+  return encrypt_device(c, d_scalars, num_scalars, nullptr, DealerKeys::state(handle), d_c1, d_c2, out_repr, stream);
 }
-
+int32_t pvw_encrypt(pvw_ctx* c, const uint64_t* scalars, size_t num_scalars, const pvw_randomness_t* rnd,
+                    uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+  return encrypt_host(c, scalars, num_scalars, rnd, seed_of(rnd), c1_out, c2_out, out_repr);
+}
 int32_t pvw_encrypt_rs(pvw_ctx* c, const uint64_t* scalars, size_t num_scalars, void* handle, uint64_t* c1_out,
                        uint64_t* c2_out, uint32_t out_repr) {
-  pvw_rnd_state* st = (pvw_rnd_state*)handle;
-  if (!c || !scalars || !st || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  pvw_randomness_t rnd{};
-  rnd.mode = PVW_RND_SEED;
-  PVW_TRY(encrypt_checks(c, num_scalars, &rnd, out_repr));
-  PVW_TRY(ensure_device(c));
-  PVW_TRY(rnd_state_checks(c, st));
-  return encrypt_host(c, scalars, &rnd, st->dev, c1_out, c2_out, out_repr);
-}
-
-int32_t pvw_encrypt_multi_rs_device(pvw_ctx* c, const uint64_t* d_scalars, size_t num_dealers, size_t scalars_per_dealer,
-                                    void* handle, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
-  pvw_rnd_state* st = (pvw_rnd_state*)handle;
-  if (!c || !d_scalars || !st || (!d_c1 && c->rowsA()) || (!d_c2 && c->rowsB())) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(encrypt_multi_checks(c, num_dealers, scalars_per_dealer, out_repr));
-  PVW_TRY(ensure_device(c));
-  PVW_TRY(rnd_state_checks(c, st));
-  hipStream_t s;
-  Workspace* w;
-  PVW_TRY(device_ws(c, stream, &s, &w, num_dealers));
-  return encrypt_multi_enqueue(c, w, d_scalars, nullptr, num_dealers, d_c1, d_c2, out_repr, s, st->dev);
-}
-
-int32_t pvw_encrypt_multi_rs(pvw_ctx* c, const uint64_t* scalars, size_t num_dealers, size_t scalars_per_dealer,
-                             void* handle, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
-  pvw_rnd_state* st = (pvw_rnd_state*)handle;
-  if (!c || !scalars || !st || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(encrypt_multi_checks(c, num_dealers, scalars_per_dealer, out_repr));
-  PVW_TRY(ensure_device(c));
-  PVW_TRY(rnd_state_checks(c, st));
-  return encrypt_multi_host(c, scalars, num_dealers, nullptr, st->dev, c1_out, c2_out, out_repr);
+  return encrypt_host(c, scalars, num_scalars, nullptr, DealerKeys::state(handle), c1_out, c2_out, out_repr);
 }
 
 // ------------------------------------------------------------------------ Shamir shares
@@ -2278,30 +2035,31 @@ int32_t pvw_shamir_reconstruct(uint64_t plain_modulus, const uint64_t* indices, 
   return PVW_OK;
 }
 
-// the shares of dealers [0, D) into d_shares [D][n] (columns [party_lo, party_hi)), PVW_MAX_PROLOGUE_KEYS dealers per launch.
-// seeds: the dealers' host seeds; rs: the device state instead (dealer d: call_seed(S, counter + rnd_off + d)).
-static int32_t shamir_enqueue(pvw_ctx* c, const ShamirDeal& deal, const uint8_t* seeds, RndState* rs, u64 rnd_off, size_t D,
-                              u64* d_shares, hipStream_t s) {
+// One call's Shamir sharing on the device (pvw_shamir_shares*, and pvw_deal_shares* through encrypt_multi_enqueue)
+struct ShamirDeal {
+  const u64* d_secrets;   // [D]
+  const u64* d_coeffs;    // [D][degree], or NULL: drawn from the dealers' keys
+  u32 degree;
+  Mod m;
+  // the same deal starting i dealers further on
+  ShamirDeal from(size_t i) const { return ShamirDeal{d_secrets + i, d_coeffs ? d_coeffs + i * degree : nullptr, degree, m}; }
+};
+// the shares of dealers [0, D) into d_shares [D][n] (columns [party_lo, party_hi)), PVW_MAX_PROLOGUE_KEYS dealers per launch
+static int32_t shamir_enqueue(pvw_ctx* c, const ShamirDeal& deal, const DealerKeys& keys, size_t D, u64* d_shares, hipStream_t s) {
   ProfScope ps(c, "shamir_eval", s);
   for (size_t d0 = 0; d0 < D; d0 += PVW_MAX_PROLOGUE_KEYS) {
+    const ShamirDeal dd = deal.from(d0);
     ShamirBatch b{};
     b.nd = (u32)((D - d0) < PVW_MAX_PROLOGUE_KEYS ? (D - d0) : PVW_MAX_PROLOGUE_KEYS);
-    b.secrets = deal.d_secrets + d0;
-    b.coeffs = deal.d_coeffs ? deal.d_coeffs + d0 * deal.degree : nullptr;
+    b.secrets = dd.d_secrets;
+    b.coeffs = dd.d_coeffs;
     b.shares = d_shares + d0 * c->n;
     b.row_stride = c->n;
     b.degree = deal.degree;
     b.party_lo = c->party_lo;
     b.party_hi = c->party_hi;
     b.m = deal.m;
-    if (!b.coeffs && deal.degree) {
-      if (rs) {
-        b.rnd = rs;
-        b.rnd_off = rnd_off + d0;
-      } else {
-        for (u32 x = 0; x < b.nd; ++x) b.key[x] = make_key(seeds + (d0 + x) * 32);
-      }
-    }
+    if (!b.coeffs && deal.degree) keys.from(d0).fill(b, b.nd);
     PVW_HIP(launch_shamir_eval(b, s));
     memset(&b, 0, sizeof b);
   }
@@ -2315,7 +2073,7 @@ int32_t pvw_shamir_shares_device(pvw_ctx* c, const uint64_t* d_secrets, size_t n
   PVW_TRY(shamir_checks(c, num_dealers, degree, plain_modulus));
   PVW_TRY(ensure_device(c));
   const ShamirDeal deal{d_secrets, d_coeffs, degree, shamir_mod(plain_modulus)};
-  return shamir_enqueue(c, deal, seeds, nullptr, 0, num_dealers, d_shares, call_stream(c, stream));
+  return shamir_enqueue(c, deal, DealerKeys::host(seeds), num_dealers, d_shares, call_stream(c, stream));
 }
 
 int32_t pvw_shamir_shares(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t degree, uint64_t plain_modulus,
@@ -2336,7 +2094,7 @@ int32_t pvw_shamir_shares(pvw_ctx* c, const uint64_t* secrets, size_t num_dealer
       PVW_HIP(hipMemcpyAsync(d_se, secrets + d0, cnt * 8, hipMemcpyHostToDevice, w->stream));
       if (d_co) PVW_HIP(hipMemcpyAsync(d_co, coeffs + d0 * t, cnt * t * 8, hipMemcpyHostToDevice, w->stream));
       const ShamirDeal deal{d_se, d_co, degree, shamir_mod(plain_modulus)};
-      PVW_TRY(shamir_enqueue(c, deal, seeds ? seeds + d0 * 32 : nullptr, nullptr, 0, cnt, d_sh, w->stream));
+      PVW_TRY(shamir_enqueue(c, deal, DealerKeys::host(seeds).from(d0), cnt, d_sh, w->stream));
       // a sharded context writes its own columns only
       if (rB) PVW_HIP(hipMemcpy2DAsync(shares_out + d0 * n + c->party_lo, n * 8, d_sh + c->party_lo, n * 8, rB * 8, cnt,
                                        hipMemcpyDeviceToHost, w->stream));
@@ -2346,20 +2104,115 @@ int32_t pvw_shamir_shares(pvw_ctx* c, const uint64_t* secrets, size_t num_dealer
   });
 }
 
-// Under stream capture a deal may not allocate: the share scratch is built with the digit buffers by pvw_prepare(PVW_PREPARE_MFMA),
-// whatever the dealer count (checked before the stream's workspace is looked up, like multi_capture_check)
-static int32_t deal_capture_check(pvw_ctx* c, hipStream_t s, size_t D) {
-  if (!stream_capturing(s)) return PVW_OK;
-  bool ready;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    auto it = c->async_ws.find((void*)s);
-    ready = it != c->async_ws.end() && it->second->shares;
+// ------------------------------------------------------------------------ multi-dealer encrypt
+// encrypt_all_party_shares (encryption.rs:253-286): dealer d encrypts scalars[d][0..n) with its own
+// randomness (seed d).  Groups of 4 dealers share one pass over A-hat / B-hat (mac_rows_multi).
+// Device layout: d_scalars [D][n]; d_c1 [D][rowsA][L][l]; d_c2 [D][rowsB][L][l].
+// keys: dealer d's seed, or call_seed(S, c + d) of a device state, with c the counter when the call's kernels run; the
+// call's last kernel then advances the counter by D.
+// deal != NULL (pvw_deal_shares*, DESIGN 8.9): d_scalars is not read; the scalars of each pass of dealers are their Shamir
+// shares, made into w->shares by shamir_enqueue in front of the pass (under the same keys, domain DOM_SHAMIR).
+static int32_t encrypt_multi_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, const DealerKeys& keys, size_t D, u64* d_c1,
+                                     u64* d_c2, uint32_t out_repr, hipStream_t s, const ShamirDeal* deal = nullptr) {
+  const u32 k = c->k, l = c->l, L = c->L, rA = c->rowsA(), rB = c->rowsB();
+  const size_t P = c->poly();
+  const bool use_gemm = multi_uses_gemm(D);
+  if (use_gemm) {
+    PVW_TRY(ws_gemm_buffers(c, w));
+    PVW_TRY(ensure_xm(c, s));
   }
-  if (!ready)
-    return fail(PVW_ERR_INVALID_PARAMETERS, "multi-dealer encrypt under stream capture: call pvw_prepare(PVW_PREPARE_MFMA) on "
-                                            "this stream first (and again after the matrices change)");
-  return multi_capture_check(c, s, D);
+  const size_t group = use_gemm ? (size_t)16 * gemm_vb() : 4;
+  // matrix-core passes: the c2 finish pass draws e2 and encodes the scalars itself (tuning build: PVW_FUSED_E2=0 the prologue does)
+  const bool fused_e2 = use_gemm && l <= 32 && PVW_ENV_INT("PVW_FUSED_E2", 1) != 0;
+  u64* vh = use_gemm ? w->vhat16 : w->rhat;
+  RndState* rs = keys.state();
+  for (size_t d0 = 0; d0 < D; d0 += group) {
+    const u32 nv = (u32)((D - d0) < group ? (D - d0) : group);
+    const u64* gsc = deal ? w->shares : d_scalars + d0 * c->n;   // the pass's scalars [nv][n]
+    if (deal) PVW_TRY(shamir_enqueue(c, deal->from(d0), keys.from(d0), nv, w->shares, s));
+    // prologue: the (r, e1, e2) families of dealer d0 replicated over the nv dealers of this pass (up to 64 keys
+    // per launch): r-hat_d -> vh[v], NTT(e1), NTT(e2) + m*g-hat -> output planes
+    for (u32 v0 = 0; v0 < nv; v0 += PVW_MAX_PROLOGUE_KEYS) {
+      const u32 cnt = (nv - v0) < PVW_MAX_PROLOGUE_KEYS ? (nv - v0) : PVW_MAX_PROLOGUE_KEYS;
+      const size_t d = d0 + v0;
+      PrologueBatch pb{};
+      PVW_TRY(fill_encrypt_jobs(c, pb, 0, ExplicitRnd{}, gsc + (size_t)v0 * c->n, vh + (size_t)v0 * k * P,
+                                d_c1 + d * rA * P, d_c2 + d * rB * P));
+      keys.from(d).fill(pb, cnt);                               // replica x: dealer d + x
+      pb.job[0].rep_key = pb.job[1].rep_key = pb.job[2].rep_key = 1;
+      pb.job[0].rep_out = (size_t)k * P;                       // r-hat vectors
+      pb.job[1].rep_out = (size_t)rA * P;                      // c1 planes
+      pb.job[2].rep_out = (size_t)rB * P;                      // c2 planes
+      pb.job[2].rep_scalars = c->n;
+      pb.njobs = fused_e2 ? 2 : 3;                              // fused: e2 + m g-hat are made by the c2 finish pass
+      pb.reps = cnt;
+      ProfScope ps(c, "prologue", s);
+      PVW_HIP(launch_prologue(pb, c->dt, L, l, s));
+    }
+    u64* c1g = d_c1 + d0 * rA * P;
+    u64* c2g = d_c2 + d0 * rB * P;
+    const bool last = d0 + nv == D;                             // its last kernel advances the randomness state
+    if (use_gemm) {
+      {
+        ProfScope ps(c, "vec_digits", s);
+        PVW_HIP(launch_vec_digits(vh, (size_t)k * P, w->yd, w->sy, nv, k, L, l, c->dt, s, 0, 0, c->xm_bytes));
+      }
+      ProfScope ps(c, "gemm_digits", s);
+      GemmSection a{c->xmA, c1g, c1g, w->gtmpA, rA, 0, 0}, b{c->xmB, c2g, c2g, w->gtmpB, rB, 0, 0};
+      std::vector<GemmErrSource> es;
+      if (fused_e2) {
+        // e2_d[i] (encryption.rs:195-196): dealer d's key, stream DOM_E2 / party index, uniform in [-b2, b2]; + m_{d,i} g-hat
+        for (u32 v0 = 0; v0 < nv; v0 += PVW_MAX_PROLOGUE_KEYS) {
+          GemmErrSource e{};
+          e.span = (nv - v0) < PVW_MAX_PROLOGUE_KEYS ? (nv - v0) : PVW_MAX_PROLOGUE_KEYS;
+          keys.from(d0 + v0).fill(e, e.span);                  // vector x: dealer d0 + v0 + x
+          e.key_v = 1;
+          e.domain = DOM_E2; e.index0 = c->party_lo; e.index_row = 1; e.index_v = 0; e.bound = c->b2;
+          e.scalars = gsc + c->party_lo; e.scalar_v = c->n;
+          es.push_back(e);
+        }
+        b.addend = nullptr;
+      }
+      if (rs && last) {
+        GemmSection& fin = rB ? b : a;                          // the finish pass launched last
+        fin.rnd_ctr = &rs->counter;
+        fin.rnd_adv = D;
+      }
+      PVW_HIP(launch_gemm_digits(a, b, w->yd, w->sy, c->dt, k, L, l, nv, (size_t)rA * P, (size_t)rB * P, s, nullptr, fused_e2 ? es.data() : nullptr, c->xm_bytes));
+    } else {
+      ProfScope ps(c, "mac_rows_multi", s);
+      MacSection a(c->dA, c1g, c1g, rA), b(c->dB, c2g, c2g, rB);
+      MultiVec mv{vh, (size_t)k * P, (size_t)rA * P, (size_t)rB * P, nv};
+      if (rs && last) {
+        a.rnd_ctr = &rs->counter;
+        a.rnd_adv = D;
+      }
+      PVW_HIP(launch_mac_rows_multi(a, b, mv, c->dt, k, L, l, s));
+    }
+  }
+  if (out_repr == PVW_REPR_POWER) {
+    ProfScope ps(c, "intt", s);
+    PVW_HIP(launch_ntt(d_c1, D * rA, true, c->dt, L, l, s));
+    PVW_HIP(launch_ntt(d_c2, D * rB, true, c->dt, L, l, s));
+  }
+  return PVW_OK;
+}
+
+static int32_t encrypt_multi_checks(pvw_ctx* c, size_t D, size_t per_dealer, uint32_t out_repr) {
+  PVW_TRY(check_repr(out_repr));
+  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no dealers");
+  if (per_dealer != c->n) {                                                          // encryption.rs:264-274
+    char buf[96];
+    snprintf(buf, sizeof buf, "Dealer provided %zu shares but needs %u", per_dealer, c->n);
+    return fail(PVW_ERR_INVALID_PARAMETERS, buf);
+  }
+  if (c->num_keys < c->party_hi)
+    return fail(PVW_ERR_INVALID_PARAMETERS, "Global public key is not complete (missing party keys)");
+  if (!c->crs_loaded) return fail(PVW_ERR_CRS, "CRS not loaded");
+  int32_t ok = 0;
+  pvw_ctx_verify_correctness_condition(c, &ok);
+  if (!ok) return fail(PVW_ERR_INVALID_PARAMETERS, "Parameters do not satisfy correctness condition - decryption may fail");
+  return PVW_OK;
 }
 
 // what a deal leaves in the workspace: the shares, and below the matrix-core threshold the dealers' r-hat in the vectors the
@@ -2368,84 +2221,210 @@ static void deal_mark(Workspace* w, size_t D) {
   ws_mark_secret(w, w->shares, w->shares_bytes);
   if (!multi_uses_gemm(D)) ws_mark_secret(w, w->rhat, w->rhat_bytes);
 }
-// device pointers: encrypt_multi_enqueue with the shares made pass by pass in the workspace's share scratch, which the call marks
-// secret (cleared on the stream behind the call's last launch)
-static int32_t deal_device(pvw_ctx* c, const uint64_t* d_secrets, size_t D, uint32_t degree, uint64_t p, const uint8_t* seeds,
-                           RndState* rs, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
-  const ShamirDeal deal{d_secrets, nullptr, degree, shamir_mod(p)};
-  return device_call(c, stream, [&](hipStream_t s) { return deal_capture_check(c, s, D); },
-                     [&](Workspace* w, hipStream_t s) -> int32_t {
-                       PVW_TRY(ws_share_buffer(c, w));
-                       deal_mark(w, D);
-                       return encrypt_multi_enqueue(c, w, nullptr, seeds, D, d_c1, d_c2, out_repr, s, rs, &deal);
-                     });
-}
-// host buffers: encrypt_multi_host's staging with the secrets in place of the scalars
-static int32_t deal_host(pvw_ctx* c, const uint64_t* secrets, size_t D, uint32_t degree, uint64_t p, const uint8_t* seeds,
-                         RndState* rs, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
-  const size_t P = c->poly(), rA = c->rowsA(), rB = c->rowsB(), n = c->n;
-  size_t per = stage_budget() / 2 / ((rA + rB) * P * 8 + 8);
+
+// host buffers, staged in pieces of `per` dealers (<= ~512 MiB of ciphertext): each dealer's input -- its n scalars, or with
+// deal != NULL its one secret -- goes up, the piece is encrypted, and its rows go to their global positions
+static int32_t encrypt_multi_stage(pvw_ctx* c, const uint64_t* in, size_t D, const DealerKeys& keys, const ShamirDeal* deal,
+                                   uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+  const size_t P = c->poly(), rA = c->rowsA(), rB = c->rowsB(), n = c->n, in_words = deal ? 1 : n;
+  size_t per = stage_budget() / 2 / ((rA + rB) * P * 8 + in_words * 8);
   if (per < 4) per = 4;
   per &= ~(size_t)3;
   if (per > D) per = D;
   Scratch sc;
-  const size_t r_se = sc.add(per * 8), r_c1 = sc.add(per * rA * P * 8), r_c2 = sc.add(per * rB * P * 8);
+  const size_t r_in = sc.add(per * in_words * 8), r_c1 = sc.add(per * rA * P * 8), r_c2 = sc.add(per * rB * P * 8);
   return host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
-    PVW_TRY(ws_share_buffer(c, w));
-    sc.secret(w, r_se, r_se);
-    deal_mark(w, per);                                           // each pass takes the matrix cores or the VALU by its OWN dealer
-    if (D % per) deal_mark(w, D % per);                          // count: a last pass of 1 or 2 leaves r-hat in the workspace
-    u64 *d_se = sc.at(r_se), *d_c1 = sc.at(r_c1), *d_c2 = sc.at(r_c2);
+    if (deal) {
+      PVW_TRY(ws_share_buffer(c, w));
+      sc.secret(w, r_in, r_in);
+      deal_mark(w, per);                                           // each pass takes the matrix cores or the VALU by its OWN dealer
+      if (D % per) deal_mark(w, D % per);                          // count: a last pass of 1 or 2 leaves r-hat in the workspace
+    }
+    u64 *d_in = sc.at(r_in), *d_c1 = sc.at(r_c1), *d_c2 = sc.at(r_c2);
+    const ShamirDeal staged = deal ? ShamirDeal{d_in, nullptr, deal->degree, deal->m} : ShamirDeal{};   // the secrets of each piece
     for (size_t d0 = 0; d0 < D; d0 += per) {
       const size_t cnt = (D - d0) < per ? (D - d0) : per;
-      PVW_HIP(hipMemcpyAsync(d_se, secrets + d0, cnt * 8, hipMemcpyHostToDevice, w->stream));
-      const ShamirDeal deal{d_se, nullptr, degree, shamir_mod(p)};
-      PVW_TRY(encrypt_multi_enqueue(c, w, nullptr, seeds ? seeds + d0 * 32 : nullptr, cnt, d_c1, d_c2, out_repr, w->stream, rs, &deal));
+      PVW_HIP(hipMemcpyAsync(d_in, in + d0 * in_words, cnt * in_words * 8, hipMemcpyHostToDevice, w->stream));
+      PVW_TRY(encrypt_multi_enqueue(c, w, deal ? nullptr : d_in, keys.piece(d0), cnt, d_c1, d_c2, out_repr, w->stream, deal ? &staged : nullptr));
       for (size_t d = 0; d < cnt; ++d) {
+        // a sharded context writes its rows at their global positions inside each dealer's block
         PVW_HIP(hipMemcpyAsync(c1_out + ((d0 + d) * c->k + c->c1_lo) * P, d_c1 + d * rA * P, rA * P * 8, hipMemcpyDeviceToHost, w->stream));
         PVW_HIP(hipMemcpyAsync(c2_out + ((d0 + d) * n + c->party_lo) * P, d_c2 + d * rB * P, rB * P * 8, hipMemcpyDeviceToHost, w->stream));
       }
-      if (d0 + cnt < D) PVW_HIP(hipStreamSynchronize(w->stream));   // the next pass reuses the pageable staging
+      if (deal && d0 + cnt < D) PVW_HIP(hipStreamSynchronize(w->stream));   // the next piece reuses the pageable staging
     }
     return PVW_OK;
   });
 }
 
+// The four multi-dealer frames, in the order of encrypt's; their seed and _rs exports differ in the key source alone.
+static int32_t encrypt_multi_device(pvw_ctx* c, const uint64_t* d_scalars, size_t D, size_t per_dealer, const DealerKeys& keys,
+                                    uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
+  if (!c || !d_scalars || keys.missing() || (!d_c1 && c->rowsA()) || (!d_c2 && c->rowsB())) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(encrypt_multi_checks(c, D, per_dealer, out_repr));
+  return device_call(c, stream, [&](hipStream_t s) -> int32_t {
+                       PVW_TRY(keys.checks(c));
+                       return multi_capture_check(c, s, D);
+                     },
+                     [&](Workspace* w, hipStream_t s) { return encrypt_multi_enqueue(c, w, d_scalars, keys, D, d_c1, d_c2, out_repr, s); });
+}
+static int32_t encrypt_multi_host(pvw_ctx* c, const uint64_t* scalars, size_t D, size_t per_dealer, const DealerKeys& keys,
+                                  uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+  if (!c || !scalars || keys.missing() || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(encrypt_multi_checks(c, D, per_dealer, out_repr));
+  PVW_TRY(ensure_device(c));
+  PVW_TRY(keys.checks(c));
+  return encrypt_multi_stage(c, scalars, D, keys, nullptr, c1_out, c2_out, out_repr);
+}
+// the deal on device pointers: encrypt_multi_enqueue with the shares made pass by pass in the workspace's share scratch, which
+// the call marks secret (cleared on the stream behind the call's last launch)
+static int32_t deal_device(pvw_ctx* c, const uint64_t* d_secrets, size_t D, uint32_t degree, uint64_t p, const DealerKeys& keys,
+                           uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
+  if (!c || !d_secrets || keys.missing() || (!d_c1 && c->rowsA()) || (!d_c2 && c->rowsB())) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(encrypt_multi_checks(c, D, c->n, out_repr));
+  PVW_TRY(shamir_checks(c, D, degree, p));
+  const ShamirDeal deal{d_secrets, nullptr, degree, shamir_mod(p)};
+  return device_call(c, stream, [&](hipStream_t s) -> int32_t {
+                       PVW_TRY(keys.checks(c));
+                       return deal_capture_check(c, s, D);
+                     },
+                     [&](Workspace* w, hipStream_t s) -> int32_t {
+                       PVW_TRY(ws_share_buffer(c, w));
+                       deal_mark(w, D);
+                       return encrypt_multi_enqueue(c, w, nullptr, keys, D, d_c1, d_c2, out_repr, s, &deal);
+                     });
+}
+static int32_t deal_host(pvw_ctx* c, const uint64_t* secrets, size_t D, uint32_t degree, uint64_t p, const DealerKeys& keys,
+                         uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+  if (!c || !secrets || keys.missing() || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(encrypt_multi_checks(c, D, c->n, out_repr));
+  PVW_TRY(shamir_checks(c, D, degree, p));
+  PVW_TRY(ensure_device(c));
+  PVW_TRY(keys.checks(c));
+  const ShamirDeal deal{nullptr, nullptr, degree, shamir_mod(p)};   // the staging loop points it at each piece's secrets in turn
+  return encrypt_multi_stage(c, secrets, D, keys, &deal, c1_out, c2_out, out_repr);
+}
+
+int32_t pvw_encrypt_multi_device(pvw_ctx* c, const uint64_t* d_scalars, size_t num_dealers, size_t scalars_per_dealer,
+                                 const uint8_t* seeds, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
+  return encrypt_multi_device(c, d_scalars, num_dealers, scalars_per_dealer, DealerKeys::host(seeds), d_c1, d_c2, out_repr, stream);
+}
+int32_t pvw_encrypt_multi_rs_device(pvw_ctx* c, const uint64_t* d_scalars, size_t num_dealers, size_t scalars_per_dealer,
+                                    void* handle, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
+  return encrypt_multi_device(c, d_scalars, num_dealers, scalars_per_dealer, DealerKeys::state(handle), d_c1, d_c2, out_repr, stream);
+}
+int32_t pvw_encrypt_multi(pvw_ctx* c, const uint64_t* scalars, size_t num_dealers, size_t scalars_per_dealer,
+                          const uint8_t* seeds, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+  return encrypt_multi_host(c, scalars, num_dealers, scalars_per_dealer, DealerKeys::host(seeds), c1_out, c2_out, out_repr);
+}
+int32_t pvw_encrypt_multi_rs(pvw_ctx* c, const uint64_t* scalars, size_t num_dealers, size_t scalars_per_dealer,
+                             void* handle, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+  return encrypt_multi_host(c, scalars, num_dealers, scalars_per_dealer, DealerKeys::state(handle), c1_out, c2_out, out_repr);
+}
 int32_t pvw_deal_shares_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t degree, uint64_t plain_modulus,
                                const uint8_t* seeds, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
-  if (!c || !d_secrets || !seeds || (!d_c1 && c->rowsA()) || (!d_c2 && c->rowsB())) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(encrypt_multi_checks(c, num_dealers, c->n, out_repr));
-  PVW_TRY(shamir_checks(c, num_dealers, degree, plain_modulus));
-  return deal_device(c, d_secrets, num_dealers, degree, plain_modulus, seeds, nullptr, d_c1, d_c2, out_repr, stream);
-}
-int32_t pvw_deal_shares(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t degree, uint64_t plain_modulus,
-                        const uint8_t* seeds, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
-  if (!c || !secrets || !seeds || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(encrypt_multi_checks(c, num_dealers, c->n, out_repr));
-  PVW_TRY(shamir_checks(c, num_dealers, degree, plain_modulus));
-  PVW_TRY(ensure_device(c));
-  return deal_host(c, secrets, num_dealers, degree, plain_modulus, seeds, nullptr, c1_out, c2_out, out_repr);
+  return deal_device(c, d_secrets, num_dealers, degree, plain_modulus, DealerKeys::host(seeds), d_c1, d_c2, out_repr, stream);
 }
 int32_t pvw_deal_shares_rs_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t degree, uint64_t plain_modulus,
                                   void* handle, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
-  pvw_rnd_state* st = (pvw_rnd_state*)handle;
-  if (!c || !d_secrets || !st || (!d_c1 && c->rowsA()) || (!d_c2 && c->rowsB())) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(encrypt_multi_checks(c, num_dealers, c->n, out_repr));
-  PVW_TRY(shamir_checks(c, num_dealers, degree, plain_modulus));
-  PVW_TRY(ensure_device(c));
-  PVW_TRY(rnd_state_checks(c, st));
-  return deal_device(c, d_secrets, num_dealers, degree, plain_modulus, nullptr, st->dev, d_c1, d_c2, out_repr, stream);
+  return deal_device(c, d_secrets, num_dealers, degree, plain_modulus, DealerKeys::state(handle), d_c1, d_c2, out_repr, stream);
+}
+int32_t pvw_deal_shares(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t degree, uint64_t plain_modulus,
+                        const uint8_t* seeds, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+  return deal_host(c, secrets, num_dealers, degree, plain_modulus, DealerKeys::host(seeds), c1_out, c2_out, out_repr);
 }
 int32_t pvw_deal_shares_rs(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t degree, uint64_t plain_modulus,
                            void* handle, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
-  pvw_rnd_state* st = (pvw_rnd_state*)handle;
-  if (!c || !secrets || !st || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(encrypt_multi_checks(c, num_dealers, c->n, out_repr));
-  PVW_TRY(shamir_checks(c, num_dealers, degree, plain_modulus));
+  return deal_host(c, secrets, num_dealers, degree, plain_modulus, DealerKeys::state(handle), c1_out, c2_out, out_repr);
+}
+
+// ------------------------------------------------------------------------ device randomness state
+// The reference draws fresh randomness on every encrypt (encryption.rs:135-167, thread_rng()).  A state on the device
+// (seed S, counter c) gives calls that are captured into a graph, or queued asynchronously, the same property: the kernels
+// derive call_seed(S, c + i) when they run and advance c themselves.  The handle is pvw_rnd_state, beside DealerKeys.
+static thread_local uint64_t g_rnd_free_residue = 0;   // pvw_selftest_rnd_free_residue
+
+int32_t pvw_rnd_call_seed(const uint8_t seed[32], uint64_t counter, uint8_t out[32]) {
+  if (!seed || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const ChaChaKey s = make_key(seed);
+  const ChaChaKey k = call_seed(s.w, counter);
+  for (int i = 0; i < 8; ++i)
+    for (int b = 0; b < 4; ++b) out[4 * i + b] = (uint8_t)(k.w[i] >> (8 * b));
+  return PVW_OK;
+}
+
+int32_t pvw_rnd_state_create(pvw_ctx* c, const uint8_t seed[32], uint64_t counter, void** out) {
+  if (!c || !seed || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  *out = nullptr;
   PVW_TRY(ensure_device(c));
-  PVW_TRY(rnd_state_checks(c, st));
-  return deal_host(c, secrets, num_dealers, degree, plain_modulus, nullptr, st->dev, c1_out, c2_out, out_repr);
+  if (stream_capturing(c->stream)) return fail(PVW_ERR_INVALID_PARAMETERS, "pvw_rnd_state_create allocates: not under stream capture");
+  RndState h{};
+  const ChaChaKey k = make_key(seed);
+  for (int i = 0; i < 8; ++i) h.seed[i] = k.w[i];
+  h.counter = h.base = counter;
+  pvw_rnd_state* st = new pvw_rnd_state{c->device, c->stream, nullptr};
+  hipError_t e = hipMalloc((void**)&st->dev, sizeof(RndState));
+  if (e == hipSuccess) e = hipMemcpyAsync(st->dev, &h, sizeof h, hipMemcpyHostToDevice, st->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(st->stream);
+  memset(&h, 0, sizeof h);
+  if (e != hipSuccess) {
+    if (st->dev) { (void)hipMemset(st->dev, 0, sizeof(RndState)); hipFree(st->dev); }
+    delete st;
+    (void)hipGetLastError();
+    return fail(PVW_ERR_INTERNAL, std::string("creating the randomness state failed: ") + hipGetErrorString(e));
+  }
+  *out = st;
+  return PVW_OK;
+}
+
+int32_t pvw_rnd_state_counter(void* handle, void* stream, uint64_t* out) {
+  pvw_rnd_state* st = (pvw_rnd_state*)handle;
+  if (!st || !st->dev || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  hipStream_t s = stream ? (hipStream_t)stream : st->stream;
+  PVW_HIP(hipSetDevice(st->device));
+  if (stream_capturing(s)) return fail(PVW_ERR_INVALID_PARAMETERS, "pvw_rnd_state_counter waits for its stream: not under stream capture");
+  uint64_t v = 0;
+  PVW_HIP(hipMemcpyAsync(&v, &st->dev->counter, sizeof v, hipMemcpyDeviceToHost, s));
+  PVW_HIP(hipStreamSynchronize(s));
+  *out = v;
+  return PVW_OK;
+}
+
+int32_t pvw_rnd_state_set_counter(void* handle, uint64_t counter, void* stream) {
+  pvw_rnd_state* st = (pvw_rnd_state*)handle;
+  if (!st || !st->dev) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  hipStream_t s = stream ? (hipStream_t)stream : st->stream;
+  PVW_HIP(hipSetDevice(st->device));
+  PVW_HIP(launch_rnd_set_counter(st->dev, counter, s));   // the value travels as a kernel argument: capturable, no host buffer
+  return PVW_OK;
+}
+
+int32_t pvw_rnd_state_free(void* handle) {
+  pvw_rnd_state* st = (pvw_rnd_state*)handle;
+  if (!st) return PVW_OK;
+  int32_t rc = PVW_OK;
+  if (st->dev) {
+    u32 back[8];
+    memset(back, 0xff, sizeof back);
+    if (hipSetDevice(st->device) != hipSuccess || hipMemsetAsync(st->dev, 0, sizeof(RndState), st->stream) != hipSuccess ||
+        hipMemcpyAsync(back, st->dev->seed, sizeof back, hipMemcpyDeviceToHost, st->stream) != hipSuccess ||
+        hipStreamSynchronize(st->stream) != hipSuccess) {
+      (void)hipGetLastError();
+      rc = fail(PVW_ERR_INTERNAL, "clearing the randomness state failed");
+    }
+    g_rnd_free_residue = 0;
+    for (u32 x : back) g_rnd_free_residue += x != 0;
+    hipFree(st->dev);
+  }
+  delete st;
+  return rc;
+}
+
+int32_t pvw_selftest_rnd_free_residue(uint64_t* nonzero_words) {
+  if (!nonzero_words) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  *nonzero_words = g_rnd_free_residue;
+  return PVW_OK;
 }
 
 // ------------------------------------------------------------------------ decode (host, integers)

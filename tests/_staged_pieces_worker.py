@@ -60,7 +60,7 @@ def cut(D, per):
 
 
 def passes(item_bytes, D, b=GIB):
-    """encrypt_multi_host / deal_host: half the budget, at least 4 dealers, a multiple of 4"""
+    """encrypt_multi_stage (pvw_encrypt_multi*, pvw_deal_shares*): half the budget, at least 4 dealers, a multiple of 4"""
     per = max((b // 2) // item_bytes, 4) & ~3
     return cut(D, min(per, D))
 
