@@ -588,6 +588,41 @@ PVW_API int32_t pvw_deal_shares_rs_device(pvw_ctx* ctx, const uint64_t* d_secret
  * be the secret; the routine cannot know the degree and does not check. */
 PVW_API int32_t pvw_shamir_reconstruct(uint64_t plain_modulus, const uint64_t* indices, const uint64_t* shares, size_t count,
                                        size_t num_secrets, uint64_t* out);
+/* Checked reconstruction: the secrets AND a report on the shares they came from.  The reference leaves validity
+ * of the shares "external" (examples/pvw_valid_dec.rs:150-159), so this contract is the library's own.  All arithmetic in Z_p,
+ * p = plain_modulus prime and below 2^62.
+ *   degree = t.  indices [count]: distinct global party indices, each < p - 1 (the points are x_c = indices[c] + 1); a HOST
+ *   pointer in every form.  shares: num_secrets rows, element (s, c) at shares[s * secret_stride + c * point_stride] (strides in
+ *   elements; any word, read mod p): strides (count, 1) read the [secret][party] rows of pvw_shamir_shares*, strides (1, D) the
+ *   [party][dealer] result of pvw_decrypt_all* with every dealer a secret.
+ *   Basis: columns 0..t in the caller's order; extras: columns t+1..count-1.  F_s: the polynomial of degree <= t through the
+ *   basis points of secret s.
+ *   out [num_secrets] = F_s(0).  bad [num_secrets] (or NULL): how many extras c have share(s, c) mod p != F_s(x_c).
+ *   col_bad [count] (or NULL): for each column, how many secrets deviate there; 0 for the basis columns.
+ * What the counts mean:
+ *   one wrong extra share is flagged at exactly that (s, c), and out is right;
+ *   one wrong basis share of secret s makes out[s] wrong and flags EVERY extra of s (the deviation at x_c is delta L_j(x_c), and
+ *   L_j(x_c) != 0 outside the basis).  So a col_bad with one full column names a bad extra party; a col_bad with every extra
+ *   column nonzero says the basis holds a bad party, and the caller reorders.  The routine detects; it neither corrects errors
+ *   nor searches for a basis.
+ * PVW_ERR_INVALID_PARAMETERS before any device work: NULL indices / shares / out (or ctx), num_secrets = 0, count < degree + 1,
+ * duplicate indices, an index >= p - 1, a composite p or p >= 2^62, a stride of 0 (and, on the device, count or num_secrets
+ * >= 2^31). */
+/* the contract in plain C++ on the host cores (no context, no GPU): what the kernels are tested against */
+PVW_API int32_t pvw_shamir_reconstruct_checked_host(uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                                    const uint64_t* shares, size_t num_secrets, size_t secret_stride,
+                                                    size_t point_stride, uint64_t* out, uint32_t* bad, uint32_t* col_bad);
+/* device pointers (indices stays a HOST pointer, read before the call returns), asynchronous on `stream`.  The weight matrix
+ * [t+1][count-t] lives in the stream's workspace, sized by the call: under stream capture the call needs an earlier call with the
+ * same (degree, count) on that stream outside capture; without it: the error of pvw_encrypt_multi_device, nothing enqueued. */
+PVW_API int32_t pvw_shamir_reconstruct_checked_device(pvw_ctx* ctx, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                      size_t count, const uint64_t* d_shares, size_t num_secrets,
+                                                      size_t secret_stride, size_t point_stride, uint64_t* d_out, uint32_t* d_bad,
+                                                      uint32_t* d_col_bad, void* stream);
+/* host buffers (synchronous); the staged shares and secrets are cleared before the call returns */
+PVW_API int32_t pvw_shamir_reconstruct_checked(pvw_ctx* ctx, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
+                                               size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
+                                               size_t point_stride, uint64_t* out, uint32_t* bad, uint32_t* col_bad);
 
 /* decode_scalar_pvw_rns alone, on the device: noisy [D][L][l] power basis (host) -> out_u64 [D] */
 PVW_API int32_t pvw_decode(pvw_ctx* ctx, const uint64_t* noisy, size_t count, uint64_t* out_u64);

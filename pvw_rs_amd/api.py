@@ -887,6 +887,35 @@ def shamir_reconstruct(indices: Sequence[int], shares, plain_modulus: int):
     return int(out[0]) if single else [int(v) for v in out]
 
 
+def shamir_reconstruct_checked(params: Optional[PvwParameters], indices: Sequence[int], shares, degree: int, plain_modulus: int, *,
+                               host: bool = False, layout: str = "secret_major") -> Tuple[List[int], np.ndarray, np.ndarray]:
+    """EXTENSION: the secrets and a report on the shares they came from.  The first degree + 1 of `indices` are the
+    basis: secrets[s] is the value at 0 of the polynomial through secret s's basis shares; bad[s] counts the other columns whose
+    share is off that polynomial, col_bad[c] the secrets that deviate in column c.  shares: layout "secret_major" is
+    [num_secrets][len(indices)] (the rows of shamir_shares), "party_major" is [len(indices)][num_secrets] (what
+    decrypt_all_party_shares* returns, every dealer a secret).  On the device (pvw_shamir_reconstruct_checked); host=True: the
+    plain C++ restatement (pvw_shamir_reconstruct_checked_host, no GPU; params may be None).  Returns (secrets, bad, col_bad)."""
+    if layout not in ("secret_major", "party_major"):
+        raise ValueError(layout)
+    idx = _words(indices)
+    count = len(idx)
+    sh = np.array([[int(v) & 0xFFFFFFFFFFFFFFFF for v in row] for row in shares], dtype=np.uint64)
+    sh = sh.reshape(len(shares), -1)
+    S, cols = sh.shape if layout == "secret_major" else sh.shape[::-1]
+    if cols != count:
+        raise PvwError(15, f"expected {count} shares per secret, got {cols}")
+    strides = (count, 1) if layout == "secret_major" else (1, S)
+    out = np.zeros(S, dtype=np.uint64)
+    bad, col_bad = np.zeros(S, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
+    args = (int(plain_modulus), int(degree), _ptr(idx), count, _ptr(sh), S, strides[0], strides[1], _ptr(out), _ptr(bad), _ptr(col_bad))
+    if host:
+        L = params._lib if params is not None else _ffi.lib()
+        _check(L.pvw_shamir_reconstruct_checked_host(*args), L)
+    else:
+        params._call("pvw_shamir_reconstruct_checked", *args)
+    return [int(v) for v in out], bad, col_bad
+
+
 def encrypt_broadcast(scalar: int, global_pk: GlobalPublicKey, seed: Optional[bytes] = None, **kw) -> PvwCiphertext:
     """encryption.rs:292-296."""
     return encrypt([scalar] * global_pk.params.n, global_pk, seed, **kw)

@@ -146,6 +146,8 @@ struct Workspace {
   u64* gtmpK = nullptr;      // ... for key generation (k rows)
   u64* shares = nullptr;     // Shamir shares of one pass of dealers [SHARE_PASS][n] (pvw_deal_shares*; built with the digit buffers)
   size_t shares_bytes = 0;
+  u64* interp = nullptr;     // checked reconstruction: points | products | weight matrix (shamir_interp_words; grown by the call)
+  size_t interp_bytes = 0;
   // helper stream + events (ws_aux): decode of chunk i under the MAC of chunk i+1, key uploads under key generation
   hipStream_t aux = nullptr;
   bool aux_used = false;     // by the current host call: drained by host_call
@@ -593,6 +595,7 @@ static void ws_free(Workspace* w) {
   hipFree(w->gtmpK);
   if (w->shares) hipMemset(w->shares, 0, w->shares_bytes);   // the last deal's shares, if its wipe did not run
   hipFree(w->shares);
+  hipFree(w->interp);
   for (hipEvent_t e : w->events) hipEventDestroy(e);
   if (w->aux) hipStreamDestroy(w->aux);
   if (w->own_stream && w->stream) hipStreamDestroy(w->stream);
@@ -2033,6 +2036,198 @@ int32_t pvw_shamir_reconstruct(uint64_t plain_modulus, const uint64_t* indices, 
     out[sidx] = acc;
   }
   return PVW_OK;
+}
+
+// ------------------------------------------------------------------------ checked reconstruction
+// The basis columns 0..t give F_s; out[s] = F_s(0); every extra column is compared with F_s at its point.
+struct Reconstruct {
+  u64 p;
+  u32 degree;
+  const u64* indices;   // [count], host
+  size_t count, S, secret_stride, point_stride;
+  size_t T() const { return count - degree; }
+  size_t ws_bytes() const { return shamir_interp_words(count, degree) * 8; }
+};
+static int32_t reconstruct_checks(const Reconstruct& r, const void* shares, const void* out) {
+  if (!r.indices || !shares || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (r.S == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no secrets to reconstruct");
+  if (r.count < (size_t)r.degree + 1) {
+    char buf[96];
+    snprintf(buf, sizeof buf, "degree %u needs at least %zu shares, got %zu", r.degree, (size_t)r.degree + 1, r.count);
+    return fail(PVW_ERR_INVALID_PARAMETERS, buf);
+  }
+  {
+    std::vector<u64> sorted(r.indices, r.indices + r.count);
+    std::sort(sorted.begin(), sorted.end());
+    for (size_t i = 1; i < r.count; ++i)
+      if (sorted[i] == sorted[i - 1]) return fail(PVW_ERR_INVALID_PARAMETERS, "duplicate party index");
+  }
+  if (r.p < 2) return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must be prime (Shamir shares live in a field)");
+  for (size_t i = 0; i < r.count; ++i)
+    if (r.indices[i] >= r.p - 1) return fail(PVW_ERR_INVALID_PARAMETERS, "party index out of range for plain_modulus");
+  PVW_TRY(shamir_modulus_check(r.p));
+  if (r.secret_stride == 0 || r.point_stride == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "a stride of 0");
+  return PVW_OK;
+}
+// what the kernels' 32-bit counts hold (the host routine has no such bound)
+static int32_t reconstruct_device_checks(const Reconstruct& r) {
+  if (r.count >= ((size_t)1 << 31) || r.S >= ((size_t)1 << 31))
+    return fail(PVW_ERR_INVALID_PARAMETERS, "count and num_secrets must be below 2^31 on the device");
+  return PVW_OK;
+}
+
+// The contract in plain C++ (no GPU), written apart from the kernels' barycentric form: for every target the basis
+// polynomials L_j(x) = prod_{i != j}(x - x_i) / prod_{i != j}(x_j - x_i) are evaluated directly, then one dot product per secret.
+int32_t pvw_shamir_reconstruct_checked_host(uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                            const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                            uint64_t* out, uint32_t* bad, uint32_t* col_bad) {
+  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  PVW_TRY(reconstruct_checks(r, shares, out));
+  const Mod m = shamir_mod(plain_modulus);
+  const size_t t = degree, T = r.T();
+  std::vector<u64> x(count), inv_den(t + 1), L(t + 1);
+  for (size_t c = 0; c < count; ++c) x[c] = indices[c] + 1;
+  for (size_t j = 0; j <= t; ++j) {
+    u64 den = 1;
+    for (size_t i = 0; i <= t; ++i)
+      if (i != j) den = mulmod(den, submod(x[j], x[i], m.q), m);
+    inv_den[j] = powmod(den, m.q - 2, m);
+  }
+  if (bad) std::fill(bad, bad + num_secrets, 0u);
+  if (col_bad) std::fill(col_bad, col_bad + count, 0u);
+  for (size_t tm = 0; tm < T; ++tm) {
+    const u64 xm = tm ? x[t + tm] : 0;
+    for (size_t j = 0; j <= t; ++j) {
+      u64 num = 1;
+      for (size_t i = 0; i <= t; ++i)
+        if (i != j) num = mulmod(num, submod(xm, x[i], m.q), m);
+      L[j] = mulmod(num, inv_den[j], m);
+    }
+    for (size_t s = 0; s < num_secrets; ++s) {
+      const u64* row = shares + s * secret_stride;
+      u64 v = 0;
+      for (size_t j = 0; j <= t; ++j) v = addmod(v, mulmod(reduce_word(row[j * point_stride], m), L[j], m), m.q);
+      if (tm == 0) {
+        out[s] = v;
+      } else if (reduce_word(row[(t + tm) * point_stride], m) != v) {
+        if (bad) ++bad[s];
+        if (col_bad) ++col_bad[t + tm];
+      }
+    }
+  }
+  return PVW_OK;
+}
+
+// the points and the weight matrix of one call into ws (shamir_interp_words words)
+static int32_t reconstruct_weights(pvw_ctx* c, const Reconstruct& r, u64* ws, hipStream_t s) {
+  ProfScope ps(c, "shamir_weights", s);
+  PVW_HIP(launch_shamir_points(r.indices, r.count, ws, s));
+  PVW_HIP(launch_shamir_weights(ws, r.count, r.degree, shamir_mod(r.p), s));
+  return PVW_OK;
+}
+// ns secrets from d_shares under the weights in ws: out and bad of these secrets; col_bad, zeroed by the caller, is added to
+static int32_t reconstruct_interp(pvw_ctx* c, const Reconstruct& r, const u64* ws, const u64* d_shares, size_t ns, size_t secret_stride,
+                                  size_t point_stride, u64* d_out, u32* d_bad, u32* d_col_bad, hipStream_t s) {
+  ProfScope ps(c, "shamir_interp", s);
+  PVW_HIP(launch_shamir_zero_counts(d_bad, ns, s));
+  ShamirInterp b{};
+  b.shares = d_shares;
+  b.secret_stride = secret_stride;
+  b.point_stride = point_stride;
+  b.W = ws + 2 * r.count + 1;
+  b.out = d_out;
+  b.bad = d_bad;
+  b.col_bad = d_col_bad;
+  b.ns = (u32)ns;
+  b.degree = r.degree;
+  b.T = (u32)r.T();
+  b.m = shamir_mod(r.p);
+  PVW_HIP(launch_shamir_interp(b, s));
+  return PVW_OK;
+}
+
+// Under stream capture the call may not allocate: the stream's workspace must hold a weight buffer of this call's size, which an
+// earlier call with the same (degree, count) outside capture leaves (checked before the workspace is looked up, like
+// multi_capture_check, and refused with the same code)
+static int32_t reconstruct_capture_check(pvw_ctx* c, hipStream_t s, size_t need) {
+  if (!stream_capturing(s)) return PVW_OK;
+  bool ready;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    auto it = c->async_ws.find((void*)s);
+    ready = it != c->async_ws.end() && it->second->interp_bytes >= need;
+  }
+  if (!ready)
+    return fail(PVW_ERR_INVALID_PARAMETERS, "checked reconstruction under stream capture: run a call with the same degree and count on "
+                                            "this stream outside capture first (it sizes the workspace)");
+  return PVW_OK;
+}
+
+int32_t pvw_shamir_reconstruct_checked_device(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
+                                              size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
+                                              size_t point_stride, uint64_t* d_out, uint32_t* d_bad, uint32_t* d_col_bad, void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  PVW_TRY(reconstruct_checks(r, d_shares, d_out));
+  PVW_TRY(reconstruct_device_checks(r));
+  // A context that has not touched its device yet initialises it inside device_call (allocations, a wait): on a capturing
+  // stream that would invalidate the caller's capture, and nothing can have sized the workspace.  So the caller's stream is
+  // checked before anything else; the context's own stream (stream == NULL) exists only once the device is initialised.
+  if (stream) PVW_TRY(reconstruct_capture_check(c, (hipStream_t)stream, r.ws_bytes()));
+  return device_call(c, stream, [&](hipStream_t s) { return reconstruct_capture_check(c, s, r.ws_bytes()); },
+                     [&](Workspace* w, hipStream_t s) -> int32_t {
+                       PVW_TRY(ws_grow(&w->interp, &w->interp_bytes, r.ws_bytes(), s, false));   // public: nothing to clear
+                       PVW_TRY(reconstruct_weights(c, r, w->interp, s));
+                       PVW_HIP(launch_shamir_zero_counts(d_col_bad, count, s));
+                       return reconstruct_interp(c, r, w->interp, d_shares, num_secrets, secret_stride, point_stride, d_out, d_bad,
+                                                 d_col_bad, s);
+                     });
+}
+
+// host buffers: the secrets go up in pieces of `per` (<= ~1 GiB of shares), each packed to [piece][count]; the weights are
+// made once.  The staged shares and the staged results are secret; the weights and the counts are not.
+int32_t pvw_shamir_reconstruct_checked(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                       const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                       uint64_t* out, uint32_t* bad, uint32_t* col_bad) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  PVW_TRY(reconstruct_checks(r, shares, out));
+  PVW_TRY(reconstruct_device_checks(r));
+  PVW_TRY(ensure_device(c));
+  const size_t per = chunk_1gib((count + 1) * 8 + 4, num_secrets);
+  Scratch sc;
+  const size_t r_sh = sc.add(per * count * 8), r_out = sc.add(per * 8), r_ws = sc.add(r.ws_bytes()), r_bad = sc.add(per * 4),
+               r_col = sc.add(count * 4);
+  std::vector<u64> packed;                                       // a piece's shares when the caller's rows are not dense
+  const bool dense = point_stride == 1 && secret_stride >= count;   // whole rows go up as they lie (a 2D copy)
+  if (!dense) packed.resize(per * count);
+  const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    sc.secret(w, r_sh, r_out);
+    u64 *d_sh = sc.at(r_sh), *d_out = sc.at(r_out), *ws = sc.at(r_ws);
+    u32 *d_bad = bad ? sc.at<u32>(r_bad) : nullptr, *d_col = col_bad ? sc.at<u32>(r_col) : nullptr;
+    PVW_TRY(reconstruct_weights(c, r, ws, w->stream));
+    PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
+    for (size_t s0 = 0; s0 < num_secrets; s0 += per) {
+      const size_t cnt = (num_secrets - s0) < per ? (num_secrets - s0) : per;
+      if (dense) {
+        PVW_HIP(hipMemcpy2DAsync(d_sh, count * 8, shares + s0 * secret_stride, secret_stride * 8, count * 8, cnt, hipMemcpyHostToDevice, w->stream));
+      } else {
+        for (size_t s = 0; s < cnt; ++s)
+          for (size_t col = 0; col < count; ++col) packed[s * count + col] = shares[(s0 + s) * secret_stride + col * point_stride];
+        PVW_HIP(hipMemcpyAsync(d_sh, packed.data(), cnt * count * 8, hipMemcpyHostToDevice, w->stream));
+      }
+      PVW_TRY(reconstruct_interp(c, r, ws, d_sh, cnt, count, 1, d_out, d_bad, d_col, w->stream));
+      PVW_HIP(hipMemcpyAsync(out + s0, d_out, cnt * 8, hipMemcpyDeviceToHost, w->stream));
+      if (bad) PVW_HIP(hipMemcpyAsync(bad + s0, d_bad, cnt * 4, hipMemcpyDeviceToHost, w->stream));
+      PVW_HIP(hipStreamSynchronize(w->stream));                // the next piece reuses the staging
+    }
+    if (col_bad) PVW_HIP(hipMemcpyAsync(col_bad, d_col, count * 4, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
+  volatile u64* vp = packed.data();                              // the host copy is as secret as the caller's shares
+  for (size_t i = 0; i < packed.size(); ++i) vp[i] = 0;
+  return rc;
 }
 
 // One call's Shamir sharing on the device (pvw_shamir_shares*, and pvw_deal_shares* through encrypt_multi_enqueue)

@@ -239,6 +239,32 @@ struct ShamirBatch {
 };
 hipError_t launch_shamir_eval(const ShamirBatch& b, hipStream_t s);
 
+// ---- Checked reconstruction (pvw_shamir.hip).  Columns 0..t of the share matrix are the basis, columns
+// t+1..count-1 the extras; T = count - t targets: target 0 is x = 0, target m >= 1 the point of column t + m.
+// Workspace words: x [count] | aux [count + 1] | W [t+1][T].  aux[j] = (prod_{i != j}(x_j - x_i))^-1 for j <= t and
+// aux[t + 1 + m] = prod_i (x_m - x_i) over the basis; W[j][m] = L_j(x_m), the basis polynomial of column j at target m.
+inline size_t shamir_interp_words(size_t count, u32 t) { return 2 * count + 1 + ((size_t)t + 1) * (count - t); }
+#define PVW_SHAMIR_POINTS 256                            // indices per launch of the point upload (kernel arguments)
+struct ShamirPoints {
+  u64 index[PVW_SHAMIR_POINTS];   // party indices; x = index + 1
+  u64* x;                         // where the first of them goes
+  u32 n;
+};
+struct ShamirInterp {
+  const u64* shares;     // element (s, c) at shares[s * secret_stride + c * point_stride], any word, read mod m.q
+  size_t secret_stride, point_stride;
+  const u64* W;          // [t+1][T]
+  u64* out;              // [ns]
+  u32* bad;              // [ns] or NULL; zeroed by the caller (launch_shamir_zero_counts), the kernel adds
+  u32* col_bad;          // [count] or NULL; likewise
+  u32 ns, degree, T;
+  Mod m;
+};
+hipError_t launch_shamir_zero_counts(u32* p, size_t n, hipStream_t s);   // p[0 .. n) = 0, as a kernel launch on s
+hipError_t launch_shamir_points(const u64* indices, size_t count, u64* x, hipStream_t s);
+hipError_t launch_shamir_weights(u64* ws, size_t count, u32 degree, const Mod& m, hipStream_t s);
+hipError_t launch_shamir_interp(const ShamirInterp& b, hipStream_t s);
+
 // p[0 .. words) = 0, as a kernel launch on s
 hipError_t launch_wipe_words(u64* p, size_t words, hipStream_t s);
 

@@ -146,4 +146,219 @@ hipError_t launch_shamir_eval(const ShamirBatch& b, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------ checked reconstruction
+// The way back: out[s] = F_s(0) for the polynomial F_s of degree <= t through the basis columns 0..t of secret s, and every
+// extra column t+1..count-1 compared with F_s at its point.  Both are one product shares[S][t+1] x W[t+1][T] over Z_p, with
+// W[j][m] = L_j(x_m) the basis polynomial of column j at target m (target 0: x = 0; target m >= 1: the point of column t + m).
+//
+// Weights, barycentric: aux[j] = (prod_{i != j}(x_j - x_i))^-1 and aux[t + 1 + m] = prod_i (x_m - x_i), one wave per product
+// (shamir_prod_kernel), then W[j][m] = aux[t + 1 + m] aux[j] (x_m - x_j)^-1 with one Fermat inversion per element
+// (shamir_weights_kernel).  x_m - x_j is never 0: the points are distinct, below p, and 0 is no party's point.
+// Interpolation: the frame of shamir_eval_kernel with the roles turned round.  A lane owns one target and SH_DG secrets; the
+// four waves own the same 64 targets and secrets and a quarter of the t + 1 terms each.  The chunk's shares are wave-uniform:
+// the workgroup stages them in LDS ([wave][term][secret], reduced below p) and lanes read them back as broadcasts, W[j][m] is
+// one coalesced 8-byte load per lane and term, and the four partial sums meet in LDS.
+
+// x[i] = index[i] + 1 for the indices of one launch's arguments: the indices are a HOST array of the caller's, and kernel
+// arguments are the one way up that neither waits nor reads the array again when a captured call is replayed
+__global__ __launch_bounds__(PVW_SHAMIR_POINTS) void shamir_points_kernel(ShamirPoints a) {
+  if (threadIdx.x < a.n) a.x[threadIdx.x] = a.index[threadIdx.x] + 1;
+}
+
+__device__ __forceinline__ u64 invmod_dev(u64 a, const Mod& m) {   // a^(p - 2)
+  u64 r = 1, e = m.q - 2;
+  while (e) {
+    if (e & 1) r = mulmod(r, a, m);
+    a = mulmod(a, a, m);
+    e >>= 1;
+  }
+  return r;
+}
+
+// item e = blockIdx.x * 4 + wave of [0, count + 1): e <= t is basis column e (the product leaves i = e out and is inverted),
+// e = t + 1 + m is target m.  64 lanes take the factors i = lane, lane + 64, ...; the 64 partial products meet in LDS.
+__global__ __launch_bounds__(256) void shamir_prod_kernel(const u64* x, u64* aux, size_t count, u32 t, Mod m) {
+  __shared__ u64 red[SH_WAVES][64];
+  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const size_t e = (size_t)blockIdx.x * SH_WAVES + wave;
+  const bool live = e <= count;
+  const bool basis = e <= t;
+  u64 xe = 0;                                                    // target 0
+  if (live && basis) xe = x[e];
+  else if (live && e > (size_t)t + 1) xe = x[e - 1];             // target m >= 1 is column t + m = e - 1
+  u64 prod = 1;
+  if (live)
+    for (u32 i = lane; i <= t; i += 64)
+      if (!(basis && i == e)) prod = mulmod(prod, submod(xe, x[i], m.q), m);
+  red[wave][lane] = prod;
+  __syncthreads();
+  if (lane == 0 && live) {
+    u64 r = red[wave][0];
+    for (u32 i = 1; i < 64; ++i) r = mulmod(r, red[wave][i], m);
+    aux[e] = basis ? invmod_dev(r, m) : r;
+  }
+}
+
+// one thread per element of W, the target fastest (W is row-major in the target)
+__global__ __launch_bounds__(256) void shamir_weights_kernel(const u64* x, const u64* aux, u64* W, size_t count, u32 t, Mod m) {
+  const size_t T = count - t;
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= ((size_t)t + 1) * T) return;
+  const size_t j = e / T, tm = e % T;
+  const u64 xm = tm ? x[t + tm] : 0;
+  const u64 inv = invmod_dev(submod(xm, x[j], m.q), m);
+  W[e] = mulmod(mulmod(aux[(size_t)t + 1 + tm], aux[j], m), inv, m);
+}
+
+// grid: x = blocks of 64 targets, y = groups of SH_DG secrets; 256 threads.
+__global__ __launch_bounds__(256) void shamir_interp_kernel(ShamirInterp b) {
+  __shared__ u64 sh[SH_WAVES][SH_JC][SH_DG];       // 8 KiB: the chunk's shares, below p
+  __shared__ u64 part[SH_WAVES][SH_DG][64];        // 8 KiB: the waves' partial sums, below p
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const Mod m = b.m;
+  const u32 nt = b.degree + 1;                     // terms: the basis columns
+  const u32 s0 = blockIdx.y * SH_DG;
+  const size_t tm = (size_t)blockIdx.x * 64 + lane;
+  const bool live = tm < b.T;
+  // wave w owns terms j = w * Q + [0, Q), cut off at nt; every wave walks the same number of chunks (barriers)
+  const u32 Q = (nt + SH_WAVES - 1) / SH_WAVES;
+  const u32 jw0 = wave * Q;
+  const u32 nchunks = (Q + SH_JC - 1) / SH_JC;
+  // the staging walks whichever of the two strides is the shorter one with neighbouring lanes
+  const bool term_fast = b.point_stride <= b.secret_stride;
+  const u64* wcol = b.W + (live ? tm : 0);
+  Acc acc[SH_DG];
+#pragma unroll
+  for (int g = 0; g < SH_DG; ++g) acc_zero(acc[g]);
+  for (u32 c = 0; c < nchunks; ++c) {
+    // ---- staging: entry e = (wave, term, secret) of the chunk, one per lane and trip ----
+    for (u32 e = tid; e < SH_WAVES * SH_JC * SH_DG; e += 256) {
+      const u32 ew = e / (SH_JC * SH_DG);
+      const u32 ej = term_fast ? e % SH_JC : (e / SH_DG) % SH_JC;
+      const u32 eg = term_fast ? (e / SH_JC) % SH_DG : e % SH_DG;
+      const u32 off = c * SH_JC + ej;              // within the wave's range
+      const u32 j = ew * Q + off;
+      u64 a = 0;
+      if (off < Q && j < nt && s0 + eg < b.ns)
+        a = reduce_word(b.shares[(size_t)(s0 + eg) * b.secret_stride + (size_t)j * b.point_stride], m);
+      sh[ew][ej][eg] = a;
+    }
+    __syncthreads();
+    // ---- this wave's terms of the chunk ----
+    const u32 base = c * SH_JC;
+    u32 cnt = 0;
+    if (base < Q && jw0 + base < nt) {
+      cnt = Q - base < SH_JC ? Q - base : SH_JC;
+      const u32 left = nt - (jw0 + base);
+      cnt = left < cnt ? left : cnt;
+    }
+    const u64* wp = wcol + (size_t)(jw0 + base) * b.T;
+    u32 jj = 0;
+    for (; jj + 4 <= cnt; jj += 4) {               // four weights in flight ahead of their multiply-adds
+      u64 w[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) w[u] = live ? wp[(size_t)u * b.T] : 0;
+      wp += (size_t)4 * b.T;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        u64 a[SH_DG];
+#pragma unroll
+        for (int g = 0; g < SH_DG; ++g) a[g] = sh[wave][jj + u][g];
+#pragma unroll
+        for (int g = 0; g < SH_DG; ++g) acc_mac_dev(acc[g], a[g], w[u]);
+      }
+    }
+    for (; jj < cnt; ++jj) {
+      const u64 w = live ? *wp : 0;
+      wp += b.T;
+      u64 a[SH_DG];
+#pragma unroll
+      for (int g = 0; g < SH_DG; ++g) a[g] = sh[wave][jj][g];
+#pragma unroll
+      for (int g = 0; g < SH_DG; ++g) acc_mac_dev(acc[g], a[g], w);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int g = 0; g < SH_DG; ++g) part[wave][g][lane] = acc_reduce(acc[g], m);
+  __syncthreads();
+  // thread (g, lane) adds the four partial sums of secret s0 + g at its target: target 0 is the secret, every other target
+  // is compared with the share of its column
+  {
+    const u32 g = wave;                            // SH_WAVES == SH_DG
+    const u32 s = s0 + g;
+    bool dev = false;
+    if (live && s < b.ns) {
+      u64 v = 0;
+#pragma unroll
+      for (int w = 0; w < SH_WAVES; ++w) v = addmod(v, part[w][g][lane], m.q);
+      if (tm == 0) {
+        b.out[s] = v;
+      } else {
+        const size_t col = (size_t)b.degree + tm;
+        dev = reduce_word(b.shares[(size_t)s * b.secret_stride + col * b.point_stride], m) != v;
+        if (dev && b.col_bad) atomicAdd(&b.col_bad[col], 1u);
+      }
+    }
+    // one add per wave: the wave's lanes share the secret
+    const u32 ndev = (u32)__popcll(__ballot(dev));
+    if (lane == 0 && ndev && b.bad && s < b.ns) atomicAdd(&b.bad[s], ndev);
+  }
+}
+
+// bad / col_bad start from 0 on every call and on every replay of a captured one: a kernel in stream order, not a memset node
+// (DESIGN 8.7 found memset nodes not to clear on replay)
+__global__ __launch_bounds__(256) void shamir_zero_counts_kernel(u32* p, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = 0;
+}
+hipError_t launch_shamir_zero_counts(u32* p, size_t n, hipStream_t s) {
+  if (!p || !n) return hipSuccess;
+  const size_t blocks = (n + 255) / 256;
+  shamir_zero_counts_kernel<<<dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, s>>>(p, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_shamir_points(const u64* indices, size_t count, u64* x, hipStream_t s) {
+  for (size_t i0 = 0; i0 < count; i0 += PVW_SHAMIR_POINTS) {
+    ShamirPoints a;
+    a.n = (u32)(count - i0 < PVW_SHAMIR_POINTS ? count - i0 : PVW_SHAMIR_POINTS);
+    for (u32 i = 0; i < PVW_SHAMIR_POINTS; ++i) a.index[i] = i < a.n ? indices[i0 + i] : 0;
+    a.x = x + i0;
+    shamir_points_kernel<<<dim3(1), dim3(PVW_SHAMIR_POINTS), 0, s>>>(a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// ws: x [count] (filled by launch_shamir_points) | aux [count + 1] | W [t+1][count-t]
+hipError_t launch_shamir_weights(u64* ws, size_t count, u32 t, const Mod& m, hipStream_t s) {
+  const u64* x = ws;
+  u64 *aux = ws + count, *W = aux + count + 1;
+  shamir_prod_kernel<<<dim3((unsigned)((count + 1 + SH_WAVES - 1) / SH_WAVES)), dim3(256), 0, s>>>(x, aux, count, t, m);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const size_t elems = ((size_t)t + 1) * (count - t);
+  shamir_weights_kernel<<<dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, s>>>(x, aux, W, count, t, m);
+  return hipGetLastError();
+}
+
+// the grid's y dimension holds 65535 groups of secrets: more secrets take more launches
+hipError_t launch_shamir_interp(const ShamirInterp& b, hipStream_t s) {
+  if (b.ns == 0 || b.T == 0) return hipSuccess;
+  const u32 per = 65535u * SH_DG;
+  for (u32 s0 = 0; s0 < b.ns; s0 += per) {
+    ShamirInterp p = b;
+    p.ns = b.ns - s0 < per ? b.ns - s0 : per;
+    p.shares = b.shares + (size_t)s0 * b.secret_stride;
+    p.out = b.out + s0;
+    p.bad = b.bad ? b.bad + s0 : nullptr;
+    const dim3 grid((b.T + 63) / 64, (p.ns + SH_DG - 1) / SH_DG);
+    shamir_interp_kernel<<<grid, dim3(256), 0, s>>>(p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 }  // namespace pvw

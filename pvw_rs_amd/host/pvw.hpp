@@ -666,6 +666,29 @@ inline std::vector<uint64_t> shamir_reconstruct(const std::vector<uint64_t>& ind
   check(pvw_shamir_reconstruct(plain_modulus, indices.data(), shares.data(), indices.size(), out.size(), out.data()));
   return out;
 }
+// ---- checked reconstruction ----
+struct CheckedSecrets {
+  std::vector<uint64_t> secrets;    // [num_secrets]: the value at 0 of the polynomial through each secret's basis shares
+  std::vector<uint32_t> bad;        // [num_secrets]: columns beyond the basis whose share is off that polynomial
+  std::vector<uint32_t> col_bad;    // [indices.size()]: secrets that deviate in each column (0 for the basis columns)
+};
+// The first degree + 1 of `indices` are the basis.  shares: party_major = false: [num_secrets][indices.size()] (the rows of
+// shamir_shares); true: [indices.size()][num_secrets] (what decrypt_all_party_shares* returns, every dealer a secret).
+// On the device (pvw_shamir_reconstruct_checked); host = true: the plain C++ restatement (no GPU, p may be null).
+inline CheckedSecrets shamir_reconstruct_checked(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& indices,
+                                                 const std::vector<uint64_t>& shares, uint32_t degree, uint64_t plain_modulus,
+                                                 bool host = false, bool party_major = false) {
+  const size_t count = indices.size();
+  if (count == 0 || shares.empty() || shares.size() % count) throw PvwError(15, "shares must hold one value per index and secret");
+  const size_t S = shares.size() / count;
+  CheckedSecrets r{std::vector<uint64_t>(S), std::vector<uint32_t>(S), std::vector<uint32_t>(count)};
+  const size_t ss = party_major ? 1 : count, ps = party_major ? S : 1;
+  check(host ? pvw_shamir_reconstruct_checked_host(plain_modulus, degree, indices.data(), count, shares.data(), S, ss, ps,
+                                                   r.secrets.data(), r.bad.data(), r.col_bad.data())
+             : pvw_shamir_reconstruct_checked(p->ctx, plain_modulus, degree, indices.data(), count, shares.data(), S, ss, ps,
+                                              r.secrets.data(), r.bad.data(), r.col_bad.data()));
+  return r;
+}
 
 // the sum of the valid dealers' ciphertexts (pvw_ct_sum): same parameters and representation, no key needed
 inline PvwCiphertext aggregate_ciphertexts(const std::vector<PvwCiphertext>& cts, const std::vector<bool>& valid = {}) {

@@ -156,6 +156,10 @@ extern "C" {
     pub fn pvw_deal_shares_rs(ctx: *mut PvwCtx, secrets: *const u64, num_dealers: usize, degree: u32, plain_modulus: u64, st: *mut c_void, c1_out: *mut u64, c2_out: *mut u64, out_repr: u32) -> i32;
     pub fn pvw_deal_shares_rs_device(ctx: *mut PvwCtx, d_secrets: *const u64, num_dealers: usize, degree: u32, plain_modulus: u64, st: *mut c_void, d_c1: *mut u64, d_c2: *mut u64, out_repr: u32, stream: *mut c_void) -> i32;
     pub fn pvw_shamir_reconstruct(plain_modulus: u64, indices: *const u64, shares: *const u64, count: usize, num_secrets: usize, out: *mut u64) -> i32;
+    // ---- checked reconstruction --------------------------------------------------
+    pub fn pvw_shamir_reconstruct_checked_host(plain_modulus: u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, out: *mut u64, bad: *mut u32, col_bad: *mut u32) -> i32;
+    pub fn pvw_shamir_reconstruct_checked_device(ctx: *mut PvwCtx, plain_modulus: u64, degree: u32, indices: *const u64, count: usize, d_shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, d_out: *mut u64, d_bad: *mut u32, d_col_bad: *mut u32, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_reconstruct_checked(ctx: *mut PvwCtx, plain_modulus: u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, out: *mut u64, bad: *mut u32, col_bad: *mut u32) -> i32;
     // ---- decrypt (src/crypto/decryption.rs:249-325) and gadget decode (:10-247) ---------------
     pub fn pvw_decrypt_batch(ctx: *mut PvwCtx, sk: *const i64, c1s: *const u64, c2col: *const u64, num_dealers: usize, in_repr: u32, out_u64: *mut u64, noisy_out: *mut u64) -> i32;
     pub fn pvw_decrypt_noisy_device(ctx: *mut PvwCtx, d_sk: *const i64, d_c1s: *const u64, d_c2col: *const u64, num_dealers: usize, in_repr: u32, d_noisy: *mut u64, stream: *mut c_void) -> i32;

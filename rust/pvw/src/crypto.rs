@@ -483,6 +483,34 @@ pub fn shamir_reconstruct(indices: &[u64], shares: &[u64], plain_modulus: u64) -
     Ok(out)
 }
 
+/// EXTENSION: what `shamir_reconstruct_checked` reports.
+pub struct CheckedSecrets {
+    /// the value at 0 of the polynomial through each secret's basis shares
+    pub secrets: Vec<u64>,
+    /// per secret: columns beyond the basis whose share is off that polynomial
+    pub bad: Vec<u32>,
+    /// per column: secrets that deviate there (0 for the basis columns)
+    pub col_bad: Vec<u32>,
+}
+
+/// EXTENSION: the secrets and a report on the shares, on the device (`pvw_shamir_reconstruct_checked`).  The
+/// first `degree + 1` of `indices` are the basis.  `shares` is `[num_secrets][indices.len()]` row-major, or with
+/// `party_major` `[indices.len()][num_secrets]` (what `decrypt_all_party_shares` returns, every dealer a secret).
+pub fn shamir_reconstruct_checked(params: &Arc<PvwParameters>, indices: &[u64], shares: &[u64], degree: u32, plain_modulus: u64,
+                                  party_major: bool) -> Result<CheckedSecrets> {
+    if indices.is_empty() || shares.is_empty() || shares.len() % indices.len() != 0 {
+        return Err(PvwError::InvalidParameters("shares must hold one value per index and secret".into()));
+    }
+    let (count, num) = (indices.len(), shares.len() / indices.len());
+    let (ss, ps) = if party_major { (1, num) } else { (count, 1) };
+    let mut r = CheckedSecrets { secrets: vec![0u64; num], bad: vec![0u32; num], col_bad: vec![0u32; count] };
+    check(unsafe {
+        sys::pvw_shamir_reconstruct_checked(params.hip.raw(), plain_modulus, degree, indices.as_ptr(), count, shares.as_ptr(), num, ss, ps,
+                                            r.secrets.as_mut_ptr(), r.bad.as_mut_ptr(), r.col_bad.as_mut_ptr())
+    })?;
+    Ok(r)
+}
+
 /// EXTENSION: the sum of the valid dealers' ciphertexts (`pvw_ct_sum`) -- a ciphertext of the sum of their
 /// shares under the same keys, folded without any key.  What examples/pvw_valid_dec.rs:150-209 reaches by decrypting every
 /// dealer's share and adding the results; the noise of the sum is the sum of the dealers' noises (`pvw_ctx_sum_capacity`).
