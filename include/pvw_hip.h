@@ -28,6 +28,21 @@
  *     and safe to call concurrently on one context, as rayon does with
  *     `encrypt` (src/crypto/encryption.rs:277-283): device tensors are
  *     read-only after load and every call takes a stream + workspace from a pool.
+ *     The promise, as tests/test_gpu_concurrent_calls.py holds it: threads that share one context may overlap any of
+ *     pvw_encrypt[_rs], pvw_encrypt_multi[_rs], pvw_deal_shares[_rs], pvw_shamir_shares, pvw_shamir_reconstruct_checked,
+ *     pvw_decrypt_batch / _checked / _plain, pvw_decrypt_all / _checked / _plain, pvw_ct_sum, pvw_decrypt_sum_checked,
+ *     pvw_decrypt_all_sum_checked, pvw_decode / _checked / _plain, pvw_wire_pack / _unpack, pvw_ntt_forward / _inverse,
+ *     pvw_sample_cbd / _uniform / _gaussian, pvw_sk_load / pvw_sk_free, and *_device calls that each thread enqueues on a
+ *     stream of its own -- the context's first calls included (device initialisation and the derived copies are built
+ *     once, under a lock).  Every result is the serial one bit for bit, pvw_last_error stays the calling thread's, and a
+ *     pooled workspace that goes from one kind of call to another carries nothing over (pvw_selftest_secret_residue).
+ *     OUTSIDE the promise, because they change the resident matrices or share a caller-owned object:
+ *       pvw_load_crs* / pvw_load_pk* (the _wire forms too), pvw_keygen, pvw_pk_fill_uniform, pvw_crs_generate and
+ *       pvw_ctx_set_roots next to any other call on the context (GlobalPublicKey's mutators take &mut self,
+ *       public_key.rs:214-263: a change and a use never overlap);
+ *       two threads drawing from one pvw_rnd_state (it is ordered by one stream at a time, see below);
+ *       two threads enqueueing *_device calls on the SAME stream (the stream's workspace is protected by stream order,
+ *       which two enqueueing threads do not have).
  *   - *_device calls take device pointers and a hipStream_t (as void*; NULL =
  *     the context's own stream) and enqueue asynchronously.  They do not
  *     synchronise or allocate ONCE pvw_prepare() has run for that stream since

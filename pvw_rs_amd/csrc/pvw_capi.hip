@@ -158,14 +158,34 @@ struct Workspace {
   // the last call that had any cleared, for pvw_selftest_secret_residue.
   struct Span { void* p; size_t bytes; bool cleared; };
   std::vector<Span> secrets, wiped;
+  // from this byte on the r-hat block holds the r-hat vectors of an encrypt (not key material), written since a key-bearing
+  // call last marked that part: see ws_public.  A call that then marks the front of the block secret clears the front only.
+  size_t rhat_public_from = SIZE_MAX;
 };
 // cleared: a kernel has cleared the region already (the wipe records it without a memset).  Marking a region again
 // replaces its earlier mark.
 static void ws_mark_secret(Workspace* w, void* p, size_t bytes, bool cleared = false) {
   if (!p || !bytes) return;
+  if (p == (void*)w->rhat && w->rhat_public_from < bytes) w->rhat_public_from = bytes;
   for (Workspace::Span& sp : w->secrets)
     if (sp.p == p) { sp.bytes = bytes > sp.bytes ? bytes : sp.bytes; sp.cleared = cleared; return; }
   w->secrets.push_back(Workspace::Span{p, bytes, cleared});
+}
+// The current call is about to write data that is NOT key material into [p, p + bytes) of the workspace: the scratch block of a
+// call that marks nothing there, the r-hat of an encrypt.  A pooled workspace goes from one kind of call to another, so the
+// block may be what an earlier call declared secret and cleared; it is the new owner's now, and `wiped` (and the standing scan
+// of the r-hat block) no longer answers for it -- pvw_selftest_secret_residue would count the new owner's data as a leftover
+// key.  A region the current call itself holds as secret stays so.
+static void ws_public(Workspace* w, void* p, size_t bytes) {
+  if (!p || !bytes) return;
+  const char *lo = (const char*)p, *hi = lo + bytes;
+  for (const Workspace::Span& sp : w->secrets)
+    if ((const char*)sp.p >= lo && (const char*)sp.p < hi) return;
+  size_t kept = 0;
+  for (const Workspace::Span& sp : w->wiped)
+    if ((const char*)sp.p < lo || (const char*)sp.p >= hi) w->wiped[kept++] = sp;
+  w->wiped.resize(kept);
+  if (p == (void*)w->rhat) w->rhat_public_from = 0;
 }
 // enqueue the wipes on `s` (call after the last kernel that reads the regions has been enqueued on `s`); nothing
 // marked: nothing enqueued, and the record of the last wipe stays
@@ -536,6 +556,7 @@ static int32_t ws_host_buffers(pvw_ctx* c, Workspace* w) {
   return PVW_OK;
 }
 static int32_t ws_scratch(Workspace* w, size_t bytes) {
+  ws_public(w, w->scratch, w->scratch_bytes);              // whatever the call marks secret in it comes back through its own wipe
   if (w->scratch_bytes >= bytes) return PVW_OK;
   // callers grow the scratch before they enqueue anything that uses it; whatever an earlier call left there is
   // cleared before the block goes back to the allocator
@@ -1483,7 +1504,7 @@ int32_t pvw_selftest_secret_residue(pvw_ctx* c, uint64_t* nonzero_words, uint64_
   std::vector<u64> host;
   for (Workspace* w : all) {
     std::vector<Workspace::Span> spans = w->wiped;
-    if (w->rhat) spans.push_back(Workspace::Span{w->rhat, w->rhat_bytes});
+    if (w->rhat) spans.push_back(Workspace::Span{w->rhat, w->rhat_bytes < w->rhat_public_from ? w->rhat_bytes : w->rhat_public_from});
     for (const Workspace::Span& sp : spans) {
       const size_t step = (size_t)64 << 20;
       for (size_t off = 0; off < sp.bytes; off += step) {
@@ -1814,6 +1835,7 @@ static int32_t encrypt_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, c
   // first call after a matrix change (and no pvw_prepare since): builds the packed copies -- allocates and synchronises
   const u32 width = ensure_packed(c, s, !stream_capturing(s));
   PrologueBatch pb{};
+  ws_public(w, w->rhat, w->rhat_bytes);                  // r-hat of this encrypt
   PVW_TRY(fill_encrypt_jobs(c, pb, 0, ex, d_scalars, w->rhat, d_c1, d_c2));
   keys.fill(pb, 1);
   // l <= 16: the addends travel in COMPACT form -- the prologue transforms r only and leaves the sampled e1 / e2 coefficients as
@@ -2320,6 +2342,7 @@ static int32_t encrypt_multi_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scal
   // matrix-core passes: the c2 finish pass draws e2 and encodes the scalars itself (tuning build: PVW_FUSED_E2=0 the prologue does)
   const bool fused_e2 = use_gemm && l <= 32 && PVW_ENV_INT("PVW_FUSED_E2", 1) != 0;
   u64* vh = use_gemm ? w->vhat16 : w->rhat;
+  if (!use_gemm) ws_public(w, w->rhat, w->rhat_bytes);   // the dealers' r-hat (a deal has marked the block: it stays secret)
   RndState* rs = keys.state();
   for (size_t d0 = 0; d0 < D; d0 += group) {
     const u32 nv = (u32)((D - d0) < group ? (D - d0) : group);
