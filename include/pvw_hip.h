@@ -638,6 +638,45 @@ PVW_API int32_t pvw_shamir_reconstruct_checked_device(pvw_ctx* ctx, uint64_t pla
 PVW_API int32_t pvw_shamir_reconstruct_checked(pvw_ctx* ctx, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
                                                size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
                                                size_t point_stride, uint64_t* out, uint32_t* bad, uint32_t* col_bad);
+/* Corrected reconstruction: the secrets although some shares are wrong, and which shares those are.  The shares of
+ * one secret are a Reed-Solomon codeword of length count and dimension t + 1.  Write r = count - t - 1 (the redundant columns)
+ * and E = r / 2 (rounded down).  Arguments as the checked calls; the contract is the library's own (the reference has none).
+ *   Secret s is DECODABLE iff some polynomial F_s of degree <= t disagrees with row s (read mod p) in at most E columns; that
+ *   F_s is then unique.
+ *   decodable:   out[s] = F_s(0); nerr[s] = the number of disagreeing columns; bit c % 64 of err_mask[s * W + c / 64]
+ *                (W = ceil(count / 64)) is set exactly for them; col_err[c] counts the decodable secrets that disagree in column c.
+ *   undecodable: out[s] = 0, nerr[s] = PVW_SHAMIR_UNDECODABLE, its mask row is 0, and it adds nothing to col_err.
+ *   nerr [num_secrets], col_err [count] and err_mask [num_secrets][W] may each be NULL.
+ *   r = 0 is plain interpolation through all columns; r = 1 detects only (E = 0: one wrong share makes the secret undecodable).
+ *   No column is a basis: a wrong share in any column is corrected alike, and the order of the columns changes no output
+ *   (mask bits and col_err move with their columns).
+ *   Every output is a function of the inputs alone, and the three forms agree bit for bit -- also for a p so small that a row
+ *   with more than E wrong shares lies within E of ANOTHER polynomial: the row is decodable by the definition above, to that one.
+ * The corrected share values are not returned: F_s is out[s] and t more of the shares that the mask leaves.
+ * PVW_ERR_INVALID_PARAMETERS before any device work, nothing written: as the checked calls; on the device also
+ * E + 1 > 4096 (count - degree - 1 >= 8192). */
+#define PVW_SHAMIR_UNDECODABLE 0xFFFFFFFFu
+/* the contract in plain C++ on the host cores (no context, no GPU), by Berlekamp-Welch and Gaussian elimination (cubic in count
+ * per secret): what the kernels are tested against */
+PVW_API int32_t pvw_shamir_reconstruct_corrected_host(uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                                      const uint64_t* shares, size_t num_secrets, size_t secret_stride,
+                                                      size_t point_stride, uint64_t* out, uint32_t* nerr, uint32_t* col_err,
+                                                      uint64_t* err_mask);
+/* device pointers (indices stays a HOST pointer, read before the call returns), asynchronous on `stream`.  The scratch (two public
+ * matrices [count][r] and [E+1][count], and per secret in flight r syndromes, E + 1 locator coefficients and count locator
+ * values) lives in the stream's workspace, sized by the call: under stream capture the call needs an earlier call with the same
+ * (degree, count) and at least as many secrets on that stream outside capture; without it: the error of
+ * pvw_shamir_reconstruct_checked_device there, nothing enqueued.  The locator values are cleared behind the call's last launch. */
+PVW_API int32_t pvw_shamir_reconstruct_corrected_device(pvw_ctx* ctx, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                        size_t count, const uint64_t* d_shares, size_t num_secrets,
+                                                        size_t secret_stride, size_t point_stride, uint64_t* d_out, uint32_t* d_nerr,
+                                                        uint32_t* d_col_err, uint64_t* d_err_mask, void* stream);
+/* host buffers (synchronous); the staged shares and secrets are cleared before the call returns.  NOT YET covered by the
+ * concurrency promise above (tests/test_gpu_concurrent_calls.py does not run it). */
+PVW_API int32_t pvw_shamir_reconstruct_corrected(pvw_ctx* ctx, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                 size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
+                                                 size_t point_stride, uint64_t* out, uint32_t* nerr, uint32_t* col_err,
+                                                 uint64_t* err_mask);
 
 /* decode_scalar_pvw_rns alone, on the device: noisy [D][L][l] power basis (host) -> out_u64 [D] */
 PVW_API int32_t pvw_decode(pvw_ctx* ctx, const uint64_t* noisy, size_t count, uint64_t* out_u64);

@@ -14,7 +14,8 @@ from .api import (DEC_LOSSY, DEC_NEGATIVE, DEC_WIDE_TRUNCATED, CheckedDecryption
                   decrypt_party_value, device_available, encrypt, encrypt_all_party_shares,
                   encrypt_broadcast, encrypt_many, encrypt_party_shares, aggregate_ciphertexts, decrypt_party_sum,
                   decrypt_all_party_sums, decode_scalar_pvw_plain, decode_scalar_pvw_plain_host,
-                  shamir_shares, deal_party_shares, shamir_reconstruct, shamir_reconstruct_checked)
+                  shamir_shares, deal_party_shares, shamir_reconstruct, shamir_reconstruct_checked,
+                  shamir_reconstruct_corrected, SHAMIR_UNDECODABLE)
 
 __all__ = [
     "PvwParametersBuilder", "PvwParameters", "PvwCrs", "SecretKey", "DeviceSecretKey", "DeviceRandomness", "Party", "GlobalPublicKey",
@@ -25,6 +26,6 @@ __all__ = [
     "decrypt_all_party_shares_checked", "decode_scalar_pvw_checked", "decode_scalar_pvw_checked_host",
     "decode_scalar_pvw_plain", "decode_scalar_pvw_plain_host",
     "aggregate_ciphertexts", "decrypt_party_sum", "decrypt_all_party_sums",
-    "shamir_shares", "deal_party_shares", "shamir_reconstruct", "shamir_reconstruct_checked",
+    "shamir_shares", "deal_party_shares", "shamir_reconstruct", "shamir_reconstruct_checked", "shamir_reconstruct_corrected", "SHAMIR_UNDECODABLE",
     "device_available", "REPR_POWER", "REPR_NTT",
 ]

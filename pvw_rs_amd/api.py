@@ -916,6 +916,40 @@ def shamir_reconstruct_checked(params: Optional[PvwParameters], indices: Sequenc
     return [int(v) for v in out], bad, col_bad
 
 
+SHAMIR_UNDECODABLE = 0xFFFFFFFF
+
+
+def shamir_reconstruct_corrected(params: Optional[PvwParameters], indices: Sequence[int], shares, degree: int, plain_modulus: int, *,
+                                 host: bool = False, layout: str = "secret_major") -> Tuple[List[int], np.ndarray, np.ndarray, np.ndarray]:
+    """EXTENSION (DESIGN 8.11): the secrets although up to E = (len(indices) - degree - 1) // 2 shares of each are wrong, in
+    whichever columns.  secrets[s] is the value at 0 of the one polynomial of degree <= `degree` within E columns of row s;
+    nerr[s] counts the columns off it, bit c % 64 of err_mask[s][c // 64] names them and col_err[c] counts the secrets that are
+    off in column c.  A row with no such polynomial: secrets[s] = 0, nerr[s] = SHAMIR_UNDECODABLE, an empty mask row.  shares and
+    layout as shamir_reconstruct_checked.  On the device (pvw_shamir_reconstruct_corrected); host=True: the plain C++ restatement
+    (pvw_shamir_reconstruct_corrected_host, no GPU; params may be None).  Returns (secrets, nerr, col_err, err_mask)."""
+    if layout not in ("secret_major", "party_major"):
+        raise ValueError(layout)
+    idx = _words(indices)
+    count = len(idx)
+    sh = np.array([[int(v) & 0xFFFFFFFFFFFFFFFF for v in row] for row in shares], dtype=np.uint64)
+    sh = sh.reshape(len(shares), -1)
+    S, cols = sh.shape if layout == "secret_major" else sh.shape[::-1]
+    if cols != count:
+        raise PvwError(15, f"expected {count} shares per secret, got {cols}")
+    strides = (count, 1) if layout == "secret_major" else (1, S)
+    out = np.zeros(S, dtype=np.uint64)
+    nerr, col_err = np.zeros(S, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
+    err_mask = np.zeros((S, (count + 63) // 64), dtype=np.uint64)
+    args = (int(plain_modulus), int(degree), _ptr(idx), count, _ptr(sh), S, strides[0], strides[1], _ptr(out), _ptr(nerr), _ptr(col_err),
+            _ptr(err_mask))
+    if host:
+        L = params._lib if params is not None else _ffi.lib()
+        _check(L.pvw_shamir_reconstruct_corrected_host(*args), L)
+    else:
+        params._call("pvw_shamir_reconstruct_corrected", *args)
+    return [int(v) for v in out], nerr, col_err, err_mask
+
+
 def encrypt_broadcast(scalar: int, global_pk: GlobalPublicKey, seed: Optional[bytes] = None, **kw) -> PvwCiphertext:
     """encryption.rs:292-296."""
     return encrypt([scalar] * global_pk.params.n, global_pk, seed, **kw)

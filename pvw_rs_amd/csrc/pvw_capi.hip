@@ -148,6 +148,8 @@ struct Workspace {
   size_t shares_bytes = 0;
   u64* interp = nullptr;     // checked reconstruction: points | products | weight matrix (shamir_interp_words; grown by the call)
   size_t interp_bytes = 0;
+  u64* correct = nullptr;    // corrected reconstruction: M | public matrices | syndromes | locators (CorrectLayout; grown by the call)
+  size_t correct_bytes = 0;
   // helper stream + events (ws_aux): decode of chunk i under the MAC of chunk i+1, key uploads under key generation
   hipStream_t aux = nullptr;
   bool aux_used = false;     // by the current host call: drained by host_call
@@ -617,6 +619,8 @@ static void ws_free(Workspace* w) {
   if (w->shares) hipMemset(w->shares, 0, w->shares_bytes);   // the last deal's shares, if its wipe did not run
   hipFree(w->shares);
   hipFree(w->interp);
+  if (w->correct) hipMemset(w->correct, 0, w->correct_bytes);   // M of the last call, if its wipe did not run
+  hipFree(w->correct);
   for (hipEvent_t e : w->events) hipEventDestroy(e);
   if (w->aux) hipStreamDestroy(w->aux);
   if (w->own_stream && w->stream) hipStreamDestroy(w->stream);
@@ -2245,6 +2249,272 @@ int32_t pvw_shamir_reconstruct_checked(pvw_ctx* c, uint64_t plain_modulus, uint3
       PVW_HIP(hipStreamSynchronize(w->stream));                // the next piece reuses the staging
     }
     if (col_bad) PVW_HIP(hipMemcpyAsync(col_bad, d_col, count * 4, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
+  volatile u64* vp = packed.data();                              // the host copy is as secret as the caller's shares
+  for (size_t i = 0; i < packed.size(); ++i) vp[i] = 0;
+  return rc;
+}
+
+// ------------------------------------------------------------------------ corrected reconstruction
+// r = count - t - 1 redundant columns, E = r / 2: secret s is decodable iff some F_s of degree <= t disagrees with its row in at
+// most E columns; F_s is then unique, out[s] = F_s(0) and the disagreeing columns are reported.  No column is a basis.
+
+// The contract in plain C++ (no GPU), by another method than the kernels' (syndromes, Berlekamp-Massey, locator roots):
+// Berlekamp-Welch.  Find N of degree <= t + E and a monic W of degree E with N(x_c) = y_c W(x_c) in every column, by Gaussian
+// elimination on count equations in t + 2E + 1 unknowns; if F_s exists, every solution has N = F_s W.  So: no solution, W does
+// not divide N, or N / W disagrees with more than E columns: undecodable.  Cubic in count per secret.
+int32_t pvw_shamir_reconstruct_corrected_host(uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                              const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                              uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  PVW_TRY(reconstruct_checks(r, shares, out));
+  const Mod m = shamir_mod(plain_modulus);
+  const size_t t = degree, E = (count - t - 1) / 2, nq = t + E + 1, nu = nq + E, words = (count + 63) / 64;
+  std::vector<u64> x(count), y(count), A(count * (nu + 1)), sol(nu), W(E + 1), N(nq);
+  std::vector<size_t> pivot_col;
+  for (size_t c = 0; c < count; ++c) x[c] = indices[c] + 1;
+  if (col_err) std::fill(col_err, col_err + count, 0u);
+  for (size_t s = 0; s < num_secrets; ++s) {
+    for (size_t c = 0; c < count; ++c) y[c] = reduce_word(shares[s * secret_stride + c * point_stride], m);
+    // row c: sum_j N_j x^j - y sum_{k < E} W_k x^k = y x^E
+    for (size_t c = 0; c < count; ++c) {
+      u64* row = &A[c * (nu + 1)];
+      u64 pw = 1;
+      for (size_t j = 0; j < nq; ++j) {
+        row[j] = pw;
+        if (j < E) row[nq + j] = submod(0, mulmod(y[c], pw, m), m.q);
+        if (j == E) row[nu] = mulmod(y[c], pw, m);
+        pw = mulmod(pw, x[c], m);
+      }
+    }
+    pivot_col.clear();
+    size_t rank = 0;
+    for (size_t col = 0; col < nu && rank < count; ++col) {
+      size_t pr = rank;
+      while (pr < count && A[pr * (nu + 1) + col] == 0) ++pr;
+      if (pr == count) continue;
+      if (pr != rank) std::swap_ranges(&A[pr * (nu + 1)], &A[(pr + 1) * (nu + 1)], &A[rank * (nu + 1)]);
+      u64* prow = &A[rank * (nu + 1)];
+      const u64 inv = powmod(prow[col], m.q - 2, m);
+      for (size_t j = col; j <= nu; ++j) prow[j] = mulmod(prow[j], inv, m);
+      for (size_t i = 0; i < count; ++i) {
+        u64* row = &A[i * (nu + 1)];
+        const u64 f = row[col];
+        if (i == rank || f == 0) continue;
+        for (size_t j = col; j <= nu; ++j) row[j] = submod(row[j], mulmod(f, prow[j], m), m.q);
+      }
+      pivot_col.push_back(col);
+      ++rank;
+    }
+    bool ok = true;
+    for (size_t i = rank; i < count && ok; ++i) ok = A[i * (nu + 1) + nu] == 0;   // a row 0 = b: no solution
+    u64 secret = 0;
+    std::vector<size_t> wrong;
+    if (ok) {
+      std::fill(sol.begin(), sol.end(), 0);                                      // free unknowns: 0
+      for (size_t i = 0; i < rank; ++i) sol[pivot_col[i]] = A[i * (nu + 1) + nu];
+      for (size_t j = 0; j < nq; ++j) N[j] = sol[j];
+      for (size_t k = 0; k < E; ++k) W[k] = sol[nq + k];
+      W[E] = 1;
+      // N / W by long division (W monic): the quotient stays in N[E ..], the remainder in N[.. E)
+      for (size_t i = nq; i-- > E;) {
+        const u64 f = N[i];
+        for (size_t k = 0; k < E; ++k) N[i - E + k] = submod(N[i - E + k], mulmod(f, W[k], m), m.q);
+      }
+      for (size_t k = 0; k < E && ok; ++k) ok = N[k] == 0;
+      if (ok) {
+        const u64* F = &N[E];                                                    // degree <= t
+        for (size_t c = 0; c < count; ++c) {
+          u64 v = F[t];
+          for (size_t j = t; j-- > 0;) v = addmod(mulmod(v, x[c], m), F[j], m.q);
+          if (v != y[c]) wrong.push_back(c);
+        }
+        ok = wrong.size() <= E;
+        secret = F[0];
+      }
+    }
+    out[s] = ok ? secret : 0;
+    if (nerr) nerr[s] = ok ? (u32)wrong.size() : PVW_SHAMIR_UNDECODABLE;
+    if (err_mask) std::fill(err_mask + s * words, err_mask + (s + 1) * words, (u64)0);
+    if (ok)
+      for (size_t c : wrong) {
+        if (col_err) ++col_err[c];
+        if (err_mask) err_mask[s * words + c / 64] |= (u64)1 << (c % 64);
+      }
+  }
+  for (std::vector<u64>* v : {&y, &A, &sol, &W, &N}) {                           // as secret as the shares
+    volatile u64* vp = v->data();
+    for (size_t i = 0; i < v->size(); ++i) vp[i] = 0;
+  }
+  return PVW_OK;
+}
+
+// The device scratch of one call, in words from its base: M first (the one region marked secret besides the staging), then
+// what the indices alone decide, then what the errors decide.  `cap` secrets are in flight at a time.
+//   M [cap][count] | x, aux, lambda, V, X (shamir_correct_public_words) | Synd [cap][r] | Lambda [cap][E+1] | L [cap] (u32)
+struct CorrectLayout {
+  size_t count, r, E, cap;
+  size_t pub, synd, lam, L, total;   // word offsets
+  CorrectLayout(const Reconstruct& rc, size_t cap_) : count(rc.count), r(rc.count - rc.degree - 1), E(r / 2), cap(cap_) {
+    pub = cap * count;
+    synd = pub + shamir_correct_public_words(count, rc.degree);
+    lam = synd + cap * r;
+    L = lam + cap * (E + 1);
+    total = L + (cap + 1) / 2;
+  }
+  size_t bytes() const { return total * 8; }
+  size_t m_bytes() const { return cap * count * 8; }
+};
+// Secrets per pass over the kernels: their per-secret scratch (a row of M, of the syndromes and of the locators) stays
+// within 64 MiB -- M alone is count words a secret -- and within what one grid holds (tuning build: PVW_CORRECT_PIECE_BYTES,
+// read per call, so that the tests take several passes at small shapes).
+static size_t correct_piece(const Reconstruct& r) {
+  const size_t red = r.count - r.degree - 1;
+  const size_t per = (r.count + red + red / 2 + 1) * 8 + 4;
+  const long env = PVW_ENV_INT("PVW_CORRECT_PIECE_BYTES", 0);
+  const size_t budget = env > 0 ? (size_t)env : (size_t)64 << 20;
+  size_t cap = budget / per;
+  if (cap == 0) cap = 1;
+  if (cap > 65535u * 4) cap = 65535u * 4;
+  return cap < r.S ? cap : r.S;
+}
+static int32_t correct_device_checks(const Reconstruct& r) {
+  PVW_TRY(reconstruct_device_checks(r));
+  if ((r.count - r.degree - 1) / 2 + 1 > PVW_SHAMIR_MAX_LOCATOR) {
+    char buf[128];
+    snprintf(buf, sizeof buf, "on the device the locator holds at most %d coefficients: count - degree - 1 must be below %d",
+             PVW_SHAMIR_MAX_LOCATOR, 2 * PVW_SHAMIR_MAX_LOCATOR);
+    return fail(PVW_ERR_INVALID_PARAMETERS, buf);
+  }
+  return PVW_OK;
+}
+// the points and the public matrices of one call
+static int32_t correct_weights(pvw_ctx* c, const Reconstruct& r, const CorrectLayout& lay, u64* ws, hipStream_t s) {
+  ProfScope ps(c, "shamir_correct_weights", s);
+  PVW_HIP(launch_shamir_points(r.indices, r.count, ws + lay.pub, s));
+  PVW_HIP(launch_shamir_correct_weights(ws + lay.pub, r.count, r.degree, shamir_mod(r.p), s));
+  return PVW_OK;
+}
+// ns <= lay.cap secrets from d_shares: their out, nerr and mask rows; col_err, zeroed by the caller, is added to
+static int32_t correct_piece_enqueue(pvw_ctx* c, const Reconstruct& r, const CorrectLayout& lay, u64* ws, const u64* d_shares, size_t ns,
+                                     size_t secret_stride, size_t point_stride, u64* d_out, u32* d_nerr, u32* d_col_err, u64* d_mask,
+                                     hipStream_t s) {
+  ProfScope ps(c, "shamir_correct", s);
+  const Mod m = shamir_mod(r.p);
+  const u64* pub = ws + lay.pub;
+  const u64 *lambda = pub + 2 * r.count + 1, *V = lambda + r.count, *X = V + r.count * lay.r;
+  u64 *M = ws, *synd = ws + lay.synd, *Lam = ws + lay.lam;
+  u32* L = (u32*)(ws + lay.L);
+  ShamirMatmul a{};
+  a.A = d_shares, a.secret_stride = secret_stride, a.term_stride = point_stride;
+  a.W = V, a.out = synd;
+  a.ns = (u32)ns, a.terms = (u32)r.count, a.T = (u32)lay.r, a.m = m;
+  PVW_HIP(launch_shamir_matmul(a, s));
+  PVW_HIP(launch_shamir_bm(synd, Lam, L, (u32)ns, (u32)lay.r, m, s));
+  ShamirMatmul b{};
+  b.A = Lam, b.secret_stride = lay.E + 1, b.term_stride = 1;
+  b.W = X, b.out = M;
+  b.ns = (u32)ns, b.terms = (u32)lay.E + 1, b.T = (u32)r.count, b.m = m;
+  PVW_HIP(launch_shamir_matmul(b, s));
+  ShamirFinish f{};
+  f.shares = d_shares, f.secret_stride = secret_stride, f.point_stride = point_stride;
+  f.M = M, f.Lam = Lam, f.L = L, f.lam = lambda;
+  f.out = d_out, f.nerr = d_nerr, f.col_err = d_col_err, f.mask = d_mask;
+  f.count = (u32)r.count, f.E = (u32)lay.E, f.m = m;
+  PVW_HIP(launch_shamir_correct_finish(f, (u32)ns, s));
+  return PVW_OK;
+}
+
+// as reconstruct_capture_check, for the stream's corrected-reconstruction scratch
+static int32_t correct_capture_check(pvw_ctx* c, hipStream_t s, size_t need) {
+  if (!stream_capturing(s)) return PVW_OK;
+  bool ready;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    auto it = c->async_ws.find((void*)s);
+    ready = it != c->async_ws.end() && it->second->correct_bytes >= need;
+  }
+  if (!ready)
+    return fail(PVW_ERR_INVALID_PARAMETERS, "corrected reconstruction under stream capture: run a call with the same degree and count and "
+                                            "at least as many secrets on this stream outside capture first (it sizes the workspace)");
+  return PVW_OK;
+}
+
+int32_t pvw_shamir_reconstruct_corrected_device(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
+                                                size_t point_stride, uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err,
+                                                uint64_t* d_err_mask, void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  PVW_TRY(reconstruct_checks(r, d_shares, d_out));
+  PVW_TRY(correct_device_checks(r));
+  const CorrectLayout lay(r, correct_piece(r));
+  const size_t words = (count + 63) / 64;
+  // the caller's stream is checked before the context initialises its device (pvw_shamir_reconstruct_checked_device)
+  if (stream) PVW_TRY(correct_capture_check(c, (hipStream_t)stream, lay.bytes()));
+  return device_call(c, stream, [&](hipStream_t s) { return correct_capture_check(c, s, lay.bytes()); },
+                     [&](Workspace* w, hipStream_t s) -> int32_t {
+                       if (w->correct_bytes < lay.bytes()) ws_public(w, w->correct, w->correct_bytes);   // the block is about to go
+                       PVW_TRY(ws_grow(&w->correct, &w->correct_bytes, lay.bytes(), s, true));
+                       ws_mark_secret(w, w->correct, lay.m_bytes());
+                       PVW_TRY(correct_weights(c, r, lay, w->correct, s));
+                       PVW_HIP(launch_shamir_zero_counts(d_col_err, count, s));
+                       for (size_t s0 = 0; s0 < num_secrets; s0 += lay.cap) {
+                         const size_t ns = num_secrets - s0 < lay.cap ? num_secrets - s0 : lay.cap;
+                         PVW_TRY(correct_piece_enqueue(c, r, lay, w->correct, d_shares + s0 * secret_stride, ns, secret_stride, point_stride,
+                                                       d_out + s0, d_nerr ? d_nerr + s0 : nullptr, d_col_err,
+                                                       d_err_mask ? d_err_mask + s0 * words : nullptr, s));
+                       }
+                       return PVW_OK;
+                     });
+}
+
+// host buffers: the secrets go up in pieces as pvw_shamir_reconstruct_checked stages them (each packed to [piece][count], or
+// whole rows by a 2D copy), a piece no larger than one pass over the kernels; the public matrices are made once and col_err
+// adds up over the pieces.  The staged shares, the staged secrets and M are cleared before the call returns.
+int32_t pvw_shamir_reconstruct_corrected(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                         const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                         uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  PVW_TRY(reconstruct_checks(r, shares, out));
+  PVW_TRY(correct_device_checks(r));
+  PVW_TRY(ensure_device(c));
+  const size_t words = (count + 63) / 64;
+  size_t per = chunk_1gib((count + 1 + words) * 8 + 4, num_secrets);
+  if (per > correct_piece(r)) per = correct_piece(r);
+  const CorrectLayout lay(r, per);
+  Scratch sc;
+  const size_t r_sh = sc.add(per * count * 8), r_out = sc.add(per * 8), r_ws = sc.add(lay.bytes()), r_nerr = sc.add(per * 4),
+               r_col = sc.add(count * 4), r_mask = sc.add(per * words * 8);
+  std::vector<u64> packed;                                       // a piece's shares when the caller's rows are not dense
+  const bool dense = point_stride == 1 && secret_stride >= count;   // whole rows go up as they lie (a 2D copy)
+  if (!dense) packed.resize(per * count);
+  const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    u64 *d_sh = sc.at(r_sh), *d_out = sc.at(r_out), *ws = sc.at(r_ws);
+    ws_mark_secret(w, d_sh, (size_t)((char*)ws - (char*)d_sh) + lay.m_bytes());   // staged shares | staged secrets | M
+    u32 *d_nerr = nerr ? sc.at<u32>(r_nerr) : nullptr, *d_col = col_err ? sc.at<u32>(r_col) : nullptr;
+    u64* d_mask = err_mask ? sc.at(r_mask) : nullptr;
+    PVW_TRY(correct_weights(c, r, lay, ws, w->stream));
+    PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
+    for (size_t s0 = 0; s0 < num_secrets; s0 += per) {
+      const size_t cnt = (num_secrets - s0) < per ? (num_secrets - s0) : per;
+      if (dense) {
+        PVW_HIP(hipMemcpy2DAsync(d_sh, count * 8, shares + s0 * secret_stride, secret_stride * 8, count * 8, cnt, hipMemcpyHostToDevice, w->stream));
+      } else {
+        for (size_t s = 0; s < cnt; ++s)
+          for (size_t col = 0; col < count; ++col) packed[s * count + col] = shares[(s0 + s) * secret_stride + col * point_stride];
+        PVW_HIP(hipMemcpyAsync(d_sh, packed.data(), cnt * count * 8, hipMemcpyHostToDevice, w->stream));
+      }
+      PVW_TRY(correct_piece_enqueue(c, r, lay, ws, d_sh, cnt, count, 1, d_out, d_nerr, d_col, d_mask, w->stream));
+      PVW_HIP(hipMemcpyAsync(out + s0, d_out, cnt * 8, hipMemcpyDeviceToHost, w->stream));
+      if (nerr) PVW_HIP(hipMemcpyAsync(nerr + s0, d_nerr, cnt * 4, hipMemcpyDeviceToHost, w->stream));
+      if (err_mask) PVW_HIP(hipMemcpyAsync(err_mask + s0 * words, d_mask, cnt * words * 8, hipMemcpyDeviceToHost, w->stream));
+      PVW_HIP(hipStreamSynchronize(w->stream));                // the next piece reuses the staging
+    }
+    if (col_err) PVW_HIP(hipMemcpyAsync(col_err, d_col, count * 4, hipMemcpyDeviceToHost, w->stream));
     return PVW_OK;
   });
   volatile u64* vp = packed.data();                              // the host copy is as secret as the caller's shares

@@ -265,6 +265,42 @@ hipError_t launch_shamir_points(const u64* indices, size_t count, u64* x, hipStr
 hipError_t launch_shamir_weights(u64* ws, size_t count, u32 degree, const Mod& m, hipStream_t s);
 hipError_t launch_shamir_interp(const ShamirInterp& b, hipStream_t s);
 
+// ---- Corrected reconstruction (pvw_shamir.hip).  r = count - t - 1 redundant columns, E = r / 2 correctable.
+// Public workspace words, from the indices alone: x [count] | aux [count + 1] (u_c, then prod_i(-x_i)) | lambda [count] |
+// V [count][r] (u_c x_c^j) | X [E+1][count] (x_c^k).
+inline size_t shamir_correct_public_words(size_t count, u32 t) {
+  const size_t r = count - t - 1;
+  return 3 * count + 1 + count * r + (r / 2 + 1) * count;
+}
+#define PVW_SHAMIR_NO_LOCATOR 0xFFFFFFFFu                // L of a row whose locator would need more than E coefficients
+#define PVW_SHAMIR_MAX_LOCATOR 4096                      // E + 1 at most: two polynomials of one wave in 64 KiB of LDS
+struct ShamirMatmul {
+  const u64* A;          // element (s, j) at A[s * secret_stride + j * term_stride], any word, read mod m.q
+  size_t secret_stride, term_stride;
+  const u64* W;          // [terms][T]
+  u64* out;              // [ns][T]
+  u32 ns, terms, T;
+  Mod m;
+};
+struct ShamirFinish {
+  const u64* shares;     // as ShamirInterp
+  size_t secret_stride, point_stride;
+  const u64* M;          // [ns][count]: the locator of row s at every point
+  const u64* Lam;        // [ns][E+1]: the reversed locators
+  const u32* L;          // [ns]: their degrees, or PVW_SHAMIR_NO_LOCATOR
+  const u64* lam;        // [count]: Lagrange weights at 0 over all columns
+  u64* out;              // [ns]
+  u32* nerr;             // [ns] or NULL
+  u32* col_err;          // [count] or NULL; zeroed by the caller, the kernel adds
+  u64* mask;             // [ns][ceil(count / 64)] or NULL; every word is stored
+  u32 count, E;
+  Mod m;
+};
+hipError_t launch_shamir_correct_weights(u64* ws, size_t count, u32 degree, const Mod& m, hipStream_t s);
+hipError_t launch_shamir_matmul(const ShamirMatmul& b, hipStream_t s);
+hipError_t launch_shamir_bm(const u64* synd, u64* lam, u32* L, u32 ns, u32 r, const Mod& m, hipStream_t s);
+hipError_t launch_shamir_correct_finish(const ShamirFinish& f, u32 ns, hipStream_t s);
+
 // p[0 .. words) = 0, as a kernel launch on s
 hipError_t launch_wipe_words(u64* p, size_t words, hipStream_t s);
 

@@ -361,4 +361,286 @@ hipError_t launch_shamir_interp(const ShamirInterp& b, hipStream_t s) {
   return hipSuccess;
 }
 
+// ------------------------------------------------------------------------ corrected reconstruction
+// The shares of one secret are a Reed-Solomon codeword of length count and dimension t + 1: with r = count - t - 1 redundant
+// columns, up to E = r / 2 wrong shares per secret are found and left out, whichever columns hold them.  No column is a basis.
+//   u_c = (prod_{i != c}(x_c - x_i))^-1 and lambda_c = u_c prod_{i != c}(-x_i)         (shamir_prod_kernel with t = count - 1)
+//   V[c][j] = u_c x_c^j [count][r],  X[k][c] = x_c^k [E+1][count]                     (public, from the indices alone)
+//   Synd = shares x V: all 0 for a row on one polynomial of degree <= t               (shamir_matmul_kernel)
+//   inversion-free Berlekamp-Massey over a row's r syndromes -> the reversed locator Lambda_s, of degree L_s <= E, whose
+//   roots are the points of the wrong columns                                          (shamir_bm_kernel)
+//   M = Lambda x X: M[s][c] = Lambda_s(x_c)                                            (shamir_matmul_kernel)
+//   the zeros of row s of M are the wrong columns; out[s] = (sum_c y_c lambda_c M[s][c]) / Lambda_s(0): Lagrange interpolation
+//   at 0 of F_s Lambda_s (degree <= t + E <= count - 1) over ALL columns, where the wrong ones carry M = 0  (finish kernel)
+
+// lambda_c = u_c P / (-x_c), P = prod_i(-x_i) = aux[count]; one thread per column
+__global__ __launch_bounds__(256) void shamir_lambda_kernel(const u64* x, const u64* aux, u64* lam, u32 count, Mod m) {
+  const u32 c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= count) return;
+  lam[c] = mulmod(mulmod(aux[c], aux[count], m), invmod_dev(m.q - x[c], m), m);   // 0 < x_c < p
+}
+
+// one wave per column c: lane l starts at u_c x_c^l and steps by x_c^64, so a wave's stores to row c of V are coalesced
+__global__ __launch_bounds__(256) void shamir_synd_weights_kernel(const u64* x, const u64* aux, u64* V, u32 count, u32 r, Mod m) {
+  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const u32 c = blockIdx.x * SH_WAVES + wave;
+  if (c >= count) return;
+  const u64 xc = x[c], step = powmod_dev(xc, 64, m);
+  u64 v = mulmod(aux[c], powmod_dev(xc, lane, m), m);
+  u64* row = V + (size_t)c * r;
+  for (u32 j = lane; j < r; j += 64) {
+    row[j] = v;
+    v = mulmod(v, step, m);
+  }
+}
+
+// grid: x = blocks of 256 columns, y = blocks of 64 powers; a thread walks its 64 powers of x_c, lanes store along a row of X
+__global__ __launch_bounds__(256) void shamir_powers_kernel(const u64* x, u64* X, u32 count, u32 nk, Mod m) {
+  const u32 c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= count) return;
+  const u32 k0 = blockIdx.y * 64, k1 = k0 + 64 < nk ? k0 + 64 : nk;
+  const u64 xc = x[c];
+  u64 v = powmod_dev(xc, k0, m);
+  for (u32 k = k0; k < k1; ++k) {
+    X[(size_t)k * count + c] = v;
+    v = mulmod(v, xc, m);
+  }
+}
+
+// Out[S][T] = A[S][terms] x W[terms][T] mod p, in the frame of shamir_interp_kernel: a lane owns one target and SH_DG secrets,
+// the four waves a quarter of the terms each; A (any words, two strides) is staged through LDS below p, four weights are in
+// flight ahead of their multiply-adds, the partial sums meet in LDS.  The epilogue only stores.
+// grid: x = blocks of 64 targets, y = groups of SH_DG secrets; 256 threads.
+__global__ __launch_bounds__(256) void shamir_matmul_kernel(ShamirMatmul b) {
+  __shared__ u64 sh[SH_WAVES][SH_JC][SH_DG];       // 8 KiB: the chunk of A, below p
+  __shared__ u64 part[SH_WAVES][SH_DG][64];        // 8 KiB: the waves' partial sums, below p
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const Mod m = b.m;
+  const u32 nt = b.terms;
+  const u32 s0 = blockIdx.y * SH_DG;
+  const size_t tm = (size_t)blockIdx.x * 64 + lane;
+  const bool live = tm < b.T;
+  // wave w owns terms j = w * Q + [0, Q), cut off at nt; every wave walks the same number of chunks (barriers)
+  const u32 Q = (nt + SH_WAVES - 1) / SH_WAVES;
+  const u32 jw0 = wave * Q;
+  const u32 nchunks = (Q + SH_JC - 1) / SH_JC;
+  const bool term_fast = b.term_stride <= b.secret_stride;
+  const u64* wcol = b.W + (live ? tm : 0);
+  Acc acc[SH_DG];
+#pragma unroll
+  for (int g = 0; g < SH_DG; ++g) acc_zero(acc[g]);
+  for (u32 c = 0; c < nchunks; ++c) {
+    for (u32 e = tid; e < SH_WAVES * SH_JC * SH_DG; e += 256) {
+      const u32 ew = e / (SH_JC * SH_DG);
+      const u32 ej = term_fast ? e % SH_JC : (e / SH_DG) % SH_JC;
+      const u32 eg = term_fast ? (e / SH_JC) % SH_DG : e % SH_DG;
+      const u32 off = c * SH_JC + ej;              // within the wave's range
+      const u32 j = ew * Q + off;
+      u64 a = 0;
+      if (off < Q && j < nt && s0 + eg < b.ns)
+        a = reduce_word(b.A[(size_t)(s0 + eg) * b.secret_stride + (size_t)j * b.term_stride], m);
+      sh[ew][ej][eg] = a;
+    }
+    __syncthreads();
+    const u32 base = c * SH_JC;
+    u32 cnt = 0;
+    if (base < Q && jw0 + base < nt) {
+      cnt = Q - base < SH_JC ? Q - base : SH_JC;
+      const u32 left = nt - (jw0 + base);
+      cnt = left < cnt ? left : cnt;
+    }
+    const u64* wp = wcol + (size_t)(jw0 + base) * b.T;
+    u32 jj = 0;
+    for (; jj + 4 <= cnt; jj += 4) {               // four weights in flight ahead of their multiply-adds
+      u64 w[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) w[u] = live ? wp[(size_t)u * b.T] : 0;
+      wp += (size_t)4 * b.T;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        u64 a[SH_DG];
+#pragma unroll
+        for (int g = 0; g < SH_DG; ++g) a[g] = sh[wave][jj + u][g];
+#pragma unroll
+        for (int g = 0; g < SH_DG; ++g) acc_mac_dev(acc[g], a[g], w[u]);
+      }
+    }
+    for (; jj < cnt; ++jj) {
+      const u64 w = live ? *wp : 0;
+      wp += b.T;
+      u64 a[SH_DG];
+#pragma unroll
+      for (int g = 0; g < SH_DG; ++g) a[g] = sh[wave][jj][g];
+#pragma unroll
+      for (int g = 0; g < SH_DG; ++g) acc_mac_dev(acc[g], a[g], w);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int g = 0; g < SH_DG; ++g) part[wave][g][lane] = acc_reduce(acc[g], m);
+  __syncthreads();
+  {
+    const u32 g = wave;                            // SH_WAVES == SH_DG
+    const u32 s = s0 + g;
+    if (live && s < b.ns) {
+      u64 v = 0;
+#pragma unroll
+      for (int w = 0; w < SH_WAVES; ++w) v = addmod(v, part[w][g][lane], m.q);
+      b.out[(size_t)s * b.T + tm] = v;
+    }
+  }
+}
+
+// the sum of the lanes' values (each below p), the same in every lane
+__device__ __forceinline__ u64 wave_addmod(u64 v, u64 q) {
+#pragma unroll
+  for (int off = 32; off; off >>= 1) v = addmod(v, (u64)__shfl_xor((unsigned long long)v, off), q);
+  return v;
+}
+
+// One wave (one workgroup) per secret: inversion-free Berlekamp-Massey over the r syndromes of row s,
+//   d = sum_{i <= L} C_i S_{n-i};  d != 0:  C <- b C - d x^m B  (and, when 2L <= n: B <- the old C, b <- d, L <- n + 1 - L).
+// C and B lie in LDS, coefficient i with lane i % 64; the discrepancy is one lazy accumulator per lane, reduced, summed over
+// the wave and so the same in every lane: every branch below is wave-uniform.  L never decreases, so the first update that
+// would take it above E ends the row as undecodable, and E + 1 coefficients per polynomial are enough (deg x^m B <= the new L).
+// The update walks the coefficients downwards in blocks of 64: B_{i-m} is read from this block or a lower one, which the
+// walk has not overwritten yet.
+// Out: lam[s][k] = C_{L-k} for k <= L, 0 up to E (all 0 for an undecodable row), and Lout[s] = L or PVW_SHAMIR_NO_LOCATOR.
+__global__ __launch_bounds__(64) void shamir_bm_kernel(const u64* synd, u64* lam, u32* Lout, u32 r, u32 E, Mod m) {
+  extern __shared__ u64 bm_lds[];                  // C [E + 1] | B [E + 1]
+  u64 *C = bm_lds, *B = bm_lds + (E + 1);
+  const u32 lane = threadIdx.x;
+  const size_t s = blockIdx.x;
+  const u64* S = synd + s * r;
+  for (u32 i = lane; i <= E; i += 64) C[i] = B[i] = i == 0;
+  __syncthreads();
+  u32 L = 0, mm = 1;
+  u64 bsc = 1;
+  bool ok = true;
+  for (u32 n = 0; n < r; ++n) {
+    Acc a;
+    acc_zero(a);
+    for (u32 i = lane; i <= L; i += 64) acc_mac_dev(a, C[i], S[n - i]);      // L <= n
+    const u64 d = wave_addmod(acc_reduce(a, m), m.q);
+    if (d == 0) { ++mm; continue; }
+    const bool grow = 2 * L <= n;
+    const u32 Ln = grow ? n + 1 - L : L;
+    if (Ln > E) { ok = false; break; }
+    for (u32 k = Ln / 64 + 1; k-- > 0;) {
+      const u32 i = k * 64 + lane;
+      const bool in = i <= Ln;
+      const u64 c = in ? C[i] : 0;
+      const u64 bb = in && i >= mm ? B[i - mm] : 0;
+      __syncthreads();
+      if (in) {
+        C[i] = submod(mulmod(bsc, c, m), mulmod(d, bb, m), m.q);
+        if (grow) B[i] = c;
+      }
+      __syncthreads();
+    }
+    if (grow) { L = Ln; bsc = d; mm = 1; } else { ++mm; }
+  }
+  u64* row = lam + s * (E + 1);
+  for (u32 k = lane; k <= E; k += 64) row[k] = ok && k <= L ? C[L - k] : 0;
+  if (lane == 0) Lout[s] = ok ? L : PVW_SHAMIR_NO_LOCATOR;
+}
+
+// One wave (one workgroup) per secret over row s of M.  Pass 1 counts the zeros: a locator of degree L has at most L roots,
+// and fewer than L among the points means no polynomial within E errors.  Pass 2: the ballot of the zeros of 64 columns is
+// the mask word, every set bit one atomicAdd to its column's count (a consistent sharing issues none), and the other
+// columns enter out[s] = (sum_c y_c lambda_c M[s][c]) Lambda_s(0)^-1.  Every mask word of the row is stored.
+__global__ __launch_bounds__(64) void shamir_correct_finish_kernel(ShamirFinish f) {
+  const u32 lane = threadIdx.x;
+  const size_t s = blockIdx.x;
+  const Mod m = f.m;
+  const u32 count = f.count, words = (count + 63) / 64;
+  const u32 L = f.L[s];
+  const u64* Mrow = f.M + s * count;
+  bool decodable = L != PVW_SHAMIR_NO_LOCATOR;
+  if (decodable) {
+    u32 nz = 0;
+    for (u32 c0 = 0; c0 < count; c0 += 64) {
+      const u32 c = c0 + lane;
+      nz += (u32)__popcll(__ballot(c < count && Mrow[c] == 0));
+    }
+    decodable = nz == L;
+  }
+  if (!decodable) {
+    if (f.mask)
+      for (u32 w = lane; w < words; w += 64) f.mask[s * words + w] = 0;
+    if (lane == 0) {
+      f.out[s] = 0;
+      if (f.nerr) f.nerr[s] = PVW_SHAMIR_NO_LOCATOR;
+    }
+    return;
+  }
+  Acc a;
+  acc_zero(a);
+  for (u32 c0 = 0; c0 < count; c0 += 64) {
+    const u32 c = c0 + lane;
+    const bool live = c < count;
+    const u64 mv = live ? Mrow[c] : 1;
+    const bool wrong = live && mv == 0;
+    const u64 bal = __ballot(wrong);
+    if (lane == 0 && f.mask) f.mask[s * words + c0 / 64] = bal;
+    if (wrong && f.col_err) atomicAdd(&f.col_err[c], 1u);
+    const u64 y = live && !wrong ? reduce_word(f.shares[s * f.secret_stride + (size_t)c * f.point_stride], m) : 0;
+    acc_mac_dev(a, y, live ? mulmod(f.lam[c], mv, m) : 0);
+  }
+  const u64 v = wave_addmod(acc_reduce(a, m), m.q);
+  if (lane == 0) {
+    f.out[s] = mulmod(v, invmod_dev(f.Lam[s * (f.E + 1)], m), m);
+    if (f.nerr) f.nerr[s] = L;
+  }
+}
+
+// ws: x [count] (filled by launch_shamir_points) | aux [count + 1] | lambda [count] | V [count][r] | X [E+1][count]
+hipError_t launch_shamir_correct_weights(u64* ws, size_t count, u32 t, const Mod& m, hipStream_t s) {
+  const u32 n = (u32)count, r = n - t - 1, nk = r / 2 + 1;
+  const u64* x = ws;
+  u64 *aux = ws + count, *lam = aux + count + 1, *V = lam + count, *X = V + count * r;
+  shamir_prod_kernel<<<dim3((unsigned)((count + 1 + SH_WAVES - 1) / SH_WAVES)), dim3(256), 0, s>>>(x, aux, count, n - 1, m);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  shamir_lambda_kernel<<<dim3((n + 255) / 256), dim3(256), 0, s>>>(x, aux, lam, n, m);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (r) {
+    shamir_synd_weights_kernel<<<dim3((n + SH_WAVES - 1) / SH_WAVES), dim3(256), 0, s>>>(x, aux, V, n, r, m);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  shamir_powers_kernel<<<dim3((n + 255) / 256, (nk + 63) / 64), dim3(256), 0, s>>>(x, X, n, nk, m);
+  return hipGetLastError();
+}
+
+// the grid's y dimension holds 65535 groups of secrets: more secrets take more launches
+hipError_t launch_shamir_matmul(const ShamirMatmul& b, hipStream_t s) {
+  if (b.ns == 0 || b.T == 0) return hipSuccess;
+  const u32 per = 65535u * SH_DG;
+  for (u32 s0 = 0; s0 < b.ns; s0 += per) {
+    ShamirMatmul p = b;
+    p.ns = b.ns - s0 < per ? b.ns - s0 : per;
+    p.A = b.A + (size_t)s0 * b.secret_stride;
+    p.out = b.out + (size_t)s0 * b.T;
+    const dim3 grid((b.T + 63) / 64, (p.ns + SH_DG - 1) / SH_DG);
+    shamir_matmul_kernel<<<grid, dim3(256), 0, s>>>(p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// E + 1 <= PVW_SHAMIR_MAX_LOCATOR: C and B of one wave fit the 64 KiB of LDS a launch gets without asking for more
+hipError_t launch_shamir_bm(const u64* synd, u64* lam, u32* L, u32 ns, u32 r, const Mod& m, hipStream_t s) {
+  if (ns == 0) return hipSuccess;
+  const u32 E = r / 2;
+  shamir_bm_kernel<<<dim3(ns), dim3(64), (size_t)2 * (E + 1) * 8, s>>>(synd, lam, L, r, E, m);
+  return hipGetLastError();
+}
+
+hipError_t launch_shamir_correct_finish(const ShamirFinish& f, u32 ns, hipStream_t s) {
+  if (ns == 0) return hipSuccess;
+  shamir_correct_finish_kernel<<<dim3(ns), dim3(64), 0, s>>>(f);
+  return hipGetLastError();
+}
+
 }  // namespace pvw

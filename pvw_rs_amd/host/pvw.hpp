@@ -690,6 +690,32 @@ inline CheckedSecrets shamir_reconstruct_checked(const std::shared_ptr<PvwParame
   return r;
 }
 
+// ---- corrected reconstruction ----
+struct CorrectedSecrets {
+  std::vector<uint64_t> secrets;    // [num_secrets]: the value at 0 of the one polynomial within E columns of the row; 0: undecodable
+  std::vector<uint32_t> nerr;       // [num_secrets]: columns off that polynomial, or PVW_SHAMIR_UNDECODABLE
+  std::vector<uint32_t> col_err;    // [indices.size()]: decodable secrets that are off in each column
+  std::vector<uint64_t> err_mask;   // [num_secrets][words]: bit c % 64 of word c / 64 names the columns of nerr
+  size_t words;                     // ceil(indices.size() / 64)
+  bool wrong(size_t s, size_t c) const { return (err_mask[s * words + c / 64] >> (c % 64)) & 1; }
+};
+// Up to E = (indices.size() - degree - 1) / 2 wrong shares per secret, in whichever columns.  shares as shamir_reconstruct_checked.
+// On the device (pvw_shamir_reconstruct_corrected); host = true: the plain C++ restatement (no GPU, p may be null).
+inline CorrectedSecrets shamir_reconstruct_corrected(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& indices,
+                                                     const std::vector<uint64_t>& shares, uint32_t degree, uint64_t plain_modulus,
+                                                     bool host = false, bool party_major = false) {
+  const size_t count = indices.size();
+  if (count == 0 || shares.empty() || shares.size() % count) throw PvwError(15, "shares must hold one value per index and secret");
+  const size_t S = shares.size() / count, words = (count + 63) / 64;
+  CorrectedSecrets r{std::vector<uint64_t>(S), std::vector<uint32_t>(S), std::vector<uint32_t>(count), std::vector<uint64_t>(S * words), words};
+  const size_t ss = party_major ? 1 : count, ps = party_major ? S : 1;
+  check(host ? pvw_shamir_reconstruct_corrected_host(plain_modulus, degree, indices.data(), count, shares.data(), S, ss, ps,
+                                                     r.secrets.data(), r.nerr.data(), r.col_err.data(), r.err_mask.data())
+             : pvw_shamir_reconstruct_corrected(p->ctx, plain_modulus, degree, indices.data(), count, shares.data(), S, ss, ps,
+                                                r.secrets.data(), r.nerr.data(), r.col_err.data(), r.err_mask.data()));
+  return r;
+}
+
 // the sum of the valid dealers' ciphertexts (pvw_ct_sum): same parameters and representation, no key needed
 inline PvwCiphertext aggregate_ciphertexts(const std::vector<PvwCiphertext>& cts, const std::vector<bool>& valid = {}) {
   const SumInputs in = sum_inputs(cts, valid);

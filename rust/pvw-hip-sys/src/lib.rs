@@ -99,6 +99,8 @@ pub const PVW_DOM_GAUSS: u32 = 6;
 pub const PVW_DOM_PK: u32 = 7;
 pub const PVW_DOM_CALL: u32 = 8;
 pub const PVW_DOM_SHAMIR: u32 = 9;
+/// `nerr` of a secret that no polynomial of the degree fits within E columns
+pub const PVW_SHAMIR_UNDECODABLE: u32 = 0xFFFF_FFFF;
 
 extern "C" {
     // ---- errors / device ------------------------------------------------------------------
@@ -160,6 +162,10 @@ extern "C" {
     pub fn pvw_shamir_reconstruct_checked_host(plain_modulus: u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, out: *mut u64, bad: *mut u32, col_bad: *mut u32) -> i32;
     pub fn pvw_shamir_reconstruct_checked_device(ctx: *mut PvwCtx, plain_modulus: u64, degree: u32, indices: *const u64, count: usize, d_shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, d_out: *mut u64, d_bad: *mut u32, d_col_bad: *mut u32, stream: *mut c_void) -> i32;
     pub fn pvw_shamir_reconstruct_checked(ctx: *mut PvwCtx, plain_modulus: u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, out: *mut u64, bad: *mut u32, col_bad: *mut u32) -> i32;
+    // ---- corrected reconstruction ------------------------------------------------
+    pub fn pvw_shamir_reconstruct_corrected_host(plain_modulus: u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, out: *mut u64, nerr: *mut u32, col_err: *mut u32, err_mask: *mut u64) -> i32;
+    pub fn pvw_shamir_reconstruct_corrected_device(ctx: *mut PvwCtx, plain_modulus: u64, degree: u32, indices: *const u64, count: usize, d_shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, d_out: *mut u64, d_nerr: *mut u32, d_col_err: *mut u32, d_err_mask: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_reconstruct_corrected(ctx: *mut PvwCtx, plain_modulus: u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, out: *mut u64, nerr: *mut u32, col_err: *mut u32, err_mask: *mut u64) -> i32;
     // ---- decrypt (src/crypto/decryption.rs:249-325) and gadget decode (:10-247) ---------------
     pub fn pvw_decrypt_batch(ctx: *mut PvwCtx, sk: *const i64, c1s: *const u64, c2col: *const u64, num_dealers: usize, in_repr: u32, out_u64: *mut u64, noisy_out: *mut u64) -> i32;
     pub fn pvw_decrypt_noisy_device(ctx: *mut PvwCtx, d_sk: *const i64, d_c1s: *const u64, d_c2col: *const u64, num_dealers: usize, in_repr: u32, d_noisy: *mut u64, stream: *mut c_void) -> i32;

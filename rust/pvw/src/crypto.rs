@@ -511,6 +511,38 @@ pub fn shamir_reconstruct_checked(params: &Arc<PvwParameters>, indices: &[u64], 
     Ok(r)
 }
 
+/// EXTENSION: what `shamir_reconstruct_corrected` reports.
+pub struct CorrectedSecrets {
+    /// the value at 0 of the one polynomial within E columns of each row; 0 for an undecodable row
+    pub secrets: Vec<u64>,
+    /// per secret: columns off that polynomial, or `sys::PVW_SHAMIR_UNDECODABLE`
+    pub nerr: Vec<u32>,
+    /// per column: decodable secrets that are off there
+    pub col_err: Vec<u32>,
+    /// `[num_secrets][words]`: bit `c % 64` of word `c / 64` names the columns counted in `nerr`
+    pub err_mask: Vec<u64>,
+    /// `ceil(indices.len() / 64)`
+    pub words: usize,
+}
+
+/// EXTENSION: the secrets although up to `(indices.len() - degree - 1) / 2` shares of each are wrong, in
+/// whichever columns, on the device (`pvw_shamir_reconstruct_corrected`).  `shares` as `shamir_reconstruct_checked`.
+pub fn shamir_reconstruct_corrected(params: &Arc<PvwParameters>, indices: &[u64], shares: &[u64], degree: u32, plain_modulus: u64,
+                                    party_major: bool) -> Result<CorrectedSecrets> {
+    if indices.is_empty() || shares.is_empty() || shares.len() % indices.len() != 0 {
+        return Err(PvwError::InvalidParameters("shares must hold one value per index and secret".into()));
+    }
+    let (count, num) = (indices.len(), shares.len() / indices.len());
+    let words = (count + 63) / 64;
+    let (ss, ps) = if party_major { (1, num) } else { (count, 1) };
+    let mut r = CorrectedSecrets { secrets: vec![0u64; num], nerr: vec![0u32; num], col_err: vec![0u32; count], err_mask: vec![0u64; num * words], words };
+    check(unsafe {
+        sys::pvw_shamir_reconstruct_corrected(params.hip.raw(), plain_modulus, degree, indices.as_ptr(), count, shares.as_ptr(), num, ss, ps,
+                                              r.secrets.as_mut_ptr(), r.nerr.as_mut_ptr(), r.col_err.as_mut_ptr(), r.err_mask.as_mut_ptr())
+    })?;
+    Ok(r)
+}
+
 /// EXTENSION: the sum of the valid dealers' ciphertexts (`pvw_ct_sum`) -- a ciphertext of the sum of their
 /// shares under the same keys, folded without any key.  What examples/pvw_valid_dec.rs:150-209 reaches by decrypting every
 /// dealer's share and adding the results; the noise of the sum is the sum of the dealers' noises (`pvw_ctx_sum_capacity`).
