@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -29,6 +30,7 @@
 #if PVW_TUNING
 #include "../../include/pvw_hip_tuning.h"
 #endif
+#include "pvw_ahead_ring.h"
 
 using namespace pvw;
 
@@ -154,6 +156,17 @@ struct Workspace {
   hipStream_t aux = nullptr;
   bool aux_used = false;     // by the current host call: drained by host_call
   std::vector<hipEvent_t> events;
+  // seed-mode encrypts on a busy stream (encrypt_enqueue's ahead path): 2R sets of (r-hat [L][k][l] | e_small) that the prologue
+  // fills on `aux` while the caller's stream still runs earlier work; which set a call takes and when a guard is due:
+  // pvw_ahead_ring.h.  Allocated by the first such call (ahead_sets).
+  AheadRing ahead;
+  char* ahead_block = nullptr;
+  size_t ahead_set_bytes = 0, ahead_rhat_bytes = 0;
+  std::vector<hipEvent_t> ahead_done;   // per set: recorded on `aux` behind the prologue that fills it
+  hipEvent_t ahead_guard[2] = {nullptr, nullptr};   // per bank: recorded on the caller's stream behind the MAC that reads its last set
+  hipEvent_t ahead_mark = nullptr;      // recorded behind the MAC of a call that could have gone ahead and did not record a guard
+  hipEvent_t ahead_last = nullptr;      // the guard or mark behind the latest such MAC: not complete = that MAC is still outstanding
+  bool ahead_off = false;               // the sets could not be allocated: the calls stay in order
   // device regions that hold secret-key material during the current call (sk coefficients, NTT(sk), key errors,
   // their MFMA-tiled / digitised copies): cleared on the call's stream before the workspace goes back to the pool
   // (the reference's SecretKey is Zeroize + ZeroizeOnDrop, src/keys/secret_key.rs:20-30).  `wiped` remembers what
@@ -622,6 +635,11 @@ static void ws_free(Workspace* w) {
   if (w->correct) hipMemset(w->correct, 0, w->correct_bytes);   // M of the last call, if its wipe did not run
   hipFree(w->correct);
   for (hipEvent_t e : w->events) hipEventDestroy(e);
+  if (w->ahead_block) hipMemset(w->ahead_block, 0, w->ahead_set_bytes * w->ahead.slots());   // r-hat and errors of the last encrypts
+  hipFree(w->ahead_block);
+  for (hipEvent_t e : w->ahead_done) hipEventDestroy(e);
+  for (hipEvent_t e : w->ahead_guard) if (e) hipEventDestroy(e);
+  if (w->ahead_mark) hipEventDestroy(w->ahead_mark);
   if (w->aux) hipStreamDestroy(w->aux);
   if (w->own_stream && w->stream) hipStreamDestroy(w->stream);
   delete w;
@@ -1825,6 +1843,77 @@ static int32_t fill_encrypt_jobs(pvw_ctx* c, PrologueBatch& pb, u32 slot, const 
   return PVW_OK;
 }
 
+// ---- the ahead path of a seed-mode encrypt ("The prologue and the step") ----
+// How long the calling thread polls for the prologue on the side stream before it falls back to a wait packet in front of the
+// MAC.  The poll ends when the prologue has run, which in steady state is when the MAC the side stream had to wait for has
+// finished: at most one MAC of the flagship shape (0.18 ms) plus the prologue.
+static constexpr long AHEAD_POLL_US = 1000;
+// sets per bank of the ring (2R sets, one guard record on the caller's stream per R calls).  Measured at config 3 (profiles/
+// r09_prologue_ahead_ab.txt, the shipped form): R = 1 steps 182.4 / 186.4 us, R = 4 184.3 / 187.1-187.7, R = 8 183.9 / 187.5-188.1
+// (by MAC regime): fewer guard records buy nothing, and R = 1 keeps the calling thread at most two MACs ahead of the GPU.
+// Tuning build: PVW_AHEAD_R, read when a stream's ring is first set up.
+static constexpr unsigned AHEAD_R = 1;
+
+// the caller's stream has something outstanding (asked only of a stream that is not capturing)
+static bool stream_busy(hipStream_t s) {
+  const hipError_t e = hipStreamQuery(s);
+  (void)hipGetLastError();
+  return e == hipErrorNotReady;
+}
+// The caller's stream has work outstanding, and enough of it to hide the wait: the MAC of the latest encrypt of this kind on
+// the stream has not finished.  (stream_busy alone says too little: behind an event record or a small copy the stream is
+// "not ready" for a few us, and a call that is alone there lost 15 us to the ahead path -- 207 against 192 us at config 3.)
+static bool ahead_busy(const Workspace* w) {
+  if (!w->ahead_last) return false;
+  const hipError_t e = hipEventQuery(w->ahead_last);
+  (void)hipGetLastError();
+  return e == hipErrorNotReady;
+}
+// the workspace's ring, side stream and events, made by the first call that wants them; false: the call stays in order
+static bool ahead_sets(pvw_ctx* c, Workspace* w) {
+  if (w->ahead_off) return false;
+  if (w->ahead_block) return true;
+  w->ahead_off = true;                                   // until everything below has succeeded
+  AheadRing ring;
+  ring.reset((unsigned)PVW_ENV_INT("PVW_AHEAD_R", AHEAD_R));
+  const size_t rhat_bytes = ((size_t)c->k * c->poly() * 8 + 255) & ~(size_t)255;
+  const size_t set_bytes = rhat_bytes + ((((size_t)c->rowsA() + c->rowsB()) * c->l * 8 + 16 + 255) & ~(size_t)255);
+  if (ws_aux(w, 0) != PVW_OK) { (void)hipGetLastError(); return false; }
+  while (w->ahead_done.size() < ring.slots()) {
+    hipEvent_t e;
+    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return false; }
+    w->ahead_done.push_back(e);
+  }
+  // The guards and the mark order no data: they say that a MAC has finished reading (the side stream may overwrite a set, the
+  // host may go ahead), so they are recorded without a system-scope fence -- what the caller enqueues behind them fences for
+  // itself.  Tuning build: PVW_AHEAD_FENCE=1 records them with the fence.
+  const unsigned flags = hipEventDisableTiming | (PVW_ENV_INT("PVW_AHEAD_FENCE", 0) != 0 ? 0u : (unsigned)hipEventDisableSystemFence);
+  for (hipEvent_t* e : {&w->ahead_guard[0], &w->ahead_guard[1], &w->ahead_mark})
+    if (!*e && hipEventCreateWithFlags(e, flags) != hipSuccess) { *e = nullptr; (void)hipGetLastError(); return false; }
+  void* block = nullptr;
+  if (hipMalloc(&block, set_bytes * ring.slots()) != hipSuccess) { (void)hipGetLastError(); return false; }
+  if (hipMemset(block, 0, set_bytes * ring.slots()) != hipSuccess) { (void)hipGetLastError(); hipFree(block); return false; }
+  w->ahead = ring;
+  w->ahead_block = (char*)block;
+  w->ahead_set_bytes = set_bytes;
+  w->ahead_rhat_bytes = rhat_bytes;
+  w->ahead_off = false;
+  return true;
+}
+// polls until `ev` has completed; false: the bound ran out (or the query failed), the caller orders the streams by a wait.
+// The calling thread SPINS here (no sleep: a wake-up costs more than the few us the MAC launch may be late by); in back-to-back
+// use that is about one MAC per call, which also paces the caller: it runs at most two MACs ahead of the GPU.
+static bool ahead_host_wait(hipEvent_t ev) {
+  const auto t0 = std::chrono::steady_clock::now();
+  for (;;) {
+    const hipError_t e = hipEventQuery(ev);
+    if (e == hipSuccess) return true;
+    (void)hipGetLastError();
+    if (e != hipErrorNotReady) return false;
+    if (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() >= AHEAD_POLL_US) return false;
+  }
+}
+
 // all pointers are device pointers; explicit r/e1/e2 are GLOBAL arrays ([k][l], [k][l], [n][l])
 // out_c1 / out_c2 != NULL: the MAC stores its results there (device-visible HOST memory of a caller whose buffers are
 // pinned) while the addends stay in d_c1 / d_c2; NTT-domain output only
@@ -1837,17 +1926,40 @@ static int32_t encrypt_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, c
   if (!out_c2) out_c2 = d_c2;
   if (out_repr == PVW_REPR_POWER && (out_c1 != d_c1 || out_c2 != d_c2)) return fail(PVW_ERR_INTERNAL, "direct output is NTT-domain only");
   // first call after a matrix change (and no pvw_prepare since): builds the packed copies -- allocates and synchronises
-  const u32 width = ensure_packed(c, s, !stream_capturing(s));
-  PrologueBatch pb{};
-  ws_public(w, w->rhat, w->rhat_bytes);                  // r-hat of this encrypt
-  PVW_TRY(fill_encrypt_jobs(c, pb, 0, ex, d_scalars, w->rhat, d_c1, d_c2));
-  keys.fill(pb, 1);
+  const bool capturing = stream_capturing(s);
+  const u32 width = ensure_packed(c, s, !capturing);
   // l <= 16: the addends travel in COMPACT form -- the prologue transforms r only and leaves the sampled e1 / e2 coefficients as
   // they are (8 l bytes per row instead of 8 L l written and read back); the MAC workgroups transform their own rows' e and add
   // m g-hat (MacSection::e_small, mac_small_make).  Explicit randomness: the caller's e1 / e2 arrays ARE the compact form.
   // (Round 3 also measured five forms of making r-hat and / or the addends inside the MAC launch instead of in a launch in front
   // of it: none was faster -- profiles/r03_front_ab.txt.)  Tuning build: PVW_MAC_COMPACT=0 the round-2 form (full addends).
   const bool compact = l <= 16 && w->esmall && PVW_ENV_INT("PVW_MAC_COMPACT", 1) != 0;
+  // AHEAD: a seed-mode prologue with compact addends reads nothing but the seed, so only stream order would make it wait for
+  // the work in front of it.  While the previous such encrypt's MAC is still outstanding on the caller's stream it runs on the
+  // side stream instead, into the next set of the workspace's ring, and the calling thread waits for it (under the work already
+  // queued) before it enqueues the MAC: the MAC then follows the one in front of it on `s` with no prologue and no wait packet
+  // between them.  A stream with nothing of that size outstanding is a single call that wants its latency (in order: nobody
+  // blocks); capture takes no host wait; the _rs prologue reads the counter the previous MAC advances; explicit randomness is
+  // the caller's data; a host-buffer call's pooled stream is idle at every call.  Tuning build: PVW_PROLOGUE_AHEAD=0 keeps every
+  // call in order.
+  const bool can_ahead = compact && !ex.r && !keys.by_state && !capturing && !w->own_stream &&
+                         PVW_ENV_INT("PVW_PROLOGUE_AHEAD", 1) != 0 && ahead_sets(c, w);
+  const bool ahead = can_ahead && ahead_busy(w);
+  // a call that stays in order leaves a mark behind its MAC for the next one only where the stream has something outstanding (a
+  // burst is starting): behind a call that is alone on an idle stream the record would be 3-5 us in front of whatever follows
+  const bool mark = can_ahead && (ahead || stream_busy(s));
+  AheadRing::Step at{};
+  u64* rhat = w->rhat;
+  i64* esmall = w->esmall;
+  if (ahead) {
+    at = w->ahead.begin();
+    rhat = (u64*)(w->ahead_block + (size_t)at.slot * w->ahead_set_bytes);
+    esmall = (i64*)(w->ahead_block + (size_t)at.slot * w->ahead_set_bytes + w->ahead_rhat_bytes);
+  }
+  PrologueBatch pb{};
+  ws_public(w, rhat, ahead ? w->ahead_set_bytes : w->rhat_bytes);   // r-hat of this encrypt
+  PVW_TRY(fill_encrypt_jobs(c, pb, 0, ex, d_scalars, rhat, d_c1, d_c2));
+  keys.fill(pb, 1);
   const i64 *es1 = nullptr, *es2 = nullptr;
   if (compact) {
     if (ex.r) {
@@ -1855,8 +1967,8 @@ static int32_t encrypt_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, c
       es2 = pb.job[2].explicit_coeffs;
       pb.njobs = 1;                                   // r only
     } else {
-      pb.job[1].raw_out = w->esmall;
-      pb.job[2].raw_out = w->esmall + (size_t)rA * l;
+      pb.job[1].raw_out = esmall;
+      pb.job[2].raw_out = esmall + (size_t)rA * l;
       es1 = pb.job[1].raw_out;
       es2 = pb.job[2].raw_out;
       pb.njobs = 3;
@@ -1864,7 +1976,17 @@ static int32_t encrypt_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, c
   } else {
     pb.njobs = 3;
   }
-  {
+  if (ahead) {
+    pb.job[2].scalars = nullptr;                         // sampled only (raw_out): the MAC adds m g-hat, nothing of the caller's is read
+    if (at.record_first) PVW_HIP(hipEventRecord(w->ahead_guard[at.bank], s));
+    if (at.wait_guard) PVW_HIP(hipStreamWaitEvent(w->aux, w->ahead_guard[at.bank], 0));   // the MACs that read this bank last time round
+    {
+      ProfScope ps(c, "prologue_ahead", w->aux);
+      PVW_HIP(launch_prologue(pb, c->dt, L, l, w->aux));
+    }
+    PVW_HIP(hipEventRecord(w->ahead_done[at.slot], w->aux));
+    if (!ahead_host_wait(w->ahead_done[at.slot])) PVW_HIP(hipStreamWaitEvent(s, w->ahead_done[at.slot], 0));   // correct, as slow as in order
+  } else {
     ProfScope ps(c, "prologue", s);
     PVW_HIP(launch_prologue(pb, c->dt, L, l, s));
   }
@@ -1880,8 +2002,14 @@ static int32_t encrypt_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, c
       a.rnd_ctr = &rs->counter;                          // the prologue in front of this launch was the state's reader
       a.rnd_adv = 1;
     }
-    if (width) PVW_HIP(launch_mac_rows_packed(a, b, w->rhat, c->dt, k, L, l, width, s));   // the same sums over the packed copy
-    else PVW_HIP(launch_mac_rows(a, b, w->rhat, c->dt, k, L, l, s));                       // crs.rs:188-201, encryption.rs:177-200
+    if (width) PVW_HIP(launch_mac_rows_packed(a, b, rhat, c->dt, k, L, l, width, s));   // the same sums over the packed copy
+    else PVW_HIP(launch_mac_rows(a, b, rhat, c->dt, k, L, l, s));                       // crs.rs:188-201, encryption.rs:177-200
+  }
+  if (mark) {                                            // one record: the bank's guard where it is due, else the mark
+    w->ahead_last = ahead && w->ahead.finish(at.slot) ? w->ahead_guard[at.bank] : w->ahead_mark;
+    PVW_HIP(hipEventRecord(w->ahead_last, s));
+  } else if (can_ahead) {
+    w->ahead_last = nullptr;                             // (a call of another kind leaves the latest mark as it is)
   }
   if (out_repr == PVW_REPR_POWER) {
     ProfScope ps(c, "intt", s);
@@ -1891,13 +2019,17 @@ static int32_t encrypt_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scalars, c
   return PVW_OK;
 }
 
-// NOTE (measured, round 1): overlapping the prologue of call i with the MAC of call i-1 on a second
-// stream was tried and reverted -- the cross-stream event dependencies cost more (step 242 us vs
-// 207 us at config 3) than the ~14 us prologue they hide.  Single-stream, in-order is the fast path.
-// Round 3, again, with nothing but the seed feeding the prologue (compact addends: it no longer reads the scalars), two
-// sets of (r-hat, addends) and one wait per stream and call: the prologue does run under the previous MAC (26 us there
-// instead of 11), but the MAC behind the cross-stream wait starts as late as it did behind the prologue: step = MAC +
-// 7.6-7.9 us against MAC + 7.8-8.3 us in order (same box, 183-184 us MACs).  Not kept.
+// NOTE (measured): the prologue of call i under the MAC of call i-1, three times.
+// Round 1: on a second stream with cross-stream event dependencies both ways -- step 242 us against 207 us in order at config 3.
+// Round 3: with nothing but the seed feeding the prologue (compact addends), two sets of (r-hat, addends) and one device-side
+// wait per stream and call: the prologue does run under the previous MAC (26 us there instead of 11), but the MAC behind the
+// cross-stream wait starts as late as it did behind the prologue: step = MAC + 7.6-7.9 us against MAC + 7.8-8.3 us in order.
+// Round 9 (profiles/r09_prologue_ahead_ab.txt), kept: the same two sets, but the HOST waits for the prologue and then enqueues
+// the MAC with nothing in front of it.  Alternating processes on one box, bench.py, 9 + 9 at config 3: step - MAC 10.4-12.4 us
+// at the parent, 3.2-6.3 us with the ahead path; the MAC itself runs 1-2.5 us longer with a prologue beside it, so the step
+// goes 192.7-193.7 -> 186.8-188.1 us where mac_rows takes 181-184 us and 187.8 -> 183.8 us where it takes 175-178 us; at
+// n = 1024 step - MAC 7.3-11.2 -> -0.5-1.9 us (66.7-70.9 -> 62.5-64.0 us).  What is left between two MACs is the kernel
+// boundary, one unfenced event record and the slower MAC.
 
 // The two single-dealer frames.  rnd: the seed forms' argument, NULL in the _rs forms (a seed form's NULL rnd is not a "NULL
 // argument": encrypt_checks names it, behind the representation check).
