@@ -31,7 +31,8 @@
  *     The promise, as tests/test_gpu_concurrent_calls.py holds it: threads that share one context may overlap any of
  *     pvw_encrypt[_rs], pvw_encrypt_multi[_rs], pvw_deal_shares[_rs], pvw_shamir_shares, pvw_shamir_reconstruct_checked,
  *     pvw_decrypt_batch / _checked / _plain, pvw_decrypt_all / _checked / _plain, pvw_ct_sum, pvw_decrypt_sum_checked,
- *     pvw_decrypt_all_sum_checked, pvw_decode / _checked / _plain, pvw_wire_pack / _unpack, pvw_ntt_forward / _inverse,
+ *     pvw_decrypt_all_sum_checked, pvw_ct_lincomb, pvw_decrypt_lincomb_plain, pvw_decrypt_all_lincomb_plain (the concurrent
+ *     calls of these three: tests/test_gpu_ct_lincomb.py), pvw_decode / _checked / _plain, pvw_wire_pack / _unpack, pvw_ntt_forward / _inverse,
  *     pvw_sample_cbd / _uniform / _gaussian, pvw_sk_load / pvw_sk_free, and *_device calls that each thread enqueues on a
  *     stream of its own -- the context's first calls included (device initialisation and the derived copies are built
  *     once, under a lock).  Every result is the serial one bit for bit, pvw_last_error stays the calling thread's, and a
@@ -550,6 +551,75 @@ PVW_API int32_t pvw_decrypt_all_sum_plain_device(pvw_ctx* ctx, uint32_t party_lo
                                                  const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise,
                                                  uint32_t* d_status, uint32_t* d_count, uint64_t plain_modulus,
                                                  uint32_t wide_words, uint64_t* d_wide, void* stream);
+
+/* ---- weighted sums of dealers' ciphertexts: the scheme is linear, not just additive, so sum_d w_d ct_d is a
+ * ciphertext of sum_d w_d m_d under the same keys, with noise sum_d |w_d| noise_d.  With w the Lagrange weights at 0 of the valid
+ * old holders (pvw_shamir_lagrange_weights) a committee handover -- every old holder d re-shares its share with a fresh polynomial
+ * f_d, new party j needs sum_d lambda_d f_d(j + 1) mod p -- is one pass over the ciphertexts and ONE decrypt per party instead of
+ * D; w = -1 gives differences, small random weights batch checks.  Each function takes the arguments of the pvw_ct_sum /
+ * pvw_decrypt_sum_plain call it mirrors plus `weights` directly after `valid`, and keeps that call's contract with this changed:
+ *   out = sum_{d participating} w_d in_d, word by word mod q_i.  weights: int64_t[D], w_d ANY value (INT64_MIN included) read as
+ *   the integer it is (its residue mod q_i is ((w mod q_i) + q_i) mod q_i); NULL: PVW_ERR_INVALID_PARAMETERS "NULL argument".
+ *   Dealer d PARTICIPATES when it is valid (valid == NULL or valid[d] != 0) and w_d != 0; a dealer that does not is never read.
+ *   *count = participating dealers.  Any 64-bit input word, every output word below q_i; both representations; the row range of
+ *   pvw_ct_sum.  With every weight 1 each call is bit-equal to the pvw_ct_sum* / pvw_decrypt_*sum_plain* call it mirrors.
+ * Argument errors are those of the mirrored call and come before any device work. */
+/* device pointers (d_weights too), asynchronous on `stream`; mask AND weights are read when the kernel runs, so a captured call
+ * replays with the values of the moment.  An all-zero mask or all-zero weights write zeros and *d_count = 0.  pvw_prepare
+ * (PVW_PREPARE_SUM) and stream capture exactly as pvw_ct_sum_device, with the same scratch. */
+PVW_API int32_t pvw_ct_lincomb_device(pvw_ctx* ctx, const uint64_t* d_c1s, const uint64_t* d_c2s, size_t num_dealers,
+                                      const uint8_t* d_valid, const int64_t* d_weights, uint32_t row_lo, uint32_t row_hi,
+                                      uint64_t* d_c1_out, uint64_t* d_c2_out, uint32_t* d_count, void* stream);
+/* host buffers (synchronous): only the participating dealers are staged, in bounded pieces, each piece with its weights.  No
+ * participating dealer: PVW_ERR_INSUFFICIENT_DATA before any device work. */
+PVW_API int32_t pvw_ct_lincomb(pvw_ctx* ctx, const uint64_t* c1s, const uint64_t* c2s, size_t num_dealers, const uint8_t* valid,
+                               const int64_t* weights, uint32_t row_lo, uint32_t row_hi, uint64_t* c1_out, uint64_t* c2_out,
+                               uint32_t* count);
+/* the definition in plain loops on the host cores (no GPU needed): what the device kernels are tested against */
+PVW_API int32_t pvw_ct_lincomb_host(const pvw_ctx* ctx, const uint64_t* c1s, const uint64_t* c2s, size_t num_dealers,
+                                    const uint8_t* valid, const int64_t* weights, uint32_t row_lo, uint32_t row_hi, uint64_t* c1_out,
+                                    uint64_t* c2_out, uint32_t* count);
+/* One party's view of the combination (c1 plus the party's column): pvw_decrypt_sum_plain* with the sum replaced.  plain_modulus /
+ * wide_words / wide, the status bits, key hygiene and the capture rules are unchanged; both options 0: the checked word.
+ * The `noise` word saturates at 2^64 - 1, which a combination with field-sized weights always reaches (its noise is near
+ * 2^72): for such combinations pvw_ctx_lincomb_fits below, not the noise word, is what a caller has. */
+PVW_API int32_t pvw_decrypt_lincomb_plain(pvw_ctx* ctx, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col,
+                                          size_t num_dealers, const uint8_t* valid, const int64_t* weights, uint32_t in_repr,
+                                          uint64_t* out_u64, uint64_t* noise, uint32_t* status, uint32_t* count,
+                                          uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide);
+PVW_API int32_t pvw_decrypt_lincomb_plain_device(pvw_ctx* ctx, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col,
+                                                 size_t num_dealers, const uint8_t* d_valid, const int64_t* d_weights,
+                                                 uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise,
+                                                 uint32_t* d_status, uint32_t* d_count, uint64_t plain_modulus, uint32_t wide_words,
+                                                 uint64_t* d_wide, void* stream);
+PVW_API int32_t pvw_decrypt_lincomb_device_sk_plain(pvw_ctx* ctx, const pvw_sk* key, const uint64_t* d_c1s, const uint64_t* d_c2col,
+                                                    size_t num_dealers, const uint8_t* d_valid, const int64_t* d_weights,
+                                                    uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise,
+                                                    uint32_t* d_status, uint32_t* d_count, uint64_t plain_modulus,
+                                                    uint32_t wide_words, uint64_t* d_wide, void* stream);
+/* Every party of [party_lo, party_hi): pvw_decrypt_all_sum_plain* with the combination.  out / noise / status [P], wide [P][wide_words].
+ * The handover: secrets = the old shares sigma_d = F(d + 1) into pvw_deal_shares; valid = the old holders whose dealing verified;
+ * weights = pvw_shamir_lagrange_weights over the valid old indices (0 elsewhere); plain_modulus = p.  out[j] is new party j's share
+ * of F(0). */
+PVW_API int32_t pvw_decrypt_all_lincomb_plain(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* sk,
+                                              const uint64_t* c1s, const uint64_t* c2s, size_t num_dealers, const uint8_t* valid,
+                                              const int64_t* weights, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise,
+                                              uint32_t* status, uint32_t* count, uint64_t plain_modulus, uint32_t wide_words,
+                                              uint64_t* wide);
+PVW_API int32_t pvw_decrypt_all_lincomb_plain_device(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* d_sk,
+                                                     const uint64_t* d_c1s, const uint64_t* d_c2s, size_t num_dealers,
+                                                     const uint8_t* d_valid, const int64_t* d_weights, uint32_t in_repr,
+                                                     uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count,
+                                                     uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream);
+/* Advisory, host only (host big integers): *fits = 1 iff (sum over the participating dealers of |w_d|) * pvw_ctx_noise_bound <= R,
+ * R the radius pvw_ctx_sum_capacity is built on; else 0.  Sufficient, not necessary, like that function, and no entry point refuses
+ * on noise grounds.  weights / valid are HOST pointers (valid may be NULL). */
+PVW_API int32_t pvw_ctx_lincomb_fits(const pvw_ctx* ctx, const int64_t* weights, size_t num_dealers, const uint8_t* valid,
+                                     uint32_t* fits);
+/* Host only, no context: weights_out[i] = the Lagrange weight at 0 of the point indices[i] + 1 among the points indices[.] + 1,
+ * mod p = plain_modulus, CENTRED in (-p/2, p/2] (so that it enlarges the noise as little as its residue class allows).  The routine
+ * and the argument rules of pvw_shamir_reconstruct below: p prime and < 2^62, no duplicate index, every index < p - 1, count >= 1. */
+PVW_API int32_t pvw_shamir_lagrange_weights(uint64_t plain_modulus, const uint64_t* indices, size_t count, int64_t* weights_out);
 
 /* ---- Shamir shares: from secrets to ciphertexts in one call, and back --------------------------------------
  * The dealing end of the protocol the reference's examples sketch (examples/pvw.rs:95-131 fill the share matrix with arbitrary

@@ -231,6 +231,18 @@ class PvwParameters:
         self._call("pvw_ctx_sum_capacity", C.byref(v))
         return int(v.value)
 
+    def lincomb_fits(self, weights, valid=None) -> bool:
+        """pvw_ctx_lincomb_fits: whether (sum of |w_d| over the participating dealers -- valid and weight not 0) * noise_bound()
+        stays inside the radius sum_capacity() is built on, so that the decode of the combination is PROVEN exact.  Advisory
+        and sufficient only, like sum_capacity()."""
+        w = np.ascontiguousarray(np.array([int(x) for x in weights], dtype=np.int64))
+        v = None if valid is None else np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+        if v is not None and v.shape != w.shape:
+            raise PvwError(15, f"valid: expected {w.size} flags, got {v.size}")
+        fits = C.c_uint32()
+        self._call("pvw_ctx_lincomb_fits", _ptr(w), w.size, _ptr(v), C.byref(fits))
+        return bool(fits.value)
+
     @staticmethod
     def suggest_error_bounds(n, k, l, moduli, variance) -> Tuple[int, int]:   # :554-603
         m = _u64(list(moduli))
@@ -1278,6 +1290,110 @@ def decrypt_all_party_sums(cts: Sequence[PvwCiphertext], parties: Sequence["Part
     return CheckedDecryption(out, noise, status, b, on, wd)
 
 
+# ---- weighted sums of dealers' ciphertexts ----
+def _weights(weights, D: int, v) -> np.ndarray:
+    """the checks the combination calls add to _sum_inputs: one int64 per ciphertext, at least one participating dealer"""
+    w = [int(x) for x in weights]
+    if len(w) != D:
+        raise PvwError(15, f"weights: expected {D} weights, got {len(w)}")
+    for d, x in enumerate(w):
+        if not -(1 << 63) <= x < 1 << 63:
+            raise PvwError(1, f"weights[{d}] = {x} is outside the int64 range")
+    w = np.array(w, dtype=np.int64)
+    if not ((w != 0) & (True if v is None else v != 0)).any():
+        raise PvwError(17, f"No participating dealer (valid, weight not 0) among the {D} ciphertexts: expected at least 1, got 0")
+    return w
+
+
+def _abs_weight_sum(w: np.ndarray, v) -> int:
+    return sum(abs(int(x)) for d, x in enumerate(w) if v is None or v[d])
+
+
+def _lincomb_report(p, out, noise, status, w, v, bound, on, wd) -> "CheckedDecryption":
+    """The report of a combination.  bound defaults to (sum of |w_d| over the participating dealers) * noise_bound(); the
+    noise word saturates at 2^64 - 1, so when the bound does not fit 64 bits `valid` takes PvwParameters.lincomb_fits(weights,
+    valid) in place of the noise test (the same for every entry)."""
+    b = _bound(p, _abs_weight_sum(w, v) * p.noise_bound() if bound is None else bound)
+    r = CheckedDecryption(out, noise, status, b, on, wd)
+    if b >= 1 << 64:
+        fits = np.full(status.shape, p.lincomb_fits(w, v), dtype=bool)
+        r.valid = fits if on else ~r.lossy & fits
+    return r
+
+
+def combine_ciphertexts(cts: Sequence[PvwCiphertext], weights, valid=None, *, host: bool = False) -> PvwCiphertext:
+    """sum_d weights[d] * cts[d] over the participating dealers (valid and weight not 0; pvw_ct_lincomb): a ciphertext of
+    sum_d w_d m_d under the same keys, in the same representation; no key is needed.  weights: one Python integer in the int64
+    range per ciphertext, read as the integer it is.  host=True computes it on the host cores (pvw_ct_lincomb_host, no GPU).
+    Its noise is sum_d |w_d| noise_d (PvwParameters.lincomb_fits)."""
+    p, repr, v = _sum_inputs(cts, valid)
+    w = _weights(weights, len(cts), v)
+    c1s = np.ascontiguousarray(np.stack([ct.c1 for ct in cts]), dtype=np.uint64)
+    c2s = np.ascontiguousarray(np.stack([ct.c2 for ct in cts]), dtype=np.uint64)
+    c1 = np.zeros((p.k, p.L, p.l), dtype=np.uint64)
+    c2 = np.zeros((p.n, p.L, p.l), dtype=np.uint64)
+    p._call("pvw_ct_lincomb_host" if host else "pvw_ct_lincomb", _ptr(c1s), _ptr(c2s), len(cts), _ptr(v), _ptr(w), 0, p.n, _ptr(c1),
+            _ptr(c2), None)
+    return PvwCiphertext(c1, c2, p, repr)
+
+
+def decrypt_party_combination(cts: Sequence[PvwCiphertext], weights, secret_key: SecretKey, party_index: int, valid=None,
+                              plain_modulus: Optional[int] = None, wide: bool = False, *, bound: Optional[int] = None) -> CheckedDecryption:
+    """Party party_index's share of the combination sum_d w_d m_d from ONE decrypt (pvw_decrypt_lincomb_plain): with the
+    Lagrange weights of the valid old holders and plain_modulus = p, the party's new share after a handover.  Arrays of shape
+    [1].  `valid` of the report: see _lincomb_report -- with field-sized weights the noise word is saturated and
+    lincomb_fits stands in for the noise test."""
+    p, repr, v = _sum_inputs(cts, valid)
+    w = _weights(weights, len(cts), v)
+    if not 0 <= party_index < p.n:
+        raise PvwError(1, f"Party index {party_index} exceeds maximum {p.n - 1}")
+    c1s = np.ascontiguousarray(np.stack([ct.c1 for ct in cts]), dtype=np.uint64)
+    c2col = np.ascontiguousarray(np.stack([ct.c2[party_index] for ct in cts]), dtype=np.uint64)
+    sk = _i64(secret_key.secret_coeffs)
+    out, noise, status = np.zeros(1, np.uint64), np.zeros(1, np.uint64), np.zeros(1, np.uint32)
+    on, m, ww, wd = _plain(p, plain_modulus, wide, out.shape)
+    p._call("pvw_decrypt_lincomb_plain", _ptr(sk), _ptr(c1s), _ptr(c2col), len(cts), _ptr(v), _ptr(w), repr, _ptr(out), _ptr(noise),
+            _ptr(status), None, m, ww, _ptr(wd))
+    return _lincomb_report(p, out, noise, status, w, v, bound, on, wd)
+
+
+def decrypt_all_party_combinations(cts: Sequence[PvwCiphertext], weights, parties: Sequence["Party"], valid=None,
+                                   plain_modulus: Optional[int] = None, wide: bool = False, *,
+                                   bound: Optional[int] = None) -> CheckedDecryption:
+    """Every party's share of the combination in one call (pvw_decrypt_all_lincomb_plain): arrays of shape [len(parties)].  The
+    parties must have consecutive indices.  `valid` of the report as decrypt_party_combination."""
+    p, repr, v = _sum_inputs(cts, valid)
+    w = _weights(weights, len(cts), v)
+    if len(parties) == 0:
+        return _lincomb_report(p, np.zeros(0, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.uint32), w, v, bound, False, None)
+    lo = parties[0].index
+    for i, party in enumerate(parties):
+        if party.index >= p.n:
+            raise PvwError(1, f"Party index {party.index} exceeds maximum {p.n - 1}")
+        if party.index != lo + i:
+            raise PvwError(1, f"Party indices must be consecutive: {party.index} follows {lo + i - 1}")
+    c1s = np.ascontiguousarray(np.stack([ct.c1 for ct in cts]), dtype=np.uint64)
+    c2s = np.ascontiguousarray(np.stack([ct.c2 for ct in cts]), dtype=np.uint64)
+    sk = np.ascontiguousarray(np.stack([_i64(party.secret_key.secret_coeffs) for party in parties]))
+    out, noise, status = np.zeros(len(parties), np.uint64), np.zeros(len(parties), np.uint64), np.zeros(len(parties), np.uint32)
+    on, m, ww, wd = _plain(p, plain_modulus, wide, out.shape)
+    try:
+        p._call("pvw_decrypt_all_lincomb_plain", lo, lo + len(parties), _ptr(sk), _ptr(c1s), _ptr(c2s), len(cts), _ptr(v), _ptr(w),
+                repr, _ptr(out), _ptr(noise), _ptr(status), None, m, ww, _ptr(wd))
+    finally:
+        sk.fill(0)                                                         # the stacked copy of the keys (secret_key.rs:20-30)
+    return _lincomb_report(p, out, noise, status, w, v, bound, on, wd)
+
+
+def shamir_lagrange_weights(indices: Sequence[int], plain_modulus: int) -> List[int]:
+    """The Lagrange weights at 0 of the points indices[i] + 1 mod plain_modulus, centred in (-p/2, p/2]
+    (pvw_shamir_lagrange_weights; host only, the argument rules of shamir_reconstruct)."""
+    idx = _words(indices)
+    out = np.zeros(len(idx), dtype=np.int64)
+    _check(_ffi.lib().pvw_shamir_lagrange_weights(int(plain_modulus), _ptr(idx), len(idx), _ptr(out)))
+    return [int(x) for x in out]
+
+
 def _dptr(x):
     """a device buffer: a torch tensor (its data_ptr()), a raw address as an int, or None"""
     if x is None:
@@ -1334,6 +1450,18 @@ class DeviceSecretKey:
         self.params._call("pvw_decrypt_sum_device_sk_checked", self._h, _dptr(d_c1s), _dptr(d_c2col), int(num_dealers),
                           _dptr(d_valid), in_repr, _dptr(d_noisy), _dptr(d_out), _dptr(d_noise), _dptr(d_status), _dptr(d_count),
                           _stream_ptr(stream))
+
+    def decrypt_lincomb_device_plain(self, d_c1s, d_c2col, num_dealers: int, d_weights, d_out, d_valid=None, d_noisy=None,
+                                     d_noise=None, d_status=None, d_count=None, stream=None, in_repr: int = REPR_NTT, *,
+                                     plain_modulus: Optional[int] = None, wide=None, wide_words: int = 0) -> None:
+        """pvw_decrypt_lincomb_device_sk_plain: this party's share of sum_d w_d m_d from ONE decrypt of the combination of the
+        participating dealers' ciphertexts.  Device buffers: d_weights int64 [D], d_valid uint8 [D] (None = all), d_out /
+        d_noise / d_status [1], d_count uint32 [1], wide [wide_words]; asynchronous on `stream`."""
+        if not self._h:
+            raise PvwError(1, "the DeviceSecretKey has been freed")
+        self.params._call("pvw_decrypt_lincomb_device_sk_plain", self._h, _dptr(d_c1s), _dptr(d_c2col), int(num_dealers),
+                          _dptr(d_valid), _dptr(d_weights), in_repr, _dptr(d_noisy), _dptr(d_out), _dptr(d_noise), _dptr(d_status),
+                          _dptr(d_count), int(plain_modulus or 0), int(wide_words), _dptr(wide), _stream_ptr(stream))
 
     def __enter__(self):
         return self

@@ -2159,10 +2159,8 @@ int32_t pvw_shamir_shares_host(const pvw_ctx* c, const uint64_t* secrets, size_t
   return PVW_OK;
 }
 
-// Lagrange weights at 0 for the points x_i = indices[i] + 1, once; then one dot product per secret.  Host only.
-int32_t pvw_shamir_reconstruct(uint64_t plain_modulus, const uint64_t* indices, const uint64_t* shares, size_t count,
-                               size_t num_secrets, uint64_t* out) {
-  if (!indices || !shares || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+// Lagrange weights at 0 for the points x_i = indices[i] + 1 (residues in [0, p)), behind the argument rules both callers share
+static int32_t shamir_weights_at_zero(uint64_t plain_modulus, const uint64_t* indices, size_t count, Mod* mod, std::vector<u64>* wout) {
   if (count == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no shares to reconstruct from");
   if (plain_modulus < 2) return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must be prime (Shamir shares live in a field)");
   PVW_TRY(shamir_modulus_check(plain_modulus));
@@ -2188,11 +2186,32 @@ int32_t pvw_shamir_reconstruct(uint64_t plain_modulus, const uint64_t* indices, 
     }
     w[i] = mulmod(num, powmod(den, m.q - 2, m), m);
   }
+  *mod = m;
+  wout->swap(w);
+  return PVW_OK;
+}
+// The weights once; then one dot product per secret.  Host only.
+int32_t pvw_shamir_reconstruct(uint64_t plain_modulus, const uint64_t* indices, const uint64_t* shares, size_t count,
+                               size_t num_secrets, uint64_t* out) {
+  if (!indices || !shares || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  Mod m;
+  std::vector<u64> w;
+  PVW_TRY(shamir_weights_at_zero(plain_modulus, indices, count, &m, &w));
   for (size_t sidx = 0; sidx < num_secrets; ++sidx) {
     u64 acc = 0;
     for (size_t i = 0; i < count; ++i) acc = addmod(acc, mulmod(reduce_word(shares[sidx * count + i], m), w[i], m), m.q);
     out[sidx] = acc;
   }
+  return PVW_OK;
+}
+// The same weights for a caller that combines ciphertexts with them: centred in (-p/2, p/2], so that the noise
+// of the combination grows by |w| and not by p - |w|.  Host only.
+int32_t pvw_shamir_lagrange_weights(uint64_t plain_modulus, const uint64_t* indices, size_t count, int64_t* weights_out) {
+  if (!indices || !weights_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  Mod m;
+  std::vector<u64> w;
+  PVW_TRY(shamir_weights_at_zero(plain_modulus, indices, count, &m, &w));
+  for (size_t i = 0; i < count; ++i) weights_out[i] = w[i] > m.q / 2 ? -(i64)(m.q - w[i]) : (i64)w[i];
   return PVW_OK;
 }
 
@@ -4045,8 +4064,10 @@ static int32_t sum_prepare(pvw_ctx* c, Workspace* w, hipStream_t s) {
 
 // c2: the first polynomial summed of dealer 0 -- c2s + row_lo L l with c2_stride = n L l (whole ciphertexts), or a party's
 // column with c2_stride = L l -- `rows` polynomials per dealer; c1_stride = k L l.  valid / count: device pointers (or NULL).
+// weights: NULL = the sum (ct_sum_kernel); else device words [D], the weighted form of DESIGN 8.12 (ct_lincomb_kernel).
 static int32_t ct_sum_enqueue(pvw_ctx* c, Workspace* w, hipStream_t s, const u64* c1s, const u64* c2, size_t c2_stride, size_t rows,
-                              size_t D, const uint8_t* valid, u64* c1_out, u64* c2_out, u32* count, bool accumulate = false) {
+                              size_t D, const uint8_t* valid, const i64* weights, u64* c1_out, u64* c2_out, u32* count,
+                              bool accumulate = false) {
   const size_t P = c->poly();
   SumRegion a, b;
   a.in = c1s; a.out = c1_out; a.stride = (size_t)c->k * P; a.items = (size_t)c->k * P / 2;
@@ -4054,40 +4075,57 @@ static int32_t ct_sum_enqueue(pvw_ctx* c, Workspace* w, hipStream_t s, const u64
   const size_t items = a.items + b.items;
   u32 ns = ct_sum_slices(items, D);
   if ((size_t)ns * items > ct_sum_partial_items_max()) ns = (u32)(ct_sum_partial_items_max() / items);   // a forced count (tuning build)
+  if (weights) {                                                   // the weighted form: weights device words [D]
+    ProfScope ps(c, "ct_lincomb", s);
+    PVW_HIP(launch_ct_lincomb(a, b, valid, weights, D, c->dt, c->L, c->l, ns > 1 ? w->sumbuf : nullptr, ns, accumulate, count, s));
+    return PVW_OK;
+  }
   ProfScope ps(c, "ct_sum", s);
   PVW_HIP(launch_ct_sum(a, b, valid, D, c->dt, c->L, c->l, ns > 1 ? w->sumbuf : nullptr, ns, accumulate, count, s));
   return PVW_OK;
 }
-static size_t count_valid(const uint8_t* valid, size_t D) {
-  if (!valid) return D;
+// a dealer takes part when it is valid and, in the weighted form (weights != NULL), its weight is not 0
+static bool takes_part(const uint8_t* valid, const i64* weights, size_t d) {
+  return (!valid || valid[d]) && (!weights || weights[d] != 0);
+}
+static size_t count_valid(const uint8_t* valid, const i64* weights, size_t D) {
+  if (!valid && !weights) return D;
   size_t nv = 0;
-  for (size_t d = 0; d < D; ++d) nv += valid[d] != 0;
+  for (size_t d = 0; d < D; ++d) nv += takes_part(valid, weights, d);
   return nv;
 }
-static int32_t no_valid_dealer(size_t D) {
-  char buf[112];
-  snprintf(buf, sizeof buf, "No valid dealer among the %zu ciphertexts: expected at least 1, got 0", D);
+static int32_t no_valid_dealer(size_t D, const i64* weights) {
+  char buf[144];
+  if (weights)
+    snprintf(buf, sizeof buf, "No participating dealer (valid, weight not 0) among the %zu ciphertexts: expected at least 1, got 0", D);
+  else
+    snprintf(buf, sizeof buf, "No valid dealer among the %zu ciphertexts: expected at least 1, got 0", D);
   return fail(PVW_ERR_INSUFFICIENT_DATA, buf);
 }
 // host buffers: runs of valid dealers are copied next to each other into st_c1 [per][k] / st_c2 [per][rows] and every full
-// piece is summed into d_c1_out / d_c2_out (the first piece stores, the later ones add); masked-out dealers are not copied
+// piece is summed into d_c1_out / d_c2_out (the first piece stores, the later ones add); masked-out dealers are not copied.
+// The weighted form (weights != NULL, host words [D]): the dealers that take part are staged, and the weights of the staged
+// runs travel with each piece into st_w [per].
 static int32_t ct_sum_staged(pvw_ctx* c, Workspace* w, u64* st_c1, u64* st_c2, size_t per, const u64* c1s, const u64* c2,
-                             size_t c2_stride, size_t rows, size_t D, const uint8_t* valid, u64* d_c1_out, u64* d_c2_out) {
+                             size_t c2_stride, size_t rows, size_t D, const uint8_t* valid, const i64* weights, i64* st_w,
+                             u64* d_c1_out, u64* d_c2_out) {
   const size_t P = c->poly(), ctw = (size_t)c->k * P;
   hipStream_t s = w->stream;
   size_t fill = 0;
   bool first = true;
   auto flush = [&]() -> int32_t {
     if (!fill) return PVW_OK;
-    PVW_TRY(ct_sum_enqueue(c, w, s, st_c1, st_c2, rows * P, rows, fill, nullptr, d_c1_out, d_c2_out, nullptr, !first));
+    PVW_TRY(ct_sum_enqueue(c, w, s, st_c1, st_c2, rows * P, rows, fill, nullptr, weights ? st_w : nullptr, d_c1_out, d_c2_out, nullptr,
+                           !first));
     first = false;
     fill = 0;
     return PVW_OK;
   };
   for (size_t d = 0; d < D;) {
-    if (valid && !valid[d]) { ++d; continue; }
+    if (!takes_part(valid, weights, d)) { ++d; continue; }
     size_t run = 1;
-    while (d + run < D && fill + run < per && (!valid || valid[d + run])) ++run;
+    while (d + run < D && fill + run < per && takes_part(valid, weights, d + run)) ++run;
+    if (weights) PVW_HIP(hipMemcpyAsync(st_w + fill, weights + d, run * 8, hipMemcpyHostToDevice, s));
     PVW_HIP(hipMemcpyAsync(st_c1 + fill * ctw, c1s + d * ctw, run * ctw * 8, hipMemcpyHostToDevice, s));
     PVW_HIP(hipMemcpy2DAsync(st_c2 + fill * rows * P, rows * P * 8, c2 + d * c2_stride, c2_stride * 8, rows * P * 8, run,
                              hipMemcpyHostToDevice, s));
@@ -4111,9 +4149,15 @@ static int32_t ct_sum_checks(const pvw_ctx* c, const void* c1s, const void* c2s,
   if (lo == hi) return fail(PVW_ERR_INVALID_PARAMETERS, "empty row range");
   return PVW_OK;
 }
+// The weighted calls are the sum calls with the kernel exchanged: every family below has ONE body that takes
+// `weights` (NULL: the sum), and NULL weights at a pvw_*lincomb* entry is refused in front of it.
+static int32_t need_weights(const void* weights) {
+  return weights ? (int32_t)PVW_OK : fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+}
 // Not a device_call: the sum marks no key material, and device_end would drain the stream of a call that failed.
-int32_t pvw_ct_sum_device(pvw_ctx* c, const uint64_t* d_c1s, const uint64_t* d_c2s, size_t D, const uint8_t* d_valid, uint32_t lo,
-                          uint32_t hi, uint64_t* d_c1_out, uint64_t* d_c2_out, uint32_t* d_count, void* stream) {
+static int32_t ct_sum_device(pvw_ctx* c, const uint64_t* d_c1s, const uint64_t* d_c2s, size_t D, const uint8_t* d_valid,
+                             const i64* d_weights, uint32_t lo, uint32_t hi, uint64_t* d_c1_out, uint64_t* d_c2_out, uint32_t* d_count,
+                             void* stream) {
   PVW_TRY(ct_sum_checks(c, d_c1s, d_c2s, D, lo, hi, d_c1_out, d_c2_out));
   PVW_TRY(ensure_device(c));
   hipStream_t s = call_stream(c, stream);
@@ -4122,22 +4166,34 @@ int32_t pvw_ct_sum_device(pvw_ctx* c, const uint64_t* d_c1s, const uint64_t* d_c
   PVW_TRY(ws_for_stream(c, s, &w));
   PVW_TRY(sum_buffer(c, w, s));
   const size_t P = c->poly();
-  return ct_sum_enqueue(c, w, s, d_c1s, d_c2s + (size_t)lo * P, (size_t)c->n * P, hi - lo, D, d_valid, d_c1_out, d_c2_out, d_count);
+  return ct_sum_enqueue(c, w, s, d_c1s, d_c2s + (size_t)lo * P, (size_t)c->n * P, hi - lo, D, d_valid, d_weights, d_c1_out, d_c2_out,
+                        d_count);
 }
-int32_t pvw_ct_sum(pvw_ctx* c, const uint64_t* c1s, const uint64_t* c2s, size_t D, const uint8_t* valid, uint32_t lo, uint32_t hi,
-                   uint64_t* c1_out, uint64_t* c2_out, uint32_t* count) {
+int32_t pvw_ct_sum_device(pvw_ctx* c, const uint64_t* d_c1s, const uint64_t* d_c2s, size_t D, const uint8_t* d_valid, uint32_t lo,
+                          uint32_t hi, uint64_t* d_c1_out, uint64_t* d_c2_out, uint32_t* d_count, void* stream) {
+  return ct_sum_device(c, d_c1s, d_c2s, D, d_valid, nullptr, lo, hi, d_c1_out, d_c2_out, d_count, stream);
+}
+int32_t pvw_ct_lincomb_device(pvw_ctx* c, const uint64_t* d_c1s, const uint64_t* d_c2s, size_t D, const uint8_t* d_valid,
+                              const int64_t* d_weights, uint32_t lo, uint32_t hi, uint64_t* d_c1_out, uint64_t* d_c2_out,
+                              uint32_t* d_count, void* stream) {
+  PVW_TRY(need_weights(d_weights));
+  return ct_sum_device(c, d_c1s, d_c2s, D, d_valid, d_weights, lo, hi, d_c1_out, d_c2_out, d_count, stream);
+}
+static int32_t ct_sum_hostbuf(pvw_ctx* c, const uint64_t* c1s, const uint64_t* c2s, size_t D, const uint8_t* valid, const i64* weights,
+                              uint32_t lo, uint32_t hi, uint64_t* c1_out, uint64_t* c2_out, uint32_t* count) {
   PVW_TRY(ct_sum_checks(c, c1s, c2s, D, lo, hi, c1_out, c2_out));
-  const size_t nv = count_valid(valid, D);
-  if (nv == 0) return no_valid_dealer(D);
+  const size_t nv = count_valid(valid, weights, D);
+  if (nv == 0) return no_valid_dealer(D, weights);
   PVW_TRY(ensure_device(c));
   const size_t P = c->poly(), k = c->k, rows = hi - lo, per = chunk_1gib((k + rows) * P * 8, nv);
   Scratch sc;
-  const size_t r_c1 = sc.add(per * k * P * 8), r_c2 = sc.add(per * rows * P * 8);
+  const size_t r_c1 = sc.add(per * k * P * 8), r_c2 = sc.add(per * rows * P * 8), r_w = sc.add(weights ? per * 8 : 0);
   const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
     PVW_TRY(sum_buffer(c, w, w->stream));
     const SumView v = sum_view(c, w);
-    PVW_TRY(ct_sum_staged(c, w, sc.at(r_c1), sc.at(r_c2), per, c1s, c2s + (size_t)lo * P, (size_t)c->n * P, rows, D, valid, v.c1, v.c2));
+    PVW_TRY(ct_sum_staged(c, w, sc.at(r_c1), sc.at(r_c2), per, c1s, c2s + (size_t)lo * P, (size_t)c->n * P, rows, D, valid, weights,
+                          sc.at<i64>(r_w), v.c1, v.c2));
     PVW_HIP(hipMemcpyAsync(c1_out, v.c1, k * P * 8, hipMemcpyDeviceToHost, w->stream));
     PVW_HIP(hipMemcpyAsync(c2_out, v.c2, rows * P * 8, hipMemcpyDeviceToHost, w->stream));
     return PVW_OK;
@@ -4145,12 +4201,21 @@ int32_t pvw_ct_sum(pvw_ctx* c, const uint64_t* c1s, const uint64_t* c2s, size_t 
   if (rc == PVW_OK && count) *count = (uint32_t)nv;
   return rc;
 }
+int32_t pvw_ct_sum(pvw_ctx* c, const uint64_t* c1s, const uint64_t* c2s, size_t D, const uint8_t* valid, uint32_t lo, uint32_t hi,
+                   uint64_t* c1_out, uint64_t* c2_out, uint32_t* count) {
+  return ct_sum_hostbuf(c, c1s, c2s, D, valid, nullptr, lo, hi, c1_out, c2_out, count);
+}
+int32_t pvw_ct_lincomb(pvw_ctx* c, const uint64_t* c1s, const uint64_t* c2s, size_t D, const uint8_t* valid, const int64_t* weights,
+                       uint32_t lo, uint32_t hi, uint64_t* c1_out, uint64_t* c2_out, uint32_t* count) {
+  PVW_TRY(need_weights(weights));
+  return ct_sum_hostbuf(c, c1s, c2s, D, valid, weights, lo, hi, c1_out, c2_out, count);
+}
 // the same function in plain loops (no GPU): a 128-bit sum per word, one Barrett step at the end
 int32_t pvw_ct_sum_host(const pvw_ctx* c, const uint64_t* c1s, const uint64_t* c2s, size_t D, const uint8_t* valid, uint32_t lo,
                         uint32_t hi, uint64_t* c1_out, uint64_t* c2_out, uint32_t* count) {
   PVW_TRY(ct_sum_checks(c, c1s, c2s, D, lo, hi, c1_out, c2_out));
-  const size_t nv = count_valid(valid, D);
-  if (nv == 0) return no_valid_dealer(D);
+  const size_t nv = count_valid(valid, nullptr, D);
+  if (nv == 0) return no_valid_dealer(D, nullptr);
   const size_t P = c->poly(), l = c->l;
   auto region = [&](const u64* in, size_t stride, size_t words, u64* out) {
     for (size_t i = 0; i < words; ++i) {
@@ -4158,6 +4223,28 @@ int32_t pvw_ct_sum_host(const pvw_ctx* c, const uint64_t* c1s, const uint64_t* c
       for (size_t d = 0; d < D; ++d)
         if (!valid || valid[d]) acc += in[d * stride + i];
       out[i] = reduce128((u64)acc, (u64)(acc >> 64), c->mods[(i % P) / l]);
+    }
+  };
+  region(c1s, (size_t)c->k * P, (size_t)c->k * P, c1_out);
+  region(c2s + (size_t)lo * P, (size_t)c->n * P, (size_t)(hi - lo) * P, c2_out);
+  if (count) *count = (uint32_t)nv;
+  return PVW_OK;
+}
+// the weighted form by its definition (no GPU): signed_residue of the weight, mulmod by the word, addmod
+int32_t pvw_ct_lincomb_host(const pvw_ctx* c, const uint64_t* c1s, const uint64_t* c2s, size_t D, const uint8_t* valid,
+                            const int64_t* weights, uint32_t lo, uint32_t hi, uint64_t* c1_out, uint64_t* c2_out, uint32_t* count) {
+  PVW_TRY(need_weights(weights));
+  PVW_TRY(ct_sum_checks(c, c1s, c2s, D, lo, hi, c1_out, c2_out));
+  const size_t nv = count_valid(valid, weights, D);
+  if (nv == 0) return no_valid_dealer(D, weights);
+  const size_t P = c->poly(), l = c->l;
+  auto region = [&](const u64* in, size_t stride, size_t words, u64* out) {
+    for (size_t i = 0; i < words; ++i) {
+      const Mod& m = c->mods[(i % P) / l];
+      u64 acc = 0;
+      for (size_t d = 0; d < D; ++d)
+        if (takes_part(valid, weights, d)) acc = addmod(acc, mulmod(signed_residue(weights[d], m), in[d * stride + i], m), m.q);
+      out[i] = acc;
     }
   };
   region(c1s, (size_t)c->k * P, (size_t)c->k * P, c1_out);
@@ -4192,7 +4279,7 @@ static int32_t decrypt_sum_checks(bool any_null, size_t D, uint32_t in_repr) {
 }
 // device pointers; checked and plain forms
 static int32_t decrypt_sum_device(pvw_ctx* c, KeyRef key, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D, const uint8_t* d_valid,
-                                  uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status,
+                                  const i64* d_weights, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status,
                                   uint32_t* d_count, uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream) {
   Report rep;
   PVW_TRY(key.rc);
@@ -4202,7 +4289,7 @@ static int32_t decrypt_sum_device(pvw_ctx* c, KeyRef key, const uint64_t* d_c1s,
                      [&](Workspace* w, hipStream_t s) -> int32_t {
     PVW_TRY(sum_buffer(c, w, s));
     const SumView v = sum_view(c, w);
-    PVW_TRY(ct_sum_enqueue(c, w, s, d_c1s, d_c2col, c->poly(), 1, D, d_valid, v.c1, v.c2, d_count));
+    PVW_TRY(ct_sum_enqueue(c, w, s, d_c1s, d_c2col, c->poly(), 1, D, d_valid, d_weights, v.c1, v.c2, d_count));
     return decrypt_sum_tail(c, w, s, key, in_repr, d_noisy, rep);
   });
 }
@@ -4210,39 +4297,55 @@ int32_t pvw_decrypt_sum_plain_device(pvw_ctx* c, const int64_t* d_sk, const uint
                                      const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise,
                                      uint32_t* d_status, uint32_t* d_count, uint64_t plain_modulus, uint32_t wide_words,
                                      uint64_t* d_wide, void* stream) {
-  return decrypt_sum_device(c, key_coeffs(c, d_sk), d_c1s, d_c2col, D, d_valid, in_repr, d_noisy, d_out, d_noise, d_status, d_count, plain_modulus,
+  return decrypt_sum_device(c, key_coeffs(c, d_sk), d_c1s, d_c2col, D, d_valid, nullptr, in_repr, d_noisy, d_out, d_noise, d_status, d_count, plain_modulus,
                             wide_words, d_wide, stream);
 }
 int32_t pvw_decrypt_sum_device_sk_plain(pvw_ctx* c, const pvw_sk* key, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
                                         const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out,
                                         uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, uint64_t plain_modulus,
                                         uint32_t wide_words, uint64_t* d_wide, void* stream) {
-  return decrypt_sum_device(c, key_resident(c, key), d_c1s, d_c2col, D, d_valid, in_repr, d_noisy, d_out, d_noise, d_status, d_count, plain_modulus,
+  return decrypt_sum_device(c, key_resident(c, key), d_c1s, d_c2col, D, d_valid, nullptr, in_repr, d_noisy, d_out, d_noise, d_status, d_count, plain_modulus,
                             wide_words, d_wide, stream);
 }
 int32_t pvw_decrypt_sum_checked_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
                                        const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out, uint64_t* d_noise,
                                        uint32_t* d_status, uint32_t* d_count, void* stream) {
-  return decrypt_sum_device(c, key_coeffs(c, d_sk), d_c1s, d_c2col, D, d_valid, in_repr, d_noisy, d_out, d_noise, d_status, d_count, 0, 0, nullptr, stream);
+  return decrypt_sum_device(c, key_coeffs(c, d_sk), d_c1s, d_c2col, D, d_valid, nullptr, in_repr, d_noisy, d_out, d_noise, d_status, d_count, 0, 0, nullptr, stream);
 }
 int32_t pvw_decrypt_sum_device_sk_checked(pvw_ctx* c, const pvw_sk* key, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
                                           const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_noisy, uint64_t* d_out,
                                           uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, void* stream) {
-  return decrypt_sum_device(c, key_resident(c, key), d_c1s, d_c2col, D, d_valid, in_repr, d_noisy, d_out, d_noise, d_status, d_count, 0, 0, nullptr, stream);
+  return decrypt_sum_device(c, key_resident(c, key), d_c1s, d_c2col, D, d_valid, nullptr, in_repr, d_noisy, d_out, d_noise, d_status, d_count, 0, 0, nullptr, stream);
+}
+int32_t pvw_decrypt_lincomb_plain_device(pvw_ctx* c, const int64_t* d_sk, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
+                                         const uint8_t* d_valid, const int64_t* d_weights, uint32_t in_repr, uint64_t* d_noisy,
+                                         uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count,
+                                         uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream) {
+  PVW_TRY(need_weights(d_weights));
+  return decrypt_sum_device(c, key_coeffs(c, d_sk), d_c1s, d_c2col, D, d_valid, d_weights, in_repr, d_noisy, d_out, d_noise, d_status,
+                            d_count, plain_modulus, wide_words, d_wide, stream);
+}
+int32_t pvw_decrypt_lincomb_device_sk_plain(pvw_ctx* c, const pvw_sk* key, const uint64_t* d_c1s, const uint64_t* d_c2col, size_t D,
+                                            const uint8_t* d_valid, const int64_t* d_weights, uint32_t in_repr, uint64_t* d_noisy,
+                                            uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count,
+                                            uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream) {
+  PVW_TRY(need_weights(d_weights));
+  return decrypt_sum_device(c, key_resident(c, key), d_c1s, d_c2col, D, d_valid, d_weights, in_repr, d_noisy, d_out, d_noise, d_status,
+                            d_count, plain_modulus, wide_words, d_wide, stream);
 }
 // host buffers
-int32_t pvw_decrypt_sum_plain(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D, const uint8_t* valid,
-                              uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status, uint32_t* count,
-                              uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
+static int32_t decrypt_sum_hostbuf(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
+                                   const uint8_t* valid, const i64* weights, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise,
+                                   uint32_t* status, uint32_t* count, uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
   Report rep;
   PVW_TRY(report_args(c, out_u64, noise, status, plain_modulus, wide_words, wide, &rep));
   PVW_TRY(decrypt_sum_checks(!sk || !c1s || !c2col || !out_u64, D, in_repr));
-  const size_t nv = count_valid(valid, D);
-  if (nv == 0) return no_valid_dealer(D);
+  const size_t nv = count_valid(valid, weights, D);
+  if (nv == 0) return no_valid_dealer(D, weights);
   PVW_TRY(ensure_device(c));
   const size_t P = c->poly(), k = c->k, l = c->l, per = chunk_1gib((k + 1) * P * 8, nv);
   Scratch sc;
-  const size_t r_sk = sc.add(k * l * 8), r_c1 = sc.add(per * k * P * 8), r_c2 = sc.add(per * P * 8);
+  const size_t r_sk = sc.add(k * l * 8), r_c1 = sc.add(per * k * P * 8), r_c2 = sc.add(per * P * 8), r_w = sc.add(weights ? per * 8 : 0);
   const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
     PVW_TRY(sum_buffer(c, w, w->stream));
@@ -4252,12 +4355,23 @@ int32_t pvw_decrypt_sum_plain(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s
     sc.secret(w, r_sk, r_sk);
     ws_mark_secret(w, v.io, Report::packed_bytes(1, rep.ww));
     PVW_HIP(hipMemcpyAsync(d_sk, sk, k * l * 8, hipMemcpyHostToDevice, w->stream));
-    PVW_TRY(ct_sum_staged(c, w, sc.at(r_c1), sc.at(r_c2), per, c1s, c2col, P, 1, D, valid, v.c1, v.c2));
+    PVW_TRY(ct_sum_staged(c, w, sc.at(r_c1), sc.at(r_c2), per, c1s, c2col, P, 1, D, valid, weights, sc.at<i64>(r_w), v.c1, v.c2));
     PVW_TRY(decrypt_sum_tail(c, w, w->stream, key_coeffs(c, d_sk), in_repr, nullptr, dev));
     return dev.copy_to(rep, 1, hipMemcpyDeviceToHost, w->stream);
   });
   if (rc == PVW_OK && count) *count = (uint32_t)nv;
   return rc;
+}
+int32_t pvw_decrypt_sum_plain(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D, const uint8_t* valid,
+                              uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status, uint32_t* count,
+                              uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
+  return decrypt_sum_hostbuf(c, sk, c1s, c2col, D, valid, nullptr, in_repr, out_u64, noise, status, count, plain_modulus, wide_words, wide);
+}
+int32_t pvw_decrypt_lincomb_plain(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
+                                  const uint8_t* valid, const int64_t* weights, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise,
+                                  uint32_t* status, uint32_t* count, uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
+  PVW_TRY(need_weights(weights));
+  return decrypt_sum_hostbuf(c, sk, c1s, c2col, D, valid, weights, in_repr, out_u64, noise, status, count, plain_modulus, wide_words, wide);
 }
 int32_t pvw_decrypt_sum_checked(pvw_ctx* c, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2col, size_t D,
                                 const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status,
@@ -4277,10 +4391,10 @@ static int32_t decrypt_all_sum_tail(pvw_ctx* c, Workspace* w, hipStream_t s, u32
   }
   return decrypt_all_run(c, w, s, AllCall{lo, (size_t)hi - lo, 1, d_sk, v.c1, v.c2, false, false, rep});
 }
-int32_t pvw_decrypt_all_sum_plain_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
-                                         const uint64_t* d_c2s, size_t D, const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_out,
-                                         uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, uint64_t plain_modulus,
-                                         uint32_t wide_words, uint64_t* d_wide, void* stream) {
+static int32_t decrypt_all_sum_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
+                                      const uint64_t* d_c2s, size_t D, const uint8_t* d_valid, const i64* d_weights, uint32_t in_repr,
+                                      uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, uint64_t plain_modulus,
+                                      uint32_t wide_words, uint64_t* d_wide, void* stream) {
   Report rep;
   PVW_TRY(report_args(c, d_out, d_noise, d_status, plain_modulus, wide_words, d_wide, &rep));
   PVW_TRY(decrypt_all_checks(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out));
@@ -4291,10 +4405,25 @@ int32_t pvw_decrypt_all_sum_plain_device(pvw_ctx* c, uint32_t lo, uint32_t hi, c
     PVW_TRY(sum_buffer(c, w, s));
     PVW_TRY(ws_scratch(w, need));                                    // before anything of this call is enqueued
     const SumView v = sum_view(c, w);
-    PVW_TRY(ct_sum_enqueue(c, w, s, d_c1s, d_c2s + (size_t)lo * P, (size_t)c->n * P, hi - lo, D, d_valid, v.c1, v.c2 + (size_t)lo * P,
-                           d_count));
+    PVW_TRY(ct_sum_enqueue(c, w, s, d_c1s, d_c2s + (size_t)lo * P, (size_t)c->n * P, hi - lo, D, d_valid, d_weights, v.c1,
+                           v.c2 + (size_t)lo * P, d_count));
     return decrypt_all_sum_tail(c, w, s, lo, hi, d_sk, in_repr, rep);
   });
+}
+int32_t pvw_decrypt_all_sum_plain_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
+                                         const uint64_t* d_c2s, size_t D, const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_out,
+                                         uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count, uint64_t plain_modulus,
+                                         uint32_t wide_words, uint64_t* d_wide, void* stream) {
+  return decrypt_all_sum_device(c, lo, hi, d_sk, d_c1s, d_c2s, D, d_valid, nullptr, in_repr, d_out, d_noise, d_status, d_count,
+                                plain_modulus, wide_words, d_wide, stream);
+}
+int32_t pvw_decrypt_all_lincomb_plain_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
+                                             const uint64_t* d_c2s, size_t D, const uint8_t* d_valid, const int64_t* d_weights,
+                                             uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count,
+                                             uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream) {
+  PVW_TRY(need_weights(d_weights));
+  return decrypt_all_sum_device(c, lo, hi, d_sk, d_c1s, d_c2s, D, d_valid, d_weights, in_repr, d_out, d_noise, d_status, d_count,
+                                plain_modulus, wide_words, d_wide, stream);
 }
 int32_t pvw_decrypt_all_sum_checked_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
                                            const uint64_t* d_c2s, size_t D, const uint8_t* d_valid, uint32_t in_repr, uint64_t* d_out,
@@ -4302,22 +4431,23 @@ int32_t pvw_decrypt_all_sum_checked_device(pvw_ctx* c, uint32_t lo, uint32_t hi,
   return pvw_decrypt_all_sum_plain_device(c, lo, hi, d_sk, d_c1s, d_c2s, D, d_valid, in_repr, d_out, d_noise, d_status, d_count, 0, 0,
                                           nullptr, stream);
 }
-int32_t pvw_decrypt_all_sum_plain(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
-                                  size_t D, const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status,
-                                  uint32_t* count, uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
+static int32_t decrypt_all_sum_hostbuf(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
+                                       size_t D, const uint8_t* valid, const i64* weights, uint32_t in_repr, uint64_t* out_u64,
+                                       uint64_t* noise, uint32_t* status, uint32_t* count, uint64_t plain_modulus, uint32_t wide_words,
+                                       uint64_t* wide) {
   Report rep;
   PVW_TRY(report_args(c, out_u64, noise, status, plain_modulus, wide_words, wide, &rep));
   PVW_TRY(decrypt_all_checks(c, lo, hi, sk, c1s, c2s, D, in_repr, out_u64));
   PVW_TRY(check_dealers(D, true));
-  const size_t nv = count_valid(valid, D);
-  if (nv == 0) return no_valid_dealer(D);
+  const size_t nv = count_valid(valid, weights, D);
+  if (nv == 0) return no_valid_dealer(D, weights);
   PVW_TRY(ensure_device(c));
   const size_t P = c->poly(), k = c->k, l = c->l, NP = (size_t)hi - lo, per = chunk_1gib((k + NP) * P * 8, nv);
   const size_t need = decrypt_all_sum_need(c, NP, rep.ww);
   // the staged pieces and the decrypt's own scratch share the front of the block (stream order: the sum has read the pieces
   // before the decrypt writes there); the uploaded keys sit behind both
   Scratch st;
-  const size_t r_c1 = st.add(per * k * P * 8), r_c2 = st.add(per * NP * P * 8);
+  const size_t r_c1 = st.add(per * k * P * 8), r_c2 = st.add(per * NP * P * 8), r_w = st.add(weights ? per * 8 : 0);
   Scratch sc;
   const size_t r_main = sc.add(need > st.total ? need : st.total), r_sk = sc.add(NP * k * l * 8);
   const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
@@ -4330,13 +4460,27 @@ int32_t pvw_decrypt_all_sum_plain(pvw_ctx* c, uint32_t lo, uint32_t hi, const in
     sc.secret(w, r_sk, r_sk);
     ws_mark_secret(w, v.io, Report::packed_bytes(c->n, rep.ww));
     PVW_HIP(hipMemcpyAsync(d_sk, sk, NP * k * l * 8, hipMemcpyHostToDevice, w->stream));
-    PVW_TRY(ct_sum_staged(c, w, st.at(r_c1), st.at(r_c2), per, c1s, c2s + (size_t)lo * P, (size_t)c->n * P, NP, D, valid, v.c1,
-                          v.c2 + (size_t)lo * P));
+    PVW_TRY(ct_sum_staged(c, w, st.at(r_c1), st.at(r_c2), per, c1s, c2s + (size_t)lo * P, (size_t)c->n * P, NP, D, valid, weights,
+                          st.at<i64>(r_w), v.c1, v.c2 + (size_t)lo * P));
     PVW_TRY(decrypt_all_sum_tail(c, w, w->stream, lo, hi, d_sk, in_repr, dev));
     return dev.copy_to(rep, NP, hipMemcpyDeviceToHost, w->stream);
   });
   if (rc == PVW_OK && count) *count = (uint32_t)nv;
   return rc;
+}
+int32_t pvw_decrypt_all_sum_plain(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
+                                  size_t D, const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status,
+                                  uint32_t* count, uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
+  return decrypt_all_sum_hostbuf(c, lo, hi, sk, c1s, c2s, D, valid, nullptr, in_repr, out_u64, noise, status, count, plain_modulus,
+                                 wide_words, wide);
+}
+int32_t pvw_decrypt_all_lincomb_plain(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
+                                      size_t D, const uint8_t* valid, const int64_t* weights, uint32_t in_repr, uint64_t* out_u64,
+                                      uint64_t* noise, uint32_t* status, uint32_t* count, uint64_t plain_modulus, uint32_t wide_words,
+                                      uint64_t* wide) {
+  PVW_TRY(need_weights(weights));
+  return decrypt_all_sum_hostbuf(c, lo, hi, sk, c1s, c2s, D, valid, weights, in_repr, out_u64, noise, status, count, plain_modulus,
+                                 wide_words, wide);
 }
 int32_t pvw_decrypt_all_sum_checked(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
                                     size_t D, const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise,
@@ -4355,6 +4499,20 @@ int32_t pvw_ctx_sum_capacity(const pvw_ctx* c, uint64_t* max_dealers) {
   const BigInt R = (c->Q - BigInt(1)) / ((c->delta_pow + BigInt(1)) * BigInt(2));
   const BigInt cap = nb ? R / BigInt(nb) : R;
   *max_dealers = cap.fits_u64() ? (cap.mag.empty() ? 0 : cap.mag[0]) : ~(uint64_t)0;
+  return PVW_OK;
+}
+// Advisory, the weighted form of the same radius: *fits = 1 iff (sum over the participating dealers of |w_d|) noise_bound <= R.
+// A weight multiplies its dealer's noise by |w|, so this is the sufficient condition of pvw_ctx_sum_capacity with the dealer
+// count replaced by the weights' absolute sum.  Host big integers (|INT64_MIN| = 2^63 is no special case there).
+int32_t pvw_ctx_lincomb_fits(const pvw_ctx* c, const int64_t* weights, size_t D, const uint8_t* valid, uint32_t* fits) {
+  if (!c || !weights || !fits) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  uint64_t nb = 0;
+  PVW_TRY(pvw_ctx_noise_bound(c, &nb));
+  const BigInt R = (c->Q - BigInt(1)) / ((c->delta_pow + BigInt(1)) * BigInt(2));
+  BigInt sum;
+  for (size_t d = 0; d < D; ++d)
+    if (takes_part(valid, weights, d)) sum = sum + BigInt(weights[d] < 0 ? (u64)0 - (u64)weights[d] : (u64)weights[d]);
+  *fits = sum * BigInt(nb) <= R ? 1u : 0u;
   return PVW_OK;
 }
 

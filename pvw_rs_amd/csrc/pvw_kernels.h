@@ -219,6 +219,12 @@ inline size_t ct_sum_partial_items_max() { return (size_t)(1024 + 512) * 256; } 
 // (out holds an earlier piece's result).  count: NULL, or receives the number of dealers summed.  dealers < 2^32.
 hipError_t launch_ct_sum(const SumRegion& a, const SumRegion& b, const unsigned char* valid, size_t dealers, const DevTables& t, u32 L,
                          u32 ell, u64* partial, u32 nslices, bool accumulate, u32* count, hipStream_t s);
+// The weighted form: out = sum over the PARTICIPATING dealers (valid and weights[d] != 0) of weights[d] * in_d,
+// weights[d] any int64 read as the integer it is (device words, read when the kernel runs).  Regions, slices, partial,
+// accumulate as launch_ct_sum; count receives the number of participating dealers.
+hipError_t launch_ct_lincomb(const SumRegion& a, const SumRegion& b, const unsigned char* valid, const i64* weights, size_t dealers,
+                             const DevTables& t, u32 L, u32 ell, u64* partial, u32 nslices, bool accumulate, u32* count,
+                             hipStream_t s);
 
 // ---- Shamir shares (pvw_shamir.hip): shares[d * row_stride + i] = f_d(i + 1) mod m.q for the dealers of the batch
 // and the parties i of [party_lo, party_hi); f_d = secrets[d] + sum_{j=1..degree} a_{d,j} x^j.  a_{d,j} = coeffs[d * degree + j - 1]

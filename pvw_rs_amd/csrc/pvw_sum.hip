@@ -149,6 +149,115 @@ hipError_t launch_ct_sum(const SumRegion& a, const SumRegion& b, const unsigned 
   return hipGetLastError();
 }
 
+// ---- weighted sums: out = sum over the participating dealers d of w_d * in_d, word by word mod q of the word's limb.
+// The frame of ct_sum_kernel (regions, items, the 64-dealer walk, U loads in flight, the split form, accumulate); the
+// arithmetic is new.  Lane i of a chunk reads valid[d0 + i] and weights[d0 + i]; a dealer PARTICIPATES when it is valid and its
+// weight is not 0, the ballot of that is the chunk's mask, and a dealer outside it is never addressed.  The weight of the
+// dealer being consumed is wave-uniform: broadcast from the lane that holds it (v_readlane), and every lane forms
+// signed_residue(w, q) for its own limb -- the lane's limb is fixed, so Mod is loaded once; |w| < q costs the compare only.
+// Accumulation: acc_mac_dev(acc, residue, word), the lazy 160-bit accumulator of mac_rows: the word is ANY 64-bit value, the
+// residue is below q < 2^62, fewer than 2^32 dealers; one acc_reduce at the end.
+template <int U>
+__global__ __launch_bounds__(256) void ct_lincomb_kernel(SumRegion ra, SumRegion rb, const unsigned char* __restrict__ valid,
+                                                         const i64* __restrict__ weights, u32 dealers, u32 per_slice,
+                                                         const Mod* __restrict__ mods, u32 ell, u32 L, u64* __restrict__ partial,
+                                                         u32 accumulate, u32* __restrict__ count) {
+  const size_t items_a = ra.items, total = ra.items + rb.items;
+  const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const u32 lane = threadIdx.x & 63;
+  const u32 dlo = blockIdx.y * per_slice;
+  const u32 dhi = (dealers - dlo) < per_slice ? dealers : dlo + per_slice;
+  // the number of participating dealers: one wave of one workgroup (ALL dealers, whatever the slices are)
+  if (count && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) {
+    u32 n = 0;
+    for (u64 d0 = 0; d0 < dealers; d0 += 64) {
+      const bool on = d0 + lane < dealers && (!valid || valid[d0 + lane] != 0) && weights[d0 + lane] != 0;
+      n += (u32)__builtin_popcountll(__builtin_amdgcn_ballot_w64(on));
+    }
+    if (lane == 0) *count = n;
+  }
+  const bool live = g < total;
+  const bool in_a = g < items_a;
+  const size_t it = live ? (in_a ? g : g - items_a) : 0;
+  const v2u64* src = reinterpret_cast<const v2u64*>(live ? (in_a ? ra.in : rb.in) : ra.in) + it;
+  const size_t stride = (in_a ? ra.stride : rb.stride) / 2;      // 16-byte items between dealers
+  const u32 poly = L * ell;
+  const Mod mq = mods[(u32)((2 * it) % poly) / ell];
+  Acc a0, a1;
+  acc_zero(a0);
+  acc_zero(a1);
+  // this chunk's weights, one dealer a lane (0 beyond the slice), and its participation bit
+  auto weight_of = [&](u64 d) -> i64 { return d < dhi ? weights[d] : 0; };
+  auto takes_part = [&](u64 d, i64 w) -> bool { return d < dhi && w != 0 && (!valid || valid[d] != 0); };
+  i64 wt = weight_of((u64)dlo + lane);
+  bool on = takes_part((u64)dlo + lane, wt);
+  for (u64 d0 = dlo; d0 < dhi; d0 += 64) {
+    u64 m = __builtin_amdgcn_ballot_w64(on);
+    const i64 wcur = wt;
+    wt = weight_of(d0 + 64 + lane);                              // the next 64 dealers' bytes and weights, under this chunk's loads
+    on = takes_part(d0 + 64 + lane, wt);
+    while (m) {
+      v2u64 x[U];
+      u32 b[U];                                                  // the lane that holds the slot's weight; 64: the slot is unused
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        x[u] = (v2u64){0, 0};
+        b[u] = 64;
+        if (m) {                                                 // wave-uniform
+          b[u] = (u32)__builtin_ctzll(m);
+          m &= m - 1;
+          if (live) x[u] = __builtin_nontemporal_load(src + (size_t)(d0 + b[u]) * stride);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);                         // every load of the group issued before its first multiply
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const u32 lo = (u32)__builtin_amdgcn_readlane((int)(u32)(u64)wcur, (int)(b[u] & 63));
+        const u32 hi = (u32)__builtin_amdgcn_readlane((int)(u32)((u64)wcur >> 32), (int)(b[u] & 63));
+        const i64 w = b[u] < 64 ? (i64)(((u64)hi << 32) | lo) : 0;   // wave-uniform; an unused slot of the last group: 0 * 0
+        const u64 r = signed_residue(w, mq);
+        acc_mac_dev(a0, r, x[u].x);
+        acc_mac_dev(a1, r, x[u].y);
+      }
+    }
+  }
+  if (!live) return;
+  v2u64 res = (v2u64){acc_reduce(a0, mq), acc_reduce(a1, mq)};
+  if (partial) {                                                 // split form: the slice's result, reduced, for ct_sum_finish
+    reinterpret_cast<v2u64*>(partial)[(size_t)blockIdx.y * total + g] = res;
+    return;
+  }
+  v2u64* o = reinterpret_cast<v2u64*>(in_a ? ra.out : rb.out) + it;
+  if (accumulate) {                                              // out += the combination (a later piece of a staged call)
+    const v2u64 p = *o;
+    res.x = addmod(res.x, reduce_word(p.x, mq), mq.q);
+    res.y = addmod(res.y, reduce_word(p.y, mq), mq.q);
+  }
+  *o = res;
+}
+
+hipError_t launch_ct_lincomb(const SumRegion& a, const SumRegion& b, const unsigned char* valid, const i64* weights, size_t dealers,
+                             const DevTables& t, u32 L, u32 ell, u64* partial, u32 nslices, bool accumulate, u32* count,
+                             hipStream_t s) {
+  const size_t total = a.items + b.items;
+  if (total == 0 || dealers == 0 || dealers >> 32 || !weights) return hipErrorInvalidValue;
+  const size_t wgs = (total + 255) / 256;
+  if (wgs >> 31) return hipErrorInvalidValue;
+  if (nslices <= 1 || !partial) {
+    ct_lincomb_kernel<8><<<dim3((u32)wgs, 1), dim3(256), 0, s>>>(a, b, valid, weights, (u32)dealers, (u32)dealers, t.mods, ell, L,
+                                                                 nullptr, accumulate ? 1u : 0u, count);
+    return hipGetLastError();
+  }
+  const u32 per = (u32)((dealers + nslices - 1) / nslices);
+  const u32 ny = (u32)((dealers + per - 1) / per);               // no empty slice: every partial plane is written
+  ct_lincomb_kernel<8><<<dim3((u32)wgs, ny), dim3(256), 0, s>>>(a, b, valid, weights, (u32)dealers, per, t.mods, ell, L, partial, 0u,
+                                                                count);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  ct_sum_finish_kernel<<<dim3((u32)wgs), dim3(256), 0, s>>>(partial, ny, a, b, t.mods, ell, L, accumulate ? 1u : 0u);
+  return hipGetLastError();
+}
+
 // p[0 .. words) = 0 as a kernel on `s`: the clearing of a small key-derived scratch region that has to stay ordered behind its
 // last reader when the call is captured into a graph and replayed
 __global__ __launch_bounds__(256) void wipe_words_kernel(u64* __restrict__ p, size_t words) {

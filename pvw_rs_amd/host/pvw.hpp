@@ -779,4 +779,90 @@ inline CheckedShares decrypt_all_party_sums(const std::vector<PvwCiphertext>& ct
   return r;
 }
 
+// ---- weighted sums of dealers' ciphertexts ----
+// the Lagrange weights at 0 of the points indices[i] + 1 mod plain_modulus, centred (pvw_shamir_lagrange_weights; host only)
+inline std::vector<int64_t> shamir_lagrange_weights(const std::vector<uint64_t>& indices, uint64_t plain_modulus) {
+  std::vector<int64_t> w(indices.size());
+  check(pvw_shamir_lagrange_weights(plain_modulus, indices.data(), indices.size(), w.data()));
+  return w;
+}
+// whether the combination is inside the radius the decode is PROVEN exact in (pvw_ctx_lincomb_fits; advisory)
+inline bool lincomb_fits(const std::shared_ptr<PvwParameters>& p, const std::vector<int64_t>& weights, const std::vector<bool>& valid = {}) {
+  if (!valid.empty() && valid.size() != weights.size()) throw PvwError(15, "valid must hold one flag per weight");
+  std::vector<uint8_t> v(valid.begin(), valid.end());
+  uint32_t fits = 0;
+  check(pvw_ctx_lincomb_fits(p->ctx, weights.data(), weights.size(), v.empty() ? nullptr : v.data(), &fits));
+  return fits != 0;
+}
+inline void combination_weights(const std::vector<PvwCiphertext>& cts, const std::vector<int64_t>& weights) {
+  if (weights.size() != cts.size()) throw PvwError(15, "weights must hold one value per ciphertext");
+}
+// sum_d weights[d] cts[d] over the participating dealers (valid and weight not 0; pvw_ct_lincomb): no key needed
+inline PvwCiphertext combine_ciphertexts(const std::vector<PvwCiphertext>& cts, const std::vector<int64_t>& weights,
+                                         const std::vector<bool>& valid = {}) {
+  const SumInputs in = sum_inputs(cts, valid);
+  combination_weights(cts, weights);
+  const auto& p = cts[0].params;
+  PvwCiphertext out{std::vector<uint64_t>(cts[0].c1.size()), std::vector<uint64_t>(cts[0].c2.size()), p, cts[0].repr};
+  check(pvw_ct_lincomb(p->ctx, in.c1s.data(), in.c2s.data(), cts.size(), in.valid_ptr(), weights.data(), 0, p->n, out.c1.data(),
+                       out.c2.data(), nullptr));
+  return out;
+}
+// The report of a combination: the noise word saturates at 2^64 - 1, so a bound of 0 means "by lincomb_fits" -- valid is that
+// predicate for every entry (and not lossy, without plain options); a bound given is the noise test of the sum wrappers.
+inline void combination_report(CheckedShares& r, const std::vector<uint32_t>& status, uint64_t bound, bool plain,
+                               const std::shared_ptr<PvwParameters>& p, const std::vector<int64_t>& weights, const std::vector<bool>& valid) {
+  checked_report(r, status, bound ? bound : ~(uint64_t)0, plain);
+  if (bound) return;
+  const bool fits = lincomb_fits(p, weights, valid);
+  for (size_t i = 0; i < r.valid.size(); ++i) r.valid[i] = r.valid[i] && fits;
+}
+// party_index's share of the combination from ONE decrypt (pvw_decrypt_lincomb_plain): the new share after a handover with the
+// Lagrange weights of the valid old holders and plain->modulus = p
+inline CheckedShares decrypt_party_combination(const std::vector<PvwCiphertext>& cts, const std::vector<int64_t>& weights, const SecretKey& sk,
+                                               uint32_t party_index, const std::vector<bool>& valid = {}, uint64_t bound = 0,
+                                               const pvw_plain_t* plain = nullptr) {
+  const SumInputs in = sum_inputs(cts, valid);
+  combination_weights(cts, weights);
+  const auto& p = cts[0].params;
+  if (party_index >= p->n) throw PvwError(1, "Party index exceeds maximum");
+  const size_t P = p->poly_words();
+  std::vector<uint64_t> c2col;
+  for (const auto& ct : cts) c2col.insert(c2col.end(), ct.c2.begin() + (size_t)party_index * P, ct.c2.begin() + (size_t)(party_index + 1) * P);
+  std::vector<uint32_t> status(1);
+  CheckedShares r{std::vector<uint64_t>(1), std::vector<uint64_t>(1), std::vector<bool>(1), std::vector<bool>(1)};
+  if (plain_on(plain)) r.wide.assign(plain->wide_words, 0);
+  check(pvw_decrypt_lincomb_plain(p->ctx, sk.secret_coeffs.data(), in.c1s.data(), c2col.data(), cts.size(), in.valid_ptr(), weights.data(),
+                                  cts[0].repr, r.values.data(), r.noise.data(), status.data(), nullptr, plain_on(plain) ? plain->modulus : 0,
+                                  plain_on(plain) ? plain->wide_words : 0, plain_on(plain) && plain->wide_words ? r.wide.data() : nullptr));
+  combination_report(r, status, bound, plain_on(plain), p, weights, valid);
+  return r;
+}
+// every party's share of the combination in one call (pvw_decrypt_all_lincomb_plain); parties with consecutive indices
+inline CheckedShares decrypt_all_party_combinations(const std::vector<PvwCiphertext>& cts, const std::vector<int64_t>& weights,
+                                                    const std::vector<Party>& parties, const std::vector<bool>& valid = {},
+                                                    uint64_t bound = 0, const pvw_plain_t* plain = nullptr) {
+  const SumInputs in = sum_inputs(cts, valid);
+  combination_weights(cts, weights);
+  const auto& p = cts[0].params;
+  const size_t NP = parties.size(), kl = (size_t)p->k * p->l;
+  CheckedShares r{std::vector<uint64_t>(NP), std::vector<uint64_t>(NP), std::vector<bool>(NP), std::vector<bool>(NP)};
+  if (NP == 0) return r;
+  std::vector<int64_t> sk(NP * kl);
+  for (size_t i = 0; i < NP; ++i) {
+    if (parties[i].index >= p->n || parties[i].index != parties[0].index + i) throw PvwError(1, "Party indices must be consecutive and below n");
+    std::copy(parties[i].secret_key.secret_coeffs.begin(), parties[i].secret_key.secret_coeffs.end(), sk.begin() + i * kl);
+  }
+  std::vector<uint32_t> status(NP);
+  if (plain_on(plain)) r.wide.assign(NP * plain->wide_words, 0);
+  const int32_t rc = pvw_decrypt_all_lincomb_plain(
+      p->ctx, parties[0].index, parties[0].index + (uint32_t)NP, sk.data(), in.c1s.data(), in.c2s.data(), cts.size(), in.valid_ptr(),
+      weights.data(), cts[0].repr, r.values.data(), r.noise.data(), status.data(), nullptr, plain_on(plain) ? plain->modulus : 0,
+      plain_on(plain) ? plain->wide_words : 0, plain_on(plain) && plain->wide_words ? r.wide.data() : nullptr);
+  std::fill(sk.begin(), sk.end(), 0);                                   // the copied keys do not outlive the call
+  check(rc);
+  combination_report(r, status, bound, plain_on(plain), p, weights, valid);
+  return r;
+}
+
 }  // namespace pvw_host

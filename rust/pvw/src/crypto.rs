@@ -626,3 +626,52 @@ pub fn decrypt_all_party_sums_plain(ciphertexts: &[PvwCiphertext], parties: &[cr
     check(rc)?;
     Ok(PlainDecryption { values: out, noise, status, wide })
 }
+
+/// The weights of a combination next to its ciphertexts: one per dealer.
+fn combination_weights(ciphertexts: &[PvwCiphertext], weights: &[i64]) -> Result<()> {
+    if weights.len() != ciphertexts.len() {
+        return Err(PvwError::DimensionMismatch { expected: ciphertexts.len(), actual: weights.len() });
+    }
+    Ok(())
+}
+
+/// EXTENSION: the weighted sum of the dealers' ciphertexts (`pvw_ct_lincomb`) -- a ciphertext of
+/// sum_d w_d m_d under the same keys, with noise sum_d |w_d| noise_d (`pvw_ctx_lincomb_fits`).  A dealer takes part when it
+/// is valid and its weight is not 0.
+pub fn combine(ciphertexts: &[PvwCiphertext], weights: &[i64], valid: Option<&[bool]>) -> Result<PvwCiphertext> {
+    let (c1s, c2s, v) = sum_inputs(ciphertexts, valid)?;
+    combination_weights(ciphertexts, weights)?;
+    let params = &ciphertexts[0].params;
+    let words = poly_words(params);
+    let (mut c1, mut c2) = (vec![0u64; params.k * words], vec![0u64; params.n * words]);
+    check(unsafe {
+        sys::pvw_ct_lincomb(params.hip.raw(), c1s.as_ptr(), c2s.as_ptr(), ciphertexts.len(), valid_ptr(&v), weights.as_ptr(), 0,
+                            params.n as u32, c1.as_mut_ptr(), c2.as_mut_ptr(), std::ptr::null_mut())
+    })?;
+    ciphertext_from_flat(&c1, &c2, params)
+}
+
+/// EXTENSION: party `party_index`'s share of the combination from ONE decrypt (`pvw_decrypt_lincomb_plain`), with the plain
+/// options of DESIGN 8.8: with the Lagrange weights of the valid old holders and `plain.modulus` = p this is the party's new
+/// share after a committee handover.  (report of one share, dealers that took part)
+pub fn decrypt_combination(ciphertexts: &[PvwCiphertext], weights: &[i64], secret_key: &SecretKey, party_index: usize, valid: Option<&[bool]>, plain: &PlainOptions) -> Result<(PlainDecryption, u32)> {
+    let (c1s, c2s, v) = sum_inputs(ciphertexts, valid)?;
+    combination_weights(ciphertexts, weights)?;
+    let params = &ciphertexts[0].params;
+    if party_index >= params.n {
+        return Err(PvwError::InvalidParameters(format!("Party index {} exceeds maximum {}", party_index, params.n - 1)));
+    }
+    let words = poly_words(params);
+    let c2col: Vec<u64> = c2s.chunks_exact(params.n * words).flat_map(|ct| ct[party_index * words..(party_index + 1) * words].to_vec()).collect();
+    let mut sk = flat_secret(secret_key);
+    let (mut out, mut noise, mut status, mut count) = (0u64, 0u64, 0u32, 0u32);
+    let mut wide = vec![0u64; plain.wide_words as usize];
+    let rc = unsafe {
+        sys::pvw_decrypt_lincomb_plain(params.hip.raw(), sk.as_ptr(), c1s.as_ptr(), c2col.as_ptr(), ciphertexts.len(), valid_ptr(&v),
+                                       weights.as_ptr(), sys::PVW_REPR_POWER, &mut out, &mut noise, &mut status, &mut count,
+                                       plain.modulus, plain.wide_words, wide_ptr(&mut wide))
+    };
+    sk.zeroize();
+    check(rc)?;
+    Ok((PlainDecryption { values: vec![out], noise: vec![noise], status: vec![status], wide }, count))
+}
