@@ -30,6 +30,8 @@
  *     read-only after load and every call takes a stream + workspace from a pool.
  *     The promise, as tests/test_gpu_concurrent_calls.py holds it: threads that share one context may overlap any of
  *     pvw_encrypt[_rs], pvw_encrypt_multi[_rs], pvw_deal_shares[_rs], pvw_shamir_shares, pvw_shamir_reconstruct_checked,
+ *     pvw_shamir_reconstruct_corrected, pvw_shamir_evaluate_corrected (the concurrent calls of these two:
+ *     tests/test_gpu_shamir_evaluate.py),
  *     pvw_decrypt_batch / _checked / _plain, pvw_decrypt_all / _checked / _plain, pvw_ct_sum, pvw_decrypt_sum_checked,
  *     pvw_decrypt_all_sum_checked, pvw_ct_lincomb, pvw_decrypt_lincomb_plain, pvw_decrypt_all_lincomb_plain (the concurrent
  *     calls of these three: tests/test_gpu_ct_lincomb.py), pvw_decode / _checked / _plain, pvw_wire_pack / _unpack, pvw_ntt_forward / _inverse,
@@ -722,7 +724,7 @@ PVW_API int32_t pvw_shamir_reconstruct_checked(pvw_ctx* ctx, uint64_t plain_modu
  *   (mask bits and col_err move with their columns).
  *   Every output is a function of the inputs alone, and the three forms agree bit for bit -- also for a p so small that a row
  *   with more than E wrong shares lies within E of ANOTHER polynomial: the row is decodable by the definition above, to that one.
- * The corrected share values are not returned: F_s is out[s] and t more of the shares that the mask leaves.
+ * The corrected share values, and F_s at any other point: pvw_shamir_evaluate_corrected* below.
  * PVW_ERR_INVALID_PARAMETERS before any device work, nothing written: as the checked calls; on the device also
  * E + 1 > 4096 (count - degree - 1 >= 8192). */
 #define PVW_SHAMIR_UNDECODABLE 0xFFFFFFFFu
@@ -741,12 +743,48 @@ PVW_API int32_t pvw_shamir_reconstruct_corrected_device(pvw_ctx* ctx, uint64_t p
                                                         size_t count, const uint64_t* d_shares, size_t num_secrets,
                                                         size_t secret_stride, size_t point_stride, uint64_t* d_out, uint32_t* d_nerr,
                                                         uint32_t* d_col_err, uint64_t* d_err_mask, void* stream);
-/* host buffers (synchronous); the staged shares and secrets are cleared before the call returns.  NOT YET covered by the
- * concurrency promise above (tests/test_gpu_concurrent_calls.py does not run it). */
+/* host buffers (synchronous); the staged shares and secrets are cleared before the call returns.  Covered by the concurrency
+ * promise above (tests/test_gpu_shamir_evaluate.py runs it next to pvw_shamir_evaluate_corrected). */
 PVW_API int32_t pvw_shamir_reconstruct_corrected(pvw_ctx* ctx, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
                                                  size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
                                                  size_t point_stride, uint64_t* out, uint32_t* nerr, uint32_t* col_err,
                                                  uint64_t* err_mask);
+/* Share repair: the corrected polynomials at any points.  The arguments of the corrected calls and their four
+ * outputs, and behind point_stride: targets [num_targets] (a HOST array in every form, like indices; global party indices, the
+ * point of target j is targets[j] + 1) and values [num_secrets][num_targets] (dense, row-major).  out may be NULL here as well;
+ * values may not.
+ *   Decodability, F_s, out, nerr, col_err and err_mask are those of the corrected calls, bit for bit: one decode yields every report.
+ *   decodable:   values[s][j] = F_s(targets[j] + 1) mod p.     undecodable: the row of values is all 0.
+ *   A target may be one of the indices: at a column the decode found right the value is the share read mod p, at a column it found
+ *   wrong the share that party should hold.  It may as well be any other index below p - 1 (a party that lost its state, or one
+ *   that joins under a new index); duplicates are allowed and the order of the targets only permutes the columns of values.
+ *   r = 0 is plain interpolation through all columns, r = 1 detects only, and the order of the share columns changes no value.
+ *   Every output is a function of the inputs alone and the three forms agree bit for bit, small-p rows included.
+ * PVW_ERR_INVALID_PARAMETERS before any device work, nothing written: what the corrected calls refuse; NULL targets or values;
+ * num_targets = 0; a target >= p - 1; on the device num_targets >= 2^31, refused before the targets are read (the _host form has
+ * no such bound: it reads every target it is given). */
+/* the contract in plain C++ on the host cores: the Berlekamp-Welch routine of pvw_shamir_reconstruct_corrected_host, whose
+ * quotient F_s is evaluated by Horner's rule at every target: what the kernels are tested against */
+PVW_API int32_t pvw_shamir_evaluate_corrected_host(uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                                   const uint64_t* shares, size_t num_secrets, size_t secret_stride,
+                                                   size_t point_stride, const uint64_t* targets, size_t num_targets, uint64_t* values,
+                                                   uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask);
+/* device pointers (indices and targets stay HOST pointers, read before the call returns), asynchronous on `stream`.  The scratch is
+ * the corrected call's block in the stream's workspace with the evaluation's regions behind it, sized by the call: under stream
+ * capture the call needs an earlier call with the same (degree, count), at least as many targets and at least as many secrets on
+ * that stream outside capture; without it: the error of pvw_shamir_reconstruct_corrected_device there, nothing enqueued.
+ * Everything in the scratch that depends on the shares is cleared behind the call's last launch. */
+PVW_API int32_t pvw_shamir_evaluate_corrected_device(pvw_ctx* ctx, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                     size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
+                                                     size_t point_stride, const uint64_t* targets, size_t num_targets,
+                                                     uint64_t* d_values, uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err,
+                                                     uint64_t* d_err_mask, void* stream);
+/* host buffers (synchronous); the staged shares, secrets and values are cleared before the call returns.  Covered by the
+ * concurrency promise above. */
+PVW_API int32_t pvw_shamir_evaluate_corrected(pvw_ctx* ctx, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
+                                              size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
+                                              size_t point_stride, const uint64_t* targets, size_t num_targets, uint64_t* values,
+                                              uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask);
 
 /* decode_scalar_pvw_rns alone, on the device: noisy [D][L][l] power basis (host) -> out_u64 [D] */
 PVW_API int32_t pvw_decode(pvw_ctx* ctx, const uint64_t* noisy, size_t count, uint64_t* out_u64);

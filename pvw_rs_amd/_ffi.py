@@ -152,6 +152,9 @@ _SIGNATURES = {
     "pvw_shamir_reconstruct_corrected_host": [C.c_uint64, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P, _P],
     "pvw_shamir_reconstruct_corrected_device": [_P, C.c_uint64, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P, _P, _P],
     "pvw_shamir_reconstruct_corrected": [_P, C.c_uint64, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P, _P],
+    "pvw_shamir_evaluate_corrected_host": [C.c_uint64, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P, _P, _P, _P, _P],
+    "pvw_shamir_evaluate_corrected_device": [_P, C.c_uint64, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P, _P, _P, _P, _P, _P],
+    "pvw_shamir_evaluate_corrected": [_P, C.c_uint64, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P, _P, _P, _P, _P],
     "pvw_decode": [_P, _P, C.c_size_t, _P],
     "pvw_decode_host": [_P, _P, C.c_size_t, _P],
     "pvw_decode_device": [_P, _P, C.c_size_t, _P, _P],

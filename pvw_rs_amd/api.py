@@ -962,6 +962,38 @@ def shamir_reconstruct_corrected(params: Optional[PvwParameters], indices: Seque
     return [int(v) for v in out], nerr, col_err, err_mask
 
 
+def shamir_evaluate_corrected(params: Optional[PvwParameters], indices: Sequence[int], shares, degree: int, plain_modulus: int,
+                              targets: Sequence[int], *, host: bool = False,
+                              layout: str = "secret_major") -> Tuple[np.ndarray, List[int], np.ndarray, np.ndarray, np.ndarray]:
+    """EXTENSION: share repair.  The decode of shamir_reconstruct_corrected, and values[s][j] = the value of secret
+    s's corrected polynomial at the point of party targets[j] (a global index: one of `indices` -- the share that party should
+    hold -- or any other index below plain_modulus - 1; duplicates allowed).  The row of an undecodable secret is 0.  shares and
+    layout as shamir_reconstruct_checked.  On the device (pvw_shamir_evaluate_corrected); host=True: the plain C++ restatement
+    (pvw_shamir_evaluate_corrected_host, no GPU; params may be None).  Returns (values, secrets, nerr, col_err, err_mask)."""
+    if layout not in ("secret_major", "party_major"):
+        raise ValueError(layout)
+    idx, tg = _words(indices), _words(targets)
+    count = len(idx)
+    sh = np.array([[int(v) & 0xFFFFFFFFFFFFFFFF for v in row] for row in shares], dtype=np.uint64)
+    sh = sh.reshape(len(shares), -1)
+    S, cols = sh.shape if layout == "secret_major" else sh.shape[::-1]
+    if cols != count:
+        raise PvwError(15, f"expected {count} shares per secret, got {cols}")
+    strides = (count, 1) if layout == "secret_major" else (1, S)
+    values = np.zeros((S, len(tg)), dtype=np.uint64)
+    out = np.zeros(S, dtype=np.uint64)
+    nerr, col_err = np.zeros(S, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
+    err_mask = np.zeros((S, (count + 63) // 64), dtype=np.uint64)
+    args = (int(plain_modulus), int(degree), _ptr(idx), count, _ptr(sh), S, strides[0], strides[1], _ptr(tg), len(tg), _ptr(values),
+            _ptr(out), _ptr(nerr), _ptr(col_err), _ptr(err_mask))
+    if host:
+        L = params._lib if params is not None else _ffi.lib()
+        _check(L.pvw_shamir_evaluate_corrected_host(*args), L)
+    else:
+        params._call("pvw_shamir_evaluate_corrected", *args)
+    return values, [int(v) for v in out], nerr, col_err, err_mask
+
+
 def encrypt_broadcast(scalar: int, global_pk: GlobalPublicKey, seed: Optional[bytes] = None, **kw) -> PvwCiphertext:
     """encryption.rs:292-296."""
     return encrypt([scalar] * global_pk.params.n, global_pk, seed, **kw)

@@ -2415,11 +2415,14 @@ int32_t pvw_shamir_reconstruct_checked(pvw_ctx* c, uint64_t plain_modulus, uint3
 // Berlekamp-Welch.  Find N of degree <= t + E and a monic W of degree E with N(x_c) = y_c W(x_c) in every column, by Gaussian
 // elimination on count equations in t + 2E + 1 unknowns; if F_s exists, every solution has N = F_s W.  So: no solution, W does
 // not divide N, or N / W disagrees with more than E columns: undecodable.  Cubic in count per secret.
-int32_t pvw_shamir_reconstruct_corrected_host(uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
-                                              const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
-                                              uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
-  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
-  PVW_TRY(reconstruct_checks(r, shares, out));
+// With targets: values[s][j] = F_s(targets[j] + 1) by Horner over the quotient's coefficients, 0 for an undecodable row
+// (pvw_shamir_evaluate_corrected_host); out may then be NULL.  The argument checks are the callers'.
+static void berlekamp_welch_host(const Reconstruct& r, const uint64_t* shares, uint64_t* out, uint32_t* nerr, uint32_t* col_err,
+                                 uint64_t* err_mask, const uint64_t* targets, size_t num_targets, uint64_t* values) {
+  const uint64_t plain_modulus = r.p;
+  const uint64_t* indices = r.indices;
+  const size_t count = r.count, num_secrets = r.S, secret_stride = r.secret_stride, point_stride = r.point_stride;
+  const uint32_t degree = r.degree;
   const Mod m = shamir_mod(plain_modulus);
   const size_t t = degree, E = (count - t - 1) / 2, nq = t + E + 1, nu = nq + E, words = (count + 63) / 64;
   std::vector<u64> x(count), y(count), A(count * (nu + 1)), sol(nu), W(E + 1), N(nq);
@@ -2483,9 +2486,16 @@ int32_t pvw_shamir_reconstruct_corrected_host(uint64_t plain_modulus, uint32_t d
         }
         ok = wrong.size() <= E;
         secret = F[0];
+        for (size_t j = 0; j < num_targets && ok; ++j) {
+          const u64 xs = targets[j] + 1;
+          u64 v = F[t];
+          for (size_t i = t; i-- > 0;) v = addmod(mulmod(v, xs, m), F[i], m.q);
+          values[s * num_targets + j] = v;
+        }
       }
     }
-    out[s] = ok ? secret : 0;
+    if (!ok && values) std::fill(values + s * num_targets, values + (s + 1) * num_targets, (u64)0);
+    if (out) out[s] = ok ? secret : 0;
     if (nerr) nerr[s] = ok ? (u32)wrong.size() : PVW_SHAMIR_UNDECODABLE;
     if (err_mask) std::fill(err_mask + s * words, err_mask + (s + 1) * words, (u64)0);
     if (ok)
@@ -2498,6 +2508,13 @@ int32_t pvw_shamir_reconstruct_corrected_host(uint64_t plain_modulus, uint32_t d
     volatile u64* vp = v->data();
     for (size_t i = 0; i < v->size(); ++i) vp[i] = 0;
   }
+}
+int32_t pvw_shamir_reconstruct_corrected_host(uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                              const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                              uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  PVW_TRY(reconstruct_checks(r, shares, out));
+  berlekamp_welch_host(r, shares, out, nerr, col_err, err_mask, nullptr, 0, nullptr);
   return PVW_OK;
 }
 
@@ -2661,6 +2678,252 @@ int32_t pvw_shamir_reconstruct_corrected(pvw_ctx* c, uint64_t plain_modulus, uin
       }
       PVW_TRY(correct_piece_enqueue(c, r, lay, ws, d_sh, cnt, count, 1, d_out, d_nerr, d_col, d_mask, w->stream));
       PVW_HIP(hipMemcpyAsync(out + s0, d_out, cnt * 8, hipMemcpyDeviceToHost, w->stream));
+      if (nerr) PVW_HIP(hipMemcpyAsync(nerr + s0, d_nerr, cnt * 4, hipMemcpyDeviceToHost, w->stream));
+      if (err_mask) PVW_HIP(hipMemcpyAsync(err_mask + s0 * words, d_mask, cnt * words * 8, hipMemcpyDeviceToHost, w->stream));
+      PVW_HIP(hipStreamSynchronize(w->stream));                // the next piece reuses the staging
+    }
+    if (col_err) PVW_HIP(hipMemcpyAsync(col_err, d_col, count * 4, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
+  volatile u64* vp = packed.data();                              // the host copy is as secret as the caller's shares
+  for (size_t i = 0; i < packed.size(); ++i) vp[i] = 0;
+  return rc;
+}
+
+// ------------------------------------------------------------------------ evaluation of the corrected polynomials
+// The decode of 8.11, then values[s][j] = F_s(targets[j] + 1) for every decodable row (0 for the others).  One decode yields
+// out, nerr, col_err, err_mask and values.
+// device: the bounds of the kernels' 32-bit counts as well; num_targets is bounded BEFORE the targets are read, so a refused count
+// costs no walk over the array (the host routine has no such bound and reads every target)
+static int32_t evaluate_checks(const Reconstruct& r, const void* shares, const uint64_t* targets, size_t num_targets, const void* values,
+                               bool device) {
+  PVW_TRY(reconstruct_checks(r, shares, values));            // values stands where the corrected call has out: out may be NULL here
+  if (!targets) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (num_targets == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no targets to evaluate at");
+  if (device) {
+    if (num_targets >= ((size_t)1 << 31)) return fail(PVW_ERR_INVALID_PARAMETERS, "num_targets must be below 2^31 on the device");
+    PVW_TRY(correct_device_checks(r));
+  }
+  for (size_t j = 0; j < num_targets; ++j)
+    if (targets[j] >= r.p - 1) return fail(PVW_ERR_INVALID_PARAMETERS, "target index out of range for plain_modulus");
+  return PVW_OK;
+}
+
+int32_t pvw_shamir_evaluate_corrected_host(uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                           const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                           const uint64_t* targets, size_t num_targets, uint64_t* values, uint64_t* out, uint32_t* nerr,
+                                           uint32_t* col_err, uint64_t* err_mask) {
+  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  PVW_TRY(evaluate_checks(r, shares, targets, num_targets, values, false));
+  berlekamp_welch_host(r, shares, out, nerr, col_err, err_mask, targets, num_targets, values);
+  return PVW_OK;
+}
+
+// Targets per group: the public matrices that depend on the targets (a column of C, of Xt and of Xd, scale and coin per target)
+// stay within 64 MiB -- at count = T = 4096, t = 2047 they would be 134 MB + 2 x 34 MB in one piece (tuning build:
+// PVW_EVALUATE_GROUP_BYTES, read per call, so that the tests walk several groups at small shapes).  Whole blocks of 64 targets
+// when there are that many.
+static size_t evaluate_group(const Reconstruct& r, size_t num_targets) {
+  const size_t E = (r.count - r.degree - 1) / 2;
+  const size_t per = (r.count + 2 * (E + 1) + 2) * 8 + 4;
+  const long env = PVW_ENV_INT("PVW_EVALUATE_GROUP_BYTES", 0);
+  const size_t budget = env > 0 ? (size_t)env : (size_t)64 << 20;
+  size_t tg = budget / per;
+  if (tg > 64) tg -= tg % 64;
+  if (tg == 0) tg = 1;
+  return tg < num_targets ? tg : num_targets;
+}
+// The per-secret scratch of the evaluation, in bytes: a row of M, of the syndromes and of the locators as in correct_piece, and a
+// row of y o M, of raw, of Lambda and of Lambda' at the group's targets, a stand-in for out, L and a stand-in for nerr
+static size_t evaluate_secret_bytes(const Reconstruct& r, size_t Tg) {
+  const size_t red = r.count - r.degree - 1;
+  return (2 * r.count + red + red / 2 + 1 + 3 * Tg + 2) * 8;
+}
+static size_t evaluate_piece_budget() {
+  const long env = PVW_ENV_INT("PVW_CORRECT_PIECE_BYTES", 0);
+  return env > 0 ? (size_t)env : (size_t)64 << 20;
+}
+// secrets per pass, by the rule of correct_piece
+static size_t evaluate_piece(const Reconstruct& r, size_t Tg) {
+  size_t cap = evaluate_piece_budget() / evaluate_secret_bytes(r, Tg);
+  if (cap == 0) cap = 1;
+  if (cap > 65535u * 4) cap = 65535u * 4;
+  return cap < r.S ? cap : r.S;
+}
+// The scratch of one call, in words from its base: the block of the corrected call first (CorrectLayout: M leads it), then
+//   YM [cap][count] | raw [cap][Tg] | outs [cap]   -- depend on the shares: the second region marked secret
+//   LamT [cap][Tg] | LamD [cap][Tg] | nerr [cap] (u32) | the group's public matrices (shamir_evaluate_public_words)
+struct EvaluateLayout {
+  CorrectLayout cl;
+  size_t Tg;
+  size_t ym, raw, outs, lamT, lamD, nerr, pub, total;   // word offsets
+  EvaluateLayout(const Reconstruct& rc, size_t cap, size_t Tg_) : cl(rc, cap), Tg(Tg_) {
+    ym = cl.total;
+    raw = ym + cap * rc.count;
+    outs = raw + cap * Tg;
+    lamT = outs + cap;
+    lamD = lamT + cap * Tg;
+    nerr = lamD + cap * Tg;
+    pub = nerr + (cap + 1) / 2;
+    total = pub + shamir_evaluate_public_words(rc.count, rc.degree, Tg);
+  }
+  size_t bytes() const { return total * 8; }
+  size_t secret_bytes() const { return (lamT - ym) * 8; }
+};
+// What the stream's block must hold for a call: never less than the layout takes, and no smaller for more secrets or more
+// targets at the same (degree, count) -- the rule a captured call is checked by.
+static size_t evaluate_need_bytes(const Reconstruct& r, size_t Tg) {
+  const size_t per = evaluate_secret_bytes(r, Tg), budget = evaluate_piece_budget();
+  size_t part = r.S > budget / per ? budget : r.S * per;
+  if (part < per) part = per;
+  return part + 16 + (shamir_correct_public_words(r.count, r.degree) + shamir_evaluate_public_words(r.count, r.degree, Tg)) * 8;
+}
+// One pass: ns <= lay.cl.cap secrets from d_shares are decoded (their out, nerr and mask rows; col_err is added to) and evaluated
+// at all targets, group by group, into d_values (rows num_targets words apart).  `resident` is the first target of the group whose
+// public matrices the block holds; with one group they are built once for all passes.
+static int32_t evaluate_pass_enqueue(pvw_ctx* c, const Reconstruct& r, const EvaluateLayout& lay, u64* ws, const u64* d_shares, size_t ns,
+                                     size_t secret_stride, size_t point_stride, const u64* targets, size_t num_targets, u64* d_values,
+                                     u64* d_out, u32* d_nerr, u32* d_col_err, u64* d_mask, size_t* resident, hipStream_t s) {
+  const Mod m = shamir_mod(r.p);
+  if (!d_out) d_out = ws + lay.outs;
+  if (!d_nerr) d_nerr = (u32*)(ws + lay.nerr);
+  PVW_TRY(correct_piece_enqueue(c, r, lay.cl, ws, d_shares, ns, secret_stride, point_stride, d_out, d_nerr, d_col_err, d_mask, s));
+  const u64 *x = ws + lay.cl.pub, *aux = x + r.count;
+  const u64 *M = ws, *Lam = ws + lay.cl.lam;
+  u64 *YM = ws + lay.ym, *raw = ws + lay.raw, *LamT = ws + lay.lamT, *LamD = ws + lay.lamD, *pub = ws + lay.pub;
+  const size_t nk = lay.cl.E + 1;
+  {
+    ProfScope ps(c, "shamir_evaluate", s);
+    PVW_HIP(launch_shamir_ym(d_shares, secret_stride, point_stride, M, YM, (u32)ns, (u32)r.count, m, s));
+  }
+  for (size_t j0 = 0; j0 < num_targets; j0 += lay.Tg) {
+    const size_t tg = num_targets - j0 < lay.Tg ? num_targets - j0 : lay.Tg;
+    if (*resident != j0) {
+      ProfScope ps(c, "shamir_evaluate_weights", s);
+      PVW_HIP(launch_shamir_points(targets + j0, tg, pub, s));
+      PVW_HIP(launch_shamir_evaluate_weights(x, aux, pub, r.count, r.degree, tg, m, s));
+      *resident = j0;
+    }
+    ProfScope ps(c, "shamir_evaluate", s);
+    const u64 *scale = pub + tg, *C = scale + tg, *Xt = C + r.count * tg, *Xd = Xt + nk * tg;
+    const u32* coin = (const u32*)(Xd + nk * tg);
+    ShamirMatmul a{};
+    a.A = YM, a.secret_stride = r.count, a.term_stride = 1;
+    a.W = C, a.out = raw;
+    a.ns = (u32)ns, a.terms = (u32)r.count, a.T = (u32)tg, a.m = m;
+    PVW_HIP(launch_shamir_matmul(a, s));
+    ShamirMatmul b{};
+    b.A = Lam, b.secret_stride = nk, b.term_stride = 1;
+    b.W = Xt, b.out = LamT;
+    b.ns = (u32)ns, b.terms = (u32)nk, b.T = (u32)tg, b.m = m;
+    PVW_HIP(launch_shamir_matmul(b, s));
+    b.W = Xd, b.out = LamD;
+    PVW_HIP(launch_shamir_matmul(b, s));
+    ShamirEvalFinish f{};
+    f.shares = d_shares, f.secret_stride = secret_stride, f.point_stride = point_stride;
+    f.M = M, f.nerr = d_nerr, f.raw = raw, f.LamT = LamT, f.LamD = LamD, f.scale = scale, f.coin = coin;
+    f.values = d_values + j0, f.value_stride = num_targets;
+    f.ns = (u32)ns, f.count = (u32)r.count, f.Tg = (u32)tg, f.m = m;
+    PVW_HIP(launch_shamir_evaluate_finish(f, s));
+  }
+  return PVW_OK;
+}
+
+// as correct_capture_check: the block is the corrected call's, with the evaluation's regions behind
+static int32_t evaluate_capture_check(pvw_ctx* c, hipStream_t s, size_t need) {
+  if (!stream_capturing(s)) return PVW_OK;
+  bool ready;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    auto it = c->async_ws.find((void*)s);
+    ready = it != c->async_ws.end() && it->second->correct_bytes >= need;
+  }
+  if (!ready)
+    return fail(PVW_ERR_INVALID_PARAMETERS, "corrected evaluation under stream capture: run a call with the same degree and count, at least "
+                                            "as many targets and at least as many secrets on this stream outside capture first (it sizes "
+                                            "the workspace)");
+  return PVW_OK;
+}
+
+int32_t pvw_shamir_evaluate_corrected_device(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                             const uint64_t* d_shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                             const uint64_t* targets, size_t num_targets, uint64_t* d_values, uint64_t* d_out,
+                                             uint32_t* d_nerr, uint32_t* d_col_err, uint64_t* d_err_mask, void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  PVW_TRY(evaluate_checks(r, d_shares, targets, num_targets, d_values, true));
+  const size_t Tg = evaluate_group(r, num_targets);
+  const EvaluateLayout lay(r, evaluate_piece(r, Tg), Tg);
+  const size_t need = evaluate_need_bytes(r, Tg);
+  if (need < lay.bytes()) return fail(PVW_ERR_INTERNAL, "evaluation scratch: layout beyond its bound");
+  const size_t words = (count + 63) / 64;
+  // the caller's stream is checked before the context initialises its device (pvw_shamir_reconstruct_checked_device)
+  if (stream) PVW_TRY(evaluate_capture_check(c, (hipStream_t)stream, need));
+  return device_call(c, stream, [&](hipStream_t s) { return evaluate_capture_check(c, s, need); },
+                     [&](Workspace* w, hipStream_t s) -> int32_t {
+                       if (w->correct_bytes < need) ws_public(w, w->correct, w->correct_bytes);   // the block is about to go
+                       PVW_TRY(ws_grow(&w->correct, &w->correct_bytes, need, s, true));
+                       ws_mark_secret(w, w->correct, lay.cl.m_bytes());
+                       ws_mark_secret(w, w->correct + lay.ym, lay.secret_bytes());
+                       PVW_TRY(correct_weights(c, r, lay.cl, w->correct, s));
+                       PVW_HIP(launch_shamir_zero_counts(d_col_err, count, s));
+                       size_t resident = SIZE_MAX;
+                       for (size_t s0 = 0; s0 < num_secrets; s0 += lay.cl.cap) {
+                         const size_t ns = num_secrets - s0 < lay.cl.cap ? num_secrets - s0 : lay.cl.cap;
+                         PVW_TRY(evaluate_pass_enqueue(c, r, lay, w->correct, d_shares + s0 * secret_stride, ns, secret_stride, point_stride,
+                                                       targets, num_targets, d_values + s0 * num_targets, d_out ? d_out + s0 : nullptr,
+                                                       d_nerr ? d_nerr + s0 : nullptr, d_col_err,
+                                                       d_err_mask ? d_err_mask + s0 * words : nullptr, &resident, s));
+                       }
+                       return PVW_OK;
+                     });
+}
+
+// host buffers: staged as pvw_shamir_reconstruct_corrected stages (each piece one pass over the kernels, packed to [piece][count]
+// or whole rows by a 2D copy); the values of a piece come down as one block.  The staged shares, secrets and values, M, y o M and
+// raw are cleared before the call returns.
+int32_t pvw_shamir_evaluate_corrected(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                      const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                      const uint64_t* targets, size_t num_targets, uint64_t* values, uint64_t* out, uint32_t* nerr,
+                                      uint32_t* col_err, uint64_t* err_mask) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  PVW_TRY(evaluate_checks(r, shares, targets, num_targets, values, true));
+  PVW_TRY(ensure_device(c));
+  const size_t words = (count + 63) / 64;
+  const size_t Tg = evaluate_group(r, num_targets);
+  size_t per = chunk_1gib((count + 1 + words + num_targets) * 8 + 4, num_secrets);
+  if (per > evaluate_piece(r, Tg)) per = evaluate_piece(r, Tg);
+  const EvaluateLayout lay(r, per, Tg);
+  Scratch sc;
+  const size_t r_sh = sc.add(per * count * 8), r_out = sc.add(per * 8), r_val = sc.add(per * num_targets * 8), r_ws = sc.add(lay.bytes()),
+               r_nerr = sc.add(per * 4), r_col = sc.add(count * 4), r_mask = sc.add(per * words * 8);
+  std::vector<u64> packed;                                       // a piece's shares when the caller's rows are not dense
+  const bool dense = point_stride == 1 && secret_stride >= count;   // whole rows go up as they lie (a 2D copy)
+  if (!dense) packed.resize(per * count);
+  const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    u64 *d_sh = sc.at(r_sh), *d_out = sc.at(r_out), *d_val = sc.at(r_val), *ws = sc.at(r_ws);
+    ws_mark_secret(w, d_sh, (size_t)((char*)ws - (char*)d_sh) + lay.cl.m_bytes());   // staged shares | secrets | values | M
+    ws_mark_secret(w, ws + lay.ym, lay.secret_bytes());                              // y o M | raw | the stand-in for out
+    u32 *d_nerr = sc.at<u32>(r_nerr), *d_col = col_err ? sc.at<u32>(r_col) : nullptr;
+    u64* d_mask = err_mask ? sc.at(r_mask) : nullptr;
+    PVW_TRY(correct_weights(c, r, lay.cl, ws, w->stream));
+    PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
+    size_t resident = SIZE_MAX;
+    for (size_t s0 = 0; s0 < num_secrets; s0 += per) {
+      const size_t cnt = (num_secrets - s0) < per ? (num_secrets - s0) : per;
+      if (dense) {
+        PVW_HIP(hipMemcpy2DAsync(d_sh, count * 8, shares + s0 * secret_stride, secret_stride * 8, count * 8, cnt, hipMemcpyHostToDevice, w->stream));
+      } else {
+        for (size_t s = 0; s < cnt; ++s)
+          for (size_t col = 0; col < count; ++col) packed[s * count + col] = shares[(s0 + s) * secret_stride + col * point_stride];
+        PVW_HIP(hipMemcpyAsync(d_sh, packed.data(), cnt * count * 8, hipMemcpyHostToDevice, w->stream));
+      }
+      PVW_TRY(evaluate_pass_enqueue(c, r, lay, ws, d_sh, cnt, count, 1, targets, num_targets, d_val, d_out, d_nerr, d_col, d_mask, &resident,
+                                    w->stream));
+      PVW_HIP(hipMemcpyAsync(values + s0 * num_targets, d_val, cnt * num_targets * 8, hipMemcpyDeviceToHost, w->stream));
+      if (out) PVW_HIP(hipMemcpyAsync(out + s0, d_out, cnt * 8, hipMemcpyDeviceToHost, w->stream));
       if (nerr) PVW_HIP(hipMemcpyAsync(nerr + s0, d_nerr, cnt * 4, hipMemcpyDeviceToHost, w->stream));
       if (err_mask) PVW_HIP(hipMemcpyAsync(err_mask + s0 * words, d_mask, cnt * words * 8, hipMemcpyDeviceToHost, w->stream));
       PVW_HIP(hipStreamSynchronize(w->stream));                // the next piece reuses the staging

@@ -307,6 +307,40 @@ hipError_t launch_shamir_matmul(const ShamirMatmul& b, hipStream_t s);
 hipError_t launch_shamir_bm(const u64* synd, u64* lam, u32* L, u32 ns, u32 r, const Mod& m, hipStream_t s);
 hipError_t launch_shamir_correct_finish(const ShamirFinish& f, u32 ns, hipStream_t s);
 
+// ---- Evaluation of the corrected polynomials (pvw_shamir.hip): values[s][j] = F_s(x*_j) for a group of Tg targets,
+// behind the decode above.  With G_s = F_s Lambda_s (degree <= count - 1, G_s(x_c) = y_c M[s][c]):
+//   raw[s][j] = sum_i YM[s][i] C[i][j],  YM = y o M,  C[i][j] = u_i / (x*_j - x_i) (0 where the points coincide)
+//   G_s(x*_j) = scale_j raw[s][j] off the points, G_s'(x_c) likewise at a point x*_j = x_c; scale_j = prod_{x_i != x*_j}(x*_j - x_i)
+// Public workspace words of a group, from the indices and targets alone:
+//   xt [Tg] | scale [Tg] | C [count][Tg] | Xt [E+1][Tg] (x*^k) | Xd [E+1][Tg] (k x*^(k-1)) | coin [Tg] (u32)
+#define PVW_SHAMIR_NO_COLUMN 0xFFFFFFFFu                 // coin[j] of a target that is no column's point
+inline size_t shamir_evaluate_public_words(size_t count, u32 t, size_t Tg) {
+  const size_t E = (count - t - 1) / 2;
+  return 2 * Tg + count * Tg + 2 * (E + 1) * Tg + (Tg + 1) / 2;
+}
+struct ShamirEvalFinish {
+  const u64* shares;     // as ShamirInterp
+  size_t secret_stride, point_stride;
+  const u64* M;          // [ns][count]
+  const u32* nerr;       // [ns]: PVW_SHAMIR_NO_LOCATOR for an undecodable row
+  const u64* raw;        // [ns][Tg]
+  const u64* LamT;       // [ns][Tg]: Lambda_s(x*_j)
+  const u64* LamD;       // [ns][Tg]: Lambda_s'(x*_j)
+  const u64* scale;      // [Tg]
+  const u32* coin;       // [Tg]: the column whose point target j is, or PVW_SHAMIR_NO_COLUMN
+  u64* values;           // element (s, j) at values[s * value_stride + j]
+  size_t value_stride;
+  u32 ns, count, Tg;
+  Mod m;
+};
+// ws: the group's public words; x, aux: the call's points and u_c (launch_shamir_correct_weights)
+hipError_t launch_shamir_evaluate_weights(const u64* x, const u64* aux, u64* ws, size_t count, u32 degree, size_t Tg, const Mod& m,
+                                          hipStream_t s);
+// YM[s][c] = y[s][c] M[s][c]
+hipError_t launch_shamir_ym(const u64* shares, size_t secret_stride, size_t point_stride, const u64* M, u64* YM, u32 ns, u32 count,
+                            const Mod& m, hipStream_t s);
+hipError_t launch_shamir_evaluate_finish(const ShamirEvalFinish& f, hipStream_t s);
+
 // p[0 .. words) = 0, as a kernel launch on s
 hipError_t launch_wipe_words(u64* p, size_t words, hipStream_t s);
 

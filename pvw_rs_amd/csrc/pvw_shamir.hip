@@ -643,4 +643,160 @@ hipError_t launch_shamir_correct_finish(const ShamirFinish& f, u32 ns, hipStream
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------ evaluation of the corrected polynomials
+// values[s][j] = F_s(x*_j) behind the decode above, for any targets x*_j = targets[j] + 1.  G_s = F_s Lambda_s has degree
+// <= t + E <= count - 1 and G_s(x_c) = y_c M[s][c] in every column (0 in the wrong ones), so G_s is interpolated through ALL
+// columns, in barycentric form, and divided by the locator:
+//   raw[s][j] = sum_i (y_i M[s][i]) C[i][j],  C[i][j] = u_i / (x*_j - x_i) (0 where x_i = x*_j)              (shamir_matmul_kernel)
+//   scale_j = prod_{i : x_i != x*_j} (x*_j - x_i)
+//   x*_j no column's point:        F_s(x*_j) = scale_j raw[s][j] / Lambda_s(x*_j)   (Lambda_s splits over the points: != 0)
+//   x*_j = x_c, M[s][c] != 0:      F_s(x_c) = y_c
+//   x*_j = x_c, M[s][c] == 0:      F_s(x_c) = G_s'(x_c) / Lambda_s'(x_c) = scale_j raw[s][j] / Lambda_s'(x_c): G_s / (x - x_c) through
+//                                  the other count - 1 columns has the weights -u_i / u_c there, and scale_j = 1 / u_c
+// Lambda_s and Lambda_s' at the targets are two more products, Lambda x Xt and Lambda x Xd with Xt[k][j] = x*_j^k and
+// Xd[k][j] = k x*_j^(k-1).
+
+// the product of the lanes' values (each below p), the same in every lane
+__device__ __forceinline__ u64 wave_mulmod(u64 v, const Mod& m) {
+#pragma unroll
+  for (int off = 32; off; off >>= 1) v = mulmod(v, (u64)__shfl_xor((unsigned long long)v, off), m);
+  return v;
+}
+
+// one wave per target j: scale_j, and the column whose point x*_j is (the points are distinct: at most one lane finds one, and
+// PVW_SHAMIR_NO_COLUMN is the largest u32, so the minimum over the wave is that column or none).  Both meet by shuffles.
+__global__ __launch_bounds__(256) void shamir_target_scale_kernel(const u64* x, const u64* xt, u64* scale, u32* coin, u32 count, u32 Tg,
+                                                                  Mod m) {
+  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const u32 j = blockIdx.x * SH_WAVES + wave;
+  if (j >= Tg) return;                                           // wave-uniform
+  const u64 xs = xt[j];
+  u64 prod = 1;
+  u32 hit = PVW_SHAMIR_NO_COLUMN;
+  for (u32 i = lane; i < count; i += 64) {
+    const u64 d = submod(xs, x[i], m.q);
+    if (d == 0) hit = i;
+    else prod = mulmod(prod, d, m);
+  }
+  prod = wave_mulmod(prod, m);
+#pragma unroll
+  for (int off = 32; off; off >>= 1) {
+    const u32 o = (u32)__shfl_xor((int)hit, off);
+    hit = o < hit ? o : hit;
+  }
+  if (lane == 0) {
+    scale[j] = prod;
+    coin[j] = hit;
+  }
+}
+
+#define SH_CB 8      // columns per thread of the Cauchy matrix: one inversion for their SH_CB differences
+// grid: x = blocks of 256 targets, y = blocks of SH_CB columns from i_base on; a thread owns one target and SH_CB columns, lanes
+// store along a row of C.  The differences are inverted together (prefix products, one Fermat inversion, and back); a zero
+// difference -- the target is that column's point -- enters the products as 1 and its entry is 0.
+__global__ __launch_bounds__(256) void shamir_cauchy_kernel(const u64* x, const u64* aux, const u64* xt, u64* C, u32 i_base, u32 count,
+                                                            u32 Tg, Mod m) {
+  const u32 j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= Tg) return;
+  const u32 i0 = i_base + blockIdx.y * SH_CB;
+  const u64 xs = xt[j];
+  u64 d[SH_CB], pre[SH_CB];
+  u64 run = 1;
+#pragma unroll
+  for (int b = 0; b < SH_CB; ++b) {
+    const u32 i = i0 + b;
+    d[b] = i < count ? submod(xs, x[i], m.q) : 0;
+    pre[b] = run;
+    run = mulmod(run, d[b] ? d[b] : 1, m);
+  }
+  u64 inv = invmod_dev(run, m);
+#pragma unroll
+  for (int b = SH_CB - 1; b >= 0; --b) {
+    const u32 i = i0 + b;
+    const u64 di = mulmod(inv, pre[b], m);           // d[b]^-1
+    inv = mulmod(inv, d[b] ? d[b] : 1, m);
+    if (i < count) C[(size_t)i * Tg + j] = d[b] ? mulmod(aux[i], di, m) : 0;
+  }
+}
+
+// Xd[k][j] = k x_j^(k-1) (row 0 is 0), in the frame of shamir_powers_kernel
+__global__ __launch_bounds__(256) void shamir_dpowers_kernel(const u64* x, u64* X, u32 count, u32 nk, Mod m) {
+  const u32 c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= count) return;
+  const u32 k0 = blockIdx.y * 64, k1 = k0 + 64 < nk ? k0 + 64 : nk;
+  const u64 xc = x[c];
+  u64 v = k0 > 1 ? powmod_dev(xc, k0 - 1, m) : 1;    // x_c^(k-1) of the first k >= 1
+  for (u32 k = k0; k < k1; ++k) {
+    if (k == 0) { X[c] = 0; continue; }
+    X[(size_t)k * count + c] = mulmod(reduce_word((u64)k, m), v, m);
+    v = mulmod(v, xc, m);
+  }
+}
+
+// YM[s][c] = y[s][c] M[s][c]: one thread per element, the column fastest
+__global__ __launch_bounds__(256) void shamir_ym_kernel(const u64* shares, size_t secret_stride, size_t point_stride, const u64* M, u64* YM,
+                                                        u32 ns, u32 count, Mod m) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)ns * count) return;
+  const size_t s = e / count, c = e % count;
+  const u64 mv = M[e];
+  YM[e] = mv ? mulmod(reduce_word(shares[s * secret_stride + c * point_stride], m), mv, m) : 0;
+}
+
+// one thread per (s, j), the target fastest: picks the case, divides (one Fermat inversion) and stores
+__global__ __launch_bounds__(256) void shamir_evaluate_finish_kernel(ShamirEvalFinish f) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)f.ns * f.Tg) return;
+  const size_t s = e / f.Tg, j = e % f.Tg;
+  const Mod m = f.m;
+  u64 v = 0;
+  if (f.nerr[s] != PVW_SHAMIR_NO_LOCATOR) {
+    const u32 c = f.coin[j];
+    if (c != PVW_SHAMIR_NO_COLUMN && f.M[s * f.count + c] != 0) {
+      v = reduce_word(f.shares[s * f.secret_stride + (size_t)c * f.point_stride], m);
+    } else {
+      const u64 den = c != PVW_SHAMIR_NO_COLUMN ? f.LamD[e] : f.LamT[e];
+      v = mulmod(mulmod(f.raw[e], f.scale[j], m), invmod_dev(den, m), m);
+    }
+  }
+  f.values[s * f.value_stride + j] = v;
+}
+
+hipError_t launch_shamir_evaluate_weights(const u64* x, const u64* aux, u64* ws, size_t count, u32 t, size_t Tg, const Mod& m,
+                                          hipStream_t s) {
+  const u32 n = (u32)count, tg = (u32)Tg, nk = (n - t - 1) / 2 + 1;
+  const u64* xt = ws;
+  u64 *scale = ws + Tg, *C = scale + Tg, *Xt = C + count * Tg, *Xd = Xt + (size_t)nk * Tg;
+  u32* coin = (u32*)(Xd + (size_t)nk * Tg);
+  shamir_target_scale_kernel<<<dim3((tg + SH_WAVES - 1) / SH_WAVES), dim3(256), 0, s>>>(x, xt, scale, coin, n, tg, m);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const u32 per = 65535u * SH_CB;                  // the grid's y dimension
+  for (u32 i0 = 0; i0 < n; i0 += per) {
+    const u32 rows = n - i0 < per ? n - i0 : per;
+    shamir_cauchy_kernel<<<dim3((tg + 255) / 256, (rows + SH_CB - 1) / SH_CB), dim3(256), 0, s>>>(x, aux, xt, C, i0, n, tg, m);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  const dim3 grid((tg + 255) / 256, (nk + 63) / 64);
+  shamir_powers_kernel<<<grid, dim3(256), 0, s>>>(xt, Xt, tg, nk, m);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  shamir_dpowers_kernel<<<grid, dim3(256), 0, s>>>(xt, Xd, tg, nk, m);
+  return hipGetLastError();
+}
+
+hipError_t launch_shamir_ym(const u64* shares, size_t secret_stride, size_t point_stride, const u64* M, u64* YM, u32 ns, u32 count,
+                            const Mod& m, hipStream_t s) {
+  if (ns == 0) return hipSuccess;
+  const size_t blocks = ((size_t)ns * count + 255) / 256;
+  shamir_ym_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(shares, secret_stride, point_stride, M, YM, ns, count, m);
+  return hipGetLastError();
+}
+
+hipError_t launch_shamir_evaluate_finish(const ShamirEvalFinish& f, hipStream_t s) {
+  if (f.ns == 0 || f.Tg == 0) return hipSuccess;
+  const size_t blocks = ((size_t)f.ns * f.Tg + 255) / 256;
+  shamir_evaluate_finish_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(f);
+  return hipGetLastError();
+}
+
 }  // namespace pvw

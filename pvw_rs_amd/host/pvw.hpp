@@ -716,6 +716,31 @@ inline CorrectedSecrets shamir_reconstruct_corrected(const std::shared_ptr<PvwPa
   return r;
 }
 
+// ---- share repair ----
+struct EvaluatedShares {
+  std::vector<uint64_t> values;     // [num_secrets][targets.size()]: the corrected polynomial of each row at each target's point; a 0 row: undecodable
+  CorrectedSecrets decode;          // what shamir_reconstruct_corrected reports for the same input
+};
+// The decode of shamir_reconstruct_corrected and its polynomials at the points of the parties `targets` (global indices: among
+// `indices` or not, duplicates allowed).  On the device (pvw_shamir_evaluate_corrected); host = true: the plain C++ restatement.
+inline EvaluatedShares shamir_evaluate_corrected(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& indices,
+                                                 const std::vector<uint64_t>& shares, uint32_t degree, uint64_t plain_modulus,
+                                                 const std::vector<uint64_t>& targets, bool host = false, bool party_major = false) {
+  const size_t count = indices.size(), T = targets.size();
+  if (count == 0 || shares.empty() || shares.size() % count) throw PvwError(15, "shares must hold one value per index and secret");
+  const size_t S = shares.size() / count, words = (count + 63) / 64;
+  EvaluatedShares r{std::vector<uint64_t>(S * T),
+                    CorrectedSecrets{std::vector<uint64_t>(S), std::vector<uint32_t>(S), std::vector<uint32_t>(count),
+                                     std::vector<uint64_t>(S * words), words}};
+  CorrectedSecrets& d = r.decode;
+  const size_t ss = party_major ? 1 : count, ps = party_major ? S : 1;
+  check(host ? pvw_shamir_evaluate_corrected_host(plain_modulus, degree, indices.data(), count, shares.data(), S, ss, ps, targets.data(), T,
+                                                  r.values.data(), d.secrets.data(), d.nerr.data(), d.col_err.data(), d.err_mask.data())
+             : pvw_shamir_evaluate_corrected(p->ctx, plain_modulus, degree, indices.data(), count, shares.data(), S, ss, ps, targets.data(),
+                                             T, r.values.data(), d.secrets.data(), d.nerr.data(), d.col_err.data(), d.err_mask.data()));
+  return r;
+}
+
 // the sum of the valid dealers' ciphertexts (pvw_ct_sum): same parameters and representation, no key needed
 inline PvwCiphertext aggregate_ciphertexts(const std::vector<PvwCiphertext>& cts, const std::vector<bool>& valid = {}) {
   const SumInputs in = sum_inputs(cts, valid);

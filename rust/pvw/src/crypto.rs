@@ -543,6 +543,27 @@ pub fn shamir_reconstruct_corrected(params: &Arc<PvwParameters>, indices: &[u64]
     Ok(r)
 }
 
+/// EXTENSION: share repair on the device (`pvw_shamir_evaluate_corrected`).  The decode of
+/// `shamir_reconstruct_corrected` and, as `[num_secrets][targets.len()]`, every row's corrected polynomial at the points of the
+/// parties `targets` (global indices, among `indices` or not; duplicates allowed).  The row of an undecodable secret is 0.
+pub fn shamir_evaluate_corrected(params: &Arc<PvwParameters>, indices: &[u64], shares: &[u64], degree: u32, plain_modulus: u64,
+                                 targets: &[u64], party_major: bool) -> Result<(Vec<u64>, CorrectedSecrets)> {
+    if indices.is_empty() || shares.is_empty() || shares.len() % indices.len() != 0 {
+        return Err(PvwError::InvalidParameters("shares must hold one value per index and secret".into()));
+    }
+    let (count, num) = (indices.len(), shares.len() / indices.len());
+    let words = (count + 63) / 64;
+    let (ss, ps) = if party_major { (1, num) } else { (count, 1) };
+    let mut values = vec![0u64; num * targets.len()];
+    let mut r = CorrectedSecrets { secrets: vec![0u64; num], nerr: vec![0u32; num], col_err: vec![0u32; count], err_mask: vec![0u64; num * words], words };
+    check(unsafe {
+        sys::pvw_shamir_evaluate_corrected(params.hip.raw(), plain_modulus, degree, indices.as_ptr(), count, shares.as_ptr(), num, ss, ps,
+                                           targets.as_ptr(), targets.len(), values.as_mut_ptr(), r.secrets.as_mut_ptr(), r.nerr.as_mut_ptr(),
+                                           r.col_err.as_mut_ptr(), r.err_mask.as_mut_ptr())
+    })?;
+    Ok((values, r))
+}
+
 /// EXTENSION: the sum of the valid dealers' ciphertexts (`pvw_ct_sum`) -- a ciphertext of the sum of their
 /// shares under the same keys, folded without any key.  What examples/pvw_valid_dec.rs:150-209 reaches by decrypting every
 /// dealer's share and adding the results; the noise of the sum is the sum of the dealers' noises (`pvw_ctx_sum_capacity`).
