@@ -899,14 +899,9 @@ def shamir_reconstruct(indices: Sequence[int], shares, plain_modulus: int):
     return int(out[0]) if single else [int(v) for v in out]
 
 
-def shamir_reconstruct_checked(params: Optional[PvwParameters], indices: Sequence[int], shares, degree: int, plain_modulus: int, *,
-                               host: bool = False, layout: str = "secret_major") -> Tuple[List[int], np.ndarray, np.ndarray]:
-    """EXTENSION (DESIGN 8.10): the secrets and a report on the shares they came from.  The first degree + 1 of `indices` are the
-    basis: secrets[s] is the value at 0 of the polynomial through secret s's basis shares; bad[s] counts the other columns whose
-    share is off that polynomial, col_bad[c] the secrets that deviate in column c.  shares: layout "secret_major" is
-    [num_secrets][len(indices)] (the rows of shamir_shares), "party_major" is [len(indices)][num_secrets] (what
-    decrypt_all_party_shares* returns, every dealer a secret).  On the device (pvw_shamir_reconstruct_checked); host=True: the
-    plain C++ restatement (pvw_shamir_reconstruct_checked_host, no GPU; params may be None).  Returns (secrets, bad, col_bad)."""
+def _share_matrix(indices: Sequence[int], shares, layout: str):
+    """(idx, sh, S, count, strides) of the checked, corrected and evaluate calls: the indices and the share matrix as uint64
+    words, and the (secret, point) strides of `layout` in words"""
     if layout not in ("secret_major", "party_major"):
         raise ValueError(layout)
     idx = _words(indices)
@@ -917,14 +912,31 @@ def shamir_reconstruct_checked(params: Optional[PvwParameters], indices: Sequenc
     if cols != count:
         raise PvwError(15, f"expected {count} shares per secret, got {cols}")
     strides = (count, 1) if layout == "secret_major" else (1, S)
+    return idx, sh, S, count, strides
+
+
+def _reconstruct_call(params: Optional[PvwParameters], name: str, host: bool, args) -> None:
+    """pvw_<name> on the context of params, or with host=True pvw_<name>_host (no GPU; params may be None)"""
+    if host:
+        L = params._lib if params is not None else _ffi.lib()
+        _check(getattr(L, f"pvw_{name}_host")(*args), L)
+    else:
+        params._call(f"pvw_{name}", *args)
+
+
+def shamir_reconstruct_checked(params: Optional[PvwParameters], indices: Sequence[int], shares, degree: int, plain_modulus: int, *,
+                               host: bool = False, layout: str = "secret_major") -> Tuple[List[int], np.ndarray, np.ndarray]:
+    """EXTENSION (DESIGN 8.10): the secrets and a report on the shares they came from.  The first degree + 1 of `indices` are the
+    basis: secrets[s] is the value at 0 of the polynomial through secret s's basis shares; bad[s] counts the other columns whose
+    share is off that polynomial, col_bad[c] the secrets that deviate in column c.  shares: layout "secret_major" is
+    [num_secrets][len(indices)] (the rows of shamir_shares), "party_major" is [len(indices)][num_secrets] (what
+    decrypt_all_party_shares* returns, every dealer a secret).  On the device (pvw_shamir_reconstruct_checked); host=True: the
+    plain C++ restatement (pvw_shamir_reconstruct_checked_host, no GPU; params may be None).  Returns (secrets, bad, col_bad)."""
+    idx, sh, S, count, strides = _share_matrix(indices, shares, layout)
     out = np.zeros(S, dtype=np.uint64)
     bad, col_bad = np.zeros(S, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
     args = (int(plain_modulus), int(degree), _ptr(idx), count, _ptr(sh), S, strides[0], strides[1], _ptr(out), _ptr(bad), _ptr(col_bad))
-    if host:
-        L = params._lib if params is not None else _ffi.lib()
-        _check(L.pvw_shamir_reconstruct_checked_host(*args), L)
-    else:
-        params._call("pvw_shamir_reconstruct_checked", *args)
+    _reconstruct_call(params, "shamir_reconstruct_checked", host, args)
     return [int(v) for v in out], bad, col_bad
 
 
@@ -939,26 +951,13 @@ def shamir_reconstruct_corrected(params: Optional[PvwParameters], indices: Seque
     off in column c.  A row with no such polynomial: secrets[s] = 0, nerr[s] = SHAMIR_UNDECODABLE, an empty mask row.  shares and
     layout as shamir_reconstruct_checked.  On the device (pvw_shamir_reconstruct_corrected); host=True: the plain C++ restatement
     (pvw_shamir_reconstruct_corrected_host, no GPU; params may be None).  Returns (secrets, nerr, col_err, err_mask)."""
-    if layout not in ("secret_major", "party_major"):
-        raise ValueError(layout)
-    idx = _words(indices)
-    count = len(idx)
-    sh = np.array([[int(v) & 0xFFFFFFFFFFFFFFFF for v in row] for row in shares], dtype=np.uint64)
-    sh = sh.reshape(len(shares), -1)
-    S, cols = sh.shape if layout == "secret_major" else sh.shape[::-1]
-    if cols != count:
-        raise PvwError(15, f"expected {count} shares per secret, got {cols}")
-    strides = (count, 1) if layout == "secret_major" else (1, S)
+    idx, sh, S, count, strides = _share_matrix(indices, shares, layout)
     out = np.zeros(S, dtype=np.uint64)
     nerr, col_err = np.zeros(S, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
     err_mask = np.zeros((S, (count + 63) // 64), dtype=np.uint64)
     args = (int(plain_modulus), int(degree), _ptr(idx), count, _ptr(sh), S, strides[0], strides[1], _ptr(out), _ptr(nerr), _ptr(col_err),
             _ptr(err_mask))
-    if host:
-        L = params._lib if params is not None else _ffi.lib()
-        _check(L.pvw_shamir_reconstruct_corrected_host(*args), L)
-    else:
-        params._call("pvw_shamir_reconstruct_corrected", *args)
+    _reconstruct_call(params, "shamir_reconstruct_corrected", host, args)
     return [int(v) for v in out], nerr, col_err, err_mask
 
 
@@ -970,27 +969,15 @@ def shamir_evaluate_corrected(params: Optional[PvwParameters], indices: Sequence
     hold -- or any other index below plain_modulus - 1; duplicates allowed).  The row of an undecodable secret is 0.  shares and
     layout as shamir_reconstruct_checked.  On the device (pvw_shamir_evaluate_corrected); host=True: the plain C++ restatement
     (pvw_shamir_evaluate_corrected_host, no GPU; params may be None).  Returns (values, secrets, nerr, col_err, err_mask)."""
-    if layout not in ("secret_major", "party_major"):
-        raise ValueError(layout)
-    idx, tg = _words(indices), _words(targets)
-    count = len(idx)
-    sh = np.array([[int(v) & 0xFFFFFFFFFFFFFFFF for v in row] for row in shares], dtype=np.uint64)
-    sh = sh.reshape(len(shares), -1)
-    S, cols = sh.shape if layout == "secret_major" else sh.shape[::-1]
-    if cols != count:
-        raise PvwError(15, f"expected {count} shares per secret, got {cols}")
-    strides = (count, 1) if layout == "secret_major" else (1, S)
+    idx, sh, S, count, strides = _share_matrix(indices, shares, layout)
+    tg = _words(targets)
     values = np.zeros((S, len(tg)), dtype=np.uint64)
     out = np.zeros(S, dtype=np.uint64)
     nerr, col_err = np.zeros(S, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
     err_mask = np.zeros((S, (count + 63) // 64), dtype=np.uint64)
     args = (int(plain_modulus), int(degree), _ptr(idx), count, _ptr(sh), S, strides[0], strides[1], _ptr(tg), len(tg), _ptr(values),
             _ptr(out), _ptr(nerr), _ptr(col_err), _ptr(err_mask))
-    if host:
-        L = params._lib if params is not None else _ffi.lib()
-        _check(L.pvw_shamir_evaluate_corrected_host(*args), L)
-    else:
-        params._call("pvw_shamir_evaluate_corrected", *args)
+    _reconstruct_call(params, "shamir_evaluate_corrected", host, args)
     return values, [int(v) for v in out], nerr, col_err, err_mask
 
 

@@ -2159,20 +2159,30 @@ int32_t pvw_shamir_shares_host(const pvw_ctx* c, const uint64_t* secrets, size_t
   return PVW_OK;
 }
 
-// Lagrange weights at 0 for the points x_i = indices[i] + 1 (residues in [0, p)), behind the argument rules both callers share
-static int32_t shamir_weights_at_zero(uint64_t plain_modulus, const uint64_t* indices, size_t count, Mod* mod, std::vector<u64>* wout) {
-  if (count == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no shares to reconstruct from");
-  if (plain_modulus < 2) return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must be prime (Shamir shares live in a field)");
-  PVW_TRY(shamir_modulus_check(plain_modulus));
-  const Mod m = shamir_mod(plain_modulus);
-  for (size_t i = 0; i < count; ++i)
-    if (indices[i] >= m.q - 1) return fail(PVW_ERR_INVALID_PARAMETERS, "party index out of range for plain_modulus");
-  {
+// The rules every reconstruction's indices and modulus obey: distinct indices, points x_i = indices[i] + 1 below p, p a prime
+// below 2^62.  The plain reconstruction (modulus_first) has always reported the modulus, then the range, then a duplicate; the
+// checked and corrected calls a duplicate, then the range, then the modulus.
+static int32_t shamir_index_checks(u64 p, const u64* indices, size_t count, bool modulus_first) {
+  auto distinct = [&]() -> int32_t {
     std::vector<u64> sorted(indices, indices + count);
     std::sort(sorted.begin(), sorted.end());
     for (size_t i = 1; i < count; ++i)
       if (sorted[i] == sorted[i - 1]) return fail(PVW_ERR_INVALID_PARAMETERS, "duplicate party index");
-  }
+    return PVW_OK;
+  };
+  if (!modulus_first) PVW_TRY(distinct());
+  if (p < 2) return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must be prime (Shamir shares live in a field)");
+  if (modulus_first) PVW_TRY(shamir_modulus_check(p));
+  for (size_t i = 0; i < count; ++i)
+    if (indices[i] >= p - 1) return fail(PVW_ERR_INVALID_PARAMETERS, "party index out of range for plain_modulus");
+  return modulus_first ? distinct() : shamir_modulus_check(p);
+}
+
+// Lagrange weights at 0 for the points x_i = indices[i] + 1 (residues in [0, p)), behind the argument rules both callers share
+static int32_t shamir_weights_at_zero(uint64_t plain_modulus, const uint64_t* indices, size_t count, Mod* mod, std::vector<u64>* wout) {
+  if (count == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no shares to reconstruct from");
+  PVW_TRY(shamir_index_checks(plain_modulus, indices, count, true));
+  const Mod m = shamir_mod(plain_modulus);
   // w_i = prod_{j != i} x_j / (x_j - x_i)
   std::vector<u64> w(count);
   for (size_t i = 0; i < count; ++i) {
@@ -2233,16 +2243,7 @@ static int32_t reconstruct_checks(const Reconstruct& r, const void* shares, cons
     snprintf(buf, sizeof buf, "degree %u needs at least %zu shares, got %zu", r.degree, (size_t)r.degree + 1, r.count);
     return fail(PVW_ERR_INVALID_PARAMETERS, buf);
   }
-  {
-    std::vector<u64> sorted(r.indices, r.indices + r.count);
-    std::sort(sorted.begin(), sorted.end());
-    for (size_t i = 1; i < r.count; ++i)
-      if (sorted[i] == sorted[i - 1]) return fail(PVW_ERR_INVALID_PARAMETERS, "duplicate party index");
-  }
-  if (r.p < 2) return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must be prime (Shamir shares live in a field)");
-  for (size_t i = 0; i < r.count; ++i)
-    if (r.indices[i] >= r.p - 1) return fail(PVW_ERR_INVALID_PARAMETERS, "party index out of range for plain_modulus");
-  PVW_TRY(shamir_modulus_check(r.p));
+  PVW_TRY(shamir_index_checks(r.p, r.indices, r.count, false));
   if (r.secret_stride == 0 || r.point_stride == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "a stride of 0");
   return PVW_OK;
 }
@@ -2323,21 +2324,15 @@ static int32_t reconstruct_interp(pvw_ctx* c, const Reconstruct& r, const u64* w
   return PVW_OK;
 }
 
-// Under stream capture the call may not allocate: the stream's workspace must hold a weight buffer of this call's size, which an
-// earlier call with the same (degree, count) outside capture leaves (checked before the workspace is looked up, like
-// multi_capture_check, and refused with the same code)
-static int32_t reconstruct_capture_check(pvw_ctx* c, hipStream_t s, size_t need) {
+// Under stream capture a call may not allocate: the block of the stream's workspace that the call grows (`bytes`: interp_bytes
+// or correct_bytes) must hold `need` already, which an earlier call of the same size outside capture leaves (checked before the
+// workspace is looked up, like multi_capture_check, and refused with the same code and the caller's message)
+static int32_t grown_capture_check(pvw_ctx* c, hipStream_t s, size_t Workspace::*bytes, size_t need, const char* msg) {
   if (!stream_capturing(s)) return PVW_OK;
-  bool ready;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    auto it = c->async_ws.find((void*)s);
-    ready = it != c->async_ws.end() && it->second->interp_bytes >= need;
-  }
-  if (!ready)
-    return fail(PVW_ERR_INVALID_PARAMETERS, "checked reconstruction under stream capture: run a call with the same degree and count on "
-                                            "this stream outside capture first (it sizes the workspace)");
-  return PVW_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  auto it = c->async_ws.find((void*)s);
+  if (it != c->async_ws.end() && it->second->*bytes >= need) return PVW_OK;
+  return fail(PVW_ERR_INVALID_PARAMETERS, msg);
 }
 
 int32_t pvw_shamir_reconstruct_checked_device(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
@@ -2350,16 +2345,55 @@ int32_t pvw_shamir_reconstruct_checked_device(pvw_ctx* c, uint64_t plain_modulus
   // A context that has not touched its device yet initialises it inside device_call (allocations, a wait): on a capturing
   // stream that would invalidate the caller's capture, and nothing can have sized the workspace.  So the caller's stream is
   // checked before anything else; the context's own stream (stream == NULL) exists only once the device is initialised.
-  if (stream) PVW_TRY(reconstruct_capture_check(c, (hipStream_t)stream, r.ws_bytes()));
-  return device_call(c, stream, [&](hipStream_t s) { return reconstruct_capture_check(c, s, r.ws_bytes()); },
-                     [&](Workspace* w, hipStream_t s) -> int32_t {
-                       PVW_TRY(ws_grow(&w->interp, &w->interp_bytes, r.ws_bytes(), s, false));   // public: nothing to clear
-                       PVW_TRY(reconstruct_weights(c, r, w->interp, s));
-                       PVW_HIP(launch_shamir_zero_counts(d_col_bad, count, s));
-                       return reconstruct_interp(c, r, w->interp, d_shares, num_secrets, secret_stride, point_stride, d_out, d_bad,
-                                                 d_col_bad, s);
-                     });
+  auto sized = [&](hipStream_t s) {
+    return grown_capture_check(c, s, &Workspace::interp_bytes, r.ws_bytes(),
+                               "checked reconstruction under stream capture: run a call with the same degree and count on this stream "
+                               "outside capture first (it sizes the workspace)");
+  };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
+    PVW_TRY(ws_grow(&w->interp, &w->interp_bytes, r.ws_bytes(), s, false));   // public: nothing to clear
+    PVW_TRY(reconstruct_weights(c, r, w->interp, s));
+    PVW_HIP(launch_shamir_zero_counts(d_col_bad, count, s));
+    return reconstruct_interp(c, r, w->interp, d_shares, num_secrets, secret_stride, point_stride, d_out, d_bad, d_col_bad, s);
+  });
 }
+
+// The staging of the host-buffer reconstruction calls (8.10, 8.11, 8.13): the secrets go up in pieces of `per`, each as a dense
+// [cnt][count] block at d_sh -- whole rows by a 2D copy where the caller's rows lie that way, else repacked on the host --, and
+// the stream is drained behind a piece before the next one reuses the staging.  piece(s0, cnt) enqueues the kernels of secrets
+// [s0, s0 + cnt) and their downloads.  The host copy is as secret as the caller's shares: it is wiped when the call ends.
+struct ShareStaging {
+  const Reconstruct& r;
+  const u64* shares;
+  size_t per;
+  bool dense;                                                    // whole rows go up as they lie
+  std::vector<u64> packed;                                       // a piece's shares when they do not
+  ShareStaging(const Reconstruct& r_, const u64* shares_, size_t per_)
+      : r(r_), shares(shares_), per(per_), dense(r_.point_stride == 1 && r_.secret_stride >= r_.count) {
+    if (!dense) packed.resize(per * r.count);
+  }
+  ~ShareStaging() {
+    volatile u64* vp = packed.data();
+    for (size_t i = 0; i < packed.size(); ++i) vp[i] = 0;
+  }
+  int32_t run(u64* d_sh, hipStream_t stream, const std::function<int32_t(size_t s0, size_t cnt)>& piece) {
+    const size_t count = r.count;
+    for (size_t s0 = 0; s0 < r.S; s0 += per) {
+      const size_t cnt = (r.S - s0) < per ? (r.S - s0) : per;
+      if (dense) {
+        PVW_HIP(hipMemcpy2DAsync(d_sh, count * 8, shares + s0 * r.secret_stride, r.secret_stride * 8, count * 8, cnt, hipMemcpyHostToDevice, stream));
+      } else {
+        for (size_t s = 0; s < cnt; ++s)
+          for (size_t col = 0; col < count; ++col) packed[s * count + col] = shares[(s0 + s) * r.secret_stride + col * r.point_stride];
+        PVW_HIP(hipMemcpyAsync(d_sh, packed.data(), cnt * count * 8, hipMemcpyHostToDevice, stream));
+      }
+      PVW_TRY(piece(s0, cnt));
+      PVW_HIP(hipStreamSynchronize(stream));                     // the next piece reuses the staging
+    }
+    return PVW_OK;
+  }
+};
 
 // host buffers: the secrets go up in pieces of `per` (<= ~1 GiB of shares), each packed to [piece][count]; the weights are
 // made once.  The staged shares and the staged results are secret; the weights and the counts are not.
@@ -2375,36 +2409,23 @@ int32_t pvw_shamir_reconstruct_checked(pvw_ctx* c, uint64_t plain_modulus, uint3
   Scratch sc;
   const size_t r_sh = sc.add(per * count * 8), r_out = sc.add(per * 8), r_ws = sc.add(r.ws_bytes()), r_bad = sc.add(per * 4),
                r_col = sc.add(count * 4);
-  std::vector<u64> packed;                                       // a piece's shares when the caller's rows are not dense
-  const bool dense = point_stride == 1 && secret_stride >= count;   // whole rows go up as they lie (a 2D copy)
-  if (!dense) packed.resize(per * count);
-  const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
+  ShareStaging st(r, shares, per);
+  return host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
     sc.secret(w, r_sh, r_out);
     u64 *d_sh = sc.at(r_sh), *d_out = sc.at(r_out), *ws = sc.at(r_ws);
     u32 *d_bad = bad ? sc.at<u32>(r_bad) : nullptr, *d_col = col_bad ? sc.at<u32>(r_col) : nullptr;
     PVW_TRY(reconstruct_weights(c, r, ws, w->stream));
     PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
-    for (size_t s0 = 0; s0 < num_secrets; s0 += per) {
-      const size_t cnt = (num_secrets - s0) < per ? (num_secrets - s0) : per;
-      if (dense) {
-        PVW_HIP(hipMemcpy2DAsync(d_sh, count * 8, shares + s0 * secret_stride, secret_stride * 8, count * 8, cnt, hipMemcpyHostToDevice, w->stream));
-      } else {
-        for (size_t s = 0; s < cnt; ++s)
-          for (size_t col = 0; col < count; ++col) packed[s * count + col] = shares[(s0 + s) * secret_stride + col * point_stride];
-        PVW_HIP(hipMemcpyAsync(d_sh, packed.data(), cnt * count * 8, hipMemcpyHostToDevice, w->stream));
-      }
+    PVW_TRY(st.run(d_sh, w->stream, [&](size_t s0, size_t cnt) -> int32_t {
       PVW_TRY(reconstruct_interp(c, r, ws, d_sh, cnt, count, 1, d_out, d_bad, d_col, w->stream));
       PVW_HIP(hipMemcpyAsync(out + s0, d_out, cnt * 8, hipMemcpyDeviceToHost, w->stream));
       if (bad) PVW_HIP(hipMemcpyAsync(bad + s0, d_bad, cnt * 4, hipMemcpyDeviceToHost, w->stream));
-      PVW_HIP(hipStreamSynchronize(w->stream));                // the next piece reuses the staging
-    }
+      return PVW_OK;
+    }));
     if (col_bad) PVW_HIP(hipMemcpyAsync(col_bad, d_col, count * 4, hipMemcpyDeviceToHost, w->stream));
     return PVW_OK;
   });
-  volatile u64* vp = packed.data();                              // the host copy is as secret as the caller's shares
-  for (size_t i = 0; i < packed.size(); ++i) vp[i] = 0;
-  return rc;
 }
 
 // ------------------------------------------------------------------------ corrected reconstruction
@@ -2594,18 +2615,17 @@ static int32_t correct_piece_enqueue(pvw_ctx* c, const Reconstruct& r, const Cor
   return PVW_OK;
 }
 
-// as reconstruct_capture_check, for the stream's corrected-reconstruction scratch
-static int32_t correct_capture_check(pvw_ctx* c, hipStream_t s, size_t need) {
-  if (!stream_capturing(s)) return PVW_OK;
-  bool ready;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    auto it = c->async_ws.find((void*)s);
-    ready = it != c->async_ws.end() && it->second->correct_bytes >= need;
-  }
-  if (!ready)
-    return fail(PVW_ERR_INVALID_PARAMETERS, "corrected reconstruction under stream capture: run a call with the same degree and count and "
-                                            "at least as many secrets on this stream outside capture first (it sizes the workspace)");
+// The stream's `correct` block for a device call of 8.11 or 8.13: grown to `need` bytes, and the regions (word offset, bytes) the
+// call's secrets decide marked secret -- M, which leads the block, and for the evaluation y o M | raw | the stand-in for out.
+static int32_t correct_block(Workspace* w, size_t need, std::initializer_list<std::pair<size_t, size_t>> secret, hipStream_t s) {
+  if (w->correct_bytes < need) ws_public(w, w->correct, w->correct_bytes);   // the block is about to go
+  PVW_TRY(ws_grow(&w->correct, &w->correct_bytes, need, s, true));
+  for (const auto& sp : secret) ws_mark_secret(w, w->correct + sp.first, sp.second);
+  return PVW_OK;
+}
+// ... and its passes over the kernels: pass(s0, ns) for every `cap` of the call's secrets
+static int32_t correct_passes(const Reconstruct& r, size_t cap, const std::function<int32_t(size_t s0, size_t ns)>& pass) {
+  for (size_t s0 = 0; s0 < r.S; s0 += cap) PVW_TRY(pass(s0, r.S - s0 < cap ? r.S - s0 : cap));
   return PVW_OK;
 }
 
@@ -2620,22 +2640,21 @@ int32_t pvw_shamir_reconstruct_corrected_device(pvw_ctx* c, uint64_t plain_modul
   const CorrectLayout lay(r, correct_piece(r));
   const size_t words = (count + 63) / 64;
   // the caller's stream is checked before the context initialises its device (pvw_shamir_reconstruct_checked_device)
-  if (stream) PVW_TRY(correct_capture_check(c, (hipStream_t)stream, lay.bytes()));
-  return device_call(c, stream, [&](hipStream_t s) { return correct_capture_check(c, s, lay.bytes()); },
-                     [&](Workspace* w, hipStream_t s) -> int32_t {
-                       if (w->correct_bytes < lay.bytes()) ws_public(w, w->correct, w->correct_bytes);   // the block is about to go
-                       PVW_TRY(ws_grow(&w->correct, &w->correct_bytes, lay.bytes(), s, true));
-                       ws_mark_secret(w, w->correct, lay.m_bytes());
-                       PVW_TRY(correct_weights(c, r, lay, w->correct, s));
-                       PVW_HIP(launch_shamir_zero_counts(d_col_err, count, s));
-                       for (size_t s0 = 0; s0 < num_secrets; s0 += lay.cap) {
-                         const size_t ns = num_secrets - s0 < lay.cap ? num_secrets - s0 : lay.cap;
-                         PVW_TRY(correct_piece_enqueue(c, r, lay, w->correct, d_shares + s0 * secret_stride, ns, secret_stride, point_stride,
-                                                       d_out + s0, d_nerr ? d_nerr + s0 : nullptr, d_col_err,
-                                                       d_err_mask ? d_err_mask + s0 * words : nullptr, s));
-                       }
-                       return PVW_OK;
-                     });
+  auto sized = [&](hipStream_t s) {
+    return grown_capture_check(c, s, &Workspace::correct_bytes, lay.bytes(),
+                               "corrected reconstruction under stream capture: run a call with the same degree and count and at least as "
+                               "many secrets on this stream outside capture first (it sizes the workspace)");
+  };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
+    PVW_TRY(correct_block(w, lay.bytes(), {{0, lay.m_bytes()}}, s));
+    PVW_TRY(correct_weights(c, r, lay, w->correct, s));
+    PVW_HIP(launch_shamir_zero_counts(d_col_err, count, s));
+    return correct_passes(r, lay.cap, [&](size_t s0, size_t ns) {
+      return correct_piece_enqueue(c, r, lay, w->correct, d_shares + s0 * secret_stride, ns, secret_stride, point_stride, d_out + s0,
+                                   Report::from(d_nerr, s0), d_col_err, Report::from(d_err_mask, s0 * words), s);
+    });
+  });
 }
 
 // host buffers: the secrets go up in pieces as pvw_shamir_reconstruct_checked stages them (each packed to [piece][count], or
@@ -2656,10 +2675,8 @@ int32_t pvw_shamir_reconstruct_corrected(pvw_ctx* c, uint64_t plain_modulus, uin
   Scratch sc;
   const size_t r_sh = sc.add(per * count * 8), r_out = sc.add(per * 8), r_ws = sc.add(lay.bytes()), r_nerr = sc.add(per * 4),
                r_col = sc.add(count * 4), r_mask = sc.add(per * words * 8);
-  std::vector<u64> packed;                                       // a piece's shares when the caller's rows are not dense
-  const bool dense = point_stride == 1 && secret_stride >= count;   // whole rows go up as they lie (a 2D copy)
-  if (!dense) packed.resize(per * count);
-  const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
+  ShareStaging st(r, shares, per);
+  return host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
     u64 *d_sh = sc.at(r_sh), *d_out = sc.at(r_out), *ws = sc.at(r_ws);
     ws_mark_secret(w, d_sh, (size_t)((char*)ws - (char*)d_sh) + lay.m_bytes());   // staged shares | staged secrets | M
@@ -2667,27 +2684,16 @@ int32_t pvw_shamir_reconstruct_corrected(pvw_ctx* c, uint64_t plain_modulus, uin
     u64* d_mask = err_mask ? sc.at(r_mask) : nullptr;
     PVW_TRY(correct_weights(c, r, lay, ws, w->stream));
     PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
-    for (size_t s0 = 0; s0 < num_secrets; s0 += per) {
-      const size_t cnt = (num_secrets - s0) < per ? (num_secrets - s0) : per;
-      if (dense) {
-        PVW_HIP(hipMemcpy2DAsync(d_sh, count * 8, shares + s0 * secret_stride, secret_stride * 8, count * 8, cnt, hipMemcpyHostToDevice, w->stream));
-      } else {
-        for (size_t s = 0; s < cnt; ++s)
-          for (size_t col = 0; col < count; ++col) packed[s * count + col] = shares[(s0 + s) * secret_stride + col * point_stride];
-        PVW_HIP(hipMemcpyAsync(d_sh, packed.data(), cnt * count * 8, hipMemcpyHostToDevice, w->stream));
-      }
+    PVW_TRY(st.run(d_sh, w->stream, [&](size_t s0, size_t cnt) -> int32_t {
       PVW_TRY(correct_piece_enqueue(c, r, lay, ws, d_sh, cnt, count, 1, d_out, d_nerr, d_col, d_mask, w->stream));
       PVW_HIP(hipMemcpyAsync(out + s0, d_out, cnt * 8, hipMemcpyDeviceToHost, w->stream));
       if (nerr) PVW_HIP(hipMemcpyAsync(nerr + s0, d_nerr, cnt * 4, hipMemcpyDeviceToHost, w->stream));
       if (err_mask) PVW_HIP(hipMemcpyAsync(err_mask + s0 * words, d_mask, cnt * words * 8, hipMemcpyDeviceToHost, w->stream));
-      PVW_HIP(hipStreamSynchronize(w->stream));                // the next piece reuses the staging
-    }
+      return PVW_OK;
+    }));
     if (col_err) PVW_HIP(hipMemcpyAsync(col_err, d_col, count * 4, hipMemcpyDeviceToHost, w->stream));
     return PVW_OK;
   });
-  volatile u64* vp = packed.data();                              // the host copy is as secret as the caller's shares
-  for (size_t i = 0; i < packed.size(); ++i) vp[i] = 0;
-  return rc;
 }
 
 // ------------------------------------------------------------------------ evaluation of the corrected polynomials
@@ -2829,22 +2835,6 @@ static int32_t evaluate_pass_enqueue(pvw_ctx* c, const Reconstruct& r, const Eva
   return PVW_OK;
 }
 
-// as correct_capture_check: the block is the corrected call's, with the evaluation's regions behind
-static int32_t evaluate_capture_check(pvw_ctx* c, hipStream_t s, size_t need) {
-  if (!stream_capturing(s)) return PVW_OK;
-  bool ready;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    auto it = c->async_ws.find((void*)s);
-    ready = it != c->async_ws.end() && it->second->correct_bytes >= need;
-  }
-  if (!ready)
-    return fail(PVW_ERR_INVALID_PARAMETERS, "corrected evaluation under stream capture: run a call with the same degree and count, at least "
-                                            "as many targets and at least as many secrets on this stream outside capture first (it sizes "
-                                            "the workspace)");
-  return PVW_OK;
-}
-
 int32_t pvw_shamir_evaluate_corrected_device(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
                                              const uint64_t* d_shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
                                              const uint64_t* targets, size_t num_targets, uint64_t* d_values, uint64_t* d_out,
@@ -2858,25 +2848,23 @@ int32_t pvw_shamir_evaluate_corrected_device(pvw_ctx* c, uint64_t plain_modulus,
   if (need < lay.bytes()) return fail(PVW_ERR_INTERNAL, "evaluation scratch: layout beyond its bound");
   const size_t words = (count + 63) / 64;
   // the caller's stream is checked before the context initialises its device (pvw_shamir_reconstruct_checked_device)
-  if (stream) PVW_TRY(evaluate_capture_check(c, (hipStream_t)stream, need));
-  return device_call(c, stream, [&](hipStream_t s) { return evaluate_capture_check(c, s, need); },
-                     [&](Workspace* w, hipStream_t s) -> int32_t {
-                       if (w->correct_bytes < need) ws_public(w, w->correct, w->correct_bytes);   // the block is about to go
-                       PVW_TRY(ws_grow(&w->correct, &w->correct_bytes, need, s, true));
-                       ws_mark_secret(w, w->correct, lay.cl.m_bytes());
-                       ws_mark_secret(w, w->correct + lay.ym, lay.secret_bytes());
-                       PVW_TRY(correct_weights(c, r, lay.cl, w->correct, s));
-                       PVW_HIP(launch_shamir_zero_counts(d_col_err, count, s));
-                       size_t resident = SIZE_MAX;
-                       for (size_t s0 = 0; s0 < num_secrets; s0 += lay.cl.cap) {
-                         const size_t ns = num_secrets - s0 < lay.cl.cap ? num_secrets - s0 : lay.cl.cap;
-                         PVW_TRY(evaluate_pass_enqueue(c, r, lay, w->correct, d_shares + s0 * secret_stride, ns, secret_stride, point_stride,
-                                                       targets, num_targets, d_values + s0 * num_targets, d_out ? d_out + s0 : nullptr,
-                                                       d_nerr ? d_nerr + s0 : nullptr, d_col_err,
-                                                       d_err_mask ? d_err_mask + s0 * words : nullptr, &resident, s));
-                       }
-                       return PVW_OK;
-                     });
+  auto sized = [&](hipStream_t s) {
+    return grown_capture_check(c, s, &Workspace::correct_bytes, need,
+                               "corrected evaluation under stream capture: run a call with the same degree and count, at least as many "
+                               "targets and at least as many secrets on this stream outside capture first (it sizes the workspace)");
+  };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
+    PVW_TRY(correct_block(w, need, {{0, lay.cl.m_bytes()}, {lay.ym, lay.secret_bytes()}}, s));
+    PVW_TRY(correct_weights(c, r, lay.cl, w->correct, s));
+    PVW_HIP(launch_shamir_zero_counts(d_col_err, count, s));
+    size_t resident = SIZE_MAX;
+    return correct_passes(r, lay.cl.cap, [&](size_t s0, size_t ns) {
+      return evaluate_pass_enqueue(c, r, lay, w->correct, d_shares + s0 * secret_stride, ns, secret_stride, point_stride, targets,
+                                   num_targets, d_values + s0 * num_targets, Report::from(d_out, s0), Report::from(d_nerr, s0), d_col_err,
+                                   Report::from(d_err_mask, s0 * words), &resident, s);
+    });
+  });
 }
 
 // host buffers: staged as pvw_shamir_reconstruct_corrected stages (each piece one pass over the kernels, packed to [piece][count]
@@ -2898,10 +2886,8 @@ int32_t pvw_shamir_evaluate_corrected(pvw_ctx* c, uint64_t plain_modulus, uint32
   Scratch sc;
   const size_t r_sh = sc.add(per * count * 8), r_out = sc.add(per * 8), r_val = sc.add(per * num_targets * 8), r_ws = sc.add(lay.bytes()),
                r_nerr = sc.add(per * 4), r_col = sc.add(count * 4), r_mask = sc.add(per * words * 8);
-  std::vector<u64> packed;                                       // a piece's shares when the caller's rows are not dense
-  const bool dense = point_stride == 1 && secret_stride >= count;   // whole rows go up as they lie (a 2D copy)
-  if (!dense) packed.resize(per * count);
-  const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
+  ShareStaging st(r, shares, per);
+  return host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
     u64 *d_sh = sc.at(r_sh), *d_out = sc.at(r_out), *d_val = sc.at(r_val), *ws = sc.at(r_ws);
     ws_mark_secret(w, d_sh, (size_t)((char*)ws - (char*)d_sh) + lay.cl.m_bytes());   // staged shares | secrets | values | M
@@ -2911,29 +2897,18 @@ int32_t pvw_shamir_evaluate_corrected(pvw_ctx* c, uint64_t plain_modulus, uint32
     PVW_TRY(correct_weights(c, r, lay.cl, ws, w->stream));
     PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
     size_t resident = SIZE_MAX;
-    for (size_t s0 = 0; s0 < num_secrets; s0 += per) {
-      const size_t cnt = (num_secrets - s0) < per ? (num_secrets - s0) : per;
-      if (dense) {
-        PVW_HIP(hipMemcpy2DAsync(d_sh, count * 8, shares + s0 * secret_stride, secret_stride * 8, count * 8, cnt, hipMemcpyHostToDevice, w->stream));
-      } else {
-        for (size_t s = 0; s < cnt; ++s)
-          for (size_t col = 0; col < count; ++col) packed[s * count + col] = shares[(s0 + s) * secret_stride + col * point_stride];
-        PVW_HIP(hipMemcpyAsync(d_sh, packed.data(), cnt * count * 8, hipMemcpyHostToDevice, w->stream));
-      }
+    PVW_TRY(st.run(d_sh, w->stream, [&](size_t s0, size_t cnt) -> int32_t {
       PVW_TRY(evaluate_pass_enqueue(c, r, lay, ws, d_sh, cnt, count, 1, targets, num_targets, d_val, d_out, d_nerr, d_col, d_mask, &resident,
                                     w->stream));
       PVW_HIP(hipMemcpyAsync(values + s0 * num_targets, d_val, cnt * num_targets * 8, hipMemcpyDeviceToHost, w->stream));
       if (out) PVW_HIP(hipMemcpyAsync(out + s0, d_out, cnt * 8, hipMemcpyDeviceToHost, w->stream));
       if (nerr) PVW_HIP(hipMemcpyAsync(nerr + s0, d_nerr, cnt * 4, hipMemcpyDeviceToHost, w->stream));
       if (err_mask) PVW_HIP(hipMemcpyAsync(err_mask + s0 * words, d_mask, cnt * words * 8, hipMemcpyDeviceToHost, w->stream));
-      PVW_HIP(hipStreamSynchronize(w->stream));                // the next piece reuses the staging
-    }
+      return PVW_OK;
+    }));
     if (col_err) PVW_HIP(hipMemcpyAsync(col_err, d_col, count * 4, hipMemcpyDeviceToHost, w->stream));
     return PVW_OK;
   });
-  volatile u64* vp = packed.data();                              // the host copy is as secret as the caller's shares
-  for (size_t i = 0; i < packed.size(); ++i) vp[i] = 0;
-  return rc;
 }
 
 // One call's Shamir sharing on the device (pvw_shamir_shares*, and pvw_deal_shares* through encrypt_multi_enqueue)

@@ -210,23 +210,31 @@ __global__ __launch_bounds__(256) void shamir_weights_kernel(const u64* x, const
   W[e] = mulmod(mulmod(aux[(size_t)t + 1 + tm], aux[j], m), inv, m);
 }
 
-// grid: x = blocks of 64 targets, y = groups of SH_DG secrets; 256 threads.
-__global__ __launch_bounds__(256) void shamir_interp_kernel(ShamirInterp b) {
-  __shared__ u64 sh[SH_WAVES][SH_JC][SH_DG];       // 8 KiB: the chunk's shares, below p
+// Out[S][T] = A[S][terms] x W[terms][T] mod p for one workgroup (256 threads, block x = 64 targets, block y = SH_DG secrets):
+// the frame both kernels below share.  A is any words at two strides, staged through LDS below p along whichever stride is the
+// shorter one with neighbouring lanes; four weights are in flight ahead of their multiply-adds; the waves' partial sums meet in
+// LDS.  Thread (wave, lane) comes back with the sum v of element (s = s0 + wave, tm) and whether that element exists.
+// m by value: through a reference into the kernel's arguments the epilogue is compiled with 24 more 64-bit multiplies.
+struct ShamirTile {
+  u64 v;
+  u32 s;
+  size_t tm;
+  bool live;
+};
+__device__ __forceinline__ ShamirTile shamir_tile_product(const u64* A, size_t secret_stride, size_t term_stride, const u64* W, u32 ns,
+                                                          u32 nt, u32 T, const Mod m) {
+  __shared__ u64 sh[SH_WAVES][SH_JC][SH_DG];       // 8 KiB: the chunk of A, below p
   __shared__ u64 part[SH_WAVES][SH_DG][64];        // 8 KiB: the waves' partial sums, below p
   const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const Mod m = b.m;
-  const u32 nt = b.degree + 1;                     // terms: the basis columns
   const u32 s0 = blockIdx.y * SH_DG;
   const size_t tm = (size_t)blockIdx.x * 64 + lane;
-  const bool live = tm < b.T;
+  const bool live = tm < T;
   // wave w owns terms j = w * Q + [0, Q), cut off at nt; every wave walks the same number of chunks (barriers)
   const u32 Q = (nt + SH_WAVES - 1) / SH_WAVES;
   const u32 jw0 = wave * Q;
   const u32 nchunks = (Q + SH_JC - 1) / SH_JC;
-  // the staging walks whichever of the two strides is the shorter one with neighbouring lanes
-  const bool term_fast = b.point_stride <= b.secret_stride;
-  const u64* wcol = b.W + (live ? tm : 0);
+  const bool term_fast = term_stride <= secret_stride;
+  const u64* wcol = W + (live ? tm : 0);
   Acc acc[SH_DG];
 #pragma unroll
   for (int g = 0; g < SH_DG; ++g) acc_zero(acc[g]);
@@ -239,8 +247,7 @@ __global__ __launch_bounds__(256) void shamir_interp_kernel(ShamirInterp b) {
       const u32 off = c * SH_JC + ej;              // within the wave's range
       const u32 j = ew * Q + off;
       u64 a = 0;
-      if (off < Q && j < nt && s0 + eg < b.ns)
-        a = reduce_word(b.shares[(size_t)(s0 + eg) * b.secret_stride + (size_t)j * b.point_stride], m);
+      if (off < Q && j < nt && s0 + eg < ns) a = reduce_word(A[(size_t)(s0 + eg) * secret_stride + (size_t)j * term_stride], m);
       sh[ew][ej][eg] = a;
     }
     __syncthreads();
@@ -252,13 +259,13 @@ __global__ __launch_bounds__(256) void shamir_interp_kernel(ShamirInterp b) {
       const u32 left = nt - (jw0 + base);
       cnt = left < cnt ? left : cnt;
     }
-    const u64* wp = wcol + (size_t)(jw0 + base) * b.T;
+    const u64* wp = wcol + (size_t)(jw0 + base) * T;
     u32 jj = 0;
     for (; jj + 4 <= cnt; jj += 4) {               // four weights in flight ahead of their multiply-adds
       u64 w[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) w[u] = live ? wp[(size_t)u * b.T] : 0;
-      wp += (size_t)4 * b.T;
+      for (int u = 0; u < 4; ++u) w[u] = live ? wp[(size_t)u * T] : 0;
+      wp += (size_t)4 * T;
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         u64 a[SH_DG];
@@ -270,7 +277,7 @@ __global__ __launch_bounds__(256) void shamir_interp_kernel(ShamirInterp b) {
     }
     for (; jj < cnt; ++jj) {
       const u64 w = live ? *wp : 0;
-      wp += b.T;
+      wp += T;
       u64 a[SH_DG];
 #pragma unroll
       for (int g = 0; g < SH_DG; ++g) a[g] = sh[wave][jj][g];
@@ -282,28 +289,36 @@ __global__ __launch_bounds__(256) void shamir_interp_kernel(ShamirInterp b) {
 #pragma unroll
   for (int g = 0; g < SH_DG; ++g) part[wave][g][lane] = acc_reduce(acc[g], m);
   __syncthreads();
-  // thread (g, lane) adds the four partial sums of secret s0 + g at its target: target 0 is the secret, every other target
-  // is compared with the share of its column
-  {
-    const u32 g = wave;                            // SH_WAVES == SH_DG
-    const u32 s = s0 + g;
-    bool dev = false;
-    if (live && s < b.ns) {
-      u64 v = 0;
+  // thread (g, lane) adds the four partial sums of secret s0 + g at its target
+  ShamirTile o;
+  o.s = s0 + wave;                                 // SH_WAVES == SH_DG
+  o.tm = tm;
+  o.live = live && o.s < ns;
+  o.v = 0;
+  if (o.live) {
 #pragma unroll
-      for (int w = 0; w < SH_WAVES; ++w) v = addmod(v, part[w][g][lane], m.q);
-      if (tm == 0) {
-        b.out[s] = v;
-      } else {
-        const size_t col = (size_t)b.degree + tm;
-        dev = reduce_word(b.shares[(size_t)s * b.secret_stride + col * b.point_stride], m) != v;
-        if (dev && b.col_bad) atomicAdd(&b.col_bad[col], 1u);
-      }
-    }
-    // one add per wave: the wave's lanes share the secret
-    const u32 ndev = (u32)__popcll(__ballot(dev));
-    if (lane == 0 && ndev && b.bad && s < b.ns) atomicAdd(&b.bad[s], ndev);
+    for (int w = 0; w < SH_WAVES; ++w) o.v = addmod(o.v, part[w][wave][lane], m.q);
   }
+  return o;
+}
+
+// The tile product of the shares' basis columns with W; target 0 is the secret, every other target is compared with the share
+// of its column.  grid: x = blocks of 64 targets, y = groups of SH_DG secrets; 256 threads.
+__global__ __launch_bounds__(256) void shamir_interp_kernel(ShamirInterp b) {
+  const ShamirTile o = shamir_tile_product(b.shares, b.secret_stride, b.point_stride, b.W, b.ns, b.degree + 1, b.T, b.m);
+  bool dev = false;
+  if (o.live) {
+    if (o.tm == 0) {
+      b.out[o.s] = o.v;
+    } else {
+      const size_t col = (size_t)b.degree + o.tm;
+      dev = reduce_word(b.shares[(size_t)o.s * b.secret_stride + col * b.point_stride], b.m) != o.v;
+      if (dev && b.col_bad) atomicAdd(&b.col_bad[col], 1u);
+    }
+  }
+  // one add per wave: the wave's lanes share the secret
+  const u32 ndev = (u32)__popcll(__ballot(dev));
+  if ((threadIdx.x & 63) == 0 && ndev && b.bad) atomicAdd(&b.bad[o.s], ndev);
 }
 
 // bad / col_bad start from 0 on every call and on every replay of a captured one: a kernel in stream order, not a memset node
@@ -343,22 +358,29 @@ hipError_t launch_shamir_weights(u64* ws, size_t count, u32 t, const Mod& m, hip
   return hipGetLastError();
 }
 
-// the grid's y dimension holds 65535 groups of secrets: more secrets take more launches
-hipError_t launch_shamir_interp(const ShamirInterp& b, hipStream_t s) {
+// One launch per 65535 groups of secrets, which is what the grid's y dimension holds; from(s0) is b from secret s0 on.
+template <class Args, class From>
+static hipError_t launch_secret_groups(void (*kernel)(Args), const Args& b, From from, hipStream_t s) {
   if (b.ns == 0 || b.T == 0) return hipSuccess;
   const u32 per = 65535u * SH_DG;
   for (u32 s0 = 0; s0 < b.ns; s0 += per) {
-    ShamirInterp p = b;
+    Args p = from(s0);
     p.ns = b.ns - s0 < per ? b.ns - s0 : per;
-    p.shares = b.shares + (size_t)s0 * b.secret_stride;
-    p.out = b.out + s0;
-    p.bad = b.bad ? b.bad + s0 : nullptr;
-    const dim3 grid((b.T + 63) / 64, (p.ns + SH_DG - 1) / SH_DG);
-    shamir_interp_kernel<<<grid, dim3(256), 0, s>>>(p);
+    kernel<<<dim3((b.T + 63) / 64, (p.ns + SH_DG - 1) / SH_DG), dim3(256), 0, s>>>(p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+hipError_t launch_shamir_interp(const ShamirInterp& b, hipStream_t s) {
+  return launch_secret_groups(shamir_interp_kernel, b, [&](u32 s0) {
+    ShamirInterp p = b;
+    p.shares += (size_t)s0 * b.secret_stride;
+    p.out += s0;
+    if (p.bad) p.bad += s0;
+    return p;
+  }, s);
 }
 
 // ------------------------------------------------------------------------ corrected reconstruction
@@ -407,88 +429,11 @@ __global__ __launch_bounds__(256) void shamir_powers_kernel(const u64* x, u64* X
   }
 }
 
-// Out[S][T] = A[S][terms] x W[terms][T] mod p, in the frame of shamir_interp_kernel: a lane owns one target and SH_DG secrets,
-// the four waves a quarter of the terms each; A (any words, two strides) is staged through LDS below p, four weights are in
-// flight ahead of their multiply-adds, the partial sums meet in LDS.  The epilogue only stores.
+// Out[S][T] = A[S][terms] x W[terms][T] mod p: the tile product, stored.
 // grid: x = blocks of 64 targets, y = groups of SH_DG secrets; 256 threads.
 __global__ __launch_bounds__(256) void shamir_matmul_kernel(ShamirMatmul b) {
-  __shared__ u64 sh[SH_WAVES][SH_JC][SH_DG];       // 8 KiB: the chunk of A, below p
-  __shared__ u64 part[SH_WAVES][SH_DG][64];        // 8 KiB: the waves' partial sums, below p
-  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const Mod m = b.m;
-  const u32 nt = b.terms;
-  const u32 s0 = blockIdx.y * SH_DG;
-  const size_t tm = (size_t)blockIdx.x * 64 + lane;
-  const bool live = tm < b.T;
-  // wave w owns terms j = w * Q + [0, Q), cut off at nt; every wave walks the same number of chunks (barriers)
-  const u32 Q = (nt + SH_WAVES - 1) / SH_WAVES;
-  const u32 jw0 = wave * Q;
-  const u32 nchunks = (Q + SH_JC - 1) / SH_JC;
-  const bool term_fast = b.term_stride <= b.secret_stride;
-  const u64* wcol = b.W + (live ? tm : 0);
-  Acc acc[SH_DG];
-#pragma unroll
-  for (int g = 0; g < SH_DG; ++g) acc_zero(acc[g]);
-  for (u32 c = 0; c < nchunks; ++c) {
-    for (u32 e = tid; e < SH_WAVES * SH_JC * SH_DG; e += 256) {
-      const u32 ew = e / (SH_JC * SH_DG);
-      const u32 ej = term_fast ? e % SH_JC : (e / SH_DG) % SH_JC;
-      const u32 eg = term_fast ? (e / SH_JC) % SH_DG : e % SH_DG;
-      const u32 off = c * SH_JC + ej;              // within the wave's range
-      const u32 j = ew * Q + off;
-      u64 a = 0;
-      if (off < Q && j < nt && s0 + eg < b.ns)
-        a = reduce_word(b.A[(size_t)(s0 + eg) * b.secret_stride + (size_t)j * b.term_stride], m);
-      sh[ew][ej][eg] = a;
-    }
-    __syncthreads();
-    const u32 base = c * SH_JC;
-    u32 cnt = 0;
-    if (base < Q && jw0 + base < nt) {
-      cnt = Q - base < SH_JC ? Q - base : SH_JC;
-      const u32 left = nt - (jw0 + base);
-      cnt = left < cnt ? left : cnt;
-    }
-    const u64* wp = wcol + (size_t)(jw0 + base) * b.T;
-    u32 jj = 0;
-    for (; jj + 4 <= cnt; jj += 4) {               // four weights in flight ahead of their multiply-adds
-      u64 w[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) w[u] = live ? wp[(size_t)u * b.T] : 0;
-      wp += (size_t)4 * b.T;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        u64 a[SH_DG];
-#pragma unroll
-        for (int g = 0; g < SH_DG; ++g) a[g] = sh[wave][jj + u][g];
-#pragma unroll
-        for (int g = 0; g < SH_DG; ++g) acc_mac_dev(acc[g], a[g], w[u]);
-      }
-    }
-    for (; jj < cnt; ++jj) {
-      const u64 w = live ? *wp : 0;
-      wp += b.T;
-      u64 a[SH_DG];
-#pragma unroll
-      for (int g = 0; g < SH_DG; ++g) a[g] = sh[wave][jj][g];
-#pragma unroll
-      for (int g = 0; g < SH_DG; ++g) acc_mac_dev(acc[g], a[g], w);
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int g = 0; g < SH_DG; ++g) part[wave][g][lane] = acc_reduce(acc[g], m);
-  __syncthreads();
-  {
-    const u32 g = wave;                            // SH_WAVES == SH_DG
-    const u32 s = s0 + g;
-    if (live && s < b.ns) {
-      u64 v = 0;
-#pragma unroll
-      for (int w = 0; w < SH_WAVES; ++w) v = addmod(v, part[w][g][lane], m.q);
-      b.out[(size_t)s * b.T + tm] = v;
-    }
-  }
+  const ShamirTile o = shamir_tile_product(b.A, b.secret_stride, b.term_stride, b.W, b.ns, b.terms, b.T, b.m);
+  if (o.live) b.out[(size_t)o.s * b.T + o.tm] = o.v;
 }
 
 // the sum of the lanes' values (each below p), the same in every lane
@@ -612,21 +557,13 @@ hipError_t launch_shamir_correct_weights(u64* ws, size_t count, u32 t, const Mod
   return hipGetLastError();
 }
 
-// the grid's y dimension holds 65535 groups of secrets: more secrets take more launches
 hipError_t launch_shamir_matmul(const ShamirMatmul& b, hipStream_t s) {
-  if (b.ns == 0 || b.T == 0) return hipSuccess;
-  const u32 per = 65535u * SH_DG;
-  for (u32 s0 = 0; s0 < b.ns; s0 += per) {
+  return launch_secret_groups(shamir_matmul_kernel, b, [&](u32 s0) {
     ShamirMatmul p = b;
-    p.ns = b.ns - s0 < per ? b.ns - s0 : per;
-    p.A = b.A + (size_t)s0 * b.secret_stride;
-    p.out = b.out + (size_t)s0 * b.T;
-    const dim3 grid((b.T + 63) / 64, (p.ns + SH_DG - 1) / SH_DG);
-    shamir_matmul_kernel<<<grid, dim3(256), 0, s>>>(p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    p.A += (size_t)s0 * b.secret_stride;
+    p.out += (size_t)s0 * b.T;
+    return p;
+  }, s);
 }
 
 // E + 1 <= PVW_SHAMIR_MAX_LOCATOR: C and B of one wave fit the 64 KiB of LDS a launch gets without asking for more

@@ -666,6 +666,15 @@ inline std::vector<uint64_t> shamir_reconstruct(const std::vector<uint64_t>& ind
   check(pvw_shamir_reconstruct(plain_modulus, indices.data(), shares.data(), indices.size(), out.size(), out.data()));
   return out;
 }
+// the share matrix of the checked, corrected and evaluate calls: its shape and the strides of its layout, in words
+struct ShareMatrix {
+  size_t count, S, words, ss, ps;   // columns, secrets, mask words per secret, secret stride, point stride
+  ShareMatrix(const std::vector<uint64_t>& indices, const std::vector<uint64_t>& shares, bool party_major) : count(indices.size()) {
+    if (count == 0 || shares.empty() || shares.size() % count) throw PvwError(15, "shares must hold one value per index and secret");
+    S = shares.size() / count, words = (count + 63) / 64;
+    ss = party_major ? 1 : count, ps = party_major ? S : 1;
+  }
+};
 // ---- checked reconstruction ----
 struct CheckedSecrets {
   std::vector<uint64_t> secrets;    // [num_secrets]: the value at 0 of the polynomial through each secret's basis shares
@@ -678,14 +687,11 @@ struct CheckedSecrets {
 inline CheckedSecrets shamir_reconstruct_checked(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& indices,
                                                  const std::vector<uint64_t>& shares, uint32_t degree, uint64_t plain_modulus,
                                                  bool host = false, bool party_major = false) {
-  const size_t count = indices.size();
-  if (count == 0 || shares.empty() || shares.size() % count) throw PvwError(15, "shares must hold one value per index and secret");
-  const size_t S = shares.size() / count;
-  CheckedSecrets r{std::vector<uint64_t>(S), std::vector<uint32_t>(S), std::vector<uint32_t>(count)};
-  const size_t ss = party_major ? 1 : count, ps = party_major ? S : 1;
-  check(host ? pvw_shamir_reconstruct_checked_host(plain_modulus, degree, indices.data(), count, shares.data(), S, ss, ps,
+  const ShareMatrix m(indices, shares, party_major);
+  CheckedSecrets r{std::vector<uint64_t>(m.S), std::vector<uint32_t>(m.S), std::vector<uint32_t>(m.count)};
+  check(host ? pvw_shamir_reconstruct_checked_host(plain_modulus, degree, indices.data(), m.count, shares.data(), m.S, m.ss, m.ps,
                                                    r.secrets.data(), r.bad.data(), r.col_bad.data())
-             : pvw_shamir_reconstruct_checked(p->ctx, plain_modulus, degree, indices.data(), count, shares.data(), S, ss, ps,
+             : pvw_shamir_reconstruct_checked(p->ctx, plain_modulus, degree, indices.data(), m.count, shares.data(), m.S, m.ss, m.ps,
                                               r.secrets.data(), r.bad.data(), r.col_bad.data()));
   return r;
 }
@@ -699,19 +705,19 @@ struct CorrectedSecrets {
   size_t words;                     // ceil(indices.size() / 64)
   bool wrong(size_t s, size_t c) const { return (err_mask[s * words + c / 64] >> (c % 64)) & 1; }
 };
+inline CorrectedSecrets corrected_report(const ShareMatrix& m) {   // all 0, of the matrix's shape
+  return {std::vector<uint64_t>(m.S), std::vector<uint32_t>(m.S), std::vector<uint32_t>(m.count), std::vector<uint64_t>(m.S * m.words), m.words};
+}
 // Up to E = (indices.size() - degree - 1) / 2 wrong shares per secret, in whichever columns.  shares as shamir_reconstruct_checked.
 // On the device (pvw_shamir_reconstruct_corrected); host = true: the plain C++ restatement (no GPU, p may be null).
 inline CorrectedSecrets shamir_reconstruct_corrected(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& indices,
                                                      const std::vector<uint64_t>& shares, uint32_t degree, uint64_t plain_modulus,
                                                      bool host = false, bool party_major = false) {
-  const size_t count = indices.size();
-  if (count == 0 || shares.empty() || shares.size() % count) throw PvwError(15, "shares must hold one value per index and secret");
-  const size_t S = shares.size() / count, words = (count + 63) / 64;
-  CorrectedSecrets r{std::vector<uint64_t>(S), std::vector<uint32_t>(S), std::vector<uint32_t>(count), std::vector<uint64_t>(S * words), words};
-  const size_t ss = party_major ? 1 : count, ps = party_major ? S : 1;
-  check(host ? pvw_shamir_reconstruct_corrected_host(plain_modulus, degree, indices.data(), count, shares.data(), S, ss, ps,
+  const ShareMatrix m(indices, shares, party_major);
+  CorrectedSecrets r = corrected_report(m);
+  check(host ? pvw_shamir_reconstruct_corrected_host(plain_modulus, degree, indices.data(), m.count, shares.data(), m.S, m.ss, m.ps,
                                                      r.secrets.data(), r.nerr.data(), r.col_err.data(), r.err_mask.data())
-             : pvw_shamir_reconstruct_corrected(p->ctx, plain_modulus, degree, indices.data(), count, shares.data(), S, ss, ps,
+             : pvw_shamir_reconstruct_corrected(p->ctx, plain_modulus, degree, indices.data(), m.count, shares.data(), m.S, m.ss, m.ps,
                                                 r.secrets.data(), r.nerr.data(), r.col_err.data(), r.err_mask.data()));
   return r;
 }
@@ -726,18 +732,15 @@ struct EvaluatedShares {
 inline EvaluatedShares shamir_evaluate_corrected(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& indices,
                                                  const std::vector<uint64_t>& shares, uint32_t degree, uint64_t plain_modulus,
                                                  const std::vector<uint64_t>& targets, bool host = false, bool party_major = false) {
-  const size_t count = indices.size(), T = targets.size();
-  if (count == 0 || shares.empty() || shares.size() % count) throw PvwError(15, "shares must hold one value per index and secret");
-  const size_t S = shares.size() / count, words = (count + 63) / 64;
-  EvaluatedShares r{std::vector<uint64_t>(S * T),
-                    CorrectedSecrets{std::vector<uint64_t>(S), std::vector<uint32_t>(S), std::vector<uint32_t>(count),
-                                     std::vector<uint64_t>(S * words), words}};
+  const ShareMatrix m(indices, shares, party_major);
+  const size_t T = targets.size();
+  EvaluatedShares r{std::vector<uint64_t>(m.S * T), corrected_report(m)};
   CorrectedSecrets& d = r.decode;
-  const size_t ss = party_major ? 1 : count, ps = party_major ? S : 1;
-  check(host ? pvw_shamir_evaluate_corrected_host(plain_modulus, degree, indices.data(), count, shares.data(), S, ss, ps, targets.data(), T,
-                                                  r.values.data(), d.secrets.data(), d.nerr.data(), d.col_err.data(), d.err_mask.data())
-             : pvw_shamir_evaluate_corrected(p->ctx, plain_modulus, degree, indices.data(), count, shares.data(), S, ss, ps, targets.data(),
-                                             T, r.values.data(), d.secrets.data(), d.nerr.data(), d.col_err.data(), d.err_mask.data()));
+  check(host ? pvw_shamir_evaluate_corrected_host(plain_modulus, degree, indices.data(), m.count, shares.data(), m.S, m.ss, m.ps, targets.data(),
+                                                  T, r.values.data(), d.secrets.data(), d.nerr.data(), d.col_err.data(), d.err_mask.data())
+             : pvw_shamir_evaluate_corrected(p->ctx, plain_modulus, degree, indices.data(), m.count, shares.data(), m.S, m.ss, m.ps,
+                                             targets.data(), T, r.values.data(), d.secrets.data(), d.nerr.data(), d.col_err.data(),
+                                             d.err_mask.data()));
   return r;
 }
 

@@ -483,6 +483,16 @@ pub fn shamir_reconstruct(indices: &[u64], shares: &[u64], plain_modulus: u64) -
     Ok(out)
 }
 
+/// The share matrix of the checked, corrected and evaluate calls: (columns, secrets, secret stride, point stride), in words.
+fn share_matrix(indices: &[u64], shares: &[u64], party_major: bool) -> Result<(usize, usize, usize, usize)> {
+    if indices.is_empty() || shares.is_empty() || shares.len() % indices.len() != 0 {
+        return Err(PvwError::InvalidParameters("shares must hold one value per index and secret".into()));
+    }
+    let (count, num) = (indices.len(), shares.len() / indices.len());
+    let (ss, ps) = if party_major { (1, num) } else { (count, 1) };
+    Ok((count, num, ss, ps))
+}
+
 /// EXTENSION: what `shamir_reconstruct_checked` reports.
 pub struct CheckedSecrets {
     /// the value at 0 of the polynomial through each secret's basis shares
@@ -498,11 +508,7 @@ pub struct CheckedSecrets {
 /// `party_major` `[indices.len()][num_secrets]` (what `decrypt_all_party_shares` returns, every dealer a secret).
 pub fn shamir_reconstruct_checked(params: &Arc<PvwParameters>, indices: &[u64], shares: &[u64], degree: u32, plain_modulus: u64,
                                   party_major: bool) -> Result<CheckedSecrets> {
-    if indices.is_empty() || shares.is_empty() || shares.len() % indices.len() != 0 {
-        return Err(PvwError::InvalidParameters("shares must hold one value per index and secret".into()));
-    }
-    let (count, num) = (indices.len(), shares.len() / indices.len());
-    let (ss, ps) = if party_major { (1, num) } else { (count, 1) };
+    let (count, num, ss, ps) = share_matrix(indices, shares, party_major)?;
     let mut r = CheckedSecrets { secrets: vec![0u64; num], bad: vec![0u32; num], col_bad: vec![0u32; count] };
     check(unsafe {
         sys::pvw_shamir_reconstruct_checked(params.hip.raw(), plain_modulus, degree, indices.as_ptr(), count, shares.as_ptr(), num, ss, ps,
@@ -525,17 +531,19 @@ pub struct CorrectedSecrets {
     pub words: usize,
 }
 
+impl CorrectedSecrets {
+    fn zeroed(count: usize, num: usize) -> Self {
+        let words = (count + 63) / 64;
+        CorrectedSecrets { secrets: vec![0u64; num], nerr: vec![0u32; num], col_err: vec![0u32; count], err_mask: vec![0u64; num * words], words }
+    }
+}
+
 /// EXTENSION: the secrets although up to `(indices.len() - degree - 1) / 2` shares of each are wrong, in
 /// whichever columns, on the device (`pvw_shamir_reconstruct_corrected`).  `shares` as `shamir_reconstruct_checked`.
 pub fn shamir_reconstruct_corrected(params: &Arc<PvwParameters>, indices: &[u64], shares: &[u64], degree: u32, plain_modulus: u64,
                                     party_major: bool) -> Result<CorrectedSecrets> {
-    if indices.is_empty() || shares.is_empty() || shares.len() % indices.len() != 0 {
-        return Err(PvwError::InvalidParameters("shares must hold one value per index and secret".into()));
-    }
-    let (count, num) = (indices.len(), shares.len() / indices.len());
-    let words = (count + 63) / 64;
-    let (ss, ps) = if party_major { (1, num) } else { (count, 1) };
-    let mut r = CorrectedSecrets { secrets: vec![0u64; num], nerr: vec![0u32; num], col_err: vec![0u32; count], err_mask: vec![0u64; num * words], words };
+    let (count, num, ss, ps) = share_matrix(indices, shares, party_major)?;
+    let mut r = CorrectedSecrets::zeroed(count, num);
     check(unsafe {
         sys::pvw_shamir_reconstruct_corrected(params.hip.raw(), plain_modulus, degree, indices.as_ptr(), count, shares.as_ptr(), num, ss, ps,
                                               r.secrets.as_mut_ptr(), r.nerr.as_mut_ptr(), r.col_err.as_mut_ptr(), r.err_mask.as_mut_ptr())
@@ -548,14 +556,9 @@ pub fn shamir_reconstruct_corrected(params: &Arc<PvwParameters>, indices: &[u64]
 /// parties `targets` (global indices, among `indices` or not; duplicates allowed).  The row of an undecodable secret is 0.
 pub fn shamir_evaluate_corrected(params: &Arc<PvwParameters>, indices: &[u64], shares: &[u64], degree: u32, plain_modulus: u64,
                                  targets: &[u64], party_major: bool) -> Result<(Vec<u64>, CorrectedSecrets)> {
-    if indices.is_empty() || shares.is_empty() || shares.len() % indices.len() != 0 {
-        return Err(PvwError::InvalidParameters("shares must hold one value per index and secret".into()));
-    }
-    let (count, num) = (indices.len(), shares.len() / indices.len());
-    let words = (count + 63) / 64;
-    let (ss, ps) = if party_major { (1, num) } else { (count, 1) };
+    let (count, num, ss, ps) = share_matrix(indices, shares, party_major)?;
     let mut values = vec![0u64; num * targets.len()];
-    let mut r = CorrectedSecrets { secrets: vec![0u64; num], nerr: vec![0u32; num], col_err: vec![0u32; count], err_mask: vec![0u64; num * words], words };
+    let mut r = CorrectedSecrets::zeroed(count, num);
     check(unsafe {
         sys::pvw_shamir_evaluate_corrected(params.hip.raw(), plain_modulus, degree, indices.as_ptr(), count, shares.as_ptr(), num, ss, ps,
                                            targets.as_ptr(), targets.len(), values.as_mut_ptr(), r.secrets.as_mut_ptr(), r.nerr.as_mut_ptr(),

@@ -1,6 +1,7 @@
 """Checked Shamir reconstruction on the device: shamir_weights_kernel + shamir_interp_kernel against
 pvw_shamir_reconstruct_checked_host bit for bit on out, bad and col_bad, the host-buffer form (several staged pieces, hygiene),
-stream capture, a full-size sharing made by pvw_shamir_shares_device, and the protocol loop closed with every party checked.
+stream capture, a full-size sharing made by pvw_shamir_shares_device, more secrets than one launch holds, and the protocol loop
+closed with every party checked.
 torch is imported FIRST so both libraries share one HIP runtime.  Spawned case by case by tests/test_gpu_shamir_check.py; prints
 SHAMIR_CHECK_OK."""
 import ctypes as C
@@ -369,7 +370,29 @@ def loop():
     print("loop ok", flush=True)
 
 
-CASES = {f.__name__: f for f in (grid, far, buffers, pieces, capture, full, loop)}
+def launches():
+    """more secrets than one launch of shamir_interp_kernel holds (the grid's y dimension: 65535 groups of 4): S = 65535 * 4 + 5,
+    so the second launch has one full group and one partial one.  count = 3, degree = 1: random rows on lines, column 2 bent in
+    the first secret, on both sides of the launch boundary and in the last secret; both layouts == the host routine on out, bad
+    and col_bad"""
+    S, t, pm, idx = 65535 * 4 + 5, 1, P61, (0, 1, 2)
+    p = _params(8)
+    s = torch.cuda.Stream(device=DEV)
+    nrng = np.random.default_rng(8)
+    a = nrng.integers(0, pm, size=(2, S), dtype=np.uint64)
+    rows = np.stack([(a[0] + a[1] * np.uint64(i + 1)) % np.uint64(pm) for i in idx], axis=1)   # a0 + 3 a1 < 2^63
+    bent = (0, 262139, 262140, 262144)
+    for b in bent:
+        rows[b, 2] ^= np.uint64(1)
+    want = host_checked(idx, rows, t, pm)
+    assert np.array_equal(want[0], a[0]) and np.flatnonzero(want[1]).tolist() == list(bent) and want[2].tolist() == [0, 0, len(bent)]
+    for layout in ("secret_major", "party_major"):
+        assert laid_out(rows, layout)[1] == ((3, 1) if layout == "secret_major" else (1, S))
+        assert same(device_checked(p, idx, rows, t, pm, layout, s), want), layout
+    print("launches ok", flush=True)
+
+
+CASES = {f.__name__: f for f in (grid, far, buffers, pieces, capture, full, launches, loop)}
 
 if __name__ == "__main__":
     assert torch.cuda.is_available()
