@@ -29,7 +29,8 @@
  *     `encrypt` (src/crypto/encryption.rs:277-283): device tensors are
  *     read-only after load and every call takes a stream + workspace from a pool.
  *     The promise, as tests/test_gpu_concurrent_calls.py holds it: threads that share one context may overlap any of
- *     pvw_encrypt[_rs], pvw_encrypt_multi[_rs], pvw_deal_shares[_rs], pvw_shamir_shares, pvw_shamir_reconstruct_checked,
+ *     pvw_encrypt[_rs], pvw_encrypt_multi[_rs], pvw_deal_shares[_rs], pvw_shamir_shares, pvw_deal_shares_packed[_rs],
+ *     pvw_shamir_shares_packed (the concurrent calls of these: tests/test_gpu_shamir_packed.py), pvw_shamir_reconstruct_checked,
  *     pvw_shamir_reconstruct_corrected, pvw_shamir_evaluate_corrected (the concurrent calls of these two:
  *     tests/test_gpu_shamir_evaluate.py),
  *     pvw_decrypt_batch / _checked / _plain, pvw_decrypt_all / _checked / _plain, pvw_ct_sum, pvw_decrypt_sum_checked,
@@ -785,6 +786,63 @@ PVW_API int32_t pvw_shamir_evaluate_corrected(pvw_ctx* ctx, uint64_t plain_modul
                                               size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
                                               size_t point_stride, const uint64_t* targets, size_t num_targets, uint64_t* values,
                                               uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask);
+
+/* ---- Packed Shamir shares: several secrets in one polynomial and one ciphertext ---------------------------
+ * Franklin-Yung packing: `pack` = K >= 1 secrets per dealer sit at the points 0, -1, ..., -(K-1) of ONE polynomial, so S secrets
+ * take S / K ciphertexts, encrypts, decrypts and wire bytes, for K - 1 of threshold slack.  The reference has no sharing code:
+ * the contract is the library's own.  All arithmetic in Z_p, p = plain_modulus; degree = t >= 0 random coefficients:
+ *   f_d(x) = sum_{j<K} s_{d,j} L_j(x)  +  Z(x) (a_{d,1} + a_{d,2} x + ... + a_{d,t} x^(t-1))
+ *   L_j = the Lagrange basis polynomial of the point -j among 0, -1, ..., -(K-1);  Z(x) = x (x+1) ... (x+K-1)
+ *   shares[d][i] = f_d(i + 1) for the global party index i
+ * deg f_d <= t + K - 1; f_d(-j) = s_{d,j}; any t + K shares determine all K secrets, and with t >= 1 any t shares are
+ * independent of them.  a_{d,j} (j = 1..t) are exactly the draws of 8.9 (same key, stream id and rule); coeffs [D][t] replaces
+ * the draw.  secrets [D][K] are dealer-major, any word read mod p.  With K = 1 the polynomial is s_d + a_{d,1} x + ... + a_{d,t} x^t:
+ * every packed call with pack = 1 is bit-equal to the 8.9 call it extends.
+ * PVW_ERR_INVALID_PARAMETERS before any device work (after the checks of the pvw_encrypt_multi* call a deal extends): pack = 0,
+ * degree + pack > n, p composite or >= 2^62, p < n + pack (the points 1..n and p-K+1..p-1, 0 must be distinct; p > n when
+ * K = 1), num_dealers = 0, NULL arguments by the rules of 8.9 (seeds may be NULL iff coeffs is given or degree = 0).
+ * The way back: pvw_shamir_reconstruct_packed on the host, or pvw_shamir_evaluate_corrected* with polynomial degree t + K - 1:
+ * `out` is secret 0 and the target index p - 1 - j (the point -j) gives secret j. */
+/* the contract in plain C++ on the host cores (no GPU needed), all n columns: what the kernels are tested against */
+PVW_API int32_t pvw_shamir_shares_packed_host(const pvw_ctx* ctx, const uint64_t* secrets, size_t num_dealers, uint32_t pack,
+                                              uint32_t degree, uint64_t plain_modulus, const uint8_t* seeds, const uint64_t* coeffs,
+                                              uint64_t* shares_out);
+/* device pointers (seeds stays a HOST pointer), asynchronous on `stream`.  The public weights L_j(i + 1) and Z(i + 1) / (i + 1) are
+ * made on the device into the stream's workspace, sized by the call: under stream capture a call needs an earlier call on that
+ * stream outside capture with at least as many pack x columns words, otherwise PVW_ERR_INVALID_PARAMETERS and nothing enqueued.
+ * A captured call holds the address of that block: a later packed call on the same stream, outside capture, that needs MORE words
+ * replaces the block, and graphs captured before it must be captured again (as for the blocks of the checked and corrected
+ * reconstruction).  Size the stream for the largest pack first.
+ * Columns of a sharded context as 8.9. */
+PVW_API int32_t pvw_shamir_shares_packed_device(pvw_ctx* ctx, const uint64_t* d_secrets, size_t num_dealers, uint32_t pack,
+                                                uint32_t degree, uint64_t plain_modulus, const uint8_t* seeds, const uint64_t* d_coeffs,
+                                                uint64_t* d_shares, void* stream);
+/* host buffers (synchronous), staged in bounded pieces; the staged secrets, coefficients and shares are cleared before the call
+ * returns */
+PVW_API int32_t pvw_shamir_shares_packed(pvw_ctx* ctx, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                         uint64_t plain_modulus, const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out);
+/* Deal: pvw_deal_shares_packed*(secrets [D][pack], D, pack, degree, p, seeds, ...) == pvw_encrypt_multi*(shares, D, n, seeds, ...)
+ * bit for bit with shares = pvw_shamir_shares_packed_host(secrets, D, pack, degree, p, seeds, NULL): both representations, both
+ * sides of the dealer-count dispatch, sharded contexts.  Everything else as pvw_deal_shares*: the _rs forms leave c + D in the
+ * state, pvw_prepare(PVW_PREPARE_MFMA) covers the share scratch, and under stream capture the weights must have been sized as
+ * for pvw_shamir_shares_packed_device (the error of pvw_encrypt_multi_device otherwise, nothing enqueued). */
+PVW_API int32_t pvw_deal_shares_packed(pvw_ctx* ctx, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                       uint64_t plain_modulus, const uint8_t* seeds /*[D][32]*/, uint64_t* c1_out, uint64_t* c2_out,
+                                       uint32_t out_repr);
+PVW_API int32_t pvw_deal_shares_packed_device(pvw_ctx* ctx, const uint64_t* d_secrets, size_t num_dealers, uint32_t pack,
+                                              uint32_t degree, uint64_t plain_modulus, const uint8_t* seeds, uint64_t* d_c1,
+                                              uint64_t* d_c2, uint32_t out_repr, void* stream);
+PVW_API int32_t pvw_deal_shares_packed_rs(pvw_ctx* ctx, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                          uint64_t plain_modulus, void* st, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr);
+PVW_API int32_t pvw_deal_shares_packed_rs_device(pvw_ctx* ctx, const uint64_t* d_secrets, size_t num_dealers, uint32_t pack,
+                                                 uint32_t degree, uint64_t plain_modulus, void* st, uint64_t* d_c1, uint64_t* d_c2,
+                                                 uint32_t out_repr, void* stream);
+/* Reconstruction, host only (no GPU, no context), like pvw_shamir_reconstruct: out[r][j] = F_r(-j), j < pack, from the Lagrange
+ * weights of the points indices[i] + 1 at each of 0, -1, ..., -(pack-1), computed once.  shares [num_rows][count], out
+ * [num_rows][pack].  The rules of pvw_shamir_reconstruct, plus pack >= 1 and every index < p - pack.  count must be at least
+ * degree + pack for the result to be the secrets; the routine cannot know the degree and does not check. */
+PVW_API int32_t pvw_shamir_reconstruct_packed(uint64_t plain_modulus, uint32_t pack, const uint64_t* indices, const uint64_t* shares,
+                                              size_t count, size_t num_rows, uint64_t* out);
 
 /* decode_scalar_pvw_rns alone, on the device: noisy [D][L][l] power basis (host) -> out_u64 [D] */
 PVW_API int32_t pvw_decode(pvw_ctx* ctx, const uint64_t* noisy, size_t count, uint64_t* out_u64);

@@ -16,7 +16,8 @@ from .api import (DEC_LOSSY, DEC_NEGATIVE, DEC_WIDE_TRUNCATED, CheckedDecryption
                   decrypt_all_party_sums, decode_scalar_pvw_plain, decode_scalar_pvw_plain_host,
                   shamir_shares, deal_party_shares, shamir_reconstruct, shamir_reconstruct_checked,
                   shamir_reconstruct_corrected, shamir_evaluate_corrected, SHAMIR_UNDECODABLE, combine_ciphertexts, decrypt_party_combination,
-                  decrypt_all_party_combinations, shamir_lagrange_weights)
+                  decrypt_all_party_combinations, shamir_lagrange_weights, shamir_shares_packed, deal_party_shares_packed,
+                  shamir_reconstruct_packed, shamir_packed_secret_indices, shamir_reconstruct_packed_corrected)
 
 __all__ = [
     "PvwParametersBuilder", "PvwParameters", "PvwCrs", "SecretKey", "DeviceSecretKey", "DeviceRandomness", "Party", "GlobalPublicKey",
@@ -28,6 +29,8 @@ __all__ = [
     "decode_scalar_pvw_plain", "decode_scalar_pvw_plain_host",
     "aggregate_ciphertexts", "decrypt_party_sum", "decrypt_all_party_sums",
     "combine_ciphertexts", "decrypt_party_combination", "decrypt_all_party_combinations", "shamir_lagrange_weights",
+    "shamir_shares_packed", "deal_party_shares_packed", "shamir_reconstruct_packed", "shamir_packed_secret_indices",
+    "shamir_reconstruct_packed_corrected",
     "shamir_shares", "deal_party_shares", "shamir_reconstruct", "shamir_reconstruct_checked", "shamir_reconstruct_corrected", "shamir_evaluate_corrected", "SHAMIR_UNDECODABLE",
     "device_available", "REPR_POWER", "REPR_NTT",
 ]

@@ -145,6 +145,15 @@ _SIGNATURES = {
     "pvw_deal_shares_rs": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint64, _P, _P, _P, C.c_uint32],
     "pvw_deal_shares_rs_device": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint64, _P, _P, _P, C.c_uint32, _P],
     "pvw_shamir_reconstruct": [C.c_uint64, _P, _P, C.c_size_t, C.c_size_t, _P],
+    # packed sharing: the 8.9 calls with `pack` after num_dealers; reconstruct (p, pack, indices, shares, count, rows, out)
+    "pvw_shamir_shares_packed_host": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P],
+    "pvw_shamir_shares_packed_device": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P, _P],
+    "pvw_shamir_shares_packed": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P],
+    "pvw_deal_shares_packed": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P, C.c_uint32],
+    "pvw_deal_shares_packed_device": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P, C.c_uint32, _P],
+    "pvw_deal_shares_packed_rs": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P, C.c_uint32],
+    "pvw_deal_shares_packed_rs_device": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P, C.c_uint32, _P],
+    "pvw_shamir_reconstruct_packed": [C.c_uint64, C.c_uint32, _P, _P, C.c_size_t, C.c_size_t, _P],
     # checked reconstruction: (p, degree, indices, count, shares, S, secret_stride, point_stride, out, bad, col_bad)
     "pvw_shamir_reconstruct_checked_host": [C.c_uint64, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P],
     "pvw_shamir_reconstruct_checked_device": [_P, C.c_uint64, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P, _P],

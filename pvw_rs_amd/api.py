@@ -981,6 +981,95 @@ def shamir_evaluate_corrected(params: Optional[PvwParameters], indices: Sequence
     return values, [int(v) for v in out], nerr, col_err, err_mask
 
 
+def _secret_rows(secrets) -> np.ndarray:
+    """secrets [D][pack] as uint64 words"""
+    rows = [[int(v) & 0xFFFFFFFFFFFFFFFF for v in row] for row in secrets]
+    if not rows or not rows[0] or any(len(r) != len(rows[0]) for r in rows):
+        raise PvwError(15, "expected secrets [num_dealers][pack] with pack >= 1 values in every row")
+    return np.array(rows, dtype=np.uint64)
+
+
+def shamir_shares_packed(params: PvwParameters, secrets, degree: int, plain_modulus: int,
+                         seeds: Optional[Sequence[bytes]] = None, coeffs=None, host: bool = False) -> np.ndarray:
+    """EXTENSION: packed sharing.  secrets [D][K]: dealer d's K secrets sit at the points 0, -1, ..., -(K-1) of one
+    polynomial f_d = sum_j secrets[d][j] L_j + Z (a_{d,1} + ... + a_{d,degree} x^(degree-1)), Z = x (x+1) ... (x+K-1), and
+    shares[d][i] = f_d(i + 1) mod plain_modulus.  The a_{d,j} are the draws of shamir_shares, or coeffs [D][degree].  K = 1 is
+    shamir_shares.  On the device (pvw_shamir_shares_packed); host=True: the plain C++ restatement (no GPU).  A sharded context's
+    device call writes its own columns of the (D, n) result and leaves the others zero."""
+    se = _secret_rows(secrets)
+    D, K = se.shape
+    sd = _seeds(seeds, D) if seeds is not None else None
+    co = None
+    if coeffs is not None:
+        co = np.array([[int(v) & 0xFFFFFFFFFFFFFFFF for v in row] for row in coeffs], dtype=np.uint64).reshape(D, -1)
+        if co.shape[1] != int(degree):
+            raise PvwError(15, f"expected {int(degree)} coefficients per dealer, got {co.shape[1]}")
+    out = np.zeros((D, params.n), dtype=np.uint64)
+    params._call("pvw_shamir_shares_packed_host" if host else "pvw_shamir_shares_packed", _ptr(se), D, K, int(degree),
+                 int(plain_modulus), _ptr(sd), _ptr(co), _ptr(out))
+    return out
+
+
+def deal_party_shares_packed(secrets, degree: int, plain_modulus: int, global_pk: GlobalPublicKey,
+                             seeds: Optional[Sequence[bytes]] = None, randomness: Optional["DeviceRandomness"] = None,
+                             out_repr: int = REPR_NTT) -> List[PvwCiphertext]:
+    """EXTENSION: dealer d shares its K secrets secrets[d] in one polynomial and encrypts the shares, in one device
+    call (pvw_deal_shares_packed): what encrypt_many(shamir_shares_packed(..., seeds), global_pk, seeds) returns, one ciphertext
+    per K secrets, without the shares or the coefficients ever existing on the host.  seeds / randomness as deal_party_shares."""
+    p = global_pk.params
+    se = _secret_rows(secrets)
+    D, K = se.shape
+    c1 = np.zeros((D, p.k, p.L, p.l), dtype=np.uint64)
+    c2 = np.zeros((D, p.n, p.L, p.l), dtype=np.uint64)
+    if randomness is not None:
+        _check_state(p, randomness, seeds)
+        p._call("pvw_deal_shares_packed_rs", _ptr(se), D, K, int(degree), int(plain_modulus), randomness._h, _ptr(c1), _ptr(c2), out_repr)
+    else:
+        if seeds is None:
+            raise PvwError(1, "deal_party_shares_packed needs one 32-byte seed per dealer or a DeviceRandomness")
+        sd = _seeds(seeds, D)
+        p._call("pvw_deal_shares_packed", _ptr(se), D, K, int(degree), int(plain_modulus), _ptr(sd), _ptr(c1), _ptr(c2), out_repr)
+    return [PvwCiphertext(c1[d], c2[d], p, out_repr) for d in range(D)]
+
+
+def shamir_reconstruct_packed(indices: Sequence[int], shares, plain_modulus: int, pack: int) -> List[List[int]]:
+    """EXTENSION: the `pack` secrets of every row from the shares of the parties `indices` (at least degree + pack of
+    them), by Lagrange interpolation at 0, -1, ..., -(pack-1) on the host (pvw_shamir_reconstruct_packed; no GPU, no context).
+    shares: rows [num_rows][len(indices)] -> [num_rows][pack] ints."""
+    idx = _words(indices)
+    sh = np.array([[int(v) & 0xFFFFFFFFFFFFFFFF for v in row] for row in shares], dtype=np.uint64).reshape(len(shares), -1)
+    if sh.shape[1] != len(idx):
+        raise PvwError(15, f"expected {len(idx)} shares per row, got {sh.shape[1]}")
+    out = np.zeros((len(shares), max(int(pack), 0)), dtype=np.uint64)
+    L = _ffi.lib()
+    _check(L.pvw_shamir_reconstruct_packed(int(plain_modulus), int(pack), _ptr(idx), _ptr(sh), len(idx), len(shares), _ptr(out)), L)
+    return [[int(v) for v in row] for row in out]
+
+
+def shamir_packed_secret_indices(plain_modulus: int, pack: int) -> List[int]:
+    """EXTENSION: the `targets` of shamir_evaluate_corrected that give secrets 1 .. pack-1 of a packed sharing:
+    index p - 1 - j is the point -j.  (Secret 0 is the call's `out`.)"""
+    return [int(plain_modulus) - 1 - j for j in range(1, int(pack))]
+
+
+def shamir_reconstruct_packed_corrected(params: Optional[PvwParameters], indices: Sequence[int], shares, degree: int, plain_modulus: int,
+                                        pack: int, *, host: bool = False,
+                                        layout: str = "secret_major") -> Tuple[List[List[int]], np.ndarray, np.ndarray, np.ndarray]:
+    """EXTENSION (DESIGN 8.14): the secrets of a packed sharing although up to (len(indices) - degree - pack) // 2 shares of each
+    row are wrong: one shamir_evaluate_corrected call with polynomial degree `degree + pack - 1` and the targets
+    shamir_packed_secret_indices.  Returns (secrets [S][pack], nerr, col_err, err_mask): column 0 from `out`, the rest from
+    `values`; an undecodable row is all 0 with nerr = SHAMIR_UNDECODABLE.  pack = 1 has no targets and is
+    shamir_reconstruct_corrected."""
+    if int(pack) == 1:
+        out, nerr, col_err, err_mask = shamir_reconstruct_corrected(params, indices, shares, degree, plain_modulus, host=host, layout=layout)
+        return [[v] for v in out], nerr, col_err, err_mask
+    values, out, nerr, col_err, err_mask = shamir_evaluate_corrected(
+        params, indices, shares, int(degree) + int(pack) - 1, plain_modulus, shamir_packed_secret_indices(plain_modulus, pack),
+        host=host, layout=layout)
+    secrets = [[int(out[s])] + [int(v) for v in values[s]] for s in range(len(out))]
+    return secrets, nerr, col_err, err_mask
+
+
 def encrypt_broadcast(scalar: int, global_pk: GlobalPublicKey, seed: Optional[bytes] = None, **kw) -> PvwCiphertext:
     """encryption.rs:292-296."""
     return encrypt([scalar] * global_pk.params.n, global_pk, seed, **kw)

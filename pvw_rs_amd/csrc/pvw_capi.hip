@@ -150,6 +150,8 @@ struct Workspace {
   size_t shares_bytes = 0;
   u64* interp = nullptr;     // checked reconstruction: points | products | weight matrix (shamir_interp_words; grown by the call)
   size_t interp_bytes = 0;
+  u64* packw = nullptr;      // packed dealing: Lw | zt | w | 1/j! (shamir_packed_words; public, grown by the call)
+  size_t packw_bytes = 0;
   u64* correct = nullptr;    // corrected reconstruction: M | public matrices | syndromes | locators (CorrectLayout; grown by the call)
   size_t correct_bytes = 0;
   // helper stream + events (ws_aux): decode of chunk i under the MAC of chunk i+1, key uploads under key generation
@@ -632,6 +634,7 @@ static void ws_free(Workspace* w) {
   if (w->shares) hipMemset(w->shares, 0, w->shares_bytes);   // the last deal's shares, if its wipe did not run
   hipFree(w->shares);
   hipFree(w->interp);
+  hipFree(w->packw);
   if (w->correct) hipMemset(w->correct, 0, w->correct_bytes);   // M of the last call, if its wipe did not run
   hipFree(w->correct);
   for (hipEvent_t e : w->events) hipEventDestroy(e);
@@ -2159,6 +2162,78 @@ int32_t pvw_shamir_shares_host(const pvw_ctx* c, const uint64_t* secrets, size_t
   return PVW_OK;
 }
 
+// ------------------------------------------------------------------------ packed shares
+// K = pack secrets per dealer at the points 0, -1, ..., -(K-1):
+//   f_d(x) = sum_{j<K} s_{d,j} L_j(x) + Z(x) (a_{d,1} + a_{d,2} x + ... + a_{d,t} x^(t-1)),  Z(x) = x (x+1) ... (x+K-1)
+// The points 1..n and p-K+1..p-1, 0 must be distinct: p >= n + K.  With K = 1 every rule below is shamir_checks'.
+static int32_t shamir_packed_checks(const pvw_ctx* c, size_t D, uint32_t pack, uint32_t degree, u64 p) {
+  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no dealers");
+  if (pack == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "pack must be at least 1");
+  if (p < (u64)c->n + pack)
+    return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must be at least n + pack (evaluation points 1..n, secrets at 0..-(pack-1))");
+  PVW_TRY(shamir_modulus_check(p));
+  if ((u64)degree + pack > c->n) {
+    char buf[112];
+    snprintf(buf, sizeof buf, "degree %u with pack %u needs more than %u parties", degree, pack, c->n);
+    return fail(PVW_ERR_INVALID_PARAMETERS, buf);
+  }
+  return PVW_OK;
+}
+
+// the contract in plain C++ (no GPU): L_j(x) and Z(x) from the definition with one inversion per denominator, sequential
+// draws, Horner.  Writes all n columns, whatever the context's shard.
+int32_t pvw_shamir_shares_packed_host(const pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                      uint64_t plain_modulus, const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out) {
+  if (!c || !secrets || !shares_out || (degree && !seeds && !coeffs)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(shamir_packed_checks(c, num_dealers, pack, degree, plain_modulus));
+  const Mod m = shamir_mod(plain_modulus);
+  const u32 n = c->n, t = degree, K = pack;
+  // Lj[j * n + i] = L_j(i + 1) = prod_{m != j} (x + m) / (m - j), Z[i] = prod_m (x + m)
+  std::vector<u64> Lj((size_t)K * n), Z(n), inv(K), suf((size_t)K + 1);
+  for (u32 j = 0; j < K; ++j) {
+    u64 den = 1;
+    for (u32 mm = 0; mm < K; ++mm)
+      if (mm != j) den = mulmod(den, submod((u64)mm, (u64)j, m.q), m);
+    inv[j] = powmod(den, m.q - 2, m);
+  }
+  for (u32 i = 0; i < n; ++i) {
+    const u64 x = (u64)i + 1;
+    suf[K] = 1;                                                // suf[j] = prod_{m >= j}(x + m)
+    for (u32 j = K; j-- > 0;) suf[j] = mulmod(suf[j + 1], x + j, m);
+    Z[i] = suf[0];
+    u64 pre = 1;                                               // prod_{m < j}(x + m)
+    for (u32 j = 0; j < K; ++j) {
+      Lj[(size_t)j * n + i] = mulmod(mulmod(pre, suf[j + 1], m), inv[j], m);
+      pre = mulmod(pre, x + j, m);
+    }
+  }
+  std::vector<u64> a((size_t)t + K);                           // s_{d,0..K-1} | a_{d,1..t}
+  for (size_t d = 0; d < num_dealers; ++d) {
+    for (u32 j = 0; j < K; ++j) a[j] = reduce_word(secrets[d * K + j], m);
+    for (u32 j = 1; j <= t; ++j) {
+      if (coeffs) {
+        a[K + j - 1] = reduce_word(coeffs[d * t + (j - 1)], m);
+      } else {
+        ChaChaRng g;
+        g.init(make_key(seeds + d * 32), PVW_DOM_SHAMIR, j);
+        u64* o = &a[K + j - 1];
+        sample_residues_poly(g, 1, m.q, [o](u32, u64 v) { *o = v; });
+      }
+    }
+    for (u32 i = 0; i < n; ++i) {
+      const u64 x = (u64)i + 1;
+      u64 r = 0;                                               // a_1 + a_2 x + ... + a_t x^(t-1)
+      for (u32 j = t; j-- > 0;) r = addmod(mulmod(r, x, m), a[K + j], m.q);
+      u64 acc = mulmod(r, Z[i], m);
+      for (u32 j = 0; j < K; ++j) acc = addmod(acc, mulmod(a[j], Lj[(size_t)j * n + i], m), m.q);
+      shares_out[d * n + i] = acc;
+    }
+  }
+  volatile u64* va = a.data();                               // the coefficients are as secret as the secrets
+  for (size_t j = 0; j < a.size(); ++j) va[j] = 0;
+  return PVW_OK;
+}
+
 // The rules every reconstruction's indices and modulus obey: distinct indices, points x_i = indices[i] + 1 below p, p a prime
 // below 2^62.  The plain reconstruction (modulus_first) has always reported the modulus, then the range, then a duplicate; the
 // checked and corrected calls a duplicate, then the range, then the modulus.
@@ -2222,6 +2297,47 @@ int32_t pvw_shamir_lagrange_weights(uint64_t plain_modulus, const uint64_t* indi
   std::vector<u64> w;
   PVW_TRY(shamir_weights_at_zero(plain_modulus, indices, count, &m, &w));
   for (size_t i = 0; i < count; ++i) weights_out[i] = w[i] > m.q / 2 ? -(i64)(m.q - w[i]) : (i64)w[i];
+  return PVW_OK;
+}
+
+// The way back of a packed sharing: out[s][j] = F_s(-j), j < pack, for the polynomial F_s through the count
+// shares of row s; the Lagrange weights of the points indices[i] + 1 at each of 0, -1, ..., -(pack-1) once, then pack dot
+// products per row.  The rules of pvw_shamir_reconstruct, and every index below p - pack (a point may not be a secret's).
+int32_t pvw_shamir_reconstruct_packed(uint64_t plain_modulus, uint32_t pack, const uint64_t* indices, const uint64_t* shares, size_t count,
+                                      size_t num_rows, uint64_t* out) {
+  if (!indices || !shares || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (pack == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "pack must be at least 1");
+  if (count == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no shares to reconstruct from");
+  PVW_TRY(shamir_index_checks(plain_modulus, indices, count, true));
+  for (size_t i = 0; i < count; ++i)
+    if (plain_modulus < pack || indices[i] >= plain_modulus - pack)
+      return fail(PVW_ERR_INVALID_PARAMETERS, "party index out of range for plain_modulus and pack");
+  const Mod m = shamir_mod(plain_modulus);
+  // u_i = (prod_{k != i}(x_i - x_k))^-1; W[j][i] = u_i prod_{k != i}(z_j - x_k), z_j = -j
+  std::vector<u64> u(count), W((size_t)pack * count), suf(count + 1);
+  for (size_t i = 0; i < count; ++i) {
+    u64 den = 1;
+    for (size_t k = 0; k < count; ++k)
+      if (k != i) den = mulmod(den, submod(indices[i] + 1, indices[k] + 1, m.q), m);
+    u[i] = powmod(den, m.q - 2, m);
+  }
+  for (u32 j = 0; j < pack; ++j) {
+    const u64 z = j ? m.q - j : 0;
+    suf[count] = 1;                                            // suf[i] = prod_{k >= i}(z - x_k)
+    for (size_t i = count; i-- > 0;) suf[i] = mulmod(suf[i + 1], submod(z, indices[i] + 1, m.q), m);
+    u64 pre = 1;                                               // prod_{k < i}(z - x_k)
+    for (size_t i = 0; i < count; ++i) {
+      W[(size_t)j * count + i] = mulmod(mulmod(pre, suf[i + 1], m), u[i], m);
+      pre = mulmod(pre, submod(z, indices[i] + 1, m.q), m);
+    }
+  }
+  for (size_t r = 0; r < num_rows; ++r)
+    for (u32 j = 0; j < pack; ++j) {
+      u64 acc = 0;
+      for (size_t i = 0; i < count; ++i)
+        acc = addmod(acc, mulmod(reduce_word(shares[r * count + i], m), W[(size_t)j * count + i], m), m.q);
+      out[r * pack + j] = acc;
+    }
   return PVW_OK;
 }
 
@@ -2913,19 +3029,44 @@ int32_t pvw_shamir_evaluate_corrected(pvw_ctx* c, uint64_t plain_modulus, uint32
 
 // One call's Shamir sharing on the device (pvw_shamir_shares*, and pvw_deal_shares* through encrypt_multi_enqueue)
 struct ShamirDeal {
-  const u64* d_secrets;   // [D]
+  const u64* d_secrets;   // [D][words()]
   const u64* d_coeffs;    // [D][degree], or NULL: drawn from the dealers' keys
   u32 degree;
   Mod m;
+  u32 pack = 0;           // the packed entry points: secrets per dealer, >= 1, and the packed kernel runs; 0: the calls of 8.9
+  const u64* d_packw = nullptr;   // ... on the weights of the call (shamir_packed_prepare)
+  u32 words() const { return pack ? pack : 1; }   // secrets per dealer
   // the same deal starting i dealers further on
-  ShamirDeal from(size_t i) const { return ShamirDeal{d_secrets + i, d_coeffs ? d_coeffs + i * degree : nullptr, degree, m}; }
+  ShamirDeal from(size_t i) const {
+    ShamirDeal d = *this;
+    d.d_secrets = d_secrets + i * words();
+    d.d_coeffs = d_coeffs ? d_coeffs + i * degree : nullptr;
+    return d;
+  }
 };
+static size_t shamir_packed_bytes(const pvw_ctx* c, u32 pack) { return shamir_packed_words(pack, c->rowsB()) * 8; }
+// Under stream capture a packed call may not allocate: the stream's workspace must hold the weights of at least as many
+// pack x columns words already, which an earlier call on that stream outside capture leaves (grown_capture_check)
+static int32_t packed_capture_check(pvw_ctx* c, hipStream_t s, u32 pack) {
+  return grown_capture_check(c, s, &Workspace::packw_bytes, shamir_packed_bytes(c, pack),
+                             "multi-dealer encrypt under stream capture: run a packed call with at least this pack on this stream "
+                             "outside capture first (it sizes the weights), and call pvw_prepare(PVW_PREPARE_MFMA)");
+}
+// once per call: Lw and zt of (p, pack, party range) into the stream's workspace, made on the device (a captured call replays
+// without reading host memory); public
+static int32_t shamir_packed_prepare(pvw_ctx* c, Workspace* w, ShamirDeal* deal, hipStream_t s) {
+  PVW_TRY(ws_grow(&w->packw, &w->packw_bytes, shamir_packed_bytes(c, deal->pack), s, false));
+  ProfScope ps(c, "shamir_packed_weights", s);
+  PVW_HIP(launch_shamir_packed_weights(w->packw, deal->pack, c->party_lo, c->party_hi, deal->m, s));
+  deal->d_packw = w->packw;
+  return PVW_OK;
+}
 // the shares of dealers [0, D) into d_shares [D][n] (columns [party_lo, party_hi)), PVW_MAX_PROLOGUE_KEYS dealers per launch
 static int32_t shamir_enqueue(pvw_ctx* c, const ShamirDeal& deal, const DealerKeys& keys, size_t D, u64* d_shares, hipStream_t s) {
-  ProfScope ps(c, "shamir_eval", s);
+  ProfScope ps(c, deal.pack ? "shamir_eval_packed" : "shamir_eval", s);
   for (size_t d0 = 0; d0 < D; d0 += PVW_MAX_PROLOGUE_KEYS) {
     const ShamirDeal dd = deal.from(d0);
-    ShamirBatch b{};
+    ShamirPackedBatch b{};
     b.nd = (u32)((D - d0) < PVW_MAX_PROLOGUE_KEYS ? (D - d0) : PVW_MAX_PROLOGUE_KEYS);
     b.secrets = dd.d_secrets;
     b.coeffs = dd.d_coeffs;
@@ -2936,7 +3077,14 @@ static int32_t shamir_enqueue(pvw_ctx* c, const ShamirDeal& deal, const DealerKe
     b.party_hi = c->party_hi;
     b.m = deal.m;
     if (!b.coeffs && deal.degree) keys.from(d0).fill(b, b.nd);
-    PVW_HIP(launch_shamir_eval(b, s));
+    if (deal.pack) {
+      b.pack = deal.pack;
+      b.Lw = deal.d_packw;
+      b.zt = deal.d_packw + (size_t)deal.pack * c->rowsB();
+      PVW_HIP(launch_shamir_eval_packed(b, s));
+    } else {
+      PVW_HIP(launch_shamir_eval(b, s));
+    }
     memset(&b, 0, sizeof b);
   }
   return PVW_OK;
@@ -2952,24 +3100,25 @@ int32_t pvw_shamir_shares_device(pvw_ctx* c, const uint64_t* d_secrets, size_t n
   return shamir_enqueue(c, deal, DealerKeys::host(seeds), num_dealers, d_shares, call_stream(c, stream));
 }
 
-int32_t pvw_shamir_shares(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t degree, uint64_t plain_modulus,
-                          const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out) {
-  if (!c || !secrets || !shares_out || (degree && !seeds && !coeffs)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(shamir_checks(c, num_dealers, degree, plain_modulus));
+// host buffers: the dealers go up in pieces of `per` (secrets [pack] each, explicit coefficients), each piece's shares come down,
+// and the staging -- secrets, coefficients and shares alike -- is cleared when the call ends.  pack != 0 (8.14): the weights once, in front
+static int32_t shamir_shares_stage(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                   uint64_t plain_modulus, const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out) {
   PVW_TRY(ensure_device(c));
-  const size_t n = c->n, t = degree, rB = c->rowsB();
-  const size_t per = chunk_1gib((n + (coeffs ? t : 0) + 1) * 8, num_dealers);
+  const size_t n = c->n, t = degree, K = pack ? pack : 1, rB = c->rowsB();
+  const size_t per = chunk_1gib((n + (coeffs ? t : 0) + K) * 8, num_dealers);
   Scratch sc;
-  const size_t r_se = sc.add(per * 8), r_co = sc.add(coeffs ? per * t * 8 : 0), r_sh = sc.add(per * n * 8);
+  const size_t r_se = sc.add(per * K * 8), r_co = sc.add(coeffs ? per * t * 8 : 0), r_sh = sc.add(per * n * 8);
   return host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
     sc.secret(w, r_se, r_sh);                                  // secrets, coefficients and shares alike
     u64 *d_se = sc.at(r_se), *d_co = coeffs && t ? sc.at(r_co) : nullptr, *d_sh = sc.at(r_sh);
+    ShamirDeal deal{d_se, d_co, degree, shamir_mod(plain_modulus), pack};
+    if (pack) PVW_TRY(shamir_packed_prepare(c, w, &deal, w->stream));
     for (size_t d0 = 0; d0 < num_dealers; d0 += per) {
       const size_t cnt = (num_dealers - d0) < per ? (num_dealers - d0) : per;
-      PVW_HIP(hipMemcpyAsync(d_se, secrets + d0, cnt * 8, hipMemcpyHostToDevice, w->stream));
+      PVW_HIP(hipMemcpyAsync(d_se, secrets + d0 * K, cnt * K * 8, hipMemcpyHostToDevice, w->stream));
       if (d_co) PVW_HIP(hipMemcpyAsync(d_co, coeffs + d0 * t, cnt * t * 8, hipMemcpyHostToDevice, w->stream));
-      const ShamirDeal deal{d_se, d_co, degree, shamir_mod(plain_modulus)};
       PVW_TRY(shamir_enqueue(c, deal, DealerKeys::host(seeds).from(d0), cnt, d_sh, w->stream));
       // a sharded context writes its own columns only
       if (rB) PVW_HIP(hipMemcpy2DAsync(shares_out + d0 * n + c->party_lo, n * 8, d_sh + c->party_lo, n * 8, rB * 8, cnt,
@@ -2978,6 +3127,35 @@ int32_t pvw_shamir_shares(pvw_ctx* c, const uint64_t* secrets, size_t num_dealer
     }
     return PVW_OK;
   });
+}
+int32_t pvw_shamir_shares(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t degree, uint64_t plain_modulus,
+                          const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out) {
+  if (!c || !secrets || !shares_out || (degree && !seeds && !coeffs)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(shamir_checks(c, num_dealers, degree, plain_modulus));
+  return shamir_shares_stage(c, secrets, num_dealers, 0, degree, plain_modulus, seeds, coeffs, shares_out);
+}
+
+// The packed forms: secrets [D][pack]; the weights once per call, then the packed kernel per launch of dealers.
+int32_t pvw_shamir_shares_packed_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                        uint64_t plain_modulus, const uint8_t* seeds, const uint64_t* d_coeffs, uint64_t* d_shares,
+                                        void* stream) {
+  if (!c || !d_secrets || !d_shares || (degree && !seeds && !d_coeffs)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(shamir_packed_checks(c, num_dealers, pack, degree, plain_modulus));
+  // the caller's stream is checked before the context initialises its device (pvw_shamir_reconstruct_checked_device)
+  auto sized = [&](hipStream_t s) { return packed_capture_check(c, s, pack); };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
+    ShamirDeal deal{d_secrets, d_coeffs, degree, shamir_mod(plain_modulus), pack};
+    PVW_TRY(shamir_packed_prepare(c, w, &deal, s));
+    return shamir_enqueue(c, deal, DealerKeys::host(seeds), num_dealers, d_shares, s);
+  });
+}
+
+int32_t pvw_shamir_shares_packed(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                 uint64_t plain_modulus, const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out) {
+  if (!c || !secrets || !shares_out || (degree && !seeds && !coeffs)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(shamir_packed_checks(c, num_dealers, pack, degree, plain_modulus));
+  return shamir_shares_stage(c, secrets, num_dealers, pack, degree, plain_modulus, seeds, coeffs, shares_out);
 }
 
 // ------------------------------------------------------------------------ multi-dealer encrypt
@@ -3100,10 +3278,10 @@ static void deal_mark(Workspace* w, size_t D) {
 }
 
 // host buffers, staged in pieces of `per` dealers (<= ~512 MiB of ciphertext): each dealer's input -- its n scalars, or with
-// deal != NULL its one secret -- goes up, the piece is encrypted, and its rows go to their global positions
+// deal != NULL its `pack` secrets -- goes up, the piece is encrypted, and its rows go to their global positions
 static int32_t encrypt_multi_stage(pvw_ctx* c, const uint64_t* in, size_t D, const DealerKeys& keys, const ShamirDeal* deal,
                                    uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
-  const size_t P = c->poly(), rA = c->rowsA(), rB = c->rowsB(), n = c->n, in_words = deal ? 1 : n;
+  const size_t P = c->poly(), rA = c->rowsA(), rB = c->rowsB(), n = c->n, in_words = deal ? deal->words() : n;
   size_t per = stage_budget() / 2 / ((rA + rB) * P * 8 + in_words * 8);
   if (per < 4) per = 4;
   per &= ~(size_t)3;
@@ -3119,7 +3297,9 @@ static int32_t encrypt_multi_stage(pvw_ctx* c, const uint64_t* in, size_t D, con
       if (D % per) deal_mark(w, D % per);                          // count: a last pass of 1 or 2 leaves r-hat in the workspace
     }
     u64 *d_in = sc.at(r_in), *d_c1 = sc.at(r_c1), *d_c2 = sc.at(r_c2);
-    const ShamirDeal staged = deal ? ShamirDeal{d_in, nullptr, deal->degree, deal->m} : ShamirDeal{};   // the secrets of each piece
+    ShamirDeal staged = deal ? *deal : ShamirDeal{};                // the secrets of each piece
+    staged.d_secrets = d_in;
+    if (deal && deal->pack) PVW_TRY(shamir_packed_prepare(c, w, &staged, w->stream));
     for (size_t d0 = 0; d0 < D; d0 += per) {
       const size_t cnt = (D - d0) < per ? (D - d0) : per;
       PVW_HIP(hipMemcpyAsync(d_in, in + d0 * in_words, cnt * in_words * 8, hipMemcpyHostToDevice, w->stream));
@@ -3156,30 +3336,36 @@ static int32_t encrypt_multi_host(pvw_ctx* c, const uint64_t* scalars, size_t D,
 }
 // the deal on device pointers: encrypt_multi_enqueue with the shares made pass by pass in the workspace's share scratch, which
 // the call marks secret (cleared on the stream behind the call's last launch)
+// pack != NULL (pvw_deal_shares_packed*): secrets [D][*pack], the weights once per call and the packed kernel, whatever
+// *pack; under capture the caller's stream is checked before the context initialises its device, as pvw_shamir_shares_packed_device does
 static int32_t deal_device(pvw_ctx* c, const uint64_t* d_secrets, size_t D, uint32_t degree, uint64_t p, const DealerKeys& keys,
-                           uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
+                           uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream, const uint32_t* pack = nullptr) {
   if (!c || !d_secrets || keys.missing() || (!d_c1 && c->rowsA()) || (!d_c2 && c->rowsB())) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   PVW_TRY(encrypt_multi_checks(c, D, c->n, out_repr));
-  PVW_TRY(shamir_checks(c, D, degree, p));
-  const ShamirDeal deal{d_secrets, nullptr, degree, shamir_mod(p)};
+  PVW_TRY(pack ? shamir_packed_checks(c, D, *pack, degree, p) : shamir_checks(c, D, degree, p));
+  ShamirDeal deal{d_secrets, nullptr, degree, shamir_mod(p), pack ? *pack : 0};
+  if (pack && stream) PVW_TRY(packed_capture_check(c, (hipStream_t)stream, *pack));
   return device_call(c, stream, [&](hipStream_t s) -> int32_t {
                        PVW_TRY(keys.checks(c));
+                       if (pack) PVW_TRY(packed_capture_check(c, s, *pack));
                        return deal_capture_check(c, s, D);
                      },
                      [&](Workspace* w, hipStream_t s) -> int32_t {
                        PVW_TRY(ws_share_buffer(c, w));
                        deal_mark(w, D);
+                       if (pack) PVW_TRY(shamir_packed_prepare(c, w, &deal, s));
                        return encrypt_multi_enqueue(c, w, nullptr, keys, D, d_c1, d_c2, out_repr, s, &deal);
                      });
 }
 static int32_t deal_host(pvw_ctx* c, const uint64_t* secrets, size_t D, uint32_t degree, uint64_t p, const DealerKeys& keys,
-                         uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+                         uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr, const uint32_t* pack = nullptr) {
   if (!c || !secrets || keys.missing() || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   PVW_TRY(encrypt_multi_checks(c, D, c->n, out_repr));
-  PVW_TRY(shamir_checks(c, D, degree, p));
+  PVW_TRY(pack ? shamir_packed_checks(c, D, *pack, degree, p) : shamir_checks(c, D, degree, p));
   PVW_TRY(ensure_device(c));
   PVW_TRY(keys.checks(c));
-  const ShamirDeal deal{nullptr, nullptr, degree, shamir_mod(p)};   // the staging loop points it at each piece's secrets in turn
+  // the staging loop points it at each piece's secrets in turn, and makes the weights of a packed deal
+  const ShamirDeal deal{nullptr, nullptr, degree, shamir_mod(p), pack ? *pack : 0};
   return encrypt_multi_stage(c, secrets, D, keys, &deal, c1_out, c2_out, out_repr);
 }
 
@@ -3214,6 +3400,25 @@ int32_t pvw_deal_shares(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers,
 int32_t pvw_deal_shares_rs(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t degree, uint64_t plain_modulus,
                            void* handle, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
   return deal_host(c, secrets, num_dealers, degree, plain_modulus, DealerKeys::state(handle), c1_out, c2_out, out_repr);
+}
+
+int32_t pvw_deal_shares_packed_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                      uint64_t plain_modulus, const uint8_t* seeds, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr,
+                                      void* stream) {
+  return deal_device(c, d_secrets, num_dealers, degree, plain_modulus, DealerKeys::host(seeds), d_c1, d_c2, out_repr, stream, &pack);
+}
+int32_t pvw_deal_shares_packed_rs_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                         uint64_t plain_modulus, void* handle, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr,
+                                         void* stream) {
+  return deal_device(c, d_secrets, num_dealers, degree, plain_modulus, DealerKeys::state(handle), d_c1, d_c2, out_repr, stream, &pack);
+}
+int32_t pvw_deal_shares_packed(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                               uint64_t plain_modulus, const uint8_t* seeds, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+  return deal_host(c, secrets, num_dealers, degree, plain_modulus, DealerKeys::host(seeds), c1_out, c2_out, out_repr, &pack);
+}
+int32_t pvw_deal_shares_packed_rs(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                  uint64_t plain_modulus, void* handle, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+  return deal_host(c, secrets, num_dealers, degree, plain_modulus, DealerKeys::state(handle), c1_out, c2_out, out_repr, &pack);
 }
 
 // ------------------------------------------------------------------------ device randomness state

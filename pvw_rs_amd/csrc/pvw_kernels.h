@@ -245,6 +245,21 @@ struct ShamirBatch {
 };
 hipError_t launch_shamir_eval(const ShamirBatch& b, hipStream_t s);
 
+// ---- Packed Shamir shares (pvw_shamir.hip): `pack` = K secrets per dealer at the points 0, -1, ..., -(K-1),
+//   f_d(x) = sum_{j<K} secrets[d * K + j] L_j(x) + Z(x) (a_{d,1} + a_{d,2} x + ... + a_{d,t} x^(t-1)),  Z(x) = x (x+1) ... (x+K-1),
+// L_j the Lagrange basis polynomial of -j among those points; a_{d,j}, the keys and the columns as ShamirBatch.  K = 1 is the
+// polynomial of ShamirBatch.  The weights are public and made on the device from (p, K, party range) alone:
+// words: Lw [K][cols] | zt [cols] | w [K] | 1/j! [K], cols = party_hi - party_lo; Lw[j][i] = L_j(party_lo + i + 1),
+// zt[i] = prod_{m=1..K-1}(party_lo + i + 1 + m) = Z(x) / x.  m.q prime, party_hi + K - 1 < m.q < 2^62.
+inline size_t shamir_packed_words(size_t pack, size_t cols) { return (pack + 1) * cols + 2 * pack; }
+struct ShamirPackedBatch : ShamirBatch {   // secrets: [nd][pack]
+  u32 pack;
+  const u64* Lw;        // [pack][party_hi - party_lo]
+  const u64* zt;        // [party_hi - party_lo]
+};
+hipError_t launch_shamir_packed_weights(u64* ws, u32 pack, u32 party_lo, u32 party_hi, const Mod& m, hipStream_t s);
+hipError_t launch_shamir_eval_packed(const ShamirPackedBatch& b, hipStream_t s);
+
 // ---- Checked reconstruction (pvw_shamir.hip).  Columns 0..t of the share matrix are the basis, columns
 // t+1..count-1 the extras; T = count - t targets: target 0 is x = 0, target m >= 1 the point of column t + m.
 // Workspace words: x [count] | aux [count + 1] | W [t+1][T].  aux[j] = (prod_{i != j}(x_j - x_i))^-1 for j <= t and

@@ -736,4 +736,193 @@ hipError_t launch_shamir_evaluate_finish(const ShamirEvalFinish& f, hipStream_t 
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------ packed shares
+// K secrets per dealer at the points 0, -1, ..., -(K-1) (Franklin-Yung):
+//   f_d(x) = sum_{j<K} s_{d,j} L_j(x) + Z(x) (a_{d,1} + a_{d,2} x + ... + a_{d,t} x^(t-1)),  Z(x) = x (x+1) ... (x+K-1).
+// L_j(x) = w_j prod_{m != j}(x + m) with w_j = ((-1)^j j! (K-1-j)!)^-1: the denominators are factorials, so ONE inversion, of
+// (K-1)!, and a walk down give every 1/j!, and no element of Lw needs one.  x + m <= n + K - 1 < p is never 0.
+
+// one workgroup: thread 0 walks the factorials (2K multiplies and the inversion), then w[j] = (-1)^j / (j! (K-1-j)!)
+__global__ __launch_bounds__(256) void shamir_packed_basis_kernel(u64* w, u64* invf, u32 K, Mod m) {
+  if (threadIdx.x == 0) {
+    u64 f = 1;
+    for (u32 j = 2; j < K; ++j) f = mulmod(f, (u64)j, m);        // (K-1)!, K - 1 < p
+    u64 inv = invmod_dev(f, m);
+    for (u32 j = K - 1;; --j) {
+      invf[j] = inv;                                               // 1 / j!
+      if (j == 0) break;
+      inv = mulmod(inv, (u64)j, m);
+    }
+  }
+  __syncthreads();
+  for (u32 j = threadIdx.x; j < K; j += 256) {
+    const u64 v = mulmod(invf[j], invf[K - 1 - j], m);             // never 0
+    w[j] = (j & 1) ? m.q - v : v;
+  }
+}
+
+// one thread per column i (x = party_lo + i + 1), lanes store along the rows of Lw: a suffix pass leaves prod_{m>j}(x + m) in
+// Lw[j][i] (and Z(x) / x = prod_{m>=1}(x + m) in zt[i]), a prefix pass multiplies prod_{m<j}(x + m) and w_j in
+__global__ __launch_bounds__(256) void shamir_packed_weights_kernel(u64* Lw, u64* zt, const u64* w, u32 K, u32 party_lo, u32 cols,
+                                                                    Mod m) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= cols) return;
+  const u64 x = (u64)party_lo + i + 1;
+  u64 suf = 1;
+  for (u32 j = K; j-- > 0;) {
+    Lw[(size_t)j * cols + i] = suf;
+    suf = mulmod(suf, x + j, m);
+  }
+  zt[i] = Lw[i];                                                   // row 0: prod_{m=1..K-1}(x + m)
+  u64 pre = 1;
+  for (u32 j = 0; j < K; ++j) {
+    u64* e = Lw + (size_t)j * cols + i;
+    *e = mulmod(mulmod(*e, pre, m), w[j], m);
+    pre = mulmod(pre, x + j, m);
+  }
+}
+
+// ws: Lw [K][cols] | zt [cols] | w [K] | 1/j! [K] (shamir_packed_words)
+hipError_t launch_shamir_packed_weights(u64* ws, u32 pack, u32 party_lo, u32 party_hi, const Mod& m, hipStream_t s) {
+  if (pack == 0 || party_hi <= party_lo) return hipSuccess;
+  const u32 cols = party_hi - party_lo;
+  u64 *Lw = ws, *zt = Lw + (size_t)pack * cols, *w = zt + cols, *invf = w + pack;
+  shamir_packed_basis_kernel<<<dim3(1), dim3(256), 0, s>>>(w, invf, pack, m);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  shamir_packed_weights_kernel<<<dim3((cols + 255) / 256), dim3(256), 0, s>>>(Lw, zt, w, pack, party_lo, cols, m);
+  return hipGetLastError();
+}
+
+// The frame of shamir_eval_kernel over the term axis e = 0 .. K + t - 1: e < K is secret term e (coefficient s_{d,e}, weight
+// Lw[e][party], loaded, four in flight ahead of their multiply-adds as in shamir_tile_product), e >= K is random term
+// j = e - K + 1 (coefficient a_{d,j}, drawn or read in the staging phase exactly as shamir_eval_kernel does; weight
+// Z(x) x^(j-1) = zt(x) x^j, kept up to date by one modular multiply per term and started from x^(j0) zt(x) at the wave's first
+// random term).  With K = 1: Lw = zt = 1 and the sum is shamir_eval_kernel's, term for term.
+// grid: x = blocks of 64 parties of [party_lo, party_hi), y = groups of SH_DG dealers; 256 threads.
+__global__ __launch_bounds__(256) void shamir_eval_packed_kernel(ShamirPackedBatch b) {
+  __shared__ u64 coef[SH_WAVES][SH_JC][SH_DG];     // 8 KiB: the chunk's coefficients, below p
+  __shared__ u64 part[SH_WAVES][SH_DG][64];        // 8 KiB: the waves' partial sums, below p
+  __shared__ u32 keyw[SH_DG][8];
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const Mod m = b.m;
+  const u32 t = b.degree, K = b.pack, nt = K + t;
+  const u32 d0 = blockIdx.y * SH_DG;
+  const u32 col = blockIdx.x * 64 + lane;
+  const u32 cols = b.party_hi - b.party_lo;
+  const u32 party = b.party_lo + col;
+  const bool live = col < cols;
+  const bool drawn = b.coeffs == nullptr && t != 0;
+  const u32 sh = (u32)__clzll((long long)m.q);
+  if (drawn && tid < SH_DG && d0 + tid < b.nd) {
+    ChaChaKey k;
+    if (b.rnd) k = call_seed(b.rnd->seed, b.rnd->counter + b.rnd_off + d0 + tid);   // derived when the kernel runs
+    else k = b.key[d0 + tid];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) keyw[tid][i] = k.w[i];
+  }
+  // wave w owns terms e = w * Q + [0, Q), cut off at nt; every wave walks the same number of chunks (barriers)
+  const u32 Q = (nt + SH_WAVES - 1) / SH_WAVES;
+  const u32 ew0 = wave * Q;
+  const u32 ew1 = ew0 + Q < nt ? ew0 + Q : nt;     // the end of the wave's range (ew1 <= ew0: none)
+  const u32 nchunks = (Q + SH_JC - 1) / SH_JC;
+  const u64 x = live ? (u64)party + 1 : 1;         // x <= n < p
+  // the wave's first random term and its weight zt(x) x^j
+  const u32 er0 = ew0 > K ? ew0 : K;
+  u64 pw = 0;
+  if (er0 < ew1) pw = mulmod(powmod_dev(x, er0 - K + 1, m), live ? b.zt[col] : 0, m);
+  const u64* wcol = b.Lw + (live ? col : 0);
+  Acc acc[SH_DG];
+#pragma unroll
+  for (int g = 0; g < SH_DG; ++g) acc_zero(acc[g]);
+  __syncthreads();
+  for (u32 c = 0; c < nchunks; ++c) {
+    // ---- staging: entry e = (wave, term, dealer) of the chunk, one per lane and trip ----
+    for (u32 e = tid; e < SH_WAVES * SH_JC * SH_DG; e += 256) {
+      const u32 ew = e / (SH_JC * SH_DG), ej = (e / SH_DG) % SH_JC, eg = e % SH_DG;
+      const u32 off = c * SH_JC + ej;              // within the wave's range
+      const u32 te = ew * Q + off;                 // the term
+      u64 a = 0;
+      if (off < Q && te < nt && d0 + eg < b.nd) {
+        if (te < K) {
+          a = reduce_word(b.secrets[(size_t)(d0 + eg) * K + te], m);
+        } else if (drawn) {
+          ChaChaKey k;
+#pragma unroll
+          for (int i = 0; i < 8; ++i) k.w[i] = keyw[eg][i];
+          a = shamir_draw(k, te - K + 1, m.q, sh);
+        } else {
+          a = reduce_word(b.coeffs[(size_t)(d0 + eg) * t + (te - K)], m);
+        }
+      }
+      coef[ew][ej][eg] = a;
+    }
+    __syncthreads();
+    // ---- this wave's terms of the chunk: [e0, e1), the secret terms [e0, es) first ----
+    const u32 base = c * SH_JC;
+    const u32 e0 = ew0 + base;
+    u32 cnt = 0;
+    if (base < Q && e0 < ew1) {
+      cnt = Q - base < SH_JC ? Q - base : SH_JC;
+      cnt = ew1 - e0 < cnt ? ew1 - e0 : cnt;
+    }
+    const u32 ns = e0 < K ? (K - e0 < cnt ? K - e0 : cnt) : 0;
+    const u64* wp = wcol + (size_t)e0 * cols;
+    u32 jj = 0;
+    for (; jj + 4 <= ns; jj += 4) {                // four weights in flight ahead of their multiply-adds
+      u64 w[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) w[u] = live ? wp[(size_t)u * cols] : 0;
+      wp += (size_t)4 * cols;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        u64 a[SH_DG];
+#pragma unroll
+        for (int g = 0; g < SH_DG; ++g) a[g] = coef[wave][jj + u][g];
+#pragma unroll
+        for (int g = 0; g < SH_DG; ++g) acc_mac_dev(acc[g], a[g], w[u]);
+      }
+    }
+    for (; jj < ns; ++jj) {
+      const u64 w = live ? *wp : 0;
+      wp += cols;
+      u64 a[SH_DG];
+#pragma unroll
+      for (int g = 0; g < SH_DG; ++g) a[g] = coef[wave][jj][g];
+#pragma unroll
+      for (int g = 0; g < SH_DG; ++g) acc_mac_dev(acc[g], a[g], w);
+    }
+    for (; jj < cnt; ++jj) {
+      u64 a[SH_DG];
+#pragma unroll
+      for (int g = 0; g < SH_DG; ++g) a[g] = coef[wave][jj][g];
+#pragma unroll
+      for (int g = 0; g < SH_DG; ++g) acc_mac_dev(acc[g], a[g], pw);
+      pw = mulmod(pw, x, m);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int g = 0; g < SH_DG; ++g) part[wave][g][lane] = acc_reduce(acc[g], m);
+  __syncthreads();
+  // thread (g, lane) adds the four partial sums and stores dealer d0 + g's share of its party
+  {
+    const u32 g = wave;                            // SH_WAVES == SH_DG
+    const u32 d = d0 + g;
+    if (live && d < b.nd) {
+      u64 s = 0;
+#pragma unroll
+      for (int w = 0; w < SH_WAVES; ++w) s = addmod(s, part[w][g][lane], m.q);
+      b.shares[(size_t)d * b.row_stride + party] = s;
+    }
+  }
+}
+
+hipError_t launch_shamir_eval_packed(const ShamirPackedBatch& b, hipStream_t s) {
+  if (b.nd == 0 || b.party_hi <= b.party_lo) return hipSuccess;
+  const dim3 grid((b.party_hi - b.party_lo + 63) / 64, (b.nd + SH_DG - 1) / SH_DG);
+  shamir_eval_packed_kernel<<<grid, dim3(256), 0, s>>>(b);
+  return hipGetLastError();
+}
+
 }  // namespace pvw

@@ -744,6 +744,95 @@ inline EvaluatedShares shamir_evaluate_corrected(const std::shared_ptr<PvwParame
   return r;
 }
 
+// ---- packed sharing ----
+// secrets [D][pack] row-major: dealer d's `pack` secrets sit at the points 0, -1, ..., -(pack-1) of one polynomial with `degree`
+// random coefficients (drawn as shamir_shares draws them, or coeffs [D][degree]); shares (D, n) row-major.  pack = 1 is
+// shamir_shares.  On the device (pvw_shamir_shares_packed); host = true: the plain C++ restatement (no GPU).
+inline std::vector<uint64_t> shamir_shares_packed(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& secrets,
+                                                  uint32_t pack, uint32_t degree, uint64_t plain_modulus, const std::vector<Seed>& seeds,
+                                                  const std::vector<uint64_t>& coeffs = {}, bool host = false) {
+  if (pack == 0 || secrets.size() % pack) throw PvwError(15, "pack secrets per dealer");
+  const size_t D = secrets.size() / pack;
+  if (!seeds.empty() && seeds.size() != D) throw PvwError(15, "one seed per dealer");
+  if (!coeffs.empty() && coeffs.size() != D * degree) throw PvwError(15, "degree coefficients per dealer");
+  std::vector<uint8_t> sd(seeds.size() * 32);
+  for (size_t d = 0; d < seeds.size(); ++d) std::copy(seeds[d].begin(), seeds[d].end(), sd.begin() + d * 32);
+  std::vector<uint64_t> out(D * p->n);
+  const uint8_t* sdp = sd.empty() ? nullptr : sd.data();
+  const uint64_t* cop = coeffs.empty() ? nullptr : coeffs.data();
+  check(host ? pvw_shamir_shares_packed_host(p->ctx, secrets.data(), D, pack, degree, plain_modulus, sdp, cop, out.data())
+             : pvw_shamir_shares_packed(p->ctx, secrets.data(), D, pack, degree, plain_modulus, sdp, cop, out.data()));
+  return out;
+}
+// dealer d shares its `pack` secrets and encrypts the shares in ONE device call (pvw_deal_shares_packed): one ciphertext per
+// `pack` secrets
+inline std::vector<PvwCiphertext> deal_party_shares_packed(const std::vector<uint64_t>& secrets, uint32_t pack, uint32_t degree,
+                                                           uint64_t plain_modulus, const GlobalPublicKey& gpk,
+                                                           const std::vector<Seed>& seeds, uint32_t out_repr = PVW_REPR_NTT) {
+  if (pack == 0 || secrets.size() % pack) throw PvwError(15, "pack secrets per dealer");
+  const auto& p = gpk.params;
+  const size_t D = secrets.size() / pack, P = p->poly_words();
+  if (seeds.size() != D) throw PvwError(15, "one seed per dealer");
+  std::vector<uint8_t> sd(D * 32);
+  for (size_t d = 0; d < D; ++d) std::copy(seeds[d].begin(), seeds[d].end(), sd.begin() + d * 32);
+  std::vector<uint64_t> c1(D * p->k * P), c2(D * p->n * P);
+  check(pvw_deal_shares_packed(p->ctx, secrets.data(), D, pack, degree, plain_modulus, sd.data(), c1.data(), c2.data(), out_repr));
+  return deal_ciphertexts(p, c1, c2, D, out_repr);
+}
+// ... with dealer d's randomness (polynomial and encryption) from call_seed(S, c + d) of a DeviceRandomness
+inline std::vector<PvwCiphertext> deal_party_shares_packed(const std::vector<uint64_t>& secrets, uint32_t pack, uint32_t degree,
+                                                           uint64_t plain_modulus, const GlobalPublicKey& gpk, DeviceRandomness& rnd,
+                                                           uint32_t out_repr = PVW_REPR_NTT) {
+  if (pack == 0 || secrets.size() % pack) throw PvwError(15, "pack secrets per dealer");
+  const auto& p = gpk.params;
+  const size_t D = secrets.size() / pack, P = p->poly_words();
+  std::vector<uint64_t> c1(D * p->k * P), c2(D * p->n * P);
+  check(pvw_deal_shares_packed_rs(p->ctx, secrets.data(), D, pack, degree, plain_modulus, rnd.raw(), c1.data(), c2.data(), out_repr));
+  return deal_ciphertexts(p, c1, c2, D, out_repr);
+}
+// the `pack` secrets of every row, [rows][pack], from the shares [rows][indices.size()] of the parties `indices` (at least
+// degree + pack of them); host only (pvw_shamir_reconstruct_packed)
+inline std::vector<uint64_t> shamir_reconstruct_packed(const std::vector<uint64_t>& indices, const std::vector<uint64_t>& shares,
+                                                       uint64_t plain_modulus, uint32_t pack) {
+  if (indices.empty() || shares.size() % indices.size()) throw PvwError(15, "shares must hold one value per index and row");
+  const size_t rows = shares.size() / indices.size();
+  std::vector<uint64_t> out(rows * pack);
+  check(pvw_shamir_reconstruct_packed(plain_modulus, pack, indices.data(), shares.data(), indices.size(), rows, out.data()));
+  return out;
+}
+// the targets of shamir_evaluate_corrected that give secrets 1 .. pack-1: index p - 1 - j is the point -j
+inline std::vector<uint64_t> shamir_packed_secret_indices(uint64_t plain_modulus, uint32_t pack) {
+  std::vector<uint64_t> t;
+  for (uint32_t j = 1; j < pack; ++j) t.push_back(plain_modulus - 1 - j);
+  return t;
+}
+struct PackedSecrets {
+  std::vector<uint64_t> secrets;    // [rows][pack]; a 0 row: undecodable
+  CorrectedSecrets decode;          // what shamir_reconstruct_corrected reports for the rows (its secrets: column 0)
+};
+// the secrets of a packed sharing although up to (indices.size() - degree - pack) / 2 shares of each row are wrong: one
+// shamir_evaluate_corrected call with polynomial degree degree + pack - 1 and the targets above (pack = 1 has none and is
+// shamir_reconstruct_corrected)
+inline PackedSecrets shamir_reconstruct_packed_corrected(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& indices,
+                                                         const std::vector<uint64_t>& shares, uint32_t degree, uint64_t plain_modulus,
+                                                         uint32_t pack, bool host = false, bool party_major = false) {
+  if (pack == 0) throw PvwError(1, "pack must be at least 1");
+  if (pack == 1) {
+    CorrectedSecrets d = shamir_reconstruct_corrected(p, indices, shares, degree, plain_modulus, host, party_major);
+    std::vector<uint64_t> secrets = d.secrets;
+    return PackedSecrets{std::move(secrets), std::move(d)};
+  }
+  EvaluatedShares e = shamir_evaluate_corrected(p, indices, shares, degree + pack - 1, plain_modulus,
+                                                shamir_packed_secret_indices(plain_modulus, pack), host, party_major);
+  const size_t S = e.decode.secrets.size(), K = pack;
+  PackedSecrets r{std::vector<uint64_t>(S * K), std::move(e.decode)};
+  for (size_t s = 0; s < S; ++s) {
+    r.secrets[s * K] = r.decode.secrets[s];
+    for (size_t j = 1; j < K; ++j) r.secrets[s * K + j] = e.values[s * (K - 1) + (j - 1)];
+  }
+  return r;
+}
+
 // the sum of the valid dealers' ciphertexts (pvw_ct_sum): same parameters and representation, no key needed
 inline PvwCiphertext aggregate_ciphertexts(const std::vector<PvwCiphertext>& cts, const std::vector<bool>& valid = {}) {
   const SumInputs in = sum_inputs(cts, valid);

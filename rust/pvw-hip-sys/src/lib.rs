@@ -158,6 +158,15 @@ extern "C" {
     pub fn pvw_deal_shares_rs(ctx: *mut PvwCtx, secrets: *const u64, num_dealers: usize, degree: u32, plain_modulus: u64, st: *mut c_void, c1_out: *mut u64, c2_out: *mut u64, out_repr: u32) -> i32;
     pub fn pvw_deal_shares_rs_device(ctx: *mut PvwCtx, d_secrets: *const u64, num_dealers: usize, degree: u32, plain_modulus: u64, st: *mut c_void, d_c1: *mut u64, d_c2: *mut u64, out_repr: u32, stream: *mut c_void) -> i32;
     pub fn pvw_shamir_reconstruct(plain_modulus: u64, indices: *const u64, shares: *const u64, count: usize, num_secrets: usize, out: *mut u64) -> i32;
+    // ---- packed sharing ------------------------------------------------------------
+    pub fn pvw_shamir_shares_packed_host(ctx: *const PvwCtx, secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: u64, seeds: *const u8, coeffs: *const u64, shares_out: *mut u64) -> i32;
+    pub fn pvw_shamir_shares_packed_device(ctx: *mut PvwCtx, d_secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: u64, seeds: *const u8, d_coeffs: *const u64, d_shares: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_shares_packed(ctx: *mut PvwCtx, secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: u64, seeds: *const u8, coeffs: *const u64, shares_out: *mut u64) -> i32;
+    pub fn pvw_deal_shares_packed(ctx: *mut PvwCtx, secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: u64, seeds: *const u8, c1_out: *mut u64, c2_out: *mut u64, out_repr: u32) -> i32;
+    pub fn pvw_deal_shares_packed_device(ctx: *mut PvwCtx, d_secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: u64, seeds: *const u8, d_c1: *mut u64, d_c2: *mut u64, out_repr: u32, stream: *mut c_void) -> i32;
+    pub fn pvw_deal_shares_packed_rs(ctx: *mut PvwCtx, secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: u64, st: *mut c_void, c1_out: *mut u64, c2_out: *mut u64, out_repr: u32) -> i32;
+    pub fn pvw_deal_shares_packed_rs_device(ctx: *mut PvwCtx, d_secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: u64, st: *mut c_void, d_c1: *mut u64, d_c2: *mut u64, out_repr: u32, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_reconstruct_packed(plain_modulus: u64, pack: u32, indices: *const u64, shares: *const u64, count: usize, num_rows: usize, out: *mut u64) -> i32;
     // ---- checked reconstruction --------------------------------------------------
     pub fn pvw_shamir_reconstruct_checked_host(plain_modulus: u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, out: *mut u64, bad: *mut u32, col_bad: *mut u32) -> i32;
     pub fn pvw_shamir_reconstruct_checked_device(ctx: *mut PvwCtx, plain_modulus: u64, degree: u32, indices: *const u64, count: usize, d_shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, d_out: *mut u64, d_bad: *mut u32, d_col_bad: *mut u32, stream: *mut c_void) -> i32;

@@ -461,6 +461,105 @@ pub fn deal_party_shares_with(secrets: &[u64], degree: u32, plain_modulus: u64, 
         .collect()
 }
 
+/// EXTENSION: packed dealing.  `secrets` is `[dealers][pack]` row-major: dealer d's `pack` secrets sit at the
+/// points 0, -1, ..., -(pack-1) of ONE polynomial with `degree` random coefficients, so `pack` secrets cost one ciphertext
+/// (`pvw_deal_shares_packed`).  `pack = 1` is `deal_party_shares`.  Seeds as there.
+pub fn deal_party_shares_packed(secrets: &[u64], pack: u32, degree: u32, plain_modulus: u64, global_pk: &GlobalPublicKey) -> Result<Vec<PvwCiphertext>> {
+    if pack == 0 || secrets.len() % pack as usize != 0 {
+        return Err(PvwError::InvalidParameters("secrets must hold pack values per dealer".into()));
+    }
+    let params = &global_pk.params;
+    let (n, dealers) = (params.n, secrets.len() / pack as usize);
+    let words = poly_words(params);
+    let mut seeds = vec![0u8; 32 * dealers];
+    rand::thread_rng().fill_bytes(&mut seeds);
+    let (mut c1, mut c2) = (vec![0u64; dealers * params.k * words], vec![0u64; dealers * n * words]);
+    let rc = unsafe {
+        sys::pvw_deal_shares_packed(params.hip.raw(), secrets.as_ptr(), dealers, pack, degree, plain_modulus, seeds.as_ptr(), c1.as_mut_ptr(),
+                                    c2.as_mut_ptr(), sys::PVW_REPR_POWER)
+    };
+    seeds.zeroize();
+    check(rc)?;
+    (0..dealers)
+        .map(|d| ciphertext_from_flat(&c1[d * params.k * words..(d + 1) * params.k * words], &c2[d * n * words..(d + 1) * n * words], params))
+        .collect()
+}
+
+/// `deal_party_shares_packed` with dealer d's randomness drawn from a `DeviceRandomness` (`call_seed(S, c + d)`).
+pub fn deal_party_shares_packed_with(secrets: &[u64], pack: u32, degree: u32, plain_modulus: u64, global_pk: &GlobalPublicKey,
+                                     rnd: &DeviceRandomness) -> Result<Vec<PvwCiphertext>> {
+    if pack == 0 || secrets.len() % pack as usize != 0 {
+        return Err(PvwError::InvalidParameters("secrets must hold pack values per dealer".into()));
+    }
+    let params = &global_pk.params;
+    let (n, dealers) = (params.n, secrets.len() / pack as usize);
+    let words = poly_words(params);
+    let (mut c1, mut c2) = (vec![0u64; dealers * params.k * words], vec![0u64; dealers * n * words]);
+    check(unsafe {
+        sys::pvw_deal_shares_packed_rs(params.hip.raw(), secrets.as_ptr(), dealers, pack, degree, plain_modulus, rnd.raw(), c1.as_mut_ptr(),
+                                       c2.as_mut_ptr(), sys::PVW_REPR_POWER)
+    })?;
+    (0..dealers)
+        .map(|d| ciphertext_from_flat(&c1[d * params.k * words..(d + 1) * params.k * words], &c2[d * n * words..(d + 1) * n * words], params))
+        .collect()
+}
+
+/// EXTENSION: the packed shares themselves, `[dealers][n]` row-major (`pvw_shamir_shares_packed`).
+pub fn shamir_shares_packed(params: &Arc<PvwParameters>, secrets: &[u64], pack: u32, degree: u32, plain_modulus: u64, seeds: Option<&[u8]>,
+                            coeffs: Option<&[u64]>) -> Result<Vec<u64>> {
+    if pack == 0 || secrets.len() % pack as usize != 0 {
+        return Err(PvwError::InvalidParameters("secrets must hold pack values per dealer".into()));
+    }
+    let dealers = secrets.len() / pack as usize;
+    let mut out = vec![0u64; dealers * params.n];
+    check(unsafe {
+        sys::pvw_shamir_shares_packed(params.hip.raw(), secrets.as_ptr(), dealers, pack, degree, plain_modulus,
+                                      seeds.map_or(std::ptr::null(), |s| s.as_ptr()), coeffs.map_or(std::ptr::null(), |c| c.as_ptr()), out.as_mut_ptr())
+    })?;
+    Ok(out)
+}
+
+/// EXTENSION: the `pack` secrets of every row, `[rows][pack]` row-major, from the shares `[rows][indices.len()]`
+/// of the parties `indices` (at least degree + pack of them).  Host only (`pvw_shamir_reconstruct_packed`).
+pub fn shamir_reconstruct_packed(indices: &[u64], shares: &[u64], plain_modulus: u64, pack: u32) -> Result<Vec<u64>> {
+    if indices.is_empty() || shares.len() % indices.len() != 0 {
+        return Err(PvwError::InvalidParameters("shares must hold one value per index and row".into()));
+    }
+    let rows = shares.len() / indices.len();
+    let mut out = vec![0u64; rows * pack as usize];
+    check(unsafe { sys::pvw_shamir_reconstruct_packed(plain_modulus, pack, indices.as_ptr(), shares.as_ptr(), indices.len(), rows, out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// The `targets` of `shamir_evaluate_corrected` that give secrets 1 .. pack-1 of a packed sharing: index p - 1 - j is the point -j.
+pub fn shamir_packed_secret_indices(plain_modulus: u64, pack: u32) -> Vec<u64> {
+    (1..pack as u64).map(|j| plain_modulus - 1 - j).collect()
+}
+
+/// EXTENSION: the secrets of a packed sharing, `[rows][pack]` row-major, although up to
+/// `(indices.len() - degree - pack) / 2` shares of each row are wrong: one `shamir_evaluate_corrected` call with polynomial
+/// degree `degree + pack - 1`.  Column 0 comes from the call's secrets, the rest from its values; an undecodable row is all 0.
+/// `pack = 1` has no targets and is `shamir_reconstruct_corrected`.
+pub fn shamir_reconstruct_packed_corrected(params: &Arc<PvwParameters>, indices: &[u64], shares: &[u64], degree: u32, plain_modulus: u64, pack: u32,
+                                           party_major: bool) -> Result<(Vec<u64>, CorrectedSecrets)> {
+    if pack == 0 {
+        return Err(PvwError::InvalidParameters("pack must be at least 1".into()));
+    }
+    if pack == 1 {
+        let r = shamir_reconstruct_corrected(params, indices, shares, degree, plain_modulus, party_major)?;
+        return Ok((r.secrets.clone(), r));
+    }
+    let targets = shamir_packed_secret_indices(plain_modulus, pack);
+    let (values, r) = shamir_evaluate_corrected(params, indices, shares, degree + pack - 1, plain_modulus, &targets, party_major)?;
+    let k = pack as usize;
+    let mut secrets = vec![0u64; r.secrets.len() * k];
+    for s in 0..r.secrets.len() {
+        secrets[s * k] = r.secrets[s];
+        secrets[s * k + 1..(s + 1) * k].copy_from_slice(&values[s * (k - 1)..(s + 1) * (k - 1)]);
+    }
+    Ok((secrets, r))
+}
+
 /// EXTENSION: the shares themselves, `[dealers][n]` row-major, made on the device (`pvw_shamir_shares`) from
 /// one 32-byte seed per dealer, or from explicit coefficients `[dealers][degree]`.
 pub fn shamir_shares(params: &Arc<PvwParameters>, secrets: &[u64], degree: u32, plain_modulus: u64, seeds: Option<&[u8]>, coeffs: Option<&[u64]>) -> Result<Vec<u64>> {
