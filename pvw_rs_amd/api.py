@@ -840,13 +840,9 @@ def _seeds(seeds, D: int) -> np.ndarray:
     return np.concatenate([_seed(s) for s in seeds])
 
 
-def shamir_shares(params: PvwParameters, secrets: Sequence[int], degree: int, plain_modulus: int,
-                  seeds: Optional[Sequence[bytes]] = None, coeffs=None, host: bool = False) -> np.ndarray:
-    """EXTENSION (DESIGN 8.9): shares[d][i] = f_d(i + 1) mod plain_modulus, f_d = secrets[d] + a_{d,1} x + ... of `degree`;
-    the a_{d,j} are drawn from dealer d's 32-byte seed (stream (DOM_SHAMIR << 32) | j) or given as coeffs [D][degree].
-    On the device (pvw_shamir_shares); host=True: the plain C++ restatement (pvw_shamir_shares_host, no GPU).  A sharded
-    context's device call writes its own columns of the (D, n) result and leaves the others zero."""
-    se = _words(secrets)
+def _shamir_shares(params: PvwParameters, se: np.ndarray, pack: tuple, degree: int, plain_modulus: int, seeds, coeffs,
+                   host: bool) -> np.ndarray:
+    """shamir_shares (se [D], pack = ()) and shamir_shares_packed (se [D][K], pack = (K,)): pvw_shamir_shares[_packed][_host]"""
     D = len(se)
     sd = _seeds(seeds, D) if seeds is not None else None
     co = None
@@ -855,9 +851,37 @@ def shamir_shares(params: PvwParameters, secrets: Sequence[int], degree: int, pl
         if co.shape[1] != int(degree):
             raise PvwError(15, f"expected {int(degree)} coefficients per dealer, got {co.shape[1]}")
     out = np.zeros((D, params.n), dtype=np.uint64)
-    params._call("pvw_shamir_shares_host" if host else "pvw_shamir_shares", _ptr(se), D, int(degree), int(plain_modulus),
-                 _ptr(sd), _ptr(co), _ptr(out))
+    params._call("pvw_shamir_shares" + ("_packed" if pack else "") + ("_host" if host else ""), _ptr(se), D, *pack, int(degree),
+                 int(plain_modulus), _ptr(sd), _ptr(co), _ptr(out))
     return out
+
+
+def _deal_party_shares(se: np.ndarray, pack: tuple, degree: int, plain_modulus: int, global_pk: GlobalPublicKey, seeds, randomness,
+                       out_repr: int) -> List[PvwCiphertext]:
+    """deal_party_shares (se [D], pack = ()) and deal_party_shares_packed (se [D][K], pack = (K,)): pvw_deal_shares[_packed][_rs]"""
+    p = global_pk.params
+    D = len(se)
+    name = "deal_shares_packed" if pack else "deal_shares"
+    c1 = np.zeros((D, p.k, p.L, p.l), dtype=np.uint64)
+    c2 = np.zeros((D, p.n, p.L, p.l), dtype=np.uint64)
+    if randomness is not None:
+        _check_state(p, randomness, seeds)
+        p._call(f"pvw_{name}_rs", _ptr(se), D, *pack, int(degree), int(plain_modulus), randomness._h, _ptr(c1), _ptr(c2), out_repr)
+    else:
+        if seeds is None:
+            raise PvwError(1, f"{name.replace('deal', 'deal_party')} needs one 32-byte seed per dealer or a DeviceRandomness")
+        sd = _seeds(seeds, D)
+        p._call(f"pvw_{name}", _ptr(se), D, *pack, int(degree), int(plain_modulus), _ptr(sd), _ptr(c1), _ptr(c2), out_repr)
+    return [PvwCiphertext(c1[d], c2[d], p, out_repr) for d in range(D)]
+
+
+def shamir_shares(params: PvwParameters, secrets: Sequence[int], degree: int, plain_modulus: int,
+                  seeds: Optional[Sequence[bytes]] = None, coeffs=None, host: bool = False) -> np.ndarray:
+    """EXTENSION (DESIGN 8.9): shares[d][i] = f_d(i + 1) mod plain_modulus, f_d = secrets[d] + a_{d,1} x + ... of `degree`;
+    the a_{d,j} are drawn from dealer d's 32-byte seed (stream (DOM_SHAMIR << 32) | j) or given as coeffs [D][degree].
+    On the device (pvw_shamir_shares); host=True: the plain C++ restatement (pvw_shamir_shares_host, no GPU).  A sharded
+    context's device call writes its own columns of the (D, n) result and leaves the others zero."""
+    return _shamir_shares(params, _words(secrets), (), degree, plain_modulus, seeds, coeffs, host)
 
 
 def deal_party_shares(secrets: Sequence[int], degree: int, plain_modulus: int, global_pk: GlobalPublicKey,
@@ -867,20 +891,7 @@ def deal_party_shares(secrets: Sequence[int], degree: int, plain_modulus: int, g
     (pvw_deal_shares): what encrypt_many(shamir_shares(..., seeds), global_pk, seeds) returns, without the shares or the
     polynomial coefficients ever existing on the host.  `randomness` instead of `seeds`: dealer d uses call_seed(S, c + d)
     of that DeviceRandomness, which then holds c + D."""
-    p = global_pk.params
-    se = _words(secrets)
-    D = len(se)
-    c1 = np.zeros((D, p.k, p.L, p.l), dtype=np.uint64)
-    c2 = np.zeros((D, p.n, p.L, p.l), dtype=np.uint64)
-    if randomness is not None:
-        _check_state(p, randomness, seeds)
-        p._call("pvw_deal_shares_rs", _ptr(se), D, int(degree), int(plain_modulus), randomness._h, _ptr(c1), _ptr(c2), out_repr)
-    else:
-        if seeds is None:
-            raise PvwError(1, "deal_party_shares needs one 32-byte seed per dealer or a DeviceRandomness")
-        sd = _seeds(seeds, D)
-        p._call("pvw_deal_shares", _ptr(se), D, int(degree), int(plain_modulus), _ptr(sd), _ptr(c1), _ptr(c2), out_repr)
-    return [PvwCiphertext(c1[d], c2[d], p, out_repr) for d in range(D)]
+    return _deal_party_shares(_words(secrets), (), degree, plain_modulus, global_pk, seeds, randomness, out_repr)
 
 
 def shamir_reconstruct(indices: Sequence[int], shares, plain_modulus: int):
@@ -997,17 +1008,7 @@ def shamir_shares_packed(params: PvwParameters, secrets, degree: int, plain_modu
     shamir_shares.  On the device (pvw_shamir_shares_packed); host=True: the plain C++ restatement (no GPU).  A sharded context's
     device call writes its own columns of the (D, n) result and leaves the others zero."""
     se = _secret_rows(secrets)
-    D, K = se.shape
-    sd = _seeds(seeds, D) if seeds is not None else None
-    co = None
-    if coeffs is not None:
-        co = np.array([[int(v) & 0xFFFFFFFFFFFFFFFF for v in row] for row in coeffs], dtype=np.uint64).reshape(D, -1)
-        if co.shape[1] != int(degree):
-            raise PvwError(15, f"expected {int(degree)} coefficients per dealer, got {co.shape[1]}")
-    out = np.zeros((D, params.n), dtype=np.uint64)
-    params._call("pvw_shamir_shares_packed_host" if host else "pvw_shamir_shares_packed", _ptr(se), D, K, int(degree),
-                 int(plain_modulus), _ptr(sd), _ptr(co), _ptr(out))
-    return out
+    return _shamir_shares(params, se, (se.shape[1],), degree, plain_modulus, seeds, coeffs, host)
 
 
 def deal_party_shares_packed(secrets, degree: int, plain_modulus: int, global_pk: GlobalPublicKey,
@@ -1016,20 +1017,8 @@ def deal_party_shares_packed(secrets, degree: int, plain_modulus: int, global_pk
     """EXTENSION: dealer d shares its K secrets secrets[d] in one polynomial and encrypts the shares, in one device
     call (pvw_deal_shares_packed): what encrypt_many(shamir_shares_packed(..., seeds), global_pk, seeds) returns, one ciphertext
     per K secrets, without the shares or the coefficients ever existing on the host.  seeds / randomness as deal_party_shares."""
-    p = global_pk.params
     se = _secret_rows(secrets)
-    D, K = se.shape
-    c1 = np.zeros((D, p.k, p.L, p.l), dtype=np.uint64)
-    c2 = np.zeros((D, p.n, p.L, p.l), dtype=np.uint64)
-    if randomness is not None:
-        _check_state(p, randomness, seeds)
-        p._call("pvw_deal_shares_packed_rs", _ptr(se), D, K, int(degree), int(plain_modulus), randomness._h, _ptr(c1), _ptr(c2), out_repr)
-    else:
-        if seeds is None:
-            raise PvwError(1, "deal_party_shares_packed needs one 32-byte seed per dealer or a DeviceRandomness")
-        sd = _seeds(seeds, D)
-        p._call("pvw_deal_shares_packed", _ptr(se), D, K, int(degree), int(plain_modulus), _ptr(sd), _ptr(c1), _ptr(c2), out_repr)
-    return [PvwCiphertext(c1[d], c2[d], p, out_repr) for d in range(D)]
+    return _deal_party_shares(se, (se.shape[1],), degree, plain_modulus, global_pk, seeds, randomness, out_repr)
 
 
 def shamir_reconstruct_packed(indices: Sequence[int], shares, plain_modulus: int, pack: int) -> List[List[int]]:

@@ -2118,13 +2118,22 @@ static int32_t shamir_modulus_check(u64 p) {
   if (!is_prime_u64(p)) return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must be prime (Shamir shares live in a field)");
   return PVW_OK;
 }
-static int32_t shamir_checks(const pvw_ctx* c, size_t D, uint32_t degree, u64 p) {
+// The rules of a sharing, each stated once and worded for the entry point they serve.  pack != NULL is a packed call (DESIGN
+// 8.14, K = *pack secrets per dealer at the points 0, -1, ..., -(K-1)); an unpacked call obeys the rules of K = 1.  The points
+// 1..n and p-K+1..p-1, 0 must be distinct: p >= n + K; and K + degree values fix the polynomial: degree + K <= n.
+static int32_t shamir_checks(const pvw_ctx* c, size_t D, uint32_t degree, u64 p, const uint32_t* pack = nullptr) {
+  const u64 K = pack ? *pack : 1;
   if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no dealers");
-  if (p <= c->n) return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must exceed the party count (evaluation points 1..n)");
+  if (K == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "pack must be at least 1");
+  if (p < c->n + K)
+    return fail(PVW_ERR_INVALID_PARAMETERS,
+                pack ? "plain_modulus must be at least n + pack (evaluation points 1..n, secrets at 0..-(pack-1))"
+                     : "plain_modulus must exceed the party count (evaluation points 1..n)");
   PVW_TRY(shamir_modulus_check(p));
-  if (degree >= c->n) {
-    char buf[96];
-    snprintf(buf, sizeof buf, "degree %u needs more than %u parties", degree, c->n);
+  if (degree + K > c->n) {
+    char buf[112];
+    if (pack) snprintf(buf, sizeof buf, "degree %u with pack %u needs more than %u parties", degree, *pack, c->n);
+    else snprintf(buf, sizeof buf, "degree %u needs more than %u parties", degree, c->n);
     return fail(PVW_ERR_INVALID_PARAMETERS, buf);
   }
   return PVW_OK;
@@ -2165,27 +2174,14 @@ int32_t pvw_shamir_shares_host(const pvw_ctx* c, const uint64_t* secrets, size_t
 // ------------------------------------------------------------------------ packed shares
 // K = pack secrets per dealer at the points 0, -1, ..., -(K-1):
 //   f_d(x) = sum_{j<K} s_{d,j} L_j(x) + Z(x) (a_{d,1} + a_{d,2} x + ... + a_{d,t} x^(t-1)),  Z(x) = x (x+1) ... (x+K-1)
-// The points 1..n and p-K+1..p-1, 0 must be distinct: p >= n + K.  With K = 1 every rule below is shamir_checks'.
-static int32_t shamir_packed_checks(const pvw_ctx* c, size_t D, uint32_t pack, uint32_t degree, u64 p) {
-  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no dealers");
-  if (pack == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "pack must be at least 1");
-  if (p < (u64)c->n + pack)
-    return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must be at least n + pack (evaluation points 1..n, secrets at 0..-(pack-1))");
-  PVW_TRY(shamir_modulus_check(p));
-  if ((u64)degree + pack > c->n) {
-    char buf[112];
-    snprintf(buf, sizeof buf, "degree %u with pack %u needs more than %u parties", degree, pack, c->n);
-    return fail(PVW_ERR_INVALID_PARAMETERS, buf);
-  }
-  return PVW_OK;
-}
+// The points 1..n and p-K+1..p-1, 0 must be distinct: p >= n + K (shamir_checks).
 
 // the contract in plain C++ (no GPU): L_j(x) and Z(x) from the definition with one inversion per denominator, sequential
 // draws, Horner.  Writes all n columns, whatever the context's shard.
 int32_t pvw_shamir_shares_packed_host(const pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
                                       uint64_t plain_modulus, const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out) {
   if (!c || !secrets || !shares_out || (degree && !seeds && !coeffs)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(shamir_packed_checks(c, num_dealers, pack, degree, plain_modulus));
+  PVW_TRY(shamir_checks(c, num_dealers, degree, plain_modulus, &pack));
   const Mod m = shamir_mod(plain_modulus);
   const u32 n = c->n, t = degree, K = pack;
   // Lj[j * n + i] = L_j(i + 1) = prod_{m != j} (x + m) / (m - j), Z[i] = prod_m (x + m)
@@ -3066,7 +3062,7 @@ static int32_t shamir_enqueue(pvw_ctx* c, const ShamirDeal& deal, const DealerKe
   ProfScope ps(c, deal.pack ? "shamir_eval_packed" : "shamir_eval", s);
   for (size_t d0 = 0; d0 < D; d0 += PVW_MAX_PROLOGUE_KEYS) {
     const ShamirDeal dd = deal.from(d0);
-    ShamirPackedBatch b{};
+    ShamirBatch b{};
     b.nd = (u32)((D - d0) < PVW_MAX_PROLOGUE_KEYS ? (D - d0) : PVW_MAX_PROLOGUE_KEYS);
     b.secrets = dd.d_secrets;
     b.coeffs = dd.d_coeffs;
@@ -3077,35 +3073,49 @@ static int32_t shamir_enqueue(pvw_ctx* c, const ShamirDeal& deal, const DealerKe
     b.party_hi = c->party_hi;
     b.m = deal.m;
     if (!b.coeffs && deal.degree) keys.from(d0).fill(b, b.nd);
-    if (deal.pack) {
-      b.pack = deal.pack;
-      b.Lw = deal.d_packw;
-      b.zt = deal.d_packw + (size_t)deal.pack * c->rowsB();
-      PVW_HIP(launch_shamir_eval_packed(b, s));
-    } else {
-      PVW_HIP(launch_shamir_eval(b, s));
-    }
+    b.pack = deal.pack;                                        // 0: the unpacked kernel, and the weights are NULL
+    b.Lw = deal.d_packw;
+    b.zt = deal.d_packw + (size_t)deal.pack * c->rowsB();
+    PVW_HIP(launch_shamir_eval(b, s));
     memset(&b, 0, sizeof b);
   }
   return PVW_OK;
 }
 
-int32_t pvw_shamir_shares_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t degree,
-                                 uint64_t plain_modulus, const uint8_t* seeds, const uint64_t* d_coeffs, uint64_t* d_shares,
-                                 void* stream) {
-  if (!c || !d_secrets || !d_shares || (degree && !seeds && !d_coeffs)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(shamir_checks(c, num_dealers, degree, plain_modulus));
-  PVW_TRY(ensure_device(c));
-  const ShamirDeal deal{d_secrets, d_coeffs, degree, shamir_mod(plain_modulus)};
-  return shamir_enqueue(c, deal, DealerKeys::host(seeds), num_dealers, d_shares, call_stream(c, stream));
+// The front of the four calls below: the NULL-argument rule, then the rules of the sharing.
+static int32_t shamir_shares_checks(const pvw_ctx* c, const uint64_t* secrets, size_t D, const uint32_t* pack, uint32_t degree, uint64_t p,
+                                    const uint8_t* seeds, const uint64_t* coeffs, const uint64_t* shares) {
+  if (!c || !secrets || !shares || (degree && !seeds && !coeffs)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  return shamir_checks(c, D, degree, p, pack);
 }
 
-// host buffers: the dealers go up in pieces of `per` (secrets [pack] each, explicit coefficients), each piece's shares come down,
-// and the staging -- secrets, coefficients and shares alike -- is cleared when the call ends.  pack != 0 (8.14): the weights once, in front
-static int32_t shamir_shares_stage(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+// device pointers.  pack != NULL (the packed form): secrets [D][*pack]; the weights once per call, then the packed
+// kernel per launch of dealers
+static int32_t shamir_shares_device(pvw_ctx* c, const uint64_t* d_secrets, size_t D, const uint32_t* pack, uint32_t degree, uint64_t p,
+                                    const uint8_t* seeds, const uint64_t* d_coeffs, uint64_t* d_shares, void* stream) {
+  PVW_TRY(shamir_shares_checks(c, d_secrets, D, pack, degree, p, seeds, d_coeffs, d_shares));
+  ShamirDeal deal{d_secrets, d_coeffs, degree, shamir_mod(p), pack ? *pack : 0};
+  const DealerKeys keys = DealerKeys::host(seeds);
+  if (!pack) {                                                 // no workspace: no device_call
+    PVW_TRY(ensure_device(c));
+    return shamir_enqueue(c, deal, keys, D, d_shares, call_stream(c, stream));
+  }
+  // the caller's stream is checked before the context initialises its device (pvw_shamir_reconstruct_checked_device)
+  auto sized = [&](hipStream_t s) { return packed_capture_check(c, s, *pack); };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
+    PVW_TRY(shamir_packed_prepare(c, w, &deal, s));
+    return shamir_enqueue(c, deal, keys, D, d_shares, s);
+  });
+}
+
+// host buffers: the dealers go up in pieces of `per` (secrets [*pack] each, explicit coefficients), each piece's shares come down,
+// and the staging -- secrets, coefficients and shares alike -- is cleared when the call ends.  pack != NULL (8.14): the weights once, in front
+static int32_t shamir_shares_stage(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, const uint32_t* pack, uint32_t degree,
                                    uint64_t plain_modulus, const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out) {
+  PVW_TRY(shamir_shares_checks(c, secrets, num_dealers, pack, degree, plain_modulus, seeds, coeffs, shares_out));
   PVW_TRY(ensure_device(c));
-  const size_t n = c->n, t = degree, K = pack ? pack : 1, rB = c->rowsB();
+  const size_t n = c->n, t = degree, K = pack ? *pack : 1, rB = c->rowsB();
   const size_t per = chunk_1gib((n + (coeffs ? t : 0) + K) * 8, num_dealers);
   Scratch sc;
   const size_t r_se = sc.add(per * K * 8), r_co = sc.add(coeffs ? per * t * 8 : 0), r_sh = sc.add(per * n * 8);
@@ -3113,7 +3123,7 @@ static int32_t shamir_shares_stage(pvw_ctx* c, const uint64_t* secrets, size_t n
     PVW_TRY(sc.take(w));
     sc.secret(w, r_se, r_sh);                                  // secrets, coefficients and shares alike
     u64 *d_se = sc.at(r_se), *d_co = coeffs && t ? sc.at(r_co) : nullptr, *d_sh = sc.at(r_sh);
-    ShamirDeal deal{d_se, d_co, degree, shamir_mod(plain_modulus), pack};
+    ShamirDeal deal{d_se, d_co, degree, shamir_mod(plain_modulus), pack ? *pack : 0};
     if (pack) PVW_TRY(shamir_packed_prepare(c, w, &deal, w->stream));
     for (size_t d0 = 0; d0 < num_dealers; d0 += per) {
       const size_t cnt = (num_dealers - d0) < per ? (num_dealers - d0) : per;
@@ -3128,34 +3138,24 @@ static int32_t shamir_shares_stage(pvw_ctx* c, const uint64_t* secrets, size_t n
     return PVW_OK;
   });
 }
+
+int32_t pvw_shamir_shares_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t degree,
+                                 uint64_t plain_modulus, const uint8_t* seeds, const uint64_t* d_coeffs, uint64_t* d_shares,
+                                 void* stream) {
+  return shamir_shares_device(c, d_secrets, num_dealers, nullptr, degree, plain_modulus, seeds, d_coeffs, d_shares, stream);
+}
 int32_t pvw_shamir_shares(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t degree, uint64_t plain_modulus,
                           const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out) {
-  if (!c || !secrets || !shares_out || (degree && !seeds && !coeffs)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(shamir_checks(c, num_dealers, degree, plain_modulus));
-  return shamir_shares_stage(c, secrets, num_dealers, 0, degree, plain_modulus, seeds, coeffs, shares_out);
+  return shamir_shares_stage(c, secrets, num_dealers, nullptr, degree, plain_modulus, seeds, coeffs, shares_out);
 }
-
-// The packed forms: secrets [D][pack]; the weights once per call, then the packed kernel per launch of dealers.
 int32_t pvw_shamir_shares_packed_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
                                         uint64_t plain_modulus, const uint8_t* seeds, const uint64_t* d_coeffs, uint64_t* d_shares,
                                         void* stream) {
-  if (!c || !d_secrets || !d_shares || (degree && !seeds && !d_coeffs)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(shamir_packed_checks(c, num_dealers, pack, degree, plain_modulus));
-  // the caller's stream is checked before the context initialises its device (pvw_shamir_reconstruct_checked_device)
-  auto sized = [&](hipStream_t s) { return packed_capture_check(c, s, pack); };
-  if (stream) PVW_TRY(sized((hipStream_t)stream));
-  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
-    ShamirDeal deal{d_secrets, d_coeffs, degree, shamir_mod(plain_modulus), pack};
-    PVW_TRY(shamir_packed_prepare(c, w, &deal, s));
-    return shamir_enqueue(c, deal, DealerKeys::host(seeds), num_dealers, d_shares, s);
-  });
+  return shamir_shares_device(c, d_secrets, num_dealers, &pack, degree, plain_modulus, seeds, d_coeffs, d_shares, stream);
 }
-
 int32_t pvw_shamir_shares_packed(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
                                  uint64_t plain_modulus, const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out) {
-  if (!c || !secrets || !shares_out || (degree && !seeds && !coeffs)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  PVW_TRY(shamir_packed_checks(c, num_dealers, pack, degree, plain_modulus));
-  return shamir_shares_stage(c, secrets, num_dealers, pack, degree, plain_modulus, seeds, coeffs, shares_out);
+  return shamir_shares_stage(c, secrets, num_dealers, &pack, degree, plain_modulus, seeds, coeffs, shares_out);
 }
 
 // ------------------------------------------------------------------------ multi-dealer encrypt
@@ -3342,7 +3342,7 @@ static int32_t deal_device(pvw_ctx* c, const uint64_t* d_secrets, size_t D, uint
                            uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream, const uint32_t* pack = nullptr) {
   if (!c || !d_secrets || keys.missing() || (!d_c1 && c->rowsA()) || (!d_c2 && c->rowsB())) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   PVW_TRY(encrypt_multi_checks(c, D, c->n, out_repr));
-  PVW_TRY(pack ? shamir_packed_checks(c, D, *pack, degree, p) : shamir_checks(c, D, degree, p));
+  PVW_TRY(shamir_checks(c, D, degree, p, pack));
   ShamirDeal deal{d_secrets, nullptr, degree, shamir_mod(p), pack ? *pack : 0};
   if (pack && stream) PVW_TRY(packed_capture_check(c, (hipStream_t)stream, *pack));
   return device_call(c, stream, [&](hipStream_t s) -> int32_t {
@@ -3361,7 +3361,7 @@ static int32_t deal_host(pvw_ctx* c, const uint64_t* secrets, size_t D, uint32_t
                          uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr, const uint32_t* pack = nullptr) {
   if (!c || !secrets || keys.missing() || !c1_out || !c2_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   PVW_TRY(encrypt_multi_checks(c, D, c->n, out_repr));
-  PVW_TRY(pack ? shamir_packed_checks(c, D, *pack, degree, p) : shamir_checks(c, D, degree, p));
+  PVW_TRY(shamir_checks(c, D, degree, p, pack));
   PVW_TRY(ensure_device(c));
   PVW_TRY(keys.checks(c));
   // the staging loop points it at each piece's secrets in turn, and makes the weights of a packed deal

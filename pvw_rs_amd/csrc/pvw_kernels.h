@@ -231,9 +231,16 @@ hipError_t launch_ct_lincomb(const SumRegion& a, const SumRegion& b, const unsig
 // (any word, read mod m.q), or with coeffs == NULL the first accepted draw of the ChaCha8 stream (key of dealer d,
 // (DOM_SHAMIR << 32) | j).  Dealer d's key is key[d], or with rnd != NULL call_seed(S, counter + rnd_off + d), derived when the
 // kernel runs (the kernel does not write the state).  nd <= PVW_MAX_PROLOGUE_KEYS; m.q prime, party_hi < m.q < 2^62.
+// Packed, pack = K != 0: K secrets per dealer at the points 0, -1, ..., -(K-1),
+//   f_d(x) = sum_{j<K} secrets[d * K + j] L_j(x) + Z(x) (a_{d,1} + a_{d,2} x + ... + a_{d,t} x^(t-1)),  Z(x) = x (x+1) ... (x+K-1),
+// L_j the Lagrange basis polynomial of -j among those points; K = 1 is the polynomial above.  The weights are public and made
+// on the device from (p, K, party range) alone:
+// words: Lw [K][cols] | zt [cols] | w [K] | 1/j! [K], cols = party_hi - party_lo; Lw[j][i] = L_j(party_lo + i + 1),
+// zt[i] = prod_{m=1..K-1}(party_lo + i + 1 + m) = Z(x) / x.  m.q prime, party_hi + K - 1 < m.q < 2^62.
 enum { DOM_SHAMIR = 9 };
+inline size_t shamir_packed_words(size_t pack, size_t cols) { return (pack + 1) * cols + 2 * pack; }
 struct ShamirBatch {
-  const u64* secrets;   // [nd] device words, read mod m.q
+  const u64* secrets;   // [nd], packed [nd][pack]: device words, read mod m.q
   const u64* coeffs;    // [nd][degree] device words, or NULL: drawn
   u64* shares;
   size_t row_stride;    // words between consecutive dealers' rows (columns are GLOBAL party indices)
@@ -242,23 +249,12 @@ struct ShamirBatch {
   ChaChaKey key[PVW_MAX_PROLOGUE_KEYS];
   const RndState* rnd;
   u64 rnd_off;
-};
-hipError_t launch_shamir_eval(const ShamirBatch& b, hipStream_t s);
-
-// ---- Packed Shamir shares (pvw_shamir.hip): `pack` = K secrets per dealer at the points 0, -1, ..., -(K-1),
-//   f_d(x) = sum_{j<K} secrets[d * K + j] L_j(x) + Z(x) (a_{d,1} + a_{d,2} x + ... + a_{d,t} x^(t-1)),  Z(x) = x (x+1) ... (x+K-1),
-// L_j the Lagrange basis polynomial of -j among those points; a_{d,j}, the keys and the columns as ShamirBatch.  K = 1 is the
-// polynomial of ShamirBatch.  The weights are public and made on the device from (p, K, party range) alone:
-// words: Lw [K][cols] | zt [cols] | w [K] | 1/j! [K], cols = party_hi - party_lo; Lw[j][i] = L_j(party_lo + i + 1),
-// zt[i] = prod_{m=1..K-1}(party_lo + i + 1 + m) = Z(x) / x.  m.q prime, party_hi + K - 1 < m.q < 2^62.
-inline size_t shamir_packed_words(size_t pack, size_t cols) { return (pack + 1) * cols + 2 * pack; }
-struct ShamirPackedBatch : ShamirBatch {   // secrets: [nd][pack]
-  u32 pack;
+  u32 pack;             // 0: the unpacked kernel, which reads neither Lw nor zt; >= 1: the packed one, whatever pack
   const u64* Lw;        // [pack][party_hi - party_lo]
   const u64* zt;        // [party_hi - party_lo]
 };
 hipError_t launch_shamir_packed_weights(u64* ws, u32 pack, u32 party_lo, u32 party_hi, const Mod& m, hipStream_t s);
-hipError_t launch_shamir_eval_packed(const ShamirPackedBatch& b, hipStream_t s);
+hipError_t launch_shamir_eval(const ShamirBatch& b, hipStream_t s);
 
 // ---- Checked reconstruction (pvw_shamir.hip).  Columns 0..t of the share matrix are the basis, columns
 // t+1..count-1 the extras; T = count - t targets: target 0 is x = 0, target m >= 1 the point of column t + m.

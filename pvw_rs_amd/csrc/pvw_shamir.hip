@@ -3,16 +3,25 @@
 // The reference has no sharing code (its examples fill the share matrix with arbitrary numbers): the contract is this
 // library's own and pvw_shamir_shares_host (pvw_capi.hip) is its plain restatement.
 //
-// Shape.  A lane owns one party (x = i + 1) and SH_DG dealers; the four waves of a workgroup own the same 64 parties and
-// dealers and a quarter of the terms j = 1 .. t each.  A wave starts from x^(j0) by square-and-multiply and then keeps
-// pw = x^j up to date with ONE full modular multiply per term, shared by its dealers; a_{d,j} pw goes into one lazy
-// accumulator per dealer (pvw_arith.h: 4 x v_mad_u64_u32 into independent sums, reduced once at the end).  The four
-// partial sums meet in LDS, as mac_rows sums its waves.
+// Shape (shamir_eval_kernel).  A lane owns one party (x = i + 1) and SH_DG dealers; the four waves of a workgroup own the same
+// 64 parties and dealers and a quarter of the terms each.  Term e of the unpacked kernel is j = e + 1: a wave starts from
+// x^(j0) by square-and-multiply and then keeps pw = x^j up to date with ONE full modular multiply per term, shared by its
+// dealers; a_{d,j} pw goes into one lazy accumulator per dealer (pvw_arith.h: 4 x v_mad_u64_u32 into independent sums, reduced
+// once at the end).  The four partial sums meet in LDS, as mac_rows sums its waves, and the secret is added there.
 // Coefficients are uniform across a wave: each chunk of SH_JC terms per wave is staged in LDS by the whole workgroup and
 // read back as broadcasts ([wave][term][dealer], so one term's SH_DG coefficients are one 32-byte read at the same address
 // in every lane).  Drawn coefficients are MADE in that staging phase -- one lane per coefficient, one ChaCha8 block per
 // try, its words statically indexed -- so nothing but the shares is ever written to memory; every workgroup of a dealer
 // group repeats the draw for its 64 parties (about a quarter of the multiply-add work at 64 parties per workgroup).
+//
+// PACKED: K secrets per dealer at the points 0, -1, ..., -(K-1) (Franklin-Yung),
+//   f_d(x) = sum_{j<K} s_{d,j} L_j(x) + Z(x) (a_{d,1} + a_{d,2} x + ... + a_{d,t} x^(t-1)),  Z(x) = x (x+1) ... (x+K-1).
+// The term axis becomes e = 0 .. K + t - 1.  e < K is secret term e: coefficient s_{d,e}, staged like any other, and weight
+// Lw[e][party], LOADED, four in flight ahead of their multiply-adds as in shamir_tile_product.  e >= K is random term
+// j = e - K + 1: weight Z(x) x^(j-1) = zt(x) x^j, the running power started from x^(j0) zt(x) at the wave's first random term.
+// Nothing is added at the meet.  With K = 1, Lw = zt = 1 and the sum is the unpacked one, term for term -- at one loaded
+// weight per secret term and one more multiply per lane, which is why the unpacked entry points keep an instantiation of
+// their own (K = 0 loaded terms, no Lw, no zt) rather than run the packed one at K = 1.
 #include <hip/hip_runtime.h>
 
 #include "pvw_arith.h"
@@ -44,7 +53,9 @@ PVW_HD u64 shamir_draw(const ChaChaKey& key, u32 j, u64 p, u32 sh) {
   }
 }
 
-__device__ __forceinline__ u64 powmod_dev(u64 b, u32 e, const Mod& m) {
+// b^e; the exponent keeps its width: a u32 is walked in 32-bit registers, and a^(p - 2) (invmod_dev) needs 64
+template <class E>
+__device__ __forceinline__ u64 powmod_dev(u64 b, E e, const Mod& m) {
   u64 r = 1;
   while (e) {
     if (e & 1) r = mulmod(r, b, m);
@@ -53,18 +64,81 @@ __device__ __forceinline__ u64 powmod_dev(u64 b, u32 e, const Mod& m) {
   }
   return r;
 }
+__device__ __forceinline__ u64 invmod_dev(u64 a, const Mod& m) { return powmod_dev(a, m.q - 2, m); }   // Fermat
+
+// The loaded multiply-adds of the frame: acc[g] += a[jj][g] * wp[jj * stride] for the terms jj < cnt of a wave's chunk `a`, four
+// weights in flight ahead of their multiply-adds, then the tail.  A lane that is not live loads nothing and adds 0.
+__device__ __forceinline__ void shamir_mac_loaded(Acc (&acc)[SH_DG], const u64 (*a)[SH_DG], const u64* wp, size_t stride, u32 cnt,
+                                                  bool live) {
+  u32 jj = 0;
+  for (; jj + 4 <= cnt; jj += 4) {
+    u64 w[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) w[u] = live ? wp[(size_t)u * stride] : 0;
+    wp += (size_t)4 * stride;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      u64 v[SH_DG];
+#pragma unroll
+      for (int g = 0; g < SH_DG; ++g) v[g] = a[jj + u][g];
+#pragma unroll
+      for (int g = 0; g < SH_DG; ++g) acc_mac_dev(acc[g], v[g], w[u]);
+    }
+  }
+  for (; jj < cnt; ++jj) {
+    const u64 w = live ? *wp : 0;
+    wp += stride;
+    u64 v[SH_DG];
+#pragma unroll
+    for (int g = 0; g < SH_DG; ++g) v[g] = a[jj][g];
+#pragma unroll
+    for (int g = 0; g < SH_DG; ++g) acc_mac_dev(acc[g], v[g], w);
+  }
+}
+
+// how many terms chunk c holds of the wave whose range is [w0, w0 + Q) cut off at nt; the chunk's first is w0 + c * SH_JC
+__device__ __forceinline__ u32 shamir_chunk_terms(u32 w0, u32 Q, u32 c, u32 nt) {
+  const u32 base = c * SH_JC;
+  u32 cnt = 0;
+  if (base < Q && w0 + base < nt) {
+    cnt = Q - base < SH_JC ? Q - base : SH_JC;
+    const u32 left = nt - (w0 + base);
+    cnt = left < cnt ? left : cnt;
+  }
+  return cnt;
+}
+
+// The four waves' partial sums meet in LDS: thread (wave = g, lane) comes back with v plus accumulator g of every wave, below
+// p; a thread that is not live with v.  m by value (shamir_tile_product).  part is the caller's, declared BEHIND its staging
+// array: declared here it lands in front of it, and shamir_interp_kernel then measured 2 % slower at 64 secrets
+// (profiles/r12_shamir_deal_fold.txt).
+__device__ __forceinline__ u64 shamir_meet(Acc (&acc)[SH_DG], u64 (&part)[SH_WAVES][SH_DG][64], u64 v, bool live, const Mod m) {
+  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int g = 0; g < SH_DG; ++g) part[wave][g][lane] = acc_reduce(acc[g], m);
+  __syncthreads();
+  if (live) {
+#pragma unroll
+    for (int w = 0; w < SH_WAVES; ++w) v = addmod(v, part[w][wave][lane], m.q);   // SH_WAVES == SH_DG
+  }
+  return v;
+}
+static_assert(SH_WAVES == SH_DG, "the last phase maps one wave to one dealer of the group");
 
 // grid: x = blocks of 64 parties of [party_lo, party_hi), y = groups of SH_DG dealers; 256 threads.
+template <bool PACKED>
 __global__ __launch_bounds__(256) void shamir_eval_kernel(ShamirBatch b) {
   __shared__ u64 coef[SH_WAVES][SH_JC][SH_DG];     // 8 KiB: the chunk's coefficients, below p
   __shared__ u64 part[SH_WAVES][SH_DG][64];        // 8 KiB: the waves' partial sums, below p
   __shared__ u32 keyw[SH_DG][8];
   const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const Mod m = b.m;
-  const u32 t = b.degree;
+  const u32 t = b.degree, K = PACKED ? b.pack : 0, nt = K + t;
   const u32 d0 = blockIdx.y * SH_DG;
-  const u32 party = b.party_lo + blockIdx.x * 64 + lane;
-  const bool live = party < b.party_hi;
+  const u32 col = blockIdx.x * 64 + lane;
+  const u32 cols = b.party_hi - b.party_lo;
+  const u32 party = b.party_lo + col;
+  const bool live = col < cols;
   const bool drawn = b.coeffs == nullptr && t != 0;
   const u32 sh = (u32)__clzll((long long)m.q);
   if (drawn && tid < SH_DG && d0 + tid < b.nd) {
@@ -74,12 +148,19 @@ __global__ __launch_bounds__(256) void shamir_eval_kernel(ShamirBatch b) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) keyw[tid][i] = k.w[i];
   }
-  // wave w owns terms j = 1 + w * Q + [0, Q), cut off at t; every wave walks the same number of chunks (barriers)
-  const u32 Q = (t + SH_WAVES - 1) / SH_WAVES;
-  const u32 jw0 = 1 + wave * Q;
+  // wave w owns terms e = w * Q + [0, Q), cut off at nt; every wave walks the same number of chunks (barriers)
+  const u32 Q = (nt + SH_WAVES - 1) / SH_WAVES;
+  const u32 ew0 = wave * Q;
+  const u32 ew1 = ew0 + Q < nt ? ew0 + Q : nt;     // the end of the wave's range (ew1 <= ew0: none)
   const u32 nchunks = (Q + SH_JC - 1) / SH_JC;
   const u64 x = live ? (u64)party + 1 : 1;         // x <= n < p
-  u64 pw = Q && jw0 <= t ? powmod_dev(x, jw0, m) : 0;
+  // the wave's first random term e, j = e - K + 1, and its weight x^j (packed: zt(x) x^j)
+  const u32 er0 = ew0 > K ? ew0 : K;
+  u64 pw = 0;
+  if (er0 < ew1) {
+    pw = powmod_dev(x, er0 - K + 1, m);
+    if (PACKED) pw = mulmod(pw, live ? b.zt[col] : 0, m);
+  }
   Acc acc[SH_DG];
 #pragma unroll
   for (int g = 0; g < SH_DG; ++g) acc_zero(acc[g]);
@@ -89,30 +170,29 @@ __global__ __launch_bounds__(256) void shamir_eval_kernel(ShamirBatch b) {
     for (u32 e = tid; e < SH_WAVES * SH_JC * SH_DG; e += 256) {
       const u32 ew = e / (SH_JC * SH_DG), ej = (e / SH_DG) % SH_JC, eg = e % SH_DG;
       const u32 off = c * SH_JC + ej;              // within the wave's range
-      const u32 j = 1 + ew * Q + off;
+      const u32 te = ew * Q + off;                 // the term
       u64 a = 0;
-      if (off < Q && j <= t && d0 + eg < b.nd) {
-        if (drawn) {
+      if (off < Q && te < nt && d0 + eg < b.nd) {
+        if (te < K) {
+          a = reduce_word(b.secrets[(size_t)(d0 + eg) * K + te], m);
+        } else if (drawn) {
           ChaChaKey k;
 #pragma unroll
           for (int i = 0; i < 8; ++i) k.w[i] = keyw[eg][i];
-          a = shamir_draw(k, j, m.q, sh);
+          a = shamir_draw(k, te - K + 1, m.q, sh);
         } else {
-          a = reduce_word(b.coeffs[(size_t)(d0 + eg) * t + (j - 1)], m);
+          a = reduce_word(b.coeffs[(size_t)(d0 + eg) * t + (te - K)], m);
         }
       }
       coef[ew][ej][eg] = a;
     }
     __syncthreads();
-    // ---- this wave's terms of the chunk ----
-    const u32 base = c * SH_JC;
-    u32 cnt = 0;
-    if (base < Q && jw0 + base <= t) {
-      cnt = Q - base < SH_JC ? Q - base : SH_JC;
-      const u32 left = t - (jw0 + base) + 1;
-      cnt = left < cnt ? left : cnt;
-    }
-    for (u32 jj = 0; jj < cnt; ++jj) {
+    // ---- this wave's terms of the chunk: cnt from e0 on, the ns secret terms first ----
+    const u32 e0 = ew0 + c * SH_JC;
+    const u32 cnt = shamir_chunk_terms(ew0, Q, c, nt);
+    const u32 ns = e0 < K ? (K - e0 < cnt ? K - e0 : cnt) : 0;
+    if (PACKED) shamir_mac_loaded(acc, coef[wave], b.Lw + (size_t)e0 * cols + (live ? col : 0), cols, ns, live);
+    for (u32 jj = ns; jj < cnt; ++jj) {
       u64 a[SH_DG];
 #pragma unroll
       for (int g = 0; g < SH_DG; ++g) a[g] = coef[wave][jj][g];
@@ -122,27 +202,19 @@ __global__ __launch_bounds__(256) void shamir_eval_kernel(ShamirBatch b) {
     }
     __syncthreads();
   }
-#pragma unroll
-  for (int g = 0; g < SH_DG; ++g) part[wave][g][lane] = acc_reduce(acc[g], m);
-  __syncthreads();
-  // thread (g, lane) adds the four partial sums and the secret and stores dealer d0 + g's share of its party
-  {
-    const u32 g = wave;                            // SH_WAVES == SH_DG
-    const u32 d = d0 + g;
-    if (live && d < b.nd) {
-      u64 s = reduce_word(b.secrets[d], m);
-#pragma unroll
-      for (int w = 0; w < SH_WAVES; ++w) s = addmod(s, part[w][g][lane], m.q);
-      b.shares[(size_t)d * b.row_stride + party] = s;
-    }
-  }
+  // thread (g, lane) adds the four partial sums -- and, unpacked, the secret -- and stores dealer d0 + g's share of its party
+  const u32 d = d0 + wave;
+  const bool out = live && d < b.nd;
+  const u64 s = shamir_meet(acc, part, !PACKED && out ? reduce_word(b.secrets[d], m) : 0, out, m);
+  if (out) b.shares[(size_t)d * b.row_stride + party] = s;
 }
-static_assert(SH_WAVES == SH_DG, "the last phase maps one wave to one dealer of the group");
 
+// pack 0 is the unpacked entry points; pack >= 1 the packed ones, whatever pack
 hipError_t launch_shamir_eval(const ShamirBatch& b, hipStream_t s) {
   if (b.nd == 0 || b.party_hi <= b.party_lo) return hipSuccess;
   const dim3 grid((b.party_hi - b.party_lo + 63) / 64, (b.nd + SH_DG - 1) / SH_DG);
-  shamir_eval_kernel<<<grid, dim3(256), 0, s>>>(b);
+  if (b.pack) shamir_eval_kernel<true><<<grid, dim3(256), 0, s>>>(b);
+  else shamir_eval_kernel<false><<<grid, dim3(256), 0, s>>>(b);
   return hipGetLastError();
 }
 
@@ -163,16 +235,6 @@ hipError_t launch_shamir_eval(const ShamirBatch& b, hipStream_t s) {
 // arguments are the one way up that neither waits nor reads the array again when a captured call is replayed
 __global__ __launch_bounds__(PVW_SHAMIR_POINTS) void shamir_points_kernel(ShamirPoints a) {
   if (threadIdx.x < a.n) a.x[threadIdx.x] = a.index[threadIdx.x] + 1;
-}
-
-__device__ __forceinline__ u64 invmod_dev(u64 a, const Mod& m) {   // a^(p - 2)
-  u64 r = 1, e = m.q - 2;
-  while (e) {
-    if (e & 1) r = mulmod(r, a, m);
-    a = mulmod(a, a, m);
-    e >>= 1;
-  }
-  return r;
 }
 
 // item e = blockIdx.x * 4 + wave of [0, count + 1): e <= t is basis column e (the product leaves i = e out and is inverted),
@@ -252,53 +314,16 @@ __device__ __forceinline__ ShamirTile shamir_tile_product(const u64* A, size_t s
     }
     __syncthreads();
     // ---- this wave's terms of the chunk ----
-    const u32 base = c * SH_JC;
-    u32 cnt = 0;
-    if (base < Q && jw0 + base < nt) {
-      cnt = Q - base < SH_JC ? Q - base : SH_JC;
-      const u32 left = nt - (jw0 + base);
-      cnt = left < cnt ? left : cnt;
-    }
-    const u64* wp = wcol + (size_t)(jw0 + base) * T;
-    u32 jj = 0;
-    for (; jj + 4 <= cnt; jj += 4) {               // four weights in flight ahead of their multiply-adds
-      u64 w[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) w[u] = live ? wp[(size_t)u * T] : 0;
-      wp += (size_t)4 * T;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        u64 a[SH_DG];
-#pragma unroll
-        for (int g = 0; g < SH_DG; ++g) a[g] = sh[wave][jj + u][g];
-#pragma unroll
-        for (int g = 0; g < SH_DG; ++g) acc_mac_dev(acc[g], a[g], w[u]);
-      }
-    }
-    for (; jj < cnt; ++jj) {
-      const u64 w = live ? *wp : 0;
-      wp += T;
-      u64 a[SH_DG];
-#pragma unroll
-      for (int g = 0; g < SH_DG; ++g) a[g] = sh[wave][jj][g];
-#pragma unroll
-      for (int g = 0; g < SH_DG; ++g) acc_mac_dev(acc[g], a[g], w);
-    }
+    const u32 j0 = jw0 + c * SH_JC;
+    shamir_mac_loaded(acc, sh[wave], wcol + (size_t)j0 * T, T, shamir_chunk_terms(jw0, Q, c, nt), live);
     __syncthreads();
   }
-#pragma unroll
-  for (int g = 0; g < SH_DG; ++g) part[wave][g][lane] = acc_reduce(acc[g], m);
-  __syncthreads();
   // thread (g, lane) adds the four partial sums of secret s0 + g at its target
   ShamirTile o;
   o.s = s0 + wave;                                 // SH_WAVES == SH_DG
   o.tm = tm;
   o.live = live && o.s < ns;
-  o.v = 0;
-  if (o.live) {
-#pragma unroll
-    for (int w = 0; w < SH_WAVES; ++w) o.v = addmod(o.v, part[w][wave][lane], m.q);
-  }
+  o.v = shamir_meet(acc, part, 0, o.live, m);
   return o;
 }
 
@@ -407,7 +432,7 @@ __global__ __launch_bounds__(256) void shamir_synd_weights_kernel(const u64* x, 
   const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const u32 c = blockIdx.x * SH_WAVES + wave;
   if (c >= count) return;
-  const u64 xc = x[c], step = powmod_dev(xc, 64, m);
+  const u64 xc = x[c], step = powmod_dev(xc, 64u, m);
   u64 v = mulmod(aux[c], powmod_dev(xc, lane, m), m);
   u64* row = V + (size_t)c * r;
   for (u32 j = lane; j < r; j += 64) {
@@ -736,9 +761,7 @@ hipError_t launch_shamir_evaluate_finish(const ShamirEvalFinish& f, hipStream_t 
   return hipGetLastError();
 }
 
-// ------------------------------------------------------------------------ packed shares
-// K secrets per dealer at the points 0, -1, ..., -(K-1) (Franklin-Yung):
-//   f_d(x) = sum_{j<K} s_{d,j} L_j(x) + Z(x) (a_{d,1} + a_{d,2} x + ... + a_{d,t} x^(t-1)),  Z(x) = x (x+1) ... (x+K-1).
+// ------------------------------------------------------------------------ the weights of packed shares
 // L_j(x) = w_j prod_{m != j}(x + m) with w_j = ((-1)^j j! (K-1-j)!)^-1: the denominators are factorials, so ONE inversion, of
 // (K-1)!, and a walk down give every 1/j!, and no element of Lw needs one.  x + m <= n + K - 1 < p is never 0.
 
@@ -791,137 +814,6 @@ hipError_t launch_shamir_packed_weights(u64* ws, u32 pack, u32 party_lo, u32 par
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   shamir_packed_weights_kernel<<<dim3((cols + 255) / 256), dim3(256), 0, s>>>(Lw, zt, w, pack, party_lo, cols, m);
-  return hipGetLastError();
-}
-
-// The frame of shamir_eval_kernel over the term axis e = 0 .. K + t - 1: e < K is secret term e (coefficient s_{d,e}, weight
-// Lw[e][party], loaded, four in flight ahead of their multiply-adds as in shamir_tile_product), e >= K is random term
-// j = e - K + 1 (coefficient a_{d,j}, drawn or read in the staging phase exactly as shamir_eval_kernel does; weight
-// Z(x) x^(j-1) = zt(x) x^j, kept up to date by one modular multiply per term and started from x^(j0) zt(x) at the wave's first
-// random term).  With K = 1: Lw = zt = 1 and the sum is shamir_eval_kernel's, term for term.
-// grid: x = blocks of 64 parties of [party_lo, party_hi), y = groups of SH_DG dealers; 256 threads.
-__global__ __launch_bounds__(256) void shamir_eval_packed_kernel(ShamirPackedBatch b) {
-  __shared__ u64 coef[SH_WAVES][SH_JC][SH_DG];     // 8 KiB: the chunk's coefficients, below p
-  __shared__ u64 part[SH_WAVES][SH_DG][64];        // 8 KiB: the waves' partial sums, below p
-  __shared__ u32 keyw[SH_DG][8];
-  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const Mod m = b.m;
-  const u32 t = b.degree, K = b.pack, nt = K + t;
-  const u32 d0 = blockIdx.y * SH_DG;
-  const u32 col = blockIdx.x * 64 + lane;
-  const u32 cols = b.party_hi - b.party_lo;
-  const u32 party = b.party_lo + col;
-  const bool live = col < cols;
-  const bool drawn = b.coeffs == nullptr && t != 0;
-  const u32 sh = (u32)__clzll((long long)m.q);
-  if (drawn && tid < SH_DG && d0 + tid < b.nd) {
-    ChaChaKey k;
-    if (b.rnd) k = call_seed(b.rnd->seed, b.rnd->counter + b.rnd_off + d0 + tid);   // derived when the kernel runs
-    else k = b.key[d0 + tid];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) keyw[tid][i] = k.w[i];
-  }
-  // wave w owns terms e = w * Q + [0, Q), cut off at nt; every wave walks the same number of chunks (barriers)
-  const u32 Q = (nt + SH_WAVES - 1) / SH_WAVES;
-  const u32 ew0 = wave * Q;
-  const u32 ew1 = ew0 + Q < nt ? ew0 + Q : nt;     // the end of the wave's range (ew1 <= ew0: none)
-  const u32 nchunks = (Q + SH_JC - 1) / SH_JC;
-  const u64 x = live ? (u64)party + 1 : 1;         // x <= n < p
-  // the wave's first random term and its weight zt(x) x^j
-  const u32 er0 = ew0 > K ? ew0 : K;
-  u64 pw = 0;
-  if (er0 < ew1) pw = mulmod(powmod_dev(x, er0 - K + 1, m), live ? b.zt[col] : 0, m);
-  const u64* wcol = b.Lw + (live ? col : 0);
-  Acc acc[SH_DG];
-#pragma unroll
-  for (int g = 0; g < SH_DG; ++g) acc_zero(acc[g]);
-  __syncthreads();
-  for (u32 c = 0; c < nchunks; ++c) {
-    // ---- staging: entry e = (wave, term, dealer) of the chunk, one per lane and trip ----
-    for (u32 e = tid; e < SH_WAVES * SH_JC * SH_DG; e += 256) {
-      const u32 ew = e / (SH_JC * SH_DG), ej = (e / SH_DG) % SH_JC, eg = e % SH_DG;
-      const u32 off = c * SH_JC + ej;              // within the wave's range
-      const u32 te = ew * Q + off;                 // the term
-      u64 a = 0;
-      if (off < Q && te < nt && d0 + eg < b.nd) {
-        if (te < K) {
-          a = reduce_word(b.secrets[(size_t)(d0 + eg) * K + te], m);
-        } else if (drawn) {
-          ChaChaKey k;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) k.w[i] = keyw[eg][i];
-          a = shamir_draw(k, te - K + 1, m.q, sh);
-        } else {
-          a = reduce_word(b.coeffs[(size_t)(d0 + eg) * t + (te - K)], m);
-        }
-      }
-      coef[ew][ej][eg] = a;
-    }
-    __syncthreads();
-    // ---- this wave's terms of the chunk: [e0, e1), the secret terms [e0, es) first ----
-    const u32 base = c * SH_JC;
-    const u32 e0 = ew0 + base;
-    u32 cnt = 0;
-    if (base < Q && e0 < ew1) {
-      cnt = Q - base < SH_JC ? Q - base : SH_JC;
-      cnt = ew1 - e0 < cnt ? ew1 - e0 : cnt;
-    }
-    const u32 ns = e0 < K ? (K - e0 < cnt ? K - e0 : cnt) : 0;
-    const u64* wp = wcol + (size_t)e0 * cols;
-    u32 jj = 0;
-    for (; jj + 4 <= ns; jj += 4) {                // four weights in flight ahead of their multiply-adds
-      u64 w[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) w[u] = live ? wp[(size_t)u * cols] : 0;
-      wp += (size_t)4 * cols;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        u64 a[SH_DG];
-#pragma unroll
-        for (int g = 0; g < SH_DG; ++g) a[g] = coef[wave][jj + u][g];
-#pragma unroll
-        for (int g = 0; g < SH_DG; ++g) acc_mac_dev(acc[g], a[g], w[u]);
-      }
-    }
-    for (; jj < ns; ++jj) {
-      const u64 w = live ? *wp : 0;
-      wp += cols;
-      u64 a[SH_DG];
-#pragma unroll
-      for (int g = 0; g < SH_DG; ++g) a[g] = coef[wave][jj][g];
-#pragma unroll
-      for (int g = 0; g < SH_DG; ++g) acc_mac_dev(acc[g], a[g], w);
-    }
-    for (; jj < cnt; ++jj) {
-      u64 a[SH_DG];
-#pragma unroll
-      for (int g = 0; g < SH_DG; ++g) a[g] = coef[wave][jj][g];
-#pragma unroll
-      for (int g = 0; g < SH_DG; ++g) acc_mac_dev(acc[g], a[g], pw);
-      pw = mulmod(pw, x, m);
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int g = 0; g < SH_DG; ++g) part[wave][g][lane] = acc_reduce(acc[g], m);
-  __syncthreads();
-  // thread (g, lane) adds the four partial sums and stores dealer d0 + g's share of its party
-  {
-    const u32 g = wave;                            // SH_WAVES == SH_DG
-    const u32 d = d0 + g;
-    if (live && d < b.nd) {
-      u64 s = 0;
-#pragma unroll
-      for (int w = 0; w < SH_WAVES; ++w) s = addmod(s, part[w][g][lane], m.q);
-      b.shares[(size_t)d * b.row_stride + party] = s;
-    }
-  }
-}
-
-hipError_t launch_shamir_eval_packed(const ShamirPackedBatch& b, hipStream_t s) {
-  if (b.nd == 0 || b.party_hi <= b.party_lo) return hipSuccess;
-  const dim3 grid((b.party_hi - b.party_lo + 63) / 64, (b.nd + SH_DG - 1) / SH_DG);
-  shamir_eval_packed_kernel<<<grid, dim3(256), 0, s>>>(b);
   return hipGetLastError();
 }
 

@@ -608,23 +608,43 @@ inline SumInputs sum_inputs(const std::vector<PvwCiphertext>& cts, const std::ve
   return in;
 }
 // ---- Shamir shares ----
+// The bodies of shamir_shares / deal_party_shares and their packed forms (8.14).  pack == nullptr: the unpacked call, one secret
+// per dealer; else secrets [D][*pack].  A deal takes seeds or, with seeds == nullptr, rnd.
+inline size_t shamir_dealers(const std::vector<uint64_t>& secrets, const uint32_t* pack) {
+  if (!pack) return secrets.size();
+  if (*pack == 0 || secrets.size() % *pack) throw PvwError(15, "pack secrets per dealer");
+  return secrets.size() / *pack;
+}
+inline std::vector<uint8_t> seed_bytes(const std::vector<Seed>& seeds) {
+  std::vector<uint8_t> sd(seeds.size() * 32);
+  for (size_t d = 0; d < seeds.size(); ++d) std::copy(seeds[d].begin(), seeds[d].end(), sd.begin() + d * 32);
+  return sd;
+}
+inline std::vector<uint64_t> shamir_shares_call(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& secrets,
+                                                const uint32_t* pack, uint32_t degree, uint64_t plain_modulus,
+                                                const std::vector<Seed>& seeds, const std::vector<uint64_t>& coeffs, bool host) {
+  const size_t D = shamir_dealers(secrets, pack);
+  if (!seeds.empty() && seeds.size() != D) throw PvwError(15, "one seed per dealer");
+  if (!coeffs.empty() && coeffs.size() != D * degree) throw PvwError(15, "degree coefficients per dealer");
+  const std::vector<uint8_t> sd = seed_bytes(seeds);
+  std::vector<uint64_t> out(D * p->n);
+  const uint8_t* sdp = sd.empty() ? nullptr : sd.data();
+  const uint64_t* cop = coeffs.empty() ? nullptr : coeffs.data();
+  if (pack)
+    check(host ? pvw_shamir_shares_packed_host(p->ctx, secrets.data(), D, *pack, degree, plain_modulus, sdp, cop, out.data())
+               : pvw_shamir_shares_packed(p->ctx, secrets.data(), D, *pack, degree, plain_modulus, sdp, cop, out.data()));
+  else
+    check(host ? pvw_shamir_shares_host(p->ctx, secrets.data(), D, degree, plain_modulus, sdp, cop, out.data())
+               : pvw_shamir_shares(p->ctx, secrets.data(), D, degree, plain_modulus, sdp, cop, out.data()));
+  return out;
+}
 // shares[d][i] = f_d(i + 1) mod plain_modulus for dealer d's polynomial of `degree` with constant term secrets[d]; its other
 // coefficients are drawn from seeds[d] (stream (PVW_DOM_SHAMIR << 32) | j) or given as coeffs [D][degree].  Row-major (D, n).
 // On the device (pvw_shamir_shares); host = true: the plain C++ restatement (pvw_shamir_shares_host, no GPU).
 inline std::vector<uint64_t> shamir_shares(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& secrets, uint32_t degree,
                                            uint64_t plain_modulus, const std::vector<Seed>& seeds,
                                            const std::vector<uint64_t>& coeffs = {}, bool host = false) {
-  const size_t D = secrets.size();
-  if (!seeds.empty() && seeds.size() != D) throw PvwError(15, "one seed per dealer");
-  if (!coeffs.empty() && coeffs.size() != D * degree) throw PvwError(15, "degree coefficients per dealer");
-  std::vector<uint8_t> sd(seeds.size() * 32);
-  for (size_t d = 0; d < seeds.size(); ++d) std::copy(seeds[d].begin(), seeds[d].end(), sd.begin() + d * 32);
-  std::vector<uint64_t> out(D * p->n);
-  const uint8_t* sdp = sd.empty() ? nullptr : sd.data();
-  const uint64_t* cop = coeffs.empty() ? nullptr : coeffs.data();
-  check(host ? pvw_shamir_shares_host(p->ctx, secrets.data(), D, degree, plain_modulus, sdp, cop, out.data())
-             : pvw_shamir_shares(p->ctx, secrets.data(), D, degree, plain_modulus, sdp, cop, out.data()));
-  return out;
+  return shamir_shares_call(p, secrets, nullptr, degree, plain_modulus, seeds, coeffs, host);
 }
 inline std::vector<PvwCiphertext> deal_ciphertexts(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& c1,
                                                    const std::vector<uint64_t>& c2, size_t D, uint32_t repr) {
@@ -635,28 +655,35 @@ inline std::vector<PvwCiphertext> deal_ciphertexts(const std::shared_ptr<PvwPara
                                 std::vector<uint64_t>(c2.begin() + d * n * P, c2.begin() + (d + 1) * n * P), p, repr});
   return out;
 }
+inline std::vector<PvwCiphertext> deal_call(const std::vector<uint64_t>& secrets, const uint32_t* pack, uint32_t degree,
+                                            uint64_t plain_modulus, const GlobalPublicKey& gpk, const std::vector<Seed>* seeds,
+                                            DeviceRandomness* rnd, uint32_t out_repr) {
+  const size_t D = shamir_dealers(secrets, pack);
+  const auto& p = gpk.params;
+  const size_t P = p->poly_words();
+  if (seeds && seeds->size() != D) throw PvwError(15, "one seed per dealer");
+  const std::vector<uint8_t> sd = seeds ? seed_bytes(*seeds) : std::vector<uint8_t>();
+  std::vector<uint64_t> c1(D * p->k * P), c2(D * p->n * P);
+  const uint64_t* se = secrets.data();
+  if (seeds)
+    check(pack ? pvw_deal_shares_packed(p->ctx, se, D, *pack, degree, plain_modulus, sd.data(), c1.data(), c2.data(), out_repr)
+               : pvw_deal_shares(p->ctx, se, D, degree, plain_modulus, sd.data(), c1.data(), c2.data(), out_repr));
+  else
+    check(pack ? pvw_deal_shares_packed_rs(p->ctx, se, D, *pack, degree, plain_modulus, rnd->raw(), c1.data(), c2.data(), out_repr)
+               : pvw_deal_shares_rs(p->ctx, se, D, degree, plain_modulus, rnd->raw(), c1.data(), c2.data(), out_repr));
+  return deal_ciphertexts(p, c1, c2, D, out_repr);
+}
 // dealer d shares secrets[d] among the n parties and encrypts the shares in ONE device call (pvw_deal_shares): what
 // encrypt of shamir_shares(...) under the same seeds returns, without the shares or coefficients existing on the host
 inline std::vector<PvwCiphertext> deal_party_shares(const std::vector<uint64_t>& secrets, uint32_t degree, uint64_t plain_modulus,
                                                     const GlobalPublicKey& gpk, const std::vector<Seed>& seeds,
                                                     uint32_t out_repr = PVW_REPR_NTT) {
-  const auto& p = gpk.params;
-  const size_t D = secrets.size(), P = p->poly_words();
-  if (seeds.size() != D) throw PvwError(15, "one seed per dealer");
-  std::vector<uint8_t> sd(D * 32);
-  for (size_t d = 0; d < D; ++d) std::copy(seeds[d].begin(), seeds[d].end(), sd.begin() + d * 32);
-  std::vector<uint64_t> c1(D * p->k * P), c2(D * p->n * P);
-  check(pvw_deal_shares(p->ctx, secrets.data(), D, degree, plain_modulus, sd.data(), c1.data(), c2.data(), out_repr));
-  return deal_ciphertexts(p, c1, c2, D, out_repr);
+  return deal_call(secrets, nullptr, degree, plain_modulus, gpk, &seeds, nullptr, out_repr);
 }
 // ... with dealer d's randomness (polynomial and encryption) from call_seed(S, c + d) of a DeviceRandomness
 inline std::vector<PvwCiphertext> deal_party_shares(const std::vector<uint64_t>& secrets, uint32_t degree, uint64_t plain_modulus,
                                                     const GlobalPublicKey& gpk, DeviceRandomness& rnd, uint32_t out_repr = PVW_REPR_NTT) {
-  const auto& p = gpk.params;
-  const size_t D = secrets.size(), P = p->poly_words();
-  std::vector<uint64_t> c1(D * p->k * P), c2(D * p->n * P);
-  check(pvw_deal_shares_rs(p->ctx, secrets.data(), D, degree, plain_modulus, rnd.raw(), c1.data(), c2.data(), out_repr));
-  return deal_ciphertexts(p, c1, c2, D, out_repr);
+  return deal_call(secrets, nullptr, degree, plain_modulus, gpk, nullptr, &rnd, out_repr);
 }
 // the secrets from the shares of the parties `indices` (at least degree + 1): shares [num_secrets][indices.size()], row-major
 inline std::vector<uint64_t> shamir_reconstruct(const std::vector<uint64_t>& indices, const std::vector<uint64_t>& shares,
@@ -751,44 +778,20 @@ inline EvaluatedShares shamir_evaluate_corrected(const std::shared_ptr<PvwParame
 inline std::vector<uint64_t> shamir_shares_packed(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& secrets,
                                                   uint32_t pack, uint32_t degree, uint64_t plain_modulus, const std::vector<Seed>& seeds,
                                                   const std::vector<uint64_t>& coeffs = {}, bool host = false) {
-  if (pack == 0 || secrets.size() % pack) throw PvwError(15, "pack secrets per dealer");
-  const size_t D = secrets.size() / pack;
-  if (!seeds.empty() && seeds.size() != D) throw PvwError(15, "one seed per dealer");
-  if (!coeffs.empty() && coeffs.size() != D * degree) throw PvwError(15, "degree coefficients per dealer");
-  std::vector<uint8_t> sd(seeds.size() * 32);
-  for (size_t d = 0; d < seeds.size(); ++d) std::copy(seeds[d].begin(), seeds[d].end(), sd.begin() + d * 32);
-  std::vector<uint64_t> out(D * p->n);
-  const uint8_t* sdp = sd.empty() ? nullptr : sd.data();
-  const uint64_t* cop = coeffs.empty() ? nullptr : coeffs.data();
-  check(host ? pvw_shamir_shares_packed_host(p->ctx, secrets.data(), D, pack, degree, plain_modulus, sdp, cop, out.data())
-             : pvw_shamir_shares_packed(p->ctx, secrets.data(), D, pack, degree, plain_modulus, sdp, cop, out.data()));
-  return out;
+  return shamir_shares_call(p, secrets, &pack, degree, plain_modulus, seeds, coeffs, host);
 }
 // dealer d shares its `pack` secrets and encrypts the shares in ONE device call (pvw_deal_shares_packed): one ciphertext per
 // `pack` secrets
 inline std::vector<PvwCiphertext> deal_party_shares_packed(const std::vector<uint64_t>& secrets, uint32_t pack, uint32_t degree,
                                                            uint64_t plain_modulus, const GlobalPublicKey& gpk,
                                                            const std::vector<Seed>& seeds, uint32_t out_repr = PVW_REPR_NTT) {
-  if (pack == 0 || secrets.size() % pack) throw PvwError(15, "pack secrets per dealer");
-  const auto& p = gpk.params;
-  const size_t D = secrets.size() / pack, P = p->poly_words();
-  if (seeds.size() != D) throw PvwError(15, "one seed per dealer");
-  std::vector<uint8_t> sd(D * 32);
-  for (size_t d = 0; d < D; ++d) std::copy(seeds[d].begin(), seeds[d].end(), sd.begin() + d * 32);
-  std::vector<uint64_t> c1(D * p->k * P), c2(D * p->n * P);
-  check(pvw_deal_shares_packed(p->ctx, secrets.data(), D, pack, degree, plain_modulus, sd.data(), c1.data(), c2.data(), out_repr));
-  return deal_ciphertexts(p, c1, c2, D, out_repr);
+  return deal_call(secrets, &pack, degree, plain_modulus, gpk, &seeds, nullptr, out_repr);
 }
 // ... with dealer d's randomness (polynomial and encryption) from call_seed(S, c + d) of a DeviceRandomness
 inline std::vector<PvwCiphertext> deal_party_shares_packed(const std::vector<uint64_t>& secrets, uint32_t pack, uint32_t degree,
                                                            uint64_t plain_modulus, const GlobalPublicKey& gpk, DeviceRandomness& rnd,
                                                            uint32_t out_repr = PVW_REPR_NTT) {
-  if (pack == 0 || secrets.size() % pack) throw PvwError(15, "pack secrets per dealer");
-  const auto& p = gpk.params;
-  const size_t D = secrets.size() / pack, P = p->poly_words();
-  std::vector<uint64_t> c1(D * p->k * P), c2(D * p->n * P);
-  check(pvw_deal_shares_packed_rs(p->ctx, secrets.data(), D, pack, degree, plain_modulus, rnd.raw(), c1.data(), c2.data(), out_repr));
-  return deal_ciphertexts(p, c1, c2, D, out_repr);
+  return deal_call(secrets, &pack, degree, plain_modulus, gpk, nullptr, &rnd, out_repr);
 }
 // the `pack` secrets of every row, [rows][pack], from the shares [rows][indices.size()] of the parties `indices` (at least
 // degree + pack of them); host only (pvw_shamir_reconstruct_packed)

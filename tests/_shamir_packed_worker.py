@@ -1,4 +1,4 @@
-"""Packed Shamir sharing on the device: shamir_eval_packed_kernel and its weights against
+"""Packed Shamir sharing on the device: shamir_eval_kernel<true> and its weights against
 pvw_shamir_shares_packed_host, the fused deal against pvw_encrypt_multi of the host shares, the _rs forms and stream capture, the
 whole loop down to the corrected sums of the valid dealers' secrets, key hygiene, staged pieces and concurrent calls.
 _shamir_worker imports torch FIRST so both libraries share one HIP runtime.  Spawned case by case by
@@ -17,11 +17,12 @@ for p_ in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
         sys.path.insert(0, p_)
 
 from _shamir_worker import DEV, S, U64, _params, dev, ptr, same, seed_bytes, system, torch, u64  # noqa: E402
+from _shamir_worker import device_shares as unpacked_device_shares  # noqa: E402
 import pvw_model as M  # noqa: E402
 import pvw_rs_amd as P  # noqa: E402
 from pvw_rs_amd import _ffi, api  # noqa: E402
 from _util import EXAMPLE_MODULI  # noqa: E402
-from test_shamir_host import P31, P61, P62, seeds_for  # noqa: E402
+from test_shamir_host import P31, P61, P62, next_prime, seeds_for  # noqa: E402
 from test_shamir_packed_host import first_prime_from, packed_secrets  # noqa: E402
 
 MARK = np.uint64(U64 - 6)
@@ -59,7 +60,7 @@ SHAPES = [
 def shares():
     """device shares == host shares at every shape, with drawn and with explicit coefficients, on a whole context and on a sharded
     one whose party_lo is no multiple of 64 (its other columns keep what the buffer held), device-pointer and host-buffer forms;
-    pack = 1 equals pvw_shamir_shares_device"""
+    pack = 1 equals pvw_shamir_shares_device, and on the chunk edges of its term axis both equal pvw_shamir_shares_host"""
     rng = random.Random(1)
     s = torch.cuda.Stream(device=DEV)
     for n, (lo, hi), Ds, kts in SHAPES:
@@ -84,13 +85,24 @@ def shares():
                             hb = P.shamir_shares_packed(part, secrets, t, pm, **kw)
                             assert np.array_equal(hb[:, lo:hi], want[:, lo:hi]) and not hb[:, :lo].any() and not hb[:, hi:].any(), tag
         print(f"shares n={n} ok", flush=True)
-    # pack = 1: the packed kernel gives the words of shamir_eval_kernel
+    # pack = 1: the packed instantiation gives the words of the unpacked one
     n, D, pm = 100, 70, P62
     p = _params(n)
     for t in (0, 1, 50, 99):
         secrets, seeds = [rng.getrandbits(64) for _ in range(D)], seeds_for(D, tag=t)
         old = P.shamir_shares(p, secrets, t, pm, seeds=seeds)
         assert np.array_equal(device_shares(p, [[x] for x in secrets], t, pm, seeds=seeds if t else None, stream=s), old), ("pack 1", t)
+    # ... and on the chunk edges of the unpacked term axis (_shamir_worker.shares), both equal to the host restatement
+    n, D = 300, 5
+    p = _params(n)
+    for t in (255, 256, 257):
+        for pm in (next_prime(n), P62):
+            secrets, seeds = [rng.getrandbits(64) for _ in range(D)], seeds_for(D, tag=t)
+            coeffs = [[pm - 1] * t] + [[rng.getrandbits(64) for _ in range(t)] for _ in range(D - 1)]
+            for what, kw in (("drawn", dict(seeds=seeds)), ("explicit", dict(coeffs=coeffs))):
+                want = P.shamir_shares(p, secrets, t, pm, host=True, **kw)
+                assert np.array_equal(unpacked_device_shares(p, secrets, t, pm, stream=s, **kw), want), ("chunk edge unpacked", what, pm, t)
+                assert np.array_equal(device_shares(p, [[x] for x in secrets], t, pm, stream=s, **kw), want), ("chunk edge pack 1", what, pm, t)
     print("shares pack=1 ok", flush=True)
 
 

@@ -1,4 +1,4 @@
-"""Shamir shares on the device: shamir_eval_kernel against pvw_shamir_shares_host, the fused deal against
+"""Shamir shares on the device: shamir_eval_kernel<false> against pvw_shamir_shares_host, the fused deal against
 pvw_encrypt_multi of the host shares, the _rs forms and stream capture, the whole loop down to the reconstructed sum of the valid
 dealers' secrets, and key hygiene.  torch is imported FIRST so both libraries share one HIP runtime.  Spawned case by case by
 tests/test_gpu_shamir.py; prints SHAMIR_OK."""
@@ -72,7 +72,8 @@ def device_shares(p, secrets, t, pm, seeds=None, coeffs=None, stream=None, fill=
 def shares():
     """device shares == host shares: the grid of the host test (every p, degree, n, D of the contract), drawn and explicit
     coefficients, unreduced words, n not a multiple of 64, D beyond one launch (64 keys) and beyond one pass (128 dealers), the
-    device-pointer form on a caller's stream and the host-buffer form; a sharded context writes its own columns only"""
+    device-pointer form on a caller's stream and the host-buffer form; degrees that put a wave's term range on a chunk edge; a
+    sharded context writes its own columns only"""
     rng = random.Random(1)
     s = torch.cuda.Stream(device=DEV)
     for n in (3, 64, 100, 1000):
@@ -96,6 +97,18 @@ def shares():
                         if t == n - 1:
                             assert np.array_equal(P.shamir_shares(p, secrets, t, pm, coeffs=coeffs), want), ("explicit host-buffer", n, D, pm)
         print(f"shares n={n} ok", flush=True)
+    # a wave's term range on a chunk edge (SH_JC = 64 terms per wave and chunk, Q = ceil(t / 4)): at t = 255 the last wave is one
+    # term short of a full chunk, at 256 every wave holds exactly one, at 257 Q = 65 and wave 3 has no term in the second chunk
+    n, D = 300, 5
+    p = _params(n)
+    for t in (255, 256, 257):
+        for pm in (next_prime(n), P62):
+            secrets, seeds = secrets_for(D, pm, rng), seeds_for(D, tag=t)
+            coeffs = [[pm - 1] * t] + [[rng.getrandbits(64) for _ in range(t)] for _ in range(D - 1)]
+            for what, kw in (("drawn", dict(seeds=seeds)), ("explicit", dict(coeffs=coeffs))):
+                want = P.shamir_shares(p, secrets, t, pm, host=True, **kw)
+                assert np.array_equal(device_shares(p, secrets, t, pm, stream=s, **kw), want), ("chunk edge", what, pm, t)
+    print("shares chunk edges ok", flush=True)
     # sharded: columns [party_lo, party_hi) are written, the others keep what the buffer held
     n, D, t, pm = 200, 70, 77, P61
     lo, hi = 37, 171

@@ -1,5 +1,5 @@
 """Packed Shamir sharing on the device (pvw_shamir_shares_packed*, pvw_deal_shares_packed*), bit for bit:
-shamir_eval_packed_kernel and the device-made weights against pvw_shamir_shares_packed_host at the shapes where the kernel can
+shamir_eval_kernel<true> and the device-made weights against pvw_shamir_shares_packed_host at the shapes where the kernel can
 go wrong (fewer terms than waves, the secret/random boundary on a wave edge, inside a wave's range and on a chunk edge, several
 chunks, D beyond one launch, sharded contexts whose first party is no multiple of 64; drawn and explicit coefficients); the fused
 deal against pvw_encrypt_multi of the host shares; the _rs forms, their counter and stream capture; the loop closed down to the

@@ -13,7 +13,7 @@ HIP events; the order rotates from round to round.  One JSON line per case: medi
 Packed dealing at config 3: the same S secrets dealt by pvw_deal_shares_packed_device at pack 1, 16 and 64
 (D = S / pack dealers, degree n / 2 - pack) beside pvw_deal_shares_device (D = S, degree n / 2 - 1), the share calls alone
 (pvw_shamir_shares_device, pvw_shamir_shares_packed_device), and from a profiled pass the part of each packed deal spent in
-shamir_eval_packed_kernel and in the weights kernels.  One JSON line."""
+shamir_eval_kernel<true> and in the weights kernels.  One JSON line."""
 import ctypes as C
 import json
 import os
