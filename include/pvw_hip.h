@@ -35,7 +35,8 @@
  *     tests/test_gpu_shamir_evaluate.py),
  *     pvw_decrypt_batch / _checked / _plain, pvw_decrypt_all / _checked / _plain, pvw_ct_sum, pvw_decrypt_sum_checked,
  *     pvw_decrypt_all_sum_checked, pvw_ct_lincomb, pvw_decrypt_lincomb_plain, pvw_decrypt_all_lincomb_plain (the concurrent
- *     calls of these three: tests/test_gpu_ct_lincomb.py), pvw_decode / _checked / _plain, pvw_wire_pack / _unpack, pvw_ntt_forward / _inverse,
+ *     calls of these three: tests/test_gpu_ct_lincomb.py), pvw_ct_lincomb_many, pvw_decrypt_all_lincomb_many_plain (the concurrent
+ *     calls of these two, R = 1 and R > 1: tests/test_gpu_ct_lincomb_many.py), pvw_decode / _checked / _plain, pvw_wire_pack / _unpack, pvw_ntt_forward / _inverse,
  *     pvw_sample_cbd / _uniform / _gaussian, pvw_sk_load / pvw_sk_free, and *_device calls that each thread enqueues on a
  *     stream of its own -- the context's first calls included (device initialisation and the derived copies are built
  *     once, under a lock).  Every result is the serial one bit for bit, pvw_last_error stays the calling thread's, and a
@@ -623,6 +624,57 @@ PVW_API int32_t pvw_ctx_lincomb_fits(const pvw_ctx* ctx, const int64_t* weights,
  * mod p = plain_modulus, CENTRED in (-p/2, p/2] (so that it enlarges the noise as little as its residue class allows).  The routine
  * and the argument rules of pvw_shamir_reconstruct below: p prime and < 2^62, no duplicate index, every index < p - 1, count >= 1. */
 PVW_API int32_t pvw_shamir_lagrange_weights(uint64_t plain_modulus, const uint64_t* indices, size_t count, int64_t* weights_out);
+
+/* ---- many weighted sums of the same dealers' ciphertexts in one pass: R = num_combos rows of weights over one set
+ * of D ciphertexts -- the handover of a PACKED sharing (one row per slot: the Lagrange weights at the point -m of the valid old
+ * points), batched random-combination checks, the re-dealt polynomials' values at several points.  weights: int64_t [R][D], row-major,
+ * each row under the per-weight rules above.  Dealer d PARTICIPATES IN COMBINATION r when it is valid and weights[r][d] != 0;
+ * counts[r] (may be NULL) is the number of such dealers.  A dealer that is not valid, or whose weight is 0 in every row, is never
+ * read.  Results: c1_out [R][k][L][l], c2_out [R][row_hi - row_lo][L][l]; row r is, bit for bit on every word and on counts[r], what
+ * the pvw_ct_lincomb* call of the same form returns with weights + r * D (any 64-bit input word, both representations); a row with no
+ * participant is all zeros with counts[r] = 0, in every form.  num_combos = 1 is that call, through its kernel.  Each ciphertext is
+ * read once per tile of rows, and crosses the bus once in the host-buffer forms.
+ * Refused with PVW_ERR_INVALID_PARAMETERS before any device work, nothing written: what the mirrored pvw_ct_lincomb* /
+ * pvw_decrypt_all_lincomb_plain* call refuses, with its text; num_combos = 0; on the device forms num_combos >= 2^31.  The host-buffer
+ * forms return PVW_ERR_INSUFFICIENT_DATA only when no dealer participates in ANY row. */
+/* Host only, no context: weights_out [num_targets][count]; row j = the Lagrange weights AT the point (targets[j] + 1) mod p of the
+ * points indices[i] + 1, centred in (-p/2, p/2].  targets[j] < p (p - 1 is the point 0: that row equals
+ * pvw_shamir_lagrange_weights; p - 1 - m is the point -m).  A target that is one of the indices gives that unit vector.
+ * Duplicate targets allowed.  Otherwise the rules of pvw_shamir_lagrange_weights, plus NULL targets / num_targets = 0 refused. */
+PVW_API int32_t pvw_shamir_lagrange_weights_at(uint64_t plain_modulus, const uint64_t* indices, size_t count, const uint64_t* targets,
+                                               size_t num_targets, int64_t* weights_out);
+/* the definition in plain loops on the host cores (no GPU needed): the loop of pvw_ct_lincomb_host over the rows */
+PVW_API int32_t pvw_ct_lincomb_many_host(const pvw_ctx* ctx, const uint64_t* c1s, const uint64_t* c2s, size_t num_dealers,
+                                         const uint8_t* valid, const int64_t* weights, size_t num_combos, uint32_t row_lo,
+                                         uint32_t row_hi, uint64_t* c1_out, uint64_t* c2_out, uint32_t* counts);
+/* device pointers (d_weights [R][D] and d_counts [R] too), asynchronous on `stream`, straight into the caller's buffers; mask and
+ * weights are read when the kernels run.  pvw_prepare(PVW_PREPARE_SUM) and stream capture exactly as pvw_ct_lincomb_device. */
+PVW_API int32_t pvw_ct_lincomb_many_device(pvw_ctx* ctx, const uint64_t* d_c1s, const uint64_t* d_c2s, size_t num_dealers,
+                                           const uint8_t* d_valid, const int64_t* d_weights, size_t num_combos, uint32_t row_lo,
+                                           uint32_t row_hi, uint64_t* d_c1_out, uint64_t* d_c2_out, uint32_t* d_counts, void* stream);
+/* host buffers (synchronous): a dealer is staged when it participates in at least one row */
+PVW_API int32_t pvw_ct_lincomb_many(pvw_ctx* ctx, const uint64_t* c1s, const uint64_t* c2s, size_t num_dealers, const uint8_t* valid,
+                                    const int64_t* weights, size_t num_combos, uint32_t row_lo, uint32_t row_hi, uint64_t* c1_out,
+                                    uint64_t* c2_out, uint32_t* counts);
+/* pvw_decrypt_all_lincomb_plain[_device] with `num_combos` directly after the weights and `counts` [R] in place of `count`:
+ * out / noise / status [P][R], wide [P][R][wide_words] -- the [party][dealer] layout of pvw_decrypt_all* with the combinations in the
+ * dealers' place, so strides (1, R) feed pvw_shamir_reconstruct_checked* in place.  Column r equals the num_combos = 1 call.  The
+ * combined ciphertexts (public) live in the stream's scratch and ONE decrypt of all of them follows.  Under stream capture the
+ * device form needs that scratch sized already: by an earlier call on that stream OUTSIDE capture with the same party range and at
+ * least as many combinations; otherwise PVW_ERR_INVALID_PARAMETERS with nothing enqueued (pvw_prepare does not size it).
+ * The packed handover: weights = pvw_shamir_lagrange_weights_at over the valid old indices with targets p - 1 - m, m < K (0 at the
+ * other dealers); out[j][m] is new party j's share of secret m. */
+PVW_API int32_t pvw_decrypt_all_lincomb_many_plain_device(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* d_sk,
+                                                          const uint64_t* d_c1s, const uint64_t* d_c2s, size_t num_dealers,
+                                                          const uint8_t* d_valid, const int64_t* d_weights, size_t num_combos,
+                                                          uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status,
+                                                          uint32_t* d_counts, uint64_t plain_modulus, uint32_t wide_words,
+                                                          uint64_t* d_wide, void* stream);
+PVW_API int32_t pvw_decrypt_all_lincomb_many_plain(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* sk,
+                                                   const uint64_t* c1s, const uint64_t* c2s, size_t num_dealers, const uint8_t* valid,
+                                                   const int64_t* weights, size_t num_combos, uint32_t in_repr, uint64_t* out_u64,
+                                                   uint64_t* noise, uint32_t* status, uint32_t* counts, uint64_t plain_modulus,
+                                                   uint32_t wide_words, uint64_t* wide);
 
 /* ---- Shamir shares: from secrets to ciphertexts in one call, and back --------------------------------------
  * The dealing end of the protocol the reference's examples sketch (examples/pvw.rs:95-131 fill the share matrix with arbitrary

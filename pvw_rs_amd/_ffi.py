@@ -121,6 +121,12 @@ _SIGNATURES = {
     "pvw_decrypt_all_lincomb_plain_device": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P],
     "pvw_ctx_lincomb_fits": [_P, _P, C.c_size_t, _P, C.POINTER(C.c_uint32)],
     "pvw_shamir_lagrange_weights": [C.c_uint64, _P, C.c_size_t, _P],
+    "pvw_shamir_lagrange_weights_at": [C.c_uint64, _P, C.c_size_t, _P, C.c_size_t, _P],
+    "pvw_ct_lincomb_many_host": [_P, _P, _P, C.c_size_t, _P, _P, C.c_size_t, C.c_uint32, C.c_uint32, _P, _P, _P],
+    "pvw_ct_lincomb_many_device": [_P, _P, _P, C.c_size_t, _P, _P, C.c_size_t, C.c_uint32, C.c_uint32, _P, _P, _P, _P],
+    "pvw_ct_lincomb_many": [_P, _P, _P, C.c_size_t, _P, _P, C.c_size_t, C.c_uint32, C.c_uint32, _P, _P, _P],
+    "pvw_decrypt_all_lincomb_many_plain_device": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P],
+    "pvw_decrypt_all_lincomb_many_plain": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P],
     # plain-modulus decode: the checked call plus (plain_modulus, wide_words, wide)
     "pvw_decode_plain": [_P, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.c_uint32, _P],
     "pvw_decode_plain_device": [_P, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P],

@@ -1491,6 +1491,90 @@ def shamir_lagrange_weights(indices: Sequence[int], plain_modulus: int) -> List[
     return [int(x) for x in out]
 
 
+# ---- many combinations of the same dealers' ciphertexts ----
+def shamir_lagrange_weights_at(indices: Sequence[int], targets: Sequence[int], plain_modulus: int) -> List[List[int]]:
+    """Row j: the Lagrange weights AT the point (targets[j] + 1) mod plain_modulus of the points indices[i] + 1, centred in
+    (-p/2, p/2] (pvw_shamir_lagrange_weights_at; host only).  The target p - 1 is the point 0 (shamir_lagrange_weights), p - 1 - m
+    the point -m; a target that is one of the indices gives that unit vector."""
+    idx, tg = _words(indices), _words(targets)
+    out = np.zeros((len(tg), len(idx)), dtype=np.int64)
+    _check(_ffi.lib().pvw_shamir_lagrange_weights_at(int(plain_modulus), _ptr(idx), len(idx), _ptr(tg), len(tg), _ptr(out)))
+    return [[int(x) for x in row] for row in out]
+
+
+def shamir_packed_handover_weights(indices: Sequence[int], plain_modulus: int, pack: int) -> List[List[int]]:
+    """The weight rows of a packed sharing's handover: row m = the Lagrange weights at the point -m (secret m of
+    shamir_shares_packed) of the old holders `indices`, m < pack."""
+    p = int(plain_modulus)
+    return shamir_lagrange_weights_at(indices, [p - 1 - m for m in range(int(pack))], p)
+
+
+def _weight_rows(weight_rows, D: int, v) -> np.ndarray:
+    """int64 [R][D]; at least one row, and at least one dealer that takes part in some row"""
+    rows = [[int(x) for x in row] for row in weight_rows]
+    if len(rows) == 0:
+        raise PvwError(1, "num_combos must be at least 1")
+    for r, row in enumerate(rows):
+        if len(row) != D:
+            raise PvwError(15, f"weight_rows[{r}]: expected {D} weights, got {len(row)}")
+        for d, x in enumerate(row):
+            if not -(1 << 63) <= x < 1 << 63:
+                raise PvwError(1, f"weight_rows[{r}][{d}] = {x} is outside the int64 range")
+    w = np.ascontiguousarray(np.array(rows, dtype=np.int64).reshape(len(rows), D))
+    if not ((w != 0).any(axis=0) & (True if v is None else v != 0)).any():
+        raise PvwError(17, f"No participating dealer (valid, weight not 0) among the {D} ciphertexts: expected at least 1, got 0")
+    return w
+
+
+def combine_ciphertexts_many(cts: Sequence[PvwCiphertext], weight_rows, valid=None, *, host: bool = False) -> List[PvwCiphertext]:
+    """One combination per row of weight_rows [R][D] over the same ciphertexts (pvw_ct_lincomb_many): element r is
+    combine_ciphertexts(cts, weight_rows[r], valid) bit for bit -- all zeros for a row nobody takes part in -- with every
+    ciphertext read once per tile of rows and uploaded once.  host=True: pvw_ct_lincomb_many_host, no GPU."""
+    p, repr, v = _sum_inputs(cts, valid)
+    w = _weight_rows(weight_rows, len(cts), v)
+    R = w.shape[0]
+    c1s = np.ascontiguousarray(np.stack([ct.c1 for ct in cts]), dtype=np.uint64)
+    c2s = np.ascontiguousarray(np.stack([ct.c2 for ct in cts]), dtype=np.uint64)
+    c1 = np.zeros((R, p.k, p.L, p.l), dtype=np.uint64)
+    c2 = np.zeros((R, p.n, p.L, p.l), dtype=np.uint64)
+    p._call("pvw_ct_lincomb_many_host" if host else "pvw_ct_lincomb_many", _ptr(c1s), _ptr(c2s), len(cts), _ptr(v), _ptr(w), R, 0, p.n,
+            _ptr(c1), _ptr(c2), None)
+    return [PvwCiphertext(c1[r], c2[r], p, repr) for r in range(R)]
+
+
+def decrypt_all_party_combinations_many(cts: Sequence[PvwCiphertext], weight_rows, parties: Sequence["Party"], valid=None,
+                                        plain_modulus: Optional[int] = None, wide: bool = False, *,
+                                        bound: Optional[int] = None) -> CheckedDecryption:
+    """Every party's share of every combination in one call (pvw_decrypt_all_lincomb_many_plain): arrays of shape
+    [len(parties)][R], column r what decrypt_all_party_combinations gives with weight_rows[r].  With
+    shamir_packed_handover_weights and plain_modulus = p: values[j][m] is new party j's share of the packed sharing's secret m.
+    `valid` of the report follows the rule of decrypt_party_combination row by row; .bound is the largest row's."""
+    p, repr, v = _sum_inputs(cts, valid)
+    w = _weight_rows(weight_rows, len(cts), v)
+    R, NP = w.shape[0], len(parties)
+    lo = parties[0].index if NP else 0
+    for i, party in enumerate(parties):
+        if party.index >= p.n:
+            raise PvwError(1, f"Party index {party.index} exceeds maximum {p.n - 1}")
+        if party.index != lo + i:
+            raise PvwError(1, f"Party indices must be consecutive: {party.index} follows {lo + i - 1}")
+    out, noise, status = np.zeros((NP, R), np.uint64), np.zeros((NP, R), np.uint64), np.zeros((NP, R), np.uint32)
+    on, m, ww, wd = _plain(p, plain_modulus, wide, out.shape) if NP else (False, 0, 0, None)
+    if NP:
+        c1s = np.ascontiguousarray(np.stack([ct.c1 for ct in cts]), dtype=np.uint64)
+        c2s = np.ascontiguousarray(np.stack([ct.c2 for ct in cts]), dtype=np.uint64)
+        sk = np.ascontiguousarray(np.stack([_i64(party.secret_key.secret_coeffs) for party in parties]))
+        try:
+            p._call("pvw_decrypt_all_lincomb_many_plain", lo, lo + NP, _ptr(sk), _ptr(c1s), _ptr(c2s), len(cts), _ptr(v), _ptr(w), R,
+                    repr, _ptr(out), _ptr(noise), _ptr(status), None, m, ww, _ptr(wd))
+        finally:
+            sk.fill(0)                                                     # the stacked copy of the keys (secret_key.rs:20-30)
+    rows = [_lincomb_report(p, out[:, r], noise[:, r], status[:, r], w[r], v, bound, on, None) for r in range(R)]
+    rep = CheckedDecryption(out, noise, status, max(x.bound for x in rows), on, wd)
+    rep.valid = np.stack([x.valid for x in rows], axis=1) if NP else np.zeros((0, R), dtype=bool)
+    return rep
+
+
 def _dptr(x):
     """a device buffer: a torch tensor (its data_ptr()), a raw address as an int, or None"""
     if x is None:

@@ -2271,6 +2271,30 @@ static int32_t shamir_weights_at_zero(uint64_t plain_modulus, const uint64_t* in
   wout->swap(w);
   return PVW_OK;
 }
+// W[j][i] = the Lagrange weight AT the point z[j] (a residue) of x_i = indices[i] + 1 among the count points, in [0, p):
+// u_i = (prod_{k != i}(x_i - x_k))^-1 once per source point (the barycentric weights), then per target
+// u_i prod_{k != i}(z_j - x_k) from prefix and suffix products.  z_j = x_i gives the unit vector by itself.
+static void shamir_weights_at_points(const Mod& m, const u64* indices, size_t count, const std::vector<u64>& z, std::vector<u64>* Wout) {
+  std::vector<u64> u(count), W(z.size() * count), suf(count + 1);
+  for (size_t i = 0; i < count; ++i) {
+    u64 den = 1;
+    for (size_t k = 0; k < count; ++k)
+      if (k != i) den = mulmod(den, submod(indices[i] + 1, indices[k] + 1, m.q), m);
+    u[i] = powmod(den, m.q - 2, m);
+  }
+  for (size_t j = 0; j < z.size(); ++j) {
+    suf[count] = 1;                                            // suf[i] = prod_{k >= i}(z - x_k)
+    for (size_t i = count; i-- > 0;) suf[i] = mulmod(suf[i + 1], submod(z[j], indices[i] + 1, m.q), m);
+    u64 pre = 1;                                               // prod_{k < i}(z - x_k)
+    for (size_t i = 0; i < count; ++i) {
+      W[j * count + i] = mulmod(mulmod(pre, suf[i + 1], m), u[i], m);
+      pre = mulmod(pre, submod(z[j], indices[i] + 1, m.q), m);
+    }
+  }
+  Wout->swap(W);
+}
+// the residue w in [0, q) centred in (-q/2, q/2]
+static i64 centred(u64 w, u64 q) { return w > q / 2 ? -(i64)(q - w) : (i64)w; }
 // The weights once; then one dot product per secret.  Host only.
 int32_t pvw_shamir_reconstruct(uint64_t plain_modulus, const uint64_t* indices, const uint64_t* shares, size_t count,
                                size_t num_secrets, uint64_t* out) {
@@ -2292,7 +2316,24 @@ int32_t pvw_shamir_lagrange_weights(uint64_t plain_modulus, const uint64_t* indi
   Mod m;
   std::vector<u64> w;
   PVW_TRY(shamir_weights_at_zero(plain_modulus, indices, count, &m, &w));
-  for (size_t i = 0; i < count; ++i) weights_out[i] = w[i] > m.q / 2 ? -(i64)(m.q - w[i]) : (i64)w[i];
+  for (size_t i = 0; i < count; ++i) weights_out[i] = centred(w[i], m.q);
+  return PVW_OK;
+}
+// The weights AT any points: row j for the point (targets[j] + 1) mod p -- p - 1 is the point 0, p - 1 - m the point
+// -m of a packed sharing's secret m.  Host only.
+int32_t pvw_shamir_lagrange_weights_at(uint64_t plain_modulus, const uint64_t* indices, size_t count, const uint64_t* targets,
+                                       size_t num_targets, int64_t* weights_out) {
+  if (!indices || !targets || !weights_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (count == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no shares to reconstruct from");
+  if (num_targets == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no target points");
+  PVW_TRY(shamir_index_checks(plain_modulus, indices, count, true));
+  for (size_t j = 0; j < num_targets; ++j)
+    if (targets[j] >= plain_modulus) return fail(PVW_ERR_INVALID_PARAMETERS, "target index out of range for plain_modulus");
+  const Mod m = shamir_mod(plain_modulus);
+  std::vector<u64> z(num_targets), W;
+  for (size_t j = 0; j < num_targets; ++j) z[j] = targets[j] + 1 == m.q ? 0 : targets[j] + 1;
+  shamir_weights_at_points(m, indices, count, z, &W);
+  for (size_t i = 0; i < num_targets * count; ++i) weights_out[i] = centred(W[i], m.q);
   return PVW_OK;
 }
 
@@ -2309,24 +2350,9 @@ int32_t pvw_shamir_reconstruct_packed(uint64_t plain_modulus, uint32_t pack, con
     if (plain_modulus < pack || indices[i] >= plain_modulus - pack)
       return fail(PVW_ERR_INVALID_PARAMETERS, "party index out of range for plain_modulus and pack");
   const Mod m = shamir_mod(plain_modulus);
-  // u_i = (prod_{k != i}(x_i - x_k))^-1; W[j][i] = u_i prod_{k != i}(z_j - x_k), z_j = -j
-  std::vector<u64> u(count), W((size_t)pack * count), suf(count + 1);
-  for (size_t i = 0; i < count; ++i) {
-    u64 den = 1;
-    for (size_t k = 0; k < count; ++k)
-      if (k != i) den = mulmod(den, submod(indices[i] + 1, indices[k] + 1, m.q), m);
-    u[i] = powmod(den, m.q - 2, m);
-  }
-  for (u32 j = 0; j < pack; ++j) {
-    const u64 z = j ? m.q - j : 0;
-    suf[count] = 1;                                            // suf[i] = prod_{k >= i}(z - x_k)
-    for (size_t i = count; i-- > 0;) suf[i] = mulmod(suf[i + 1], submod(z, indices[i] + 1, m.q), m);
-    u64 pre = 1;                                               // prod_{k < i}(z - x_k)
-    for (size_t i = 0; i < count; ++i) {
-      W[(size_t)j * count + i] = mulmod(mulmod(pre, suf[i + 1], m), u[i], m);
-      pre = mulmod(pre, submod(z, indices[i] + 1, m.q), m);
-    }
-  }
+  std::vector<u64> z(pack), W;
+  for (u32 j = 0; j < pack; ++j) z[j] = j ? m.q - j : 0;
+  shamir_weights_at_points(m, indices, count, z, &W);
   for (size_t r = 0; r < num_rows; ++r)
     for (u32 j = 0; j < pack; ++j) {
       u64 acc = 0;
@@ -4270,7 +4296,8 @@ static AllLayout decrypt_all_layout(const pvw_ctx* c, size_t NP, size_t D, bool 
   return a;
 }
 // The shape of one call, as both sides take it.  host: sk / c1s / c2s / rep are host buffers; otherwise device pointers on `s`.
-// rep: [P][D], on the same side.
+// rep: [P][D], on the same side; rep_ld: results between consecutive parties when the call fills a block of
+// columns of a wider report (0: D).
 struct AllCall {
   u32 lo;
   size_t NP, D;
@@ -4278,6 +4305,8 @@ struct AllCall {
   const u64 *c1s, *c2s;
   bool host, power;
   Report rep;
+  size_t rep_ld = 0;
+  size_t ld() const { return rep_ld ? rep_ld : D; }
 };
 // ---- party by party
 static int32_t decrypt_all_by_party(pvw_ctx* c, Workspace* w, hipStream_t s, const AllLayout& a, const AllCall& q) {
@@ -4315,7 +4344,7 @@ static int32_t decrypt_all_by_party(pvw_ctx* c, Workspace* w, hipStream_t s, con
       const int32_t rm = decrypt_mac_only(c, w, c1, d_c2, cnt, d_nz, s, &ntt_domain);          // decryption.rs:257-274
       if (w->dpart && (p == 0 || rm != PVW_OK)) ws_mark_secret(w, w->dpart, w->dpart_bytes);   // range sums of s-hat c1
       PVW_TRY(rm);
-      const Report to = q.rep.at(p * D + d0);
+      const Report to = q.rep.at(p * q.ld() + d0);
       PVW_TRY(decode_tail(c, d_nz, cnt, ntt_domain, false, s, q.host ? dev : to));
       if (q.host) PVW_TRY(dev.copy_to(to, cnt, hipMemcpyDeviceToHost, s, true));
     }
@@ -4389,7 +4418,7 @@ static int32_t decrypt_all_gemm(pvw_ctx* c, Workspace* w, hipStream_t s, const A
       }
       PVW_TRY(decode_tail(c, d_nz, (size_t)pc * dg, true, false, s, dev));
       // results[recipient][dealer] (examples/pvw.rs:157-170): the chunk's [pc][dg] block into out[p0..][d0..]
-      PVW_TRY(dev.copy_block_to(q.rep.at(p0 * D + d0), pc, dg, D, kout, s));
+      PVW_TRY(dev.copy_block_to(q.rep.at(p0 * q.ld() + d0), pc, dg, q.ld(), kout, s));
     }
   }
   return PVW_OK;
@@ -4508,9 +4537,12 @@ static int32_t sum_prepare(pvw_ctx* c, Workspace* w, hipStream_t s) {
 // c2: the first polynomial summed of dealer 0 -- c2s + row_lo L l with c2_stride = n L l (whole ciphertexts), or a party's
 // column with c2_stride = L l -- `rows` polynomials per dealer; c1_stride = k L l.  valid / count: device pointers (or NULL).
 // weights: NULL = the sum (ct_sum_kernel); else device words [D], the weighted form of DESIGN 8.12 (ct_lincomb_kernel).
+// Many combinations: m.R > 1 rows of weights, m.wstride words apart; row r's result m.c1_stride / m.c2_stride words
+// behind c1_out / c2_out and its count in count[r] (ct_lincomb_many_kernel, one pass over the dealers per row tile).
+struct Combos { size_t R = 1, wstride = 0, c1_stride = 0, c2_stride = 0; };
 static int32_t ct_sum_enqueue(pvw_ctx* c, Workspace* w, hipStream_t s, const u64* c1s, const u64* c2, size_t c2_stride, size_t rows,
                               size_t D, const uint8_t* valid, const i64* weights, u64* c1_out, u64* c2_out, u32* count,
-                              bool accumulate = false) {
+                              bool accumulate = false, const Combos& m = Combos()) {
   const size_t P = c->poly();
   SumRegion a, b;
   a.in = c1s; a.out = c1_out; a.stride = (size_t)c->k * P; a.items = (size_t)c->k * P / 2;
@@ -4518,6 +4550,14 @@ static int32_t ct_sum_enqueue(pvw_ctx* c, Workspace* w, hipStream_t s, const u64
   const size_t items = a.items + b.items;
   u32 ns = ct_sum_slices(items, D);
   if ((size_t)ns * items > ct_sum_partial_items_max()) ns = (u32)(ct_sum_partial_items_max() / items);   // a forced count (tuning build)
+  if (weights && m.R > 1) {                                        // a row tile's slice planes share the partial region
+    const size_t tile = ct_lincomb_many_tile(items, ns);
+    if ((size_t)ns * tile * items > ct_sum_partial_items_max()) ns = (u32)(ct_sum_partial_items_max() / (tile * items));
+    ProfScope ps(c, "ct_lincomb_many", s);
+    PVW_HIP(launch_ct_lincomb_many(a, b, m.c1_stride, m.c2_stride, valid, weights, m.wstride, m.R, D, c->dt, c->L, c->l,
+                                   ns > 1 ? w->sumbuf : nullptr, ns, accumulate, count, s));
+    return PVW_OK;
+  }
   if (weights) {                                                   // the weighted form: weights device words [D]
     ProfScope ps(c, "ct_lincomb", s);
     PVW_HIP(launch_ct_lincomb(a, b, valid, weights, D, c->dt, c->L, c->l, ns > 1 ? w->sumbuf : nullptr, ns, accumulate, count, s));
@@ -4530,6 +4570,17 @@ static int32_t ct_sum_enqueue(pvw_ctx* c, Workspace* w, hipStream_t s, const u64
 // a dealer takes part when it is valid and, in the weighted form (weights != NULL), its weight is not 0
 static bool takes_part(const uint8_t* valid, const i64* weights, size_t d) {
   return (!valid || valid[d]) && (!weights || weights[d] != 0);
+}
+// ... in at least one of the R combinations, weights [R][D]
+static bool takes_part_any(const uint8_t* valid, const i64* weights, size_t d, size_t R, size_t D) {
+  for (size_t r = 0; r < R; ++r)
+    if (takes_part(valid, weights ? weights + r * D : nullptr, d)) return true;
+  return false;
+}
+static size_t count_valid_any(const uint8_t* valid, const i64* weights, size_t D, size_t R) {
+  size_t nv = 0;
+  for (size_t d = 0; d < D; ++d) nv += takes_part_any(valid, weights, d, R, D);
+  return nv;
 }
 static size_t count_valid(const uint8_t* valid, const i64* weights, size_t D) {
   if (!valid && !weights) return D;
@@ -4548,10 +4599,12 @@ static int32_t no_valid_dealer(size_t D, const i64* weights) {
 // host buffers: runs of valid dealers are copied next to each other into st_c1 [per][k] / st_c2 [per][rows] and every full
 // piece is summed into d_c1_out / d_c2_out (the first piece stores, the later ones add); masked-out dealers are not copied.
 // The weighted form (weights != NULL, host words [D]): the dealers that take part are staged, and the weights of the staged
-// runs travel with each piece into st_w [per].
+// runs travel with each piece into st_w [per].  Many combinations (R > 1, weights [R][D]): a dealer is staged when
+// it takes part in at least one row, so the ciphertexts cross once whatever R is; the weights travel as st_w [R][per], and row
+// r's result lies c1_ostride / c2_ostride words behind d_c1_out / d_c2_out.
 static int32_t ct_sum_staged(pvw_ctx* c, Workspace* w, u64* st_c1, u64* st_c2, size_t per, const u64* c1s, const u64* c2,
                              size_t c2_stride, size_t rows, size_t D, const uint8_t* valid, const i64* weights, i64* st_w,
-                             u64* d_c1_out, u64* d_c2_out) {
+                             u64* d_c1_out, u64* d_c2_out, size_t R = 1, size_t c1_ostride = 0, size_t c2_ostride = 0) {
   const size_t P = c->poly(), ctw = (size_t)c->k * P;
   hipStream_t s = w->stream;
   size_t fill = 0;
@@ -4559,16 +4612,17 @@ static int32_t ct_sum_staged(pvw_ctx* c, Workspace* w, u64* st_c1, u64* st_c2, s
   auto flush = [&]() -> int32_t {
     if (!fill) return PVW_OK;
     PVW_TRY(ct_sum_enqueue(c, w, s, st_c1, st_c2, rows * P, rows, fill, nullptr, weights ? st_w : nullptr, d_c1_out, d_c2_out, nullptr,
-                           !first));
+                           !first, Combos{R, per, c1_ostride, c2_ostride}));
     first = false;
     fill = 0;
     return PVW_OK;
   };
   for (size_t d = 0; d < D;) {
-    if (!takes_part(valid, weights, d)) { ++d; continue; }
+    if (!takes_part_any(valid, weights, d, R, D)) { ++d; continue; }
     size_t run = 1;
-    while (d + run < D && fill + run < per && takes_part(valid, weights, d + run)) ++run;
-    if (weights) PVW_HIP(hipMemcpyAsync(st_w + fill, weights + d, run * 8, hipMemcpyHostToDevice, s));
+    while (d + run < D && fill + run < per && takes_part_any(valid, weights, d + run, R, D)) ++run;
+    if (weights && R == 1) PVW_HIP(hipMemcpyAsync(st_w + fill, weights + d, run * 8, hipMemcpyHostToDevice, s));
+    if (weights && R > 1) PVW_HIP(hipMemcpy2DAsync(st_w + fill, per * 8, weights + d, D * 8, run * 8, R, hipMemcpyHostToDevice, s));
     PVW_HIP(hipMemcpyAsync(st_c1 + fill * ctw, c1s + d * ctw, run * ctw * 8, hipMemcpyHostToDevice, s));
     PVW_HIP(hipMemcpy2DAsync(st_c2 + fill * rows * P, rows * P * 8, c2 + d * c2_stride, c2_stride * 8, rows * P * 8, run,
                              hipMemcpyHostToDevice, s));
@@ -4674,12 +4728,8 @@ int32_t pvw_ct_sum_host(const pvw_ctx* c, const uint64_t* c1s, const uint64_t* c
   return PVW_OK;
 }
 // the weighted form by its definition (no GPU): signed_residue of the weight, mulmod by the word, addmod
-int32_t pvw_ct_lincomb_host(const pvw_ctx* c, const uint64_t* c1s, const uint64_t* c2s, size_t D, const uint8_t* valid,
-                            const int64_t* weights, uint32_t lo, uint32_t hi, uint64_t* c1_out, uint64_t* c2_out, uint32_t* count) {
-  PVW_TRY(need_weights(weights));
-  PVW_TRY(ct_sum_checks(c, c1s, c2s, D, lo, hi, c1_out, c2_out));
-  const size_t nv = count_valid(valid, weights, D);
-  if (nv == 0) return no_valid_dealer(D, weights);
+static void ct_lincomb_host_row(const pvw_ctx* c, const uint64_t* c1s, const uint64_t* c2s, size_t D, const uint8_t* valid,
+                                const int64_t* weights, uint32_t lo, uint32_t hi, uint64_t* c1_out, uint64_t* c2_out) {
   const size_t P = c->poly(), l = c->l;
   auto region = [&](const u64* in, size_t stride, size_t words, u64* out) {
     for (size_t i = 0; i < words; ++i) {
@@ -4692,8 +4742,84 @@ int32_t pvw_ct_lincomb_host(const pvw_ctx* c, const uint64_t* c1s, const uint64_
   };
   region(c1s, (size_t)c->k * P, (size_t)c->k * P, c1_out);
   region(c2s + (size_t)lo * P, (size_t)c->n * P, (size_t)(hi - lo) * P, c2_out);
+}
+int32_t pvw_ct_lincomb_host(const pvw_ctx* c, const uint64_t* c1s, const uint64_t* c2s, size_t D, const uint8_t* valid,
+                            const int64_t* weights, uint32_t lo, uint32_t hi, uint64_t* c1_out, uint64_t* c2_out, uint32_t* count) {
+  PVW_TRY(need_weights(weights));
+  PVW_TRY(ct_sum_checks(c, c1s, c2s, D, lo, hi, c1_out, c2_out));
+  const size_t nv = count_valid(valid, weights, D);
+  if (nv == 0) return no_valid_dealer(D, weights);
+  ct_lincomb_host_row(c, c1s, c2s, D, valid, weights, lo, hi, c1_out, c2_out);
   if (count) *count = (uint32_t)nv;
   return PVW_OK;
+}
+
+// ---- many combinations of the same dealers' ciphertexts: R rows of weights [R][D], row r's result at
+// c1_out [r][k] / c2_out [r][row_hi - row_lo] and its participants in counts[r].  R = 1 is the call above, through its own path.
+static int32_t combos_check(size_t R, bool device) {
+  if (R == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "num_combos must be at least 1");
+  if (device && R >> 31) return fail(PVW_ERR_INVALID_PARAMETERS, "num_combos must be below 2^31 on the device");
+  return PVW_OK;
+}
+static void combo_counts(const uint8_t* valid, const i64* weights, size_t D, size_t R, uint32_t* counts) {
+  for (size_t r = 0; counts && r < R; ++r) counts[r] = (uint32_t)count_valid(valid, weights + r * D, D);
+}
+// the definition: the loop of pvw_ct_lincomb_host over the rows (a row nobody takes part in: zeros)
+int32_t pvw_ct_lincomb_many_host(const pvw_ctx* c, const uint64_t* c1s, const uint64_t* c2s, size_t D, const uint8_t* valid,
+                                 const int64_t* weights, size_t R, uint32_t lo, uint32_t hi, uint64_t* c1_out, uint64_t* c2_out,
+                                 uint32_t* counts) {
+  PVW_TRY(need_weights(weights));
+  PVW_TRY(ct_sum_checks(c, c1s, c2s, D, lo, hi, c1_out, c2_out));
+  PVW_TRY(combos_check(R, false));
+  if (count_valid_any(valid, weights, D, R) == 0) return no_valid_dealer(D, weights);
+  const size_t P = c->poly();
+  for (size_t r = 0; r < R; ++r)
+    ct_lincomb_host_row(c, c1s, c2s, D, valid, weights + r * D, lo, hi, c1_out + r * c->k * P, c2_out + r * (hi - lo) * P);
+  combo_counts(valid, weights, D, R, counts);
+  return PVW_OK;
+}
+int32_t pvw_ct_lincomb_many_device(pvw_ctx* c, const uint64_t* d_c1s, const uint64_t* d_c2s, size_t D, const uint8_t* d_valid,
+                                   const int64_t* d_weights, size_t R, uint32_t lo, uint32_t hi, uint64_t* d_c1_out,
+                                   uint64_t* d_c2_out, uint32_t* d_counts, void* stream) {
+  PVW_TRY(need_weights(d_weights));
+  PVW_TRY(ct_sum_checks(c, d_c1s, d_c2s, D, lo, hi, d_c1_out, d_c2_out));
+  PVW_TRY(combos_check(R, true));
+  if (R == 1) return ct_sum_device(c, d_c1s, d_c2s, D, d_valid, d_weights, lo, hi, d_c1_out, d_c2_out, d_counts, stream);
+  PVW_TRY(ensure_device(c));
+  hipStream_t s = call_stream(c, stream);
+  PVW_TRY(sum_capture_check(c, s, 0, 0));
+  Workspace* w;
+  PVW_TRY(ws_for_stream(c, s, &w));
+  PVW_TRY(sum_buffer(c, w, s));
+  const size_t P = c->poly(), rows = hi - lo;
+  return ct_sum_enqueue(c, w, s, d_c1s, d_c2s + (size_t)lo * P, (size_t)c->n * P, rows, D, d_valid, d_weights, d_c1_out, d_c2_out,
+                        d_counts, false, Combos{R, D, (size_t)c->k * P, rows * P});
+}
+// host buffers: the participating dealers (of any row) are staged once, the R results leave through the stream's scratch
+int32_t pvw_ct_lincomb_many(pvw_ctx* c, const uint64_t* c1s, const uint64_t* c2s, size_t D, const uint8_t* valid, const int64_t* weights,
+                            size_t R, uint32_t lo, uint32_t hi, uint64_t* c1_out, uint64_t* c2_out, uint32_t* counts) {
+  PVW_TRY(need_weights(weights));
+  PVW_TRY(ct_sum_checks(c, c1s, c2s, D, lo, hi, c1_out, c2_out));
+  PVW_TRY(combos_check(R, false));
+  if (R == 1) return ct_sum_hostbuf(c, c1s, c2s, D, valid, weights, lo, hi, c1_out, c2_out, counts);
+  const size_t nv = count_valid_any(valid, weights, D, R);
+  if (nv == 0) return no_valid_dealer(D, weights);
+  PVW_TRY(ensure_device(c));
+  const size_t P = c->poly(), k = c->k, rows = hi - lo, per = chunk_1gib((k + rows) * P * 8, nv);
+  Scratch sc;
+  const size_t r_c1 = sc.add(per * k * P * 8), r_c2 = sc.add(per * rows * P * 8), r_w = sc.add(R * per * 8);
+  const size_t r_o1 = sc.add(R * k * P * 8), r_o2 = sc.add(R * rows * P * 8);
+  const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    PVW_TRY(sum_buffer(c, w, w->stream));
+    PVW_TRY(ct_sum_staged(c, w, sc.at(r_c1), sc.at(r_c2), per, c1s, c2s + (size_t)lo * P, (size_t)c->n * P, rows, D, valid, weights,
+                          sc.at<i64>(r_w), sc.at(r_o1), sc.at(r_o2), R, k * P, rows * P));
+    PVW_HIP(hipMemcpyAsync(c1_out, sc.at(r_o1), R * k * P * 8, hipMemcpyDeviceToHost, w->stream));
+    PVW_HIP(hipMemcpyAsync(c2_out, sc.at(r_o2), R * rows * P * 8, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
+  if (rc == PVW_OK) combo_counts(valid, weights, D, R, counts);
+  return rc;
 }
 
 // One party's aggregate share.  The summed ciphertext sits in the sum buffer (c1 | the column's sum: k + 1 polynomials in one
@@ -4929,6 +5055,132 @@ int32_t pvw_decrypt_all_sum_checked(pvw_ctx* c, uint32_t lo, uint32_t hi, const 
                                     size_t D, const uint8_t* valid, uint32_t in_repr, uint64_t* out_u64, uint64_t* noise,
                                     uint32_t* status, uint32_t* count) {
   return pvw_decrypt_all_sum_plain(c, lo, hi, sk, c1s, c2s, D, valid, in_repr, out_u64, noise, status, count, 0, 0, nullptr);
+}
+
+// Every party's share of R combinations.  The sum buffer holds one combined ciphertext, so the R of them (public)
+// go into the stream's scratch as whole ciphertexts, c1 [R][k] | c2 [R][n] (row j at its global position), a POWER-basis input is
+// transformed there, and ONE decrypt_all_run with the combinations in the dealers' place follows: its 22-party dispatch, GEMM
+// path, plain decode and hygiene are its own.  R is cut into groups of at most one staging budget of combined ciphertexts; each
+// group is one more set of passes over the dealers and fills its block of columns of the [P][R] report.
+struct ManyLayout {
+  size_t Rg, need;                    // combinations per group; the decrypt's own scratch (the front of the block)
+  Scratch sc;
+  size_t r_main, r_cc1, r_cc2;
+};
+static ManyLayout decrypt_all_many_layout(const pvw_ctx* c, size_t NP, size_t R, size_t ww, size_t front) {
+  const size_t P = c->poly();
+  ManyLayout m;
+  m.Rg = chunk_1gib(((size_t)c->k + c->n) * P * 8, R);
+  m.need = decrypt_all_layout(c, NP, m.Rg, false, false, true, true, ww).sc.total;
+  if (R % m.Rg) {                                                  // the last group's own layout (not monotone in the count)
+    const size_t last = decrypt_all_layout(c, NP, R % m.Rg, false, false, true, true, ww).sc.total;
+    if (last > m.need) m.need = last;
+  }
+  m.r_main = m.sc.add(m.need > front ? m.need : front);
+  m.r_cc1 = m.sc.add(m.Rg * c->k * P * 8), m.r_cc2 = m.sc.add(m.Rg * c->n * P * 8);
+  return m;
+}
+// the group's combined ciphertexts are in place: transform (POWER basis) and decrypt into columns [r0, r0 + cnt) of rep [P][R]
+static int32_t decrypt_all_many_tail(pvw_ctx* c, Workspace* w, hipStream_t s, u32 lo, u32 hi, const int64_t* d_sk, uint32_t in_repr,
+                                     u64* cc1, u64* cc2, size_t cnt, const Report& rep, size_t ld) {
+  const size_t P = c->poly();
+  if (in_repr == PVW_REPR_POWER) {
+    ProfScope ps(c, "ntt", s);
+    PVW_HIP(launch_ntt(cc1, cnt * c->k, false, c->dt, c->L, c->l, s));
+    for (size_t r = 0; r < cnt; ++r) PVW_HIP(launch_ntt(cc2 + (r * c->n + lo) * P, hi - lo, false, c->dt, c->L, c->l, s));
+  }
+  AllCall q{lo, (size_t)hi - lo, cnt, d_sk, cc1, cc2, false, false, rep};
+  q.rep_ld = ld;
+  return decrypt_all_run(c, w, s, q);
+}
+int32_t pvw_decrypt_all_lincomb_many_plain_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
+                                                  const uint64_t* d_c2s, size_t D, const uint8_t* d_valid, const int64_t* d_weights,
+                                                  size_t R, uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status,
+                                                  uint32_t* d_counts, uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide,
+                                                  void* stream) {
+  PVW_TRY(need_weights(d_weights));
+  if (R == 1)
+    return decrypt_all_sum_device(c, lo, hi, d_sk, d_c1s, d_c2s, D, d_valid, d_weights, in_repr, d_out, d_noise, d_status, d_counts,
+                                  plain_modulus, wide_words, d_wide, stream);
+  Report rep;
+  PVW_TRY(report_args(c, d_out, d_noise, d_status, plain_modulus, wide_words, d_wide, &rep));
+  PVW_TRY(decrypt_all_checks(c, lo, hi, d_sk, d_c1s, d_c2s, D, in_repr, d_out));
+  PVW_TRY(check_dealers(D, true));
+  PVW_TRY(combos_check(R, true));
+  const size_t P = c->poly(), NP = (size_t)hi - lo;
+  ManyLayout m = decrypt_all_many_layout(c, NP, R, rep.ww, 0);
+  // as the checked reconstruction: the caller's stream is looked at before the device is initialised
+  auto sized = [&](hipStream_t s) -> int32_t {
+    PVW_TRY(grown_capture_check(c, s, &Workspace::scratch_bytes, m.sc.total,
+                                "many combinations under stream capture: run a call with the same party range and at least as many "
+                                "combinations on this stream outside capture first (it sizes the scratch)"));
+    return sum_capture_check(c, s, 0, 0);
+  };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
+    PVW_TRY(sum_buffer(c, w, s));
+    PVW_TRY(m.sc.take(w));                                           // before anything of this call is enqueued
+    u64 *cc1 = m.sc.at(m.r_cc1), *cc2 = m.sc.at(m.r_cc2);
+    for (size_t r0 = 0; r0 < R; r0 += m.Rg) {
+      const size_t cnt = (R - r0) < m.Rg ? (R - r0) : m.Rg;
+      u32* cnts = d_counts ? d_counts + r0 : nullptr;
+      PVW_TRY(ct_sum_enqueue(c, w, s, d_c1s, d_c2s + (size_t)lo * P, (size_t)c->n * P, NP, D, d_valid, d_weights + r0 * D, cc1,
+                             cc2 + (size_t)lo * P, cnts, false, Combos{cnt, D, (size_t)c->k * P, (size_t)c->n * P}));
+      PVW_TRY(decrypt_all_many_tail(c, w, s, lo, hi, d_sk, in_repr, cc1, cc2, cnt, rep.at(r0), R));
+    }
+    return PVW_OK;
+  });
+}
+int32_t pvw_decrypt_all_lincomb_many_plain(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s,
+                                           const uint64_t* c2s, size_t D, const uint8_t* valid, const int64_t* weights, size_t R,
+                                           uint32_t in_repr, uint64_t* out_u64, uint64_t* noise, uint32_t* status, uint32_t* counts,
+                                           uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
+  PVW_TRY(need_weights(weights));
+  if (R == 1)
+    return decrypt_all_sum_hostbuf(c, lo, hi, sk, c1s, c2s, D, valid, weights, in_repr, out_u64, noise, status, counts, plain_modulus,
+                                   wide_words, wide);
+  Report rep;
+  PVW_TRY(report_args(c, out_u64, noise, status, plain_modulus, wide_words, wide, &rep));
+  PVW_TRY(decrypt_all_checks(c, lo, hi, sk, c1s, c2s, D, in_repr, out_u64));
+  PVW_TRY(check_dealers(D, true));
+  PVW_TRY(combos_check(R, false));
+  const size_t nv = count_valid_any(valid, weights, D, R);
+  if (nv == 0) return no_valid_dealer(D, weights);
+  PVW_TRY(ensure_device(c));
+  const size_t P = c->poly(), k = c->k, l = c->l, NP = (size_t)hi - lo, per = chunk_1gib((k + NP) * P * 8, nv);
+  // the staged pieces and the decrypt's own scratch share the front of the block, as in decrypt_all_sum_hostbuf; behind them the
+  // combined ciphertexts, the group's report [P][Rg] and the uploaded keys
+  Scratch st;
+  const size_t r_c1 = st.add(per * k * P * 8), r_c2 = st.add(per * NP * P * 8);
+  ManyLayout m = decrypt_all_many_layout(c, NP, R, rep.ww, 0);
+  const size_t r_w = st.add(m.Rg * per * 8);
+  m = decrypt_all_many_layout(c, NP, R, rep.ww, st.total);
+  const size_t r_io = m.sc.add(Report::packed_bytes(NP * m.Rg, rep.ww)), r_sk = m.sc.add(NP * k * l * 8);
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(m.sc.take(w));
+    PVW_TRY(sum_buffer(c, w, w->stream));
+    st.base = m.sc.at<char>(m.r_main);
+    u64 *cc1 = m.sc.at(m.r_cc1), *cc2 = m.sc.at(m.r_cc2);
+    i64* d_sk = m.sc.at<i64>(r_sk);
+    m.sc.secret(w, r_io, r_sk);
+    PVW_HIP(hipMemcpyAsync(d_sk, sk, NP * k * l * 8, hipMemcpyHostToDevice, w->stream));
+    for (size_t r0 = 0; r0 < R; r0 += m.Rg) {
+      const size_t cnt = (R - r0) < m.Rg ? (R - r0) : m.Rg;
+      const i64* wr = weights + r0 * D;
+      if (count_valid_any(valid, wr, D, cnt) == 0) {                  // nobody takes part in this group's rows: zeros
+        PVW_HIP(hipMemsetAsync(cc1, 0, cnt * k * P * 8, w->stream));
+        PVW_HIP(hipMemsetAsync(cc2, 0, cnt * c->n * P * 8, w->stream));
+      } else {
+        PVW_TRY(ct_sum_staged(c, w, st.at(r_c1), st.at(r_c2), per, c1s, c2s + (size_t)lo * P, (size_t)c->n * P, NP, D, valid, wr,
+                              st.at<i64>(r_w), cc1, cc2 + (size_t)lo * P, cnt, k * P, (size_t)c->n * P));
+      }
+      const Report dev = rep.packed_at(m.sc.at(r_io), NP * cnt);
+      PVW_TRY(decrypt_all_many_tail(c, w, w->stream, lo, hi, d_sk, in_repr, cc1, cc2, cnt, dev, 0));
+      PVW_TRY(dev.copy_block_to(rep.at(r0), NP, cnt, R, hipMemcpyDeviceToHost, w->stream));
+      combo_counts(valid, wr, D, cnt, counts ? counts + r0 : nullptr);
+    }
+    return PVW_OK;
+  });
 }
 
 // Advisory: for how many dealers at the builder's noise bound the gadget decode of the aggregate is PROVEN exact.  With

@@ -225,6 +225,15 @@ hipError_t launch_ct_sum(const SumRegion& a, const SumRegion& b, const unsigned 
 hipError_t launch_ct_lincomb(const SumRegion& a, const SumRegion& b, const unsigned char* valid, const i64* weights, size_t dealers,
                              const DevTables& t, u32 L, u32 ell, u64* partial, u32 nslices, bool accumulate, u32* count,
                              hipStream_t s);
+// Many combinations of the same dealers: row r of weights [nrows][wstride] (2 <= nrows < 2^31) gives what
+// launch_ct_lincomb gives with weights + r * wstride, written r * out_stride_a / _b words behind a.out / b.out, and counts[r].
+// One pass over the dealers per tile of ct_lincomb_many_tile(items, nslices) rows (2 or 4, by the shape), the last rows in
+// narrower passes; the split form needs nslices * tile * items <= ct_sum_partial_items_max().
+u32 ct_lincomb_many_tile(size_t items, u32 nslices);
+hipError_t launch_ct_lincomb_many(const SumRegion& a, const SumRegion& b, size_t out_stride_a, size_t out_stride_b,
+                                  const unsigned char* valid, const i64* weights, size_t wstride, size_t nrows, size_t dealers,
+                                  const DevTables& t, u32 L, u32 ell, u64* partial, u32 nslices, bool accumulate, u32* counts,
+                                  hipStream_t s);
 
 // ---- Shamir shares (pvw_shamir.hip): shares[d * row_stride + i] = f_d(i + 1) mod m.q for the dealers of the batch
 // and the parties i of [party_lo, party_hi); f_d = secrets[d] + sum_{j=1..degree} a_{d,j} x^j.  a_{d,j} = coeffs[d * degree + j - 1]

@@ -985,4 +985,78 @@ inline CheckedShares decrypt_all_party_combinations(const std::vector<PvwCiphert
   return r;
 }
 
+// ---- many combinations of the same dealers' ciphertexts ----
+// row j: the Lagrange weights AT the point (targets[j] + 1) mod plain_modulus, centred (pvw_shamir_lagrange_weights_at; host only)
+inline std::vector<std::vector<int64_t>> shamir_lagrange_weights_at(const std::vector<uint64_t>& indices, const std::vector<uint64_t>& targets,
+                                                                    uint64_t plain_modulus) {
+  std::vector<int64_t> flat(targets.size() * indices.size());
+  check(pvw_shamir_lagrange_weights_at(plain_modulus, indices.data(), indices.size(), targets.data(), targets.size(), flat.data()));
+  std::vector<std::vector<int64_t>> rows(targets.size());
+  for (size_t j = 0; j < targets.size(); ++j) rows[j].assign(flat.begin() + j * indices.size(), flat.begin() + (j + 1) * indices.size());
+  return rows;
+}
+// the weight rows of a packed sharing's handover: row m at the point -m (secret m), m < pack
+inline std::vector<std::vector<int64_t>> shamir_packed_handover_weights(const std::vector<uint64_t>& indices, uint64_t plain_modulus, uint32_t pack) {
+  std::vector<uint64_t> targets(pack);
+  for (uint32_t m = 0; m < pack; ++m) targets[m] = plain_modulus - 1 - m;
+  return shamir_lagrange_weights_at(indices, targets, plain_modulus);
+}
+// weight_rows [R][D] flattened row-major
+inline std::vector<int64_t> combination_weight_rows(const std::vector<PvwCiphertext>& cts, const std::vector<std::vector<int64_t>>& weight_rows) {
+  if (weight_rows.empty()) throw PvwError(1, "num_combos must be at least 1");
+  std::vector<int64_t> flat;
+  for (const auto& row : weight_rows) {
+    combination_weights(cts, row);
+    flat.insert(flat.end(), row.begin(), row.end());
+  }
+  return flat;
+}
+// element r = combine_ciphertexts(cts, weight_rows[r], valid), every ciphertext read once per tile of rows (pvw_ct_lincomb_many)
+inline std::vector<PvwCiphertext> combine_ciphertexts_many(const std::vector<PvwCiphertext>& cts, const std::vector<std::vector<int64_t>>& weight_rows,
+                                                           const std::vector<bool>& valid = {}) {
+  const SumInputs in = sum_inputs(cts, valid);
+  const std::vector<int64_t> w = combination_weight_rows(cts, weight_rows);
+  const auto& p = cts[0].params;
+  const size_t R = weight_rows.size(), n1 = cts[0].c1.size(), n2 = cts[0].c2.size();
+  std::vector<uint64_t> c1(R * n1), c2(R * n2);
+  check(pvw_ct_lincomb_many(p->ctx, in.c1s.data(), in.c2s.data(), cts.size(), in.valid_ptr(), w.data(), R, 0, p->n, c1.data(), c2.data(), nullptr));
+  std::vector<PvwCiphertext> out;
+  for (size_t r = 0; r < R; ++r)
+    out.push_back(PvwCiphertext{std::vector<uint64_t>(c1.begin() + r * n1, c1.begin() + (r + 1) * n1),
+                                std::vector<uint64_t>(c2.begin() + r * n2, c2.begin() + (r + 1) * n2), p, cts[0].repr});
+  return out;
+}
+// every party's share of every combination in one call (pvw_decrypt_all_lincomb_many_plain): arrays [parties][R]; the report's
+// valid follows combination_report row by row
+inline CheckedShares decrypt_all_party_combinations_many(const std::vector<PvwCiphertext>& cts, const std::vector<std::vector<int64_t>>& weight_rows,
+                                                         const std::vector<Party>& parties, const std::vector<bool>& valid = {},
+                                                         uint64_t bound = 0, const pvw_plain_t* plain = nullptr) {
+  const SumInputs in = sum_inputs(cts, valid);
+  const std::vector<int64_t> w = combination_weight_rows(cts, weight_rows);
+  const auto& p = cts[0].params;
+  const size_t NP = parties.size(), R = weight_rows.size(), kl = (size_t)p->k * p->l;
+  CheckedShares r{std::vector<uint64_t>(NP * R), std::vector<uint64_t>(NP * R), std::vector<bool>(NP * R), std::vector<bool>(NP * R)};
+  if (NP == 0) return r;
+  std::vector<int64_t> sk(NP * kl);
+  for (size_t i = 0; i < NP; ++i) {
+    if (parties[i].index >= p->n || parties[i].index != parties[0].index + i) throw PvwError(1, "Party indices must be consecutive and below n");
+    std::copy(parties[i].secret_key.secret_coeffs.begin(), parties[i].secret_key.secret_coeffs.end(), sk.begin() + i * kl);
+  }
+  std::vector<uint32_t> status(NP * R);
+  if (plain_on(plain)) r.wide.assign(NP * R * plain->wide_words, 0);
+  const int32_t rc = pvw_decrypt_all_lincomb_many_plain(
+      p->ctx, parties[0].index, parties[0].index + (uint32_t)NP, sk.data(), in.c1s.data(), in.c2s.data(), cts.size(), in.valid_ptr(), w.data(), R,
+      cts[0].repr, r.values.data(), r.noise.data(), status.data(), nullptr, plain_on(plain) ? plain->modulus : 0,
+      plain_on(plain) ? plain->wide_words : 0, plain_on(plain) && plain->wide_words ? r.wide.data() : nullptr);
+  std::fill(sk.begin(), sk.end(), 0);                                   // the copied keys do not outlive the call
+  check(rc);
+  checked_report(r, status, bound ? bound : ~(uint64_t)0, plain_on(plain));
+  if (bound) return r;
+  for (size_t c = 0; c < R; ++c) {
+    const bool fits = lincomb_fits(p, weight_rows[c], valid);
+    for (size_t i = 0; i < NP; ++i) r.valid[i * R + c] = r.valid[i * R + c] && fits;
+  }
+  return r;
+}
+
 }  // namespace pvw_host

@@ -234,6 +234,13 @@ extern "C" {
     pub fn pvw_decrypt_all_lincomb_plain_device(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, d_sk: *const i64, d_c1s: *const u64, d_c2s: *const u64, num_dealers: usize, d_valid: *const u8, d_weights: *const i64, in_repr: u32, d_out: *mut u64, d_noise: *mut u64, d_status: *mut u32, d_count: *mut u32, plain_modulus: u64, wide_words: u32, d_wide: *mut u64, stream: *mut c_void) -> i32;
     pub fn pvw_ctx_lincomb_fits(ctx: *const PvwCtx, weights: *const i64, num_dealers: usize, valid: *const u8, fits: *mut u32) -> i32;
     pub fn pvw_shamir_lagrange_weights(plain_modulus: u64, indices: *const u64, count: usize, weights_out: *mut i64) -> i32;
+    // many combinations of the same dealers' ciphertexts
+    pub fn pvw_shamir_lagrange_weights_at(plain_modulus: u64, indices: *const u64, count: usize, targets: *const u64, num_targets: usize, weights_out: *mut i64) -> i32;
+    pub fn pvw_ct_lincomb_many_host(ctx: *const PvwCtx, c1s: *const u64, c2s: *const u64, num_dealers: usize, valid: *const u8, weights: *const i64, num_combos: usize, row_lo: u32, row_hi: u32, c1_out: *mut u64, c2_out: *mut u64, counts: *mut u32) -> i32;
+    pub fn pvw_ct_lincomb_many_device(ctx: *mut PvwCtx, d_c1s: *const u64, d_c2s: *const u64, num_dealers: usize, d_valid: *const u8, d_weights: *const i64, num_combos: usize, row_lo: u32, row_hi: u32, d_c1_out: *mut u64, d_c2_out: *mut u64, d_counts: *mut u32, stream: *mut c_void) -> i32;
+    pub fn pvw_ct_lincomb_many(ctx: *mut PvwCtx, c1s: *const u64, c2s: *const u64, num_dealers: usize, valid: *const u8, weights: *const i64, num_combos: usize, row_lo: u32, row_hi: u32, c1_out: *mut u64, c2_out: *mut u64, counts: *mut u32) -> i32;
+    pub fn pvw_decrypt_all_lincomb_many_plain_device(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, d_sk: *const i64, d_c1s: *const u64, d_c2s: *const u64, num_dealers: usize, d_valid: *const u8, d_weights: *const i64, num_combos: usize, in_repr: u32, d_out: *mut u64, d_noise: *mut u64, d_status: *mut u32, d_counts: *mut u32, plain_modulus: u64, wide_words: u32, d_wide: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_decrypt_all_lincomb_many_plain(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, sk: *const i64, c1s: *const u64, c2s: *const u64, num_dealers: usize, valid: *const u8, weights: *const i64, num_combos: usize, in_repr: u32, out_u64: *mut u64, noise: *mut u64, status: *mut u32, counts: *mut u32, plain_modulus: u64, wide_words: u32, wide: *mut u64) -> i32;
     pub fn pvw_decode(ctx: *mut PvwCtx, noisy: *const u64, count: usize, out_u64: *mut u64) -> i32;
     pub fn pvw_decode_host(ctx: *const PvwCtx, noisy: *const u64, count: usize, out_u64: *mut u64) -> i32;
     pub fn pvw_decode_device(ctx: *mut PvwCtx, d_noisy: *const u64, count: usize, d_out: *mut u64, stream: *mut c_void) -> i32;

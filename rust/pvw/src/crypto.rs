@@ -774,6 +774,36 @@ pub fn combine(ciphertexts: &[PvwCiphertext], weights: &[i64], valid: Option<&[b
     ciphertext_from_flat(&c1, &c2, params)
 }
 
+/// EXTENSION: row j = the Lagrange weights AT the point (targets[j] + 1) mod p of the points indices[i] + 1,
+/// centred in (-p/2, p/2] (`pvw_shamir_lagrange_weights_at`; host only).  Target p - 1 - m is the point -m of a packed sharing.
+pub fn shamir_lagrange_weights_at(indices: &[u64], targets: &[u64], plain_modulus: u64) -> Result<Vec<Vec<i64>>> {
+    let mut flat = vec![0i64; indices.len() * targets.len()];
+    check(unsafe {
+        sys::pvw_shamir_lagrange_weights_at(plain_modulus, indices.as_ptr(), indices.len(), targets.as_ptr(), targets.len(), flat.as_mut_ptr())
+    })?;
+    Ok(flat.chunks(indices.len().max(1)).map(|row| row.to_vec()).collect())
+}
+
+/// EXTENSION: one combination per row of `weight_rows` over the same ciphertexts (`pvw_ct_lincomb_many`): element
+/// r is `combine(ciphertexts, &weight_rows[r], valid)` bit for bit, zeros for a row nobody takes part in; every ciphertext is
+/// uploaded once and read once per tile of rows.
+pub fn combine_many(ciphertexts: &[PvwCiphertext], weight_rows: &[Vec<i64>], valid: Option<&[bool]>) -> Result<Vec<PvwCiphertext>> {
+    let (c1s, c2s, v) = sum_inputs(ciphertexts, valid)?;
+    let mut weights = Vec::with_capacity(weight_rows.len() * ciphertexts.len());
+    for row in weight_rows {
+        combination_weights(ciphertexts, row)?;
+        weights.extend_from_slice(row);
+    }
+    let params = &ciphertexts[0].params;
+    let (words, rows) = (poly_words(params), weight_rows.len());
+    let (mut c1, mut c2) = (vec![0u64; rows * params.k * words], vec![0u64; rows * params.n * words]);
+    check(unsafe {
+        sys::pvw_ct_lincomb_many(params.hip.raw(), c1s.as_ptr(), c2s.as_ptr(), ciphertexts.len(), valid_ptr(&v), weights.as_ptr(), rows, 0,
+                                 params.n as u32, c1.as_mut_ptr(), c2.as_mut_ptr(), std::ptr::null_mut())
+    })?;
+    c1.chunks_exact(params.k * words).zip(c2.chunks_exact(params.n * words)).map(|(a, b)| ciphertext_from_flat(a, b, params)).collect()
+}
+
 /// EXTENSION: party `party_index`'s share of the combination from ONE decrypt (`pvw_decrypt_lincomb_plain`), with the plain
 /// options of DESIGN 8.8: with the Lagrange weights of the valid old holders and `plain.modulus` = p this is the party's new
 /// share after a committee handover.  (report of one share, dealers that took part)
