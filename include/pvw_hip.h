@@ -32,7 +32,8 @@
  *     pvw_encrypt[_rs], pvw_encrypt_multi[_rs], pvw_deal_shares[_rs], pvw_shamir_shares, pvw_deal_shares_packed[_rs],
  *     pvw_shamir_shares_packed (the concurrent calls of these: tests/test_gpu_shamir_packed.py), pvw_shamir_reconstruct_checked,
  *     pvw_shamir_reconstruct_corrected, pvw_shamir_evaluate_corrected (the concurrent calls of these two:
- *     tests/test_gpu_shamir_evaluate.py),
+ *     tests/test_gpu_shamir_evaluate.py), pvw_shamir_reconstruct_erasures, pvw_shamir_evaluate_erasures (the concurrent calls of
+ *     these two: tests/test_gpu_shamir_erasures.py),
  *     pvw_decrypt_batch / _checked / _plain, pvw_decrypt_all / _checked / _plain, pvw_ct_sum, pvw_decrypt_sum_checked,
  *     pvw_decrypt_all_sum_checked, pvw_ct_lincomb, pvw_decrypt_lincomb_plain, pvw_decrypt_all_lincomb_plain (the concurrent
  *     calls of these three: tests/test_gpu_ct_lincomb.py), pvw_ct_lincomb_many, pvw_decrypt_all_lincomb_many_plain (the concurrent
@@ -838,6 +839,69 @@ PVW_API int32_t pvw_shamir_evaluate_corrected(pvw_ctx* ctx, uint64_t plain_modul
                                               size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
                                               size_t point_stride, const uint64_t* targets, size_t num_targets, uint64_t* values,
                                               uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask);
+/* Reconstruction with erasures: a share the caller KNOWS to be bad -- flagged by a checked decrypt, never arrived,
+ * from a refused dealer -- costs one redundant column instead of two.  The arguments of the corrected and evaluate calls, and
+ * directly behind point_stride: erased [num_secrets][W], W = ceil(count / 64), bit c % 64 of word c / 64 of row s set iff share
+ * (s, c) is erased: the layout of err_mask, so one call's err_mask can be the next call's erased.  A device pointer in the
+ * _device forms, a host pointer elsewhere; bits at columns >= count are ignored; NULL means no erasures, and every call is then
+ * the corrected or evaluate call it extends, bit for bit on every output.
+ *   For row s let eps_s be the number of erased columns, r = count - degree - 1 and E_s = (r - eps_s) / 2 (rounded down).
+ *   Row s is DECODABLE iff eps_s <= r and some polynomial F_s of degree <= t disagrees with the row (read mod p) in at most E_s of
+ *   the columns that are not erased in row s: the corrected call's definition on the sub-row of those columns.  F_s is then
+ *   unique.  So 2 errors + erasures <= r per row; r erasures and no error still decode; eps_s > r is undecodable (a property of
+ *   the row, not an argument error).
+ *   decodable:   out[s] = F_s(0); nerr[s] = the number of non-erased columns that disagree; err_mask row s has exactly their
+ *                bits (an erased column is never reported as an error); col_err[c] counts the decodable rows with an error at c;
+ *                values[s][j] = F_s(targets[j] + 1): at an erased or wrong column the share that party should hold.
+ *   undecodable: out = 0, nerr = PVW_SHAMIR_UNDECODABLE, mask row and values row 0, nothing added to col_err.
+ *   The word stored at an erased position influences no output: it may be any 64-bit word.  Column order, target order, determinism and
+ *   the agreement of the three forms (small p included) are those of the calls extended.
+ * PVW_ERR_INVALID_PARAMETERS before any device work, nothing written: what the extended call refuses, with its text; on the
+ * device, for a call WITH a mask, also count - degree - 1 >= 4096 (the errata locator of a row has up to r + 1 coefficients; with
+ * erased == NULL the bound is the one of the call extended, as everything else is; the corrected calls keep
+ * their own bound).  Under stream capture: the rule of the extended device call, sized by a call WITH a mask (its scratch is the
+ * larger: the public power matrices have r + 1 rows); the mask is read when the kernels run.  The host-buffer forms stage the mask
+ * rows with the shares and are covered by the concurrency promise above. */
+/* the contract in plain C++ on the host cores: per row the non-erased columns are compacted and decoded by the Berlekamp-Welch
+ * routine of pvw_shamir_reconstruct_corrected_host with the same degree: what the kernels are tested against */
+PVW_API int32_t pvw_shamir_reconstruct_erasures_host(uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                                     const uint64_t* shares, size_t num_secrets, size_t secret_stride,
+                                                     size_t point_stride, const uint64_t* erased, uint64_t* out, uint32_t* nerr,
+                                                     uint32_t* col_err, uint64_t* err_mask);
+PVW_API int32_t pvw_shamir_reconstruct_erasures_device(pvw_ctx* ctx, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                       size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
+                                                       size_t point_stride, const uint64_t* d_erased, uint64_t* d_out, uint32_t* d_nerr,
+                                                       uint32_t* d_col_err, uint64_t* d_err_mask, void* stream);
+PVW_API int32_t pvw_shamir_reconstruct_erasures(pvw_ctx* ctx, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
+                                                size_t point_stride, const uint64_t* erased, uint64_t* out, uint32_t* nerr,
+                                                uint32_t* col_err, uint64_t* err_mask);
+PVW_API int32_t pvw_shamir_evaluate_erasures_host(uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                                  const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                                  const uint64_t* erased, const uint64_t* targets, size_t num_targets, uint64_t* values,
+                                                  uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask);
+PVW_API int32_t pvw_shamir_evaluate_erasures_device(pvw_ctx* ctx, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                    size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
+                                                    size_t point_stride, const uint64_t* d_erased, const uint64_t* targets,
+                                                    size_t num_targets, uint64_t* d_values, uint64_t* d_out, uint32_t* d_nerr,
+                                                    uint32_t* d_col_err, uint64_t* d_err_mask, void* stream);
+PVW_API int32_t pvw_shamir_evaluate_erasures(pvw_ctx* ctx, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
+                                             size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
+                                             size_t point_stride, const uint64_t* erased, const uint64_t* targets, size_t num_targets,
+                                             uint64_t* values, uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask);
+/* The mask from a decrypt report: bit (s, c) of mask_out [num_secrets][W] is set iff status[..] & status_bits is non-zero or
+ * noise[..] > noise_bound, element (s, c) of status (u32) and noise (u64) at s * secret_stride + c * point_stride as the shares are.
+ * Either array may be NULL, not both; both are only read (status is declared as the decrypt calls declare it, so their buffer
+ * passes as it is).  Every word of mask_out is written, padding bits 0.  Strides (1, D) read the [party][dealer]
+ * report of pvw_decrypt_all_*_checked / _plain in place (every dealer a secret), so decrypt-all -> mask -> decode stays on the
+ * device.  PVW_ERR_INVALID_PARAMETERS, nothing written: NULL mask_out (or ctx), both arrays NULL, count or num_secrets 0, a
+ * stride of 0; on the device count or num_secrets >= 2^31. */
+PVW_API int32_t pvw_shamir_erasure_mask_host(uint32_t* status, const uint64_t* noise, uint32_t status_bits, uint64_t noise_bound,
+                                             size_t count, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                             uint64_t* mask_out);
+PVW_API int32_t pvw_shamir_erasure_mask_device(pvw_ctx* ctx, uint32_t* d_status, const uint64_t* d_noise, uint32_t status_bits,
+                                               uint64_t noise_bound, size_t count, size_t num_secrets, size_t secret_stride,
+                                               size_t point_stride, uint64_t* d_mask_out, void* stream);
 
 /* ---- Packed Shamir shares: several secrets in one polynomial and one ciphertext ---------------------------
  * Franklin-Yung packing: `pack` = K >= 1 secrets per dealer sit at the points 0, -1, ..., -(K-1) of ONE polynomial, so S secrets

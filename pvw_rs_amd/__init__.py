@@ -15,7 +15,7 @@ from .api import (DEC_LOSSY, DEC_NEGATIVE, DEC_WIDE_TRUNCATED, CheckedDecryption
                   encrypt_broadcast, encrypt_many, encrypt_party_shares, aggregate_ciphertexts, decrypt_party_sum,
                   decrypt_all_party_sums, decode_scalar_pvw_plain, decode_scalar_pvw_plain_host,
                   shamir_shares, deal_party_shares, shamir_reconstruct, shamir_reconstruct_checked,
-                  shamir_reconstruct_corrected, shamir_evaluate_corrected, SHAMIR_UNDECODABLE, combine_ciphertexts, decrypt_party_combination,
+                  shamir_reconstruct_corrected, shamir_evaluate_corrected, shamir_erasure_mask, SHAMIR_UNDECODABLE, combine_ciphertexts, decrypt_party_combination,
                   decrypt_all_party_combinations, shamir_lagrange_weights, shamir_shares_packed, deal_party_shares_packed,
                   shamir_reconstruct_packed, shamir_packed_secret_indices, shamir_reconstruct_packed_corrected,
                   combine_ciphertexts_many, decrypt_all_party_combinations_many, shamir_lagrange_weights_at,
@@ -34,6 +34,6 @@ __all__ = [
     "shamir_shares_packed", "deal_party_shares_packed", "shamir_reconstruct_packed", "shamir_packed_secret_indices",
     "shamir_reconstruct_packed_corrected",
     "combine_ciphertexts_many", "decrypt_all_party_combinations_many", "shamir_lagrange_weights_at", "shamir_packed_handover_weights",
-    "shamir_shares", "deal_party_shares", "shamir_reconstruct", "shamir_reconstruct_checked", "shamir_reconstruct_corrected", "shamir_evaluate_corrected", "SHAMIR_UNDECODABLE",
+    "shamir_shares", "deal_party_shares", "shamir_reconstruct", "shamir_reconstruct_checked", "shamir_reconstruct_corrected", "shamir_evaluate_corrected", "shamir_erasure_mask", "SHAMIR_UNDECODABLE",
     "device_available", "REPR_POWER", "REPR_NTT",
 ]

@@ -170,6 +170,15 @@ _SIGNATURES = {
     "pvw_shamir_evaluate_corrected_host": [C.c_uint64, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P, _P, _P, _P, _P],
     "pvw_shamir_evaluate_corrected_device": [_P, C.c_uint64, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P, _P, _P, _P, _P, _P],
     "pvw_shamir_evaluate_corrected": [_P, C.c_uint64, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P, _P, _P, _P, _P],
+    # reconstruction with erasures: the corrected / evaluate arguments with `erased` behind point_stride
+    "pvw_shamir_reconstruct_erasures_host": [C.c_uint64, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P, _P, _P],
+    "pvw_shamir_reconstruct_erasures_device": [_P, C.c_uint64, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P, _P, _P, _P],
+    "pvw_shamir_reconstruct_erasures": [_P, C.c_uint64, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P, _P, _P],
+    "pvw_shamir_evaluate_erasures_host": [C.c_uint64, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, C.c_size_t, _P, _P, _P, _P, _P],
+    "pvw_shamir_evaluate_erasures_device": [_P, C.c_uint64, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P],
+    "pvw_shamir_evaluate_erasures": [_P, C.c_uint64, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, C.c_size_t, _P, _P, _P, _P, _P],
+    "pvw_shamir_erasure_mask_host": [_P, _P, C.c_uint32, C.c_uint64, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _P],
+    "pvw_shamir_erasure_mask_device": [_P, _P, _P, C.c_uint32, C.c_uint64, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P],
     "pvw_decode": [_P, _P, C.c_size_t, _P],
     "pvw_decode_host": [_P, _P, C.c_size_t, _P],
     "pvw_decode_device": [_P, _P, C.c_size_t, _P, _P],

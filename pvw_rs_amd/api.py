@@ -926,6 +926,25 @@ def _share_matrix(indices: Sequence[int], shares, layout: str):
     return idx, sh, S, count, strides
 
 
+def _erased_words(erased, S: int, count: int, layout: str) -> np.ndarray:
+    """the erasure mask of a call as packed words [S][ceil(count / 64)] (bit c % 64 of word c // 64 of row s: share (s, c) is
+    erased): a uint64 array is taken as packed already (an err_mask, or what shamir_erasure_mask returns), anything else as a
+    matrix of truth values in the call's `layout`"""
+    W = (count + 63) // 64
+    if isinstance(erased, np.ndarray) and erased.dtype == np.uint64:
+        if erased.shape != (S, W):
+            raise PvwError(15, f"expected packed erasures of shape {(S, W)}, got {erased.shape}")
+        return np.ascontiguousarray(erased)
+    m = np.asarray(erased).astype(bool)
+    if layout == "party_major":
+        m = m.T
+    if m.shape != (S, count):
+        raise PvwError(15, f"expected erasures for {S} secrets x {count} shares, got {m.shape}")
+    bits = np.zeros((S, W * 64), dtype=np.uint8)
+    bits[:, :count] = m
+    return np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little").view(np.uint64))
+
+
 def _reconstruct_call(params: Optional[PvwParameters], name: str, host: bool, args) -> None:
     """pvw_<name> on the context of params, or with host=True pvw_<name>_host (no GPU; params may be None)"""
     if host:
@@ -955,41 +974,114 @@ SHAMIR_UNDECODABLE = 0xFFFFFFFF
 
 
 def shamir_reconstruct_corrected(params: Optional[PvwParameters], indices: Sequence[int], shares, degree: int, plain_modulus: int, *,
-                                 host: bool = False, layout: str = "secret_major") -> Tuple[List[int], np.ndarray, np.ndarray, np.ndarray]:
+                                 host: bool = False, layout: str = "secret_major",
+                                 erased=None) -> Tuple[List[int], np.ndarray, np.ndarray, np.ndarray]:
     """EXTENSION (DESIGN 8.11): the secrets although up to E = (len(indices) - degree - 1) // 2 shares of each are wrong, in
     whichever columns.  secrets[s] is the value at 0 of the one polynomial of degree <= `degree` within E columns of row s;
     nerr[s] counts the columns off it, bit c % 64 of err_mask[s][c // 64] names them and col_err[c] counts the secrets that are
     off in column c.  A row with no such polynomial: secrets[s] = 0, nerr[s] = SHAMIR_UNDECODABLE, an empty mask row.  shares and
     layout as shamir_reconstruct_checked.  On the device (pvw_shamir_reconstruct_corrected); host=True: the plain C++ restatement
-    (pvw_shamir_reconstruct_corrected_host, no GPU; params may be None).  Returns (secrets, nerr, col_err, err_mask)."""
+    (pvw_shamir_reconstruct_corrected_host, no GPU; params may be None).  Returns (secrets, nerr, col_err, err_mask).
+    erased: the shares KNOWN to be bad, a matrix of truth values in `layout` or packed words in the layout of
+    err_mask (an earlier call's err_mask, or shamir_erasure_mask).  Each costs one redundant column instead of two: row s decodes
+    while 2 * errors + erasures <= len(indices) - degree - 1; the word at an erased position influences nothing and an erased column
+    is never reported as an error.  Routes to pvw_shamir_reconstruct_erasures*; omitted, the call is untouched."""
     idx, sh, S, count, strides = _share_matrix(indices, shares, layout)
     out = np.zeros(S, dtype=np.uint64)
     nerr, col_err = np.zeros(S, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
     err_mask = np.zeros((S, (count + 63) // 64), dtype=np.uint64)
-    args = (int(plain_modulus), int(degree), _ptr(idx), count, _ptr(sh), S, strides[0], strides[1], _ptr(out), _ptr(nerr), _ptr(col_err),
-            _ptr(err_mask))
-    _reconstruct_call(params, "shamir_reconstruct_corrected", host, args)
+    head = (int(plain_modulus), int(degree), _ptr(idx), count, _ptr(sh), S, strides[0], strides[1])
+    tail = (_ptr(out), _ptr(nerr), _ptr(col_err), _ptr(err_mask))
+    if erased is None:
+        _reconstruct_call(params, "shamir_reconstruct_corrected", host, head + tail)
+    else:
+        er = _erased_words(erased, S, count, layout)
+        _reconstruct_call(params, "shamir_reconstruct_erasures", host, head + (_ptr(er),) + tail)
     return [int(v) for v in out], nerr, col_err, err_mask
 
 
 def shamir_evaluate_corrected(params: Optional[PvwParameters], indices: Sequence[int], shares, degree: int, plain_modulus: int,
-                              targets: Sequence[int], *, host: bool = False,
-                              layout: str = "secret_major") -> Tuple[np.ndarray, List[int], np.ndarray, np.ndarray, np.ndarray]:
+                              targets: Sequence[int], *, host: bool = False, layout: str = "secret_major",
+                              erased=None) -> Tuple[np.ndarray, List[int], np.ndarray, np.ndarray, np.ndarray]:
     """EXTENSION: share repair.  The decode of shamir_reconstruct_corrected, and values[s][j] = the value of secret
     s's corrected polynomial at the point of party targets[j] (a global index: one of `indices` -- the share that party should
     hold -- or any other index below plain_modulus - 1; duplicates allowed).  The row of an undecodable secret is 0.  shares and
     layout as shamir_reconstruct_checked.  On the device (pvw_shamir_evaluate_corrected); host=True: the plain C++ restatement
-    (pvw_shamir_evaluate_corrected_host, no GPU; params may be None).  Returns (values, secrets, nerr, col_err, err_mask)."""
+    (pvw_shamir_evaluate_corrected_host, no GPU; params may be None).  Returns (values, secrets, nerr, col_err, err_mask).
+    erased as shamir_reconstruct_corrected (pvw_shamir_evaluate_erasures*): at an erased column the value is the
+    share that party should hold, which is the repair of a party that lost its state."""
     idx, sh, S, count, strides = _share_matrix(indices, shares, layout)
     tg = _words(targets)
     values = np.zeros((S, len(tg)), dtype=np.uint64)
     out = np.zeros(S, dtype=np.uint64)
     nerr, col_err = np.zeros(S, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
     err_mask = np.zeros((S, (count + 63) // 64), dtype=np.uint64)
-    args = (int(plain_modulus), int(degree), _ptr(idx), count, _ptr(sh), S, strides[0], strides[1], _ptr(tg), len(tg), _ptr(values),
-            _ptr(out), _ptr(nerr), _ptr(col_err), _ptr(err_mask))
-    _reconstruct_call(params, "shamir_evaluate_corrected", host, args)
+    head = (int(plain_modulus), int(degree), _ptr(idx), count, _ptr(sh), S, strides[0], strides[1])
+    tail = (_ptr(tg), len(tg), _ptr(values), _ptr(out), _ptr(nerr), _ptr(col_err), _ptr(err_mask))
+    if erased is None:
+        _reconstruct_call(params, "shamir_evaluate_corrected", host, head + tail)
+    else:
+        er = _erased_words(erased, S, count, layout)
+        _reconstruct_call(params, "shamir_evaluate_erasures", host, head + (_ptr(er),) + tail)
     return values, [int(v) for v in out], nerr, col_err, err_mask
+
+
+def shamir_erasure_mask(status=None, noise=None, *, status_bits: int = 0xFFFFFFFF, noise_bound: int = 0xFFFFFFFFFFFFFFFF,
+                        layout: str = "secret_major", host: bool = False, params: Optional[PvwParameters] = None, stream=None):
+    """EXTENSION: the packed erasure mask [S][ceil(count / 64)] of a decrypt report.  status (uint32) and noise
+    (uint64) are matrices in `layout` ("party_major" is the [party][dealer] report of decrypt_all_party_shares_checked, every
+    dealer a secret); either may be None.  Share (s, c) is erased iff status & status_bits is non-zero or noise > noise_bound
+    (noise == noise_bound is not).  host=True: pvw_shamir_erasure_mask_host (no GPU); otherwise the report goes through device
+    memory and pvw_shamir_erasure_mask_device on the context of `params`.  Given as device tensors (int32 status, int64 noise)
+    the report is read in place, asynchronously on `stream`, and the mask comes back as a device tensor (int64 words): what
+    pvw_shamir_*_erasures_device take, so decrypt-all -> mask -> decode never leaves the device."""
+    if layout not in ("secret_major", "party_major"):
+        raise ValueError(layout)
+    if status is None and noise is None:
+        raise PvwError(15, "status and noise are both None")
+    if any(hasattr(a, "data_ptr") for a in (status, noise)):
+        # device tensors (int32 status, int64 noise, contiguous): the mask is made where they lie and stays there, on `stream`
+        import torch
+        first = status if status is not None else noise
+        if params is None or host or any(a is not None and (not hasattr(a, "data_ptr") or not a.is_contiguous() or a.dim() != 2
+                                                             or a.shape != first.shape) for a in (status, noise)):
+            raise PvwError(15, "device reports need params, host=False and contiguous matrices of one shape")
+        S, count = first.shape if layout == "secret_major" else tuple(first.shape)[::-1]
+        strides = (count, 1) if layout == "secret_major" else (1, S)
+        d_mask = torch.zeros((S, (count + 63) // 64), dtype=torch.int64, device=first.device)
+        params._call("pvw_shamir_erasure_mask_device", _dptr(status), _dptr(noise), int(status_bits), int(noise_bound), count, S,
+                     strides[0], strides[1], _dptr(d_mask), _stream_ptr(stream))
+        return d_mask
+    st = None if status is None else np.ascontiguousarray(np.asarray(status, dtype=np.uint32))
+    if noise is None:
+        nz = None
+    elif isinstance(noise, np.ndarray) and noise.dtype.kind in "ui":
+        nz = np.ascontiguousarray(noise.astype(np.uint64, copy=False))      # a report as it came back: no walk over its elements
+    else:
+        nz = np.ascontiguousarray(np.array([[int(v) & 0xFFFFFFFFFFFFFFFF for v in row] for row in noise], dtype=np.uint64))
+    shape = (st if st is not None else nz).shape
+    if len(shape) != 2 or (st is not None and nz is not None and st.shape != nz.shape):
+        raise PvwError(15, "status and noise must be matrices of one shape")
+    S, count = shape if layout == "secret_major" else shape[::-1]
+    strides = (count, 1) if layout == "secret_major" else (1, S)
+    mask = np.zeros((S, (count + 63) // 64), dtype=np.uint64)
+    if host:
+        L = params._lib if params is not None else _ffi.lib()
+        _check(L.pvw_shamir_erasure_mask_host(_ptr(st) if st is not None else None, _ptr(nz) if nz is not None else None,
+                                              int(status_bits), int(noise_bound), count, S, strides[0], strides[1], _ptr(mask)), L)
+        return mask
+    if params is None:
+        raise PvwError(15, "the device form needs params (or host=True)")
+    import torch
+    dev = torch.device("cuda", params.device) if getattr(params, "device", -1) >= 0 else torch.device("cuda")
+    d_st = torch.from_numpy(st.view(np.int32)).to(dev) if st is not None else None
+    d_nz = torch.from_numpy(nz.view(np.int64)).to(dev) if nz is not None else None
+    d_mask = torch.zeros(mask.shape, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize(dev)
+    params._call("pvw_shamir_erasure_mask_device", _dptr(d_st) if d_st is not None else None, _dptr(d_nz) if d_nz is not None else None,
+                 int(status_bits), int(noise_bound), count, S, strides[0], strides[1], _dptr(d_mask), None)
+    params.synchronize()
+    return d_mask.cpu().numpy().view(np.uint64)
 
 
 def _secret_rows(secrets) -> np.ndarray:
@@ -1042,19 +1134,20 @@ def shamir_packed_secret_indices(plain_modulus: int, pack: int) -> List[int]:
 
 
 def shamir_reconstruct_packed_corrected(params: Optional[PvwParameters], indices: Sequence[int], shares, degree: int, plain_modulus: int,
-                                        pack: int, *, host: bool = False,
-                                        layout: str = "secret_major") -> Tuple[List[List[int]], np.ndarray, np.ndarray, np.ndarray]:
+                                        pack: int, *, host: bool = False, layout: str = "secret_major",
+                                        erased=None) -> Tuple[List[List[int]], np.ndarray, np.ndarray, np.ndarray]:
     """EXTENSION (DESIGN 8.14): the secrets of a packed sharing although up to (len(indices) - degree - pack) // 2 shares of each
     row are wrong: one shamir_evaluate_corrected call with polynomial degree `degree + pack - 1` and the targets
     shamir_packed_secret_indices.  Returns (secrets [S][pack], nerr, col_err, err_mask): column 0 from `out`, the rest from
     `values`; an undecodable row is all 0 with nerr = SHAMIR_UNDECODABLE.  pack = 1 has no targets and is
-    shamir_reconstruct_corrected."""
+    shamir_reconstruct_corrected.  erased is passed through."""
     if int(pack) == 1:
-        out, nerr, col_err, err_mask = shamir_reconstruct_corrected(params, indices, shares, degree, plain_modulus, host=host, layout=layout)
+        out, nerr, col_err, err_mask = shamir_reconstruct_corrected(params, indices, shares, degree, plain_modulus, host=host, layout=layout,
+                                                                    erased=erased)
         return [[v] for v in out], nerr, col_err, err_mask
     values, out, nerr, col_err, err_mask = shamir_evaluate_corrected(
         params, indices, shares, int(degree) + int(pack) - 1, plain_modulus, shamir_packed_secret_indices(plain_modulus, pack),
-        host=host, layout=layout)
+        host=host, layout=layout, erased=erased)
     secrets = [[int(out[s])] + [int(v) for v in values[s]] for s in range(len(out))]
     return secrets, nerr, col_err, err_mask
 

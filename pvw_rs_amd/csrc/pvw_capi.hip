@@ -2370,7 +2370,10 @@ struct Reconstruct {
   u32 degree;
   const u64* indices;   // [count], host
   size_t count, S, secret_stride, point_stride;
+  bool erasures = false;   // a call with an erasure mask: the locator of a row has up to r + 1 coefficients
   size_t T() const { return count - degree; }
+  size_t red() const { return count - degree - 1; }
+  size_t nk() const { return erasures ? red() + 1 : red() / 2 + 1; }   // the locator capacity of the corrected decode
   size_t ws_bytes() const { return shamir_interp_words(count, degree) * 8; }
 };
 static int32_t reconstruct_checks(const Reconstruct& r, const void* shares, const void* out) {
@@ -2515,10 +2518,15 @@ struct ShareStaging {
     volatile u64* vp = packed.data();
     for (size_t i = 0; i < packed.size(); ++i) vp[i] = 0;
   }
+  // the rows [S][ewords] of the caller's erasure mask go up with their shares, dense as they lie, to d_erased
+  const u64* erased = nullptr;
+  u64* d_erased = nullptr;
+  size_t ewords() const { return (r.count + 63) / 64; }
   int32_t run(u64* d_sh, hipStream_t stream, const std::function<int32_t(size_t s0, size_t cnt)>& piece) {
     const size_t count = r.count;
     for (size_t s0 = 0; s0 < r.S; s0 += per) {
       const size_t cnt = (r.S - s0) < per ? (r.S - s0) : per;
+      if (erased) PVW_HIP(hipMemcpyAsync(d_erased, erased + s0 * ewords(), cnt * ewords() * 8, hipMemcpyHostToDevice, stream));
       if (dense) {
         PVW_HIP(hipMemcpy2DAsync(d_sh, count * 8, shares + s0 * r.secret_stride, r.secret_stride * 8, count * 8, cnt, hipMemcpyHostToDevice, stream));
       } else {
@@ -2679,15 +2687,16 @@ int32_t pvw_shamir_reconstruct_corrected_host(uint64_t plain_modulus, uint32_t d
 
 // The device scratch of one call, in words from its base: M first (the one region marked secret besides the staging), then
 // what the indices alone decide, then what the errors decide.  `cap` secrets are in flight at a time.
-//   M [cap][count] | x, aux, lambda, V, X (shamir_correct_public_words) | Synd [cap][r] | Lambda [cap][E+1] | L [cap] (u32)
+//   M [cap][count] | x, aux, lambda, V, X (shamir_correct_public_words) | Synd [cap][r] | Lambda [cap][nk] | L [cap] (u32)
+// nk, the locator capacity, is E + 1, or r + 1 for a call with erasures: X has nk rows as well.
 struct CorrectLayout {
-  size_t count, r, E, cap;
+  size_t count, r, nk, cap;
   size_t pub, synd, lam, L, total;   // word offsets
-  CorrectLayout(const Reconstruct& rc, size_t cap_) : count(rc.count), r(rc.count - rc.degree - 1), E(r / 2), cap(cap_) {
+  CorrectLayout(const Reconstruct& rc, size_t cap_) : count(rc.count), r(rc.red()), nk(rc.nk()), cap(cap_) {
     pub = cap * count;
-    synd = pub + shamir_correct_public_words(count, rc.degree);
+    synd = pub + shamir_correct_public_words(count, rc.degree, nk);
     lam = synd + cap * r;
-    L = lam + cap * (E + 1);
+    L = lam + cap * nk;
     total = L + (cap + 1) / 2;
   }
   size_t bytes() const { return total * 8; }
@@ -2697,8 +2706,7 @@ struct CorrectLayout {
 // within 64 MiB -- M alone is count words a secret -- and within what one grid holds (tuning build: PVW_CORRECT_PIECE_BYTES,
 // read per call, so that the tests take several passes at small shapes).
 static size_t correct_piece(const Reconstruct& r) {
-  const size_t red = r.count - r.degree - 1;
-  const size_t per = (r.count + red + red / 2 + 1) * 8 + 4;
+  const size_t per = (r.count + r.red() + r.nk()) * 8 + 4;
   const long env = PVW_ENV_INT("PVW_CORRECT_PIECE_BYTES", 0);
   const size_t budget = env > 0 ? (size_t)env : (size_t)64 << 20;
   size_t cap = budget / per;
@@ -2720,36 +2728,44 @@ static int32_t correct_device_checks(const Reconstruct& r) {
 static int32_t correct_weights(pvw_ctx* c, const Reconstruct& r, const CorrectLayout& lay, u64* ws, hipStream_t s) {
   ProfScope ps(c, "shamir_correct_weights", s);
   PVW_HIP(launch_shamir_points(r.indices, r.count, ws + lay.pub, s));
-  PVW_HIP(launch_shamir_correct_weights(ws + lay.pub, r.count, r.degree, shamir_mod(r.p), s));
+  PVW_HIP(launch_shamir_correct_weights(ws + lay.pub, r.count, r.degree, (u32)lay.nk, shamir_mod(r.p), s));
   return PVW_OK;
 }
-// ns <= lay.cap secrets from d_shares: their out, nerr and mask rows; col_err, zeroed by the caller, is added to
+// ns <= lay.cap secrets from d_shares: their out, nerr and mask rows; col_err, zeroed by the caller, is added to.
+// d_erased: the ns rows of the erasure mask, or NULL for the calls of 8.11 and 8.13.
 static int32_t correct_piece_enqueue(pvw_ctx* c, const Reconstruct& r, const CorrectLayout& lay, u64* ws, const u64* d_shares, size_t ns,
                                      size_t secret_stride, size_t point_stride, u64* d_out, u32* d_nerr, u32* d_col_err, u64* d_mask,
-                                     hipStream_t s) {
+                                     hipStream_t s, const u64* d_erased = nullptr) {
   ProfScope ps(c, "shamir_correct", s);
   const Mod m = shamir_mod(r.p);
   const u64* pub = ws + lay.pub;
   const u64 *lambda = pub + 2 * r.count + 1, *V = lambda + r.count, *X = V + r.count * lay.r;
   u64 *M = ws, *synd = ws + lay.synd, *Lam = ws + lay.lam;
   u32* L = (u32*)(ws + lay.L);
-  ShamirMatmul a{};
+  ShamirMaskedMatmul a{};
   a.A = d_shares, a.secret_stride = secret_stride, a.term_stride = point_stride;
   a.W = V, a.out = synd;
   a.ns = (u32)ns, a.terms = (u32)r.count, a.T = (u32)lay.r, a.m = m;
-  PVW_HIP(launch_shamir_matmul(a, s));
-  PVW_HIP(launch_shamir_bm(synd, Lam, L, (u32)ns, (u32)lay.r, m, s));
+  a.erased = d_erased, a.ewords = (u32)((r.count + 63) / 64);
+  if (d_erased) {
+    PVW_HIP(launch_shamir_matmul_masked(a, s));
+    PVW_HIP(launch_shamir_bm_erasures(synd, d_erased, pub, Lam, L, (u32)ns, (u32)r.count, (u32)lay.r, m, s));
+  } else {
+    PVW_HIP(launch_shamir_matmul(a, s));
+    PVW_HIP(launch_shamir_bm(synd, Lam, L, (u32)ns, (u32)lay.r, m, s));
+  }
   ShamirMatmul b{};
-  b.A = Lam, b.secret_stride = lay.E + 1, b.term_stride = 1;
+  b.A = Lam, b.secret_stride = lay.nk, b.term_stride = 1;
   b.W = X, b.out = M;
-  b.ns = (u32)ns, b.terms = (u32)lay.E + 1, b.T = (u32)r.count, b.m = m;
+  b.ns = (u32)ns, b.terms = (u32)lay.nk, b.T = (u32)r.count, b.m = m;
   PVW_HIP(launch_shamir_matmul(b, s));
   ShamirFinish f{};
   f.shares = d_shares, f.secret_stride = secret_stride, f.point_stride = point_stride;
   f.M = M, f.Lam = Lam, f.L = L, f.lam = lambda;
   f.out = d_out, f.nerr = d_nerr, f.col_err = d_col_err, f.mask = d_mask;
-  f.count = (u32)r.count, f.E = (u32)lay.E, f.m = m;
-  PVW_HIP(launch_shamir_correct_finish(f, (u32)ns, s));
+  f.count = (u32)r.count, f.E = (u32)lay.nk - 1, f.m = m;
+  if (d_erased) PVW_HIP(launch_shamir_erasures_finish(f, d_erased, (u32)ns, s));
+  else PVW_HIP(launch_shamir_correct_finish(f, (u32)ns, s));
   return PVW_OK;
 }
 
@@ -2767,6 +2783,27 @@ static int32_t correct_passes(const Reconstruct& r, size_t cap, const std::funct
   return PVW_OK;
 }
 
+// The device call of 8.11 behind its argument checks; with d_erased (r.erasures) that of 8.16.  `unsized`: what a captured call
+// is refused with when nothing has sized the workspace.
+static int32_t corrected_device_call(pvw_ctx* c, const Reconstruct& r, const u64* d_shares, const u64* d_erased, u64* d_out, u32* d_nerr,
+                                     u32* d_col_err, u64* d_err_mask, void* stream, const char* unsized) {
+  const CorrectLayout lay(r, correct_piece(r));
+  const size_t words = (r.count + 63) / 64;
+  // the caller's stream is checked before the context initialises its device (pvw_shamir_reconstruct_checked_device)
+  auto sized = [&](hipStream_t s) { return grown_capture_check(c, s, &Workspace::correct_bytes, lay.bytes(), unsized); };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
+    PVW_TRY(correct_block(w, lay.bytes(), {{0, lay.m_bytes()}}, s));
+    PVW_TRY(correct_weights(c, r, lay, w->correct, s));
+    PVW_HIP(launch_shamir_zero_counts(d_col_err, r.count, s));
+    return correct_passes(r, lay.cap, [&](size_t s0, size_t ns) {
+      return correct_piece_enqueue(c, r, lay, w->correct, d_shares + s0 * r.secret_stride, ns, r.secret_stride, r.point_stride, d_out + s0,
+                                   Report::from(d_nerr, s0), d_col_err, Report::from(d_err_mask, s0 * words), s,
+                                   Report::from(d_erased, s0 * words));
+    });
+  });
+}
+
 int32_t pvw_shamir_reconstruct_corrected_device(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
                                                 size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
                                                 size_t point_stride, uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err,
@@ -2775,44 +2812,25 @@ int32_t pvw_shamir_reconstruct_corrected_device(pvw_ctx* c, uint64_t plain_modul
   const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(reconstruct_checks(r, d_shares, d_out));
   PVW_TRY(correct_device_checks(r));
-  const CorrectLayout lay(r, correct_piece(r));
-  const size_t words = (count + 63) / 64;
-  // the caller's stream is checked before the context initialises its device (pvw_shamir_reconstruct_checked_device)
-  auto sized = [&](hipStream_t s) {
-    return grown_capture_check(c, s, &Workspace::correct_bytes, lay.bytes(),
+  return corrected_device_call(c, r, d_shares, nullptr, d_out, d_nerr, d_col_err, d_err_mask, stream,
                                "corrected reconstruction under stream capture: run a call with the same degree and count and at least as "
                                "many secrets on this stream outside capture first (it sizes the workspace)");
-  };
-  if (stream) PVW_TRY(sized((hipStream_t)stream));
-  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
-    PVW_TRY(correct_block(w, lay.bytes(), {{0, lay.m_bytes()}}, s));
-    PVW_TRY(correct_weights(c, r, lay, w->correct, s));
-    PVW_HIP(launch_shamir_zero_counts(d_col_err, count, s));
-    return correct_passes(r, lay.cap, [&](size_t s0, size_t ns) {
-      return correct_piece_enqueue(c, r, lay, w->correct, d_shares + s0 * secret_stride, ns, secret_stride, point_stride, d_out + s0,
-                                   Report::from(d_nerr, s0), d_col_err, Report::from(d_err_mask, s0 * words), s);
-    });
-  });
 }
 
 // host buffers: the secrets go up in pieces as pvw_shamir_reconstruct_checked stages them (each packed to [piece][count], or
 // whole rows by a 2D copy), a piece no larger than one pass over the kernels; the public matrices are made once and col_err
 // adds up over the pieces.  The staged shares, the staged secrets and M are cleared before the call returns.
-int32_t pvw_shamir_reconstruct_corrected(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
-                                         const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
-                                         uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
-  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
-  PVW_TRY(reconstruct_checks(r, shares, out));
-  PVW_TRY(correct_device_checks(r));
+// Behind the argument checks; with `erased` (r.erasures) the host-buffer call of 8.16, whose mask rows are staged with the shares.
+static int32_t corrected_host_call(pvw_ctx* c, const Reconstruct& r, const u64* shares, const u64* erased, u64* out, u32* nerr, u32* col_err,
+                                   u64* err_mask) {
   PVW_TRY(ensure_device(c));
-  const size_t words = (count + 63) / 64;
-  size_t per = chunk_1gib((count + 1 + words) * 8 + 4, num_secrets);
+  const size_t count = r.count, words = (count + 63) / 64;
+  size_t per = chunk_1gib((count + 1 + words + (erased ? words : 0)) * 8 + 4, r.S);
   if (per > correct_piece(r)) per = correct_piece(r);
   const CorrectLayout lay(r, per);
   Scratch sc;
   const size_t r_sh = sc.add(per * count * 8), r_out = sc.add(per * 8), r_ws = sc.add(lay.bytes()), r_nerr = sc.add(per * 4),
-               r_col = sc.add(count * 4), r_mask = sc.add(per * words * 8);
+               r_col = sc.add(count * 4), r_mask = sc.add(per * words * 8), r_er = sc.add(erased ? per * words * 8 : 0);
   ShareStaging st(r, shares, per);
   return host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
@@ -2820,10 +2838,11 @@ int32_t pvw_shamir_reconstruct_corrected(pvw_ctx* c, uint64_t plain_modulus, uin
     ws_mark_secret(w, d_sh, (size_t)((char*)ws - (char*)d_sh) + lay.m_bytes());   // staged shares | staged secrets | M
     u32 *d_nerr = nerr ? sc.at<u32>(r_nerr) : nullptr, *d_col = col_err ? sc.at<u32>(r_col) : nullptr;
     u64* d_mask = err_mask ? sc.at(r_mask) : nullptr;
+    if (erased) st.erased = erased, st.d_erased = sc.at(r_er);
     PVW_TRY(correct_weights(c, r, lay, ws, w->stream));
     PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
     PVW_TRY(st.run(d_sh, w->stream, [&](size_t s0, size_t cnt) -> int32_t {
-      PVW_TRY(correct_piece_enqueue(c, r, lay, ws, d_sh, cnt, count, 1, d_out, d_nerr, d_col, d_mask, w->stream));
+      PVW_TRY(correct_piece_enqueue(c, r, lay, ws, d_sh, cnt, count, 1, d_out, d_nerr, d_col, d_mask, w->stream, st.d_erased));
       PVW_HIP(hipMemcpyAsync(out + s0, d_out, cnt * 8, hipMemcpyDeviceToHost, w->stream));
       if (nerr) PVW_HIP(hipMemcpyAsync(nerr + s0, d_nerr, cnt * 4, hipMemcpyDeviceToHost, w->stream));
       if (err_mask) PVW_HIP(hipMemcpyAsync(err_mask + s0 * words, d_mask, cnt * words * 8, hipMemcpyDeviceToHost, w->stream));
@@ -2832,6 +2851,15 @@ int32_t pvw_shamir_reconstruct_corrected(pvw_ctx* c, uint64_t plain_modulus, uin
     if (col_err) PVW_HIP(hipMemcpyAsync(col_err, d_col, count * 4, hipMemcpyDeviceToHost, w->stream));
     return PVW_OK;
   });
+}
+int32_t pvw_shamir_reconstruct_corrected(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                         const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                         uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  PVW_TRY(reconstruct_checks(r, shares, out));
+  PVW_TRY(correct_device_checks(r));
+  return corrected_host_call(c, r, shares, nullptr, out, nerr, col_err, err_mask);
 }
 
 // ------------------------------------------------------------------------ evaluation of the corrected polynomials
@@ -2868,8 +2896,7 @@ int32_t pvw_shamir_evaluate_corrected_host(uint64_t plain_modulus, uint32_t degr
 // PVW_EVALUATE_GROUP_BYTES, read per call, so that the tests walk several groups at small shapes).  Whole blocks of 64 targets
 // when there are that many.
 static size_t evaluate_group(const Reconstruct& r, size_t num_targets) {
-  const size_t E = (r.count - r.degree - 1) / 2;
-  const size_t per = (r.count + 2 * (E + 1) + 2) * 8 + 4;
+  const size_t per = (r.count + 2 * r.nk() + 2) * 8 + 4;
   const long env = PVW_ENV_INT("PVW_EVALUATE_GROUP_BYTES", 0);
   const size_t budget = env > 0 ? (size_t)env : (size_t)64 << 20;
   size_t tg = budget / per;
@@ -2880,8 +2907,7 @@ static size_t evaluate_group(const Reconstruct& r, size_t num_targets) {
 // The per-secret scratch of the evaluation, in bytes: a row of M, of the syndromes and of the locators as in correct_piece, and a
 // row of y o M, of raw, of Lambda and of Lambda' at the group's targets, a stand-in for out, L and a stand-in for nerr
 static size_t evaluate_secret_bytes(const Reconstruct& r, size_t Tg) {
-  const size_t red = r.count - r.degree - 1;
-  return (2 * r.count + red + red / 2 + 1 + 3 * Tg + 2) * 8;
+  return (2 * r.count + r.red() + r.nk() + 3 * Tg + 2) * 8;
 }
 static size_t evaluate_piece_budget() {
   const long env = PVW_ENV_INT("PVW_CORRECT_PIECE_BYTES", 0);
@@ -2909,7 +2935,7 @@ struct EvaluateLayout {
     lamD = lamT + cap * Tg;
     nerr = lamD + cap * Tg;
     pub = nerr + (cap + 1) / 2;
-    total = pub + shamir_evaluate_public_words(rc.count, rc.degree, Tg);
+    total = pub + shamir_evaluate_public_words(rc.count, Tg, cl.nk);
   }
   size_t bytes() const { return total * 8; }
   size_t secret_bytes() const { return (lamT - ym) * 8; }
@@ -2920,22 +2946,23 @@ static size_t evaluate_need_bytes(const Reconstruct& r, size_t Tg) {
   const size_t per = evaluate_secret_bytes(r, Tg), budget = evaluate_piece_budget();
   size_t part = r.S > budget / per ? budget : r.S * per;
   if (part < per) part = per;
-  return part + 16 + (shamir_correct_public_words(r.count, r.degree) + shamir_evaluate_public_words(r.count, r.degree, Tg)) * 8;
+  return part + 16 + (shamir_correct_public_words(r.count, r.degree, r.nk()) + shamir_evaluate_public_words(r.count, Tg, r.nk())) * 8;
 }
 // One pass: ns <= lay.cl.cap secrets from d_shares are decoded (their out, nerr and mask rows; col_err is added to) and evaluated
 // at all targets, group by group, into d_values (rows num_targets words apart).  `resident` is the first target of the group whose
 // public matrices the block holds; with one group they are built once for all passes.
 static int32_t evaluate_pass_enqueue(pvw_ctx* c, const Reconstruct& r, const EvaluateLayout& lay, u64* ws, const u64* d_shares, size_t ns,
                                      size_t secret_stride, size_t point_stride, const u64* targets, size_t num_targets, u64* d_values,
-                                     u64* d_out, u32* d_nerr, u32* d_col_err, u64* d_mask, size_t* resident, hipStream_t s) {
+                                     u64* d_out, u32* d_nerr, u32* d_col_err, u64* d_mask, size_t* resident, hipStream_t s,
+                                     const u64* d_erased = nullptr) {
   const Mod m = shamir_mod(r.p);
   if (!d_out) d_out = ws + lay.outs;
   if (!d_nerr) d_nerr = (u32*)(ws + lay.nerr);
-  PVW_TRY(correct_piece_enqueue(c, r, lay.cl, ws, d_shares, ns, secret_stride, point_stride, d_out, d_nerr, d_col_err, d_mask, s));
+  PVW_TRY(correct_piece_enqueue(c, r, lay.cl, ws, d_shares, ns, secret_stride, point_stride, d_out, d_nerr, d_col_err, d_mask, s, d_erased));
   const u64 *x = ws + lay.cl.pub, *aux = x + r.count;
   const u64 *M = ws, *Lam = ws + lay.cl.lam;
   u64 *YM = ws + lay.ym, *raw = ws + lay.raw, *LamT = ws + lay.lamT, *LamD = ws + lay.lamD, *pub = ws + lay.pub;
-  const size_t nk = lay.cl.E + 1;
+  const size_t nk = lay.cl.nk;
   {
     ProfScope ps(c, "shamir_evaluate", s);
     PVW_HIP(launch_shamir_ym(d_shares, secret_stride, point_stride, M, YM, (u32)ns, (u32)r.count, m, s));
@@ -2945,7 +2972,7 @@ static int32_t evaluate_pass_enqueue(pvw_ctx* c, const Reconstruct& r, const Eva
     if (*resident != j0) {
       ProfScope ps(c, "shamir_evaluate_weights", s);
       PVW_HIP(launch_shamir_points(targets + j0, tg, pub, s));
-      PVW_HIP(launch_shamir_evaluate_weights(x, aux, pub, r.count, r.degree, tg, m, s));
+      PVW_HIP(launch_shamir_evaluate_weights(x, aux, pub, r.count, (u32)nk, tg, m, s));
       *resident = j0;
     }
     ProfScope ps(c, "shamir_evaluate", s);
@@ -2973,6 +3000,31 @@ static int32_t evaluate_pass_enqueue(pvw_ctx* c, const Reconstruct& r, const Eva
   return PVW_OK;
 }
 
+// The device call of 8.13 behind its argument checks; with d_erased (r.erasures) that of 8.16 (corrected_device_call)
+static int32_t evaluate_device_call(pvw_ctx* c, const Reconstruct& r, const u64* d_shares, const u64* d_erased, const u64* targets,
+                                    size_t num_targets, u64* d_values, u64* d_out, u32* d_nerr, u32* d_col_err, u64* d_err_mask, void* stream,
+                                    const char* unsized) {
+  const size_t Tg = evaluate_group(r, num_targets);
+  const EvaluateLayout lay(r, evaluate_piece(r, Tg), Tg);
+  const size_t need = evaluate_need_bytes(r, Tg);
+  if (need < lay.bytes()) return fail(PVW_ERR_INTERNAL, "evaluation scratch: layout beyond its bound");
+  const size_t words = (r.count + 63) / 64;
+  // the caller's stream is checked before the context initialises its device (pvw_shamir_reconstruct_checked_device)
+  auto sized = [&](hipStream_t s) { return grown_capture_check(c, s, &Workspace::correct_bytes, need, unsized); };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
+    PVW_TRY(correct_block(w, need, {{0, lay.cl.m_bytes()}, {lay.ym, lay.secret_bytes()}}, s));
+    PVW_TRY(correct_weights(c, r, lay.cl, w->correct, s));
+    PVW_HIP(launch_shamir_zero_counts(d_col_err, r.count, s));
+    size_t resident = SIZE_MAX;
+    return correct_passes(r, lay.cl.cap, [&](size_t s0, size_t ns) {
+      return evaluate_pass_enqueue(c, r, lay, w->correct, d_shares + s0 * r.secret_stride, ns, r.secret_stride, r.point_stride, targets,
+                                   num_targets, d_values + s0 * num_targets, Report::from(d_out, s0), Report::from(d_nerr, s0), d_col_err,
+                                   Report::from(d_err_mask, s0 * words), &resident, s, Report::from(d_erased, s0 * words));
+    });
+  });
+}
+
 int32_t pvw_shamir_evaluate_corrected_device(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
                                              const uint64_t* d_shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
                                              const uint64_t* targets, size_t num_targets, uint64_t* d_values, uint64_t* d_out,
@@ -2980,50 +3032,26 @@ int32_t pvw_shamir_evaluate_corrected_device(pvw_ctx* c, uint64_t plain_modulus,
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(evaluate_checks(r, d_shares, targets, num_targets, d_values, true));
-  const size_t Tg = evaluate_group(r, num_targets);
-  const EvaluateLayout lay(r, evaluate_piece(r, Tg), Tg);
-  const size_t need = evaluate_need_bytes(r, Tg);
-  if (need < lay.bytes()) return fail(PVW_ERR_INTERNAL, "evaluation scratch: layout beyond its bound");
-  const size_t words = (count + 63) / 64;
-  // the caller's stream is checked before the context initialises its device (pvw_shamir_reconstruct_checked_device)
-  auto sized = [&](hipStream_t s) {
-    return grown_capture_check(c, s, &Workspace::correct_bytes, need,
-                               "corrected evaluation under stream capture: run a call with the same degree and count, at least as many "
-                               "targets and at least as many secrets on this stream outside capture first (it sizes the workspace)");
-  };
-  if (stream) PVW_TRY(sized((hipStream_t)stream));
-  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
-    PVW_TRY(correct_block(w, need, {{0, lay.cl.m_bytes()}, {lay.ym, lay.secret_bytes()}}, s));
-    PVW_TRY(correct_weights(c, r, lay.cl, w->correct, s));
-    PVW_HIP(launch_shamir_zero_counts(d_col_err, count, s));
-    size_t resident = SIZE_MAX;
-    return correct_passes(r, lay.cl.cap, [&](size_t s0, size_t ns) {
-      return evaluate_pass_enqueue(c, r, lay, w->correct, d_shares + s0 * secret_stride, ns, secret_stride, point_stride, targets,
-                                   num_targets, d_values + s0 * num_targets, Report::from(d_out, s0), Report::from(d_nerr, s0), d_col_err,
-                                   Report::from(d_err_mask, s0 * words), &resident, s);
-    });
-  });
+  return evaluate_device_call(c, r, d_shares, nullptr, targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask, stream,
+                              "corrected evaluation under stream capture: run a call with the same degree and count, at least as many "
+                              "targets and at least as many secrets on this stream outside capture first (it sizes the workspace)");
 }
 
 // host buffers: staged as pvw_shamir_reconstruct_corrected stages (each piece one pass over the kernels, packed to [piece][count]
 // or whole rows by a 2D copy); the values of a piece come down as one block.  The staged shares, secrets and values, M, y o M and
 // raw are cleared before the call returns.
-int32_t pvw_shamir_evaluate_corrected(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
-                                      const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
-                                      const uint64_t* targets, size_t num_targets, uint64_t* values, uint64_t* out, uint32_t* nerr,
-                                      uint32_t* col_err, uint64_t* err_mask) {
-  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
-  PVW_TRY(evaluate_checks(r, shares, targets, num_targets, values, true));
+static int32_t evaluate_host_call(pvw_ctx* c, const Reconstruct& r, const u64* shares, const u64* erased, const u64* targets,
+                                  size_t num_targets, u64* values, u64* out, u32* nerr, u32* col_err, u64* err_mask) {
   PVW_TRY(ensure_device(c));
-  const size_t words = (count + 63) / 64;
+  const size_t count = r.count, words = (count + 63) / 64;
   const size_t Tg = evaluate_group(r, num_targets);
-  size_t per = chunk_1gib((count + 1 + words + num_targets) * 8 + 4, num_secrets);
+  size_t per = chunk_1gib((count + 1 + words + (erased ? words : 0) + num_targets) * 8 + 4, r.S);
   if (per > evaluate_piece(r, Tg)) per = evaluate_piece(r, Tg);
   const EvaluateLayout lay(r, per, Tg);
   Scratch sc;
   const size_t r_sh = sc.add(per * count * 8), r_out = sc.add(per * 8), r_val = sc.add(per * num_targets * 8), r_ws = sc.add(lay.bytes()),
-               r_nerr = sc.add(per * 4), r_col = sc.add(count * 4), r_mask = sc.add(per * words * 8);
+               r_nerr = sc.add(per * 4), r_col = sc.add(count * 4), r_mask = sc.add(per * words * 8),
+               r_er = sc.add(erased ? per * words * 8 : 0);
   ShareStaging st(r, shares, per);
   return host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
@@ -3032,12 +3060,13 @@ int32_t pvw_shamir_evaluate_corrected(pvw_ctx* c, uint64_t plain_modulus, uint32
     ws_mark_secret(w, ws + lay.ym, lay.secret_bytes());                              // y o M | raw | the stand-in for out
     u32 *d_nerr = sc.at<u32>(r_nerr), *d_col = col_err ? sc.at<u32>(r_col) : nullptr;
     u64* d_mask = err_mask ? sc.at(r_mask) : nullptr;
+    if (erased) st.erased = erased, st.d_erased = sc.at(r_er);
     PVW_TRY(correct_weights(c, r, lay.cl, ws, w->stream));
     PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
     size_t resident = SIZE_MAX;
     PVW_TRY(st.run(d_sh, w->stream, [&](size_t s0, size_t cnt) -> int32_t {
       PVW_TRY(evaluate_pass_enqueue(c, r, lay, ws, d_sh, cnt, count, 1, targets, num_targets, d_val, d_out, d_nerr, d_col, d_mask, &resident,
-                                    w->stream));
+                                    w->stream, st.d_erased));
       PVW_HIP(hipMemcpyAsync(values + s0 * num_targets, d_val, cnt * num_targets * 8, hipMemcpyDeviceToHost, w->stream));
       if (out) PVW_HIP(hipMemcpyAsync(out + s0, d_out, cnt * 8, hipMemcpyDeviceToHost, w->stream));
       if (nerr) PVW_HIP(hipMemcpyAsync(nerr + s0, d_nerr, cnt * 4, hipMemcpyDeviceToHost, w->stream));
@@ -3045,6 +3074,200 @@ int32_t pvw_shamir_evaluate_corrected(pvw_ctx* c, uint64_t plain_modulus, uint32
       return PVW_OK;
     }));
     if (col_err) PVW_HIP(hipMemcpyAsync(col_err, d_col, count * 4, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
+}
+int32_t pvw_shamir_evaluate_corrected(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                      const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                      const uint64_t* targets, size_t num_targets, uint64_t* values, uint64_t* out, uint32_t* nerr,
+                                      uint32_t* col_err, uint64_t* err_mask) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  PVW_TRY(evaluate_checks(r, shares, targets, num_targets, values, true));
+  return evaluate_host_call(c, r, shares, nullptr, targets, num_targets, values, out, nerr, col_err, err_mask);
+}
+
+// ------------------------------------------------------------------------ reconstruction with erasures
+// erased [num_secrets][W], W = ceil(count / 64), in the layout of err_mask: share (s, c) is known to be bad.  With eps_s erased
+// columns in row s and E_s = (r - eps_s) / 2, row s is decodable iff eps_s <= r and some F_s of degree <= t disagrees with the row
+// in at most E_s of the columns that are not erased: 8.11's definition on the sub-row, which is what the host form runs.
+// erased == NULL is the call of 8.11 or 8.13, its bounds included: every entry point hands such a call over as it is.
+
+// The contract in plain C++: per row the columns that are not erased are compacted, berlekamp_welch_host decodes that sub-row
+// with the same t, and the mask bits and col_err go back to the original columns.  A row with fewer than t + 1 columns left
+// (eps_s > r) is undecodable.  Nothing at an erased position is read.
+static void erasures_host(const Reconstruct& r, const u64* shares, const u64* erased, u64* out, u32* nerr, u32* col_err, u64* err_mask,
+                          const u64* targets, size_t num_targets, u64* values) {
+  const size_t count = r.count, words = (count + 63) / 64;
+  std::vector<size_t> cols;
+  std::vector<u64> sub_idx(count), sub_sh(count), sub_mask(words);
+  std::vector<u32> sub_col(count);
+  if (col_err) std::fill(col_err, col_err + count, 0u);
+  for (size_t s = 0; s < r.S; ++s) {
+    cols.clear();
+    for (size_t c = 0; c < count; ++c)
+      if (!((erased[s * words + c / 64] >> (c % 64)) & 1)) cols.push_back(c);
+    if (err_mask) std::fill(err_mask + s * words, err_mask + (s + 1) * words, (u64)0);
+    const size_t n = cols.size();
+    if (n < (size_t)r.degree + 1) {
+      if (out) out[s] = 0;
+      if (nerr) nerr[s] = PVW_SHAMIR_UNDECODABLE;
+      if (values) std::fill(values + s * num_targets, values + (s + 1) * num_targets, (u64)0);
+      continue;
+    }
+    for (size_t i = 0; i < n; ++i) {
+      sub_idx[i] = r.indices[cols[i]];
+      sub_sh[i] = shares[s * r.secret_stride + cols[i] * r.point_stride];
+    }
+    const Reconstruct sub{r.p, r.degree, sub_idx.data(), n, 1, n, 1};
+    u64 o = 0;
+    u32 ne = 0;
+    berlekamp_welch_host(sub, sub_sh.data(), &o, &ne, sub_col.data(), sub_mask.data(), targets, num_targets,
+                         values ? values + s * num_targets : nullptr);
+    if (out) out[s] = o;
+    if (nerr) nerr[s] = ne;
+    for (size_t i = 0; i < n; ++i)
+      if ((sub_mask[i / 64] >> (i % 64)) & 1) {
+        if (col_err) ++col_err[cols[i]];
+        if (err_mask) err_mask[s * words + cols[i] / 64] |= (u64)1 << (cols[i] % 64);
+      }
+  }
+  volatile u64* vp = sub_sh.data();                                              // as secret as the shares
+  for (size_t i = 0; i < sub_sh.size(); ++i) vp[i] = 0;
+}
+// on the device the errata locator of a row has up to r + 1 coefficients, in one wave's LDS
+static int32_t erasures_device_checks(const Reconstruct& r) {
+  if (r.red() + 1 > PVW_SHAMIR_MAX_LOCATOR) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "on the device the locator of a row with erasures holds at most %d coefficients: count - degree - 1 must be "
+             "below %d", PVW_SHAMIR_MAX_LOCATOR, PVW_SHAMIR_MAX_LOCATOR);
+    return fail(PVW_ERR_INVALID_PARAMETERS, buf);
+  }
+  return PVW_OK;
+}
+static const char* const kErasuresUnsized =
+    "reconstruction with erasures under stream capture: run a call with an erasure mask, the same degree and count, at least as many "
+    "targets and at least as many secrets on this stream outside capture first (it sizes the workspace)";
+
+int32_t pvw_shamir_reconstruct_erasures_host(uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                             const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                             const uint64_t* erased, uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  if (!erased)
+    return pvw_shamir_reconstruct_corrected_host(plain_modulus, degree, indices, count, shares, num_secrets, secret_stride, point_stride, out,
+                                                 nerr, col_err, err_mask);
+  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
+  PVW_TRY(reconstruct_checks(r, shares, out));
+  erasures_host(r, shares, erased, out, nerr, col_err, err_mask, nullptr, 0, nullptr);
+  return PVW_OK;
+}
+int32_t pvw_shamir_reconstruct_erasures_device(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                               const uint64_t* d_shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                               const uint64_t* d_erased, uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err,
+                                               uint64_t* d_err_mask, void* stream) {
+  if (!d_erased)
+    return pvw_shamir_reconstruct_corrected_device(c, plain_modulus, degree, indices, count, d_shares, num_secrets, secret_stride,
+                                                   point_stride, d_out, d_nerr, d_col_err, d_err_mask, stream);
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
+  PVW_TRY(reconstruct_checks(r, d_shares, d_out));
+  PVW_TRY(correct_device_checks(r));
+  PVW_TRY(erasures_device_checks(r));
+  return corrected_device_call(c, r, d_shares, d_erased, d_out, d_nerr, d_col_err, d_err_mask, stream, kErasuresUnsized);
+}
+int32_t pvw_shamir_reconstruct_erasures(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                        const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                        const uint64_t* erased, uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  if (!erased)
+    return pvw_shamir_reconstruct_corrected(c, plain_modulus, degree, indices, count, shares, num_secrets, secret_stride, point_stride, out,
+                                            nerr, col_err, err_mask);
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
+  PVW_TRY(reconstruct_checks(r, shares, out));
+  PVW_TRY(correct_device_checks(r));
+  PVW_TRY(erasures_device_checks(r));
+  return corrected_host_call(c, r, shares, erased, out, nerr, col_err, err_mask);
+}
+
+int32_t pvw_shamir_evaluate_erasures_host(uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                          const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                          const uint64_t* erased, const uint64_t* targets, size_t num_targets, uint64_t* values, uint64_t* out,
+                                          uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  if (!erased)
+    return pvw_shamir_evaluate_corrected_host(plain_modulus, degree, indices, count, shares, num_secrets, secret_stride, point_stride, targets,
+                                              num_targets, values, out, nerr, col_err, err_mask);
+  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
+  PVW_TRY(evaluate_checks(r, shares, targets, num_targets, values, false));
+  erasures_host(r, shares, erased, out, nerr, col_err, err_mask, targets, num_targets, values);
+  return PVW_OK;
+}
+int32_t pvw_shamir_evaluate_erasures_device(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                            const uint64_t* d_shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                            const uint64_t* d_erased, const uint64_t* targets, size_t num_targets, uint64_t* d_values,
+                                            uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err, uint64_t* d_err_mask, void* stream) {
+  if (!d_erased)
+    return pvw_shamir_evaluate_corrected_device(c, plain_modulus, degree, indices, count, d_shares, num_secrets, secret_stride, point_stride,
+                                                targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask, stream);
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
+  PVW_TRY(evaluate_checks(r, d_shares, targets, num_targets, d_values, true));
+  PVW_TRY(erasures_device_checks(r));
+  return evaluate_device_call(c, r, d_shares, d_erased, targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask, stream,
+                              kErasuresUnsized);
+}
+int32_t pvw_shamir_evaluate_erasures(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                     const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                     const uint64_t* erased, const uint64_t* targets, size_t num_targets, uint64_t* values, uint64_t* out,
+                                     uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  if (!erased)
+    return pvw_shamir_evaluate_corrected(c, plain_modulus, degree, indices, count, shares, num_secrets, secret_stride, point_stride, targets,
+                                         num_targets, values, out, nerr, col_err, err_mask);
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
+  PVW_TRY(evaluate_checks(r, shares, targets, num_targets, values, true));
+  PVW_TRY(erasures_device_checks(r));
+  return evaluate_host_call(c, r, shares, erased, targets, num_targets, values, out, nerr, col_err, err_mask);
+}
+
+// The mask from a decrypt report: bit (s, c) set iff status(s, c) & status_bits or noise(s, c) > noise_bound; either array may be
+// NULL, not both; element (s, c) at s * secret_stride + c * point_stride; every word of mask_out [num_secrets][W] is written.
+static int32_t erasure_mask_checks(const void* status, const void* noise, size_t count, size_t num_secrets, size_t secret_stride,
+                                   size_t point_stride, const void* mask_out) {
+  if ((!status && !noise) || !mask_out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (count == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no shares to flag");
+  if (num_secrets == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no secrets to reconstruct");
+  if (secret_stride == 0 || point_stride == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "a stride of 0");
+  return PVW_OK;
+}
+int32_t pvw_shamir_erasure_mask_host(uint32_t* status, const uint64_t* noise, uint32_t status_bits, uint64_t noise_bound, size_t count,
+                                     size_t num_secrets, size_t secret_stride, size_t point_stride, uint64_t* mask_out) {
+  PVW_TRY(erasure_mask_checks(status, noise, count, num_secrets, secret_stride, point_stride, mask_out));
+  const size_t words = (count + 63) / 64;
+  std::fill(mask_out, mask_out + num_secrets * words, (u64)0);
+  for (size_t s = 0; s < num_secrets; ++s)
+    for (size_t c = 0; c < count; ++c) {
+      const size_t off = s * secret_stride + c * point_stride;
+      if ((status && (status[off] & status_bits)) || (noise && noise[off] > noise_bound)) mask_out[s * words + c / 64] |= (u64)1 << (c % 64);
+    }
+  return PVW_OK;
+}
+int32_t pvw_shamir_erasure_mask_device(pvw_ctx* c, uint32_t* d_status, const uint64_t* d_noise, uint32_t status_bits,
+                                       uint64_t noise_bound, size_t count, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                       uint64_t* d_mask_out, void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(erasure_mask_checks(d_status, d_noise, count, num_secrets, secret_stride, point_stride, d_mask_out));
+  if (count >= ((size_t)1 << 31) || num_secrets >= ((size_t)1 << 31))
+    return fail(PVW_ERR_INVALID_PARAMETERS, "count and num_secrets must be below 2^31 on the device");
+  // no scratch of its own; under capture the stream's workspace must exist already, as for the calls the mask is made for
+  auto sized = [&](hipStream_t s) {
+    return grown_capture_check(c, s, &Workspace::correct_bytes, 0,
+                               "erasure mask under stream capture: run a call on this stream outside capture first (it makes the stream's "
+                               "workspace)");
+  };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  return device_call(c, stream, sized, [&](Workspace*, hipStream_t s) -> int32_t {
+    ProfScope ps(c, "shamir_erasure_mask", s);
+    PVW_HIP(launch_shamir_erasure_mask(d_status, d_noise, status_bits, noise_bound, (u32)count, (u32)num_secrets, secret_stride, point_stride,
+                                       d_mask_out, s));
     return PVW_OK;
   });
 }

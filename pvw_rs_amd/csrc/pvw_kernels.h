@@ -293,11 +293,9 @@ hipError_t launch_shamir_interp(const ShamirInterp& b, hipStream_t s);
 
 // ---- Corrected reconstruction (pvw_shamir.hip).  r = count - t - 1 redundant columns, E = r / 2 correctable.
 // Public workspace words, from the indices alone: x [count] | aux [count + 1] (u_c, then prod_i(-x_i)) | lambda [count] |
-// V [count][r] (u_c x_c^j) | X [E+1][count] (x_c^k).
-inline size_t shamir_correct_public_words(size_t count, u32 t) {
-  const size_t r = count - t - 1;
-  return 3 * count + 1 + count * r + (r / 2 + 1) * count;
-}
+// V [count][r] (u_c x_c^j) | X [nk][count] (x_c^k).  nk is the locator capacity of the call: E + 1, or r + 1 with erasures
+// (DESIGN 8.16).
+inline size_t shamir_correct_public_words(size_t count, u32 t, size_t nk) { return 3 * count + 1 + count * (count - t - 1) + nk * count; }
 #define PVW_SHAMIR_NO_LOCATOR 0xFFFFFFFFu                // L of a row whose locator would need more than E coefficients
 #define PVW_SHAMIR_MAX_LOCATOR 4096                      // E + 1 at most: two polynomials of one wave in 64 KiB of LDS
 struct ShamirMatmul {
@@ -322,7 +320,7 @@ struct ShamirFinish {
   u32 count, E;
   Mod m;
 };
-hipError_t launch_shamir_correct_weights(u64* ws, size_t count, u32 degree, const Mod& m, hipStream_t s);
+hipError_t launch_shamir_correct_weights(u64* ws, size_t count, u32 degree, u32 nk, const Mod& m, hipStream_t s);
 hipError_t launch_shamir_matmul(const ShamirMatmul& b, hipStream_t s);
 hipError_t launch_shamir_bm(const u64* synd, u64* lam, u32* L, u32 ns, u32 r, const Mod& m, hipStream_t s);
 hipError_t launch_shamir_correct_finish(const ShamirFinish& f, u32 ns, hipStream_t s);
@@ -332,12 +330,9 @@ hipError_t launch_shamir_correct_finish(const ShamirFinish& f, u32 ns, hipStream
 //   raw[s][j] = sum_i YM[s][i] C[i][j],  YM = y o M,  C[i][j] = u_i / (x*_j - x_i) (0 where the points coincide)
 //   G_s(x*_j) = scale_j raw[s][j] off the points, G_s'(x_c) likewise at a point x*_j = x_c; scale_j = prod_{x_i != x*_j}(x*_j - x_i)
 // Public workspace words of a group, from the indices and targets alone:
-//   xt [Tg] | scale [Tg] | C [count][Tg] | Xt [E+1][Tg] (x*^k) | Xd [E+1][Tg] (k x*^(k-1)) | coin [Tg] (u32)
+//   xt [Tg] | scale [Tg] | C [count][Tg] | Xt [nk][Tg] (x*^k) | Xd [nk][Tg] (k x*^(k-1)) | coin [Tg] (u32)
 #define PVW_SHAMIR_NO_COLUMN 0xFFFFFFFFu                 // coin[j] of a target that is no column's point
-inline size_t shamir_evaluate_public_words(size_t count, u32 t, size_t Tg) {
-  const size_t E = (count - t - 1) / 2;
-  return 2 * Tg + count * Tg + 2 * (E + 1) * Tg + (Tg + 1) / 2;
-}
+inline size_t shamir_evaluate_public_words(size_t count, size_t Tg, size_t nk) { return 2 * Tg + count * Tg + 2 * nk * Tg + (Tg + 1) / 2; }
 struct ShamirEvalFinish {
   const u64* shares;     // as ShamirInterp
   size_t secret_stride, point_stride;
@@ -354,12 +349,31 @@ struct ShamirEvalFinish {
   Mod m;
 };
 // ws: the group's public words; x, aux: the call's points and u_c (launch_shamir_correct_weights)
-hipError_t launch_shamir_evaluate_weights(const u64* x, const u64* aux, u64* ws, size_t count, u32 degree, size_t Tg, const Mod& m,
+hipError_t launch_shamir_evaluate_weights(const u64* x, const u64* aux, u64* ws, size_t count, u32 nk, size_t Tg, const Mod& m,
                                           hipStream_t s);
 // YM[s][c] = y[s][c] M[s][c]
 hipError_t launch_shamir_ym(const u64* shares, size_t secret_stride, size_t point_stride, const u64* M, u64* YM, u32 ns, u32 count,
                             const Mod& m, hipStream_t s);
 hipError_t launch_shamir_evaluate_finish(const ShamirEvalFinish& f, hipStream_t s);
+
+// ---- Reconstruction with erasures (pvw_shamir.hip): erased[s][W], W = ceil(count / 64), bit c % 64 of word c / 64
+// set where share (s, c) is known to be bad.  The frame of the corrected decode with a locator capacity of nk = r + 1 instead of
+// E + 1: the errata locator Psi_s = Gamma_s Lambda_s of a row has up to r + 1 coefficients.
+struct ShamirMaskedMatmul : ShamirMatmul {
+  const u64* erased;     // [ns][ewords]: element (s, j) of A is read as 0 where bit j of row s is set
+  u32 ewords;
+};
+hipError_t launch_shamir_matmul_masked(const ShamirMaskedMatmul& b, hipStream_t s);
+// synd [ns][r] is overwritten (the Forney syndromes take the place of a row's upper part); psi [ns][r + 1] reversed like Lambda,
+// L [ns] = eps_s + deg Lambda_s or PVW_SHAMIR_NO_LOCATOR; x [count] the points
+hipError_t launch_shamir_bm_erasures(u64* synd, const u64* erased, const u64* x, u64* psi, u32* L, u32 ns, u32 count, u32 r, const Mod& m,
+                                     hipStream_t s);
+// f as for launch_shamir_correct_finish with Lam = psi, E = r (rows r + 1 words apart) and L from launch_shamir_bm_erasures
+hipError_t launch_shamir_erasures_finish(const ShamirFinish& f, const u64* erased, u32 ns, hipStream_t s);
+// mask[s][w] for all w < ceil(count / 64): bit (s, c) set iff status[..] & status_bits or noise[..] > noise_bound, element (s, c) of
+// either array (one may be NULL) at s * secret_stride + c * point_stride; padding bits 0
+hipError_t launch_shamir_erasure_mask(const u32* status, const u64* noise, u32 status_bits, u64 noise_bound, u32 count, u32 ns,
+                                      size_t secret_stride, size_t point_stride, u64* mask, hipStream_t s);
 
 // p[0 .. words) = 0, as a kernel launch on s
 hipError_t launch_wipe_words(u64* p, size_t words, hipStream_t s);

@@ -283,8 +283,11 @@ struct ShamirTile {
   size_t tm;
   bool live;
 };
+// MASKED: element (s, j) of A is staged as 0 where bit j of row s of `erased` is set -- the bit test stands beside
+// the load.
+template <bool MASKED = false>
 __device__ __forceinline__ ShamirTile shamir_tile_product(const u64* A, size_t secret_stride, size_t term_stride, const u64* W, u32 ns,
-                                                          u32 nt, u32 T, const Mod m) {
+                                                          u32 nt, u32 T, const Mod m, const u64* erased = nullptr, u32 ewords = 0) {
   __shared__ u64 sh[SH_WAVES][SH_JC][SH_DG];       // 8 KiB: the chunk of A, below p
   __shared__ u64 part[SH_WAVES][SH_DG][64];        // 8 KiB: the waves' partial sums, below p
   const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -309,7 +312,10 @@ __device__ __forceinline__ ShamirTile shamir_tile_product(const u64* A, size_t s
       const u32 off = c * SH_JC + ej;              // within the wave's range
       const u32 j = ew * Q + off;
       u64 a = 0;
-      if (off < Q && j < nt && s0 + eg < ns) a = reduce_word(A[(size_t)(s0 + eg) * secret_stride + (size_t)j * term_stride], m);
+      if (off < Q && j < nt && s0 + eg < ns) {
+        if (!MASKED || !((erased[(size_t)(s0 + eg) * ewords + j / 64] >> (j % 64)) & 1))
+          a = reduce_word(A[(size_t)(s0 + eg) * secret_stride + (size_t)j * term_stride], m);
+      }
       sh[ew][ej][eg] = a;
     }
     __syncthreads();
@@ -564,9 +570,9 @@ __global__ __launch_bounds__(64) void shamir_correct_finish_kernel(ShamirFinish 
   }
 }
 
-// ws: x [count] (filled by launch_shamir_points) | aux [count + 1] | lambda [count] | V [count][r] | X [E+1][count]
-hipError_t launch_shamir_correct_weights(u64* ws, size_t count, u32 t, const Mod& m, hipStream_t s) {
-  const u32 n = (u32)count, r = n - t - 1, nk = r / 2 + 1;
+// ws: x [count] (filled by launch_shamir_points) | aux [count + 1] | lambda [count] | V [count][r] | X [nk][count]
+hipError_t launch_shamir_correct_weights(u64* ws, size_t count, u32 t, u32 nk, const Mod& m, hipStream_t s) {
+  const u32 n = (u32)count, r = n - t - 1;
   const u64* x = ws;
   u64 *aux = ws + count, *lam = aux + count + 1, *V = lam + count, *X = V + count * r;
   shamir_prod_kernel<<<dim3((unsigned)((count + 1 + SH_WAVES - 1) / SH_WAVES)), dim3(256), 0, s>>>(x, aux, count, n - 1, m);
@@ -724,9 +730,9 @@ __global__ __launch_bounds__(256) void shamir_evaluate_finish_kernel(ShamirEvalF
   f.values[s * f.value_stride + j] = v;
 }
 
-hipError_t launch_shamir_evaluate_weights(const u64* x, const u64* aux, u64* ws, size_t count, u32 t, size_t Tg, const Mod& m,
+hipError_t launch_shamir_evaluate_weights(const u64* x, const u64* aux, u64* ws, size_t count, u32 nk, size_t Tg, const Mod& m,
                                           hipStream_t s) {
-  const u32 n = (u32)count, tg = (u32)Tg, nk = (n - t - 1) / 2 + 1;
+  const u32 n = (u32)count, tg = (u32)Tg;
   const u64* xt = ws;
   u64 *scale = ws + Tg, *C = scale + Tg, *Xt = C + count * Tg, *Xd = Xt + (size_t)nk * Tg;
   u32* coin = (u32*)(Xd + (size_t)nk * Tg);
@@ -759,6 +765,248 @@ hipError_t launch_shamir_evaluate_finish(const ShamirEvalFinish& f, hipStream_t 
   const size_t blocks = ((size_t)f.ns * f.Tg + 255) / 256;
   shamir_evaluate_finish_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(f);
   return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------ reconstruction with erasures
+// erased[s][W] flags the shares of row s that are known to be bad: eps_s of them, each costing ONE of the r redundant columns.
+// The decode above with the erased shares read as 0 and a per-row erasure locator:
+//   Synd = (shares o !erased) x V                                                       (shamir_matmul_masked_kernel)
+//   Gamma_s(z) = prod_{c erased}(1 - x_c z);  T = Gamma_s Synd_s mod z^r, of which T_eps .. T_{r-1} are a sequence the error
+//   locator Lambda_s alone generates; Berlekamp-Massey over those r - eps_s words with the bound E_s = (r - eps_s) / 2;
+//   Psi_s = Gamma_s Lambda_s, reversed, of degree L_s = eps_s + deg Lambda_s <= r        (shamir_bm_erasures_kernel)
+//   M = Psi x X with X [r+1][count]                                                      (shamir_matmul_kernel)
+//   decodable iff row s of M has exactly L_s zeros (a root of Lambda_s on an erased point is a double root of Psi_s: fewer
+//   distinct zeros); the zeros that are not erased are the wrong columns; out[s] as above with Psi_s(0)  (finish kernel)
+// The evaluation of 8.13 runs unchanged with Psi_s in Lambda_s's place: an erased column carries M = 0 and is served by Psi_s'.
+// The mask, Gamma, T and Psi follow from the mask and the indices alone or are as public as the locators of 8.11.
+
+__global__ __launch_bounds__(256) void shamir_matmul_masked_kernel(ShamirMaskedMatmul b) {
+  const ShamirTile o = shamir_tile_product<true>(b.A, b.secret_stride, b.term_stride, b.W, b.ns, b.terms, b.T, b.m, b.erased, b.ewords);
+  if (o.live) b.out[(size_t)o.s * b.T + o.tm] = o.v;
+}
+
+// word w of a mask row of `count` columns, the padding bits of the last word cleared
+__device__ __forceinline__ u64 shamir_erased_word(const u64* erow, u32 w, u32 count) {
+  const u64 v = erow[w];
+  return (w + 1) * 64 > count ? v & (((u64)1 << (count % 64)) - 1) : v;      // count % 64 != 0 there
+}
+
+// One wave (one workgroup) per secret.  LDS: Gamma [eps + 1] | C [E_s + 1] | B [E_s + 1], at most r + 3 words.
+// Gamma grows by one factor per erased column, walked downwards in blocks of 64 like the update of shamir_bm_kernel.  T takes the
+// place of Synd_s[eps ..] in global memory, blocks downwards: T_n reads Synd_s[n - eps .. n], which no earlier block has written.
+// Then the recurrence of shamir_bm_kernel on T_eps .. T_{r-1}.  Every branch is wave-uniform (the mask words are read by all
+// lanes alike, the discrepancy is the same in every lane).
+// Out: psi[s][k] = Psi_{L_s - k} for k <= L_s, 0 up to r (all 0 for an undecodable row), Lout[s] = L_s or PVW_SHAMIR_NO_LOCATOR.
+__global__ __launch_bounds__(64) void shamir_bm_erasures_kernel(u64* synd, const u64* erased, const u64* x, u64* psi, u32* Lout, u32 count,
+                                                                u32 r, Mod m) {
+  extern __shared__ u64 bme_lds[];
+  const u32 lane = threadIdx.x;
+  const size_t s = blockIdx.x;
+  const u32 words = (count + 63) / 64;
+  const u64* erow = erased + s * words;
+  u64* S = synd + s * r;
+  u64* row = psi + s * ((size_t)r + 1);
+  u32 eps = 0;
+  for (u32 w = 0; w < words; ++w) eps += (u32)__popcll(shamir_erased_word(erow, w, count));
+  if (eps > r) {
+    for (u32 k = lane; k <= r; k += 64) row[k] = 0;
+    if (lane == 0) Lout[s] = PVW_SHAMIR_NO_LOCATOR;
+    return;
+  }
+  u64* G = bme_lds;
+  if (lane == 0) G[0] = 1;
+  __syncthreads();
+  u32 g = 0;                                                       // deg Gamma so far
+  for (u32 w = 0; w < words; ++w) {
+    u64 word = shamir_erased_word(erow, w, count);
+    while (word) {
+      const u64 xc = x[w * 64 + (u32)__builtin_ctzll(word)];
+      word &= word - 1;
+      for (u32 k = (g + 1) / 64 + 1; k-- > 0;) {                   // Gamma_i <- Gamma_i - x_c Gamma_{i-1}, i <= g + 1
+        const u32 i = k * 64 + lane;
+        const bool in = i <= g + 1;
+        const u64 cur = in && i <= g ? G[i] : 0;
+        const u64 prev = in && i >= 1 ? G[i - 1] : 0;
+        __syncthreads();
+        if (in) G[i] = submod(cur, mulmod(xc, prev, m), m.q);
+        __syncthreads();
+      }
+      ++g;
+    }
+  }
+  const u32 nT = r - eps, E = nT / 2;
+  if (eps)
+    for (u32 k = (nT + 63) / 64; k-- > 0;) {
+      const u32 idx = k * 64 + lane, n = eps + idx;
+      const bool live = idx < nT;
+      Acc a;
+      acc_zero(a);
+      for (u32 i = 0; i <= eps; ++i) acc_mac_dev(a, G[i], live ? S[n - i] : 0);
+      const u64 v = acc_reduce(a, m);
+      __syncthreads();
+      if (live) S[n] = v;
+      __syncthreads();
+    }
+  const u64* T = S + eps;
+  u64 *C = G + eps + 1, *B = C + E + 1;
+  for (u32 i = lane; i <= E; i += 64) C[i] = B[i] = i == 0;
+  __syncthreads();
+  u32 L = 0, mm = 1;
+  u64 bsc = 1;
+  bool ok = true;
+  for (u32 n = 0; n < nT; ++n) {
+    Acc a;
+    acc_zero(a);
+    for (u32 i = lane; i <= L; i += 64) acc_mac_dev(a, C[i], T[n - i]);      // L <= n
+    const u64 d = wave_addmod(acc_reduce(a, m), m.q);
+    if (d == 0) { ++mm; continue; }
+    const bool grow = 2 * L <= n;
+    const u32 Ln = grow ? n + 1 - L : L;
+    if (Ln > E) { ok = false; break; }
+    for (u32 k = Ln / 64 + 1; k-- > 0;) {
+      const u32 i = k * 64 + lane;
+      const bool in = i <= Ln;
+      const u64 c = in ? C[i] : 0;
+      const u64 bb = in && i >= mm ? B[i - mm] : 0;
+      __syncthreads();
+      if (in) {
+        C[i] = submod(mulmod(bsc, c, m), mulmod(d, bb, m), m.q);
+        if (grow) B[i] = c;
+      }
+      __syncthreads();
+    }
+    if (grow) { L = Ln; bsc = d; mm = 1; } else { ++mm; }
+  }
+  // Psi_j = sum_i Lambda_i Gamma_{j-i}, stored at k = L_s - j
+  const u32 Ls = eps + L;
+  for (u32 k = lane; k <= r; k += 64) {
+    u64 v = 0;
+    if (ok && k <= Ls) {
+      const u32 j = Ls - k;
+      Acc a;
+      acc_zero(a);
+      for (u32 i = j > eps ? j - eps : 0; i <= L && i <= j; ++i) acc_mac_dev(a, C[i], G[j - i]);
+      v = acc_reduce(a, m);
+    }
+    row[k] = v;
+  }
+  if (lane == 0) Lout[s] = ok ? Ls : PVW_SHAMIR_NO_LOCATOR;
+}
+
+// shamir_correct_finish_kernel for a row with erasures: the zeros of M's row must number exactly L_s, the erased ones among them;
+// the mask word is the ballot of the zeros without the erased word, nerr = L_s - eps_s, and out[s] divides by Psi_s(0) = f.Lam[s][0]
+// (rows f.E + 1 = r + 1 words apart).  No share at an erased position enters: M is 0 there.
+__global__ __launch_bounds__(64) void shamir_erasures_finish_kernel(ShamirFinish f, const u64* erased) {
+  const u32 lane = threadIdx.x;
+  const size_t s = blockIdx.x;
+  const Mod m = f.m;
+  const u32 count = f.count, words = (count + 63) / 64;
+  const u32 L = f.L[s];
+  const u64* Mrow = f.M + s * count;
+  const u64* erow = erased + s * words;
+  bool decodable = L != PVW_SHAMIR_NO_LOCATOR;
+  u32 eps = 0;
+  if (decodable) {
+    u32 nz = 0;
+    for (u32 c0 = 0; c0 < count; c0 += 64) {
+      const u32 c = c0 + lane;
+      nz += (u32)__popcll(__ballot(c < count && Mrow[c] == 0));
+      eps += (u32)__popcll(shamir_erased_word(erow, c0 / 64, count));
+    }
+    decodable = nz == L;
+  }
+  if (!decodable) {
+    if (f.mask)
+      for (u32 w = lane; w < words; w += 64) f.mask[s * words + w] = 0;
+    if (lane == 0) {
+      f.out[s] = 0;
+      if (f.nerr) f.nerr[s] = PVW_SHAMIR_NO_LOCATOR;
+    }
+    return;
+  }
+  Acc a;
+  acc_zero(a);
+  for (u32 c0 = 0; c0 < count; c0 += 64) {
+    const u32 c = c0 + lane;
+    const bool live = c < count;
+    const u64 mv = live ? Mrow[c] : 1;
+    const bool zero = live && mv == 0;
+    const u64 bal = __ballot(zero) & ~shamir_erased_word(erow, c0 / 64, count);
+    const bool wrong = (bal >> lane) & 1;
+    if (lane == 0 && f.mask) f.mask[s * words + c0 / 64] = bal;
+    if (wrong && f.col_err) atomicAdd(&f.col_err[c], 1u);
+    const u64 y = live && !zero ? reduce_word(f.shares[s * f.secret_stride + (size_t)c * f.point_stride], m) : 0;
+    acc_mac_dev(a, y, live ? mulmod(f.lam[c], mv, m) : 0);
+  }
+  const u64 v = wave_addmod(acc_reduce(a, m), m.q);
+  if (lane == 0) {
+    f.out[s] = mulmod(v, invmod_dev(f.Lam[s * ((size_t)f.E + 1)], m), m);
+    if (f.nerr) f.nerr[s] = L - eps;
+  }
+}
+
+// One wave per 64 words of one row: trip k packs the 64 columns of word w0 + k by ballot and lane k keeps it, so the wave's
+// store runs along the row.  The loads follow the caller's strides.  block = row * wb + block of words.
+__global__ __launch_bounds__(64) void shamir_erasure_mask_kernel(const u32* status, const u64* noise, u32 status_bits, u64 noise_bound,
+                                                                 u32 count, u32 wb, size_t secret_stride, size_t point_stride, u64* mask) {
+  const u32 lane = threadIdx.x;
+  const size_t s = blockIdx.x / wb;
+  const u32 words = (count + 63) / 64, w0 = (blockIdx.x % wb) * 64;
+  const u32 nw = words - w0 < 64 ? words - w0 : 64;
+  u64 mine = 0;
+  for (u32 k = 0; k < nw; ++k) {
+    const u32 c = (w0 + k) * 64 + lane;
+    bool e = false;
+    if (c < count) {
+      const size_t off = s * secret_stride + (size_t)c * point_stride;
+      if (status) e = (status[off] & status_bits) != 0;
+      if (noise) e = e || noise[off] > noise_bound;
+    }
+    const u64 bal = __ballot(e);
+    if (lane == k) mine = bal;
+  }
+  if (lane < nw) mask[s * words + w0 + lane] = mine;
+}
+
+hipError_t launch_shamir_matmul_masked(const ShamirMaskedMatmul& b, hipStream_t s) {
+  return launch_secret_groups(shamir_matmul_masked_kernel, b, [&](u32 s0) {
+    ShamirMaskedMatmul p = b;
+    p.A += (size_t)s0 * b.secret_stride;
+    p.out += (size_t)s0 * b.T;
+    p.erased += (size_t)s0 * b.ewords;
+    return p;
+  }, s);
+}
+
+// r + 1 <= PVW_SHAMIR_MAX_LOCATOR: Gamma, C and B of one wave take at most r + 3 words of LDS
+hipError_t launch_shamir_bm_erasures(u64* synd, const u64* erased, const u64* x, u64* psi, u32* L, u32 ns, u32 count, u32 r, const Mod& m,
+                                     hipStream_t s) {
+  if (ns == 0) return hipSuccess;
+  shamir_bm_erasures_kernel<<<dim3(ns), dim3(64), ((size_t)r + 3) * 8, s>>>(synd, erased, x, psi, L, count, r, m);
+  return hipGetLastError();
+}
+
+hipError_t launch_shamir_erasures_finish(const ShamirFinish& f, const u64* erased, u32 ns, hipStream_t s) {
+  if (ns == 0) return hipSuccess;
+  shamir_erasures_finish_kernel<<<dim3(ns), dim3(64), 0, s>>>(f, erased);
+  return hipGetLastError();
+}
+
+hipError_t launch_shamir_erasure_mask(const u32* status, const u64* noise, u32 status_bits, u64 noise_bound, u32 count, u32 ns,
+                                      size_t secret_stride, size_t point_stride, u64* mask, hipStream_t s) {
+  if (ns == 0 || count == 0) return hipSuccess;
+  const u32 words = (count + 63) / 64, wb = (words + 63) / 64;
+  const u32 per = 0x7FFFFFFFu / wb;                                // rows per launch: what the grid's x dimension holds
+  for (u32 s0 = 0; s0 < ns; s0 += per) {
+    const u32 rows = ns - s0 < per ? ns - s0 : per;
+    shamir_erasure_mask_kernel<<<dim3(rows * wb), dim3(64), 0, s>>>(status ? status + (size_t)s0 * secret_stride : nullptr,
+                                                                    noise ? noise + (size_t)s0 * secret_stride : nullptr, status_bits,
+                                                                    noise_bound, count, wb, secret_stride, point_stride,
+                                                                    mask + (size_t)s0 * words);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 // ------------------------------------------------------------------------ the weights of packed shares

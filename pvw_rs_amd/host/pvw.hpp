@@ -771,6 +771,60 @@ inline EvaluatedShares shamir_evaluate_corrected(const std::shared_ptr<PvwParame
   return r;
 }
 
+// ---- reconstruction with erasures ----
+// The calls above with `erased` [num_secrets][words] in the layout of CorrectedSecrets::err_mask (bit c % 64 of word c / 64 of row
+// s: share (s, c) is known to be bad).  An erased share costs one redundant column instead of two: a row decodes while
+// 2 errors + erasures <= indices.size() - degree - 1; the word at an erased position influences nothing and an erased column is never
+// reported as an error.  An empty `erased` is the call above.
+inline const uint64_t* erased_rows(const ShareMatrix& m, const std::vector<uint64_t>& erased) {
+  if (erased.empty()) return nullptr;
+  if (erased.size() != m.S * m.words) throw PvwError(15, "erased must hold ceil(count / 64) words per secret");
+  return erased.data();
+}
+inline CorrectedSecrets shamir_reconstruct_corrected(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& indices,
+                                                     const std::vector<uint64_t>& shares, uint32_t degree, uint64_t plain_modulus,
+                                                     const std::vector<uint64_t>& erased, bool host, bool party_major = false) {
+  const ShareMatrix m(indices, shares, party_major);
+  const uint64_t* er = erased_rows(m, erased);
+  CorrectedSecrets r = corrected_report(m);
+  check(host ? pvw_shamir_reconstruct_erasures_host(plain_modulus, degree, indices.data(), m.count, shares.data(), m.S, m.ss, m.ps, er,
+                                                    r.secrets.data(), r.nerr.data(), r.col_err.data(), r.err_mask.data())
+             : pvw_shamir_reconstruct_erasures(p->ctx, plain_modulus, degree, indices.data(), m.count, shares.data(), m.S, m.ss, m.ps, er,
+                                               r.secrets.data(), r.nerr.data(), r.col_err.data(), r.err_mask.data()));
+  return r;
+}
+// At an erased or wrong column the value is the share that party should hold: the repair of a party that lost its state.
+inline EvaluatedShares shamir_evaluate_corrected(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& indices,
+                                                 const std::vector<uint64_t>& shares, uint32_t degree, uint64_t plain_modulus,
+                                                 const std::vector<uint64_t>& targets, const std::vector<uint64_t>& erased, bool host,
+                                                 bool party_major = false) {
+  const ShareMatrix m(indices, shares, party_major);
+  const uint64_t* er = erased_rows(m, erased);
+  const size_t T = targets.size();
+  EvaluatedShares r{std::vector<uint64_t>(m.S * T), corrected_report(m)};
+  CorrectedSecrets& d = r.decode;
+  check(host ? pvw_shamir_evaluate_erasures_host(plain_modulus, degree, indices.data(), m.count, shares.data(), m.S, m.ss, m.ps, er,
+                                                 targets.data(), T, r.values.data(), d.secrets.data(), d.nerr.data(), d.col_err.data(),
+                                                 d.err_mask.data())
+             : pvw_shamir_evaluate_erasures(p->ctx, plain_modulus, degree, indices.data(), m.count, shares.data(), m.S, m.ss, m.ps, er,
+                                            targets.data(), T, r.values.data(), d.secrets.data(), d.nerr.data(), d.col_err.data(),
+                                            d.err_mask.data()));
+  return r;
+}
+// The mask of a decrypt report on the host (pvw_shamir_erasure_mask_host): status / noise [num_secrets][count], or with party_major
+// [count][num_secrets]; either may be empty, not both.  Share (s, c) is erased iff status & status_bits or noise > noise_bound.
+inline std::vector<uint64_t> shamir_erasure_mask(const std::vector<uint32_t>& status, const std::vector<uint64_t>& noise, size_t count,
+                                                 uint32_t status_bits, uint64_t noise_bound, bool party_major = false) {
+  const size_t cells = status.empty() ? noise.size() : status.size();
+  if (count == 0 || cells == 0 || cells % count || (!status.empty() && !noise.empty() && status.size() != noise.size()))
+    throw PvwError(15, "status and noise must hold one value per share");
+  const size_t S = cells / count;
+  std::vector<uint64_t> mask(S * ((count + 63) / 64));
+  check(pvw_shamir_erasure_mask_host(status.empty() ? nullptr : const_cast<uint32_t*>(status.data()) /* only read */, noise.empty() ? nullptr : noise.data(), status_bits,
+                                     noise_bound, count, S, party_major ? 1 : count, party_major ? S : 1, mask.data()));
+  return mask;
+}
+
 // ---- packed sharing ----
 // secrets [D][pack] row-major: dealer d's `pack` secrets sit at the points 0, -1, ..., -(pack-1) of one polynomial with `degree`
 // random coefficients (drawn as shamir_shares draws them, or coeffs [D][degree]); shares (D, n) row-major.  pack = 1 is

@@ -179,6 +179,15 @@ extern "C" {
     pub fn pvw_shamir_evaluate_corrected_device(ctx: *mut PvwCtx, plain_modulus: u64, degree: u32, indices: *const u64, count: usize, d_shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, targets: *const u64, num_targets: usize, d_values: *mut u64, d_out: *mut u64, d_nerr: *mut u32, d_col_err: *mut u32, d_err_mask: *mut u64, stream: *mut c_void) -> i32;
     pub fn pvw_shamir_evaluate_corrected(ctx: *mut PvwCtx, plain_modulus: u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, targets: *const u64, num_targets: usize, values: *mut u64, out: *mut u64, nerr: *mut u32, col_err: *mut u32, err_mask: *mut u64) -> i32;
     pub fn pvw_shamir_reconstruct_corrected(ctx: *mut PvwCtx, plain_modulus: u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, out: *mut u64, nerr: *mut u32, col_err: *mut u32, err_mask: *mut u64) -> i32;
+    // ---- reconstruction with erasures ----------------------------------------------
+    pub fn pvw_shamir_reconstruct_erasures_host(plain_modulus: u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, erased: *const u64, out: *mut u64, nerr: *mut u32, col_err: *mut u32, err_mask: *mut u64) -> i32;
+    pub fn pvw_shamir_reconstruct_erasures_device(ctx: *mut PvwCtx, plain_modulus: u64, degree: u32, indices: *const u64, count: usize, d_shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, d_erased: *const u64, d_out: *mut u64, d_nerr: *mut u32, d_col_err: *mut u32, d_err_mask: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_reconstruct_erasures(ctx: *mut PvwCtx, plain_modulus: u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, erased: *const u64, out: *mut u64, nerr: *mut u32, col_err: *mut u32, err_mask: *mut u64) -> i32;
+    pub fn pvw_shamir_evaluate_erasures_host(plain_modulus: u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, erased: *const u64, targets: *const u64, num_targets: usize, values: *mut u64, out: *mut u64, nerr: *mut u32, col_err: *mut u32, err_mask: *mut u64) -> i32;
+    pub fn pvw_shamir_evaluate_erasures_device(ctx: *mut PvwCtx, plain_modulus: u64, degree: u32, indices: *const u64, count: usize, d_shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, d_erased: *const u64, targets: *const u64, num_targets: usize, d_values: *mut u64, d_out: *mut u64, d_nerr: *mut u32, d_col_err: *mut u32, d_err_mask: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_evaluate_erasures(ctx: *mut PvwCtx, plain_modulus: u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, erased: *const u64, targets: *const u64, num_targets: usize, values: *mut u64, out: *mut u64, nerr: *mut u32, col_err: *mut u32, err_mask: *mut u64) -> i32;
+    pub fn pvw_shamir_erasure_mask_host(status: *mut u32, noise: *const u64, status_bits: u32, noise_bound: u64, count: usize, num_secrets: usize, secret_stride: usize, point_stride: usize, mask_out: *mut u64) -> i32;
+    pub fn pvw_shamir_erasure_mask_device(ctx: *mut PvwCtx, d_status: *mut u32, d_noise: *const u64, status_bits: u32, noise_bound: u64, count: usize, num_secrets: usize, secret_stride: usize, point_stride: usize, d_mask_out: *mut u64, stream: *mut c_void) -> i32;
     // ---- decrypt (src/crypto/decryption.rs:249-325) and gadget decode (:10-247) ---------------
     pub fn pvw_decrypt_batch(ctx: *mut PvwCtx, sk: *const i64, c1s: *const u64, c2col: *const u64, num_dealers: usize, in_repr: u32, out_u64: *mut u64, noisy_out: *mut u64) -> i32;
     pub fn pvw_decrypt_noisy_device(ctx: *mut PvwCtx, d_sk: *const i64, d_c1s: *const u64, d_c2col: *const u64, num_dealers: usize, in_repr: u32, d_noisy: *mut u64, stream: *mut c_void) -> i32;

@@ -666,6 +666,66 @@ pub fn shamir_evaluate_corrected(params: &Arc<PvwParameters>, indices: &[u64], s
     Ok((values, r))
 }
 
+/// The mask rows of a call with erasures: `[num_secrets][ceil(count / 64)]` words in the layout of `CorrectedSecrets::err_mask`.
+fn erased_rows(erased: &[u64], count: usize, num: usize) -> Result<*const u64> {
+    if erased.len() != num * ((count + 63) / 64) {
+        return Err(PvwError::InvalidParameters("erased must hold ceil(count / 64) words per secret".into()));
+    }
+    Ok(erased.as_ptr())
+}
+
+/// EXTENSION: `shamir_reconstruct_corrected` with the shares KNOWN to be bad flagged in `erased` (bit `c % 64` of
+/// word `c / 64` of row `s`; an earlier call's `err_mask`, or `shamir_erasure_mask`).  Each costs one redundant column instead of
+/// two: a row decodes while `2 * errors + erasures <= indices.len() - degree - 1`.  The word at an erased position influences nothing
+/// and an erased column is never reported as an error (`pvw_shamir_reconstruct_erasures`).
+pub fn shamir_reconstruct_erasures(params: &Arc<PvwParameters>, indices: &[u64], shares: &[u64], degree: u32, plain_modulus: u64,
+                                   erased: &[u64], party_major: bool) -> Result<CorrectedSecrets> {
+    let (count, num, ss, ps) = share_matrix(indices, shares, party_major)?;
+    let er = erased_rows(erased, count, num)?;
+    let mut r = CorrectedSecrets::zeroed(count, num);
+    check(unsafe {
+        sys::pvw_shamir_reconstruct_erasures(params.hip.raw(), plain_modulus, degree, indices.as_ptr(), count, shares.as_ptr(), num, ss, ps, er,
+                                             r.secrets.as_mut_ptr(), r.nerr.as_mut_ptr(), r.col_err.as_mut_ptr(), r.err_mask.as_mut_ptr())
+    })?;
+    Ok(r)
+}
+
+/// EXTENSION: `shamir_evaluate_corrected` with erasures (`pvw_shamir_evaluate_erasures`).  At an erased or wrong
+/// column the value is the share that party should hold: the repair of a party that lost its state.
+pub fn shamir_evaluate_erasures(params: &Arc<PvwParameters>, indices: &[u64], shares: &[u64], degree: u32, plain_modulus: u64,
+                                erased: &[u64], targets: &[u64], party_major: bool) -> Result<(Vec<u64>, CorrectedSecrets)> {
+    let (count, num, ss, ps) = share_matrix(indices, shares, party_major)?;
+    let er = erased_rows(erased, count, num)?;
+    let mut values = vec![0u64; num * targets.len()];
+    let mut r = CorrectedSecrets::zeroed(count, num);
+    check(unsafe {
+        sys::pvw_shamir_evaluate_erasures(params.hip.raw(), plain_modulus, degree, indices.as_ptr(), count, shares.as_ptr(), num, ss, ps, er,
+                                          targets.as_ptr(), targets.len(), values.as_mut_ptr(), r.secrets.as_mut_ptr(), r.nerr.as_mut_ptr(),
+                                          r.col_err.as_mut_ptr(), r.err_mask.as_mut_ptr())
+    })?;
+    Ok((values, r))
+}
+
+/// EXTENSION: the erasure mask of a decrypt report, on the host (`pvw_shamir_erasure_mask_host`).  `status` and
+/// `noise` are `[num_secrets][count]`, or with `party_major` `[count][num_secrets]` (the `[party][dealer]` report of the
+/// decrypt-all calls, every dealer a secret); either may be empty, not both.  Share `(s, c)` is erased iff
+/// `status & status_bits != 0` or `noise > noise_bound`.
+pub fn shamir_erasure_mask(status: &[u32], noise: &[u64], count: usize, status_bits: u32, noise_bound: u64, party_major: bool) -> Result<Vec<u64>> {
+    let cells = if status.is_empty() { noise.len() } else { status.len() };
+    if count == 0 || cells == 0 || cells % count != 0 || (!status.is_empty() && !noise.is_empty() && status.len() != noise.len()) {
+        return Err(PvwError::InvalidParameters("status and noise must hold one value per share".into()));
+    }
+    let num = cells / count;
+    let (ss, ps) = if party_major { (1, num) } else { (count, 1) };
+    let mut mask = vec![0u64; num * ((count + 63) / 64)];
+    check(unsafe {
+        sys::pvw_shamir_erasure_mask_host(if status.is_empty() { std::ptr::null_mut() } else { status.as_ptr() as *mut u32 },   // only read
+                                          if noise.is_empty() { std::ptr::null() } else { noise.as_ptr() }, status_bits, noise_bound, count, num, ss,
+                                          ps, mask.as_mut_ptr())
+    })?;
+    Ok(mask)
+}
+
 /// EXTENSION: the sum of the valid dealers' ciphertexts (`pvw_ct_sum`) -- a ciphertext of the sum of their
 /// shares under the same keys, folded without any key.  What examples/pvw_valid_dec.rs:150-209 reaches by decrypting every
 /// dealer's share and adding the results; the noise of the sum is the sum of the dealers' noises (`pvw_ctx_sum_capacity`).
