@@ -43,7 +43,7 @@
  *     once, under a lock).  Every result is the serial one bit for bit, pvw_last_error stays the calling thread's, and a
  *     pooled workspace that goes from one kind of call to another carries nothing over (pvw_selftest_secret_residue).
  *     OUTSIDE the promise, because they change the resident matrices or share a caller-owned object:
- *       pvw_load_crs* / pvw_load_pk* (the _wire forms too), pvw_keygen, pvw_pk_fill_uniform, pvw_crs_generate and
+ *       pvw_load_crs* / pvw_load_pk* (the _wire forms too), pvw_keygen[_seeded], pvw_pk_fill_uniform, pvw_crs_generate and
  *       pvw_ctx_set_roots next to any other call on the context (GlobalPublicKey's mutators take &mut self,
  *       public_key.rs:214-263: a change and a use never overlap);
  *       two threads drawing from one pvw_rnd_state (it is ordered by one stream at a time, see below);
@@ -234,6 +234,22 @@ PVW_API int32_t pvw_keygen(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, c
 /* SecretKey::random (secret_key.rs:45-63) for `count` parties from a seed (PVW_DOM_SK) */
 PVW_API int32_t pvw_sample_secret_keys(const pvw_ctx* ctx, const uint8_t seed[32], uint32_t party_lo,
                                uint32_t count, int64_t* sk_out /*[count][k][l]*/);
+/* Key generation from a seed: GlobalPublicKey::generate_all_party_keys (public_key.rs:376-401) over Party::new /
+ * SecretKey::random (public_key.rs:62-79, secret_key.rs:45-63), which draws the keys where it uses them.  b_p = s_p * A + e_p for
+ * the parties of [party_lo, party_hi) this context holds, with s_p[j] the CBD polynomial of stream (sk_seed, PVW_DOM_SK,
+ * p * k + j), p the GLOBAL party index -- the words pvw_sample_secret_keys(ctx, sk_seed, p, 1, .) returns -- drawn by the
+ * kernel that transforms them, and e_p drawn as pvw_keygen draws it with ek == NULL (seed, PVW_DOM_EKEY).  The rows of B-hat
+ * are bit-equal to pvw_sample_secret_keys + pvw_keygen(.., ek = NULL, seed); no secret key crosses the bus or exists on the
+ * host.  sk_seed == seed is allowed (the domains differ).  Checks, codes and bookkeeping are pvw_keygen's; party_hi * k must be
+ * below 2^32 (the stream index is 32 bits). */
+PVW_API int32_t pvw_keygen_seeded(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const uint8_t sk_seed[32],
+                                  const uint8_t seed[32]);
+/* SecretKey::random (secret_key.rs:45-63; Party::new, public_key.rs:62-79) for `count` parties straight into caller-owned
+ * device memory on the caller's stream (NULL: the context's): the words pvw_sample_secret_keys returns, with no staging, no
+ * download and no synchronisation -- what the _device forms of pvw_decrypt_all* / pvw_decrypt_batch* take as d_sk.  The caller
+ * clears the buffer.  (party_lo + count) * k must be below 2^32; count == 0 does nothing. */
+PVW_API int32_t pvw_sample_secret_keys_device(pvw_ctx* ctx, const uint8_t seed[32], uint32_t party_lo, uint32_t count,
+                                              int64_t* d_sk_out /*[count][k][l]*/, void* stream);
 
 /* ---- encrypt (src/crypto/encryption.rs:105-214) -----------------------------------
  * Checks mirror :109 (scalar count), :117 (key fullness), :124 (correctness gate).
@@ -337,6 +353,10 @@ PVW_API int32_t pvw_decrypt_batch_device(pvw_ctx* ctx, const int64_t* d_sk, cons
  * sk: k x l coefficients on the host.  The handle belongs to `ctx` and must be freed before it. */
 typedef struct pvw_sk pvw_sk;
 PVW_API int32_t pvw_sk_load(pvw_ctx* ctx, const int64_t* sk /*[k][l]*/, pvw_sk** out);
+/* The resident key pvw_sk_load(ctx, pvw_sample_secret_keys(sk_seed, party_index)) would hold, drawn on the device
+ * (SecretKey::random, secret_key.rs:45-63; Party::new, public_key.rs:62-79): no coefficient buffer exists at any time.  Same
+ * ownership and pvw_sk_free rules. */
+PVW_API int32_t pvw_sk_load_seeded(pvw_ctx* ctx, const uint8_t sk_seed[32], uint32_t party_index, pvw_sk** out);
 PVW_API int32_t pvw_sk_free(pvw_sk* key);
 PVW_API int32_t pvw_decrypt_batch_device_sk(pvw_ctx* ctx, const pvw_sk* key, const uint64_t* d_c1s,
                                             const uint64_t* d_c2col, size_t num_dealers, uint32_t in_repr,

@@ -70,6 +70,8 @@ _SIGNATURES = {
     "pvw_is_full": [_P, C.POINTER(C.c_int32)],
     "pvw_keygen": [_P, C.c_uint32, C.c_uint32, _P, _P, _P],
     "pvw_sample_secret_keys": [_P, _P, C.c_uint32, C.c_uint32, _P],
+    "pvw_keygen_seeded": [_P, C.c_uint32, C.c_uint32, _P, _P],
+    "pvw_sample_secret_keys_device": [_P, _P, C.c_uint32, C.c_uint32, _P, _P],
     "pvw_encrypt": [_P, _P, C.c_size_t, C.POINTER(pvw_randomness_t), _P, _P, C.c_uint32],
     "pvw_encrypt_device": [_P, _P, C.c_size_t, C.POINTER(pvw_randomness_t), _P, _P, C.c_uint32, _P],
     "pvw_encrypt_multi": [_P, _P, C.c_size_t, C.c_size_t, _P, _P, _P, C.c_uint32],
@@ -88,6 +90,7 @@ _SIGNATURES = {
     "pvw_decrypt_noisy_device": [_P, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P],
     "pvw_decrypt_batch_device": [_P, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P],
     "pvw_sk_load": [_P, _P, C.POINTER(C.c_void_p)],
+    "pvw_sk_load_seeded": [_P, _P, C.c_uint32, C.POINTER(C.c_void_p)],
     "pvw_sk_free": [_P],
     "pvw_decrypt_batch_device_sk": [_P, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P],
     "pvw_decrypt_all": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, C.c_uint32, _P],

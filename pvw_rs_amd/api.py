@@ -589,6 +589,16 @@ class GlobalPublicKey:
         """b_i = s_i*A + e_i with explicit key errors (public_key.rs:111-147)."""
         self._keygen(party_lo, party_lo + len(sk), sk, ek, None)
 
+    def generate_seeded(self, party_lo: int, party_hi: int, sk_seed: bytes, seed: bytes) -> None:
+        """pvw_keygen_seeded: generate_all_party_keys over Party.new (public_key.rs:376-401, :62-79) with the secret keys drawn
+        on the device from `sk_seed` by the kernel that transforms them -- party p's key is SecretKey.random(params, sk_seed, p) --
+        and the key errors from `seed`; bit-equal to Party.new + generate_all_party_keys, without the keys on the host."""
+        sk_sd, sd = _seed(sk_seed), _seed(seed)
+        try:
+            self.params._call("pvw_keygen_seeded", int(party_lo), int(party_hi), _ptr(sk_sd), _ptr(sd))
+        finally:
+            sk_sd.fill(0)
+
     def _keygen(self, lo, hi, sk, ek, seed):
         p = self.params
         sk = _i64(sk)
@@ -1686,6 +1696,21 @@ class DeviceSecretKey:
         self.params._call("pvw_sk_load", _ptr(sk), C.byref(h))
         self._h = h
 
+    @staticmethod
+    def from_seed(params: "PvwParameters", seed: bytes, party_index: int) -> "DeviceSecretKey":
+        """pvw_sk_load_seeded: the resident key of SecretKey.random(params, seed, party_index), drawn on the device -- the
+        coefficients exist neither on the host nor in a device buffer."""
+        key = DeviceSecretKey.__new__(DeviceSecretKey)
+        key.params, key._h = params, None
+        h = C.c_void_p()
+        sd = _seed(seed)
+        try:
+            params._call("pvw_sk_load_seeded", _ptr(sd), int(party_index), C.byref(h))
+        finally:
+            sd.fill(0)
+        key._h = h
+        return key
+
     def free(self) -> None:
         h, self._h = getattr(self, "_h", None), None
         if h:
@@ -1755,6 +1780,24 @@ def _stream_ptr(stream):
     if stream is None:
         return None
     return C.c_void_p(int(getattr(stream, "cuda_stream", stream)) or None)
+
+
+def sample_secret_keys_device(params: "PvwParameters", seed: bytes, party_lo: int, count: int, out=None, stream=None):
+    """pvw_sample_secret_keys_device: the keys of parties [party_lo, party_lo + count) -- SecretKey.random(params, seed, p) each --
+    drawn straight into a torch int64 tensor [count][k][l] on the device (`out`, or a new one), asynchronously on `stream`:
+    what the d_sk argument of the *_device decrypt calls takes.  The tensor is key material; the caller clears it."""
+    import torch
+    if out is None:
+        dev = torch.device("cuda", params.device) if getattr(params, "device", -1) >= 0 else torch.device("cuda")
+        out = torch.empty((int(count), params.k, params.l), dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != int(count) * params.k * params.l:
+        raise PvwError(1, f"out must be a contiguous int64 tensor of {int(count) * params.k * params.l} elements")
+    sd = _seed(seed)
+    try:
+        params._call("pvw_sample_secret_keys_device", _ptr(sd), int(party_lo), int(count), _dptr(out), _stream_ptr(stream))
+    finally:
+        sd.fill(0)
+    return out
 
 
 class DeviceRandomness:

@@ -1703,6 +1703,27 @@ int32_t pvw_sample_secret_keys(const pvw_ctx* cc, const uint8_t seed[32], uint32
   // party p, polynomial j uses stream index p*k + j
   return pvw_sample_cbd(c, seed, PVW_DOM_SK, party_lo * c->k, (size_t)count * c->k, c->variance, sk_out);
 }
+// a drawn key's stream index p * k + j is 32 bits wide
+static int32_t check_sk_index(const pvw_ctx* c, uint64_t party_end) {
+  if (party_end * c->k >= ((uint64_t)1 << 32)) return fail(PVW_ERR_INVALID_PARAMETERS, "party_hi * k must be below 2^32 for seeded secret keys");
+  return PVW_OK;
+}
+// the same words straight into the caller's device buffer on the caller's stream: one launch, no staging, no download, no
+// synchronisation.  The buffer is the caller's to clear.
+int32_t pvw_sample_secret_keys_device(pvw_ctx* c, const uint8_t seed[32], uint32_t party_lo, uint32_t count, int64_t* d_sk_out,
+                                      void* stream) {
+  if (!c || !seed || (!d_sk_out && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  SampleJob j{}, z{};
+  PVW_TRY(cbd_job(c->variance, j));
+  PVW_TRY(check_sk_index(c, (uint64_t)party_lo + count));
+  if (count == 0) return PVW_OK;
+  PVW_TRY(ensure_device(c));
+  j.domain = DOM_SK; j.index0 = party_lo * c->k; j.count = count * c->k; j.out_poly0 = 0;
+  hipStream_t s = call_stream(c, stream);
+  ProfScope ps(c, "sample", s);
+  PVW_HIP(launch_sample(d_sk_out, make_key(seed), c->l, j, z, z, s));
+  return PVW_OK;
+}
 
 // ------------------------------------------------------------------------ ring primitives on host buffers
 static int32_t ntt_host(pvw_ctx* c, uint64_t* polys, size_t count, bool inverse) {
@@ -4434,6 +4455,36 @@ int32_t pvw_sk_load(pvw_ctx* c, const int64_t* sk, pvw_sk** out) {
   *out = key;
   return PVW_OK;
 }
+// the resident key of party_index drawn from its seed (SecretKey::random, secret_key.rs:45-63): one sampled prologue family
+// straight into the key's NTT form -- no coefficient buffer exists at any time
+int32_t pvw_sk_load_seeded(pvw_ctx* c, const uint8_t sk_seed[32], uint32_t party_index, pvw_sk** out) {
+  if (!c || !sk_seed || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  *out = nullptr;
+  PrologueBatch pb{};
+  PrologueJob& js = pb.job[0];
+  PVW_TRY(cbd_job(c->variance, js.sj));
+  PVW_TRY(check_sk_index(c, (uint64_t)party_index + 1));
+  PVW_TRY(ensure_device(c));
+  const size_t k = c->k, l = c->l, P = c->poly();
+  pvw_sk* key = new pvw_sk{c, nullptr, k * P * 8};
+  pb.key[0] = make_key(sk_seed);
+  js.sj.domain = DOM_SK; js.sj.index0 = party_index * c->k; js.sj.count = c->k;
+  js.stride_poly = P; js.stride_limb = l;
+  pb.njobs = 1;
+  hipError_t e = hipMalloc((void**)&key->shat, key->bytes);
+  js.out = key->shat;
+  if (e == hipSuccess) e = launch_prologue(pb, c->dt, c->L, c->l, c->stream);
+  hipError_t e3 = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = e3;
+  if (e != hipSuccess) {
+    if (key->shat) { hipMemset(key->shat, 0, key->bytes); hipFree(key->shat); }
+    delete key;
+    (void)hipGetLastError();
+    return fail(PVW_ERR_INTERNAL, "loading the secret key failed");
+  }
+  *out = key;
+  return PVW_OK;
+}
 int32_t pvw_sk_free(pvw_sk* key) {
   if (!key) return PVW_OK;
   int32_t rc = PVW_OK;
@@ -4601,7 +4652,7 @@ static int32_t decrypt_all_gemm(pvw_ctx* c, Workspace* w, hipStream_t s, const A
     {
       ProfScope ps(c, "prep", s);
       if (a.direct) {
-        PVW_HIP(launch_shat_mftile(skp, d_xm, pc, k, L, l, c->dt, s));                        // secret_key.rs:98-112
+        PVW_HIP(launch_shat_mftile(skp, nullptr, d_xm, pc, k, L, l, c->dt, s));                        // secret_key.rs:98-112
       } else {
         PVW_HIP(launch_prep(skp, nullptr, d_rows, P, l, pc * k, true, c->dt, L, l, s));
         PVW_HIP(hipMemsetAsync(d_xm, 0, xm_words(pc, k, L, l) * 8, s));
@@ -5435,6 +5486,30 @@ int32_t pvw_ctx_lincomb_fits(const pvw_ctx* c, const int64_t* weights, size_t D,
 }
 
 // ------------------------------------------------------------------------ key generation
+// Where key generation gets the parties' secret keys: host coefficients [hi - lo][k][l] (pvw_keygen), or the seed they are
+// drawn from on the device, by the kernel that transforms them (pvw_keygen_seeded; SecretKey::random, secret_key.rs:45-63:
+// polynomial j of party p is the CBD stream (seed, DOM_SK, p * k + j)).  Exactly one is set.
+struct KeySource {
+  const int64_t* sk = nullptr;
+  const uint8_t* sk_seed = nullptr;
+  bool seeded() const { return sk_seed != nullptr; }
+  // the `js` job of a key-generation prologue for the parties from p0 on: the uploaded coefficients at `coeffs`, or the
+  // sampled family with its key beside the error key in pb.key[]
+  int32_t job(const pvw_ctx* c, PrologueBatch& pb, PrologueJob& js, const i64* coeffs, u32 p0) const {
+    js.sj.count = c->k;
+    if (!seeded()) {
+      js.explicit_coeffs = coeffs;
+      js.rep_coeffs = (size_t)c->k * c->l;
+      return PVW_OK;
+    }
+    PVW_TRY(cbd_job(c->variance, js.sj));
+    js.sj.domain = DOM_SK; js.sj.index0 = p0 * c->k; js.rep_index0 = c->k;
+    js.key_idx = 1;
+    pb.key[1] = make_key(sk_seed);
+    return PVW_OK;
+  }
+};
+
 // b_i = s_i * A + e_i: for every party the k-term inner products over A's COLUMNS, i.e. one
 // mac_rows pass over the transposed CRS per party (public_key.rs:111-147, crs.rs:138-171).
 // The CRS is transposed once per call into a temporary tiled matrix; groups of 4 parties then
@@ -5444,7 +5519,7 @@ int32_t pvw_ctx_lincomb_fits(const pvw_ctx* c, const int64_t* weights, size_t D,
 // GEMM rows = parties (their s-hat rows are the raw streamed operand, MFMA-tiled per chunk), GEMM vectors = the k
 // columns of A-hat (digit tiles built ONCE per call, straight from the CRS in API layout: no transpose), the
 // finish pass adds e_p and writes into the tiled B-hat.  Chunks of up to 1024 parties.
-static int32_t keygen_gemm_swapped(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 lo, const int64_t* sk, const int64_t* ek,
+static int32_t keygen_gemm_swapped(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 lo, const KeySource& ks, const int64_t* ek,
                                    const uint8_t* seed) {
   const u32 k = c->k, l = c->l, L = c->L;
   const size_t P = c->poly();
@@ -5455,7 +5530,8 @@ static int32_t keygen_gemm_swapped(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 l
   Scratch sc;
   const size_t r_api = sc.add((size_t)k * k * P * 8);
   const size_t r_yd = sc.add(yd_bytes(16 * nb, k, L, l)), r_sy = sc.add(sy_bytes(16 * nb, L, l));   // whole batches: the last one is read in full
-  const size_t r_small0 = sc.add((size_t)2 * chunk * k * l * 8), r_small1 = sc.add((size_t)2 * chunk * k * l * 8);   // sk | ek of one chunk, double buffered
+  const size_t small_bytes = ks.seeded() ? 0 : (size_t)2 * chunk * k * l * 8;   // seeded: nothing is uploaded
+  const size_t r_small0 = sc.add(small_bytes), r_small1 = sc.add(small_bytes);   // sk | ek of one chunk, double buffered
   const size_t r_srow = sc.add(direct ? 0 : (size_t)chunk * k * P * 8);   // l = 64 only: s-hat rows | e rows, API layout [p][j or col][P]
   const size_t r_erow = sc.add(direct ? 0 : (size_t)chunk * k * P * 8);
   const size_t r_xm = sc.add(xm_words(chunk, k, L, l) * 8);
@@ -5471,7 +5547,15 @@ static int32_t keygen_gemm_swapped(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 l
   sc.secret(w, r_small0, r_tmp);
   // the secret keys of chunk i+1 are uploaded on a helper stream while chunk i computes
   const u32 nchunks = (b - a + chunk - 1) / chunk;
-  PVW_TRY(ws_aux(w, 2 * (size_t)nchunks + 2));
+  const i64* sk = ks.sk;
+  ShatDraw draw{};
+  if (ks.seeded()) {                                                  // drawn keys: no buffers, helper stream or events
+    SampleJob sj{};
+    PVW_TRY(cbd_job(c->variance, sj));
+    draw.key = make_key(ks.sk_seed); draw.cbd_half = sj.cbd_half; draw.cbd_v = sj.cbd_v;
+  } else {
+    PVW_TRY(ws_aux(w, 2 * (size_t)nchunks + 2));
+  }
   auto upload = [&](u32 ci, hipStream_t st) -> int32_t {
     const u32 q0 = a + ci * chunk, cn = (b - q0) < chunk ? (b - q0) : chunk;
     const size_t wd = (size_t)cn * k * l;
@@ -5480,7 +5564,7 @@ static int32_t keygen_gemm_swapped(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 l
     if (ek) PVW_HIP(hipMemcpyAsync(dst + (size_t)chunk * k * l, ek + (size_t)(q0 - lo) * k * l, wd * 8, hipMemcpyHostToDevice, st));
     return PVW_OK;
   };
-  PVW_TRY(upload(0, s));
+  if (!ks.seeded()) PVW_TRY(upload(0, s));
   // A-hat -> API layout [j][col][limb][slot]; vector `col` is its column: element j at col * P + limb * l + j * (k * P)
   PVW_HIP(launch_untile(c->dA, d_api, k, 0, k, L, l, false, c->dt, s));
   PVW_HIP(launch_vec_digits(d_api, P, d_yd, d_sy, k, k, L, l, c->dt, s, l, (size_t)k * P));
@@ -5488,7 +5572,7 @@ static int32_t keygen_gemm_swapped(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 l
     const u32 p0 = a + ci * chunk;
     const u32 cnt = (b - p0) < chunk ? (b - p0) : chunk;
     i64* d_small = d_small2[ci & 1];
-    if (ci > 0) PVW_HIP(hipStreamWaitEvent(s, w->events[2 * ci], 0));          // this chunk's keys have arrived
+    if (ci > 0 && !ks.seeded()) PVW_HIP(hipStreamWaitEvent(s, w->events[2 * ci], 0));          // this chunk's keys have arrived
     ProfScope ps(c, "keygen", s);
     // l <= 32: s-hat_p (secret_key.rs:98-112) goes straight from the uploaded coefficients into the MFMA-tiled raw
     // operand and the key errors e_p (public_key.rs:128-132) are drawn (or read) by the finish pass of the GEMM --
@@ -5499,7 +5583,8 @@ static int32_t keygen_gemm_swapped(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 l
     ga.tiled_swap = 1;
     ga.row_stride = (size_t)k * P;
     if (direct) {
-      PVW_HIP(launch_shat_mftile(d_small, d_xm, cnt, k, L, l, c->dt, s));
+      draw.party0 = p0;
+      PVW_HIP(launch_shat_mftile(ks.seeded() ? nullptr : d_small, ks.seeded() ? &draw : nullptr, d_xm, cnt, k, L, l, c->dt, s));
       GemmErrSource es{};
       if (ek) { es.explicit_coeffs = d_small + (size_t)chunk * k * l; es.coef_row = k; es.coef_v = 1; }
       else es.key[0] = make_key(seed);
@@ -5513,7 +5598,7 @@ static int32_t keygen_gemm_swapped(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 l
       if (seed) pb.key[0] = make_key(seed);
       PrologueJob& js = pb.job[0];
       PrologueJob& je = pb.job[1];
-      js.sj.count = k; js.explicit_coeffs = d_small; js.rep_coeffs = (size_t)k * l;
+      PVW_TRY(ks.job(c, pb, js, d_small, p0));
       js.out = d_srow; js.stride_poly = P; js.stride_limb = l; js.rep_out = (size_t)k * P;
       je.sj.kind = SAMPLE_UNIFORM; je.sj.domain = DOM_EKEY; je.sj.index0 = p0 * k; je.sj.count = k; je.sj.bound = c->b1;
       je.rep_index0 = k;
@@ -5527,6 +5612,7 @@ static int32_t keygen_gemm_swapped(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 l
       // out / addend element (v = col, row = p) at p * k * P + col * P
       PVW_HIP(launch_gemm_digits(ga, gb, d_yd, d_sy, c->dt, k, L, l, k, P, 0, s));
     }
+    if (ks.seeded()) continue;
     PVW_HIP(hipEventRecord(w->events[2 * ci + 1], s));                         // this chunk's key buffer is free again
     if (ci + 1 < nchunks) {
       // issued after this chunk's launches so that the host-side staging of a pageable copy overlaps the GPU's work;
@@ -5542,7 +5628,7 @@ static int32_t keygen_gemm_swapped(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 l
 // fewer than 64 parties, or PVW_KEYGEN_SWAP=0: the CRS transposed once per call and streamed, the parties' s-hat as the
 // vectors -- 16 per pass on the matrix cores (everything around the GEMM batched over super-groups of up to 128 parties),
 // 4 per pass on the VALU
-static int32_t keygen_transposed(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 lo, const int64_t* sk, const int64_t* ek,
+static int32_t keygen_transposed(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 lo, const KeySource& ks, const int64_t* ek,
                                  const uint8_t* seed, bool use_gemm) {
   const u32 k = c->k, l = c->l, L = c->L;
   const size_t P = c->poly();
@@ -5565,7 +5651,7 @@ static int32_t keygen_transposed(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 lo,
   Scratch sc;
   const size_t r_api = sc.add((size_t)k * k * P * 8), r_apiT = sc.add((size_t)k * k * P * 8);
   const size_t r_tt = sc.add((use_gemm ? xm_words(k, k, L, l) : c->tiled_words(k)) * 8);
-  const size_t r_small = sc.add((size_t)2 * chunk * k * l * 8), r_row = sc.add((size_t)sg * k * P * 8);
+  const size_t r_small = sc.add(ks.seeded() ? 0 : (size_t)2 * chunk * k * l * 8), r_row = sc.add((size_t)sg * k * P * 8);   // seeded: nothing is uploaded
   const size_t r_tmp = sc.add(use_gemm ? (size_t)(sg / 16) * gemm_tmp_words(k, L, l) * 8 : 0);
   const size_t r_vh = sc.add(use_gemm ? (size_t)sg * k * P * 8 : 0);
   const size_t r_yd = sc.add(use_gemm ? yd_bytes(sg, k, L, l) : 0), r_sy = sc.add(use_gemm ? sy_bytes(sg, L, l) : 0);
@@ -5592,7 +5678,8 @@ static int32_t keygen_transposed(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 lo,
   for (u32 p0 = a; p0 < b; p0 += sg) {
     const u32 nv = (b - p0) < sg ? (b - p0) : sg;
     const u32 in_chunk = (p0 - a) % chunk;                       // position inside the uploaded chunk
-    if (in_chunk == 0) {
+    if (in_chunk == 0 && !ks.seeded()) {
+      const i64* sk = ks.sk;
       const u32 cn = (b - p0) < chunk ? (b - p0) : chunk;
       const size_t words = (size_t)cn * k * l;
       PVW_HIP(hipMemcpyAsync(d_small, sk + (size_t)(p0 - lo) * k * l, words * 8, hipMemcpyHostToDevice, s));
@@ -5607,9 +5694,9 @@ static int32_t keygen_transposed(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 lo,
     PrologueJob& js = pb.job[0];
     PrologueJob& je = pb.job[1];
     u64* vh = use_gemm ? d_vh : w->rhat;
-    js.sj.count = k; js.explicit_coeffs = d_small + (size_t)in_chunk * k * l;
+    PVW_TRY(ks.job(c, pb, js, d_small + (size_t)in_chunk * k * l, p0));
     js.out = vh; js.stride_poly = l; js.stride_limb = (size_t)k * l;
-    js.rep_coeffs = (size_t)k * l; js.rep_out = (size_t)k * P;
+    js.rep_out = (size_t)k * P;
     je.sj.kind = SAMPLE_UNIFORM; je.sj.domain = DOM_EKEY; je.sj.index0 = p0 * k; je.sj.count = k; je.sj.bound = c->b1;
     je.rep_index0 = k;
     if (ek) { je.explicit_coeffs = d_small + (size_t)(chunk + in_chunk) * k * l; je.rep_coeffs = (size_t)k * l; }
@@ -5636,10 +5723,10 @@ static int32_t keygen_transposed(pvw_ctx* c, Workspace* w, u32 a, u32 b, u32 lo,
   return PVW_OK;
 }
 
-int32_t pvw_keygen(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const int64_t* ek, const uint8_t seed[32]) {
-  if (!c || !sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  if (!ek && !seed) return fail(PVW_ERR_INVALID_PARAMETERS, "either explicit key errors or a seed is required");
+// pvw_keygen and pvw_keygen_seeded behind their own NULL checks: one sequence of checks, one bookkeeping
+static int32_t keygen_call(pvw_ctx* c, uint32_t lo, uint32_t hi, const KeySource& ks, const int64_t* ek, const uint8_t* seed) {
   PVW_TRY(check_party_range(c, lo, hi));
+  if (ks.seeded()) PVW_TRY(check_sk_index(c, hi));
   PVW_TRY(ensure_device(c));
   matrix_changed(c, false);
   if (!c->crs_loaded) return fail(PVW_ERR_CRS, "CRS not loaded");
@@ -5653,11 +5740,26 @@ int32_t pvw_keygen(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, cons
   // form with the transposed CRS as the streamed operand and the secret keys digitised per super-group)
   const int swap_roles = (int)PVW_ENV_INT("PVW_KEYGEN_SWAP", 1);   // tuning build, per call: the tests walk both
   const int32_t rc = host_call(c, [&](Workspace* w) {
-    return use_gemm && swap_roles && (b - a) >= 64 ? keygen_gemm_swapped(c, w, a, b, lo, sk, ek, seed)
-                                                   : keygen_transposed(c, w, a, b, lo, sk, ek, seed, use_gemm);
+    return use_gemm && swap_roles && (b - a) >= 64 ? keygen_gemm_swapped(c, w, a, b, lo, ks, ek, seed)
+                                                   : keygen_transposed(c, w, a, b, lo, ks, ek, seed, use_gemm);
   });
   if (rc == PVW_OK && hi > c->num_keys) c->num_keys = hi;
   return rc;
+}
+int32_t pvw_keygen(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const int64_t* ek, const uint8_t seed[32]) {
+  if (!c || !sk) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (!ek && !seed) return fail(PVW_ERR_INVALID_PARAMETERS, "either explicit key errors or a seed is required");
+  KeySource ks;
+  ks.sk = sk;
+  return keygen_call(c, lo, hi, ks, ek, seed);
+}
+// GlobalPublicKey::generate_all_party_keys over Party::new / SecretKey::random (public_key.rs:376-401, :62-79,
+// secret_key.rs:45-63): the keys are drawn where they are used and never exist on the host
+int32_t pvw_keygen_seeded(pvw_ctx* c, uint32_t lo, uint32_t hi, const uint8_t sk_seed[32], const uint8_t seed[32]) {
+  if (!c || !sk_seed || !seed) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  KeySource ks;
+  ks.sk_seed = sk_seed;
+  return keygen_call(c, lo, hi, ks, nullptr, seed);
 }
 
 // ------------------------------------------------------------------------ wire format, version 1

@@ -116,8 +116,14 @@ __global__ __launch_bounds__(256) void mftile_rows_kernel(const u64* __restrict_
 // keeps ONE polynomial's coefficients in registers and per limb transforms them into an LDS image of the l x JBG
 // tiles (two images in turn: one barrier per limb), which leave as whole 1-KiB tiles.  Padding rows / j are written
 // as the offset-zero byte pattern, as mftile_rows_kernel does.
-template <int ELL>
-__global__ __launch_bounds__(256) void shat_mftile_kernel(const i64* __restrict__ coeffs, u64* __restrict__ XM, u32 rows, u32 k, u32 L, DevTables t) {
+// DRAWN: the coefficients are not loaded but drawn where they are used (SecretKey::random, secret_key.rs:45-63): the
+// polynomial of (row, j) is the CBD stream (key, DOM_SK, (party0 + row) * k + j), the words pvw_sample_secret_keys returns for
+// that party -- the key never exists outside the registers of this kernel.  Blocks that differ only in blockIdx.z draw the
+// same polynomial again (one ChaCha8 block per 8 coefficients at variance 0.5).
+template <bool DRAWN> struct ShatSource { typedef const i64* __restrict__ type; };
+template <> struct ShatSource<true> { typedef ShatDraw type; };
+template <int ELL, bool DRAWN>
+__global__ __launch_bounds__(256) void shat_mftile_kernel(typename ShatSource<DRAWN>::type src_, u64* __restrict__ XM, u32 rows, u32 k, u32 L, DevTables t) {
   constexpr int JBG = 2, NJ = 4 * JBG;                          // 32 rows x 8 j = 256 polynomials: one per thread
   constexpr int PLANE = JBG * 128 + 2;                          // u64 per slot plane of the tile image (+2: bank spread)
   __shared__ u64 lt[2][ELL * PLANE];
@@ -125,17 +131,28 @@ __global__ __launch_bounds__(256) void shat_mftile_kernel(const i64* __restrict_
   const u32 row = threadIdx.x & 31, jj = threadIdx.x >> 5;       // consecutive lanes: consecutive rows of one j
   const u32 grow = rt * 32 + row, gj = jg * NJ + jj;
   i64 c[ELL];
+#pragma unroll
+  for (int sl = 0; sl < ELL; ++sl) c[sl] = 0;                    // padding rows / j stay zero
   if (grow < rows && gj < k) {
-    const v2u64* src = reinterpret_cast<const v2u64*>(coeffs + ((size_t)grow * k + gj) * ELL);
+    if constexpr (DRAWN) {
+      ChaChaRng g;
+      g.init(src_.key, DOM_SK, (src_.party0 + grow) * k + gj);
+      // sample_cbd_poly indexes its output at run time in the general-variance branch: every emit is a chain of selects over
+      // the registers, so c[] never becomes a scratch array
+      auto emit = [&c](u32 s, i64 v) {
 #pragma unroll
-    for (int sl = 0; sl < ELL; sl += 2) {
-      const v2u64 v = src[sl / 2];
-      c[sl] = (i64)v.x;
-      c[sl + 1] = (i64)v.y;
+        for (int sl = 0; sl < ELL; ++sl) c[sl] = (u32)sl == s ? v : c[sl];
+      };
+      sample_cbd_poly(g, ELL, src_.cbd_half != 0, src_.cbd_v, emit);
+    } else {
+      const v2u64* src = reinterpret_cast<const v2u64*>(src_ + ((size_t)grow * k + gj) * ELL);
+#pragma unroll
+      for (int sl = 0; sl < ELL; sl += 2) {
+        const v2u64 v = src[sl / 2];
+        c[sl] = (i64)v.x;
+        c[sl + 1] = (i64)v.y;
+      }
     }
-  } else {
-#pragma unroll
-    for (int sl = 0; sl < ELL; ++sl) c[sl] = 0;
   }
   const u32 w = ((jj >> 2) * 64 + ((jj >> 1) & 1) * 32 + row) * 2 + (jj & 1);
   const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1059,7 +1076,10 @@ hipError_t launch_mftile(const u64* src, bool src_is_tiled, u64* XM, u32 rows, u
   return hipGetLastError();
 }
 
-hipError_t launch_shat_mftile(const i64* coeffs, u64* XM, u32 rows, u32 k, u32 L, u32 ell, const DevTables& t, hipStream_t s) {
+// exactly one source: the coefficients [rows][k][l], or the draw (key, CBD parameters, first party) they are sampled from
+hipError_t launch_shat_mftile(const i64* coeffs, const ShatDraw* draw, u64* XM, u32 rows, u32 k, u32 L, u32 ell, const DevTables& t,
+                              hipStream_t s) {
+  if ((coeffs != nullptr) == (draw != nullptr)) return hipErrorInvalidValue;
   if (rows == 0) return hipSuccess;
   if (ell > 32) return hipErrorInvalidValue;                 // callers keep the prologue + launch_mftile pair for l = 64
   const u32 jbg = 2;
@@ -1068,11 +1088,16 @@ hipError_t launch_shat_mftile(const i64* coeffs, u64* XM, u32 rows, u32 k, u32 L
   u32 ls = 1;                                                 // limb interleave: enough blocks for several rounds on the chip
   while (ls < L && (size_t)JG * RT * ls < 4096) ls *= 2;
   if (ls > L) ls = L;
+  const dim3 grid(JG, RT, ls);
+#define PVW_SHAT(E)                                                                                        \
+  if (draw) shat_mftile_kernel<E, true><<<grid, dim3(256), 0, s>>>(*draw, XM, rows, k, L, t);             \
+  else shat_mftile_kernel<E, false><<<grid, dim3(256), 0, s>>>(coeffs, XM, rows, k, L, t);
   switch (ell) {
-    case 8: shat_mftile_kernel<8><<<dim3(JG, RT, ls), dim3(256), 0, s>>>(coeffs, XM, rows, k, L, t); break;
-    case 16: shat_mftile_kernel<16><<<dim3(JG, RT, ls), dim3(256), 0, s>>>(coeffs, XM, rows, k, L, t); break;
-    default: shat_mftile_kernel<32><<<dim3(JG, RT, ls), dim3(256), 0, s>>>(coeffs, XM, rows, k, L, t); break;
+    case 8: PVW_SHAT(8) break;
+    case 16: PVW_SHAT(16) break;
+    default: PVW_SHAT(32) break;
   }
+#undef PVW_SHAT
   return hipGetLastError();
 }
 

@@ -424,7 +424,15 @@ inline size_t sy_bytes(u32 nv, u32 L, u32 ell) { return (size_t)((nv + 3) / 4) *
 hipError_t launch_mftile(const u64* src, bool src_is_tiled, u64* XM, u32 rows, u32 k, u32 L, u32 ell, hipStream_t s, u32 bytes = 8,
                          const Mod* mods = nullptr);
 // small coefficients [row][j][l] -> NTT -> MFMA-tiled raw operand in one pass (l <= 32); padding included
-hipError_t launch_shat_mftile(const i64* coeffs, u64* XM, u32 rows, u32 k, u32 L, u32 ell, const DevTables& t, hipStream_t s);
+// Exactly one source is set: `coeffs`, or `draw` -- row r, polynomial j is then the CBD stream (key, DOM_SK, (party0 + r) * k + j)
+// drawn by the thread that transforms it (cbd_half / cbd_v as SampleJob's)
+struct ShatDraw {
+  ChaChaKey key;
+  u32 cbd_half, cbd_v;
+  u32 party0;     // global index of row 0's party
+};
+hipError_t launch_shat_mftile(const i64* coeffs, const ShatDraw* draw, u64* XM, u32 rows, u32 k, u32 L, u32 ell, const DevTables& t,
+                              hipStream_t s);
 // element j of vector v at (limb, slot): vhat[v * vstride + limb * lstride + j * jstride + slot];
 // lstride = jstride = 0 selects the r-hat layout [limb][j][slot] (lstride = k * l, jstride = l)
 hipError_t launch_vec_digits(const u64* vhat, size_t vstride, signed char* YD, int* SY, u32 nv, u32 k, u32 L, u32 ell,

@@ -220,6 +220,11 @@ class SecretKey {
 class DeviceSecretKey {
  public:
   explicit DeviceSecretKey(const SecretKey& sk) : params_(sk.params) { check(pvw_sk_load(params_->ctx, sk.secret_coeffs.data(), &key_)); }
+  // the resident key of SecretKey::random(p, seed, party_index), drawn on the device (pvw_sk_load_seeded): no coefficients
+  // on the host or in a device buffer
+  DeviceSecretKey(const std::shared_ptr<PvwParameters>& p, const Seed& seed, uint32_t party_index) : params_(p) {
+    check(pvw_sk_load_seeded(params_->ctx, seed.data(), party_index, &key_));
+  }
   DeviceSecretKey(const DeviceSecretKey&) = delete;
   DeviceSecretKey& operator=(const DeviceSecretKey&) = delete;
   DeviceSecretKey(DeviceSecretKey&& o) noexcept : params_(std::move(o.params_)), key_(o.key_) { o.key_ = nullptr; }
@@ -279,6 +284,13 @@ class Party {
   }
 };
 
+// SecretKey::random for parties [party_lo, party_lo + count) straight into caller-owned device memory [count][k][l] on the
+// caller's stream (pvw_sample_secret_keys_device): the d_sk of the *_device decrypt calls.  The caller clears the buffer.
+inline void sample_secret_keys_device(const std::shared_ptr<PvwParameters>& p, const Seed& seed, uint32_t party_lo, uint32_t count,
+                                      int64_t* d_sk_out, void* stream = nullptr) {
+  check(pvw_sample_secret_keys_device(p->ctx, seed.data(), party_lo, count, d_sk_out, stream));
+}
+
 // GlobalPublicKey (public_key.rs:43-54): the n x k matrix B is resident on the device
 class GlobalPublicKey {
  public:
@@ -307,6 +319,11 @@ class GlobalPublicKey {
       check(rc);
       i = j;
     }
+  }
+  // generate_all_party_keys over Party::new (:376-401, :62-79) with the secret keys drawn on the device from sk_seed
+  // (pvw_keygen_seeded): party p's key is SecretKey::random(params, sk_seed, p); it never exists on the host
+  void generate_all_party_keys(uint32_t party_lo, uint32_t party_hi, const Seed& sk_seed, const Seed& seed) {
+    check(pvw_keygen_seeded(params->ctx, party_lo, party_hi, sk_seed.data(), seed.data()));
   }
   uint32_t num_public_keys() const { uint32_t v = 0; check(pvw_num_public_keys(params->ctx, &v)); return v; }   // :344
   bool is_full() const { int32_t v = 0; check(pvw_is_full(params->ctx, &v)); return v != 0; }                   // :349

@@ -134,6 +134,8 @@ extern "C" {
     // ---- key generation: PublicKey::generate (public_key.rs:111-147) over crs.rs:138-171 ------
     pub fn pvw_keygen(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, sk: *const i64, ek: *const i64, seed: *const u8) -> i32;
     pub fn pvw_sample_secret_keys(ctx: *const PvwCtx, seed: *const u8, party_lo: u32, count: u32, sk_out: *mut i64) -> i32;
+    pub fn pvw_keygen_seeded(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, sk_seed: *const u8, seed: *const u8) -> i32;
+    pub fn pvw_sample_secret_keys_device(ctx: *mut PvwCtx, seed: *const u8, party_lo: u32, count: u32, d_sk_out: *mut i64, stream: *mut c_void) -> i32;
     // ---- encrypt (src/crypto/encryption.rs:105-214), encrypt_all_party_shares (:253-286) ------
     pub fn pvw_encrypt(ctx: *mut PvwCtx, scalars: *const u64, num_scalars: usize, rnd: *const PvwRandomnessT, c1_out: *mut u64, c2_out: *mut u64, out_repr: u32) -> i32;
     pub fn pvw_encrypt_device(ctx: *mut PvwCtx, d_scalars: *const u64, num_scalars: usize, rnd: *const PvwRandomnessT, d_c1: *mut u64, d_c2: *mut u64, out_repr: u32, stream: *mut c_void) -> i32;
@@ -193,6 +195,7 @@ extern "C" {
     pub fn pvw_decrypt_noisy_device(ctx: *mut PvwCtx, d_sk: *const i64, d_c1s: *const u64, d_c2col: *const u64, num_dealers: usize, in_repr: u32, d_noisy: *mut u64, stream: *mut c_void) -> i32;
     pub fn pvw_decrypt_batch_device(ctx: *mut PvwCtx, d_sk: *const i64, d_c1s: *const u64, d_c2col: *const u64, num_dealers: usize, in_repr: u32, d_noisy: *mut u64, d_out: *mut u64, stream: *mut c_void) -> i32;
     pub fn pvw_sk_load(ctx: *mut PvwCtx, sk: *const i64, out: *mut *mut PvwSk) -> i32;
+    pub fn pvw_sk_load_seeded(ctx: *mut PvwCtx, sk_seed: *const u8, party_index: u32, out: *mut *mut PvwSk) -> i32;
     pub fn pvw_sk_free(key: *mut PvwSk) -> i32;
     pub fn pvw_decrypt_batch_device_sk(ctx: *mut PvwCtx, key: *const PvwSk, d_c1s: *const u64, d_c2col: *const u64, num_dealers: usize, in_repr: u32, d_noisy: *mut u64, d_out: *mut u64, stream: *mut c_void) -> i32;
     pub fn pvw_decrypt_all(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, sk: *const i64, c1s: *const u64, c2s: *const u64, num_dealers: usize, in_repr: u32, out_u64: *mut u64) -> i32;

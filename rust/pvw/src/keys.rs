@@ -113,6 +113,24 @@ impl GlobalPublicKey {
         self.prepare_device().map(|_| ())
     }
 
+    /// `generate_all_party_keys` (public_key.rs:376-401) over `Party::new` / `SecretKey::random` (:62-79,
+    /// secret_key.rs:45-63) for parties `[party_lo, party_hi)` with the secret keys drawn ON THE DEVICE from `sk_seed`
+    /// (`pvw_keygen_seeded`): party p's key is the one `pvw_sample_secret_keys(ctx, sk_seed, p, 1, ..)` returns, it is
+    /// drawn by the kernel that transforms it and never exists on the host.  The key errors come from a fresh seed,
+    /// as in `generate_all_party_keys`.
+    pub fn generate_all_party_keys_seeded(&mut self, party_lo: usize, party_hi: usize, sk_seed: &[u8; 32]) -> Result<()> {
+        if party_hi > self.params.n {
+            return Err(PvwError::InvalidParameters(format!("Party index {} exceeds maximum {}", party_hi - 1, self.params.n - 1)));
+        }
+        let seed = seed_from_rng(&mut rand::thread_rng());
+        check(unsafe { sys::pvw_keygen_seeded(self.params.hip.raw(), party_lo as u32, party_hi as u32, sk_seed.as_ptr(), seed.as_ptr()) })?;
+        if party_hi > self.num_keys {
+            self.num_keys = party_hi;
+        }
+        self.refresh_host_mirror()?;
+        self.prepare_device().map(|_| ())
+    }
+
     /// Build the device-side copies the encrypt calls stream from (`pvw_prepare`: the bit-packed copy of A-hat / B-hat
     /// for `encrypt`, the MFMA-tiled copy for `encrypt_all_party_shares`) NOW, so that the first encrypt after a key
     /// change neither allocates nor waits.  `&self`: the mutators above take `&mut self` (public_key.rs:214-263), so no
