@@ -980,6 +980,82 @@ PVW_API int32_t pvw_deal_shares_packed_rs_device(pvw_ctx* ctx, const uint64_t* d
 PVW_API int32_t pvw_shamir_reconstruct_packed(uint64_t plain_modulus, uint32_t pack, const uint64_t* indices, const uint64_t* shares,
                                               size_t count, size_t num_rows, uint64_t* out);
 
+/* ---- Shamir shares over a prime field of up to 256 bits: wide shares as limb ciphertexts -------------------
+ * The family above works in Z_p with p < 2^62; a PVSS / DKG round most often shares a scalar of an elliptic-curve group
+ * (secp256k1's order, BLS12-381's r, the Ed25519 group order, 2^255 - 19).  This family is the same dealing end over such a
+ * field.  The reference has no sharing code: the contract is the library's own.  No call above changes; p >= 2^62 stays
+ * refused by every one of them.
+ *   A wide element is PVW_WIDE_WORDS = 4 little-endian uint64_t words.  plain_modulus (a HOST pointer in every form) is such an
+ *   element: an odd prime with n < p < 2^256.  Primality is checked on the host, before any device work, by Miller-Rabin over
+ *   the 32 prime bases 2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37, 41, 43, 47, 53, 59, 61, 67, 71, 73, 79, 83, 89, 97, 101,
+ *   103, 107, 109, 113, 127, 131 (a single-word p by the deterministic test of the family above).  A composite or even p,
+ *   p <= n, degree >= n, num_dealers = 0 or a NULL argument: PVW_ERR_INVALID_PARAMETERS.
+ *   f_d(x) = s_d + a_{d,1} x + ... + a_{d,t} x^t mod p and shares[d][i] = f_d(i + 1), i the global party index.  secrets [D][4]
+ *   and explicit coefficients [D][t][4] are wide words that mean w mod p: any word is accepted, 2^256 - 1 included.  t = 0
+ *   copies the secret and draws nothing.
+ *   a_{d,j} = the first accepted attempt of the ChaCha8 stream (PVW_DOM_SHAMIR << 32) | j under dealer d's key: an attempt is
+ *   four consecutive next_u64() words, word 0 least significant, masked to the low bitlen(p) bits and accepted when below p
+ *   (at least every second attempt).  For p < 2^62 these are NOT the coefficients pvw_shamir_shares* draws.
+ *   Limbs: a share is cut into NL = ceil(bitlen(p) / limb_bits) limbs of limb_bits bits, 16 <= limb_bits <= 62 and
+ *   NL <= PVW_WIDE_MAX_LIMBS = 16, limb w = (share >> (w limb_bits)) mod 2^limb_bits.  Each limb is one PVW plaintext (below
+ *   2^63, encryption.rs:195); ciphertext v = d NL + w carries limb w of dealer d's shares.  With limb_bits = 52 (5 limbs at 256
+ *   bits) the limb-wise sum of up to 2048 dealers stays below 2^63, so pvw_ct_sum* / pvw_decrypt_*sum* aggregate a wide
+ *   sharing unchanged, limb by limb, and pvw_shamir_wide_from_limbs_host folds the summed limbs back mod p.
+ *   Keys: the shares-alone calls take seeds [D][32], dealer d's coefficient key.  The deal calls take seeds [D NL][32]: vector v
+ *   is encrypted exactly as vector v of pvw_encrypt_multi, and dealer d's coefficients are drawn under the key of vector d NL;
+ *   a dealer never shares one r between two of its limbs.  _rs forms: vector v's key is call_seed(S, c + v), and the state
+ *   ends at c + D NL. */
+#define PVW_WIDE_WORDS 4
+#define PVW_WIDE_MAX_LIMBS 16
+/* NL for (p, limb_bits); host only, no context.  p even or below 3, limb_bits outside [16, 62], NL > 16: INVALID_PARAMETERS */
+PVW_API int32_t pvw_shamir_wide_limbs(const uint64_t* plain_modulus, uint32_t limb_bits, uint32_t* num_limbs);
+/* shares [D][n][4].  The host routine (no GPU needed; what the kernel is tested against) writes every column; the device
+ * routines write columns [party_lo, party_hi) of a sharded context and leave the others untouched.  The _device form takes
+ * device pointers (seeds and plain_modulus stay HOST pointers), is asynchronous on `stream`, allocates nothing and may be
+ * captured.  The host-buffer form stages the dealers in bounded pieces and clears what it staged before it returns. */
+PVW_API int32_t pvw_shamir_shares_wide_host(const pvw_ctx* ctx, const uint64_t* secrets, size_t num_dealers, uint32_t degree,
+                                            const uint64_t* plain_modulus, const uint8_t* seeds, const uint64_t* coeffs,
+                                            uint64_t* shares_out);
+PVW_API int32_t pvw_shamir_shares_wide_device(pvw_ctx* ctx, const uint64_t* d_secrets, size_t num_dealers, uint32_t degree,
+                                              const uint64_t* plain_modulus, const uint8_t* seeds, const uint64_t* d_coeffs,
+                                              uint64_t* d_shares, void* stream);
+PVW_API int32_t pvw_shamir_shares_wide(pvw_ctx* ctx, const uint64_t* secrets, size_t num_dealers, uint32_t degree,
+                                       const uint64_t* plain_modulus, const uint8_t* seeds, const uint64_t* coeffs,
+                                       uint64_t* shares_out);
+/* Deal: pvw_encrypt_multi* on D NL vectors, outputs c1 [D NL]..., c2 [D NL]..., bit for bit what pvw_encrypt_multi* gives for
+ * the limb planes (pvw_shamir_wide_to_limbs_host per dealer) of pvw_shamir_shares_wide_host(..., seeds[d NL], NULL): both
+ * representations, both sides of the dealer-count dispatch (by D NL), sharded contexts.  The checks of pvw_encrypt_multi* come
+ * first, then the ones above.  Capture rules and the wipe of the share scratch as pvw_deal_shares*: after
+ * pvw_prepare(PVW_PREPARE_MFMA) the _device forms neither allocate nor synchronise and may be captured, and every replay of the
+ * _rs form deals a fresh sharing. */
+PVW_API int32_t pvw_deal_shares_wide(pvw_ctx* ctx, const uint64_t* secrets, size_t num_dealers, uint32_t degree,
+                                     const uint64_t* plain_modulus, uint32_t limb_bits, const uint8_t* seeds, uint64_t* c1_out,
+                                     uint64_t* c2_out, uint32_t out_repr);
+PVW_API int32_t pvw_deal_shares_wide_device(pvw_ctx* ctx, const uint64_t* d_secrets, size_t num_dealers, uint32_t degree,
+                                            const uint64_t* plain_modulus, uint32_t limb_bits, const uint8_t* seeds, uint64_t* d_c1,
+                                            uint64_t* d_c2, uint32_t out_repr, void* stream);
+PVW_API int32_t pvw_deal_shares_wide_rs(pvw_ctx* ctx, const uint64_t* secrets, size_t num_dealers, uint32_t degree,
+                                        const uint64_t* plain_modulus, uint32_t limb_bits, void* st, uint64_t* c1_out,
+                                        uint64_t* c2_out, uint32_t out_repr);
+PVW_API int32_t pvw_deal_shares_wide_rs_device(pvw_ctx* ctx, const uint64_t* d_secrets, size_t num_dealers, uint32_t degree,
+                                               const uint64_t* plain_modulus, uint32_t limb_bits, void* st, uint64_t* d_c1,
+                                               uint64_t* d_c2, uint32_t out_repr, void* stream);
+/* Host only: values [count][4] -> limbs_out [num_limbs][count] (a value that does not fit num_limbs limbs: INVALID_PARAMETERS),
+ * and back: out[i] = sum_w limbs[w][i] 2^(w limb_bits) mod p, where each input word is ANY uint64_t -- a limb, or a sum of limbs. */
+PVW_API int32_t pvw_shamir_wide_to_limbs_host(const uint64_t* values, size_t count, uint32_t limb_bits, uint32_t num_limbs,
+                                              uint64_t* limbs_out);
+PVW_API int32_t pvw_shamir_wide_from_limbs_host(const uint64_t* plain_modulus, const uint64_t* limbs, size_t count, uint32_t limb_bits,
+                                                uint32_t num_limbs, uint64_t* out);
+/* Reconstruction, host only: Lagrange at 0 of the points indices[i] + 1.  shares [num_secrets][count][4] (any words, read mod
+ * p), out [num_secrets][4].  The rules of pvw_shamir_reconstruct: count = 0, a duplicate index, an index >= p - 1, a composite
+ * p: INVALID_PARAMETERS; count must be at least degree + 1 for the result to be the secret. */
+PVW_API int32_t pvw_shamir_reconstruct_wide(const uint64_t* plain_modulus, const uint64_t* indices, const uint64_t* shares, size_t count,
+                                            size_t num_secrets, uint64_t* out);
+/* SELF-TEST: the kernel's own Horner step on the device, out[i] = (acc[i] x[i] + add[i]) mod p for acc, add [count][4] below
+ * p and x [count] below 2^32 (anything else: INVALID_PARAMETERS).  It exists because x near 2^32 cannot be reached through n. */
+PVW_API int32_t pvw_selftest_shamir_wide_step(pvw_ctx* ctx, const uint64_t* plain_modulus, const uint64_t* acc, const uint64_t* x,
+                                              const uint64_t* add, size_t count, uint64_t* out);
+
 /* decode_scalar_pvw_rns alone, on the device: noisy [D][L][l] power basis (host) -> out_u64 [D] */
 PVW_API int32_t pvw_decode(pvw_ctx* ctx, const uint64_t* noisy, size_t count, uint64_t* out_u64);
 /* the same with host big integers on the host cores (no GPU needed): an independent

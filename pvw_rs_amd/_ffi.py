@@ -155,6 +155,19 @@ _SIGNATURES = {
     "pvw_deal_shares_rs_device": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint64, _P, _P, _P, C.c_uint32, _P],
     "pvw_shamir_reconstruct": [C.c_uint64, _P, _P, C.c_size_t, C.c_size_t, _P],
     # packed sharing: the 8.9 calls with `pack` after num_dealers; reconstruct (p, pack, indices, shares, count, rows, out)
+    # Shamir shares over a prime below 2^256: plain_modulus is a pointer to four words
+    "pvw_shamir_wide_limbs": [_P, C.c_uint32, _P],
+    "pvw_shamir_shares_wide_host": [_P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, _P],
+    "pvw_shamir_shares_wide_device": [_P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, _P, _P],
+    "pvw_shamir_shares_wide": [_P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, _P],
+    "pvw_deal_shares_wide": [_P, _P, C.c_size_t, C.c_uint32, _P, C.c_uint32, _P, _P, _P, C.c_uint32],
+    "pvw_deal_shares_wide_device": [_P, _P, C.c_size_t, C.c_uint32, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P],
+    "pvw_deal_shares_wide_rs": [_P, _P, C.c_size_t, C.c_uint32, _P, C.c_uint32, _P, _P, _P, C.c_uint32],
+    "pvw_deal_shares_wide_rs_device": [_P, _P, C.c_size_t, C.c_uint32, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P],
+    "pvw_shamir_wide_to_limbs_host": [_P, C.c_size_t, C.c_uint32, C.c_uint32, _P],
+    "pvw_shamir_wide_from_limbs_host": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, _P],
+    "pvw_shamir_reconstruct_wide": [_P, _P, _P, C.c_size_t, C.c_size_t, _P],
+    "pvw_selftest_shamir_wide_step": [_P, _P, _P, _P, _P, C.c_size_t, _P],
     "pvw_shamir_shares_packed_host": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P],
     "pvw_shamir_shares_packed_device": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P, _P],
     "pvw_shamir_shares_packed": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P],

@@ -920,6 +920,127 @@ def shamir_reconstruct(indices: Sequence[int], shares, plain_modulus: int):
     return int(out[0]) if single else [int(v) for v in out]
 
 
+WIDE_WORDS = 4   # PVW_WIDE_WORDS: a wide element is four little-endian uint64 words
+
+
+def _wide(values) -> np.ndarray:
+    """Python ints (any size: the low 256 bits) or ready-made words [..., 4] -> uint64 [N][4]"""
+    if isinstance(values, np.ndarray) and values.dtype == np.uint64 and values.ndim >= 1 and values.shape[-1] == WIDE_WORDS:
+        return np.ascontiguousarray(values).reshape(-1, WIDE_WORDS)
+    return np.array([[(int(v) >> (64 * w)) & 0xFFFFFFFFFFFFFFFF for w in range(WIDE_WORDS)] for v in values],
+                    dtype=np.uint64).reshape(-1, WIDE_WORDS)
+
+
+def _wide_ints(words: np.ndarray) -> list:
+    return [sum(int(row[w]) << (64 * w) for w in range(WIDE_WORDS)) for row in np.asarray(words).reshape(-1, WIDE_WORDS)]
+
+
+def _wide_modulus(plain_modulus: int) -> np.ndarray:
+    p = int(plain_modulus)
+    if p < 0 or p >> 256:
+        raise PvwError(1, "plain_modulus must be below 2^256")
+    return _wide([p])
+
+
+def shamir_wide_limbs(plain_modulus: int, limb_bits: int = 52) -> int:
+    """EXTENSION: NL = ceil(bitlen(plain_modulus) / limb_bits), the ciphertexts per dealer of
+    deal_party_shares_wide (pvw_shamir_wide_limbs; no GPU, no context)."""
+    nl = C.c_uint32()
+    L = _ffi.lib()
+    _check(L.pvw_shamir_wide_limbs(_ptr(_wide_modulus(plain_modulus)), int(limb_bits), C.byref(nl)), L)
+    return int(nl.value)
+
+
+def shamir_shares_wide(params: PvwParameters, secrets: Sequence[int], degree: int, plain_modulus: int,
+                       seeds: Optional[Sequence[bytes]] = None, coeffs=None, host: bool = False) -> np.ndarray:
+    """EXTENSION: shamir_shares over an odd prime plain_modulus < 2^256.  secrets and coeffs [D][degree] are Python
+    ints (any value: read mod p); the result is a uint64 array [D][n][4] of little-endian words.  On the device
+    (pvw_shamir_shares_wide); host=True: the restatement on the host cores (pvw_shamir_shares_wide_host, no GPU).  A sharded
+    context's device call writes its own columns and leaves the others zero."""
+    se = _wide(secrets)
+    D = len(se)
+    sd = _seeds(seeds, D) if seeds is not None else None
+    co = None
+    if coeffs is not None:
+        rows = [list(row) for row in coeffs]
+        if any(len(row) != int(degree) for row in rows) or len(rows) != D:
+            raise PvwError(15, f"expected {D} rows of {int(degree)} coefficients")
+        co = _wide([v for row in rows for v in row]) if int(degree) else None     # degree 0 reads no coefficient
+    out = np.zeros((D, params.n, WIDE_WORDS), dtype=np.uint64)
+    params._call("pvw_shamir_shares_wide" + ("_host" if host else ""), _ptr(se), D, int(degree), _ptr(_wide_modulus(plain_modulus)),
+                 _ptr(sd), _ptr(co), _ptr(out))
+    return out
+
+
+def deal_party_shares_wide(secrets: Sequence[int], degree: int, plain_modulus: int, global_pk: GlobalPublicKey,
+                           seeds: Optional[Sequence[bytes]] = None, randomness: Optional["DeviceRandomness"] = None,
+                           limb_bits: int = 52, out_repr: int = REPR_NTT) -> List[List[PvwCiphertext]]:
+    """EXTENSION: dealer d shares secrets[d] over the field of plain_modulus (an odd prime below 2^256) and encrypts
+    the shares limb by limb in one device call (pvw_deal_shares_wide): D lists of NL ciphertexts, ciphertext [d][w] carrying limb
+    w (limb_bits bits) of dealer d's shares.  seeds: D * NL of them, vector d * NL + w's; dealer d's coefficients are drawn under
+    seeds[d * NL].  `randomness` instead: vector v uses call_seed(S, c + v) and the state then holds c + D * NL."""
+    p = global_pk.params
+    se = _wide(secrets)
+    D = len(se)
+    NL = shamir_wide_limbs(plain_modulus, limb_bits)
+    V = D * NL
+    pm = _wide_modulus(plain_modulus)
+    c1 = np.zeros((V, p.k, p.L, p.l), dtype=np.uint64)
+    c2 = np.zeros((V, p.n, p.L, p.l), dtype=np.uint64)
+    if randomness is not None:
+        _check_state(p, randomness, seeds)
+        p._call("pvw_deal_shares_wide_rs", _ptr(se), D, int(degree), _ptr(pm), int(limb_bits), randomness._h, _ptr(c1), _ptr(c2), out_repr)
+    else:
+        if seeds is None:
+            raise PvwError(1, "deal_party_shares_wide needs one 32-byte seed per limb ciphertext or a DeviceRandomness")
+        sd = _seeds(seeds, V)
+        p._call("pvw_deal_shares_wide", _ptr(se), D, int(degree), _ptr(pm), int(limb_bits), _ptr(sd), _ptr(c1), _ptr(c2), out_repr)
+    return [[PvwCiphertext(c1[d * NL + w], c2[d * NL + w], p, out_repr) for w in range(NL)] for d in range(D)]
+
+
+def shamir_wide_to_limbs(values, limb_bits: int = 52, num_limbs: Optional[int] = None, plain_modulus: Optional[int] = None) -> np.ndarray:
+    """EXTENSION: values (ints, or words [count][4]) -> uint64 limbs [num_limbs][count], limb w of value i at
+    [w][i] (pvw_shamir_wide_to_limbs_host).  num_limbs, or plain_modulus to take it from shamir_wide_limbs."""
+    v = _wide(values)
+    nl = int(num_limbs) if num_limbs is not None else shamir_wide_limbs(plain_modulus, limb_bits)
+    out = np.zeros((nl, len(v)), dtype=np.uint64)
+    L = _ffi.lib()
+    _check(L.pvw_shamir_wide_to_limbs_host(_ptr(v), len(v), int(limb_bits), nl, _ptr(out)), L)
+    return out
+
+
+def shamir_wide_from_limbs(limbs, plain_modulus: int, limb_bits: int = 52) -> list:
+    """EXTENSION: limbs [num_limbs][count] (each any uint64: a limb, or a sum of limbs as decrypt_all_party_sums
+    returns it) -> the ints sum_w limbs[w][i] 2^(w limb_bits) mod plain_modulus (pvw_shamir_wide_from_limbs_host)."""
+    lm = np.array([[int(v) & 0xFFFFFFFFFFFFFFFF for v in row] for row in limbs], dtype=np.uint64)
+    lm = lm.reshape(len(lm), -1)
+    out = np.zeros((lm.shape[1], WIDE_WORDS), dtype=np.uint64)
+    L = _ffi.lib()
+    _check(L.pvw_shamir_wide_from_limbs_host(_ptr(_wide_modulus(plain_modulus)), _ptr(lm), lm.shape[1], int(limb_bits), lm.shape[0], _ptr(out)), L)
+    return _wide_ints(out)
+
+
+def shamir_reconstruct_wide(indices: Sequence[int], shares, plain_modulus: int):
+    """EXTENSION: shamir_reconstruct over a prime below 2^256 (pvw_shamir_reconstruct_wide; host only).  shares:
+    one int per index -> an int; rows [num_secrets][len(indices)] of ints, or words [num_secrets][len(indices)][4] -> a list."""
+    idx = _words(indices)
+    if isinstance(shares, np.ndarray) and shares.dtype == np.uint64 and shares.ndim == 3:
+        single, sh = False, np.ascontiguousarray(shares)
+    else:
+        single = len(shares) == 0 or np.ndim(shares[0]) == 0
+        rows = [shares] if single else shares
+        if any(len(row) != len(idx) for row in rows):
+            raise PvwError(15, f"expected {len(idx)} shares per secret")
+        sh = _wide([v for row in rows for v in row]).reshape(len(rows), len(idx), WIDE_WORDS)
+    if sh.shape[1] != len(idx):
+        raise PvwError(15, f"expected {len(idx)} shares per secret, got {sh.shape[1]}")
+    out = np.zeros((sh.shape[0], WIDE_WORDS), dtype=np.uint64)
+    L = _ffi.lib()
+    _check(L.pvw_shamir_reconstruct_wide(_ptr(_wide_modulus(plain_modulus)), _ptr(idx), _ptr(sh), len(idx), sh.shape[0], _ptr(out)), L)
+    res = _wide_ints(out)
+    return res[0] if single else res
+
+
 def _share_matrix(indices: Sequence[int], shares, layout: str):
     """(idx, sh, S, count, strides) of the checked, corrected and evaluate calls: the indices and the share matrix as uint64
     words, and the (secret, point) strides of `layout` in words"""

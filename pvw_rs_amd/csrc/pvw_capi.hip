@@ -3301,6 +3301,7 @@ struct ShamirDeal {
   Mod m;
   u32 pack = 0;           // the packed entry points: secrets per dealer, >= 1, and the packed kernel runs; 0: the calls of 8.9
   const u64* d_packw = nullptr;   // ... on the weights of the call (shamir_packed_prepare)
+  const struct ShamirWideDeal* wide = nullptr;   // the wide entry points: the dealers of a pass are these, cut into limbs
   u32 words() const { return pack ? pack : 1; }   // secrets per dealer
   // the same deal starting i dealers further on
   ShamirDeal from(size_t i) const {
@@ -3347,6 +3348,56 @@ static int32_t shamir_enqueue(pvw_ctx* c, const ShamirDeal& deal, const DealerKe
     b.Lw = deal.d_packw;
     b.zt = deal.d_packw + (size_t)deal.pack * c->rowsB();
     PVW_HIP(launch_shamir_eval(b, s));
+    memset(&b, 0, sizeof b);
+  }
+  return PVW_OK;
+}
+
+// One call's sharing over a prime below 2^256.  num_limbs == 0: the shares themselves, [dealer][n][4];
+// otherwise vector v = d * num_limbs + w is limb w of dealer d, and key_stride = num_limbs: dealer d draws under vector d * num_limbs's key
+struct ShamirWideDeal {
+  const u64* d_secrets;   // [D][4]
+  const u64* d_coeffs;    // [D][degree][4], or NULL: drawn
+  u32 degree;
+  WideMod m;
+  u32 limb_bits = 0, num_limbs = 0;
+};
+// rows [v0, v0 + nv) of the call (dealers when num_limbs == 0, limb vectors otherwise) into out; `keys` is the source of the
+// call's (piece's) vector 0.  PVW_MAX_PROLOGUE_KEYS dealers per launch; a dealer whose limbs straddle two passes is evaluated
+// in both and stores only the rows of each (the arithmetic is exact).
+static int32_t shamir_wide_enqueue(pvw_ctx* c, const ShamirWideDeal& deal, const DealerKeys& keys, size_t v0, size_t nv, u64* out,
+                                   hipStream_t s) {
+  if (!nv) return PVW_OK;
+  ProfScope ps(c, "shamir_eval_wide", s);
+  const u32 NL = deal.num_limbs, ks = NL ? NL : 1;
+  const size_t dlo = v0 / ks, dhi = (v0 + nv - 1) / ks + 1;
+  struct OneKey { ChaChaKey key[1]; const RndState* rnd; u64 rnd_off; };
+  for (size_t d0 = dlo; d0 < dhi; d0 += PVW_MAX_PROLOGUE_KEYS) {
+    ShamirWideBatch b{};
+    b.secrets = deal.d_secrets;
+    b.coeffs = deal.d_coeffs;
+    b.row_stride = c->n;
+    b.d_lo = (u32)d0;
+    b.nd = (u32)((dhi - d0) < PVW_MAX_PROLOGUE_KEYS ? (dhi - d0) : PVW_MAX_PROLOGUE_KEYS);
+    b.degree = deal.degree;
+    b.party_lo = c->party_lo;
+    b.party_hi = c->party_hi;
+    b.limb_bits = deal.limb_bits;
+    b.num_limbs = NL;
+    b.v0 = (u32)v0;
+    b.nv = (u32)nv;
+    b.out = out;
+    b.m = deal.m;
+    b.key_stride = ks;
+    if (!b.coeffs && deal.degree)
+      for (u32 x = 0; x < b.nd; ++x) {
+        OneKey k{};
+        keys.from((d0 + x) * ks).fill(k, 1);
+        b.key[x] = k.key[0];
+        if (x == 0) { b.rnd = k.rnd; b.rnd_off = k.rnd_off; }
+        memset(&k, 0, sizeof k);
+      }
+    PVW_HIP(launch_shamir_eval_wide(b, s));
     memset(&b, 0, sizeof b);
   }
   return PVW_OK;
@@ -3454,7 +3505,8 @@ static int32_t encrypt_multi_enqueue(pvw_ctx* c, Workspace* w, const u64* d_scal
   for (size_t d0 = 0; d0 < D; d0 += group) {
     const u32 nv = (u32)((D - d0) < group ? (D - d0) : group);
     const u64* gsc = deal ? w->shares : d_scalars + d0 * c->n;   // the pass's scalars [nv][n]
-    if (deal) PVW_TRY(shamir_enqueue(c, deal->from(d0), keys.from(d0), nv, w->shares, s));
+    if (deal && deal->wide) PVW_TRY(shamir_wide_enqueue(c, *deal->wide, keys, d0, nv, w->shares, s));   // vectors [d0, d0 + nv) of the piece
+    else if (deal) PVW_TRY(shamir_enqueue(c, deal->from(d0), keys.from(d0), nv, w->shares, s));
     // prologue: the (r, e1, e2) families of dealer d0 replicated over the nv dealers of this pass (up to 64 keys
     // per launch): r-hat_d -> vh[v], NTT(e1), NTT(e2) + m*g-hat -> output planes
     for (u32 v0 = 0; v0 < nv; v0 += PVW_MAX_PROLOGUE_KEYS) {
@@ -3689,6 +3741,448 @@ int32_t pvw_deal_shares_packed(pvw_ctx* c, const uint64_t* secrets, size_t num_d
 int32_t pvw_deal_shares_packed_rs(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
                                   uint64_t plain_modulus, void* handle, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
   return deal_host(c, secrets, num_dealers, degree, plain_modulus, DealerKeys::state(handle), c1_out, c2_out, out_repr, &pack);
+}
+
+// ------------------------------------------------------------------------ Shamir shares over a prime below 2^256
+// Elements of four words; the host side runs the kernel's own arithmetic (pvw_wide.h), scaled as the kernel runs it.
+typedef u64 Wide[4];
+static void wide_set(Wide o, const u64* a) { for (int i = 0; i < 4; ++i) o[i] = a[i]; }
+static void wide_small(Wide o, u64 v) { o[0] = v; o[1] = o[2] = o[3] = 0; }
+static bool wide_is_zero(const Wide a) { return !(a[0] | a[1] | a[2] | a[3]); }
+// a, b below pn: (a + b) mod pn and (a - b) mod pn
+static void wide_addmod(Wide a, const Wide b, const WideMod& m) {
+  u64 r[4];
+  wide_set(r, a);
+  wide_step(r, 1, *(const u64(*)[4])b, m);
+  wide_set(a, r);
+}
+static void wide_negmod(Wide a, const WideMod& m) {   // pn - a, 0 stays 0
+  if (wide_is_zero(a)) return;
+  u64 br = 0;
+  for (int i = 0; i < 4; ++i) {
+    const u64 s1 = m.pn[i] - a[i], s2 = s1 - br;
+    br = (m.pn[i] < a[i]) | (s1 < br);
+    a[i] = s2;
+  }
+}
+// res = a b mod p, scaled: a scaled and below pn, b ANY four words (its 16-bit digits are the multipliers of 32 steps)
+static void wide_mulmod(Wide res, const Wide a, const Wide b, const WideMod& m) {
+  u64 r[4] = {0, 0, 0, 0}, zero[4] = {0, 0, 0, 0}, av[4];
+  wide_set(av, a);
+  for (int k = 16; k-- > 0;) {
+    const u32 dg = (u32)(b[k / 4] >> (16 * (k % 4))) & 0xFFFF;
+    wide_step(r, 1u << 16, zero, m);
+    u64 t[4];
+    wide_set(t, av);
+    wide_step(t, dg, r, m);
+    wide_set(r, t);
+  }
+  wide_set(res, r);
+}
+// a scaled -> the plain words of a, and back
+static void wide_unscale(Wide o, const Wide a, const WideMod& m) {
+  u64 t[4];
+  wide_set(t, a);
+  wide_shr(t, m.shift);
+  wide_set(o, t);
+}
+static void wide_reduce(Wide o, const u64* w, const WideMod& m) {
+  u64 t[4];
+  wide_reduce_scaled(w, m, t);
+  wide_set(o, t);
+}
+// a^e mod p (scaled in, scaled out), e any four words
+static void wide_powmod(Wide res, const Wide a, const Wide e, const WideMod& m) {
+  Wide r, one, b, plain;
+  wide_small(one, 1);
+  wide_reduce(r, one, m);
+  wide_set(b, a);
+  for (int i = 255; i >= 0; --i) {
+    wide_unscale(plain, r, m);
+    wide_mulmod(r, r, plain, m);
+    if ((e[i / 64] >> (i % 64)) & 1) {
+      wide_unscale(plain, b, m);
+      wide_mulmod(r, r, plain, m);
+    }
+  }
+  wide_set(res, r);
+}
+static void wide_invmod(Wide res, const Wide a, const Wide p, const WideMod& m) {   // Fermat: a^(p - 2)
+  Wide e;
+  wide_set(e, p);
+  u64 br = 2;
+  for (int i = 0; i < 4 && br; ++i) {
+    const u64 v = e[i];
+    e[i] = v - br;
+    br = v < br;
+  }
+  wide_powmod(res, a, e, m);
+}
+
+// Miller-Rabin over the first 32 primes as bases (include/pvw_hip.h states the list); p odd and >= 3
+static const u32 WIDE_MR_BASES[32] = {2,  3,  5,  7,  11, 13, 17, 19, 23, 29, 31, 37,  41,  43,  47,  53,
+                                      59, 61, 67, 71, 73, 79, 83, 89, 97, 101, 103, 107, 109, 113, 127, 131};
+static bool wide_is_prime(const Wide p, const WideMod& m) {
+  if (!p[1] && !p[2] && !p[3]) return is_prime_u64(p[0]);
+  Wide pm1, dd, one, onep, m1;
+  wide_set(pm1, p);
+  pm1[0] -= 1;                                             // p odd
+  wide_set(dd, pm1);
+  u32 r = 0;
+  while (!(dd[0] & 1)) {
+    u64 t[4];
+    wide_set(t, dd);
+    wide_shr(t, 1);
+    wide_set(dd, t);
+    ++r;
+  }
+  wide_small(one, 1);
+  wide_reduce(onep, one, m);
+  wide_reduce(m1, pm1, m);
+  for (u32 bi = 0; bi < 32; ++bi) {
+    Wide a, x;
+    wide_small(a, WIDE_MR_BASES[bi]);
+    wide_reduce(a, a, m);
+    wide_powmod(x, a, dd, m);
+    if (!memcmp(x, onep, 32) || !memcmp(x, m1, 32)) continue;
+    bool witness = true;
+    for (u32 i = 1; i < r && witness; ++i) {
+      Wide plain;
+      wide_unscale(plain, x, m);
+      wide_mulmod(x, x, plain, m);
+      if (!memcmp(x, m1, 32)) witness = false;
+    }
+    if (witness) return false;
+  }
+  return true;
+}
+
+// p odd, >= 3 and prime; the verdict of the last modulus a thread asked about is kept (a protocol runs many calls on one field)
+static int32_t wide_modulus_check(const uint64_t* p, WideMod* out) {
+  if (!p) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (!(p[0] & 1) || (p[0] < 3 && !p[1] && !p[2] && !p[3]))
+    return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must be an odd prime (Shamir shares live in a field)");
+  *out = make_wide_mod(p);
+  static thread_local u64 known[4] = {0, 0, 0, 0};
+  if (memcmp(known, p, 32) != 0) {
+    if (!wide_is_prime(p, *out)) return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must be prime (Shamir shares live in a field)");
+    memcpy(known, p, 32);
+  }
+  return PVW_OK;
+}
+static int32_t wide_limb_count(const WideMod& m, uint32_t limb_bits, uint32_t* num_limbs) {
+  if (limb_bits < 16 || limb_bits > 62) return fail(PVW_ERR_INVALID_PARAMETERS, "limb_bits must be in [16, 62]");
+  const u32 nl = (m.bits + limb_bits - 1) / limb_bits;
+  if (nl > PVW_WIDE_MAX_LIMBS) return fail(PVW_ERR_INVALID_PARAMETERS, "more than 16 limbs: choose wider limbs");
+  *num_limbs = nl;
+  return PVW_OK;
+}
+static int32_t shamir_wide_checks(const pvw_ctx* c, size_t D, uint32_t degree, const uint64_t* p, WideMod* m) {
+  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no dealers");
+  if (!p) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (!p[1] && !p[2] && !p[3] && p[0] <= c->n)
+    return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must exceed the party count (evaluation points 1..n)");
+  PVW_TRY(wide_modulus_check(p, m));
+  if (degree >= c->n) {
+    char buf[112];
+    snprintf(buf, sizeof buf, "degree %u needs more than %u parties", degree, c->n);
+    return fail(PVW_ERR_INVALID_PARAMETERS, buf);
+  }
+  return PVW_OK;
+}
+
+int32_t pvw_shamir_wide_limbs(const uint64_t* plain_modulus, uint32_t limb_bits, uint32_t* num_limbs) {
+  if (!plain_modulus || !num_limbs) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (!(plain_modulus[0] & 1) || (plain_modulus[0] < 3 && !plain_modulus[1] && !plain_modulus[2] && !plain_modulus[3]))
+    return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must be an odd prime (Shamir shares live in a field)");
+  return wide_limb_count(make_wide_mod(plain_modulus), limb_bits, num_limbs);
+}
+
+// the contract on the host cores (no GPU), through the kernel's own step.  Writes all n columns, whatever the context's shard.
+int32_t pvw_shamir_shares_wide_host(const pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t degree,
+                                    const uint64_t* plain_modulus, const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out) {
+  if (!c || !secrets || !shares_out || !plain_modulus || (degree && !seeds && !coeffs)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  WideMod m;
+  PVW_TRY(shamir_wide_checks(c, num_dealers, degree, plain_modulus, &m));
+  const u32 n = c->n, t = degree;
+  std::vector<u64> a(((size_t)t + 1) * 4);
+  for (size_t d = 0; d < num_dealers; ++d) {
+    wide_reduce(&a[0], secrets + d * 4, m);
+    for (u32 j = 1; j <= t; ++j) {
+      if (coeffs) wide_reduce(&a[(size_t)j * 4], coeffs + (d * t + (j - 1)) * 4, m);
+      else wide_draw_scaled(make_key(seeds + d * 32), PVW_DOM_SHAMIR, j, m, *(u64(*)[4]) & a[(size_t)j * 4]);
+    }
+    for (u32 i = 0; i < n; ++i) {
+      u64 acc[4] = {0, 0, 0, 0};
+      for (u32 e = t + 1; e-- > 0;) wide_step(acc, i + 1, *(const u64(*)[4]) & a[(size_t)e * 4], m);
+      wide_shr(acc, m.shift);
+      wide_set(shares_out + (d * n + i) * 4, acc);
+    }
+  }
+  volatile u64* va = a.data();                               // the coefficients are as secret as the secret
+  for (size_t j = 0; j < a.size(); ++j) va[j] = 0;
+  return PVW_OK;
+}
+
+int32_t pvw_shamir_wide_to_limbs_host(const uint64_t* values, size_t count, uint32_t limb_bits, uint32_t num_limbs, uint64_t* limbs_out) {
+  if ((!values || !limbs_out) && count) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (limb_bits < 16 || limb_bits > 62) return fail(PVW_ERR_INVALID_PARAMETERS, "limb_bits must be in [16, 62]");
+  if (num_limbs < 1 || num_limbs > PVW_WIDE_MAX_LIMBS) return fail(PVW_ERR_INVALID_PARAMETERS, "num_limbs must be in [1, 16]");
+  const u64 mask = ((u64)1 << limb_bits) - 1;
+  for (size_t i = 0; i < count; ++i) {
+    u64 v[4];
+    wide_set(v, values + i * 4);
+    for (u32 w = 0; w < num_limbs; ++w) {
+      limbs_out[(size_t)w * count + i] = v[0] & mask;
+      wide_shr(v, limb_bits);
+    }
+    if ((size_t)num_limbs * limb_bits < 256 && !wide_is_zero(v)) return fail(PVW_ERR_INVALID_PARAMETERS, "a value does not fit num_limbs limbs");
+  }
+  return PVW_OK;
+}
+
+int32_t pvw_shamir_wide_from_limbs_host(const uint64_t* plain_modulus, const uint64_t* limbs, size_t count, uint32_t limb_bits,
+                                        uint32_t num_limbs, uint64_t* out) {
+  if (!plain_modulus || ((!limbs || !out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (limb_bits < 16 || limb_bits > 62) return fail(PVW_ERR_INVALID_PARAMETERS, "limb_bits must be in [16, 62]");
+  if (num_limbs < 1 || num_limbs > PVW_WIDE_MAX_LIMBS) return fail(PVW_ERR_INVALID_PARAMETERS, "num_limbs must be in [1, 16]");
+  WideMod m;
+  PVW_TRY(wide_modulus_check(plain_modulus, &m));
+  const u32 h0 = limb_bits / 2, h1 = limb_bits - h0;       // 2^limb_bits in two multipliers below 2^32
+  for (size_t i = 0; i < count; ++i) {
+    u64 acc[4] = {0, 0, 0, 0}, zero[4] = {0, 0, 0, 0};
+    for (u32 w = num_limbs; w-- > 0;) {
+      Wide lw;
+      wide_small(lw, limbs[(size_t)w * count + i]);
+      u64 add[4];
+      wide_reduce_scaled(lw, m, add);
+      wide_step(acc, 1u << h0, zero, m);
+      wide_step(acc, 1u << h1, add, m);
+    }
+    wide_shr(acc, m.shift);
+    wide_set(out + i * 4, acc);
+  }
+  return PVW_OK;
+}
+
+// Lagrange at 0 from the points indices[i] + 1: w_i = prod_{j != i} x_j / (x_j - x_i), one inversion per weight
+int32_t pvw_shamir_reconstruct_wide(const uint64_t* plain_modulus, const uint64_t* indices, const uint64_t* shares, size_t count,
+                                    size_t num_secrets, uint64_t* out) {
+  if (!plain_modulus || !indices || ((!shares || !out) && num_secrets)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (count == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no shares");
+  WideMod m;
+  PVW_TRY(wide_modulus_check(plain_modulus, &m));
+  const bool small_p = !plain_modulus[1] && !plain_modulus[2] && !plain_modulus[3];
+  {
+    std::vector<u64> sorted(indices, indices + count);
+    std::sort(sorted.begin(), sorted.end());
+    for (size_t i = 0; i < count; ++i) {
+      if (i && sorted[i] == sorted[i - 1]) return fail(PVW_ERR_INVALID_PARAMETERS, "duplicate party index");
+      if (sorted[i] == ~(u64)0 || (small_p && sorted[i] >= plain_modulus[0] - 1))
+        return fail(PVW_ERR_INVALID_PARAMETERS, "party index must be below plain_modulus - 1");
+    }
+  }
+  std::vector<u64> wts(count * 4);
+  for (size_t i = 0; i < count; ++i) {
+    Wide num, den, one, f;
+    wide_small(one, 1);
+    wide_reduce(num, one, m);
+    wide_set(den, num);
+    bool neg = false;
+    for (size_t j = 0; j < count; ++j) {
+      if (j == i) continue;
+      const u64 xj = indices[j] + 1, xi = indices[i] + 1;
+      wide_small(f, xj);
+      wide_mulmod(num, num, f, m);
+      wide_small(f, xj > xi ? xj - xi : xi - xj);
+      if (xj < xi) neg = !neg;
+      wide_mulmod(den, den, f, m);
+    }
+    Wide inv, plain;
+    wide_invmod(inv, den, plain_modulus, m);
+    wide_unscale(plain, inv, m);
+    wide_mulmod(num, num, plain, m);
+    if (neg) wide_negmod(num, m);
+    wide_unscale(&wts[i * 4], num, m);                     // the weight, plain and below p
+  }
+  for (size_t s = 0; s < num_secrets; ++s) {
+    Wide acc, y, prod;
+    wide_small(acc, 0);
+    for (size_t i = 0; i < count; ++i) {
+      wide_reduce(y, shares + (s * count + i) * 4, m);
+      wide_mulmod(prod, y, &wts[i * 4], m);
+      wide_addmod(acc, prod, m);
+    }
+    wide_unscale(out + s * 4, acc, m);
+  }
+  volatile u64* vw = wts.data();
+  for (size_t j = 0; j < wts.size(); ++j) vw[j] = 0;
+  return PVW_OK;
+}
+
+// the front of the two device-side shares calls
+static int32_t shamir_wide_shares_checks(const pvw_ctx* c, const uint64_t* secrets, size_t D, uint32_t degree, const uint64_t* p,
+                                         const uint8_t* seeds, const uint64_t* coeffs, const uint64_t* shares, WideMod* m) {
+  if (!c || !secrets || !shares || !p || (degree && !seeds && !coeffs)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  return shamir_wide_checks(c, D, degree, p, m);
+}
+
+// device pointers (seeds and plain_modulus stay HOST pointers): no workspace, nothing allocated, may be captured
+int32_t pvw_shamir_shares_wide_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t degree,
+                                      const uint64_t* plain_modulus, const uint8_t* seeds, const uint64_t* d_coeffs, uint64_t* d_shares,
+                                      void* stream) {
+  WideMod m;
+  PVW_TRY(shamir_wide_shares_checks(c, d_secrets, num_dealers, degree, plain_modulus, seeds, d_coeffs, d_shares, &m));
+  PVW_TRY(ensure_device(c));
+  const ShamirWideDeal deal{d_secrets, degree ? d_coeffs : nullptr, degree, m};
+  return shamir_wide_enqueue(c, deal, DealerKeys::host(seeds), 0, num_dealers, d_shares, call_stream(c, stream));
+}
+
+// host buffers: the dealers go up in bounded pieces, each piece's shares come down, and the staging is cleared when the call ends
+int32_t pvw_shamir_shares_wide(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t degree, const uint64_t* plain_modulus,
+                               const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out) {
+  WideMod m;
+  PVW_TRY(shamir_wide_shares_checks(c, secrets, num_dealers, degree, plain_modulus, seeds, coeffs, shares_out, &m));
+  PVW_TRY(ensure_device(c));
+  const size_t n = c->n, t = degree, rB = c->rowsB();
+  const size_t per = chunk_1gib((n + (coeffs ? t : 0) + 1) * 32, num_dealers);
+  Scratch sc;
+  const size_t r_se = sc.add(per * 32), r_co = sc.add(coeffs ? per * t * 32 : 0), r_sh = sc.add(per * n * 32);
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    sc.secret(w, r_se, r_sh);
+    u64 *d_se = sc.at(r_se), *d_co = coeffs && t ? sc.at(r_co) : nullptr, *d_sh = sc.at(r_sh);
+    const ShamirWideDeal deal{d_se, d_co, degree, m};
+    for (size_t d0 = 0; d0 < num_dealers; d0 += per) {
+      const size_t cnt = (num_dealers - d0) < per ? (num_dealers - d0) : per;
+      PVW_HIP(hipMemcpyAsync(d_se, secrets + d0 * 4, cnt * 32, hipMemcpyHostToDevice, w->stream));
+      if (d_co) PVW_HIP(hipMemcpyAsync(d_co, coeffs + d0 * t * 4, cnt * t * 32, hipMemcpyHostToDevice, w->stream));
+      PVW_TRY(shamir_wide_enqueue(c, deal, DealerKeys::host(seeds).from(d0), 0, cnt, d_sh, w->stream));
+      // a sharded context writes its own columns only
+      if (rB) PVW_HIP(hipMemcpy2DAsync(shares_out + (d0 * n + c->party_lo) * 4, n * 32, d_sh + (size_t)c->party_lo * 4, n * 32, rB * 32, cnt,
+                                       hipMemcpyDeviceToHost, w->stream));
+      PVW_HIP(hipStreamSynchronize(w->stream));                // the next piece reuses the staging
+    }
+    return PVW_OK;
+  });
+}
+
+// The deal: pvw_encrypt_multi* on D * NL vectors whose scalars are the limb planes, made pass by pass in the share scratch.
+static int32_t deal_wide_front(pvw_ctx* c, const uint64_t* secrets, size_t D, uint32_t degree, const uint64_t* p, uint32_t limb_bits,
+                               const DealerKeys& keys, const uint64_t* c1, const uint64_t* c2, bool device, uint32_t out_repr,
+                               ShamirWideDeal* deal) {
+  if (!c || !secrets || !p || keys.missing() || (device ? (!c1 && c->rowsA()) || (!c2 && c->rowsB()) : !c1 || !c2))
+    return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(encrypt_multi_checks(c, D, c->n, out_repr));
+  WideMod m;
+  PVW_TRY(shamir_wide_checks(c, D, degree, p, &m));
+  u32 nl = 0;
+  PVW_TRY(wide_limb_count(m, limb_bits, &nl));
+  *deal = ShamirWideDeal{secrets, nullptr, degree, m, limb_bits, nl};
+  return PVW_OK;
+}
+static int32_t deal_wide_device(pvw_ctx* c, const uint64_t* d_secrets, size_t D, uint32_t degree, const uint64_t* p, uint32_t limb_bits,
+                                const DealerKeys& keys, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
+  ShamirWideDeal wd;
+  PVW_TRY(deal_wide_front(c, d_secrets, D, degree, p, limb_bits, keys, d_c1, d_c2, true, out_repr, &wd));
+  ShamirDeal deal{nullptr, nullptr, degree, Mod{}, 0};
+  deal.wide = &wd;
+  const size_t V = D * wd.num_limbs;
+  return device_call(c, stream, [&](hipStream_t s) -> int32_t {
+                       PVW_TRY(keys.checks(c));
+                       return deal_capture_check(c, s, V);
+                     },
+                     [&](Workspace* w, hipStream_t s) -> int32_t {
+                       PVW_TRY(ws_share_buffer(c, w));
+                       deal_mark(w, V);
+                       return encrypt_multi_enqueue(c, w, nullptr, keys, V, d_c1, d_c2, out_repr, s, &deal);
+                     });
+}
+// host buffers, staged in pieces of whole dealers (<= ~512 MiB of ciphertext), so that every piece starts on a dealer's first
+// vector and its keys are the piece's own
+static int32_t deal_wide_host(pvw_ctx* c, const uint64_t* secrets, size_t D, uint32_t degree, const uint64_t* p, uint32_t limb_bits,
+                              const DealerKeys& keys, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+  ShamirWideDeal wd;
+  PVW_TRY(deal_wide_front(c, secrets, D, degree, p, limb_bits, keys, c1_out, c2_out, false, out_repr, &wd));
+  PVW_TRY(ensure_device(c));
+  PVW_TRY(keys.checks(c));
+  const size_t P = c->poly(), rA = c->rowsA(), rB = c->rowsB(), n = c->n, NL = wd.num_limbs;
+  size_t per = stage_budget() / 2 / (NL * (rA + rB) * P * 8 + 32);
+  if (per < 1) per = 1;
+  if (per > D) per = D;
+  Scratch sc;
+  const size_t r_in = sc.add(per * 32), r_c1 = sc.add(per * NL * rA * P * 8), r_c2 = sc.add(per * NL * rB * P * 8);
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    PVW_TRY(ws_share_buffer(c, w));
+    sc.secret(w, r_in, r_in);
+    deal_mark(w, per * NL);
+    if (D % per) deal_mark(w, (D % per) * NL);
+    u64 *d_in = sc.at(r_in), *d_c1 = sc.at(r_c1), *d_c2 = sc.at(r_c2);
+    wd.d_secrets = d_in;
+    ShamirDeal deal{nullptr, nullptr, degree, Mod{}, 0};
+    deal.wide = &wd;
+    for (size_t d0 = 0; d0 < D; d0 += per) {
+      const size_t cnt = (D - d0) < per ? (D - d0) : per, nvec = cnt * NL;
+      PVW_HIP(hipMemcpyAsync(d_in, secrets + d0 * 4, cnt * 32, hipMemcpyHostToDevice, w->stream));
+      PVW_TRY(encrypt_multi_enqueue(c, w, nullptr, keys.piece(d0 * NL), nvec, d_c1, d_c2, out_repr, w->stream, &deal));
+      for (size_t v = 0; v < nvec; ++v) {
+        // a sharded context writes its rows at their global positions inside each vector's block
+        PVW_HIP(hipMemcpyAsync(c1_out + ((d0 * NL + v) * c->k + c->c1_lo) * P, d_c1 + v * rA * P, rA * P * 8, hipMemcpyDeviceToHost, w->stream));
+        PVW_HIP(hipMemcpyAsync(c2_out + ((d0 * NL + v) * n + c->party_lo) * P, d_c2 + v * rB * P, rB * P * 8, hipMemcpyDeviceToHost, w->stream));
+      }
+      if (d0 + cnt < D) PVW_HIP(hipStreamSynchronize(w->stream));   // the next piece reuses the pageable staging
+    }
+    return PVW_OK;
+  });
+}
+
+int32_t pvw_deal_shares_wide(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t degree, const uint64_t* plain_modulus,
+                             uint32_t limb_bits, const uint8_t* seeds, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+  return deal_wide_host(c, secrets, num_dealers, degree, plain_modulus, limb_bits, DealerKeys::host(seeds), c1_out, c2_out, out_repr);
+}
+int32_t pvw_deal_shares_wide_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t degree,
+                                    const uint64_t* plain_modulus, uint32_t limb_bits, const uint8_t* seeds, uint64_t* d_c1, uint64_t* d_c2,
+                                    uint32_t out_repr, void* stream) {
+  return deal_wide_device(c, d_secrets, num_dealers, degree, plain_modulus, limb_bits, DealerKeys::host(seeds), d_c1, d_c2, out_repr, stream);
+}
+int32_t pvw_deal_shares_wide_rs(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t degree, const uint64_t* plain_modulus,
+                                uint32_t limb_bits, void* handle, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+  return deal_wide_host(c, secrets, num_dealers, degree, plain_modulus, limb_bits, DealerKeys::state(handle), c1_out, c2_out, out_repr);
+}
+int32_t pvw_deal_shares_wide_rs_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t degree,
+                                       const uint64_t* plain_modulus, uint32_t limb_bits, void* handle, uint64_t* d_c1, uint64_t* d_c2,
+                                       uint32_t out_repr, void* stream) {
+  return deal_wide_device(c, d_secrets, num_dealers, degree, plain_modulus, limb_bits, DealerKeys::state(handle), d_c1, d_c2, out_repr, stream);
+}
+
+// SELF-TEST: the kernel's Horner step on the device, out = (acc x + add) mod p
+int32_t pvw_selftest_shamir_wide_step(pvw_ctx* c, const uint64_t* plain_modulus, const uint64_t* acc, const uint64_t* x, const uint64_t* add,
+                                      size_t count, uint64_t* out) {
+  if (!c || !plain_modulus || ((!acc || !x || !add || !out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  WideMod m;
+  PVW_TRY(wide_modulus_check(plain_modulus, &m));
+  for (size_t i = 0; i < count; ++i) {
+    u64 a[4], b[4], pp[4];
+    wide_set(a, acc + i * 4);
+    wide_set(b, add + i * 4);
+    wide_set(pp, plain_modulus);
+    if (x[i] >> 32 || !wide_less(a, pp) || !wide_less(b, pp))
+      return fail(PVW_ERR_INVALID_PARAMETERS, "the step takes acc, add below plain_modulus and x below 2^32");
+  }
+  if (!count) return PVW_OK;
+  PVW_TRY(ensure_device(c));
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(ws_scratch(w, count * 104));
+    u64* base = (u64*)w->scratch;
+    u64 *d_acc = base, *d_add = base + count * 4, *d_out = base + count * 8, *d_x = base + count * 12;
+    PVW_HIP(hipMemcpyAsync(d_acc, acc, count * 32, hipMemcpyHostToDevice, w->stream));
+    PVW_HIP(hipMemcpyAsync(d_add, add, count * 32, hipMemcpyHostToDevice, w->stream));
+    PVW_HIP(hipMemcpyAsync(d_x, x, count * 8, hipMemcpyHostToDevice, w->stream));
+    PVW_HIP(launch_shamir_wide_step(m, d_acc, d_x, d_add, count, d_out, w->stream));
+    PVW_HIP(hipMemcpyAsync(out, d_out, count * 32, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
 }
 
 // ------------------------------------------------------------------------ device randomness state

@@ -5,6 +5,7 @@
 #include "pvw_arith.h"
 #include "pvw_chacha.h"
 #include "pvw_decode.h"
+#include "pvw_wide.h"
 
 // PVW_TUNING selects the MEASUREMENT build (libpvw_hip_tuning.so, pvw_rs_amd/build.py): only there are the
 // timing switches (PVW_DECODE_TIMING, PVW_GEMM_ZERO_OPERANDS), the schedule selectors (PVW_MAC_VARIANT, PVW_MAC_PACKED,
@@ -264,6 +265,29 @@ struct ShamirBatch {
 };
 hipError_t launch_shamir_packed_weights(u64* ws, u32 pack, u32 party_lo, u32 party_hi, const Mod& m, hipStream_t s);
 hipError_t launch_shamir_eval(const ShamirBatch& b, hipStream_t s);
+
+// ---- Shamir shares over a prime below 2^256 (pvw_shamir.hip): elements of four words, pvw_wide.h.
+// Dealers [d_lo, d_lo + nd) of the arrays; dealer d's key is key[d - d_lo], or with rnd != NULL
+// call_seed(S, counter + rnd_off + (d - d_lo) * key_stride).
+// num_limbs == 0: the shares themselves, out[(d * row_stride + party) * 4 + word].
+// num_limbs >= 1: limb w of dealer d is row v = d * num_limbs + w; the rows of [v0, v0 + nv) are stored, row v at
+// out[(v - v0) * row_stride + party], and nothing else is written.
+struct ShamirWideBatch {
+  const u64* secrets;   // [*][4] device words, read mod p
+  const u64* coeffs;    // [*][degree][4] device words, or NULL: drawn
+  u64* out;
+  size_t row_stride;
+  u32 d_lo, nd, degree, party_lo, party_hi;
+  u32 limb_bits, num_limbs, v0, nv;
+  WideMod m;
+  ChaChaKey key[PVW_MAX_PROLOGUE_KEYS];
+  const RndState* rnd;
+  u64 rnd_off;
+  u32 key_stride;
+};
+hipError_t launch_shamir_eval_wide(const ShamirWideBatch& b, hipStream_t s);
+// out[i] = (acc[i] x[i] + add[i]) mod p by the kernel's own step; acc, add < p, x < 2^32 (pvw_selftest_shamir_wide_step)
+hipError_t launch_shamir_wide_step(const WideMod& m, const u64* acc, const u64* x, const u64* add, size_t count, u64* out, hipStream_t s);
 
 // ---- Checked reconstruction (pvw_shamir.hip).  Columns 0..t of the share matrix are the basis, columns
 // t+1..count-1 the extras; T = count - t targets: target 0 is x = 0, target m >= 1 the point of column t + m.

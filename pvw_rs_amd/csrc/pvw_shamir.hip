@@ -1065,4 +1065,111 @@ hipError_t launch_shamir_packed_weights(u64* ws, u32 pack, u32 party_lo, u32 par
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------ shares over a prime below 2^256
+// shares[d][i] = f_d(i + 1) mod p with elements of four words (pvw_wide.h).  The point x = i + 1 is below 2^32, so the
+// polynomial is walked by Horner from the top coefficient, acc <- acc x + a_e for e = t .. 0 (a_0 the secret): one wide_step
+// per term, 8 + 8 v_mad_u64_u32 and one correction, where a power-and-product walk would pay a general 256 x 256-bit product.
+// A lane owns one party of one dealer; the 256 lanes of a workgroup own 256 parties and walk ALL t + 1 terms -- no term split:
+// partial sums of a split would have to be multiplied by a power of x at the meet, which is the general product again.
+// Coefficients are uniform across the workgroup: each chunk of SHW_JC terms is made in LDS, one lane per coefficient (drawn
+// from the dealer's key, or an input word reduced), scaled and below pn, and read back as broadcasts; every workgroup of a
+// dealer repeats the draw for its 256 parties (one ChaCha8 block or so per lane against 256 steps per lane).  Nothing but
+// the result reaches memory: the share's four words, or its limbs as rows of the pass's scratch.
+#define SHW_JC 256   // terms per staging chunk: one per lane
+
+// grid: x = blocks of 256 parties of [party_lo, party_hi), y = the launch's dealers; 256 threads.
+__global__ __launch_bounds__(256) void shamir_eval_wide_kernel(ShamirWideBatch b) {
+  __shared__ u64 coef[SHW_JC][4];                  // 8 KiB: the chunk's coefficients, scaled, below pn
+  __shared__ u32 keyw[8];
+  const u32 tid = threadIdx.x;
+  const WideMod m = b.m;
+  const u32 t = b.degree, nt = t + 1;
+  const u32 dx = blockIdx.y, d = b.d_lo + dx;
+  const u32 col = blockIdx.x * 256 + tid;
+  const u32 party = b.party_lo + col;
+  const bool live = col < b.party_hi - b.party_lo;
+  const bool drawn = b.coeffs == nullptr && t != 0;
+  if (drawn && tid == 0) {
+    ChaChaKey k;
+    if (b.rnd) k = call_seed(b.rnd->seed, b.rnd->counter + b.rnd_off + (u64)dx * b.key_stride);   // derived when the kernel runs
+    else k = b.key[dx];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) keyw[i] = k.w[i];
+  }
+  __syncthreads();
+  const u32 x = live ? party + 1 : 1;              // x <= n < 2^32
+  u64 acc[4] = {0, 0, 0, 0};
+  const u32 nchunks = (nt + SHW_JC - 1) / SHW_JC;
+  for (u32 c = 0; c < nchunks; ++c) {
+    // ---- staging: slot tid holds term e = t - c * SHW_JC - tid, the terms in the order Horner takes them ----
+    const u32 first = c * SHW_JC;                  // terms taken before this chunk
+    u64 a[4] = {0, 0, 0, 0};
+    if (first + tid < nt) {
+      const u32 e = t - first - tid;
+      if (e == 0) {
+        wide_reduce_scaled(b.secrets + (size_t)d * 4, m, a);
+      } else if (drawn) {
+        ChaChaKey k;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) k.w[i] = keyw[i];
+        wide_draw_scaled(k, DOM_SHAMIR, e, m, a);
+      } else {
+        wide_reduce_scaled(b.coeffs + ((size_t)d * t + (e - 1)) * 4, m, a);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) coef[tid][i] = a[i];
+    __syncthreads();
+    const u32 cnt = nt - first < SHW_JC ? nt - first : SHW_JC;
+    for (u32 jj = 0; jj < cnt; ++jj) {
+      u64 v[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = coef[jj][i];
+      wide_step(acc, x, v, m);
+    }
+    __syncthreads();
+  }
+  if (!live) return;
+  wide_shr(acc, m.shift);                          // the share, below p
+  if (b.num_limbs == 0) {
+    u64* o = b.out + ((size_t)d * b.row_stride + party) * 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = acc[i];
+    return;
+  }
+  const u64 mask = ((u64)1 << b.limb_bits) - 1;
+  for (u32 w = 0; w < b.num_limbs; ++w) {
+    const u64 v = (u64)d * b.num_limbs + w;
+    if (v >= b.v0 && v < (u64)b.v0 + b.nv) b.out[(size_t)(v - b.v0) * b.row_stride + party] = acc[0] & mask;
+    wide_shr(acc, b.limb_bits);                    // limb_bits < 64
+  }
+}
+
+hipError_t launch_shamir_eval_wide(const ShamirWideBatch& b, hipStream_t s) {
+  if (b.nd == 0 || b.party_hi <= b.party_lo) return hipSuccess;
+  shamir_eval_wide_kernel<<<dim3((b.party_hi - b.party_lo + 255) / 256, b.nd), dim3(256), 0, s>>>(b);
+  return hipGetLastError();
+}
+
+// the step alone on operands of the caller's, scaled on the way in and back on the way out
+__global__ __launch_bounds__(256) void shamir_wide_step_kernel(WideMod m, const u64* acc, const u64* x, const u64* add, size_t count,
+                                                               u64* out) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  u64 a[4], v[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { a[k] = acc[i * 4 + k]; v[k] = add[i * 4 + k]; }
+  wide_shl(a, m.shift);
+  wide_shl(v, m.shift);
+  wide_step(a, (u32)x[i], v, m);
+  wide_shr(a, m.shift);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) out[i * 4 + k] = a[k];
+}
+hipError_t launch_shamir_wide_step(const WideMod& m, const u64* acc, const u64* x, const u64* add, size_t count, u64* out, hipStream_t s) {
+  if (!count) return hipSuccess;
+  shamir_wide_step_kernel<<<dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s>>>(m, acc, x, add, count, out);
+  return hipGetLastError();
+}
+
 }  // namespace pvw

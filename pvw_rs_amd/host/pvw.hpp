@@ -710,6 +710,84 @@ inline std::vector<uint64_t> shamir_reconstruct(const std::vector<uint64_t>& ind
   check(pvw_shamir_reconstruct(plain_modulus, indices.data(), shares.data(), indices.size(), out.size(), out.data()));
   return out;
 }
+// ---- Shamir shares over a prime below 2^256.  A wide element is four little-endian words; vectors of them are
+// flat, four words per element.
+using Wide = std::array<uint64_t, PVW_WIDE_WORDS>;
+inline uint32_t shamir_wide_limbs(const Wide& plain_modulus, uint32_t limb_bits = 52) {
+  uint32_t nl = 0;
+  check(pvw_shamir_wide_limbs(plain_modulus.data(), limb_bits, &nl));
+  return nl;
+}
+// shares [D][n][4] of secrets [D][4]; coefficients drawn from seeds[d] or given as coeffs [D][degree][4].  On the device
+// (pvw_shamir_shares_wide); host = true: the restatement on the host cores (pvw_shamir_shares_wide_host, no GPU).
+inline std::vector<uint64_t> shamir_shares_wide(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& secrets, uint32_t degree,
+                                                const Wide& plain_modulus, const std::vector<Seed>& seeds,
+                                                const std::vector<uint64_t>& coeffs = {}, bool host = false) {
+  if (secrets.size() % PVW_WIDE_WORDS) throw PvwError(15, "four words per secret");
+  const size_t D = secrets.size() / PVW_WIDE_WORDS;
+  if (!seeds.empty() && seeds.size() != D) throw PvwError(15, "one seed per dealer");
+  if (!coeffs.empty() && coeffs.size() != D * degree * PVW_WIDE_WORDS) throw PvwError(15, "degree coefficients per dealer");
+  const std::vector<uint8_t> sd = seed_bytes(seeds);
+  std::vector<uint64_t> out(D * p->n * PVW_WIDE_WORDS);
+  const uint8_t* sdp = sd.empty() ? nullptr : sd.data();
+  const uint64_t* cop = coeffs.empty() ? nullptr : coeffs.data();
+  check(host ? pvw_shamir_shares_wide_host(p->ctx, secrets.data(), D, degree, plain_modulus.data(), sdp, cop, out.data())
+             : pvw_shamir_shares_wide(p->ctx, secrets.data(), D, degree, plain_modulus.data(), sdp, cop, out.data()));
+  return out;
+}
+inline std::vector<PvwCiphertext> deal_wide_call(const std::vector<uint64_t>& secrets, uint32_t degree, const Wide& plain_modulus,
+                                                 const GlobalPublicKey& gpk, const std::vector<Seed>* seeds, DeviceRandomness* rnd,
+                                                 uint32_t limb_bits, uint32_t out_repr) {
+  if (secrets.size() % PVW_WIDE_WORDS) throw PvwError(15, "four words per secret");
+  const size_t D = secrets.size() / PVW_WIDE_WORDS, V = D * shamir_wide_limbs(plain_modulus, limb_bits);
+  const auto& p = gpk.params;
+  const size_t P = p->poly_words();
+  if (seeds && seeds->size() != V) throw PvwError(15, "one seed per limb ciphertext");
+  const std::vector<uint8_t> sd = seeds ? seed_bytes(*seeds) : std::vector<uint8_t>();
+  std::vector<uint64_t> c1(V * p->k * P), c2(V * p->n * P);
+  if (seeds)
+    check(pvw_deal_shares_wide(p->ctx, secrets.data(), D, degree, plain_modulus.data(), limb_bits, sd.data(), c1.data(), c2.data(), out_repr));
+  else
+    check(pvw_deal_shares_wide_rs(p->ctx, secrets.data(), D, degree, plain_modulus.data(), limb_bits, rnd->raw(), c1.data(), c2.data(), out_repr));
+  return deal_ciphertexts(p, c1, c2, V, out_repr);
+}
+// dealer d shares secrets[d] and encrypts the shares limb by limb in ONE device call (pvw_deal_shares_wide): D * NL ciphertexts,
+// ciphertext d * NL + w carrying limb w of dealer d's shares; seeds: one per ciphertext, dealer d draws under seeds[d * NL]
+inline std::vector<PvwCiphertext> deal_party_shares_wide(const std::vector<uint64_t>& secrets, uint32_t degree, const Wide& plain_modulus,
+                                                         const GlobalPublicKey& gpk, const std::vector<Seed>& seeds, uint32_t limb_bits = 52,
+                                                         uint32_t out_repr = PVW_REPR_NTT) {
+  return deal_wide_call(secrets, degree, plain_modulus, gpk, &seeds, nullptr, limb_bits, out_repr);
+}
+// ... with vector v's randomness from call_seed(S, c + v) of a DeviceRandomness, which then holds c + D * NL
+inline std::vector<PvwCiphertext> deal_party_shares_wide(const std::vector<uint64_t>& secrets, uint32_t degree, const Wide& plain_modulus,
+                                                         const GlobalPublicKey& gpk, DeviceRandomness& rnd, uint32_t limb_bits = 52,
+                                                         uint32_t out_repr = PVW_REPR_NTT) {
+  return deal_wide_call(secrets, degree, plain_modulus, gpk, nullptr, &rnd, limb_bits, out_repr);
+}
+// values [count][4] -> limbs [num_limbs][count], and back mod p (each input word any uint64_t: a limb or a sum of limbs)
+inline std::vector<uint64_t> shamir_wide_to_limbs(const std::vector<uint64_t>& values, uint32_t limb_bits, uint32_t num_limbs) {
+  const size_t count = values.size() / PVW_WIDE_WORDS;
+  std::vector<uint64_t> out(count * num_limbs);
+  check(pvw_shamir_wide_to_limbs_host(values.data(), count, limb_bits, num_limbs, out.data()));
+  return out;
+}
+inline std::vector<uint64_t> shamir_wide_from_limbs(const Wide& plain_modulus, const std::vector<uint64_t>& limbs, uint32_t limb_bits,
+                                                    uint32_t num_limbs) {
+  if (!num_limbs || limbs.size() % num_limbs) throw PvwError(15, "limbs must hold num_limbs rows");
+  const size_t count = limbs.size() / num_limbs;
+  std::vector<uint64_t> out(count * PVW_WIDE_WORDS);
+  check(pvw_shamir_wide_from_limbs_host(plain_modulus.data(), limbs.data(), count, limb_bits, num_limbs, out.data()));
+  return out;
+}
+// the secrets [num_secrets][4] from shares [num_secrets][indices.size()][4] of the parties `indices` (at least degree + 1)
+inline std::vector<uint64_t> shamir_reconstruct_wide(const std::vector<uint64_t>& indices, const std::vector<uint64_t>& shares,
+                                                     const Wide& plain_modulus) {
+  if (indices.empty() || shares.size() % (indices.size() * PVW_WIDE_WORDS)) throw PvwError(15, "shares must hold one element per index and secret");
+  const size_t S = shares.size() / (indices.size() * PVW_WIDE_WORDS);
+  std::vector<uint64_t> out(S * PVW_WIDE_WORDS);
+  check(pvw_shamir_reconstruct_wide(plain_modulus.data(), indices.data(), shares.data(), indices.size(), S, out.data()));
+  return out;
+}
 // the share matrix of the checked, corrected and evaluate calls: its shape and the strides of its layout, in words
 struct ShareMatrix {
   size_t count, S, words, ss, ps;   // columns, secrets, mask words per secret, secret stride, point stride

@@ -582,6 +582,100 @@ pub fn shamir_reconstruct(indices: &[u64], shares: &[u64], plain_modulus: u64) -
     Ok(out)
 }
 
+/// EXTENSION: a field element of up to 256 bits, four little-endian words.
+pub type Wide = [u64; 4];
+
+/// EXTENSION: the limb ciphertexts per dealer of `deal_party_shares_wide` (`pvw_shamir_wide_limbs`).
+pub fn shamir_wide_limbs(plain_modulus: &Wide, limb_bits: u32) -> Result<u32> {
+    let mut nl = 0u32;
+    check(unsafe { sys::pvw_shamir_wide_limbs(plain_modulus.as_ptr(), limb_bits, &mut nl) })?;
+    Ok(nl)
+}
+
+/// EXTENSION: the shares `[dealers][n][4]` over an odd prime below 2^256, made on the device
+/// (`pvw_shamir_shares_wide`) from one 32-byte seed per dealer or from explicit coefficients `[dealers][degree][4]`.
+pub fn shamir_shares_wide(params: &Arc<PvwParameters>, secrets: &[Wide], degree: u32, plain_modulus: &Wide, seeds: Option<&[u8]>, coeffs: Option<&[Wide]>) -> Result<Vec<Wide>> {
+    let mut out = vec![[0u64; 4]; secrets.len() * params.n];
+    check(unsafe {
+        sys::pvw_shamir_shares_wide(params.hip.raw(), secrets.as_ptr() as *const u64, secrets.len(), degree, plain_modulus.as_ptr(),
+                                    seeds.map_or(std::ptr::null(), |s| s.as_ptr()), coeffs.map_or(std::ptr::null(), |c| c.as_ptr() as *const u64),
+                                    out.as_mut_ptr() as *mut u64)
+    })?;
+    Ok(out)
+}
+
+fn wide_ciphertexts(c1: &[u64], c2: &[u64], vectors: usize, params: &Arc<PvwParameters>) -> Result<Vec<PvwCiphertext>> {
+    let (n, words) = (params.n, poly_words(params));
+    (0..vectors)
+        .map(|v| ciphertext_from_flat(&c1[v * params.k * words..(v + 1) * params.k * words], &c2[v * n * words..(v + 1) * n * words], params))
+        .collect()
+}
+
+/// EXTENSION: dealer d shares `secrets[d]` over the field of `plain_modulus` and encrypts the shares limb by limb
+/// in ONE device call (`pvw_deal_shares_wide`): `dealers * NL` ciphertexts, ciphertext `d * NL + w` carrying limb w of dealer
+/// d's shares.  One seed per ciphertext comes from `thread_rng` and is cleared afterwards.
+pub fn deal_party_shares_wide(secrets: &[Wide], degree: u32, plain_modulus: &Wide, limb_bits: u32, global_pk: &GlobalPublicKey) -> Result<Vec<PvwCiphertext>> {
+    let params = &global_pk.params;
+    let vectors = secrets.len() * shamir_wide_limbs(plain_modulus, limb_bits)? as usize;
+    let words = poly_words(params);
+    let mut seeds = vec![0u8; 32 * vectors];
+    rand::thread_rng().fill_bytes(&mut seeds);
+    let (mut c1, mut c2) = (vec![0u64; vectors * params.k * words], vec![0u64; vectors * params.n * words]);
+    let rc = unsafe {
+        sys::pvw_deal_shares_wide(params.hip.raw(), secrets.as_ptr() as *const u64, secrets.len(), degree, plain_modulus.as_ptr(), limb_bits,
+                                  seeds.as_ptr(), c1.as_mut_ptr(), c2.as_mut_ptr(), sys::PVW_REPR_POWER)
+    };
+    seeds.zeroize();
+    check(rc)?;
+    wide_ciphertexts(&c1, &c2, vectors, params)
+}
+
+/// `deal_party_shares_wide` with vector v's randomness drawn from a `DeviceRandomness` (`call_seed(S, c + v)`).
+pub fn deal_party_shares_wide_with(secrets: &[Wide], degree: u32, plain_modulus: &Wide, limb_bits: u32, global_pk: &GlobalPublicKey, rnd: &DeviceRandomness) -> Result<Vec<PvwCiphertext>> {
+    let params = &global_pk.params;
+    let vectors = secrets.len() * shamir_wide_limbs(plain_modulus, limb_bits)? as usize;
+    let words = poly_words(params);
+    let (mut c1, mut c2) = (vec![0u64; vectors * params.k * words], vec![0u64; vectors * params.n * words]);
+    check(unsafe {
+        sys::pvw_deal_shares_wide_rs(params.hip.raw(), secrets.as_ptr() as *const u64, secrets.len(), degree, plain_modulus.as_ptr(), limb_bits,
+                                     rnd.raw(), c1.as_mut_ptr(), c2.as_mut_ptr(), sys::PVW_REPR_POWER)
+    })?;
+    wide_ciphertexts(&c1, &c2, vectors, params)
+}
+
+/// EXTENSION: `values` -> limbs `[num_limbs][values.len()]` (`pvw_shamir_wide_to_limbs_host`).
+pub fn shamir_wide_to_limbs(values: &[Wide], limb_bits: u32, num_limbs: u32) -> Result<Vec<u64>> {
+    let mut out = vec![0u64; values.len() * num_limbs as usize];
+    check(unsafe { sys::pvw_shamir_wide_to_limbs_host(values.as_ptr() as *const u64, values.len(), limb_bits, num_limbs, out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// EXTENSION: limbs `[num_limbs][count]`, each any word (a limb or a sum of limbs), folded back mod p
+/// (`pvw_shamir_wide_from_limbs_host`).
+pub fn shamir_wide_from_limbs(plain_modulus: &Wide, limbs: &[u64], limb_bits: u32, num_limbs: u32) -> Result<Vec<Wide>> {
+    if num_limbs == 0 || limbs.len() % num_limbs as usize != 0 {
+        return Err(PvwError::InvalidParameters("limbs must hold num_limbs rows".into()));
+    }
+    let count = limbs.len() / num_limbs as usize;
+    let mut out = vec![[0u64; 4]; count];
+    check(unsafe { sys::pvw_shamir_wide_from_limbs_host(plain_modulus.as_ptr(), limbs.as_ptr(), count, limb_bits, num_limbs, out.as_mut_ptr() as *mut u64) })?;
+    Ok(out)
+}
+
+/// EXTENSION: the secrets from the shares `[num_secrets][indices.len()]` of the parties `indices` (at least
+/// degree + 1 of them).  Host only (`pvw_shamir_reconstruct_wide`).
+pub fn shamir_reconstruct_wide(indices: &[u64], shares: &[Wide], plain_modulus: &Wide) -> Result<Vec<Wide>> {
+    if indices.is_empty() || shares.len() % indices.len() != 0 {
+        return Err(PvwError::InvalidParameters("shares must hold one element per index and secret".into()));
+    }
+    let mut out = vec![[0u64; 4]; shares.len() / indices.len()];
+    check(unsafe {
+        sys::pvw_shamir_reconstruct_wide(plain_modulus.as_ptr(), indices.as_ptr(), shares.as_ptr() as *const u64, indices.len(), out.len(),
+                                         out.as_mut_ptr() as *mut u64)
+    })?;
+    Ok(out)
+}
+
 /// The share matrix of the checked, corrected and evaluate calls: (columns, secrets, secret stride, point stride), in words.
 fn share_matrix(indices: &[u64], shares: &[u64], party_major: bool) -> Result<(usize, usize, usize, usize)> {
     if indices.is_empty() || shares.is_empty() || shares.len() % indices.len() != 0 {
