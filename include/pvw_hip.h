@@ -1056,6 +1056,54 @@ PVW_API int32_t pvw_shamir_reconstruct_wide(const uint64_t* plain_modulus, const
 PVW_API int32_t pvw_selftest_shamir_wide_step(pvw_ctx* ctx, const uint64_t* plain_modulus, const uint64_t* acc, const uint64_t* x,
                                               const uint64_t* add, size_t count, uint64_t* out);
 
+/* ---- The receiving end over a prime field of up to 256 bits: the fold of decrypted limbs on the device, and
+ * checked reconstruction with wide elements.  The contract is the library's own.  plain_modulus is a HOST pointer to an odd
+ * prime below 2^256 in every form, checked as above.
+ * Fold: out[i] = sum_w limbs[w * limb_stride + i * elem_stride] 2^(w limb_bits) mod p for i < count, out [count][4]; each input
+ *   word is ANY uint64_t, a limb or a sum of limbs.  Strides (count, 1) read the planes of pvw_shamir_wide_from_limbs_host;
+ *   strides (1, NL) read the [party][dealer NL + w] result of pvw_decrypt_all* in place, as P D elements in [party][dealer]
+ *   order.  Device pointers, asynchronous on `stream`, allocates nothing, may be captured; bit-equal to the host form.
+ *   PVW_ERR_INVALID_PARAMETERS before any device work: what pvw_shamir_wide_from_limbs_host refuses, a NULL ctx, a stride of 0. */
+PVW_API int32_t pvw_shamir_wide_from_limbs_device(pvw_ctx* ctx, const uint64_t* plain_modulus, const uint64_t* d_limbs, size_t count,
+                                                  size_t limb_stride, size_t elem_stride, uint32_t limb_bits, uint32_t num_limbs,
+                                                  uint64_t* d_out, void* stream);
+/* Checked reconstruction: the contract of pvw_shamir_reconstruct_checked*  word for word, with wide elements.
+ *   degree = t.  indices [count]: distinct global party indices, a HOST pointer in every form; the points are the INTEGERS
+ *   x_c = indices[c] + 1, each below p (an index of 2^64 - 1 is legal when p > 2^64 + 1).  shares: num_secrets rows, element
+ *   (s, c) is the four words at shares + 4 (s * secret_stride + c * point_stride) (strides in elements; any words, read mod p):
+ *   strides (count, 1) read [secret][party][4], strides (1, D) the fold's [party][dealer][4] output in place, every dealer a
+ *   secret.  Basis: columns 0..t in the caller's order; extras: columns t+1..count-1.  F_s: the polynomial of degree <= t
+ *   through the basis points of secret s.
+ *   out [num_secrets][4] = F_s(0).  bad [num_secrets] (or NULL): how many extras c have share(s, c) mod p != F_s(x_c).
+ *   col_bad [count] (or NULL): for each column, how many secrets deviate there; 0 for the basis columns.
+ *   One wrong extra share is flagged at exactly that (s, c) and out is right; one wrong basis share of secret s makes out[s]
+ *   wrong and flags EVERY extra of s.  The routine detects; it neither corrects errors nor searches for a basis.
+ * PVW_ERR_INVALID_PARAMETERS before any device work, nothing written: NULL plain_modulus / indices / shares / out (or ctx),
+ * num_secrets = 0, count < degree + 1, duplicate indices, an index whose point is not below p, a composite or even p, a stride
+ * of 0 (and, on the device, count or num_secrets >= 2^31). */
+/* the contract in plain C++ on the host cores (no context, no GPU): what the kernels are tested against */
+PVW_API int32_t pvw_shamir_reconstruct_wide_checked_host(const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                         size_t count, const uint64_t* shares, size_t num_secrets,
+                                                         size_t secret_stride, size_t point_stride, uint64_t* out, uint32_t* bad,
+                                                         uint32_t* col_bad);
+/* device pointers (indices and plain_modulus stay HOST pointers, read before the call returns), asynchronous on `stream`.  The
+ * wide weight matrix [t+1][count-t][4] lives in the stream's workspace, sized by the call (134 MB at count 4096, t 2047): under
+ * stream capture the call needs an earlier call with the same (degree, count) on that stream outside capture; without it: the
+ * error of pvw_shamir_reconstruct_checked_device, nothing enqueued. */
+PVW_API int32_t pvw_shamir_reconstruct_wide_checked_device(pvw_ctx* ctx, const uint64_t* plain_modulus, uint32_t degree,
+                                                           const uint64_t* indices, size_t count, const uint64_t* d_shares,
+                                                           size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                                           uint64_t* d_out, uint32_t* d_bad, uint32_t* d_col_bad, void* stream);
+/* host buffers (synchronous), staged in bounded pieces; the staged shares and secrets are cleared before the call returns */
+PVW_API int32_t pvw_shamir_reconstruct_wide_checked(pvw_ctx* ctx, const uint64_t* plain_modulus, uint32_t degree,
+                                                    const uint64_t* indices, size_t count, const uint64_t* shares, size_t num_secrets,
+                                                    size_t secret_stride, size_t point_stride, uint64_t* out, uint32_t* bad,
+                                                    uint32_t* col_bad);
+/* SELF-TEST: the kernels' general product on the device, out[i] = a[i] b[i] mod p for a, b [count][4] below p (anything else:
+ * INVALID_PARAMETERS). */
+PVW_API int32_t pvw_selftest_shamir_wide_mul(pvw_ctx* ctx, const uint64_t* plain_modulus, const uint64_t* a, const uint64_t* b,
+                                             size_t count, uint64_t* out);
+
 /* decode_scalar_pvw_rns alone, on the device: noisy [D][L][l] power basis (host) -> out_u64 [D] */
 PVW_API int32_t pvw_decode(pvw_ctx* ctx, const uint64_t* noisy, size_t count, uint64_t* out_u64);
 /* the same with host big integers on the host cores (no GPU needed): an independent

@@ -20,7 +20,8 @@ from .api import (DEC_LOSSY, DEC_NEGATIVE, DEC_WIDE_TRUNCATED, CheckedDecryption
                   shamir_reconstruct_packed, shamir_packed_secret_indices, shamir_reconstruct_packed_corrected,
                   combine_ciphertexts_many, decrypt_all_party_combinations_many, shamir_lagrange_weights_at,
                   shamir_packed_handover_weights, sample_secret_keys_device, shamir_shares_wide, deal_party_shares_wide,
-                  shamir_wide_limbs, shamir_wide_to_limbs, shamir_wide_from_limbs, shamir_reconstruct_wide)
+                  shamir_wide_limbs, shamir_wide_to_limbs, shamir_wide_from_limbs, shamir_reconstruct_wide,
+                  shamir_wide_from_limbs_device, shamir_reconstruct_wide_checked)
 
 __all__ = [
     "PvwParametersBuilder", "PvwParameters", "PvwCrs", "SecretKey", "DeviceSecretKey", "DeviceRandomness", "Party", "GlobalPublicKey",
@@ -38,5 +39,6 @@ __all__ = [
     "shamir_shares", "deal_party_shares", "shamir_reconstruct", "shamir_reconstruct_checked", "shamir_reconstruct_corrected", "shamir_evaluate_corrected", "shamir_erasure_mask", "SHAMIR_UNDECODABLE",
     "sample_secret_keys_device",
     "shamir_shares_wide", "deal_party_shares_wide", "shamir_wide_limbs", "shamir_wide_to_limbs", "shamir_wide_from_limbs", "shamir_reconstruct_wide",
+    "shamir_wide_from_limbs_device", "shamir_reconstruct_wide_checked",
     "device_available", "REPR_POWER", "REPR_NTT",
 ]

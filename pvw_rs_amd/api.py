@@ -1041,6 +1041,63 @@ def shamir_reconstruct_wide(indices: Sequence[int], shares, plain_modulus: int):
     return res[0] if single else res
 
 
+def shamir_wide_from_limbs_device(params: PvwParameters, limbs, plain_modulus: int, limb_bits: int = 52, *,
+                                  layout: str = "limb_major", num_limbs: Optional[int] = None, stream=None):
+    """EXTENSION: shamir_wide_from_limbs where the limbs lie (pvw_shamir_wide_from_limbs_device).  limbs is a
+    contiguous int64 device tensor of any words: layout "limb_major" is [num_limbs][count], the planes of shamir_wide_from_limbs;
+    "limb_minor" is [...][num_limbs] with the limbs of one element side by side -- the [party][dealer * NL + w] values of
+    decrypt_all_party_shares* read in place with num_limbs = NL, giving P * D elements in [party][dealer] order.  Returns an
+    int64 device tensor [count][4] of little-endian words, made asynchronously on `stream`."""
+    import torch
+    if layout not in ("limb_major", "limb_minor"):
+        raise ValueError(layout)
+    if not hasattr(limbs, "data_ptr") or not limbs.is_contiguous() or limbs.dtype != torch.int64 or limbs.dim() < 1:
+        raise PvwError(15, "limbs must be a contiguous int64 device tensor")
+    if layout == "limb_major":
+        nl = int(limbs.shape[0])
+        count = limbs.numel() // nl if nl else 0
+        strides = (max(count, 1), 1)
+    else:
+        nl = int(num_limbs) if num_limbs is not None else int(limbs.shape[-1])
+        if nl < 1 or limbs.numel() % nl:
+            raise PvwError(15, f"{limbs.numel()} words are no whole number of {nl}-limb elements")
+        count = limbs.numel() // nl
+        strides = (1, nl)
+    out = torch.zeros((count, WIDE_WORDS), dtype=torch.int64, device=limbs.device)
+    params._call("pvw_shamir_wide_from_limbs_device", _ptr(_wide_modulus(plain_modulus)), _dptr(limbs), count, strides[0], strides[1],
+                 int(limb_bits), nl, _dptr(out), _stream_ptr(stream))
+    return out
+
+
+def shamir_reconstruct_wide_checked(params: Optional[PvwParameters], indices: Sequence[int], shares, degree: int, plain_modulus: int, *,
+                                    host: bool = False, layout: str = "secret_major") -> Tuple[List[int], np.ndarray, np.ndarray]:
+    """EXTENSION: shamir_reconstruct_checked over an odd prime plain_modulus < 2^256.  shares: a matrix of Python
+    ints (any value: the low 256 bits, read mod p) or uint64 words [...][...][4], "secret_major" [num_secrets][len(indices)] or
+    "party_major" [len(indices)][num_secrets].  On the device (pvw_shamir_reconstruct_wide_checked); host=True: the plain C++
+    restatement (pvw_shamir_reconstruct_wide_checked_host, no GPU; params may be None).  Returns (secrets as ints, bad, col_bad)."""
+    if layout not in ("secret_major", "party_major"):
+        raise ValueError(layout)
+    idx = _words(indices)
+    count = len(idx)
+    if isinstance(shares, np.ndarray) and shares.dtype == np.uint64 and shares.ndim == 3 and shares.shape[-1] == WIDE_WORDS:
+        sh = np.ascontiguousarray(shares)
+    else:
+        rows = [list(row) for row in shares]
+        if any(len(row) != len(rows[0]) for row in rows):
+            raise PvwError(15, "the rows of shares differ in length")
+        sh = _wide([v for row in rows for v in row]).reshape(len(rows), -1, WIDE_WORDS)
+    S, cols = sh.shape[:2] if layout == "secret_major" else sh.shape[:2][::-1]
+    if cols != count:
+        raise PvwError(15, f"expected {count} shares per secret, got {cols}")
+    strides = (count, 1) if layout == "secret_major" else (1, S)
+    out = np.zeros((S, WIDE_WORDS), dtype=np.uint64)
+    bad, col_bad = np.zeros(S, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
+    args = (_ptr(_wide_modulus(plain_modulus)), int(degree), _ptr(idx), count, _ptr(sh), S, strides[0], strides[1], _ptr(out), _ptr(bad),
+            _ptr(col_bad))
+    _reconstruct_call(params, "shamir_reconstruct_wide_checked", host, args)
+    return _wide_ints(out), bad, col_bad
+
+
 def _share_matrix(indices: Sequence[int], shares, layout: str):
     """(idx, sh, S, count, strides) of the checked, corrected and evaluate calls: the indices and the share matrix as uint64
     words, and the (secret, point) strides of `layout` in words"""

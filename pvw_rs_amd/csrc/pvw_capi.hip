@@ -150,6 +150,8 @@ struct Workspace {
   size_t shares_bytes = 0;
   u64* interp = nullptr;     // checked reconstruction: points | products | weight matrix (shamir_interp_words; grown by the call)
   size_t interp_bytes = 0;
+  u64* interp_wide = nullptr;   // the same over a prime below 2^256 (shamir_interp_wide_words)
+  size_t interp_wide_bytes = 0;
   u64* packw = nullptr;      // packed dealing: Lw | zt | w | 1/j! (shamir_packed_words; public, grown by the call)
   size_t packw_bytes = 0;
   u64* correct = nullptr;    // corrected reconstruction: M | public matrices | syndromes | locators (CorrectLayout; grown by the call)
@@ -634,6 +636,7 @@ static void ws_free(Workspace* w) {
   if (w->shares) hipMemset(w->shares, 0, w->shares_bytes);   // the last deal's shares, if its wipe did not run
   hipFree(w->shares);
   hipFree(w->interp);
+  hipFree(w->interp_wide);
   hipFree(w->packw);
   if (w->correct) hipMemset(w->correct, 0, w->correct_bytes);   // M of the last call, if its wipe did not run
   hipFree(w->correct);
@@ -4180,6 +4183,293 @@ int32_t pvw_selftest_shamir_wide_step(pvw_ctx* c, const uint64_t* plain_modulus,
     PVW_HIP(hipMemcpyAsync(d_add, add, count * 32, hipMemcpyHostToDevice, w->stream));
     PVW_HIP(hipMemcpyAsync(d_x, x, count * 8, hipMemcpyHostToDevice, w->stream));
     PVW_HIP(launch_shamir_wide_step(m, d_acc, d_x, d_add, count, d_out, w->stream));
+    PVW_HIP(hipMemcpyAsync(out, d_out, count * 32, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
+}
+
+// ------------------------------------------------------------------------ the receiving end over a prime below 2^256
+// The fold of decrypted limbs on the device, and checked reconstruction with wide elements: the contract of 8.10.
+
+static int32_t wide_fold_checks(const uint64_t* p, const void* limbs, const void* out, size_t count, uint32_t limb_bits, uint32_t num_limbs,
+                                WideMod* m) {
+  if (!p || ((!limbs || !out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (limb_bits < 16 || limb_bits > 62) return fail(PVW_ERR_INVALID_PARAMETERS, "limb_bits must be in [16, 62]");
+  if (num_limbs < 1 || num_limbs > PVW_WIDE_MAX_LIMBS) return fail(PVW_ERR_INVALID_PARAMETERS, "num_limbs must be in [1, 16]");
+  return wide_modulus_check(p, m);
+}
+
+// device pointers (plain_modulus stays a HOST pointer): no workspace, nothing allocated, may be captured
+int32_t pvw_shamir_wide_from_limbs_device(pvw_ctx* c, const uint64_t* plain_modulus, const uint64_t* d_limbs, size_t count,
+                                          size_t limb_stride, size_t elem_stride, uint32_t limb_bits, uint32_t num_limbs, uint64_t* d_out,
+                                          void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  WideMod m;
+  PVW_TRY(wide_fold_checks(plain_modulus, d_limbs, d_out, count, limb_bits, num_limbs, &m));
+  if (limb_stride == 0 || elem_stride == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "a stride of 0");
+  if (!count) return PVW_OK;
+  PVW_TRY(ensure_device(c));
+  const hipStream_t s = call_stream(c, stream);
+  ProfScope ps(c, "shamir_wide_fold", s);
+  PVW_HIP(launch_shamir_wide_fold(m, d_limbs, count, limb_stride, elem_stride, limb_bits, num_limbs, d_out, s));
+  return PVW_OK;
+}
+
+struct ReconstructWide {
+  const u64* p;         // [4], host
+  u32 degree;
+  const u64* indices;   // [count], host
+  size_t count, S, secret_stride, point_stride;
+  WideMod m;            // set by reconstruct_wide_checks
+  size_t T() const { return count - degree; }
+  size_t ws_bytes() const { return shamir_interp_wide_words(count, degree) * 8; }
+};
+// the order of reconstruct_checks: NULL, no secrets, too few shares, a duplicate, the range, the modulus, the strides
+static int32_t reconstruct_wide_checks(ReconstructWide& r, const void* shares, const void* out) {
+  if (!r.p || !r.indices || !shares || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (r.S == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no secrets to reconstruct");
+  if (r.count < (size_t)r.degree + 1) {
+    char buf[96];
+    snprintf(buf, sizeof buf, "degree %u needs at least %zu shares, got %zu", r.degree, (size_t)r.degree + 1, r.count);
+    return fail(PVW_ERR_INVALID_PARAMETERS, buf);
+  }
+  {
+    std::vector<u64> sorted(r.indices, r.indices + r.count);
+    std::sort(sorted.begin(), sorted.end());
+    for (size_t i = 1; i < r.count; ++i)
+      if (sorted[i] == sorted[i - 1]) return fail(PVW_ERR_INVALID_PARAMETERS, "duplicate party index");
+  }
+  const bool one_word = !r.p[1] && !r.p[2] && !r.p[3];
+  if (one_word && r.p[0] < 2) return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must be prime (Shamir shares live in a field)");
+  // the point x = index + 1 <= 2^64 must be below p: p of one word bounds the index; 2^64 itself needs p > 2^64
+  const bool above_2_64 = r.p[2] || r.p[3] || r.p[1] > 1 || (r.p[1] == 1 && r.p[0] != 0);
+  for (size_t i = 0; i < r.count; ++i)
+    if (one_word ? r.indices[i] >= r.p[0] - 1 : (r.indices[i] == ~(u64)0 && !above_2_64))
+      return fail(PVW_ERR_INVALID_PARAMETERS, "party index out of range for plain_modulus");
+  PVW_TRY(wide_modulus_check(r.p, &r.m));
+  if (r.secret_stride == 0 || r.point_stride == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "a stride of 0");
+  return PVW_OK;
+}
+static int32_t reconstruct_wide_device_checks(const ReconstructWide& r) {
+  if (r.count >= ((size_t)1 << 31) || r.S >= ((size_t)1 << 31))
+    return fail(PVW_ERR_INVALID_PARAMETERS, "count and num_secrets must be below 2^31 on the device");
+  return PVW_OK;
+}
+
+// a <- (a - b) mod pn and res = a b mod p for scaled a, b below pn
+static void wide_submod(Wide a, const Wide b, const WideMod& m) {
+  Wide nb;
+  wide_set(nb, b);
+  wide_negmod(nb, m);
+  wide_addmod(a, nb, m);
+}
+static void wide_mulmod_scaled(Wide res, const Wide a, const Wide b, const WideMod& m) {
+  Wide plain;
+  wide_unscale(plain, b, m);
+  wide_mulmod(res, a, plain, m);
+}
+
+// The contract in plain C++ (no GPU), apart from the kernels in method and in arithmetic: the scaled step of pvw_wide.h, not
+// the Montgomery product; for every target the basis polynomials L_j(x) = prod_{i != j}(x - x_i) / prod_{i != j}(x_j - x_i)
+// from prefix and suffix products of the factors (x - x_i), then one dot product per secret.
+int32_t pvw_shamir_reconstruct_wide_checked_host(const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                                 const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                                 uint64_t* out, uint32_t* bad, uint32_t* col_bad) {
+  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  PVW_TRY(reconstruct_wide_checks(r, shares, out));
+  const WideMod& m = r.m;
+  const size_t t = degree, T = r.T();
+  std::vector<u64> x(count * 4), inv_den((t + 1) * 4), L((t + 1) * 4), suf((t + 2) * 4), basis((t + 1) * 4);
+  Wide one;
+  {
+    Wide w1;
+    wide_small(w1, 1);
+    wide_reduce(one, w1, m);
+  }
+  for (size_t c = 0; c < count; ++c) {
+    const u64 xw[4] = {indices[c] + 1, indices[c] + 1 == 0 ? (u64)1 : (u64)0, 0, 0};
+    wide_reduce(&x[c * 4], xw, m);
+  }
+  for (size_t j = 0; j <= t; ++j) {
+    Wide den, d;
+    wide_set(den, one);
+    for (size_t i = 0; i <= t; ++i)
+      if (i != j) {
+        wide_set(d, &x[j * 4]);
+        wide_submod(d, &x[i * 4], m);
+        wide_mulmod_scaled(den, den, d, m);
+      }
+    wide_invmod(&inv_den[j * 4], den, plain_modulus, m);
+  }
+  if (bad) std::fill(bad, bad + num_secrets, 0u);
+  if (col_bad) std::fill(col_bad, col_bad + count, 0u);
+  for (size_t tm = 0; tm < T; ++tm) {
+    Wide xm, d, pre;
+    wide_small(xm, 0);
+    if (tm) wide_set(xm, &x[(t + tm) * 4]);
+    wide_set(&suf[(t + 1) * 4], one);                          // suf[i] = prod_{k >= i, k <= t}(x_m - x_k)
+    for (size_t i = t + 1; i-- > 0;) {
+      wide_set(d, xm);
+      wide_submod(d, &x[i * 4], m);
+      wide_mulmod_scaled(&suf[i * 4], &suf[(i + 1) * 4], d, m);
+    }
+    wide_set(pre, one);                                        // prod_{k < j}(x_m - x_k)
+    for (size_t j = 0; j <= t; ++j) {
+      Wide v;
+      wide_mulmod_scaled(v, pre, &suf[(j + 1) * 4], m);
+      wide_mulmod_scaled(&L[j * 4], v, &inv_den[j * 4], m);
+      wide_set(d, xm);
+      wide_submod(d, &x[j * 4], m);
+      wide_mulmod_scaled(pre, pre, d, m);
+    }
+    for (size_t s = 0; s < num_secrets; ++s) {
+      const u64* row = shares + s * secret_stride * 4;
+      Wide v, y, prod;
+      wide_small(v, 0);
+      for (size_t j = 0; j <= t; ++j) {
+        wide_reduce(y, row + j * point_stride * 4, m);
+        wide_mulmod_scaled(prod, y, &L[j * 4], m);
+        wide_addmod(v, prod, m);
+      }
+      if (tm == 0) {
+        wide_unscale(out + s * 4, v, m);
+      } else {
+        wide_reduce(y, row + (t + tm) * point_stride * 4, m);
+        if (memcmp(y, v, 32) != 0) {
+          if (bad) ++bad[s];
+          if (col_bad) ++col_bad[t + tm];
+        }
+      }
+    }
+  }
+  return PVW_OK;
+}
+
+// the points and the weight matrix of one call into ws (shamir_interp_wide_words words)
+static int32_t reconstruct_wide_weights(pvw_ctx* c, const ReconstructWide& r, const WideMont& mm, u64* ws, hipStream_t s) {
+  ProfScope ps(c, "shamir_weights_wide", s);
+  PVW_HIP(launch_shamir_points_wide(r.indices, r.count, ws, mm, s));
+  PVW_HIP(launch_shamir_weights_wide(ws, r.count, r.degree, mm, s));
+  return PVW_OK;
+}
+// ns secrets from d_shares under the weights in ws: out and bad of these secrets; col_bad, zeroed by the caller, is added to
+static int32_t reconstruct_wide_interp(pvw_ctx* c, const ReconstructWide& r, const WideMont& mm, const u64* ws, const u64* d_shares,
+                                       size_t ns, size_t secret_stride, size_t point_stride, u64* d_out, u32* d_bad, u32* d_col_bad,
+                                       hipStream_t s) {
+  ProfScope ps(c, "shamir_interp_wide", s);
+  PVW_HIP(launch_shamir_zero_counts(d_bad, ns, s));
+  ShamirInterpWide b{};
+  b.shares = d_shares;
+  b.secret_stride = secret_stride;
+  b.point_stride = point_stride;
+  b.W = ws + (2 * r.count + 1) * 4;
+  b.out = d_out;
+  b.bad = d_bad;
+  b.col_bad = d_col_bad;
+  b.ns = (u32)ns;
+  b.degree = r.degree;
+  b.T = (u32)r.T();
+  b.m = mm;
+  PVW_HIP(launch_shamir_interp_wide(b, s));
+  return PVW_OK;
+}
+
+int32_t pvw_shamir_reconstruct_wide_checked_device(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                   size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
+                                                   size_t point_stride, uint64_t* d_out, uint32_t* d_bad, uint32_t* d_col_bad,
+                                                   void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  PVW_TRY(reconstruct_wide_checks(r, d_shares, d_out));
+  PVW_TRY(reconstruct_wide_device_checks(r));
+  const WideMont mm = make_wide_mont(plain_modulus);
+  // the caller's stream is checked before the device is touched (pvw_shamir_reconstruct_checked_device)
+  auto sized = [&](hipStream_t s) {
+    return grown_capture_check(c, s, &Workspace::interp_wide_bytes, r.ws_bytes(),
+                               "checked reconstruction under stream capture: run a call with the same degree and count on this stream "
+                               "outside capture first (it sizes the workspace)");
+  };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
+    PVW_TRY(ws_grow(&w->interp_wide, &w->interp_wide_bytes, r.ws_bytes(), s, false));   // public: nothing to clear
+    PVW_TRY(reconstruct_wide_weights(c, r, mm, w->interp_wide, s));
+    PVW_HIP(launch_shamir_zero_counts(d_col_bad, count, s));
+    return reconstruct_wide_interp(c, r, mm, w->interp_wide, d_shares, num_secrets, secret_stride, point_stride, d_out, d_bad, d_col_bad, s);
+  });
+}
+
+// host buffers: the secrets go up in pieces of `per` (<= ~1 GiB of shares), each a dense [piece][count][4] block -- whole rows
+// by a 2D copy where the caller's rows lie that way, else repacked on the host into a copy that is wiped when the call ends;
+// the weights are made once.  The staged shares and the staged results are secret; the weights and the counts are not.
+int32_t pvw_shamir_reconstruct_wide_checked(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                            const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                            uint64_t* out, uint32_t* bad, uint32_t* col_bad) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  PVW_TRY(reconstruct_wide_checks(r, shares, out));
+  PVW_TRY(reconstruct_wide_device_checks(r));
+  PVW_TRY(ensure_device(c));
+  const WideMont mm = make_wide_mont(plain_modulus);
+  const size_t per = chunk_1gib((count + 1) * 32 + 4, num_secrets);
+  Scratch sc;
+  const size_t r_sh = sc.add(per * count * 32), r_out = sc.add(per * 32), r_ws = sc.add(r.ws_bytes()), r_bad = sc.add(per * 4),
+               r_col = sc.add(count * 4);
+  const bool dense = point_stride == 1 && secret_stride >= count;
+  std::vector<u64> packed(dense ? 0 : per * count * 4);
+  const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    sc.secret(w, r_sh, r_out);
+    u64 *d_sh = sc.at(r_sh), *d_out = sc.at(r_out), *ws = sc.at(r_ws);
+    u32 *d_bad = bad ? sc.at<u32>(r_bad) : nullptr, *d_col = col_bad ? sc.at<u32>(r_col) : nullptr;
+    PVW_TRY(reconstruct_wide_weights(c, r, mm, ws, w->stream));
+    PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
+    for (size_t s0 = 0; s0 < num_secrets; s0 += per) {
+      const size_t cnt = (num_secrets - s0) < per ? (num_secrets - s0) : per;
+      if (dense) {
+        PVW_HIP(hipMemcpy2DAsync(d_sh, count * 32, shares + s0 * secret_stride * 4, secret_stride * 32, count * 32, cnt,
+                                 hipMemcpyHostToDevice, w->stream));
+      } else {
+        for (size_t s = 0; s < cnt; ++s)
+          for (size_t col = 0; col < count; ++col)
+            memcpy(&packed[(s * count + col) * 4], shares + ((s0 + s) * secret_stride + col * point_stride) * 4, 32);
+        PVW_HIP(hipMemcpyAsync(d_sh, packed.data(), cnt * count * 32, hipMemcpyHostToDevice, w->stream));
+      }
+      PVW_TRY(reconstruct_wide_interp(c, r, mm, ws, d_sh, cnt, count, 1, d_out, d_bad, d_col, w->stream));
+      PVW_HIP(hipMemcpyAsync(out + s0 * 4, d_out, cnt * 32, hipMemcpyDeviceToHost, w->stream));
+      if (bad) PVW_HIP(hipMemcpyAsync(bad + s0, d_bad, cnt * 4, hipMemcpyDeviceToHost, w->stream));
+      PVW_HIP(hipStreamSynchronize(w->stream));                  // the next piece reuses the staging
+    }
+    if (col_bad) PVW_HIP(hipMemcpyAsync(col_bad, d_col, count * 4, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
+  volatile u64* vp = packed.data();
+  for (size_t i = 0; i < packed.size(); ++i) vp[i] = 0;
+  return rc;
+}
+
+// SELF-TEST: the kernels' product on the device, out = a b mod p
+int32_t pvw_selftest_shamir_wide_mul(pvw_ctx* c, const uint64_t* plain_modulus, const uint64_t* a, const uint64_t* b, size_t count,
+                                     uint64_t* out) {
+  if (!c || !plain_modulus || ((!a || !b || !out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  WideMod m;
+  PVW_TRY(wide_modulus_check(plain_modulus, &m));
+  for (size_t i = 0; i < count; ++i) {
+    u64 x[4], y[4], pp[4];
+    wide_set(x, a + i * 4);
+    wide_set(y, b + i * 4);
+    wide_set(pp, plain_modulus);
+    if (!wide_less(x, pp) || !wide_less(y, pp)) return fail(PVW_ERR_INVALID_PARAMETERS, "the product takes a, b below plain_modulus");
+  }
+  if (!count) return PVW_OK;
+  PVW_TRY(ensure_device(c));
+  const WideMont mm = make_wide_mont(plain_modulus);
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(ws_scratch(w, count * 96));
+    u64* base = (u64*)w->scratch;
+    u64 *d_a = base, *d_b = base + count * 4, *d_out = base + count * 8;
+    PVW_HIP(hipMemcpyAsync(d_a, a, count * 32, hipMemcpyHostToDevice, w->stream));
+    PVW_HIP(hipMemcpyAsync(d_b, b, count * 32, hipMemcpyHostToDevice, w->stream));
+    PVW_HIP(launch_shamir_wide_mul(mm, d_a, d_b, count, d_out, w->stream));
     PVW_HIP(hipMemcpyAsync(out, d_out, count * 32, hipMemcpyDeviceToHost, w->stream));
     return PVW_OK;
   });

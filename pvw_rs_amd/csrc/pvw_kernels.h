@@ -289,6 +289,30 @@ hipError_t launch_shamir_eval_wide(const ShamirWideBatch& b, hipStream_t s);
 // out[i] = (acc[i] x[i] + add[i]) mod p by the kernel's own step; acc, add < p, x < 2^32 (pvw_selftest_shamir_wide_step)
 hipError_t launch_shamir_wide_step(const WideMod& m, const u64* acc, const u64* x, const u64* add, size_t count, u64* out, hipStream_t s);
 
+// ---- Checked reconstruction over a prime below 2^256 (pvw_shamir.hip): the layout of 8.10 below with elements of
+// four words.  Workspace words: x [count][4] | aux [count + 1][4] | W [t+1][T][4], ALL in Montgomery form (v 2^256 mod p,
+// pvw_wide.h), so that a plain share times a stored weight is one REDC away from the plain product.
+inline size_t shamir_interp_wide_words(size_t count, u32 t) { return 4 * (2 * count + 1 + ((size_t)t + 1) * (count - t)); }
+struct ShamirInterpWide {
+  const u64* shares;     // element (s, c): four words at shares + 4 (s * secret_stride + c * point_stride), any words, read mod p
+  size_t secret_stride, point_stride;
+  const u64* W;          // [t+1][T][4]
+  u64* out;              // [ns][4]
+  u32* bad;              // [ns] or NULL; zeroed by the caller (launch_shamir_zero_counts), the kernel adds
+  u32* col_bad;          // [count] or NULL; likewise
+  u32 ns, degree, T;
+  WideMont m;
+};
+// x[i] = (indices[i] + 1) 2^256 mod p, four words each (the point of index 2^64 - 1 is 2^64)
+hipError_t launch_shamir_points_wide(const u64* indices, size_t count, u64* x, const WideMont& m, hipStream_t s);
+hipError_t launch_shamir_weights_wide(u64* ws, size_t count, u32 degree, const WideMont& m, hipStream_t s);
+hipError_t launch_shamir_interp_wide(const ShamirInterpWide& b, hipStream_t s);
+// out[i] = sum_w limbs[w * limb_stride + i * elem_stride] 2^(w limb_bits) mod p, [count][4]; any words
+hipError_t launch_shamir_wide_fold(const WideMod& m, const u64* limbs, size_t count, size_t limb_stride, size_t elem_stride, u32 limb_bits,
+                                   u32 num_limbs, u64* out, hipStream_t s);
+// out[i] = a[i] b[i] mod p by the kernels' own product; a, b < p (pvw_selftest_shamir_wide_mul)
+hipError_t launch_shamir_wide_mul(const WideMont& m, const u64* a, const u64* b, size_t count, u64* out, hipStream_t s);
+
 // ---- Checked reconstruction (pvw_shamir.hip).  Columns 0..t of the share matrix are the basis, columns
 // t+1..count-1 the extras; T = count - t targets: target 0 is x = 0, target m >= 1 the point of column t + m.
 // Workspace words: x [count] | aux [count + 1] | W [t+1][T].  aux[j] = (prod_{i != j}(x_j - x_i))^-1 for j <= t and

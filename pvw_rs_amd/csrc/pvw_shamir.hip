@@ -1172,4 +1172,317 @@ hipError_t launch_shamir_wide_step(const WideMod& m, const u64* acc, const u64* 
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------ checked reconstruction below 2^256
+// The contract and the layout of 8.10 with elements of four words: columns 0..t are the basis, T = count - t targets (target 0
+// is x = 0, target m >= 1 the point of column t + m), out[s] = F_s(0) and every extra share is compared with F_s at its point.
+// Arithmetic: Montgomery's product of pvw_wide.h.  The workspace (points, products, weights) is public and holds everything
+// times R = 2^256; the shares stay plain, and share * (W R) reduced once is the plain share * W.
+// Weights: aux as in 8.10, one wave per product (shamir_prod_wide_kernel; a basis column's product is inverted by Fermat, about
+// 380 products on one lane), then W[j][m] = aux[t+1+m] aux[j] (x_m - x_j)^-1.  An inversion per element would cost 380 products
+// against the half product per secret that the element is used for below, so SHW_WG = 32 entries of one target (rows j0 .. j0+31)
+// share one inversion by Montgomery's trick: the running products of the differences go out to the entries' own slots of W,
+// the last one is inverted, and the walk back turns every slot into its weight -- 3 products an entry for the trick, 2 for
+// the weight, 380 / 32 = 12 for its part of the inversion.  No register holds a prefix: the group size costs no VGPRs.
+// Product: the frame of shamir_tile_product.  A lane owns one target and SHW_SG secrets; the four waves own the same 64 targets
+// and secrets and a quarter of the t + 1 terms each.  The chunk's shares are staged in LDS below p ([wave][term][secret]) and
+// read back as broadcasts; W[j][m] is two coalesced 16-byte loads per lane and term, the next term's in flight.  A term is a
+// 16-digit schoolbook product (64 v_mad_u64_u32) ADDED to an unreduced accumulator that wide_acc_add keeps below p 2^256 with
+// one conditional subtraction; the accumulator is reduced ONCE, when the wave's terms are done.  Partial sums are field
+// elements, so the waves' four meet in LDS by plain additions mod p.
+#define SHW_SG 4      // secrets per lane
+#define SHW_TC 8      // terms per wave and staging chunk
+#define SHW_WG 32     // entries of W that share one inversion
+static_assert(SHW_SG == SH_WAVES && SHW_SG == SH_DG, "the last phase maps one wave to one secret of the group; launch_secret_groups");
+
+// the workspace's elements are 32-byte aligned: two 16-byte accesses
+__device__ __forceinline__ void wide_ld(const u64* p, u64 (&v)[4]) {
+  const ulonglong2 lo = ((const ulonglong2*)p)[0], hi = ((const ulonglong2*)p)[1];
+  v[0] = lo.x; v[1] = lo.y; v[2] = hi.x; v[3] = hi.y;
+}
+__device__ __forceinline__ void wide_st(u64* p, const u64 (&v)[4]) {
+  ((ulonglong2*)p)[0] = make_ulonglong2(v[0], v[1]);
+  ((ulonglong2*)p)[1] = make_ulonglong2(v[2], v[3]);
+}
+
+// x[i] = (index[i] + 1) R mod p (the indices travel as kernel arguments, shamir_points_kernel)
+__global__ __launch_bounds__(PVW_SHAMIR_POINTS) void shamir_points_wide_kernel(ShamirPoints a, WideMont m) {
+  if (threadIdx.x >= a.n) return;
+  const u64 i = a.index[threadIdx.x];
+  const u64 x[4] = {i + 1, i + 1 == 0 ? (u64)1 : (u64)0, 0, 0};
+  u64 xm[4];
+  wide_mont_in(x, m, xm);
+  wide_st(a.x + (size_t)threadIdx.x * 4, xm);
+}
+
+// shamir_prod_kernel over four words: item e = blockIdx.x * 4 + wave of [0, count + 1)
+__global__ __launch_bounds__(256) void shamir_prod_wide_kernel(const u64* x, u64* aux, size_t count, u32 t, WideMont m) {
+  __shared__ u64 red[SH_WAVES][64][4];
+  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const size_t e = (size_t)blockIdx.x * SH_WAVES + wave;
+  const bool live = e <= count;
+  const bool basis = e <= t;
+  u64 xe[4] = {0, 0, 0, 0};                                      // target 0
+  if (live && basis) wide_ld(x + e * 4, xe);
+  else if (live && e > (size_t)t + 1) wide_ld(x + (e - 1) * 4, xe);
+  u64 prod[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) prod[k] = m.one[k];
+  if (live)
+    for (u32 i = lane; i <= t; i += 64)
+      if (!(basis && i == e)) {
+        u64 xi[4], d[4];
+        wide_ld(x + (size_t)i * 4, xi);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) d[k] = xe[k];
+        wide_sub_p(d, xi, m);
+        wide_mont_mul(prod, d, m, prod);
+      }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) red[wave][lane][k] = prod[k];
+  __syncthreads();
+  if (lane == 0 && live) {
+    for (u32 i = 1; i < 64; ++i) {
+      u64 f[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) f[k] = red[wave][i][k];
+      wide_mont_mul(prod, f, m, prod);
+    }
+    if (basis) wide_mont_inv(prod, m, prod);
+    wide_st(aux + e * 4, prod);
+  }
+}
+
+// one thread per target and group of SHW_WG rows, the target fastest: thread e = group * T + target
+__global__ __launch_bounds__(256) void shamir_weights_wide_kernel(const u64* x, const u64* aux, u64* W, size_t count, u32 t, WideMont m) {
+  const size_t T = count - t;
+  const size_t groups = ((size_t)t + SHW_WG) / SHW_WG;           // ceil((t + 1) / SHW_WG)
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= groups * T) return;
+  const size_t tm = e % T, j0 = (e / T) * SHW_WG;
+  const u32 cnt = (size_t)t + 1 - j0 < SHW_WG ? (u32)((size_t)t + 1 - j0) : SHW_WG;
+  u64 xm[4] = {0, 0, 0, 0};
+  if (tm) wide_ld(x + ((size_t)t + tm) * 4, xm);
+  // forward: slot k <- d_0 ... d_k, d_k = x_m - x_{j0+k} (never 0: distinct points below p, and 0 is no party's point)
+  u64 run[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) run[k] = m.one[k];
+  for (u32 k = 0; k < cnt; ++k) {
+    u64 xj[4], d[4];
+    wide_ld(x + (j0 + k) * 4, xj);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) d[i] = xm[i];
+    wide_sub_p(d, xj, m);
+    wide_mont_mul(run, d, m, run);
+    wide_st(W + ((j0 + k) * T + tm) * 4, run);
+  }
+  u64 inv[4], lm[4];
+  wide_mont_inv(run, m, inv);                                    // (d_0 ... d_{cnt-1})^-1
+  wide_ld(aux + ((size_t)t + 1 + tm) * 4, lm);
+  // back: inv = (d_0 ... d_k)^-1 on entry to step k; d_k^-1 = inv * slot[k-1]
+  for (u32 k = cnt; k-- > 0;) {
+    u64 xj[4], d[4], pre[4], wj[4], dinv[4];
+    wide_ld(x + (j0 + k) * 4, xj);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) d[i] = xm[i];
+    wide_sub_p(d, xj, m);
+    if (k) wide_ld(W + ((j0 + k - 1) * T + tm) * 4, pre);
+    else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) pre[i] = m.one[i];
+    }
+    wide_mont_mul(inv, pre, m, dinv);
+    wide_mont_mul(inv, d, m, inv);
+    wide_ld(aux + (j0 + k) * 4, wj);
+    wide_mont_mul(wj, lm, m, wj);
+    wide_mont_mul(wj, dinv, m, wj);
+    wide_st(W + ((j0 + k) * T + tm) * 4, wj);
+  }
+}
+
+// grid: x = blocks of 64 targets, y = groups of SHW_SG secrets; 256 threads.
+__global__ __launch_bounds__(256) void shamir_interp_wide_kernel(ShamirInterpWide b) {
+  __shared__ u64 sh[SH_WAVES][SHW_TC][SHW_SG][4];  // 4 KiB: the chunk of the shares, below p
+  __shared__ u64 part[SH_WAVES][SHW_SG][64][4];    // 32 KiB: the waves' partial sums, below p
+  const WideMont m = b.m;
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const u32 s0 = blockIdx.y * SHW_SG, ns = b.ns, nt = b.degree + 1, T = b.T;
+  const size_t tm = (size_t)blockIdx.x * 64 + lane;
+  const bool live = tm < T;
+  // wave w owns terms j = w * Q + [0, Q), cut off at nt; every wave walks the same number of chunks (barriers)
+  const u32 Q = (nt + SH_WAVES - 1) / SH_WAVES;
+  const u32 jw0 = wave * Q;
+  const u32 nchunks = (Q + SHW_TC - 1) / SHW_TC;
+  const bool term_fast = b.point_stride <= b.secret_stride;
+  const u64* wcol = b.W + (live ? tm : 0) * 4;
+  u32 acc[SHW_SG][16];                             // each below p 2^256 (wide_acc_add)
+#pragma unroll
+  for (int g = 0; g < SHW_SG; ++g) wide_acc_zero(acc[g]);
+  for (u32 c = 0; c < nchunks; ++c) {
+    // ---- staging: entry e = (wave, term, secret) of the chunk, one per lane of the first two waves ----
+    if (tid < SH_WAVES * SHW_TC * SHW_SG) {
+      const u32 e = tid;
+      const u32 ew = e / (SHW_TC * SHW_SG);
+      const u32 ej = term_fast ? e % SHW_TC : (e / SHW_SG) % SHW_TC;
+      const u32 eg = term_fast ? (e / SHW_TC) % SHW_SG : e % SHW_SG;
+      const u32 off = c * SHW_TC + ej;             // within the wave's range
+      const u32 j = ew * Q + off;
+      u64 a[4] = {0, 0, 0, 0};
+      if (off < Q && j < nt && s0 + eg < ns) {
+        const u64* sp = b.shares + ((size_t)(s0 + eg) * b.secret_stride + (size_t)j * b.point_stride) * 4;
+        const u64 w[4] = {sp[0], sp[1], sp[2], sp[3]};
+        wide_reduce_p(w, m, a);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) sh[ew][ej][eg][k] = a[k];
+    }
+    __syncthreads();
+    // ---- this wave's terms of the chunk ----
+    const u32 lo = c * SHW_TC;
+    u32 cnt = lo < Q ? (Q - lo < SHW_TC ? Q - lo : SHW_TC) : 0;
+    const u32 j0 = jw0 + lo;
+    if (j0 >= nt) cnt = 0;
+    else if (nt - j0 < cnt) cnt = nt - j0;
+    u64 w[4] = {0, 0, 0, 0};
+    if (cnt) wide_ld(wcol + (size_t)j0 * T * 4, w);
+    for (u32 jj = 0; jj < cnt; ++jj) {
+      u64 wn[4] = {0, 0, 0, 0};
+      if (jj + 1 < cnt) wide_ld(wcol + (size_t)(j0 + jj + 1) * T * 4, wn);
+#pragma unroll
+      for (int g = 0; g < SHW_SG; ++g) {
+        u64 a[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a[k] = sh[wave][jj][g][k];
+        u32 P[16];
+        wide_mul_full(a, w, P);
+        wide_acc_add(acc[g], P, m);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) w[k] = wn[k];
+    }
+    __syncthreads();
+  }
+  // every wave reduces its sums once; thread (g, lane) adds the four partial sums of secret s0 + g at its target
+#pragma unroll
+  for (int g = 0; g < SHW_SG; ++g) {
+    u64 r[4];
+    wide_redc(acc[g], m, r);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) part[wave][g][lane][k] = r[k];
+  }
+  __syncthreads();
+  u64 v[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = part[0][wave][lane][k];
+#pragma unroll
+  for (int ww = 1; ww < SH_WAVES; ++ww) {
+    u64 f[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) f[k] = part[ww][wave][lane][k];
+    wide_add_p(v, f, m);
+  }
+  const u32 s = s0 + wave;
+  bool dev = false;
+  if (live && s < ns) {
+    if (tm == 0) {
+      u64* o = b.out + (size_t)s * 4;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] = v[k];
+    } else {
+      const size_t col = (size_t)b.degree + tm;
+      const u64* sp = b.shares + ((size_t)s * b.secret_stride + col * b.point_stride) * 4;
+      const u64 w[4] = {sp[0], sp[1], sp[2], sp[3]};
+      u64 y[4];
+      wide_reduce_p(w, m, y);
+      dev = (y[0] != v[0]) | (y[1] != v[1]) | (y[2] != v[2]) | (y[3] != v[3]);
+      if (dev && b.col_bad) atomicAdd(&b.col_bad[col], 1u);
+    }
+  }
+  // one add per wave: the wave's lanes share the secret
+  const u32 ndev = (u32)__popcll(__ballot(dev));
+  if (lane == 0 && ndev && b.bad) atomicAdd(&b.bad[s], ndev);
+}
+
+hipError_t launch_shamir_points_wide(const u64* indices, size_t count, u64* x, const WideMont& m, hipStream_t s) {
+  for (size_t i0 = 0; i0 < count; i0 += PVW_SHAMIR_POINTS) {
+    ShamirPoints a;
+    a.n = (u32)(count - i0 < PVW_SHAMIR_POINTS ? count - i0 : PVW_SHAMIR_POINTS);
+    for (u32 i = 0; i < PVW_SHAMIR_POINTS; ++i) a.index[i] = i < a.n ? indices[i0 + i] : 0;
+    a.x = x + i0 * 4;
+    shamir_points_wide_kernel<<<dim3(1), dim3(PVW_SHAMIR_POINTS), 0, s>>>(a, m);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// ws: x [count][4] (filled by launch_shamir_points_wide) | aux [count + 1][4] | W [t+1][count-t][4]
+hipError_t launch_shamir_weights_wide(u64* ws, size_t count, u32 t, const WideMont& m, hipStream_t s) {
+  const u64* x = ws;
+  u64 *aux = ws + count * 4, *W = aux + (count + 1) * 4;
+  shamir_prod_wide_kernel<<<dim3((unsigned)((count + 1 + SH_WAVES - 1) / SH_WAVES)), dim3(256), 0, s>>>(x, aux, count, t, m);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const size_t threads = (((size_t)t + SHW_WG) / SHW_WG) * (count - t);
+  shamir_weights_wide_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>(x, aux, W, count, t, m);
+  return hipGetLastError();
+}
+
+hipError_t launch_shamir_interp_wide(const ShamirInterpWide& b, hipStream_t s) {
+  return launch_secret_groups(shamir_interp_wide_kernel, b, [&](u32 s0) {
+    ShamirInterpWide p = b;
+    p.shares += (size_t)s0 * b.secret_stride * 4;
+    p.out += (size_t)s0 * 4;
+    if (p.bad) p.bad += s0;
+    return p;
+  }, s);
+}
+
+// One lane per element, by the host routine's own walk (pvw_shamir_wide_from_limbs_host): Horner over the limbs from the top,
+// acc <- acc 2^limb_bits + limb in two steps with multipliers below 2^32, every limb word read mod p first.
+__global__ __launch_bounds__(256) void shamir_wide_fold_kernel(WideMod m, const u64* limbs, size_t count, size_t limb_stride,
+                                                               size_t elem_stride, u32 limb_bits, u32 num_limbs, u64* out) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const u32 h0 = limb_bits / 2, h1 = limb_bits - h0;
+  u64 acc[4] = {0, 0, 0, 0};
+  const u64 zero[4] = {0, 0, 0, 0};
+  for (u32 w = num_limbs; w-- > 0;) {
+    u64 add[4];
+    wide_reduce_word_scaled(limbs[(size_t)w * limb_stride + i * elem_stride], m, add);
+    wide_step(acc, 1u << h0, zero, m);
+    wide_step(acc, 1u << h1, add, m);
+  }
+  wide_shr(acc, m.shift);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) out[i * 4 + k] = acc[k];
+}
+hipError_t launch_shamir_wide_fold(const WideMod& m, const u64* limbs, size_t count, size_t limb_stride, size_t elem_stride, u32 limb_bits,
+                                   u32 num_limbs, u64* out, hipStream_t s) {
+  for (size_t i0 = 0; i0 < count; i0 += (size_t)1 << 30) {      // what one grid's x dimension carries with room to spare
+    const size_t cnt = count - i0 < ((size_t)1 << 30) ? count - i0 : (size_t)1 << 30;
+    shamir_wide_fold_kernel<<<dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s>>>(m, limbs + i0 * elem_stride, cnt, limb_stride,
+                                                                                    elem_stride, limb_bits, num_limbs, out + i0 * 4);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// the product alone on operands of the caller's
+__global__ __launch_bounds__(256) void shamir_wide_mul_kernel(WideMont m, const u64* a, const u64* b, size_t count, u64* out) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  u64 x[4], y[4], r[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { x[k] = a[i * 4 + k]; y[k] = b[i * 4 + k]; }
+  wide_mul(x, y, m, r);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) out[i * 4 + k] = r[k];
+}
+hipError_t launch_shamir_wide_mul(const WideMont& m, const u64* a, const u64* b, size_t count, u64* out, hipStream_t s) {
+  if (!count) return hipSuccess;
+  shamir_wide_mul_kernel<<<dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s>>>(m, a, b, count, out);
+  return hipGetLastError();
+}
+
 }  // namespace pvw

@@ -1,11 +1,13 @@
-// pvw_wide.h -- arithmetic in Z_p for an odd prime p < 2^256, shared by host and gfx950 device code (DESIGN 8.18).
+// pvw_wide.h -- arithmetic in Z_p for an odd prime p < 2^256, shared by host and gfx950 device code (DESIGN 8.18, 8.19).
+// Two parts: the Horner step of the dealing end, on scaled elements (here), and the general product of the receiving end,
+// Montgomery's on plain elements (further down, with its own argument).
 //
-// A wide element is four little-endian u64 words.  Everything below works on SCALED elements: v' = v * 2^s with
+// A wide element is four little-endian u64 words.  The first part works on SCALED elements: v' = v * 2^s with
 // s = 256 - bitlen(p), modulo pn = p * 2^s, whose bit 255 is set.  Addition and multiplication by an integer commute with the
 // scaling, (acc' x + add') mod pn = ((acc x + add) mod p) * 2^s, so a whole Horner walk runs scaled: its inputs are shifted left
 // once and its result is shifted right once, and the quotient estimate below always finds the modulus in the same place.
 //
-// The one arithmetic routine is wide_step: acc <- (acc x + add) mod pn for acc, add < pn and x < 2^32.  With the shares'
+// Its one arithmetic routine is wide_step: acc <- (acc x + add) mod pn for acc, add < pn and x < 2^32.  With the shares'
 // points x = i + 1 <= n < 2^32 Horner from the top coefficient needs nothing else: 8 multiply-adds (v_mad_u64_u32) for
 // T = acc x + add < pn 2^32, one quotient below 2^32, 8 more for T - q pn, one conditional subtraction.
 //
@@ -128,6 +130,20 @@ PVW_HD void wide_reduce_scaled(const u64* w, const WideMod& m, u64 (&out)[4]) {
   for (int i = 0; i < 4; ++i) out[i] = acc[i];
 }
 
+// the same for one word v (the upper words' digits are 0 and leave acc = 0): the digits come out of a register by shifts
+PVW_HD void wide_reduce_word_scaled(u64 v, const WideMod& m, u64 (&out)[4]) {
+  const u32 dw = wide_digit_bits(m), nd = (64 + dw - 1) / dw;
+  const u64 mask = ((u64)1 << dw) - 1;
+  u64 acc[4] = {0, 0, 0, 0};
+  for (u32 k = nd; k-- > 0;) {
+    u64 add[4] = {(v >> (k * dw)) & mask, 0, 0, 0};
+    wide_shl(add, m.shift);
+    wide_step(acc, (u32)1 << dw, add, m);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) out[i] = acc[i];
+}
+
 // a_{d,j} scaled: the first accepted draw of the stream (key, (DOM_SHAMIR << 32) | j).  An attempt is four consecutive
 // next_u64() words, word 0 least significant, masked to the low bitlen(p) bits and accepted when below p.  Shifting the 256-bit
 // draw left by `shift` drops exactly the bits the mask drops, so the scaled candidate is the shifted draw and the test is
@@ -154,7 +170,232 @@ PVW_HD void wide_draw_scaled(const ChaChaKey& key, u32 domain, u32 j, const Wide
   }
 }
 
-// host: the constants of p (odd, >= 3, below 2^256)
+// ------------------------------------------------------------------------ the general product
+// wide_step multiplies by x < 2^32 only.  Checked reconstruction multiplies two field elements: a share by a Lagrange weight.
+// The product is Montgomery's over eight 32-bit digits, R = 2^256, on PLAIN elements (no scaling), because of who pays for
+// the conversions: the weights are public and made once, so they are stored as W R mod p; the shares are secret, arrive as
+// they are and need no conversion at all, for REDC(share * (W R)) = share W mod p is a plain field element.
+//
+// Three pieces, all with static digit indices only (every loop below is fully unrolled):
+//   wide_mul_full   P = a b, sixteen digits, schoolbook by rows: 64 multiply-adds (v_mad_u64_u32).  In row i the running value
+//                   a_i b_j + P[i+j] + c <= (2^32 - 1)^2 + 2 (2^32 - 1) = 2^64 - 1 fits a u64.
+//   wide_acc_add    T <- T + P, kept BELOW p R.  Invariant T < p R.  One operand of P is below p and the other below R, so
+//                   P <= (p - 1)(R - 1) < p R and T + P < 2 p R < 2^513: sixteen digits and one carry bit.  T + P >= p R holds
+//                   exactly when the carry is set or the upper eight digits are >= p (the lower eight are below R), and then
+//                   p is taken off the upper half ONCE: T + P - p R < p R again.  A sum of any number of products is therefore
+//                   accumulated unreduced at 64 multiply-adds a term, and reduced once at the end.
+//   wide_redc       out = T R^-1 mod p for T < p R.  Row i takes m = T[i] n0 mod 2^32 (n0 = -p^-1 mod 2^32) and adds m p 2^(32 i),
+//                   which clears digit i; after eight rows the lower half is 0 and the upper half plus the last carry is
+//                   U = (T + M p) / R with M < R, so U < (p R + R p) / R = 2 p and U = T R^-1 (mod p): ONE conditional
+//                   subtraction of p ends it (taken when the carry is set or the eight digits are >= p).  Carries: row i's
+//                   last carry c and the bit e left by row i - 1 go into digit i + 8 as T[i+8] + c + e <= 2 (2^32 - 1) + 1;
+//                   digit i + 8 is touched by later rows only after that, and digit i + 9 by nobody before row i + 1 ends.
+// wide_mont_mul(a, b) = REDC(a b) = a b R^-1 mod p, below p, for a < R and b < p (or the other way round).
+// wide_mul(a, b) = REDC(REDC(a b) r2) with r2 = R^2 mod p: a b mod p for a < R, b < p -- the general product in Z_p.
+// Any four words w are read mod p by the same two steps: wide_mont_in(w) = REDC(w r2) = w R mod p (w < R, r2 < p) and
+// wide_redc of that alone (upper half 0: T < R <= p R) gives w mod p.
+// Inversion is Fermat's, a^(p-2), 256 squarings and a product per set bit: about 380 products for a 256-bit p.
+struct WideMont {
+  u64 p[4];     // the modulus: odd, >= 3
+  u64 r2[4];    // 2^512 mod p
+  u64 one[4];   // 2^256 mod p: 1 in Montgomery form
+  u32 n0;       // -p^-1 mod 2^32
+};
+
+#define PVW_WIDE_DIGIT(a, i) ((u32)((a)[(i) >> 1] >> (32 * ((i) & 1))))
+
+PVW_HD void wide_mul_full(const u64 (&a)[4], const u64 (&b)[4], u32 (&P)[16]) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) P[i] = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const u32 ai = PVW_WIDE_DIGIT(a, i);
+    u64 c = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const u64 v = (u64)ai * PVW_WIDE_DIGIT(b, j) + P[i + j] + c;
+      P[i + j] = (u32)v;
+      c = v >> 32;
+    }
+    P[i + 8] = (u32)c;
+  }
+}
+
+// h (eight digits, with `top` as the ninth) >= p ? h - p : h, mod 2^256
+PVW_HD void wide_cond_sub(u32 (&h)[8], u32 top, const u64 (&p)[4]) {
+  bool lt = false;                                   // h < p over the eight digits
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const u32 pi = PVW_WIDE_DIGIT(p, i);
+    lt = h[i] < pi || (h[i] == pi && lt);
+  }
+  if (top || !lt) {
+    i64 bw = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const i64 d = (i64)h[i] - (i64)PVW_WIDE_DIGIT(p, i) + bw;   // in (-2^32, 2^32)
+      h[i] = (u32)d;
+      bw = d >> 32;                                  // 0 or -1
+    }
+  }
+}
+
+PVW_HD void wide_acc_zero(u32 (&T)[16]) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) T[i] = 0;
+}
+
+// T <- T + P - (T + P >= p R ? p R : 0); T < p R, P < p R
+PVW_HD void wide_acc_add(u32 (&T)[16], const u32 (&P)[16], const WideMont& m) {
+  u64 c = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const u64 v = (u64)T[i] + P[i] + c;
+    T[i] = (u32)v;
+    c = v >> 32;
+  }
+  u32 h[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) h[i] = T[8 + i];
+  wide_cond_sub(h, (u32)c, m.p);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) T[8 + i] = h[i];
+}
+
+// out = T R^-1 mod p, below p; T < p R (T is used up)
+PVW_HD void wide_redc(u32 (&T)[16], const WideMont& m, u64 (&out)[4]) {
+  u32 e = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const u32 q = T[i] * m.n0;
+    u64 c = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const u64 v = (u64)q * PVW_WIDE_DIGIT(m.p, j) + T[i + j] + c;
+      T[i + j] = (u32)v;
+      c = v >> 32;
+    }
+    const u64 s = (u64)T[i + 8] + c + e;
+    T[i + 8] = (u32)s;
+    e = (u32)(s >> 32);
+  }
+  u32 h[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) h[i] = T[8 + i];
+  wide_cond_sub(h, e, m.p);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) out[i] = (u64)h[2 * i] | ((u64)h[2 * i + 1] << 32);
+}
+
+// out = a b R^-1 mod p; a < 2^256 and b < p (or the other way round).  out may be a or b.
+PVW_HD void wide_mont_mul(const u64 (&a)[4], const u64 (&b)[4], const WideMont& m, u64 (&out)[4]) {
+  u32 T[16];
+  wide_mul_full(a, b, T);
+  wide_redc(T, m, out);
+}
+// out = a b mod p; a < 2^256, b < p
+PVW_HD void wide_mul(const u64 (&a)[4], const u64 (&b)[4], const WideMont& m, u64 (&out)[4]) {
+  u64 t[4];
+  wide_mont_mul(a, b, m, t);
+  wide_mont_mul(t, m.r2, m, out);
+}
+// out = w R mod p for any four words w, and back: out = a R^-1 mod p for a < 2^256
+PVW_HD void wide_mont_in(const u64 (&w)[4], const WideMont& m, u64 (&out)[4]) { wide_mont_mul(w, m.r2, m, out); }
+PVW_HD void wide_mont_out(const u64 (&a)[4], const WideMont& m, u64 (&out)[4]) {
+  u32 T[16];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { T[i] = PVW_WIDE_DIGIT(a, i); T[8 + i] = 0; }
+  wide_redc(T, m, out);
+}
+// out = w mod p for any four words w
+PVW_HD void wide_reduce_p(const u64 (&w)[4], const WideMont& m, u64 (&out)[4]) {
+  u64 t[4];
+  wide_mont_in(w, m, t);
+  wide_mont_out(t, m, out);
+}
+
+// a <- (a + b) mod p and a <- (a - b) mod p for a, b < p
+PVW_HD void wide_add_p(u64 (&a)[4], const u64 (&b)[4], const WideMont& m) {
+  u32 h[8];
+  u64 c = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const u64 v = (u64)PVW_WIDE_DIGIT(a, i) + PVW_WIDE_DIGIT(b, i) + c;
+    h[i] = (u32)v;
+    c = v >> 32;
+  }
+  wide_cond_sub(h, (u32)c, m.p);                       // a + b < 2 p
+#pragma unroll
+  for (int i = 0; i < 4; ++i) a[i] = (u64)h[2 * i] | ((u64)h[2 * i + 1] << 32);
+}
+PVW_HD void wide_sub_p(u64 (&a)[4], const u64 (&b)[4], const WideMont& m) {
+  u64 r[4], br = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const u64 s1 = a[i] - b[i], s2 = s1 - br;
+    br = (a[i] < b[i]) | (s1 < br);
+    r[i] = s2;
+  }
+  u64 c = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {                        // + p where the difference went below 0
+    const u64 add = br ? m.p[i] : 0, s1 = r[i] + add, s2 = s1 + c;
+    c = (s1 < add) | (s2 < s1);
+    a[i] = s2;
+  }
+}
+
+// out = a^-1 in Montgomery form for a != 0 in Montgomery form: a^(p-2), bits from the top, the exponent's words by static index
+PVW_HD void wide_mont_inv(const u64 (&a)[4], const WideMont& m, u64 (&out)[4]) {
+  u64 e[4], br = 2;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const u64 v = m.p[i];
+    e[i] = v - br;
+    br = v < br;
+  }
+  u64 r[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r[i] = m.one[i];
+#pragma unroll
+  for (int w = 3; w >= 0; --w) {
+    u64 ew = e[w];
+#pragma unroll 1
+    for (int b = 0; b < 64; ++b) {
+      wide_mont_mul(r, r, m, r);
+      if (ew >> 63) wide_mont_mul(r, a, m, r);
+      ew <<= 1;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) out[i] = r[i];
+}
+
+// host: the constants of p (odd, >= 3, below 2^256), for the product above and for the step at the top
+inline WideMont make_wide_mont(const u64 p[4]) {
+  WideMont m;
+  for (int i = 0; i < 4; ++i) m.p[i] = p[i];
+  u32 inv = (u32)p[0];                                 // p p = 1 mod 8; each Newton step doubles the correct bits
+  for (int i = 0; i < 5; ++i) inv *= 2 - (u32)p[0] * inv;
+  m.n0 = 0u - inv;
+  u64 v[4] = {1, 0, 0, 0};                             // 2^k mod p by doubling: v < p, 2 v < 2^257
+  for (int k = 0; k < 512; ++k) {
+    const u64 top = v[3] >> 63;
+    wide_shl(v, 1);
+    if (top || !wide_less(v, m.p)) {
+      u64 br = 0;
+      for (int i = 0; i < 4; ++i) {
+        const u64 s1 = v[i] - m.p[i], s2 = s1 - br;
+        br = (v[i] < m.p[i]) | (s1 < br);
+        v[i] = s2;
+      }
+    }
+    if (k == 255) for (int i = 0; i < 4; ++i) m.one[i] = v[i];
+  }
+  for (int i = 0; i < 4; ++i) m.r2[i] = v[i];
+  return m;
+}
+
 inline WideMod make_wide_mod(const u64 p[4]) {
   WideMod m;
   u32 bits = 0;

@@ -788,6 +788,37 @@ inline std::vector<uint64_t> shamir_reconstruct_wide(const std::vector<uint64_t>
   check(pvw_shamir_reconstruct_wide(plain_modulus.data(), indices.data(), shares.data(), indices.size(), S, out.data()));
   return out;
 }
+// ---- the receiving end over a prime below 2^256 ----
+// shamir_wide_from_limbs where the limbs lie (pvw_shamir_wide_from_limbs_device): device pointers, count elements [count][4] at
+// d_out, asynchronous on `stream` (NULL: the context's).  Strides (count, 1) read limb planes, (1, num_limbs) the
+// [party][dealer * NL + w] result of a decrypt-all in place.
+inline void shamir_wide_from_limbs_device(const std::shared_ptr<PvwParameters>& p, const Wide& plain_modulus, const uint64_t* d_limbs,
+                                          size_t count, size_t limb_stride, size_t elem_stride, uint32_t limb_bits, uint32_t num_limbs,
+                                          uint64_t* d_out, void* stream = nullptr) {
+  check(pvw_shamir_wide_from_limbs_device(p->ctx, plain_modulus.data(), d_limbs, count, limb_stride, elem_stride, limb_bits, num_limbs,
+                                          d_out, stream));
+}
+struct CheckedWideSecrets {
+  std::vector<uint64_t> secrets;    // [num_secrets][4]: the value at 0 of the polynomial through each secret's basis shares
+  std::vector<uint32_t> bad;        // [num_secrets]: columns beyond the basis whose share is off that polynomial
+  std::vector<uint32_t> col_bad;    // [indices.size()]: secrets that deviate in each column (0 for the basis columns)
+};
+// shamir_reconstruct_checked over an odd prime below 2^256.  The first degree + 1 of `indices` are the basis.  shares
+// [num_secrets][indices.size()][4] row-major, or party_major [indices.size()][num_secrets][4]; any words, read mod p.  On the
+// device (pvw_shamir_reconstruct_wide_checked); host = true: the plain C++ restatement (no GPU; p may be null).
+inline CheckedWideSecrets shamir_reconstruct_wide_checked(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& indices,
+                                                          const std::vector<uint64_t>& shares, uint32_t degree, const Wide& plain_modulus,
+                                                          bool party_major = false, bool host = false) {
+  const size_t count = indices.size();
+  if (count == 0 || shares.empty() || shares.size() % (count * PVW_WIDE_WORDS)) throw PvwError(15, "shares must hold one element per index and secret");
+  const size_t S = shares.size() / (count * PVW_WIDE_WORDS), ss = party_major ? 1 : count, ps = party_major ? S : 1;
+  CheckedWideSecrets r{std::vector<uint64_t>(S * PVW_WIDE_WORDS), std::vector<uint32_t>(S), std::vector<uint32_t>(count)};
+  check(host ? pvw_shamir_reconstruct_wide_checked_host(plain_modulus.data(), degree, indices.data(), count, shares.data(), S, ss, ps,
+                                                        r.secrets.data(), r.bad.data(), r.col_bad.data())
+             : pvw_shamir_reconstruct_wide_checked(p->ctx, plain_modulus.data(), degree, indices.data(), count, shares.data(), S, ss, ps,
+                                                   r.secrets.data(), r.bad.data(), r.col_bad.data()));
+  return r;
+}
 // the share matrix of the checked, corrected and evaluate calls: its shape and the strides of its layout, in words
 struct ShareMatrix {
   size_t count, S, words, ss, ps;   // columns, secrets, mask words per secret, secret stride, point stride

@@ -174,6 +174,12 @@ extern "C" {
     pub fn pvw_shamir_wide_from_limbs_host(plain_modulus: *const u64, limbs: *const u64, count: usize, limb_bits: u32, num_limbs: u32, out: *mut u64) -> i32;
     pub fn pvw_shamir_reconstruct_wide(plain_modulus: *const u64, indices: *const u64, shares: *const u64, count: usize, num_secrets: usize, out: *mut u64) -> i32;
     pub fn pvw_selftest_shamir_wide_step(ctx: *mut PvwCtx, plain_modulus: *const u64, acc: *const u64, x: *const u64, add: *const u64, count: usize, out: *mut u64) -> i32;
+    // ---- the receiving end over a prime below 2^256: device fold of limbs, checked reconstruction ----
+    pub fn pvw_shamir_wide_from_limbs_device(ctx: *mut PvwCtx, plain_modulus: *const u64, d_limbs: *const u64, count: usize, limb_stride: usize, elem_stride: usize, limb_bits: u32, num_limbs: u32, d_out: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_reconstruct_wide_checked_host(plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, out: *mut u64, bad: *mut u32, col_bad: *mut u32) -> i32;
+    pub fn pvw_shamir_reconstruct_wide_checked_device(ctx: *mut PvwCtx, plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, d_shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, d_out: *mut u64, d_bad: *mut u32, d_col_bad: *mut u32, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_reconstruct_wide_checked(ctx: *mut PvwCtx, plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, out: *mut u64, bad: *mut u32, col_bad: *mut u32) -> i32;
+    pub fn pvw_selftest_shamir_wide_mul(ctx: *mut PvwCtx, plain_modulus: *const u64, a: *const u64, b: *const u64, count: usize, out: *mut u64) -> i32;
     pub fn pvw_shamir_shares_packed_host(ctx: *const PvwCtx, secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: u64, seeds: *const u8, coeffs: *const u64, shares_out: *mut u64) -> i32;
     pub fn pvw_shamir_shares_packed_device(ctx: *mut PvwCtx, d_secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: u64, seeds: *const u8, d_coeffs: *const u64, d_shares: *mut u64, stream: *mut c_void) -> i32;
     pub fn pvw_shamir_shares_packed(ctx: *mut PvwCtx, secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: u64, seeds: *const u8, coeffs: *const u64, shares_out: *mut u64) -> i32;

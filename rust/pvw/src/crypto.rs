@@ -676,6 +676,48 @@ pub fn shamir_reconstruct_wide(indices: &[u64], shares: &[Wide], plain_modulus: 
     Ok(out)
 }
 
+/// EXTENSION: what `shamir_reconstruct_wide_checked` reports: `CheckedSecrets` with wide secrets.
+pub struct CheckedWideSecrets {
+    /// the value at 0 of the polynomial through each secret's basis shares
+    pub secrets: Vec<Wide>,
+    /// per secret: columns beyond the basis whose share is off that polynomial
+    pub bad: Vec<u32>,
+    /// per column: secrets that deviate there (0 for the basis columns)
+    pub col_bad: Vec<u32>,
+}
+
+/// EXTENSION: `shamir_reconstruct_checked` over an odd prime below 2^256, on the device
+/// (`pvw_shamir_reconstruct_wide_checked`).  The first `degree + 1` of `indices` are the basis.  `shares` is
+/// `[num_secrets][indices.len()]` row-major, or with `party_major` `[indices.len()][num_secrets]`; any words, read mod p.
+pub fn shamir_reconstruct_wide_checked(params: &Arc<PvwParameters>, indices: &[u64], shares: &[Wide], degree: u32, plain_modulus: &Wide,
+                                       party_major: bool) -> Result<CheckedWideSecrets> {
+    if indices.is_empty() || shares.is_empty() || shares.len() % indices.len() != 0 {
+        return Err(PvwError::InvalidParameters("shares must hold one element per index and secret".into()));
+    }
+    let (count, num) = (indices.len(), shares.len() / indices.len());
+    let (ss, ps) = if party_major { (1, num) } else { (count, 1) };
+    let mut r = CheckedWideSecrets { secrets: vec![[0u64; 4]; num], bad: vec![0u32; num], col_bad: vec![0u32; count] };
+    check(unsafe {
+        sys::pvw_shamir_reconstruct_wide_checked(params.hip.raw(), plain_modulus.as_ptr(), degree, indices.as_ptr(), count,
+                                                 shares.as_ptr() as *const u64, num, ss, ps, r.secrets.as_mut_ptr() as *mut u64,
+                                                 r.bad.as_mut_ptr(), r.col_bad.as_mut_ptr())
+    })?;
+    Ok(r)
+}
+
+/// EXTENSION: `shamir_wide_from_limbs` where the limbs lie (`pvw_shamir_wide_from_limbs_device`): device
+/// pointers, `count` elements of `[count][4]` words written at `d_out`, asynchronous on `stream` (null: the context's).
+/// Strides `(count, 1)` read limb planes, `(1, num_limbs)` the `[party][dealer * NL + w]` result of a decrypt-all in place.
+///
+/// # Safety
+/// `d_limbs` and `d_out` must be device buffers that hold what the strides reach and `count * 4` words.
+pub unsafe fn shamir_wide_from_limbs_device(params: &Arc<PvwParameters>, plain_modulus: &Wide, d_limbs: *const u64, count: usize,
+                                            limb_stride: usize, elem_stride: usize, limb_bits: u32, num_limbs: u32, d_out: *mut u64,
+                                            stream: *mut std::ffi::c_void) -> Result<()> {
+    check(sys::pvw_shamir_wide_from_limbs_device(params.hip.raw(), plain_modulus.as_ptr(), d_limbs, count, limb_stride, elem_stride,
+                                                 limb_bits, num_limbs, d_out, stream))
+}
+
 /// The share matrix of the checked, corrected and evaluate calls: (columns, secrets, secret stride, point stride), in words.
 fn share_matrix(indices: &[u64], shares: &[u64], party_major: bool) -> Result<(usize, usize, usize, usize)> {
     if indices.is_empty() || shares.is_empty() || shares.len() % indices.len() != 0 {
