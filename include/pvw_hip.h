@@ -1099,6 +1099,39 @@ PVW_API int32_t pvw_shamir_reconstruct_wide_checked(pvw_ctx* ctx, const uint64_t
                                                     const uint64_t* indices, size_t count, const uint64_t* shares, size_t num_secrets,
                                                     size_t secret_stride, size_t point_stride, uint64_t* out, uint32_t* bad,
                                                     uint32_t* col_bad);
+/* Corrected reconstruction over a prime field of up to 256 bits: the contract of
+ * pvw_shamir_reconstruct_corrected*  word for word, with wide elements.  Arguments as for
+ * pvw_shamir_reconstruct_wide_checked*.  No column is a basis: with r = count - degree - 1 redundant columns, row s is DECODABLE
+ * iff some polynomial F_s of degree <= t disagrees with it in at most E = r / 2 columns (F_s is then unique), whichever columns.
+ *   out [num_secrets][4] = F_s(0), 0 for an undecodable row.  nerr [num_secrets] (or NULL): the number of disagreeing columns, or
+ *   PVW_SHAMIR_UNDECODABLE.  col_err [count] (or NULL): for each column, in how many decodable rows it disagrees.  err_mask
+ *   [num_secrets][ceil(count / 64)] (or NULL): bit c % 64 of word c / 64 of row s set iff column c disagrees in row s; a zero
+ *   row for an undecodable secret, padding bits 0.
+ *   r = 0 is plain interpolation through all columns, r = 1 detects only.  The order of the columns changes no output; mask
+ *   bits and col_err move with their columns.  The three forms agree bit for bit on every input.
+ * PVW_ERR_INVALID_PARAMETERS before any device work, nothing written: what pvw_shamir_reconstruct_wide_checked* refuses, in its
+ * order; and, in the two device forms, r / 2 + 1 > PVW_SHAMIR_WIDE_MAX_LOCATOR (r >= 4096): the two polynomials of one wave
+ * take 2 (E + 1) 32 bytes of LDS, 128 KiB at the bound. */
+#define PVW_SHAMIR_WIDE_MAX_LOCATOR 2048
+/* the contract in plain C++ on the host cores (no context, no GPU), Berlekamp-Welch: cubic in count, a reference */
+PVW_API int32_t pvw_shamir_reconstruct_wide_corrected_host(const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                           size_t count, const uint64_t* shares, size_t num_secrets,
+                                                           size_t secret_stride, size_t point_stride, uint64_t* out, uint32_t* nerr,
+                                                           uint32_t* col_err, uint64_t* err_mask);
+/* device pointers (indices and plain_modulus stay HOST pointers, read before the call returns), asynchronous on `stream`.  The
+ * public matrices and the per-secret scratch live in the stream's workspace, sized by the call: under stream capture the call
+ * needs an earlier call with the same (degree, count) and at least as many secrets on that stream outside capture; without it:
+ * the error of pvw_shamir_reconstruct_wide_checked_device, nothing enqueued. */
+PVW_API int32_t pvw_shamir_reconstruct_wide_corrected_device(pvw_ctx* ctx, const uint64_t* plain_modulus, uint32_t degree,
+                                                             const uint64_t* indices, size_t count, const uint64_t* d_shares,
+                                                             size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                                             uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err,
+                                                             uint64_t* d_err_mask, void* stream);
+/* host buffers (synchronous), staged in bounded pieces; the staged shares and secrets are cleared before the call returns */
+PVW_API int32_t pvw_shamir_reconstruct_wide_corrected(pvw_ctx* ctx, const uint64_t* plain_modulus, uint32_t degree,
+                                                      const uint64_t* indices, size_t count, const uint64_t* shares,
+                                                      size_t num_secrets, size_t secret_stride, size_t point_stride, uint64_t* out,
+                                                      uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask);
 /* SELF-TEST: the kernels' general product on the device, out[i] = a[i] b[i] mod p for a, b [count][4] below p (anything else:
  * INVALID_PARAMETERS). */
 PVW_API int32_t pvw_selftest_shamir_wide_mul(pvw_ctx* ctx, const uint64_t* plain_modulus, const uint64_t* a, const uint64_t* b,

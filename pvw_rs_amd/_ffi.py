@@ -172,6 +172,10 @@ _SIGNATURES = {
     "pvw_shamir_reconstruct_wide_checked_host": [_P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P],
     "pvw_shamir_reconstruct_wide_checked_device": [_P, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P, _P],
     "pvw_shamir_reconstruct_wide_checked": [_P, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P],
+    "pvw_shamir_reconstruct_wide_corrected_host": [_P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P, _P],
+    "pvw_shamir_reconstruct_wide_corrected_device": [_P, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P, _P,
+                                                     _P],
+    "pvw_shamir_reconstruct_wide_corrected": [_P, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P, _P],
     "pvw_selftest_shamir_wide_mul": [_P, _P, _P, _P, C.c_size_t, _P],
     "pvw_shamir_shares_packed_host": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P],
     "pvw_shamir_shares_packed_device": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P, _P],

@@ -1069,12 +1069,9 @@ def shamir_wide_from_limbs_device(params: PvwParameters, limbs, plain_modulus: i
     return out
 
 
-def shamir_reconstruct_wide_checked(params: Optional[PvwParameters], indices: Sequence[int], shares, degree: int, plain_modulus: int, *,
-                                    host: bool = False, layout: str = "secret_major") -> Tuple[List[int], np.ndarray, np.ndarray]:
-    """EXTENSION (DESIGN 8.19): shamir_reconstruct_checked over an odd prime plain_modulus < 2^256.  shares: a matrix of Python
-    ints (any value: the low 256 bits, read mod p) or uint64 words [...][...][4], "secret_major" [num_secrets][len(indices)] or
-    "party_major" [len(indices)][num_secrets].  On the device (pvw_shamir_reconstruct_wide_checked); host=True: the plain C++
-    restatement (pvw_shamir_reconstruct_wide_checked_host, no GPU; params may be None).  Returns (secrets as ints, bad, col_bad)."""
+def _wide_share_matrix(indices: Sequence[int], shares, layout: str):
+    """(idx, sh, S, count, strides) of the wide checked and corrected calls: the indices as words, the share matrix as uint64
+    words [...][...][4], and the (secret, point) strides of `layout` in elements"""
     if layout not in ("secret_major", "party_major"):
         raise ValueError(layout)
     idx = _words(indices)
@@ -1090,12 +1087,41 @@ def shamir_reconstruct_wide_checked(params: Optional[PvwParameters], indices: Se
     if cols != count:
         raise PvwError(15, f"expected {count} shares per secret, got {cols}")
     strides = (count, 1) if layout == "secret_major" else (1, S)
+    return idx, sh, S, count, strides
+
+
+def shamir_reconstruct_wide_checked(params: Optional[PvwParameters], indices: Sequence[int], shares, degree: int, plain_modulus: int, *,
+                                    host: bool = False, layout: str = "secret_major") -> Tuple[List[int], np.ndarray, np.ndarray]:
+    """EXTENSION (DESIGN 8.19): shamir_reconstruct_checked over an odd prime plain_modulus < 2^256.  shares: a matrix of Python
+    ints (any value: the low 256 bits, read mod p) or uint64 words [...][...][4], "secret_major" [num_secrets][len(indices)] or
+    "party_major" [len(indices)][num_secrets].  On the device (pvw_shamir_reconstruct_wide_checked); host=True: the plain C++
+    restatement (pvw_shamir_reconstruct_wide_checked_host, no GPU; params may be None).  Returns (secrets as ints, bad, col_bad)."""
+    idx, sh, S, count, strides = _wide_share_matrix(indices, shares, layout)
     out = np.zeros((S, WIDE_WORDS), dtype=np.uint64)
     bad, col_bad = np.zeros(S, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
     args = (_ptr(_wide_modulus(plain_modulus)), int(degree), _ptr(idx), count, _ptr(sh), S, strides[0], strides[1], _ptr(out), _ptr(bad),
             _ptr(col_bad))
     _reconstruct_call(params, "shamir_reconstruct_wide_checked", host, args)
     return _wide_ints(out), bad, col_bad
+
+
+def shamir_reconstruct_wide_corrected(params: Optional[PvwParameters], indices: Sequence[int], shares, degree: int, plain_modulus: int, *,
+                                      host: bool = False,
+                                      layout: str = "secret_major") -> Tuple[List[int], np.ndarray, np.ndarray, np.ndarray]:
+    """EXTENSION: shamir_reconstruct_corrected over an odd prime plain_modulus < 2^256: the secrets although up to
+    E = (len(indices) - degree - 1) // 2 shares of each are wrong, in whichever columns.  shares and layout as
+    shamir_reconstruct_wide_checked.  On the device (pvw_shamir_reconstruct_wide_corrected); host=True: the plain C++ restatement
+    (pvw_shamir_reconstruct_wide_corrected_host, Berlekamp-Welch, no GPU; params may be None).  Returns (secrets as ints, nerr,
+    col_err, err_mask) as shamir_reconstruct_corrected does: an undecodable row has secret 0, nerr SHAMIR_UNDECODABLE and an empty
+    mask row."""
+    idx, sh, S, count, strides = _wide_share_matrix(indices, shares, layout)
+    out = np.zeros((S, WIDE_WORDS), dtype=np.uint64)
+    nerr, col_err = np.zeros(S, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
+    err_mask = np.zeros((S, (count + 63) // 64), dtype=np.uint64)
+    args = (_ptr(_wide_modulus(plain_modulus)), int(degree), _ptr(idx), count, _ptr(sh), S, strides[0], strides[1], _ptr(out), _ptr(nerr),
+            _ptr(col_err), _ptr(err_mask))
+    _reconstruct_call(params, "shamir_reconstruct_wide_corrected", host, args)
+    return _wide_ints(out), nerr, col_err, err_mask
 
 
 def _share_matrix(indices: Sequence[int], shares, layout: str):

@@ -156,6 +156,8 @@ struct Workspace {
   size_t packw_bytes = 0;
   u64* correct = nullptr;    // corrected reconstruction: M | public matrices | syndromes | locators (CorrectLayout; grown by the call)
   size_t correct_bytes = 0;
+  u64* correct_wide = nullptr;   // the same over a prime below 2^256 (CorrectWideLayout)
+  size_t correct_wide_bytes = 0;
   // helper stream + events (ws_aux): decode of chunk i under the MAC of chunk i+1, key uploads under key generation
   hipStream_t aux = nullptr;
   bool aux_used = false;     // by the current host call: drained by host_call
@@ -553,6 +555,7 @@ static int32_t ensure_device(pvw_ctx* c) {
   PVW_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   PVW_HIP(init_kernel_attributes());          // per device: dynamic-LDS limits of the decode kernels
   PVW_HIP(init_wire_attributes());            // ... and of the wire codec
+  PVW_HIP(init_shamir_attributes());          // ... and of the wide Berlekamp-Massey kernel
   PVW_TRY(upload_tables(c));
   c->dev_ready = true;
   c->roots_locked = true;
@@ -640,6 +643,8 @@ static void ws_free(Workspace* w) {
   hipFree(w->packw);
   if (w->correct) hipMemset(w->correct, 0, w->correct_bytes);   // M of the last call, if its wipe did not run
   hipFree(w->correct);
+  if (w->correct_wide) hipMemset(w->correct_wide, 0, w->correct_wide_bytes);
+  hipFree(w->correct_wide);
   for (hipEvent_t e : w->events) hipEventDestroy(e);
   if (w->ahead_block) hipMemset(w->ahead_block, 0, w->ahead_set_bytes * w->ahead.slots());   // r-hat and errors of the last encrypts
   hipFree(w->ahead_block);
@@ -4440,6 +4445,301 @@ int32_t pvw_shamir_reconstruct_wide_checked(pvw_ctx* c, const uint64_t* plain_mo
       PVW_HIP(hipStreamSynchronize(w->stream));                  // the next piece reuses the staging
     }
     if (col_bad) PVW_HIP(hipMemcpyAsync(col_bad, d_col, count * 4, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
+  volatile u64* vp = packed.data();
+  for (size_t i = 0; i < packed.size(); ++i) vp[i] = 0;
+  return rc;
+}
+
+// ------------------------------------------------------------------------ corrected reconstruction below 2^256
+// The contract of 8.11 with wide elements: row s is decodable iff some F_s of degree <= t disagrees with it in at most
+// E = (count - t - 1) / 2 columns; F_s is then unique, out[s] = F_s(0) and the disagreeing columns are reported.
+
+static inline u64 (&wel(std::vector<u64>& v, size_t i))[4] { return *(u64(*)[4]) & v[i * 4]; }
+
+// The contract in plain C++ (no GPU), by another method than the kernels' (syndromes, Berlekamp-Massey, locator roots):
+// Berlekamp-Welch as berlekamp_welch_host runs it, over the Montgomery product of pvw_wide.h with every element times R (a zero
+// test and an equality test do not depend on the form; the secret is taken out of it at the end).  Its last step is the
+// contract itself: N / W is compared with the row in every column.  Cubic in count per secret.
+static void berlekamp_welch_wide_host(const ReconstructWide& r, const uint64_t* shares, uint64_t* out, uint32_t* nerr, uint32_t* col_err,
+                                      uint64_t* err_mask) {
+  const WideMont mm = make_wide_mont(r.p);
+  const size_t count = r.count, t = r.degree, E = (count - t - 1) / 2, nq = t + E + 1, nu = nq + E, ld = nu + 1;
+  const size_t words = (count + 63) / 64;
+  std::vector<u64> x(count * 4), y(count * 4), A(count * ld * 4), sol(nu * 4), W((E + 1) * 4), N(nq * 4);
+  std::vector<size_t> pivot_col;
+  const u64 zero[4] = {0, 0, 0, 0};
+  auto set = [](u64(&o)[4], const u64(&a)[4]) { for (int i = 0; i < 4; ++i) o[i] = a[i]; };
+  auto is0 = [](const u64(&a)[4]) { return !(a[0] | a[1] | a[2] | a[3]); };
+  for (size_t c = 0; c < count; ++c) {
+    const u64 xw[4] = {r.indices[c] + 1, r.indices[c] + 1 == 0 ? (u64)1 : (u64)0, 0, 0};
+    wide_mont_in(xw, mm, wel(x, c));
+  }
+  if (col_err) std::fill(col_err, col_err + count, 0u);
+  for (size_t s = 0; s < r.S; ++s) {
+    for (size_t c = 0; c < count; ++c) {
+      const u64* sp = shares + (s * r.secret_stride + c * r.point_stride) * 4;
+      const u64 w[4] = {sp[0], sp[1], sp[2], sp[3]};
+      wide_mont_in(w, mm, wel(y, c));
+    }
+    // row c: sum_j N_j x^j - y sum_{k < E} W_k x^k = y x^E
+    for (size_t c = 0; c < count; ++c) {
+      u64 pw[4], v[4];
+      set(pw, mm.one);
+      for (size_t j = 0; j < nq; ++j) {
+        set(wel(A, c * ld + j), pw);
+        if (j <= E) {
+          wide_mont_mul(wel(y, c), pw, mm, v);
+          if (j == E) set(wel(A, c * ld + nu), v);
+          else {
+            u64 neg[4] = {0, 0, 0, 0};
+            wide_sub_p(neg, v, mm);
+            set(wel(A, c * ld + nq + j), neg);
+          }
+        }
+        wide_mont_mul(pw, wel(x, c), mm, pw);
+      }
+    }
+    pivot_col.clear();
+    size_t rank = 0;
+    for (size_t col = 0; col < nu && rank < count; ++col) {
+      size_t pr = rank;
+      while (pr < count && is0(wel(A, pr * ld + col))) ++pr;
+      if (pr == count) continue;
+      if (pr != rank) std::swap_ranges(&A[pr * ld * 4], &A[(pr + 1) * ld * 4], &A[rank * ld * 4]);
+      u64 inv[4];
+      wide_mont_inv(wel(A, rank * ld + col), mm, inv);
+      for (size_t j = col; j <= nu; ++j) wide_mont_mul(wel(A, rank * ld + j), inv, mm, wel(A, rank * ld + j));
+      for (size_t i = 0; i < count; ++i) {
+        u64 f[4];
+        set(f, wel(A, i * ld + col));
+        if (i == rank || is0(f)) continue;
+        for (size_t j = col; j <= nu; ++j) {
+          u64 v[4];
+          wide_mont_mul(f, wel(A, rank * ld + j), mm, v);
+          wide_sub_p(wel(A, i * ld + j), v, mm);
+        }
+      }
+      pivot_col.push_back(col);
+      ++rank;
+    }
+    bool ok = true;
+    for (size_t i = rank; i < count && ok; ++i) ok = is0(wel(A, i * ld + nu));   // a row 0 = b: no solution
+    u64 secret[4] = {0, 0, 0, 0};
+    std::vector<size_t> wrong;
+    if (ok) {
+      std::fill(sol.begin(), sol.end(), (u64)0);                                 // free unknowns: 0
+      for (size_t i = 0; i < rank; ++i) set(wel(sol, pivot_col[i]), wel(A, i * ld + nu));
+      for (size_t j = 0; j < nq; ++j) set(wel(N, j), wel(sol, j));
+      for (size_t k = 0; k < E; ++k) set(wel(W, k), wel(sol, nq + k));
+      set(wel(W, E), mm.one);
+      // N / W by long division (W monic): the quotient stays in N[E ..], the remainder in N[.. E)
+      for (size_t i = nq; i-- > E;) {
+        u64 f[4];
+        set(f, wel(N, i));
+        for (size_t k = 0; k < E; ++k) {
+          u64 v[4];
+          wide_mont_mul(f, wel(W, k), mm, v);
+          wide_sub_p(wel(N, i - E + k), v, mm);
+        }
+      }
+      for (size_t k = 0; k < E && ok; ++k) ok = is0(wel(N, k));
+      if (ok) {
+        for (size_t c = 0; c < count; ++c) {                                     // F = N[E ..], degree <= t
+          u64 v[4];
+          set(v, wel(N, E + t));
+          for (size_t j = t; j-- > 0;) {
+            wide_mont_mul(v, wel(x, c), mm, v);
+            wide_add_p(v, wel(N, E + j), mm);
+          }
+          if (memcmp(v, &y[c * 4], 32) != 0) wrong.push_back(c);
+        }
+        ok = wrong.size() <= E;
+        wide_mont_out(wel(N, E), mm, secret);
+      }
+    }
+    for (int i = 0; i < 4; ++i) out[s * 4 + i] = ok ? secret[i] : zero[i];
+    if (nerr) nerr[s] = ok ? (u32)wrong.size() : PVW_SHAMIR_UNDECODABLE;
+    if (err_mask) std::fill(err_mask + s * words, err_mask + (s + 1) * words, (u64)0);
+    if (ok)
+      for (size_t c : wrong) {
+        if (col_err) ++col_err[c];
+        if (err_mask) err_mask[s * words + c / 64] |= (u64)1 << (c % 64);
+      }
+    volatile u64* vs = secret;
+    for (int i = 0; i < 4; ++i) vs[i] = 0;
+  }
+  for (std::vector<u64>* v : {&y, &A, &sol, &W, &N}) {                           // as secret as the shares
+    volatile u64* vp = v->data();
+    for (size_t i = 0; i < v->size(); ++i) vp[i] = 0;
+  }
+}
+int32_t pvw_shamir_reconstruct_wide_corrected_host(const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                                   const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                                   uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  PVW_TRY(reconstruct_wide_checks(r, shares, out));
+  berlekamp_welch_wide_host(r, shares, out, nerr, col_err, err_mask);
+  return PVW_OK;
+}
+
+// The device scratch of one call, in words from its base, laid out like CorrectLayout with elements of four words:
+//   M [cap][count][4] | x, aux, lambda, V, X (shamir_correct_wide_public_words) | Synd [cap][r][4] | Lambda [cap][nk][4] | L [cap] (u32)
+// M leads the block and is the one region marked secret besides the staging.  Every offset is a multiple of four words.
+struct CorrectWideLayout {
+  size_t count, r, nk, cap;
+  size_t pub, synd, lam, L, total;   // word offsets
+  CorrectWideLayout(const ReconstructWide& rc, size_t cap_)
+      : count(rc.count), r(rc.count - rc.degree - 1), nk((rc.count - rc.degree - 1) / 2 + 1), cap(cap_) {
+    pub = cap * count * 4;
+    synd = pub + shamir_correct_wide_public_words(count, rc.degree, nk);
+    lam = synd + cap * r * 4;
+    L = lam + cap * nk * 4;
+    total = L + (cap + 1) / 2;
+  }
+  size_t bytes() const { return total * 8; }
+  size_t m_bytes() const { return cap * count * 32; }
+};
+// secrets per pass over the kernels, by the rule of correct_piece: a secret takes (count + r + E + 1) 32 + 4 bytes of scratch
+static size_t correct_wide_piece(const ReconstructWide& r) {
+  const size_t red = r.count - r.degree - 1;
+  const size_t per = (r.count + red + red / 2 + 1) * 32 + 4;
+  const long env = PVW_ENV_INT("PVW_CORRECT_PIECE_BYTES", 0);
+  const size_t budget = env > 0 ? (size_t)env : (size_t)64 << 20;
+  size_t cap = budget / per;
+  if (cap == 0) cap = 1;
+  if (cap > 65535u * 4) cap = 65535u * 4;
+  return cap < r.S ? cap : r.S;
+}
+static int32_t correct_wide_device_checks(const ReconstructWide& r) {
+  PVW_TRY(reconstruct_wide_device_checks(r));
+  if ((r.count - r.degree - 1) / 2 + 1 > PVW_SHAMIR_WIDE_MAX_LOCATOR) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "on the device the wide locator holds at most %d coefficients: count - degree - 1 must be below %d",
+             PVW_SHAMIR_WIDE_MAX_LOCATOR, 2 * PVW_SHAMIR_WIDE_MAX_LOCATOR);
+    return fail(PVW_ERR_INVALID_PARAMETERS, buf);
+  }
+  return PVW_OK;
+}
+// the points and the public matrices of one call
+static int32_t correct_wide_weights(pvw_ctx* c, const ReconstructWide& r, const WideMont& mm, const CorrectWideLayout& lay, u64* ws,
+                                    hipStream_t s) {
+  ProfScope ps(c, "shamir_correct_wide_weights", s);
+  PVW_HIP(launch_shamir_points_wide(r.indices, r.count, ws + lay.pub, mm, s));
+  PVW_HIP(launch_shamir_correct_weights_wide(ws + lay.pub, r.count, r.degree, (u32)lay.nk, mm, s));
+  return PVW_OK;
+}
+// ns <= lay.cap secrets from d_shares: their out, nerr and mask rows; col_err, zeroed by the caller, is added to
+static int32_t correct_wide_piece_enqueue(pvw_ctx* c, const ReconstructWide& r, const WideMont& mm, const CorrectWideLayout& lay, u64* ws,
+                                          const u64* d_shares, size_t ns, size_t secret_stride, size_t point_stride, u64* d_out,
+                                          u32* d_nerr, u32* d_col_err, u64* d_mask, hipStream_t s) {
+  ProfScope ps(c, "shamir_correct_wide", s);
+  const u64* pub = ws + lay.pub;
+  const u64 *lambda = pub + (2 * r.count + 1) * 4, *V = lambda + r.count * 4, *X = V + r.count * lay.r * 4;
+  u64 *M = ws, *synd = ws + lay.synd, *Lam = ws + lay.lam;
+  u32* L = (u32*)(ws + lay.L);
+  ShamirMatmulWide a{};
+  a.A = d_shares, a.secret_stride = secret_stride, a.term_stride = point_stride;
+  a.W = V, a.out = synd;
+  a.ns = (u32)ns, a.terms = (u32)r.count, a.T = (u32)lay.r, a.m = mm;
+  PVW_HIP(launch_shamir_matmul_wide(a, s));
+  PVW_HIP(launch_shamir_bm_wide(synd, Lam, L, (u32)ns, (u32)lay.r, mm, s));
+  ShamirMatmulWide b{};
+  b.A = Lam, b.secret_stride = lay.nk, b.term_stride = 1;
+  b.W = X, b.out = M;
+  b.ns = (u32)ns, b.terms = (u32)lay.nk, b.T = (u32)r.count, b.m = mm;
+  PVW_HIP(launch_shamir_matmul_wide(b, s));
+  ShamirFinishWide f{};
+  f.shares = d_shares, f.secret_stride = secret_stride, f.point_stride = point_stride;
+  f.M = M, f.Lam = Lam, f.L = L, f.lam = lambda;
+  f.out = d_out, f.nerr = d_nerr, f.col_err = d_col_err, f.mask = d_mask;
+  f.count = (u32)r.count, f.E = (u32)lay.nk - 1, f.m = mm;
+  PVW_HIP(launch_shamir_correct_finish_wide(f, (u32)ns, s));
+  return PVW_OK;
+}
+
+int32_t pvw_shamir_reconstruct_wide_corrected_device(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                     size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
+                                                     size_t point_stride, uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err,
+                                                     uint64_t* d_err_mask, void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  PVW_TRY(reconstruct_wide_checks(r, d_shares, d_out));
+  PVW_TRY(correct_wide_device_checks(r));
+  const WideMont mm = make_wide_mont(plain_modulus);
+  const CorrectWideLayout lay(r, correct_wide_piece(r));
+  const size_t words = (count + 63) / 64;
+  // the caller's stream is checked before the device is touched (pvw_shamir_reconstruct_checked_device)
+  auto sized = [&](hipStream_t s) {
+    return grown_capture_check(c, s, &Workspace::correct_wide_bytes, lay.bytes(),
+                               "corrected reconstruction under stream capture: run a call with the same degree and count and at least as "
+                               "many secrets on this stream outside capture first (it sizes the workspace)");
+  };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
+    if (w->correct_wide_bytes < lay.bytes()) ws_public(w, w->correct_wide, w->correct_wide_bytes);   // the block is about to go
+    PVW_TRY(ws_grow(&w->correct_wide, &w->correct_wide_bytes, lay.bytes(), s, true));
+    ws_mark_secret(w, w->correct_wide, lay.m_bytes());
+    PVW_TRY(correct_wide_weights(c, r, mm, lay, w->correct_wide, s));
+    PVW_HIP(launch_shamir_zero_counts(d_col_err, count, s));
+    for (size_t s0 = 0; s0 < num_secrets; s0 += lay.cap) {
+      const size_t ns = num_secrets - s0 < lay.cap ? num_secrets - s0 : lay.cap;
+      PVW_TRY(correct_wide_piece_enqueue(c, r, mm, lay, w->correct_wide, d_shares + s0 * secret_stride * 4, ns, secret_stride,
+                                         point_stride, d_out + s0 * 4, Report::from(d_nerr, s0), d_col_err,
+                                         Report::from(d_err_mask, s0 * words), s));
+    }
+    return PVW_OK;
+  });
+}
+
+// host buffers: the secrets go up in pieces as pvw_shamir_reconstruct_wide_checked stages them (a 2D copy for dense rows, else a
+// host repack that is wiped at the end), a piece no larger than one pass over the kernels; the public matrices are made once and
+// col_err adds up over the pieces.  The staged shares, the staged secrets and M are cleared before the call returns.
+int32_t pvw_shamir_reconstruct_wide_corrected(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                              size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
+                                              size_t point_stride, uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  PVW_TRY(reconstruct_wide_checks(r, shares, out));
+  PVW_TRY(correct_wide_device_checks(r));
+  PVW_TRY(ensure_device(c));
+  const WideMont mm = make_wide_mont(plain_modulus);
+  const size_t words = (count + 63) / 64;
+  size_t per = chunk_1gib((count + 1) * 32 + words * 8 + 4, num_secrets);
+  if (per > correct_wide_piece(r)) per = correct_wide_piece(r);
+  const CorrectWideLayout lay(r, per);
+  Scratch sc;
+  const size_t r_sh = sc.add(per * count * 32), r_out = sc.add(per * 32), r_ws = sc.add(lay.bytes()), r_nerr = sc.add(per * 4),
+               r_col = sc.add(count * 4), r_mask = sc.add(per * words * 8);
+  const bool dense = point_stride == 1 && secret_stride >= count;
+  std::vector<u64> packed(dense ? 0 : per * count * 4);
+  const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    u64 *d_sh = sc.at(r_sh), *d_out = sc.at(r_out), *ws = sc.at(r_ws);
+    ws_mark_secret(w, d_sh, (size_t)((char*)ws - (char*)d_sh) + lay.m_bytes());   // staged shares | staged secrets | M
+    u32 *d_nerr = nerr ? sc.at<u32>(r_nerr) : nullptr, *d_col = col_err ? sc.at<u32>(r_col) : nullptr;
+    u64* d_mask = err_mask ? sc.at(r_mask) : nullptr;
+    PVW_TRY(correct_wide_weights(c, r, mm, lay, ws, w->stream));
+    PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
+    for (size_t s0 = 0; s0 < num_secrets; s0 += per) {
+      const size_t cnt = (num_secrets - s0) < per ? (num_secrets - s0) : per;
+      if (dense) {
+        PVW_HIP(hipMemcpy2DAsync(d_sh, count * 32, shares + s0 * secret_stride * 4, secret_stride * 32, count * 32, cnt,
+                                 hipMemcpyHostToDevice, w->stream));
+      } else {
+        for (size_t s = 0; s < cnt; ++s)
+          for (size_t col = 0; col < count; ++col)
+            memcpy(&packed[(s * count + col) * 4], shares + ((s0 + s) * secret_stride + col * point_stride) * 4, 32);
+        PVW_HIP(hipMemcpyAsync(d_sh, packed.data(), cnt * count * 32, hipMemcpyHostToDevice, w->stream));
+      }
+      PVW_TRY(correct_wide_piece_enqueue(c, r, mm, lay, ws, d_sh, cnt, count, 1, d_out, d_nerr, d_col, d_mask, w->stream));
+      PVW_HIP(hipMemcpyAsync(out + s0 * 4, d_out, cnt * 32, hipMemcpyDeviceToHost, w->stream));
+      if (nerr) PVW_HIP(hipMemcpyAsync(nerr + s0, d_nerr, cnt * 4, hipMemcpyDeviceToHost, w->stream));
+      if (err_mask) PVW_HIP(hipMemcpyAsync(err_mask + s0 * words, d_mask, cnt * words * 8, hipMemcpyDeviceToHost, w->stream));
+      PVW_HIP(hipStreamSynchronize(w->stream));                  // the next piece reuses the staging
+    }
+    if (col_err) PVW_HIP(hipMemcpyAsync(col_err, d_col, count * 4, hipMemcpyDeviceToHost, w->stream));
     return PVW_OK;
   });
   volatile u64* vp = packed.data();

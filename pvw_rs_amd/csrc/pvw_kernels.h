@@ -423,6 +423,40 @@ hipError_t launch_shamir_erasures_finish(const ShamirFinish& f, const u64* erase
 hipError_t launch_shamir_erasure_mask(const u32* status, const u64* noise, u32 status_bits, u64 noise_bound, u32 count, u32 ns,
                                       size_t secret_stride, size_t point_stride, u64* mask, hipStream_t s);
 
+// ---- Corrected reconstruction over a prime below 2^256 (pvw_shamir.hip): the decode of 8.11 with elements of four
+// words.  Public workspace words, all times R = 2^256 (pvw_wide.h): x [count][4] | aux [count + 1][4] | lambda [count][4] |
+// V [count][r][4] | X [nk][count][4], nk = E + 1.  The syndromes are plain; the locators and M are times R.
+inline size_t shamir_correct_wide_public_words(size_t count, u32 t, size_t nk) { return 4 * shamir_correct_public_words(count, t, nk); }
+#define PVW_SHAMIR_WIDE_MAX_LOCATOR 2048                 // E + 1 at most: two polynomials of one wave in 128 KiB of LDS
+struct ShamirMatmulWide {
+  const u64* A;          // element (s, j): four words at A + 4 (s * secret_stride + j * term_stride), any words, read mod p
+  size_t secret_stride, term_stride;
+  const u64* W;          // [terms][T][4], times R
+  u64* out;              // [ns][T][4]
+  u32 ns, terms, T;
+  WideMont m;
+};
+struct ShamirFinishWide {
+  const u64* shares;     // as ShamirInterpWide
+  size_t secret_stride, point_stride;
+  const u64* M;          // [ns][count][4]: the locator of row s at every point
+  const u64* Lam;        // [ns][E+1][4]: the reversed locators
+  const u32* L;          // [ns]: their degrees, or PVW_SHAMIR_NO_LOCATOR
+  const u64* lam;        // [count][4]: Lagrange weights at 0 over all columns
+  u64* out;              // [ns][4]
+  u32* nerr;             // [ns] or NULL
+  u32* col_err;          // [count] or NULL; zeroed by the caller, the kernel adds
+  u64* mask;             // [ns][ceil(count / 64)] or NULL; every word is stored
+  u32 count, E;
+  WideMont m;
+};
+hipError_t launch_shamir_correct_weights_wide(u64* ws, size_t count, u32 degree, u32 nk, const WideMont& m, hipStream_t s);
+hipError_t launch_shamir_matmul_wide(const ShamirMatmulWide& b, hipStream_t s);
+hipError_t launch_shamir_bm_wide(const u64* synd, u64* lam, u32* L, u32 ns, u32 r, const WideMont& m, hipStream_t s);
+hipError_t launch_shamir_correct_finish_wide(const ShamirFinishWide& f, u32 ns, hipStream_t s);
+// the dynamic-LDS limit of the wide Berlekamp-Massey kernel; once per context after hipSetDevice, beside init_kernel_attributes
+hipError_t init_shamir_attributes();
+
 // p[0 .. words) = 0, as a kernel launch on s
 hipError_t launch_wipe_words(u64* p, size_t words, hipStream_t s);
 

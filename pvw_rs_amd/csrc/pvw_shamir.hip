@@ -1299,21 +1299,30 @@ __global__ __launch_bounds__(256) void shamir_weights_wide_kernel(const u64* x, 
   }
 }
 
-// grid: x = blocks of 64 targets, y = groups of SHW_SG secrets; 256 threads.
-__global__ __launch_bounds__(256) void shamir_interp_wide_kernel(ShamirInterpWide b) {
-  __shared__ u64 sh[SH_WAVES][SHW_TC][SHW_SG][4];  // 4 KiB: the chunk of the shares, below p
+// Out[S][T][4] = A[S][terms][4] x W[terms][T][4] mod p for one workgroup (256 threads, block x = 64 targets, block y = SHW_SG
+// secrets): the frame shamir_interp_wide_kernel and shamir_matmul_wide_kernel share, as shamir_tile_product serves the one-word
+// family.  A is any words at two strides (in elements), staged below p; W is stored times R.  Thread (wave, lane) comes back with
+// the plain sum v of element (s = s0 + wave, tm) and whether that element exists.
+struct ShamirWideTile {
+  u64 v[4];
+  u32 s;
+  size_t tm;
+  bool live;
+};
+__device__ __forceinline__ ShamirWideTile shamir_tile_product_wide(const u64* A, size_t secret_stride, size_t term_stride, const u64* W,
+                                                                   u32 ns, u32 nt, u32 T, const WideMont m) {
+  __shared__ u64 sh[SH_WAVES][SHW_TC][SHW_SG][4];  // 4 KiB: the chunk of A, below p
   __shared__ u64 part[SH_WAVES][SHW_SG][64][4];    // 32 KiB: the waves' partial sums, below p
-  const WideMont m = b.m;
   const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const u32 s0 = blockIdx.y * SHW_SG, ns = b.ns, nt = b.degree + 1, T = b.T;
+  const u32 s0 = blockIdx.y * SHW_SG;
   const size_t tm = (size_t)blockIdx.x * 64 + lane;
   const bool live = tm < T;
   // wave w owns terms j = w * Q + [0, Q), cut off at nt; every wave walks the same number of chunks (barriers)
   const u32 Q = (nt + SH_WAVES - 1) / SH_WAVES;
   const u32 jw0 = wave * Q;
   const u32 nchunks = (Q + SHW_TC - 1) / SHW_TC;
-  const bool term_fast = b.point_stride <= b.secret_stride;
-  const u64* wcol = b.W + (live ? tm : 0) * 4;
+  const bool term_fast = term_stride <= secret_stride;
+  const u64* wcol = W + (live ? tm : 0) * 4;
   u32 acc[SHW_SG][16];                             // each below p 2^256 (wide_acc_add)
 #pragma unroll
   for (int g = 0; g < SHW_SG; ++g) wide_acc_zero(acc[g]);
@@ -1328,7 +1337,7 @@ __global__ __launch_bounds__(256) void shamir_interp_wide_kernel(ShamirInterpWid
       const u32 j = ew * Q + off;
       u64 a[4] = {0, 0, 0, 0};
       if (off < Q && j < nt && s0 + eg < ns) {
-        const u64* sp = b.shares + ((size_t)(s0 + eg) * b.secret_stride + (size_t)j * b.point_stride) * 4;
+        const u64* sp = A + ((size_t)(s0 + eg) * secret_stride + (size_t)j * term_stride) * 4;
         const u64 w[4] = {sp[0], sp[1], sp[2], sp[3]};
         wide_reduce_p(w, m, a);
       }
@@ -1370,36 +1379,47 @@ __global__ __launch_bounds__(256) void shamir_interp_wide_kernel(ShamirInterpWid
     for (int k = 0; k < 4; ++k) part[wave][g][lane][k] = r[k];
   }
   __syncthreads();
-  u64 v[4];
+  ShamirWideTile o;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = part[0][wave][lane][k];
+  for (int k = 0; k < 4; ++k) o.v[k] = part[0][wave][lane][k];
 #pragma unroll
   for (int ww = 1; ww < SH_WAVES; ++ww) {
     u64 f[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) f[k] = part[ww][wave][lane][k];
-    wide_add_p(v, f, m);
+    wide_add_p(o.v, f, m);
   }
-  const u32 s = s0 + wave;
+  o.s = s0 + wave;                                 // SH_WAVES == SHW_SG
+  o.tm = tm;
+  o.live = live && o.s < ns;
+  return o;
+}
+
+// The tile product of the shares' basis columns with W; target 0 is the secret, every other target is compared with the share
+// of its column.  grid: x = blocks of 64 targets, y = groups of SHW_SG secrets; 256 threads.
+__global__ __launch_bounds__(256) void shamir_interp_wide_kernel(ShamirInterpWide b) {
+  const WideMont m = b.m;
+  const ShamirWideTile o = shamir_tile_product_wide(b.shares, b.secret_stride, b.point_stride, b.W, b.ns, b.degree + 1, b.T, m);
+  const u32 s = o.s;
   bool dev = false;
-  if (live && s < ns) {
-    if (tm == 0) {
-      u64* o = b.out + (size_t)s * 4;
+  if (o.live) {
+    if (o.tm == 0) {
+      u64* out = b.out + (size_t)s * 4;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = v[k];
+      for (int k = 0; k < 4; ++k) out[k] = o.v[k];
     } else {
-      const size_t col = (size_t)b.degree + tm;
+      const size_t col = (size_t)b.degree + o.tm;
       const u64* sp = b.shares + ((size_t)s * b.secret_stride + col * b.point_stride) * 4;
       const u64 w[4] = {sp[0], sp[1], sp[2], sp[3]};
       u64 y[4];
       wide_reduce_p(w, m, y);
-      dev = (y[0] != v[0]) | (y[1] != v[1]) | (y[2] != v[2]) | (y[3] != v[3]);
+      dev = (y[0] != o.v[0]) | (y[1] != o.v[1]) | (y[2] != o.v[2]) | (y[3] != o.v[3]);
       if (dev && b.col_bad) atomicAdd(&b.col_bad[col], 1u);
     }
   }
   // one add per wave: the wave's lanes share the secret
   const u32 ndev = (u32)__popcll(__ballot(dev));
-  if (lane == 0 && ndev && b.bad) atomicAdd(&b.bad[s], ndev);
+  if ((threadIdx.x & 63) == 0 && ndev && b.bad) atomicAdd(&b.bad[s], ndev);
 }
 
 hipError_t launch_shamir_points_wide(const u64* indices, size_t count, u64* x, const WideMont& m, hipStream_t s) {
@@ -1482,6 +1502,350 @@ __global__ __launch_bounds__(256) void shamir_wide_mul_kernel(WideMont m, const 
 hipError_t launch_shamir_wide_mul(const WideMont& m, const u64* a, const u64* b, size_t count, u64* out, hipStream_t s) {
   if (!count) return hipSuccess;
   shamir_wide_mul_kernel<<<dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s>>>(m, a, b, count, out);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------ corrected reconstruction below 2^256
+// The decode of 8.11 step by step, with elements of four words and the product of pvw_wide.h.  Forms (R = 2^256):
+//   x, aux (u_c, then prod_i(-x_i)), lambda, V, X        public, stored times R
+//   shares, Synd = shares x V                            plain: REDC(plain * (V R)) is the plain product
+//   C, B, b, Lambda                                      times R: the locator is the operand that meets plain syndromes
+//   M = Lambda x X                                       times R: REDC((Lambda R)(X R)); its zero test does not depend on the form
+//   out                                                  plain: (sum_c y_c REDC((lambda_c R)(M_c R))) reduced once, then times
+//                                                        (Lambda_s(0) R)^-1 R by one more REDC
+#define SHW_LG 16     // columns of lambda that share one inversion
+
+// a^e times R for a times R; the exponent's bits from the top
+__device__ __forceinline__ void wide_mont_pow(const u64 (&a)[4], u32 e, const WideMont& m, u64 (&out)[4]) {
+  u64 r[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) r[k] = m.one[k];
+  for (int b = 31 - __builtin_clz(e | 1); b >= 0; --b) {
+    wide_mont_mul(r, r, m, r);
+    if ((e >> b) & 1) wide_mont_mul(r, a, m, r);
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) out[k] = r[k];
+}
+
+// lambda_c = u_c P / (-x_c), P = prod_i(-x_i) = aux[count].  One thread per group of SHW_LG columns, which share one Fermat
+// inversion by Montgomery's trick (shamir_weights_wide_kernel): the running products of -x_c go out to the columns' own slots of
+// lam, the last one is inverted, and the walk back turns every slot into its weight.
+__global__ __launch_bounds__(64) void shamir_lambda_wide_kernel(const u64* x, const u64* aux, u64* lam, u32 count, WideMont m) {
+  const u32 g = blockIdx.x * 64 + threadIdx.x;
+  const u32 c0 = g * SHW_LG;
+  if (c0 >= count) return;
+  const u32 cnt = count - c0 < SHW_LG ? count - c0 : SHW_LG;
+  const u64 zero[4] = {0, 0, 0, 0};
+  u64 run[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) run[k] = m.one[k];
+  for (u32 k = 0; k < cnt; ++k) {
+    u64 xc[4], d[4] = {0, 0, 0, 0};
+    wide_ld(x + (size_t)(c0 + k) * 4, xc);
+    wide_sub_p(d, xc, m);                                        // -x_c, never 0: 0 < x_c < p
+    wide_mont_mul(run, d, m, run);
+    wide_st(lam + (size_t)(c0 + k) * 4, run);
+  }
+  u64 inv[4], P[4];
+  wide_mont_inv(run, m, inv);
+  wide_ld(aux + (size_t)count * 4, P);
+  for (u32 k = cnt; k-- > 0;) {
+    u64 xc[4], d[4], pre[4], u[4], dinv[4];
+    wide_ld(x + (size_t)(c0 + k) * 4, xc);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) d[i] = zero[i];
+    wide_sub_p(d, xc, m);
+    if (k) wide_ld(lam + (size_t)(c0 + k - 1) * 4, pre);
+    else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) pre[i] = m.one[i];
+    }
+    wide_mont_mul(inv, pre, m, dinv);                            // (-x_c)^-1
+    wide_mont_mul(inv, d, m, inv);
+    wide_ld(aux + (size_t)(c0 + k) * 4, u);
+    wide_mont_mul(u, P, m, u);
+    wide_mont_mul(u, dinv, m, u);
+    wide_st(lam + (size_t)(c0 + k) * 4, u);
+  }
+}
+
+// one wave per column c: lane l starts at u_c x_c^l and steps by x_c^64, so a wave's stores to row c of V are coalesced
+__global__ __launch_bounds__(256) void shamir_synd_weights_wide_kernel(const u64* x, const u64* aux, u64* V, u32 count, u32 r, WideMont m) {
+  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const u32 c = blockIdx.x * SH_WAVES + wave;
+  if (c >= count) return;
+  u64 xc[4], step[4], v[4], u[4];
+  wide_ld(x + (size_t)c * 4, xc);
+  wide_ld(aux + (size_t)c * 4, u);
+  wide_mont_pow(xc, 64u, m, step);
+  wide_mont_pow(xc, lane, m, v);
+  wide_mont_mul(v, u, m, v);
+  u64* row = V + (size_t)c * r * 4;
+  for (u32 j = lane; j < r; j += 64) {
+    wide_st(row + (size_t)j * 4, v);
+    wide_mont_mul(v, step, m, v);
+  }
+}
+
+// grid: x = blocks of 256 columns, y = blocks of 64 powers; a thread walks its 64 powers of x_c, lanes store along a row of X
+__global__ __launch_bounds__(256) void shamir_powers_wide_kernel(const u64* x, u64* X, u32 count, u32 nk, WideMont m) {
+  const u32 c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= count) return;
+  const u32 k0 = blockIdx.y * 64, k1 = k0 + 64 < nk ? k0 + 64 : nk;
+  u64 xc[4], v[4];
+  wide_ld(x + (size_t)c * 4, xc);
+  wide_mont_pow(xc, k0, m, v);
+  for (u32 k = k0; k < k1; ++k) {
+    wide_st(X + ((size_t)k * count + c) * 4, v);
+    wide_mont_mul(v, xc, m, v);
+  }
+}
+
+// Out[S][T][4] = A[S][terms][4] x W[terms][T][4] mod p: the wide tile product, stored.
+// grid: x = blocks of 64 targets, y = groups of SHW_SG secrets; 256 threads.
+__global__ __launch_bounds__(256) void shamir_matmul_wide_kernel(ShamirMatmulWide b) {
+  const ShamirWideTile o = shamir_tile_product_wide(b.A, b.secret_stride, b.term_stride, b.W, b.ns, b.terms, b.T, b.m);
+  if (o.live) wide_st(b.out + ((size_t)o.s * b.T + o.tm) * 4, o.v);
+}
+
+// the sum of the lanes' values (each below p), the same in every lane
+__device__ __forceinline__ void wave_add_wide(u64 (&v)[4], const WideMont& m) {
+#pragma unroll
+  for (int off = 32; off; off >>= 1) {
+    u64 f[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) f[k] = (u64)__shfl_xor((unsigned long long)v[k], off);
+    wide_add_p(v, f, m);
+  }
+}
+__device__ __forceinline__ bool wide_zero(const u64 (&v)[4]) { return !(v[0] | v[1] | v[2] | v[3]); }
+
+// shamir_bm_kernel over four words: one wave (one workgroup) per secret, inversion-free Berlekamp-Massey over the r syndromes of
+// row s,  d = sum_{i <= L} C_i S_{n-i};  d != 0:  C <- b C - d x^m B  (and, when 2L <= n: B <- the old C, b <- d, L <- n + 1 - L).
+// C and B lie in dynamic LDS, each as four planes of E + 1 words (word k of coefficient i at plane k, slot i), so that the lanes
+// of one access are consecutive words; coefficient i belongs to lane i % 64.  C, B and b are kept times R, the syndromes are
+// plain: a term C_i S_{n-i} is wide_mul_full of (C_i R) < p and S_{n-i} < p, so every product is below p p < p R and
+// wide_acc_add's invariant (one operand below p, the other below R) holds term by term: the lane's accumulator stays below
+// p 2^256 however many terms it takes, and ONE wide_redc gives the lane's plain part of d.  The parts are summed over the wave by
+// shuffles and wide_add_p, so d is the same in every lane and every branch is wave-uniform.  d R = REDC(d r2) once per step;
+// the update's two products are REDC((b R)(C_i R)) and REDC((d R)(B_j R)), each with both operands below p.
+// L never decreases: the first update that would take it above E ends the row as undecodable.  The update walks downwards in
+// blocks of 64: B_{i-m} is read from this block or a lower one, which the walk has not overwritten yet.
+// Out: lam[s][k] = C_{L-k} R for k <= L, 0 up to E (all 0 for an undecodable row), and Lout[s] = L or PVW_SHAMIR_NO_LOCATOR.
+__global__ __launch_bounds__(64) void shamir_bm_wide_kernel(const u64* synd, u64* lam, u32* Lout, u32 r, u32 E, WideMont m) {
+  extern __shared__ u64 bmw_lds[];                 // C [4][E + 1] | B [4][E + 1]
+  const u32 nE = E + 1;
+  u64 *C = bmw_lds, *B = bmw_lds + (size_t)4 * nE;
+  const u32 lane = threadIdx.x;
+  const size_t s = blockIdx.x;
+  const u64* S = synd + s * r * 4;
+  for (u32 i = lane; i <= E; i += 64)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) C[k * nE + i] = B[k * nE + i] = i == 0 ? m.one[k] : 0;
+  __syncthreads();
+  u32 L = 0, mm = 1;
+  u64 bsc[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) bsc[k] = m.one[k];
+  bool ok = true;
+  for (u32 n = 0; n < r; ++n) {
+    u32 acc[16];
+    wide_acc_zero(acc);
+    for (u32 i = lane; i <= L; i += 64) {          // L <= n
+      u64 c[4], sv[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) c[k] = C[k * nE + i];
+      wide_ld(S + (size_t)(n - i) * 4, sv);
+      u32 P[16];
+      wide_mul_full(c, sv, P);
+      wide_acc_add(acc, P, m);
+    }
+    u64 d[4];
+    wide_redc(acc, m, d);
+    wave_add_wide(d, m);
+    if (wide_zero(d)) { ++mm; continue; }
+    const bool grow = 2 * L <= n;
+    const u32 Ln = grow ? n + 1 - L : L;
+    if (Ln > E) { ok = false; break; }
+    wide_mont_in(d, m, d);
+    for (u32 k = Ln / 64 + 1; k-- > 0;) {
+      const u32 i = k * 64 + lane;
+      const bool in = i <= Ln;
+      u64 c[4] = {0, 0, 0, 0}, bb[4] = {0, 0, 0, 0};
+      if (in) {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) c[w] = C[w * nE + i];
+        if (i >= mm) {
+#pragma unroll
+          for (int w = 0; w < 4; ++w) bb[w] = B[w * nE + i - mm];
+        }
+      }
+      __syncthreads();
+      if (in) {
+        u64 v[4], t[4];
+        wide_mont_mul(bsc, c, m, v);
+        wide_mont_mul(d, bb, m, t);
+        wide_sub_p(v, t, m);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) C[w * nE + i] = v[w];
+        if (grow) {
+#pragma unroll
+          for (int w = 0; w < 4; ++w) B[w * nE + i] = c[w];
+        }
+      }
+      __syncthreads();
+    }
+    if (grow) {
+      L = Ln;
+      mm = 1;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) bsc[k] = d[k];
+    } else {
+      ++mm;
+    }
+  }
+  u64* row = lam + s * nE * 4;
+  for (u32 k = lane; k <= E; k += 64) {
+    u64 v[4] = {0, 0, 0, 0};
+    if (ok && k <= L) {
+#pragma unroll
+      for (int w = 0; w < 4; ++w) v[w] = C[w * nE + L - k];
+    }
+    wide_st(row + (size_t)k * 4, v);
+  }
+  if (lane == 0) Lout[s] = ok ? L : PVW_SHAMIR_NO_LOCATOR;
+}
+
+// v, held in two vector registers from here on (the compiler would keep a wave-uniform value in scalar ones)
+__device__ __forceinline__ u64 wide_in_vgpr(u64 v) {
+  u32 lo = (u32)v, hi = (u32)(v >> 32);
+  asm volatile("" : "+v"(lo), "+v"(hi));
+  return ((u64)hi << 32) | lo;
+}
+
+// shamir_correct_finish_kernel over four words: one wave (one workgroup) per secret over row s of M.  Pass 1 counts the zeros
+// (four zero words: the same test whether the element is stored times R or not); fewer than L means no polynomial within E
+// errors.  Pass 2: the ballot of the zeros of 64 columns is the mask word, every set bit one atomicAdd to its column's count, and
+// the other columns enter out[s] = (sum_c y_c lambda_c M[s][c]) Lambda_s(0)^-1: the weight REDC((lambda_c R)(M R)) is below p and
+// the share is reduced below p, so the lane's accumulator stays below p 2^256 (wide_acc_add) and is reduced once.
+__global__ __launch_bounds__(64) void shamir_correct_finish_wide_kernel(ShamirFinishWide f) {
+  const u32 lane = threadIdx.x;
+  const size_t s = blockIdx.x;
+  // r2 and one travel in vector registers: held in scalar ones beside the kernel's thirteen arguments and the carries of the
+  // products they cost 32 spilled SGPRs
+  WideMont m = f.m;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    m.r2[k] = wide_in_vgpr(m.r2[k]);
+    m.one[k] = wide_in_vgpr(m.one[k]);
+  }
+  const u32 count = f.count, words = (count + 63) / 64;
+  const u32 L = f.L[s];
+  const u64* Mrow = f.M + s * count * 4;
+  bool decodable = L != PVW_SHAMIR_NO_LOCATOR;
+  if (decodable) {
+    u32 nz = 0;
+    for (u32 c0 = 0; c0 < count; c0 += 64) {
+      const u32 c = c0 + lane;
+      u64 mv[4] = {1, 0, 0, 0};
+      if (c < count) wide_ld(Mrow + (size_t)c * 4, mv);
+      nz += (u32)__popcll(__ballot(wide_zero(mv)));
+    }
+    decodable = nz == L;
+  }
+  if (!decodable) {
+    if (f.mask)
+      for (u32 w = lane; w < words; w += 64) f.mask[s * words + w] = 0;
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) f.out[s * 4 + k] = 0;          // the caller's buffer: word stores, as the checked kernel's
+      if (f.nerr) f.nerr[s] = PVW_SHAMIR_NO_LOCATOR;
+    }
+    return;
+  }
+  u32 acc[16];
+  wide_acc_zero(acc);
+  for (u32 c0 = 0; c0 < count; c0 += 64) {
+    const u32 c = c0 + lane;
+    const bool live = c < count;
+    u64 mv[4] = {1, 0, 0, 0};
+    if (live) wide_ld(Mrow + (size_t)c * 4, mv);
+    const bool wrong = wide_zero(mv);
+    const u64 bal = __ballot(wrong);
+    if (lane == 0 && f.mask) f.mask[s * words + c0 / 64] = bal;
+    if (wrong && f.col_err) atomicAdd(&f.col_err[c], 1u);
+    if (live && !wrong) {
+      const u64* sp = f.shares + (s * f.secret_stride + (size_t)c * f.point_stride) * 4;
+      const u64 w[4] = {sp[0], sp[1], sp[2], sp[3]};
+      u64 y[4], lw[4];
+      wide_reduce_p(w, m, y);
+      wide_ld(f.lam + (size_t)c * 4, lw);
+      wide_mont_mul(lw, mv, m, lw);
+      u32 P[16];
+      wide_mul_full(y, lw, P);
+      wide_acc_add(acc, P, m);
+    }
+  }
+  u64 v[4];
+  wide_redc(acc, m, v);
+  wave_add_wide(v, m);
+  if (lane == 0) {
+    u64 l0[4];
+    wide_ld(f.Lam + s * (f.E + 1) * 4, l0);
+    wide_mont_inv(l0, m, l0);
+    wide_mont_mul(v, l0, m, v);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) f.out[s * 4 + k] = v[k];
+    if (f.nerr) f.nerr[s] = L;
+  }
+}
+
+// ws: x [count][4] (filled by launch_shamir_points_wide) | aux [count + 1][4] | lambda [count][4] | V [count][r][4] | X [nk][count][4]
+hipError_t launch_shamir_correct_weights_wide(u64* ws, size_t count, u32 t, u32 nk, const WideMont& m, hipStream_t s) {
+  const u32 n = (u32)count, r = n - t - 1;
+  const u64* x = ws;
+  u64 *aux = ws + count * 4, *lam = aux + (count + 1) * 4, *V = lam + count * 4, *X = V + count * r * 4;
+  shamir_prod_wide_kernel<<<dim3((unsigned)((count + 1 + SH_WAVES - 1) / SH_WAVES)), dim3(256), 0, s>>>(x, aux, count, n - 1, m);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const u32 groups = (n + SHW_LG - 1) / SHW_LG;
+  shamir_lambda_wide_kernel<<<dim3((groups + 63) / 64), dim3(64), 0, s>>>(x, aux, lam, n, m);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (r) {
+    shamir_synd_weights_wide_kernel<<<dim3((n + SH_WAVES - 1) / SH_WAVES), dim3(256), 0, s>>>(x, aux, V, n, r, m);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  shamir_powers_wide_kernel<<<dim3((n + 255) / 256, (nk + 63) / 64), dim3(256), 0, s>>>(x, X, n, nk, m);
+  return hipGetLastError();
+}
+
+hipError_t launch_shamir_matmul_wide(const ShamirMatmulWide& b, hipStream_t s) {
+  return launch_secret_groups(shamir_matmul_wide_kernel, b, [&](u32 s0) {
+    ShamirMatmulWide p = b;
+    p.A += (size_t)s0 * b.secret_stride * 4;
+    p.out += (size_t)s0 * b.T * 4;
+    return p;
+  }, s);
+}
+
+// E + 1 <= PVW_SHAMIR_WIDE_MAX_LOCATOR: C and B of one wave take 2 (E + 1) 32 bytes, up to 128 KiB of the 160 KiB a gfx950 CU has.
+// That is more than the 64 KiB a launch gets without asking: the limit is raised once per device (init_shamir_attributes), and
+// each launch asks for what its E takes.
+hipError_t init_shamir_attributes() {
+  return hipFuncSetAttribute((const void*)shamir_bm_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             2 * PVW_SHAMIR_WIDE_MAX_LOCATOR * 32);
+}
+hipError_t launch_shamir_bm_wide(const u64* synd, u64* lam, u32* L, u32 ns, u32 r, const WideMont& m, hipStream_t s) {
+  if (ns == 0) return hipSuccess;
+  const u32 E = r / 2;
+  shamir_bm_wide_kernel<<<dim3(ns), dim3(64), (size_t)2 * (E + 1) * 32, s>>>(synd, lam, L, r, E, m);
+  return hipGetLastError();
+}
+
+hipError_t launch_shamir_correct_finish_wide(const ShamirFinishWide& f, u32 ns, hipStream_t s) {
+  if (ns == 0) return hipSuccess;
+  shamir_correct_finish_wide_kernel<<<dim3(ns), dim3(64), 0, s>>>(f);
   return hipGetLastError();
 }
 

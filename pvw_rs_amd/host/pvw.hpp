@@ -819,6 +819,33 @@ inline CheckedWideSecrets shamir_reconstruct_wide_checked(const std::shared_ptr<
                                                    r.secrets.data(), r.bad.data(), r.col_bad.data()));
   return r;
 }
+// ---- corrected reconstruction over an odd prime below 2^256 ----
+struct CorrectedWideSecrets {
+  std::vector<uint64_t> secrets;    // [num_secrets][4]: the value at 0 of the one polynomial within E columns of the row; 0: undecodable
+  std::vector<uint32_t> nerr;       // [num_secrets]: columns off that polynomial, or PVW_SHAMIR_UNDECODABLE
+  std::vector<uint32_t> col_err;    // [indices.size()]: decodable secrets that are off in each column
+  std::vector<uint64_t> err_mask;   // [num_secrets][words]: bit c % 64 of word c / 64 names the columns of nerr
+  size_t words;                     // ceil(indices.size() / 64)
+  bool wrong(size_t s, size_t c) const { return (err_mask[s * words + c / 64] >> (c % 64)) & 1; }
+};
+// Up to E = (indices.size() - degree - 1) / 2 wrong shares per secret, in whichever columns.  shares as
+// shamir_reconstruct_wide_checked.  On the device (pvw_shamir_reconstruct_wide_corrected); host = true: the plain C++ restatement
+// (Berlekamp-Welch, no GPU; p may be null).
+inline CorrectedWideSecrets shamir_reconstruct_wide_corrected(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& indices,
+                                                              const std::vector<uint64_t>& shares, uint32_t degree, const Wide& plain_modulus,
+                                                              bool party_major = false, bool host = false) {
+  const size_t count = indices.size();
+  if (count == 0 || shares.empty() || shares.size() % (count * PVW_WIDE_WORDS)) throw PvwError(15, "shares must hold one element per index and secret");
+  const size_t S = shares.size() / (count * PVW_WIDE_WORDS), ss = party_major ? 1 : count, ps = party_major ? S : 1;
+  const size_t words = (count + 63) / 64;
+  CorrectedWideSecrets r{std::vector<uint64_t>(S * PVW_WIDE_WORDS), std::vector<uint32_t>(S), std::vector<uint32_t>(count),
+                         std::vector<uint64_t>(S * words), words};
+  check(host ? pvw_shamir_reconstruct_wide_corrected_host(plain_modulus.data(), degree, indices.data(), count, shares.data(), S, ss, ps,
+                                                          r.secrets.data(), r.nerr.data(), r.col_err.data(), r.err_mask.data())
+             : pvw_shamir_reconstruct_wide_corrected(p->ctx, plain_modulus.data(), degree, indices.data(), count, shares.data(), S, ss, ps,
+                                                     r.secrets.data(), r.nerr.data(), r.col_err.data(), r.err_mask.data()));
+  return r;
+}
 // the share matrix of the checked, corrected and evaluate calls: its shape and the strides of its layout, in words
 struct ShareMatrix {
   size_t count, S, words, ss, ps;   // columns, secrets, mask words per secret, secret stride, point stride

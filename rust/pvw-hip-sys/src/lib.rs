@@ -101,6 +101,8 @@ pub const PVW_DOM_CALL: u32 = 8;
 pub const PVW_DOM_SHAMIR: u32 = 9;
 /// `nerr` of a secret that no polynomial of the degree fits within E columns
 pub const PVW_SHAMIR_UNDECODABLE: u32 = 0xFFFF_FFFF;
+/// the device forms of `pvw_shamir_reconstruct_wide_corrected` take at most this many locator coefficients
+pub const PVW_SHAMIR_WIDE_MAX_LOCATOR: u32 = 2048;
 
 extern "C" {
     // ---- errors / device ------------------------------------------------------------------
@@ -179,6 +181,9 @@ extern "C" {
     pub fn pvw_shamir_reconstruct_wide_checked_host(plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, out: *mut u64, bad: *mut u32, col_bad: *mut u32) -> i32;
     pub fn pvw_shamir_reconstruct_wide_checked_device(ctx: *mut PvwCtx, plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, d_shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, d_out: *mut u64, d_bad: *mut u32, d_col_bad: *mut u32, stream: *mut c_void) -> i32;
     pub fn pvw_shamir_reconstruct_wide_checked(ctx: *mut PvwCtx, plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, out: *mut u64, bad: *mut u32, col_bad: *mut u32) -> i32;
+    pub fn pvw_shamir_reconstruct_wide_corrected_host(plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, out: *mut u64, nerr: *mut u32, col_err: *mut u32, err_mask: *mut u64) -> i32;
+    pub fn pvw_shamir_reconstruct_wide_corrected_device(ctx: *mut PvwCtx, plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, d_shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, d_out: *mut u64, d_nerr: *mut u32, d_col_err: *mut u32, d_err_mask: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_reconstruct_wide_corrected(ctx: *mut PvwCtx, plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, out: *mut u64, nerr: *mut u32, col_err: *mut u32, err_mask: *mut u64) -> i32;
     pub fn pvw_selftest_shamir_wide_mul(ctx: *mut PvwCtx, plain_modulus: *const u64, a: *const u64, b: *const u64, count: usize, out: *mut u64) -> i32;
     pub fn pvw_shamir_shares_packed_host(ctx: *const PvwCtx, secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: u64, seeds: *const u8, coeffs: *const u64, shares_out: *mut u64) -> i32;
     pub fn pvw_shamir_shares_packed_device(ctx: *mut PvwCtx, d_secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: u64, seeds: *const u8, d_coeffs: *const u64, d_shares: *mut u64, stream: *mut c_void) -> i32;

@@ -705,6 +705,41 @@ pub fn shamir_reconstruct_wide_checked(params: &Arc<PvwParameters>, indices: &[u
     Ok(r)
 }
 
+/// EXTENSION: what `shamir_reconstruct_wide_corrected` reports: `CorrectedSecrets` with wide secrets.
+pub struct CorrectedWideSecrets {
+    /// the value at 0 of the one polynomial within E columns of each row; 0 for an undecodable row
+    pub secrets: Vec<Wide>,
+    /// per secret: columns off that polynomial, or `sys::PVW_SHAMIR_UNDECODABLE`
+    pub nerr: Vec<u32>,
+    /// per column: decodable secrets that are off there
+    pub col_err: Vec<u32>,
+    /// `[num_secrets][words]`: bit `c % 64` of word `c / 64` names the columns counted in `nerr`
+    pub err_mask: Vec<u64>,
+    /// `ceil(indices.len() / 64)`
+    pub words: usize,
+}
+
+/// EXTENSION: `shamir_reconstruct_corrected` over an odd prime below 2^256, on the device
+/// (`pvw_shamir_reconstruct_wide_corrected`): the secrets although up to `(indices.len() - degree - 1) / 2` shares of each are
+/// wrong, in whichever columns.  `shares` as `shamir_reconstruct_wide_checked`.
+pub fn shamir_reconstruct_wide_corrected(params: &Arc<PvwParameters>, indices: &[u64], shares: &[Wide], degree: u32, plain_modulus: &Wide,
+                                         party_major: bool) -> Result<CorrectedWideSecrets> {
+    if indices.is_empty() || shares.is_empty() || shares.len() % indices.len() != 0 {
+        return Err(PvwError::InvalidParameters("shares must hold one element per index and secret".into()));
+    }
+    let (count, num) = (indices.len(), shares.len() / indices.len());
+    let (ss, ps) = if party_major { (1, num) } else { (count, 1) };
+    let words = (count + 63) / 64;
+    let mut r = CorrectedWideSecrets { secrets: vec![[0u64; 4]; num], nerr: vec![0u32; num], col_err: vec![0u32; count],
+                                       err_mask: vec![0u64; num * words], words };
+    check(unsafe {
+        sys::pvw_shamir_reconstruct_wide_corrected(params.hip.raw(), plain_modulus.as_ptr(), degree, indices.as_ptr(), count,
+                                                   shares.as_ptr() as *const u64, num, ss, ps, r.secrets.as_mut_ptr() as *mut u64,
+                                                   r.nerr.as_mut_ptr(), r.col_err.as_mut_ptr(), r.err_mask.as_mut_ptr())
+    })?;
+    Ok(r)
+}
+
 /// EXTENSION: `shamir_wide_from_limbs` where the limbs lie (`pvw_shamir_wide_from_limbs_device`): device
 /// pointers, `count` elements of `[count][4]` words written at `d_out`, asynchronous on `stream` (null: the context's).
 /// Strides `(count, 1)` read limb planes, `(1, num_limbs)` the `[party][dealer * NL + w]` result of a decrypt-all in place.
