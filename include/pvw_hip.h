@@ -33,7 +33,12 @@
  *     pvw_shamir_shares_packed (the concurrent calls of these: tests/test_gpu_shamir_packed.py), pvw_shamir_reconstruct_checked,
  *     pvw_shamir_reconstruct_corrected, pvw_shamir_evaluate_corrected (the concurrent calls of these two:
  *     tests/test_gpu_shamir_evaluate.py), pvw_shamir_reconstruct_erasures, pvw_shamir_evaluate_erasures (the concurrent calls of
- *     these two: tests/test_gpu_shamir_erasures.py),
+ *     these two: tests/test_gpu_shamir_erasures.py), pvw_shamir_shares_wide, pvw_deal_shares_wide[_rs],
+ *     pvw_shamir_reconstruct_wide_checked, pvw_shamir_reconstruct_wide_corrected, pvw_selftest_shamir_wide_step / _mul and, each
+ *     on the calling thread's stream, pvw_shamir_shares_wide_device, pvw_deal_shares_wide[_rs]_device,
+ *     pvw_shamir_wide_from_limbs_device, pvw_shamir_reconstruct_wide_checked_device / _corrected_device (the concurrent calls of
+ *     this family, a context's very first calls and a count whose launch needs the raised LDS limit among them:
+ *     tests/test_gpu_shamir_wide_concurrent.py),
  *     pvw_decrypt_batch / _checked / _plain, pvw_decrypt_all / _checked / _plain, pvw_ct_sum, pvw_decrypt_sum_checked,
  *     pvw_decrypt_all_sum_checked, pvw_ct_lincomb, pvw_decrypt_lincomb_plain, pvw_decrypt_all_lincomb_plain (the concurrent
  *     calls of these three: tests/test_gpu_ct_lincomb.py), pvw_ct_lincomb_many, pvw_decrypt_all_lincomb_many_plain (the concurrent

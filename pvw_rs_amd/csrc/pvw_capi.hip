@@ -562,11 +562,21 @@ static int32_t ensure_device(pvw_ctx* c) {
   return PVW_OK;
 }
 
+// Zeroes a block that has just been allocated and STAYS in use (recycled device memory may hold an earlier owner's data).
+// hipMemset returns to the host before the fill has run, and the legacy default stream it runs on is not ordered against the
+// workspaces' non-blocking streams: with that stream busy (a framework's work, other threads' fills) the fill landed AFTER the
+// first kernels had written the block -- a deal then encrypted zeros for shares (tests/test_gpu_shamir_wide_concurrent.py,
+// `default-stream`).  So the fill is waited for, once per block.  (A fill in front of hipFree needs no wait: hipFree waits.)
+static hipError_t zero_fresh(void* p, size_t bytes) {
+  const hipError_t e = hipMemset(p, 0, bytes);
+  return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
+}
+
 static int32_t ws_alloc(pvw_ctx* c, Workspace* w) {
   const size_t k = c->k, P = c->poly();
   PVW_HIP(hipMalloc((void**)&w->rhat, 4 * k * P * 8));   // up to 4 r-hat / s-hat vectors (mac_rows_multi)
   w->rhat_bytes = 4 * k * P * 8;
-  PVW_HIP(hipMemset(w->rhat, 0, w->rhat_bytes));          // recycled device memory may hold an earlier owner's data
+  PVW_HIP(zero_fresh(w->rhat, w->rhat_bytes));
   if (c->l <= 16) PVW_HIP(hipMalloc((void**)&w->esmall, ((size_t)c->rowsA() + c->rowsB()) * c->l * 8 + 16));
   return PVW_OK;
 }
@@ -1264,7 +1274,7 @@ static int32_t ws_share_buffer(pvw_ctx* c, Workspace* w) {
   const size_t bytes = (size_t)SHARE_PASS * c->n * 8;
   PVW_HIP(hipMalloc((void**)&w->shares, bytes));
   w->shares_bytes = bytes;
-  PVW_HIP(hipMemset(w->shares, 0, bytes));                 // recycled device memory may hold an earlier owner's data
+  PVW_HIP(zero_fresh(w->shares, bytes));
   return PVW_OK;
 }
 static int32_t ws_gemm_buffers(pvw_ctx* c, Workspace* w) {
@@ -1924,7 +1934,7 @@ static bool ahead_sets(pvw_ctx* c, Workspace* w) {
     if (!*e && hipEventCreateWithFlags(e, flags) != hipSuccess) { *e = nullptr; (void)hipGetLastError(); return false; }
   void* block = nullptr;
   if (hipMalloc(&block, set_bytes * ring.slots()) != hipSuccess) { (void)hipGetLastError(); return false; }
-  if (hipMemset(block, 0, set_bytes * ring.slots()) != hipSuccess) { (void)hipGetLastError(); hipFree(block); return false; }
+  if (zero_fresh(block, set_bytes * ring.slots()) != hipSuccess) { (void)hipGetLastError(); hipFree(block); return false; }
   w->ahead = ring;
   w->ahead_block = (char*)block;
   w->ahead_set_bytes = set_bytes;
