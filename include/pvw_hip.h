@@ -38,7 +38,9 @@
  *     on the calling thread's stream, pvw_shamir_shares_wide_device, pvw_deal_shares_wide[_rs]_device,
  *     pvw_shamir_wide_from_limbs_device, pvw_shamir_reconstruct_wide_checked_device / _corrected_device (the concurrent calls of
  *     this family, a context's very first calls and a count whose launch needs the raised LDS limit among them:
- *     tests/test_gpu_shamir_wide_concurrent.py),
+ *     tests/test_gpu_shamir_wide_concurrent.py), pvw_shamir_reconstruct_wide_erasures and, on the calling thread's stream,
+ *     pvw_shamir_reconstruct_wide_erasures_device / pvw_shamir_wide_erasure_mask_device (the concurrent calls of these:
+ *     tests/test_gpu_shamir_wide_erasures.py),
  *     pvw_decrypt_batch / _checked / _plain, pvw_decrypt_all / _checked / _plain, pvw_ct_sum, pvw_decrypt_sum_checked,
  *     pvw_decrypt_all_sum_checked, pvw_ct_lincomb, pvw_decrypt_lincomb_plain, pvw_decrypt_all_lincomb_plain (the concurrent
  *     calls of these three: tests/test_gpu_ct_lincomb.py), pvw_ct_lincomb_many, pvw_decrypt_all_lincomb_many_plain (the concurrent
@@ -1137,6 +1139,68 @@ PVW_API int32_t pvw_shamir_reconstruct_wide_corrected(pvw_ctx* ctx, const uint64
                                                       const uint64_t* indices, size_t count, const uint64_t* shares,
                                                       size_t num_secrets, size_t secret_stride, size_t point_stride, uint64_t* out,
                                                       uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask);
+/* Reconstruction with erasures over a prime field of up to 256 bits: the contract of
+ * pvw_shamir_reconstruct_erasures*  with wide elements.  A wide share arrives as num_limbs ciphertexts and is lost
+ * as soon as ONE of them is flagged by the checked decrypt, never arrived or came from a refused dealer; the combiner knows that
+ * before it reconstructs, and a share it KNOWS to be bad costs one redundant column instead of two.  The arguments of the
+ * matching pvw_shamir_reconstruct_wide_corrected* form in its order, and directly behind point_stride:
+ * erased [num_secrets][W], W = ceil(count / 64), bit c % 64 of word c / 64 of row s set iff share (s, c) is erased: the layout of
+ * err_mask, so one call's err_mask can be the next call's erased.  A device pointer in the _device form, a host pointer
+ * elsewhere; bits at columns >= count are ignored; NULL means no erasures, and the call is then the wide corrected call, bit for
+ * bit on every output: behind the argument checks it IS that call.
+ *   For row s let eps_s be the number of erased columns, r = count - degree - 1 and E_s = (r - eps_s) / 2 (rounded down).
+ *   Row s is DECODABLE iff eps_s <= r and some polynomial F_s of degree <= t disagrees with the row (read mod p) in at most E_s of
+ *   the columns that are not erased in row s: the wide corrected call's definition on the sub-row of those columns.  F_s is then
+ *   unique.  So 2 errors + erasures <= r per row; r erasures and no error still decode; eps_s > r is undecodable (a property of
+ *   the row, not an argument error).
+ *   decodable:   out[s][4] = F_s(0); nerr[s] = the number of non-erased columns that disagree; err_mask row s has exactly their
+ *                bits (an erased column is never reported as an error); col_err[c] counts the decodable rows with an error at c.
+ *   undecodable: out = 0, nerr = PVW_SHAMIR_UNDECODABLE, a zero mask row, nothing added to col_err.
+ *   The four words stored at an erased position influence no output: they may be anything, 2^256 - 1 included.  Column order,
+ *   determinism and the agreement of the three forms on every input (small p included) are those of the call extended.
+ * PVW_ERR_INVALID_PARAMETERS before any device work, nothing written: what the wide corrected forms refuse, with their texts and
+ * in their order.  The device forms keep exactly that call's bound, with or without a mask: r >= 4096 is refused.  No further
+ * refusal is needed: with a mask one wave keeps the erasure locator Gamma [eps + 1] and the two polynomials C, B [E_s + 1] of the
+ * recurrence in LDS, eps + 1 + 2 ((r - eps) / 2 + 1) <= r + 3 elements of 32 bytes, 131 136 bytes at r = 4095, and one gfx950
+ * workgroup may take 160 KiB.  No new status code.
+ * Under stream capture: the rule of the wide corrected device call, sized by a call WITH a mask (its scratch is the larger: the
+ * locators and the public power matrix have r + 1 rows); a stream sized by maskless calls alone is refused with this call's own
+ * error and nothing is enqueued.  The mask is read when the kernels run, so a replay may see a new mask.  The host-buffer form
+ * stages the mask rows of a piece with its shares and is covered by the concurrency promise above.  The mask, the erasure
+ * locators and the Forney syndromes are not secret; the secret regions are those of the call extended. */
+/* the contract in plain C++ on the host cores: per row the non-erased columns are compacted and decoded by the Berlekamp-Welch
+ * routine of pvw_shamir_reconstruct_wide_corrected_host with the same degree, mask bits and col_err scattered back: what the
+ * kernels are tested against, sharing nothing with them */
+PVW_API int32_t pvw_shamir_reconstruct_wide_erasures_host(const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                          size_t count, const uint64_t* shares, size_t num_secrets,
+                                                          size_t secret_stride, size_t point_stride, const uint64_t* erased,
+                                                          uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask);
+PVW_API int32_t pvw_shamir_reconstruct_wide_erasures_device(pvw_ctx* ctx, const uint64_t* plain_modulus, uint32_t degree,
+                                                            const uint64_t* indices, size_t count, const uint64_t* d_shares,
+                                                            size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                                            const uint64_t* d_erased, uint64_t* d_out, uint32_t* d_nerr,
+                                                            uint32_t* d_col_err, uint64_t* d_err_mask, void* stream);
+PVW_API int32_t pvw_shamir_reconstruct_wide_erasures(pvw_ctx* ctx, const uint64_t* plain_modulus, uint32_t degree,
+                                                     const uint64_t* indices, size_t count, const uint64_t* shares,
+                                                     size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                                     const uint64_t* erased, uint64_t* out, uint32_t* nerr, uint32_t* col_err,
+                                                     uint64_t* err_mask);
+/* The mask of wide shares from a per-limb decrypt report: the arguments of pvw_shamir_erasure_mask_* plus num_limbs and
+ * limb_stride.  Bit (s, c) of mask_out [num_secrets][W] is set iff, for some w < num_limbs, the element at
+ * s * secret_stride + c * point_stride + w * limb_stride has status & status_bits non-zero or noise > noise_bound.  Either array
+ * may be NULL, not both; both are only read (status is declared as the decrypt calls declare it, so their buffer passes as it
+ * is).  Every word of mask_out is written, padding bits 0.  Strides (NL, D NL, 1) with NL = num_limbs read the
+ * [party][dealer NL + w] report of pvw_decrypt_all_*_checked / _plain in place (every dealer a secret), so decrypt-all -> mask ->
+ * fold -> decode stays on the device.  With num_limbs = 1 the call is pvw_shamir_erasure_mask_*, bit for bit.
+ * PVW_ERR_INVALID_PARAMETERS, nothing written: what pvw_shamir_erasure_mask_* refuses, in its order, then num_limbs = 0 and
+ * limb_stride = 0. */
+PVW_API int32_t pvw_shamir_wide_erasure_mask_host(uint32_t* status, const uint64_t* noise, uint32_t status_bits, uint64_t noise_bound,
+                                                  size_t count, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                                  uint32_t num_limbs, size_t limb_stride, uint64_t* mask_out);
+PVW_API int32_t pvw_shamir_wide_erasure_mask_device(pvw_ctx* ctx, uint32_t* d_status, const uint64_t* d_noise, uint32_t status_bits,
+                                                    uint64_t noise_bound, size_t count, size_t num_secrets, size_t secret_stride,
+                                                    size_t point_stride, uint32_t num_limbs, size_t limb_stride,
+                                                    uint64_t* d_mask_out, void* stream);
 /* SELF-TEST: the kernels' general product on the device, out[i] = a[i] b[i] mod p for a, b [count][4] below p (anything else:
  * INVALID_PARAMETERS). */
 PVW_API int32_t pvw_selftest_shamir_wide_mul(pvw_ctx* ctx, const uint64_t* plain_modulus, const uint64_t* a, const uint64_t* b,

@@ -176,6 +176,17 @@ _SIGNATURES = {
     "pvw_shamir_reconstruct_wide_corrected_device": [_P, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P, _P,
                                                      _P],
     "pvw_shamir_reconstruct_wide_corrected": [_P, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P, _P],
+    # wide reconstruction with erasures: the wide corrected calls with `erased` directly behind point_stride
+    "pvw_shamir_reconstruct_wide_erasures_host": [_P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P, _P,
+                                                  _P],
+    "pvw_shamir_reconstruct_wide_erasures_device": [_P, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P,
+                                                    _P, _P, _P],
+    "pvw_shamir_reconstruct_wide_erasures": [_P, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P, _P,
+                                             _P],
+    "pvw_shamir_wide_erasure_mask_host": [_P, _P, C.c_uint32, C.c_uint64, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32,
+                                          C.c_size_t, _P],
+    "pvw_shamir_wide_erasure_mask_device": [_P, _P, _P, C.c_uint32, C.c_uint64, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                            C.c_uint32, C.c_size_t, _P, _P],
     "pvw_selftest_shamir_wide_mul": [_P, _P, _P, _P, C.c_size_t, _P],
     "pvw_shamir_shares_packed_host": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P],
     "pvw_shamir_shares_packed_device": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P, _P],

@@ -1106,21 +1106,30 @@ def shamir_reconstruct_wide_checked(params: Optional[PvwParameters], indices: Se
 
 
 def shamir_reconstruct_wide_corrected(params: Optional[PvwParameters], indices: Sequence[int], shares, degree: int, plain_modulus: int, *,
-                                      host: bool = False,
-                                      layout: str = "secret_major") -> Tuple[List[int], np.ndarray, np.ndarray, np.ndarray]:
+                                      host: bool = False, layout: str = "secret_major",
+                                      erased=None) -> Tuple[List[int], np.ndarray, np.ndarray, np.ndarray]:
     """EXTENSION: shamir_reconstruct_corrected over an odd prime plain_modulus < 2^256: the secrets although up to
     E = (len(indices) - degree - 1) // 2 shares of each are wrong, in whichever columns.  shares and layout as
     shamir_reconstruct_wide_checked.  On the device (pvw_shamir_reconstruct_wide_corrected); host=True: the plain C++ restatement
     (pvw_shamir_reconstruct_wide_corrected_host, Berlekamp-Welch, no GPU; params may be None).  Returns (secrets as ints, nerr,
     col_err, err_mask) as shamir_reconstruct_corrected does: an undecodable row has secret 0, nerr SHAMIR_UNDECODABLE and an empty
-    mask row."""
+    mask row.
+    erased: the shares KNOWN to be bad, as shamir_reconstruct_corrected takes them: a matrix of truth values in
+    `layout` or packed words in the layout of err_mask (an earlier call's err_mask, or shamir_wide_erasure_mask).  Each costs one
+    redundant column instead of two: row s decodes while 2 * errors + erasures <= len(indices) - degree - 1; the words at an
+    erased position influence nothing and an erased column is never reported as an error.  Routes to
+    pvw_shamir_reconstruct_wide_erasures*; omitted, the call is untouched."""
     idx, sh, S, count, strides = _wide_share_matrix(indices, shares, layout)
     out = np.zeros((S, WIDE_WORDS), dtype=np.uint64)
     nerr, col_err = np.zeros(S, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
     err_mask = np.zeros((S, (count + 63) // 64), dtype=np.uint64)
-    args = (_ptr(_wide_modulus(plain_modulus)), int(degree), _ptr(idx), count, _ptr(sh), S, strides[0], strides[1], _ptr(out), _ptr(nerr),
-            _ptr(col_err), _ptr(err_mask))
-    _reconstruct_call(params, "shamir_reconstruct_wide_corrected", host, args)
+    head = (_ptr(_wide_modulus(plain_modulus)), int(degree), _ptr(idx), count, _ptr(sh), S, strides[0], strides[1])
+    tail = (_ptr(out), _ptr(nerr), _ptr(col_err), _ptr(err_mask))
+    if erased is None:
+        _reconstruct_call(params, "shamir_reconstruct_wide_corrected", host, head + tail)
+    else:
+        er = _erased_words(erased, S, count, layout)
+        _reconstruct_call(params, "shamir_reconstruct_wide_erasures", host, head + (_ptr(er),) + tail)
     return _wide_ints(out), nerr, col_err, err_mask
 
 
@@ -1294,6 +1303,73 @@ def shamir_erasure_mask(status=None, noise=None, *, status_bits: int = 0xFFFFFFF
     torch.cuda.synchronize(dev)
     params._call("pvw_shamir_erasure_mask_device", _dptr(d_st) if d_st is not None else None, _dptr(d_nz) if d_nz is not None else None,
                  int(status_bits), int(noise_bound), count, S, strides[0], strides[1], _dptr(d_mask), None)
+    params.synchronize()
+    return d_mask.cpu().numpy().view(np.uint64)
+
+
+def shamir_wide_erasure_mask(status=None, noise=None, *, num_limbs: int, status_bits: int = 0xFFFFFFFF,
+                             noise_bound: int = 0xFFFFFFFFFFFFFFFF, layout: str = "secret_major", host: bool = False,
+                             params: Optional[PvwParameters] = None, stream=None):
+    """EXTENSION: the packed erasure mask [S][ceil(count / 64)] of wide shares from a per-limb decrypt report.
+    status (uint32) and noise (uint64) are matrices whose rows hold num_limbs consecutive entries per share: "secret_major" is
+    [S][count * num_limbs], "party_major" is [count][S * num_limbs], the [party][dealer * NL + w] report of
+    decrypt_all_party_shares_checked over the limb ciphertexts of deal_party_shares_wide (every dealer a secret); either may be
+    None.  Share (s, c) is erased iff ONE of its limbs has status & status_bits non-zero or noise > noise_bound.  host=True:
+    pvw_shamir_wide_erasure_mask_host (no GPU); otherwise pvw_shamir_wide_erasure_mask_device on the context of `params`: device
+    tensors (int32 status, int64 noise) are read in place, asynchronously on `stream`, and the mask comes back as a device tensor
+    (int64 words), which is what pvw_shamir_reconstruct_wide_erasures_device takes."""
+    if layout not in ("secret_major", "party_major"):
+        raise ValueError(layout)
+    if status is None and noise is None:
+        raise PvwError(15, "status and noise are both None")
+    NL = int(num_limbs)
+
+    def dims(shape):
+        if len(shape) != 2 or NL <= 0 or shape[1] % NL:
+            raise PvwError(15, "a report is a matrix whose rows hold num_limbs entries per share")
+        S, count = (shape[0], shape[1] // NL) if layout == "secret_major" else (shape[1] // NL, shape[0])
+        return S, count, ((count * NL, NL) if layout == "secret_major" else (NL, S * NL))
+
+    if any(hasattr(a, "data_ptr") for a in (status, noise)):
+        import torch
+        first = status if status is not None else noise
+        if params is None or host or any(a is not None and (not hasattr(a, "data_ptr") or not a.is_contiguous() or a.dim() != 2
+                                                             or a.shape != first.shape) for a in (status, noise)):
+            raise PvwError(15, "device reports need params, host=False and contiguous matrices of one shape")
+        S, count, strides = dims(tuple(first.shape))
+        d_mask = torch.zeros((S, (count + 63) // 64), dtype=torch.int64, device=first.device)
+        params._call("pvw_shamir_wide_erasure_mask_device", _dptr(status), _dptr(noise), int(status_bits), int(noise_bound), count, S,
+                     strides[0], strides[1], NL, 1, _dptr(d_mask), _stream_ptr(stream))
+        return d_mask
+    st = None if status is None else np.ascontiguousarray(np.asarray(status, dtype=np.uint32))
+    if noise is None:
+        nz = None
+    elif isinstance(noise, np.ndarray) and noise.dtype.kind in "ui":
+        nz = np.ascontiguousarray(noise.astype(np.uint64, copy=False))
+    else:
+        nz = np.ascontiguousarray(np.array([[int(v) & 0xFFFFFFFFFFFFFFFF for v in row] for row in noise], dtype=np.uint64))
+    shape = (st if st is not None else nz).shape
+    if st is not None and nz is not None and st.shape != nz.shape:
+        raise PvwError(15, "status and noise must be matrices of one shape")
+    S, count, strides = dims(shape)
+    mask = np.zeros((S, (count + 63) // 64), dtype=np.uint64)
+    if host:
+        L = params._lib if params is not None else _ffi.lib()
+        _check(L.pvw_shamir_wide_erasure_mask_host(_ptr(st) if st is not None else None, _ptr(nz) if nz is not None else None,
+                                                   int(status_bits), int(noise_bound), count, S, strides[0], strides[1], NL, 1,
+                                                   _ptr(mask)), L)
+        return mask
+    if params is None:
+        raise PvwError(15, "the device form needs params (or host=True)")
+    import torch
+    dev = torch.device("cuda", params.device) if getattr(params, "device", -1) >= 0 else torch.device("cuda")
+    d_st = torch.from_numpy(st.view(np.int32)).to(dev) if st is not None else None
+    d_nz = torch.from_numpy(nz.view(np.int64)).to(dev) if nz is not None else None
+    d_mask = torch.zeros(mask.shape, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize(dev)
+    params._call("pvw_shamir_wide_erasure_mask_device", _dptr(d_st) if d_st is not None else None,
+                 _dptr(d_nz) if d_nz is not None else None, int(status_bits), int(noise_bound), count, S, strides[0], strides[1], NL, 1,
+                 _dptr(d_mask), None)
     params.synchronize()
     return d_mask.cpu().numpy().view(np.uint64)
 

@@ -4236,8 +4236,11 @@ struct ReconstructWide {
   const u64* indices;   // [count], host
   size_t count, S, secret_stride, point_stride;
   WideMod m;            // set by reconstruct_wide_checks
+  bool erasures = false;   // a call with an erasure mask: the locator of a row has up to r + 1 coefficients
   size_t T() const { return count - degree; }
   size_t ws_bytes() const { return shamir_interp_wide_words(count, degree) * 8; }
+  size_t red() const { return count - degree - 1; }
+  size_t nk() const { return erasures ? red() + 1 : red() / 2 + 1; }   // the locator capacity of the corrected decode
 };
 // the order of reconstruct_checks: NULL, no secrets, too few shares, a duplicate, the range, the modulus, the strides
 static int32_t reconstruct_wide_checks(ReconstructWide& r, const void* shares, const void* out) {
@@ -4597,11 +4600,11 @@ int32_t pvw_shamir_reconstruct_wide_corrected_host(const uint64_t* plain_modulus
 // The device scratch of one call, in words from its base, laid out like CorrectLayout with elements of four words:
 //   M [cap][count][4] | x, aux, lambda, V, X (shamir_correct_wide_public_words) | Synd [cap][r][4] | Lambda [cap][nk][4] | L [cap] (u32)
 // M leads the block and is the one region marked secret besides the staging.  Every offset is a multiple of four words.
+// nk, the locator capacity, is E + 1, or r + 1 for a call with erasures: X has nk rows as well.
 struct CorrectWideLayout {
   size_t count, r, nk, cap;
   size_t pub, synd, lam, L, total;   // word offsets
-  CorrectWideLayout(const ReconstructWide& rc, size_t cap_)
-      : count(rc.count), r(rc.count - rc.degree - 1), nk((rc.count - rc.degree - 1) / 2 + 1), cap(cap_) {
+  CorrectWideLayout(const ReconstructWide& rc, size_t cap_) : count(rc.count), r(rc.red()), nk(rc.nk()), cap(cap_) {
     pub = cap * count * 4;
     synd = pub + shamir_correct_wide_public_words(count, rc.degree, nk);
     lam = synd + cap * r * 4;
@@ -4611,10 +4614,9 @@ struct CorrectWideLayout {
   size_t bytes() const { return total * 8; }
   size_t m_bytes() const { return cap * count * 32; }
 };
-// secrets per pass over the kernels, by the rule of correct_piece: a secret takes (count + r + E + 1) 32 + 4 bytes of scratch
+// secrets per pass over the kernels, by the rule of correct_piece: a secret takes (count + r + nk) 32 + 4 bytes of scratch
 static size_t correct_wide_piece(const ReconstructWide& r) {
-  const size_t red = r.count - r.degree - 1;
-  const size_t per = (r.count + red + red / 2 + 1) * 32 + 4;
+  const size_t per = (r.count + r.red() + r.nk()) * 32 + 4;
   const long env = PVW_ENV_INT("PVW_CORRECT_PIECE_BYTES", 0);
   const size_t budget = env > 0 ? (size_t)env : (size_t)64 << 20;
   size_t cap = budget / per;
@@ -4624,7 +4626,7 @@ static size_t correct_wide_piece(const ReconstructWide& r) {
 }
 static int32_t correct_wide_device_checks(const ReconstructWide& r) {
   PVW_TRY(reconstruct_wide_device_checks(r));
-  if ((r.count - r.degree - 1) / 2 + 1 > PVW_SHAMIR_WIDE_MAX_LOCATOR) {
+  if (r.red() / 2 + 1 > PVW_SHAMIR_WIDE_MAX_LOCATOR) {   // with a mask as well: r + 3 elements of LDS then, 131 136 bytes at the bound
     char buf[160];
     snprintf(buf, sizeof buf, "on the device the wide locator holds at most %d coefficients: count - degree - 1 must be below %d",
              PVW_SHAMIR_WIDE_MAX_LOCATOR, 2 * PVW_SHAMIR_WIDE_MAX_LOCATOR);
@@ -4641,20 +4643,27 @@ static int32_t correct_wide_weights(pvw_ctx* c, const ReconstructWide& r, const 
   return PVW_OK;
 }
 // ns <= lay.cap secrets from d_shares: their out, nerr and mask rows; col_err, zeroed by the caller, is added to
+// d_erased: the ns rows of the erasure mask, or NULL for the call of 8.20.
 static int32_t correct_wide_piece_enqueue(pvw_ctx* c, const ReconstructWide& r, const WideMont& mm, const CorrectWideLayout& lay, u64* ws,
                                           const u64* d_shares, size_t ns, size_t secret_stride, size_t point_stride, u64* d_out,
-                                          u32* d_nerr, u32* d_col_err, u64* d_mask, hipStream_t s) {
+                                          u32* d_nerr, u32* d_col_err, u64* d_mask, hipStream_t s, const u64* d_erased = nullptr) {
   ProfScope ps(c, "shamir_correct_wide", s);
   const u64* pub = ws + lay.pub;
   const u64 *lambda = pub + (2 * r.count + 1) * 4, *V = lambda + r.count * 4, *X = V + r.count * lay.r * 4;
   u64 *M = ws, *synd = ws + lay.synd, *Lam = ws + lay.lam;
   u32* L = (u32*)(ws + lay.L);
-  ShamirMatmulWide a{};
+  ShamirMaskedMatmulWide a{};
   a.A = d_shares, a.secret_stride = secret_stride, a.term_stride = point_stride;
   a.W = V, a.out = synd;
   a.ns = (u32)ns, a.terms = (u32)r.count, a.T = (u32)lay.r, a.m = mm;
-  PVW_HIP(launch_shamir_matmul_wide(a, s));
-  PVW_HIP(launch_shamir_bm_wide(synd, Lam, L, (u32)ns, (u32)lay.r, mm, s));
+  a.erased = d_erased, a.ewords = (u32)((r.count + 63) / 64);
+  if (d_erased) {
+    PVW_HIP(launch_shamir_matmul_masked_wide(a, s));
+    PVW_HIP(launch_shamir_bm_erasures_wide(synd, d_erased, pub, Lam, L, (u32)ns, (u32)r.count, (u32)lay.r, mm, s));
+  } else {
+    PVW_HIP(launch_shamir_matmul_wide(a, s));
+    PVW_HIP(launch_shamir_bm_wide(synd, Lam, L, (u32)ns, (u32)lay.r, mm, s));
+  }
   ShamirMatmulWide b{};
   b.A = Lam, b.secret_stride = lay.nk, b.term_stride = 1;
   b.W = X, b.out = M;
@@ -4665,10 +4674,36 @@ static int32_t correct_wide_piece_enqueue(pvw_ctx* c, const ReconstructWide& r, 
   f.M = M, f.Lam = Lam, f.L = L, f.lam = lambda;
   f.out = d_out, f.nerr = d_nerr, f.col_err = d_col_err, f.mask = d_mask;
   f.count = (u32)r.count, f.E = (u32)lay.nk - 1, f.m = mm;
-  PVW_HIP(launch_shamir_correct_finish_wide(f, (u32)ns, s));
+  if (d_erased) PVW_HIP(launch_shamir_erasures_finish_wide(f, d_erased, (u32)ns, s));
+  else PVW_HIP(launch_shamir_correct_finish_wide(f, (u32)ns, s));
   return PVW_OK;
 }
 
+// The device call of 8.20 behind its argument checks; with d_erased (r.erasures) that of 8.21.  `unsized`: what a captured call
+// is refused with when nothing has sized the workspace.
+static int32_t correct_wide_device_call(pvw_ctx* c, const ReconstructWide& r, const u64* d_shares, const u64* d_erased, u64* d_out,
+                                        u32* d_nerr, u32* d_col_err, u64* d_err_mask, void* stream, const char* unsized) {
+  const WideMont mm = make_wide_mont(r.p);
+  const CorrectWideLayout lay(r, correct_wide_piece(r));
+  const size_t count = r.count, words = (count + 63) / 64;
+  // the caller's stream is checked before the device is touched (pvw_shamir_reconstruct_checked_device)
+  auto sized = [&](hipStream_t s) { return grown_capture_check(c, s, &Workspace::correct_wide_bytes, lay.bytes(), unsized); };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
+    if (w->correct_wide_bytes < lay.bytes()) ws_public(w, w->correct_wide, w->correct_wide_bytes);   // the block is about to go
+    PVW_TRY(ws_grow(&w->correct_wide, &w->correct_wide_bytes, lay.bytes(), s, true));
+    ws_mark_secret(w, w->correct_wide, lay.m_bytes());
+    PVW_TRY(correct_wide_weights(c, r, mm, lay, w->correct_wide, s));
+    PVW_HIP(launch_shamir_zero_counts(d_col_err, count, s));
+    for (size_t s0 = 0; s0 < r.S; s0 += lay.cap) {
+      const size_t ns = r.S - s0 < lay.cap ? r.S - s0 : lay.cap;
+      PVW_TRY(correct_wide_piece_enqueue(c, r, mm, lay, w->correct_wide, d_shares + s0 * r.secret_stride * 4, ns, r.secret_stride,
+                                         r.point_stride, d_out + s0 * 4, Report::from(d_nerr, s0), d_col_err,
+                                         Report::from(d_err_mask, s0 * words), s, Report::from(d_erased, s0 * words)));
+    }
+    return PVW_OK;
+  });
+}
 int32_t pvw_shamir_reconstruct_wide_corrected_device(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
                                                      size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
                                                      size_t point_stride, uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err,
@@ -4677,51 +4712,28 @@ int32_t pvw_shamir_reconstruct_wide_corrected_device(pvw_ctx* c, const uint64_t*
   ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
   PVW_TRY(reconstruct_wide_checks(r, d_shares, d_out));
   PVW_TRY(correct_wide_device_checks(r));
-  const WideMont mm = make_wide_mont(plain_modulus);
-  const CorrectWideLayout lay(r, correct_wide_piece(r));
-  const size_t words = (count + 63) / 64;
-  // the caller's stream is checked before the device is touched (pvw_shamir_reconstruct_checked_device)
-  auto sized = [&](hipStream_t s) {
-    return grown_capture_check(c, s, &Workspace::correct_wide_bytes, lay.bytes(),
-                               "corrected reconstruction under stream capture: run a call with the same degree and count and at least as "
-                               "many secrets on this stream outside capture first (it sizes the workspace)");
-  };
-  if (stream) PVW_TRY(sized((hipStream_t)stream));
-  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
-    if (w->correct_wide_bytes < lay.bytes()) ws_public(w, w->correct_wide, w->correct_wide_bytes);   // the block is about to go
-    PVW_TRY(ws_grow(&w->correct_wide, &w->correct_wide_bytes, lay.bytes(), s, true));
-    ws_mark_secret(w, w->correct_wide, lay.m_bytes());
-    PVW_TRY(correct_wide_weights(c, r, mm, lay, w->correct_wide, s));
-    PVW_HIP(launch_shamir_zero_counts(d_col_err, count, s));
-    for (size_t s0 = 0; s0 < num_secrets; s0 += lay.cap) {
-      const size_t ns = num_secrets - s0 < lay.cap ? num_secrets - s0 : lay.cap;
-      PVW_TRY(correct_wide_piece_enqueue(c, r, mm, lay, w->correct_wide, d_shares + s0 * secret_stride * 4, ns, secret_stride,
-                                         point_stride, d_out + s0 * 4, Report::from(d_nerr, s0), d_col_err,
-                                         Report::from(d_err_mask, s0 * words), s));
-    }
-    return PVW_OK;
-  });
+  return correct_wide_device_call(c, r, d_shares, nullptr, d_out, d_nerr, d_col_err, d_err_mask, stream,
+                                  "corrected reconstruction under stream capture: run a call with the same degree and count and at least as "
+                                  "many secrets on this stream outside capture first (it sizes the workspace)");
 }
 
 // host buffers: the secrets go up in pieces as pvw_shamir_reconstruct_wide_checked stages them (a 2D copy for dense rows, else a
 // host repack that is wiped at the end), a piece no larger than one pass over the kernels; the public matrices are made once and
 // col_err adds up over the pieces.  The staged shares, the staged secrets and M are cleared before the call returns.
-int32_t pvw_shamir_reconstruct_wide_corrected(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
-                                              size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
-                                              size_t point_stride, uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
-  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
-  PVW_TRY(reconstruct_wide_checks(r, shares, out));
-  PVW_TRY(correct_wide_device_checks(r));
+// Behind the argument checks; with `erased` (r.erasures) the host-buffer call of 8.21, whose mask rows are staged with the shares
+// of their piece, whichever way those are copied.
+static int32_t correct_wide_host_call(pvw_ctx* c, const ReconstructWide& r, const u64* shares, const u64* erased, u64* out, u32* nerr,
+                                      u32* col_err, u64* err_mask) {
   PVW_TRY(ensure_device(c));
-  const WideMont mm = make_wide_mont(plain_modulus);
+  const WideMont mm = make_wide_mont(r.p);
+  const size_t count = r.count, num_secrets = r.S, secret_stride = r.secret_stride, point_stride = r.point_stride;
   const size_t words = (count + 63) / 64;
-  size_t per = chunk_1gib((count + 1) * 32 + words * 8 + 4, num_secrets);
+  size_t per = chunk_1gib((count + 1) * 32 + (words + (erased ? words : 0)) * 8 + 4, num_secrets);
   if (per > correct_wide_piece(r)) per = correct_wide_piece(r);
   const CorrectWideLayout lay(r, per);
   Scratch sc;
   const size_t r_sh = sc.add(per * count * 32), r_out = sc.add(per * 32), r_ws = sc.add(lay.bytes()), r_nerr = sc.add(per * 4),
-               r_col = sc.add(count * 4), r_mask = sc.add(per * words * 8);
+               r_col = sc.add(count * 4), r_mask = sc.add(per * words * 8), r_er = sc.add(erased ? per * words * 8 : 0);
   const bool dense = point_stride == 1 && secret_stride >= count;
   std::vector<u64> packed(dense ? 0 : per * count * 4);
   const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
@@ -4730,6 +4742,7 @@ int32_t pvw_shamir_reconstruct_wide_corrected(pvw_ctx* c, const uint64_t* plain_
     ws_mark_secret(w, d_sh, (size_t)((char*)ws - (char*)d_sh) + lay.m_bytes());   // staged shares | staged secrets | M
     u32 *d_nerr = nerr ? sc.at<u32>(r_nerr) : nullptr, *d_col = col_err ? sc.at<u32>(r_col) : nullptr;
     u64* d_mask = err_mask ? sc.at(r_mask) : nullptr;
+    u64* d_er = erased ? sc.at(r_er) : nullptr;
     PVW_TRY(correct_wide_weights(c, r, mm, lay, ws, w->stream));
     PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
     for (size_t s0 = 0; s0 < num_secrets; s0 += per) {
@@ -4743,7 +4756,8 @@ int32_t pvw_shamir_reconstruct_wide_corrected(pvw_ctx* c, const uint64_t* plain_
             memcpy(&packed[(s * count + col) * 4], shares + ((s0 + s) * secret_stride + col * point_stride) * 4, 32);
         PVW_HIP(hipMemcpyAsync(d_sh, packed.data(), cnt * count * 32, hipMemcpyHostToDevice, w->stream));
       }
-      PVW_TRY(correct_wide_piece_enqueue(c, r, mm, lay, ws, d_sh, cnt, count, 1, d_out, d_nerr, d_col, d_mask, w->stream));
+      if (erased) PVW_HIP(hipMemcpyAsync(d_er, erased + s0 * words, cnt * words * 8, hipMemcpyHostToDevice, w->stream));
+      PVW_TRY(correct_wide_piece_enqueue(c, r, mm, lay, ws, d_sh, cnt, count, 1, d_out, d_nerr, d_col, d_mask, w->stream, d_er));
       PVW_HIP(hipMemcpyAsync(out + s0 * 4, d_out, cnt * 32, hipMemcpyDeviceToHost, w->stream));
       if (nerr) PVW_HIP(hipMemcpyAsync(nerr + s0, d_nerr, cnt * 4, hipMemcpyDeviceToHost, w->stream));
       if (err_mask) PVW_HIP(hipMemcpyAsync(err_mask + s0 * words, d_mask, cnt * words * 8, hipMemcpyDeviceToHost, w->stream));
@@ -4755,6 +4769,148 @@ int32_t pvw_shamir_reconstruct_wide_corrected(pvw_ctx* c, const uint64_t* plain_
   volatile u64* vp = packed.data();
   for (size_t i = 0; i < packed.size(); ++i) vp[i] = 0;
   return rc;
+}
+int32_t pvw_shamir_reconstruct_wide_corrected(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                              size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
+                                              size_t point_stride, uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  PVW_TRY(reconstruct_wide_checks(r, shares, out));
+  PVW_TRY(correct_wide_device_checks(r));
+  return correct_wide_host_call(c, r, shares, nullptr, out, nerr, col_err, err_mask);
+}
+
+// ------------------------------------------------------------------------ erasures below 2^256
+// The contract of 8.16 with wide elements: erased [num_secrets][W] in the layout of err_mask; with eps_s erased columns in row s
+// and E_s = (r - eps_s) / 2, row s is decodable iff eps_s <= r and some F_s of degree <= t disagrees with the row in at most E_s
+// of the columns that are not erased.  erased == NULL is the call of 8.20: every entry point hands such a call over as it is.
+
+// The contract in plain C++: per row the columns that are not erased are compacted, berlekamp_welch_wide_host decodes that
+// sub-row with the same t, and the mask bits and col_err go back to the original columns.  A row with fewer than t + 1 columns
+// left (eps_s > r) is undecodable.  Nothing at an erased position is read.
+static void erasures_wide_host(const ReconstructWide& r, const u64* shares, const u64* erased, u64* out, u32* nerr, u32* col_err,
+                               u64* err_mask) {
+  const size_t count = r.count, words = (count + 63) / 64;
+  std::vector<size_t> cols;
+  std::vector<u64> sub_idx(count), sub_sh(count * 4), sub_mask(words);
+  std::vector<u32> sub_col(count);
+  if (col_err) std::fill(col_err, col_err + count, 0u);
+  for (size_t s = 0; s < r.S; ++s) {
+    cols.clear();
+    for (size_t c = 0; c < count; ++c)
+      if (!((erased[s * words + c / 64] >> (c % 64)) & 1)) cols.push_back(c);
+    if (err_mask) std::fill(err_mask + s * words, err_mask + (s + 1) * words, (u64)0);
+    const size_t n = cols.size();
+    if (n < (size_t)r.degree + 1) {
+      for (int k = 0; k < 4; ++k) out[s * 4 + k] = 0;
+      if (nerr) nerr[s] = PVW_SHAMIR_UNDECODABLE;
+      continue;
+    }
+    for (size_t i = 0; i < n; ++i) {
+      sub_idx[i] = r.indices[cols[i]];
+      memcpy(&sub_sh[i * 4], shares + (s * r.secret_stride + cols[i] * r.point_stride) * 4, 32);
+    }
+    ReconstructWide sub{r.p, r.degree, sub_idx.data(), n, 1, n, 1, r.m};
+    u32 ne = 0;
+    berlekamp_welch_wide_host(sub, sub_sh.data(), out + s * 4, &ne, sub_col.data(), sub_mask.data());
+    if (nerr) nerr[s] = ne;
+    for (size_t i = 0; i < n; ++i)
+      if ((sub_mask[i / 64] >> (i % 64)) & 1) {
+        if (col_err) ++col_err[cols[i]];
+        if (err_mask) err_mask[s * words + cols[i] / 64] |= (u64)1 << (cols[i] % 64);
+      }
+  }
+  volatile u64* vp = sub_sh.data();                                              // as secret as the shares
+  for (size_t i = 0; i < sub_sh.size(); ++i) vp[i] = 0;
+}
+static const char* const kWideErasuresUnsized =
+    "wide reconstruction with erasures under stream capture: run a call with an erasure mask, the same degree and count and at least as "
+    "many secrets on this stream outside capture first (it sizes the workspace)";
+
+int32_t pvw_shamir_reconstruct_wide_erasures_host(const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                                  const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                                  const uint64_t* erased, uint64_t* out, uint32_t* nerr, uint32_t* col_err,
+                                                  uint64_t* err_mask) {
+  if (!erased)
+    return pvw_shamir_reconstruct_wide_corrected_host(plain_modulus, degree, indices, count, shares, num_secrets, secret_stride,
+                                                      point_stride, out, nerr, col_err, err_mask);
+  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}, true};
+  PVW_TRY(reconstruct_wide_checks(r, shares, out));
+  erasures_wide_host(r, shares, erased, out, nerr, col_err, err_mask);
+  return PVW_OK;
+}
+int32_t pvw_shamir_reconstruct_wide_erasures_device(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                    size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
+                                                    size_t point_stride, const uint64_t* d_erased, uint64_t* d_out, uint32_t* d_nerr,
+                                                    uint32_t* d_col_err, uint64_t* d_err_mask, void* stream) {
+  if (!d_erased)
+    return pvw_shamir_reconstruct_wide_corrected_device(c, plain_modulus, degree, indices, count, d_shares, num_secrets, secret_stride,
+                                                        point_stride, d_out, d_nerr, d_col_err, d_err_mask, stream);
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}, true};
+  PVW_TRY(reconstruct_wide_checks(r, d_shares, d_out));
+  PVW_TRY(correct_wide_device_checks(r));
+  return correct_wide_device_call(c, r, d_shares, d_erased, d_out, d_nerr, d_col_err, d_err_mask, stream, kWideErasuresUnsized);
+}
+int32_t pvw_shamir_reconstruct_wide_erasures(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                             size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
+                                             size_t point_stride, const uint64_t* erased, uint64_t* out, uint32_t* nerr,
+                                             uint32_t* col_err, uint64_t* err_mask) {
+  if (!erased)
+    return pvw_shamir_reconstruct_wide_corrected(c, plain_modulus, degree, indices, count, shares, num_secrets, secret_stride,
+                                                 point_stride, out, nerr, col_err, err_mask);
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}, true};
+  PVW_TRY(reconstruct_wide_checks(r, shares, out));
+  PVW_TRY(correct_wide_device_checks(r));
+  return correct_wide_host_call(c, r, shares, erased, out, nerr, col_err, err_mask);
+}
+
+// The mask of wide shares from a per-limb decrypt report: bit (s, c) set iff for some w < num_limbs the element at
+// s * secret_stride + c * point_stride + w * limb_stride has status & status_bits or noise > noise_bound.  The checks of
+// erasure_mask_checks first, in its order, then the two limb arguments.
+static int32_t wide_erasure_mask_checks(const void* status, const void* noise, size_t count, size_t num_secrets, size_t secret_stride,
+                                        size_t point_stride, uint32_t num_limbs, size_t limb_stride, const void* mask_out) {
+  PVW_TRY(erasure_mask_checks(status, noise, count, num_secrets, secret_stride, point_stride, mask_out));
+  if (num_limbs == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "a share of no limbs");
+  if (limb_stride == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "a stride of 0");
+  return PVW_OK;
+}
+int32_t pvw_shamir_wide_erasure_mask_host(uint32_t* status, const uint64_t* noise, uint32_t status_bits, uint64_t noise_bound, size_t count,
+                                          size_t num_secrets, size_t secret_stride, size_t point_stride, uint32_t num_limbs,
+                                          size_t limb_stride, uint64_t* mask_out) {
+  PVW_TRY(wide_erasure_mask_checks(status, noise, count, num_secrets, secret_stride, point_stride, num_limbs, limb_stride, mask_out));
+  const size_t words = (count + 63) / 64;
+  std::fill(mask_out, mask_out + num_secrets * words, (u64)0);
+  for (size_t s = 0; s < num_secrets; ++s)
+    for (size_t c = 0; c < count; ++c)
+      for (size_t w = 0; w < num_limbs; ++w) {
+        const size_t off = s * secret_stride + c * point_stride + w * limb_stride;
+        if ((status && (status[off] & status_bits)) || (noise && noise[off] > noise_bound)) mask_out[s * words + c / 64] |= (u64)1 << (c % 64);
+      }
+  return PVW_OK;
+}
+int32_t pvw_shamir_wide_erasure_mask_device(pvw_ctx* c, uint32_t* d_status, const uint64_t* d_noise, uint32_t status_bits,
+                                            uint64_t noise_bound, size_t count, size_t num_secrets, size_t secret_stride,
+                                            size_t point_stride, uint32_t num_limbs, size_t limb_stride, uint64_t* d_mask_out,
+                                            void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(wide_erasure_mask_checks(d_status, d_noise, count, num_secrets, secret_stride, point_stride, num_limbs, limb_stride, d_mask_out));
+  if (count >= ((size_t)1 << 31) || num_secrets >= ((size_t)1 << 31))
+    return fail(PVW_ERR_INVALID_PARAMETERS, "count and num_secrets must be below 2^31 on the device");
+  // no scratch of its own; under capture the stream's workspace must exist already (pvw_shamir_erasure_mask_device)
+  auto sized = [&](hipStream_t s) {
+    return grown_capture_check(c, s, &Workspace::correct_wide_bytes, 0,
+                               "wide erasure mask under stream capture: run a call on this stream outside capture first (it makes the "
+                               "stream's workspace)");
+  };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  return device_call(c, stream, sized, [&](Workspace*, hipStream_t s) -> int32_t {
+    ProfScope ps(c, "shamir_wide_erasure_mask", s);
+    PVW_HIP(launch_shamir_wide_erasure_mask(d_status, d_noise, status_bits, noise_bound, (u32)count, (u32)num_secrets, secret_stride,
+                                            point_stride, num_limbs, limb_stride, d_mask_out, s));
+    return PVW_OK;
+  });
 }
 
 // SELF-TEST: the kernels' product on the device, out = a b mod p

@@ -425,7 +425,8 @@ hipError_t launch_shamir_erasure_mask(const u32* status, const u64* noise, u32 s
 
 // ---- Corrected reconstruction over a prime below 2^256 (pvw_shamir.hip): the decode of 8.11 with elements of four
 // words.  Public workspace words, all times R = 2^256 (pvw_wide.h): x [count][4] | aux [count + 1][4] | lambda [count][4] |
-// V [count][r][4] | X [nk][count][4], nk = E + 1.  The syndromes are plain; the locators and M are times R.
+// V [count][r][4] | X [nk][count][4], nk = E + 1 (r + 1 with erasures, 8.21).  The syndromes are plain; the locators and M are
+// times R.
 inline size_t shamir_correct_wide_public_words(size_t count, u32 t, size_t nk) { return 4 * shamir_correct_public_words(count, t, nk); }
 #define PVW_SHAMIR_WIDE_MAX_LOCATOR 2048                 // E + 1 at most: two polynomials of one wave in 128 KiB of LDS
 struct ShamirMatmulWide {
@@ -454,8 +455,28 @@ hipError_t launch_shamir_correct_weights_wide(u64* ws, size_t count, u32 degree,
 hipError_t launch_shamir_matmul_wide(const ShamirMatmulWide& b, hipStream_t s);
 hipError_t launch_shamir_bm_wide(const u64* synd, u64* lam, u32* L, u32 ns, u32 r, const WideMont& m, hipStream_t s);
 hipError_t launch_shamir_correct_finish_wide(const ShamirFinishWide& f, u32 ns, hipStream_t s);
-// the dynamic-LDS limit of the wide Berlekamp-Massey kernel; once per context after hipSetDevice, beside init_kernel_attributes
+// the dynamic-LDS limits of the wide Berlekamp-Massey kernels; once per context after hipSetDevice, beside init_kernel_attributes
 hipError_t init_shamir_attributes();
+
+// ---- Reconstruction with erasures over a prime below 2^256 (pvw_shamir.hip): the decode of 8.16 with elements of
+// four words, in the forms of 8.20 (public operands times R, shares and syndromes plain).  erased[s][W] as above; the locator
+// capacity is nk = r + 1, so X has r + 1 rows and a row of psi r + 1 elements.
+struct ShamirMaskedMatmulWide : ShamirMatmulWide {
+  const u64* erased;     // [ns][ewords]: element (s, j) of A is not loaded and counts as 0 where bit j of row s is set
+  u32 ewords;
+};
+hipError_t launch_shamir_matmul_masked_wide(const ShamirMaskedMatmulWide& b, hipStream_t s);
+// synd [ns][r][4] is overwritten (the Forney syndromes take the place of a row's upper part); psi [ns][r + 1][4] reversed like
+// Lambda and times R, L [ns] = eps_s + deg Lambda_s or PVW_SHAMIR_NO_LOCATOR; x [count][4] the points times R.
+// r + 1 <= 2 PVW_SHAMIR_WIDE_MAX_LOCATOR: Gamma, C and B of one wave take at most r + 3 elements of LDS.
+hipError_t launch_shamir_bm_erasures_wide(u64* synd, const u64* erased, const u64* x, u64* psi, u32* L, u32 ns, u32 count, u32 r,
+                                          const WideMont& m, hipStream_t s);
+// f as for launch_shamir_correct_finish_wide with Lam = psi, E = r (rows r + 1 elements apart) and L from the kernel above
+hipError_t launch_shamir_erasures_finish_wide(const ShamirFinishWide& f, const u64* erased, u32 ns, hipStream_t s);
+// launch_shamir_erasure_mask with an OR over the num_limbs elements limb_stride apart that make one share
+hipError_t launch_shamir_wide_erasure_mask(const u32* status, const u64* noise, u32 status_bits, u64 noise_bound, u32 count, u32 ns,
+                                           size_t secret_stride, size_t point_stride, u32 num_limbs, size_t limb_stride, u64* mask,
+                                           hipStream_t s);
 
 // p[0 .. words) = 0, as a kernel launch on s
 hipError_t launch_wipe_words(u64* p, size_t words, hipStream_t s);

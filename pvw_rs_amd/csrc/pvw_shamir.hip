@@ -1309,8 +1309,12 @@ struct ShamirWideTile {
   size_t tm;
   bool live;
 };
+// MASKED: element (s, j) of A is staged as 0 where bit j of row s of `erased` is set -- the bit test stands beside
+// the load, so an erased element is not loaded.
+template <bool MASKED = false>
 __device__ __forceinline__ ShamirWideTile shamir_tile_product_wide(const u64* A, size_t secret_stride, size_t term_stride, const u64* W,
-                                                                   u32 ns, u32 nt, u32 T, const WideMont m) {
+                                                                   u32 ns, u32 nt, u32 T, const WideMont m, const u64* erased = nullptr,
+                                                                   u32 ewords = 0) {
   __shared__ u64 sh[SH_WAVES][SHW_TC][SHW_SG][4];  // 4 KiB: the chunk of A, below p
   __shared__ u64 part[SH_WAVES][SHW_SG][64][4];    // 32 KiB: the waves' partial sums, below p
   const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1336,7 +1340,7 @@ __device__ __forceinline__ ShamirWideTile shamir_tile_product_wide(const u64* A,
       const u32 off = c * SHW_TC + ej;             // within the wave's range
       const u32 j = ew * Q + off;
       u64 a[4] = {0, 0, 0, 0};
-      if (off < Q && j < nt && s0 + eg < ns) {
+      if (off < Q && j < nt && s0 + eg < ns && (!MASKED || !((erased[(size_t)(s0 + eg) * ewords + j / 64] >> (j % 64)) & 1))) {
         const u64* sp = A + ((size_t)(s0 + eg) * secret_stride + (size_t)j * term_stride) * 4;
         const u64 w[4] = {sp[0], sp[1], sp[2], sp[3]};
         wide_reduce_p(w, m, a);
@@ -1829,12 +1833,367 @@ hipError_t launch_shamir_matmul_wide(const ShamirMatmulWide& b, hipStream_t s) {
   }, s);
 }
 
+// ------------------------------------------------------------------------ erasures below 2^256
+// The decode of 8.16 with elements of four words, in the forms of 8.20: x, V, X, Gamma, the locators, Psi and M are times R; the
+// shares, the syndromes and the Forney syndromes are plain.
+//   Synd = (shares o !erased) x V                                                       (shamir_matmul_masked_wide_kernel)
+//   Gamma_s, T = Gamma_s Synd_s mod z^r in place, Berlekamp-Massey over T_eps .. T_{r-1} with the bound E_s = (r - eps_s) / 2,
+//   Psi_s = Gamma_s Lambda_s reversed, L_s = eps_s + deg Lambda_s                       (shamir_bm_erasures_wide_kernel)
+//   M = Psi x X with X [r+1][count]                                                      (shamir_matmul_wide_kernel)
+//   decodable iff row s of M has exactly L_s zeros; the zeros that are not erased are the wrong columns   (finish kernel)
+// The mask, Gamma, T and Psi are as public as the locators of 8.20.
+
+__global__ __launch_bounds__(256) void shamir_matmul_masked_wide_kernel(ShamirMaskedMatmulWide b) {
+  const ShamirWideTile o =
+      shamir_tile_product_wide<true>(b.A, b.secret_stride, b.term_stride, b.W, b.ns, b.terms, b.T, b.m, b.erased, b.ewords);
+  if (o.live) wide_st(b.out + ((size_t)o.s * b.T + o.tm) * 4, o.v);
+}
+
+// shamir_bm_erasures_kernel over four words: one wave (one workgroup) per secret.
+// Dynamic LDS: Gamma [eps + 1] | C [E_s + 1] | B [E_s + 1], at most r + 3 elements, each polynomial as four planes of words (word
+// k of coefficient i at plane k, slot i) so that the lanes of one access touch consecutive words, as in shamir_bm_wide_kernel.
+// Gamma grows by one factor (1 - x_c z) per set bit of the row's mask words, walked downwards in blocks of 64; it is kept times
+// R: Gamma_i R <- Gamma_i R - REDC((x_c R)(Gamma_{i-1} R)) with x_c R from the points buffer, both operands below p.
+// T takes the place of Synd_s[eps ..] in global memory, blocks downwards: T_n = sum_{i <= eps} Gamma_i S_{n-i} reads
+// Synd_s[n - eps .. n], which no earlier (higher) block has written, and the block's own stores wait behind a barrier for its
+// loads.  A term is wide_mul_full of (Gamma_i R) < p and the plain S_{n-i} < p (a tile product's output, wide_add_p's result),
+// so every product is below p p < p R and wide_acc_add's invariant (accumulator and addend below p R) holds term by term
+// however large eps is; ONE wide_redc then gives the plain T_n < p.
+// Then the recurrence of shamir_bm_wide_kernel on T_eps .. T_{r-1} with the bound E_s, its invariants word for word: C, B and b
+// times R, T plain.  Psi_j = sum_i Lambda_i Gamma_{j-i}, a lane per coefficient: a term is wide_mul_full of (Lambda_i R) < p and
+// (Gamma_{j-i} R) < p, below p p again, and one wide_redc leaves Psi_j R.
+// Every branch that holds a barrier is wave-uniform: the mask words are read by all lanes alike and the discrepancy is the same
+// in every lane; only the tail of a block (a lane past the last coefficient) is predicated, between the barriers.
+// Out: psi[s][k] = Psi_{L_s - k} R for k <= L_s, 0 up to r (all 0 for an undecodable row: eps_s > r or deg Lambda_s > E_s),
+// Lout[s] = L_s or PVW_SHAMIR_NO_LOCATOR.
+__global__ __launch_bounds__(64) void shamir_bm_erasures_wide_kernel(u64* synd, const u64* erased, const u64* x, u64* psi, u32* Lout,
+                                                                     u32 count, u32 r, WideMont m) {
+  extern __shared__ u64 bmew_lds[];
+  const u32 lane = threadIdx.x;
+  const size_t s = blockIdx.x;
+  const u32 words = (count + 63) / 64;
+  const u64* erow = erased + s * words;
+  u64* S = synd + s * r * 4;
+  u64* row = psi + s * ((size_t)r + 1) * 4;
+  u32 eps = 0;
+  for (u32 w = 0; w < words; ++w) eps += (u32)__popcll(shamir_erased_word(erow, w, count));
+  if (eps > r) {
+    const u64 z[4] = {0, 0, 0, 0};
+    for (u32 k = lane; k <= r; k += 64) wide_st(row + (size_t)k * 4, z);
+    if (lane == 0) Lout[s] = PVW_SHAMIR_NO_LOCATOR;
+    return;
+  }
+  const u32 nG = eps + 1;
+  u64* G = bmew_lds;
+  for (u32 i = lane; i <= eps; i += 64)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) G[k * nG + i] = i == 0 ? m.one[k] : 0;
+  __syncthreads();
+  u32 g = 0;                                                       // deg Gamma so far
+  for (u32 w = 0; w < words; ++w) {
+    u64 word = shamir_erased_word(erow, w, count);
+    while (word) {
+      u64 xc[4];
+      wide_ld(x + (size_t)(w * 64 + (u32)__builtin_ctzll(word)) * 4, xc);
+      word &= word - 1;
+      for (u32 k = (g + 1) / 64 + 1; k-- > 0;) {                   // Gamma_i <- Gamma_i - x_c Gamma_{i-1}, i <= g + 1
+        const u32 i = k * 64 + lane;
+        const bool in = i <= g + 1;
+        u64 cur[4] = {0, 0, 0, 0}, prev[4] = {0, 0, 0, 0};
+        if (in && i <= g) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) cur[q] = G[q * nG + i];
+        }
+        if (in && i >= 1) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) prev[q] = G[q * nG + i - 1];
+        }
+        __syncthreads();
+        if (in) {
+          u64 t[4];
+          wide_mont_mul(xc, prev, m, t);
+          wide_sub_p(cur, t, m);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) G[q * nG + i] = cur[q];
+        }
+        __syncthreads();
+      }
+      ++g;
+    }
+  }
+  const u32 nT = r - eps, E = nT / 2, nE = E + 1;
+  if (eps)
+    for (u32 k = (nT + 63) / 64; k-- > 0;) {
+      const u32 idx = k * 64 + lane, n = eps + idx;
+      const bool live = idx < nT;
+      u32 acc[16];
+      wide_acc_zero(acc);
+      if (live)
+        for (u32 i = 0; i <= eps; ++i) {
+          u64 gi[4], sv[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) gi[q] = G[q * nG + i];
+          wide_ld(S + (size_t)(n - i) * 4, sv);
+          u32 P[16];
+          wide_mul_full(gi, sv, P);
+          wide_acc_add(acc, P, m);
+        }
+      u64 v[4];
+      wide_redc(acc, m, v);
+      __syncthreads();
+      if (live) wide_st(S + (size_t)n * 4, v);
+      __syncthreads();
+    }
+  const u64* T = S + (size_t)eps * 4;
+  u64 *C = G + (size_t)4 * nG, *B = C + (size_t)4 * nE;
+  for (u32 i = lane; i <= E; i += 64)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) C[k * nE + i] = B[k * nE + i] = i == 0 ? m.one[k] : 0;
+  __syncthreads();
+  u32 L = 0, mm = 1;
+  u64 bsc[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) bsc[k] = m.one[k];
+  bool ok = true;
+  for (u32 n = 0; n < nT; ++n) {
+    u32 acc[16];
+    wide_acc_zero(acc);
+    for (u32 i = lane; i <= L; i += 64) {          // L <= n
+      u64 c[4], sv[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) c[k] = C[k * nE + i];
+      wide_ld(T + (size_t)(n - i) * 4, sv);
+      u32 P[16];
+      wide_mul_full(c, sv, P);
+      wide_acc_add(acc, P, m);
+    }
+    u64 d[4];
+    wide_redc(acc, m, d);
+    wave_add_wide(d, m);
+    if (wide_zero(d)) { ++mm; continue; }
+    const bool grow = 2 * L <= n;
+    const u32 Ln = grow ? n + 1 - L : L;
+    if (Ln > E) { ok = false; break; }
+    wide_mont_in(d, m, d);
+    for (u32 k = Ln / 64 + 1; k-- > 0;) {
+      const u32 i = k * 64 + lane;
+      const bool in = i <= Ln;
+      u64 c[4] = {0, 0, 0, 0}, bb[4] = {0, 0, 0, 0};
+      if (in) {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) c[w] = C[w * nE + i];
+        if (i >= mm) {
+#pragma unroll
+          for (int w = 0; w < 4; ++w) bb[w] = B[w * nE + i - mm];
+        }
+      }
+      __syncthreads();
+      if (in) {
+        u64 v[4], t[4];
+        wide_mont_mul(bsc, c, m, v);
+        wide_mont_mul(d, bb, m, t);
+        wide_sub_p(v, t, m);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) C[w * nE + i] = v[w];
+        if (grow) {
+#pragma unroll
+          for (int w = 0; w < 4; ++w) B[w * nE + i] = c[w];
+        }
+      }
+      __syncthreads();
+    }
+    if (grow) {
+      L = Ln;
+      mm = 1;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) bsc[k] = d[k];
+    } else {
+      ++mm;
+    }
+  }
+  // Psi_j = sum_i Lambda_i Gamma_{j-i}, stored at k = L_s - j
+  const u32 Ls = eps + L;
+  for (u32 k = lane; k <= r; k += 64) {
+    u64 v[4] = {0, 0, 0, 0};
+    if (ok && k <= Ls) {
+      const u32 j = Ls - k;
+      u32 acc[16];
+      wide_acc_zero(acc);
+      for (u32 i = j > eps ? j - eps : 0; i <= L && i <= j; ++i) {
+        u64 ci[4], gj[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          ci[q] = C[q * nE + i];
+          gj[q] = G[q * nG + j - i];
+        }
+        u32 P[16];
+        wide_mul_full(ci, gj, P);
+        wide_acc_add(acc, P, m);
+      }
+      wide_redc(acc, m, v);
+    }
+    wide_st(row + (size_t)k * 4, v);
+  }
+  if (lane == 0) Lout[s] = ok ? Ls : PVW_SHAMIR_NO_LOCATOR;
+}
+
+// shamir_correct_finish_wide_kernel for a row with erasures: the zeros of M's row must number exactly L_s, the erased ones among
+// them; the mask word is the ballot of the zeros without the erased word, nerr = L_s - eps_s, and out[s] divides by
+// Psi_s(0) = f.Lam[s][0] (rows f.E + 1 = r + 1 elements apart).  No share at a zero column is read: M is 0 at every erased one.
+__global__ __launch_bounds__(64) void shamir_erasures_finish_wide_kernel(ShamirFinishWide f, const u64* erased) {
+  const u32 lane = threadIdx.x;
+  const size_t s = blockIdx.x;
+  WideMont m = f.m;                                // r2 and one in vector registers, as in shamir_correct_finish_wide_kernel
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    m.r2[k] = wide_in_vgpr(m.r2[k]);
+    m.one[k] = wide_in_vgpr(m.one[k]);
+  }
+  const u32 count = f.count, words = (count + 63) / 64;
+  const u32 L = f.L[s];
+  const u64* Mrow = f.M + s * count * 4;
+  const u64* erow = erased + s * words;
+  bool decodable = L != PVW_SHAMIR_NO_LOCATOR;
+  u32 eps = 0;
+  if (decodable) {
+    u32 nz = 0;
+    for (u32 c0 = 0; c0 < count; c0 += 64) {
+      const u32 c = c0 + lane;
+      u64 mv[4] = {1, 0, 0, 0};
+      if (c < count) wide_ld(Mrow + (size_t)c * 4, mv);
+      nz += (u32)__popcll(__ballot(wide_zero(mv)));
+      eps += (u32)__popcll(shamir_erased_word(erow, c0 / 64, count));
+    }
+    decodable = nz == L;
+  }
+  if (!decodable) {
+    if (f.mask)
+      for (u32 w = lane; w < words; w += 64) f.mask[s * words + w] = 0;
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) f.out[s * 4 + k] = 0;
+      if (f.nerr) f.nerr[s] = PVW_SHAMIR_NO_LOCATOR;
+    }
+    return;
+  }
+  u32 acc[16];
+  wide_acc_zero(acc);
+  for (u32 c0 = 0; c0 < count; c0 += 64) {
+    const u32 c = c0 + lane;
+    const bool live = c < count;
+    u64 mv[4] = {1, 0, 0, 0};
+    if (live) wide_ld(Mrow + (size_t)c * 4, mv);
+    const bool zero = wide_zero(mv);
+    const u64 bal = __ballot(zero) & ~shamir_erased_word(erow, c0 / 64, count);
+    const bool wrong = (bal >> lane) & 1;
+    if (lane == 0 && f.mask) f.mask[s * words + c0 / 64] = bal;
+    if (wrong && f.col_err) atomicAdd(&f.col_err[c], 1u);
+    if (live && !zero) {
+      const u64* sp = f.shares + (s * f.secret_stride + (size_t)c * f.point_stride) * 4;
+      const u64 w[4] = {sp[0], sp[1], sp[2], sp[3]};
+      u64 y[4], lw[4];
+      wide_reduce_p(w, m, y);
+      wide_ld(f.lam + (size_t)c * 4, lw);
+      wide_mont_mul(lw, mv, m, lw);
+      u32 P[16];
+      wide_mul_full(y, lw, P);
+      wide_acc_add(acc, P, m);
+    }
+  }
+  u64 v[4];
+  wide_redc(acc, m, v);
+  wave_add_wide(v, m);
+  if (lane == 0) {
+    u64 l0[4];
+    wide_ld(f.Lam + s * (f.E + 1) * 4, l0);
+    wide_mont_inv(l0, m, l0);
+    wide_mont_mul(v, l0, m, v);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) f.out[s * 4 + k] = v[k];
+    if (f.nerr) f.nerr[s] = L - eps;
+  }
+}
+
+// The frame of shamir_erasure_mask_kernel with an inner OR over the num_limbs elements of a share, limb_stride apart: a share is
+// erased as soon as one of its limbs is flagged.
+__global__ __launch_bounds__(64) void shamir_wide_erasure_mask_kernel(const u32* status, const u64* noise, u32 status_bits,
+                                                                      u64 noise_bound, u32 count, u32 wb, size_t secret_stride,
+                                                                      size_t point_stride, u32 num_limbs, size_t limb_stride, u64* mask) {
+  const u32 lane = threadIdx.x;
+  const size_t s = blockIdx.x / wb;
+  const u32 words = (count + 63) / 64, w0 = (blockIdx.x % wb) * 64;
+  const u32 nw = words - w0 < 64 ? words - w0 : 64;
+  u64 mine = 0;
+  for (u32 k = 0; k < nw; ++k) {
+    const u32 c = (w0 + k) * 64 + lane;
+    bool e = false;
+    if (c < count) {
+      const size_t base = s * secret_stride + (size_t)c * point_stride;
+      for (u32 w = 0; w < num_limbs; ++w) {
+        const size_t off = base + (size_t)w * limb_stride;
+        if (status) e = e || (status[off] & status_bits) != 0;
+        if (noise) e = e || noise[off] > noise_bound;
+      }
+    }
+    const u64 bal = __ballot(e);
+    if (lane == k) mine = bal;
+  }
+  if (lane < nw) mask[s * words + w0 + lane] = mine;
+}
+
+hipError_t launch_shamir_matmul_masked_wide(const ShamirMaskedMatmulWide& b, hipStream_t s) {
+  return launch_secret_groups(shamir_matmul_masked_wide_kernel, b, [&](u32 s0) {
+    ShamirMaskedMatmulWide p = b;
+    p.A += (size_t)s0 * b.secret_stride * 4;
+    p.out += (size_t)s0 * b.T * 4;
+    p.erased += (size_t)s0 * b.ewords;
+    return p;
+  }, s);
+}
+
+// r <= 2 PVW_SHAMIR_WIDE_MAX_LOCATOR - 1: Gamma, C and B of one wave take at most r + 3 elements of 32 bytes, 131 136 bytes at
+// r = 4095 of the 160 KiB a gfx950 workgroup may take; the limit is raised in init_shamir_attributes, each launch asks for
+// what its r takes.
+hipError_t launch_shamir_bm_erasures_wide(u64* synd, const u64* erased, const u64* x, u64* psi, u32* L, u32 ns, u32 count, u32 r,
+                                          const WideMont& m, hipStream_t s) {
+  if (ns == 0) return hipSuccess;
+  shamir_bm_erasures_wide_kernel<<<dim3(ns), dim3(64), ((size_t)r + 3) * 32, s>>>(synd, erased, x, psi, L, count, r, m);
+  return hipGetLastError();
+}
+
+hipError_t launch_shamir_erasures_finish_wide(const ShamirFinishWide& f, const u64* erased, u32 ns, hipStream_t s) {
+  if (ns == 0) return hipSuccess;
+  shamir_erasures_finish_wide_kernel<<<dim3(ns), dim3(64), 0, s>>>(f, erased);
+  return hipGetLastError();
+}
+
+hipError_t launch_shamir_wide_erasure_mask(const u32* status, const u64* noise, u32 status_bits, u64 noise_bound, u32 count, u32 ns,
+                                           size_t secret_stride, size_t point_stride, u32 num_limbs, size_t limb_stride, u64* mask,
+                                           hipStream_t s) {
+  if (ns == 0 || count == 0) return hipSuccess;
+  const u32 words = (count + 63) / 64, wb = (words + 63) / 64;
+  const u32 per = 0x7FFFFFFFu / wb;                                // rows per launch: what the grid's x dimension holds
+  for (u32 s0 = 0; s0 < ns; s0 += per) {
+    const u32 rows = ns - s0 < per ? ns - s0 : per;
+    shamir_wide_erasure_mask_kernel<<<dim3(rows * wb), dim3(64), 0, s>>>(
+        status ? status + (size_t)s0 * secret_stride : nullptr, noise ? noise + (size_t)s0 * secret_stride : nullptr, status_bits,
+        noise_bound, count, wb, secret_stride, point_stride, num_limbs, limb_stride, mask + (size_t)s0 * words);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 // E + 1 <= PVW_SHAMIR_WIDE_MAX_LOCATOR: C and B of one wave take 2 (E + 1) 32 bytes, up to 128 KiB of the 160 KiB a gfx950 CU has.
 // That is more than the 64 KiB a launch gets without asking: the limit is raised once per device (init_shamir_attributes), and
 // each launch asks for what its E takes.
+// The kernel of 8.21 keeps Gamma, C and B: at most r + 3 elements with r <= 2 PVW_SHAMIR_WIDE_MAX_LOCATOR - 1 = 4095, 131 136 bytes.
 hipError_t init_shamir_attributes() {
-  return hipFuncSetAttribute((const void*)shamir_bm_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             2 * PVW_SHAMIR_WIDE_MAX_LOCATOR * 32);
+  hipError_t e = hipFuncSetAttribute((const void*)shamir_bm_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     2 * PVW_SHAMIR_WIDE_MAX_LOCATOR * 32);
+  if (e != hipSuccess) return e;
+  return hipFuncSetAttribute((const void*)shamir_bm_erasures_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (2 * PVW_SHAMIR_WIDE_MAX_LOCATOR - 1 + 3) * 32);
 }
 hipError_t launch_shamir_bm_wide(const u64* synd, u64* lam, u32* L, u32 ns, u32 r, const WideMont& m, hipStream_t s) {
   if (ns == 0) return hipSuccess;

@@ -846,6 +846,46 @@ inline CorrectedWideSecrets shamir_reconstruct_wide_corrected(const std::shared_
                                                      r.secrets.data(), r.nerr.data(), r.col_err.data(), r.err_mask.data()));
   return r;
 }
+// ---- reconstruction with erasures over an odd prime below 2^256 ----
+// The call above with `erased` [num_secrets][words] in the layout of CorrectedWideSecrets::err_mask (bit c % 64 of word c / 64 of
+// row s: share (s, c) is known to be bad).  An erased share costs one redundant column instead of two: a row decodes while
+// 2 errors + erasures <= indices.size() - degree - 1; the words at an erased position influence nothing and an erased column is
+// never reported as an error.  An empty `erased` is the call above.
+inline CorrectedWideSecrets shamir_reconstruct_wide_corrected(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& indices,
+                                                              const std::vector<uint64_t>& shares, uint32_t degree, const Wide& plain_modulus,
+                                                              const std::vector<uint64_t>& erased, bool party_major, bool host = false) {
+  const size_t count = indices.size();
+  if (count == 0 || shares.empty() || shares.size() % (count * PVW_WIDE_WORDS)) throw PvwError(15, "shares must hold one element per index and secret");
+  const size_t S = shares.size() / (count * PVW_WIDE_WORDS), ss = party_major ? 1 : count, ps = party_major ? S : 1;
+  const size_t words = (count + 63) / 64;
+  if (!erased.empty() && erased.size() != S * words) throw PvwError(15, "erased must hold ceil(count / 64) words per secret");
+  const uint64_t* er = erased.empty() ? nullptr : erased.data();
+  CorrectedWideSecrets r{std::vector<uint64_t>(S * PVW_WIDE_WORDS), std::vector<uint32_t>(S), std::vector<uint32_t>(count),
+                         std::vector<uint64_t>(S * words), words};
+  check(host ? pvw_shamir_reconstruct_wide_erasures_host(plain_modulus.data(), degree, indices.data(), count, shares.data(), S, ss, ps, er,
+                                                         r.secrets.data(), r.nerr.data(), r.col_err.data(), r.err_mask.data())
+             : pvw_shamir_reconstruct_wide_erasures(p->ctx, plain_modulus.data(), degree, indices.data(), count, shares.data(), S, ss, ps,
+                                                    er, r.secrets.data(), r.nerr.data(), r.col_err.data(), r.err_mask.data()));
+  return r;
+}
+// The mask of wide shares from a per-limb decrypt report on the host (pvw_shamir_wide_erasure_mask_host): status / noise
+// [num_secrets][count * num_limbs], or with party_major [count][num_secrets * num_limbs] (the [party][dealer NL + w] report of the
+// decrypt-all calls); either may be empty, not both.  Share (s, c) is erased iff one of its limbs has status & status_bits or
+// noise > noise_bound.
+inline std::vector<uint64_t> shamir_wide_erasure_mask(const std::vector<uint32_t>& status, const std::vector<uint64_t>& noise, size_t count,
+                                                      uint32_t num_limbs, uint32_t status_bits, uint64_t noise_bound,
+                                                      bool party_major = false) {
+  const size_t cells = status.empty() ? noise.size() : status.size();
+  if (count == 0 || num_limbs == 0 || cells == 0 || cells % (count * num_limbs) ||
+      (!status.empty() && !noise.empty() && status.size() != noise.size()))
+    throw PvwError(15, "status and noise must hold num_limbs values per share");
+  const size_t S = cells / (count * num_limbs), NL = num_limbs;
+  std::vector<uint64_t> mask(S * ((count + 63) / 64));
+  check(pvw_shamir_wide_erasure_mask_host(status.empty() ? nullptr : const_cast<uint32_t*>(status.data()) /* only read */,
+                                          noise.empty() ? nullptr : noise.data(), status_bits, noise_bound, count, S,
+                                          party_major ? NL : count * NL, party_major ? S * NL : NL, num_limbs, 1, mask.data()));
+  return mask;
+}
 // the share matrix of the checked, corrected and evaluate calls: its shape and the strides of its layout, in words
 struct ShareMatrix {
   size_t count, S, words, ss, ps;   // columns, secrets, mask words per secret, secret stride, point stride

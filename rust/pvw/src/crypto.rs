@@ -740,6 +740,55 @@ pub fn shamir_reconstruct_wide_corrected(params: &Arc<PvwParameters>, indices: &
     Ok(r)
 }
 
+/// EXTENSION: `shamir_reconstruct_wide_corrected` with the shares KNOWN to be bad flagged in `erased` (bit `c % 64`
+/// of word `c / 64` of row `s`; an earlier call's `err_mask`, or `shamir_wide_erasure_mask`).  Each costs one redundant column
+/// instead of two: a row decodes while `2 * errors + erasures <= indices.len() - degree - 1`.  The words at an erased position
+/// influence nothing and an erased column is never reported as an error (`pvw_shamir_reconstruct_wide_erasures`).
+pub fn shamir_reconstruct_wide_erasures(params: &Arc<PvwParameters>, indices: &[u64], shares: &[Wide], degree: u32, plain_modulus: &Wide,
+                                        erased: &[u64], party_major: bool) -> Result<CorrectedWideSecrets> {
+    if indices.is_empty() || shares.is_empty() || shares.len() % indices.len() != 0 {
+        return Err(PvwError::InvalidParameters("shares must hold one element per index and secret".into()));
+    }
+    let (count, num) = (indices.len(), shares.len() / indices.len());
+    let (ss, ps) = if party_major { (1, num) } else { (count, 1) };
+    let words = (count + 63) / 64;
+    if erased.len() != num * words {
+        return Err(PvwError::InvalidParameters("erased must hold ceil(count / 64) words per secret".into()));
+    }
+    let mut r = CorrectedWideSecrets { secrets: vec![[0u64; 4]; num], nerr: vec![0u32; num], col_err: vec![0u32; count],
+                                       err_mask: vec![0u64; num * words], words };
+    check(unsafe {
+        sys::pvw_shamir_reconstruct_wide_erasures(params.hip.raw(), plain_modulus.as_ptr(), degree, indices.as_ptr(), count,
+                                                  shares.as_ptr() as *const u64, num, ss, ps, erased.as_ptr(),
+                                                  r.secrets.as_mut_ptr() as *mut u64, r.nerr.as_mut_ptr(), r.col_err.as_mut_ptr(),
+                                                  r.err_mask.as_mut_ptr())
+    })?;
+    Ok(r)
+}
+
+/// EXTENSION: the erasure mask of wide shares from a per-limb decrypt report, on the host
+/// (`pvw_shamir_wide_erasure_mask_host`).  `status` and `noise` are `[num_secrets][count * num_limbs]`, or with `party_major`
+/// `[count][num_secrets * num_limbs]` (the `[party][dealer * NL + w]` report of the decrypt-all calls, every dealer a secret);
+/// either may be empty, not both.  Share `(s, c)` is erased iff one of its limbs has `status & status_bits != 0` or
+/// `noise > noise_bound`.
+pub fn shamir_wide_erasure_mask(status: &[u32], noise: &[u64], count: usize, num_limbs: u32, status_bits: u32, noise_bound: u64,
+                                party_major: bool) -> Result<Vec<u64>> {
+    let cells = if status.is_empty() { noise.len() } else { status.len() };
+    let nl = num_limbs as usize;
+    if count == 0 || nl == 0 || cells == 0 || cells % (count * nl) != 0 || (!status.is_empty() && !noise.is_empty() && status.len() != noise.len()) {
+        return Err(PvwError::InvalidParameters("status and noise must hold num_limbs values per share".into()));
+    }
+    let num = cells / (count * nl);
+    let (ss, ps) = if party_major { (nl, num * nl) } else { (count * nl, nl) };
+    let mut mask = vec![0u64; num * ((count + 63) / 64)];
+    check(unsafe {
+        sys::pvw_shamir_wide_erasure_mask_host(if status.is_empty() { std::ptr::null_mut() } else { status.as_ptr() as *mut u32 },   // only read
+                                               if noise.is_empty() { std::ptr::null() } else { noise.as_ptr() }, status_bits, noise_bound,
+                                               count, num, ss, ps, num_limbs, 1, mask.as_mut_ptr())
+    })?;
+    Ok(mask)
+}
+
 /// EXTENSION: `shamir_wide_from_limbs` where the limbs lie (`pvw_shamir_wide_from_limbs_device`): device
 /// pointers, `count` elements of `[count][4]` words written at `d_out`, asynchronous on `stream` (null: the context's).
 /// Strides `(count, 1)` read limb planes, `(1, num_limbs)` the `[party][dealer * NL + w]` result of a decrypt-all in place.
