@@ -40,7 +40,8 @@
  *     this family, a context's very first calls and a count whose launch needs the raised LDS limit among them:
  *     tests/test_gpu_shamir_wide_concurrent.py), pvw_shamir_reconstruct_wide_erasures and, on the calling thread's stream,
  *     pvw_shamir_reconstruct_wide_erasures_device / pvw_shamir_wide_erasure_mask_device (the concurrent calls of these:
- *     tests/test_gpu_shamir_wide_erasures.py),
+ *     tests/test_gpu_shamir_wide_erasures.py), pvw_shamir_evaluate_wide_corrected, pvw_shamir_evaluate_wide_erasures and, on
+ *     the calling thread's stream, their _device forms (the concurrent calls of these: tests/test_gpu_shamir_wide_evaluate.py),
  *     pvw_decrypt_batch / _checked / _plain, pvw_decrypt_all / _checked / _plain, pvw_ct_sum, pvw_decrypt_sum_checked,
  *     pvw_decrypt_all_sum_checked, pvw_ct_lincomb, pvw_decrypt_lincomb_plain, pvw_decrypt_all_lincomb_plain (the concurrent
  *     calls of these three: tests/test_gpu_ct_lincomb.py), pvw_ct_lincomb_many, pvw_decrypt_all_lincomb_many_plain (the concurrent
@@ -1185,6 +1186,66 @@ PVW_API int32_t pvw_shamir_reconstruct_wide_erasures(pvw_ctx* ctx, const uint64_
                                                      size_t num_secrets, size_t secret_stride, size_t point_stride,
                                                      const uint64_t* erased, uint64_t* out, uint32_t* nerr, uint32_t* col_err,
                                                      uint64_t* err_mask);
+/* Share repair over a prime field of up to 256 bits: the contract of pvw_shamir_evaluate_corrected* (8.13) and
+ * pvw_shamir_evaluate_erasures* (8.16) with wide elements.  The arguments of the matching pvw_shamir_reconstruct_wide_corrected* /
+ * _wide_erasures* form in its order (erased directly behind point_stride), then targets, num_targets and values, then the four
+ * outputs out, nerr, col_err, err_mask, and stream in the _device form.
+ *   targets [num_targets]: a HOST array of global party indices in every form, like indices; the point of target j is the integer
+ *   targets[j] + 1, which must be below p (a target of 2^64 - 1 is legal when p > 2^64 + 1, as for indices).
+ *   values [num_secrets][num_targets][4], dense and row-major, may not be NULL; out may be NULL here.
+ *   Decodability, F_s, out, nerr, col_err and err_mask are those of the wide corrected call without a mask and of the wide
+ *   erasures call with one, bit for bit: one decode yields every report.
+ *   decodable row:   values[s][j] = F_s(targets[j] + 1) mod p, fully reduced, four words.
+ *   undecodable row: its row of values is 0 (eps_s > r, too many errors, a root of the error locator on an erased point).
+ *   A target may be one of the indices: at a column the decode found right the value is the share read mod p, at a wrong or an
+ *   erased column the share that party should hold.  The words at an erased position influence nothing, 2^256 - 1 included.
+ *   Duplicates are allowed; the order of the targets only permutes the columns of values; the order of the share columns changes
+ *   no value; r = 0 is plain interpolation through all columns.  The three forms agree bit for bit on every input, small-p rows
+ *   that decode to a polynomial nobody dealt included.  erased == NULL is the wide evaluate-corrected call bit for bit: behind
+ *   the argument checks it IS that call.
+ * PVW_ERR_INVALID_PARAMETERS before any device work, nothing written: what the matching wide corrected / erasures form refuses,
+ * with its texts and in its order (the device forms' bound included, unchanged: r >= 4096 is refused); then NULL targets or
+ * values, num_targets = 0, a target whose point is not below p; on the device num_targets >= 2^31, checked before the targets
+ * are walked.  No new status code and no new LDS bound: the evaluation needs no LDS beyond the tile product's.
+ * Under stream capture: an earlier call of this kind on that stream outside capture with the same (degree, count), at least as
+ * many targets and at least as many secrets, and with a mask if this one has a mask; otherwise the call fails with its own error
+ * and enqueues nothing.  The host-buffer forms stage through the wide corrected call's staging (the mask rows of a piece with its
+ * shares), are synchronous and are covered by the concurrency promise above.  Cleared behind the last launch: M, y o M, the
+ * unscaled sums and the stand-in for out, and in the host-buffer form the staged shares, out and values; the public matrices, the
+ * syndromes, the locators and their values at the public targets are not secret. */
+/* the contract in plain C++ on the host cores: the Berlekamp-Welch routine of pvw_shamir_reconstruct_wide_corrected_host (on the
+ * compacted sub-row with a mask) holds F_s as coefficients and evaluates them by Horner's rule at every target */
+PVW_API int32_t pvw_shamir_evaluate_wide_corrected_host(const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                        size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
+                                                        size_t point_stride, const uint64_t* targets, size_t num_targets,
+                                                        uint64_t* values, uint64_t* out, uint32_t* nerr, uint32_t* col_err,
+                                                        uint64_t* err_mask);
+PVW_API int32_t pvw_shamir_evaluate_wide_corrected_device(pvw_ctx* ctx, const uint64_t* plain_modulus, uint32_t degree,
+                                                          const uint64_t* indices, size_t count, const uint64_t* d_shares,
+                                                          size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                                          const uint64_t* targets, size_t num_targets, uint64_t* d_values,
+                                                          uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err, uint64_t* d_err_mask,
+                                                          void* stream);
+PVW_API int32_t pvw_shamir_evaluate_wide_corrected(pvw_ctx* ctx, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                   size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
+                                                   size_t point_stride, const uint64_t* targets, size_t num_targets, uint64_t* values,
+                                                   uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask);
+PVW_API int32_t pvw_shamir_evaluate_wide_erasures_host(const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                       size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
+                                                       size_t point_stride, const uint64_t* erased, const uint64_t* targets,
+                                                       size_t num_targets, uint64_t* values, uint64_t* out, uint32_t* nerr,
+                                                       uint32_t* col_err, uint64_t* err_mask);
+PVW_API int32_t pvw_shamir_evaluate_wide_erasures_device(pvw_ctx* ctx, const uint64_t* plain_modulus, uint32_t degree,
+                                                         const uint64_t* indices, size_t count, const uint64_t* d_shares,
+                                                         size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                                         const uint64_t* d_erased, const uint64_t* targets, size_t num_targets,
+                                                         uint64_t* d_values, uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err,
+                                                         uint64_t* d_err_mask, void* stream);
+PVW_API int32_t pvw_shamir_evaluate_wide_erasures(pvw_ctx* ctx, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                  size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
+                                                  size_t point_stride, const uint64_t* erased, const uint64_t* targets,
+                                                  size_t num_targets, uint64_t* values, uint64_t* out, uint32_t* nerr, uint32_t* col_err,
+                                                  uint64_t* err_mask);
 /* The mask of wide shares from a per-limb decrypt report: the arguments of pvw_shamir_erasure_mask_* plus num_limbs and
  * limb_stride.  Bit (s, c) of mask_out [num_secrets][W] is set iff, for some w < num_limbs, the element at
  * s * secret_stride + c * point_stride + w * limb_stride has status & status_bits non-zero or noise > noise_bound.  Either array

@@ -183,6 +183,19 @@ _SIGNATURES = {
                                                     _P, _P, _P],
     "pvw_shamir_reconstruct_wide_erasures": [_P, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P, _P,
                                              _P],
+    # wide share repair: the wide corrected / erasures arguments, then targets, num_targets, values and the four outputs
+    "pvw_shamir_evaluate_wide_corrected_host": [_P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P,
+                                                _P, _P, _P, _P],
+    "pvw_shamir_evaluate_wide_corrected_device": [_P, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P,
+                                                  C.c_size_t, _P, _P, _P, _P, _P, _P],
+    "pvw_shamir_evaluate_wide_corrected": [_P, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P,
+                                           _P, _P, _P, _P],
+    "pvw_shamir_evaluate_wide_erasures_host": [_P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, C.c_size_t,
+                                               _P, _P, _P, _P, _P],
+    "pvw_shamir_evaluate_wide_erasures_device": [_P, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P,
+                                                 C.c_size_t, _P, _P, _P, _P, _P, _P],
+    "pvw_shamir_evaluate_wide_erasures": [_P, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, C.c_size_t,
+                                          _P, _P, _P, _P, _P],
     "pvw_shamir_wide_erasure_mask_host": [_P, _P, C.c_uint32, C.c_uint64, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32,
                                           C.c_size_t, _P],
     "pvw_shamir_wide_erasure_mask_device": [_P, _P, _P, C.c_uint32, C.c_uint64, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,

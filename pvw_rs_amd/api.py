@@ -1133,6 +1133,36 @@ def shamir_reconstruct_wide_corrected(params: Optional[PvwParameters], indices: 
     return _wide_ints(out), nerr, col_err, err_mask
 
 
+def shamir_evaluate_wide_corrected(params: Optional[PvwParameters], indices: Sequence[int], shares, degree: int, plain_modulus: int,
+                                   targets: Sequence[int], *, host: bool = False, layout: str = "secret_major",
+                                   erased=None) -> Tuple[List[List[int]], List[int], np.ndarray, np.ndarray, np.ndarray]:
+    """EXTENSION: share repair over an odd prime plain_modulus < 2^256.  The decode of
+    shamir_reconstruct_wide_corrected, and values[s][j] = the value of secret s's corrected polynomial at the point of party
+    targets[j] (a global index below 2^64 whose point targets[j] + 1 is below plain_modulus: one of `indices` -- the share that
+    party should hold -- or any other; duplicates allowed).  The row of an undecodable secret is 0.  shares and layout as
+    shamir_reconstruct_wide_checked.  On the device (pvw_shamir_evaluate_wide_corrected); host=True: the plain C++ restatement
+    (pvw_shamir_evaluate_wide_corrected_host, no GPU; params may be None).  Returns (values as ints [S][T], secrets as ints, nerr,
+    col_err, err_mask).
+    erased as shamir_reconstruct_wide_corrected (pvw_shamir_evaluate_wide_erasures*): at an erased column the value
+    is the share that party should hold, which is the repair of a party that lost its state."""
+    idx, sh, S, count, strides = _wide_share_matrix(indices, shares, layout)
+    tg = _words(targets)
+    T = len(tg)
+    values = np.zeros((S, T, WIDE_WORDS), dtype=np.uint64)
+    out = np.zeros((S, WIDE_WORDS), dtype=np.uint64)
+    nerr, col_err = np.zeros(S, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
+    err_mask = np.zeros((S, (count + 63) // 64), dtype=np.uint64)
+    head = (_ptr(_wide_modulus(plain_modulus)), int(degree), _ptr(idx), count, _ptr(sh), S, strides[0], strides[1])
+    tail = (_ptr(tg), T, _ptr(values), _ptr(out), _ptr(nerr), _ptr(col_err), _ptr(err_mask))
+    if erased is None:
+        _reconstruct_call(params, "shamir_evaluate_wide_corrected", host, head + tail)
+    else:
+        er = _erased_words(erased, S, count, layout)
+        _reconstruct_call(params, "shamir_evaluate_wide_erasures", host, head + (_ptr(er),) + tail)
+    flat = _wide_ints(values.reshape(S * T, WIDE_WORDS)) if T else []
+    return [flat[s * T:(s + 1) * T] for s in range(S)], _wide_ints(out), nerr, col_err, err_mask
+
+
 def _share_matrix(indices: Sequence[int], shares, layout: str):
     """(idx, sh, S, count, strides) of the checked, corrected and evaluate calls: the indices and the share matrix as uint64
     words, and the (secret, point) strides of `layout` in words"""

@@ -4475,8 +4475,11 @@ static inline u64 (&wel(std::vector<u64>& v, size_t i))[4] { return *(u64(*)[4])
 // Berlekamp-Welch as berlekamp_welch_host runs it, over the Montgomery product of pvw_wide.h with every element times R (a zero
 // test and an equality test do not depend on the form; the secret is taken out of it at the end).  Its last step is the
 // contract itself: N / W is compared with the row in every column.  Cubic in count per secret.
+// With targets: values[s][j] = F_s(targets[j] + 1), four plain words, by Horner over the quotient's coefficients, 0 for an
+// undecodable row (pvw_shamir_evaluate_wide_corrected_host); out may then be NULL.
 static void berlekamp_welch_wide_host(const ReconstructWide& r, const uint64_t* shares, uint64_t* out, uint32_t* nerr, uint32_t* col_err,
-                                      uint64_t* err_mask) {
+                                      uint64_t* err_mask, const uint64_t* targets = nullptr, size_t num_targets = 0,
+                                      uint64_t* values = nullptr) {
   const WideMont mm = make_wide_mont(r.p);
   const size_t count = r.count, t = r.degree, E = (count - t - 1) / 2, nq = t + E + 1, nu = nq + E, ld = nu + 1;
   const size_t words = (count + 63) / 64;
@@ -4572,7 +4575,23 @@ static void berlekamp_welch_wide_host(const ReconstructWide& r, const uint64_t* 
         wide_mont_out(wel(N, E), mm, secret);
       }
     }
-    for (int i = 0; i < 4; ++i) out[s * 4 + i] = ok ? secret[i] : zero[i];
+    for (size_t j = 0; j < num_targets; ++j) {
+      u64 v[4] = {0, 0, 0, 0};
+      if (ok) {
+        const u64 xw[4] = {targets[j] + 1, targets[j] + 1 == 0 ? (u64)1 : (u64)0, 0, 0};
+        u64 xs[4];
+        wide_mont_in(xw, mm, xs);
+        set(v, wel(N, E + t));
+        for (size_t k = t; k-- > 0;) {
+          wide_mont_mul(v, xs, mm, v);
+          wide_add_p(v, wel(N, E + k), mm);
+        }
+        wide_mont_out(v, mm, v);
+      }
+      for (int i = 0; i < 4; ++i) values[(s * num_targets + j) * 4 + i] = v[i];
+    }
+    if (out)
+      for (int i = 0; i < 4; ++i) out[s * 4 + i] = ok ? secret[i] : zero[i];
     if (nerr) nerr[s] = ok ? (u32)wrong.size() : PVW_SHAMIR_UNDECODABLE;
     if (err_mask) std::fill(err_mask + s * words, err_mask + (s + 1) * words, (u64)0);
     if (ok)
@@ -4717,6 +4736,44 @@ int32_t pvw_shamir_reconstruct_wide_corrected_device(pvw_ctx* c, const uint64_t*
                                   "many secrets on this stream outside capture first (it sizes the workspace)");
 }
 
+// The staging of the host-buffer calls of 8.20 - 8.22 (ShareStaging with elements of four words): piece(s0, cnt) enqueues the
+// kernels of secrets [s0, s0 + cnt), staged dense at d_sh with their mask rows at d_er, and their downloads; the stream is
+// drained behind a piece before the next one reuses the staging.
+struct WideShareStaging {
+  const ReconstructWide& r;
+  const u64* shares;
+  const u64* erased;
+  size_t per;
+  bool dense;                                                    // whole rows go up as they lie
+  std::vector<u64> packed;                                       // a piece's shares when they do not
+  WideShareStaging(const ReconstructWide& r_, const u64* shares_, const u64* erased_, size_t per_)
+      : r(r_), shares(shares_), erased(erased_), per(per_), dense(r_.point_stride == 1 && r_.secret_stride >= r_.count) {
+    if (!dense) packed.resize(per * r.count * 4);
+  }
+  ~WideShareStaging() {
+    volatile u64* vp = packed.data();
+    for (size_t i = 0; i < packed.size(); ++i) vp[i] = 0;
+  }
+  int32_t run(u64* d_sh, u64* d_er, hipStream_t stream, const std::function<int32_t(size_t s0, size_t cnt)>& piece) {
+    const size_t count = r.count, words = (count + 63) / 64;
+    for (size_t s0 = 0; s0 < r.S; s0 += per) {
+      const size_t cnt = (r.S - s0) < per ? (r.S - s0) : per;
+      if (dense) {
+        PVW_HIP(hipMemcpy2DAsync(d_sh, count * 32, shares + s0 * r.secret_stride * 4, r.secret_stride * 32, count * 32, cnt,
+                                 hipMemcpyHostToDevice, stream));
+      } else {
+        for (size_t s = 0; s < cnt; ++s)
+          for (size_t col = 0; col < count; ++col)
+            memcpy(&packed[(s * count + col) * 4], shares + ((s0 + s) * r.secret_stride + col * r.point_stride) * 4, 32);
+        PVW_HIP(hipMemcpyAsync(d_sh, packed.data(), cnt * count * 32, hipMemcpyHostToDevice, stream));
+      }
+      if (erased) PVW_HIP(hipMemcpyAsync(d_er, erased + s0 * words, cnt * words * 8, hipMemcpyHostToDevice, stream));
+      PVW_TRY(piece(s0, cnt));
+      PVW_HIP(hipStreamSynchronize(stream));                     // the next piece reuses the staging
+    }
+    return PVW_OK;
+  }
+};
 // host buffers: the secrets go up in pieces as pvw_shamir_reconstruct_wide_checked stages them (a 2D copy for dense rows, else a
 // host repack that is wiped at the end), a piece no larger than one pass over the kernels; the public matrices are made once and
 // col_err adds up over the pieces.  The staged shares, the staged secrets and M are cleared before the call returns.
@@ -4726,7 +4783,7 @@ static int32_t correct_wide_host_call(pvw_ctx* c, const ReconstructWide& r, cons
                                       u32* col_err, u64* err_mask) {
   PVW_TRY(ensure_device(c));
   const WideMont mm = make_wide_mont(r.p);
-  const size_t count = r.count, num_secrets = r.S, secret_stride = r.secret_stride, point_stride = r.point_stride;
+  const size_t count = r.count, num_secrets = r.S;
   const size_t words = (count + 63) / 64;
   size_t per = chunk_1gib((count + 1) * 32 + (words + (erased ? words : 0)) * 8 + 4, num_secrets);
   if (per > correct_wide_piece(r)) per = correct_wide_piece(r);
@@ -4734,9 +4791,8 @@ static int32_t correct_wide_host_call(pvw_ctx* c, const ReconstructWide& r, cons
   Scratch sc;
   const size_t r_sh = sc.add(per * count * 32), r_out = sc.add(per * 32), r_ws = sc.add(lay.bytes()), r_nerr = sc.add(per * 4),
                r_col = sc.add(count * 4), r_mask = sc.add(per * words * 8), r_er = sc.add(erased ? per * words * 8 : 0);
-  const bool dense = point_stride == 1 && secret_stride >= count;
-  std::vector<u64> packed(dense ? 0 : per * count * 4);
-  const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
+  WideShareStaging st(r, shares, erased, per);
+  return host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
     u64 *d_sh = sc.at(r_sh), *d_out = sc.at(r_out), *ws = sc.at(r_ws);
     ws_mark_secret(w, d_sh, (size_t)((char*)ws - (char*)d_sh) + lay.m_bytes());   // staged shares | staged secrets | M
@@ -4745,30 +4801,16 @@ static int32_t correct_wide_host_call(pvw_ctx* c, const ReconstructWide& r, cons
     u64* d_er = erased ? sc.at(r_er) : nullptr;
     PVW_TRY(correct_wide_weights(c, r, mm, lay, ws, w->stream));
     PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
-    for (size_t s0 = 0; s0 < num_secrets; s0 += per) {
-      const size_t cnt = (num_secrets - s0) < per ? (num_secrets - s0) : per;
-      if (dense) {
-        PVW_HIP(hipMemcpy2DAsync(d_sh, count * 32, shares + s0 * secret_stride * 4, secret_stride * 32, count * 32, cnt,
-                                 hipMemcpyHostToDevice, w->stream));
-      } else {
-        for (size_t s = 0; s < cnt; ++s)
-          for (size_t col = 0; col < count; ++col)
-            memcpy(&packed[(s * count + col) * 4], shares + ((s0 + s) * secret_stride + col * point_stride) * 4, 32);
-        PVW_HIP(hipMemcpyAsync(d_sh, packed.data(), cnt * count * 32, hipMemcpyHostToDevice, w->stream));
-      }
-      if (erased) PVW_HIP(hipMemcpyAsync(d_er, erased + s0 * words, cnt * words * 8, hipMemcpyHostToDevice, w->stream));
+    PVW_TRY(st.run(d_sh, d_er, w->stream, [&](size_t s0, size_t cnt) -> int32_t {
       PVW_TRY(correct_wide_piece_enqueue(c, r, mm, lay, ws, d_sh, cnt, count, 1, d_out, d_nerr, d_col, d_mask, w->stream, d_er));
       PVW_HIP(hipMemcpyAsync(out + s0 * 4, d_out, cnt * 32, hipMemcpyDeviceToHost, w->stream));
       if (nerr) PVW_HIP(hipMemcpyAsync(nerr + s0, d_nerr, cnt * 4, hipMemcpyDeviceToHost, w->stream));
       if (err_mask) PVW_HIP(hipMemcpyAsync(err_mask + s0 * words, d_mask, cnt * words * 8, hipMemcpyDeviceToHost, w->stream));
-      PVW_HIP(hipStreamSynchronize(w->stream));                  // the next piece reuses the staging
-    }
+      return PVW_OK;
+    }));
     if (col_err) PVW_HIP(hipMemcpyAsync(col_err, d_col, count * 4, hipMemcpyDeviceToHost, w->stream));
     return PVW_OK;
   });
-  volatile u64* vp = packed.data();
-  for (size_t i = 0; i < packed.size(); ++i) vp[i] = 0;
-  return rc;
 }
 int32_t pvw_shamir_reconstruct_wide_corrected(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
                                               size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
@@ -4789,7 +4831,7 @@ int32_t pvw_shamir_reconstruct_wide_corrected(pvw_ctx* c, const uint64_t* plain_
 // sub-row with the same t, and the mask bits and col_err go back to the original columns.  A row with fewer than t + 1 columns
 // left (eps_s > r) is undecodable.  Nothing at an erased position is read.
 static void erasures_wide_host(const ReconstructWide& r, const u64* shares, const u64* erased, u64* out, u32* nerr, u32* col_err,
-                               u64* err_mask) {
+                               u64* err_mask, const u64* targets = nullptr, size_t num_targets = 0, u64* values = nullptr) {
   const size_t count = r.count, words = (count + 63) / 64;
   std::vector<size_t> cols;
   std::vector<u64> sub_idx(count), sub_sh(count * 4), sub_mask(words);
@@ -4802,8 +4844,10 @@ static void erasures_wide_host(const ReconstructWide& r, const u64* shares, cons
     if (err_mask) std::fill(err_mask + s * words, err_mask + (s + 1) * words, (u64)0);
     const size_t n = cols.size();
     if (n < (size_t)r.degree + 1) {
-      for (int k = 0; k < 4; ++k) out[s * 4 + k] = 0;
+      if (out)
+        for (int k = 0; k < 4; ++k) out[s * 4 + k] = 0;
       if (nerr) nerr[s] = PVW_SHAMIR_UNDECODABLE;
+      if (values) std::fill(values + s * num_targets * 4, values + (s + 1) * num_targets * 4, (u64)0);
       continue;
     }
     for (size_t i = 0; i < n; ++i) {
@@ -4812,7 +4856,8 @@ static void erasures_wide_host(const ReconstructWide& r, const u64* shares, cons
     }
     ReconstructWide sub{r.p, r.degree, sub_idx.data(), n, 1, n, 1, r.m};
     u32 ne = 0;
-    berlekamp_welch_wide_host(sub, sub_sh.data(), out + s * 4, &ne, sub_col.data(), sub_mask.data());
+    berlekamp_welch_wide_host(sub, sub_sh.data(), out ? out + s * 4 : nullptr, &ne, sub_col.data(), sub_mask.data(), targets, num_targets,
+                              values ? values + s * num_targets * 4 : nullptr);
     if (nerr) nerr[s] = ne;
     for (size_t i = 0; i < n; ++i)
       if ((sub_mask[i / 64] >> (i % 64)) & 1) {
@@ -4864,6 +4909,284 @@ int32_t pvw_shamir_reconstruct_wide_erasures(pvw_ctx* c, const uint64_t* plain_m
   PVW_TRY(reconstruct_wide_checks(r, shares, out));
   PVW_TRY(correct_wide_device_checks(r));
   return correct_wide_host_call(c, r, shares, erased, out, nerr, col_err, err_mask);
+}
+
+// ------------------------------------------------------------------------ evaluation below 2^256
+// The decode of 8.20 (8.21 with a mask), then values[s][j] = F_s(targets[j] + 1), four words, for every decodable row (0 for the
+// others).  One decode yields out, nerr, col_err, err_mask and values; the frame is that of 8.13 with elements of four words.
+
+// What the matching wide call refuses, in its order (values stands where it has out: out may be NULL here), then the targets.
+// device: num_targets is bounded BEFORE the targets are read, so a refused count costs no walk over the array.
+static int32_t evaluate_wide_checks(ReconstructWide& r, const void* shares, const uint64_t* targets, size_t num_targets, const void* values,
+                                    bool device) {
+  PVW_TRY(reconstruct_wide_checks(r, shares, values));
+  if (device) PVW_TRY(correct_wide_device_checks(r));
+  if (!targets) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (num_targets == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no targets to evaluate at");
+  if (device && num_targets >= ((size_t)1 << 31))
+    return fail(PVW_ERR_INVALID_PARAMETERS, "num_targets must be below 2^31 on the device");
+  // the point targets[j] + 1 <= 2^64 must be below p, as for the indices (reconstruct_wide_checks)
+  const bool one_word = !r.p[1] && !r.p[2] && !r.p[3];
+  const bool above_2_64 = r.p[2] || r.p[3] || r.p[1] > 1 || (r.p[1] == 1 && r.p[0] != 0);
+  for (size_t j = 0; j < num_targets; ++j)
+    if (one_word ? targets[j] >= r.p[0] - 1 : (targets[j] == ~(u64)0 && !above_2_64))
+      return fail(PVW_ERR_INVALID_PARAMETERS, "target index out of range for plain_modulus");
+  return PVW_OK;
+}
+
+int32_t pvw_shamir_evaluate_wide_corrected_host(const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                                const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                                const uint64_t* targets, size_t num_targets, uint64_t* values, uint64_t* out,
+                                                uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  PVW_TRY(evaluate_wide_checks(r, shares, targets, num_targets, values, false));
+  berlekamp_welch_wide_host(r, shares, out, nerr, col_err, err_mask, targets, num_targets, values);
+  return PVW_OK;
+}
+int32_t pvw_shamir_evaluate_wide_erasures_host(const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                               const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                               const uint64_t* erased, const uint64_t* targets, size_t num_targets, uint64_t* values,
+                                               uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  if (!erased)
+    return pvw_shamir_evaluate_wide_corrected_host(plain_modulus, degree, indices, count, shares, num_secrets, secret_stride, point_stride,
+                                                   targets, num_targets, values, out, nerr, col_err, err_mask);
+  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}, true};
+  PVW_TRY(evaluate_wide_checks(r, shares, targets, num_targets, values, false));
+  erasures_wide_host(r, shares, erased, out, nerr, col_err, err_mask, targets, num_targets, values);
+  return PVW_OK;
+}
+
+// Targets per group, by the rule of evaluate_group: a target costs a column of C, of Xt and of Xd, xt, scale and coin
+static size_t evaluate_wide_group(const ReconstructWide& r, size_t num_targets) {
+  const size_t per = (r.count + 2 * r.nk() + 2) * 32 + 4;
+  const long env = PVW_ENV_INT("PVW_EVALUATE_GROUP_BYTES", 0);
+  const size_t budget = env > 0 ? (size_t)env : (size_t)64 << 20;
+  size_t tg = budget / per;
+  if (tg > 64) tg -= tg % 64;
+  if (tg == 0) tg = 1;
+  return tg < num_targets ? tg : num_targets;
+}
+// The per-secret scratch in bytes: a row of M, of the syndromes and of the locators as in correct_wide_piece, a row of y o M, of
+// raw, of Psi and of Psi' at the group's targets and a stand-in for out; L and a stand-in for nerr
+static size_t evaluate_wide_secret_bytes(const ReconstructWide& r, size_t Tg) {
+  return (2 * r.count + r.red() + r.nk() + 3 * Tg + 1) * 32 + 8;
+}
+// secrets per pass, by the rule of correct_wide_piece
+static size_t evaluate_wide_piece(const ReconstructWide& r, size_t Tg) {
+  size_t cap = evaluate_piece_budget() / evaluate_wide_secret_bytes(r, Tg);
+  if (cap == 0) cap = 1;
+  if (cap > 65535u * 4) cap = 65535u * 4;
+  return cap < r.S ? cap : r.S;
+}
+// The scratch of one call, in words from its base: the block of the wide corrected call first (CorrectWideLayout: M leads it), then
+//   YM [cap][count][4] | raw [cap][Tg][4] | outs [cap][4]   -- depend on the shares: the second region marked secret
+//   PsiT [cap][Tg][4] | PsiD [cap][Tg][4] | nerr [cap] (u32) | the group's public matrices (shamir_evaluate_wide_public_words)
+// Every region of elements starts at a multiple of four words.
+struct EvaluateWideLayout {
+  CorrectWideLayout cl;
+  size_t Tg;
+  size_t ym, raw, outs, psiT, psiD, nerr, pub, total;   // word offsets
+  static size_t up4(size_t w) { return (w + 3) & ~(size_t)3; }
+  EvaluateWideLayout(const ReconstructWide& rc, size_t cap, size_t Tg_) : cl(rc, cap), Tg(Tg_) {
+    ym = up4(cl.total);
+    raw = ym + cap * rc.count * 4;
+    outs = raw + cap * Tg * 4;
+    psiT = outs + cap * 4;
+    psiD = psiT + cap * Tg * 4;
+    nerr = psiD + cap * Tg * 4;
+    pub = up4(nerr + (cap + 1) / 2);
+    total = pub + shamir_evaluate_wide_public_words(rc.count, Tg, cl.nk);
+  }
+  size_t bytes() const { return total * 8; }
+  size_t secret_bytes() const { return (psiT - ym) * 8; }
+};
+// What the stream's block must hold for a call: never less than the layout takes (96 bytes cover its roundings), and no smaller
+// for more secrets or more targets at the same (degree, count) and no smaller with a mask -- the rule a captured call is checked by.
+static size_t evaluate_wide_need_bytes(const ReconstructWide& r, size_t Tg) {
+  const size_t per = evaluate_wide_secret_bytes(r, Tg), budget = evaluate_piece_budget();
+  size_t part = r.S > budget / per ? budget : r.S * per;
+  if (part < per) part = per;
+  return part + 96 +
+         (shamir_correct_wide_public_words(r.count, r.degree, r.nk()) + shamir_evaluate_wide_public_words(r.count, Tg, r.nk())) * 8;
+}
+// One pass: ns <= lay.cl.cap secrets from d_shares are decoded (their out, nerr and mask rows; col_err is added to) and evaluated
+// at all targets, group by group, into d_values (rows num_targets elements apart).  `resident` is the first target of the group
+// whose public matrices the block holds; with one group they are built once for all passes.
+static int32_t evaluate_wide_pass_enqueue(pvw_ctx* c, const ReconstructWide& r, const WideMont& mm, const EvaluateWideLayout& lay, u64* ws,
+                                          const u64* d_shares, size_t ns, size_t secret_stride, size_t point_stride, const u64* targets,
+                                          size_t num_targets, u64* d_values, u64* d_out, u32* d_nerr, u32* d_col_err, u64* d_mask,
+                                          size_t* resident, hipStream_t s, const u64* d_erased) {
+  if (!d_out) d_out = ws + lay.outs;
+  if (!d_nerr) d_nerr = (u32*)(ws + lay.nerr);
+  PVW_TRY(correct_wide_piece_enqueue(c, r, mm, lay.cl, ws, d_shares, ns, secret_stride, point_stride, d_out, d_nerr, d_col_err, d_mask, s,
+                                     d_erased));
+  const u64 *x = ws + lay.cl.pub, *aux = x + r.count * 4;
+  const u64 *M = ws, *Psi = ws + lay.cl.lam;
+  u64 *YM = ws + lay.ym, *raw = ws + lay.raw, *PsiT = ws + lay.psiT, *PsiD = ws + lay.psiD, *pub = ws + lay.pub;
+  const size_t nk = lay.cl.nk;
+  {
+    ProfScope ps(c, "shamir_evaluate_wide", s);
+    PVW_HIP(launch_shamir_ym_wide(d_shares, secret_stride, point_stride, M, YM, (u32)ns, (u32)r.count, mm, s));
+  }
+  for (size_t j0 = 0; j0 < num_targets; j0 += lay.Tg) {
+    const size_t tg = num_targets - j0 < lay.Tg ? num_targets - j0 : lay.Tg;
+    if (*resident != j0) {
+      ProfScope ps(c, "shamir_evaluate_wide_weights", s);
+      PVW_HIP(launch_shamir_points_wide(targets + j0, tg, pub, mm, s));
+      PVW_HIP(launch_shamir_evaluate_weights_wide(x, aux, pub, r.count, (u32)nk, tg, mm, s));
+      *resident = j0;
+    }
+    ProfScope ps(c, "shamir_evaluate_wide", s);
+    const u64 *scale = pub + tg * 4, *C = scale + tg * 4, *Xt = C + r.count * tg * 4, *Xd = Xt + nk * tg * 4;
+    const u32* coin = (const u32*)(Xd + nk * tg * 4);
+    ShamirMatmulWide a{};
+    a.A = YM, a.secret_stride = r.count, a.term_stride = 1;
+    a.W = C, a.out = raw;
+    a.ns = (u32)ns, a.terms = (u32)r.count, a.T = (u32)tg, a.m = mm;
+    PVW_HIP(launch_shamir_matmul_wide(a, s));
+    ShamirMatmulWide b{};
+    b.A = Psi, b.secret_stride = nk, b.term_stride = 1;
+    b.W = Xt, b.out = PsiT;
+    b.ns = (u32)ns, b.terms = (u32)nk, b.T = (u32)tg, b.m = mm;
+    PVW_HIP(launch_shamir_matmul_wide(b, s));
+    b.W = Xd, b.out = PsiD;
+    PVW_HIP(launch_shamir_matmul_wide(b, s));
+    ShamirEvalFinishWide f{};
+    f.shares = d_shares, f.secret_stride = secret_stride, f.point_stride = point_stride;
+    f.M = M, f.nerr = d_nerr, f.raw = raw, f.PsiT = PsiT, f.PsiD = PsiD, f.scale = scale, f.coin = coin;
+    f.values = d_values + j0 * 4, f.value_stride = num_targets;
+    f.ns = (u32)ns, f.count = (u32)r.count, f.Tg = (u32)tg, f.m = mm;
+    PVW_HIP(launch_shamir_evaluate_finish_wide(f, s));
+  }
+  return PVW_OK;
+}
+
+// The device call behind its argument checks; with d_erased (r.erasures) the decode is that of 8.21
+static int32_t evaluate_wide_device_call(pvw_ctx* c, const ReconstructWide& r, const u64* d_shares, const u64* d_erased, const u64* targets,
+                                         size_t num_targets, u64* d_values, u64* d_out, u32* d_nerr, u32* d_col_err, u64* d_err_mask,
+                                         void* stream, const char* unsized) {
+  const WideMont mm = make_wide_mont(r.p);
+  const size_t Tg = evaluate_wide_group(r, num_targets);
+  const EvaluateWideLayout lay(r, evaluate_wide_piece(r, Tg), Tg);
+  const size_t need = evaluate_wide_need_bytes(r, Tg);
+  if (need < lay.bytes()) return fail(PVW_ERR_INTERNAL, "wide evaluation scratch: layout beyond its bound");
+  const size_t words = (r.count + 63) / 64;
+  // the caller's stream is checked before the context initialises its device (pvw_shamir_reconstruct_checked_device)
+  auto sized = [&](hipStream_t s) { return grown_capture_check(c, s, &Workspace::correct_wide_bytes, need, unsized); };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
+    if (w->correct_wide_bytes < need) ws_public(w, w->correct_wide, w->correct_wide_bytes);   // the block is about to go
+    PVW_TRY(ws_grow(&w->correct_wide, &w->correct_wide_bytes, need, s, true));
+    ws_mark_secret(w, w->correct_wide, lay.cl.m_bytes());
+    ws_mark_secret(w, w->correct_wide + lay.ym, lay.secret_bytes());
+    PVW_TRY(correct_wide_weights(c, r, mm, lay.cl, w->correct_wide, s));
+    PVW_HIP(launch_shamir_zero_counts(d_col_err, r.count, s));
+    size_t resident = SIZE_MAX;
+    for (size_t s0 = 0; s0 < r.S; s0 += lay.cl.cap) {
+      const size_t ns = r.S - s0 < lay.cl.cap ? r.S - s0 : lay.cl.cap;
+      PVW_TRY(evaluate_wide_pass_enqueue(c, r, mm, lay, w->correct_wide, d_shares + s0 * r.secret_stride * 4, ns, r.secret_stride,
+                                         r.point_stride, targets, num_targets, d_values + s0 * num_targets * 4, Report::from(d_out, s0 * 4),
+                                         Report::from(d_nerr, s0), d_col_err, Report::from(d_err_mask, s0 * words), &resident, s,
+                                         Report::from(d_erased, s0 * words)));
+    }
+    return PVW_OK;
+  });
+}
+static const char* const kWideEvaluateUnsized =
+    "wide corrected evaluation under stream capture: run a call with the same degree and count, at least as many targets and at least "
+    "as many secrets on this stream outside capture first (it sizes the workspace)";
+static const char* const kWideEvaluateErasuresUnsized =
+    "wide evaluation with erasures under stream capture: run a call with an erasure mask, the same degree and count, at least as many "
+    "targets and at least as many secrets on this stream outside capture first (it sizes the workspace)";
+
+int32_t pvw_shamir_evaluate_wide_corrected_device(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                  size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
+                                                  size_t point_stride, const uint64_t* targets, size_t num_targets, uint64_t* d_values,
+                                                  uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err, uint64_t* d_err_mask,
+                                                  void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  PVW_TRY(evaluate_wide_checks(r, d_shares, targets, num_targets, d_values, true));
+  return evaluate_wide_device_call(c, r, d_shares, nullptr, targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask, stream,
+                                   kWideEvaluateUnsized);
+}
+int32_t pvw_shamir_evaluate_wide_erasures_device(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                 size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
+                                                 size_t point_stride, const uint64_t* d_erased, const uint64_t* targets, size_t num_targets,
+                                                 uint64_t* d_values, uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err,
+                                                 uint64_t* d_err_mask, void* stream) {
+  if (!d_erased)
+    return pvw_shamir_evaluate_wide_corrected_device(c, plain_modulus, degree, indices, count, d_shares, num_secrets, secret_stride,
+                                                     point_stride, targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask,
+                                                     stream);
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}, true};
+  PVW_TRY(evaluate_wide_checks(r, d_shares, targets, num_targets, d_values, true));
+  return evaluate_wide_device_call(c, r, d_shares, d_erased, targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask, stream,
+                                   kWideEvaluateErasuresUnsized);
+}
+
+// host buffers: staged as pvw_shamir_reconstruct_wide_corrected stages (WideShareStaging: both copy paths, a piece at most one
+// pass, the mask rows with their shares); the values of a piece come down as one block.  The staged shares, secrets and values,
+// M, y o M and raw are cleared before the call returns.
+static int32_t evaluate_wide_host_call(pvw_ctx* c, const ReconstructWide& r, const u64* shares, const u64* erased, const u64* targets,
+                                       size_t num_targets, u64* values, u64* out, u32* nerr, u32* col_err, u64* err_mask) {
+  PVW_TRY(ensure_device(c));
+  const WideMont mm = make_wide_mont(r.p);
+  const size_t count = r.count, words = (count + 63) / 64;
+  const size_t Tg = evaluate_wide_group(r, num_targets);
+  size_t per = chunk_1gib((count + 1 + num_targets) * 32 + (words + (erased ? words : 0)) * 8 + 4, r.S);
+  if (per > evaluate_wide_piece(r, Tg)) per = evaluate_wide_piece(r, Tg);
+  const EvaluateWideLayout lay(r, per, Tg);
+  Scratch sc;
+  const size_t r_sh = sc.add(per * count * 32), r_out = sc.add(per * 32), r_val = sc.add(per * num_targets * 32), r_ws = sc.add(lay.bytes()),
+               r_nerr = sc.add(per * 4), r_col = sc.add(count * 4), r_mask = sc.add(per * words * 8),
+               r_er = sc.add(erased ? per * words * 8 : 0);
+  WideShareStaging st(r, shares, erased, per);
+  return host_call(c, [&](Workspace* w) -> int32_t {
+    PVW_TRY(sc.take(w));
+    u64 *d_sh = sc.at(r_sh), *d_out = sc.at(r_out), *d_val = sc.at(r_val), *ws = sc.at(r_ws);
+    ws_mark_secret(w, d_sh, (size_t)((char*)ws - (char*)d_sh) + lay.cl.m_bytes());   // staged shares | secrets | values | M
+    ws_mark_secret(w, ws + lay.ym, lay.secret_bytes());                              // y o M | raw | the stand-in for out
+    u32 *d_nerr = sc.at<u32>(r_nerr), *d_col = col_err ? sc.at<u32>(r_col) : nullptr;
+    u64* d_mask = err_mask ? sc.at(r_mask) : nullptr;
+    u64* d_er = erased ? sc.at(r_er) : nullptr;
+    PVW_TRY(correct_wide_weights(c, r, mm, lay.cl, ws, w->stream));
+    PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
+    size_t resident = SIZE_MAX;
+    PVW_TRY(st.run(d_sh, d_er, w->stream, [&](size_t s0, size_t cnt) -> int32_t {
+      PVW_TRY(evaluate_wide_pass_enqueue(c, r, mm, lay, ws, d_sh, cnt, count, 1, targets, num_targets, d_val, d_out, d_nerr, d_col, d_mask,
+                                         &resident, w->stream, d_er));
+      PVW_HIP(hipMemcpyAsync(values + s0 * num_targets * 4, d_val, cnt * num_targets * 32, hipMemcpyDeviceToHost, w->stream));
+      if (out) PVW_HIP(hipMemcpyAsync(out + s0 * 4, d_out, cnt * 32, hipMemcpyDeviceToHost, w->stream));
+      if (nerr) PVW_HIP(hipMemcpyAsync(nerr + s0, d_nerr, cnt * 4, hipMemcpyDeviceToHost, w->stream));
+      if (err_mask) PVW_HIP(hipMemcpyAsync(err_mask + s0 * words, d_mask, cnt * words * 8, hipMemcpyDeviceToHost, w->stream));
+      return PVW_OK;
+    }));
+    if (col_err) PVW_HIP(hipMemcpyAsync(col_err, d_col, count * 4, hipMemcpyDeviceToHost, w->stream));
+    return PVW_OK;
+  });
+}
+int32_t pvw_shamir_evaluate_wide_corrected(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                           const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                           const uint64_t* targets, size_t num_targets, uint64_t* values, uint64_t* out, uint32_t* nerr,
+                                           uint32_t* col_err, uint64_t* err_mask) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  PVW_TRY(evaluate_wide_checks(r, shares, targets, num_targets, values, true));
+  return evaluate_wide_host_call(c, r, shares, nullptr, targets, num_targets, values, out, nerr, col_err, err_mask);
+}
+int32_t pvw_shamir_evaluate_wide_erasures(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                          const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                          const uint64_t* erased, const uint64_t* targets, size_t num_targets, uint64_t* values,
+                                          uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  if (!erased)
+    return pvw_shamir_evaluate_wide_corrected(c, plain_modulus, degree, indices, count, shares, num_secrets, secret_stride, point_stride,
+                                              targets, num_targets, values, out, nerr, col_err, err_mask);
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}, true};
+  PVW_TRY(evaluate_wide_checks(r, shares, targets, num_targets, values, true));
+  return evaluate_wide_host_call(c, r, shares, erased, targets, num_targets, values, out, nerr, col_err, err_mask);
 }
 
 // The mask of wide shares from a per-limb decrypt report: bit (s, c) set iff for some w < num_limbs the element at

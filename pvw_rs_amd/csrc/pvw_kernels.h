@@ -478,6 +478,35 @@ hipError_t launch_shamir_wide_erasure_mask(const u32* status, const u64* noise, 
                                            size_t secret_stride, size_t point_stride, u32 num_limbs, size_t limb_stride, u64* mask,
                                            hipStream_t s);
 
+// ---- Evaluation of the corrected polynomials over a prime below 2^256 (pvw_shamir.hip): the evaluation of 8.13
+// with elements of four words behind the decode of 8.20 or 8.21.  Public workspace words of a group of Tg targets, all times R:
+//   xt [Tg][4] | scale [Tg][4] | C [count][Tg][4] | Xt [nk][Tg][4] | Xd [nk][Tg][4] | coin [Tg] (u32)
+// YM and raw are plain, the locator's values at the targets are times R like M.
+inline size_t shamir_evaluate_wide_public_words(size_t count, size_t Tg, size_t nk) {
+  return 4 * (2 * Tg + count * Tg + 2 * nk * Tg) + (Tg + 1) / 2;
+}
+struct ShamirEvalFinishWide {
+  const u64* shares;     // as ShamirInterpWide
+  size_t secret_stride, point_stride;
+  const u64* M;          // [ns][count][4]
+  const u32* nerr;       // [ns]: PVW_SHAMIR_NO_LOCATOR for an undecodable row
+  const u64* raw;        // [ns][Tg][4]
+  const u64* PsiT;       // [ns][Tg][4]: Psi_s(x*_j)
+  const u64* PsiD;       // [ns][Tg][4]: Psi_s'(x*_j)
+  const u64* scale;      // [Tg][4]
+  const u32* coin;       // [Tg]: the column whose point target j is, or PVW_SHAMIR_NO_COLUMN
+  u64* values;           // element (s, j): four words at values + 4 (s * value_stride + j)
+  size_t value_stride;
+  u32 ns, count, Tg;
+  WideMont m;
+};
+// ws: the group's public words, xt filled by launch_shamir_points_wide; x, aux: the call's points and u_c
+hipError_t launch_shamir_evaluate_weights_wide(const u64* x, const u64* aux, u64* ws, size_t count, u32 nk, size_t Tg, const WideMont& m,
+                                               hipStream_t s);
+hipError_t launch_shamir_ym_wide(const u64* shares, size_t secret_stride, size_t point_stride, const u64* M, u64* YM, u32 ns, u32 count,
+                                 const WideMont& m, hipStream_t s);
+hipError_t launch_shamir_evaluate_finish_wide(const ShamirEvalFinishWide& f, hipStream_t s);
+
 // p[0 .. words) = 0, as a kernel launch on s
 hipError_t launch_wipe_words(u64* p, size_t words, hipStream_t s);
 

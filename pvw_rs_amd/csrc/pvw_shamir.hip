@@ -2208,4 +2208,206 @@ hipError_t launch_shamir_correct_finish_wide(const ShamirFinishWide& f, u32 ns, 
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------ evaluation below 2^256
+// The table of 8.13 with elements of four words, behind the decode of 8.20 or 8.21, Psi_s standing for Lambda_s.  Forms:
+//   xt, scale, C, Xt, Xd                                 public, stored times R
+//   shares, YM = REDC(y (M R)), raw = YM x C             plain
+//   Psi(x*) = Psi x Xt, Psi'(x*) = Psi x Xd              times R, like M
+//   values                                               plain: REDC(raw (scale R)), then REDC with (den R)^-1 R (wide_mont_inv)
+
+// the product of the lanes' values (each times R and below p), the same in every lane: 8 32-bit shuffles a step, no LDS
+__device__ __forceinline__ void wave_mul_wide(u64 (&v)[4], const WideMont& m) {
+#pragma unroll
+  for (int off = 32; off; off >>= 1) {
+    u64 f[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) f[k] = (u64)__shfl_xor((unsigned long long)v[k], off);
+    wide_mont_mul(v, f, m, v);
+  }
+}
+
+// shamir_target_scale_kernel over four words: one wave per target j
+__global__ __launch_bounds__(256) void shamir_target_scale_wide_kernel(const u64* x, const u64* xt, u64* scale, u32* coin, u32 count, u32 Tg,
+                                                                       WideMont m) {
+  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const u32 j = blockIdx.x * SH_WAVES + wave;
+  if (j >= Tg) return;                                           // wave-uniform
+  u64 xs[4], prod[4];
+  wide_ld(xt + (size_t)j * 4, xs);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) prod[k] = m.one[k];
+  u32 hit = PVW_SHAMIR_NO_COLUMN;
+  for (u32 i = lane; i < count; i += 64) {
+    u64 xi[4], d[4];
+    wide_ld(x + (size_t)i * 4, xi);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d[k] = xs[k];
+    wide_sub_p(d, xi, m);
+    if (wide_zero(d)) hit = i;
+    else wide_mont_mul(prod, d, m, prod);
+  }
+  wave_mul_wide(prod, m);
+#pragma unroll
+  for (int off = 32; off; off >>= 1) {
+    const u32 o = (u32)__shfl_xor((int)hit, off);
+    hit = o < hit ? o : hit;
+  }
+  if (lane == 0) {
+    wide_st(scale + (size_t)j * 4, prod);
+    coin[j] = hit;
+  }
+}
+
+// C[i][j] = u_i / (x*_j - x_i), 0 where the points coincide.  The shape of shamir_weights_wide_kernel: one thread per target and
+// group of SHW_WG columns, the target fastest (thread e = group * Tg + j), so lanes store along a row of C.  The group's
+// differences share one inversion, their running products going through the entries' own slots of C; a zero difference enters
+// the products as 1, which leaves its slot equal to the one before it.
+__global__ __launch_bounds__(256) void shamir_cauchy_wide_kernel(const u64* x, const u64* aux, const u64* xt, u64* C, u32 count, u32 Tg,
+                                                                 WideMont m) {
+  const size_t groups = ((size_t)count + SHW_WG - 1) / SHW_WG;
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= groups * Tg) return;
+  const size_t j = e % Tg, i0 = (e / Tg) * SHW_WG;
+  const u32 cnt = (size_t)count - i0 < SHW_WG ? (u32)((size_t)count - i0) : SHW_WG;
+  u64 xs[4], run[4];
+  wide_ld(xt + j * 4, xs);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) run[k] = m.one[k];
+  for (u32 k = 0; k < cnt; ++k) {
+    u64 xi[4], d[4];
+    wide_ld(x + (i0 + k) * 4, xi);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) d[i] = xs[i];
+    wide_sub_p(d, xi, m);
+    if (!wide_zero(d)) wide_mont_mul(run, d, m, run);
+    wide_st(C + ((i0 + k) * Tg + j) * 4, run);
+  }
+  u64 inv[4];
+  wide_mont_inv(run, m, inv);
+  // back: inv = (d_0 ... d_k)^-1 on entry to step k; d_k^-1 = inv * slot[k-1]
+  for (u32 k = cnt; k-- > 0;) {
+    u64 xi[4], d[4], pre[4], v[4] = {0, 0, 0, 0};
+    wide_ld(x + (i0 + k) * 4, xi);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) d[i] = xs[i];
+    wide_sub_p(d, xi, m);
+    if (!wide_zero(d)) {
+      if (k) wide_ld(C + ((i0 + k - 1) * Tg + j) * 4, pre);
+      else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) pre[i] = m.one[i];
+      }
+      u64 u[4];
+      wide_mont_mul(inv, pre, m, v);                             // d_k^-1
+      wide_mont_mul(inv, d, m, inv);
+      wide_ld(aux + (i0 + k) * 4, u);
+      wide_mont_mul(v, u, m, v);
+    }
+    wide_st(C + ((i0 + k) * Tg + j) * 4, v);
+  }
+}
+
+// Xd[k][j] = k x_j^(k-1) (row 0 is 0), in the frame of shamir_powers_wide_kernel; k R goes along by additions of R
+__global__ __launch_bounds__(256) void shamir_dpowers_wide_kernel(const u64* x, u64* X, u32 count, u32 nk, WideMont m) {
+  const u32 c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= count) return;
+  const u32 k0 = blockIdx.y * 64, k1 = k0 + 64 < nk ? k0 + 64 : nk;
+  u64 xc[4], v[4], kr[4];
+  wide_ld(x + (size_t)c * 4, xc);
+  wide_mont_pow(xc, k0 > 1 ? k0 - 1 : 0, m, v);                  // x_c^(k-1) of the first k >= 1
+  const u64 kw[4] = {k0, 0, 0, 0};
+  wide_mont_in(kw, m, kr);
+  for (u32 k = k0; k < k1; ++k) {
+    u64 o[4] = {0, 0, 0, 0};
+    if (k) {
+      wide_mont_mul(kr, v, m, o);
+      wide_mont_mul(v, xc, m, v);
+    }
+    wide_st(X + ((size_t)k * count + c) * 4, o);
+    wide_add_p(kr, m.one, m);
+  }
+}
+
+// YM[s][c] = y[s][c] M[s][c], plain: one REDC of the share's words times M R.  One thread per element, the column fastest; where
+// M is 0 nothing is loaded from the shares, so the words at a wrong or an erased position never enter.
+__global__ __launch_bounds__(256) void shamir_ym_wide_kernel(const u64* shares, size_t secret_stride, size_t point_stride, const u64* M,
+                                                             u64* YM, u32 ns, u32 count, WideMont m) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)ns * count) return;
+  const size_t s = e / count, c = e % count;
+  u64 mv[4], v[4] = {0, 0, 0, 0};
+  wide_ld(M + e * 4, mv);
+  if (!wide_zero(mv)) {
+    const u64* sp = shares + (s * secret_stride + c * point_stride) * 4;
+    const u64 w[4] = {sp[0], sp[1], sp[2], sp[3]};
+    wide_mont_mul(w, mv, m, v);
+  }
+  wide_st(YM + e * 4, v);
+}
+
+// shamir_evaluate_finish_kernel over four words: one thread per (s, j), the target fastest.  The zero test on M is on the times-R
+// form, exact since M < p.
+__global__ __launch_bounds__(256) void shamir_evaluate_finish_wide_kernel(ShamirEvalFinishWide f) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)f.ns * f.Tg) return;
+  const size_t s = e / f.Tg, j = e % f.Tg;
+  const WideMont m = f.m;
+  u64 v[4] = {0, 0, 0, 0};
+  if (f.nerr[s] != PVW_SHAMIR_NO_LOCATOR) {
+    const u32 c = f.coin[j];
+    u64 mv[4] = {0, 0, 0, 0};
+    if (c != PVW_SHAMIR_NO_COLUMN) wide_ld(f.M + (s * f.count + c) * 4, mv);
+    if (!wide_zero(mv)) {
+      const u64* sp = f.shares + (s * f.secret_stride + (size_t)c * f.point_stride) * 4;
+      const u64 w[4] = {sp[0], sp[1], sp[2], sp[3]};
+      wide_reduce_p(w, m, v);
+    } else {
+      u64 den[4], sc[4];
+      wide_ld((c != PVW_SHAMIR_NO_COLUMN ? f.PsiD : f.PsiT) + e * 4, den);
+      wide_ld(f.raw + e * 4, v);
+      wide_ld(f.scale + j * 4, sc);
+      wide_mont_mul(v, sc, m, v);
+      wide_mont_inv(den, m, den);
+      wide_mont_mul(v, den, m, v);
+    }
+  }
+  u64* out = f.values + (s * f.value_stride + j) * 4;              // the caller's buffer: word stores
+#pragma unroll
+  for (int k = 0; k < 4; ++k) out[k] = v[k];
+}
+
+hipError_t launch_shamir_evaluate_weights_wide(const u64* x, const u64* aux, u64* ws, size_t count, u32 nk, size_t Tg, const WideMont& m,
+                                               hipStream_t s) {
+  const u32 n = (u32)count, tg = (u32)Tg;
+  const u64* xt = ws;
+  u64 *scale = ws + Tg * 4, *C = scale + Tg * 4, *Xt = C + count * Tg * 4, *Xd = Xt + (size_t)nk * Tg * 4;
+  u32* coin = (u32*)(Xd + (size_t)nk * Tg * 4);
+  shamir_target_scale_wide_kernel<<<dim3((tg + SH_WAVES - 1) / SH_WAVES), dim3(256), 0, s>>>(x, xt, scale, coin, n, tg, m);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const size_t threads = ((count + SHW_WG - 1) / SHW_WG) * Tg;
+  shamir_cauchy_wide_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>(x, aux, xt, C, n, tg, m);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  const dim3 grid((tg + 255) / 256, (nk + 63) / 64);
+  shamir_powers_wide_kernel<<<grid, dim3(256), 0, s>>>(xt, Xt, tg, nk, m);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  shamir_dpowers_wide_kernel<<<grid, dim3(256), 0, s>>>(xt, Xd, tg, nk, m);
+  return hipGetLastError();
+}
+
+hipError_t launch_shamir_ym_wide(const u64* shares, size_t secret_stride, size_t point_stride, const u64* M, u64* YM, u32 ns, u32 count,
+                                 const WideMont& m, hipStream_t s) {
+  if (ns == 0) return hipSuccess;
+  const size_t blocks = ((size_t)ns * count + 255) / 256;
+  shamir_ym_wide_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(shares, secret_stride, point_stride, M, YM, ns, count, m);
+  return hipGetLastError();
+}
+
+hipError_t launch_shamir_evaluate_finish_wide(const ShamirEvalFinishWide& f, hipStream_t s) {
+  if (f.ns == 0 || f.Tg == 0) return hipSuccess;
+  const size_t blocks = ((size_t)f.ns * f.Tg + 255) / 256;
+  shamir_evaluate_finish_wide_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(f);
+  return hipGetLastError();
+}
+
 }  // namespace pvw

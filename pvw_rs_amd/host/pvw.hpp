@@ -868,6 +868,37 @@ inline CorrectedWideSecrets shamir_reconstruct_wide_corrected(const std::shared_
                                                     er, r.secrets.data(), r.nerr.data(), r.col_err.data(), r.err_mask.data()));
   return r;
 }
+// ---- share repair over an odd prime below 2^256 ----
+struct EvaluatedWideShares {
+  std::vector<uint64_t> values;     // [num_secrets][targets.size()][4]: F_s(targets[j] + 1); the row of an undecodable secret is 0
+  CorrectedWideSecrets report;      // what shamir_reconstruct_wide_corrected returns on the same input
+};
+// The decode of shamir_reconstruct_wide_corrected and the corrected polynomials at the points of the parties `targets` (global
+// indices whose point targets[j] + 1 is below p: columns of the call -- the share that party should hold -- or any other;
+// duplicates allowed).  `erased` as in the overload above; empty: no mask.  On the device (pvw_shamir_evaluate_wide_corrected /
+// _erasures); host = true: the plain C++ restatement (no GPU; p may be null).
+inline EvaluatedWideShares shamir_evaluate_wide_corrected(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& indices,
+                                                          const std::vector<uint64_t>& shares, uint32_t degree, const Wide& plain_modulus,
+                                                          const std::vector<uint64_t>& targets, const std::vector<uint64_t>& erased = {},
+                                                          bool party_major = false, bool host = false) {
+  const size_t count = indices.size(), T = targets.size();
+  if (count == 0 || shares.empty() || shares.size() % (count * PVW_WIDE_WORDS)) throw PvwError(15, "shares must hold one element per index and secret");
+  const size_t S = shares.size() / (count * PVW_WIDE_WORDS), ss = party_major ? 1 : count, ps = party_major ? S : 1;
+  const size_t words = (count + 63) / 64;
+  if (!erased.empty() && erased.size() != S * words) throw PvwError(15, "erased must hold ceil(count / 64) words per secret");
+  const uint64_t* er = erased.empty() ? nullptr : erased.data();
+  EvaluatedWideShares r{std::vector<uint64_t>(S * T * PVW_WIDE_WORDS),
+                        CorrectedWideSecrets{std::vector<uint64_t>(S * PVW_WIDE_WORDS), std::vector<uint32_t>(S), std::vector<uint32_t>(count),
+                                             std::vector<uint64_t>(S * words), words}};
+  CorrectedWideSecrets& c = r.report;
+  check(host ? pvw_shamir_evaluate_wide_erasures_host(plain_modulus.data(), degree, indices.data(), count, shares.data(), S, ss, ps, er,
+                                                      targets.data(), T, r.values.data(), c.secrets.data(), c.nerr.data(), c.col_err.data(),
+                                                      c.err_mask.data())
+             : pvw_shamir_evaluate_wide_erasures(p->ctx, plain_modulus.data(), degree, indices.data(), count, shares.data(), S, ss, ps, er,
+                                                 targets.data(), T, r.values.data(), c.secrets.data(), c.nerr.data(), c.col_err.data(),
+                                                 c.err_mask.data()));
+  return r;
+}
 // The mask of wide shares from a per-limb decrypt report on the host (pvw_shamir_wide_erasure_mask_host): status / noise
 // [num_secrets][count * num_limbs], or with party_major [count][num_secrets * num_limbs] (the [party][dealer NL + w] report of the
 // decrypt-all calls); either may be empty, not both.  Share (s, c) is erased iff one of its limbs has status & status_bits or

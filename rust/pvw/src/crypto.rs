@@ -766,6 +766,35 @@ pub fn shamir_reconstruct_wide_erasures(params: &Arc<PvwParameters>, indices: &[
     Ok(r)
 }
 
+/// EXTENSION: share repair over a prime below 2^256.  The decode of `shamir_reconstruct_wide_corrected` (of
+/// `shamir_reconstruct_wide_erasures` when `erased` is not empty) and the corrected polynomials at the points of the parties
+/// `targets`: global indices whose point `targets[j] + 1` is below p, columns of the call -- the share that party should hold --
+/// or any other, duplicates allowed.  Returns `values [num_secrets][targets.len()]` (the row of an undecodable secret is 0) and
+/// the decode's report (`pvw_shamir_evaluate_wide_corrected` / `pvw_shamir_evaluate_wide_erasures`).
+pub fn shamir_evaluate_wide_corrected(params: &Arc<PvwParameters>, indices: &[u64], shares: &[Wide], degree: u32, plain_modulus: &Wide,
+                                      erased: &[u64], targets: &[u64], party_major: bool) -> Result<(Vec<Wide>, CorrectedWideSecrets)> {
+    if indices.is_empty() || shares.is_empty() || shares.len() % indices.len() != 0 {
+        return Err(PvwError::InvalidParameters("shares must hold one element per index and secret".into()));
+    }
+    let (count, num) = (indices.len(), shares.len() / indices.len());
+    let (ss, ps) = if party_major { (1, num) } else { (count, 1) };
+    let words = (count + 63) / 64;
+    if !erased.is_empty() && erased.len() != num * words {
+        return Err(PvwError::InvalidParameters("erased must hold ceil(count / 64) words per secret".into()));
+    }
+    let er = if erased.is_empty() { std::ptr::null() } else { erased.as_ptr() };
+    let mut values = vec![[0u64; 4]; num * targets.len()];
+    let mut r = CorrectedWideSecrets { secrets: vec![[0u64; 4]; num], nerr: vec![0u32; num], col_err: vec![0u32; count],
+                                       err_mask: vec![0u64; num * words], words };
+    check(unsafe {
+        sys::pvw_shamir_evaluate_wide_erasures(params.hip.raw(), plain_modulus.as_ptr(), degree, indices.as_ptr(), count,
+                                               shares.as_ptr() as *const u64, num, ss, ps, er, targets.as_ptr(), targets.len(),
+                                               values.as_mut_ptr() as *mut u64, r.secrets.as_mut_ptr() as *mut u64, r.nerr.as_mut_ptr(),
+                                               r.col_err.as_mut_ptr(), r.err_mask.as_mut_ptr())
+    })?;
+    Ok((values, r))
+}
+
 /// EXTENSION: the erasure mask of wide shares from a per-limb decrypt report, on the host
 /// (`pvw_shamir_wide_erasure_mask_host`).  `status` and `noise` are `[num_secrets][count * num_limbs]`, or with `party_major`
 /// `[count][num_secrets * num_limbs]` (the `[party][dealer * NL + w]` report of the decrypt-all calls, every dealer a secret);
