@@ -1064,6 +1064,58 @@ PVW_API int32_t pvw_shamir_reconstruct_wide(const uint64_t* plain_modulus, const
 PVW_API int32_t pvw_selftest_shamir_wide_step(pvw_ctx* ctx, const uint64_t* plain_modulus, const uint64_t* acc, const uint64_t* x,
                                               const uint64_t* add, size_t count, uint64_t* out);
 
+/* ---- Packed Shamir shares over a prime field of up to 256 bits: the polynomial of 8.14 with the elements, draws
+ * and limbs of 8.18.  `pack` = K >= 1 secrets per dealer, `degree` = t >= 0 random coefficients, all arithmetic in Z_p:
+ *   f_d(x) = sum_{j<K} s_{d,j} L_j(x)  +  Z(x) (a_{d,1} + a_{d,2} x + ... + a_{d,t} x^(t-1))  mod p
+ *   L_j = the Lagrange basis polynomial of the point -j among 0, -1, ..., -(K-1);  Z(x) = x (x+1) ... (x+K-1)
+ *   shares[d][i] = f_d(i + 1), i the global party index; a share is four words, fully reduced
+ * secrets [D][K][4] are dealer-major and coeffs [D][t][4] optional; any words are accepted and read mod p.  a_{d,j} (j = 1..t) are
+ * exactly the draws of 8.18; degree = 0 draws nothing and needs no seeds.  With K = 1 the polynomial is that of 8.18 (L_0 = 1,
+ * Z = x): every call below with pack = 1 is bit-equal to the wide call it extends, for shares and for ciphertexts.  Limbs, keys
+ * and the _rs counter as pvw_deal_shares_wide*: seeds [D NL][32], dealer d's coefficients drawn under the key of vector d NL, the
+ * state ends at c + D NL; the shares-alone calls take seeds [D][32].  S wide secrets cost S NL / K ciphertexts.
+ * PVW_ERR_INVALID_PARAMETERS before any device work, nothing written: what the call being extended refuses, then pack = 0,
+ * pack > PVW_WIDE_MAX_PACK (the weights are 32 pack columns bytes: 128 MiB at 4096 columns), degree + pack > n,
+ * n + pack - 1 >= 2^32 (the weights are built with 32-bit multipliers), p < n + pack (as wide integers; p <= n when K = 1).
+ * The weights L_j(i + 1) and Z(i + 1) are public and made on the device into a block of the stream's workspace, sized by the
+ * call: under stream capture the _device forms need an earlier call of this kind on that stream outside capture with at least as
+ * many pack x columns words (and pvw_prepare(PVW_PREPARE_MFMA) for the deals), otherwise the error of pvw_encrypt_multi_device
+ * and nothing enqueued.  A later call that needs more words replaces the block: capture again, as for 8.14.
+ * The way back: pvw_ct_sum*, pvw_decrypt_*sum*, pvw_shamir_wide_from_limbs_* and the wide reconstruct / evaluate calls take a
+ * packed sharing as a polynomial of degree t + K - 1; pvw_shamir_reconstruct_packed_wide reads the K secrets off its shares. */
+#define PVW_WIDE_MAX_PACK 1024
+/* the contract on the host cores (no GPU needed), all n columns: what the kernels are tested against.  shares [D][n][4] */
+PVW_API int32_t pvw_shamir_shares_packed_wide_host(const pvw_ctx* ctx, const uint64_t* secrets, size_t num_dealers, uint32_t pack,
+                                                   uint32_t degree, const uint64_t* plain_modulus, const uint8_t* seeds,
+                                                   const uint64_t* coeffs, uint64_t* shares_out);
+PVW_API int32_t pvw_shamir_shares_packed_wide_device(pvw_ctx* ctx, const uint64_t* d_secrets, size_t num_dealers, uint32_t pack,
+                                                     uint32_t degree, const uint64_t* plain_modulus, const uint8_t* seeds,
+                                                     const uint64_t* d_coeffs, uint64_t* d_shares, void* stream);
+PVW_API int32_t pvw_shamir_shares_packed_wide(pvw_ctx* ctx, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                              const uint64_t* plain_modulus, const uint8_t* seeds, const uint64_t* coeffs,
+                                              uint64_t* shares_out);
+/* Deal: pvw_encrypt_multi* on D NL vectors, bit for bit what it gives for the limb planes of
+ * pvw_shamir_shares_packed_wide_host(..., seeds[d NL], NULL): both representations, both sides of the dealer-count dispatch (by
+ * D NL), sharded contexts.  Every replay of a captured _rs form deals a fresh sharing. */
+PVW_API int32_t pvw_deal_shares_packed_wide(pvw_ctx* ctx, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                            const uint64_t* plain_modulus, uint32_t limb_bits, const uint8_t* seeds, uint64_t* c1_out,
+                                            uint64_t* c2_out, uint32_t out_repr);
+PVW_API int32_t pvw_deal_shares_packed_wide_device(pvw_ctx* ctx, const uint64_t* d_secrets, size_t num_dealers, uint32_t pack,
+                                                   uint32_t degree, const uint64_t* plain_modulus, uint32_t limb_bits,
+                                                   const uint8_t* seeds, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream);
+PVW_API int32_t pvw_deal_shares_packed_wide_rs(pvw_ctx* ctx, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                               const uint64_t* plain_modulus, uint32_t limb_bits, void* st, uint64_t* c1_out,
+                                               uint64_t* c2_out, uint32_t out_repr);
+PVW_API int32_t pvw_deal_shares_packed_wide_rs_device(pvw_ctx* ctx, const uint64_t* d_secrets, size_t num_dealers, uint32_t pack,
+                                                      uint32_t degree, const uint64_t* plain_modulus, uint32_t limb_bits, void* st,
+                                                      uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream);
+/* Reconstruction, host only (no GPU, no context): out[r][j] = F_r(-j), j < pack, from the Lagrange weights of the points
+ * indices[i] + 1 at each of 0, -1, ..., -(pack-1), computed once, then pack dot products per row.  shares [num_rows][count][4]
+ * (any words, read mod p), out [num_rows][pack][4].  The rules of pvw_shamir_reconstruct_wide, plus pack >= 1 and every index
+ * < p - pack.  count must be at least degree + pack for the result to be the secrets. */
+PVW_API int32_t pvw_shamir_reconstruct_packed_wide(const uint64_t* plain_modulus, uint32_t pack, const uint64_t* indices,
+                                                   const uint64_t* shares, size_t count, size_t num_rows, uint64_t* out);
+
 /* ---- The receiving end over a prime field of up to 256 bits: the fold of decrypted limbs on the device, and
  * checked reconstruction with wide elements.  The contract is the library's own.  plain_modulus is a HOST pointer to an odd
  * prime below 2^256 in every form, checked as above.

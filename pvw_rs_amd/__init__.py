@@ -22,7 +22,9 @@ from .api import (DEC_LOSSY, DEC_NEGATIVE, DEC_WIDE_TRUNCATED, CheckedDecryption
                   shamir_packed_handover_weights, sample_secret_keys_device, shamir_shares_wide, deal_party_shares_wide,
                   shamir_wide_limbs, shamir_wide_to_limbs, shamir_wide_from_limbs, shamir_reconstruct_wide,
                   shamir_wide_from_limbs_device, shamir_reconstruct_wide_checked,
-                  shamir_reconstruct_wide_corrected, shamir_wide_erasure_mask, shamir_evaluate_wide_corrected)
+                  shamir_reconstruct_wide_corrected, shamir_wide_erasure_mask, shamir_evaluate_wide_corrected,
+                  shamir_shares_packed_wide, deal_party_shares_packed_wide, shamir_reconstruct_packed_wide,
+                  shamir_reconstruct_packed_wide_corrected)
 
 __all__ = [
     "PvwParametersBuilder", "PvwParameters", "PvwCrs", "SecretKey", "DeviceSecretKey", "DeviceRandomness", "Party", "GlobalPublicKey",
@@ -42,5 +44,6 @@ __all__ = [
     "shamir_shares_wide", "deal_party_shares_wide", "shamir_wide_limbs", "shamir_wide_to_limbs", "shamir_wide_from_limbs", "shamir_reconstruct_wide",
     "shamir_wide_from_limbs_device", "shamir_reconstruct_wide_checked", "shamir_reconstruct_wide_corrected", "shamir_wide_erasure_mask",
     "shamir_evaluate_wide_corrected",
+    "shamir_shares_packed_wide", "deal_party_shares_packed_wide", "shamir_reconstruct_packed_wide", "shamir_reconstruct_packed_wide_corrected",
     "device_available", "REPR_POWER", "REPR_NTT",
 ]

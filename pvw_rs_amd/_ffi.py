@@ -168,6 +168,15 @@ _SIGNATURES = {
     "pvw_shamir_wide_from_limbs_host": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, _P],
     "pvw_shamir_reconstruct_wide": [_P, _P, _P, C.c_size_t, C.c_size_t, _P],
     "pvw_selftest_shamir_wide_step": [_P, _P, _P, _P, _P, C.c_size_t, _P],
+    # packed sharing over a prime below 2^256: the 8.18 calls with `pack` after num_dealers
+    "pvw_shamir_shares_packed_wide_host": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, _P, _P, _P, _P],
+    "pvw_shamir_shares_packed_wide_device": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P],
+    "pvw_shamir_shares_packed_wide": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, _P, _P, _P, _P],
+    "pvw_deal_shares_packed_wide": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, _P, C.c_uint32],
+    "pvw_deal_shares_packed_wide_device": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P],
+    "pvw_deal_shares_packed_wide_rs": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, _P, C.c_uint32],
+    "pvw_deal_shares_packed_wide_rs_device": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P],
+    "pvw_shamir_reconstruct_packed_wide": [_P, C.c_uint32, _P, _P, C.c_size_t, C.c_size_t, _P],
     "pvw_shamir_wide_from_limbs_device": [_P, _P, _P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, _P, _P],
     "pvw_shamir_reconstruct_wide_checked_host": [_P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P],
     "pvw_shamir_reconstruct_wide_checked_device": [_P, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P, _P],

@@ -1041,6 +1041,117 @@ def shamir_reconstruct_wide(indices: Sequence[int], shares, plain_modulus: int):
     return res[0] if single else res
 
 
+def _wide_packed_secrets(secrets, pack: int) -> np.ndarray:
+    """rows [D][pack] of ints (or words [D][pack][4]) -> uint64 [D][pack][4], dealer-major"""
+    K = int(pack)
+    if isinstance(secrets, np.ndarray) and secrets.dtype == np.uint64 and secrets.ndim == 3 and secrets.shape[-1] == WIDE_WORDS:
+        se = np.ascontiguousarray(secrets)
+        if K and se.shape[1] != K:
+            raise PvwError(15, f"expected {K} secrets per dealer, got {se.shape[1]}")
+        return se
+    rows = [list(row) for row in secrets]
+    if any(len(row) != K for row in rows):
+        raise PvwError(15, f"expected {K} secrets per dealer")
+    return _wide([v for row in rows for v in row]).reshape(len(rows), K, WIDE_WORDS)
+
+
+def shamir_shares_packed_wide(params: PvwParameters, secrets, pack: int, degree: int, plain_modulus: int,
+                              seeds: Optional[Sequence[bytes]] = None, coeffs=None, host: bool = False) -> np.ndarray:
+    """EXTENSION: shamir_shares_packed over an odd prime plain_modulus < 2^256: secrets [D][pack] (ints, any value:
+    read mod p) sit at the points 0, -1, .., -(pack-1) of dealer d's polynomial of degree <= degree + pack - 1, with `degree`
+    random coefficients drawn as shamir_shares_wide draws them or given as coeffs [D][degree].  Returns uint64 words [D][n][4].
+    On the device (pvw_shamir_shares_packed_wide); host=True: the restatement on the host cores (no GPU).  pack = 1 is
+    shamir_shares_wide bit for bit."""
+    se = _wide_packed_secrets(secrets, pack)
+    D = len(se)
+    sd = _seeds(seeds, D) if seeds is not None else None
+    co = None
+    if coeffs is not None:
+        rows = [list(row) for row in coeffs]
+        if any(len(row) != int(degree) for row in rows) or len(rows) != D:
+            raise PvwError(15, f"expected {D} rows of {int(degree)} coefficients")
+        co = _wide([v for row in rows for v in row]) if int(degree) else None     # degree 0 reads no coefficient
+    out = np.zeros((D, params.n, WIDE_WORDS), dtype=np.uint64)
+    params._call("pvw_shamir_shares_packed_wide" + ("_host" if host else ""), _ptr(se), D, int(pack), int(degree),
+                 _ptr(_wide_modulus(plain_modulus)), _ptr(sd), _ptr(co), _ptr(out))
+    return out
+
+
+def deal_party_shares_packed_wide(secrets, pack: int, degree: int, plain_modulus: int, global_pk: GlobalPublicKey,
+                                  seeds: Optional[Sequence[bytes]] = None, randomness: Optional["DeviceRandomness"] = None,
+                                  limb_bits: int = 52, out_repr: int = REPR_NTT) -> List[List[PvwCiphertext]]:
+    """EXTENSION: deal_party_shares_wide with `pack` secrets per dealer (secrets [D][pack]) in one polynomial: D lists
+    of NL limb ciphertexts carry D * pack wide secrets (pvw_deal_shares_packed_wide).  seeds, `randomness` and the limbs as
+    deal_party_shares_wide; pack = 1 gives its ciphertexts bit for bit."""
+    p = global_pk.params
+    se = _wide_packed_secrets(secrets, pack)
+    D = len(se)
+    NL = shamir_wide_limbs(plain_modulus, limb_bits)
+    V = D * NL
+    pm = _wide_modulus(plain_modulus)
+    c1 = np.zeros((V, p.k, p.L, p.l), dtype=np.uint64)
+    c2 = np.zeros((V, p.n, p.L, p.l), dtype=np.uint64)
+    if randomness is not None:
+        _check_state(p, randomness, seeds)
+        p._call("pvw_deal_shares_packed_wide_rs", _ptr(se), D, int(pack), int(degree), _ptr(pm), int(limb_bits), randomness._h, _ptr(c1),
+                _ptr(c2), out_repr)
+    else:
+        if seeds is None:
+            raise PvwError(1, "deal_party_shares_packed_wide needs one 32-byte seed per limb ciphertext or a DeviceRandomness")
+        sd = _seeds(seeds, V)
+        p._call("pvw_deal_shares_packed_wide", _ptr(se), D, int(pack), int(degree), _ptr(pm), int(limb_bits), _ptr(sd), _ptr(c1), _ptr(c2),
+                out_repr)
+    return [[PvwCiphertext(c1[d * NL + w], c2[d * NL + w], p, out_repr) for w in range(NL)] for d in range(D)]
+
+
+def shamir_reconstruct_packed_wide(indices: Sequence[int], shares, plain_modulus: int, pack: int) -> List[List[int]]:
+    """EXTENSION: the `pack` secrets of each row from the shares of the parties `indices` (at least degree + pack of
+    them, each below plain_modulus - pack), on the host (pvw_shamir_reconstruct_packed_wide; no GPU, no context).  shares: rows
+    [num_rows][len(indices)] of ints, or words [num_rows][len(indices)][4].  Returns [num_rows][pack] ints: row r's value at -j."""
+    idx = _words(indices)
+    if isinstance(shares, np.ndarray) and shares.dtype == np.uint64 and shares.ndim == 3:
+        sh = np.ascontiguousarray(shares)
+    else:
+        rows = [list(row) for row in shares]
+        if any(len(row) != len(idx) for row in rows):
+            raise PvwError(15, f"expected {len(idx)} shares per row")
+        sh = _wide([v for row in rows for v in row]).reshape(len(rows), len(idx), WIDE_WORDS)
+    if sh.shape[1] != len(idx):
+        raise PvwError(15, f"expected {len(idx)} shares per row, got {sh.shape[1]}")
+    K, R = int(pack), sh.shape[0]
+    out = np.zeros((R, max(K, 1), WIDE_WORDS), dtype=np.uint64)
+    L = _ffi.lib()
+    _check(L.pvw_shamir_reconstruct_packed_wide(_ptr(_wide_modulus(plain_modulus)), K, _ptr(idx), _ptr(sh), len(idx), R, _ptr(out)), L)
+    flat = _wide_ints(out)
+    return [flat[r * K:(r + 1) * K] for r in range(R)]
+
+
+def shamir_reconstruct_packed_wide_corrected(params: Optional[PvwParameters], plain_modulus: int, pack: int, degree: int,
+                                             indices: Sequence[int], shares, erased=None, *, host: bool = False,
+                                             layout: str = "secret_major"):
+    """EXTENSION (DESIGN 8.23): the `pack` secrets of each row although up to (len(indices) - degree - pack) // 2 of its shares are
+    wrong (an erased one counts half).  The wide evaluate calls take targets as party indices, so the points -j cannot be named for
+    a wide p: ONE shamir_evaluate_wide_corrected call at polynomial degree degree + pack - 1 evaluates the corrected polynomials at
+    the first degree + pack of `indices` -- corrected shares -- and shamir_reconstruct_packed_wide reads the secrets off them.
+    Returns (secrets [num_rows][pack] as ints, nerr, col_err, err_mask) with the decode's report unchanged; a row reported
+    SHAMIR_UNDECODABLE gives `pack` zeros.  pack = 1 is shamir_reconstruct_wide_corrected (rows of one secret)."""
+    K, t = int(pack), int(degree)
+    if K == 1:
+        sec, nerr, col_err, err_mask = shamir_reconstruct_wide_corrected(params, indices, shares, t, plain_modulus, host=host,
+                                                                         layout=layout, erased=erased)
+        return [[s] for s in sec], nerr, col_err, err_mask
+    if K < 1:
+        raise PvwError(1, "pack must be at least 1")
+    basis = list(indices)[:t + K]
+    if len(basis) < t + K:
+        raise PvwError(1, f"degree {t} with pack {K} needs at least {t + K} shares")
+    values, _, nerr, col_err, err_mask = shamir_evaluate_wide_corrected(params, indices, shares, t + K - 1, plain_modulus, basis, host=host,
+                                                                        layout=layout, erased=erased)
+    sec = shamir_reconstruct_packed_wide(basis, values, plain_modulus, K) if len(values) else []
+    sec = [[0] * K if int(nerr[r]) == SHAMIR_UNDECODABLE else row for r, row in enumerate(sec)]
+    return sec, nerr, col_err, err_mask
+
+
 def shamir_wide_from_limbs_device(params: PvwParameters, limbs, plain_modulus: int, limb_bits: int = 52, *,
                                   layout: str = "limb_major", num_limbs: Optional[int] = None, stream=None):
     """EXTENSION: shamir_wide_from_limbs where the limbs lie (pvw_shamir_wide_from_limbs_device).  limbs is a

@@ -154,6 +154,8 @@ struct Workspace {
   size_t interp_wide_bytes = 0;
   u64* packw = nullptr;      // packed dealing: Lw | zt | w | 1/j! (shamir_packed_words; public, grown by the call)
   size_t packw_bytes = 0;
+  u64* packw_wide = nullptr; // the same over a prime below 2^256 (shamir_packed_wide_words; public, grown by the call)
+  size_t packw_wide_bytes = 0;
   u64* correct = nullptr;    // corrected reconstruction: M | public matrices | syndromes | locators (CorrectLayout; grown by the call)
   size_t correct_bytes = 0;
   u64* correct_wide = nullptr;   // the same over a prime below 2^256 (CorrectWideLayout)
@@ -651,6 +653,7 @@ static void ws_free(Workspace* w) {
   hipFree(w->interp);
   hipFree(w->interp_wide);
   hipFree(w->packw);
+  hipFree(w->packw_wide);
   if (w->correct) hipMemset(w->correct, 0, w->correct_bytes);   // M of the last call, if its wipe did not run
   hipFree(w->correct);
   if (w->correct_wide) hipMemset(w->correct_wide, 0, w->correct_wide_bytes);
@@ -3379,19 +3382,38 @@ struct ShamirWideDeal {
   u32 degree;
   WideMod m;
   u32 limb_bits = 0, num_limbs = 0;
+  u32 pack = 0;           // the packed entry points: secrets per dealer, d_secrets [D][pack][4], and the packed kernel runs
+  const u64* d_packw = nullptr;   // ... on the weights of the call (shamir_packed_wide_prepare)
+  WideMont mm{};          // ... with the constants of the general product
 };
+static size_t shamir_packed_wide_bytes(const pvw_ctx* c, u32 pack) { return shamir_packed_wide_words(pack, c->rowsB()) * 8; }
+// packed_capture_check for the wide weights, a block of their own
+static int32_t packed_wide_capture_check(pvw_ctx* c, hipStream_t s, u32 pack) {
+  return grown_capture_check(c, s, &Workspace::packw_wide_bytes, shamir_packed_wide_bytes(c, pack),
+                             "multi-dealer encrypt under stream capture: run a packed wide call with at least this pack on this stream "
+                             "outside capture first (it sizes the weights), and call pvw_prepare(PVW_PREPARE_MFMA)");
+}
+// once per call: Lw and zt of (p, pack, party range) into the stream's workspace, made on the device; public
+static int32_t shamir_packed_wide_prepare(pvw_ctx* c, Workspace* w, ShamirWideDeal* deal, hipStream_t s) {
+  PVW_TRY(ws_grow(&w->packw_wide, &w->packw_wide_bytes, shamir_packed_wide_bytes(c, deal->pack), s, false));
+  ProfScope ps(c, "shamir_packed_wide_weights", s);
+  PVW_HIP(launch_shamir_packed_wide_weights(w->packw_wide, deal->pack, c->party_lo, c->party_hi, deal->m, deal->mm, s));
+  deal->d_packw = w->packw_wide;
+  return PVW_OK;
+}
 // rows [v0, v0 + nv) of the call (dealers when num_limbs == 0, limb vectors otherwise) into out; `keys` is the source of the
 // call's (piece's) vector 0.  PVW_MAX_PROLOGUE_KEYS dealers per launch; a dealer whose limbs straddle two passes is evaluated
 // in both and stores only the rows of each (the arithmetic is exact).
 static int32_t shamir_wide_enqueue(pvw_ctx* c, const ShamirWideDeal& deal, const DealerKeys& keys, size_t v0, size_t nv, u64* out,
                                    hipStream_t s) {
   if (!nv) return PVW_OK;
-  ProfScope ps(c, "shamir_eval_wide", s);
+  ProfScope ps(c, deal.pack ? "shamir_eval_packed_wide" : "shamir_eval_wide", s);
   const u32 NL = deal.num_limbs, ks = NL ? NL : 1;
   const size_t dlo = v0 / ks, dhi = (v0 + nv - 1) / ks + 1;
   struct OneKey { ChaChaKey key[1]; const RndState* rnd; u64 rnd_off; };
   for (size_t d0 = dlo; d0 < dhi; d0 += PVW_MAX_PROLOGUE_KEYS) {
-    ShamirWideBatch b{};
+    ShamirWidePackedBatch pb{};                                   // the unpacked launch takes its first member alone
+    ShamirWideBatch& b = pb.b;
     b.secrets = deal.d_secrets;
     b.coeffs = deal.d_coeffs;
     b.row_stride = c->n;
@@ -3415,8 +3437,16 @@ static int32_t shamir_wide_enqueue(pvw_ctx* c, const ShamirWideDeal& deal, const
         if (x == 0) { b.rnd = k.rnd; b.rnd_off = k.rnd_off; }
         memset(&k, 0, sizeof k);
       }
-    PVW_HIP(launch_shamir_eval_wide(b, s));
-    memset(&b, 0, sizeof b);
+    if (deal.pack) {
+      pb.pack = deal.pack;
+      pb.Lw = deal.d_packw;
+      pb.zt = deal.d_packw + (size_t)deal.pack * c->rowsB() * 4;
+      pb.mm = deal.mm;
+      PVW_HIP(launch_shamir_eval_packed_wide(pb, s));
+    } else {
+      PVW_HIP(launch_shamir_eval_wide(b, s));
+    }
+    memset(&pb, 0, sizeof pb);
   }
   return PVW_OK;
 }
@@ -3895,7 +3925,8 @@ static int32_t wide_limb_count(const WideMod& m, uint32_t limb_bits, uint32_t* n
   *num_limbs = nl;
   return PVW_OK;
 }
-static int32_t shamir_wide_checks(const pvw_ctx* c, size_t D, uint32_t degree, const uint64_t* p, WideMod* m) {
+// The rules of both wide dealing families.  pack != NULL: the rules of 8.18 first, then the packed ones.
+static int32_t shamir_wide_checks(const pvw_ctx* c, size_t D, uint32_t degree, const uint64_t* p, WideMod* m, const uint32_t* pack = nullptr) {
   if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no dealers");
   if (!p) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   if (!p[1] && !p[2] && !p[3] && p[0] <= c->n)
@@ -3906,6 +3937,18 @@ static int32_t shamir_wide_checks(const pvw_ctx* c, size_t D, uint32_t degree, c
     snprintf(buf, sizeof buf, "degree %u needs more than %u parties", degree, c->n);
     return fail(PVW_ERR_INVALID_PARAMETERS, buf);
   }
+  if (!pack) return PVW_OK;
+  const u64 K = *pack, n = c->n;
+  if (K == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "pack must be at least 1");
+  if (K > PVW_WIDE_MAX_PACK) return fail(PVW_ERR_INVALID_PARAMETERS, "pack must be at most PVW_WIDE_MAX_PACK");
+  if ((u64)degree + K > n) {
+    char buf[128];
+    snprintf(buf, sizeof buf, "degree %u with pack %u needs at least %llu parties", degree, *pack, (unsigned long long)degree + K);
+    return fail(PVW_ERR_INVALID_PARAMETERS, buf);
+  }
+  if (n + K - 1 >= ((u64)1 << 32)) return fail(PVW_ERR_INVALID_PARAMETERS, "n + pack - 1 must be below 2^32");
+  if (!p[1] && !p[2] && !p[3] && p[0] < n + K)
+    return fail(PVW_ERR_INVALID_PARAMETERS, "plain_modulus must be at least n + pack (the points 1..n and 0, -1, .., -(pack-1) are distinct)");
   return PVW_OK;
 }
 
@@ -3939,6 +3982,86 @@ int32_t pvw_shamir_shares_wide_host(const pvw_ctx* c, const uint64_t* secrets, s
   }
   volatile u64* va = a.data();                               // the coefficients are as secret as the secret
   for (size_t j = 0; j < a.size(); ++j) va[j] = 0;
+  return PVW_OK;
+}
+
+// the packed contract on the host cores, by the definition: the weights L_j(i + 1) and Z(i + 1) once per call (one
+// inversion, of (K-1)!), then per share t steps and K + 1 products.  Writes all n columns.
+int32_t pvw_shamir_shares_packed_wide_host(const pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                           const uint64_t* plain_modulus, const uint8_t* seeds, const uint64_t* coeffs,
+                                           uint64_t* shares_out) {
+  if (!c || !secrets || !shares_out || !plain_modulus || (degree && !seeds && !coeffs)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  WideMod m;
+  PVW_TRY(shamir_wide_checks(c, num_dealers, degree, plain_modulus, &m, &pack));
+  const u32 n = c->n, t = degree, K = pack;
+  const u64 zero[4] = {0, 0, 0, 0};
+  Wide one, ones, f, inv, fj, plain;
+  wide_small(one, 1);
+  wide_reduce(ones, one, m);                                 // 1, scaled
+  // w_j = (-1)^j / (j! (K-1-j)!), plain
+  std::vector<u64> invf((size_t)K * 4), wj((size_t)K * 4);
+  wide_set(f, ones);
+  for (u32 j = 2; j < K; ++j) {
+    wide_small(fj, j);
+    wide_mulmod(f, f, fj, m);
+  }
+  wide_invmod(inv, f, plain_modulus, m);
+  for (u32 j = K - 1;; --j) {
+    wide_set(&invf[(size_t)j * 4], inv);                     // 1 / j!, scaled
+    if (j == 0) break;
+    wide_small(fj, j);
+    wide_mulmod(inv, inv, fj, m);
+  }
+  for (u32 j = 0; j < K; ++j) {
+    Wide v;
+    wide_unscale(plain, &invf[(size_t)(K - 1 - j) * 4], m);
+    wide_mulmod(v, &invf[(size_t)j * 4], plain, m);
+    if (j & 1) wide_negmod(v, m);
+    wide_unscale(&wj[(size_t)j * 4], v, m);
+  }
+  // Lw[j][i] = L_j(i + 1) and zt[i] = Z(i + 1), plain
+  std::vector<u64> Lw((size_t)K * n * 4), zt((size_t)n * 4), sufv((size_t)K * 4);
+  for (u32 i = 0; i < n; ++i) {
+    u64 suf[4], pre[4];
+    wide_set(suf, ones);
+    for (u32 j = K; j-- > 0;) {
+      wide_set(&sufv[(size_t)j * 4], suf);
+      wide_step(suf, i + 1 + j, zero, m);                    // i + K < 2^32
+    }
+    wide_unscale(&zt[(size_t)i * 4], suf, m);
+    wide_set(pre, ones);
+    for (u32 j = 0; j < K; ++j) {
+      Wide v;
+      wide_unscale(plain, pre, m);
+      wide_mulmod(v, &sufv[(size_t)j * 4], plain, m);
+      wide_mulmod(v, v, &wj[(size_t)j * 4], m);
+      wide_unscale(&Lw[((size_t)j * n + i) * 4], v, m);
+      wide_step(pre, i + 1 + j, zero, m);
+    }
+  }
+  std::vector<u64> a(((size_t)t + 1) * 4), sec((size_t)K * 4);
+  for (size_t d = 0; d < num_dealers; ++d) {
+    for (u32 j = 0; j < K; ++j) wide_reduce(&sec[(size_t)j * 4], secrets + (d * K + j) * 4, m);
+    for (u32 j = 1; j <= t; ++j) {
+      if (coeffs) wide_reduce(&a[(size_t)j * 4], coeffs + (d * t + (j - 1)) * 4, m);
+      else wide_draw_scaled(make_key(seeds + d * 32), PVW_DOM_SHAMIR, j, m, *(u64(*)[4]) & a[(size_t)j * 4]);
+    }
+    for (u32 i = 0; i < n; ++i) {
+      u64 r[4] = {0, 0, 0, 0};
+      for (u32 e = t; e >= 1; --e) wide_step(r, i + 1, *(const u64(*)[4]) & a[(size_t)e * 4], m);   // a_1 + a_2 x + ... + a_t x^(t-1)
+      Wide acc, prod;
+      wide_mulmod(acc, r, &zt[(size_t)i * 4], m);
+      for (u32 j = 0; j < K; ++j) {
+        wide_mulmod(prod, &sec[(size_t)j * 4], &Lw[((size_t)j * n + i) * 4], m);
+        wide_addmod(acc, prod, m);
+      }
+      wide_unscale(shares_out + (d * n + i) * 4, acc, m);
+    }
+  }
+  volatile u64* va = a.data();                               // the coefficients are as secret as the secrets
+  for (size_t j = 0; j < a.size(); ++j) va[j] = 0;
+  volatile u64* vs = sec.data();
+  for (size_t j = 0; j < sec.size(); ++j) vs[j] = 0;
   return PVW_OK;
 }
 
@@ -4038,42 +4161,152 @@ int32_t pvw_shamir_reconstruct_wide(const uint64_t* plain_modulus, const uint64_
   return PVW_OK;
 }
 
-// the front of the two device-side shares calls
+// Lagrange at 0, -1, .., -(pack-1) from the points x_i = indices[i] + 1: the weight of point i at -k is
+// prod_{j != i}(x_j + k) / (x_j - x_i).  The denominators do not depend on k: one inversion per point; the numerators of one k
+// come from prefix and suffix products of the x_j + k.  Then pack dot products per row.
+int32_t pvw_shamir_reconstruct_packed_wide(const uint64_t* plain_modulus, uint32_t pack, const uint64_t* indices, const uint64_t* shares,
+                                           size_t count, size_t num_rows, uint64_t* out) {
+  if (!plain_modulus || !indices || ((!shares || !out) && num_rows)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (count == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no shares");
+  WideMod m;
+  PVW_TRY(wide_modulus_check(plain_modulus, &m));
+  if (pack == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "pack must be at least 1");
+  const bool small_p = !plain_modulus[1] && !plain_modulus[2] && !plain_modulus[3];
+  {
+    u64 pw[4];
+    wide_set(pw, plain_modulus);
+    std::vector<u64> sorted(indices, indices + count);
+    std::sort(sorted.begin(), sorted.end());
+    for (size_t i = 0; i < count; ++i) {
+      if (i && sorted[i] == sorted[i - 1]) return fail(PVW_ERR_INVALID_PARAMETERS, "duplicate party index");
+      if (sorted[i] == ~(u64)0 || (small_p && sorted[i] >= plain_modulus[0] - 1))
+        return fail(PVW_ERR_INVALID_PARAMETERS, "party index must be below plain_modulus - 1");
+      u64 top[4] = {sorted[i] + pack, 0, 0, 0};            // index + pack as a wide integer
+      top[1] = top[0] < sorted[i];
+      if (!wide_less(top, pw)) return fail(PVW_ERR_INVALID_PARAMETERS, "party index must be below plain_modulus - pack");
+    }
+  }
+  Wide one, ones;
+  wide_small(one, 1);
+  wide_reduce(ones, one, m);
+  // 1 / prod_{j != i}(x_j - x_i), scaled
+  std::vector<u64> dinv(count * 4);
+  for (size_t i = 0; i < count; ++i) {
+    Wide den, f;
+    wide_set(den, ones);
+    bool neg = false;
+    for (size_t j = 0; j < count; ++j) {
+      if (j == i) continue;
+      const u64 xj = indices[j] + 1, xi = indices[i] + 1;
+      wide_small(f, xj > xi ? xj - xi : xi - xj);
+      if (xj < xi) neg = !neg;
+      wide_mulmod(den, den, f, m);
+    }
+    wide_invmod(&dinv[i * 4], den, plain_modulus, m);
+    if (neg) wide_negmod(&dinv[i * 4], m);
+  }
+  // wts[k][i], plain and below p
+  std::vector<u64> wts((size_t)pack * count * 4), sufv(count * 4);
+  for (u32 k = 0; k < pack; ++k) {
+    auto factor = [&](size_t j, Wide f) {                  // x_j + k, at most 2^64 + pack - 2
+      const u64 xj = indices[j] + 1;
+      f[0] = xj + k;
+      f[1] = f[0] < xj;
+      f[2] = f[3] = 0;
+    };
+    Wide suf, pre, f, plain, v;
+    wide_set(suf, ones);
+    for (size_t j = count; j-- > 0;) {
+      wide_set(&sufv[j * 4], suf);
+      factor(j, f);
+      wide_mulmod(suf, suf, f, m);
+    }
+    wide_set(pre, ones);
+    for (size_t i = 0; i < count; ++i) {
+      wide_unscale(plain, pre, m);
+      wide_mulmod(v, &sufv[i * 4], plain, m);
+      wide_unscale(plain, &dinv[i * 4], m);
+      wide_mulmod(v, v, plain, m);
+      wide_unscale(&wts[((size_t)k * count + i) * 4], v, m);
+      factor(i, f);
+      wide_mulmod(pre, pre, f, m);
+    }
+  }
+  for (size_t s = 0; s < num_rows; ++s) {
+    std::vector<u64> y(count * 4);
+    for (size_t i = 0; i < count; ++i) wide_reduce(&y[i * 4], shares + (s * count + i) * 4, m);
+    for (u32 k = 0; k < pack; ++k) {
+      Wide acc, prod;
+      wide_small(acc, 0);
+      for (size_t i = 0; i < count; ++i) {
+        wide_mulmod(prod, &y[i * 4], &wts[((size_t)k * count + i) * 4], m);
+        wide_addmod(acc, prod, m);
+      }
+      wide_unscale(out + (s * pack + k) * 4, acc, m);
+    }
+    volatile u64* vy = y.data();
+    for (size_t j = 0; j < y.size(); ++j) vy[j] = 0;
+  }
+  return PVW_OK;
+}
+
+// the front of the device-side shares calls.  pack != NULL: the packed forms
 static int32_t shamir_wide_shares_checks(const pvw_ctx* c, const uint64_t* secrets, size_t D, uint32_t degree, const uint64_t* p,
-                                         const uint8_t* seeds, const uint64_t* coeffs, const uint64_t* shares, WideMod* m) {
+                                         const uint8_t* seeds, const uint64_t* coeffs, const uint64_t* shares, WideMod* m,
+                                         const uint32_t* pack = nullptr) {
   if (!c || !secrets || !shares || !p || (degree && !seeds && !coeffs)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  return shamir_wide_checks(c, D, degree, p, m);
+  return shamir_wide_checks(c, D, degree, p, m, pack);
 }
 
-// device pointers (seeds and plain_modulus stay HOST pointers): no workspace, nothing allocated, may be captured
-int32_t pvw_shamir_shares_wide_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t degree,
-                                      const uint64_t* plain_modulus, const uint8_t* seeds, const uint64_t* d_coeffs, uint64_t* d_shares,
-                                      void* stream) {
+// device pointers (seeds and plain_modulus stay HOST pointers): no workspace, nothing allocated, may be captured.
+// pack != NULL (the packed form): secrets [D][*pack][4]; the weights once per call into the stream's workspace, then
+// the packed kernel per launch of dealers
+static int32_t shamir_wide_shares_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, const uint32_t* pack, uint32_t degree,
+                                         const uint64_t* plain_modulus, const uint8_t* seeds, const uint64_t* d_coeffs, uint64_t* d_shares,
+                                         void* stream) {
   WideMod m;
-  PVW_TRY(shamir_wide_shares_checks(c, d_secrets, num_dealers, degree, plain_modulus, seeds, d_coeffs, d_shares, &m));
-  PVW_TRY(ensure_device(c));
-  const ShamirWideDeal deal{d_secrets, degree ? d_coeffs : nullptr, degree, m};
-  return shamir_wide_enqueue(c, deal, DealerKeys::host(seeds), 0, num_dealers, d_shares, call_stream(c, stream));
+  PVW_TRY(shamir_wide_shares_checks(c, d_secrets, num_dealers, degree, plain_modulus, seeds, d_coeffs, d_shares, &m, pack));
+  ShamirWideDeal deal{d_secrets, degree ? d_coeffs : nullptr, degree, m};
+  const DealerKeys keys = DealerKeys::host(seeds);
+  if (!pack) {
+    PVW_TRY(ensure_device(c));
+    return shamir_wide_enqueue(c, deal, keys, 0, num_dealers, d_shares, call_stream(c, stream));
+  }
+  deal.pack = *pack;
+  deal.mm = make_wide_mont(plain_modulus);
+  // the caller's stream is checked before the context initialises its device (pvw_shamir_reconstruct_checked_device)
+  auto sized = [&](hipStream_t s) { return packed_wide_capture_check(c, s, *pack); };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
+    PVW_TRY(shamir_packed_wide_prepare(c, w, &deal, s));
+    return shamir_wide_enqueue(c, deal, keys, 0, num_dealers, d_shares, s);
+  });
 }
 
-// host buffers: the dealers go up in bounded pieces, each piece's shares come down, and the staging is cleared when the call ends
-int32_t pvw_shamir_shares_wide(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t degree, const uint64_t* plain_modulus,
-                               const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out) {
+// host buffers: the dealers go up in bounded pieces (secrets [*pack][4] each), each piece's shares come down, and the staging is
+// cleared when the call ends.  pack != NULL: the weights once, in front
+static int32_t shamir_wide_shares_stage(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, const uint32_t* pack, uint32_t degree,
+                                        const uint64_t* plain_modulus, const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out) {
   WideMod m;
-  PVW_TRY(shamir_wide_shares_checks(c, secrets, num_dealers, degree, plain_modulus, seeds, coeffs, shares_out, &m));
+  PVW_TRY(shamir_wide_shares_checks(c, secrets, num_dealers, degree, plain_modulus, seeds, coeffs, shares_out, &m, pack));
   PVW_TRY(ensure_device(c));
-  const size_t n = c->n, t = degree, rB = c->rowsB();
-  const size_t per = chunk_1gib((n + (coeffs ? t : 0) + 1) * 32, num_dealers);
+  const size_t n = c->n, t = degree, K = pack ? *pack : 1, rB = c->rowsB();
+  const size_t per = chunk_1gib((n + (coeffs ? t : 0) + K) * 32, num_dealers);
   Scratch sc;
-  const size_t r_se = sc.add(per * 32), r_co = sc.add(coeffs ? per * t * 32 : 0), r_sh = sc.add(per * n * 32);
+  const size_t r_se = sc.add(per * K * 32), r_co = sc.add(coeffs ? per * t * 32 : 0), r_sh = sc.add(per * n * 32);
   return host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
     sc.secret(w, r_se, r_sh);
     u64 *d_se = sc.at(r_se), *d_co = coeffs && t ? sc.at(r_co) : nullptr, *d_sh = sc.at(r_sh);
-    const ShamirWideDeal deal{d_se, d_co, degree, m};
+    ShamirWideDeal deal{d_se, d_co, degree, m};
+    if (pack) {
+      deal.pack = *pack;
+      deal.mm = make_wide_mont(plain_modulus);
+      PVW_TRY(shamir_packed_wide_prepare(c, w, &deal, w->stream));
+    }
     for (size_t d0 = 0; d0 < num_dealers; d0 += per) {
       const size_t cnt = (num_dealers - d0) < per ? (num_dealers - d0) : per;
-      PVW_HIP(hipMemcpyAsync(d_se, secrets + d0 * 4, cnt * 32, hipMemcpyHostToDevice, w->stream));
+      PVW_HIP(hipMemcpyAsync(d_se, secrets + d0 * K * 4, cnt * K * 32, hipMemcpyHostToDevice, w->stream));
       if (d_co) PVW_HIP(hipMemcpyAsync(d_co, coeffs + d0 * t * 4, cnt * t * 32, hipMemcpyHostToDevice, w->stream));
       PVW_TRY(shamir_wide_enqueue(c, deal, DealerKeys::host(seeds).from(d0), 0, cnt, d_sh, w->stream));
       // a sharded context writes its own columns only
@@ -4085,51 +4318,81 @@ int32_t pvw_shamir_shares_wide(pvw_ctx* c, const uint64_t* secrets, size_t num_d
   });
 }
 
+int32_t pvw_shamir_shares_wide_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t degree,
+                                      const uint64_t* plain_modulus, const uint8_t* seeds, const uint64_t* d_coeffs, uint64_t* d_shares,
+                                      void* stream) {
+  return shamir_wide_shares_device(c, d_secrets, num_dealers, nullptr, degree, plain_modulus, seeds, d_coeffs, d_shares, stream);
+}
+int32_t pvw_shamir_shares_wide(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t degree, const uint64_t* plain_modulus,
+                               const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out) {
+  return shamir_wide_shares_stage(c, secrets, num_dealers, nullptr, degree, plain_modulus, seeds, coeffs, shares_out);
+}
+int32_t pvw_shamir_shares_packed_wide_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                             const uint64_t* plain_modulus, const uint8_t* seeds, const uint64_t* d_coeffs,
+                                             uint64_t* d_shares, void* stream) {
+  return shamir_wide_shares_device(c, d_secrets, num_dealers, &pack, degree, plain_modulus, seeds, d_coeffs, d_shares, stream);
+}
+int32_t pvw_shamir_shares_packed_wide(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                      const uint64_t* plain_modulus, const uint8_t* seeds, const uint64_t* coeffs, uint64_t* shares_out) {
+  return shamir_wide_shares_stage(c, secrets, num_dealers, &pack, degree, plain_modulus, seeds, coeffs, shares_out);
+}
+
 // The deal: pvw_encrypt_multi* on D * NL vectors whose scalars are the limb planes, made pass by pass in the share scratch.
 static int32_t deal_wide_front(pvw_ctx* c, const uint64_t* secrets, size_t D, uint32_t degree, const uint64_t* p, uint32_t limb_bits,
                                const DealerKeys& keys, const uint64_t* c1, const uint64_t* c2, bool device, uint32_t out_repr,
-                               ShamirWideDeal* deal) {
+                               ShamirWideDeal* deal, const uint32_t* pack) {
   if (!c || !secrets || !p || keys.missing() || (device ? (!c1 && c->rowsA()) || (!c2 && c->rowsB()) : !c1 || !c2))
     return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   PVW_TRY(encrypt_multi_checks(c, D, c->n, out_repr));
   WideMod m;
-  PVW_TRY(shamir_wide_checks(c, D, degree, p, &m));
+  PVW_TRY(shamir_wide_checks(c, D, degree, p, &m, pack));
   u32 nl = 0;
   PVW_TRY(wide_limb_count(m, limb_bits, &nl));
   *deal = ShamirWideDeal{secrets, nullptr, degree, m, limb_bits, nl};
+  if (pack) {
+    deal->pack = *pack;
+    deal->mm = make_wide_mont(p);
+  }
   return PVW_OK;
 }
+// pack != NULL (pvw_deal_shares_packed_wide*): secrets [D][*pack][4], the weights once per call and the packed kernel,
+// whatever *pack; under capture the caller's stream is checked before the context initialises its device
 static int32_t deal_wide_device(pvw_ctx* c, const uint64_t* d_secrets, size_t D, uint32_t degree, const uint64_t* p, uint32_t limb_bits,
-                                const DealerKeys& keys, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream) {
+                                const DealerKeys& keys, uint64_t* d_c1, uint64_t* d_c2, uint32_t out_repr, void* stream,
+                                const uint32_t* pack = nullptr) {
   ShamirWideDeal wd;
-  PVW_TRY(deal_wide_front(c, d_secrets, D, degree, p, limb_bits, keys, d_c1, d_c2, true, out_repr, &wd));
+  PVW_TRY(deal_wide_front(c, d_secrets, D, degree, p, limb_bits, keys, d_c1, d_c2, true, out_repr, &wd, pack));
   ShamirDeal deal{nullptr, nullptr, degree, Mod{}, 0};
   deal.wide = &wd;
   const size_t V = D * wd.num_limbs;
+  if (pack && stream) PVW_TRY(packed_wide_capture_check(c, (hipStream_t)stream, *pack));
   return device_call(c, stream, [&](hipStream_t s) -> int32_t {
                        PVW_TRY(keys.checks(c));
+                       if (pack) PVW_TRY(packed_wide_capture_check(c, s, *pack));
                        return deal_capture_check(c, s, V);
                      },
                      [&](Workspace* w, hipStream_t s) -> int32_t {
                        PVW_TRY(ws_share_buffer(c, w));
                        deal_mark(w, V);
+                       if (pack) PVW_TRY(shamir_packed_wide_prepare(c, w, &wd, s));
                        return encrypt_multi_enqueue(c, w, nullptr, keys, V, d_c1, d_c2, out_repr, s, &deal);
                      });
 }
 // host buffers, staged in pieces of whole dealers (<= ~512 MiB of ciphertext), so that every piece starts on a dealer's first
 // vector and its keys are the piece's own
 static int32_t deal_wide_host(pvw_ctx* c, const uint64_t* secrets, size_t D, uint32_t degree, const uint64_t* p, uint32_t limb_bits,
-                              const DealerKeys& keys, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr) {
+                              const DealerKeys& keys, uint64_t* c1_out, uint64_t* c2_out, uint32_t out_repr,
+                              const uint32_t* pack = nullptr) {
   ShamirWideDeal wd;
-  PVW_TRY(deal_wide_front(c, secrets, D, degree, p, limb_bits, keys, c1_out, c2_out, false, out_repr, &wd));
+  PVW_TRY(deal_wide_front(c, secrets, D, degree, p, limb_bits, keys, c1_out, c2_out, false, out_repr, &wd, pack));
   PVW_TRY(ensure_device(c));
   PVW_TRY(keys.checks(c));
-  const size_t P = c->poly(), rA = c->rowsA(), rB = c->rowsB(), n = c->n, NL = wd.num_limbs;
-  size_t per = stage_budget() / 2 / (NL * (rA + rB) * P * 8 + 32);
+  const size_t P = c->poly(), rA = c->rowsA(), rB = c->rowsB(), n = c->n, NL = wd.num_limbs, K = pack ? *pack : 1;   // K * 4 words a dealer
+  size_t per = stage_budget() / 2 / (NL * (rA + rB) * P * 8 + K * 32);
   if (per < 1) per = 1;
   if (per > D) per = D;
   Scratch sc;
-  const size_t r_in = sc.add(per * 32), r_c1 = sc.add(per * NL * rA * P * 8), r_c2 = sc.add(per * NL * rB * P * 8);
+  const size_t r_in = sc.add(per * K * 32), r_c1 = sc.add(per * NL * rA * P * 8), r_c2 = sc.add(per * NL * rB * P * 8);
   return host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
     PVW_TRY(ws_share_buffer(c, w));
@@ -4140,9 +4403,10 @@ static int32_t deal_wide_host(pvw_ctx* c, const uint64_t* secrets, size_t D, uin
     wd.d_secrets = d_in;
     ShamirDeal deal{nullptr, nullptr, degree, Mod{}, 0};
     deal.wide = &wd;
+    if (pack) PVW_TRY(shamir_packed_wide_prepare(c, w, &wd, w->stream));
     for (size_t d0 = 0; d0 < D; d0 += per) {
       const size_t cnt = (D - d0) < per ? (D - d0) : per, nvec = cnt * NL;
-      PVW_HIP(hipMemcpyAsync(d_in, secrets + d0 * 4, cnt * 32, hipMemcpyHostToDevice, w->stream));
+      PVW_HIP(hipMemcpyAsync(d_in, secrets + d0 * K * 4, cnt * K * 32, hipMemcpyHostToDevice, w->stream));
       PVW_TRY(encrypt_multi_enqueue(c, w, nullptr, keys.piece(d0 * NL), nvec, d_c1, d_c2, out_repr, w->stream, &deal));
       for (size_t v = 0; v < nvec; ++v) {
         // a sharded context writes its rows at their global positions inside each vector's block
@@ -4172,6 +4436,29 @@ int32_t pvw_deal_shares_wide_rs_device(pvw_ctx* c, const uint64_t* d_secrets, si
                                        const uint64_t* plain_modulus, uint32_t limb_bits, void* handle, uint64_t* d_c1, uint64_t* d_c2,
                                        uint32_t out_repr, void* stream) {
   return deal_wide_device(c, d_secrets, num_dealers, degree, plain_modulus, limb_bits, DealerKeys::state(handle), d_c1, d_c2, out_repr, stream);
+}
+
+int32_t pvw_deal_shares_packed_wide(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                    const uint64_t* plain_modulus, uint32_t limb_bits, const uint8_t* seeds, uint64_t* c1_out,
+                                    uint64_t* c2_out, uint32_t out_repr) {
+  return deal_wide_host(c, secrets, num_dealers, degree, plain_modulus, limb_bits, DealerKeys::host(seeds), c1_out, c2_out, out_repr, &pack);
+}
+int32_t pvw_deal_shares_packed_wide_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                           const uint64_t* plain_modulus, uint32_t limb_bits, const uint8_t* seeds, uint64_t* d_c1,
+                                           uint64_t* d_c2, uint32_t out_repr, void* stream) {
+  return deal_wide_device(c, d_secrets, num_dealers, degree, plain_modulus, limb_bits, DealerKeys::host(seeds), d_c1, d_c2, out_repr, stream,
+                          &pack);
+}
+int32_t pvw_deal_shares_packed_wide_rs(pvw_ctx* c, const uint64_t* secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                       const uint64_t* plain_modulus, uint32_t limb_bits, void* handle, uint64_t* c1_out, uint64_t* c2_out,
+                                       uint32_t out_repr) {
+  return deal_wide_host(c, secrets, num_dealers, degree, plain_modulus, limb_bits, DealerKeys::state(handle), c1_out, c2_out, out_repr, &pack);
+}
+int32_t pvw_deal_shares_packed_wide_rs_device(pvw_ctx* c, const uint64_t* d_secrets, size_t num_dealers, uint32_t pack, uint32_t degree,
+                                              const uint64_t* plain_modulus, uint32_t limb_bits, void* handle, uint64_t* d_c1,
+                                              uint64_t* d_c2, uint32_t out_repr, void* stream) {
+  return deal_wide_device(c, d_secrets, num_dealers, degree, plain_modulus, limb_bits, DealerKeys::state(handle), d_c1, d_c2, out_repr, stream,
+                          &pack);
 }
 
 // SELF-TEST: the kernel's Horner step on the device, out = (acc x + add) mod p

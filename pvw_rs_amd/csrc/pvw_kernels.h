@@ -286,6 +286,20 @@ struct ShamirWideBatch {
   u32 key_stride;
 };
 hipError_t launch_shamir_eval_wide(const ShamirWideBatch& b, hipStream_t s);
+// packed dealing: the batch above with secrets [*][pack][4], and the weights.  A type of its own, so the unpacked
+// kernel keeps the arguments it had.
+struct ShamirWidePackedBatch {
+  ShamirWideBatch b;
+  u32 pack;             // >= 1
+  const u64* Lw;        // [pack][party_hi - party_lo][4], times 2^256 mod p
+  const u64* zt;        // [party_hi - party_lo][4], likewise
+  WideMont mm;          // the constants of the general product
+};
+hipError_t launch_shamir_eval_packed_wide(const ShamirWidePackedBatch& b, hipStream_t s);
+// The weights of packed wide shares, public: Lw [pack][cols][4] | zt [cols][4] | w R^3 [pack][4] | 1/j! [pack][4], cols = party_hi - party_lo.
+// party_hi + pack - 1 < 2^32 and party_hi + pack <= p.
+inline size_t shamir_packed_wide_words(size_t pack, size_t cols) { return 4 * ((pack + 1) * cols + 2 * pack); }
+hipError_t launch_shamir_packed_wide_weights(u64* ws, u32 pack, u32 party_lo, u32 party_hi, const WideMod& m, const WideMont& mm, hipStream_t s);
 // out[i] = (acc[i] x[i] + add[i]) mod p by the kernel's own step; acc, add < p, x < 2^32 (pvw_selftest_shamir_wide_step)
 hipError_t launch_shamir_wide_step(const WideMod& m, const u64* acc, const u64* x, const u64* add, size_t count, u64* out, hipStream_t s);
 

@@ -2410,4 +2410,222 @@ hipError_t launch_shamir_evaluate_finish_wide(const ShamirEvalFinishWide& f, hip
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------ packed shares over a prime below 2^256
+// f_d(x) = sum_{j<K} s_{d,j} L_j(x) + Z(x) R_d(x) with R_d = a_{d,1} + ... + a_{d,t} x^(t-1): the frame of shamir_eval_wide_kernel
+// (its grid, 256 parties per workgroup, LDS chunks of SHW_JC terms, limb epilogue) as a text of its own at the END of this file,
+// so that the kernel of 8.18 and everything behind it keep their code and their place in the code object (8.23 says what a
+// shared template body measured).  The Horner loop runs over a_t .. a_1 alone (no e = 0 term) and leaves R_d(x), shifted back to
+// a plain value below p.  The K secrets are staged in LDS like coefficients, 256 per chunk, but plain and below p; each is
+// multiplied with the lane's Lw[j][party] (stored times 2^256) by wide_mul_full and added by wide_acc_add into ONE unreduced
+// accumulator below p 2^256 (the invariant of shamir_tile_product_wide), which starts as R_d(x) zt[party]; SHW_PF weights are in
+// flight ahead of their products.  ONE wide_redc gives the share.
+#define SHW_PF 4     // weights loaded ahead of their products
+
+// grid and block of shamir_eval_wide_kernel
+__global__ __launch_bounds__(256) void shamir_eval_packed_wide_kernel(ShamirWidePackedBatch args) {
+  const ShamirWideBatch& b = args.b;
+  __shared__ u64 coef[SHW_JC][4];                  // 8 KiB: the chunk's coefficients, scaled, below pn
+  __shared__ u32 keyw[8];
+  const u32 tid = threadIdx.x;
+  const WideMod m = b.m;
+  const u32 t = b.degree, nt = t;                  // a_t .. a_1: the secrets come through the weights
+  const u32 dx = blockIdx.y, d = b.d_lo + dx;
+  const u32 col = blockIdx.x * 256 + tid;
+  const u32 party = b.party_lo + col;
+  const bool live = col < b.party_hi - b.party_lo;
+  const bool drawn = b.coeffs == nullptr && t != 0;
+  if (drawn && tid == 0) {
+    ChaChaKey k;
+    if (b.rnd) k = call_seed(b.rnd->seed, b.rnd->counter + b.rnd_off + (u64)dx * b.key_stride);   // derived when the kernel runs
+    else k = b.key[dx];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) keyw[i] = k.w[i];
+  }
+  __syncthreads();
+  const u32 x = live ? party + 1 : 1;              // x <= n < 2^32
+  u64 acc[4] = {0, 0, 0, 0};
+  const u32 nchunks = (nt + SHW_JC - 1) / SHW_JC;
+  for (u32 c = 0; c < nchunks; ++c) {
+    // ---- staging: slot tid holds term e = t - c * SHW_JC - tid, the terms in the order Horner takes them ----
+    const u32 first = c * SHW_JC;                  // terms taken before this chunk
+    u64 a[4] = {0, 0, 0, 0};
+    if (first + tid < nt) {
+      const u32 e = t - first - tid;               // 1 .. t
+      if (drawn) {
+        ChaChaKey k;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) k.w[i] = keyw[i];
+        wide_draw_scaled(k, DOM_SHAMIR, e, m, a);
+      } else {
+        wide_reduce_scaled(b.coeffs + ((size_t)d * t + (e - 1)) * 4, m, a);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) coef[tid][i] = a[i];
+    __syncthreads();
+    const u32 cnt = nt - first < SHW_JC ? nt - first : SHW_JC;
+    for (u32 jj = 0; jj < cnt; ++jj) {
+      u64 v[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = coef[jj][i];
+      wide_step(acc, x, v, m);
+    }
+    __syncthreads();
+  }
+  {
+    const WideMont mm = args.mm;
+    const u32 K = args.pack, cols = b.party_hi - b.party_lo;
+    const u32 lc = live ? col : 0;                 // a lane past the range walks column 0 and stores nothing
+    wide_shr(acc, m.shift);                        // R_d(x), plain and below p
+    u32 T[16], P[16];
+    {
+      u64 z[4];
+      wide_ld(args.zt + (size_t)lc * 4, z);
+      wide_mul_full(acc, z, T);                    // acc < p, z < 2^256: below p 2^256
+    }
+    for (u32 c0 = 0; c0 < K; c0 += SHW_JC) {
+      u64 a[4] = {0, 0, 0, 0};
+      if (c0 + tid < K) {
+        wide_reduce_scaled(b.secrets + ((size_t)d * K + c0 + tid) * 4, m, a);
+        wide_shr(a, m.shift);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) coef[tid][i] = a[i];
+      __syncthreads();
+      const u32 cnt = K - c0 < SHW_JC ? K - c0 : SHW_JC;
+      const u64* lw = args.Lw + ((size_t)c0 * cols + lc) * 4;
+      for (u32 j0 = 0; j0 < cnt; j0 += SHW_PF) {
+        u64 w[SHW_PF][4];
+#pragma unroll
+        for (u32 q = 0; q < SHW_PF; ++q) {
+          const u32 jj = j0 + q < cnt ? j0 + q : cnt - 1;
+          wide_ld(lw + (size_t)jj * cols * 4, w[q]);
+        }
+#pragma unroll
+        for (u32 q = 0; q < SHW_PF; ++q) {
+          if (j0 + q < cnt) {                      // uniform
+            u64 v[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = coef[j0 + q][i];
+            wide_mul_full(v, w[q], P);             // v < p, w < 2^256
+            wide_acc_add(T, P, mm);
+          }
+        }
+      }
+      __syncthreads();
+    }
+    wide_redc(T, mm, acc);                         // the share, below p
+  }
+  if (!live) return;
+  if (b.num_limbs == 0) {
+    u64* o = b.out + ((size_t)d * b.row_stride + party) * 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = acc[i];
+    return;
+  }
+  const u64 mask = ((u64)1 << b.limb_bits) - 1;
+  for (u32 w = 0; w < b.num_limbs; ++w) {
+    const u64 v = (u64)d * b.num_limbs + w;
+    if (v >= b.v0 && v < (u64)b.v0 + b.nv) b.out[(size_t)(v - b.v0) * b.row_stride + party] = acc[0] & mask;
+    wide_shr(acc, b.limb_bits);                    // limb_bits < 64
+  }
+}
+
+hipError_t launch_shamir_eval_packed_wide(const ShamirWidePackedBatch& a, hipStream_t s) {
+  const ShamirWideBatch& b = a.b;
+  if (b.nd == 0 || b.party_hi <= b.party_lo || a.pack == 0) return hipSuccess;
+  shamir_eval_packed_wide_kernel<<<dim3((b.party_hi - b.party_lo + 255) / 256, b.nd), dim3(256), 0, s>>>(a);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------ the weights of packed wide shares
+// shamir_packed_basis_kernel and shamir_packed_weights_kernel with elements of four words.  Everything stored is in Montgomery
+// form (times R = 2^256), as 8.19 stores its weights.  One lane walks the factorials and makes the ONE inversion, of (K-1)!; the
+// workgroup then forms w_j = (-1)^j / (j! (K-1-j)!) and stores w_j R^3: a column's entry is suffix x prefix, two plain values
+// below p, so REDC(REDC(suffix prefix) w_j R^3) = suffix prefix w_j R is the entry at the cost of one wide_mul.  The factors
+// x + m <= n + K - 1 < 2^32 go into suffix and prefix by wide_step.
+__global__ __launch_bounds__(256) void shamir_packed_wide_basis_kernel(u64* w3, u64* invf, u32 K, WideMont mm) {
+  if (threadIdx.x == 0) {
+    u64 f[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f[i] = mm.one[i];
+    for (u32 j = 2; j < K; ++j) {                                   // (K-1)! R, K - 1 < p
+      const u64 jj[4] = {j, 0, 0, 0};
+      wide_mul(jj, f, mm, f);                                       // j (f R) mod p: stays in Montgomery form
+    }
+    u64 inv[4];
+    wide_mont_inv(f, mm, inv);
+    for (u32 j = K - 1;; --j) {
+      wide_st(invf + (size_t)j * 4, inv);                           // R / j!
+      if (j == 0) break;
+      const u64 jj[4] = {j, 0, 0, 0};
+      wide_mul(jj, inv, mm, inv);
+    }
+  }
+  __syncthreads();
+  for (u32 j = threadIdx.x; j < K; j += 256) {
+    u64 a[4], c[4];
+    wide_ld(invf + (size_t)j * 4, a);
+    wide_ld(invf + (size_t)(K - 1 - j) * 4, c);
+    wide_mont_mul(a, c, mm, a);                                     // R / (j! (K-1-j)!), never 0
+    if (j & 1) {
+      u64 z[4] = {0, 0, 0, 0};
+      wide_sub_p(z, a, mm);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a[i] = z[i];
+    }
+    wide_mont_mul(a, mm.r2, mm, a);                                 // w_j R^2
+    wide_mont_mul(a, mm.r2, mm, a);                                 // w_j R^3
+    wide_st(w3 + (size_t)j * 4, a);
+  }
+}
+
+// one thread per column i (x = party_lo + i + 1), lanes store along the rows of Lw: a suffix pass leaves prod_{m>j}(x + m), scaled
+// (pvw_wide.h), in Lw[j][i] and ends on Z(x) in full; a prefix pass multiplies prod_{m<j}(x + m) and w_j in
+__global__ __launch_bounds__(256) void shamir_packed_wide_weights_kernel(u64* Lw, u64* zt, const u64* w3, u32 K, u32 party_lo, u32 cols,
+                                                                         WideMod m, WideMont mm) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= cols) return;
+  const u32 x = party_lo + i + 1;                                   // x + K - 1 < 2^32
+  const u64 zero[4] = {0, 0, 0, 0};
+  u64 suf[4] = {1, 0, 0, 0};
+  wide_shl(suf, m.shift);
+  for (u32 j = K; j-- > 0;) {
+    wide_st(Lw + ((size_t)j * cols + i) * 4, suf);
+    wide_step(suf, x + j, zero, m);
+  }
+  wide_shr(suf, m.shift);                                           // Z(x) = x (x + 1) ... (x + K - 1) mod p
+  wide_mont_in(suf, mm, suf);
+  wide_st(zt + (size_t)i * 4, suf);
+  u64 pre[4] = {1, 0, 0, 0};
+  wide_shl(pre, m.shift);
+  for (u32 j = 0; j < K; ++j) {
+    u64* e = Lw + ((size_t)j * cols + i) * 4;
+    u64 sv[4], pv[4], wj[4];
+    wide_ld(e, sv);
+    wide_shr(sv, m.shift);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) pv[k] = pre[k];
+    wide_shr(pv, m.shift);
+    wide_ld(w3 + (size_t)j * 4, wj);
+    wide_mont_mul(sv, pv, mm, sv);                                  // suffix prefix / R
+    wide_mont_mul(sv, wj, mm, sv);                                  // L_j(x) R
+    wide_st(e, sv);
+    wide_step(pre, x + j, zero, m);
+  }
+}
+
+// ws: shamir_packed_wide_words
+hipError_t launch_shamir_packed_wide_weights(u64* ws, u32 pack, u32 party_lo, u32 party_hi, const WideMod& m, const WideMont& mm,
+                                             hipStream_t s) {
+  if (pack == 0 || party_hi <= party_lo) return hipSuccess;
+  const u32 cols = party_hi - party_lo;
+  u64 *Lw = ws, *zt = Lw + (size_t)pack * cols * 4, *w3 = zt + (size_t)cols * 4, *invf = w3 + (size_t)pack * 4;
+  shamir_packed_wide_basis_kernel<<<dim3(1), dim3(256), 0, s>>>(w3, invf, pack, mm);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  shamir_packed_wide_weights_kernel<<<dim3((cols + 255) / 256), dim3(256), 0, s>>>(Lw, zt, w3, pack, party_lo, cols, m, mm);
+  return hipGetLastError();
+}
+
 }  // namespace pvw

@@ -899,6 +899,96 @@ inline EvaluatedWideShares shamir_evaluate_wide_corrected(const std::shared_ptr<
                                                  c.err_mask.data()));
   return r;
 }
+// ---- packed dealing over an odd prime below 2^256 ----
+// shares [D][n][4] of secrets [D][pack][4], dealer-major: `pack` secrets at the points 0, -1, .., -(pack-1) of one polynomial with
+// `degree` random coefficients, drawn from seeds[d] or given as coeffs [D][degree][4].  On the device
+// (pvw_shamir_shares_packed_wide); host = true: the restatement on the host cores (no GPU).  pack = 1 is shamir_shares_wide.
+inline std::vector<uint64_t> shamir_shares_packed_wide(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& secrets,
+                                                       uint32_t pack, uint32_t degree, const Wide& plain_modulus, const std::vector<Seed>& seeds,
+                                                       const std::vector<uint64_t>& coeffs = {}, bool host = false) {
+  if (!pack || secrets.size() % ((size_t)pack * PVW_WIDE_WORDS)) throw PvwError(15, "pack elements of four words per dealer");
+  const size_t D = secrets.size() / ((size_t)pack * PVW_WIDE_WORDS);
+  if (!seeds.empty() && seeds.size() != D) throw PvwError(15, "one seed per dealer");
+  if (!coeffs.empty() && coeffs.size() != D * degree * PVW_WIDE_WORDS) throw PvwError(15, "degree coefficients per dealer");
+  const std::vector<uint8_t> sd = seed_bytes(seeds);
+  std::vector<uint64_t> out(D * p->n * PVW_WIDE_WORDS);
+  const uint8_t* sdp = sd.empty() ? nullptr : sd.data();
+  const uint64_t* cop = coeffs.empty() ? nullptr : coeffs.data();
+  check(host ? pvw_shamir_shares_packed_wide_host(p->ctx, secrets.data(), D, pack, degree, plain_modulus.data(), sdp, cop, out.data())
+             : pvw_shamir_shares_packed_wide(p->ctx, secrets.data(), D, pack, degree, plain_modulus.data(), sdp, cop, out.data()));
+  return out;
+}
+inline std::vector<PvwCiphertext> deal_packed_wide_call(const std::vector<uint64_t>& secrets, uint32_t pack, uint32_t degree,
+                                                        const Wide& plain_modulus, const GlobalPublicKey& gpk, const std::vector<Seed>* seeds,
+                                                        DeviceRandomness* rnd, uint32_t limb_bits, uint32_t out_repr) {
+  if (!pack || secrets.size() % ((size_t)pack * PVW_WIDE_WORDS)) throw PvwError(15, "pack elements of four words per dealer");
+  const size_t D = secrets.size() / ((size_t)pack * PVW_WIDE_WORDS), V = D * shamir_wide_limbs(plain_modulus, limb_bits);
+  const auto& p = gpk.params;
+  const size_t P = p->poly_words();
+  if (seeds && seeds->size() != V) throw PvwError(15, "one seed per limb ciphertext");
+  const std::vector<uint8_t> sd = seeds ? seed_bytes(*seeds) : std::vector<uint8_t>();
+  std::vector<uint64_t> c1(V * p->k * P), c2(V * p->n * P);
+  if (seeds)
+    check(pvw_deal_shares_packed_wide(p->ctx, secrets.data(), D, pack, degree, plain_modulus.data(), limb_bits, sd.data(), c1.data(), c2.data(),
+                                      out_repr));
+  else
+    check(pvw_deal_shares_packed_wide_rs(p->ctx, secrets.data(), D, pack, degree, plain_modulus.data(), limb_bits, rnd->raw(), c1.data(),
+                                         c2.data(), out_repr));
+  return deal_ciphertexts(p, c1, c2, V, out_repr);
+}
+// deal_party_shares_wide with `pack` secrets per dealer in one polynomial (pvw_deal_shares_packed_wide): D * NL ciphertexts carry
+// D * pack wide secrets; seeds and limbs as deal_party_shares_wide
+inline std::vector<PvwCiphertext> deal_party_shares_packed_wide(const std::vector<uint64_t>& secrets, uint32_t pack, uint32_t degree,
+                                                                const Wide& plain_modulus, const GlobalPublicKey& gpk,
+                                                                const std::vector<Seed>& seeds, uint32_t limb_bits = 52,
+                                                                uint32_t out_repr = PVW_REPR_NTT) {
+  return deal_packed_wide_call(secrets, pack, degree, plain_modulus, gpk, &seeds, nullptr, limb_bits, out_repr);
+}
+// ... with vector v's randomness from call_seed(S, c + v) of a DeviceRandomness, which then holds c + D * NL
+inline std::vector<PvwCiphertext> deal_party_shares_packed_wide(const std::vector<uint64_t>& secrets, uint32_t pack, uint32_t degree,
+                                                                const Wide& plain_modulus, const GlobalPublicKey& gpk, DeviceRandomness& rnd,
+                                                                uint32_t limb_bits = 52, uint32_t out_repr = PVW_REPR_NTT) {
+  return deal_packed_wide_call(secrets, pack, degree, plain_modulus, gpk, nullptr, &rnd, limb_bits, out_repr);
+}
+// out [num_rows][pack][4]: every row's values at 0, -1, .., -(pack-1) from shares [num_rows][indices.size()][4] of the parties
+// `indices` (at least degree + pack of them); host only (pvw_shamir_reconstruct_packed_wide)
+inline std::vector<uint64_t> shamir_reconstruct_packed_wide(const std::vector<uint64_t>& indices, const std::vector<uint64_t>& shares,
+                                                            const Wide& plain_modulus, uint32_t pack) {
+  if (indices.empty() || shares.size() % (indices.size() * PVW_WIDE_WORDS)) throw PvwError(15, "shares must hold one element per index and row");
+  const size_t R = shares.size() / (indices.size() * PVW_WIDE_WORDS);
+  std::vector<uint64_t> out(R * (pack ? pack : 1) * PVW_WIDE_WORDS);
+  check(pvw_shamir_reconstruct_packed_wide(plain_modulus.data(), pack, indices.data(), shares.data(), indices.size(), R, out.data()));
+  return out;
+}
+struct CorrectedPackedWideSecrets {
+  std::vector<uint64_t> secrets;    // [num_rows][pack][4]; the row of an undecodable sharing is 0
+  CorrectedWideSecrets report;      // the decode's report, unchanged
+};
+// The secrets of a packed wide sharing although up to (indices.size() - degree - pack) / 2 shares of each row are wrong.  The wide
+// evaluate calls take targets as party indices, so the points -j cannot be named for a wide p: ONE shamir_evaluate_wide_corrected
+// call at polynomial degree degree + pack - 1 evaluates the corrected polynomials at the first degree + pack of `indices`, and
+// shamir_reconstruct_packed_wide reads the secrets off those corrected shares.  pack = 1: shamir_reconstruct_wide_corrected.
+inline CorrectedPackedWideSecrets shamir_reconstruct_packed_wide_corrected(const std::shared_ptr<PvwParameters>& p, const Wide& plain_modulus,
+                                                                           uint32_t pack, uint32_t degree, const std::vector<uint64_t>& indices,
+                                                                           const std::vector<uint64_t>& shares,
+                                                                           const std::vector<uint64_t>& erased = {}, bool party_major = false,
+                                                                           bool host = false) {
+  if (pack == 0) throw PvwError(1, "pack must be at least 1");
+  if (pack == 1) {
+    CorrectedWideSecrets r = shamir_reconstruct_wide_corrected(p, indices, shares, degree, plain_modulus, erased, party_major, host);
+    std::vector<uint64_t> secrets = r.secrets;
+    return CorrectedPackedWideSecrets{std::move(secrets), std::move(r)};
+  }
+  const size_t need = (size_t)degree + pack;
+  if (indices.size() < need) throw PvwError(1, "degree + pack shares are needed");
+  const std::vector<uint64_t> basis(indices.begin(), indices.begin() + need);
+  EvaluatedWideShares ev = shamir_evaluate_wide_corrected(p, indices, shares, degree + pack - 1, plain_modulus, basis, erased, party_major, host);
+  std::vector<uint64_t> secrets = shamir_reconstruct_packed_wide(basis, ev.values, plain_modulus, pack);
+  for (size_t r = 0; r < ev.report.nerr.size(); ++r)
+    if (ev.report.nerr[r] == PVW_SHAMIR_UNDECODABLE)
+      std::fill(secrets.begin() + r * pack * PVW_WIDE_WORDS, secrets.begin() + (r + 1) * pack * PVW_WIDE_WORDS, (uint64_t)0);
+  return CorrectedPackedWideSecrets{std::move(secrets), std::move(ev.report)};
+}
 // The mask of wide shares from a per-limb decrypt report on the host (pvw_shamir_wide_erasure_mask_host): status / noise
 // [num_secrets][count * num_limbs], or with party_major [count][num_secrets * num_limbs] (the [party][dealer NL + w] report of the
 // decrypt-all calls); either may be empty, not both.  Share (s, c) is erased iff one of its limbs has status & status_bits or

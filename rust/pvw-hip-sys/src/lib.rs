@@ -176,6 +176,15 @@ extern "C" {
     pub fn pvw_shamir_wide_from_limbs_host(plain_modulus: *const u64, limbs: *const u64, count: usize, limb_bits: u32, num_limbs: u32, out: *mut u64) -> i32;
     pub fn pvw_shamir_reconstruct_wide(plain_modulus: *const u64, indices: *const u64, shares: *const u64, count: usize, num_secrets: usize, out: *mut u64) -> i32;
     pub fn pvw_selftest_shamir_wide_step(ctx: *mut PvwCtx, plain_modulus: *const u64, acc: *const u64, x: *const u64, add: *const u64, count: usize, out: *mut u64) -> i32;
+    // ---- packed sharing over a prime below 2^256: secrets [D][pack][4] ----
+    pub fn pvw_shamir_shares_packed_wide_host(ctx: *const PvwCtx, secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: *const u64, seeds: *const u8, coeffs: *const u64, shares_out: *mut u64) -> i32;
+    pub fn pvw_shamir_shares_packed_wide_device(ctx: *mut PvwCtx, d_secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: *const u64, seeds: *const u8, d_coeffs: *const u64, d_shares: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_shares_packed_wide(ctx: *mut PvwCtx, secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: *const u64, seeds: *const u8, coeffs: *const u64, shares_out: *mut u64) -> i32;
+    pub fn pvw_deal_shares_packed_wide(ctx: *mut PvwCtx, secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: *const u64, limb_bits: u32, seeds: *const u8, c1_out: *mut u64, c2_out: *mut u64, out_repr: u32) -> i32;
+    pub fn pvw_deal_shares_packed_wide_device(ctx: *mut PvwCtx, d_secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: *const u64, limb_bits: u32, seeds: *const u8, d_c1: *mut u64, d_c2: *mut u64, out_repr: u32, stream: *mut c_void) -> i32;
+    pub fn pvw_deal_shares_packed_wide_rs(ctx: *mut PvwCtx, secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: *const u64, limb_bits: u32, st: *mut c_void, c1_out: *mut u64, c2_out: *mut u64, out_repr: u32) -> i32;
+    pub fn pvw_deal_shares_packed_wide_rs_device(ctx: *mut PvwCtx, d_secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: *const u64, limb_bits: u32, st: *mut c_void, d_c1: *mut u64, d_c2: *mut u64, out_repr: u32, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_reconstruct_packed_wide(plain_modulus: *const u64, pack: u32, indices: *const u64, shares: *const u64, count: usize, num_rows: usize, out: *mut u64) -> i32;
     // ---- the receiving end over a prime below 2^256: device fold of limbs, checked reconstruction ----
     pub fn pvw_shamir_wide_from_limbs_device(ctx: *mut PvwCtx, plain_modulus: *const u64, d_limbs: *const u64, count: usize, limb_stride: usize, elem_stride: usize, limb_bits: u32, num_limbs: u32, d_out: *mut u64, stream: *mut c_void) -> i32;
     pub fn pvw_shamir_reconstruct_wide_checked_host(plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, out: *mut u64, bad: *mut u32, col_bad: *mut u32) -> i32;

@@ -795,6 +795,108 @@ pub fn shamir_evaluate_wide_corrected(params: &Arc<PvwParameters>, indices: &[u6
     Ok((values, r))
 }
 
+/// EXTENSION: packed shares over an odd prime below 2^256.  `secrets` is `[dealers][pack]`, dealer-major: the
+/// `pack` secrets of a dealer sit at the points 0, -1, .., -(pack-1) of one polynomial with `degree` random coefficients, drawn as
+/// `shamir_shares_wide` draws them or given as `coeffs [dealers][degree]`.  Returns `[dealers][n]` (`pvw_shamir_shares_packed_wide`).
+pub fn shamir_shares_packed_wide(params: &Arc<PvwParameters>, secrets: &[Wide], pack: u32, degree: u32, plain_modulus: &Wide,
+                                 seeds: Option<&[u8]>, coeffs: Option<&[Wide]>) -> Result<Vec<Wide>> {
+    if pack == 0 || secrets.len() % pack as usize != 0 {
+        return Err(PvwError::InvalidParameters("secrets must hold pack elements per dealer".into()));
+    }
+    let dealers = secrets.len() / pack as usize;
+    let mut out = vec![[0u64; 4]; dealers * params.n];
+    check(unsafe {
+        sys::pvw_shamir_shares_packed_wide(params.hip.raw(), secrets.as_ptr() as *const u64, dealers, pack, degree, plain_modulus.as_ptr(),
+                                           seeds.map_or(std::ptr::null(), |s| s.as_ptr()),
+                                           coeffs.map_or(std::ptr::null(), |c| c.as_ptr() as *const u64), out.as_mut_ptr() as *mut u64)
+    })?;
+    Ok(out)
+}
+
+/// EXTENSION: `deal_party_shares_wide` with `pack` secrets per dealer in one polynomial
+/// (`pvw_deal_shares_packed_wide`): `dealers * NL` ciphertexts carry `dealers * pack` wide secrets.  One seed per ciphertext comes
+/// from `thread_rng` and is cleared afterwards.
+pub fn deal_party_shares_packed_wide(secrets: &[Wide], pack: u32, degree: u32, plain_modulus: &Wide, limb_bits: u32,
+                                     global_pk: &GlobalPublicKey) -> Result<Vec<PvwCiphertext>> {
+    if pack == 0 || secrets.len() % pack as usize != 0 {
+        return Err(PvwError::InvalidParameters("secrets must hold pack elements per dealer".into()));
+    }
+    let params = &global_pk.params;
+    let dealers = secrets.len() / pack as usize;
+    let vectors = dealers * shamir_wide_limbs(plain_modulus, limb_bits)? as usize;
+    let words = poly_words(params);
+    let mut seeds = vec![0u8; 32 * vectors];
+    rand::thread_rng().fill_bytes(&mut seeds);
+    let (mut c1, mut c2) = (vec![0u64; vectors * params.k * words], vec![0u64; vectors * params.n * words]);
+    let rc = unsafe {
+        sys::pvw_deal_shares_packed_wide(params.hip.raw(), secrets.as_ptr() as *const u64, dealers, pack, degree, plain_modulus.as_ptr(),
+                                         limb_bits, seeds.as_ptr(), c1.as_mut_ptr(), c2.as_mut_ptr(), sys::PVW_REPR_POWER)
+    };
+    seeds.zeroize();
+    check(rc)?;
+    wide_ciphertexts(&c1, &c2, vectors, params)
+}
+
+/// `deal_party_shares_packed_wide` with vector v's randomness drawn from a `DeviceRandomness` (`call_seed(S, c + v)`).
+pub fn deal_party_shares_packed_wide_with(secrets: &[Wide], pack: u32, degree: u32, plain_modulus: &Wide, limb_bits: u32,
+                                          global_pk: &GlobalPublicKey, rnd: &DeviceRandomness) -> Result<Vec<PvwCiphertext>> {
+    if pack == 0 || secrets.len() % pack as usize != 0 {
+        return Err(PvwError::InvalidParameters("secrets must hold pack elements per dealer".into()));
+    }
+    let params = &global_pk.params;
+    let dealers = secrets.len() / pack as usize;
+    let vectors = dealers * shamir_wide_limbs(plain_modulus, limb_bits)? as usize;
+    let words = poly_words(params);
+    let (mut c1, mut c2) = (vec![0u64; vectors * params.k * words], vec![0u64; vectors * params.n * words]);
+    check(unsafe {
+        sys::pvw_deal_shares_packed_wide_rs(params.hip.raw(), secrets.as_ptr() as *const u64, dealers, pack, degree, plain_modulus.as_ptr(),
+                                            limb_bits, rnd.raw(), c1.as_mut_ptr(), c2.as_mut_ptr(), sys::PVW_REPR_POWER)
+    })?;
+    wide_ciphertexts(&c1, &c2, vectors, params)
+}
+
+/// EXTENSION: `[num_rows][pack]`: every row's values at 0, -1, .., -(pack-1) from the shares
+/// `[num_rows][indices.len()]` of the parties `indices` (at least degree + pack of them).  Host only
+/// (`pvw_shamir_reconstruct_packed_wide`).
+pub fn shamir_reconstruct_packed_wide(indices: &[u64], shares: &[Wide], plain_modulus: &Wide, pack: u32) -> Result<Vec<Wide>> {
+    if indices.is_empty() || shares.len() % indices.len() != 0 {
+        return Err(PvwError::InvalidParameters("shares must hold one element per index and row".into()));
+    }
+    let rows = shares.len() / indices.len();
+    let mut out = vec![[0u64; 4]; rows * pack.max(1) as usize];
+    check(unsafe {
+        sys::pvw_shamir_reconstruct_packed_wide(plain_modulus.as_ptr(), pack, indices.as_ptr(), shares.as_ptr() as *const u64, indices.len(),
+                                                rows, out.as_mut_ptr() as *mut u64)
+    })?;
+    Ok(out)
+}
+
+/// EXTENSION: the secrets `[num_rows][pack]` of a packed wide sharing although up to
+/// `(indices.len() - degree - pack) / 2` shares of each row are wrong.  The wide evaluate calls take targets as party indices, so
+/// the points -j cannot be named for a wide p: ONE `shamir_evaluate_wide_corrected` call at polynomial degree `degree + pack - 1`
+/// evaluates the corrected polynomials at the first `degree + pack` of `indices`, and `shamir_reconstruct_packed_wide` reads the
+/// secrets off those corrected shares.  A row reported `PVW_SHAMIR_UNDECODABLE` gives `pack` zero elements; the report passes
+/// through unchanged.  `pack = 1` is `shamir_reconstruct_wide_corrected`.
+pub fn shamir_reconstruct_packed_wide_corrected(params: &Arc<PvwParameters>, plain_modulus: &Wide, pack: u32, degree: u32, indices: &[u64],
+                                                shares: &[Wide], erased: &[u64], party_major: bool) -> Result<(Vec<Wide>, CorrectedWideSecrets)> {
+    if pack == 0 {
+        return Err(PvwError::InvalidParameters("pack must be at least 1".into()));
+    }
+    let need = degree as usize + pack as usize;
+    if indices.len() < need {
+        return Err(PvwError::InvalidParameters("degree + pack shares are needed".into()));
+    }
+    let basis = &indices[..need];
+    let (values, report) = shamir_evaluate_wide_corrected(params, indices, shares, degree + pack - 1, plain_modulus, erased, basis, party_major)?;
+    let mut secrets = shamir_reconstruct_packed_wide(basis, &values, plain_modulus, pack)?;
+    for (r, &e) in report.nerr.iter().enumerate() {
+        if e == sys::PVW_SHAMIR_UNDECODABLE {
+            secrets[r * pack as usize..(r + 1) * pack as usize].iter_mut().for_each(|s| *s = [0u64; 4]);
+        }
+    }
+    Ok((secrets, report))
+}
+
 /// EXTENSION: the erasure mask of wide shares from a per-limb decrypt report, on the host
 /// (`pvw_shamir_wide_erasure_mask_host`).  `status` and `noise` are `[num_secrets][count * num_limbs]`, or with `party_major`
 /// `[count][num_secrets * num_limbs]` (the `[party][dealer * NL + w]` report of the decrypt-all calls, every dealer a secret);
