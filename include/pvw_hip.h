@@ -1378,6 +1378,82 @@ PVW_API int32_t pvw_sample_uniform(pvw_ctx* ctx, const uint8_t seed[32], uint32_
 PVW_API int32_t pvw_sample_gaussian(pvw_ctx* ctx, const uint8_t seed[32], uint32_t index0, size_t count,
                             uint64_t bound, int64_t* out /*[count]*/);    /* normal.rs:12-20,136-162 */
 
+/* ---- Handover over a prime field of up to 256 bits: the public arithmetic either side of ONE pass of int64
+ * combinations (pvw_ct_lincomb_many*, pvw_decrypt_all_lincomb_many_plain*), so that a committee moves its wide shares to a new
+ * one with V decrypts a party instead of D NL.  Vector d NL + w is limb w of old holder d (the order pvw_deal_shares_wide*
+ * writes).  A Lagrange weight of 256 bits cannot be an int64 weight, but |P| only has to stay below Q/2 (plain-modulus decode,
+ * "Radius"), so mu_{d,w} = lambda_d 2^(limb_bits w) mod p is cut into V signed digits c_{d,w,v} of b = digit_bits bits, B = 2^b:
+ *   P_v[j]       = sum_{d,w} c_{d,w,v} limb_{d,w}[j]      one combined ciphertext per digit, decrypted with wide_words = ww
+ *   new share[j] = sum_v P_v[j] B^v mod p = sum_d lambda_d f_d(j + 1) mod p
+ * The digit rule (host and device agree bit for bit): 8 <= b <= 64, V = ceil((bitlen(p) + 1) / b); for a value read mod p, x = its
+ * centred residue in (-p/2, p/2]; for v = 0 .. V - 2: c_v = x mod B taken in [-B/2, B/2), x <- (x - c_v) / B; c_{V-1} = the
+ * remaining x.  Every digit, the top one included, lies in [-2^(b-1), 2^(b-1)) and sum_v c_v B^v = x.  (The "+ 1" matters: with
+ * ceil(bitlen(p) / b) digits the chain does not close, B = 4, V = 2, x = 6.)
+ * plain_modulus is a HOST pointer to an odd prime below 2^256, checked as in the wide family; limb_bits follows
+ * pvw_shamir_wide_limbs and gives NL.  Every refusal is PVW_ERR_INVALID_PARAMETERS before any device work, nothing written. */
+/* NL and V of a field, a limb width and a digit width; host only */
+PVW_API int32_t pvw_shamir_wide_handover_shape(const uint64_t* plain_modulus, uint32_t limb_bits, uint32_t digit_bits, uint32_t* num_limbs,
+                                               uint32_t* num_digits);
+/* digits [count][V] of values [count][4] (any words, read mod p) by the rule above; the device form runs the cut of the weights
+ * kernel on device pointers, asynchronous on `stream`, allocates nothing, may be captured */
+PVW_API int32_t pvw_shamir_wide_signed_digits_host(const uint64_t* plain_modulus, const uint64_t* values, size_t count, uint32_t digit_bits,
+                                                   int64_t* digits);
+PVW_API int32_t pvw_shamir_wide_signed_digits_device(pvw_ctx* ctx, const uint64_t* plain_modulus, const uint64_t* d_values, size_t count,
+                                                     uint32_t digit_bits, int64_t* d_digits, void* stream);
+/* The weight rows, weights [T V][D NL]: row m V + v, column d NL + w holds digit v of lambda_{d,m} 2^(limb_bits w) mod p, where
+ * lambda_{.,m} are the Lagrange weights at points[m] over the points indices[d] + 1 of the VALID holders (valid [D] bytes, NULL =
+ * all); every column of an invalid holder is 0.  points [T][4] below p, or NULL for the single point 0 (T = 1 then); the point
+ * -m of a packed sharing is p - m.  A point equal to a valid holder's point gives that holder's unit vector (its columns hold
+ * the digits of 2^(limb_bits w), all others 0); the point of an invalid holder is an ordinary point.  indices, valid and points
+ * are HOST arrays in both forms, consumed at call time.  Refused: what pvw_shamir_reconstruct_wide refuses about the indices of
+ * the valid holders, no valid holder, a point >= p, T = 0, digit_bits outside [8, 64], D NL >= 2^32, and T V >= 2^31 on the device.
+ * The device form builds its public matrices in a block of the stream's workspace sized by the call: under stream capture it
+ * needs an earlier call on that stream outside capture with at least as many valid holders and points. */
+PVW_API int32_t pvw_shamir_wide_handover_weights_host(const uint64_t* plain_modulus, const uint64_t* indices, const uint8_t* valid,
+                                                      size_t num_holders, const uint64_t* points, size_t num_points, uint32_t limb_bits,
+                                                      uint32_t digit_bits, int64_t* weights);
+PVW_API int32_t pvw_shamir_wide_handover_weights_device(pvw_ctx* ctx, const uint64_t* plain_modulus, const uint64_t* indices,
+                                                        const uint8_t* valid, size_t num_holders, const uint64_t* points, size_t num_points,
+                                                        uint32_t limb_bits, uint32_t digit_bits, int64_t* d_weights, void* stream);
+/* The fold: out[i] = sum_v +-|P_{i,v}| B^v mod p, fully reduced, for wide [count][V][wide_words] and status [count][V] -- exactly
+ * what pvw_decrypt_all_lincomb_many_plain* writes for R = T V rows, read in place with count = P T.  The sign is PVW_DEC_NEGATIVE
+ * of status[i][v]; status_out[i] is the OR of the V words with PVW_DEC_NEGATIVE cleared (PVW_DEC_WIDE_TRUNCATED and the lossy bit
+ * survive).  1 <= wide_words <= 4, 1 <= num_digits <= 33.  The device form: device pointers, asynchronous, may be captured. */
+PVW_API int32_t pvw_shamir_wide_from_digits_host(const uint64_t* plain_modulus, uint32_t digit_bits, uint32_t num_digits,
+                                                 const uint64_t* wide, uint32_t* status, uint32_t wide_words, size_t count,
+                                                 uint64_t* out, uint32_t* status_out);
+PVW_API int32_t pvw_shamir_wide_from_digits_device(pvw_ctx* ctx, const uint64_t* plain_modulus, uint32_t digit_bits, uint32_t num_digits,
+                                                   const uint64_t* d_wide, uint32_t* d_status, uint32_t wide_words, size_t count,
+                                                   uint64_t* d_out, uint32_t* d_status_out, void* stream);
+/* Every new party's new share in one call: out [P][T][4] (fully reduced) and status [P][T] for the parties [party_lo, party_hi),
+ * P = party_hi - party_lo, from the old holders' limb ciphertexts c1s [D NL][k][L][l], c2s [D NL][n][L][l].  Behind the checks it
+ * runs the device weights above, the body of pvw_decrypt_all_lincomb_many_plain* with R = T V rows over all D NL vectors
+ * (valid = NULL there: a masked holder's weights are 0) and wide_words = ww = ceil((limb_bits + digit_bits +
+ * ceil(log2(num_valid NL)) + 1) / 64), unchanged, and the fold above over its report in place.  out / status are bit for bit
+ * pvw_shamir_wide_handover_weights_host -> that call -> pvw_shamir_wide_from_digits_host; *count (may be NULL) = the valid
+ * holders.  Refused: NULL, what the weights call refuses, ww beyond the words of Q, what the many-combinations call refuses.
+ * The digit plaintexts [P][R] are marked secret and cleared behind the fold (the weights and the combined ciphertexts are
+ * public); the keys are staged and cleared by the many-combinations call.  The _device form takes device pointers for sk,
+ * c1s, c2s, out, status and count (indices, valid, points and plain_modulus stay HOST arrays, consumed at call time) and is
+ * asynchronous on `stream`; under stream capture it needs an earlier call outside capture on that stream with the same party
+ * range and at least as many valid holders, rows T V and vectors (the rule of 8.15), and is refused with nothing enqueued
+ * otherwise; a replay reads no host memory.  The host-buffer form may be called from several threads at once. */
+PVW_API int32_t pvw_decrypt_all_handover_wide(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* sk, const uint64_t* c1s,
+                                              const uint64_t* c2s, size_t num_dealers, const uint64_t* plain_modulus, uint32_t limb_bits,
+                                              uint32_t digit_bits, const uint64_t* indices, const uint8_t* valid, const uint64_t* points,
+                                              size_t num_points, uint32_t in_repr, uint64_t* out, uint32_t* status, uint32_t* count);
+PVW_API int32_t pvw_decrypt_all_handover_wide_device(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* d_sk,
+                                                     const uint64_t* d_c1s, const uint64_t* d_c2s, size_t num_dealers,
+                                                     const uint64_t* plain_modulus, uint32_t limb_bits, uint32_t digit_bits,
+                                                     const uint64_t* indices, const uint8_t* valid, const uint64_t* points,
+                                                     size_t num_points, uint32_t in_repr, uint64_t* d_out, uint32_t* d_status,
+                                                     uint32_t* d_count, void* stream);
+/* Advisory (host): *fits = 1 iff num_valid NL 2^(digit_bits - 1) pvw_ctx_noise_bound <= the radius of pvw_ctx_sum_capacity, and
+ * ww = ceil((limb_bits + digit_bits + ceil(log2(num_valid NL)) + 1) / 64) is at most the words of Q.  Sufficient, not necessary,
+ * like pvw_ctx_lincomb_fits; no entry point refuses on noise grounds. */
+PVW_API int32_t pvw_ctx_wide_handover_fits(const pvw_ctx* ctx, const uint64_t* plain_modulus, size_t num_valid, uint32_t limb_bits,
+                                           uint32_t digit_bits, uint32_t* fits);
+
 /* ---- measurement hooks -------------------------------------------------------------
  * With profiling on, every kernel launch of the context is bracketed by HIP events on
  * its stream; pvw_ctx_kernel_time returns the accumulated device time of kernel `name`

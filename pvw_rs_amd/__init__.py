@@ -24,7 +24,9 @@ from .api import (DEC_LOSSY, DEC_NEGATIVE, DEC_WIDE_TRUNCATED, CheckedDecryption
                   shamir_wide_from_limbs_device, shamir_reconstruct_wide_checked,
                   shamir_reconstruct_wide_corrected, shamir_wide_erasure_mask, shamir_evaluate_wide_corrected,
                   shamir_shares_packed_wide, deal_party_shares_packed_wide, shamir_reconstruct_packed_wide,
-                  shamir_reconstruct_packed_wide_corrected)
+                  shamir_reconstruct_packed_wide_corrected, shamir_wide_handover_shape, shamir_wide_signed_digits,
+                  shamir_wide_handover_weights, shamir_wide_from_digits, shamir_packed_wide_handover_points,
+                  decrypt_all_party_handover_wide)
 
 __all__ = [
     "PvwParametersBuilder", "PvwParameters", "PvwCrs", "SecretKey", "DeviceSecretKey", "DeviceRandomness", "Party", "GlobalPublicKey",
@@ -45,5 +47,7 @@ __all__ = [
     "shamir_wide_from_limbs_device", "shamir_reconstruct_wide_checked", "shamir_reconstruct_wide_corrected", "shamir_wide_erasure_mask",
     "shamir_evaluate_wide_corrected",
     "shamir_shares_packed_wide", "deal_party_shares_packed_wide", "shamir_reconstruct_packed_wide", "shamir_reconstruct_packed_wide_corrected",
+    "shamir_wide_handover_shape", "shamir_wide_signed_digits", "shamir_wide_handover_weights", "shamir_wide_from_digits",
+    "shamir_packed_wide_handover_points", "decrypt_all_party_handover_wide",
     "device_available", "REPR_POWER", "REPR_NTT",
 ]

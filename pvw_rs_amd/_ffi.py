@@ -210,6 +210,19 @@ _SIGNATURES = {
     "pvw_shamir_wide_erasure_mask_device": [_P, _P, _P, C.c_uint32, C.c_uint64, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                             C.c_uint32, C.c_size_t, _P, _P],
     "pvw_selftest_shamir_wide_mul": [_P, _P, _P, _P, C.c_size_t, _P],
+    # wide handover: the weight rows of one many-combinations pass and the fold of its digit plaintexts
+    "pvw_shamir_wide_handover_shape": [_P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    "pvw_shamir_wide_signed_digits_host": [_P, _P, C.c_size_t, C.c_uint32, _P],
+    "pvw_shamir_wide_signed_digits_device": [_P, _P, _P, C.c_size_t, C.c_uint32, _P, _P],
+    "pvw_shamir_wide_handover_weights_host": [_P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint32, C.c_uint32, _P],
+    "pvw_shamir_wide_handover_weights_device": [_P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint32, C.c_uint32, _P, _P],
+    "pvw_shamir_wide_from_digits_host": [_P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, C.c_size_t, _P, _P],
+    "pvw_shamir_wide_from_digits_device": [_P, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, C.c_size_t, _P, _P, _P],
+    "pvw_decrypt_all_handover_wide": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t,
+                                      C.c_uint32, _P, _P, _P],
+    "pvw_decrypt_all_handover_wide_device": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P, C.c_uint32, C.c_uint32, _P, _P, _P,
+                                             C.c_size_t, C.c_uint32, _P, _P, _P, _P],
+    "pvw_ctx_wide_handover_fits": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)],
     "pvw_shamir_shares_packed_host": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P],
     "pvw_shamir_shares_packed_device": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P, _P],
     "pvw_shamir_shares_packed": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P],

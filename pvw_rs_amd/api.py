@@ -243,6 +243,14 @@ class PvwParameters:
         self._call("pvw_ctx_lincomb_fits", _ptr(w), w.size, _ptr(v), C.byref(fits))
         return bool(fits.value)
 
+    def wide_handover_fits(self, plain_modulus: int, num_valid: int, limb_bits: int = 52, digit_bits: int = 64) -> bool:
+        """pvw_ctx_wide_handover_fits: lincomb_fits for every weight row of a wide handover at once -- num_valid * NL
+        weights of at most 2^(digit_bits - 1) each -- and the digit plaintexts fit the words of Q.  Advisory and sufficient only."""
+        fits = C.c_uint32()
+        self._call("pvw_ctx_wide_handover_fits", _ptr(_wide_modulus(plain_modulus)), int(num_valid), int(limb_bits), int(digit_bits),
+                   C.byref(fits))
+        return bool(fits.value)
+
     @staticmethod
     def suggest_error_bounds(n, k, l, moduli, variance) -> Tuple[int, int]:   # :554-603
         m = _u64(list(moduli))
@@ -1180,6 +1188,119 @@ def shamir_wide_from_limbs_device(params: PvwParameters, limbs, plain_modulus: i
     return out
 
 
+def shamir_wide_handover_shape(plain_modulus: int, limb_bits: int = 52, digit_bits: int = 64) -> Tuple[int, int]:
+    """EXTENSION: (NL, V) of a wide handover: the limbs of a share and the signed digits of a weight,
+    V = ceil((bitlen(p) + 1) / digit_bits) (pvw_shamir_wide_handover_shape; no GPU, no context)."""
+    nl, nd = C.c_uint32(), C.c_uint32()
+    L = _ffi.lib()
+    _check(L.pvw_shamir_wide_handover_shape(_ptr(_wide_modulus(plain_modulus)), int(limb_bits), int(digit_bits), C.byref(nl), C.byref(nd)), L)
+    return int(nl.value), int(nd.value)
+
+
+def _handover_device(params, host: bool):
+    """torch, for the device forms of the handover's public arithmetic (device pointers only: there is no host-buffer form)"""
+    if host:
+        return None
+    if params is None:
+        raise PvwError(1, "the device form needs the parameters (a context); host=True needs none")
+    import torch
+    return torch
+
+
+def shamir_wide_signed_digits(params: Optional[PvwParameters], values, plain_modulus: int, digit_bits: int = 64, *,
+                              host: bool = False) -> np.ndarray:
+    """EXTENSION: the signed digits int64 [count][V] of values (ints or words [count][4], read mod p): the centred
+    residue x = sum_v c_v 2^(digit_bits v), every c_v in [-2^(digit_bits-1), 2^(digit_bits-1)).  host=True:
+    pvw_shamir_wide_signed_digits_host (no GPU); else the cut of the weights kernel (pvw_shamir_wide_signed_digits_device)."""
+    v = _wide(values)
+    V = shamir_wide_handover_shape(plain_modulus, 62, digit_bits)[1]                  # V does not depend on the limb width
+    pm = _wide_modulus(plain_modulus)
+    out = np.zeros((len(v), V), dtype=np.int64)
+    torch = _handover_device(params, host)
+    if torch is None:
+        L = _ffi.lib()
+        _check(L.pvw_shamir_wide_signed_digits_host(_ptr(pm), _ptr(v), len(v), int(digit_bits), _ptr(out)), L)
+        return out
+    dv = torch.from_numpy(v.view(np.int64)).cuda()
+    do = torch.zeros((len(v), V), dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    params._call("pvw_shamir_wide_signed_digits_device", _ptr(pm), _dptr(dv), len(v), int(digit_bits), _dptr(do), None)
+    params.synchronize()
+    return do.cpu().numpy()
+
+
+def shamir_packed_wide_handover_points(plain_modulus: int, pack: int) -> List[int]:
+    """EXTENSION: the points 0, -1, .., -(pack-1) of a packed wide sharing as field elements (-m is p - m), the
+    `points` of shamir_wide_handover_weights for its handover."""
+    p = int(plain_modulus)
+    return [(p - m) % p for m in range(int(pack))]
+
+
+def shamir_wide_handover_weights(params: Optional[PvwParameters], indices: Sequence[int], plain_modulus: int, valid=None, points=None,
+                                 limb_bits: int = 52, digit_bits: int = 64, *, host: bool = False) -> np.ndarray:
+    """EXTENSION: the int64 weight rows [T * V][D * NL] of a wide handover: row m * V + v, column d * NL + w holds
+    signed digit v of lambda_{d,m} 2^(limb_bits w) mod p, lambda_{.,m} the Lagrange weights at points[m] (ints below p; None: the
+    single point 0) over the points indices[d] + 1 of the valid holders; an invalid holder's columns are 0.  The rows go to
+    combine_ciphertexts_many / decrypt_all_party_combinations_many over the D * NL limb ciphertexts (vector d * NL + w), and
+    shamir_wide_from_digits folds the V plaintexts of a target.  host=True: pvw_shamir_wide_handover_weights_host (no GPU)."""
+    idx = _words(indices)
+    D = len(idx)
+    v = None if valid is None else np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+    if v is not None and v.shape != (D,):
+        raise PvwError(15, f"valid: expected {D} flags, got {v.size}")
+    pts = None if points is None else _wide([int(x) for x in points])
+    if points is not None and any(int(x) < 0 or int(x) >> 256 for x in points):
+        raise PvwError(1, "a target point must be a field element (the point -m is p - m)")
+    T = 1 if pts is None else len(pts)
+    NL, V = shamir_wide_handover_shape(plain_modulus, limb_bits, digit_bits)
+    pm = _wide_modulus(plain_modulus)
+    torch = _handover_device(params, host)
+    if torch is None:
+        out = np.zeros((T * V, D * NL), dtype=np.int64)
+        L = _ffi.lib()
+        _check(L.pvw_shamir_wide_handover_weights_host(_ptr(pm), _ptr(idx), _ptr(v), D, _ptr(pts), T, int(limb_bits), int(digit_bits),
+                                                       _ptr(out)), L)
+        return out
+    do = torch.zeros((T * V, D * NL), dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    params._call("pvw_shamir_wide_handover_weights_device", _ptr(pm), _ptr(idx), _ptr(v), D, _ptr(pts), T, int(limb_bits), int(digit_bits),
+                 _dptr(do), None)
+    params.synchronize()
+    return do.cpu().numpy()
+
+
+def shamir_wide_from_digits(params: Optional[PvwParameters], wide, status, plain_modulus: int, digit_bits: int = 64, *,
+                            host: bool = False) -> Tuple[list, np.ndarray]:
+    """EXTENSION: (values, status) from the digit plaintexts of a wide handover: wide uint64 [..][V][ww] (the
+    magnitudes) and status uint32 [..][V] as decrypt_all_party_combinations_many(wide=True) reports them for R = T * V rows
+    (.wide words reshaped [P][T][V][ww]); values[i] = sum_v +-|P_v| 2^(digit_bits v) mod p as ints, status[i] the OR of the V words
+    without DEC_NEGATIVE.  host=True: pvw_shamir_wide_from_digits_host (no GPU)."""
+    wd = np.ascontiguousarray(wide, dtype=np.uint64)
+    st = np.ascontiguousarray(status, dtype=np.uint32)
+    if wd.ndim < 2 or st.shape != wd.shape[:-1]:
+        raise PvwError(15, "wide must be [..][V][wide_words] and status [..][V]")
+    V, ww = int(wd.shape[-2]), int(wd.shape[-1])
+    count = st.size // V if V else 0
+    pm = _wide_modulus(plain_modulus)
+    out = np.zeros((count, WIDE_WORDS), dtype=np.uint64)
+    so = np.zeros(count, dtype=np.uint32)
+    torch = _handover_device(params, host)
+    if torch is None:
+        L = _ffi.lib()
+        _check(L.pvw_shamir_wide_from_digits_host(_ptr(pm), int(digit_bits), V, _ptr(wd), _ptr(st), ww, count, _ptr(out), _ptr(so)), L)
+    else:
+        dw = torch.from_numpy(wd.view(np.int64)).cuda()
+        ds = torch.from_numpy(st.view(np.int32)).cuda()
+        do = torch.zeros((count, WIDE_WORDS), dtype=torch.int64, device="cuda")
+        dso = torch.zeros(count, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        params._call("pvw_shamir_wide_from_digits_device", _ptr(pm), int(digit_bits), V, _dptr(dw), _dptr(ds), ww, count, _dptr(do),
+                     _dptr(dso), None)
+        params.synchronize()
+        out, so = do.cpu().numpy().view(np.uint64), dso.cpu().numpy().view(np.uint32)
+    return _wide_ints(out), so.reshape(st.shape[:-1])
+
+
 def _wide_share_matrix(indices: Sequence[int], shares, layout: str):
     """(idx, sh, S, count, strides) of the wide checked and corrected calls: the indices as words, the share matrix as uint64
     words [...][...][4], and the (secret, point) strides of `layout` in elements"""
@@ -2097,6 +2218,46 @@ def decrypt_all_party_combinations_many(cts: Sequence[PvwCiphertext], weight_row
     rep = CheckedDecryption(out, noise, status, max(x.bound for x in rows), on, wd)
     rep.valid = np.stack([x.valid for x in rows], axis=1) if NP else np.zeros((0, R), dtype=bool)
     return rep
+
+
+def decrypt_all_party_handover_wide(cts: Sequence[Sequence[PvwCiphertext]], parties: Sequence["Party"], indices: Sequence[int],
+                                    plain_modulus: int, valid=None, points=None, limb_bits: int = 52,
+                                    digit_bits: int = 64) -> Tuple[List[List[int]], np.ndarray]:
+    """EXTENSION: the handover of a wide sharing in one call (pvw_decrypt_all_handover_wide).  cts [D][NL] are the
+    old holders' re-dealt limb ciphertexts (deal_party_shares_wide's lists, holder d at party index indices[d]); `valid` masks
+    holders out; points are ints below p (None: the point 0; shamir_packed_wide_handover_points for a packed old sharing).
+    Returns (values [P][T] as ints, status uint32 [P][T]): values[j][m] = sum_d lambda_{d,m} f_d(j + 1) mod p, new party j's share
+    of the secret at points[m], from V decrypts a party and target; status is the OR of the digit decodes' status words without
+    DEC_NEGATIVE.  PvwParameters.wide_handover_fits says beforehand whether the decode is proven exact."""
+    rows = [list(r) for r in cts]
+    D, NL = len(rows), shamir_wide_limbs(plain_modulus, limb_bits)
+    if D == 0 or any(len(r) != NL for r in rows):
+        raise PvwError(15, f"expected rows of {NL} limb ciphertexts")
+    flat = [ct for r in rows for ct in r]
+    p, repr, _ = _sum_inputs(flat, None)
+    idx = _words(indices)
+    if len(idx) != D:
+        raise PvwError(15, f"indices: expected {D} holders, got {len(idx)}")
+    v = None if valid is None else np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+    if v is not None and v.shape != (D,):
+        raise PvwError(15, f"valid: expected {D} flags, got {v.size}")
+    pts = None if points is None else _wide([int(x) for x in points])
+    T, NP = (1 if pts is None else len(pts)), len(parties)
+    lo = parties[0].index if NP else 0
+    for i, party in enumerate(parties):
+        if party.index != lo + i:
+            raise PvwError(1, f"Party indices must be consecutive: {party.index} follows {lo + i - 1}")
+    out, status, count = np.zeros((NP, T, WIDE_WORDS), np.uint64), np.zeros((NP, T), np.uint32), C.c_uint32()
+    c1s = np.ascontiguousarray(np.stack([ct.c1 for ct in flat]), dtype=np.uint64)
+    c2s = np.ascontiguousarray(np.stack([ct.c2 for ct in flat]), dtype=np.uint64)
+    sk = np.ascontiguousarray(np.stack([_i64(party.secret_key.secret_coeffs) for party in parties])) if NP else np.zeros(1, np.int64)
+    try:
+        p._call("pvw_decrypt_all_handover_wide", lo, lo + NP, _ptr(sk), _ptr(c1s), _ptr(c2s), D, _ptr(_wide_modulus(plain_modulus)),
+                int(limb_bits), int(digit_bits), _ptr(idx), _ptr(v), _ptr(pts), T, repr, _ptr(out), _ptr(status), C.byref(count))
+    finally:
+        sk.fill(0)                                                         # the stacked copy of the keys (secret_key.rs:20-30)
+    vals = _wide_ints(out)
+    return [vals[j * T:(j + 1) * T] for j in range(NP)], status
 
 
 def _dptr(x):

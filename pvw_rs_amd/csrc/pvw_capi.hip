@@ -156,6 +156,10 @@ struct Workspace {
   size_t packw_bytes = 0;
   u64* packw_wide = nullptr; // the same over a prime below 2^256 (shamir_packed_wide_words; public, grown by the call)
   size_t packw_wide_bytes = 0;
+  u64* handover_wide = nullptr;  // wide handover: points | column weights | a group's scale, Cauchy entries, coin | column map
+  size_t handover_wide_bytes = 0;   // (shamir_handover_wide_words; public, grown by the call)
+  u64* handover_io = nullptr;    // wide handover on device pointers: weight rows (public) | the digit report [P][R] (HandoverIo; secret)
+  size_t handover_io_bytes = 0;
   u64* correct = nullptr;    // corrected reconstruction: M | public matrices | syndromes | locators (CorrectLayout; grown by the call)
   size_t correct_bytes = 0;
   u64* correct_wide = nullptr;   // the same over a prime below 2^256 (CorrectWideLayout)
@@ -654,6 +658,9 @@ static void ws_free(Workspace* w) {
   hipFree(w->interp_wide);
   hipFree(w->packw);
   hipFree(w->packw_wide);
+  hipFree(w->handover_wide);
+  if (w->handover_io) hipMemset(w->handover_io, 0, w->handover_io_bytes);   // the last report, if its wipe did not run
+  hipFree(w->handover_io);
   if (w->correct) hipMemset(w->correct, 0, w->correct_bytes);   // M of the last call, if its wipe did not run
   hipFree(w->correct);
   if (w->correct_wide) hipMemset(w->correct_wide, 0, w->correct_wide_bytes);
@@ -5476,6 +5483,302 @@ int32_t pvw_shamir_evaluate_wide_erasures(pvw_ctx* c, const uint64_t* plain_modu
   return evaluate_wide_host_call(c, r, shares, erased, targets, num_targets, values, out, nerr, col_err, err_mask);
 }
 
+// ------------------------------------------------------------------------ handover over a prime below 2^256
+// The public arithmetic either side of one pass of int64 combinations: the weight rows (signed digits of
+// lambda_{d,m} 2^(limb_bits w) mod p) and the fold of the decrypted digit plaintexts.  The host forms run the scaled step of
+// pvw_wide.h (the kernels run Montgomery's product) and prefix / suffix products (the kernels run the Cauchy entries of 8.22).
+static_assert(DEC_NEGATIVE == PVW_DEC_NEGATIVE && PVW_DEC_NEGATIVE == 2, "shamir_wide_from_digits_kernel tests this bit");
+#define PVW_WIDE_MAX_DIGITS 33                           // ceil(257 / 8): the digits of a 256-bit prime at digit_bits = 8
+
+static int32_t digit_bits_check(uint32_t digit_bits) {
+  if (digit_bits < 8 || digit_bits > 64) return fail(PVW_ERR_INVALID_PARAMETERS, "digit_bits must be in [8, 64]");
+  return PVW_OK;
+}
+int32_t pvw_shamir_wide_handover_shape(const uint64_t* plain_modulus, uint32_t limb_bits, uint32_t digit_bits, uint32_t* num_limbs,
+                                       uint32_t* num_digits) {
+  if (!plain_modulus || !num_limbs || !num_digits) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  WideMod m;
+  PVW_TRY(wide_modulus_check(plain_modulus, &m));
+  uint32_t nl = 0;
+  PVW_TRY(wide_limb_count(m, limb_bits, &nl));
+  PVW_TRY(digit_bits_check(digit_bits));
+  *num_limbs = nl;
+  *num_digits = wide_signed_digit_count(m.bits, digit_bits);
+  return PVW_OK;
+}
+
+static int32_t signed_digits_checks(const uint64_t* p, const void* values, size_t count, uint32_t digit_bits, const void* digits, WideMod* m) {
+  if (!p || ((!values || !digits) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(digit_bits_check(digit_bits));
+  return wide_modulus_check(p, m);
+}
+int32_t pvw_shamir_wide_signed_digits_host(const uint64_t* plain_modulus, const uint64_t* values, size_t count, uint32_t digit_bits,
+                                           int64_t* digits) {
+  WideMod m;
+  PVW_TRY(signed_digits_checks(plain_modulus, values, count, digit_bits, digits, &m));
+  const u32 V = wide_signed_digit_count(m.bits, digit_bits);
+  const u64 p[4] = {plain_modulus[0], plain_modulus[1], plain_modulus[2], plain_modulus[3]};
+  for (size_t i = 0; i < count; ++i) {
+    Wide r;
+    wide_reduce(r, values + i * 4, m);
+    u64 x[4];
+    wide_unscale(x, r, m);
+    wide_signed_digits(x, p, digit_bits, V, (i64*)digits + i * V, 1);
+  }
+  return PVW_OK;
+}
+int32_t pvw_shamir_wide_signed_digits_device(pvw_ctx* c, const uint64_t* plain_modulus, const uint64_t* d_values, size_t count,
+                                             uint32_t digit_bits, int64_t* d_digits, void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  WideMod m;
+  PVW_TRY(signed_digits_checks(plain_modulus, d_values, count, digit_bits, d_digits, &m));
+  if (!count) return PVW_OK;
+  PVW_TRY(ensure_device(c));
+  const hipStream_t s = call_stream(c, stream);
+  ProfScope ps(c, "shamir_wide_signed_digits", s);
+  PVW_HIP(launch_shamir_signed_digits_wide(d_values, count, digit_bits, wide_signed_digit_count(m.bits, digit_bits), (i64*)d_digits,
+                                           make_wide_mont(plain_modulus), s));
+  return PVW_OK;
+}
+
+// One call's arguments behind their checks: the valid holders compacted (their indices and the holder each of them is), the
+// target points resolved (NULL: the point 0)
+struct HandoverWide {
+  const u64* p;
+  const u64* indices;
+  const uint8_t* valid;
+  size_t D;
+  const u64* points;
+  size_t T;
+  u32 limb_bits, digit_bits;
+  WideMod m{};
+  u32 NL = 0, V = 0;
+  std::vector<u64> vidx, pts;
+  std::vector<u32> col;
+  size_t nv() const { return vidx.size(); }
+  size_t ld() const { return D * NL; }
+  size_t rows() const { return T * V; }
+};
+// the order: NULL, no holders, the targets' count, digit_bits, no valid holder, what reconstruct_wide_checks says about the valid
+// subset (a duplicate, the range, the modulus), limb_bits, a point not below p, D NL, and T V on the device
+static int32_t handover_wide_checks(HandoverWide& h, const void* weights, bool device) {
+  if (!h.p || !h.indices || !weights) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (h.D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no holders");
+  if (h.T == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no target points");
+  if (!h.points && h.T != 1) return fail(PVW_ERR_INVALID_PARAMETERS, "points == NULL is the single point 0: num_points must be 1");
+  PVW_TRY(digit_bits_check(h.digit_bits));
+  if (h.D >= ((size_t)1 << 32)) return fail(PVW_ERR_INVALID_PARAMETERS, "num_holders x num_limbs must be below 2^32");
+  for (size_t d = 0; d < h.D; ++d)
+    if (!h.valid || h.valid[d]) {
+      h.vidx.push_back(h.indices[d]);
+      h.col.push_back((u32)d);
+    }
+  if (h.vidx.empty()) return fail(PVW_ERR_INVALID_PARAMETERS, "no valid holder");
+  ReconstructWide r{h.p, 0, h.vidx.data(), h.vidx.size(), 1, 1, 1, WideMod{}};
+  PVW_TRY(reconstruct_wide_checks(r, weights, weights));
+  h.m = r.m;
+  PVW_TRY(wide_limb_count(h.m, h.limb_bits, &h.NL));
+  h.V = wide_signed_digit_count(h.m.bits, h.digit_bits);
+  h.pts.assign(h.T * 4, 0);
+  if (h.points) {
+    const u64 pw[4] = {h.p[0], h.p[1], h.p[2], h.p[3]};
+    for (size_t j = 0; j < h.T; ++j) {
+      const u64 x[4] = {h.points[j * 4], h.points[j * 4 + 1], h.points[j * 4 + 2], h.points[j * 4 + 3]};
+      if (!wide_less(x, pw)) return fail(PVW_ERR_INVALID_PARAMETERS, "a target point must be below plain_modulus (the point -m is p - m)");
+    }
+    h.pts.assign(h.points, h.points + h.T * 4);
+  }
+  if (h.D * h.NL >= ((size_t)1 << 32)) return fail(PVW_ERR_INVALID_PARAMETERS, "num_holders x num_limbs must be below 2^32");
+  if (device && h.T * h.V >= ((size_t)1 << 31)) return fail(PVW_ERR_INVALID_PARAMETERS, "num_points x num_digits must be below 2^31 on the device");
+  return PVW_OK;
+}
+static void handover_wide_weights_host(const HandoverWide& h, i64* weights) {
+  const WideMod& m = h.m;
+  const size_t nv = h.nv(), ld = h.ld();
+  const u64 p[4] = {h.p[0], h.p[1], h.p[2], h.p[3]};
+  std::fill(weights, weights + h.rows() * ld, (i64)0);
+  Wide one;
+  {
+    Wide w1;
+    wide_small(w1, 1);
+    wide_reduce(one, w1, m);
+  }
+  std::vector<u64> x(nv * 4), u(nv * 4), run(nv * 4), suf((nv + 1) * 4);
+  for (size_t i = 0; i < nv; ++i) {
+    const u64 xw[4] = {h.vidx[i] + 1, h.vidx[i] + 1 == 0 ? (u64)1 : (u64)0, 0, 0};
+    wide_reduce(&x[i * 4], xw, m);
+  }
+  // u_i = 1 / prod_{c != i}(x_i - x_c): the denominators' running products, ONE inversion, the walk back
+  for (size_t i = 0; i < nv; ++i) {
+    Wide den, d;
+    wide_set(den, one);
+    for (size_t c = 0; c < nv; ++c)
+      if (c != i) {
+        wide_set(d, &x[i * 4]);
+        wide_submod(d, &x[c * 4], m);
+        wide_mulmod_scaled(den, den, d, m);
+      }
+    wide_set(&u[i * 4], den);
+    wide_mulmod_scaled(&run[i * 4], i ? &run[(i - 1) * 4] : one, den, m);
+  }
+  {
+    Wide inv;
+    wide_invmod(inv, &run[(nv - 1) * 4], h.p, m);
+    for (size_t i = nv; i-- > 0;) {
+      Wide den, ui;
+      wide_set(den, &u[i * 4]);
+      wide_mulmod_scaled(ui, inv, i ? &run[(i - 1) * 4] : one, m);
+      wide_mulmod_scaled(inv, inv, den, m);
+      wide_set(&u[i * 4], ui);
+    }
+  }
+  const u32 h0 = h.limb_bits / 2, h1 = h.limb_bits - h0;
+  const u64 zero[4] = {0, 0, 0, 0};
+  for (size_t j = 0; j < h.T; ++j) {
+    Wide xs, d;
+    wide_reduce(xs, &h.pts[j * 4], m);
+    size_t coin = SIZE_MAX;
+    for (size_t i = 0; i < nv; ++i)
+      if (!memcmp(xs, &x[i * 4], 32)) coin = i;
+    wide_set(&suf[nv * 4], one);                                 // suf[i] = prod_{c >= i}(x* - x_c)
+    for (size_t i = nv; i-- > 0;) {
+      wide_set(d, xs);
+      wide_submod(d, &x[i * 4], m);
+      wide_mulmod_scaled(&suf[i * 4], &suf[(i + 1) * 4], d, m);
+    }
+    Wide pre;
+    wide_set(pre, one);
+    for (size_t i = 0; i < nv; ++i) {
+      u64 mu[4] = {0, 0, 0, 0};
+      if (coin == SIZE_MAX) {
+        Wide v;
+        wide_mulmod_scaled(v, pre, &suf[(i + 1) * 4], m);
+        wide_mulmod_scaled(mu, v, &u[i * 4], m);
+        wide_set(d, xs);
+        wide_submod(d, &x[i * 4], m);
+        wide_mulmod_scaled(pre, pre, d, m);
+      } else if (coin == i) {
+        wide_set(mu, one);
+      }
+      i64* out = weights + j * h.V * ld + (size_t)h.col[i] * h.NL;
+      for (u32 w = 0; w < h.NL; ++w) {
+        u64 pl[4] = {mu[0], mu[1], mu[2], mu[3]};
+        wide_shr(pl, m.shift);
+        wide_signed_digits(pl, p, h.digit_bits, h.V, out + w, ld);
+        wide_step(mu, 1u << h0, zero, m);
+        wide_step(mu, 1u << h1, zero, m);
+      }
+    }
+  }
+}
+int32_t pvw_shamir_wide_handover_weights_host(const uint64_t* plain_modulus, const uint64_t* indices, const uint8_t* valid,
+                                              size_t num_holders, const uint64_t* points, size_t num_points, uint32_t limb_bits,
+                                              uint32_t digit_bits, int64_t* weights) {
+  HandoverWide h{plain_modulus, indices, valid, num_holders, points, num_points, limb_bits, digit_bits};
+  PVW_TRY(handover_wide_checks(h, weights, false));
+  handover_wide_weights_host(h, (i64*)weights);
+  return PVW_OK;
+}
+
+// targets per group: a target costs a column of C, xt, scale and coin; the budget of evaluate_wide_group
+static size_t handover_wide_group(const HandoverWide& h) {
+  const size_t per = (h.nv() + 2) * 32 + 4;
+  size_t tg = ((size_t)64 << 20) / per;
+  if (tg > 64) tg -= tg % 64;
+  if (tg == 0) tg = 1;
+  return tg < h.T ? tg : h.T;
+}
+static size_t handover_wide_ws_bytes(const HandoverWide& h) { return shamir_handover_wide_words(h.nv(), handover_wide_group(h)) * 8; }
+// the weight rows into d_weights [T V][D NL] through the public block ws (handover_wide_ws_bytes); the host arrays are consumed here
+static int32_t handover_wide_weights_enqueue(pvw_ctx* c, const HandoverWide& h, u64* ws, i64* d_weights, hipStream_t s) {
+  ProfScope ps(c, "shamir_handover_weights_wide", s);
+  const WideMont mm = make_wide_mont(h.p);
+  const size_t nv = h.nv(), Tg = handover_wide_group(h);
+  u64 *x = ws, *aux = x + nv * 4, *xt = aux + (nv + 1) * 4, *scale = xt + Tg * 4, *C = scale + Tg * 4;
+  u32 *coin = (u32*)(C + nv * Tg * 4), *col = (u32*)(C + nv * Tg * 4 + (Tg + 1) / 2);
+  PVW_HIP(launch_shamir_points_wide(h.vidx.data(), nv, x, mm, s));
+  PVW_HIP(launch_shamir_column_weights_wide(x, aux, nv, mm, s));
+  PVW_HIP(launch_shamir_handover_columns(h.col.data(), nv, col, s));
+  PVW_HIP(launch_wipe_words((u64*)d_weights, h.rows() * h.ld(), s));
+  for (size_t j0 = 0; j0 < h.T; j0 += Tg) {
+    const size_t tg = h.T - j0 < Tg ? h.T - j0 : Tg;
+    PVW_HIP(launch_shamir_points_from_wide(h.pts.data() + j0 * 4, tg, xt, mm, s));
+    PVW_HIP(launch_shamir_cauchy_wide(x, aux, xt, scale, C, coin, nv, tg, mm, s));
+    ShamirHandoverDigits a{};
+    a.scale = scale, a.C = C, a.coin = coin, a.col = col;
+    a.weights = d_weights + j0 * h.V * h.ld(), a.ld = h.ld();
+    a.nv = (u32)nv, a.Tg = (u32)tg, a.NL = h.NL, a.V = h.V, a.limb_bits = h.limb_bits, a.digit_bits = h.digit_bits, a.m = mm;
+    PVW_HIP(launch_shamir_handover_digits_wide(a, s));
+  }
+  return PVW_OK;
+}
+static const char* const kHandoverWeightsUnsized =
+    "wide handover weights under stream capture: run a call with at least as many valid holders and target points on this stream "
+    "outside capture first (it sizes the workspace)";
+int32_t pvw_shamir_wide_handover_weights_device(pvw_ctx* c, const uint64_t* plain_modulus, const uint64_t* indices, const uint8_t* valid,
+                                                size_t num_holders, const uint64_t* points, size_t num_points, uint32_t limb_bits,
+                                                uint32_t digit_bits, int64_t* d_weights, void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  HandoverWide h{plain_modulus, indices, valid, num_holders, points, num_points, limb_bits, digit_bits};
+  PVW_TRY(handover_wide_checks(h, d_weights, true));
+  const size_t need = handover_wide_ws_bytes(h);
+  auto sized = [&](hipStream_t s) { return grown_capture_check(c, s, &Workspace::handover_wide_bytes, need, kHandoverWeightsUnsized); };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
+    PVW_TRY(ws_grow(&w->handover_wide, &w->handover_wide_bytes, need, s, false));   // public: nothing to clear
+    return handover_wide_weights_enqueue(c, h, w->handover_wide, (i64*)d_weights, s);
+  });
+}
+
+static int32_t from_digits_checks(const uint64_t* p, uint32_t digit_bits, uint32_t num_digits, const void* wide, const void* status,
+                                  uint32_t ww, size_t count, const void* out, const void* status_out, WideMod* m) {
+  if (!p || ((!wide || !status || !out || !status_out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(digit_bits_check(digit_bits));
+  if (num_digits < 1 || num_digits > PVW_WIDE_MAX_DIGITS) return fail(PVW_ERR_INVALID_PARAMETERS, "num_digits must be in [1, 33]");
+  if (ww < 1 || ww > 4) return fail(PVW_ERR_INVALID_PARAMETERS, "wide_words must be in [1, 4]");
+  return wide_modulus_check(p, m);
+}
+int32_t pvw_shamir_wide_from_digits_host(const uint64_t* plain_modulus, uint32_t digit_bits, uint32_t num_digits, const uint64_t* wide,
+                                         uint32_t* status, uint32_t wide_words, size_t count, uint64_t* out, uint32_t* status_out) {
+  WideMod m;
+  PVW_TRY(from_digits_checks(plain_modulus, digit_bits, num_digits, wide, status, wide_words, count, out, status_out, &m));
+  const u64 zero[4] = {0, 0, 0, 0};
+  for (size_t i = 0; i < count; ++i) {
+    u64 acc[4] = {0, 0, 0, 0};
+    u32 st = 0;
+    for (u32 v = num_digits; v-- > 0;) {
+      u64 mag[4] = {0, 0, 0, 0};
+      for (u32 k = 0; k < wide_words; ++k) mag[k] = wide[(i * num_digits + v) * wide_words + k];
+      const u32 sv = status[i * num_digits + v];
+      st |= sv;
+      Wide r;
+      wide_reduce(r, mag, m);
+      if (sv & PVW_DEC_NEGATIVE) wide_negmod(r, m);
+      u32 rem = digit_bits;
+      for (; rem > 31; rem -= 31) wide_step(acc, 1u << 31, zero, m);
+      wide_step(acc, 1u << rem, *(const u64(*)[4])r, m);
+    }
+    wide_shr(acc, m.shift);
+    for (int k = 0; k < 4; ++k) out[i * 4 + k] = acc[k];
+    status_out[i] = st & ~(u32)PVW_DEC_NEGATIVE;
+  }
+  return PVW_OK;
+}
+int32_t pvw_shamir_wide_from_digits_device(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t digit_bits, uint32_t num_digits,
+                                           const uint64_t* d_wide, uint32_t* d_status, uint32_t wide_words, size_t count,
+                                           uint64_t* d_out, uint32_t* d_status_out, void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  WideMod m;
+  PVW_TRY(from_digits_checks(plain_modulus, digit_bits, num_digits, d_wide, d_status, wide_words, count, d_out, d_status_out, &m));
+  if (!count) return PVW_OK;
+  PVW_TRY(ensure_device(c));
+  const hipStream_t s = call_stream(c, stream);
+  ProfScope ps(c, "shamir_wide_from_digits", s);
+  PVW_HIP(launch_shamir_wide_from_digits(d_wide, d_status, count, num_digits, wide_words, digit_bits, d_out, d_status_out, m,
+                                         make_wide_mont(plain_modulus), s));
+  return PVW_OK;
+}
+
 // The mask of wide shares from a per-limb decrypt report: bit (s, c) set iff for some w < num_limbs the element at
 // s * secret_stride + c * point_stride + w * limb_stride has status & status_bits or noise > noise_bound.  The checks of
 // erasure_mask_checks first, in its order, then the two limb arguments.
@@ -7343,6 +7646,164 @@ int32_t pvw_ctx_lincomb_fits(const pvw_ctx* c, const int64_t* weights, size_t D,
     if (takes_part(valid, weights, d)) sum = sum + BigInt(weights[d] < 0 ? (u64)0 - (u64)weights[d] : (u64)weights[d]);
   *fits = sum * BigInt(nb) <= R ? 1u : 0u;
   return PVW_OK;
+}
+// the words a digit plaintext of the wide handover takes: |P_v| < num_valid NL 2^(b - 1) 2^limb_bits
+static u32 handover_wide_words(size_t num_valid, u32 NL, u32 limb_bits, u32 digit_bits) {
+  const u64 terms = (u64)num_valid * NL;
+  u32 lg = 0;
+  while (lg < 64 && ((u64)1 << lg) < terms) ++lg;                  // ceil(log2(terms))
+  return (limb_bits + digit_bits + lg + 1 + 63) / 64;
+}
+// Advisory, pvw_ctx_lincomb_fits for the rows of a wide handover without the rows: every weight is a signed digit of digit_bits
+// bits, so num_valid NL 2^(digit_bits - 1) bounds a row's absolute sum; and the digit plaintexts must fit the words of Q.
+int32_t pvw_ctx_wide_handover_fits(const pvw_ctx* c, const uint64_t* plain_modulus, size_t num_valid, uint32_t limb_bits,
+                                   uint32_t digit_bits, uint32_t* fits) {
+  if (!c || !plain_modulus || !fits) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (num_valid == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no valid holder");
+  WideMod m;
+  PVW_TRY(wide_modulus_check(plain_modulus, &m));
+  uint32_t NL = 0;
+  PVW_TRY(wide_limb_count(m, limb_bits, &NL));
+  PVW_TRY(digit_bits_check(digit_bits));
+  uint64_t nb = 0;
+  PVW_TRY(pvw_ctx_noise_bound(c, &nb));
+  const BigInt R = (c->Q - BigInt(1)) / ((c->delta_pow + BigInt(1)) * BigInt(2));
+  const BigInt sum = BigInt((u64)num_valid) * BigInt((u64)NL) * BigInt((u64)1 << (digit_bits - 1));
+  *fits = (sum * BigInt(nb) <= R && handover_wide_words(num_valid, NL, limb_bits, digit_bits) <= c->Q.mag.size()) ? 1u : 0u;
+  return PVW_OK;
+}
+
+// Every new party's new share from the old holders' limb ciphertexts in one call: the weight rows by the kernels
+// of pvw_shamir_wide_handover_weights_device, the many-combinations call of 8.15 as it is with R = T V rows over the D NL
+// vectors and wide_words = ww, and the fold of pvw_shamir_wide_from_digits_device over its report, read in place.  The weights
+// and the combined ciphertexts are public; the report [P][R] (values, words, status) depends on the shares: it is marked secret
+// and cleared behind the fold.  The keys are staged, marked and cleared by the many-combinations call itself.
+struct HandoverIo {
+  size_t NP, R, ww, ld;
+  size_t b_w, b_res, b_wide, b_st;
+  HandoverIo(size_t NP_, const HandoverWide& h, size_t ww_) : NP(NP_), R(h.rows()), ww(ww_), ld(h.ld()) {
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    b_w = up(R * ld * 8), b_res = up(NP * R * 8), b_wide = up(NP * R * ww * 8), b_st = up(NP * R * 4);
+  }
+  size_t report_bytes() const { return b_res + b_wide + b_st; }
+  size_t total() const { return b_w + report_bytes(); }
+  i64* weights(char* base) const { return (i64*)base; }
+  u64* res(char* base) const { return (u64*)(base + b_w); }
+  u64* wide(char* base) const { return (u64*)(base + b_w + b_res); }
+  u32* status(char* base) const { return (u32*)(base + b_w + b_res + b_wide); }
+};
+// the order: NULL, the checks of the weights, the words of Q, then what the many-combinations call refuses about its arguments
+static int32_t handover_all_checks(pvw_ctx* c, u32 lo, u32 hi, const void* sk, const void* c1s, const void* c2s, HandoverWide& h,
+                                   uint32_t in_repr, const void* out, const void* status, bool device, u32* ww) {
+  if (!c || !out || !status) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(handover_wide_checks(h, out, device));
+  *ww = handover_wide_words(h.nv(), h.NL, h.limb_bits, h.digit_bits);
+  if (*ww > c->Q.mag.size()) {
+    char buf[128];
+    snprintf(buf, sizeof buf, "the digit plaintexts of this handover take %u words, Q has %zu: choose narrower digits", *ww, c->Q.mag.size());
+    return fail(PVW_ERR_INVALID_PARAMETERS, buf);
+  }
+  PVW_TRY(decrypt_all_checks(c, lo, hi, sk, c1s, c2s, h.ld(), in_repr, out));
+  PVW_TRY(check_dealers(h.ld(), true));
+  return combos_check(h.rows(), device);
+}
+static const char* const kHandoverUnsized =
+    "wide handover under stream capture: run a call with the same party range, at least as many valid holders, target points and "
+    "vectors on this stream outside capture first (it sizes the scratch)";
+// what pvw_decrypt_all_lincomb_many_plain_device asks of a capturing stream, asked before anything of the handover is enqueued
+static int32_t handover_many_capture_check(pvw_ctx* c, hipStream_t s, size_t NP, size_t R, size_t ww) {
+  if (R == 1) return sum_capture_check(c, s, sum_dpart_need(c), decrypt_all_sum_need(c, NP, ww));
+  const ManyLayout m = decrypt_all_many_layout(c, NP, R, ww, 0);
+  PVW_TRY(grown_capture_check(c, s, &Workspace::scratch_bytes, m.sc.total, kHandoverUnsized));
+  return sum_capture_check(c, s, 0, 0);
+}
+int32_t pvw_decrypt_all_handover_wide_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
+                                             const uint64_t* d_c2s, size_t num_dealers, const uint64_t* plain_modulus, uint32_t limb_bits,
+                                             uint32_t digit_bits, const uint64_t* indices, const uint8_t* valid, const uint64_t* points,
+                                             size_t num_points, uint32_t in_repr, uint64_t* d_out, uint32_t* d_status, uint32_t* d_count,
+                                             void* stream) {
+  HandoverWide h{plain_modulus, indices, valid, num_dealers, points, num_points, limb_bits, digit_bits};
+  u32 ww = 0;
+  PVW_TRY(handover_all_checks(c, lo, hi, d_sk, d_c1s, d_c2s, h, in_repr, d_out, d_status, true, &ww));
+  const size_t NP = (size_t)hi - lo;
+  const HandoverIo io(NP, h, ww);
+  const size_t pub_need = handover_wide_ws_bytes(h);
+  auto sized = [&](hipStream_t s) -> int32_t {
+    PVW_TRY(grown_capture_check(c, s, &Workspace::handover_wide_bytes, pub_need, kHandoverUnsized));
+    PVW_TRY(grown_capture_check(c, s, &Workspace::handover_io_bytes, io.total(), kHandoverUnsized));
+    return handover_many_capture_check(c, s, NP, io.R, ww);
+  };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  char* base = nullptr;
+  PVW_TRY(device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
+    PVW_TRY(ws_grow(&w->handover_wide, &w->handover_wide_bytes, pub_need, s, false));
+    if (w->handover_io_bytes < io.total()) ws_public(w, w->handover_io, w->handover_io_bytes);   // the block is about to go
+    PVW_TRY(ws_grow(&w->handover_io, &w->handover_io_bytes, io.total(), s, true));
+    base = (char*)w->handover_io;
+    return handover_wide_weights_enqueue(c, h, w->handover_wide, io.weights(base), s);
+  }));
+  const int32_t rc = pvw_decrypt_all_lincomb_many_plain_device(c, lo, hi, d_sk, d_c1s, d_c2s, io.ld, nullptr, io.weights(base), io.R, in_repr,
+                                                               io.res(base), nullptr, io.status(base), nullptr, 0, ww, io.wide(base), stream);
+  const WideMont mm = make_wide_mont(plain_modulus);
+  return device_call(c, stream, [&](Workspace* w, hipStream_t s) -> int32_t {
+    ws_mark_secret(w, io.res(base), io.report_bytes());              // cleared by device_end, also behind a pass that failed
+    if (rc != PVW_OK) return rc;
+    ProfScope ps(c, "shamir_wide_from_digits", s);
+    PVW_HIP(launch_shamir_wide_from_digits(io.wide(base), io.status(base), NP * h.T, h.V, ww, h.digit_bits, d_out, d_status, h.m, mm, s));
+    const u32 nv = (u32)h.nv();
+    if (d_count) PVW_HIP(launch_shamir_handover_columns(&nv, 1, d_count, s));
+    return PVW_OK;
+  });
+}
+// host buffers: the weights by the same kernels on a pooled workspace, the many-combinations call on host buffers (its staging
+// in pieces, its key hygiene), the fold by its kernel on a pooled workspace; the host copies of the report are wiped
+int32_t pvw_decrypt_all_handover_wide(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
+                                      size_t num_dealers, const uint64_t* plain_modulus, uint32_t limb_bits, uint32_t digit_bits,
+                                      const uint64_t* indices, const uint8_t* valid, const uint64_t* points, size_t num_points,
+                                      uint32_t in_repr, uint64_t* out, uint32_t* status, uint32_t* count) {
+  HandoverWide h{plain_modulus, indices, valid, num_dealers, points, num_points, limb_bits, digit_bits};
+  u32 ww = 0;
+  PVW_TRY(handover_all_checks(c, lo, hi, sk, c1s, c2s, h, in_repr, out, status, false, &ww));
+  PVW_TRY(ensure_device(c));
+  const size_t NP = (size_t)hi - lo, R = h.rows(), ld = h.ld(), cnt = NP * h.T;
+  std::vector<i64> wts(R * ld);
+  {
+    Scratch sc;
+    const size_t r_pub = sc.add(handover_wide_ws_bytes(h)), r_w = sc.add(R * ld * 8);
+    PVW_TRY(host_call(c, [&](Workspace* w) -> int32_t {
+      PVW_TRY(sc.take(w));
+      PVW_TRY(handover_wide_weights_enqueue(c, h, sc.at(r_pub), sc.at<i64>(r_w), w->stream));
+      PVW_HIP(hipMemcpyAsync(wts.data(), sc.at(r_w), R * ld * 8, hipMemcpyDeviceToHost, w->stream));
+      return PVW_OK;
+    }));
+  }
+  std::vector<u64> res(NP * R), wide(NP * R * ww);
+  std::vector<u32> st(NP * R);
+  int32_t rc = pvw_decrypt_all_lincomb_many_plain(c, lo, hi, sk, c1s, c2s, ld, nullptr, wts.data(), R, in_repr, res.data(), nullptr, st.data(),
+                                                  nullptr, 0, ww, wide.data());
+  if (rc == PVW_OK) {
+    const WideMont mm = make_wide_mont(plain_modulus);
+    Scratch sc;
+    const size_t r_wide = sc.add(wide.size() * 8), r_st = sc.add(st.size() * 4), r_out = sc.add(cnt * 32), r_so = sc.add(cnt * 4);
+    rc = host_call(c, [&](Workspace* w) -> int32_t {
+      PVW_TRY(sc.take(w));
+      sc.secret(w, r_wide, r_so);
+      PVW_HIP(hipMemcpyAsync(sc.at(r_wide), wide.data(), wide.size() * 8, hipMemcpyHostToDevice, w->stream));
+      PVW_HIP(hipMemcpyAsync(sc.at(r_st), st.data(), st.size() * 4, hipMemcpyHostToDevice, w->stream));
+      ProfScope ps(c, "shamir_wide_from_digits", w->stream);
+      PVW_HIP(launch_shamir_wide_from_digits(sc.at(r_wide), sc.at<u32>(r_st), cnt, h.V, ww, h.digit_bits, sc.at(r_out), sc.at<u32>(r_so), h.m, mm,
+                                             w->stream));
+      PVW_HIP(hipMemcpyAsync(out, sc.at(r_out), cnt * 32, hipMemcpyDeviceToHost, w->stream));
+      PVW_HIP(hipMemcpyAsync(status, sc.at(r_so), cnt * 4, hipMemcpyDeviceToHost, w->stream));
+      return PVW_OK;
+    });
+  }
+  volatile u64* vp = wide.data();
+  for (size_t i = 0; i < wide.size(); ++i) vp[i] = 0;
+  vp = res.data();
+  for (size_t i = 0; i < res.size(); ++i) vp[i] = 0;
+  if (rc == PVW_OK && count) *count = (uint32_t)h.nv();
+  return rc;
 }
 
 // ------------------------------------------------------------------------ key generation

@@ -521,6 +521,41 @@ hipError_t launch_shamir_ym_wide(const u64* shares, size_t secret_stride, size_t
                                  const WideMont& m, hipStream_t s);
 hipError_t launch_shamir_evaluate_finish_wide(const ShamirEvalFinishWide& f, hipStream_t s);
 
+// ---- Handover over a prime below 2^256 (pvw_shamir.hip): the int64 weight rows of a ct_lincomb_many pass from the
+// signed digits of lambda_{d,m} 2^(limb_bits w) mod p, and the fold of the decrypted digit plaintexts.  Public workspace words of
+// nv valid holders and a group of Tg targets, all elements times R:
+//   x [nv][4] | aux [nv + 1][4] | xt [Tg][4] | scale [Tg][4] | C [nv][Tg][4] | coin [Tg] (u32) | col [nv] (u32)
+#define PVW_SHAMIR_WIDE_POINTS 64                        // target points per launch of the point upload (kernel arguments)
+struct ShamirWidePoints {
+  u64 pt[PVW_SHAMIR_WIDE_POINTS][4];   // points below p
+  u64* x;                              // where the first of them goes, times R
+  u32 n;
+};
+inline size_t shamir_handover_wide_words(size_t nv, size_t Tg) {
+  return 4 * (2 * nv + 1 + 2 * Tg + nv * Tg) + (Tg + 1) / 2 + (nv + 1) / 2;
+}
+struct ShamirHandoverDigits {
+  const u64* scale;      // [Tg][4]
+  const u64* C;          // [nv][Tg][4]
+  const u32* coin;       // [Tg]
+  const u32* col;        // [nv]: the holder (of all D) that valid holder i is
+  i64* weights;          // row j V + v of the group, column d NL + w: weights[(j V + v) ld + d NL + w]; zeroed by the caller
+  size_t ld;             // D NL
+  u32 nv, Tg, NL, V, limb_bits, digit_bits;
+  WideMont m;
+};
+hipError_t launch_shamir_points_from_wide(const u64* points, size_t count, u64* x, const WideMont& m, hipStream_t s);
+hipError_t launch_shamir_handover_columns(const u32* col, size_t count, u32* d_col, hipStream_t s);
+hipError_t launch_shamir_column_weights_wide(const u64* x, u64* aux, size_t count, const WideMont& m, hipStream_t s);
+hipError_t launch_shamir_cauchy_wide(const u64* x, const u64* aux, const u64* xt, u64* scale, u64* C, u32* coin, size_t count, size_t Tg,
+                                     const WideMont& m, hipStream_t s);
+hipError_t launch_shamir_handover_digits_wide(const ShamirHandoverDigits& a, hipStream_t s);
+// digits [count][V] of values [count][4] (any words, read mod p)
+hipError_t launch_shamir_signed_digits_wide(const u64* values, size_t count, u32 b, u32 V, i64* digits, const WideMont& m, hipStream_t s);
+// out[i] = sum_v +-wide[i][v][ww] 2^(b v) mod p, status_out[i] = OR_v status[i][v] without PVW_DEC_NEGATIVE
+hipError_t launch_shamir_wide_from_digits(const u64* wide, const u32* status, size_t count, u32 V, u32 ww, u32 b, u64* out, u32* status_out,
+                                          const WideMod& m, const WideMont& mm, hipStream_t s);
+
 // p[0 .. words) = 0, as a kernel launch on s
 hipError_t launch_wipe_words(u64* p, size_t words, hipStream_t s);
 

@@ -2628,4 +2628,177 @@ hipError_t launch_shamir_packed_wide_weights(u64* ws, u32 pack, u32 party_lo, u3
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------ handover over a prime below 2^256
+// The public arithmetic either side of one ct_lincomb_many pass.  A Lagrange weight of 256 bits cannot multiply a ciphertext
+// (int64 weights, and the noise would grow by 2^255), but its signed digits of b <= 64 bits can: row m V + v of the weight
+// matrix holds digit v of mu_{d,w} = lambda_{d,m} 2^(limb_bits w) mod p at column d NL + w, the combined ciphertext of that row
+// decrypts to P_v = sum_{d,w} c_{d,w,v} limb_{d,w}, and sum_v P_v B^v mod p is the new share.  These kernels stand at the END of
+// the file, like those of 8.23: nothing before them moves in the code object.  The cut itself is wide_signed_digits (pvw_wide.h).
+
+// x[i] = pt[i] R mod p for target points below p that travel as kernel arguments (shamir_points_wide_kernel takes indices)
+__global__ __launch_bounds__(PVW_SHAMIR_WIDE_POINTS) void shamir_points_from_wide_kernel(ShamirWidePoints a, WideMont m) {
+  if (threadIdx.x >= a.n) return;
+  const u64 x[4] = {a.pt[threadIdx.x][0], a.pt[threadIdx.x][1], a.pt[threadIdx.x][2], a.pt[threadIdx.x][3]};
+  u64 xm[4];
+  wide_mont_in(x, m, xm);
+  wide_st(a.x + (size_t)threadIdx.x * 4, xm);
+}
+hipError_t launch_shamir_points_from_wide(const u64* points, size_t count, u64* x, const WideMont& m, hipStream_t s) {
+  for (size_t i0 = 0; i0 < count; i0 += PVW_SHAMIR_WIDE_POINTS) {
+    ShamirWidePoints a;
+    a.n = (u32)(count - i0 < PVW_SHAMIR_WIDE_POINTS ? count - i0 : PVW_SHAMIR_WIDE_POINTS);
+    for (u32 i = 0; i < PVW_SHAMIR_WIDE_POINTS; ++i)
+      for (int k = 0; k < 4; ++k) a.pt[i][k] = i < a.n ? points[(i0 + i) * 4 + k] : 0;
+    a.x = x + i0 * 4;
+    shamir_points_from_wide_kernel<<<dim3(1), dim3(PVW_SHAMIR_WIDE_POINTS), 0, s>>>(a, m);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// col[i] = the holder that valid holder i is, from kernel arguments like the points (the compaction is the host's)
+__global__ __launch_bounds__(PVW_SHAMIR_POINTS) void shamir_handover_columns_kernel(ShamirPoints a) {
+  if (threadIdx.x < a.n) ((u32*)a.x)[threadIdx.x] = (u32)a.index[threadIdx.x];
+}
+hipError_t launch_shamir_handover_columns(const u32* col, size_t count, u32* d_col, hipStream_t s) {
+  for (size_t i0 = 0; i0 < count; i0 += PVW_SHAMIR_POINTS) {
+    ShamirPoints a;
+    a.n = (u32)(count - i0 < PVW_SHAMIR_POINTS ? count - i0 : PVW_SHAMIR_POINTS);
+    for (u32 i = 0; i < PVW_SHAMIR_POINTS; ++i) a.index[i] = i < a.n ? col[i0 + i] : 0;
+    a.x = (u64*)(d_col + i0);                              // i0 is a multiple of 256: aligned
+    shamir_handover_columns_kernel<<<dim3(1), dim3(PVW_SHAMIR_POINTS), 0, s>>>(a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// u_i = (prod_{c != i}(x_i - x_c))^-1 over ALL count columns into aux[0 .. count) (aux[count] = prod_c(-x_c)): the first kernel of
+// launch_shamir_correct_weights_wide alone, as it is
+hipError_t launch_shamir_column_weights_wide(const u64* x, u64* aux, size_t count, const WideMont& m, hipStream_t s) {
+  shamir_prod_wide_kernel<<<dim3((unsigned)((count + 1 + SH_WAVES - 1) / SH_WAVES)), dim3(256), 0, s>>>(x, aux, count, (u32)count - 1, m);
+  return hipGetLastError();
+}
+// scale, coin and C of a group of Tg targets at xt, as they are (the first two launches of launch_shamir_evaluate_weights_wide)
+hipError_t launch_shamir_cauchy_wide(const u64* x, const u64* aux, const u64* xt, u64* scale, u64* C, u32* coin, size_t count, size_t Tg,
+                                     const WideMont& m, hipStream_t s) {
+  const u32 n = (u32)count, tg = (u32)Tg;
+  shamir_target_scale_wide_kernel<<<dim3((tg + SH_WAVES - 1) / SH_WAVES), dim3(256), 0, s>>>(x, xt, scale, coin, n, tg, m);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const size_t threads = ((count + SHW_WG - 1) / SHW_WG) * Tg;
+  shamir_cauchy_wide_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>(x, aux, xt, C, n, tg, m);
+  return hipGetLastError();
+}
+
+// One thread per (valid holder i, target j), the holder fastest: the lanes of a wave store along a weight row, NL words apart.
+// lambda = scale_j C[i][j] (times R); where the target is a valid holder's point the row is that holder's unit vector, said
+// explicitly: scale_j C[i][j] is not 0 at the other columns there.  mu_w = lambda 2^(limb_bits w) is carried along in Montgomery
+// form by one product per limb, left, centred and cut.  The matrix is zeroed before the launch: masked holders' columns stay 0.
+__global__ __launch_bounds__(256) void shamir_handover_digits_wide_kernel(ShamirHandoverDigits a) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)a.nv * a.Tg) return;
+  const u32 i = (u32)(e % a.nv), j = (u32)(e / a.nv);
+  const WideMont m = a.m;
+  u64 mu[4] = {0, 0, 0, 0};
+  const u32 c = a.coin[j];
+  if (c != PVW_SHAMIR_NO_COLUMN) {
+    if (c == i) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) mu[k] = m.one[k];
+    }
+  } else {
+    u64 sc[4], cv[4];
+    wide_ld(a.scale + (size_t)j * 4, sc);
+    wide_ld(a.C + ((size_t)i * a.Tg + j) * 4, cv);
+    wide_mont_mul(sc, cv, m, mu);
+  }
+  u64 tw[4] = {(u64)1 << a.limb_bits, 0, 0, 0};                    // limb_bits <= 62
+  wide_mont_in(tw, m, tw);
+  i64* out = a.weights + (size_t)j * a.V * a.ld + (size_t)a.col[i] * a.NL;
+  for (u32 w = 0; w < a.NL; ++w) {
+    u64 pl[4];
+    wide_mont_out(mu, m, pl);
+    wide_signed_digits(pl, m.p, a.digit_bits, a.V, out + w, a.ld);
+    wide_mont_mul(mu, tw, m, mu);
+  }
+}
+hipError_t launch_shamir_handover_digits_wide(const ShamirHandoverDigits& a, hipStream_t s) {
+  const size_t threads = (size_t)a.nv * a.Tg;
+  if (!threads) return hipSuccess;
+  shamir_handover_digits_wide_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>(a);
+  return hipGetLastError();
+}
+
+// digits[i][V] of values[i] mod p, one thread per value: the cut of the kernel above on operands of the caller's
+__global__ __launch_bounds__(256) void shamir_signed_digits_wide_kernel(const u64* values, size_t count, u32 b, u32 V, i64* digits,
+                                                                        WideMont m) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const u64 w[4] = {values[i * 4], values[i * 4 + 1], values[i * 4 + 2], values[i * 4 + 3]};
+  u64 r[4];
+  wide_reduce_p(w, m, r);
+  wide_signed_digits(r, m.p, b, V, digits + i * V, 1);
+}
+hipError_t launch_shamir_signed_digits_wide(const u64* values, size_t count, u32 b, u32 V, i64* digits, const WideMont& m, hipStream_t s) {
+  for (size_t i0 = 0; i0 < count; i0 += (size_t)1 << 30) {
+    const size_t cnt = count - i0 < ((size_t)1 << 30) ? count - i0 : (size_t)1 << 30;
+    shamir_signed_digits_wide_kernel<<<dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s>>>(values + i0 * 4, cnt, b, V, digits + i0 * V, m);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// out[i] = sum_v +-|P_{i,v}| B^v mod p, one thread per element i = (party, target): Horner from the top digit in the scaled
+// form of wide_step, acc <- acc 2^b + r with multipliers below 2^32 (2^31 as often as b takes, then the rest with the addend).
+// r is the magnitude's ww words mod p (wide_reduce_p), p - r where the decode said P < 0.  ONE status word: the OR of the V words
+// without the sign bit.
+#define SHW_DEC_NEGATIVE 2u                          // PVW_DEC_NEGATIVE (pvw_capi.hip asserts it)
+__global__ __launch_bounds__(256) void shamir_wide_from_digits_kernel(const u64* wide, const u32* status, size_t count, u32 V, u32 ww, u32 b,
+                                                                      u64* out, u32* status_out, WideMod m, WideMont mm) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const u64 zero[4] = {0, 0, 0, 0};
+  u64 acc[4] = {0, 0, 0, 0};
+  u32 st = 0;
+  for (u32 v = V; v-- > 0;) {
+    const u64* src = wide + (i * V + v) * ww;
+    const u64 mag[4] = {src[0], ww > 1 ? src[1] : 0, ww > 2 ? src[2] : 0, ww > 3 ? src[3] : 0};
+    const u32 sv = status[i * V + v];
+    st |= sv;
+    u64 r[4];
+    wide_reduce_p(mag, mm, r);
+    if ((sv & SHW_DEC_NEGATIVE) && (r[0] | r[1] | r[2] | r[3])) {
+      u64 br = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const u64 s1 = mm.p[k] - r[k], s2 = s1 - br;
+        br = (mm.p[k] < r[k]) | (s1 < br);
+        r[k] = s2;
+      }
+    }
+    wide_shl(r, m.shift);
+    u32 rem = b;
+    for (; rem > 31; rem -= 31) wide_step(acc, 1u << 31, zero, m);
+    wide_step(acc, 1u << rem, r, m);
+  }
+  wide_shr(acc, m.shift);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) out[i * 4 + k] = acc[k];
+  status_out[i] = st & ~SHW_DEC_NEGATIVE;
+}
+hipError_t launch_shamir_wide_from_digits(const u64* wide, const u32* status, size_t count, u32 V, u32 ww, u32 b, u64* out, u32* status_out,
+                                          const WideMod& m, const WideMont& mm, hipStream_t s) {
+  for (size_t i0 = 0; i0 < count; i0 += (size_t)1 << 30) {
+    const size_t cnt = count - i0 < ((size_t)1 << 30) ? count - i0 : (size_t)1 << 30;
+    shamir_wide_from_digits_kernel<<<dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s>>>(wide + i0 * V * ww, status + i0 * V, cnt, V, ww, b,
+                                                                                           out + i0 * 4, status_out + i0, m, mm);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 }  // namespace pvw

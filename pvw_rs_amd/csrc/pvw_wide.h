@@ -371,6 +371,60 @@ PVW_HD void wide_mont_inv(const u64 (&a)[4], const WideMont& m, u64 (&out)[4]) {
   for (int i = 0; i < 4; ++i) out[i] = r[i];
 }
 
+// ------------------------------------------------------------------------ signed digits
+// A value x below p is cut into V = ceil((bitlen(p) + 1) / b) signed digits of b bits, 8 <= b <= 64, B = 2^b: the centred residue
+// xc in (-p/2, p/2] is xc = sum_v c_v B^v with every c_v in [-B/2, B/2).  Digits 0 .. V - 2 are xc mod B taken centred, xc <- (xc - c_v) / B;
+// the top digit is what is left.  It fits: |xc| < 2^(bits - 1), a centred step takes |xc| to at most |xc| / B + 1/2, so after
+// V - 1 steps |xc| < 2^(bits - 1 - b (V - 1)) + 1/2 + 1/(2 (B - 1)) <= 2^(b - 2) + 0.51 (b V >= bits + 1): the integer is at most
+// 2^(b - 2).  (With V = ceil(bits / b) the same bound is 2^(b - 1) + 0.51 and the chain does not close: B = 4, V = 2, x = 6.)
+// xc travels as 256 bits of two's complement (|xc| < 2^255): the centred low digit is the low b bits read as signed, and
+// (xc - c) / B is the arithmetic shift plus the bit b - 1 of the low digit.  Static word indices only.
+PVW_HD u32 wide_signed_digit_count(u32 bits, u32 b) { return (bits + 1 + b - 1) / b; }
+
+// x <- the centred residue of x (below p) as two's complement over four words
+PVW_HD void wide_centre(u64 (&x)[4], const u64 (&p)[4]) {
+  u64 h[4] = {p[0], p[1], p[2], p[3]};
+  wide_shr(h, 1);                                        // floor(p / 2): x > h means x - p is the centred residue
+  if (!wide_less(h, x)) return;
+  u64 br = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const u64 s1 = x[i] - p[i], s2 = s1 - br;
+    br = (x[i] < p[i]) | (s1 < br);
+    x[i] = s2;
+  }
+}
+// the next digit of x (two's complement, four words), x <- (x - digit) / 2^b; 1 <= b <= 64
+PVW_HD i64 wide_signed_digit_next(u64 (&x)[4], u32 b) {
+  const u64 low = b == 64 ? x[0] : x[0] & (((u64)1 << b) - 1);
+  const u64 carry = (low >> (b - 1)) & 1;
+  const i64 c = b == 64 ? (i64)low : (i64)(low - (carry << b));
+  const u64 sign = (u64)((i64)x[3] >> 63);
+  if (b == 64) {
+    x[0] = x[1]; x[1] = x[2]; x[2] = x[3]; x[3] = sign;
+  } else {
+    x[0] = (x[0] >> b) | (x[1] << (64 - b));
+    x[1] = (x[1] >> b) | (x[2] << (64 - b));
+    x[2] = (x[2] >> b) | (x[3] << (64 - b));
+    x[3] = (u64)((i64)x[3] >> b);
+  }
+  u64 cy = carry;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const u64 s = x[i] + cy;
+    cy = s < cy;
+    x[i] = s;
+  }
+  return c;
+}
+// digits[v * stride] = c_v for v < V, of x below p
+PVW_HD void wide_signed_digits(const u64 (&x)[4], const u64 (&p)[4], u32 b, u32 V, i64* digits, size_t stride) {
+  u64 t[4] = {x[0], x[1], x[2], x[3]};
+  wide_centre(t, p);
+  for (u32 v = 0; v + 1 < V; ++v) digits[(size_t)v * stride] = wide_signed_digit_next(t, b);
+  digits[(size_t)(V - 1) * stride] = (i64)t[0];
+}
+
 // host: the constants of p (odd, >= 3, below 2^256), for the product above and for the step at the top
 inline WideMont make_wide_mont(const u64 p[4]) {
   WideMont m;

@@ -1427,4 +1427,105 @@ inline CheckedShares decrypt_all_party_combinations_many(const std::vector<PvwCi
   return r;
 }
 
+// ---- Handover over a prime below 2^256: the weight rows of signed digits, the fold of the digit plaintexts and the
+// call that ties them to one many-combinations pass.  The public pieces run on the host cores (the *_host entry points); the
+// device forms take device pointers and are reached through the C ABI.
+struct WideHandoverShape {
+  uint32_t num_limbs, num_digits;
+};
+inline WideHandoverShape shamir_wide_handover_shape(const Wide& plain_modulus, uint32_t limb_bits = 52, uint32_t digit_bits = 64) {
+  WideHandoverShape s{0, 0};
+  check(pvw_shamir_wide_handover_shape(plain_modulus.data(), limb_bits, digit_bits, &s.num_limbs, &s.num_digits));
+  return s;
+}
+// digits [count][V] of values [count][4] (pvw_shamir_wide_signed_digits_host)
+inline std::vector<int64_t> shamir_wide_signed_digits(const std::vector<uint64_t>& values, const Wide& plain_modulus, uint32_t digit_bits = 64) {
+  if (values.size() % PVW_WIDE_WORDS) throw PvwError(15, "four words per value");
+  const size_t count = values.size() / PVW_WIDE_WORDS;
+  std::vector<int64_t> out(count * shamir_wide_handover_shape(plain_modulus, 62, digit_bits).num_digits);
+  check(pvw_shamir_wide_signed_digits_host(plain_modulus.data(), values.data(), count, digit_bits, out.data()));
+  return out;
+}
+// the points 0, -1, .., -(pack-1) of a packed wide sharing as field elements [pack][4] (-m is p - m)
+inline std::vector<uint64_t> shamir_packed_wide_handover_points(const Wide& plain_modulus, uint32_t pack) {
+  std::vector<uint64_t> out((size_t)pack * PVW_WIDE_WORDS, 0);
+  for (uint32_t m = 1; m < pack; ++m) {
+    uint64_t br = m;
+    for (int i = 0; i < PVW_WIDE_WORDS; ++i) {
+      const uint64_t v = plain_modulus[i];
+      out[(size_t)m * PVW_WIDE_WORDS + i] = v - br;
+      br = v < br;
+    }
+  }
+  return out;
+}
+// weight rows [T V][D NL] (pvw_shamir_wide_handover_weights_host); points [T][4], empty = the single point 0
+inline std::vector<int64_t> shamir_wide_handover_weights(const std::vector<uint64_t>& indices, const Wide& plain_modulus,
+                                                         const std::vector<bool>& valid = {}, const std::vector<uint64_t>& points = {},
+                                                         uint32_t limb_bits = 52, uint32_t digit_bits = 64) {
+  if (!valid.empty() && valid.size() != indices.size()) throw PvwError(15, "valid must hold one flag per holder");
+  if (points.size() % PVW_WIDE_WORDS) throw PvwError(15, "four words per point");
+  const std::vector<uint8_t> v(valid.begin(), valid.end());
+  const size_t T = points.empty() ? 1 : points.size() / PVW_WIDE_WORDS;
+  const WideHandoverShape s = shamir_wide_handover_shape(plain_modulus, limb_bits, digit_bits);
+  std::vector<int64_t> out(T * s.num_digits * indices.size() * s.num_limbs);
+  check(pvw_shamir_wide_handover_weights_host(plain_modulus.data(), indices.data(), v.empty() ? nullptr : v.data(), indices.size(),
+                                              points.empty() ? nullptr : points.data(), T, limb_bits, digit_bits, out.data()));
+  return out;
+}
+struct WideHandoverShares {
+  std::vector<uint64_t> values;     // [count][4], fully reduced
+  std::vector<uint32_t> status;     // [count]: the OR of the digit decodes' status words without PVW_DEC_NEGATIVE
+  uint32_t count = 0;               // the valid holders (decrypt_all_party_handover_wide)
+};
+// values[i] = sum_v +-wide[i][v] 2^(digit_bits v) mod p from wide [count][V][wide_words], status [count][V]
+// (pvw_shamir_wide_from_digits_host)
+inline WideHandoverShares shamir_wide_from_digits(const std::vector<uint64_t>& wide, const std::vector<uint32_t>& status, uint32_t num_digits,
+                                                  uint32_t wide_words, const Wide& plain_modulus, uint32_t digit_bits = 64) {
+  if (num_digits == 0 || wide_words == 0 || status.size() % num_digits || wide.size() != status.size() * wide_words)
+    throw PvwError(15, "wide must hold wide_words words per status word, num_digits of them per element");
+  const size_t count = status.size() / num_digits;
+  WideHandoverShares r{std::vector<uint64_t>(count * PVW_WIDE_WORDS), std::vector<uint32_t>(count), 0};
+  std::vector<uint32_t> st(status);
+  check(pvw_shamir_wide_from_digits_host(plain_modulus.data(), digit_bits, num_digits, wide.data(), st.data(), wide_words, count, r.values.data(),
+                                         r.status.data()));
+  return r;
+}
+// whether every weight row of a wide handover is inside the radius the decode is PROVEN exact in (pvw_ctx_wide_handover_fits)
+inline bool wide_handover_fits(const std::shared_ptr<PvwParameters>& p, const Wide& plain_modulus, size_t num_valid, uint32_t limb_bits = 52,
+                               uint32_t digit_bits = 64) {
+  uint32_t fits = 0;
+  check(pvw_ctx_wide_handover_fits(p->ctx, plain_modulus.data(), num_valid, limb_bits, digit_bits, &fits));
+  return fits != 0;
+}
+// every new party's new share in one call (pvw_decrypt_all_handover_wide): cts holds the old holders' limb ciphertexts, vector
+// d NL + w limb w of holder d; values [parties][T][4]
+inline WideHandoverShares decrypt_all_party_handover_wide(const std::vector<PvwCiphertext>& cts, const std::vector<Party>& parties,
+                                                          const std::vector<uint64_t>& indices, const Wide& plain_modulus,
+                                                          const std::vector<bool>& valid = {}, const std::vector<uint64_t>& points = {},
+                                                          uint32_t limb_bits = 52, uint32_t digit_bits = 64) {
+  const SumInputs in = sum_inputs(cts, {});
+  const auto& p = cts[0].params;
+  const uint32_t NL = shamir_wide_limbs(plain_modulus, limb_bits);
+  if (indices.empty() || cts.size() != indices.size() * NL) throw PvwError(15, "num_limbs ciphertexts per holder");
+  if (!valid.empty() && valid.size() != indices.size()) throw PvwError(15, "valid must hold one flag per holder");
+  if (points.size() % PVW_WIDE_WORDS) throw PvwError(15, "four words per point");
+  const std::vector<uint8_t> v(valid.begin(), valid.end());
+  const size_t NP = parties.size(), T = points.empty() ? 1 : points.size() / PVW_WIDE_WORDS, kl = (size_t)p->k * p->l;
+  WideHandoverShares r{std::vector<uint64_t>(NP * T * PVW_WIDE_WORDS), std::vector<uint32_t>(NP * T), 0};
+  if (NP == 0) return r;
+  std::vector<int64_t> sk(NP * kl);
+  for (size_t i = 0; i < NP; ++i) {
+    if (parties[i].index >= p->n || parties[i].index != parties[0].index + i) throw PvwError(1, "Party indices must be consecutive and below n");
+    std::copy(parties[i].secret_key.secret_coeffs.begin(), parties[i].secret_key.secret_coeffs.end(), sk.begin() + i * kl);
+  }
+  const int32_t rc = pvw_decrypt_all_handover_wide(p->ctx, parties[0].index, parties[0].index + (uint32_t)NP, sk.data(), in.c1s.data(),
+                                                   in.c2s.data(), indices.size(), plain_modulus.data(), limb_bits, digit_bits, indices.data(),
+                                                   v.empty() ? nullptr : v.data(), points.empty() ? nullptr : points.data(), T, cts[0].repr,
+                                                   r.values.data(), r.status.data(), &r.count);
+  std::fill(sk.begin(), sk.end(), 0);                                   // the copied keys do not outlive the call
+  check(rc);
+  return r;
+}
+
 }  // namespace pvw_host

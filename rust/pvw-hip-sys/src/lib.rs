@@ -185,6 +185,17 @@ extern "C" {
     pub fn pvw_deal_shares_packed_wide_rs(ctx: *mut PvwCtx, secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: *const u64, limb_bits: u32, st: *mut c_void, c1_out: *mut u64, c2_out: *mut u64, out_repr: u32) -> i32;
     pub fn pvw_deal_shares_packed_wide_rs_device(ctx: *mut PvwCtx, d_secrets: *const u64, num_dealers: usize, pack: u32, degree: u32, plain_modulus: *const u64, limb_bits: u32, st: *mut c_void, d_c1: *mut u64, d_c2: *mut u64, out_repr: u32, stream: *mut c_void) -> i32;
     pub fn pvw_shamir_reconstruct_packed_wide(plain_modulus: *const u64, pack: u32, indices: *const u64, shares: *const u64, count: usize, num_rows: usize, out: *mut u64) -> i32;
+    // ---- handover over a prime below 2^256: weight rows of signed digits, the fold of the digit plaintexts ----
+    pub fn pvw_shamir_wide_handover_shape(plain_modulus: *const u64, limb_bits: u32, digit_bits: u32, num_limbs: *mut u32, num_digits: *mut u32) -> i32;
+    pub fn pvw_shamir_wide_signed_digits_host(plain_modulus: *const u64, values: *const u64, count: usize, digit_bits: u32, digits: *mut i64) -> i32;
+    pub fn pvw_shamir_wide_signed_digits_device(ctx: *mut PvwCtx, plain_modulus: *const u64, d_values: *const u64, count: usize, digit_bits: u32, d_digits: *mut i64, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_wide_handover_weights_host(plain_modulus: *const u64, indices: *const u64, valid: *const u8, num_holders: usize, points: *const u64, num_points: usize, limb_bits: u32, digit_bits: u32, weights: *mut i64) -> i32;
+    pub fn pvw_shamir_wide_handover_weights_device(ctx: *mut PvwCtx, plain_modulus: *const u64, indices: *const u64, valid: *const u8, num_holders: usize, points: *const u64, num_points: usize, limb_bits: u32, digit_bits: u32, d_weights: *mut i64, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_wide_from_digits_host(plain_modulus: *const u64, digit_bits: u32, num_digits: u32, wide: *const u64, status: *mut u32, wide_words: u32, count: usize, out: *mut u64, status_out: *mut u32) -> i32;
+    pub fn pvw_shamir_wide_from_digits_device(ctx: *mut PvwCtx, plain_modulus: *const u64, digit_bits: u32, num_digits: u32, d_wide: *const u64, d_status: *mut u32, wide_words: u32, count: usize, d_out: *mut u64, d_status_out: *mut u32, stream: *mut c_void) -> i32;
+    pub fn pvw_decrypt_all_handover_wide(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, sk: *const i64, c1s: *const u64, c2s: *const u64, num_dealers: usize, plain_modulus: *const u64, limb_bits: u32, digit_bits: u32, indices: *const u64, valid: *const u8, points: *const u64, num_points: usize, in_repr: u32, out: *mut u64, status: *mut u32, count: *mut u32) -> i32;
+    pub fn pvw_decrypt_all_handover_wide_device(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, d_sk: *const i64, d_c1s: *const u64, d_c2s: *const u64, num_dealers: usize, plain_modulus: *const u64, limb_bits: u32, digit_bits: u32, indices: *const u64, valid: *const u8, points: *const u64, num_points: usize, in_repr: u32, d_out: *mut u64, d_status: *mut u32, d_count: *mut u32, stream: *mut c_void) -> i32;
+    pub fn pvw_ctx_wide_handover_fits(ctx: *const PvwCtx, plain_modulus: *const u64, num_valid: usize, limb_bits: u32, digit_bits: u32, fits: *mut u32) -> i32;
     // ---- the receiving end over a prime below 2^256: device fold of limbs, checked reconstruction ----
     pub fn pvw_shamir_wide_from_limbs_device(ctx: *mut PvwCtx, plain_modulus: *const u64, d_limbs: *const u64, count: usize, limb_stride: usize, elem_stride: usize, limb_bits: u32, num_limbs: u32, d_out: *mut u64, stream: *mut c_void) -> i32;
     pub fn pvw_shamir_reconstruct_wide_checked_host(plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, out: *mut u64, bad: *mut u32, col_bad: *mut u32) -> i32;

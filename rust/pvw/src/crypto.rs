@@ -1239,3 +1239,115 @@ pub fn decrypt_combination(ciphertexts: &[PvwCiphertext], weights: &[i64], secre
     check(rc)?;
     Ok((PlainDecryption { values: vec![out], noise: vec![noise], status: vec![status], wide }, count))
 }
+
+/// EXTENSION: (NL, V) of a wide handover: the limbs of a share and the signed digits of a weight,
+/// V = ceil((bitlen(p) + 1) / digit_bits) (`pvw_shamir_wide_handover_shape`; host only).
+pub fn shamir_wide_handover_shape(plain_modulus: &Wide, limb_bits: u32, digit_bits: u32) -> Result<(u32, u32)> {
+    let (mut nl, mut nd) = (0u32, 0u32);
+    check(unsafe { sys::pvw_shamir_wide_handover_shape(plain_modulus.as_ptr(), limb_bits, digit_bits, &mut nl, &mut nd) })?;
+    Ok((nl, nd))
+}
+
+/// EXTENSION: the signed digits `[values.len()][V]` of the centred residues of `values` mod p, every digit in
+/// [-2^(digit_bits-1), 2^(digit_bits-1)) (`pvw_shamir_wide_signed_digits_host`).
+pub fn shamir_wide_signed_digits(values: &[Wide], plain_modulus: &Wide, digit_bits: u32) -> Result<Vec<i64>> {
+    let (_, nd) = shamir_wide_handover_shape(plain_modulus, 62, digit_bits)?;
+    let mut out = vec![0i64; values.len() * nd as usize];
+    check(unsafe {
+        sys::pvw_shamir_wide_signed_digits_host(plain_modulus.as_ptr(), values.as_ptr() as *const u64, values.len(), digit_bits, out.as_mut_ptr())
+    })?;
+    Ok(out)
+}
+
+/// EXTENSION: the points 0, -1, .., -(pack-1) of a packed wide sharing as field elements (-m is p - m).
+pub fn shamir_packed_wide_handover_points(plain_modulus: &Wide, pack: u32) -> Vec<Wide> {
+    (0..pack as u64).map(|m| {
+        let mut out = [0u64; 4];
+        if m != 0 {
+            let mut br = m;
+            for i in 0..4 {
+                let v = plain_modulus[i];
+                out[i] = v.wrapping_sub(br);
+                br = (v < br) as u64;
+            }
+        }
+        out
+    }).collect()
+}
+
+fn handover_valid(valid: Option<&[bool]>, holders: usize) -> Result<Vec<u8>> {
+    match valid {
+        Some(v) if v.len() != holders => Err(PvwError::InvalidParameters("valid must hold one flag per holder".into())),
+        Some(v) => Ok(v.iter().map(|&b| b as u8).collect()),
+        None => Ok(Vec::new()),
+    }
+}
+
+/// EXTENSION: the int64 weight rows `[T V][D NL]` of a wide handover, row m V + v, column d NL + w = signed digit v
+/// of lambda_{d,m} 2^(limb_bits w) mod p; `points` empty = the single point 0 (`pvw_shamir_wide_handover_weights_host`).
+pub fn shamir_wide_handover_weights(indices: &[u64], plain_modulus: &Wide, valid: Option<&[bool]>, points: &[Wide], limb_bits: u32,
+                                    digit_bits: u32) -> Result<Vec<i64>> {
+    let v = handover_valid(valid, indices.len())?;
+    let (nl, nd) = shamir_wide_handover_shape(plain_modulus, limb_bits, digit_bits)?;
+    let t = points.len().max(1);
+    let mut out = vec![0i64; t * nd as usize * indices.len() * nl as usize];
+    let pts = if points.is_empty() { std::ptr::null() } else { points.as_ptr() as *const u64 };
+    check(unsafe {
+        sys::pvw_shamir_wide_handover_weights_host(plain_modulus.as_ptr(), indices.as_ptr(), valid_ptr(&v), indices.len(), pts, t, limb_bits,
+                                                   digit_bits, out.as_mut_ptr())
+    })?;
+    Ok(out)
+}
+
+/// EXTENSION: (values, status) from digit plaintexts `wide [count][num_digits][wide_words]` and
+/// `status [count][num_digits]`: values[i] = sum_v +-wide[i][v] 2^(digit_bits v) mod p, status[i] the OR of the digit words
+/// without `PVW_DEC_NEGATIVE` (`pvw_shamir_wide_from_digits_host`).
+pub fn shamir_wide_from_digits(wide: &[u64], status: &[u32], num_digits: u32, wide_words: u32, plain_modulus: &Wide,
+                               digit_bits: u32) -> Result<(Vec<Wide>, Vec<u32>)> {
+    if num_digits == 0 || wide_words == 0 || status.len() % num_digits as usize != 0 || wide.len() != status.len() * wide_words as usize {
+        return Err(PvwError::InvalidParameters("wide must hold wide_words words per status word, num_digits of them per element".into()));
+    }
+    let count = status.len() / num_digits as usize;
+    let (mut out, mut st_out) = (vec![[0u64; 4]; count], vec![0u32; count]);
+    let mut st = status.to_vec();
+    check(unsafe {
+        sys::pvw_shamir_wide_from_digits_host(plain_modulus.as_ptr(), digit_bits, num_digits, wide.as_ptr(), st.as_mut_ptr(), wide_words, count,
+                                              out.as_mut_ptr() as *mut u64, st_out.as_mut_ptr())
+    })?;
+    Ok((out, st_out))
+}
+
+/// EXTENSION: whether every weight row of a wide handover stays inside the radius the decode is proven exact in,
+/// and its digit plaintexts fit the words of Q (`pvw_ctx_wide_handover_fits`; advisory, sufficient only).
+pub fn wide_handover_fits(params: &Arc<PvwParameters>, plain_modulus: &Wide, num_valid: usize, limb_bits: u32, digit_bits: u32) -> Result<bool> {
+    let mut fits = 0u32;
+    check(unsafe { sys::pvw_ctx_wide_handover_fits(params.hip.raw(), plain_modulus.as_ptr(), num_valid, limb_bits, digit_bits, &mut fits) })?;
+    Ok(fits != 0)
+}
+
+/// EXTENSION: every new party's new share in one call (`pvw_decrypt_all_handover_wide`).  `ciphertexts` are the old
+/// holders' limb ciphertexts, vector d NL + w limb w of holder d; `secret_keys` those of the consecutive parties from `party_lo`.
+/// (values `[parties][T]`, status `[parties][T]`, valid holders)
+pub fn decrypt_all_party_handover_wide(ciphertexts: &[PvwCiphertext], secret_keys: &[SecretKey], party_lo: usize, indices: &[u64],
+                                       plain_modulus: &Wide, valid: Option<&[bool]>, points: &[Wide], limb_bits: u32,
+                                       digit_bits: u32) -> Result<(Vec<Wide>, Vec<u32>, u32)> {
+    let (c1s, c2s, _) = sum_inputs(ciphertexts, None)?;
+    let v = handover_valid(valid, indices.len())?;
+    let nl = shamir_wide_limbs(plain_modulus, limb_bits)? as usize;
+    if indices.is_empty() || ciphertexts.len() != indices.len() * nl {
+        return Err(PvwError::InvalidParameters("num_limbs ciphertexts per holder".into()));
+    }
+    let params = &ciphertexts[0].params;
+    let (np, t) = (secret_keys.len(), points.len().max(1));
+    let mut sk: Vec<i64> = secret_keys.iter().flat_map(flat_secret).collect();
+    let (mut out, mut status, mut count) = (vec![[0u64; 4]; np * t], vec![0u32; np * t], 0u32);
+    let pts = if points.is_empty() { std::ptr::null() } else { points.as_ptr() as *const u64 };
+    let rc = unsafe {
+        sys::pvw_decrypt_all_handover_wide(params.hip.raw(), party_lo as u32, (party_lo + np) as u32, sk.as_ptr(), c1s.as_ptr(), c2s.as_ptr(),
+                                           indices.len(), plain_modulus.as_ptr(), limb_bits, digit_bits, indices.as_ptr(), valid_ptr(&v), pts, t,
+                                           sys::PVW_REPR_POWER, out.as_mut_ptr() as *mut u64, status.as_mut_ptr(), &mut count)
+    };
+    sk.zeroize();
+    check(rc)?;
+    Ok((out, status, count))
+}
