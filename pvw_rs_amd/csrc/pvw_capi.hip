@@ -27,6 +27,7 @@
 #include "pvw_chacha.h"
 #include "pvw_decode.h"
 #include "pvw_kernels.h"
+#include "pvw_shamir_fields.h"
 #if PVW_TUNING
 #include "../../include/pvw_hip_tuning.h"
 #endif
@@ -162,7 +163,7 @@ struct Workspace {
   size_t handover_io_bytes = 0;
   u64* correct = nullptr;    // corrected reconstruction: M | public matrices | syndromes | locators (CorrectLayout; grown by the call)
   size_t correct_bytes = 0;
-  u64* correct_wide = nullptr;   // the same over a prime below 2^256 (CorrectWideLayout)
+  u64* correct_wide = nullptr;   // the same over a prime below 2^256 (CorrectLayout<WideField>)
   size_t correct_wide_bytes = 0;
   // helper stream + events (ws_aux): decode of chunk i under the MAC of chunk i+1, key uploads under key generation
   hipStream_t aux = nullptr;
@@ -2414,42 +2415,133 @@ int32_t pvw_shamir_reconstruct_packed(uint64_t plain_modulus, uint32_t pack, con
 
 // ------------------------------------------------------------------------ checked reconstruction
 // The basis columns 0..t give F_s; out[s] = F_s(0); every extra column is compared with F_s at its point.
-struct Reconstruct {
-  u64 p;
-  u32 degree;
-  const u64* indices;   // [count], host
-  size_t count, S, secret_stride, point_stride;
-  bool erasures = false;   // a call with an erasure mask: the locator of a row has up to r + 1 coefficients
-  size_t T() const { return count - degree; }
-  size_t red() const { return count - degree - 1; }
-  size_t nk() const { return erasures ? red() + 1 : red() / 2 + 1; }   // the locator capacity of the corrected decode
-  size_t ws_bytes() const { return shamir_interp_words(count, degree) * 8; }
+// Reconstruct<F>, the layouts and the sizing rules: pvw_shamir_fields.h.  Its fields take their word counts from the kernels' header,
+inline size_t NarrowField::interp_words(size_t count, u32 t) { return shamir_interp_words(count, t); }
+inline size_t NarrowField::correct_public_words(size_t count, u32 t, size_t nk) { return shamir_correct_public_words(count, t, nk); }
+inline size_t NarrowField::evaluate_public_words(size_t count, size_t Tg, size_t nk) { return shamir_evaluate_public_words(count, Tg, nk); }
+inline size_t WideField::interp_words(size_t count, u32 t) { return shamir_interp_wide_words(count, t); }
+inline size_t WideField::correct_public_words(size_t count, u32 t, size_t nk) { return shamir_correct_wide_public_words(count, t, nk); }
+inline size_t WideField::evaluate_public_words(size_t count, size_t Tg, size_t nk) { return shamir_evaluate_wide_public_words(count, Tg, nk); }
+
+// ... and a driver below takes from NarrowCalls or WideCalls everything else the two families differ in: the modulus as the kernels
+// take it, their parameter blocks and launchers, the blocks of the stream's workspace, the locator bound, the names the timing
+// tools look the ProfScopes up by, the messages, and the plain-C++ decoder the erasure host form runs on a sub-row.
+struct NarrowCalls;
+struct WideCalls;
+static void berlekamp_welch_host(const Reconstruct<NarrowCalls>& r, const uint64_t* shares, uint64_t* out, uint32_t* nerr, uint32_t* col_err,
+                                 uint64_t* err_mask, const uint64_t* targets, size_t num_targets, uint64_t* values);
+static void berlekamp_welch_wide_host(const Reconstruct<WideCalls>& r, const uint64_t* shares, uint64_t* out, uint32_t* nerr,
+                                      uint32_t* col_err, uint64_t* err_mask, const uint64_t* targets, size_t num_targets, uint64_t* values);
+struct NarrowCalls : NarrowField {
+  typedef Mod KMod;
+  static KMod kmod(u64 p) { return shamir_mod(p); }
+  typedef ShamirInterp Interp;
+  typedef ShamirMatmul Matmul;
+  typedef ShamirMaskedMatmul MaskedMatmul;
+  typedef ShamirFinish Finish;
+  typedef ShamirEvalFinish EvalFinish;
+  static constexpr u64* Workspace::*interp = &Workspace::interp;
+  static constexpr size_t Workspace::*interp_bytes = &Workspace::interp_bytes;
+  static constexpr u64* Workspace::*correct = &Workspace::correct;
+  static constexpr size_t Workspace::*correct_bytes = &Workspace::correct_bytes;
+  static constexpr int kMaxLocator = PVW_SHAMIR_MAX_LOCATOR;
+  static constexpr const char* kLocatorBound = "on the device the locator holds at most %d coefficients: count - degree - 1 must be below %d";
+  static constexpr const char* kLayoutBound = "evaluation scratch: layout beyond its bound";
+  static constexpr const char *kWeights = "shamir_weights", *kInterp = "shamir_interp", *kCorrectWeights = "shamir_correct_weights",
+                              *kCorrect = "shamir_correct", *kEvaluate = "shamir_evaluate", *kEvaluateWeights = "shamir_evaluate_weights";
+  // the launchers; launch_shamir_points takes no modulus, and the evaluate finish names the locator's values LamT / LamD
+  static hipError_t points(const u64* idx, size_t n, u64* x, const KMod&, hipStream_t s) { return launch_shamir_points(idx, n, x, s); }
+  static constexpr auto weights = &launch_shamir_weights;
+  static constexpr auto interpolate = &launch_shamir_interp;
+  static constexpr auto correct_weights = &launch_shamir_correct_weights;
+  static constexpr auto matmul = &launch_shamir_matmul;
+  static constexpr auto matmul_masked = &launch_shamir_matmul_masked;
+  static constexpr auto bm = &launch_shamir_bm;
+  static constexpr auto bm_erasures = &launch_shamir_bm_erasures;
+  static constexpr auto correct_finish = &launch_shamir_correct_finish;
+  static constexpr auto erasures_finish = &launch_shamir_erasures_finish;
+  static constexpr auto ym = &launch_shamir_ym;
+  static constexpr auto evaluate_weights = &launch_shamir_evaluate_weights;
+  static hipError_t evaluate_finish(EvalFinish& f, const u64* lamT, const u64* lamD, hipStream_t s) {
+    f.LamT = lamT, f.LamD = lamD;
+    return launch_shamir_evaluate_finish(f, s);
+  }
+  static constexpr auto decode = &berlekamp_welch_host;
 };
-static int32_t reconstruct_checks(const Reconstruct& r, const void* shares, const void* out) {
-  if (!r.indices || !shares || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+struct WideCalls : WideField {
+  typedef WideMont KMod;
+  static KMod kmod(const u64* p) { return make_wide_mont(p); }
+  typedef ShamirInterpWide Interp;
+  typedef ShamirMatmulWide Matmul;
+  typedef ShamirMaskedMatmulWide MaskedMatmul;
+  typedef ShamirFinishWide Finish;
+  typedef ShamirEvalFinishWide EvalFinish;
+  static constexpr u64* Workspace::*interp = &Workspace::interp_wide;
+  static constexpr size_t Workspace::*interp_bytes = &Workspace::interp_wide_bytes;
+  static constexpr u64* Workspace::*correct = &Workspace::correct_wide;
+  static constexpr size_t Workspace::*correct_bytes = &Workspace::correct_wide_bytes;
+  // with a mask as well: r + 3 elements of LDS then, 131 136 bytes at the bound
+  static constexpr int kMaxLocator = PVW_SHAMIR_WIDE_MAX_LOCATOR;
+  static constexpr const char* kLocatorBound = "on the device the wide locator holds at most %d coefficients: count - degree - 1 must be below %d";
+  static constexpr const char* kLayoutBound = "wide evaluation scratch: layout beyond its bound";
+  static constexpr const char *kWeights = "shamir_weights_wide", *kInterp = "shamir_interp_wide", *kCorrectWeights = "shamir_correct_wide_weights",
+                              *kCorrect = "shamir_correct_wide", *kEvaluate = "shamir_evaluate_wide",
+                              *kEvaluateWeights = "shamir_evaluate_wide_weights";
+  // the launchers; the evaluate finish names the locator's values PsiT / PsiD
+  static constexpr auto points = &launch_shamir_points_wide;
+  static constexpr auto weights = &launch_shamir_weights_wide;
+  static constexpr auto interpolate = &launch_shamir_interp_wide;
+  static constexpr auto correct_weights = &launch_shamir_correct_weights_wide;
+  static constexpr auto matmul = &launch_shamir_matmul_wide;
+  static constexpr auto matmul_masked = &launch_shamir_matmul_masked_wide;
+  static constexpr auto bm = &launch_shamir_bm_wide;
+  static constexpr auto bm_erasures = &launch_shamir_bm_erasures_wide;
+  static constexpr auto correct_finish = &launch_shamir_correct_finish_wide;
+  static constexpr auto erasures_finish = &launch_shamir_erasures_finish_wide;
+  static constexpr auto ym = &launch_shamir_ym_wide;
+  static constexpr auto evaluate_weights = &launch_shamir_evaluate_weights_wide;
+  static hipError_t evaluate_finish(EvalFinish& f, const u64* psiT, const u64* psiD, hipStream_t s) {
+    f.PsiT = psiT, f.PsiD = psiD;
+    return launch_shamir_evaluate_finish_wide(f, s);
+  }
+  static constexpr auto decode = &berlekamp_welch_wide_host;
+};
+
+extern "C++" {
+// What the argument checks of both fields begin with, in this order: NULL (`given`: every pointer of the call is there), no
+// secrets, too few shares.  reconstruct_checks and reconstruct_wide_checks go on from here, each by its own index rules.
+template <class F>
+static int32_t reconstruct_front_checks(const Reconstruct<F>& r, bool given) {
+  if (!given) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   if (r.S == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no secrets to reconstruct");
   if (r.count < (size_t)r.degree + 1) {
     char buf[96];
     snprintf(buf, sizeof buf, "degree %u needs at least %zu shares, got %zu", r.degree, (size_t)r.degree + 1, r.count);
     return fail(PVW_ERR_INVALID_PARAMETERS, buf);
   }
+  return PVW_OK;
+}
+static int32_t reconstruct_checks(const Reconstruct<NarrowCalls>& r, const void* shares, const void* out) {
+  PVW_TRY(reconstruct_front_checks(r, r.indices && shares && out));
   PVW_TRY(shamir_index_checks(r.p, r.indices, r.count, false));
   if (r.secret_stride == 0 || r.point_stride == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "a stride of 0");
   return PVW_OK;
 }
 // what the kernels' 32-bit counts hold (the host routine has no such bound)
-static int32_t reconstruct_device_checks(const Reconstruct& r) {
+template <class F>
+static int32_t reconstruct_device_checks(const Reconstruct<F>& r) {
   if (r.count >= ((size_t)1 << 31) || r.S >= ((size_t)1 << 31))
     return fail(PVW_ERR_INVALID_PARAMETERS, "count and num_secrets must be below 2^31 on the device");
   return PVW_OK;
 }
+}  // extern "C++"
 
 // The contract in plain C++ (no GPU), written apart from the kernels' barycentric form: for every target the basis
 // polynomials L_j(x) = prod_{i != j}(x - x_i) / prod_{i != j}(x_j - x_i) are evaluated directly, then one dot product per secret.
 int32_t pvw_shamir_reconstruct_checked_host(uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
                                             const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
                                             uint64_t* out, uint32_t* bad, uint32_t* col_bad) {
-  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(reconstruct_checks(r, shares, out));
   const Mod m = shamir_mod(plain_modulus);
   const size_t t = degree, T = r.T();
@@ -2486,31 +2578,35 @@ int32_t pvw_shamir_reconstruct_checked_host(uint64_t plain_modulus, uint32_t deg
   return PVW_OK;
 }
 
-// the points and the weight matrix of one call into ws (shamir_interp_words words)
-static int32_t reconstruct_weights(pvw_ctx* c, const Reconstruct& r, u64* ws, hipStream_t s) {
-  ProfScope ps(c, "shamir_weights", s);
-  PVW_HIP(launch_shamir_points(r.indices, r.count, ws, s));
-  PVW_HIP(launch_shamir_weights(ws, r.count, r.degree, shamir_mod(r.p), s));
+extern "C++" {
+// the points and the weight matrix of one call into ws (F::interp_words words)
+template <class F>
+static int32_t reconstruct_weights(pvw_ctx* c, const Reconstruct<F>& r, const typename F::KMod& m, u64* ws, hipStream_t s) {
+  ProfScope ps(c, F::kWeights, s);
+  PVW_HIP(F::points(r.indices, r.count, ws, m, s));
+  PVW_HIP(F::weights(ws, r.count, r.degree, m, s));
   return PVW_OK;
 }
 // ns secrets from d_shares under the weights in ws: out and bad of these secrets; col_bad, zeroed by the caller, is added to
-static int32_t reconstruct_interp(pvw_ctx* c, const Reconstruct& r, const u64* ws, const u64* d_shares, size_t ns, size_t secret_stride,
-                                  size_t point_stride, u64* d_out, u32* d_bad, u32* d_col_bad, hipStream_t s) {
-  ProfScope ps(c, "shamir_interp", s);
+template <class F>
+static int32_t reconstruct_interp(pvw_ctx* c, const Reconstruct<F>& r, const typename F::KMod& m, const u64* ws, const u64* d_shares,
+                                  size_t ns, size_t secret_stride, size_t point_stride, u64* d_out, u32* d_bad, u32* d_col_bad,
+                                  hipStream_t s) {
+  ProfScope ps(c, F::kInterp, s);
   PVW_HIP(launch_shamir_zero_counts(d_bad, ns, s));
-  ShamirInterp b{};
+  typename F::Interp b{};
   b.shares = d_shares;
   b.secret_stride = secret_stride;
   b.point_stride = point_stride;
-  b.W = ws + 2 * r.count + 1;
+  b.W = ws + (2 * r.count + 1) * F::EW;
   b.out = d_out;
   b.bad = d_bad;
   b.col_bad = d_col_bad;
   b.ns = (u32)ns;
   b.degree = r.degree;
   b.T = (u32)r.T();
-  b.m = shamir_mod(r.p);
-  PVW_HIP(launch_shamir_interp(b, s));
+  b.m = m;
+  PVW_HIP(F::interpolate(b, s));
   return PVW_OK;
 }
 
@@ -2525,63 +2621,77 @@ static int32_t grown_capture_check(pvw_ctx* c, hipStream_t s, size_t Workspace::
   return fail(PVW_ERR_INVALID_PARAMETERS, msg);
 }
 
-int32_t pvw_shamir_reconstruct_checked_device(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
-                                              size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
-                                              size_t point_stride, uint64_t* d_out, uint32_t* d_bad, uint32_t* d_col_bad, void* stream) {
-  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
-  PVW_TRY(reconstruct_checks(r, d_shares, d_out));
-  PVW_TRY(reconstruct_device_checks(r));
+// The checked device call behind its argument checks
+template <class F>
+static int32_t checked_device_call(pvw_ctx* c, const Reconstruct<F>& r, const u64* d_shares, u64* d_out, u32* d_bad, u32* d_col_bad,
+                                   void* stream) {
+  const typename F::KMod m = F::kmod(r.p);
   // A context that has not touched its device yet initialises it inside device_call (allocations, a wait): on a capturing
   // stream that would invalidate the caller's capture, and nothing can have sized the workspace.  So the caller's stream is
   // checked before anything else; the context's own stream (stream == NULL) exists only once the device is initialised.
   auto sized = [&](hipStream_t s) {
-    return grown_capture_check(c, s, &Workspace::interp_bytes, r.ws_bytes(),
+    return grown_capture_check(c, s, F::interp_bytes, r.ws_bytes(),
                                "checked reconstruction under stream capture: run a call with the same degree and count on this stream "
                                "outside capture first (it sizes the workspace)");
   };
   if (stream) PVW_TRY(sized((hipStream_t)stream));
   return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
-    PVW_TRY(ws_grow(&w->interp, &w->interp_bytes, r.ws_bytes(), s, false));   // public: nothing to clear
-    PVW_TRY(reconstruct_weights(c, r, w->interp, s));
-    PVW_HIP(launch_shamir_zero_counts(d_col_bad, count, s));
-    return reconstruct_interp(c, r, w->interp, d_shares, num_secrets, secret_stride, point_stride, d_out, d_bad, d_col_bad, s);
+    PVW_TRY(ws_grow(&(w->*F::interp), &(w->*F::interp_bytes), r.ws_bytes(), s, false));   // public: nothing to clear
+    PVW_TRY(reconstruct_weights(c, r, m, w->*F::interp, s));
+    PVW_HIP(launch_shamir_zero_counts(d_col_bad, r.count, s));
+    return reconstruct_interp(c, r, m, w->*F::interp, d_shares, r.S, r.secret_stride, r.point_stride, d_out, d_bad, d_col_bad, s);
   });
 }
+}  // extern "C++"
 
-// The staging of the host-buffer reconstruction calls (8.10, 8.11, 8.13): the secrets go up in pieces of `per`, each as a dense
-// [cnt][count] block at d_sh -- whole rows by a 2D copy where the caller's rows lie that way, else repacked on the host --, and
-// the stream is drained behind a piece before the next one reuses the staging.  piece(s0, cnt) enqueues the kernels of secrets
-// [s0, s0 + cnt) and their downloads.  The host copy is as secret as the caller's shares: it is wiped when the call ends.
+int32_t pvw_shamir_reconstruct_checked_device(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
+                                              size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
+                                              size_t point_stride, uint64_t* d_out, uint32_t* d_bad, uint32_t* d_col_bad, void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  PVW_TRY(reconstruct_checks(r, d_shares, d_out));
+  PVW_TRY(reconstruct_device_checks(r));
+  return checked_device_call(c, r, d_shares, d_out, d_bad, d_col_bad, stream);
+}
+
+extern "C++" {
+// The staging of the host-buffer reconstruction calls of both fields (8.10 - 8.16, 8.19 - 8.22): the secrets go up in pieces of
+// `per`, each as a dense [cnt][count][EW] block at d_sh -- whole rows by a 2D copy where the caller's rows lie that way, else
+// repacked on the host --, and the stream is drained behind a piece before the next one reuses the staging.  piece(s0, cnt)
+// enqueues the kernels of secrets [s0, s0 + cnt) and their downloads.  The host copy is as secret as the caller's shares: it is
+// wiped when the call ends.
+template <class F>
 struct ShareStaging {
-  const Reconstruct& r;
+  static constexpr size_t EW = F::EW;
+  const Reconstruct<F>& r;
   const u64* shares;
   size_t per;
   bool dense;                                                    // whole rows go up as they lie
   std::vector<u64> packed;                                       // a piece's shares when they do not
-  ShareStaging(const Reconstruct& r_, const u64* shares_, size_t per_)
+  ShareStaging(const Reconstruct<F>& r_, const u64* shares_, size_t per_)
       : r(r_), shares(shares_), per(per_), dense(r_.point_stride == 1 && r_.secret_stride >= r_.count) {
-    if (!dense) packed.resize(per * r.count);
+    if (!dense) packed.resize(per * r.count * EW);
   }
   ~ShareStaging() {
     volatile u64* vp = packed.data();
     for (size_t i = 0; i < packed.size(); ++i) vp[i] = 0;
   }
-  // DESIGN 8.16: the rows [S][ewords] of the caller's erasure mask go up with their shares, dense as they lie, to d_erased
+  // DESIGN 8.16, 8.21: the rows [S][ewords] of the caller's erasure mask go up with their shares, dense as they lie, to d_erased
   const u64* erased = nullptr;
   u64* d_erased = nullptr;
   size_t ewords() const { return (r.count + 63) / 64; }
   int32_t run(u64* d_sh, hipStream_t stream, const std::function<int32_t(size_t s0, size_t cnt)>& piece) {
-    const size_t count = r.count;
+    const size_t count = r.count, row = count * EW * 8;
     for (size_t s0 = 0; s0 < r.S; s0 += per) {
       const size_t cnt = (r.S - s0) < per ? (r.S - s0) : per;
       if (erased) PVW_HIP(hipMemcpyAsync(d_erased, erased + s0 * ewords(), cnt * ewords() * 8, hipMemcpyHostToDevice, stream));
       if (dense) {
-        PVW_HIP(hipMemcpy2DAsync(d_sh, count * 8, shares + s0 * r.secret_stride, r.secret_stride * 8, count * 8, cnt, hipMemcpyHostToDevice, stream));
+        PVW_HIP(hipMemcpy2DAsync(d_sh, row, shares + s0 * r.secret_stride * EW, r.secret_stride * EW * 8, row, cnt, hipMemcpyHostToDevice, stream));
       } else {
         for (size_t s = 0; s < cnt; ++s)
-          for (size_t col = 0; col < count; ++col) packed[s * count + col] = shares[(s0 + s) * r.secret_stride + col * r.point_stride];
-        PVW_HIP(hipMemcpyAsync(d_sh, packed.data(), cnt * count * 8, hipMemcpyHostToDevice, stream));
+          for (size_t col = 0; col < count; ++col)
+            memcpy(&packed[(s * count + col) * EW], shares + ((s0 + s) * r.secret_stride + col * r.point_stride) * EW, EW * 8);
+        PVW_HIP(hipMemcpyAsync(d_sh, packed.data(), cnt * row, hipMemcpyHostToDevice, stream));
       }
       PVW_TRY(piece(s0, cnt));
       PVW_HIP(hipStreamSynchronize(stream));                     // the next piece reuses the staging
@@ -2592,35 +2702,42 @@ struct ShareStaging {
 
 // host buffers: the secrets go up in pieces of `per` (<= ~1 GiB of shares), each packed to [piece][count]; the weights are
 // made once.  The staged shares and the staged results are secret; the weights and the counts are not.
-int32_t pvw_shamir_reconstruct_checked(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
-                                       const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
-                                       uint64_t* out, uint32_t* bad, uint32_t* col_bad) {
-  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
-  PVW_TRY(reconstruct_checks(r, shares, out));
-  PVW_TRY(reconstruct_device_checks(r));
+template <class F>
+static int32_t checked_host_call(pvw_ctx* c, const Reconstruct<F>& r, const u64* shares, u64* out, u32* bad, u32* col_bad) {
   PVW_TRY(ensure_device(c));
-  const size_t per = chunk_1gib((count + 1) * 8 + 4, num_secrets);
+  constexpr size_t EB = F::EW * 8;                               // bytes per element
+  const typename F::KMod m = F::kmod(r.p);
+  const size_t count = r.count, per = chunk_1gib((count + 1) * EB + 4, r.S);
   Scratch sc;
-  const size_t r_sh = sc.add(per * count * 8), r_out = sc.add(per * 8), r_ws = sc.add(r.ws_bytes()), r_bad = sc.add(per * 4),
+  const size_t r_sh = sc.add(per * count * EB), r_out = sc.add(per * EB), r_ws = sc.add(r.ws_bytes()), r_bad = sc.add(per * 4),
                r_col = sc.add(count * 4);
-  ShareStaging st(r, shares, per);
+  ShareStaging<F> st(r, shares, per);
   return host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
     sc.secret(w, r_sh, r_out);
     u64 *d_sh = sc.at(r_sh), *d_out = sc.at(r_out), *ws = sc.at(r_ws);
     u32 *d_bad = bad ? sc.at<u32>(r_bad) : nullptr, *d_col = col_bad ? sc.at<u32>(r_col) : nullptr;
-    PVW_TRY(reconstruct_weights(c, r, ws, w->stream));
+    PVW_TRY(reconstruct_weights(c, r, m, ws, w->stream));
     PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
     PVW_TRY(st.run(d_sh, w->stream, [&](size_t s0, size_t cnt) -> int32_t {
-      PVW_TRY(reconstruct_interp(c, r, ws, d_sh, cnt, count, 1, d_out, d_bad, d_col, w->stream));
-      PVW_HIP(hipMemcpyAsync(out + s0, d_out, cnt * 8, hipMemcpyDeviceToHost, w->stream));
+      PVW_TRY(reconstruct_interp(c, r, m, ws, d_sh, cnt, count, 1, d_out, d_bad, d_col, w->stream));
+      PVW_HIP(hipMemcpyAsync(out + s0 * F::EW, d_out, cnt * EB, hipMemcpyDeviceToHost, w->stream));
       if (bad) PVW_HIP(hipMemcpyAsync(bad + s0, d_bad, cnt * 4, hipMemcpyDeviceToHost, w->stream));
       return PVW_OK;
     }));
     if (col_bad) PVW_HIP(hipMemcpyAsync(col_bad, d_col, count * 4, hipMemcpyDeviceToHost, w->stream));
     return PVW_OK;
   });
+}
+}  // extern "C++"
+int32_t pvw_shamir_reconstruct_checked(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                       const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                       uint64_t* out, uint32_t* bad, uint32_t* col_bad) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  PVW_TRY(reconstruct_checks(r, shares, out));
+  PVW_TRY(reconstruct_device_checks(r));
+  return checked_host_call(c, r, shares, out, bad, col_bad);
 }
 
 // ------------------------------------------------------------------------ corrected reconstruction
@@ -2633,7 +2750,7 @@ int32_t pvw_shamir_reconstruct_checked(pvw_ctx* c, uint64_t plain_modulus, uint3
 // not divide N, or N / W disagrees with more than E columns: undecodable.  Cubic in count per secret.
 // With targets: values[s][j] = F_s(targets[j] + 1) by Horner over the quotient's coefficients, 0 for an undecodable row
 // (pvw_shamir_evaluate_corrected_host); out may then be NULL.  The argument checks are the callers'.
-static void berlekamp_welch_host(const Reconstruct& r, const uint64_t* shares, uint64_t* out, uint32_t* nerr, uint32_t* col_err,
+static void berlekamp_welch_host(const Reconstruct<NarrowCalls>& r, const uint64_t* shares, uint64_t* out, uint32_t* nerr, uint32_t* col_err,
                                  uint64_t* err_mask, const uint64_t* targets, size_t num_targets, uint64_t* values) {
   const uint64_t plain_modulus = r.p;
   const uint64_t* indices = r.indices;
@@ -2728,159 +2845,142 @@ static void berlekamp_welch_host(const Reconstruct& r, const uint64_t* shares, u
 int32_t pvw_shamir_reconstruct_corrected_host(uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
                                               const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
                                               uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
-  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(reconstruct_checks(r, shares, out));
   berlekamp_welch_host(r, shares, out, nerr, col_err, err_mask, nullptr, 0, nullptr);
   return PVW_OK;
 }
 
-// The device scratch of one call, in words from its base: M first (the one region marked secret besides the staging), then
-// what the indices alone decide, then what the errors decide.  `cap` secrets are in flight at a time.
-//   M [cap][count] | x, aux, lambda, V, X (shamir_correct_public_words) | Synd [cap][r] | Lambda [cap][nk] | L [cap] (u32)
-// nk, the locator capacity, is E + 1, or r + 1 for a call with erasures: X has nk rows as well.
-struct CorrectLayout {
-  size_t count, r, nk, cap;
-  size_t pub, synd, lam, L, total;   // word offsets
-  CorrectLayout(const Reconstruct& rc, size_t cap_) : count(rc.count), r(rc.red()), nk(rc.nk()), cap(cap_) {
-    pub = cap * count;
-    synd = pub + shamir_correct_public_words(count, rc.degree, nk);
-    lam = synd + cap * r;
-    L = lam + cap * nk;
-    total = L + (cap + 1) / 2;
-  }
-  size_t bytes() const { return total * 8; }
-  size_t m_bytes() const { return cap * count * 8; }
-};
-// Secrets per pass over the kernels: their per-secret scratch (a row of M, of the syndromes and of the locators) stays
-// within 64 MiB -- M alone is count words a secret -- and within what one grid holds (tuning build: PVW_CORRECT_PIECE_BYTES,
-// read per call, so that the tests take several passes at small shapes).
-static size_t correct_piece(const Reconstruct& r) {
-  const size_t per = (r.count + r.red() + r.nk()) * 8 + 4;
+extern "C++" {
+// Secrets per pass and targets per group (correct_piece, evaluate_piece, evaluate_group) are sized within these budgets (tuning
+// build: PVW_CORRECT_PIECE_BYTES and PVW_EVALUATE_GROUP_BYTES, read per call, so that the tests take several passes and walk
+// several groups at small shapes)
+static size_t piece_budget() {
   const long env = PVW_ENV_INT("PVW_CORRECT_PIECE_BYTES", 0);
-  const size_t budget = env > 0 ? (size_t)env : (size_t)64 << 20;
-  size_t cap = budget / per;
-  if (cap == 0) cap = 1;
-  if (cap > 65535u * 4) cap = 65535u * 4;
-  return cap < r.S ? cap : r.S;
+  return env > 0 ? (size_t)env : (size_t)64 << 20;
 }
-static int32_t correct_device_checks(const Reconstruct& r) {
+static size_t group_budget() {
+  const long env = PVW_ENV_INT("PVW_EVALUATE_GROUP_BYTES", 0);
+  return env > 0 ? (size_t)env : (size_t)64 << 20;
+}
+template <class F>
+static int32_t correct_device_checks(const Reconstruct<F>& r) {
   PVW_TRY(reconstruct_device_checks(r));
-  if ((r.count - r.degree - 1) / 2 + 1 > PVW_SHAMIR_MAX_LOCATOR) {
-    char buf[128];
-    snprintf(buf, sizeof buf, "on the device the locator holds at most %d coefficients: count - degree - 1 must be below %d",
-             PVW_SHAMIR_MAX_LOCATOR, 2 * PVW_SHAMIR_MAX_LOCATOR);
+  if (r.red() / 2 + 1 > (size_t)F::kMaxLocator) {
+    char buf[160];
+    snprintf(buf, sizeof buf, F::kLocatorBound, F::kMaxLocator, 2 * F::kMaxLocator);
     return fail(PVW_ERR_INVALID_PARAMETERS, buf);
   }
   return PVW_OK;
 }
 // the points and the public matrices of one call
-static int32_t correct_weights(pvw_ctx* c, const Reconstruct& r, const CorrectLayout& lay, u64* ws, hipStream_t s) {
-  ProfScope ps(c, "shamir_correct_weights", s);
-  PVW_HIP(launch_shamir_points(r.indices, r.count, ws + lay.pub, s));
-  PVW_HIP(launch_shamir_correct_weights(ws + lay.pub, r.count, r.degree, (u32)lay.nk, shamir_mod(r.p), s));
+template <class F>
+static int32_t correct_weights(pvw_ctx* c, const Reconstruct<F>& r, const typename F::KMod& m, const CorrectLayout<F>& lay, u64* ws,
+                               hipStream_t s) {
+  ProfScope ps(c, F::kCorrectWeights, s);
+  PVW_HIP(F::points(r.indices, r.count, ws + lay.pub, m, s));
+  PVW_HIP(F::correct_weights(ws + lay.pub, r.count, r.degree, (u32)lay.nk, m, s));
   return PVW_OK;
 }
 // ns <= lay.cap secrets from d_shares: their out, nerr and mask rows; col_err, zeroed by the caller, is added to.
-// d_erased: the ns rows of the erasure mask, or NULL for the calls of 8.11 and 8.13.
-static int32_t correct_piece_enqueue(pvw_ctx* c, const Reconstruct& r, const CorrectLayout& lay, u64* ws, const u64* d_shares, size_t ns,
-                                     size_t secret_stride, size_t point_stride, u64* d_out, u32* d_nerr, u32* d_col_err, u64* d_mask,
-                                     hipStream_t s, const u64* d_erased = nullptr) {
-  ProfScope ps(c, "shamir_correct", s);
-  const Mod m = shamir_mod(r.p);
+// d_erased: the ns rows of the erasure mask, or NULL for the calls without one.
+template <class F>
+static int32_t correct_piece_enqueue(pvw_ctx* c, const Reconstruct<F>& r, const typename F::KMod& m, const CorrectLayout<F>& lay, u64* ws,
+                                     const u64* d_shares, size_t ns, size_t secret_stride, size_t point_stride, u64* d_out, u32* d_nerr,
+                                     u32* d_col_err, u64* d_mask, hipStream_t s, const u64* d_erased) {
+  ProfScope ps(c, F::kCorrect, s);
+  constexpr size_t EW = F::EW;
   const u64* pub = ws + lay.pub;
-  const u64 *lambda = pub + 2 * r.count + 1, *V = lambda + r.count, *X = V + r.count * lay.r;
+  const u64 *lambda = pub + (2 * r.count + 1) * EW, *V = lambda + r.count * EW, *X = V + r.count * lay.r * EW;
   u64 *M = ws, *synd = ws + lay.synd, *Lam = ws + lay.lam;
   u32* L = (u32*)(ws + lay.L);
-  ShamirMaskedMatmul a{};
+  typename F::MaskedMatmul a{};
   a.A = d_shares, a.secret_stride = secret_stride, a.term_stride = point_stride;
   a.W = V, a.out = synd;
   a.ns = (u32)ns, a.terms = (u32)r.count, a.T = (u32)lay.r, a.m = m;
   a.erased = d_erased, a.ewords = (u32)((r.count + 63) / 64);
   if (d_erased) {
-    PVW_HIP(launch_shamir_matmul_masked(a, s));
-    PVW_HIP(launch_shamir_bm_erasures(synd, d_erased, pub, Lam, L, (u32)ns, (u32)r.count, (u32)lay.r, m, s));
+    PVW_HIP(F::matmul_masked(a, s));
+    PVW_HIP(F::bm_erasures(synd, d_erased, pub, Lam, L, (u32)ns, (u32)r.count, (u32)lay.r, m, s));
   } else {
-    PVW_HIP(launch_shamir_matmul(a, s));
-    PVW_HIP(launch_shamir_bm(synd, Lam, L, (u32)ns, (u32)lay.r, m, s));
+    PVW_HIP(F::matmul(a, s));
+    PVW_HIP(F::bm(synd, Lam, L, (u32)ns, (u32)lay.r, m, s));
   }
-  ShamirMatmul b{};
+  typename F::Matmul b{};
   b.A = Lam, b.secret_stride = lay.nk, b.term_stride = 1;
   b.W = X, b.out = M;
   b.ns = (u32)ns, b.terms = (u32)lay.nk, b.T = (u32)r.count, b.m = m;
-  PVW_HIP(launch_shamir_matmul(b, s));
-  ShamirFinish f{};
+  PVW_HIP(F::matmul(b, s));
+  typename F::Finish f{};
   f.shares = d_shares, f.secret_stride = secret_stride, f.point_stride = point_stride;
   f.M = M, f.Lam = Lam, f.L = L, f.lam = lambda;
   f.out = d_out, f.nerr = d_nerr, f.col_err = d_col_err, f.mask = d_mask;
   f.count = (u32)r.count, f.E = (u32)lay.nk - 1, f.m = m;
-  if (d_erased) PVW_HIP(launch_shamir_erasures_finish(f, d_erased, (u32)ns, s));
-  else PVW_HIP(launch_shamir_correct_finish(f, (u32)ns, s));
+  if (d_erased) PVW_HIP(F::erasures_finish(f, d_erased, (u32)ns, s));
+  else PVW_HIP(F::correct_finish(f, (u32)ns, s));
   return PVW_OK;
 }
 
-// The stream's `correct` block for a device call of 8.11 or 8.13: grown to `need` bytes, and the regions (word offset, bytes) the
-// call's secrets decide marked secret -- M, which leads the block, and for the evaluation y o M | raw | the stand-in for out.
+// The stream's `correct` block (F::correct) for a device call of the corrected decode or of the evaluation: grown to `need` bytes,
+// and the regions (word offset, bytes) the call's secrets decide marked secret -- M, which leads the block, and for the evaluation
+// y o M | raw | the stand-in for out.
+template <class F>
 static int32_t correct_block(Workspace* w, size_t need, std::initializer_list<std::pair<size_t, size_t>> secret, hipStream_t s) {
-  if (w->correct_bytes < need) ws_public(w, w->correct, w->correct_bytes);   // the block is about to go
-  PVW_TRY(ws_grow(&w->correct, &w->correct_bytes, need, s, true));
-  for (const auto& sp : secret) ws_mark_secret(w, w->correct + sp.first, sp.second);
+  if (w->*F::correct_bytes < need) ws_public(w, w->*F::correct, w->*F::correct_bytes);   // the block is about to go
+  PVW_TRY(ws_grow(&(w->*F::correct), &(w->*F::correct_bytes), need, s, true));
+  for (const auto& sp : secret) ws_mark_secret(w, w->*F::correct + sp.first, sp.second);
   return PVW_OK;
 }
-// ... and its passes over the kernels: pass(s0, ns) for every `cap` of the call's secrets
-static int32_t correct_passes(const Reconstruct& r, size_t cap, const std::function<int32_t(size_t s0, size_t ns)>& pass) {
-  for (size_t s0 = 0; s0 < r.S; s0 += cap) PVW_TRY(pass(s0, r.S - s0 < cap ? r.S - s0 : cap));
+// ... and its passes over the kernels: pass(s0, ns) for every `cap` of the call's S secrets
+static int32_t correct_passes(size_t S, size_t cap, const std::function<int32_t(size_t s0, size_t ns)>& pass) {
+  for (size_t s0 = 0; s0 < S; s0 += cap) PVW_TRY(pass(s0, S - s0 < cap ? S - s0 : cap));
   return PVW_OK;
 }
 
-// The device call of 8.11 behind its argument checks; with d_erased (r.erasures) that of 8.16.  `unsized`: what a captured call
-// is refused with when nothing has sized the workspace.
-static int32_t corrected_device_call(pvw_ctx* c, const Reconstruct& r, const u64* d_shares, const u64* d_erased, u64* d_out, u32* d_nerr,
+// The device call of 8.11 or 8.20 behind its argument checks; with d_erased (r.erasures) that of 8.16 or 8.21.  `unsized`: what a
+// captured call is refused with when nothing has sized the workspace.
+template <class F>
+static int32_t corrected_device_call(pvw_ctx* c, const Reconstruct<F>& r, const u64* d_shares, const u64* d_erased, u64* d_out, u32* d_nerr,
                                      u32* d_col_err, u64* d_err_mask, void* stream, const char* unsized) {
-  const CorrectLayout lay(r, correct_piece(r));
+  constexpr size_t EW = F::EW;
+  const typename F::KMod m = F::kmod(r.p);
+  const CorrectLayout<F> lay(r, correct_piece(r, piece_budget()));
   const size_t words = (r.count + 63) / 64;
-  // the caller's stream is checked before the context initialises its device (pvw_shamir_reconstruct_checked_device)
-  auto sized = [&](hipStream_t s) { return grown_capture_check(c, s, &Workspace::correct_bytes, lay.bytes(), unsized); };
+  // the caller's stream is checked before the context initialises its device (checked_device_call)
+  auto sized = [&](hipStream_t s) { return grown_capture_check(c, s, F::correct_bytes, lay.bytes(), unsized); };
   if (stream) PVW_TRY(sized((hipStream_t)stream));
   return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
-    PVW_TRY(correct_block(w, lay.bytes(), {{0, lay.m_bytes()}}, s));
-    PVW_TRY(correct_weights(c, r, lay, w->correct, s));
+    PVW_TRY(correct_block<F>(w, lay.bytes(), {{0, lay.m_bytes()}}, s));
+    u64* ws = w->*F::correct;
+    PVW_TRY(correct_weights(c, r, m, lay, ws, s));
     PVW_HIP(launch_shamir_zero_counts(d_col_err, r.count, s));
-    return correct_passes(r, lay.cap, [&](size_t s0, size_t ns) {
-      return correct_piece_enqueue(c, r, lay, w->correct, d_shares + s0 * r.secret_stride, ns, r.secret_stride, r.point_stride, d_out + s0,
-                                   Report::from(d_nerr, s0), d_col_err, Report::from(d_err_mask, s0 * words), s,
+    return correct_passes(r.S, lay.cap, [&](size_t s0, size_t ns) {
+      return correct_piece_enqueue(c, r, m, lay, ws, d_shares + s0 * r.secret_stride * EW, ns, r.secret_stride, r.point_stride,
+                                   d_out + s0 * EW, Report::from(d_nerr, s0), d_col_err, Report::from(d_err_mask, s0 * words), s,
                                    Report::from(d_erased, s0 * words));
     });
   });
 }
 
-int32_t pvw_shamir_reconstruct_corrected_device(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
-                                                size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
-                                                size_t point_stride, uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err,
-                                                uint64_t* d_err_mask, void* stream) {
-  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
-  PVW_TRY(reconstruct_checks(r, d_shares, d_out));
-  PVW_TRY(correct_device_checks(r));
-  return corrected_device_call(c, r, d_shares, nullptr, d_out, d_nerr, d_col_err, d_err_mask, stream,
-                               "corrected reconstruction under stream capture: run a call with the same degree and count and at least as "
-                               "many secrets on this stream outside capture first (it sizes the workspace)");
-}
-
-// host buffers: the secrets go up in pieces as pvw_shamir_reconstruct_checked stages them (each packed to [piece][count], or
+// host buffers: the secrets go up in pieces as the checked call stages them (ShareStaging: each packed to [piece][count][EW], or
 // whole rows by a 2D copy), a piece no larger than one pass over the kernels; the public matrices are made once and col_err
 // adds up over the pieces.  The staged shares, the staged secrets and M are cleared before the call returns.
-// Behind the argument checks; with `erased` (r.erasures) the host-buffer call of 8.16, whose mask rows are staged with the shares.
-static int32_t corrected_host_call(pvw_ctx* c, const Reconstruct& r, const u64* shares, const u64* erased, u64* out, u32* nerr, u32* col_err,
-                                   u64* err_mask) {
+// Behind the argument checks; with `erased` (r.erasures) the host-buffer call of 8.16 or 8.21, whose mask rows are staged with the
+// shares of their piece.
+template <class F>
+static int32_t corrected_host_call(pvw_ctx* c, const Reconstruct<F>& r, const u64* shares, const u64* erased, u64* out, u32* nerr,
+                                   u32* col_err, u64* err_mask) {
   PVW_TRY(ensure_device(c));
+  constexpr size_t EB = F::EW * 8;                               // bytes per element
+  const typename F::KMod m = F::kmod(r.p);
   const size_t count = r.count, words = (count + 63) / 64;
-  size_t per = chunk_1gib((count + 1 + words + (erased ? words : 0)) * 8 + 4, r.S);
-  if (per > correct_piece(r)) per = correct_piece(r);
-  const CorrectLayout lay(r, per);
+  size_t per = chunk_1gib((count + 1) * EB + (words + (erased ? words : 0)) * 8 + 4, r.S);
+  if (per > correct_piece(r, piece_budget())) per = correct_piece(r, piece_budget());
+  const CorrectLayout<F> lay(r, per);
   Scratch sc;
-  const size_t r_sh = sc.add(per * count * 8), r_out = sc.add(per * 8), r_ws = sc.add(lay.bytes()), r_nerr = sc.add(per * 4),
+  const size_t r_sh = sc.add(per * count * EB), r_out = sc.add(per * EB), r_ws = sc.add(lay.bytes()), r_nerr = sc.add(per * 4),
                r_col = sc.add(count * 4), r_mask = sc.add(per * words * 8), r_er = sc.add(erased ? per * words * 8 : 0);
-  ShareStaging st(r, shares, per);
+  ShareStaging<F> st(r, shares, per);
   return host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
     u64 *d_sh = sc.at(r_sh), *d_out = sc.at(r_out), *ws = sc.at(r_ws);
@@ -2888,11 +2988,11 @@ static int32_t corrected_host_call(pvw_ctx* c, const Reconstruct& r, const u64* 
     u32 *d_nerr = nerr ? sc.at<u32>(r_nerr) : nullptr, *d_col = col_err ? sc.at<u32>(r_col) : nullptr;
     u64* d_mask = err_mask ? sc.at(r_mask) : nullptr;
     if (erased) st.erased = erased, st.d_erased = sc.at(r_er);
-    PVW_TRY(correct_weights(c, r, lay, ws, w->stream));
+    PVW_TRY(correct_weights(c, r, m, lay, ws, w->stream));
     PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
     PVW_TRY(st.run(d_sh, w->stream, [&](size_t s0, size_t cnt) -> int32_t {
-      PVW_TRY(correct_piece_enqueue(c, r, lay, ws, d_sh, cnt, count, 1, d_out, d_nerr, d_col, d_mask, w->stream, st.d_erased));
-      PVW_HIP(hipMemcpyAsync(out + s0, d_out, cnt * 8, hipMemcpyDeviceToHost, w->stream));
+      PVW_TRY(correct_piece_enqueue(c, r, m, lay, ws, d_sh, cnt, count, 1, d_out, d_nerr, d_col, d_mask, w->stream, st.d_erased));
+      PVW_HIP(hipMemcpyAsync(out + s0 * F::EW, d_out, cnt * EB, hipMemcpyDeviceToHost, w->stream));
       if (nerr) PVW_HIP(hipMemcpyAsync(nerr + s0, d_nerr, cnt * 4, hipMemcpyDeviceToHost, w->stream));
       if (err_mask) PVW_HIP(hipMemcpyAsync(err_mask + s0 * words, d_mask, cnt * words * 8, hipMemcpyDeviceToHost, w->stream));
       return PVW_OK;
@@ -2901,11 +3001,26 @@ static int32_t corrected_host_call(pvw_ctx* c, const Reconstruct& r, const u64* 
     return PVW_OK;
   });
 }
+}  // extern "C++"
+
+int32_t pvw_shamir_reconstruct_corrected_device(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
+                                                size_t point_stride, uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err,
+                                                uint64_t* d_err_mask, void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  PVW_TRY(reconstruct_checks(r, d_shares, d_out));
+  PVW_TRY(correct_device_checks(r));
+  return corrected_device_call(c, r, d_shares, nullptr, d_out, d_nerr, d_col_err, d_err_mask, stream,
+                               "corrected reconstruction under stream capture: run a call with the same degree and count and at least as "
+                               "many secrets on this stream outside capture first (it sizes the workspace)");
+}
+
 int32_t pvw_shamir_reconstruct_corrected(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
                                          const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
                                          uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(reconstruct_checks(r, shares, out));
   PVW_TRY(correct_device_checks(r));
   return corrected_host_call(c, r, shares, nullptr, out, nerr, col_err, err_mask);
@@ -2916,7 +3031,7 @@ int32_t pvw_shamir_reconstruct_corrected(pvw_ctx* c, uint64_t plain_modulus, uin
 // out, nerr, col_err, err_mask and values.
 // device: the bounds of the kernels' 32-bit counts as well; num_targets is bounded BEFORE the targets are read, so a refused count
 // costs no walk over the array (the host routine has no such bound and reads every target)
-static int32_t evaluate_checks(const Reconstruct& r, const void* shares, const uint64_t* targets, size_t num_targets, const void* values,
+static int32_t evaluate_checks(const Reconstruct<NarrowCalls>& r, const void* shares, const uint64_t* targets, size_t num_targets, const void* values,
                                bool device) {
   PVW_TRY(reconstruct_checks(r, shares, values));            // values stands where the corrected call has out: out may be NULL here
   if (!targets) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
@@ -2934,174 +3049,115 @@ int32_t pvw_shamir_evaluate_corrected_host(uint64_t plain_modulus, uint32_t degr
                                            const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
                                            const uint64_t* targets, size_t num_targets, uint64_t* values, uint64_t* out, uint32_t* nerr,
                                            uint32_t* col_err, uint64_t* err_mask) {
-  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(evaluate_checks(r, shares, targets, num_targets, values, false));
   berlekamp_welch_host(r, shares, out, nerr, col_err, err_mask, targets, num_targets, values);
   return PVW_OK;
 }
 
-// Targets per group: the public matrices that depend on the targets (a column of C, of Xt and of Xd, scale and coin per target)
-// stay within 64 MiB -- at count = T = 4096, t = 2047 they would be 134 MB + 2 x 34 MB in one piece (tuning build:
-// PVW_EVALUATE_GROUP_BYTES, read per call, so that the tests walk several groups at small shapes).  Whole blocks of 64 targets
-// when there are that many.
-static size_t evaluate_group(const Reconstruct& r, size_t num_targets) {
-  const size_t per = (r.count + 2 * r.nk() + 2) * 8 + 4;
-  const long env = PVW_ENV_INT("PVW_EVALUATE_GROUP_BYTES", 0);
-  const size_t budget = env > 0 ? (size_t)env : (size_t)64 << 20;
-  size_t tg = budget / per;
-  if (tg > 64) tg -= tg % 64;
-  if (tg == 0) tg = 1;
-  return tg < num_targets ? tg : num_targets;
-}
-// The per-secret scratch of the evaluation, in bytes: a row of M, of the syndromes and of the locators as in correct_piece, and a
-// row of y o M, of raw, of Lambda and of Lambda' at the group's targets, a stand-in for out, L and a stand-in for nerr
-static size_t evaluate_secret_bytes(const Reconstruct& r, size_t Tg) {
-  return (2 * r.count + r.red() + r.nk() + 3 * Tg + 2) * 8;
-}
-static size_t evaluate_piece_budget() {
-  const long env = PVW_ENV_INT("PVW_CORRECT_PIECE_BYTES", 0);
-  return env > 0 ? (size_t)env : (size_t)64 << 20;
-}
-// secrets per pass, by the rule of correct_piece
-static size_t evaluate_piece(const Reconstruct& r, size_t Tg) {
-  size_t cap = evaluate_piece_budget() / evaluate_secret_bytes(r, Tg);
-  if (cap == 0) cap = 1;
-  if (cap > 65535u * 4) cap = 65535u * 4;
-  return cap < r.S ? cap : r.S;
-}
-// The scratch of one call, in words from its base: the block of the corrected call first (CorrectLayout: M leads it), then
-//   YM [cap][count] | raw [cap][Tg] | outs [cap]   -- depend on the shares: the second region marked secret
-//   LamT [cap][Tg] | LamD [cap][Tg] | nerr [cap] (u32) | the group's public matrices (shamir_evaluate_public_words)
-struct EvaluateLayout {
-  CorrectLayout cl;
-  size_t Tg;
-  size_t ym, raw, outs, lamT, lamD, nerr, pub, total;   // word offsets
-  EvaluateLayout(const Reconstruct& rc, size_t cap, size_t Tg_) : cl(rc, cap), Tg(Tg_) {
-    ym = cl.total;
-    raw = ym + cap * rc.count;
-    outs = raw + cap * Tg;
-    lamT = outs + cap;
-    lamD = lamT + cap * Tg;
-    nerr = lamD + cap * Tg;
-    pub = nerr + (cap + 1) / 2;
-    total = pub + shamir_evaluate_public_words(rc.count, Tg, cl.nk);
-  }
-  size_t bytes() const { return total * 8; }
-  size_t secret_bytes() const { return (lamT - ym) * 8; }
-};
-// What the stream's block must hold for a call: never less than the layout takes, and no smaller for more secrets or more
-// targets at the same (degree, count) -- the rule a captured call is checked by.
-static size_t evaluate_need_bytes(const Reconstruct& r, size_t Tg) {
-  const size_t per = evaluate_secret_bytes(r, Tg), budget = evaluate_piece_budget();
-  size_t part = r.S > budget / per ? budget : r.S * per;
-  if (part < per) part = per;
-  return part + 16 + (shamir_correct_public_words(r.count, r.degree, r.nk()) + shamir_evaluate_public_words(r.count, Tg, r.nk())) * 8;
-}
+extern "C++" {
 // One pass: ns <= lay.cl.cap secrets from d_shares are decoded (their out, nerr and mask rows; col_err is added to) and evaluated
-// at all targets, group by group, into d_values (rows num_targets words apart).  `resident` is the first target of the group whose
-// public matrices the block holds; with one group they are built once for all passes.
-static int32_t evaluate_pass_enqueue(pvw_ctx* c, const Reconstruct& r, const EvaluateLayout& lay, u64* ws, const u64* d_shares, size_t ns,
-                                     size_t secret_stride, size_t point_stride, const u64* targets, size_t num_targets, u64* d_values,
-                                     u64* d_out, u32* d_nerr, u32* d_col_err, u64* d_mask, size_t* resident, hipStream_t s,
-                                     const u64* d_erased = nullptr) {
-  const Mod m = shamir_mod(r.p);
+// at all targets, group by group, into d_values (rows num_targets elements apart).  `resident` is the first target of the group
+// whose public matrices the block holds; with one group they are built once for all passes.
+template <class F>
+static int32_t evaluate_pass_enqueue(pvw_ctx* c, const Reconstruct<F>& r, const typename F::KMod& m, const EvaluateLayout<F>& lay, u64* ws,
+                                     const u64* d_shares, size_t ns, size_t secret_stride, size_t point_stride, const u64* targets,
+                                     size_t num_targets, u64* d_values, u64* d_out, u32* d_nerr, u32* d_col_err, u64* d_mask,
+                                     size_t* resident, hipStream_t s, const u64* d_erased) {
+  constexpr size_t EW = F::EW;
   if (!d_out) d_out = ws + lay.outs;
   if (!d_nerr) d_nerr = (u32*)(ws + lay.nerr);
-  PVW_TRY(correct_piece_enqueue(c, r, lay.cl, ws, d_shares, ns, secret_stride, point_stride, d_out, d_nerr, d_col_err, d_mask, s, d_erased));
-  const u64 *x = ws + lay.cl.pub, *aux = x + r.count;
+  PVW_TRY(correct_piece_enqueue(c, r, m, lay.cl, ws, d_shares, ns, secret_stride, point_stride, d_out, d_nerr, d_col_err, d_mask, s, d_erased));
+  const u64 *x = ws + lay.cl.pub, *aux = x + r.count * EW;
   const u64 *M = ws, *Lam = ws + lay.cl.lam;
   u64 *YM = ws + lay.ym, *raw = ws + lay.raw, *LamT = ws + lay.lamT, *LamD = ws + lay.lamD, *pub = ws + lay.pub;
   const size_t nk = lay.cl.nk;
   {
-    ProfScope ps(c, "shamir_evaluate", s);
-    PVW_HIP(launch_shamir_ym(d_shares, secret_stride, point_stride, M, YM, (u32)ns, (u32)r.count, m, s));
+    ProfScope ps(c, F::kEvaluate, s);
+    PVW_HIP(F::ym(d_shares, secret_stride, point_stride, M, YM, (u32)ns, (u32)r.count, m, s));
   }
   for (size_t j0 = 0; j0 < num_targets; j0 += lay.Tg) {
     const size_t tg = num_targets - j0 < lay.Tg ? num_targets - j0 : lay.Tg;
     if (*resident != j0) {
-      ProfScope ps(c, "shamir_evaluate_weights", s);
-      PVW_HIP(launch_shamir_points(targets + j0, tg, pub, s));
-      PVW_HIP(launch_shamir_evaluate_weights(x, aux, pub, r.count, (u32)nk, tg, m, s));
+      ProfScope ps(c, F::kEvaluateWeights, s);
+      PVW_HIP(F::points(targets + j0, tg, pub, m, s));
+      PVW_HIP(F::evaluate_weights(x, aux, pub, r.count, (u32)nk, tg, m, s));
       *resident = j0;
     }
-    ProfScope ps(c, "shamir_evaluate", s);
-    const u64 *scale = pub + tg, *C = scale + tg, *Xt = C + r.count * tg, *Xd = Xt + nk * tg;
-    const u32* coin = (const u32*)(Xd + nk * tg);
-    ShamirMatmul a{};
+    ProfScope ps(c, F::kEvaluate, s);
+    const u64 *scale = pub + tg * EW, *C = scale + tg * EW, *Xt = C + r.count * tg * EW, *Xd = Xt + nk * tg * EW;
+    const u32* coin = (const u32*)(Xd + nk * tg * EW);
+    typename F::Matmul a{};
     a.A = YM, a.secret_stride = r.count, a.term_stride = 1;
     a.W = C, a.out = raw;
     a.ns = (u32)ns, a.terms = (u32)r.count, a.T = (u32)tg, a.m = m;
-    PVW_HIP(launch_shamir_matmul(a, s));
-    ShamirMatmul b{};
+    PVW_HIP(F::matmul(a, s));
+    typename F::Matmul b{};
     b.A = Lam, b.secret_stride = nk, b.term_stride = 1;
     b.W = Xt, b.out = LamT;
     b.ns = (u32)ns, b.terms = (u32)nk, b.T = (u32)tg, b.m = m;
-    PVW_HIP(launch_shamir_matmul(b, s));
+    PVW_HIP(F::matmul(b, s));
     b.W = Xd, b.out = LamD;
-    PVW_HIP(launch_shamir_matmul(b, s));
-    ShamirEvalFinish f{};
+    PVW_HIP(F::matmul(b, s));
+    typename F::EvalFinish f{};
     f.shares = d_shares, f.secret_stride = secret_stride, f.point_stride = point_stride;
-    f.M = M, f.nerr = d_nerr, f.raw = raw, f.LamT = LamT, f.LamD = LamD, f.scale = scale, f.coin = coin;
-    f.values = d_values + j0, f.value_stride = num_targets;
+    f.M = M, f.nerr = d_nerr, f.raw = raw, f.scale = scale, f.coin = coin;
+    f.values = d_values + j0 * EW, f.value_stride = num_targets;
     f.ns = (u32)ns, f.count = (u32)r.count, f.Tg = (u32)tg, f.m = m;
-    PVW_HIP(launch_shamir_evaluate_finish(f, s));
+    PVW_HIP(F::evaluate_finish(f, LamT, LamD, s));
   }
   return PVW_OK;
 }
 
-// The device call of 8.13 behind its argument checks; with d_erased (r.erasures) that of 8.16 (corrected_device_call)
-static int32_t evaluate_device_call(pvw_ctx* c, const Reconstruct& r, const u64* d_shares, const u64* d_erased, const u64* targets,
+// The device call of 8.13 or 8.22 behind its argument checks; with d_erased (r.erasures) the decode is that of 8.16 or 8.21
+// (corrected_device_call)
+template <class F>
+static int32_t evaluate_device_call(pvw_ctx* c, const Reconstruct<F>& r, const u64* d_shares, const u64* d_erased, const u64* targets,
                                     size_t num_targets, u64* d_values, u64* d_out, u32* d_nerr, u32* d_col_err, u64* d_err_mask, void* stream,
                                     const char* unsized) {
-  const size_t Tg = evaluate_group(r, num_targets);
-  const EvaluateLayout lay(r, evaluate_piece(r, Tg), Tg);
-  const size_t need = evaluate_need_bytes(r, Tg);
-  if (need < lay.bytes()) return fail(PVW_ERR_INTERNAL, "evaluation scratch: layout beyond its bound");
+  constexpr size_t EW = F::EW;
+  const typename F::KMod m = F::kmod(r.p);
+  const size_t Tg = evaluate_group(r, num_targets, group_budget());
+  const EvaluateLayout<F> lay(r, evaluate_piece(r, Tg, piece_budget()), Tg);
+  const size_t need = evaluate_need_bytes(r, Tg, piece_budget());
+  if (need < lay.bytes()) return fail(PVW_ERR_INTERNAL, F::kLayoutBound);
   const size_t words = (r.count + 63) / 64;
-  // the caller's stream is checked before the context initialises its device (pvw_shamir_reconstruct_checked_device)
-  auto sized = [&](hipStream_t s) { return grown_capture_check(c, s, &Workspace::correct_bytes, need, unsized); };
+  // the caller's stream is checked before the context initialises its device (checked_device_call)
+  auto sized = [&](hipStream_t s) { return grown_capture_check(c, s, F::correct_bytes, need, unsized); };
   if (stream) PVW_TRY(sized((hipStream_t)stream));
   return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
-    PVW_TRY(correct_block(w, need, {{0, lay.cl.m_bytes()}, {lay.ym, lay.secret_bytes()}}, s));
-    PVW_TRY(correct_weights(c, r, lay.cl, w->correct, s));
+    PVW_TRY(correct_block<F>(w, need, {{0, lay.cl.m_bytes()}, {lay.ym, lay.secret_bytes()}}, s));
+    u64* ws = w->*F::correct;
+    PVW_TRY(correct_weights(c, r, m, lay.cl, ws, s));
     PVW_HIP(launch_shamir_zero_counts(d_col_err, r.count, s));
     size_t resident = SIZE_MAX;
-    return correct_passes(r, lay.cl.cap, [&](size_t s0, size_t ns) {
-      return evaluate_pass_enqueue(c, r, lay, w->correct, d_shares + s0 * r.secret_stride, ns, r.secret_stride, r.point_stride, targets,
-                                   num_targets, d_values + s0 * num_targets, Report::from(d_out, s0), Report::from(d_nerr, s0), d_col_err,
-                                   Report::from(d_err_mask, s0 * words), &resident, s, Report::from(d_erased, s0 * words));
+    return correct_passes(r.S, lay.cl.cap, [&](size_t s0, size_t ns) {
+      return evaluate_pass_enqueue(c, r, m, lay, ws, d_shares + s0 * r.secret_stride * EW, ns, r.secret_stride, r.point_stride, targets,
+                                   num_targets, d_values + s0 * num_targets * EW, Report::from(d_out, s0 * EW), Report::from(d_nerr, s0),
+                                   d_col_err, Report::from(d_err_mask, s0 * words), &resident, s, Report::from(d_erased, s0 * words));
     });
   });
 }
 
-int32_t pvw_shamir_evaluate_corrected_device(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
-                                             const uint64_t* d_shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
-                                             const uint64_t* targets, size_t num_targets, uint64_t* d_values, uint64_t* d_out,
-                                             uint32_t* d_nerr, uint32_t* d_col_err, uint64_t* d_err_mask, void* stream) {
-  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
-  PVW_TRY(evaluate_checks(r, d_shares, targets, num_targets, d_values, true));
-  return evaluate_device_call(c, r, d_shares, nullptr, targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask, stream,
-                              "corrected evaluation under stream capture: run a call with the same degree and count, at least as many "
-                              "targets and at least as many secrets on this stream outside capture first (it sizes the workspace)");
-}
-
-// host buffers: staged as pvw_shamir_reconstruct_corrected stages (each piece one pass over the kernels, packed to [piece][count]
-// or whole rows by a 2D copy); the values of a piece come down as one block.  The staged shares, secrets and values, M, y o M and
-// raw are cleared before the call returns.
-static int32_t evaluate_host_call(pvw_ctx* c, const Reconstruct& r, const u64* shares, const u64* erased, const u64* targets,
+// host buffers: staged as corrected_host_call stages (each piece one pass over the kernels, the mask rows with their shares); the
+// values of a piece come down as one block.  The staged shares, secrets and values, M, y o M and raw are cleared before the call
+// returns.
+template <class F>
+static int32_t evaluate_host_call(pvw_ctx* c, const Reconstruct<F>& r, const u64* shares, const u64* erased, const u64* targets,
                                   size_t num_targets, u64* values, u64* out, u32* nerr, u32* col_err, u64* err_mask) {
   PVW_TRY(ensure_device(c));
+  constexpr size_t EB = F::EW * 8;                               // bytes per element
+  const typename F::KMod m = F::kmod(r.p);
   const size_t count = r.count, words = (count + 63) / 64;
-  const size_t Tg = evaluate_group(r, num_targets);
-  size_t per = chunk_1gib((count + 1 + words + (erased ? words : 0) + num_targets) * 8 + 4, r.S);
-  if (per > evaluate_piece(r, Tg)) per = evaluate_piece(r, Tg);
-  const EvaluateLayout lay(r, per, Tg);
+  const size_t Tg = evaluate_group(r, num_targets, group_budget());
+  size_t per = chunk_1gib((count + 1 + num_targets) * EB + (words + (erased ? words : 0)) * 8 + 4, r.S);
+  if (per > evaluate_piece(r, Tg, piece_budget())) per = evaluate_piece(r, Tg, piece_budget());
+  const EvaluateLayout<F> lay(r, per, Tg);
   Scratch sc;
-  const size_t r_sh = sc.add(per * count * 8), r_out = sc.add(per * 8), r_val = sc.add(per * num_targets * 8), r_ws = sc.add(lay.bytes()),
+  const size_t r_sh = sc.add(per * count * EB), r_out = sc.add(per * EB), r_val = sc.add(per * num_targets * EB), r_ws = sc.add(lay.bytes()),
                r_nerr = sc.add(per * 4), r_col = sc.add(count * 4), r_mask = sc.add(per * words * 8),
                r_er = sc.add(erased ? per * words * 8 : 0);
-  ShareStaging st(r, shares, per);
+  ShareStaging<F> st(r, shares, per);
   return host_call(c, [&](Workspace* w) -> int32_t {
     PVW_TRY(sc.take(w));
     u64 *d_sh = sc.at(r_sh), *d_out = sc.at(r_out), *d_val = sc.at(r_val), *ws = sc.at(r_ws);
@@ -3110,14 +3166,14 @@ static int32_t evaluate_host_call(pvw_ctx* c, const Reconstruct& r, const u64* s
     u32 *d_nerr = sc.at<u32>(r_nerr), *d_col = col_err ? sc.at<u32>(r_col) : nullptr;
     u64* d_mask = err_mask ? sc.at(r_mask) : nullptr;
     if (erased) st.erased = erased, st.d_erased = sc.at(r_er);
-    PVW_TRY(correct_weights(c, r, lay.cl, ws, w->stream));
+    PVW_TRY(correct_weights(c, r, m, lay.cl, ws, w->stream));
     PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
     size_t resident = SIZE_MAX;
     PVW_TRY(st.run(d_sh, w->stream, [&](size_t s0, size_t cnt) -> int32_t {
-      PVW_TRY(evaluate_pass_enqueue(c, r, lay, ws, d_sh, cnt, count, 1, targets, num_targets, d_val, d_out, d_nerr, d_col, d_mask, &resident,
+      PVW_TRY(evaluate_pass_enqueue(c, r, m, lay, ws, d_sh, cnt, count, 1, targets, num_targets, d_val, d_out, d_nerr, d_col, d_mask, &resident,
                                     w->stream, st.d_erased));
-      PVW_HIP(hipMemcpyAsync(values + s0 * num_targets, d_val, cnt * num_targets * 8, hipMemcpyDeviceToHost, w->stream));
-      if (out) PVW_HIP(hipMemcpyAsync(out + s0, d_out, cnt * 8, hipMemcpyDeviceToHost, w->stream));
+      PVW_HIP(hipMemcpyAsync(values + s0 * num_targets * F::EW, d_val, cnt * num_targets * EB, hipMemcpyDeviceToHost, w->stream));
+      if (out) PVW_HIP(hipMemcpyAsync(out + s0 * F::EW, d_out, cnt * EB, hipMemcpyDeviceToHost, w->stream));
       if (nerr) PVW_HIP(hipMemcpyAsync(nerr + s0, d_nerr, cnt * 4, hipMemcpyDeviceToHost, w->stream));
       if (err_mask) PVW_HIP(hipMemcpyAsync(err_mask + s0 * words, d_mask, cnt * words * 8, hipMemcpyDeviceToHost, w->stream));
       return PVW_OK;
@@ -3126,12 +3182,26 @@ static int32_t evaluate_host_call(pvw_ctx* c, const Reconstruct& r, const u64* s
     return PVW_OK;
   });
 }
+}  // extern "C++"
+
+int32_t pvw_shamir_evaluate_corrected_device(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                             const uint64_t* d_shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                             const uint64_t* targets, size_t num_targets, uint64_t* d_values, uint64_t* d_out,
+                                             uint32_t* d_nerr, uint32_t* d_col_err, uint64_t* d_err_mask, void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  PVW_TRY(evaluate_checks(r, d_shares, targets, num_targets, d_values, true));
+  return evaluate_device_call(c, r, d_shares, nullptr, targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask, stream,
+                              "corrected evaluation under stream capture: run a call with the same degree and count, at least as many "
+                              "targets and at least as many secrets on this stream outside capture first (it sizes the workspace)");
+}
+
 int32_t pvw_shamir_evaluate_corrected(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
                                       const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
                                       const uint64_t* targets, size_t num_targets, uint64_t* values, uint64_t* out, uint32_t* nerr,
                                       uint32_t* col_err, uint64_t* err_mask) {
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
+  const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(evaluate_checks(r, shares, targets, num_targets, values, true));
   return evaluate_host_call(c, r, shares, nullptr, targets, num_targets, values, out, nerr, col_err, err_mask);
 }
@@ -3142,14 +3212,18 @@ int32_t pvw_shamir_evaluate_corrected(pvw_ctx* c, uint64_t plain_modulus, uint32
 // in at most E_s of the columns that are not erased: 8.11's definition on the sub-row, which is what the host form runs.
 // erased == NULL is the call of 8.11 or 8.13, its bounds included: every entry point hands such a call over as it is.
 
-// The contract in plain C++: per row the columns that are not erased are compacted, berlekamp_welch_host decodes that sub-row
+extern "C++" {
+// The contract in plain C++, for both fields: per row the columns that are not erased are compacted, the field's Berlekamp-Welch
+// (F::decode: berlekamp_welch_host or berlekamp_welch_wide_host) decodes that sub-row
 // with the same t, and the mask bits and col_err go back to the original columns.  A row with fewer than t + 1 columns left
 // (eps_s > r) is undecodable.  Nothing at an erased position is read.
-static void erasures_host(const Reconstruct& r, const u64* shares, const u64* erased, u64* out, u32* nerr, u32* col_err, u64* err_mask,
+template <class F>
+static void erasures_host(const Reconstruct<F>& r, const u64* shares, const u64* erased, u64* out, u32* nerr, u32* col_err, u64* err_mask,
                           const u64* targets, size_t num_targets, u64* values) {
+  constexpr size_t EW = F::EW;
   const size_t count = r.count, words = (count + 63) / 64;
   std::vector<size_t> cols;
-  std::vector<u64> sub_idx(count), sub_sh(count), sub_mask(words);
+  std::vector<u64> sub_idx(count), sub_sh(count * EW), sub_mask(words);
   std::vector<u32> sub_col(count);
   if (col_err) std::fill(col_err, col_err + count, 0u);
   for (size_t s = 0; s < r.S; ++s) {
@@ -3159,21 +3233,20 @@ static void erasures_host(const Reconstruct& r, const u64* shares, const u64* er
     if (err_mask) std::fill(err_mask + s * words, err_mask + (s + 1) * words, (u64)0);
     const size_t n = cols.size();
     if (n < (size_t)r.degree + 1) {
-      if (out) out[s] = 0;
+      if (out) std::fill(out + s * EW, out + (s + 1) * EW, (u64)0);
       if (nerr) nerr[s] = PVW_SHAMIR_UNDECODABLE;
-      if (values) std::fill(values + s * num_targets, values + (s + 1) * num_targets, (u64)0);
+      if (values) std::fill(values + s * num_targets * EW, values + (s + 1) * num_targets * EW, (u64)0);
       continue;
     }
     for (size_t i = 0; i < n; ++i) {
       sub_idx[i] = r.indices[cols[i]];
-      sub_sh[i] = shares[s * r.secret_stride + cols[i] * r.point_stride];
+      memcpy(&sub_sh[i * EW], shares + (s * r.secret_stride + cols[i] * r.point_stride) * EW, EW * 8);
     }
-    const Reconstruct sub{r.p, r.degree, sub_idx.data(), n, 1, n, 1};
-    u64 o = 0;
+    Reconstruct<F> sub = r;                                                        // one dense row of n columns, no mask
+    sub.indices = sub_idx.data(), sub.count = n, sub.S = 1, sub.secret_stride = n, sub.point_stride = 1, sub.erasures = false;
     u32 ne = 0;
-    berlekamp_welch_host(sub, sub_sh.data(), &o, &ne, sub_col.data(), sub_mask.data(), targets, num_targets,
-                         values ? values + s * num_targets : nullptr);
-    if (out) out[s] = o;
+    F::decode(sub, sub_sh.data(), out ? out + s * EW : nullptr, &ne, sub_col.data(), sub_mask.data(), targets, num_targets,
+              values ? values + s * num_targets * EW : nullptr);
     if (nerr) nerr[s] = ne;
     for (size_t i = 0; i < n; ++i)
       if ((sub_mask[i / 64] >> (i % 64)) & 1) {
@@ -3184,8 +3257,9 @@ static void erasures_host(const Reconstruct& r, const u64* shares, const u64* er
   volatile u64* vp = sub_sh.data();                                              // as secret as the shares
   for (size_t i = 0; i < sub_sh.size(); ++i) vp[i] = 0;
 }
+}  // extern "C++"
 // on the device the errata locator of a row has up to r + 1 coefficients, in one wave's LDS
-static int32_t erasures_device_checks(const Reconstruct& r) {
+static int32_t erasures_device_checks(const Reconstruct<NarrowCalls>& r) {
   if (r.red() + 1 > PVW_SHAMIR_MAX_LOCATOR) {
     char buf[160];
     snprintf(buf, sizeof buf, "on the device the locator of a row with erasures holds at most %d coefficients: count - degree - 1 must be "
@@ -3204,7 +3278,7 @@ int32_t pvw_shamir_reconstruct_erasures_host(uint64_t plain_modulus, uint32_t de
   if (!erased)
     return pvw_shamir_reconstruct_corrected_host(plain_modulus, degree, indices, count, shares, num_secrets, secret_stride, point_stride, out,
                                                  nerr, col_err, err_mask);
-  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
+  const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
   PVW_TRY(reconstruct_checks(r, shares, out));
   erasures_host(r, shares, erased, out, nerr, col_err, err_mask, nullptr, 0, nullptr);
   return PVW_OK;
@@ -3217,7 +3291,7 @@ int32_t pvw_shamir_reconstruct_erasures_device(pvw_ctx* c, uint64_t plain_modulu
     return pvw_shamir_reconstruct_corrected_device(c, plain_modulus, degree, indices, count, d_shares, num_secrets, secret_stride,
                                                    point_stride, d_out, d_nerr, d_col_err, d_err_mask, stream);
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
+  const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
   PVW_TRY(reconstruct_checks(r, d_shares, d_out));
   PVW_TRY(correct_device_checks(r));
   PVW_TRY(erasures_device_checks(r));
@@ -3230,7 +3304,7 @@ int32_t pvw_shamir_reconstruct_erasures(pvw_ctx* c, uint64_t plain_modulus, uint
     return pvw_shamir_reconstruct_corrected(c, plain_modulus, degree, indices, count, shares, num_secrets, secret_stride, point_stride, out,
                                             nerr, col_err, err_mask);
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
+  const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
   PVW_TRY(reconstruct_checks(r, shares, out));
   PVW_TRY(correct_device_checks(r));
   PVW_TRY(erasures_device_checks(r));
@@ -3244,7 +3318,7 @@ int32_t pvw_shamir_evaluate_erasures_host(uint64_t plain_modulus, uint32_t degre
   if (!erased)
     return pvw_shamir_evaluate_corrected_host(plain_modulus, degree, indices, count, shares, num_secrets, secret_stride, point_stride, targets,
                                               num_targets, values, out, nerr, col_err, err_mask);
-  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
+  const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
   PVW_TRY(evaluate_checks(r, shares, targets, num_targets, values, false));
   erasures_host(r, shares, erased, out, nerr, col_err, err_mask, targets, num_targets, values);
   return PVW_OK;
@@ -3257,7 +3331,7 @@ int32_t pvw_shamir_evaluate_erasures_device(pvw_ctx* c, uint64_t plain_modulus, 
     return pvw_shamir_evaluate_corrected_device(c, plain_modulus, degree, indices, count, d_shares, num_secrets, secret_stride, point_stride,
                                                 targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask, stream);
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
+  const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
   PVW_TRY(evaluate_checks(r, d_shares, targets, num_targets, d_values, true));
   PVW_TRY(erasures_device_checks(r));
   return evaluate_device_call(c, r, d_shares, d_erased, targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask, stream,
@@ -3271,7 +3345,7 @@ int32_t pvw_shamir_evaluate_erasures(pvw_ctx* c, uint64_t plain_modulus, uint32_
     return pvw_shamir_evaluate_corrected(c, plain_modulus, degree, indices, count, shares, num_secrets, secret_stride, point_stride, targets,
                                          num_targets, values, out, nerr, col_err, err_mask);
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  const Reconstruct r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
+  const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
   PVW_TRY(evaluate_checks(r, shares, targets, num_targets, values, true));
   PVW_TRY(erasures_device_checks(r));
   return evaluate_host_call(c, r, shares, erased, targets, num_targets, values, out, nerr, col_err, err_mask);
@@ -3476,7 +3550,7 @@ static int32_t shamir_shares_device(pvw_ctx* c, const uint64_t* d_secrets, size_
     PVW_TRY(ensure_device(c));
     return shamir_enqueue(c, deal, keys, D, d_shares, call_stream(c, stream));
   }
-  // the caller's stream is checked before the context initialises its device (pvw_shamir_reconstruct_checked_device)
+  // the caller's stream is checked before the context initialises its device (checked_device_call)
   auto sized = [&](hipStream_t s) { return packed_capture_check(c, s, *pack); };
   if (stream) PVW_TRY(sized((hipStream_t)stream));
   return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
@@ -4281,7 +4355,7 @@ static int32_t shamir_wide_shares_device(pvw_ctx* c, const uint64_t* d_secrets, 
   }
   deal.pack = *pack;
   deal.mm = make_wide_mont(plain_modulus);
-  // the caller's stream is checked before the context initialises its device (pvw_shamir_reconstruct_checked_device)
+  // the caller's stream is checked before the context initialises its device (checked_device_call)
   auto sized = [&](hipStream_t s) { return packed_wide_capture_check(c, s, *pack); };
   if (stream) PVW_TRY(sized((hipStream_t)stream));
   return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
@@ -4524,27 +4598,9 @@ int32_t pvw_shamir_wide_from_limbs_device(pvw_ctx* c, const uint64_t* plain_modu
   return PVW_OK;
 }
 
-struct ReconstructWide {
-  const u64* p;         // [4], host
-  u32 degree;
-  const u64* indices;   // [count], host
-  size_t count, S, secret_stride, point_stride;
-  WideMod m;            // set by reconstruct_wide_checks
-  bool erasures = false;   // a call with an erasure mask: the locator of a row has up to r + 1 coefficients
-  size_t T() const { return count - degree; }
-  size_t ws_bytes() const { return shamir_interp_wide_words(count, degree) * 8; }
-  size_t red() const { return count - degree - 1; }
-  size_t nk() const { return erasures ? red() + 1 : red() / 2 + 1; }   // the locator capacity of the corrected decode
-};
-// the order of reconstruct_checks: NULL, no secrets, too few shares, a duplicate, the range, the modulus, the strides
-static int32_t reconstruct_wide_checks(ReconstructWide& r, const void* shares, const void* out) {
-  if (!r.p || !r.indices || !shares || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  if (r.S == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no secrets to reconstruct");
-  if (r.count < (size_t)r.degree + 1) {
-    char buf[96];
-    snprintf(buf, sizeof buf, "degree %u needs at least %zu shares, got %zu", r.degree, (size_t)r.degree + 1, r.count);
-    return fail(PVW_ERR_INVALID_PARAMETERS, buf);
-  }
+// the order of reconstruct_checks: NULL, no secrets, too few shares, a duplicate, the range, the modulus (which sets r.m), the strides
+static int32_t reconstruct_wide_checks(Reconstruct<WideCalls>& r, const void* shares, const void* out) {
+  PVW_TRY(reconstruct_front_checks(r, r.p && r.indices && shares && out));
   {
     std::vector<u64> sorted(r.indices, r.indices + r.count);
     std::sort(sorted.begin(), sorted.end());
@@ -4562,12 +4618,6 @@ static int32_t reconstruct_wide_checks(ReconstructWide& r, const void* shares, c
   if (r.secret_stride == 0 || r.point_stride == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "a stride of 0");
   return PVW_OK;
 }
-static int32_t reconstruct_wide_device_checks(const ReconstructWide& r) {
-  if (r.count >= ((size_t)1 << 31) || r.S >= ((size_t)1 << 31))
-    return fail(PVW_ERR_INVALID_PARAMETERS, "count and num_secrets must be below 2^31 on the device");
-  return PVW_OK;
-}
-
 // a <- (a - b) mod pn and res = a b mod p for scaled a, b below pn
 static void wide_submod(Wide a, const Wide b, const WideMod& m) {
   Wide nb;
@@ -4587,7 +4637,7 @@ static void wide_mulmod_scaled(Wide res, const Wide a, const Wide b, const WideM
 int32_t pvw_shamir_reconstruct_wide_checked_host(const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
                                                  const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
                                                  uint64_t* out, uint32_t* bad, uint32_t* col_bad) {
-  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(reconstruct_wide_checks(r, shares, out));
   const WideMod& m = r.m;
   const size_t t = degree, T = r.T();
@@ -4657,106 +4707,25 @@ int32_t pvw_shamir_reconstruct_wide_checked_host(const uint64_t* plain_modulus, 
   return PVW_OK;
 }
 
-// the points and the weight matrix of one call into ws (shamir_interp_wide_words words)
-static int32_t reconstruct_wide_weights(pvw_ctx* c, const ReconstructWide& r, const WideMont& mm, u64* ws, hipStream_t s) {
-  ProfScope ps(c, "shamir_weights_wide", s);
-  PVW_HIP(launch_shamir_points_wide(r.indices, r.count, ws, mm, s));
-  PVW_HIP(launch_shamir_weights_wide(ws, r.count, r.degree, mm, s));
-  return PVW_OK;
-}
-// ns secrets from d_shares under the weights in ws: out and bad of these secrets; col_bad, zeroed by the caller, is added to
-static int32_t reconstruct_wide_interp(pvw_ctx* c, const ReconstructWide& r, const WideMont& mm, const u64* ws, const u64* d_shares,
-                                       size_t ns, size_t secret_stride, size_t point_stride, u64* d_out, u32* d_bad, u32* d_col_bad,
-                                       hipStream_t s) {
-  ProfScope ps(c, "shamir_interp_wide", s);
-  PVW_HIP(launch_shamir_zero_counts(d_bad, ns, s));
-  ShamirInterpWide b{};
-  b.shares = d_shares;
-  b.secret_stride = secret_stride;
-  b.point_stride = point_stride;
-  b.W = ws + (2 * r.count + 1) * 4;
-  b.out = d_out;
-  b.bad = d_bad;
-  b.col_bad = d_col_bad;
-  b.ns = (u32)ns;
-  b.degree = r.degree;
-  b.T = (u32)r.T();
-  b.m = mm;
-  PVW_HIP(launch_shamir_interp_wide(b, s));
-  return PVW_OK;
-}
-
 int32_t pvw_shamir_reconstruct_wide_checked_device(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
                                                    size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
                                                    size_t point_stride, uint64_t* d_out, uint32_t* d_bad, uint32_t* d_col_bad,
                                                    void* stream) {
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(reconstruct_wide_checks(r, d_shares, d_out));
-  PVW_TRY(reconstruct_wide_device_checks(r));
-  const WideMont mm = make_wide_mont(plain_modulus);
-  // the caller's stream is checked before the device is touched (pvw_shamir_reconstruct_checked_device)
-  auto sized = [&](hipStream_t s) {
-    return grown_capture_check(c, s, &Workspace::interp_wide_bytes, r.ws_bytes(),
-                               "checked reconstruction under stream capture: run a call with the same degree and count on this stream "
-                               "outside capture first (it sizes the workspace)");
-  };
-  if (stream) PVW_TRY(sized((hipStream_t)stream));
-  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
-    PVW_TRY(ws_grow(&w->interp_wide, &w->interp_wide_bytes, r.ws_bytes(), s, false));   // public: nothing to clear
-    PVW_TRY(reconstruct_wide_weights(c, r, mm, w->interp_wide, s));
-    PVW_HIP(launch_shamir_zero_counts(d_col_bad, count, s));
-    return reconstruct_wide_interp(c, r, mm, w->interp_wide, d_shares, num_secrets, secret_stride, point_stride, d_out, d_bad, d_col_bad, s);
-  });
+  PVW_TRY(reconstruct_device_checks(r));
+  return checked_device_call(c, r, d_shares, d_out, d_bad, d_col_bad, stream);
 }
-
-// host buffers: the secrets go up in pieces of `per` (<= ~1 GiB of shares), each a dense [piece][count][4] block -- whole rows
-// by a 2D copy where the caller's rows lie that way, else repacked on the host into a copy that is wiped when the call ends;
-// the weights are made once.  The staged shares and the staged results are secret; the weights and the counts are not.
+// host buffers: staged and run as pvw_shamir_reconstruct_checked is (checked_host_call), in dense [piece][count][4] blocks
 int32_t pvw_shamir_reconstruct_wide_checked(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
                                             const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
                                             uint64_t* out, uint32_t* bad, uint32_t* col_bad) {
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(reconstruct_wide_checks(r, shares, out));
-  PVW_TRY(reconstruct_wide_device_checks(r));
-  PVW_TRY(ensure_device(c));
-  const WideMont mm = make_wide_mont(plain_modulus);
-  const size_t per = chunk_1gib((count + 1) * 32 + 4, num_secrets);
-  Scratch sc;
-  const size_t r_sh = sc.add(per * count * 32), r_out = sc.add(per * 32), r_ws = sc.add(r.ws_bytes()), r_bad = sc.add(per * 4),
-               r_col = sc.add(count * 4);
-  const bool dense = point_stride == 1 && secret_stride >= count;
-  std::vector<u64> packed(dense ? 0 : per * count * 4);
-  const int32_t rc = host_call(c, [&](Workspace* w) -> int32_t {
-    PVW_TRY(sc.take(w));
-    sc.secret(w, r_sh, r_out);
-    u64 *d_sh = sc.at(r_sh), *d_out = sc.at(r_out), *ws = sc.at(r_ws);
-    u32 *d_bad = bad ? sc.at<u32>(r_bad) : nullptr, *d_col = col_bad ? sc.at<u32>(r_col) : nullptr;
-    PVW_TRY(reconstruct_wide_weights(c, r, mm, ws, w->stream));
-    PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
-    for (size_t s0 = 0; s0 < num_secrets; s0 += per) {
-      const size_t cnt = (num_secrets - s0) < per ? (num_secrets - s0) : per;
-      if (dense) {
-        PVW_HIP(hipMemcpy2DAsync(d_sh, count * 32, shares + s0 * secret_stride * 4, secret_stride * 32, count * 32, cnt,
-                                 hipMemcpyHostToDevice, w->stream));
-      } else {
-        for (size_t s = 0; s < cnt; ++s)
-          for (size_t col = 0; col < count; ++col)
-            memcpy(&packed[(s * count + col) * 4], shares + ((s0 + s) * secret_stride + col * point_stride) * 4, 32);
-        PVW_HIP(hipMemcpyAsync(d_sh, packed.data(), cnt * count * 32, hipMemcpyHostToDevice, w->stream));
-      }
-      PVW_TRY(reconstruct_wide_interp(c, r, mm, ws, d_sh, cnt, count, 1, d_out, d_bad, d_col, w->stream));
-      PVW_HIP(hipMemcpyAsync(out + s0 * 4, d_out, cnt * 32, hipMemcpyDeviceToHost, w->stream));
-      if (bad) PVW_HIP(hipMemcpyAsync(bad + s0, d_bad, cnt * 4, hipMemcpyDeviceToHost, w->stream));
-      PVW_HIP(hipStreamSynchronize(w->stream));                  // the next piece reuses the staging
-    }
-    if (col_bad) PVW_HIP(hipMemcpyAsync(col_bad, d_col, count * 4, hipMemcpyDeviceToHost, w->stream));
-    return PVW_OK;
-  });
-  volatile u64* vp = packed.data();
-  for (size_t i = 0; i < packed.size(); ++i) vp[i] = 0;
-  return rc;
+  PVW_TRY(reconstruct_device_checks(r));
+  return checked_host_call(c, r, shares, out, bad, col_bad);
 }
 
 // ------------------------------------------------------------------------ corrected reconstruction below 2^256
@@ -4771,7 +4740,7 @@ static inline u64 (&wel(std::vector<u64>& v, size_t i))[4] { return *(u64(*)[4])
 // contract itself: N / W is compared with the row in every column.  Cubic in count per secret.
 // With targets: values[s][j] = F_s(targets[j] + 1), four plain words, by Horner over the quotient's coefficients, 0 for an
 // undecodable row (pvw_shamir_evaluate_wide_corrected_host); out may then be NULL.
-static void berlekamp_welch_wide_host(const ReconstructWide& r, const uint64_t* shares, uint64_t* out, uint32_t* nerr, uint32_t* col_err,
+static void berlekamp_welch_wide_host(const Reconstruct<WideCalls>& r, const uint64_t* shares, uint64_t* out, uint32_t* nerr, uint32_t* col_err,
                                       uint64_t* err_mask, const uint64_t* targets = nullptr, size_t num_targets = 0,
                                       uint64_t* values = nullptr) {
   const WideMont mm = make_wide_mont(r.p);
@@ -4904,216 +4873,33 @@ static void berlekamp_welch_wide_host(const ReconstructWide& r, const uint64_t* 
 int32_t pvw_shamir_reconstruct_wide_corrected_host(const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
                                                    const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
                                                    uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
-  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(reconstruct_wide_checks(r, shares, out));
   berlekamp_welch_wide_host(r, shares, out, nerr, col_err, err_mask);
   return PVW_OK;
 }
 
-// The device scratch of one call, in words from its base, laid out like CorrectLayout with elements of four words:
-//   M [cap][count][4] | x, aux, lambda, V, X (shamir_correct_wide_public_words) | Synd [cap][r][4] | Lambda [cap][nk][4] | L [cap] (u32)
-// M leads the block and is the one region marked secret besides the staging.  Every offset is a multiple of four words.
-// nk, the locator capacity, is E + 1, or r + 1 for a call with erasures: X has nk rows as well.
-struct CorrectWideLayout {
-  size_t count, r, nk, cap;
-  size_t pub, synd, lam, L, total;   // word offsets
-  CorrectWideLayout(const ReconstructWide& rc, size_t cap_) : count(rc.count), r(rc.red()), nk(rc.nk()), cap(cap_) {
-    pub = cap * count * 4;
-    synd = pub + shamir_correct_wide_public_words(count, rc.degree, nk);
-    lam = synd + cap * r * 4;
-    L = lam + cap * nk * 4;
-    total = L + (cap + 1) / 2;
-  }
-  size_t bytes() const { return total * 8; }
-  size_t m_bytes() const { return cap * count * 32; }
-};
-// secrets per pass over the kernels, by the rule of correct_piece: a secret takes (count + r + nk) 32 + 4 bytes of scratch
-static size_t correct_wide_piece(const ReconstructWide& r) {
-  const size_t per = (r.count + r.red() + r.nk()) * 32 + 4;
-  const long env = PVW_ENV_INT("PVW_CORRECT_PIECE_BYTES", 0);
-  const size_t budget = env > 0 ? (size_t)env : (size_t)64 << 20;
-  size_t cap = budget / per;
-  if (cap == 0) cap = 1;
-  if (cap > 65535u * 4) cap = 65535u * 4;
-  return cap < r.S ? cap : r.S;
-}
-static int32_t correct_wide_device_checks(const ReconstructWide& r) {
-  PVW_TRY(reconstruct_wide_device_checks(r));
-  if (r.red() / 2 + 1 > PVW_SHAMIR_WIDE_MAX_LOCATOR) {   // with a mask as well: r + 3 elements of LDS then, 131 136 bytes at the bound
-    char buf[160];
-    snprintf(buf, sizeof buf, "on the device the wide locator holds at most %d coefficients: count - degree - 1 must be below %d",
-             PVW_SHAMIR_WIDE_MAX_LOCATOR, 2 * PVW_SHAMIR_WIDE_MAX_LOCATOR);
-    return fail(PVW_ERR_INVALID_PARAMETERS, buf);
-  }
-  return PVW_OK;
-}
-// the points and the public matrices of one call
-static int32_t correct_wide_weights(pvw_ctx* c, const ReconstructWide& r, const WideMont& mm, const CorrectWideLayout& lay, u64* ws,
-                                    hipStream_t s) {
-  ProfScope ps(c, "shamir_correct_wide_weights", s);
-  PVW_HIP(launch_shamir_points_wide(r.indices, r.count, ws + lay.pub, mm, s));
-  PVW_HIP(launch_shamir_correct_weights_wide(ws + lay.pub, r.count, r.degree, (u32)lay.nk, mm, s));
-  return PVW_OK;
-}
-// ns <= lay.cap secrets from d_shares: their out, nerr and mask rows; col_err, zeroed by the caller, is added to
-// d_erased: the ns rows of the erasure mask, or NULL for the call of 8.20.
-static int32_t correct_wide_piece_enqueue(pvw_ctx* c, const ReconstructWide& r, const WideMont& mm, const CorrectWideLayout& lay, u64* ws,
-                                          const u64* d_shares, size_t ns, size_t secret_stride, size_t point_stride, u64* d_out,
-                                          u32* d_nerr, u32* d_col_err, u64* d_mask, hipStream_t s, const u64* d_erased = nullptr) {
-  ProfScope ps(c, "shamir_correct_wide", s);
-  const u64* pub = ws + lay.pub;
-  const u64 *lambda = pub + (2 * r.count + 1) * 4, *V = lambda + r.count * 4, *X = V + r.count * lay.r * 4;
-  u64 *M = ws, *synd = ws + lay.synd, *Lam = ws + lay.lam;
-  u32* L = (u32*)(ws + lay.L);
-  ShamirMaskedMatmulWide a{};
-  a.A = d_shares, a.secret_stride = secret_stride, a.term_stride = point_stride;
-  a.W = V, a.out = synd;
-  a.ns = (u32)ns, a.terms = (u32)r.count, a.T = (u32)lay.r, a.m = mm;
-  a.erased = d_erased, a.ewords = (u32)((r.count + 63) / 64);
-  if (d_erased) {
-    PVW_HIP(launch_shamir_matmul_masked_wide(a, s));
-    PVW_HIP(launch_shamir_bm_erasures_wide(synd, d_erased, pub, Lam, L, (u32)ns, (u32)r.count, (u32)lay.r, mm, s));
-  } else {
-    PVW_HIP(launch_shamir_matmul_wide(a, s));
-    PVW_HIP(launch_shamir_bm_wide(synd, Lam, L, (u32)ns, (u32)lay.r, mm, s));
-  }
-  ShamirMatmulWide b{};
-  b.A = Lam, b.secret_stride = lay.nk, b.term_stride = 1;
-  b.W = X, b.out = M;
-  b.ns = (u32)ns, b.terms = (u32)lay.nk, b.T = (u32)r.count, b.m = mm;
-  PVW_HIP(launch_shamir_matmul_wide(b, s));
-  ShamirFinishWide f{};
-  f.shares = d_shares, f.secret_stride = secret_stride, f.point_stride = point_stride;
-  f.M = M, f.Lam = Lam, f.L = L, f.lam = lambda;
-  f.out = d_out, f.nerr = d_nerr, f.col_err = d_col_err, f.mask = d_mask;
-  f.count = (u32)r.count, f.E = (u32)lay.nk - 1, f.m = mm;
-  if (d_erased) PVW_HIP(launch_shamir_erasures_finish_wide(f, d_erased, (u32)ns, s));
-  else PVW_HIP(launch_shamir_correct_finish_wide(f, (u32)ns, s));
-  return PVW_OK;
-}
-
-// The device call of 8.20 behind its argument checks; with d_erased (r.erasures) that of 8.21.  `unsized`: what a captured call
-// is refused with when nothing has sized the workspace.
-static int32_t correct_wide_device_call(pvw_ctx* c, const ReconstructWide& r, const u64* d_shares, const u64* d_erased, u64* d_out,
-                                        u32* d_nerr, u32* d_col_err, u64* d_err_mask, void* stream, const char* unsized) {
-  const WideMont mm = make_wide_mont(r.p);
-  const CorrectWideLayout lay(r, correct_wide_piece(r));
-  const size_t count = r.count, words = (count + 63) / 64;
-  // the caller's stream is checked before the device is touched (pvw_shamir_reconstruct_checked_device)
-  auto sized = [&](hipStream_t s) { return grown_capture_check(c, s, &Workspace::correct_wide_bytes, lay.bytes(), unsized); };
-  if (stream) PVW_TRY(sized((hipStream_t)stream));
-  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
-    if (w->correct_wide_bytes < lay.bytes()) ws_public(w, w->correct_wide, w->correct_wide_bytes);   // the block is about to go
-    PVW_TRY(ws_grow(&w->correct_wide, &w->correct_wide_bytes, lay.bytes(), s, true));
-    ws_mark_secret(w, w->correct_wide, lay.m_bytes());
-    PVW_TRY(correct_wide_weights(c, r, mm, lay, w->correct_wide, s));
-    PVW_HIP(launch_shamir_zero_counts(d_col_err, count, s));
-    for (size_t s0 = 0; s0 < r.S; s0 += lay.cap) {
-      const size_t ns = r.S - s0 < lay.cap ? r.S - s0 : lay.cap;
-      PVW_TRY(correct_wide_piece_enqueue(c, r, mm, lay, w->correct_wide, d_shares + s0 * r.secret_stride * 4, ns, r.secret_stride,
-                                         r.point_stride, d_out + s0 * 4, Report::from(d_nerr, s0), d_col_err,
-                                         Report::from(d_err_mask, s0 * words), s, Report::from(d_erased, s0 * words)));
-    }
-    return PVW_OK;
-  });
-}
 int32_t pvw_shamir_reconstruct_wide_corrected_device(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
                                                      size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
                                                      size_t point_stride, uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err,
                                                      uint64_t* d_err_mask, void* stream) {
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(reconstruct_wide_checks(r, d_shares, d_out));
-  PVW_TRY(correct_wide_device_checks(r));
-  return correct_wide_device_call(c, r, d_shares, nullptr, d_out, d_nerr, d_col_err, d_err_mask, stream,
+  PVW_TRY(correct_device_checks(r));
+  return corrected_device_call(c, r, d_shares, nullptr, d_out, d_nerr, d_col_err, d_err_mask, stream,
                                   "corrected reconstruction under stream capture: run a call with the same degree and count and at least as "
                                   "many secrets on this stream outside capture first (it sizes the workspace)");
 }
 
-// The staging of the host-buffer calls of 8.20 - 8.22 (ShareStaging with elements of four words): piece(s0, cnt) enqueues the
-// kernels of secrets [s0, s0 + cnt), staged dense at d_sh with their mask rows at d_er, and their downloads; the stream is
-// drained behind a piece before the next one reuses the staging.
-struct WideShareStaging {
-  const ReconstructWide& r;
-  const u64* shares;
-  const u64* erased;
-  size_t per;
-  bool dense;                                                    // whole rows go up as they lie
-  std::vector<u64> packed;                                       // a piece's shares when they do not
-  WideShareStaging(const ReconstructWide& r_, const u64* shares_, const u64* erased_, size_t per_)
-      : r(r_), shares(shares_), erased(erased_), per(per_), dense(r_.point_stride == 1 && r_.secret_stride >= r_.count) {
-    if (!dense) packed.resize(per * r.count * 4);
-  }
-  ~WideShareStaging() {
-    volatile u64* vp = packed.data();
-    for (size_t i = 0; i < packed.size(); ++i) vp[i] = 0;
-  }
-  int32_t run(u64* d_sh, u64* d_er, hipStream_t stream, const std::function<int32_t(size_t s0, size_t cnt)>& piece) {
-    const size_t count = r.count, words = (count + 63) / 64;
-    for (size_t s0 = 0; s0 < r.S; s0 += per) {
-      const size_t cnt = (r.S - s0) < per ? (r.S - s0) : per;
-      if (dense) {
-        PVW_HIP(hipMemcpy2DAsync(d_sh, count * 32, shares + s0 * r.secret_stride * 4, r.secret_stride * 32, count * 32, cnt,
-                                 hipMemcpyHostToDevice, stream));
-      } else {
-        for (size_t s = 0; s < cnt; ++s)
-          for (size_t col = 0; col < count; ++col)
-            memcpy(&packed[(s * count + col) * 4], shares + ((s0 + s) * r.secret_stride + col * r.point_stride) * 4, 32);
-        PVW_HIP(hipMemcpyAsync(d_sh, packed.data(), cnt * count * 32, hipMemcpyHostToDevice, stream));
-      }
-      if (erased) PVW_HIP(hipMemcpyAsync(d_er, erased + s0 * words, cnt * words * 8, hipMemcpyHostToDevice, stream));
-      PVW_TRY(piece(s0, cnt));
-      PVW_HIP(hipStreamSynchronize(stream));                     // the next piece reuses the staging
-    }
-    return PVW_OK;
-  }
-};
-// host buffers: the secrets go up in pieces as pvw_shamir_reconstruct_wide_checked stages them (a 2D copy for dense rows, else a
-// host repack that is wiped at the end), a piece no larger than one pass over the kernels; the public matrices are made once and
-// col_err adds up over the pieces.  The staged shares, the staged secrets and M are cleared before the call returns.
-// Behind the argument checks; with `erased` (r.erasures) the host-buffer call of 8.21, whose mask rows are staged with the shares
-// of their piece, whichever way those are copied.
-static int32_t correct_wide_host_call(pvw_ctx* c, const ReconstructWide& r, const u64* shares, const u64* erased, u64* out, u32* nerr,
-                                      u32* col_err, u64* err_mask) {
-  PVW_TRY(ensure_device(c));
-  const WideMont mm = make_wide_mont(r.p);
-  const size_t count = r.count, num_secrets = r.S;
-  const size_t words = (count + 63) / 64;
-  size_t per = chunk_1gib((count + 1) * 32 + (words + (erased ? words : 0)) * 8 + 4, num_secrets);
-  if (per > correct_wide_piece(r)) per = correct_wide_piece(r);
-  const CorrectWideLayout lay(r, per);
-  Scratch sc;
-  const size_t r_sh = sc.add(per * count * 32), r_out = sc.add(per * 32), r_ws = sc.add(lay.bytes()), r_nerr = sc.add(per * 4),
-               r_col = sc.add(count * 4), r_mask = sc.add(per * words * 8), r_er = sc.add(erased ? per * words * 8 : 0);
-  WideShareStaging st(r, shares, erased, per);
-  return host_call(c, [&](Workspace* w) -> int32_t {
-    PVW_TRY(sc.take(w));
-    u64 *d_sh = sc.at(r_sh), *d_out = sc.at(r_out), *ws = sc.at(r_ws);
-    ws_mark_secret(w, d_sh, (size_t)((char*)ws - (char*)d_sh) + lay.m_bytes());   // staged shares | staged secrets | M
-    u32 *d_nerr = nerr ? sc.at<u32>(r_nerr) : nullptr, *d_col = col_err ? sc.at<u32>(r_col) : nullptr;
-    u64* d_mask = err_mask ? sc.at(r_mask) : nullptr;
-    u64* d_er = erased ? sc.at(r_er) : nullptr;
-    PVW_TRY(correct_wide_weights(c, r, mm, lay, ws, w->stream));
-    PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
-    PVW_TRY(st.run(d_sh, d_er, w->stream, [&](size_t s0, size_t cnt) -> int32_t {
-      PVW_TRY(correct_wide_piece_enqueue(c, r, mm, lay, ws, d_sh, cnt, count, 1, d_out, d_nerr, d_col, d_mask, w->stream, d_er));
-      PVW_HIP(hipMemcpyAsync(out + s0 * 4, d_out, cnt * 32, hipMemcpyDeviceToHost, w->stream));
-      if (nerr) PVW_HIP(hipMemcpyAsync(nerr + s0, d_nerr, cnt * 4, hipMemcpyDeviceToHost, w->stream));
-      if (err_mask) PVW_HIP(hipMemcpyAsync(err_mask + s0 * words, d_mask, cnt * words * 8, hipMemcpyDeviceToHost, w->stream));
-      return PVW_OK;
-    }));
-    if (col_err) PVW_HIP(hipMemcpyAsync(col_err, d_col, count * 4, hipMemcpyDeviceToHost, w->stream));
-    return PVW_OK;
-  });
-}
 int32_t pvw_shamir_reconstruct_wide_corrected(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
                                               size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
                                               size_t point_stride, uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(reconstruct_wide_checks(r, shares, out));
-  PVW_TRY(correct_wide_device_checks(r));
-  return correct_wide_host_call(c, r, shares, nullptr, out, nerr, col_err, err_mask);
+  PVW_TRY(correct_device_checks(r));
+  return corrected_host_call(c, r, shares, nullptr, out, nerr, col_err, err_mask);
 }
 
 // ------------------------------------------------------------------------ erasures below 2^256
@@ -5121,47 +4907,7 @@ int32_t pvw_shamir_reconstruct_wide_corrected(pvw_ctx* c, const uint64_t* plain_
 // and E_s = (r - eps_s) / 2, row s is decodable iff eps_s <= r and some F_s of degree <= t disagrees with the row in at most E_s
 // of the columns that are not erased.  erased == NULL is the call of 8.20: every entry point hands such a call over as it is.
 
-// The contract in plain C++: per row the columns that are not erased are compacted, berlekamp_welch_wide_host decodes that
-// sub-row with the same t, and the mask bits and col_err go back to the original columns.  A row with fewer than t + 1 columns
-// left (eps_s > r) is undecodable.  Nothing at an erased position is read.
-static void erasures_wide_host(const ReconstructWide& r, const u64* shares, const u64* erased, u64* out, u32* nerr, u32* col_err,
-                               u64* err_mask, const u64* targets = nullptr, size_t num_targets = 0, u64* values = nullptr) {
-  const size_t count = r.count, words = (count + 63) / 64;
-  std::vector<size_t> cols;
-  std::vector<u64> sub_idx(count), sub_sh(count * 4), sub_mask(words);
-  std::vector<u32> sub_col(count);
-  if (col_err) std::fill(col_err, col_err + count, 0u);
-  for (size_t s = 0; s < r.S; ++s) {
-    cols.clear();
-    for (size_t c = 0; c < count; ++c)
-      if (!((erased[s * words + c / 64] >> (c % 64)) & 1)) cols.push_back(c);
-    if (err_mask) std::fill(err_mask + s * words, err_mask + (s + 1) * words, (u64)0);
-    const size_t n = cols.size();
-    if (n < (size_t)r.degree + 1) {
-      if (out)
-        for (int k = 0; k < 4; ++k) out[s * 4 + k] = 0;
-      if (nerr) nerr[s] = PVW_SHAMIR_UNDECODABLE;
-      if (values) std::fill(values + s * num_targets * 4, values + (s + 1) * num_targets * 4, (u64)0);
-      continue;
-    }
-    for (size_t i = 0; i < n; ++i) {
-      sub_idx[i] = r.indices[cols[i]];
-      memcpy(&sub_sh[i * 4], shares + (s * r.secret_stride + cols[i] * r.point_stride) * 4, 32);
-    }
-    ReconstructWide sub{r.p, r.degree, sub_idx.data(), n, 1, n, 1, r.m};
-    u32 ne = 0;
-    berlekamp_welch_wide_host(sub, sub_sh.data(), out ? out + s * 4 : nullptr, &ne, sub_col.data(), sub_mask.data(), targets, num_targets,
-                              values ? values + s * num_targets * 4 : nullptr);
-    if (nerr) nerr[s] = ne;
-    for (size_t i = 0; i < n; ++i)
-      if ((sub_mask[i / 64] >> (i % 64)) & 1) {
-        if (col_err) ++col_err[cols[i]];
-        if (err_mask) err_mask[s * words + cols[i] / 64] |= (u64)1 << (cols[i] % 64);
-      }
-  }
-  volatile u64* vp = sub_sh.data();                                              // as secret as the shares
-  for (size_t i = 0; i < sub_sh.size(); ++i) vp[i] = 0;
-}
+// The contract in plain C++: erasures_host over berlekamp_welch_wide_host.
 static const char* const kWideErasuresUnsized =
     "wide reconstruction with erasures under stream capture: run a call with an erasure mask, the same degree and count and at least as "
     "many secrets on this stream outside capture first (it sizes the workspace)";
@@ -5173,9 +4919,9 @@ int32_t pvw_shamir_reconstruct_wide_erasures_host(const uint64_t* plain_modulus,
   if (!erased)
     return pvw_shamir_reconstruct_wide_corrected_host(plain_modulus, degree, indices, count, shares, num_secrets, secret_stride,
                                                       point_stride, out, nerr, col_err, err_mask);
-  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}, true};
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
   PVW_TRY(reconstruct_wide_checks(r, shares, out));
-  erasures_wide_host(r, shares, erased, out, nerr, col_err, err_mask);
+  erasures_host(r, shares, erased, out, nerr, col_err, err_mask, nullptr, 0, nullptr);
   return PVW_OK;
 }
 int32_t pvw_shamir_reconstruct_wide_erasures_device(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
@@ -5186,10 +4932,10 @@ int32_t pvw_shamir_reconstruct_wide_erasures_device(pvw_ctx* c, const uint64_t* 
     return pvw_shamir_reconstruct_wide_corrected_device(c, plain_modulus, degree, indices, count, d_shares, num_secrets, secret_stride,
                                                         point_stride, d_out, d_nerr, d_col_err, d_err_mask, stream);
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}, true};
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
   PVW_TRY(reconstruct_wide_checks(r, d_shares, d_out));
-  PVW_TRY(correct_wide_device_checks(r));
-  return correct_wide_device_call(c, r, d_shares, d_erased, d_out, d_nerr, d_col_err, d_err_mask, stream, kWideErasuresUnsized);
+  PVW_TRY(correct_device_checks(r));
+  return corrected_device_call(c, r, d_shares, d_erased, d_out, d_nerr, d_col_err, d_err_mask, stream, kWideErasuresUnsized);
 }
 int32_t pvw_shamir_reconstruct_wide_erasures(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
                                              size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
@@ -5199,10 +4945,10 @@ int32_t pvw_shamir_reconstruct_wide_erasures(pvw_ctx* c, const uint64_t* plain_m
     return pvw_shamir_reconstruct_wide_corrected(c, plain_modulus, degree, indices, count, shares, num_secrets, secret_stride,
                                                  point_stride, out, nerr, col_err, err_mask);
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}, true};
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
   PVW_TRY(reconstruct_wide_checks(r, shares, out));
-  PVW_TRY(correct_wide_device_checks(r));
-  return correct_wide_host_call(c, r, shares, erased, out, nerr, col_err, err_mask);
+  PVW_TRY(correct_device_checks(r));
+  return corrected_host_call(c, r, shares, erased, out, nerr, col_err, err_mask);
 }
 
 // ------------------------------------------------------------------------ evaluation below 2^256
@@ -5211,10 +4957,10 @@ int32_t pvw_shamir_reconstruct_wide_erasures(pvw_ctx* c, const uint64_t* plain_m
 
 // What the matching wide call refuses, in its order (values stands where it has out: out may be NULL here), then the targets.
 // device: num_targets is bounded BEFORE the targets are read, so a refused count costs no walk over the array.
-static int32_t evaluate_wide_checks(ReconstructWide& r, const void* shares, const uint64_t* targets, size_t num_targets, const void* values,
+static int32_t evaluate_wide_checks(Reconstruct<WideCalls>& r, const void* shares, const uint64_t* targets, size_t num_targets, const void* values,
                                     bool device) {
   PVW_TRY(reconstruct_wide_checks(r, shares, values));
-  if (device) PVW_TRY(correct_wide_device_checks(r));
+  if (device) PVW_TRY(correct_device_checks(r));
   if (!targets) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   if (num_targets == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no targets to evaluate at");
   if (device && num_targets >= ((size_t)1 << 31))
@@ -5232,7 +4978,7 @@ int32_t pvw_shamir_evaluate_wide_corrected_host(const uint64_t* plain_modulus, u
                                                 const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
                                                 const uint64_t* targets, size_t num_targets, uint64_t* values, uint64_t* out,
                                                 uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
-  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(evaluate_wide_checks(r, shares, targets, num_targets, values, false));
   berlekamp_welch_wide_host(r, shares, out, nerr, col_err, err_mask, targets, num_targets, values);
   return PVW_OK;
@@ -5244,148 +4990,12 @@ int32_t pvw_shamir_evaluate_wide_erasures_host(const uint64_t* plain_modulus, ui
   if (!erased)
     return pvw_shamir_evaluate_wide_corrected_host(plain_modulus, degree, indices, count, shares, num_secrets, secret_stride, point_stride,
                                                    targets, num_targets, values, out, nerr, col_err, err_mask);
-  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}, true};
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
   PVW_TRY(evaluate_wide_checks(r, shares, targets, num_targets, values, false));
-  erasures_wide_host(r, shares, erased, out, nerr, col_err, err_mask, targets, num_targets, values);
+  erasures_host(r, shares, erased, out, nerr, col_err, err_mask, targets, num_targets, values);
   return PVW_OK;
 }
 
-// Targets per group, by the rule of evaluate_group: a target costs a column of C, of Xt and of Xd, xt, scale and coin
-static size_t evaluate_wide_group(const ReconstructWide& r, size_t num_targets) {
-  const size_t per = (r.count + 2 * r.nk() + 2) * 32 + 4;
-  const long env = PVW_ENV_INT("PVW_EVALUATE_GROUP_BYTES", 0);
-  const size_t budget = env > 0 ? (size_t)env : (size_t)64 << 20;
-  size_t tg = budget / per;
-  if (tg > 64) tg -= tg % 64;
-  if (tg == 0) tg = 1;
-  return tg < num_targets ? tg : num_targets;
-}
-// The per-secret scratch in bytes: a row of M, of the syndromes and of the locators as in correct_wide_piece, a row of y o M, of
-// raw, of Psi and of Psi' at the group's targets and a stand-in for out; L and a stand-in for nerr
-static size_t evaluate_wide_secret_bytes(const ReconstructWide& r, size_t Tg) {
-  return (2 * r.count + r.red() + r.nk() + 3 * Tg + 1) * 32 + 8;
-}
-// secrets per pass, by the rule of correct_wide_piece
-static size_t evaluate_wide_piece(const ReconstructWide& r, size_t Tg) {
-  size_t cap = evaluate_piece_budget() / evaluate_wide_secret_bytes(r, Tg);
-  if (cap == 0) cap = 1;
-  if (cap > 65535u * 4) cap = 65535u * 4;
-  return cap < r.S ? cap : r.S;
-}
-// The scratch of one call, in words from its base: the block of the wide corrected call first (CorrectWideLayout: M leads it), then
-//   YM [cap][count][4] | raw [cap][Tg][4] | outs [cap][4]   -- depend on the shares: the second region marked secret
-//   PsiT [cap][Tg][4] | PsiD [cap][Tg][4] | nerr [cap] (u32) | the group's public matrices (shamir_evaluate_wide_public_words)
-// Every region of elements starts at a multiple of four words.
-struct EvaluateWideLayout {
-  CorrectWideLayout cl;
-  size_t Tg;
-  size_t ym, raw, outs, psiT, psiD, nerr, pub, total;   // word offsets
-  static size_t up4(size_t w) { return (w + 3) & ~(size_t)3; }
-  EvaluateWideLayout(const ReconstructWide& rc, size_t cap, size_t Tg_) : cl(rc, cap), Tg(Tg_) {
-    ym = up4(cl.total);
-    raw = ym + cap * rc.count * 4;
-    outs = raw + cap * Tg * 4;
-    psiT = outs + cap * 4;
-    psiD = psiT + cap * Tg * 4;
-    nerr = psiD + cap * Tg * 4;
-    pub = up4(nerr + (cap + 1) / 2);
-    total = pub + shamir_evaluate_wide_public_words(rc.count, Tg, cl.nk);
-  }
-  size_t bytes() const { return total * 8; }
-  size_t secret_bytes() const { return (psiT - ym) * 8; }
-};
-// What the stream's block must hold for a call: never less than the layout takes (96 bytes cover its roundings), and no smaller
-// for more secrets or more targets at the same (degree, count) and no smaller with a mask -- the rule a captured call is checked by.
-static size_t evaluate_wide_need_bytes(const ReconstructWide& r, size_t Tg) {
-  const size_t per = evaluate_wide_secret_bytes(r, Tg), budget = evaluate_piece_budget();
-  size_t part = r.S > budget / per ? budget : r.S * per;
-  if (part < per) part = per;
-  return part + 96 +
-         (shamir_correct_wide_public_words(r.count, r.degree, r.nk()) + shamir_evaluate_wide_public_words(r.count, Tg, r.nk())) * 8;
-}
-// One pass: ns <= lay.cl.cap secrets from d_shares are decoded (their out, nerr and mask rows; col_err is added to) and evaluated
-// at all targets, group by group, into d_values (rows num_targets elements apart).  `resident` is the first target of the group
-// whose public matrices the block holds; with one group they are built once for all passes.
-static int32_t evaluate_wide_pass_enqueue(pvw_ctx* c, const ReconstructWide& r, const WideMont& mm, const EvaluateWideLayout& lay, u64* ws,
-                                          const u64* d_shares, size_t ns, size_t secret_stride, size_t point_stride, const u64* targets,
-                                          size_t num_targets, u64* d_values, u64* d_out, u32* d_nerr, u32* d_col_err, u64* d_mask,
-                                          size_t* resident, hipStream_t s, const u64* d_erased) {
-  if (!d_out) d_out = ws + lay.outs;
-  if (!d_nerr) d_nerr = (u32*)(ws + lay.nerr);
-  PVW_TRY(correct_wide_piece_enqueue(c, r, mm, lay.cl, ws, d_shares, ns, secret_stride, point_stride, d_out, d_nerr, d_col_err, d_mask, s,
-                                     d_erased));
-  const u64 *x = ws + lay.cl.pub, *aux = x + r.count * 4;
-  const u64 *M = ws, *Psi = ws + lay.cl.lam;
-  u64 *YM = ws + lay.ym, *raw = ws + lay.raw, *PsiT = ws + lay.psiT, *PsiD = ws + lay.psiD, *pub = ws + lay.pub;
-  const size_t nk = lay.cl.nk;
-  {
-    ProfScope ps(c, "shamir_evaluate_wide", s);
-    PVW_HIP(launch_shamir_ym_wide(d_shares, secret_stride, point_stride, M, YM, (u32)ns, (u32)r.count, mm, s));
-  }
-  for (size_t j0 = 0; j0 < num_targets; j0 += lay.Tg) {
-    const size_t tg = num_targets - j0 < lay.Tg ? num_targets - j0 : lay.Tg;
-    if (*resident != j0) {
-      ProfScope ps(c, "shamir_evaluate_wide_weights", s);
-      PVW_HIP(launch_shamir_points_wide(targets + j0, tg, pub, mm, s));
-      PVW_HIP(launch_shamir_evaluate_weights_wide(x, aux, pub, r.count, (u32)nk, tg, mm, s));
-      *resident = j0;
-    }
-    ProfScope ps(c, "shamir_evaluate_wide", s);
-    const u64 *scale = pub + tg * 4, *C = scale + tg * 4, *Xt = C + r.count * tg * 4, *Xd = Xt + nk * tg * 4;
-    const u32* coin = (const u32*)(Xd + nk * tg * 4);
-    ShamirMatmulWide a{};
-    a.A = YM, a.secret_stride = r.count, a.term_stride = 1;
-    a.W = C, a.out = raw;
-    a.ns = (u32)ns, a.terms = (u32)r.count, a.T = (u32)tg, a.m = mm;
-    PVW_HIP(launch_shamir_matmul_wide(a, s));
-    ShamirMatmulWide b{};
-    b.A = Psi, b.secret_stride = nk, b.term_stride = 1;
-    b.W = Xt, b.out = PsiT;
-    b.ns = (u32)ns, b.terms = (u32)nk, b.T = (u32)tg, b.m = mm;
-    PVW_HIP(launch_shamir_matmul_wide(b, s));
-    b.W = Xd, b.out = PsiD;
-    PVW_HIP(launch_shamir_matmul_wide(b, s));
-    ShamirEvalFinishWide f{};
-    f.shares = d_shares, f.secret_stride = secret_stride, f.point_stride = point_stride;
-    f.M = M, f.nerr = d_nerr, f.raw = raw, f.PsiT = PsiT, f.PsiD = PsiD, f.scale = scale, f.coin = coin;
-    f.values = d_values + j0 * 4, f.value_stride = num_targets;
-    f.ns = (u32)ns, f.count = (u32)r.count, f.Tg = (u32)tg, f.m = mm;
-    PVW_HIP(launch_shamir_evaluate_finish_wide(f, s));
-  }
-  return PVW_OK;
-}
-
-// The device call behind its argument checks; with d_erased (r.erasures) the decode is that of 8.21
-static int32_t evaluate_wide_device_call(pvw_ctx* c, const ReconstructWide& r, const u64* d_shares, const u64* d_erased, const u64* targets,
-                                         size_t num_targets, u64* d_values, u64* d_out, u32* d_nerr, u32* d_col_err, u64* d_err_mask,
-                                         void* stream, const char* unsized) {
-  const WideMont mm = make_wide_mont(r.p);
-  const size_t Tg = evaluate_wide_group(r, num_targets);
-  const EvaluateWideLayout lay(r, evaluate_wide_piece(r, Tg), Tg);
-  const size_t need = evaluate_wide_need_bytes(r, Tg);
-  if (need < lay.bytes()) return fail(PVW_ERR_INTERNAL, "wide evaluation scratch: layout beyond its bound");
-  const size_t words = (r.count + 63) / 64;
-  // the caller's stream is checked before the context initialises its device (pvw_shamir_reconstruct_checked_device)
-  auto sized = [&](hipStream_t s) { return grown_capture_check(c, s, &Workspace::correct_wide_bytes, need, unsized); };
-  if (stream) PVW_TRY(sized((hipStream_t)stream));
-  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
-    if (w->correct_wide_bytes < need) ws_public(w, w->correct_wide, w->correct_wide_bytes);   // the block is about to go
-    PVW_TRY(ws_grow(&w->correct_wide, &w->correct_wide_bytes, need, s, true));
-    ws_mark_secret(w, w->correct_wide, lay.cl.m_bytes());
-    ws_mark_secret(w, w->correct_wide + lay.ym, lay.secret_bytes());
-    PVW_TRY(correct_wide_weights(c, r, mm, lay.cl, w->correct_wide, s));
-    PVW_HIP(launch_shamir_zero_counts(d_col_err, r.count, s));
-    size_t resident = SIZE_MAX;
-    for (size_t s0 = 0; s0 < r.S; s0 += lay.cl.cap) {
-      const size_t ns = r.S - s0 < lay.cl.cap ? r.S - s0 : lay.cl.cap;
-      PVW_TRY(evaluate_wide_pass_enqueue(c, r, mm, lay, w->correct_wide, d_shares + s0 * r.secret_stride * 4, ns, r.secret_stride,
-                                         r.point_stride, targets, num_targets, d_values + s0 * num_targets * 4, Report::from(d_out, s0 * 4),
-                                         Report::from(d_nerr, s0), d_col_err, Report::from(d_err_mask, s0 * words), &resident, s,
-                                         Report::from(d_erased, s0 * words)));
-    }
-    return PVW_OK;
-  });
-}
 static const char* const kWideEvaluateUnsized =
     "wide corrected evaluation under stream capture: run a call with the same degree and count, at least as many targets and at least "
     "as many secrets on this stream outside capture first (it sizes the workspace)";
@@ -5399,9 +5009,9 @@ int32_t pvw_shamir_evaluate_wide_corrected_device(pvw_ctx* c, const uint64_t* pl
                                                   uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err, uint64_t* d_err_mask,
                                                   void* stream) {
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(evaluate_wide_checks(r, d_shares, targets, num_targets, d_values, true));
-  return evaluate_wide_device_call(c, r, d_shares, nullptr, targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask, stream,
+  return evaluate_device_call(c, r, d_shares, nullptr, targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask, stream,
                                    kWideEvaluateUnsized);
 }
 int32_t pvw_shamir_evaluate_wide_erasures_device(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
@@ -5414,61 +5024,20 @@ int32_t pvw_shamir_evaluate_wide_erasures_device(pvw_ctx* c, const uint64_t* pla
                                                      point_stride, targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask,
                                                      stream);
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}, true};
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
   PVW_TRY(evaluate_wide_checks(r, d_shares, targets, num_targets, d_values, true));
-  return evaluate_wide_device_call(c, r, d_shares, d_erased, targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask, stream,
+  return evaluate_device_call(c, r, d_shares, d_erased, targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask, stream,
                                    kWideEvaluateErasuresUnsized);
 }
 
-// host buffers: staged as pvw_shamir_reconstruct_wide_corrected stages (WideShareStaging: both copy paths, a piece at most one
-// pass, the mask rows with their shares); the values of a piece come down as one block.  The staged shares, secrets and values,
-// M, y o M and raw are cleared before the call returns.
-static int32_t evaluate_wide_host_call(pvw_ctx* c, const ReconstructWide& r, const u64* shares, const u64* erased, const u64* targets,
-                                       size_t num_targets, u64* values, u64* out, u32* nerr, u32* col_err, u64* err_mask) {
-  PVW_TRY(ensure_device(c));
-  const WideMont mm = make_wide_mont(r.p);
-  const size_t count = r.count, words = (count + 63) / 64;
-  const size_t Tg = evaluate_wide_group(r, num_targets);
-  size_t per = chunk_1gib((count + 1 + num_targets) * 32 + (words + (erased ? words : 0)) * 8 + 4, r.S);
-  if (per > evaluate_wide_piece(r, Tg)) per = evaluate_wide_piece(r, Tg);
-  const EvaluateWideLayout lay(r, per, Tg);
-  Scratch sc;
-  const size_t r_sh = sc.add(per * count * 32), r_out = sc.add(per * 32), r_val = sc.add(per * num_targets * 32), r_ws = sc.add(lay.bytes()),
-               r_nerr = sc.add(per * 4), r_col = sc.add(count * 4), r_mask = sc.add(per * words * 8),
-               r_er = sc.add(erased ? per * words * 8 : 0);
-  WideShareStaging st(r, shares, erased, per);
-  return host_call(c, [&](Workspace* w) -> int32_t {
-    PVW_TRY(sc.take(w));
-    u64 *d_sh = sc.at(r_sh), *d_out = sc.at(r_out), *d_val = sc.at(r_val), *ws = sc.at(r_ws);
-    ws_mark_secret(w, d_sh, (size_t)((char*)ws - (char*)d_sh) + lay.cl.m_bytes());   // staged shares | secrets | values | M
-    ws_mark_secret(w, ws + lay.ym, lay.secret_bytes());                              // y o M | raw | the stand-in for out
-    u32 *d_nerr = sc.at<u32>(r_nerr), *d_col = col_err ? sc.at<u32>(r_col) : nullptr;
-    u64* d_mask = err_mask ? sc.at(r_mask) : nullptr;
-    u64* d_er = erased ? sc.at(r_er) : nullptr;
-    PVW_TRY(correct_wide_weights(c, r, mm, lay.cl, ws, w->stream));
-    PVW_HIP(launch_shamir_zero_counts(d_col, count, w->stream));
-    size_t resident = SIZE_MAX;
-    PVW_TRY(st.run(d_sh, d_er, w->stream, [&](size_t s0, size_t cnt) -> int32_t {
-      PVW_TRY(evaluate_wide_pass_enqueue(c, r, mm, lay, ws, d_sh, cnt, count, 1, targets, num_targets, d_val, d_out, d_nerr, d_col, d_mask,
-                                         &resident, w->stream, d_er));
-      PVW_HIP(hipMemcpyAsync(values + s0 * num_targets * 4, d_val, cnt * num_targets * 32, hipMemcpyDeviceToHost, w->stream));
-      if (out) PVW_HIP(hipMemcpyAsync(out + s0 * 4, d_out, cnt * 32, hipMemcpyDeviceToHost, w->stream));
-      if (nerr) PVW_HIP(hipMemcpyAsync(nerr + s0, d_nerr, cnt * 4, hipMemcpyDeviceToHost, w->stream));
-      if (err_mask) PVW_HIP(hipMemcpyAsync(err_mask + s0 * words, d_mask, cnt * words * 8, hipMemcpyDeviceToHost, w->stream));
-      return PVW_OK;
-    }));
-    if (col_err) PVW_HIP(hipMemcpyAsync(col_err, d_col, count * 4, hipMemcpyDeviceToHost, w->stream));
-    return PVW_OK;
-  });
-}
 int32_t pvw_shamir_evaluate_wide_corrected(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
                                            const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
                                            const uint64_t* targets, size_t num_targets, uint64_t* values, uint64_t* out, uint32_t* nerr,
                                            uint32_t* col_err, uint64_t* err_mask) {
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}};
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(evaluate_wide_checks(r, shares, targets, num_targets, values, true));
-  return evaluate_wide_host_call(c, r, shares, nullptr, targets, num_targets, values, out, nerr, col_err, err_mask);
+  return evaluate_host_call(c, r, shares, nullptr, targets, num_targets, values, out, nerr, col_err, err_mask);
 }
 int32_t pvw_shamir_evaluate_wide_erasures(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
                                           const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
@@ -5478,9 +5047,9 @@ int32_t pvw_shamir_evaluate_wide_erasures(pvw_ctx* c, const uint64_t* plain_modu
     return pvw_shamir_evaluate_wide_corrected(c, plain_modulus, degree, indices, count, shares, num_secrets, secret_stride, point_stride,
                                               targets, num_targets, values, out, nerr, col_err, err_mask);
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
-  ReconstructWide r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, WideMod{}, true};
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
   PVW_TRY(evaluate_wide_checks(r, shares, targets, num_targets, values, true));
-  return evaluate_wide_host_call(c, r, shares, erased, targets, num_targets, values, out, nerr, col_err, err_mask);
+  return evaluate_host_call(c, r, shares, erased, targets, num_targets, values, out, nerr, col_err, err_mask);
 }
 
 // ------------------------------------------------------------------------ handover over a prime below 2^256
@@ -5574,7 +5143,7 @@ static int32_t handover_wide_checks(HandoverWide& h, const void* weights, bool d
       h.col.push_back((u32)d);
     }
   if (h.vidx.empty()) return fail(PVW_ERR_INVALID_PARAMETERS, "no valid holder");
-  ReconstructWide r{h.p, 0, h.vidx.data(), h.vidx.size(), 1, 1, 1, WideMod{}};
+  Reconstruct<WideCalls> r{h.p, 0, h.vidx.data(), h.vidx.size(), 1, 1, 1};
   PVW_TRY(reconstruct_wide_checks(r, weights, weights));
   h.m = r.m;
   PVW_TRY(wide_limb_count(h.m, h.limb_bits, &h.NL));
@@ -5680,7 +5249,7 @@ int32_t pvw_shamir_wide_handover_weights_host(const uint64_t* plain_modulus, con
   return PVW_OK;
 }
 
-// targets per group: a target costs a column of C, xt, scale and coin; the budget of evaluate_wide_group
+// targets per group: a target costs a column of C, xt, scale and coin; the budget of evaluate_group
 static size_t handover_wide_group(const HandoverWide& h) {
   const size_t per = (h.nv() + 2) * 32 + 4;
   size_t tg = ((size_t)64 << 20) / per;

@@ -33,7 +33,7 @@ P17, P64, P89, P255 = 65537, 2**64 + 13, 2**89 - 1, 2**255 - 19
 PRIMES4 = (P17, P64, P255, SECP_N)
 U64 = (1 << 64) - 1
 CORRECT_PIECE_BYTES = 2048          # the `staged` case's PVW_CORRECT_PIECE_BYTES
-CORRECT_PIECE_DEFAULT = 64 << 20    # correct_wide_piece without it
+CORRECT_PIECE_DEFAULT = 64 << 20    # correct_piece without it
 POINTS = 140                        # party indices of the reconstructions are drawn below this
 W = api._wide
 
@@ -216,7 +216,7 @@ def j_checked_wide(g, t, count, party_major, pm, S, device=False):
 
 
 def corrected_pieces(t, count, S, b, cb):
-    """pvw_shamir_reconstruct_wide_corrected: the staging piece, no larger than one pass over the kernels (correct_wide_piece)"""
+    """pvw_shamir_reconstruct_wide_corrected: the staging piece, no larger than one pass over the kernels (correct_piece)"""
     r = count - t - 1
     per = chunk((count + 1) * 32 + (count + 63) // 64 * 8 + 4, S, b)
     cap = min(max(cb // ((count + r + r // 2 + 1) * 32 + 4), 1), 65535 * 4, S)

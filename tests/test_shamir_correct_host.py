@@ -216,6 +216,23 @@ def test_device_entry_points_refuse_the_same_arguments_before_any_device_work():
         assert _rc(name=name, ctx=prm._h, t=0, S=1, idx=tuple(range(8193))) == INVALID_PARAMETERS      # r = 8192: E + 1 = 4097
 
 
+def test_device_forms_refuse_2_31_secrets_and_name_the_locator_bound_before_any_device_work():
+    """the kernels' 32-bit counts: refused before the shares are read (the array behind the count holds two rows); the locator
+    bound's own text"""
+    lib = _ffi.lib()
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    prm = P.PvwParametersBuilder().set_parties(8).set_dimension(2).set_l(8).set_moduli([0xFFFFEE001, 0xFFFFC4001, 0x1FFFFE0001]).build()
+    ix, sh, o = np.arange(4, dtype=np.uint64), np.ones(8, dtype=np.uint64), np.zeros(2, dtype=np.uint64)
+    for name, tail in (("pvw_shamir_reconstruct_corrected_device", (None,)), ("pvw_shamir_reconstruct_corrected", ())):
+        rc = getattr(lib, name)(prm._h, P61, 1, ptr(ix), 4, ptr(sh), 1 << 31, 4, 1, ptr(o), None, None, None, *tail)
+        assert rc == INVALID_PARAMETERS and "2^31" in _ffi.last_error(lib), name
+    assert not o.any()
+    for name in ("buffers", "device"):
+        assert _rc(name=name, ctx=prm._h, t=0, S=1, idx=tuple(range(8193))) == INVALID_PARAMETERS
+        text = _ffi.last_error(lib)
+        assert "locator" in text and "4096" in text and "8192" in text and "wide" not in text and "erasures" not in text, name
+
+
 # ---- C++ mirror -------------------------------------------------------------------------------------------------------
 SRC = os.path.join(ROOT, "tests", "cpp", "reconstruct_corrected.cpp")
 EXE = os.path.join(ROOT, "build", "reconstruct_corrected_cpp")

@@ -366,6 +366,25 @@ def test_device_entry_points_refuse_the_same_arguments_before_any_device_work():
         assert _rc(name=name, ctx=prm._h, targets=(7,), T=1 << 31) == INVALID_PARAMETERS and "num_targets" in _ffi.last_error(lib)
 
 
+def test_device_forms_refuse_2_31_secrets_before_any_device_work():
+    """the kernels' 32-bit counts, with a mask as without: refused before the shares are read (the arrays behind the count hold two
+    rows)"""
+    lib = _ffi.lib()
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    prm = P.PvwParametersBuilder().set_parties(8).set_dimension(2).set_l(8).set_moduli([0xFFFFEE001, 0xFFFFC4001, 0x1FFFFE0001]).build()
+    ix, sh, er = np.arange(4, dtype=np.uint64), np.ones(8, dtype=np.uint64), np.zeros(2, dtype=np.uint64)
+    tg, v = np.array([9], dtype=np.uint64), np.zeros(2, dtype=np.uint64)
+    for tail in ((None,), ()):
+        suffix = "_device" if tail else ""
+        rc = getattr(lib, "pvw_shamir_reconstruct_erasures" + suffix)(prm._h, P61, 1, ptr(ix), 4, ptr(sh), 1 << 31, 4, 1, ptr(er), ptr(v), None, None,
+                                                                      None, *tail)
+        assert rc == INVALID_PARAMETERS and "2^31" in _ffi.last_error(lib), suffix
+        rc = getattr(lib, "pvw_shamir_evaluate_erasures" + suffix)(prm._h, P61, 1, ptr(ix), 4, ptr(sh), 1 << 31, 4, 1, ptr(er), ptr(tg), 1, ptr(v),
+                                                                   None, None, None, None, *tail)
+        assert rc == INVALID_PARAMETERS and "2^31" in _ffi.last_error(lib) and "num_targets" not in _ffi.last_error(lib), suffix
+    assert not v.any()
+
+
 # ---- C++ mirror -------------------------------------------------------------------------------------------------------
 SRC = os.path.join(ROOT, "tests", "cpp", "reconstruct_erasures.cpp")
 EXE = os.path.join(ROOT, "build", "reconstruct_erasures_cpp")
