@@ -169,6 +169,39 @@ MIXED_CHAINS = {
 EDGE_CHAINS = {**{"pure_" + k: v for k, v in PURE_CHAINS.items()}, **{"mixed_" + k: v for k, v in MIXED_CHAINS.items()}}
 
 
+# ---------------------------------------------------------------- wide prime classes
+# Concrete primes p < 2^256 at the widths where the arithmetic of the 256-bit Shamir family (pvw_wide.h) switches code paths.
+# With bits = bitlen(p) and shift = 256 - bits: wide_shl / wide_shr move words when shift & 128 and when shift & 64 and shift
+# bits under `if (shift & 63)`; the word reduction cuts its input into digits of min(16, bits - 1) bits; make_wide_mod takes
+# another branch for the reciprocal when the top word of p << shift is 2^64 - 1; the ninth-digit (`top` / carry) paths of
+# wide_cond_sub, wide_acc_add, wide_redc and wide_add_p fire only for p close to 2^256.
+# tiny: word-reduction digits of 1, 2, 2, 7, 8 and 15 bits (up to 256 Horner steps a word, for p = 3)
+WIDE_TINY = [3, 5, 7, 251, 257, 65521]
+# word16: the first prime with the full 16-bit digit
+WIDE_WORD16 = [65537]
+# one_word: 31, 32, 33, 63 and 64 bits; at 64 bits shift = 192 is both word stages and no bit stage (the `if (b)` guard alone
+# keeps a shift by 64 away), and p << 192 has a top word of 2^64 - 59, 2^64 - 1 for none of these
+WIDE_ONE_WORD = [2**31 - 1, 2**32 - 5, 2**32 + 15, 2**63 - 25, 2**64 - 59]
+# word_edges: each pair of shift stages from both ends (65..128 bits: the 128 stage alone; 129..192 bits: the 64 stage alone;
+# 193 bits and up: neither), and the word-move-only shifts 128 (2^128 - 159) and 64 (2^192 - 237)
+WIDE_WORD_EDGES = [2**64 + 13, 2**96 - 17, 2**128 - 159, 2**128 + 51, 2**160 - 47, 2**192 - 237, 2**192 + 133, 2**224 - 63]
+# top: 255 bits and the bottom of 256 bits, and two primes close to 2^256: the carry / `top` paths, and the reciprocal's
+# wrapped branch (the top word of p << shift is 2^64 - 1)
+WIDE_SECP_N = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
+WIDE_TOP = [2**255 - 19, 2**255 + 95, WIDE_SECP_N, 2**256 - 189]
+WIDE_PRIME_CLASSES = {"tiny": WIDE_TINY, "word16": WIDE_WORD16, "one_word": WIDE_ONE_WORD, "word_edges": WIDE_WORD_EDGES, "top": WIDE_TOP}
+WIDE_EDGE_PRIMES = sorted({p for c in WIDE_PRIME_CLASSES.values() for p in c})
+
+
+def wide_branches(p):
+    """the branches of pvw_wide.h that p reaches, from bitlen(p) and the words of p alone: (shift & 128, shift & 64, whether the
+    bit stage is skipped, the digit width of the word reduction, whether the reciprocal's divisor wraps)"""
+    bits = p.bit_length()
+    shift = 256 - bits
+    top_word = ((p << shift) >> 192) & 0xFFFFFFFFFFFFFFFF
+    return bool(shift & 128), bool(shift & 64), shift & 63 == 0, min(16, bits - 1), (top_word + 1) & 0xFFFFFFFFFFFFFFFF == 0
+
+
 def chain_max_l(moduli):
     """largest ring degree l <= 64 every modulus of the chain serves (q = 1 mod 2l)"""
     l = 64

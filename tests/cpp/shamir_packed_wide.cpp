@@ -211,9 +211,15 @@ int main(int argc, char** argv) {
     const WideMont mm = make_wide_mont(p);
     rng_state = p[0] ^ 0x5eed;
     static const u32 PACKS[] = {1, 2, 3, 5, 8, 17};
-    static const u32 XS[] = {1, 2, 255, 4096, 65000};                 // x + K - 1 < 65537, the smallest prime
+    static const u32 XS[] = {1, 2, 255, 4096, 65000};                 // x + K - 1 < 65537
+    // a prime below 65537 serves the packs and points with x + K - 1 < p only: the others are left out, and the last point is
+    // the largest one the pack leaves, x = p - K
+    const bool small_p = !(p[1] | p[2] | p[3]) && p[0] < 65537;
+    u32 served = 0;
     for (u32 c = 0; c < cases; ++c) {
       const u32 K = PACKS[c % 6], t = (c / 6) % 5;
+      if (small_p && (u64)K + 1 > p[0]) continue;                        // not even x = 1
+      ++served;
       std::vector<W4> w3;
       basis(w3, K, mm);
       const std::vector<W4> dinv = difference_inverses(K, mm);
@@ -221,7 +227,9 @@ int main(int argc, char** argv) {
       for (u32 j = 0; j < K; ++j) secrets[j] = edge_word(p, c + j);
       for (u32 j = 0; j < t; ++j) coeffs[j] = edge_word(p, c + j + 2);
       for (u32 xi = 0; xi < 5; ++xi) {
-        const u32 x = XS[xi];
+        u32 x = XS[xi];
+        if (small_p && xi == 4) x = (u32)p[0] - K;
+        if (small_p && (u64)x + K > p[0]) continue;
         std::vector<W4> Lw;
         W4 zt;
         weights(Lw, zt, w3, K, x, m, mm);
@@ -231,6 +239,10 @@ int main(int argc, char** argv) {
           return 1;
         }
       }
+    }
+    if (!served) {
+      printf("prime %s served no case\n", argv[a]);
+      return 1;
     }
   }
   printf("SHAMIR_PACKED_WIDE_OK\n");

@@ -251,15 +251,19 @@ int main(int argc, char** argv) {
     const WideMont m = make_wide_mont(p);
     const bool above_2_64 = p[2] || p[3] || p[1] > 1 || (p[1] == 1 && p[0] != 0);
     rng_state = 0xDEC0DE00 + (u64)a;
+    // the points come from 1 .. pool: 60000 of them, or every point of the field where p has fewer; a tiny p cuts t and r
+    // down to the shapes whose points it can tell apart (count <= pool)
+    const u64 pool = (p[1] | p[2] | p[3]) || p[0] > 60000 ? 60000 : p[0] - 1;
     for (long i = 0; i < cases; ++i) {
       // the shapes in turn: t 0..6, r 0..9; for the first and the last prime one row with E = 66 errors, whose locator spans more
       // than one block of 64 coefficients (r = 132)
-      const bool big = i == cases - 1 && (a == 2 || a == argc - 1);
-      const u32 t = (u32)(i % 7), r = big ? 132 : (u32)((i / 7 + i) % 10), count = t + 1 + r, E = r / 2;
+      const bool big = i == cases - 1 && (a == 2 || a == argc - 1) && pool >= 140;
+      const u32 t = (u32)((u64)(i % 7) % pool), rmax = (u32)(pool - t < 10 ? pool - t : 10);
+      const u32 r = big ? 132 : (u32)((i / 7 + i) % rmax), count = t + 1 + r, E = r / 2;
       std::vector<W4> x(count), y(count), co(t + 1);
       std::vector<u64> pts;
       while (pts.size() < count) {
-        u64 v = 1 + rnd64() % 60000;                           // below every prime of the list
+        u64 v = 1 + rnd64() % pool;                            // below the prime
         if (pts.empty() && above_2_64) v = 0;                    // stands for the point 2^64 (index 2^64 - 1)
         bool dup = false;
         for (u64 q : pts) dup |= q == v;

@@ -469,21 +469,24 @@ int main(int argc, char** argv) {
     rng_state = 0xE7A5E500 + (u64)a;
     // the shapes: t 0..3 x r 0..7, and every (eps, nu) with eps <= r + 1 and nu <= E_s + 1; for the first and the last prime one
     // row with r = 200, eps = 70 and E_s = 65 errors: Gamma, the Forney pass and the locator each span more than one block of 64
+    // the points come from 1 .. pool: 60000 of them, or every point of the field where p has fewer; a tiny p keeps the shapes
+    // whose points it can tell apart (count <= pool)
+    const u64 pool = (p[1] | p[2] | p[3]) || p[0] > 60000 ? 60000 : p[0] - 1;
     struct Shape { u32 t, r, eps, nu; };
     std::vector<Shape> shapes;
     for (u32 t = 0; t < 4; ++t)
-      for (u32 r = 0; r < 8; ++r)
+      for (u32 r = 0; r < 8 && t + 1 + r <= pool; ++r)
         for (u32 eps = 0; eps <= r + 1; ++eps) {
           const u32 Es = eps <= r ? (r - eps) / 2 : 0;
           for (u32 nu = 0; nu <= Es + 1 && eps + nu <= t + 1 + r; ++nu) shapes.push_back({t, r, eps, nu});
         }
-    if (a == 1 || a == argc - 1) shapes.push_back({2, 200, 70, 65});
+    if ((a == 1 || a == argc - 1) && pool >= 203) shapes.push_back({2, 200, 70, 65});
     for (size_t i = 0; i < shapes.size(); ++i) {
       const u32 t = shapes[i].t, r = shapes[i].r, eps = shapes[i].eps, nu = shapes[i].nu, count = t + 1 + r;
       std::vector<W4> x(count), y(count), co(t + 1);
       std::vector<u64> pts;
       while (pts.size() < count) {
-        u64 v = 1 + rnd64() % 60000;                           // below every prime of the list
+        u64 v = 1 + rnd64() % pool;                            // below the prime
         if (pts.empty() && above_2_64) v = 0;                    // stands for the point 2^64 (index 2^64 - 1)
         bool dup = false;
         for (u64 q : pts) dup |= q == v;
@@ -526,7 +529,8 @@ int main(int argc, char** argv) {
       // columns), three points that are no column's, and the first column once more
       std::vector<W4> xt = x;
       for (u32 k = 0; k < 3; ++k) {
-        const u64 xw[4] = {60001 + rnd64() % 5000, 0, 0, 0};       // below every prime of the list, above every column's point
+        // above every column's point and below the prime; where p has no such point, any point of the field
+        const u64 xw[4] = {pool == 60000 && ((p[1] | p[2] | p[3]) || p[0] > 65001) ? 60001 + rnd64() % 5000 : 1 + rnd64() % pool, 0, 0, 0};
         W4 v;
         wide_mont_in(xw, m, v.v);
         xt.push_back(v);

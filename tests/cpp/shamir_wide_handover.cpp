@@ -5,7 +5,7 @@
 // (lambda = scale C or the unit vector, one product by 2^limb_bits R per limb, out of Montgomery form, centred, cut),
 // shamir_signed_digits_wide_kernel and shamir_wide_from_digits_kernel.  The program prints what the kernels would store; the
 // test compares it with the _host routines of the library, which run the scaled step and prefix / suffix products instead.
-// Stand-alone: shamir_wide_handover <prime in hex>...
+// Stand-alone: shamir_wide_handover [holders=i,j,..] <prime in hex>...
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -205,16 +205,30 @@ int main(int argc, char** argv) {
     return 2;
   }
   const u32 widths[4] = {8, 33, 60, 64};
-  for (int a = 1; a < argc; ++a) {
+  // holders 0, 2, 3, 5, 9 with holder 2 (the second of the list) masked out, or the list of "holders=i,j,.." (two at least, for
+  // a prime whose field has no point 10); targets 0, the point of the third holder (valid; of the last one where there are
+  // two), the point of the masked one
+  std::vector<u64> idx = {0, 2, 3, 5, 9};
+  int first = 1;
+  if (strncmp(argv[1], "holders=", 8) == 0) {
+    idx.clear();
+    for (const char* s = argv[1] + 8; *s;) {
+      char* end;
+      idx.push_back(strtoull(s, &end, 10));
+      if (end == s) return 2;
+      s = *end == ',' ? end + 1 : end;
+    }
+    if (idx.size() < 2) return 2;
+    first = 2;
+  }
+  for (int a = first; a < argc; ++a) {
     u64 p[4];
     if (!parse_hex(argv[a], p)) return 2;
     const WideMont mm = make_wide_mont(p);
     const WideMod m = make_wide_mod(p);
-    rng_state = 0x5EED0000u + (u64)a;
-    // holders 0, 2, 3, 5, 9 with holder 2 masked out; targets 0, the point of holder 3 (valid), the point of holder 2 (masked)
-    const u64 idx[5] = {0, 2, 3, 5, 9};
-    const u32 D = 5, limb_bits = 52, NL = (m.bits + limb_bits - 1) / limb_bits;
-    std::vector<W4> xp, xt = {W4{{0, 0, 0, 0}}, W4{{idx[2] + 1, 0, 0, 0}}, W4{{idx[1] + 1, 0, 0, 0}}};
+    rng_state = 0x5EED0000u + (u64)(a - first + 1);
+    const u32 D = (u32)idx.size(), limb_bits = 52, NL = (m.bits + limb_bits - 1) / limb_bits;
+    std::vector<W4> xp, xt = {W4{{0, 0, 0, 0}}, W4{{idx[D > 2 ? 2 : D - 1] + 1, 0, 0, 0}}, W4{{idx[1] + 1, 0, 0, 0}}};
     std::vector<u32> col;
     for (u32 d = 0; d < D; ++d)
       if (d != 1) {
@@ -224,11 +238,11 @@ int main(int argc, char** argv) {
     for (u32 wi = 0; wi < 4; ++wi) {
       const u32 b = widths[wi], V = wide_signed_digit_count(m.bits, b);
       const std::vector<i64> w = kernel_weights(xp, col, xt, D, NL, V, limb_bits, b, mm);
-      printf("W %d %u", a - 1, b);
+      printf("W %d %u", a - first, b);
       for (i64 v : w) printf(" %" PRId64, v);
       printf("\n");
       // shamir_signed_digits_wide_kernel on eight words of any size
-      printf("S %d %u", a - 1, b);
+      printf("S %d %u", a - first, b);
       std::vector<i64> dg(V);
       for (u32 i = 0; i < 8; ++i) {
         const u64 val[4] = {rnd64(), rnd64(), rnd64(), i < 4 ? rnd64() : 0};
@@ -244,7 +258,7 @@ int main(int argc, char** argv) {
       std::vector<u32> st((size_t)8 * V);
       for (u64& v : wide) v = rnd64();
       for (u32& v : st) v = (u32)(rnd64() & 7);
-      printf("F %d %u", a - 1, b);
+      printf("F %d %u", a - first, b);
       for (u32 i = 0; i < 8; ++i) {
         u32 so = 0;
         print_w4(kernel_fold(wide.data(), st.data(), i, V, ww, b, &so, m, mm));
