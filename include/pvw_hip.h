@@ -42,6 +42,8 @@
  *     pvw_shamir_reconstruct_wide_erasures_device / pvw_shamir_wide_erasure_mask_device (the concurrent calls of these:
  *     tests/test_gpu_shamir_wide_erasures.py), pvw_shamir_evaluate_wide_corrected, pvw_shamir_evaluate_wide_erasures and, on
  *     the calling thread's stream, their _device forms (the concurrent calls of these: tests/test_gpu_shamir_wide_evaluate.py),
+ *     pvw_shamir_evaluate_wide_corrected_at / _erasures_at, pvw_shamir_packed_wide_secrets and, on the calling thread's stream,
+ *     their _device forms (the concurrent calls of these: tests/test_gpu_shamir_wide_points.py),
  *     pvw_decrypt_batch / _checked / _plain, pvw_decrypt_all / _checked / _plain, pvw_ct_sum, pvw_decrypt_sum_checked,
  *     pvw_decrypt_all_sum_checked, pvw_ct_lincomb, pvw_decrypt_lincomb_plain, pvw_decrypt_all_lincomb_plain (the concurrent
  *     calls of these three: tests/test_gpu_ct_lincomb.py), pvw_ct_lincomb_many, pvw_decrypt_all_lincomb_many_plain (the concurrent
@@ -1453,6 +1455,80 @@ PVW_API int32_t pvw_decrypt_all_handover_wide_device(pvw_ctx* ctx, uint32_t part
  * like pvw_ctx_lincomb_fits; no entry point refuses on noise grounds. */
 PVW_API int32_t pvw_ctx_wide_handover_fits(const pvw_ctx* ctx, const uint64_t* plain_modulus, size_t num_valid, uint32_t limb_bits,
                                            uint32_t digit_bits, uint32_t* fits);
+
+/* ---- Wide share repair at field points: pvw_shamir_evaluate_wide_corrected* / _wide_erasures* (8.22) with the point
+ * of every column of `values` given as a field element.  The arguments of the matching index form in its order, except that
+ * `points`, `num_points` stand where it has `targets`, `num_targets`.
+ *   points [num_points][4]: a HOST array of little-endian words in every form (like `points` in 8.24); the point of column j of
+ *   values is points[j], which must be below p.  0, points above 2^64 and points that are some column's indices[c] + 1 are legal;
+ *   duplicates and any order are allowed.
+ *   out, nerr, col_err and err_mask are the decode-only call's, bit for bit.  values [num_secrets][num_points][4] follows 8.22's
+ *   rule with x*_j = points[j]: at a point that equals indices[c] + 1 of a column the decode found right the share read mod p, on
+ *   a wrong or erased column the share that party should hold, anywhere else F_s(x*_j); an undecodable row stores 0.
+ *   With points[j] = targets[j] + 1 the call equals the index call on all five outputs, bit for bit; at points[j] = 0,
+ *   values[s][j] = out[s].  erased == NULL is the corrected _at call bit for bit: behind the checks it is that call.  The three
+ *   forms agree on every input.
+ * PVW_ERR_INVALID_PARAMETERS before any device work, nothing written: what the matching index form refuses, with its texts and
+ * in its order (the device bound r < 4096 included); then NULL points or values, num_points = 0, a point >= p; on the device
+ * num_points >= 2^31, checked before the points are walked.
+ * Under stream capture the rule of 8.22 unchanged, with num_points in the place of num_targets; the points travel as kernel
+ * arguments (64 per launch), so a replay reads no host memory. */
+PVW_API int32_t pvw_shamir_evaluate_wide_corrected_at_host(const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                           size_t count, const uint64_t* shares, size_t num_secrets,
+                                                           size_t secret_stride, size_t point_stride, const uint64_t* points,
+                                                           size_t num_points, uint64_t* values, uint64_t* out, uint32_t* nerr,
+                                                           uint32_t* col_err, uint64_t* err_mask);
+PVW_API int32_t pvw_shamir_evaluate_wide_corrected_at_device(pvw_ctx* ctx, const uint64_t* plain_modulus, uint32_t degree,
+                                                             const uint64_t* indices, size_t count, const uint64_t* d_shares,
+                                                             size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                                             const uint64_t* points, size_t num_points, uint64_t* d_values,
+                                                             uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err,
+                                                             uint64_t* d_err_mask, void* stream);
+PVW_API int32_t pvw_shamir_evaluate_wide_corrected_at(pvw_ctx* ctx, const uint64_t* plain_modulus, uint32_t degree,
+                                                      const uint64_t* indices, size_t count, const uint64_t* shares, size_t num_secrets,
+                                                      size_t secret_stride, size_t point_stride, const uint64_t* points,
+                                                      size_t num_points, uint64_t* values, uint64_t* out, uint32_t* nerr,
+                                                      uint32_t* col_err, uint64_t* err_mask);
+PVW_API int32_t pvw_shamir_evaluate_wide_erasures_at_host(const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                          size_t count, const uint64_t* shares, size_t num_secrets,
+                                                          size_t secret_stride, size_t point_stride, const uint64_t* erased,
+                                                          const uint64_t* points, size_t num_points, uint64_t* values, uint64_t* out,
+                                                          uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask);
+PVW_API int32_t pvw_shamir_evaluate_wide_erasures_at_device(pvw_ctx* ctx, const uint64_t* plain_modulus, uint32_t degree,
+                                                            const uint64_t* indices, size_t count, const uint64_t* d_shares,
+                                                            size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                                            const uint64_t* d_erased, const uint64_t* points, size_t num_points,
+                                                            uint64_t* d_values, uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err,
+                                                            uint64_t* d_err_mask, void* stream);
+PVW_API int32_t pvw_shamir_evaluate_wide_erasures_at(pvw_ctx* ctx, const uint64_t* plain_modulus, uint32_t degree,
+                                                     const uint64_t* indices, size_t count, const uint64_t* shares, size_t num_secrets,
+                                                     size_t secret_stride, size_t point_stride, const uint64_t* erased,
+                                                     const uint64_t* points, size_t num_points, uint64_t* values, uint64_t* out,
+                                                     uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask);
+/* The secrets of packed wide rows (8.23) in one call, with shares wrong or erased.  degree = t, the number of random coefficients,
+ * as in pvw_shamir_shares_packed_wide*: a row is decoded at polynomial degree t + pack - 1 with r = count - t - pack and decodes
+ * while 2 errors + erasures <= r.  secrets [num_rows][pack][4]: secrets[s][m] = F_s(-m), fully reduced; a row reported
+ * PVW_SHAMIR_UNDECODABLE gives `pack` zero elements.  erased may be NULL; nerr, col_err, err_mask as the wide erasures call at
+ * that degree reports them, each optional.  pack = 1 is pvw_shamir_reconstruct_wide_erasures* on secrets and all three reports.
+ * Refused (PVW_ERR_INVALID_PARAMETERS, nothing written): NULL plain_modulus, indices, shares or secrets; pack = 0 or
+ * pack > PVW_WIDE_MAX_PACK; count < degree + pack and everything else the wide erasures call refuses at degree + pack - 1; an
+ * index >= p - pack (the rule of pvw_shamir_reconstruct_packed_wide: no secret point meets a column).
+ * Behind the checks it is the evaluation above with num_points = pack and `secrets` its values.  The _device form makes the
+ * points p - m on the device and takes no host array of points, so it captures like the decode: an earlier call of this kind on
+ * that stream outside capture with the same degree, pack and count, at least as many rows, and a mask if this one has one. */
+PVW_API int32_t pvw_shamir_packed_wide_secrets_host(const uint64_t* plain_modulus, uint32_t pack, uint32_t degree, const uint64_t* indices,
+                                                    size_t count, const uint64_t* shares, size_t num_rows, size_t secret_stride,
+                                                    size_t point_stride, const uint64_t* erased, uint64_t* secrets, uint32_t* nerr,
+                                                    uint32_t* col_err, uint64_t* err_mask);
+PVW_API int32_t pvw_shamir_packed_wide_secrets_device(pvw_ctx* ctx, const uint64_t* plain_modulus, uint32_t pack, uint32_t degree,
+                                                      const uint64_t* indices, size_t count, const uint64_t* d_shares, size_t num_rows,
+                                                      size_t secret_stride, size_t point_stride, const uint64_t* d_erased,
+                                                      uint64_t* d_secrets, uint32_t* d_nerr, uint32_t* d_col_err, uint64_t* d_err_mask,
+                                                      void* stream);
+PVW_API int32_t pvw_shamir_packed_wide_secrets(pvw_ctx* ctx, const uint64_t* plain_modulus, uint32_t pack, uint32_t degree,
+                                               const uint64_t* indices, size_t count, const uint64_t* shares, size_t num_rows,
+                                               size_t secret_stride, size_t point_stride, const uint64_t* erased, uint64_t* secrets,
+                                               uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask);
 
 /* ---- measurement hooks -------------------------------------------------------------
  * With profiling on, every kernel launch of the context is bracketed by HIP events on

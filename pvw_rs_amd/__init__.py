@@ -24,7 +24,8 @@ from .api import (DEC_LOSSY, DEC_NEGATIVE, DEC_WIDE_TRUNCATED, CheckedDecryption
                   shamir_wide_from_limbs_device, shamir_reconstruct_wide_checked,
                   shamir_reconstruct_wide_corrected, shamir_wide_erasure_mask, shamir_evaluate_wide_corrected,
                   shamir_shares_packed_wide, deal_party_shares_packed_wide, shamir_reconstruct_packed_wide,
-                  shamir_reconstruct_packed_wide_corrected, shamir_wide_handover_shape, shamir_wide_signed_digits,
+                  shamir_reconstruct_packed_wide_corrected, shamir_evaluate_wide_corrected_at,
+                  shamir_packed_wide_secrets, shamir_wide_handover_shape, shamir_wide_signed_digits,
                   shamir_wide_handover_weights, shamir_wide_from_digits, shamir_packed_wide_handover_points,
                   decrypt_all_party_handover_wide)
 
@@ -47,6 +48,7 @@ __all__ = [
     "shamir_wide_from_limbs_device", "shamir_reconstruct_wide_checked", "shamir_reconstruct_wide_corrected", "shamir_wide_erasure_mask",
     "shamir_evaluate_wide_corrected",
     "shamir_shares_packed_wide", "deal_party_shares_packed_wide", "shamir_reconstruct_packed_wide", "shamir_reconstruct_packed_wide_corrected",
+    "shamir_evaluate_wide_corrected_at", "shamir_packed_wide_secrets",
     "shamir_wide_handover_shape", "shamir_wide_signed_digits", "shamir_wide_handover_weights", "shamir_wide_from_digits",
     "shamir_packed_wide_handover_points", "decrypt_all_party_handover_wide",
     "device_available", "REPR_POWER", "REPR_NTT",

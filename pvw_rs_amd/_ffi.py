@@ -223,6 +223,26 @@ _SIGNATURES = {
     "pvw_decrypt_all_handover_wide_device": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P, C.c_uint32, C.c_uint32, _P, _P, _P,
                                              C.c_size_t, C.c_uint32, _P, _P, _P, _P],
     "pvw_ctx_wide_handover_fits": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)],
+    # wide share repair at field points: the 8.22 calls with points [T][4], num_points for targets, num_targets; and
+    # the packed secrets (p, pack, degree, indices, count, shares, rows, strides, erased, secrets, nerr, col_err, err_mask)
+    "pvw_shamir_evaluate_wide_corrected_at_host": [_P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, C.c_size_t,
+                                                   _P, _P, _P, _P, _P],
+    "pvw_shamir_evaluate_wide_corrected_at_device": [_P, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P,
+                                                     C.c_size_t, _P, _P, _P, _P, _P, _P],
+    "pvw_shamir_evaluate_wide_corrected_at": [_P, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, C.c_size_t,
+                                              _P, _P, _P, _P, _P],
+    "pvw_shamir_evaluate_wide_erasures_at_host": [_P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P,
+                                                  C.c_size_t, _P, _P, _P, _P, _P],
+    "pvw_shamir_evaluate_wide_erasures_at_device": [_P, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P,
+                                                    C.c_size_t, _P, _P, _P, _P, _P, _P],
+    "pvw_shamir_evaluate_wide_erasures_at": [_P, _P, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P,
+                                             C.c_size_t, _P, _P, _P, _P, _P],
+    "pvw_shamir_packed_wide_secrets_host": [_P, C.c_uint32, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P,
+                                            _P, _P, _P],
+    "pvw_shamir_packed_wide_secrets_device": [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P,
+                                              _P, _P, _P, _P, _P],
+    "pvw_shamir_packed_wide_secrets": [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P,
+                                       _P, _P, _P],
     "pvw_shamir_shares_packed_host": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P],
     "pvw_shamir_shares_packed_device": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P, _P],
     "pvw_shamir_shares_packed": [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P],

@@ -1395,6 +1395,59 @@ def shamir_evaluate_wide_corrected(params: Optional[PvwParameters], indices: Seq
     return [flat[s * T:(s + 1) * T] for s in range(S)], _wide_ints(out), nerr, col_err, err_mask
 
 
+def shamir_evaluate_wide_corrected_at(params: Optional[PvwParameters], indices: Sequence[int], shares, degree: int, plain_modulus: int,
+                                      points: Sequence[int], *, host: bool = False, layout: str = "secret_major",
+                                      erased=None) -> Tuple[List[List[int]], List[int], np.ndarray, np.ndarray, np.ndarray]:
+    """EXTENSION: shamir_evaluate_wide_corrected with the point of column j of the values given as the field element
+    points[j] (an int in [0, plain_modulus), or words [T][4]): 0 -- the value is then the secret --, points above 2^64 and points
+    that are some column's index + 1 are legal; duplicates and any order allowed.  With points[j] = targets[j] + 1 the call equals
+    shamir_evaluate_wide_corrected on all five outputs.  On the device (pvw_shamir_evaluate_wide_corrected_at /
+    _erasures_at); host=True: the plain C++ restatement (no GPU; params may be None).  Returns what
+    shamir_evaluate_wide_corrected returns."""
+    idx, sh, S, count, strides = _wide_share_matrix(indices, shares, layout)
+    if not isinstance(points, np.ndarray) and any(int(x) < 0 or int(x) >> 256 for x in points):
+        raise PvwError(1, "point out of range for plain_modulus")
+    pts = _wide(points)
+    T = len(pts)
+    values = np.zeros((S, T, WIDE_WORDS), dtype=np.uint64)
+    out = np.zeros((S, WIDE_WORDS), dtype=np.uint64)
+    nerr, col_err = np.zeros(S, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
+    err_mask = np.zeros((S, (count + 63) // 64), dtype=np.uint64)
+    head = (_ptr(_wide_modulus(plain_modulus)), int(degree), _ptr(idx), count, _ptr(sh), S, strides[0], strides[1])
+    tail = (_ptr(pts), T, _ptr(values), _ptr(out), _ptr(nerr), _ptr(col_err), _ptr(err_mask))
+    if erased is None:
+        _reconstruct_call(params, "shamir_evaluate_wide_corrected_at", host, head + tail)
+    else:
+        er = _erased_words(erased, S, count, layout)
+        _reconstruct_call(params, "shamir_evaluate_wide_erasures_at", host, head + (_ptr(er),) + tail)
+    flat = _wide_ints(values.reshape(S * T, WIDE_WORDS)) if T else []
+    return [flat[s * T:(s + 1) * T] for s in range(S)], _wide_ints(out), nerr, col_err, err_mask
+
+
+def shamir_packed_wide_secrets(params: Optional[PvwParameters], plain_modulus: int, pack: int, degree: int, indices: Sequence[int],
+                               shares, erased=None, *, host: bool = False, layout: str = "secret_major"):
+    """EXTENSION: the `pack` secrets of each row of a packed wide sharing in ONE call, although shares
+    are wrong or erased: a row is decoded at polynomial degree degree + pack - 1 and read at the points -m; it decodes while
+    2 * errors + erasures <= len(indices) - degree - pack.  Every index must be below plain_modulus - pack.  shares, layout and
+    erased as shamir_reconstruct_wide_corrected.  On the device (pvw_shamir_packed_wide_secrets); host=True: the plain C++
+    restatement (pvw_shamir_packed_wide_secrets_host, no GPU; params may be None).  Returns (secrets [num_rows][pack] as ints,
+    nerr, col_err, err_mask); a row reported SHAMIR_UNDECODABLE gives `pack` zeros.  shamir_reconstruct_packed_wide_corrected
+    computes the same by the older route through t + pack corrected shares and the host."""
+    idx, sh, S, count, strides = _wide_share_matrix(indices, shares, layout)
+    K = int(pack)
+    if K < 0 or K >> 32:
+        raise PvwError(1, "pack must be at least 1")
+    secrets = np.zeros((S, max(K, 1), WIDE_WORDS), dtype=np.uint64)
+    nerr, col_err = np.zeros(S, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
+    err_mask = np.zeros((S, (count + 63) // 64), dtype=np.uint64)
+    er = None if erased is None else _erased_words(erased, S, count, layout)
+    args = (_ptr(_wide_modulus(plain_modulus)), K, int(degree), _ptr(idx), count, _ptr(sh), S, strides[0], strides[1], _ptr(er),
+            _ptr(secrets), _ptr(nerr), _ptr(col_err), _ptr(err_mask))
+    _reconstruct_call(params, "shamir_packed_wide_secrets", host, args)
+    flat = _wide_ints(secrets)
+    return [flat[s * K:(s + 1) * K] for s in range(S)], nerr, col_err, err_mask
+
+
 def _share_matrix(indices: Sequence[int], shares, layout: str):
     """(idx, sh, S, count, strides) of the checked, corrected and evaluate calls: the indices and the share matrix as uint64
     words, and the (secret, point) strides of `layout` in words"""

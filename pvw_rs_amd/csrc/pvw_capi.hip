@@ -2428,6 +2428,16 @@ inline size_t WideField::evaluate_public_words(size_t count, size_t Tg, size_t n
 // tools look the ProfScopes up by, the messages, and the plain-C++ decoder the erasure host form runs on a sub-row.
 struct NarrowCalls;
 struct WideCalls;
+// Where the evaluation points of a call come from: global party indices (the point is index + 1), field elements
+// below p of four HOST words each (wide fields only), or the secret points 0, -1, ..., -(K - 1) of a packed wide sharing, which
+// need no array.  F::target_points(t, j0, tg, ...) puts group j0 .. j0 + tg of them into the workspace.
+struct EvalTargets {
+  enum Kind { kIndices, kWidePoints, kPackedSecrets } kind;
+  const u64* data;
+  static EvalTargets indices(const u64* t) { return EvalTargets{kIndices, t}; }
+  static EvalTargets wide_points(const u64* pts) { return EvalTargets{kWidePoints, pts}; }
+  static EvalTargets packed_secrets() { return EvalTargets{kPackedSecrets, nullptr}; }
+};
 static void berlekamp_welch_host(const Reconstruct<NarrowCalls>& r, const uint64_t* shares, uint64_t* out, uint32_t* nerr, uint32_t* col_err,
                                  uint64_t* err_mask, const uint64_t* targets, size_t num_targets, uint64_t* values);
 static void berlekamp_welch_wide_host(const Reconstruct<WideCalls>& r, const uint64_t* shares, uint64_t* out, uint32_t* nerr,
@@ -2451,6 +2461,9 @@ struct NarrowCalls : NarrowField {
                               *kCorrect = "shamir_correct", *kEvaluate = "shamir_evaluate", *kEvaluateWeights = "shamir_evaluate_weights";
   // the launchers; launch_shamir_points takes no modulus, and the evaluate finish names the locator's values LamT / LamD
   static hipError_t points(const u64* idx, size_t n, u64* x, const KMod&, hipStream_t s) { return launch_shamir_points(idx, n, x, s); }
+  static hipError_t target_points(const EvalTargets& t, size_t j0, size_t tg, u64* x, const KMod& m, hipStream_t s) {
+    return points(t.data + j0, tg, x, m, s);               // the one-word family keeps indices only
+  }
   static constexpr auto weights = &launch_shamir_weights;
   static constexpr auto interpolate = &launch_shamir_interp;
   static constexpr auto correct_weights = &launch_shamir_correct_weights;
@@ -2489,6 +2502,13 @@ struct WideCalls : WideField {
                               *kEvaluateWeights = "shamir_evaluate_wide_weights";
   // the launchers; the evaluate finish names the locator's values PsiT / PsiD
   static constexpr auto points = &launch_shamir_points_wide;
+  static hipError_t target_points(const EvalTargets& t, size_t j0, size_t tg, u64* x, const KMod& m, hipStream_t s) {
+    switch (t.kind) {
+      case EvalTargets::kWidePoints: return launch_shamir_points_from_wide(t.data + j0 * 4, tg, x, m, s);
+      case EvalTargets::kPackedSecrets: return launch_shamir_packed_secret_points_wide((u32)j0, tg, x, m, s);
+      default: return launch_shamir_points_wide(t.data + j0, tg, x, m, s);
+    }
+  }
   static constexpr auto weights = &launch_shamir_weights_wide;
   static constexpr auto interpolate = &launch_shamir_interp_wide;
   static constexpr auto correct_weights = &launch_shamir_correct_weights_wide;
@@ -3061,9 +3081,9 @@ extern "C++" {
 // whose public matrices the block holds; with one group they are built once for all passes.
 template <class F>
 static int32_t evaluate_pass_enqueue(pvw_ctx* c, const Reconstruct<F>& r, const typename F::KMod& m, const EvaluateLayout<F>& lay, u64* ws,
-                                     const u64* d_shares, size_t ns, size_t secret_stride, size_t point_stride, const u64* targets,
-                                     size_t num_targets, u64* d_values, u64* d_out, u32* d_nerr, u32* d_col_err, u64* d_mask,
-                                     size_t* resident, hipStream_t s, const u64* d_erased) {
+                                     const u64* d_shares, size_t ns, size_t secret_stride, size_t point_stride,
+                                     const EvalTargets& targets, size_t num_targets, u64* d_values, u64* d_out, u32* d_nerr, u32* d_col_err,
+                                     u64* d_mask, size_t* resident, hipStream_t s, const u64* d_erased) {
   constexpr size_t EW = F::EW;
   if (!d_out) d_out = ws + lay.outs;
   if (!d_nerr) d_nerr = (u32*)(ws + lay.nerr);
@@ -3080,7 +3100,7 @@ static int32_t evaluate_pass_enqueue(pvw_ctx* c, const Reconstruct<F>& r, const 
     const size_t tg = num_targets - j0 < lay.Tg ? num_targets - j0 : lay.Tg;
     if (*resident != j0) {
       ProfScope ps(c, F::kEvaluateWeights, s);
-      PVW_HIP(F::points(targets + j0, tg, pub, m, s));
+      PVW_HIP(F::target_points(targets, j0, tg, pub, m, s));
       PVW_HIP(F::evaluate_weights(x, aux, pub, r.count, (u32)nk, tg, m, s));
       *resident = j0;
     }
@@ -3112,7 +3132,7 @@ static int32_t evaluate_pass_enqueue(pvw_ctx* c, const Reconstruct<F>& r, const 
 // The device call of 8.13 or 8.22 behind its argument checks; with d_erased (r.erasures) the decode is that of 8.16 or 8.21
 // (corrected_device_call)
 template <class F>
-static int32_t evaluate_device_call(pvw_ctx* c, const Reconstruct<F>& r, const u64* d_shares, const u64* d_erased, const u64* targets,
+static int32_t evaluate_device_call(pvw_ctx* c, const Reconstruct<F>& r, const u64* d_shares, const u64* d_erased, const EvalTargets& targets,
                                     size_t num_targets, u64* d_values, u64* d_out, u32* d_nerr, u32* d_col_err, u64* d_err_mask, void* stream,
                                     const char* unsized) {
   constexpr size_t EW = F::EW;
@@ -3143,7 +3163,7 @@ static int32_t evaluate_device_call(pvw_ctx* c, const Reconstruct<F>& r, const u
 // values of a piece come down as one block.  The staged shares, secrets and values, M, y o M and raw are cleared before the call
 // returns.
 template <class F>
-static int32_t evaluate_host_call(pvw_ctx* c, const Reconstruct<F>& r, const u64* shares, const u64* erased, const u64* targets,
+static int32_t evaluate_host_call(pvw_ctx* c, const Reconstruct<F>& r, const u64* shares, const u64* erased, const EvalTargets& targets,
                                   size_t num_targets, u64* values, u64* out, u32* nerr, u32* col_err, u64* err_mask) {
   PVW_TRY(ensure_device(c));
   constexpr size_t EB = F::EW * 8;                               // bytes per element
@@ -3191,7 +3211,8 @@ int32_t pvw_shamir_evaluate_corrected_device(pvw_ctx* c, uint64_t plain_modulus,
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(evaluate_checks(r, d_shares, targets, num_targets, d_values, true));
-  return evaluate_device_call(c, r, d_shares, nullptr, targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask, stream,
+  return evaluate_device_call(c, r, d_shares, nullptr, EvalTargets::indices(targets), num_targets, d_values,
+                              d_out, d_nerr, d_col_err, d_err_mask, stream,
                               "corrected evaluation under stream capture: run a call with the same degree and count, at least as many "
                               "targets and at least as many secrets on this stream outside capture first (it sizes the workspace)");
 }
@@ -3203,7 +3224,8 @@ int32_t pvw_shamir_evaluate_corrected(pvw_ctx* c, uint64_t plain_modulus, uint32
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(evaluate_checks(r, shares, targets, num_targets, values, true));
-  return evaluate_host_call(c, r, shares, nullptr, targets, num_targets, values, out, nerr, col_err, err_mask);
+  return evaluate_host_call(c, r, shares, nullptr, EvalTargets::indices(targets), num_targets, values,
+                            out, nerr, col_err, err_mask);
 }
 
 // ------------------------------------------------------------------------ reconstruction with erasures
@@ -3334,8 +3356,8 @@ int32_t pvw_shamir_evaluate_erasures_device(pvw_ctx* c, uint64_t plain_modulus, 
   const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
   PVW_TRY(evaluate_checks(r, d_shares, targets, num_targets, d_values, true));
   PVW_TRY(erasures_device_checks(r));
-  return evaluate_device_call(c, r, d_shares, d_erased, targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask, stream,
-                              kErasuresUnsized);
+  return evaluate_device_call(c, r, d_shares, d_erased, EvalTargets::indices(targets), num_targets, d_values,
+                              d_out, d_nerr, d_col_err, d_err_mask, stream, kErasuresUnsized);
 }
 int32_t pvw_shamir_evaluate_erasures(pvw_ctx* c, uint64_t plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
                                      const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
@@ -3348,7 +3370,8 @@ int32_t pvw_shamir_evaluate_erasures(pvw_ctx* c, uint64_t plain_modulus, uint32_
   const Reconstruct<NarrowCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
   PVW_TRY(evaluate_checks(r, shares, targets, num_targets, values, true));
   PVW_TRY(erasures_device_checks(r));
-  return evaluate_host_call(c, r, shares, erased, targets, num_targets, values, out, nerr, col_err, err_mask);
+  return evaluate_host_call(c, r, shares, erased, EvalTargets::indices(targets), num_targets, values,
+                            out, nerr, col_err, err_mask);
 }
 
 // The mask from a decrypt report: bit (s, c) set iff status(s, c) & status_bits or noise(s, c) > noise_bound; either array may be
@@ -4738,8 +4761,9 @@ static inline u64 (&wel(std::vector<u64>& v, size_t i))[4] { return *(u64(*)[4])
 // Berlekamp-Welch as berlekamp_welch_host runs it, over the Montgomery product of pvw_wide.h with every element times R (a zero
 // test and an equality test do not depend on the form; the secret is taken out of it at the end).  Its last step is the
 // contract itself: N / W is compared with the row in every column.  Cubic in count per secret.
-// With targets: values[s][j] = F_s(targets[j] + 1), four plain words, by Horner over the quotient's coefficients, 0 for an
-// undecodable row (pvw_shamir_evaluate_wide_corrected_host); out may then be NULL.
+// With targets, which are FIELD ELEMENTS here, [num_targets][4] plain words below p (the index forms convert targets + 1 into
+// them: wide_index_points): values[s][j] = F_s(targets[j]), four plain words, by Horner over the quotient's
+// coefficients, 0 for an undecodable row (pvw_shamir_evaluate_wide_corrected_host); out may then be NULL.
 static void berlekamp_welch_wide_host(const Reconstruct<WideCalls>& r, const uint64_t* shares, uint64_t* out, uint32_t* nerr, uint32_t* col_err,
                                       uint64_t* err_mask, const uint64_t* targets = nullptr, size_t num_targets = 0,
                                       uint64_t* values = nullptr) {
@@ -4841,7 +4865,7 @@ static void berlekamp_welch_wide_host(const Reconstruct<WideCalls>& r, const uin
     for (size_t j = 0; j < num_targets; ++j) {
       u64 v[4] = {0, 0, 0, 0};
       if (ok) {
-        const u64 xw[4] = {targets[j] + 1, targets[j] + 1 == 0 ? (u64)1 : (u64)0, 0, 0};
+        const u64 xw[4] = {targets[j * 4], targets[j * 4 + 1], targets[j * 4 + 2], targets[j * 4 + 3]};
         u64 xs[4];
         wide_mont_in(xw, mm, xs);
         set(v, wel(N, E + t));
@@ -4974,13 +4998,20 @@ static int32_t evaluate_wide_checks(Reconstruct<WideCalls>& r, const void* share
   return PVW_OK;
 }
 
+// the points targets[j] + 1 <= 2^64 of an index form as field elements (below p: evaluate_wide_checks)
+static std::vector<u64> wide_index_points(const uint64_t* targets, size_t num_targets) {
+  std::vector<u64> pts(num_targets * 4, 0);
+  for (size_t j = 0; j < num_targets; ++j) pts[j * 4] = targets[j] + 1, pts[j * 4 + 1] = targets[j] + 1 == 0;
+  return pts;
+}
 int32_t pvw_shamir_evaluate_wide_corrected_host(const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
                                                 const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
                                                 const uint64_t* targets, size_t num_targets, uint64_t* values, uint64_t* out,
                                                 uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
   Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(evaluate_wide_checks(r, shares, targets, num_targets, values, false));
-  berlekamp_welch_wide_host(r, shares, out, nerr, col_err, err_mask, targets, num_targets, values);
+  const std::vector<u64> pts = wide_index_points(targets, num_targets);
+  berlekamp_welch_wide_host(r, shares, out, nerr, col_err, err_mask, pts.data(), num_targets, values);
   return PVW_OK;
 }
 int32_t pvw_shamir_evaluate_wide_erasures_host(const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
@@ -4992,7 +5023,8 @@ int32_t pvw_shamir_evaluate_wide_erasures_host(const uint64_t* plain_modulus, ui
                                                    targets, num_targets, values, out, nerr, col_err, err_mask);
   Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
   PVW_TRY(evaluate_wide_checks(r, shares, targets, num_targets, values, false));
-  erasures_host(r, shares, erased, out, nerr, col_err, err_mask, targets, num_targets, values);
+  const std::vector<u64> pts = wide_index_points(targets, num_targets);
+  erasures_host(r, shares, erased, out, nerr, col_err, err_mask, pts.data(), num_targets, values);
   return PVW_OK;
 }
 
@@ -5011,8 +5043,8 @@ int32_t pvw_shamir_evaluate_wide_corrected_device(pvw_ctx* c, const uint64_t* pl
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(evaluate_wide_checks(r, d_shares, targets, num_targets, d_values, true));
-  return evaluate_device_call(c, r, d_shares, nullptr, targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask, stream,
-                                   kWideEvaluateUnsized);
+  return evaluate_device_call(c, r, d_shares, nullptr, EvalTargets::indices(targets), num_targets, d_values,
+                              d_out, d_nerr, d_col_err, d_err_mask, stream, kWideEvaluateUnsized);
 }
 int32_t pvw_shamir_evaluate_wide_erasures_device(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
                                                  size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
@@ -5026,8 +5058,8 @@ int32_t pvw_shamir_evaluate_wide_erasures_device(pvw_ctx* c, const uint64_t* pla
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
   PVW_TRY(evaluate_wide_checks(r, d_shares, targets, num_targets, d_values, true));
-  return evaluate_device_call(c, r, d_shares, d_erased, targets, num_targets, d_values, d_out, d_nerr, d_col_err, d_err_mask, stream,
-                                   kWideEvaluateErasuresUnsized);
+  return evaluate_device_call(c, r, d_shares, d_erased, EvalTargets::indices(targets), num_targets, d_values,
+                              d_out, d_nerr, d_col_err, d_err_mask, stream, kWideEvaluateErasuresUnsized);
 }
 
 int32_t pvw_shamir_evaluate_wide_corrected(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
@@ -5037,7 +5069,8 @@ int32_t pvw_shamir_evaluate_wide_corrected(pvw_ctx* c, const uint64_t* plain_mod
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride};
   PVW_TRY(evaluate_wide_checks(r, shares, targets, num_targets, values, true));
-  return evaluate_host_call(c, r, shares, nullptr, targets, num_targets, values, out, nerr, col_err, err_mask);
+  return evaluate_host_call(c, r, shares, nullptr, EvalTargets::indices(targets), num_targets, values,
+                            out, nerr, col_err, err_mask);
 }
 int32_t pvw_shamir_evaluate_wide_erasures(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
                                           const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
@@ -5049,7 +5082,146 @@ int32_t pvw_shamir_evaluate_wide_erasures(pvw_ctx* c, const uint64_t* plain_modu
   if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
   Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, true};
   PVW_TRY(evaluate_wide_checks(r, shares, targets, num_targets, values, true));
-  return evaluate_host_call(c, r, shares, erased, targets, num_targets, values, out, nerr, col_err, err_mask);
+  return evaluate_host_call(c, r, shares, erased, EvalTargets::indices(targets), num_targets, values,
+                            out, nerr, col_err, err_mask);
+}
+
+// ------------------------------------------------------------------------ evaluation at field points below 2^256
+// The calls of 8.22 with the point of column j of `values` given as the field element points[j], a HOST array [num_points][4]
+// below p in every form: 0, points above 2^64 and points that meet a column without being a target's index + 1 are legal.  The
+// packed call evaluates at 0, -1, ..., -(pack - 1), where a packed row of 8.23 keeps its secrets.
+
+// What the matching index form refuses, with its texts and in its order; then the points.  device: num_points is bounded BEFORE
+// the points are walked.
+static int32_t evaluate_wide_at_checks(Reconstruct<WideCalls>& r, const void* shares, const uint64_t* points, size_t num_points,
+                                       const void* values, bool device) {
+  PVW_TRY(reconstruct_wide_checks(r, shares, values));
+  if (device) PVW_TRY(correct_device_checks(r));
+  if (!points) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (num_points == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no points to evaluate at");
+  if (device && num_points >= ((size_t)1 << 31)) return fail(PVW_ERR_INVALID_PARAMETERS, "num_points must be below 2^31 on the device");
+  const u64 pw[4] = {r.p[0], r.p[1], r.p[2], r.p[3]};
+  for (size_t j = 0; j < num_points; ++j) {
+    const u64 x[4] = {points[j * 4], points[j * 4 + 1], points[j * 4 + 2], points[j * 4 + 3]};
+    if (!wide_less(x, pw)) return fail(PVW_ERR_INVALID_PARAMETERS, "point out of range for plain_modulus");
+  }
+  return PVW_OK;
+}
+
+// erased may be NULL in all three: the corrected call, its capture message included
+int32_t pvw_shamir_evaluate_wide_erasures_at_host(const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                                  const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                                  const uint64_t* erased, const uint64_t* points, size_t num_points, uint64_t* values,
+                                                  uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, erased != nullptr};
+  PVW_TRY(evaluate_wide_at_checks(r, shares, points, num_points, values, false));
+  if (erased) erasures_host(r, shares, erased, out, nerr, col_err, err_mask, points, num_points, values);
+  else berlekamp_welch_wide_host(r, shares, out, nerr, col_err, err_mask, points, num_points, values);
+  return PVW_OK;
+}
+int32_t pvw_shamir_evaluate_wide_erasures_at_device(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                    size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
+                                                    size_t point_stride, const uint64_t* d_erased, const uint64_t* points,
+                                                    size_t num_points, uint64_t* d_values, uint64_t* d_out, uint32_t* d_nerr,
+                                                    uint32_t* d_col_err, uint64_t* d_err_mask, void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, d_erased != nullptr};
+  PVW_TRY(evaluate_wide_at_checks(r, d_shares, points, num_points, d_values, true));
+  return evaluate_device_call(c, r, d_shares, d_erased, EvalTargets::wide_points(points), num_points, d_values, d_out, d_nerr, d_col_err,
+                              d_err_mask, stream, d_erased ? kWideEvaluateErasuresUnsized : kWideEvaluateUnsized);
+}
+int32_t pvw_shamir_evaluate_wide_erasures_at(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                             size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
+                                             size_t point_stride, const uint64_t* erased, const uint64_t* points, size_t num_points,
+                                             uint64_t* values, uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_secrets, secret_stride, point_stride, erased != nullptr};
+  PVW_TRY(evaluate_wide_at_checks(r, shares, points, num_points, values, true));
+  return evaluate_host_call(c, r, shares, erased, EvalTargets::wide_points(points), num_points, values, out, nerr, col_err, err_mask);
+}
+int32_t pvw_shamir_evaluate_wide_corrected_at_host(const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices, size_t count,
+                                                   const uint64_t* shares, size_t num_secrets, size_t secret_stride, size_t point_stride,
+                                                   const uint64_t* points, size_t num_points, uint64_t* values, uint64_t* out,
+                                                   uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  return pvw_shamir_evaluate_wide_erasures_at_host(plain_modulus, degree, indices, count, shares, num_secrets, secret_stride, point_stride,
+                                                   nullptr, points, num_points, values, out, nerr, col_err, err_mask);
+}
+int32_t pvw_shamir_evaluate_wide_corrected_at_device(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                                     size_t count, const uint64_t* d_shares, size_t num_secrets, size_t secret_stride,
+                                                     size_t point_stride, const uint64_t* points, size_t num_points, uint64_t* d_values,
+                                                     uint64_t* d_out, uint32_t* d_nerr, uint32_t* d_col_err, uint64_t* d_err_mask,
+                                                     void* stream) {
+  return pvw_shamir_evaluate_wide_erasures_at_device(c, plain_modulus, degree, indices, count, d_shares, num_secrets, secret_stride,
+                                                     point_stride, nullptr, points, num_points, d_values, d_out, d_nerr, d_col_err,
+                                                     d_err_mask, stream);
+}
+int32_t pvw_shamir_evaluate_wide_corrected_at(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t degree, const uint64_t* indices,
+                                              size_t count, const uint64_t* shares, size_t num_secrets, size_t secret_stride,
+                                              size_t point_stride, const uint64_t* points, size_t num_points, uint64_t* values,
+                                              uint64_t* out, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  return pvw_shamir_evaluate_wide_erasures_at(c, plain_modulus, degree, indices, count, shares, num_secrets, secret_stride, point_stride,
+                                              nullptr, points, num_points, values, out, nerr, col_err, err_mask);
+}
+
+// The packed secrets in one call: a row of `degree` random coefficients and `pack` secrets is decoded at polynomial degree
+// degree + pack - 1 and read at the points -m.  Refused in this order: NULL, pack, what the wide erasures call refuses at that
+// degree, an index at or above p - pack (the rule of pvw_shamir_reconstruct_packed_wide: no secret point meets a column).
+static int32_t packed_wide_secrets_checks(Reconstruct<WideCalls>& r, uint32_t pack, uint32_t degree, const void* shares, const void* secrets,
+                                          bool device) {
+  if (!r.p || !r.indices || !shares || !secrets) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (pack == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "pack must be at least 1");
+  if (pack > PVW_WIDE_MAX_PACK) return fail(PVW_ERR_INVALID_PARAMETERS, "pack must be at most PVW_WIDE_MAX_PACK");
+  if (degree > 0xFFFFFFFFu - pack) return fail(PVW_ERR_INVALID_PARAMETERS, "degree + pack must be below 2^32");
+  r.degree = degree + pack - 1;
+  PVW_TRY(reconstruct_wide_checks(r, shares, secrets));
+  const u64 pw[4] = {r.p[0], r.p[1], r.p[2], r.p[3]};
+  for (size_t i = 0; i < r.count; ++i) {
+    u64 top[4] = {r.indices[i] + pack, 0, 0, 0};           // index + pack as a wide integer
+    top[1] = top[0] < r.indices[i];
+    if (!wide_less(top, pw)) return fail(PVW_ERR_INVALID_PARAMETERS, "party index must be below plain_modulus - pack");
+  }
+  if (device) PVW_TRY(correct_device_checks(r));
+  return PVW_OK;
+}
+static const char* const kPackedWideSecretsUnsized =
+    "packed wide secrets under stream capture: run a call with the same mask or none, the same degree, pack and count and at least as "
+    "many rows on this stream outside capture first (it sizes the workspace)";
+
+int32_t pvw_shamir_packed_wide_secrets_host(const uint64_t* plain_modulus, uint32_t pack, uint32_t degree, const uint64_t* indices,
+                                            size_t count, const uint64_t* shares, size_t num_rows, size_t secret_stride,
+                                            size_t point_stride, const uint64_t* erased, uint64_t* secrets, uint32_t* nerr,
+                                            uint32_t* col_err, uint64_t* err_mask) {
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_rows, secret_stride, point_stride, erased != nullptr};
+  PVW_TRY(packed_wide_secrets_checks(r, pack, degree, shares, secrets, false));
+  std::vector<u64> pts((size_t)pack * 4, 0);               // p - m, and 0 for m = 0
+  for (u32 m = 1; m < pack; ++m) {
+    u64 br = m;
+    for (int k = 0; k < 4; ++k) {
+      pts[(size_t)m * 4 + k] = plain_modulus[k] - br;
+      br = plain_modulus[k] < br;
+    }
+  }
+  if (erased) erasures_host(r, shares, erased, (u64*)nullptr, nerr, col_err, err_mask, pts.data(), pack, secrets);
+  else berlekamp_welch_wide_host(r, shares, nullptr, nerr, col_err, err_mask, pts.data(), pack, secrets);
+  return PVW_OK;
+}
+int32_t pvw_shamir_packed_wide_secrets_device(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t pack, uint32_t degree,
+                                              const uint64_t* indices, size_t count, const uint64_t* d_shares, size_t num_rows,
+                                              size_t secret_stride, size_t point_stride, const uint64_t* d_erased, uint64_t* d_secrets,
+                                              uint32_t* d_nerr, uint32_t* d_col_err, uint64_t* d_err_mask, void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_rows, secret_stride, point_stride, d_erased != nullptr};
+  PVW_TRY(packed_wide_secrets_checks(r, pack, degree, d_shares, d_secrets, true));
+  return evaluate_device_call(c, r, d_shares, d_erased, EvalTargets::packed_secrets(), pack, d_secrets, nullptr, d_nerr, d_col_err,
+                              d_err_mask, stream, kPackedWideSecretsUnsized);
+}
+int32_t pvw_shamir_packed_wide_secrets(pvw_ctx* c, const uint64_t* plain_modulus, uint32_t pack, uint32_t degree, const uint64_t* indices,
+                                       size_t count, const uint64_t* shares, size_t num_rows, size_t secret_stride, size_t point_stride,
+                                       const uint64_t* erased, uint64_t* secrets, uint32_t* nerr, uint32_t* col_err, uint64_t* err_mask) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  Reconstruct<WideCalls> r{plain_modulus, degree, indices, count, num_rows, secret_stride, point_stride, erased != nullptr};
+  PVW_TRY(packed_wide_secrets_checks(r, pack, degree, shares, secrets, true));
+  return evaluate_host_call(c, r, shares, erased, EvalTargets::packed_secrets(), pack, secrets, nullptr, nerr, col_err, err_mask);
 }
 
 // ------------------------------------------------------------------------ handover over a prime below 2^256

@@ -555,6 +555,8 @@ hipError_t launch_shamir_signed_digits_wide(const u64* values, size_t count, u32
 // out[i] = sum_v +-wide[i][v][ww] 2^(b v) mod p, status_out[i] = OR_v status[i][v] without PVW_DEC_NEGATIVE
 hipError_t launch_shamir_wide_from_digits(const u64* wide, const u32* status, size_t count, u32 V, u32 ww, u32 b, u64* out, u32* status_out,
                                           const WideMod& m, const WideMont& mm, hipStream_t s);
+// x[i] = (p - (m0 + i)) R mod p for i < count: the secret points -m of a packed wide sharing, m0 + count <= 2^32
+hipError_t launch_shamir_packed_secret_points_wide(u32 m0, size_t count, u64* x, const WideMont& m, hipStream_t s);
 
 // p[0 .. words) = 0, as a kernel launch on s
 hipError_t launch_wipe_words(u64* p, size_t words, hipStream_t s);

@@ -2801,4 +2801,23 @@ hipError_t launch_shamir_wide_from_digits(const u64* wide, const u32* status, si
   return hipSuccess;
 }
 
+// ------------------------------------------------------------------------ the secret points of a packed wide sharing
+// x[i] = (p - (m0 + i)) R mod p, the point -(m0 + i) at which a packed row keeps secret m0 + i (m = 0 gives 0): wide_mont_in of m,
+// then the negation.  One thread per point and no argument array, so a captured call reads no host memory on replay.  At the END
+// of the file, like the kernels of 8.23 and 8.24.
+__global__ __launch_bounds__(256) void shamir_packed_secret_points_wide_kernel(u64* x, u32 m0, u32 n, WideMont m) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const u64 mw[4] = {(u64)m0 + i, 0, 0, 0};
+  u64 mr[4], v[4] = {0, 0, 0, 0};
+  wide_mont_in(mw, m, mr);
+  wide_sub_p(v, mr, m);
+  wide_st(x + (size_t)i * 4, v);
+}
+hipError_t launch_shamir_packed_secret_points_wide(u32 m0, size_t count, u64* x, const WideMont& m, hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  shamir_packed_secret_points_wide_kernel<<<dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s>>>(x, m0, (u32)count, m);
+  return hipGetLastError();
+}
+
 }  // namespace pvw

@@ -989,6 +989,57 @@ inline CorrectedPackedWideSecrets shamir_reconstruct_packed_wide_corrected(const
       std::fill(secrets.begin() + r * pack * PVW_WIDE_WORDS, secrets.begin() + (r + 1) * pack * PVW_WIDE_WORDS, (uint64_t)0);
   return CorrectedPackedWideSecrets{std::move(secrets), std::move(ev.report)};
 }
+// ---- wide share repair at field points ----
+// shamir_evaluate_wide_corrected with the point of column j of values given as the field element points[j] (points holds four
+// little-endian words per point, each point below p): 0, points above 2^64 and points on columns are legal; at the point 0 the
+// value is the secret.  (pvw_shamir_evaluate_wide_erasures_at / _at_host)
+inline EvaluatedWideShares shamir_evaluate_wide_corrected_at(const std::shared_ptr<PvwParameters>& p, const std::vector<uint64_t>& indices,
+                                                             const std::vector<uint64_t>& shares, uint32_t degree, const Wide& plain_modulus,
+                                                             const std::vector<uint64_t>& points, const std::vector<uint64_t>& erased = {},
+                                                             bool party_major = false, bool host = false) {
+  const size_t count = indices.size();
+  if (points.size() % PVW_WIDE_WORDS) throw PvwError(15, "points must hold four words per point");
+  const size_t T = points.size() / PVW_WIDE_WORDS;
+  if (count == 0 || shares.empty() || shares.size() % (count * PVW_WIDE_WORDS)) throw PvwError(15, "shares must hold one element per index and secret");
+  const size_t S = shares.size() / (count * PVW_WIDE_WORDS), ss = party_major ? 1 : count, ps = party_major ? S : 1;
+  const size_t words = (count + 63) / 64;
+  if (!erased.empty() && erased.size() != S * words) throw PvwError(15, "erased must hold ceil(count / 64) words per secret");
+  const uint64_t* er = erased.empty() ? nullptr : erased.data();
+  EvaluatedWideShares r{std::vector<uint64_t>(S * T * PVW_WIDE_WORDS),
+                        CorrectedWideSecrets{std::vector<uint64_t>(S * PVW_WIDE_WORDS), std::vector<uint32_t>(S), std::vector<uint32_t>(count),
+                                             std::vector<uint64_t>(S * words), words}};
+  CorrectedWideSecrets& c = r.report;
+  check(host ? pvw_shamir_evaluate_wide_erasures_at_host(plain_modulus.data(), degree, indices.data(), count, shares.data(), S, ss, ps, er,
+                                                         points.data(), T, r.values.data(), c.secrets.data(), c.nerr.data(),
+                                                         c.col_err.data(), c.err_mask.data())
+             : pvw_shamir_evaluate_wide_erasures_at(p->ctx, plain_modulus.data(), degree, indices.data(), count, shares.data(), S, ss, ps, er,
+                                                    points.data(), T, r.values.data(), c.secrets.data(), c.nerr.data(), c.col_err.data(),
+                                                    c.err_mask.data()));
+  return r;
+}
+// The secrets [num_rows][pack][4] of a packed wide sharing in ONE call, with shares wrong or erased: the rows are decoded at
+// polynomial degree degree + pack - 1 and read at the points -m (pvw_shamir_packed_wide_secrets / _host).  The report's `secrets`
+// stays empty: the secrets of a packed row are the first member.  Every index must be below p - pack.
+inline CorrectedPackedWideSecrets shamir_packed_wide_secrets(const std::shared_ptr<PvwParameters>& p, const Wide& plain_modulus, uint32_t pack,
+                                                             uint32_t degree, const std::vector<uint64_t>& indices,
+                                                             const std::vector<uint64_t>& shares, const std::vector<uint64_t>& erased = {},
+                                                             bool party_major = false, bool host = false) {
+  const size_t count = indices.size();
+  if (count == 0 || shares.empty() || shares.size() % (count * PVW_WIDE_WORDS)) throw PvwError(15, "shares must hold one element per index and row");
+  const size_t S = shares.size() / (count * PVW_WIDE_WORDS), ss = party_major ? 1 : count, ps = party_major ? S : 1;
+  const size_t words = (count + 63) / 64;
+  if (!erased.empty() && erased.size() != S * words) throw PvwError(15, "erased must hold ceil(count / 64) words per row");
+  const uint64_t* er = erased.empty() ? nullptr : erased.data();
+  CorrectedPackedWideSecrets r{std::vector<uint64_t>(S * (pack ? pack : 1) * PVW_WIDE_WORDS),
+                               CorrectedWideSecrets{{}, std::vector<uint32_t>(S), std::vector<uint32_t>(count),
+                                                    std::vector<uint64_t>(S * words), words}};
+  CorrectedWideSecrets& c = r.report;
+  check(host ? pvw_shamir_packed_wide_secrets_host(plain_modulus.data(), pack, degree, indices.data(), count, shares.data(), S, ss, ps, er,
+                                                   r.secrets.data(), c.nerr.data(), c.col_err.data(), c.err_mask.data())
+             : pvw_shamir_packed_wide_secrets(p->ctx, plain_modulus.data(), pack, degree, indices.data(), count, shares.data(), S, ss, ps, er,
+                                              r.secrets.data(), c.nerr.data(), c.col_err.data(), c.err_mask.data()));
+  return r;
+}
 // The mask of wide shares from a per-limb decrypt report on the host (pvw_shamir_wide_erasure_mask_host): status / noise
 // [num_secrets][count * num_limbs], or with party_major [count][num_secrets * num_limbs] (the [party][dealer NL + w] report of the
 // decrypt-all calls); either may be empty, not both.  Share (s, c) is erased iff one of its limbs has status & status_bits or

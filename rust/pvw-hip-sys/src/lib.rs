@@ -241,6 +241,15 @@ extern "C" {
     pub fn pvw_shamir_evaluate_wide_erasures_host(plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, erased: *const u64, targets: *const u64, num_targets: usize, values: *mut u64, out: *mut u64, nerr: *mut u32, col_err: *mut u32, err_mask: *mut u64) -> i32;
     pub fn pvw_shamir_evaluate_wide_erasures_device(ctx: *mut PvwCtx, plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, d_shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, d_erased: *const u64, targets: *const u64, num_targets: usize, d_values: *mut u64, d_out: *mut u64, d_nerr: *mut u32, d_col_err: *mut u32, d_err_mask: *mut u64, stream: *mut c_void) -> i32;
     pub fn pvw_shamir_evaluate_wide_erasures(ctx: *mut PvwCtx, plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, erased: *const u64, targets: *const u64, num_targets: usize, values: *mut u64, out: *mut u64, nerr: *mut u32, col_err: *mut u32, err_mask: *mut u64) -> i32;
+    pub fn pvw_shamir_evaluate_wide_corrected_at_host(plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, points: *const u64, num_points: usize, values: *mut u64, out: *mut u64, nerr: *mut u32, col_err: *mut u32, err_mask: *mut u64) -> i32;
+    pub fn pvw_shamir_evaluate_wide_corrected_at_device(ctx: *mut PvwCtx, plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, d_shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, points: *const u64, num_points: usize, d_values: *mut u64, d_out: *mut u64, d_nerr: *mut u32, d_col_err: *mut u32, d_err_mask: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_evaluate_wide_corrected_at(ctx: *mut PvwCtx, plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, points: *const u64, num_points: usize, values: *mut u64, out: *mut u64, nerr: *mut u32, col_err: *mut u32, err_mask: *mut u64) -> i32;
+    pub fn pvw_shamir_evaluate_wide_erasures_at_host(plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, erased: *const u64, points: *const u64, num_points: usize, values: *mut u64, out: *mut u64, nerr: *mut u32, col_err: *mut u32, err_mask: *mut u64) -> i32;
+    pub fn pvw_shamir_evaluate_wide_erasures_at_device(ctx: *mut PvwCtx, plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, d_shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, d_erased: *const u64, points: *const u64, num_points: usize, d_values: *mut u64, d_out: *mut u64, d_nerr: *mut u32, d_col_err: *mut u32, d_err_mask: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_evaluate_wide_erasures_at(ctx: *mut PvwCtx, plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, erased: *const u64, points: *const u64, num_points: usize, values: *mut u64, out: *mut u64, nerr: *mut u32, col_err: *mut u32, err_mask: *mut u64) -> i32;
+    pub fn pvw_shamir_packed_wide_secrets_host(plain_modulus: *const u64, pack: u32, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_rows: usize, secret_stride: usize, point_stride: usize, erased: *const u64, secrets: *mut u64, nerr: *mut u32, col_err: *mut u32, err_mask: *mut u64) -> i32;
+    pub fn pvw_shamir_packed_wide_secrets_device(ctx: *mut PvwCtx, plain_modulus: *const u64, pack: u32, degree: u32, indices: *const u64, count: usize, d_shares: *const u64, num_rows: usize, secret_stride: usize, point_stride: usize, d_erased: *const u64, d_secrets: *mut u64, d_nerr: *mut u32, d_col_err: *mut u32, d_err_mask: *mut u64, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_packed_wide_secrets(ctx: *mut PvwCtx, plain_modulus: *const u64, pack: u32, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_rows: usize, secret_stride: usize, point_stride: usize, erased: *const u64, secrets: *mut u64, nerr: *mut u32, col_err: *mut u32, err_mask: *mut u64) -> i32;
     pub fn pvw_shamir_wide_erasure_mask_host(status: *mut u32, noise: *const u64, status_bits: u32, noise_bound: u64, count: usize, num_secrets: usize, secret_stride: usize, point_stride: usize, num_limbs: u32, limb_stride: usize, mask_out: *mut u64) -> i32;
     pub fn pvw_shamir_wide_erasure_mask_device(ctx: *mut PvwCtx, d_status: *mut u32, d_noise: *const u64, status_bits: u32, noise_bound: u64, count: usize, num_secrets: usize, secret_stride: usize, point_stride: usize, num_limbs: u32, limb_stride: usize, d_mask_out: *mut u64, stream: *mut c_void) -> i32;
     pub fn pvw_shamir_erasure_mask_host(status: *mut u32, noise: *const u64, status_bits: u32, noise_bound: u64, count: usize, num_secrets: usize, secret_stride: usize, point_stride: usize, mask_out: *mut u64) -> i32;

@@ -897,6 +897,59 @@ pub fn shamir_reconstruct_packed_wide_corrected(params: &Arc<PvwParameters>, pla
     Ok((secrets, report))
 }
 
+/// EXTENSION: `shamir_evaluate_wide_corrected` with the point of column `j` of the values given as the field
+/// element `points[j]`, which must be below p: 0 (the value is then the secret), points above 2^64 and points on columns are
+/// legal (`pvw_shamir_evaluate_wide_erasures_at`; an empty `erased` is the corrected call).
+pub fn shamir_evaluate_wide_corrected_at(params: &Arc<PvwParameters>, indices: &[u64], shares: &[Wide], degree: u32, plain_modulus: &Wide,
+                                         erased: &[u64], points: &[Wide], party_major: bool) -> Result<(Vec<Wide>, CorrectedWideSecrets)> {
+    if indices.is_empty() || shares.is_empty() || shares.len() % indices.len() != 0 {
+        return Err(PvwError::InvalidParameters("shares must hold one element per index and secret".into()));
+    }
+    let (count, num) = (indices.len(), shares.len() / indices.len());
+    let (ss, ps) = if party_major { (1, num) } else { (count, 1) };
+    let words = (count + 63) / 64;
+    if !erased.is_empty() && erased.len() != num * words {
+        return Err(PvwError::InvalidParameters("erased must hold ceil(count / 64) words per secret".into()));
+    }
+    let er = if erased.is_empty() { std::ptr::null() } else { erased.as_ptr() };
+    let mut values = vec![[0u64; 4]; num * points.len()];
+    let mut r = CorrectedWideSecrets { secrets: vec![[0u64; 4]; num], nerr: vec![0u32; num], col_err: vec![0u32; count],
+                                       err_mask: vec![0u64; num * words], words };
+    check(unsafe {
+        sys::pvw_shamir_evaluate_wide_erasures_at(params.hip.raw(), plain_modulus.as_ptr(), degree, indices.as_ptr(), count,
+                                                  shares.as_ptr() as *const u64, num, ss, ps, er, points.as_ptr() as *const u64,
+                                                  points.len(), values.as_mut_ptr() as *mut u64, r.secrets.as_mut_ptr() as *mut u64,
+                                                  r.nerr.as_mut_ptr(), r.col_err.as_mut_ptr(), r.err_mask.as_mut_ptr())
+    })?;
+    Ok((values, r))
+}
+
+/// EXTENSION: the secrets `[num_rows][pack]` of a packed wide sharing in ONE device call, with shares wrong or
+/// erased: the rows are decoded at polynomial degree `degree + pack - 1` and read at the points `-m`
+/// (`pvw_shamir_packed_wide_secrets`).  Every index must be below `p - pack`.  The report's `secrets` stays empty.
+pub fn shamir_packed_wide_secrets(params: &Arc<PvwParameters>, plain_modulus: &Wide, pack: u32, degree: u32, indices: &[u64],
+                                  shares: &[Wide], erased: &[u64], party_major: bool) -> Result<(Vec<Wide>, CorrectedWideSecrets)> {
+    if indices.is_empty() || shares.is_empty() || shares.len() % indices.len() != 0 {
+        return Err(PvwError::InvalidParameters("shares must hold one element per index and row".into()));
+    }
+    let (count, num) = (indices.len(), shares.len() / indices.len());
+    let (ss, ps) = if party_major { (1, num) } else { (count, 1) };
+    let words = (count + 63) / 64;
+    if !erased.is_empty() && erased.len() != num * words {
+        return Err(PvwError::InvalidParameters("erased must hold ceil(count / 64) words per row".into()));
+    }
+    let er = if erased.is_empty() { std::ptr::null() } else { erased.as_ptr() };
+    let mut secrets = vec![[0u64; 4]; num * pack.max(1) as usize];
+    let mut r = CorrectedWideSecrets { secrets: Vec::new(), nerr: vec![0u32; num], col_err: vec![0u32; count],
+                                       err_mask: vec![0u64; num * words], words };
+    check(unsafe {
+        sys::pvw_shamir_packed_wide_secrets(params.hip.raw(), plain_modulus.as_ptr(), pack, degree, indices.as_ptr(), count,
+                                            shares.as_ptr() as *const u64, num, ss, ps, er, secrets.as_mut_ptr() as *mut u64,
+                                            r.nerr.as_mut_ptr(), r.col_err.as_mut_ptr(), r.err_mask.as_mut_ptr())
+    })?;
+    Ok((secrets, r))
+}
+
 /// EXTENSION: the erasure mask of wide shares from a per-limb decrypt report, on the host
 /// (`pvw_shamir_wide_erasure_mask_host`).  `status` and `noise` are `[num_secrets][count * num_limbs]`, or with `party_major`
 /// `[count][num_secrets * num_limbs]` (the `[party][dealer * NL + w]` report of the decrypt-all calls, every dealer a secret);

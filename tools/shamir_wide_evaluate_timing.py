@@ -12,7 +12,14 @@ Each case is interleaved round by round with the decode-only call on the same in
 Every run is checked against the dealt shares at the targets and the dealt secrets.  Times are whole calls between two HIP
 events, --steps calls back to back, after warm-up.  Without --case every case runs in a child process of its own under a time
 limit of --limit seconds, and the first failure ends the run.  One JSON line per case: median, minimum and maximum ms over the
-rounds, the rounds themselves, and the secrets per pass of either call."""
+rounds, the rounds themselves, and the secrets per pass of either call.
+    python tools/shamir_wide_evaluate_timing.py --points [--steps 2] [--rounds 5]
+The packed secrets in one call against the route the library offered before it, in ONE process: 64 packed rows
+(pvw_shamir_shares_packed_wide_device), count = 4096, polynomial degree 2047 (t = 2048 - K), K in {16, 64}; inputs consistent,
+1024 columns overwritten, 1024 columns erased.  One side is pvw_shamir_packed_wide_secrets_device; the other is
+pvw_shamir_evaluate_wide_corrected_device / _erasures_device at the first t + K columns, the copy of those corrected shares to the
+host and pvw_shamir_reconstruct_packed_wide on them, all between the two HIP events.  The sides alternate round by round; both
+are checked against the dealt secrets.  One JSON line per case."""
 import ctypes as C
 import json
 import os
@@ -144,8 +151,113 @@ def run_case(case, steps, rounds):
     return 0 if ok_new and ok_old else 1
 
 
+def run_points(steps, rounds):
+    import torch
+
+    import pvw_rs_amd as P
+    from pvw_rs_amd import api
+
+    dev = torch.device("cuda", 0)
+    N, n, S = 8192, 4096, 64
+    p = P.PvwParametersBuilder().set_parties(N).set_dimension(2).set_l(8).set_moduli(MODULI).build()
+    lib = p._lib
+    s = torch.cuda.Stream(device=dev)
+    sp = C.c_void_p(s.cuda_stream)
+    ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+    nptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    pm = api._wide_modulus(SECP_N)
+    ix = np.arange(n, dtype=np.uint64)
+    W = (n + 63) // 64
+    failed = 0
+    for K in (16, 64):
+        t = 2048 - K                                            # polynomial degree t + K - 1 = 2047, r = 2048
+        rng = np.random.default_rng(K)
+        secrets = rng.integers(0, 1 << 63, size=(S, K, 4), dtype=np.uint64)
+        d_se = torch.from_numpy(secrets.view(np.int64)).to(dev)
+        seeds = rng.integers(0, 256, size=S * 32, dtype=np.uint8)
+        dealt = torch.empty((S, N, 4), dtype=torch.int64, device=dev)
+        api._check(lib.pvw_shamir_shares_packed_wide_device(p._h, ptr(d_se), S, K, t, nptr(pm), nptr(seeds), None, ptr(dealt), sp), lib)
+        s.synchronize()
+        order = rng.permutation(n)
+        basis = np.ascontiguousarray(ix[:t + K])
+        for inp in ("consistent", "1024_overwritten", "1024_erased"):
+            n_erased, n_over, masked = INPUTS[inp]
+            cols = order[:n_erased + n_over]
+            shares = dealt[:, :n].clone()
+            if len(cols):
+                junk = rng.integers(0, 1 << 63, size=(S, len(cols), 4), dtype=np.int64)
+                shares[:, torch.from_numpy(np.sort(cols)).to(dev)] = torch.from_numpy(junk).to(dev)
+            er = np.zeros((S, W), dtype=np.uint64)
+            for c in order[:n_erased]:
+                er[:, c // 64] |= np.uint64(1 << (int(c) % 64))
+            d_er = torch.from_numpy(er.view(np.int64)).to(dev) if masked else None
+            sec = torch.empty((S, K, 4), dtype=torch.int64, device=dev)
+            val = torch.empty((S, t + K, 4), dtype=torch.int64, device=dev)
+            nerr = torch.empty(S, dtype=torch.int32, device=dev)
+            col = torch.empty(n, dtype=torch.int32, device=dev)
+            mask = torch.empty((S, W), dtype=torch.int64, device=dev)
+            h_val_t = torch.zeros((S, t + K, 4), dtype=torch.int64).pin_memory()
+            h_val = h_val_t.numpy().view(np.uint64)
+            h_sec = np.zeros((S, K, 4), dtype=np.uint64)
+            report = (ptr(nerr), ptr(col), ptr(mask), sp)
+
+            def new():
+                api._check(lib.pvw_shamir_packed_wide_secrets_device(p._h, nptr(pm), K, t, nptr(ix), n, ptr(shares), S, n, 1, ptr(d_er),
+                                                                     ptr(sec), *report), lib)
+
+            def old():
+                head = (p._h, nptr(pm), t + K - 1, nptr(ix), n, ptr(shares), S, n, 1)
+                tail = (nptr(basis), t + K, ptr(val), None, *report)
+                if masked:
+                    api._check(lib.pvw_shamir_evaluate_wide_erasures_device(*head, ptr(d_er), *tail), lib)
+                else:
+                    api._check(lib.pvw_shamir_evaluate_wide_corrected_device(*head, *tail), lib)
+                with torch.cuda.stream(s):
+                    h_val_t.copy_(val, non_blocking=True)
+                s.synchronize()
+                api._check(lib.pvw_shamir_reconstruct_packed_wide(nptr(pm), K, nptr(basis), nptr(h_val), t + K, S, nptr(h_sec)), lib)
+
+            def timed(fn, k):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(s)
+                for _ in range(k):
+                    fn()
+                b.record(s)
+                torch.cuda.synchronize()
+                return a.elapsed_time(b) / k
+
+            def errs_ok():
+                return bool((nerr.cpu().numpy().view(np.uint32) == n_over).all())
+
+            timed(new, 1)                                       # warm-up (sizes the workspace)
+            ok_new = errs_ok() and np.array_equal(sec.cpu().numpy().view(np.uint64), secrets)
+            timed(old, 1)
+            ok_old = errs_ok() and np.array_equal(h_sec, secrets)
+            t_new, t_old = [], []
+            for _ in range(rounds):                             # interleaved round by round
+                t_new.append(timed(new, steps))
+                t_old.append(timed(old, steps))
+            sec.zero_()
+            h_sec[:] = 0
+            timed(new, 1)
+            timed(old, 1)
+            ok_new = ok_new and np.array_equal(sec.cpu().numpy().view(np.uint64), secrets)
+            ok_old = ok_old and np.array_equal(h_sec, secrets)
+            nk = 2049 if masked else 1025
+            print(json.dumps(dict(host=socket.gethostname(), steps=steps, rounds=rounds, S=S, count=n, pack=K, degree=t, r=2048,
+                                  what="packed_wide_secrets", input=inp, erased=n_erased, overwritten=n_over, correct=ok_new,
+                                  old_route_correct=ok_old, secrets_per_pass_new=passes(S, n, 2048, nk, group(n, nk, K)),
+                                  secrets_per_pass_old=passes(S, n, 2048, nk, group(n, nk, t + K)), ms_packed_call=stats(t_new),
+                                  ms_old_route=stats(t_old), ratio_of_medians=round(float(np.median(t_old) / np.median(t_new)), 3))),
+                  flush=True)
+            failed += not (ok_new and ok_old)
+    return 1 if failed else 0
+
+
 def main():
     steps, rounds, limit = int(arg("--steps", 2)), int(arg("--rounds", 5)), int(arg("--limit", 240))
+    if "--points" in sys.argv:
+        sys.exit(run_points(steps, rounds))
     if "--case" in sys.argv:
         sys.exit(run_case(arg("--case", None), steps, rounds))
     for case in CASES:                                          # a child each, under its own time limit; the first failure ends the run
