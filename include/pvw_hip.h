@@ -707,6 +707,67 @@ PVW_API int32_t pvw_decrypt_all_lincomb_many_plain(pvw_ctx* ctx, uint32_t party_
                                                    uint64_t* noise, uint32_t* status, uint32_t* counts, uint64_t plain_modulus,
                                                    uint32_t wide_words, uint64_t* wide);
 
+/* ---- the one-word handover in one call, its weights from a mask that may be made on the device -----------------
+ * weights [num_targets][num_holders], row-major: row j = the Lagrange weights AT the point (targets[j] + 1) mod p (the target rule of
+ * pvw_shamir_lagrange_weights_at: p - 1 is the point 0, p - 1 - m the point -m) over the points indices[d] + 1 of the holders with
+ * valid[d] != 0 (valid == NULL: all of them), centred in (-p/2, p/2]; the column of a holder that is not valid is 0.  Row j is, bit
+ * for bit, pvw_shamir_lagrange_weights_at over the compacted valid indices, scattered back to their columns.  targets == NULL is the
+ * single point 0 and num_targets must then be 1.  A target on a VALID holder's point gives that holder's unit vector; a target on a
+ * holder that is not valid is an ordinary point.  *count (may be NULL) = the number of valid holders; with none, every weight is 0
+ * and the count is 0, which is no error (as pvw_ct_lincomb_device with an all-zero mask).
+ * Refused with PVW_ERR_INVALID_PARAMETERS before any device work, nothing written, and the same by both forms: NULL indices or
+ * weights; num_holders = 0; num_targets = 0; what pvw_shamir_lagrange_weights refuses (p not prime or >= 2^62, a duplicate index, an
+ * index >= p - 1) about ALL num_holders indices, masked ones included -- the device form cannot know the mask at call time, and the
+ * host form follows it; a target >= p; on the device num_holders >= 2^32 or num_targets >= 2^31. */
+PVW_API int32_t pvw_shamir_handover_weights_host(uint64_t plain_modulus, const uint64_t* indices, const uint8_t* valid, size_t num_holders,
+                                                 const uint64_t* targets, size_t num_targets, int64_t* weights, uint32_t* count);
+/* indices and targets are HOST arrays, consumed at call time (they travel as kernel arguments); d_valid, d_weights and d_count are
+ * DEVICE pointers, and the mask is read when the kernels run: a captured call replays with the mask of the moment.  Asynchronous on
+ * `stream`; allocates nothing once the stream's workspace holds the call's public matrices, which it sizes by (num_holders,
+ * num_targets).  Under stream capture that block must be there already, from an earlier call on that stream OUTSIDE capture with at
+ * least as many holders and targets; otherwise PVW_ERR_INVALID_PARAMETERS with nothing enqueued. */
+PVW_API int32_t pvw_shamir_handover_weights_device(pvw_ctx* ctx, uint64_t plain_modulus, const uint64_t* indices, const uint8_t* d_valid,
+                                                   size_t num_holders, const uint64_t* targets, size_t num_targets, int64_t* d_weights,
+                                                   uint32_t* d_count, void* stream);
+/* The holder mask from a report: valid_out[c] = 1 iff for no row r the element at r * row_stride + c * col_stride has
+ * status & status_bits != 0 or noise > noise_bound, else 0; *num_valid (may be NULL) = the number of ones.  Either array may be NULL,
+ * not both; both are only read.  The argument and refusal rules of pvw_shamir_erasure_mask_* (count, rows, strides of 0).  With
+ * rows = 1, strides (count, 1), status = the col_err of a corrected reconstruction and status_bits = 0xFFFFFFFF: the columns without
+ * a wrong share.  With strides (D, 1): the [party][dealer] report of pvw_decrypt_all_*_checked / _plain in place.  The device form
+ * takes device pointers throughout, is asynchronous on `stream`, and on the device count and rows are below 2^31; under stream
+ * capture the stream's workspace must exist (any earlier call of this section on that stream). */
+PVW_API int32_t pvw_shamir_valid_mask_host(uint32_t* status, const uint64_t* noise, uint32_t status_bits, uint64_t noise_bound, size_t count,
+                                           size_t rows, size_t row_stride, size_t col_stride, uint8_t* valid_out, uint32_t* num_valid);
+PVW_API int32_t pvw_shamir_valid_mask_device(pvw_ctx* ctx, uint32_t* d_status, const uint64_t* d_noise, uint32_t status_bits,
+                                             uint64_t noise_bound, size_t count, size_t rows, size_t row_stride, size_t col_stride,
+                                             uint8_t* d_valid_out, uint32_t* d_num_valid, void* stream);
+/* Every new party's new share in one call: pvw_decrypt_all_lincomb_many_plain[_device] with (indices, targets, num_targets) in place
+ * of (weights, num_combos) and one `count` word, the number of valid holders, in place of `counts`.  plain_modulus is the field of
+ * the weights (prime, below 2^62) AND the decode modulus.  out / noise / status [P][T], wide [P][T][wide_words].  Behind the checks:
+ * the weights above, the many-combinations call itself with valid = NULL there (a masked holder's weights are 0, so its ciphertext
+ * is never addressed), and that call's report as it is.  Results are bit for bit pvw_shamir_handover_weights_host ->
+ * pvw_decrypt_all_lincomb_many_plain with the same arguments.  Refused: what the weights refuse, then what that call refuses.
+ * Nothing refuses on noise grounds: pvw_ctx_lincomb_fits stays the advisory test.  Keys are staged, marked and wiped by the
+ * many-combinations call.
+ * Device form: d_valid is a DEVICE pointer (NULL: all valid), indices and targets HOST arrays consumed at call time; asynchronous on
+ * `stream`.  With no valid holder: zeros and *d_count = 0.  Under stream capture every workspace block (the weights' public
+ * matrices, the weight rows, the many-combinations scratch) must be sized by an earlier call on that stream OUTSIDE capture with the
+ * same party range and at least as many holders and targets; otherwise PVW_ERR_INVALID_PARAMETERS with nothing enqueued.  A replay
+ * reads no host memory and follows the mask of the moment.
+ * Host-buffer form (synchronous): valid is a HOST array, only valid holders are staged (in pieces, as the many-combinations call
+ * stages them); the weights run through the same kernels on a pooled workspace, so the call joins the concurrency promise.  With
+ * no valid holder: PVW_ERR_INSUFFICIENT_DATA. */
+PVW_API int32_t pvw_decrypt_all_handover_device(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* d_sk,
+                                                const uint64_t* d_c1s, const uint64_t* d_c2s, size_t num_holders, const uint8_t* d_valid,
+                                                const uint64_t* indices, const uint64_t* targets, size_t num_targets, uint32_t in_repr,
+                                                uint64_t* d_out, uint64_t* d_noise, uint32_t* d_status, uint32_t* d_count,
+                                                uint64_t plain_modulus, uint32_t wide_words, uint64_t* d_wide, void* stream);
+PVW_API int32_t pvw_decrypt_all_handover(pvw_ctx* ctx, uint32_t party_lo, uint32_t party_hi, const int64_t* sk, const uint64_t* c1s,
+                                         const uint64_t* c2s, size_t num_holders, const uint8_t* valid, const uint64_t* indices,
+                                         const uint64_t* targets, size_t num_targets, uint32_t in_repr, uint64_t* out_u64,
+                                         uint64_t* noise, uint32_t* status, uint32_t* count, uint64_t plain_modulus,
+                                         uint32_t wide_words, uint64_t* wide);
+
 /* ---- Shamir shares: from secrets to ciphertexts in one call, and back --------------------------------------
  * The dealing end of the protocol the reference's examples sketch (examples/pvw.rs:95-131 fill the share matrix with arbitrary
  * numbers; the reference has no sharing code, so this contract is the library's own).  All arithmetic in Z_p, p = plain_modulus:

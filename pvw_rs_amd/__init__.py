@@ -27,7 +27,7 @@ from .api import (DEC_LOSSY, DEC_NEGATIVE, DEC_WIDE_TRUNCATED, CheckedDecryption
                   shamir_reconstruct_packed_wide_corrected, shamir_evaluate_wide_corrected_at,
                   shamir_packed_wide_secrets, shamir_wide_handover_shape, shamir_wide_signed_digits,
                   shamir_wide_handover_weights, shamir_wide_from_digits, shamir_packed_wide_handover_points,
-                  decrypt_all_party_handover_wide)
+                  decrypt_all_party_handover_wide, shamir_handover_weights, shamir_valid_mask, decrypt_all_party_handover)
 
 __all__ = [
     "PvwParametersBuilder", "PvwParameters", "PvwCrs", "SecretKey", "DeviceSecretKey", "DeviceRandomness", "Party", "GlobalPublicKey",
@@ -51,5 +51,6 @@ __all__ = [
     "shamir_evaluate_wide_corrected_at", "shamir_packed_wide_secrets",
     "shamir_wide_handover_shape", "shamir_wide_signed_digits", "shamir_wide_handover_weights", "shamir_wide_from_digits",
     "shamir_packed_wide_handover_points", "decrypt_all_party_handover_wide",
+    "shamir_handover_weights", "shamir_valid_mask", "decrypt_all_party_handover",
     "device_available", "REPR_POWER", "REPR_NTT",
 ]

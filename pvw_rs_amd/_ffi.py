@@ -130,6 +130,15 @@ _SIGNATURES = {
     "pvw_ct_lincomb_many": [_P, _P, _P, C.c_size_t, _P, _P, C.c_size_t, C.c_uint32, C.c_uint32, _P, _P, _P],
     "pvw_decrypt_all_lincomb_many_plain_device": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P],
     "pvw_decrypt_all_lincomb_many_plain": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P],
+    # one-word handover from a mask: the weights [T][D], the mask from a report, the handover in one call
+    "pvw_shamir_handover_weights_host": [C.c_uint64, _P, _P, C.c_size_t, _P, C.c_size_t, _P, _P],
+    "pvw_shamir_handover_weights_device": [_P, C.c_uint64, _P, _P, C.c_size_t, _P, C.c_size_t, _P, _P, _P],
+    "pvw_shamir_valid_mask_host": [_P, _P, C.c_uint32, C.c_uint64, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P],
+    "pvw_shamir_valid_mask_device": [_P, _P, _P, C.c_uint32, C.c_uint64, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P],
+    "pvw_decrypt_all_handover_device": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, _P,
+                                        C.c_uint64, C.c_uint32, _P, _P],
+    "pvw_decrypt_all_handover": [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P, _P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, _P,
+                                 C.c_uint64, C.c_uint32, _P],
     # plain-modulus decode: the checked call plus (plain_modulus, wide_words, wide)
     "pvw_decode_plain": [_P, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.c_uint32, _P],
     "pvw_decode_plain_device": [_P, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P],

@@ -2313,6 +2313,162 @@ def decrypt_all_party_handover_wide(cts: Sequence[Sequence[PvwCiphertext]], part
     return [vals[j * T:(j + 1) * T] for j in range(NP)], status
 
 
+# ---- the one-word handover from a mask that may be made on the device ----
+def _holder_mask(valid, D: int):
+    """(host uint8 [D] or None, device tensor or None): a device tensor (uint8 / bool, contiguous, [D]) is used in place"""
+    if valid is None:
+        return None, None
+    if hasattr(valid, "data_ptr"):
+        if valid.dim() != 1 or valid.shape[0] != D or valid.element_size() != 1 or not valid.is_contiguous():
+            raise PvwError(15, f"valid: expected a contiguous device tensor of {D} bytes")
+        return None, valid
+    v = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+    if v.shape != (D,):
+        raise PvwError(15, f"valid: expected {D} flags, got {v.size}")
+    return v, None
+
+
+def shamir_handover_weights(params: Optional[PvwParameters], indices: Sequence[int], plain_modulus: int, valid=None, targets=None, *,
+                            host: bool = False, stream=None):
+    """EXTENSION: the int64 weight rows [T][D] of a one-word handover: row j = the Lagrange weights AT the point
+    (targets[j] + 1) mod p (None: the single point 0; the target rule of shamir_lagrange_weights_at) over the points indices[d] + 1
+    of the holders with valid[d] != 0, centred; a masked holder's column is 0.  Returns (weights, count of valid holders).
+    host=True: pvw_shamir_handover_weights_host (no GPU).  Otherwise pvw_shamir_handover_weights_device: `valid` as a device tensor
+    (uint8 [D]) is read in place when the kernels run, asynchronously on `stream`, and (weights, count) come back as device tensors."""
+    idx = _words(indices)
+    D = len(idx)
+    v, dv = _holder_mask(valid, D)
+    tg = None if targets is None else _words(targets)
+    T = 1 if tg is None else len(tg)
+    count = C.c_uint32()
+    if host:
+        if dv is not None:
+            raise PvwError(15, "host=True takes a host mask")
+        out = np.zeros((T, D), dtype=np.int64)
+        L = _ffi.lib()
+        _check(L.pvw_shamir_handover_weights_host(int(plain_modulus), _ptr(idx), _ptr(v), D, _ptr(tg), T, _ptr(out), C.byref(count)), L)
+        return out, int(count.value)
+    if params is None:
+        raise PvwError(1, "the device form needs the parameters (a context); host=True needs none")
+    import torch
+    in_place = dv is not None
+    if v is not None:
+        dv = torch.from_numpy(v).cuda()
+    do = torch.zeros((T, D), dtype=torch.int64, device="cuda")
+    dc = torch.zeros(1, dtype=torch.int32, device="cuda")
+    if not in_place:
+        torch.cuda.synchronize()
+    params._call("pvw_shamir_handover_weights_device", int(plain_modulus), _ptr(idx), _dptr(dv), D, _ptr(tg), T, _dptr(do), _dptr(dc),
+                 _stream_ptr(stream) if in_place else None)
+    if in_place:
+        return do, dc
+    params.synchronize()
+    return do.cpu().numpy(), int(dc.item())
+
+
+def shamir_valid_mask(status=None, noise=None, *, status_bits: int = 0xFFFFFFFF, noise_bound: int = 0xFFFFFFFFFFFFFFFF,
+                      host: bool = False, params: Optional[PvwParameters] = None, stream=None):
+    """EXTENSION: the holder mask of a report.  status (uint32) and noise (uint64) are [rows][count] matrices (a
+    vector is one row: the col_err of a corrected reconstruction; the [party][dealer] report of decrypt_all_party_shares_checked
+    as it is); either may be None.  valid[c] = 1 iff no row has status & status_bits != 0 or noise > noise_bound in column c.
+    Returns (valid uint8 [count], number of ones).  host=True: pvw_shamir_valid_mask_host.  Device tensors (int32 status, int64
+    noise) are read in place on `stream` and (valid, count) stay on the device: what decrypt_all_party_handover takes."""
+    if status is None and noise is None:
+        raise PvwError(15, "status and noise are both None")
+    if any(hasattr(a, "data_ptr") for a in (status, noise)):
+        import torch
+        first = status if status is not None else noise
+        if params is None or host or any(a is not None and (not hasattr(a, "data_ptr") or not a.is_contiguous() or a.shape != first.shape)
+                                         for a in (status, noise)) or first.dim() not in (1, 2):
+            raise PvwError(15, "device reports need params, host=False and contiguous arrays of one shape")
+        rows, count = (1, first.shape[0]) if first.dim() == 1 else tuple(first.shape)
+        d_valid = torch.zeros(count, dtype=torch.uint8, device=first.device)
+        d_num = torch.zeros(1, dtype=torch.int32, device=first.device)
+        params._call("pvw_shamir_valid_mask_device", _dptr(status), _dptr(noise), int(status_bits), int(noise_bound), count, rows, count, 1,
+                     _dptr(d_valid), _dptr(d_num), _stream_ptr(stream))
+        return d_valid, d_num
+    st = None if status is None else np.atleast_2d(np.ascontiguousarray(np.asarray(status, dtype=np.uint32)))
+    nz = None if noise is None else np.atleast_2d(np.ascontiguousarray(np.asarray(noise).astype(np.uint64, copy=False)))
+    shape = (st if st is not None else nz).shape
+    if len(shape) != 2 or (st is not None and nz is not None and st.shape != nz.shape):
+        raise PvwError(15, "status and noise must be arrays of one shape")
+    rows, count = shape
+    out, num = np.zeros(count, dtype=np.uint8), C.c_uint32()
+    if host:
+        L = params._lib if params is not None else _ffi.lib()
+        _check(L.pvw_shamir_valid_mask_host(_ptr(st), _ptr(nz), int(status_bits), int(noise_bound), count, rows, count, 1, _ptr(out),
+                                            C.byref(num)), L)
+        return out, int(num.value)
+    if params is None:
+        raise PvwError(15, "the device form needs params (or host=True)")
+    import torch
+    d_st = torch.from_numpy(st.view(np.int32)).cuda() if st is not None else None
+    d_nz = torch.from_numpy(nz.view(np.int64)).cuda() if nz is not None else None
+    d_valid, d_num = torch.zeros(count, dtype=torch.uint8, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    params._call("pvw_shamir_valid_mask_device", _dptr(d_st), _dptr(d_nz), int(status_bits), int(noise_bound), count, rows, count, 1,
+                 _dptr(d_valid), _dptr(d_num), None)
+    params.synchronize()
+    return d_valid.cpu().numpy(), int(d_num.item())
+
+
+def decrypt_all_party_handover(cts: Sequence[PvwCiphertext], parties: Sequence["Party"], indices: Sequence[int], plain_modulus: int,
+                               valid=None, targets=None, wide: bool = False, *, bound: Optional[int] = None) -> CheckedDecryption:
+    """EXTENSION: the handover of a one-word sharing in one call.  cts [D] are the old holders' re-dealt ciphertexts
+    (holder d at party index indices[d]); targets as in shamir_handover_weights (None: the point 0; p - 1 - m, m < K, for a packed
+    old sharing).  `valid` as a host array goes through pvw_decrypt_all_handover (only valid holders are uploaded); as a device
+    tensor (uint8 [D]) it is used in place by pvw_decrypt_all_handover_device, read when the kernels run.  Returns the report
+    [P][T] of decrypt_all_party_combinations_many: values[j][m] = sum_d lambda_{d,m} f_d(j + 1) mod p, new party j's share at
+    target m; .count is the number of valid holders."""
+    cts = list(cts)
+    D = len(cts)
+    p, repr, _ = _sum_inputs(cts, None)
+    idx = _words(indices)
+    if len(idx) != D:
+        raise PvwError(15, f"indices: expected {D} holders, got {len(idx)}")
+    v, dv = _holder_mask(valid, D)
+    tg = None if targets is None else _words(targets)
+    T, NP = (1 if tg is None else len(tg)), len(parties)
+    lo = parties[0].index if NP else 0
+    for i, party in enumerate(parties):
+        if party.index != lo + i:
+            raise PvwError(1, f"Party indices must be consecutive: {party.index} follows {lo + i - 1}")
+    out, noise, status = np.zeros((NP, T), np.uint64), np.zeros((NP, T), np.uint64), np.zeros((NP, T), np.uint32)
+    on, m, ww, wd = _plain(p, plain_modulus, wide, out.shape)
+    count = C.c_uint32()
+    c1s = np.ascontiguousarray(np.stack([ct.c1 for ct in cts]), dtype=np.uint64)
+    c2s = np.ascontiguousarray(np.stack([ct.c2 for ct in cts]), dtype=np.uint64)
+    sk = np.ascontiguousarray(np.stack([_i64(party.secret_key.secret_coeffs) for party in parties])) if NP else np.zeros(1, np.int64)
+    try:
+        if dv is None:
+            p._call("pvw_decrypt_all_handover", lo, lo + NP, _ptr(sk), _ptr(c1s), _ptr(c2s), D, _ptr(v), _ptr(idx), _ptr(tg), T, repr,
+                    _ptr(out), _ptr(noise), _ptr(status), C.byref(count), m, ww, _ptr(wd))
+            nv = int(count.value)
+        else:
+            import torch
+            dev = dv.device
+            up = lambda a: torch.from_numpy(a.view(np.int64)).to(dev)
+            d_sk, d_c1, d_c2 = up(sk), up(c1s), up(c2s)
+            d_out, d_noise = torch.zeros((NP, T), dtype=torch.int64, device=dev), torch.zeros((NP, T), dtype=torch.int64, device=dev)
+            d_status, d_count = torch.zeros((NP, T), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+            d_wide = torch.zeros((NP, T, ww), dtype=torch.int64, device=dev) if ww else None
+            torch.cuda.synchronize(dev)
+            try:
+                p._call("pvw_decrypt_all_handover_device", lo, lo + NP, _dptr(d_sk), _dptr(d_c1), _dptr(d_c2), D, _dptr(dv), _ptr(idx),
+                        _ptr(tg), T, repr, _dptr(d_out), _dptr(d_noise), _dptr(d_status), _dptr(d_count), m, ww, _dptr(d_wide), None)
+                p.synchronize()
+            finally:
+                d_sk.zero_()
+            out, noise = d_out.cpu().numpy().view(np.uint64), d_noise.cpu().numpy().view(np.uint64)
+            status, nv = d_status.cpu().numpy().view(np.uint32), int(d_count.item())
+            wd = d_wide.cpu().numpy().view(np.uint64) if ww else None
+    finally:
+        sk.fill(0)                                                         # the stacked copy of the keys (secret_key.rs:20-30)
+    rep = CheckedDecryption(out, noise, status, _bound(p, bound), on, wd)
+    rep.count = nv
+    return rep
+
+
 def _dptr(x):
     """a device buffer: a torch tensor (its data_ptr()), a raw address as an int, or None"""
     if x is None:

@@ -161,6 +161,10 @@ struct Workspace {
   size_t handover_wide_bytes = 0;   // (shamir_handover_wide_words; public, grown by the call)
   u64* handover_io = nullptr;    // wide handover on device pointers: weight rows (public) | the digit report [P][R] (HandoverIo; secret)
   size_t handover_io_bytes = 0;
+  u64* handover = nullptr;       // one-word handover weights: points | column weights | a group's targets, scale, Cauchy entries, coin
+  size_t handover_bytes = 0;     // (shamir_handover_words; public, grown by the call)
+  u64* handover_rows = nullptr;  // one-word handover on device pointers: the weight rows [T][D] (public)
+  size_t handover_rows_bytes = 0;
   u64* correct = nullptr;    // corrected reconstruction: M | public matrices | syndromes | locators (CorrectLayout; grown by the call)
   size_t correct_bytes = 0;
   u64* correct_wide = nullptr;   // the same over a prime below 2^256 (CorrectLayout<WideField>)
@@ -662,6 +666,8 @@ static void ws_free(Workspace* w) {
   hipFree(w->handover_wide);
   if (w->handover_io) hipMemset(w->handover_io, 0, w->handover_io_bytes);   // the last report, if its wipe did not run
   hipFree(w->handover_io);
+  hipFree(w->handover);
+  hipFree(w->handover_rows);
   if (w->correct) hipMemset(w->correct, 0, w->correct_bytes);   // M of the last call, if its wipe did not run
   hipFree(w->correct);
   if (w->correct_wide) hipMemset(w->correct_wide, 0, w->correct_wide_bytes);
@@ -5471,6 +5477,139 @@ int32_t pvw_shamir_wide_handover_weights_device(pvw_ctx* c, const uint64_t* plai
   });
 }
 
+// ------------------------------------------------------------------------ one-word handover weights from a mask
+// Row j = the Lagrange weights AT (targets[j] + 1) mod p of the holders with valid[d] != 0, centred, 0 in a masked column.  The
+// device form reads the mask when its kernels run, so both forms hold ALL num_holders indices to the rules of
+// pvw_shamir_lagrange_weights: the order is NULL, no holders, the targets' count, the device's bounds (before an array of that
+// length is read), the indices (modulus first), a target not below p.
+static int32_t handover_checks(u64 p, const u64* indices, size_t D, const u64* targets, size_t T, const void* weights, bool device) {
+  if (!indices || !weights) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  if (D == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no holders");
+  if (T == 0) return fail(PVW_ERR_INVALID_PARAMETERS, "no target points");
+  if (!targets && T != 1) return fail(PVW_ERR_INVALID_PARAMETERS, "targets == NULL is the single point 0: num_targets must be 1");
+  if (device && D >= ((size_t)1 << 32)) return fail(PVW_ERR_INVALID_PARAMETERS, "num_holders must be below 2^32 on the device");
+  if (device && T >= ((size_t)1 << 31)) return fail(PVW_ERR_INVALID_PARAMETERS, "num_targets must be below 2^31 on the device");
+  PVW_TRY(shamir_index_checks(p, indices, D, true));
+  for (size_t j = 0; targets && j < T; ++j)
+    if (targets[j] >= p) return fail(PVW_ERR_INVALID_PARAMETERS, "target index out of range for plain_modulus");
+  return PVW_OK;
+}
+int32_t pvw_shamir_handover_weights_host(uint64_t plain_modulus, const uint64_t* indices, const uint8_t* valid, size_t num_holders,
+                                         const uint64_t* targets, size_t num_targets, int64_t* weights, uint32_t* count) {
+  PVW_TRY(handover_checks(plain_modulus, indices, num_holders, targets, num_targets, weights, false));
+  const Mod m = shamir_mod(plain_modulus);
+  std::vector<u64> vidx, z(num_targets, 0), W;
+  std::vector<size_t> col;
+  for (size_t d = 0; d < num_holders; ++d)
+    if (!valid || valid[d]) {
+      vidx.push_back(indices[d]);
+      col.push_back(d);
+    }
+  for (size_t j = 0; targets && j < num_targets; ++j) z[j] = targets[j] + 1 == m.q ? 0 : targets[j] + 1;
+  std::fill(weights, weights + num_targets * num_holders, (int64_t)0);
+  if (!vidx.empty()) {
+    shamir_weights_at_points(m, vidx.data(), vidx.size(), z, &W);
+    for (size_t j = 0; j < num_targets; ++j)
+      for (size_t i = 0; i < vidx.size(); ++i) weights[j * num_holders + col[i]] = centred(W[j * vidx.size() + i], m.q);
+  }
+  if (count) *count = (uint32_t)vidx.size();
+  return PVW_OK;
+}
+
+// targets per group: a target costs a column of C, xt, scale and coin, within the budget of evaluate_group
+static size_t handover_group(size_t D, size_t T) {
+  const size_t per = (D + 2) * 8 + 4;
+  size_t tg = group_budget() / per;
+  if (tg > 64) tg -= tg % 64;
+  if (tg == 0) tg = 1;
+  return tg < T ? tg : T;
+}
+// The block is sized by a bound that never shrinks when D or T grow, so that a call with at least as many holders and targets
+// sizes the block for every smaller one (the words of the group itself do shrink where Tg drops to the next multiple of 64).
+// A group of Tg targets takes g(Tg) = 2 Tg + D Tg + ceil(Tg / 2) words, and g(Tg) <= g(T).  Where the budget B holds the group,
+// Tg ((D + 2) 8 + 4) <= B gives g(Tg) <= B / 8 + 1; where it holds no target at all, Tg = 1 and g(1) = D + 3.
+static size_t handover_ws_bytes(size_t D, size_t T) {
+  const size_t whole = 2 * T + D * T + (T + 1) / 2, budget = group_budget() / 8 + 1;
+  const size_t cap = budget > D + 3 ? budget : D + 3;
+  return (2 * D + (whole < cap ? whole : cap)) * 8;
+}
+// the weight rows [T][D] into d_weights through the public block ws (handover_ws_bytes), and the number of valid holders into
+// *d_count (may be NULL); indices and targets (NULL: the point 0) are consumed here, d_valid is read when the kernels run
+static int32_t handover_weights_enqueue(pvw_ctx* c, u64 p, const u64* indices, const uint8_t* d_valid, size_t D, const u64* targets,
+                                        size_t T, u64* ws, i64* d_weights, u32* d_count, hipStream_t s) {
+  ProfScope ps(c, "shamir_handover_weights", s);
+  const Mod m = shamir_mod(p);
+  const size_t Tg = handover_group(D, T);
+  const u64 zero_point = p - 1;                                    // index p - 1 is the point 0
+  if (!targets) targets = &zero_point;
+  u64 *x = ws, *aux = x + D, *grp = aux + D;
+  PVW_HIP(launch_shamir_points(indices, D, x, s));
+  PVW_HIP(launch_shamir_masked_column_weights(x, d_valid, aux, d_count, D, m, s));
+  for (size_t j0 = 0; j0 < T; j0 += Tg) {
+    const size_t tg = T - j0 < Tg ? T - j0 : Tg;
+    PVW_HIP(launch_shamir_points(targets + j0, tg, grp, s));
+    PVW_HIP(launch_shamir_handover_weights(x, aux, d_valid, grp, D, tg, d_weights + j0 * D, m, s));
+  }
+  return PVW_OK;
+}
+static const char* const kHandoverNarrowWeightsUnsized =
+    "handover weights under stream capture: run a call with at least as many holders and target points on this stream outside "
+    "capture first (it sizes the workspace)";
+int32_t pvw_shamir_handover_weights_device(pvw_ctx* c, uint64_t plain_modulus, const uint64_t* indices, const uint8_t* d_valid,
+                                           size_t num_holders, const uint64_t* targets, size_t num_targets, int64_t* d_weights,
+                                           uint32_t* d_count, void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(handover_checks(plain_modulus, indices, num_holders, targets, num_targets, d_weights, true));
+  const size_t need = handover_ws_bytes(num_holders, num_targets);
+  auto sized = [&](hipStream_t s) { return grown_capture_check(c, s, &Workspace::handover_bytes, need, kHandoverNarrowWeightsUnsized); };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  return device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
+    PVW_TRY(ws_grow(&w->handover, &w->handover_bytes, need, s, false));   // public: nothing to clear
+    return handover_weights_enqueue(c, plain_modulus, indices, d_valid, num_holders, targets, num_targets, w->handover, (i64*)d_weights,
+                                    d_count, s);
+  });
+}
+
+// The holder mask from a report: valid_out[c] = 1 iff no row r has status & status_bits or noise > noise_bound at
+// r * row_stride + c * col_stride.  The argument rules of pvw_shamir_erasure_mask_* (erasure_mask_checks).
+int32_t pvw_shamir_valid_mask_host(uint32_t* status, const uint64_t* noise, uint32_t status_bits, uint64_t noise_bound, size_t count,
+                                   size_t rows, size_t row_stride, size_t col_stride, uint8_t* valid_out, uint32_t* num_valid) {
+  PVW_TRY(erasure_mask_checks(status, noise, count, rows, row_stride, col_stride, valid_out));
+  uint32_t nv = 0;
+  for (size_t c = 0; c < count; ++c) {
+    bool bad = false;
+    for (size_t r = 0; r < rows && !bad; ++r) {
+      const size_t off = r * row_stride + c * col_stride;
+      bad = (status && (status[off] & status_bits)) || (noise && noise[off] > noise_bound);
+    }
+    valid_out[c] = bad ? 0 : 1;
+    nv += !bad;
+  }
+  if (num_valid) *num_valid = nv;
+  return PVW_OK;
+}
+int32_t pvw_shamir_valid_mask_device(pvw_ctx* c, uint32_t* d_status, const uint64_t* d_noise, uint32_t status_bits, uint64_t noise_bound,
+                                     size_t count, size_t rows, size_t row_stride, size_t col_stride, uint8_t* d_valid_out,
+                                     uint32_t* d_num_valid, void* stream) {
+  if (!c) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(erasure_mask_checks(d_status, d_noise, count, rows, row_stride, col_stride, d_valid_out));
+  if (count >= ((size_t)1 << 31) || rows >= ((size_t)1 << 31))
+    return fail(PVW_ERR_INVALID_PARAMETERS, "count and rows must be below 2^31 on the device");
+  // no scratch of its own; under capture the stream's workspace must exist already (pvw_shamir_erasure_mask_device)
+  auto sized = [&](hipStream_t s) {
+    return grown_capture_check(c, s, &Workspace::handover_bytes, 0,
+                               "valid mask under stream capture: run a call on this stream outside capture first (it makes the stream's "
+                               "workspace)");
+  };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  return device_call(c, stream, sized, [&](Workspace*, hipStream_t s) -> int32_t {
+    ProfScope ps(c, "shamir_valid_mask", s);
+    PVW_HIP(launch_shamir_valid_mask(d_status, d_noise, status_bits, noise_bound, (u32)count, (u32)rows, row_stride, col_stride, d_valid_out,
+                                     d_num_valid, s));
+    return PVW_OK;
+  });
+}
+
 static int32_t from_digits_checks(const uint64_t* p, uint32_t digit_bits, uint32_t num_digits, const void* wide, const void* status,
                                   uint32_t ww, size_t count, const void* out, const void* status_out, WideMod* m) {
   if (!p || ((!wide || !status || !out || !status_out) && count)) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
@@ -7452,10 +7591,10 @@ static const char* const kHandoverUnsized =
     "wide handover under stream capture: run a call with the same party range, at least as many valid holders, target points and "
     "vectors on this stream outside capture first (it sizes the scratch)";
 // what pvw_decrypt_all_lincomb_many_plain_device asks of a capturing stream, asked before anything of the handover is enqueued
-static int32_t handover_many_capture_check(pvw_ctx* c, hipStream_t s, size_t NP, size_t R, size_t ww) {
+static int32_t handover_many_capture_check(pvw_ctx* c, hipStream_t s, size_t NP, size_t R, size_t ww, const char* msg = kHandoverUnsized) {
   if (R == 1) return sum_capture_check(c, s, sum_dpart_need(c), decrypt_all_sum_need(c, NP, ww));
   const ManyLayout m = decrypt_all_many_layout(c, NP, R, ww, 0);
-  PVW_TRY(grown_capture_check(c, s, &Workspace::scratch_bytes, m.sc.total, kHandoverUnsized));
+  PVW_TRY(grown_capture_check(c, s, &Workspace::scratch_bytes, m.sc.total, msg));
   return sum_capture_check(c, s, 0, 0);
 }
 int32_t pvw_decrypt_all_handover_wide_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
@@ -7544,6 +7683,83 @@ int32_t pvw_decrypt_all_handover_wide(pvw_ctx* c, uint32_t lo, uint32_t hi, cons
   vp = res.data();
   for (size_t i = 0; i < res.size(); ++i) vp[i] = 0;
   if (rc == PVW_OK && count) *count = (uint32_t)h.nv();
+  return rc;
+}
+
+// The one-word handover in one call: the weight rows by the kernels of pvw_shamir_handover_weights_device from a
+// mask read when they run, then the many-combinations call of 8.15 ITSELF with R = T rows and valid = NULL -- a masked holder's
+// weights are 0, so its ciphertext is never addressed -- and that call's report as it is.  The rows are public; keys and report
+// are the many-combinations call's to stage, mark and clear.
+// the order: NULL, the checks of the weights, the report's arguments, then what the many-combinations call refuses
+static int32_t handover_narrow_checks(pvw_ctx* c, u32 lo, u32 hi, const void* sk, const void* c1s, const void* c2s, size_t D,
+                                      const u64* indices, const u64* targets, size_t T, uint32_t in_repr, u64* out, u64* noise, u32* status,
+                                      u64 p, u32 wide_words, u64* wide, bool device, Report* rep) {
+  if (!c || !out) return fail(PVW_ERR_INVALID_PARAMETERS, "NULL argument");
+  PVW_TRY(handover_checks(p, indices, D, targets, T, out, device));
+  PVW_TRY(report_args(c, out, noise, status, p, wide_words, wide, rep));
+  PVW_TRY(decrypt_all_checks(c, lo, hi, sk, c1s, c2s, D, in_repr, out));
+  PVW_TRY(check_dealers(D, true));
+  return combos_check(T, device);
+}
+static const char* const kHandoverNarrowUnsized =
+    "handover under stream capture: run a call with the same party range and at least as many holders and target points on this "
+    "stream outside capture first (it sizes the workspace and the scratch)";
+int32_t pvw_decrypt_all_handover_device(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* d_sk, const uint64_t* d_c1s,
+                                        const uint64_t* d_c2s, size_t num_holders, const uint8_t* d_valid, const uint64_t* indices,
+                                        const uint64_t* targets, size_t num_targets, uint32_t in_repr, uint64_t* d_out, uint64_t* d_noise,
+                                        uint32_t* d_status, uint32_t* d_count, uint64_t plain_modulus, uint32_t wide_words,
+                                        uint64_t* d_wide, void* stream) {
+  Report rep;
+  PVW_TRY(handover_narrow_checks(c, lo, hi, d_sk, d_c1s, d_c2s, num_holders, indices, targets, num_targets, in_repr, d_out, d_noise, d_status,
+                                 plain_modulus, wide_words, d_wide, true, &rep));
+  const size_t NP = (size_t)hi - lo, D = num_holders, T = num_targets;
+  const size_t pub_need = handover_ws_bytes(D, T), rows_need = T * D * 8;
+  auto sized = [&](hipStream_t s) -> int32_t {
+    PVW_TRY(grown_capture_check(c, s, &Workspace::handover_bytes, pub_need, kHandoverNarrowUnsized));
+    PVW_TRY(grown_capture_check(c, s, &Workspace::handover_rows_bytes, rows_need, kHandoverNarrowUnsized));
+    return handover_many_capture_check(c, s, NP, T, rep.ww, kHandoverNarrowUnsized);
+  };
+  if (stream) PVW_TRY(sized((hipStream_t)stream));
+  i64* rows = nullptr;
+  PVW_TRY(device_call(c, stream, sized, [&](Workspace* w, hipStream_t s) -> int32_t {
+    PVW_TRY(ws_grow(&w->handover, &w->handover_bytes, pub_need, s, false));          // public: nothing to clear
+    PVW_TRY(ws_grow(&w->handover_rows, &w->handover_rows_bytes, rows_need, s, false));
+    rows = (i64*)w->handover_rows;
+    return handover_weights_enqueue(c, plain_modulus, indices, d_valid, D, targets, T, w->handover, rows, d_count, s);
+  }));
+  return pvw_decrypt_all_lincomb_many_plain_device(c, lo, hi, d_sk, d_c1s, d_c2s, D, nullptr, rows, T, in_repr, d_out, d_noise, d_status,
+                                                   nullptr, plain_modulus, wide_words, d_wide, stream);
+}
+// host buffers: the weights by the same kernels on a pooled workspace (the mask goes up with the call), then the many-combinations
+// call on host buffers with the caller's mask: its staging of the valid holders in pieces, its key hygiene, its refusals
+int32_t pvw_decrypt_all_handover(pvw_ctx* c, uint32_t lo, uint32_t hi, const int64_t* sk, const uint64_t* c1s, const uint64_t* c2s,
+                                 size_t num_holders, const uint8_t* valid, const uint64_t* indices, const uint64_t* targets,
+                                 size_t num_targets, uint32_t in_repr, uint64_t* out, uint64_t* noise, uint32_t* status, uint32_t* count,
+                                 uint64_t plain_modulus, uint32_t wide_words, uint64_t* wide) {
+  Report rep;
+  PVW_TRY(handover_narrow_checks(c, lo, hi, sk, c1s, c2s, num_holders, indices, targets, num_targets, in_repr, out, noise, status,
+                                 plain_modulus, wide_words, wide, false, &rep));
+  const size_t D = num_holders, T = num_targets;
+  size_t nv = 0;
+  for (size_t d = 0; d < D; ++d) nv += !valid || valid[d];
+  if (nv == 0) return no_valid_dealer(D, nullptr);
+  PVW_TRY(ensure_device(c));
+  std::vector<i64> wts(T * D);
+  {
+    Scratch sc;
+    const size_t r_pub = sc.add(handover_ws_bytes(D, T)), r_w = sc.add(T * D * 8), r_v = sc.add(D);
+    PVW_TRY(host_call(c, [&](Workspace* w) -> int32_t {
+      PVW_TRY(sc.take(w));
+      uint8_t* d_valid = valid ? sc.at<uint8_t>(r_v) : nullptr;
+      if (valid) PVW_HIP(hipMemcpyAsync(d_valid, valid, D, hipMemcpyHostToDevice, w->stream));
+      PVW_TRY(handover_weights_enqueue(c, plain_modulus, indices, d_valid, D, targets, T, sc.at(r_pub), sc.at<i64>(r_w), nullptr, w->stream));
+      PVW_HIP(hipMemcpyAsync(wts.data(), sc.at(r_w), T * D * 8, hipMemcpyDeviceToHost, w->stream));
+      return PVW_OK;
+    }));
+  }
+  const int32_t rc = pvw_decrypt_all_lincomb_many_plain(c, lo, hi, sk, c1s, c2s, D, valid, wts.data(), T, in_repr, out, noise, status, nullptr,
+                                                        plain_modulus, wide_words, wide);
+  if (rc == PVW_OK && count) *count = (uint32_t)nv;
   return rc;
 }
 

@@ -558,6 +558,22 @@ hipError_t launch_shamir_wide_from_digits(const u64* wide, const u32* status, si
 // x[i] = (p - (m0 + i)) R mod p for i < count: the secret points -m of a packed wide sharing, m0 + count <= 2^32
 hipError_t launch_shamir_packed_secret_points_wide(u32 m0, size_t count, u64* x, const WideMont& m, hipStream_t s);
 
+// ---- One-word handover weights from a device-side mask (pvw_shamir.hip): weights [T][D] of the holders with
+// valid[d] != 0 (NULL: all) at the targets, centred, 0 in a masked column; the mask is read when the kernels run.  Public
+// workspace words of D holders and a group of Tg targets:
+//   x [D] | aux [D] | xt [Tg] | scale [Tg] | C [D][Tg] | coin [Tg] (u32)
+inline size_t shamir_handover_words(size_t D, size_t Tg) { return 2 * D + 2 * Tg + D * Tg + (Tg + 1) / 2; }
+// aux[i] = u_i over the valid holders (0 for a masked i); *count_out (may be NULL) = the number of valid holders
+hipError_t launch_shamir_masked_column_weights(const u64* x, const unsigned char* valid, u64* aux, u32* count_out, size_t count, const Mod& m,
+                                               hipStream_t s);
+// ws: the group's words from xt on, xt filled by launch_shamir_points; weights: the group's rows [Tg][count]
+hipError_t launch_shamir_handover_weights(const u64* x, const u64* aux, const unsigned char* valid, u64* ws, size_t count, size_t Tg,
+                                          i64* weights, const Mod& m, hipStream_t s);
+// valid[c] = 1 iff no row r has status & status_bits or noise > noise_bound at r * row_stride + c * col_stride (one array may be
+// NULL); *num_valid (may be NULL) = the number of ones
+hipError_t launch_shamir_valid_mask(const u32* status, const u64* noise, u32 status_bits, u64 noise_bound, u32 count, u32 rows,
+                                    size_t row_stride, size_t col_stride, unsigned char* valid, u32* num_valid, hipStream_t s);
+
 // p[0 .. words) = 0, as a kernel launch on s
 hipError_t launch_wipe_words(u64* p, size_t words, hipStream_t s);
 

@@ -2820,4 +2820,145 @@ hipError_t launch_shamir_packed_secret_points_wide(u32 m0, size_t count, u64* x,
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------ one-word handover weights from a device mask
+// The Lagrange weights of the VALID holders at any points, with the mask read when the kernels run: the points of all D holders
+// are public and travel as kernel arguments, the mask bytes are device memory.  A masked holder enters every product as the
+// factor 1 and has u_i = 0, so its Cauchy entries and its weights are 0 without a branch.  At the END of the file, like the
+// kernels of 8.23 - 8.25: nothing before them moves in the code object.
+
+// the mask of the 64 holders from c0 on, wave-uniform (ct_sum_kernel's walk): bit b is holder c0 + b, NULL is everybody.  c0 is
+// walked in 64 bits, as there: count may be anything below 2^32, and c0 + 64 must not wrap
+__device__ __forceinline__ u64 shamir_valid_ballot(const unsigned char* valid, u64 c0, u32 lane, u32 count) {
+  return __builtin_amdgcn_ballot_w64(c0 + lane < count && (!valid || valid[c0 + lane] != 0));
+}
+
+// one wave per holder i, in the frame of shamir_prod_kernel: u_i = (prod_{k valid, k != i}(x_i - x_k))^-1, 0 for a masked i.
+// A chunk with no valid holder is skipped, and a lane loads its factor's point only where the ballot has its bit.
+__global__ __launch_bounds__(256) void shamir_masked_prod_kernel(const u64* x, const unsigned char* valid, u64* aux, u32 count, Mod m) {
+  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const u32 i = blockIdx.x * SH_WAVES + wave;
+  if (i >= count) return;                                          // wave-uniform
+  const u64 own = shamir_valid_ballot(valid, i & ~63u, lane, count);
+  if (!((own >> (i & 63)) & 1)) {
+    if (lane == 0) aux[i] = 0;
+    return;
+  }
+  const u64 xi = x[i];
+  u64 prod = 1;
+  for (u64 c0 = 0; c0 < count; c0 += 64) {
+    const u64 bal = shamir_valid_ballot(valid, c0, lane, count);
+    if (!bal) continue;
+    const u64 k = c0 + lane;
+    if (((bal >> lane) & 1) && k != i) prod = mulmod(prod, submod(xi, x[k], m.q), m);
+  }
+  prod = wave_mulmod(prod, m);
+  if (lane == 0) aux[i] = invmod_dev(prod, m);
+}
+
+// shamir_target_scale_kernel over the valid holders only: a masked column is no factor and can never be `coin`
+__global__ __launch_bounds__(256) void shamir_masked_target_scale_kernel(const u64* x, const unsigned char* valid, const u64* xt, u64* scale,
+                                                                         u32* coin, u32 count, u32 Tg, Mod m) {
+  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const u32 j = blockIdx.x * SH_WAVES + wave;
+  if (j >= Tg) return;                                             // wave-uniform
+  const u64 xs = xt[j];
+  u64 prod = 1;
+  u32 hit = PVW_SHAMIR_NO_COLUMN;
+  for (u64 c0 = 0; c0 < count; c0 += 64) {
+    const u64 bal = shamir_valid_ballot(valid, c0, lane, count);
+    if (!bal) continue;
+    if ((bal >> lane) & 1) {
+      const u64 d = submod(xs, x[c0 + lane], m.q);
+      if (d == 0) hit = (u32)(c0 + lane);
+      else prod = mulmod(prod, d, m);
+    }
+  }
+  prod = wave_mulmod(prod, m);
+#pragma unroll
+  for (int off = 32; off; off >>= 1) {
+    const u32 o = (u32)__shfl_xor((int)hit, off);
+    hit = o < hit ? o : hit;
+  }
+  if (lane == 0) {
+    scale[j] = prod;
+    coin[j] = hit;
+  }
+}
+
+// One thread per (holder i, target j), the holder fastest: the lanes of a wave store along a weight row.  lambda = scale_j
+// C[i][j]; where the target is a valid holder's point the row is that holder's unit vector, said explicitly: scale_j C[i][j] is
+// not 0 at the other columns there.  Centred in (-p/2, p/2].  Every word of the group's rows is stored.
+__global__ __launch_bounds__(256) void shamir_handover_weights_kernel(const u64* scale, const u64* C, const u32* coin, i64* weights,
+                                                                      u32 count, u32 Tg, Mod m) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)count * Tg) return;
+  const u32 i = (u32)(e % count), j = (u32)(e / count);
+  const u32 c = coin[j];
+  const u64 lam = c != PVW_SHAMIR_NO_COLUMN ? (c == i ? 1 : 0) : mulmod(scale[j], C[(size_t)i * Tg + j], m);
+  weights[e] = lam > m.q / 2 ? -(i64)(m.q - lam) : (i64)lam;
+}
+
+// *num = the number of bytes of valid[0 .. count) that are not 0 (NULL: count), one wave
+__global__ __launch_bounds__(64) void shamir_valid_count_kernel(const unsigned char* valid, u32 count, u32* num) {
+  u32 n = 0;
+  for (u64 c0 = 0; c0 < count; c0 += 64) n += (u32)__builtin_popcountll(shamir_valid_ballot(valid, c0, threadIdx.x, count));
+  if (threadIdx.x == 0) *num = n;
+}
+
+// valid[c] = 1 iff no row r has status & status_bits or noise > noise_bound at r * row_stride + c * col_stride: a lane per
+// column walks the rows (either array may be NULL)
+__global__ __launch_bounds__(256) void shamir_valid_mask_kernel(const u32* status, const u64* noise, u32 status_bits, u64 noise_bound,
+                                                                u32 count, u32 rows, size_t row_stride, size_t col_stride,
+                                                                unsigned char* valid) {
+  const u32 c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= count) return;
+  bool bad = false;
+  for (u32 r = 0; r < rows; ++r) {
+    const size_t off = (size_t)r * row_stride + (size_t)c * col_stride;
+    if (status) bad = bad || (status[off] & status_bits) != 0;
+    if (noise) bad = bad || noise[off] > noise_bound;
+  }
+  valid[c] = bad ? 0 : 1;
+}
+
+hipError_t launch_shamir_masked_column_weights(const u64* x, const unsigned char* valid, u64* aux, u32* count_out, size_t count, const Mod& m,
+                                               hipStream_t s) {
+  shamir_masked_prod_kernel<<<dim3((unsigned)((count + SH_WAVES - 1) / SH_WAVES)), dim3(256), 0, s>>>(x, valid, aux, (u32)count, m);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !count_out) return e;
+  shamir_valid_count_kernel<<<dim3(1), dim3(64), 0, s>>>(valid, (u32)count, count_out);
+  return hipGetLastError();
+}
+// ws of the group: xt [Tg] (filled by launch_shamir_points) | scale [Tg] | C [count][Tg] | coin [Tg] (u32); the Cauchy entries by
+// shamir_cauchy_kernel as it is, over ALL columns (aux is 0 in a masked one)
+hipError_t launch_shamir_handover_weights(const u64* x, const u64* aux, const unsigned char* valid, u64* ws, size_t count, size_t Tg,
+                                          i64* weights, const Mod& m, hipStream_t s) {
+  const u32 n = (u32)count, tg = (u32)Tg;
+  const u64* xt = ws;
+  u64 *scale = ws + Tg, *C = scale + Tg;
+  u32* coin = (u32*)(C + count * Tg);
+  shamir_masked_target_scale_kernel<<<dim3((tg + SH_WAVES - 1) / SH_WAVES), dim3(256), 0, s>>>(x, valid, xt, scale, coin, n, tg, m);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const u32 bx = (tg + 255) / 256;
+  for (u32 i0 = 0; i0 < n; i0 += 65535 * SH_CB) {                  // what the grid's y dimension holds
+    const u32 cols = n - i0 < 65535 * SH_CB ? n - i0 : 65535 * SH_CB;
+    shamir_cauchy_kernel<<<dim3(bx, (cols + SH_CB - 1) / SH_CB), dim3(256), 0, s>>>(x, aux, xt, C, i0, n, tg, m);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  const size_t threads = count * Tg;
+  shamir_handover_weights_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>(scale, C, coin, weights, n, tg, m);
+  return hipGetLastError();
+}
+hipError_t launch_shamir_valid_mask(const u32* status, const u64* noise, u32 status_bits, u64 noise_bound, u32 count, u32 rows,
+                                    size_t row_stride, size_t col_stride, unsigned char* valid, u32* num_valid, hipStream_t s) {
+  shamir_valid_mask_kernel<<<dim3((count + 255) / 256), dim3(256), 0, s>>>(status, noise, status_bits, noise_bound, count, rows, row_stride,
+                                                                          col_stride, valid);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !num_valid) return e;
+  shamir_valid_count_kernel<<<dim3(1), dim3(64), 0, s>>>(valid, count, num_valid);
+  return hipGetLastError();
+}
+
 }  // namespace pvw

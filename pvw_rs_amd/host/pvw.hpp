@@ -1579,4 +1579,74 @@ inline WideHandoverShares decrypt_all_party_handover_wide(const std::vector<PvwC
   return r;
 }
 
+// ---- The one-word handover from a mask.  The host forms; the device forms take device pointers (the mask among
+// them) and are reached through the C ABI.
+struct HandoverWeights {
+  std::vector<int64_t> weights;     // [T][D], row-major; a masked holder's column is 0
+  uint32_t count = 0;               // the valid holders
+};
+// row j = the Lagrange weights AT (targets[j] + 1) mod p over the valid holders (pvw_shamir_handover_weights_host); targets empty =
+// the single point 0
+inline HandoverWeights shamir_handover_weights(const std::vector<uint64_t>& indices, uint64_t plain_modulus, const std::vector<bool>& valid = {},
+                                               const std::vector<uint64_t>& targets = {}) {
+  if (!valid.empty() && valid.size() != indices.size()) throw PvwError(15, "valid must hold one flag per holder");
+  const std::vector<uint8_t> v(valid.begin(), valid.end());
+  const size_t T = targets.empty() ? 1 : targets.size();
+  HandoverWeights r{std::vector<int64_t>(T * indices.size()), 0};
+  check(pvw_shamir_handover_weights_host(plain_modulus, indices.data(), v.empty() ? nullptr : v.data(), indices.size(),
+                                         targets.empty() ? nullptr : targets.data(), T, r.weights.data(), &r.count));
+  return r;
+}
+struct ValidMask {
+  std::vector<uint8_t> valid;       // [count]
+  uint32_t num_valid = 0;
+};
+// valid[c] = 1 iff no row of the [rows][count] report has status & status_bits or noise > noise_bound in column c
+// (pvw_shamir_valid_mask_host); either array may be empty, not both
+inline ValidMask shamir_valid_mask(const std::vector<uint32_t>& status, const std::vector<uint64_t>& noise, size_t count,
+                                   uint32_t status_bits = 0xFFFFFFFFu, uint64_t noise_bound = ~(uint64_t)0) {
+  const size_t have = status.empty() ? noise.size() : status.size();
+  if (count == 0 || have % count || (!status.empty() && !noise.empty() && status.size() != noise.size()))
+    throw PvwError(15, "status and noise must be [rows][count] arrays of one shape");
+  std::vector<uint32_t> st(status);
+  ValidMask r{std::vector<uint8_t>(count), 0};
+  check(pvw_shamir_valid_mask_host(st.empty() ? nullptr : st.data(), noise.empty() ? nullptr : noise.data(), status_bits, noise_bound, count,
+                                   have / count, count, 1, r.valid.data(), &r.num_valid));
+  return r;
+}
+// every new party's new share in one call (pvw_decrypt_all_handover): cts holds the old holders' re-dealt ciphertexts, holder d at
+// party index indices[d]; arrays [parties][T]; .count of the result is the number of valid holders
+struct HandoverShares : CheckedShares {
+  uint32_t count = 0;
+};
+inline HandoverShares decrypt_all_party_handover(const std::vector<PvwCiphertext>& cts, const std::vector<Party>& parties,
+                                                 const std::vector<uint64_t>& indices, uint64_t plain_modulus,
+                                                 const std::vector<bool>& valid = {}, const std::vector<uint64_t>& targets = {},
+                                                 uint64_t bound = 0, uint32_t wide_words = 0) {
+  const SumInputs in = sum_inputs(cts, {});
+  const auto& p = cts[0].params;
+  if (cts.size() != indices.size()) throw PvwError(15, "one ciphertext per holder");
+  if (!valid.empty() && valid.size() != indices.size()) throw PvwError(15, "valid must hold one flag per holder");
+  const std::vector<uint8_t> v(valid.begin(), valid.end());
+  const size_t NP = parties.size(), T = targets.empty() ? 1 : targets.size(), kl = (size_t)p->k * p->l;
+  HandoverShares r;
+  r.values.assign(NP * T, 0), r.noise.assign(NP * T, 0), r.lossy.assign(NP * T, false), r.valid.assign(NP * T, false);
+  if (NP == 0) return r;
+  std::vector<int64_t> sk(NP * kl);
+  for (size_t i = 0; i < NP; ++i) {
+    if (parties[i].index >= p->n || parties[i].index != parties[0].index + i) throw PvwError(1, "Party indices must be consecutive and below n");
+    std::copy(parties[i].secret_key.secret_coeffs.begin(), parties[i].secret_key.secret_coeffs.end(), sk.begin() + i * kl);
+  }
+  std::vector<uint32_t> status(NP * T);
+  if (wide_words) r.wide.assign(NP * T * wide_words, 0);
+  const int32_t rc = pvw_decrypt_all_handover(p->ctx, parties[0].index, parties[0].index + (uint32_t)NP, sk.data(), in.c1s.data(), in.c2s.data(),
+                                              indices.size(), v.empty() ? nullptr : v.data(), indices.data(),
+                                              targets.empty() ? nullptr : targets.data(), T, cts[0].repr, r.values.data(), r.noise.data(),
+                                              status.data(), &r.count, plain_modulus, wide_words, wide_words ? r.wide.data() : nullptr);
+  std::fill(sk.begin(), sk.end(), 0);                                   // the copied keys do not outlive the call
+  check(rc);
+  checked_report(r, status, bound ? bound : ~(uint64_t)0, true);
+  return r;
+}
+
 }  // namespace pvw_host

@@ -196,6 +196,13 @@ extern "C" {
     pub fn pvw_decrypt_all_handover_wide(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, sk: *const i64, c1s: *const u64, c2s: *const u64, num_dealers: usize, plain_modulus: *const u64, limb_bits: u32, digit_bits: u32, indices: *const u64, valid: *const u8, points: *const u64, num_points: usize, in_repr: u32, out: *mut u64, status: *mut u32, count: *mut u32) -> i32;
     pub fn pvw_decrypt_all_handover_wide_device(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, d_sk: *const i64, d_c1s: *const u64, d_c2s: *const u64, num_dealers: usize, plain_modulus: *const u64, limb_bits: u32, digit_bits: u32, indices: *const u64, valid: *const u8, points: *const u64, num_points: usize, in_repr: u32, d_out: *mut u64, d_status: *mut u32, d_count: *mut u32, stream: *mut c_void) -> i32;
     pub fn pvw_ctx_wide_handover_fits(ctx: *const PvwCtx, plain_modulus: *const u64, num_valid: usize, limb_bits: u32, digit_bits: u32, fits: *mut u32) -> i32;
+    // ---- the one-word handover from a mask that may be made on the device ----
+    pub fn pvw_shamir_handover_weights_host(plain_modulus: u64, indices: *const u64, valid: *const u8, num_holders: usize, targets: *const u64, num_targets: usize, weights: *mut i64, count: *mut u32) -> i32;
+    pub fn pvw_shamir_handover_weights_device(ctx: *mut PvwCtx, plain_modulus: u64, indices: *const u64, d_valid: *const u8, num_holders: usize, targets: *const u64, num_targets: usize, d_weights: *mut i64, d_count: *mut u32, stream: *mut c_void) -> i32;
+    pub fn pvw_shamir_valid_mask_host(status: *mut u32, noise: *const u64, status_bits: u32, noise_bound: u64, count: usize, rows: usize, row_stride: usize, col_stride: usize, valid_out: *mut u8, num_valid: *mut u32) -> i32;
+    pub fn pvw_shamir_valid_mask_device(ctx: *mut PvwCtx, d_status: *mut u32, d_noise: *const u64, status_bits: u32, noise_bound: u64, count: usize, rows: usize, row_stride: usize, col_stride: usize, d_valid_out: *mut u8, d_num_valid: *mut u32, stream: *mut c_void) -> i32;
+    pub fn pvw_decrypt_all_handover(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, sk: *const i64, c1s: *const u64, c2s: *const u64, num_holders: usize, valid: *const u8, indices: *const u64, targets: *const u64, num_targets: usize, in_repr: u32, out_u64: *mut u64, noise: *mut u64, status: *mut u32, count: *mut u32, plain_modulus: u64, wide_words: u32, wide: *mut u64) -> i32;
+    pub fn pvw_decrypt_all_handover_device(ctx: *mut PvwCtx, party_lo: u32, party_hi: u32, d_sk: *const i64, d_c1s: *const u64, d_c2s: *const u64, num_holders: usize, d_valid: *const u8, indices: *const u64, targets: *const u64, num_targets: usize, in_repr: u32, d_out: *mut u64, d_noise: *mut u64, d_status: *mut u32, d_count: *mut u32, plain_modulus: u64, wide_words: u32, d_wide: *mut u64, stream: *mut c_void) -> i32;
     // ---- the receiving end over a prime below 2^256: device fold of limbs, checked reconstruction ----
     pub fn pvw_shamir_wide_from_limbs_device(ctx: *mut PvwCtx, plain_modulus: *const u64, d_limbs: *const u64, count: usize, limb_stride: usize, elem_stride: usize, limb_bits: u32, num_limbs: u32, d_out: *mut u64, stream: *mut c_void) -> i32;
     pub fn pvw_shamir_reconstruct_wide_checked_host(plain_modulus: *const u64, degree: u32, indices: *const u64, count: usize, shares: *const u64, num_secrets: usize, secret_stride: usize, point_stride: usize, out: *mut u64, bad: *mut u32, col_bad: *mut u32) -> i32;

@@ -1404,3 +1404,59 @@ pub fn decrypt_all_party_handover_wide(ciphertexts: &[PvwCiphertext], secret_key
     check(rc)?;
     Ok((out, status, count))
 }
+
+/// EXTENSION: the int64 weight rows `[T][D]` of a one-word handover and the number of valid holders: row j = the
+/// Lagrange weights AT the point (targets[j] + 1) mod p over the holders with `valid[d]`, centred; a masked holder's column is 0;
+/// `targets` empty = the single point 0 (`pvw_shamir_handover_weights_host`; the device form reads its mask from device memory
+/// and is reached through the C ABI).
+pub fn shamir_handover_weights(indices: &[u64], plain_modulus: u64, valid: Option<&[bool]>, targets: &[u64]) -> Result<(Vec<i64>, u32)> {
+    let v = handover_valid(valid, indices.len())?;
+    let t = targets.len().max(1);
+    let (mut out, mut count) = (vec![0i64; t * indices.len()], 0u32);
+    let tg = if targets.is_empty() { std::ptr::null() } else { targets.as_ptr() };
+    check(unsafe {
+        sys::pvw_shamir_handover_weights_host(plain_modulus, indices.as_ptr(), valid_ptr(&v), indices.len(), tg, t, out.as_mut_ptr(), &mut count)
+    })?;
+    Ok((out, count))
+}
+
+/// EXTENSION: the holder mask of a `[rows][count]` report and the number of ones: valid[c] = 1 iff no row has
+/// `status & status_bits != 0` or `noise > noise_bound` in column c; either slice may be empty, not both
+/// (`pvw_shamir_valid_mask_host`).
+pub fn shamir_valid_mask(status: &[u32], noise: &[u64], count: usize, status_bits: u32, noise_bound: u64) -> Result<(Vec<u8>, u32)> {
+    let have = if status.is_empty() { noise.len() } else { status.len() };
+    if count == 0 || have % count != 0 || (!status.is_empty() && !noise.is_empty() && status.len() != noise.len()) {
+        return Err(PvwError::InvalidParameters("status and noise must be [rows][count] arrays of one shape".into()));
+    }
+    let mut st = status.to_vec();
+    let (mut out, mut num) = (vec![0u8; count], 0u32);
+    let sp = if st.is_empty() { std::ptr::null_mut() } else { st.as_mut_ptr() };
+    let np = if noise.is_empty() { std::ptr::null() } else { noise.as_ptr() };
+    check(unsafe { sys::pvw_shamir_valid_mask_host(sp, np, status_bits, noise_bound, count, have / count, count, 1, out.as_mut_ptr(), &mut num) })?;
+    Ok((out, num))
+}
+
+/// EXTENSION: every new party's new share in one call (`pvw_decrypt_all_handover`).  `ciphertexts` are the old
+/// holders' re-dealt ciphertexts, holder d at party index `indices[d]`; `secret_keys` those of the consecutive parties from
+/// `party_lo`.  (values `[parties][T]` mod p, noise, status, valid holders)
+pub fn decrypt_all_party_handover(ciphertexts: &[PvwCiphertext], secret_keys: &[SecretKey], party_lo: usize, indices: &[u64],
+                                  plain_modulus: u64, valid: Option<&[bool]>, targets: &[u64]) -> Result<(Vec<u64>, Vec<u64>, Vec<u32>, u32)> {
+    let (c1s, c2s, _) = sum_inputs(ciphertexts, None)?;
+    let v = handover_valid(valid, indices.len())?;
+    if ciphertexts.len() != indices.len() {
+        return Err(PvwError::InvalidParameters("one ciphertext per holder".into()));
+    }
+    let params = &ciphertexts[0].params;
+    let (np, t) = (secret_keys.len(), targets.len().max(1));
+    let mut sk: Vec<i64> = secret_keys.iter().flat_map(flat_secret).collect();
+    let (mut out, mut noise, mut status, mut count) = (vec![0u64; np * t], vec![0u64; np * t], vec![0u32; np * t], 0u32);
+    let tg = if targets.is_empty() { std::ptr::null() } else { targets.as_ptr() };
+    let rc = unsafe {
+        sys::pvw_decrypt_all_handover(params.hip.raw(), party_lo as u32, (party_lo + np) as u32, sk.as_ptr(), c1s.as_ptr(), c2s.as_ptr(),
+                                      indices.len(), valid_ptr(&v), indices.as_ptr(), tg, t, sys::PVW_REPR_POWER, out.as_mut_ptr(),
+                                      noise.as_mut_ptr(), status.as_mut_ptr(), &mut count, plain_modulus, 0, std::ptr::null_mut())
+    };
+    sk.zeroize();
+    check(rc)?;
+    Ok((out, noise, status, count))
+}
